@@ -18,8 +18,11 @@ worker threads at half a millisecond a frame. What bounds `value` is the PCIe li
 engine the library measured as the device's fastest (j40_amd/csrc/device/hostcopy.hip); DESIGN.md section 5 has the breakdown.
 
 Also on the line: `roofline` (the stage of a batch furthest below the HBM roofline -- the LfGroup launch, k_lf_rows + k_lf_predict -- with the four stages'
-own durations inside the timed region and alone, device-recorded); `latency_mode` (one frame alone); BASELINE.json's other configurations (`configs`); `cpu_baseline` = the
-unmodified reference on one host core, same stream; `parity_vs_reference` for a frame decoded inside the timed region.
+own durations inside the timed region, device-recorded). A plain run does no more than that: it sets up, warms up, times the --steps steps and prints
+the line (--dump-outputs DIR: and writes what the last step computed). `--full` adds what takes runs of its own: the stages alone, `device_output`,
+`device_resident`, `latency_mode` (one frame alone), `restoration`, BASELINE.json's other configurations (`configs`), `cpu_baseline` = the unmodified
+reference on one host core, same stream, `parity_vs_reference` for a frame decoded inside the timed region, the link probe before the warm-up, and with
+several ranks the `sharded` record.
 
 N > 1 (torch.distributed.run, one rank per GPU): frames are independent, every rank runs its own pipeline on its own frames with
 its share of the host CPUs (weak scaling, no data-path collective); `value` is the whole-job aggregate. `--shard-groups` is the
@@ -200,6 +203,43 @@ def synth_many(specs, workers):
         return list(ex.map(lambda s: synth(s[0], s[1], s[2], s[3], **s[4]), specs))
 
 
+def stream_specs(args):
+    """the `--distinct` streams a batch of the timed path cycles through"""
+    stream_opts = {"forward": 1} if args.stream == "forward" else ({"maxlog": args.maxlog} if args.maxlog else {})
+    return [("vardct", args.width, args.height, args.seed + 1000 * i, stream_opts) for i in range(max(1, min(args.distinct, args.batch)))]
+
+
+def prepare_inputs():
+    """generates the default run's streams into build/streams (called by __graft_entry__.build()): 64 8K encodes are about 20 s of
+    16 CPUs, which a run of the benchmark would otherwise spend before its first step"""
+    synth_many(stream_specs(parser().parse_args([])), cpu_quota())
+
+
+DUMP_SAMPLE_BYTES = 48 << 20
+
+
+def dump_outputs(out_dir, frames):
+    """--dump-outputs: what the timed path handed back in its last step, RGBA u8x4 frames (H, W, 4), as .npy files that a run of another
+    build with the same arguments can be compared with value for value. A frame is 133 MB at 8K, so each is kept as its per-channel sums
+    over the whole frame (`rgba_channel_sums`, float64, exact) and the RGBA of a fixed, seeded sample of its pixels (`rgba_sample`, float32;
+    positions in `sample_yx`), under 64 MB in all"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    h, w = frames[0].shape[:2]
+    n = min(32768, h * w, DUMP_SAMPLE_BYTES // (16 * len(frames)))
+    idx = np.sort(np.random.default_rng(20240607).choice(h * w, n, replace=False))
+    sample = np.empty((len(frames), n, 4), np.float32)
+    sums = np.empty((len(frames), 4), np.float64)
+    for k, f in enumerate(frames):
+        a = np.ascontiguousarray(f)
+        sample[k] = a.reshape(h * w, 4)[idx]
+        # (column sums first: a row of 8K samples fits u32 accumulators many times over, and the pass runs at memory speed)
+        sums[k] = a.reshape(h, w * 4).sum(axis=0, dtype=np.uint32).reshape(w, 4).sum(axis=0, dtype=np.uint64)
+    np.save(os.path.join(out_dir, "rgba_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "rgba_channel_sums.npy"), sums)
+    np.save(os.path.join(out_dir, "sample_yx.npy"), np.stack([idx // w, idx % w], axis=1).astype(np.float64))
+
+
 def run_pipeline_steps(pipe, bufs, sizes, outs, stride, device_output, steps, torch, dev, dist):
     """`steps` timed steps: every frame of the batch submitted, then drained; returns (elapsed seconds, tickets of the last step)"""
     if dist is not None:
@@ -228,7 +268,7 @@ def run_pipeline_steps(pipe, bufs, sizes, outs, stride, device_output, steps, to
     return elapsed, tickets
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=12)
@@ -262,7 +302,17 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--skip-sections", action="store_true", help="only the timed pipeline (no device-resident / latency / other-config sections)")
     ap.add_argument("--skip-modular", action="store_true", help="leave BASELINE config 4 (16384 x 16384 Modular) out of `configs`")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the link probe, `device_output`, `device_resident`, `sharded`, the CPU baseline and "
+                         "parity with the reference, the stages alone, one frame alone, restoration, BASELINE's other configs (without it: set up, warm up, "
+                         "time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, under 64 MB)")
+    return ap
+
+
+def main():
+    args = parser().parse_args()
 
     import torch
     import numpy as np
@@ -310,11 +360,10 @@ def main():
     # (several ranks share the quota: quota / world each, at least one -- 8 ranks on a 16-CPU quota get two)
     threads = args.host_threads or (max(2, min(4, quota)) if world == 1 else max(1, min(4, quota // world)))
     threads_host_lf = args.host_threads or (max(2, quota) if world == 1 else max(1, quota // world))   # (pipelines whose worker threads decode the LfGroup streams themselves)
-    D = max(1, min(args.distinct, B))
     # every rank decodes its own batch of the same D streams: rank 0 generates them with all the CPUs the container has (an 8K
-    # encode takes ~10 s of one core), the other ranks wait and read them from build/streams
-    stream_opts = {"forward": 1} if args.stream == "forward" else ({"maxlog": args.maxlog} if args.maxlog else {})
-    specs = [("vardct", W, H, args.seed + 1000 * i, stream_opts) for i in range(D)]
+    # encode takes ~10 s of one core; build() made the default run's already), the other ranks wait and read them from build/streams
+    specs = stream_specs(args)
+    D = len(specs)
     if rank == 0:
         synth_many(specs, max(1, quota))
     if dist is not None:
@@ -327,27 +376,28 @@ def main():
     # the pixels land in pinned host memory, used round-robin: frame i and frame i + D are the same stream, hence the same pixels
     # (letting the pixel kernels store straight into pinned memory instead was measured: 5.1 Gpx/s against 7.5 for the copy)
     nh = args.host_buffers or min(D, B, 64 if world == 1 else 24)
-    host_outs = [torch.empty((H, W, 4), dtype=torch.uint8).pin_memory() for _ in range(nh)]
+    host_outs = [torch.empty((H, W, 4), dtype=torch.uint8, pin_memory=True) for _ in range(nh)]
     step_outs = [host_outs[i % nh] for i in range(B)]
-    # the link as this process finds it, before anything else runs: one device image copied into every landing buffer in turn (the
-    # copy the pipeline issues per frame: hipMemcpyAsync of 133 MB, device -> pinned host), each timed by itself on an idle device
+    # (--full) the link as this process finds it, before anything else runs: one device image copied into every landing buffer in turn
+    # (the copy the pipeline issues per frame: hipMemcpyAsync of 133 MB, device -> pinned host), each timed by itself on an idle device
     link_probe = None
-    try:
-        src = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
-        rates = []
-        for rep in range(2):
-            for hbuf in host_outs:
-                torch.cuda.synchronize(dev); t0 = time.perf_counter()
-                hbuf.copy_(src, non_blocking=True)
-                torch.cuda.synchronize(dev)
-                if rep:
-                    rates.append(hbuf.numel() / (time.perf_counter() - t0) / 1e9)
-        rates.sort()
-        link_probe = {"d2h_gb_per_s_per_landing_buffer": {"min": round(rates[0], 2), "median": round(rates[len(rates) // 2], 2), "max": round(rates[-1], 2), "buffers": len(rates)},
-                      "how": "before the warm-up, idle device: one 133 MB device image copied into each pinned landing buffer by itself (second pass timed)"}
-        del src
-    except RuntimeError as e:
-        link_probe = {"error": str(e)[:200]}
+    if args.full:
+        try:
+            src = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
+            rates = []
+            for rep in range(2):
+                for hbuf in host_outs:
+                    torch.cuda.synchronize(dev); t0 = time.perf_counter()
+                    hbuf.copy_(src, non_blocking=True)
+                    torch.cuda.synchronize(dev)
+                    if rep:
+                        rates.append(hbuf.numel() / (time.perf_counter() - t0) / 1e9)
+            rates.sort()
+            link_probe = {"d2h_gb_per_s_per_landing_buffer": {"min": round(rates[0], 2), "median": round(rates[len(rates) // 2], 2), "max": round(rates[-1], 2), "buffers": len(rates)},
+                          "how": "before the warm-up, idle device: one 133 MB device image copied into each pinned landing buffer by itself (second pass timed)"}
+            del src
+        except RuntimeError as e:
+            link_probe = {"error": str(e)[:200]}
 
     # the W untimed steps, queued back to back like the timed ones: the pipeline reaches the depth it has in the timed region (frames
     # parsed ahead, three batches' working sets, the device memory cache grown to hold them) before the clock starts -- W steps drained
@@ -362,11 +412,14 @@ def main():
     st = pipe.stats()
     for t in tickets:
         assert pipe.result(t) == "", "decode error: " + pipe.result(t)
-    first_pixels = host_outs[0].clone()
-    # ---- the same path with the pixels left in HBM (what rounds 2 and 3 reported as `value`): the device's own pace, its own pipeline,
-    # the LfGroup streams on the GPU
+    if args.dump_outputs and rank == 0:
+        # every landing buffer holds the pixels of the last frame of the last step that was copied into it
+        dump_outputs(args.dump_outputs, [o.numpy() for o in host_outs])
+    first_pixels = host_outs[0].clone() if args.full else None
+    # ---- (--full) the same path with the pixels left in HBM (what rounds 2 and 3 reported as `value`): the device's own pace, its own
+    # pipeline, the LfGroup streams on the GPU
     device_output = None
-    if not args.skip_sections or world > 1:
+    if args.full and (not args.skip_sections or world > 1):
         pipe.close()
         torch.cuda.empty_cache()
         Bd = max(1, args.device_output_batch)
@@ -429,7 +482,7 @@ def main():
         del outs, douts
         torch.cuda.empty_cache()
     resident_multi = None
-    if world > 1 and not args.skip_sections:
+    if args.full and world > 1 and not args.skip_sections:
         # every rank's kernels alone on frames prepared ahead (what scales with the GPUs when the host's CPU quota does not):
         # the same figure the single-GPU line carries as `device_resident`, aggregated over the ranks
         pipe.close()
@@ -457,7 +510,7 @@ def main():
                           "note": "kernels only on frames parsed, planned and uploaded ahead, all ranks at once (max over ranks, barriers on both sides)"}
         del routs, frames, batch
     sharded = None
-    if (world > 1 or args.sharded_record or dist is not None) and not args.skip_sections:
+    if args.full and (world > 1 or args.sharded_record or dist is not None) and not args.skip_sections:
         if resident_multi is None:
             pipe.close()
             torch.cuda.empty_cache()
@@ -566,7 +619,7 @@ def main():
                                       "step_frac = algorithmic bytes of the steps / wall time / peak -- the wall time of `value` is PCIe time, see device_output for the device's own pace")
 
     # parity at the full size: a frame decoded inside the timed region against the reference's pixels (bar: 1 level)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cb = cpu_baseline(datas[0], W, H)
         if cb:
             result["cpu_baseline"] = cb
@@ -574,7 +627,7 @@ def main():
             result["parity_vs_reference"] = {"max_abs_diff": int(d.max()), "differing_samples": int((d > 0).sum()), "samples": int(d.size)}
             assert d.max() <= 1, "GPU and reference pixels differ by more than one level"
 
-    if not args.skip_sections and world == 1:
+    if args.full and not args.skip_sections and world == 1:
         del host_outs, step_outs
         pipe.close()
         torch.cuda.empty_cache()
@@ -829,8 +882,9 @@ def time_sharded(steps, warmup, torch, j40_amd, dist, dev, rank, local_rank, dat
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         step()
+    time_sharded.last = step()   # (the assembled frame on rank 0, None elsewhere: --dump-outputs)
     torch.cuda.synchronize(dev)
     if dist is not None:
         dist.barrier()
@@ -869,6 +923,8 @@ def bench_sharded(args, torch, j40_amd, dist, dev, rank, local_rank, world, data
     sec = time_sharded(args.steps, args.warmup, torch, j40_amd, dist, dev, rank, local_rank, data)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [time_sharded.last.cpu().numpy()])
     print(json.dumps({
         "metric": METRIC, "value": round(W * H / sec / 1e6, 2), "unit": "Mpixels/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(sec * 1e3, 4), "higher_is_better": True, "scaling": "strong",

@@ -26,7 +26,7 @@ def free_port():
 def test_two_ranks_through_bench_py_print_one_line_with_the_sharded_record(built):
     env = dict(os.environ, J40_BENCH_BACKEND="gloo", J40_BENCH_SHARE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--width", "2048", "--height", "1280", "--batch", "8", "--distinct", "2", "--pipe-batch", "8",
            "--device-output-batch", "8", "--device-output-steps", "2", "--resident-batch", "4", "--skip-modular"]
     run = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)

@@ -16,8 +16,8 @@ python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1
 git rev-parse HEAD > $O/commit.txt 2>/dev/null
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -4 > $O/gputest.txt
 cd /tmp && export TMPDIR=/tmp
-timeout 1500 python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
-timeout 1200 python $R/bench.py --steps 20 --warmup 5 --skip-modular > $O/bench_steps20_warmup5.json 2> $O/bench_steps20_warmup5.err
+timeout 1500 python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+timeout 1200 python $R/bench.py --full --steps 20 --warmup 5 --skip-modular > $O/bench_steps20_warmup5.json 2> $O/bench_steps20_warmup5.err
 P8K=$(ls $R/build/streams/vardct_7680_4320_*forward-1.jxl | head -4 | tr '\n' ' ')
 J40HIP_API_TIMING=1 J40HIP_SERVE=0 timeout 300 $R/build/api_threads 1 8 --warm 2 $P8K > $O/api_one_thread_latency.json 2> $O/api_one_thread_latency.err
 timeout 300 $R/build/api_threads 64 8 --warm 3 --verify-every 8 $P8K > $O/api_64_threads.json 2> $O/api_64_threads.err

@@ -9,5 +9,5 @@ probe ev8_dev PROBE_ONLY=device
 probe ev0_dev J40HIP_LIB=$V/libj40hip_ev0.so PROBE_ONLY=device
 probe ev8_dev_b PROBE_ONLY=device
 probe ev0_dev_b J40HIP_LIB=$V/libj40hip_ev0.so PROBE_ONLY=device
-timeout 400 python bench.py --steps 8 --warmup 2 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/rc.txt
+timeout 400 python bench.py --full --steps 8 --warmup 2 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/rc.txt
 cat $O/rc.txt; cat $O/probes.jsonl; tail -n 5 $O/bench.err; cut -c1-6000 $O/bench.json

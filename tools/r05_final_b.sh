@@ -10,8 +10,8 @@ export TMPDIR=/tmp
 timeout 300 python -c "import __graft_entry__ as g; g.build()" > $O/build_b.log 2>&1
 cat $R/.commit_for_profiles > $O/commit_bench_lines.txt 2>/dev/null
 timeout 600 python -u -m pytest tests/test_device_stages.py -m gpu -q -p no:cacheprovider -k "earlier_forms or damaged or 7680" > $O/gputest_new_tests.txt 2>&1; echo "gputest_new rc=$? $(tail -n 1 $O/gputest_new_tests.txt)" >> $O/rc_b.txt
-timeout 600 python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench_default rc=$?" >> $O/rc_b.txt
-timeout 600 python $R/bench.py --steps 20 --warmup 5 > $O/bench_steps20_warmup5.json 2> $O/bench_steps20_warmup5.err; echo "bench_steps20 rc=$?" >> $O/rc_b.txt
+timeout 600 python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench_default rc=$?" >> $O/rc_b.txt
+timeout 600 python $R/bench.py --full --steps 20 --warmup 5 > $O/bench_steps20_warmup5.json 2> $O/bench_steps20_warmup5.err; echo "bench_steps20 rc=$?" >> $O/rc_b.txt
 cat $O/rc_b.txt; tail -n 3 $O/gputest_new_tests.txt
 python - <<'PY'
 import json

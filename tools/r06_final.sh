@@ -26,8 +26,8 @@ J40HIP_API_TIMING=1 J40HIP_SERVE=0 timeout 200 $R/build/api_threads 1 8 --warm 2
 for n in 64 128; do timeout 300 $R/build/api_threads $n 8 --warm 3 --verify-every 8 $P8K > $O/api_${n}_threads.json 2> $O/api_${n}_threads.err; echo "api_$n rc=$?" >> $O/rc.txt; done
 timeout 1500 python -u -m pytest tests -m gpu -q -p no:cacheprovider > $O/gputest_full.txt 2>&1; tail -n 6 $O/gputest_full.txt > $O/gputest.txt; echo "gputest rc=$?" >> $O/rc.txt
 timeout 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc=$?" >> $O/rc.txt
-timeout 600 python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench_default rc=$?" >> $O/rc.txt
-timeout 600 python $R/bench.py --steps 20 --warmup 5 > $O/bench_steps20_warmup5.json 2> $O/bench_steps20_warmup5.err; echo "bench_steps20 rc=$?" >> $O/rc.txt
+timeout 600 python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench_default rc=$?" >> $O/rc.txt
+timeout 600 python $R/bench.py --full --steps 20 --warmup 5 > $O/bench_steps20_warmup5.json 2> $O/bench_steps20_warmup5.err; echo "bench_steps20 rc=$?" >> $O/rc.txt
 # the contract clock in five fresh processes at the driver's flags, the copies' engines on each line
 for i in 1 2 3 4 5; do timeout 200 python $R/bench.py --skip-sections --no-cpu-baseline --steps 20 --warmup 5 >> $O/contract_clock_five_runs.jsonl 2>> $O/contract_clock_five_runs.err; echo "clock$i rc=$?" >> $O/rc.txt; done
 timeout 300 python $R/tools/modular_split_probe.py > $O/modular_split_probe.json 2> $O/modular_split_probe.err; echo "split_probe rc=$?" >> $O/rc.txt
