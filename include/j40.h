@@ -51,9 +51,11 @@ typedef struct {
 typedef void (*j40_memory_free_func)(void *data);
 
 #define J40_U8X4 0x0f33 /* j40.h:202 */
+#define J40_U16X4 0x0f35 /* j40.h:203: reserved there; here 16-bit RGBA (see j40_frame_pixels_u16x4) */
 #define J40_RGBA 0x1755 /* j40.h:228 */
 
 typedef uint8_t j40_u8x4[4];
+typedef uint16_t j40_u16x4[4]; /* j40.h:258 (commented out there) */
 typedef float j40_f32x4[4]; /* j40.h:256: declared there ahead of a float API that does not exist yet; kept so that sources naming it compile */
 
 /* j40.h:244-251 */
@@ -79,6 +81,19 @@ J40_API j40_frame j40_current_frame(j40_image *image);                          
 /* rows are 32-byte aligned, stride_bytes = 32 * ceil((4 * width + 1) / 32); memory belongs to the image */
 J40_API j40_pixels_u8x4 j40_frame_pixels_u8x4(const j40_frame *frame, int32_t channel); /* j40.h:250 / 8425 */
 J40_API const j40_u8x4 *j40_row_u8x4(j40_pixels_u8x4 pixels, int32_t y);          /* j40.h:251 / 8464 */
+
+/* 16-bit RGBA, the reference's reserved trio (j40.h:268): asked for with j40_output_format(image, J40_RGBA, J40_U16X4) before the
+ * first j40_next_frame. Every sample at the image's bit depth bpp, level p clamped to [0, maxpixel = 2^bpp - 1], is
+ * (p * 65535 + 2^(bpp - 1)) / maxpixel -- the reference's 8-bit render (j40.h:7947-7953) with 255 replaced by 65535; 8-bit images
+ * give u8 * 257. stride_bytes = 32 * ceil((8 * width + 1) / 32). The accessor of the format that was not decoded returns the error
+ * placeholder and sets "Ufm?". */
+typedef struct {
+	int32_t width, height;
+	int32_t stride_bytes;
+	const void *data;
+} j40_pixels_u16x4;
+J40_API j40_pixels_u16x4 j40_frame_pixels_u16x4(const j40_frame *frame, int32_t channel);
+J40_API const j40_u16x4 *j40_row_u16x4(j40_pixels_u16x4 pixels, int32_t y);
 
 J40_API void j40_free(j40_image *image);                                           /* j40.h:272 / 8471 */
 

@@ -230,6 +230,16 @@ J40HIP_API uint32_t j40hip_frame_set_group_range(j40hip_frame *f, int64_t first_
  * equivalents) into device memory `rgba_dev` with `stride_bytes` per row. Asynchronous. */
 J40HIP_API uint32_t j40hip_frame_decode(j40hip_frame *f, void *rgba_dev, size_t stride_bytes, void *stream);
 
+/* The frame's output format: J40HIP_U8X4 (the default; 4 bytes a pixel) or J40HIP_U16X4 (16-bit RGBA, 8 bytes a pixel: every
+ * sample at the image's bit depth p in [0, maxpixel = 2^bpp - 1] as (p * 65535 + 2^(bpp - 1)) / maxpixel; 8-bit images: u8 * 257).
+ * Every entry point that writes pixels -- j40hip_frame_decode / _timed / _decode_to_host, j40hip_batch_decode* -- writes the frame's
+ * format; a 16-bit frame's stride_bytes below 8 * width is "rnge", a batch whose frames disagree "Uof?", before anything is launched.
+ * set: 0, or "Ufm?" for any other value (the frame is left as it was). Pipelines write u8x4 only. */
+#define J40HIP_U8X4 0x0f33  /* = J40_U8X4 (include/j40.h) */
+#define J40HIP_U16X4 0x0f35 /* = J40_U16X4 */
+J40HIP_API uint32_t j40hip_frame_set_output_format(j40hip_frame *f, int32_t format);
+J40HIP_API int32_t j40hip_frame_output_format(const j40hip_frame *f);
+
 /* After the stream has been synchronised: first failing section in TOC order -> its 4-char code
  * ("coef", "shrt", "excs", "ans?" ...), 0 if every section decoded cleanly (j40.h:530-534). */
 J40HIP_API uint32_t j40hip_frame_status(j40hip_frame *f);
@@ -280,6 +290,8 @@ J40HIP_API uint32_t j40hip_frame_decode_timed(j40hip_frame *f, void *rgba_dev, s
 /* known-answer hook for the renderer's per-sample tail on the device: linear sample -> sRGB transfer -> u8
  * (j40.h:7213-7240, 7925-7935); host arrays in and out */
 J40HIP_API uint32_t j40hip_kat_device_srgb_u8(const float *v_host, size_t n, uint8_t *out_host);
+/* ... and for the 16-bit output at bit depth bpp (8..15): the level (transfer, conversion, clamp) scaled to u16 as above */
+J40HIP_API uint32_t j40hip_kat_device_srgb_u16(const float *v_host, size_t n, int32_t bpp, uint16_t *out_host);
 
 /* ---- batches: throughput mode ----
  * A batch is a set of uploaded VarDCT frames decoded together: ONE entropy launch with one pass-group

@@ -8,6 +8,7 @@ path. Function names mirror the reference's public API (j40.h:233-272):
     img.output_format(J40_RGBA, J40_U8X4)
     if img.next_frame():                 # j40_next_frame
         rgba = img.frame_pixels_u8x4()   # j40_current_frame + j40_frame_pixels_u8x4 (numpy view copy)
+    # 16-bit RGBA (J40_U16X4): img.output_format(J40_RGBA, J40_U16X4) before next_frame, then img.frame_pixels_u16x4()
     img.error(), img.error_string(); img.free()
 
 `Frame` exposes the thin C-ABI of include/j40hip.h (parse / upload / decode on a stream / status /
@@ -19,6 +20,7 @@ import numpy as np
 
 J40_RGBA = 0x1755
 J40_U8X4 = 0x0F33
+J40_U16X4 = 0x0F35
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("J40HIP_LIB") or os.path.join(_ROOT, "build", "libj40hip.so")
@@ -49,6 +51,11 @@ class _Pixels(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("stride_bytes", C.c_int32), ("data", C.c_void_p)]
 
 
+class _PixelsU16(C.Structure):
+    """j40_pixels_u16x4 (include/j40.h): the same layout as j40_pixels_u8x4"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("stride_bytes", C.c_int32), ("data", C.c_void_p)]
+
+
 # j40hip_output_alloc (include/j40hip.h): (ctx, width, height, *stride_bytes) -> host memory for the pixels
 OUTPUT_ALLOC = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_size_t))
 
@@ -75,6 +82,9 @@ def lib():
         "j40_output_format": (u32, [vp, i32, i32]), "j40_next_frame": (C.c_int, [vp]),
         "j40_current_frame": (_FrameHandle, [vp]), "j40_frame_pixels_u8x4": (_Pixels, [vp, i32]),
         "j40_row_u8x4": (vp, [_Pixels, i32]), "j40_free": (None, [vp]),
+        "j40_frame_pixels_u16x4": (_PixelsU16, [vp, i32]), "j40_row_u16x4": (vp, [_PixelsU16, i32]),
+        "j40hip_frame_set_output_format": (u32, [vp, i32]), "j40hip_frame_output_format": (i32, [vp]),
+        "j40hip_kat_device_srgb_u16": (u32, [vp, sz, i32, vp]),
         "j40hip_frame_parse": (vp, [vp, sz, C.c_int, C.POINTER(u32)]), "j40hip_frame_free": (None, [vp]),
         "j40hip_frame_parse_ex": (vp, [vp, sz, C.c_int, u32, C.POINTER(u32)]),
         "j40hip_frame_info": (None, [vp, vp]), "j40hip_frame_codestream_size": (sz, [vp]), "j40hip_frame_num_sections": (i64, [vp]),
@@ -168,6 +178,14 @@ class Image:
         rows = np.ctypeslib.as_array(C.cast(px.data, C.POINTER(C.c_uint8)), shape=(px.height, px.stride_bytes))
         return rows[:, : px.width * 4].reshape(px.height, px.width, 4).copy(), px.stride_bytes, px.data
 
+    def frame_pixels_u16x4(self, channel=J40_RGBA):
+        """the 16-bit counterpart (J40_U16X4): a uint16 numpy copy [height, width, 4], the stride in bytes, the data pointer"""
+        L = lib()
+        fr = L.j40_current_frame(C.byref(self._img))
+        px = L.j40_frame_pixels_u16x4(C.byref(fr), channel)
+        rows = np.ctypeslib.as_array(C.cast(px.data, C.POINTER(C.c_uint16)), shape=(px.height, px.stride_bytes // 2))
+        return rows[:, : px.width * 4].reshape(px.height, px.width, 4).copy(), px.stride_bytes, px.data
+
     def free(self):
         if self._live:
             lib().j40_free(C.byref(self._img))
@@ -189,13 +207,13 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes):
-    """whole path through the public API; returns (err4, rgba ndarray or None)"""
+def decode(data: bytes, fmt=J40_U8X4):
+    """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4"""
     img = from_memory(data)
-    img.output_format()
+    img.output_format(J40_RGBA, fmt)
     out = None
     if img.next_frame():
-        out = img.frame_pixels_u8x4()[0]
+        out = (img.frame_pixels_u16x4 if fmt == J40_U16X4 else img.frame_pixels_u8x4)()[0]
     err = img.error()
     img.free()
     return err, out
@@ -245,6 +263,14 @@ class Restoration(C.Structure):
     def params15(self):
         """sharp_lut[8], channel_scale[3], quant_mul, pass0, pass2, border_sad_mul: what the checkers' filter entry points take"""
         return np.array(list(self.epf_sharp_lut) + list(self.epf_channel_scale) + [self.epf_quant_mul, self.epf_pass0_sigma_scale, self.epf_pass2_sigma_scale, self.epf_border_sad_mul], np.float32)
+
+
+def kat_device_srgb_u16(values, bpp):
+    """j40hip_kat_device_srgb_u16: linear values -> the 16-bit output sample at bit depth bpp, on the device; returns (err4, uint16 array)"""
+    v = np.ascontiguousarray(values, np.float32)
+    out = np.zeros(v.size, np.uint16)
+    code = lib().j40hip_kat_device_srgb_u16(v.ctypes.data, v.size, int(bpp), out.ctypes.data)
+    return err4(code), out
 
 
 def kat_device_restoration(planes, sharpness, hfmul_inv, r, mode=1, device=0):
@@ -410,9 +436,18 @@ class Frame:
     def status(self):
         return err4(lib().j40hip_frame_status(self.h))
 
+    def set_output_format(self, fmt):
+        """J40_U8X4 (default) or J40_U16X4: what the decode entry points write for this frame (j40hip_frame_set_output_format)"""
+        self._chk(lib().j40hip_frame_set_output_format(self.h, int(fmt)), "in j40hip_frame_set_output_format")
+
+    def output_format(self):
+        return int(lib().j40hip_frame_output_format(self.h))
+
     def decode_to_host(self):
-        out = np.zeros((self.height, self.width, 4), np.uint8)
-        code = lib().j40hip_frame_decode_to_host(self.h, out.ctypes.data, self.width * 4)
+        """(err4, pixels [h, w, 4]): uint8, or uint16 when the frame is set to J40_U16X4"""
+        u16 = self.output_format() == J40_U16X4
+        out = np.zeros((self.height, self.width, 4), np.uint16 if u16 else np.uint8)
+        code = lib().j40hip_frame_decode_to_host(self.h, out.ctypes.data, self.width * (8 if u16 else 4))
         return err4(code), out
 
     def two_phase_sections(self):

@@ -59,6 +59,7 @@ struct j40__inner {
 	j40hip_frame *frame;
 	int decoded, rendered;
 	uint8_t *pixels; size_t pixels_bytes; int32_t width, height, stride_bytes;   // image-owned plane: pinned host memory from the library's pool
+	int32_t format;                                          // J40_U8X4 (default) or J40_U16X4: what j40_output_format asked for
 };
 
 namespace {
@@ -99,17 +100,18 @@ void free_inner(j40__inner *inner) {
 
 j40__inner *new_inner() {
 	j40__inner *inner = (j40__inner *) calloc(1, sizeof(j40__inner));
-	if (inner) inner->magic = INNER_MAGIC;
+	if (inner) { inner->magic = INNER_MAGIC; inner->format = J40_U8X4; }
 	return inner;
 }
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // The image-owned pixel plane in the reference's layout: rows of stride = 32 * ceil((4 * width + 1) / 32) bytes, 32-byte aligned
-// (forced padding, j40.h:1061-1065, 7939). Pinned host memory, so that the copy from the device runs at the link's rate.
-uint32_t make_plane(j40__inner *inner, int64_t width, int64_t height) {
-	const int64_t stride = (width * 4 + 1 + 31) / 32 * 32;
-	if (width >= INT32_MAX / 4 || stride > INT32_MAX || height > INT32_MAX) return code4("bigg");
+// (forced padding, j40.h:1061-1065, 7939); 16-bit images the same shape with 8 bytes a pixel. Pinned host memory, so that the copy
+// from the device runs at the link's rate.
+uint32_t make_plane(j40__inner *inner, int64_t width, int64_t height, int64_t pixel_bytes = 4) {
+	const int64_t stride = (width * pixel_bytes + 1 + 31) / 32 * 32;
+	if (width >= INT32_MAX / pixel_bytes || stride > INT32_MAX || height > INT32_MAX) return code4("bigg");
 	inner->width = (int32_t) width; inner->height = (int32_t) height; inner->stride_bytes = (int32_t) stride;
 	inner->pixels_bytes = (size_t) stride * (size_t) height;
 	inner->pixels = (uint8_t *) j40hip_pinned_acquire(inner->pixels_bytes);
@@ -202,7 +204,8 @@ j40_err advance(j40__inner *inner, int origin) {
 	const int policy = serve_policy();
 	const int64_t now = (int64_t) now_ms();
 	if (inside.n > 1) g_last_overlap_ms.store(now);
-	const bool serve = policy == 1 || (policy == 2 && (inside.n > 1 || now - g_last_overlap_ms.load() < 200));
+	const bool u16 = inner->format == J40_U16X4;   // (16-bit images take the single-frame path: the pipeline writes u8x4 only)
+	const bool serve = !u16 && (policy == 1 || (policy == 2 && (inside.n > 1 || now - g_last_overlap_ms.load() < 200)));
 	static const bool timing = getenv("J40HIP_API_TIMING") != nullptr;
 	uint32_t err = 0;
 	std::unique_ptr<FileSource> src;
@@ -252,8 +255,9 @@ j40_err advance(j40__inner *inner, int origin) {
 	if (!err) {
 		int64_t info[32];
 		j40hip_frame_info(inner->frame, info);
-		err = make_plane(inner, info[0], info[1]);
+		err = make_plane(inner, info[0], info[1], u16 ? 8 : 4);
 	}
+	if (!err) err = j40hip_frame_set_output_format(inner->frame, inner->format);
 	t2 = now_ms();
 	if (!err) err = j40hip_frame_upload(inner->frame, device_index());
 	t3 = now_ms();
@@ -263,6 +267,33 @@ j40_err advance(j40__inner *inner, int origin) {
 	if (err) { inner->origin = origin; inner->err = err; return err; }
 	inner->decoded = 1;
 	return 0;
+}
+
+// placeholder shown on error: "ERR" on red, 21 x 7 (same picture as j40.h:8432-8441); 1 = opaque. The 16-bit one: every byte * 257.
+const char *const ERR_ROWS[7] = {
+	"111111111111111111111", "100011111111111111111", "101111111111111111111", "100010001000100010001",
+	"101110111011101010111", "100010111011100010111", "111111111111111111111"};
+template <class T> const T *error_pixels() {
+	static T px[21 * 7 * 4];
+	static const bool ready = [] {   // (a function-local static: filled once, also with many threads in here)
+		const T one = (T) (sizeof(T) == 1 ? 255 : 65535);
+		for (int y = 0; y < 7; ++y) for (int x = 0; x < 21; ++x) { T *p = px + (y * 21 + x) * 4; p[0] = one; p[1] = 0; p[2] = 0; p[3] = ERR_ROWS[y][x] == '1' ? one : 0; }
+		return true;
+	}();
+	(void) ready;
+	return px;
+}
+
+// the image's decoded plane for the accessor of `format`, or null (the placeholder; errors as the reference's j40.h:8425-8462, and
+// "Ufm?" when the image was decoded in the other format)
+j40__inner *pixels_inner(const j40_frame *frame, int32_t channel, int32_t format) {
+	if (!frame || frame->magic != FRAME_MAGIC) return nullptr;
+	j40__inner *inner = frame->inner;
+	if (!inner || inner->magic != INNER_MAGIC) return nullptr;
+	if (channel != J40_RGBA) return nullptr;
+	if (!inner->rendered) { inner->origin = O_frame_pixels; inner->err = code4("Urnd"); return nullptr; }
+	if (inner->format != format) { inner->origin = O_frame_pixels; inner->err = code4("Ufm?"); return nullptr; }
+	return inner;
 }
 
 } // namespace
@@ -329,7 +360,11 @@ j40_err j40_output_format(j40_image *image, int32_t channel, int32_t format) {
 	j40_err err = check_image(image, O_output_format, &inner);
 	if (err) return err;
 	if (channel != J40_RGBA) { inner->origin = O_output_format; return inner->err = code4("Uch?"); }
-	if (format != J40_U8X4) { inner->origin = O_output_format; return inner->err = code4("Ufm?"); }
+	if (format != J40_U8X4 && format != J40_U16X4) { inner->origin = O_output_format; return inner->err = code4("Ufm?"); }
+	// (the plane is decoded in one format: once it is there, asking for the other one is refused and changes nothing -- the image
+	// keeps its pixels and no error is recorded)
+	if (inner->decoded && format != inner->format) return code4("Uof?");
+	inner->format = format;
 	return 0;
 }
 
@@ -354,22 +389,9 @@ j40_frame j40_current_frame(j40_image *image) {
 }
 
 j40_pixels_u8x4 j40_frame_pixels_u8x4(const j40_frame *frame, int32_t channel) {
-	// placeholder shown on error: "ERR" on red, 21 x 7 (same picture as j40.h:8432-8441); 1 = opaque
-	static const char *const ERR_ROWS[7] = {
-		"111111111111111111111", "100011111111111111111", "101111111111111111111", "100010001000100010001",
-		"101110111011101010111", "100010111011100010111", "111111111111111111111"};
-	static uint8_t error_pixels[21 * 7 * 4];
-	static const bool error_pixels_ready = [] {   // (a function-local static: filled once, also with many threads in here)
-		for (int y = 0; y < 7; ++y) for (int x = 0; x < 21; ++x) { uint8_t *p = error_pixels + (y * 21 + x) * 4; p[0] = 255; p[1] = 0; p[2] = 0; p[3] = ERR_ROWS[y][x] == '1' ? 255 : 0; }
-		return true;
-	}();
-	(void) error_pixels_ready;
-	const j40_pixels_u8x4 ERROR_PIXELS = {21, 7, 21 * 4, error_pixels};
-	if (!frame || frame->magic != FRAME_MAGIC) return ERROR_PIXELS;
-	j40__inner *inner = frame->inner;
-	if (!inner || inner->magic != INNER_MAGIC) return ERROR_PIXELS;
-	if (channel != J40_RGBA) return ERROR_PIXELS;
-	if (!inner->rendered) { inner->origin = O_frame_pixels; inner->err = code4("Urnd"); return ERROR_PIXELS; }
+	const j40_pixels_u8x4 ERROR_PIXELS = {21, 7, 21 * 4, error_pixels<uint8_t>()};
+	j40__inner *inner = pixels_inner(frame, channel, J40_U8X4);
+	if (!inner) return ERROR_PIXELS;
 	j40_pixels_u8x4 px;
 	px.width = inner->width; px.height = inner->height; px.stride_bytes = inner->stride_bytes; px.data = inner->pixels;
 	return px;
@@ -377,6 +399,19 @@ j40_pixels_u8x4 j40_frame_pixels_u8x4(const j40_frame *frame, int32_t channel) {
 
 const j40_u8x4 *j40_row_u8x4(j40_pixels_u8x4 pixels, int32_t y) {
 	return (const j40_u8x4 *) ((const char *) pixels.data + (size_t) pixels.stride_bytes * (size_t) y);
+}
+
+j40_pixels_u16x4 j40_frame_pixels_u16x4(const j40_frame *frame, int32_t channel) {
+	const j40_pixels_u16x4 ERROR_PIXELS = {21, 7, 21 * 8, error_pixels<uint16_t>()};
+	j40__inner *inner = pixels_inner(frame, channel, J40_U16X4);
+	if (!inner) return ERROR_PIXELS;
+	j40_pixels_u16x4 px;
+	px.width = inner->width; px.height = inner->height; px.stride_bytes = inner->stride_bytes; px.data = inner->pixels;
+	return px;
+}
+
+const j40_u16x4 *j40_row_u16x4(j40_pixels_u16x4 pixels, int32_t y) {
+	return (const j40_u16x4 *) ((const char *) pixels.data + (size_t) pixels.stride_bytes * (size_t) y);
 }
 
 void j40_free(j40_image *image) {

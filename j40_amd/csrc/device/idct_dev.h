@@ -125,6 +125,24 @@ J40_DEV int32_t srgb_u8_from_thresholds(float v, const J40_LDS float *thr) {
 	return k + (int32_t) (v >= thr[k + 1]);
 }
 
+// the sample at the frame's bit depth for one linear value: transfer curve, conversion with the reference's int16 quirk, clamp to
+// [0, 2^bpp - 1] (j40.h:7213-7240) -- the level the reference's int16 planes hold before its render reduces it to 8 bits
+J40_DEV int32_t srgb_level(float v, int32_t bpp) {
+	const int32_t maxpixel = (1 << bpp) - 1;
+	const int32_t px = f32_to_i16_x86((float) maxpixel * srgb_transfer(v) + 0.5f);
+	return px < 0 ? 0 : px > maxpixel ? maxpixel : px;
+}
+
+// The 16-bit output sample (J40_U16X4; INTEGRATION.md "16-bit output"): the reference's 8-bit render (j40.h:7947-7953) with 255
+// replaced by 65535. p = a level at bit depth bpp, clamped here to [0, maxpixel = 2^bpp - 1]:
+//   u16 = (p * 65535 + 2^(bpp - 1)) / maxpixel      (unsigned 32-bit; no overflow up to bpp 16)
+// 8-bit frames: u16 = u8 * 257 exactly. Bit depths 8-16: injective, and p = (u16 * maxpixel + 32767) / 65535 recovers the level.
+J40_DEV uint32_t scale_to_u16(int32_t p, int32_t bpp) {
+	const int32_t maxpixel = (1 << bpp) - 1;
+	p = p < 0 ? 0 : p > maxpixel ? maxpixel : p;
+	return ((uint32_t) p * 65535u + (1u << (bpp - 1))) / (uint32_t) maxpixel;
+}
+
 // the long way for one linear value: transfer curve, conversion with the reference's int16 quirk, clamp, scaling to 8 bits
 // (j40.h:7213-7240, 7925-7935). Kept out of line: the pixel kernels almost never need it (8-bit frames, values inside
 // (-9, 50000)), and inlined it bloats their inner loops.
@@ -135,9 +153,17 @@ static inline
 #endif
 int32_t srgb_sample_slow(float v, int32_t bpp) {
 	const int32_t maxpixel = (1 << bpp) - 1, maxpixel2 = 1 << (bpp - 1);
-	int32_t px = f32_to_i16_x86((float) maxpixel * srgb_transfer(v) + 0.5f);
-	px = px < 0 ? 0 : px > maxpixel ? maxpixel : px;
-	return (px * 255 + maxpixel2) / maxpixel;
+	return (srgb_level(v, bpp) * 255 + maxpixel2) / maxpixel;
+}
+
+// the long way to the 16-bit sample (scale_to_u16 on the level); out of line for the same reason
+#ifdef __HIPCC__
+__device__ __attribute__((noinline))
+#else
+static inline
+#endif
+uint32_t srgb_u16_slow(float v, int32_t bpp) {
+	return scale_to_u16(srgb_level(v, bpp), bpp);
 }
 
 // the frame constants of the colour conversion, copied out of DevFrame once per kernel so that they live in (scalar)
@@ -180,6 +206,31 @@ J40_DEV uint32_t xyb_to_rgba8(float sx, float sy, float sb, const ColourConsts &
 }
 J40_DEV uint32_t xyb_to_rgba8(float sx, float sy, float sb, const DevFrame &f, const J40_LDS float *thr) {
 	return xyb_to_rgba8(sx, sy, sb, load_colour_consts(f), thr);
+}
+
+// the 16-bit counterpart: RGBA as four u16 packed little-endian (R in the low 16 bits), alpha = 65535 (the reference drops a VarDCT
+// frame's extra channels, j40.h:7869). 8-bit frames take the threshold table as xyb_to_rgba8 does, times 257; other depths the level
+// function and scale_to_u16.
+J40_DEV uint64_t xyb_to_rgba16(float sx, float sy, float sb, const ColourConsts &f, const J40_LDS float *thr) {
+	float p[3] = {sy + sx, sy - sx, sb};
+	float s[3];
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		const float pp = p[c] - f.cbrt_opsin_bias[c];
+		s[c] = (pp * pp * pp + f.opsin_bias[c]) * f.itscale;
+	}
+	float v[3];
+#pragma unroll
+	for (int c = 0; c < 3; ++c) v[c] = s[0] * f.m[c * 3] + s[1] * f.m[c * 3 + 1] + s[2] * f.m[c * 3 + 2];
+	const float vmin = fminf(fminf(v[0], v[1]), v[2]), vmax = fmaxf(fmaxf(v[0], v[1]), v[2]);
+	uint32_t o[3];
+	if (f.bpp == 8 && vmin > -9.0f && vmax < 50000.0f && v[0] == v[0] && v[1] == v[1] && v[2] == v[2]) {
+#pragma unroll
+		for (int c = 0; c < 3; ++c) o[c] = (uint32_t) srgb_u8_from_thresholds(v[c], thr) * 257u;
+	} else {
+		for (int c = 0; c < 3; ++c) o[c] = srgb_u16_slow(v[c], f.bpp);
+	}
+	return (uint64_t) (o[0] | (o[1] << 16)) | (uint64_t) (o[2] | 0xffff0000u) << 32;
 }
 
 // host: the sample the long way, for one linear value of an 8-bit frame (table construction and tests)

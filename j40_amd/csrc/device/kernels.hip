@@ -590,14 +590,19 @@ template <int NB> struct K2Ahead {
 #ifndef J40_K2_WAVES_PER_EU
 #define J40_K2_WAVES_PER_EU 8
 #endif
-// XYB = true (single-frame launches only; the restoration filters' input, restore_kernels.hip): the samples leave as they come out of
+// OutMode::XYB (single-frame launches only; the restoration filters' input, restore_kernels.hip): the samples leave as they come out of
 // the inverse transforms -- three float planes of the frame, X, Y, B, `stride_bytes` per row (4 bytes a sample, like RGBA), one
 // behind the other from `rgba` -- instead of going through the colour conversion. The fused default is not touched by it.
+// The pixel kernels' output mode (a template parameter: each mode is an instantiation of its own, none pays for the others' code):
+// RGBA8 -- the colour tail to one u8x4 word per pixel, the default and the batches' form; XYB -- store_xyb above; RGBA16 -- the
+// colour tail to four u16 (xyb_to_rgba16, J40_U16X4), 8 bytes per pixel as one store (single-frame launches only)
+enum class OutMode { RGBA8, XYB, RGBA16 };
+template <OutMode OUT> constexpr int out_bytes() { return OUT == OutMode::RGBA16 ? 8 : 4; }   // bytes a pixel (a sample, XYB) takes in the output
 __device__ __forceinline__ void store_xyb(uint8_t *base, size_t off, size_t plane_bytes, float sx, float sy, float sb) {
 	*(float *) (base + off) = sx; *(float *) (base + plane_bytes + off) = sy; *(float *) (base + 2 * plane_bytes + off) = sb;
 }
 
-template <int LOGR, int LOGC, int NB, bool BATCH, bool XYB = false>
+template <int LOGR, int LOGC, int NB, bool BATCH, OutMode OUT = OutMode::RGBA8>
 __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU : 1)) k_vardct_dct(DevPlan plan_arg, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, uint8_t *rgba, size_t stride_bytes,
 		const K2Frame *batch, const int32_t *tile_prefix, int32_t nframes, int32_t class_a, int32_t class_b) {
 	constexpr int R = 1 << LOGR, C = 1 << LOGC, P = C + 1, TILE = R * P;
@@ -660,7 +665,7 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 			g.coeff_base = vb.coeff_base; g.llf_base = vb.llf_base;
 			g.mult[1] = vb.mult1; g.mult[0] = vb.mult1 * x_qm_mul; g.mult[2] = vb.mult1 * b_qm_mul;   // (varblock_geometry with the frame's factors at hand; j40.h:7078-7080)
 			g.kx_hf = vb.kx_hf; g.kb_hf = vb.kb_hf; g.px = vb.px; g.py = vb.py; g.effw = vb.effw; g.effh = vb.effh;
-			geom[tid] = g; g_out[tid] = (size_t) g.py * stride_bytes + (size_t) g.px * 4;
+			geom[tid] = g; g_out[tid] = (size_t) g.py * stride_bytes + (size_t) g.px * out_bytes<OUT>();
 			if (sparse) { g_be[tid][0] = be0; g_be[tid][1] = be1; g_be[tid][2] = be2; g_be[tid][3] = be3; nevents = be1 + be2 + be3; }
 		}
 		if (!(BATCH && J40_K2_AHEAD)) K2_PREFETCH_BLK(NB);
@@ -722,12 +727,13 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 		for (int k = 0; k < PER; ++k) {
 			const int32_t p = N >= 256 ? tid + 256 * k : tid % N;
 			const int32_t y = p / C, x = p % C;
-			const uint32_t in_block = (uint32_t) y * (uint32_t) stride_bytes + (uint32_t) x * 4u;   // a block spans < 4 GB of output
+			const uint32_t in_block = (uint32_t) y * (uint32_t) stride_bytes + (uint32_t) x * (uint32_t) out_bytes<OUT>();   // a block spans < 4 GB of output
 			for (int32_t b = N >= 256 ? 0 : tid / N; b < nb; b += PAR) {
 				const VbGeom &g = geom[b];
 				if (y >= g.effh || x >= g.effw) continue;
 				const float *t = lds + (size_t) b * 3 * TILE + y * P + x;
-				if constexpr (XYB) { store_xyb(rgba, g_out[b] + in_block, stride_bytes * (size_t) plan.frame->height, t[0], t[TILE], t[2 * TILE]); continue; }
+				if constexpr (OUT == OutMode::XYB) { store_xyb(rgba, g_out[b] + in_block, stride_bytes * (size_t) plan.frame->height, t[0], t[TILE], t[2 * TILE]); continue; }
+				if constexpr (OUT == OutMode::RGBA16) { __builtin_nontemporal_store(xyb_to_rgba16(t[0], t[TILE], t[2 * TILE], cc, srgb_thr), (uint64_t *) (rgba + g_out[b] + in_block)); continue; }
 				const uint32_t px = xyb_to_rgba8(t[0], t[TILE], t[2 * TILE], cc, srgb_thr);
 				__builtin_nontemporal_store(px, (uint32_t *) (rgba + g_out[b] + in_block));   // written once, never read here: keep it out of the L2's way (-2 %)
 			}
@@ -776,7 +782,7 @@ template <int SET> __device__ __forceinline__ void special8_set_phase1(int sel, 
 	else if (SET == 2) { if (sel == 12) wide_halves_phase1(lane, mid, dst, hs); else tall_halves_phase1(lane, mid, dst, hs); }
 	else afv_phase1(lane, mid, dst, hs, (sel - 14) & 1, (sel - 14) >> 1);
 }
-template <int NB, bool BATCH, int SET, bool XYB = false>
+template <int NB, bool BATCH, int SET, OutMode OUT = OutMode::RGBA8>
 __device__ __forceinline__ void vardct_special_body(DevPlan plan_arg, const DevVarblock *list, int32_t count, uint8_t *rgba, size_t stride_bytes, const K2Frame *batch, const int32_t *tile_prefix, int32_t nframes,
 		int32_t class_a, int32_t class_b) {
 	constexpr int P = SP8_TILE;
@@ -875,7 +881,8 @@ __device__ __forceinline__ void vardct_special_body(DevPlan plan_arg, const DevV
 			const VbGeom &g = geom[b];
 			if (y >= g.effh || x >= g.effw) continue;
 			const float *t = tiles + (size_t) b * 3 * P + SP8(i);
-			if constexpr (XYB) { store_xyb(rgba, (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4, stride_bytes * (size_t) f.height, t[0], t[P], t[2 * P]); continue; }
+			if constexpr (OUT == OutMode::XYB) { store_xyb(rgba, (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4, stride_bytes * (size_t) f.height, t[0], t[P], t[2 * P]); continue; }
+			if constexpr (OUT == OutMode::RGBA16) { __builtin_nontemporal_store(xyb_to_rgba16(t[0], t[P], t[2 * P], cc, srgb_thr), (uint64_t *) (rgba + (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 8)); continue; }
 			const uint32_t px = xyb_to_rgba8(t[0], t[P], t[2 * P], cc, srgb_thr);
 			*(uint32_t *) (rgba + (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4) = px;
 		}
@@ -893,10 +900,10 @@ __device__ __forceinline__ void vardct_special_body(DevPlan plan_arg, const DevV
 // the three kernels: the sets' transforms need 98 / 106 / 118 registers left alone; sets 1 and 2 fit the 64 that eight wavefronts per
 // SIMD leave (one register spilled / none), the AFV set gets the 96 of five (J40_K2_SPECIAL_WAVES, J40_K2_SPECIAL_WAVES_AFV)
 #define J40_SPECIAL_KERNEL(NAME_, SET_, WAVES_) \
-template <int NB, bool BATCH, bool XYB = false> \
+template <int NB, bool BATCH, OutMode OUT = OutMode::RGBA8> \
 __global__ void __launch_bounds__(J40_K2_SPECIAL_THREADS) __attribute__((amdgpu_waves_per_eu(WAVES_))) NAME_(DevPlan plan_arg, const DevVarblock *list, int32_t count, uint8_t *rgba, size_t stride_bytes, const K2Frame *batch, \
 		const int32_t *tile_prefix, int32_t nframes, int32_t class_a, int32_t class_b) { \
-	vardct_special_body<NB, BATCH, SET_, XYB>(plan_arg, list, count, rgba, stride_bytes, batch, tile_prefix, nframes, class_a, class_b); \
+	vardct_special_body<NB, BATCH, SET_, OUT>(plan_arg, list, count, rgba, stride_bytes, batch, tile_prefix, nframes, class_a, class_b); \
 }
 J40_SPECIAL_KERNEL(k_vardct_special_123, 1, J40_K2_SPECIAL_WAVES)
 J40_SPECIAL_KERNEL(k_vardct_special_halves, 2, J40_K2_SPECIAL_WAVES)
@@ -989,7 +996,7 @@ struct WorkgroupExec {
 #ifndef J40_LARGE_THREADS
 #define J40_LARGE_THREADS 512
 #endif
-template <bool BATCH, bool REG64, bool XYB = false>
+template <bool BATCH, bool REG64, OutMode OUT = OutMode::RGBA8>
 __global__ void __launch_bounds__(J40_LARGE_THREADS) k_vardct_large(DevPlan plan_arg, const DevVarblock *list, int32_t count, float *scratch, uint8_t *rgba, size_t stride_bytes, const K2Frame *batch, const int32_t *tile_prefix, int32_t nframes,
 		int32_t class_a, int32_t class_b) {
 	const int32_t tid = threadIdx.x, nthreads = blockDim.x;
@@ -1044,7 +1051,8 @@ __global__ void __launch_bounds__(J40_LARGE_THREADS) k_vardct_large(DevPlan plan
 		for (int32_t i = tid; i < size; i += nthreads) {
 			const int32_t y = i >> log_columns, x = i & (C - 1);
 			if (y >= g.effh || x >= g.effw) continue;
-			if constexpr (XYB) { store_xyb(rgba, (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4, stride_bytes * (size_t) f.height, S.p[0][y * S.pitch[0] + x], S.p[1][y * S.pitch[1] + x], S.p[2][y * S.pitch[2] + x]); continue; }
+			if constexpr (OUT == OutMode::XYB) { store_xyb(rgba, (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4, stride_bytes * (size_t) f.height, S.p[0][y * S.pitch[0] + x], S.p[1][y * S.pitch[1] + x], S.p[2][y * S.pitch[2] + x]); continue; }
+			if constexpr (OUT == OutMode::RGBA16) { __builtin_nontemporal_store(xyb_to_rgba16(S.p[0][y * S.pitch[0] + x], S.p[1][y * S.pitch[1] + x], S.p[2][y * S.pitch[2] + x], cc, srgb_thr), (uint64_t *) (rgba + (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 8)); continue; }
 			const uint32_t px = xyb_to_rgba8(S.p[0][y * S.pitch[0] + x], S.p[1][y * S.pitch[1] + x], S.p[2][y * S.pitch[2] + x], cc, srgb_thr);
 			*(uint32_t *) (rgba + (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4) = px;
 		}
@@ -1078,19 +1086,22 @@ __global__ void __launch_bounds__(256) k_merge_block_events(const uint32_t *grou
 	for (uint32_t i = b0 + threadIdx.x; i < b1; i += 256) dst[i] = src[i];
 }
 // the rectangles of the groups order[0 .. k) of the device image `src` written into the (pinned, device-visible) host image `dst`:
-// workgroup (row, i) copies one row of group i's rectangle, a dword per lane and turn
+// workgroup (row, i) copies one row of group i's rectangle, a dword per lane and turn; PIXEL_BYTES: 4 (u8x4) or 8 (u16x4)
+template <int PIXEL_BYTES>
 __global__ void __launch_bounds__(256) k_store_group_rects(const uint32_t *order, int32_t gcolumns, int32_t shift, int32_t width, int32_t height, const uint8_t *src, uint8_t *dst, size_t stride_bytes) {
 	const uint32_t g = order[blockIdx.y];
 	const int32_t x0 = (int32_t) (g % (uint32_t) gcolumns) << shift, y = ((int32_t) (g / (uint32_t) gcolumns) << shift) + (int32_t) blockIdx.x;
 	if (y >= height) return;
-	const int32_t w = min(1 << shift, width - x0);
-	const size_t off = (size_t) y * stride_bytes + (size_t) x0 * 4;
+	const int32_t w = min(1 << shift, width - x0) * (PIXEL_BYTES / 4);
+	const size_t off = (size_t) y * stride_bytes + (size_t) x0 * PIXEL_BYTES;
 	const uint32_t *s = (const uint32_t *) (src + off);
 	uint32_t *d = (uint32_t *) (dst + off);
 	for (int32_t x = threadIdx.x; x < w; x += 256) d[x] = s[x];
 }
-void launch_store_group_rects(const uint32_t *order, int32_t k, int32_t gcolumns, int32_t shift, int32_t width, int32_t height, const uint8_t *src, uint8_t *dst_host_mapped, size_t stride_bytes, hipStream_t stream) {
-	if (k > 0) hipLaunchKernelGGL(k_store_group_rects, dim3(1u << shift, (unsigned) k), dim3(256), 0, stream, order, gcolumns, shift, width, height, src, dst_host_mapped, stride_bytes);
+void launch_store_group_rects(const uint32_t *order, int32_t k, int32_t gcolumns, int32_t shift, int32_t width, int32_t height, const uint8_t *src, uint8_t *dst_host_mapped, size_t stride_bytes, hipStream_t stream, int32_t pixel_bytes) {
+	if (k <= 0) return;
+	if (pixel_bytes == 8) hipLaunchKernelGGL(k_store_group_rects<8>, dim3(1u << shift, (unsigned) k), dim3(256), 0, stream, order, gcolumns, shift, width, height, src, dst_host_mapped, stride_bytes);
+	else hipLaunchKernelGGL(k_store_group_rects<4>, dim3(1u << shift, (unsigned) k), dim3(256), 0, stream, order, gcolumns, shift, width, height, src, dst_host_mapped, stride_bytes);
 }
 void launch_merge_block_events(const DevPlan &plan, const uint32_t *order, int32_t k, const uint32_t *shadow, hipStream_t stream) {
 	if (k > 0) hipLaunchKernelGGL(k_merge_block_events, dim3((unsigned) k), dim3(256), 0, stream, plan.group_block_start, order, (const uint4 *) shadow, (uint4 *) plan.block_events);
@@ -1136,7 +1147,7 @@ void launch_hf_entropy(const DevPlan &plan, const HfLaunchInfo &info, int32_t fi
 // `batch` = nullptr: one frame, everything in the kernel arguments. Otherwise a persistent launch over the tiles of one class of
 // `nframes` frames (k2_bind): `grid` workgroups, tile_prefix = this launch's row of the table k_k2_tiles built; plan / list /
 // count / rgba / stride are then ignored, `large_scratch` holds 6 * 65536 floats per workgroup of the launch.
-struct K2Launch { const K2Frame *batch; const int32_t *tile_prefix; int32_t nframes, class_a, class_b, grid; int32_t xyb; };   // xyb: single-frame launches, store_xyb instead of the colour tail
+struct K2Launch { const K2Frame *batch; const int32_t *tile_prefix; int32_t nframes, class_a, class_b, grid; OutMode out; };   // out: XYB / RGBA16 for single-frame launches only
 
 template <int LOGR, int LOGC, int NB>
 static void launch_dct(const DevPlan &plan, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
@@ -1145,11 +1156,13 @@ static void launch_dct(const DevPlan &plan, const DevVarblock *list, int32_t cou
 	if (!configured) {
 		(void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
 		(void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-		(void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
+		(void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, false, OutMode::XYB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
+		(void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, false, OutMode::RGBA16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
 		configured = true;
 	}
 	const int32_t blocks = (count + NB - 1) / NB;
-	if (!bl.batch && bl.xyb) hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, false, true>), dim3((unsigned) blocks), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, nullptr, 1, 0, 0);
+	if (!bl.batch && bl.out == OutMode::XYB) hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, false, OutMode::XYB>), dim3((unsigned) blocks), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, nullptr, 1, 0, 0);
+	else if (!bl.batch && bl.out == OutMode::RGBA16) hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, false, OutMode::RGBA16>), dim3((unsigned) blocks), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, nullptr, 1, 0, 0);
 	else if (bl.batch) hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, true>), dim3((unsigned) bl.grid), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
 	else hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, false>), dim3((unsigned) blocks), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, nullptr, 1, 0, 0);
 }
@@ -1174,7 +1187,8 @@ static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const 
 	case 19: launch_dct<6, 5, 1>(plan, list, count, 12, 8, rgba, stride, bl, stream); break;
 	case 20: launch_dct<5, 6, 1>(plan, list, count, 12, 8, rgba, stride, bl, stream); break;
 #define J40_LAUNCH_SPECIAL(KERNEL_) do { \
-		if (!bl.batch && bl.xyb) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, false, true>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
+		if (!bl.batch && bl.out == OutMode::XYB) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, false, OutMode::XYB>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
+		else if (!bl.batch && bl.out == OutMode::RGBA16) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, false, OutMode::RGBA16>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
 		else if (bl.batch) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, true>), dim3((unsigned) bl.grid), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b); \
 		else hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, false>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
 	} while (0)
@@ -1191,7 +1205,8 @@ static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const 
 				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
 				(void) hipFuncSetAttribute((const void *) k_vardct_large<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
 				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
+				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, true, OutMode::XYB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
+				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, true, OutMode::RGBA16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
 				configured = true;
 			}
 			// (J40HIP_LARGE_IDCT=sweeps: round 3's kernel, every butterfly level as a sweep over an LDS panel -- kept for comparison)
@@ -1199,8 +1214,10 @@ static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const 
 			if (bl.batch) {
 				if (reg64) hipLaunchKernelGGL((k_vardct_large<true, true>), dim3((unsigned) bl.grid), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
 				else hipLaunchKernelGGL((k_vardct_large<true, false>), dim3((unsigned) bl.grid), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
-			} else if (bl.xyb) {
-				hipLaunchKernelGGL((k_vardct_large<false, true, true>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
+			} else if (bl.out == OutMode::XYB) {
+				hipLaunchKernelGGL((k_vardct_large<false, true, OutMode::XYB>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
+			} else if (bl.out == OutMode::RGBA16) {   // (the LDS form of the transforms, as XYB: same values as the sweeps)
+				hipLaunchKernelGGL((k_vardct_large<false, true, OutMode::RGBA16>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
 			} else {
 				if (reg64) hipLaunchKernelGGL((k_vardct_large<false, true>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
 				else hipLaunchKernelGGL((k_vardct_large<false, false>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
@@ -1209,8 +1226,8 @@ static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const 
 		break;
 	}
 }
-void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream) {
-	launch_vardct_class_impl(plan, dctsel, list, count, large_scratch, rgba, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, 0}, stream);
+void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
+	launch_vardct_class_impl(plan, dctsel, list, count, large_scratch, rgba, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, rgba16 ? OutMode::RGBA16 : OutMode::RGBA8}, stream);
 }
 
 // known-answer hook: the renderer's per-sample tail (sRGB transfer + conversion, j40.h:7213-7240 / 7925-7935)
@@ -1229,6 +1246,22 @@ __global__ void k_kat_srgb_u8(const float *v, size_t n, uint8_t *out) {
 void launch_kat_srgb_u8(const float *v, size_t n, uint8_t *out, hipStream_t stream) {
 	hipLaunchKernelGGL(k_kat_srgb_u8, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, v, n, out);
 }
+// the same for the 16-bit output at bit depth bpp (8..15): per sample what xyb_to_rgba16 does with one channel
+__global__ void k_kat_srgb_u16(const float *v, size_t n, int32_t bpp, uint16_t *out) {
+	__shared__ float s_thr[SRGB_TABLE_FLOATS];
+	for (int32_t i = threadIdx.x; i < SRGB_TABLE_FLOATS; i += blockDim.x) s_thr[i] = c_srgb_thr[i];
+	__syncthreads();
+	const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float x = v[i];
+	uint32_t px;
+	if (bpp == 8 && x > -9.0f && x < 50000.0f) px = (uint32_t) srgb_u8_from_thresholds(x, (const J40_LDS float *) s_thr) * 257u;
+	else px = srgb_u16_slow(x, bpp);
+	out[i] = (uint16_t) px;
+}
+void launch_kat_srgb_u16(const float *v, size_t n, int32_t bpp, uint16_t *out, hipStream_t stream) {
+	hipLaunchKernelGGL(k_kat_srgb_u16, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, v, n, bpp, out);
+}
 
 // every class of one frame; the nine 8x8 special transforms (DctSelect 1-3, 12-13 and 14-17, each run contiguous in the
 // sorted list) share three launches: k_vardct_special dispatches per varblock among the transforms of its set
@@ -1237,14 +1270,14 @@ static bool class_range(int d, int *a, int *b) {
 	*a = d; *b = d == 1 ? 4 : d == 12 ? 14 : d == 14 ? 18 : d + 1;
 	return true;
 }
-void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream) {
+void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
 	for (int d = 0, a, b; d < 27; ++d) if (class_range(d, &a, &b))
-		launch_vardct_class(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, rgba, stride, stream);
+		launch_vardct_class(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, rgba, stride, stream, rgba16);
 }
 // the same with the samples left in XYB: three float planes of the frame from `xyb`, `stride` bytes per row (store_xyb)
 void launch_vardct_frame_xyb(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, float *xyb, size_t stride, hipStream_t stream) {
 	for (int d = 0, a, b; d < 27; ++d) if (class_range(d, &a, &b))
-		launch_vardct_class_impl(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, (uint8_t *) xyb, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, 1}, stream);
+		launch_vardct_class_impl(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, (uint8_t *) xyb, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, OutMode::XYB}, stream);
 }
 
 // ---- the same for every frame of a batch at once: one persistent launch per class ----
@@ -1310,7 +1343,7 @@ void launch_vardct_batch(const K2Frame *frames_dev, int32_t nframes, int32_t *ti
 	if (nside > 0) { (void) hipEventRecord(fork, stream); for (int k = 0; k < nside; ++k) (void) hipStreamWaitEvent(side[k], fork, 0); }
 	for (int l = 0; l < K2_NUM_BATCH_LAUNCHES; ++l) {
 		const auto &L = k2_table().l[l];
-		launch_vardct_class_impl(none, L.a, nullptr, 0, large_scratch, nullptr, 0, K2Launch{frames_dev, tile_prefix_dev + (size_t) l * (size_t) (nframes + 1), nframes, L.a, L.b, grids[l], 0}, nside > 0 ? side[k2_launch_stream()[l] % nside] : stream);
+		launch_vardct_class_impl(none, L.a, nullptr, 0, large_scratch, nullptr, 0, K2Launch{frames_dev, tile_prefix_dev + (size_t) l * (size_t) (nframes + 1), nframes, L.a, L.b, grids[l], OutMode::RGBA8}, nside > 0 ? side[k2_launch_stream()[l] % nside] : stream);
 	}
 	if (nside > 0) for (int k = 0; k < nside; ++k) { (void) hipEventRecord(side_done[k], side[k]); (void) hipStreamWaitEvent(stream, side_done[k], 0); }
 }

@@ -5,6 +5,7 @@
 #pragma once
 #include "entropy_dev.h"
 #include "props_dev.h"
+#include "idct_dev.h"
 
 namespace j40hip {
 
@@ -389,6 +390,11 @@ J40_DEV uint32_t pack_rgba8(int32_t r, int32_t g, int32_t b2, int32_t a, int32_t
 		out |= (uint32_t) ((p * 255 + maxpixel2) / maxpixel) << (8 * i);
 	}
 	return out;
+}
+
+// the same pixel in 16 bits (J40_U16X4): scale_to_u16 (idct_dev.h) on each clamped level, R in the low 16 bits
+J40_DEV uint64_t pack_rgba16(int32_t r, int32_t g, int32_t b2, int32_t a, int32_t bpp) {
+	return (uint64_t) (scale_to_u16(r, bpp) | (scale_to_u16(g, bpp) << 16)) | (uint64_t) (scale_to_u16(b2, bpp) | (scale_to_u16(a, bpp) << 16)) << 32;
 }
 
 } // namespace j40hip

@@ -236,6 +236,24 @@ __global__ void __launch_bounds__(256) k_pack_planes_rect(const int16_t *r, cons
 	}
 }
 
+// the 16-bit forms (J40_U16X4): pack_rgba16, 8 bytes a pixel as one store; alpha without a plane: 65535
+__global__ void __launch_bounds__(256) k_pack_planes16(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
+	const size_t n = (size_t) width * (size_t) height;
+	const int32_t opaque = (1 << bpp) - 1;
+	for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x) {
+		const size_t y = i / (size_t) width, x = i - y * (size_t) width;
+		__builtin_nontemporal_store(pack_rgba16(r[i], g[i], b[i], a ? a[i] : opaque, bpp), (uint64_t *) (rgba + y * stride_bytes + x * 8));
+	}
+}
+__global__ void __launch_bounds__(256) k_pack_planes16_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
+	const size_t n = (size_t) rw * (size_t) rh;
+	const int32_t opaque = (1 << bpp) - 1;
+	for (size_t k = (size_t) blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t) gridDim.x * blockDim.x) {
+		const size_t y = k / (size_t) rw + (size_t) y0, x = k % (size_t) rw + (size_t) x0, i = y * (size_t) plane_width + x;
+		__builtin_nontemporal_store(pack_rgba16(r[i], g[i], b[i], a ? a[i] : opaque, bpp), (uint64_t *) (rgba + y * stride_bytes + x * 8));
+	}
+}
+
 static unsigned grid_for(size_t n) { size_t b = (n + 255) / 256; return (unsigned) (b < 1 ? 1 : b > 8192 ? 8192 : b); }
 
 // sections [first_section, first_section + num_sections): the passes of a multi-pass frame are launched one after the other
@@ -286,13 +304,15 @@ void launch_inverse_squeeze(const int16_t *avg, const int16_t *res, int16_t *out
 	if (horizontal) hipLaunchKernelGGL(k_unsqueeze_h, dim3((unsigned) ((ah + 63) / 64)), dim3(64), 0, stream, avg, res, out, aw, ah, rw);
 	else hipLaunchKernelGGL(k_unsqueeze_v, dim3((unsigned) ((aw + 255) / 256)), dim3(256), 0, stream, avg, res, out, aw, ah, rh);
 }
-void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream) {
-	hipLaunchKernelGGL(k_pack_planes, dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
+	if (rgba16) hipLaunchKernelGGL(k_pack_planes16, dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+	else hipLaunchKernelGGL(k_pack_planes, dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
 }
 
-void launch_pack_planes_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream) {
+void launch_pack_planes_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
 	if (rw <= 0 || rh <= 0) return;
-	hipLaunchKernelGGL(k_pack_planes_rect, dim3(grid_for((size_t) rw * (size_t) rh)), dim3(256), 0, stream, r, g, b, a, plane_width, x0, y0, rw, rh, bpp, rgba, stride);
+	if (rgba16) hipLaunchKernelGGL(k_pack_planes16_rect, dim3(grid_for((size_t) rw * (size_t) rh)), dim3(256), 0, stream, r, g, b, a, plane_width, x0, y0, rw, rh, bpp, rgba, stride);
+	else hipLaunchKernelGGL(k_pack_planes_rect, dim3(grid_for((size_t) rw * (size_t) rh)), dim3(256), 0, stream, r, g, b, a, plane_width, x0, y0, rw, rh, bpp, rgba, stride);
 }
 
 } // namespace j40hip

@@ -68,6 +68,8 @@ __global__ void __launch_bounds__(256) k_epf(XybPlanes in, XybPlanesOut out, con
 	}
 }
 
+// RGBA16: the 16-bit output (xyb_to_rgba16, 8 bytes a pixel), an instantiation of its own
+template <bool RGBA16>
 __global__ void __launch_bounds__(256) k_xyb_to_rgba(XybPlanes in, const DevFrame *frame, int32_t width, int32_t height, uint8_t *rgba, size_t stride_bytes) {
 	J40_STAGE_SRGB_THRESHOLDS(f);
 	const ColourConsts cc = load_colour_consts(*frame);
@@ -75,6 +77,7 @@ __global__ void __launch_bounds__(256) k_xyb_to_rgba(XybPlanes in, const DevFram
 	const int32_t x = (int32_t) (blockIdx.x * 64 + (threadIdx.x & 63)), y = (int32_t) (blockIdx.y * 4 + (threadIdx.x >> 6));
 	if (x >= width || y >= height) return;
 	const size_t i = (size_t) y * in.pitch + (size_t) x;
+	if constexpr (RGBA16) { __builtin_nontemporal_store(xyb_to_rgba16(in.p[0][i], in.p[1][i], in.p[2][i], cc, srgb_thr), (uint64_t *) (rgba + (size_t) y * stride_bytes + (size_t) x * 8)); return; }
 	const uint32_t px = xyb_to_rgba8(in.p[0][i], in.p[1][i], in.p[2][i], cc, srgb_thr);
 	__builtin_nontemporal_store(px, (uint32_t *) (rgba + (size_t) y * stride_bytes + (size_t) x * 4));
 }
@@ -109,7 +112,9 @@ __global__ void k_epf_sigma_cells(const int16_t *sharpness, const float *hfmul_i
 void launch_epf_sigma_cells(const int16_t *sharpness, const float *hfmul_inv, const RestoreParams &p, float *sigma, uint32_t *sharp_or, hipStream_t stream) {
 	hipLaunchKernelGGL(k_epf_sigma_cells, dim3((unsigned) ((p.w8 * p.h8 + 255) / 256)), dim3(256), 0, stream, sharpness, hfmul_inv, p, sigma, sharp_or);
 }
-void launch_xyb_to_rgba(const float *xyb, size_t pitch, const DevFrame *frame_dev, int32_t width, int32_t height, uint8_t *rgba, size_t stride_bytes, hipStream_t stream) {
+void launch_xyb_to_rgba(const float *xyb, size_t pitch, const DevFrame *frame_dev, int32_t width, int32_t height, uint8_t *rgba, size_t stride_bytes, hipStream_t stream, bool rgba16) {
 	XybPlanes q; for (int c = 0; c < 3; ++c) q.p[c] = xyb + (size_t) c * pitch * (size_t) height; q.pitch = pitch;
-	hipLaunchKernelGGL(k_xyb_to_rgba, dim3((unsigned) ((width + 63) / 64), (unsigned) ((height + 3) / 4)), dim3(256), 0, stream, q, frame_dev, width, height, rgba, stride_bytes);
+	const dim3 grid((unsigned) ((width + 63) / 64), (unsigned) ((height + 3) / 4));
+	if (rgba16) hipLaunchKernelGGL(k_xyb_to_rgba<true>, grid, dim3(256), 0, stream, q, frame_dev, width, height, rgba, stride_bytes);
+	else hipLaunchKernelGGL(k_xyb_to_rgba<false>, grid, dim3(256), 0, stream, q, frame_dev, width, height, rgba, stride_bytes);
 }

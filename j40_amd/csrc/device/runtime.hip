@@ -566,6 +566,12 @@ static uint32_t upload_modular(j40hip_frame *h, int device) {
 	return 0;
 }
 
+// the frame's output format (j40hip_frame_set_output_format): 16-bit RGBA, 8 bytes a pixel, or the default u8x4
+static bool out16(const j40hip_frame *h) { return h->output_format == J40HIP_U16X4; }
+static size_t pixel_bytes(const j40hip_frame *h) { return out16(h) ? 8 : 4; }
+// a 16-bit frame's rows must hold 8 * width bytes: "rnge" before anything is launched (the u8 entry points keep their old contract)
+static bool stride_too_small(const j40hip_frame *h, size_t stride_bytes) { return out16(h) && stride_bytes < 8 * (size_t) h->frame.fh.width; }
+
 static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
 	j40hip_device_state *st = h->dev;
 	const DevModPlan &plan = st->mod;
@@ -596,8 +602,8 @@ static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_by
 	if (ranged) {   // only this process' pixels are written
 		int32_t rects[3][4];
 		const int nr = group_range_rects(g0, gn, fr.fh.width, fr.fh.height, fr.fh.group_size_shift, rects);
-		for (int k = 0; k < nr; ++k) launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s);
-	} else launch_pack_planes(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s);
+		for (int k = 0; k < nr; ++k) launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
+	} else launch_pack_planes(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	if (ms3) {
 		(void) hipEventRecord(st->ev[3], s);
 		if (hipEventSynchronize(st->ev[3]) != hipSuccess) return ERR_GPU;
@@ -1078,7 +1084,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	}
 	if (perr) {   // the filters cannot run: the picture without them, and the complaint behind the sections' own (j40hip_frame_status)
 		st->restore_err = perr;
-		launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, rgba_dev, stride_bytes, s);
+		launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, rgba_dev, stride_bytes, s, out16(h));
 		return 0;
 	}
 	bool ok = true;
@@ -1096,7 +1102,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	}
 	st->d_restored = launch_restoration(st->d_xyb, st->d_xyb_tmp, (size_t) W, p, r.gab, r.epf_iters, st->d_sigma, s);
 	if (e0 && e1) (void) hipEventRecord(e1, s);
-	launch_xyb_to_rgba(st->d_restored, (size_t) W, st->plan.frame, W, H, rgba_dev, stride_bytes, s);
+	launch_xyb_to_rgba(st->d_restored, (size_t) W, st->plan.frame, W, H, rgba_dev, stride_bytes, s, out16(h));
 	st->restore_ran = mode;
 	if (e0 && e1) { if (hipEventSynchronize(e1) == hipSuccess) (void) hipEventElapsedTime(&st->restore_ms, e0, e1); }
 	if (e0) (void) hipEventDestroy(e0);
@@ -1106,6 +1112,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 
 static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
 	if (!h || !h->dev) return ERR_GPU;
+	if (stride_too_small(h, stride_bytes)) return ERR_RNGE;
 	j40hip_device_state *st = h->dev;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
 	if (st->is_modular) return decode_modular(h, rgba_dev, stride_bytes, s, ms3);
@@ -1126,10 +1133,10 @@ static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes
 		// edge-preserving filter run over the whole picture, the colour tail follows on the filtered planes (restore_kernels.h)
 		if (uint32_t e = decode_restored(h, (uint8_t *) rgba_dev, stride_bytes, rmode, s)) return e;
 	} else if (whole) {
-		launch_vardct_frame(plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev, stride_bytes, s);
+		launch_vardct_frame(plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	} else {
 		// sharded decode: only the varblocks of this process' groups
-		launch_vardct_frame(plan, st->range_class_start, st->d_vb_range, st->d_large_scratch, (uint8_t *) rgba_dev, stride_bytes, s);
+		launch_vardct_frame(plan, st->range_class_start, st->d_vb_range, st->d_large_scratch, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	}
 	if (ms3) {
 		(void) hipEventRecord(st->ev[3], s);
@@ -1269,6 +1276,11 @@ extern "C" uint32_t j40hip_batch_reset(j40hip_batch *b, j40hip_frame *const *fra
 // ev: four events to record around the three stages (clear | entropy | pixels), or nullptr
 static uint32_t batch_enqueue(j40hip_batch *b, void *const *rgba_dev, const size_t *stride_bytes, hipStream_t s, hipEvent_t *ev) {
 	if (!b) return ERR_GPU;
+	// every member in one output format (mixed batches: "Uof?"), each 16-bit member's rows wide enough: checked before anything is launched
+	for (size_t i = 0; i < b->frames.size(); ++i) {
+		if (b->frames[i]->output_format != b->frames[0]->output_format) return ERR4('U', 'o', 'f', '?');
+		if (stride_too_small(b->frames[i], stride_bytes[i])) return ERR_RNGE;
+	}
 	if (hipSetDevice(b->device) != hipSuccess) return ERR_GPU;
 	// a member that was uploaded again since the batch was made (j40hip_frame_force_dense + j40hip_frame_upload after "evof")
 	// has a new plan in new blocks: the array the entropy kernel reads is brought up to date, stream-ordered behind the
@@ -1302,14 +1314,14 @@ static uint32_t batch_enqueue(j40hip_batch *b, void *const *rgba_dev, const size
 	if (b->side_in_use == 0) {
 		for (size_t i = 0; i < b->frames.size(); ++i) {
 			j40hip_device_state *st = b->frames[i]->dev;
-			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev[i], stride_bytes[i], s);
+			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev[i], stride_bytes[i], s, out16(b->frames[i]));
 		}
 	} else {
 		if (hipEventRecord(b->fork, s) != hipSuccess) return ERR_GPU;
 		for (int k = 0; k < b->side_in_use; ++k) if (hipStreamWaitEvent(b->side[(size_t) k], b->fork, 0) != hipSuccess) return ERR_GPU;
 		for (size_t i = 0; i < b->frames.size(); ++i) {
 			j40hip_device_state *st = b->frames[i]->dev;
-			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev[i], stride_bytes[i], b->side[i % (size_t) b->side_in_use]);
+			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev[i], stride_bytes[i], b->side[i % (size_t) b->side_in_use], out16(b->frames[i]));
 		}
 		for (size_t k = 0; k < (size_t) b->side_in_use; ++k) {
 			if (hipEventRecord(b->side_done[k], b->side[k]) != hipSuccess || hipStreamWaitEvent(s, b->side_done[k], 0) != hipSuccess) return ERR_GPU;
@@ -1501,10 +1513,10 @@ static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host
 	plan_long.block_events = st->d_two_shadow;
 	launch_hf_entropy_fast_ordered(plan_long, st->hf, st->d_two_order, 0, k, s1);          // the long sections, on their own
 	launch_hf_entropy_fast_ordered(plan, st->hf, st->d_two_order, k, ng - k, s0);           // all the others
-	launch_vardct_frame(plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, d, stride_bytes, s0);
+	launch_vardct_frame(plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, d, stride_bytes, s0, out16(h));
 	if (hipEventRecord(tp.ev[1], s0) != hipSuccess || hipStreamWaitEvent(s1, tp.ev[1], 0) != hipSuccess) return ERR_GPU;
 	launch_merge_block_events(plan, st->d_two_order, k, st->d_two_shadow, s1);
-	launch_vardct_frame(plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, d, stride_bytes, s1);
+	launch_vardct_frame(plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, d, stride_bytes, s1, out16(h));
 	if (hipEventRecord(tp.ev[2], s1) != hipSuccess) return ERR_GPU;
 	if (hipGetLastError() != hipSuccess) return ERR_GPU;
 	// the image of the first pass over the link while the long sections are still being decoded: the copy the one-phase decode issues,
@@ -1523,15 +1535,16 @@ static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host
 		else (void) hipGetLastError();
 	}
 	const int32_t shift = fr.fh.group_size_shift, gdim = 1 << shift;
-	if (mapped) launch_store_group_rects(st->d_two_order, k, fr.fh.gcolumns, shift, fr.fh.width, fr.fh.height, d, mapped, stride_bytes, s1);
+	const size_t pb = pixel_bytes(h);
+	if (mapped) launch_store_group_rects(st->d_two_order, k, fr.fh.gcolumns, shift, fr.fh.width, fr.fh.height, d, mapped, stride_bytes, s1, (int32_t) pb);
 	else {
 		if (hipEventSynchronize(tp.ev[2]) != hipSuccess) return ERR_GPU;
 		for (int32_t i = 0; i < k; ++i) {
 			const int64_t g = st->two_order[(size_t) i], gx = g % fr.fh.gcolumns, gy = g / fr.fh.gcolumns;
 			const size_t x0 = (size_t) gx << shift, y0 = (size_t) gy << shift;
 			const size_t w = std::min<size_t>((size_t) gdim, (size_t) fr.fh.width - x0), rows = std::min<size_t>((size_t) gdim, (size_t) fr.fh.height - y0);
-			const size_t off = y0 * stride_bytes + x0 * 4;
-			if (hipMemcpy2DAsync(rgba_host + off, stride_bytes, d + off, stride_bytes, w * 4, rows, hipMemcpyDeviceToHost, s1) != hipSuccess) return ERR_GPU;
+			const size_t off = y0 * stride_bytes + x0 * pb;
+			if (hipMemcpy2DAsync(rgba_host + off, stride_bytes, d + off, stride_bytes, w * pb, rows, hipMemcpyDeviceToHost, s1) != hipSuccess) return ERR_GPU;
 		}
 	}
 	const double t4 = timing ? now() : 0;
@@ -1544,6 +1557,7 @@ static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host
 
 static uint32_t j40hip_frame_decode_to_host_body(j40hip_frame *h, void *rgba_host, size_t stride_bytes) {
 	if (!h || !h->dev) return ERR_GPU;
+	if (stride_too_small(h, stride_bytes)) return ERR_RNGE;
 	const Frame &fr = h->frame;
 	const int device = h->dev->device;
 	if (hipSetDevice(device) != hipSuccess) return ERR_GPU;
@@ -1577,6 +1591,13 @@ static uint32_t j40hip_frame_decode_to_host_body(j40hip_frame *h, void *rgba_hos
 	return err;
 }
 
+extern "C" uint32_t j40hip_frame_set_output_format(j40hip_frame *h, int32_t format) {
+	if (!h) return ERR_RNGE;
+	if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
+	h->output_format = format;
+	return 0;
+}
+extern "C" int32_t j40hip_frame_output_format(const j40hip_frame *h) { return h ? h->output_format : 0; }
 extern "C" void j40hip_frame_set_restoration(j40hip_frame *h, int mode) { if (h) h->restoration = mode < 0 ? -1 : mode > 2 ? 2 : mode; }
 extern "C" void j40hip_frame_restoration(const j40hip_frame *h, j40hip_restoration *out) {
 	if (!h || !out) return;
@@ -1706,6 +1727,19 @@ extern "C" uint32_t j40hip_kat_device_srgb_u8(const float *v_host, size_t n, uin
 	ok = ok && hipMemcpy(dv, v_host, n * 4, hipMemcpyHostToDevice) == hipSuccess;
 	if (ok) { int dev = 0; ok = hipGetDevice(&dev) == hipSuccess && ensure_constant_tables(dev); if (ok) launch_kat_srgb_u8(dv, n, dout, nullptr); }
 	ok = ok && hipMemcpy(out_host, dout, n, hipMemcpyDeviceToHost) == hipSuccess;
+	if (dv) (void) hipFree(dv);
+	if (dout) (void) hipFree(dout);
+	return ok ? 0 : ERR_GPU;
+}
+
+extern "C" uint32_t j40hip_kat_device_srgb_u16(const float *v_host, size_t n, int32_t bpp, uint16_t *out_host) {
+	if (bpp < 8 || bpp > 15) return ERR_RNGE;
+	if (j40hip_device_count() <= 0) return ERR_GPU;
+	float *dv = nullptr; uint16_t *dout = nullptr;
+	bool ok = hipMalloc((void **) &dv, n * 4 + 16) == hipSuccess && hipMalloc((void **) &dout, n * 2 + 16) == hipSuccess;
+	ok = ok && hipMemcpy(dv, v_host, n * 4, hipMemcpyHostToDevice) == hipSuccess;
+	if (ok) { int dev = 0; ok = hipGetDevice(&dev) == hipSuccess && ensure_constant_tables(dev); if (ok) launch_kat_srgb_u16(dv, n, bpp, dout, nullptr); }
+	ok = ok && hipMemcpy(out_host, dout, n * 2, hipMemcpyDeviceToHost) == hipSuccess;
 	if (dv) (void) hipFree(dv);
 	if (dout) (void) hipFree(dout);
 	return ok ? 0 : ERR_GPU;
