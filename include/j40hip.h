@@ -53,6 +53,26 @@ J40HIP_API j40hip_frame *j40hip_frame_parse_on(const void *buf, size_t size, int
 J40HIP_API int j40hip_frame_lf_on_device(const j40hip_frame *f);
 J40HIP_API void j40hip_frame_free(j40hip_frame *f);
 
+/* ---- the LF preview: the 1:8 image every VarDCT frame carries in its LfGroup sections (one XYB sample per 8x8 cell, the cell's mean),
+ *      decoded from those sections alone -- libjxl's progressive "DC" step. INTEGRATION.md, "LF preview". ----
+ * flags & J40HIP_PARSE_LF_ONLY (j40hip_frame_parse_ex / _streamed / _on): the parse reads headers, TOC, LfGlobal and every LfGroup
+ * section, with the same checks and codes as the full parse, and never reads nor asks for HfGlobal or a pass-group section, so a
+ * codestream cut at j40hip_frame_lf_end parses. Such a frame can only be previewed: j40hip_frame_decode / _timed / _decode_to_host and
+ * j40hip_batch_create refuse it with "Ulf?". Modular frames: "TODO" (no LF image without Squeeze). */
+#define J40HIP_PARSE_LF_ONLY 2u
+/* the shortest prefix of the codestream holding headers, TOC, LfGlobal and every LfGroup section (the largest end among those
+ * sections, so a permuted TOC is covered); a bare codestream's file prefix. Single-section frames: the whole codestream. */
+J40HIP_API int64_t j40hip_frame_lf_end(const j40hip_frame *f);
+/* the preview's size: ceil(width / 8) x ceil(height / 8) */
+J40HIP_API void j40hip_frame_lf_size(const j40hip_frame *f, int32_t *w, int32_t *h);
+/* channel c (0 X, 1 Y, 2 B) of the LF image on the host: every cell's integer times its LfGroup's dequantisation factor (j40.h:6562),
+ * adaptively smoothed within the LfGroup unless the frame skips it (j40.h:6492-6540), over the preview's grid row by row -- the
+ * samples the LLF coefficients are made of. 0, "rnge" (c out of range), "TODO" (Modular frames; frames built from a plan view) */
+J40HIP_API uint32_t j40hip_frame_lf_plane(const j40hip_frame *f, int c, float *out);
+/* the constants of the preview's colour tail as parsed: out15 = opsin_inv_mat[9] (row-major), opsin_bias[3], intensity_target, and the
+ * LF chroma-from-luma factors kx_lf, kb_lf (j40.h:7115-7116) */
+J40HIP_API void j40hip_frame_colour_consts(const j40hip_frame *f, float *out15);
+
 /* out[0..20] = width, height, is_modular, num_lf_groups, num_groups, num_passes, nb_block_ctx,
  * block_ctx_size, num_hf_presets, global_scale, quant_lf, x_qm_scale, b_qm_scale, nb_qf_thr,
  * nb_lf_thr[0..2], group_size_shift, bpp, num_extra_channels, xyb_encoded */
@@ -250,6 +270,23 @@ J40HIP_API uint32_t j40hip_frame_decode_to_host(j40hip_frame *f, void *rgba_host
  * their own beside the others, the image on its way over the link while they finish (device/runtime.hip; J40HIP_TWO_PHASE=0: never);
  * 0: in one; -1: not decoded to the host since its upload. Same pixels, same codes either way. */
 J40HIP_API int32_t j40hip_frame_two_phase_sections(const j40hip_frame *f);
+
+/* The LF preview on the device (device/lf_preview.hip): every cell of the LF image through the LF chroma from luma (X += kx_lf * Y,
+ * B += kb_lf * Y: what the reference does to every LLF coefficient, j40.h:7158, 7170) and the full decode's colour tail (XYB ->
+ * linear -> sRGB -> level at the image's bit depth, then the 8-bit render or the J40_U16X4 rule, whichever the frame's output format
+ * is), alpha opaque, into lf_w x lf_h pixels (j40hip_frame_lf_size) of `stride_bytes` per row. No restoration filter, no upsampling.
+ * j40hip_frame_upload of an LF-only frame uploads the LF integers, the LfGroups' geometry and dequantisation factors and the colour
+ * constants only; a full frame parsed without flags & 1 gets its LF integers uploaded, into an allocation of its own, at its first
+ * preview. Checked before anything is launched: a frame not uploaded or on another device "!gpu", Modular "TODO", stride_bytes below
+ * 4 * lf_w (u8) or 8 * lf_w (u16) "rnge". Asynchronous on `stream`. */
+J40HIP_API uint32_t j40hip_frame_decode_lf(j40hip_frame *f, void *rgba_dev, size_t stride_bytes, void *stream);
+/* ... into host memory, synchronously */
+J40HIP_API uint32_t j40hip_frame_decode_lf_to_host(j40hip_frame *f, void *rgba_host, size_t stride_bytes);
+/* n uploaded frames, LF-only or full, of one device in ONE launch; rgba_dev[i] / stride_bytes[i] belong to frames[i]. The same checks for
+ * every member, and members that disagree on the output format: "Uof?" -- nothing is launched then. */
+J40HIP_API uint32_t j40hip_frames_decode_lf(j40hip_frame *const *frames, int64_t n, void *const *rgba_dev, const size_t *stride_bytes, void *stream);
+/* parity tests: channel c of the device's dequantised, smoothed LF image (j40hip_frame_lf_plane's layout), by the preview kernel */
+J40HIP_API uint32_t j40hip_frame_read_lf(j40hip_frame *f, int c, float *out);
 
 /* Stage dumps for parity tests (device -> host copies, synchronous):
  *   quantised HF coefficients of LF group gg, channel c (f32[w8*h8*64], as j40__hf_coeffs leaves them) */

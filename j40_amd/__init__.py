@@ -21,6 +21,7 @@ import numpy as np
 J40_RGBA = 0x1755
 J40_U8X4 = 0x0F33
 J40_U16X4 = 0x0F35
+PARSE_LF_ONLY = 2   # J40HIP_PARSE_LF_ONLY (include/j40hip.h): the LF preview's parse
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("J40HIP_LIB") or os.path.join(_ROOT, "build", "libj40hip.so")
@@ -119,6 +120,10 @@ def lib():
         "j40hip_frame_restoration": (None, [vp, vp]), "j40hip_frame_set_restoration": (None, [vp, C.c_int]), "j40hip_frame_sharpness": (C.c_int, [vp, i64, vp]),
         "j40hip_frame_read_xyb": (u32, [vp, C.c_int, vp]), "j40hip_frame_restoration_ms": (C.c_float, [vp]),
         "j40hip_kat_device_restoration": (u32, [vp, i32, i32, vp, vp, vp, C.c_int, C.c_int, vp]),
+        "j40hip_frame_lf_end": (i64, [vp]), "j40hip_frame_lf_size": (None, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "j40hip_frame_lf_plane": (u32, [vp, C.c_int, vp]), "j40hip_frame_colour_consts": (None, [vp, vp]),
+        "j40hip_frame_decode_lf": (u32, [vp, vp, sz, vp]), "j40hip_frame_decode_lf_to_host": (u32, [vp, vp, sz]),
+        "j40hip_frames_decode_lf": (u32, [vp, i64, vp, vp, vp]), "j40hip_frame_read_lf": (u32, [vp, C.c_int, vp]),
         "j40hip_pipeline_result": (u32, [vp, i64]), "j40hip_pipeline_stats": (None, [vp, vp]), "j40hip_pipeline_stats_ex": (None, [vp, vp]), "j40hip_pipeline_lf_stats": (None, [vp, vp]), "j40hip_pipeline_reset_stats": (None, [vp]),
     }
     for name, (res, args) in sigs.items():
@@ -287,15 +292,18 @@ def kat_device_restoration(planes, sharpness, hfmul_inv, r, mode=1, device=0):
 class Frame:
     """thin C-ABI (include/j40hip.h): host parse, plan upload, hot path on a HIP stream"""
 
-    def __init__(self, data: bytes, threads: int = 4, lf_device=None):
-        """lf_device: a HIP device index -- the LfGroup streams are decoded there instead of on the host (j40hip_frame_parse_on)"""
+    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False):
+        """lf_device: a HIP device index -- the LfGroup streams are decoded there instead of on the host (j40hip_frame_parse_on).
+        lf_only: parse what the LF preview needs and nothing more (J40HIP_PARSE_LF_ONLY): `data` may end at lf_end(); such a frame
+        can only be previewed (decode_lf_to_host, decode_lf)"""
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
+        flags = PARSE_LF_ONLY if lf_only else 0
         if lf_device is None:
-            self.h = L.j40hip_frame_parse(self._buf, len(data), threads, C.byref(err))
+            self.h = L.j40hip_frame_parse_ex(self._buf, len(data), threads, flags, C.byref(err))
         else:
-            self.h = L.j40hip_frame_parse_on(self._buf, len(data), threads, 1, int(lf_device), None, C.byref(err))
+            self.h = L.j40hip_frame_parse_on(self._buf, len(data), threads, 1 | flags, int(lf_device), None, C.byref(err))
         if not self.h:
             raise J40Error(err4(err.value), "in j40hip_frame_parse")
         info = np.zeros(32, np.int64)
@@ -534,6 +542,94 @@ class Frame:
         a = np.zeros(gi["height8"] * gi["width8"] * 64, np.float32)
         self._chk(lib().j40hip_frame_read_coeffs(self.h, gg, c, a.ctypes.data), "in j40hip_frame_read_coeffs")
         return a
+
+    # ---- the LF preview (include/j40hip.h; INTEGRATION.md, "LF preview") ----
+    def lf_end(self):
+        """bytes of the codestream the preview needs: headers, TOC, LfGlobal and every LfGroup section (single section: all of it)"""
+        return int(lib().j40hip_frame_lf_end(self.h))
+
+    def lf_size(self):
+        """(w8, h8) = (ceil(width / 8), ceil(height / 8))"""
+        w, h = C.c_int32(), C.c_int32()
+        lib().j40hip_frame_lf_size(self.h, C.byref(w), C.byref(h))
+        return w.value, h.value
+
+    def lf_plane(self, c):
+        """channel c (0 X, 1 Y, 2 B) of the dequantised, smoothed LF image, from the host parse: float32 [h8, w8]"""
+        w8, h8 = self.lf_size()
+        a = np.zeros((h8, w8), np.float32)
+        self._chk(lib().j40hip_frame_lf_plane(self.h, int(c), a.ctypes.data), "in j40hip_frame_lf_plane")
+        return a
+
+    def read_lf(self, c):
+        """the same plane as the device's preview kernel computes it (uploaded frames): float32 [h8, w8]"""
+        w8, h8 = self.lf_size()
+        a = np.zeros((h8, w8), np.float32)
+        self._chk(lib().j40hip_frame_read_lf(self.h, int(c), a.ctypes.data), "in j40hip_frame_read_lf")
+        return a
+
+    def colour_consts(self):
+        """(opsin_inv_mat [3, 3], opsin_bias [3], intensity_target, kx_lf, kb_lf) as parsed, float32"""
+        a = np.zeros(15, np.float32)
+        lib().j40hip_frame_colour_consts(self.h, a.ctypes.data)
+        return a[:9].reshape(3, 3).copy(), a[9:12].copy(), np.float32(a[12]), np.float32(a[13]), np.float32(a[14])
+
+    def decode_lf(self, rgba_ptr, stride_bytes, stream=0):
+        """the preview into device memory, asynchronously on `stream`"""
+        self._chk(lib().j40hip_frame_decode_lf(self.h, rgba_ptr, stride_bytes, stream), "in j40hip_frame_decode_lf")
+
+    def decode_lf_to_host(self):
+        """the preview [h8, w8, 4]: uint8, or uint16 when the frame is set to J40_U16X4 (raises J40Error on failure)"""
+        w8, h8 = self.lf_size()
+        u16 = self.output_format() == J40_U16X4
+        out = np.zeros((h8, w8, 4), np.uint16 if u16 else np.uint8)
+        self._chk(lib().j40hip_frame_decode_lf_to_host(self.h, out.ctypes.data, w8 * (8 if u16 else 4)), "in j40hip_frame_decode_lf_to_host")
+        return out
+
+
+def frames_decode_lf(frames, rgba_ptrs, strides, stream=0):
+    """j40hip_frames_decode_lf: the previews of uploaded frames (LF-only or full) in one launch; returns the 4-char code ("" = launched)"""
+    n = len(frames)
+    hs = (C.c_void_p * n)(*[f.h for f in frames])
+    ptrs = (C.c_void_p * n)(*rgba_ptrs)
+    st = (C.c_size_t * n)(*strides)
+    return err4(lib().j40hip_frames_decode_lf(hs, n, ptrs, st, stream))
+
+
+def decode_lf(data: bytes, fmt=J40_U8X4, device=0):
+    """the LF preview of one stream (LF-only parse, upload, decode): (err4, [h8, w8, 4] uint8 or uint16 with fmt=J40_U16X4, or None)"""
+    err, out = decode_lf_many([data], fmt, device)
+    return err, out[0]
+
+
+def decode_lf_many(datas, fmt=J40_U8X4, device=0):
+    """the LF previews of many streams through ONE preview launch (j40hip_frames_decode_lf) into one device buffer: (err4, list of
+    arrays). The first stream that fails to parse or upload ends it: its code and no arrays."""
+    import torch
+    frames = []
+    try:
+        for d in datas:
+            fr = Frame(d, lf_only=True)
+            frames.append(fr)
+            fr.set_output_format(fmt)
+            fr.upload(device)
+        px = 8 if fmt == J40_U16X4 else 4
+        sizes = [f.lf_size() for f in frames]
+        offs = np.cumsum([0] + [w * h * px for w, h in sizes])
+        buf = torch.empty(int(offs[-1]), dtype=torch.uint8, device="cuda:%d" % device)
+        stream = torch.cuda.current_stream(device)
+        err = frames_decode_lf(frames, [buf.data_ptr() + int(o) for o in offs[:-1]], [w * px for w, _ in sizes], stream.cuda_stream)
+        if err:
+            return err, [None] * len(datas)
+        stream.synchronize()
+        host = buf.cpu().numpy()
+        dt = np.uint16 if fmt == J40_U16X4 else np.uint8
+        return "", [host[offs[i]:offs[i + 1]].view(dt).reshape(h, w, 4).copy() for i, (w, h) in enumerate(sizes)]
+    except J40Error as e:
+        return e.code, [None] * len(datas)
+    finally:
+        for f in frames:
+            f.close()
 
 
 class Batch:

@@ -17,7 +17,9 @@ j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads,
 	j40hip_frame *h = new j40hip_frame();
 	uint32_t code = 0;
 	try {
-		h->frame.defer_lf_tail = (flags & 1u) != 0;
+		// (an LF-only frame keeps the LLF coefficients, which nothing of the preview reads, to whoever asks for them)
+		h->frame.defer_lf_tail = (flags & (1u | J40HIP_PARSE_LF_ONLY)) != 0;
+		h->frame.lf_only = (flags & J40HIP_PARSE_LF_ONLY) != 0;
 		h->frame.lf_decoder = lf_decoder; h->frame.lf_decoder_ctx = lf_ctx;
 		extract_codestream((const uint8_t *) buf, size, &h->cs, &h->cs_size, &h->cs_storage, &h->container_stray_tail);
 		h->bare_codestream = h->cs == (const uint8_t *) buf && h->cs_size == size;
@@ -44,7 +46,8 @@ j40hip_frame *j40hip_frame_parse_streamed(const void *buf, size_t size, int thre
 	j40hip_frame *h = new j40hip_frame();
 	uint32_t code = 0;
 	try {
-		h->frame.defer_lf_tail = (flags & 1u) != 0;
+		h->frame.defer_lf_tail = (flags & (1u | J40HIP_PARSE_LF_ONLY)) != 0;
+		h->frame.lf_only = (flags & J40HIP_PARSE_LF_ONLY) != 0;
 		h->frame.need_bytes = need; h->frame.have_bytes = have; h->frame.need_ctx = ctx;
 		h->cs = p; h->cs_size = size; h->bare_codestream = true;
 		parse_frame(h->cs, h->cs_size, &h->frame, threads);
@@ -141,7 +144,7 @@ j40hip_frame *j40hip_frame_from_vardct_view(const j40hip_vardct_view *v, uint32_
 }
 
 uint32_t j40hip_frame_after_frame_status(const j40hip_frame *h) {
-	if (!h) return 0;
+	if (!h || h->frame.lf_only) return 0;   // (an LF-only parse never looks behind the LF sections)
 	const size_t end = h->frame.toc.end_offset;
 	if (!h->bare_codestream) {
 		// container: the reference asks for the next box when it looks behind the frame, and a header cut short is `shrt`
@@ -181,6 +184,30 @@ int64_t j40hip_frame_section_sizes(const j40hip_frame *h, int64_t *out) {
 	const std::vector<Section> &pg = h->frame.toc.pass_groups;
 	if (out) for (size_t i = 0; i < pg.size(); ++i) out[i] = (int64_t) pg[i].size;
 	return (int64_t) pg.size();
+}
+
+// ---- the LF preview's host half (include/j40hip.h) ----
+int64_t j40hip_frame_lf_end(const j40hip_frame *h) { return h ? (int64_t) h->frame.toc.lf_end : 0; }
+
+void j40hip_frame_lf_size(const j40hip_frame *h, int32_t *w, int32_t *hh) {
+	if (w) *w = h ? (h->frame.fh.width + 7) / 8 : 0;
+	if (hh) *hh = h ? (h->frame.fh.height + 7) / 8 : 0;
+}
+
+uint32_t j40hip_frame_lf_plane(const j40hip_frame *h, int c, float *out) {
+	if (!h || !out || c < 0 || c > 2) return E4("rnge");
+	if (h->frame.fh.is_modular) return E4("TODO");
+	try { return lf_plane(h->frame, c, out) ? 0 : E4("TODO"); }   // (frames built from a plan view carry LLF coefficients, no LF integers)
+	catch (const std::bad_alloc &) { return E4("!mem"); }
+}
+
+void j40hip_frame_colour_consts(const j40hip_frame *h, float *out) {
+	const Frame &f = h->frame;
+	for (int i = 0; i < 9; ++i) out[i] = f.im.opsin_inv_mat[i / 3][i % 3];
+	for (int i = 0; i < 3; ++i) out[9 + i] = f.im.opsin_bias[i];
+	out[12] = f.im.intensity_target;
+	out[13] = f.base_corr_x + (float) f.x_factor_lf * f.inv_colour_factor;   // j40.h:7115-7116
+	out[14] = f.base_corr_b + (float) f.b_factor_lf * f.inv_colour_factor;
 }
 
 void j40hip_frame_lf_group_info(const j40hip_frame *h, int64_t gg, int32_t *out) {

@@ -50,6 +50,12 @@ void launch_plan_build(const DevPlanBuild *builds, const DevBatchLf *lfs, int32_
 void launch_clear_block_events(const DevPlan *plans, const DevPlanBuild *builds, int32_t nframes, size_t max_frame_cells, hipStream_t stream);
 void launch_plan_verdict(const DevPlanBuild *builds, const DevPlan *plans, int32_t nframes, hipStream_t stream);
 
+// the LF preview (device/lf_preview.hip): nblocks workgroups of LFP_LANES lanes over the work list (DevLfpWork, plan.h); mode LFP_U8 /
+// LFP_U16 writes the pixels, LFP_PLANE channel `channel` of the dequantised, smoothed samples as floats
+enum { LFP_U8 = 0, LFP_U16 = 1, LFP_PLANE = 2, LFP_LANES = 256 };
+void upload_lf_preview_tables(const float *srgb_thr, hipStream_t stream);
+void launch_lf_preview(const DevLfpFrame *frames, const DevLfpWork *work, int32_t nwork, uint32_t nblocks, int32_t mode, int32_t channel, hipStream_t stream);
+
 void launch_kat_srgb_u8(const float *v, size_t n, uint8_t *out, hipStream_t stream);
 void launch_kat_srgb_u16(const float *v, size_t n, int32_t bpp, uint16_t *out, hipStream_t stream);
 

@@ -12,6 +12,7 @@
 //   k_llf_large           one 64-lane workgroup per varblock with a 64-, 128- or 256-sized side: columns in parallel through LDS
 #include <hip/hip_runtime.h>
 #include "hf_dev.h"
+#include "lf_smooth_dev.h"
 #include "kernels.h"
 
 namespace j40hip {
@@ -36,22 +37,9 @@ __device__ __forceinline__ void lf_dequant_smooth_cell(const DevPlan &plan, cons
 		for (int c = 0; c < 3; ++c) out[c][at] = (float) plan.lfraw[c][at] * gg.mult_lf[c];
 		return;
 	}
-	const float W0 = 0.05226273532324128f, W1 = 0.20345139757231578f, W2 = 0.0334829185968739f;
-	float wa[3], centre[3], gap = 0.5f;
-	for (int c = 0; c < 3; ++c) {
-		const int16_t *p = plan.lfraw[c] + at;
-		const float m = gg.mult_lf[c];
-		const float n0 = (float) p[-w8 - 1] * m, n1 = (float) p[-w8] * m, n2 = (float) p[-w8 + 1] * m;
-		const float l0 = (float) p[-1] * m, l1 = (float) p[0] * m, l2 = (float) p[1] * m;
-		const float s0 = (float) p[w8 - 1] * m, s1 = (float) p[w8] * m, s2 = (float) p[w8 + 1] * m;
-		wa[c] = (n0 * W2 + n1 * W1 + n2 * W2) + (l0 * W1 + l1 * W0 + l2 * W1) + (s0 * W2 + s1 * W1 + s2 * W2);
-		centre[c] = l1;
-		const float diff = fabsf(wa[c] - l1) * inv_m_lf[c];
-		if (gap < diff) gap = diff;
-	}
-	gap = 3.0f - 4.0f * gap;
-	gap = 0.0f > gap ? 0.0f : gap;
-	for (int c = 0; c < 3; ++c) out[c][at] = (wa[c] - centre[c]) * gap + centre[c];
+	float v[3];
+	lf_smooth_interior(plan.lfraw, at, w8, gg.mult_lf, inv_m_lf, v);   // (lf_smooth_dev.h)
+	for (int c = 0; c < 3; ++c) out[c][at] = v[c];
 }
 
 __global__ void __launch_bounds__(256) k_lf_dequant_smooth(DevPlan plan, float *out0, float *out1, float *out2, int32_t smooth, float inv0, float inv1, float inv2) {

@@ -477,4 +477,22 @@ static inline int group_range_rects(int64_t first, int64_t count, int32_t width,
 	return n;
 }
 
+// ---- the LF preview (lf_preview.hip): one lane per 8x8 cell of the LF image, any number of frames in one launch ----
+struct DevLfpGroup {
+	int32_t x8, y8, width8, height8;   // the LfGroup's place and size in cells
+	int32_t cell_base;                 // its first cell in the frame's LF integer planes (DevLfGroup::cell_base's layout)
+	float mult_lf[3];                  // dequantisation factors, channels X, Y, B (j40.h:6562)
+};
+struct DevLfpFrame {
+	const int16_t *lfraw[3];           // the frame's LF integers, channels X, Y, B
+	const DevLfpGroup *groups;
+	uint8_t *out; uint64_t stride;     // the preview's pixels (or j40hip_frame_read_lf's float plane) and their bytes per row
+	float opsin_inv_mat[9], opsin_bias[3], cbrt_opsin_bias[3], itscale;   // as DevFrame's
+	float inv_m_lf[3];                 // the smoothing's scale, j40.h:6497
+	float kx_lf, kb_lf;                // LF chroma from luma, as DevFrame's (j40.h:7115-7116, applied at 7158 / 7170)
+	int32_t bpp, smooth;
+};
+// workgroups [first_block, the next item's first_block) serve LfGroup `group` of frame `frame`, 256 cells each
+struct DevLfpWork { int32_t frame, group; uint32_t first_block, pad; };
+
 } // namespace j40hip

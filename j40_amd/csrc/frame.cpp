@@ -392,6 +392,9 @@ static void read_toc(BitReader &br, const FrameHeader &fh, Toc *toc) {
 	toc->lf_groups.assign(sections.begin() + 1, sections.begin() + 1 + fh.num_lf_groups);
 	toc->hf_global = sections[(size_t) (1 + fh.num_lf_groups)];
 	toc->pass_groups.assign(sections.begin() + 2 + fh.num_lf_groups, sections.end());
+	// (the largest end, not the last listed: a permuted TOC may store an LfGroup section behind pass groups)
+	toc->lf_end = toc->lf_global.offset + toc->lf_global.size;
+	for (const Section &s : toc->lf_groups) toc->lf_end = std::max(toc->lf_end, s.offset + s.size);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -573,18 +576,35 @@ static void smooth_lf(const Frame &f, int32_t w8, int32_t h8, std::vector<float>
 	}
 }
 
-// the tail of an LfGroup: dequantisation (j40.h:6562), adaptive smoothing (j40.h:6492), LLF coefficients of every varblock
-// (j40.h:6668-6683, 5944) from the decoded integers and the varblock layout. The device does the same at upload
-// (device/lf_tail_kernels: k_lf_dequant_smooth, k_llf) when Frame::defer_lf_tail is set.
+// the LF image of an LfGroup: dequantisation (j40.h:6562) and adaptive smoothing (j40.h:6492) of the decoded integers
+static void lf_samples(const Frame &f, const LfGroup &gg, std::vector<float> lfq[3]) {
+	const int32_t w8 = gg.width8, h8 = gg.height8;
+	for (int c = 0; c < 3; ++c) {
+		lfq[c].resize((size_t) w8 * (size_t) h8);
+		for (size_t i = 0; i < lfq[c].size(); ++i) lfq[c][i] = (float) gg.lfraw[c][i] * gg.mult_lf[c];
+	}
+	if (!f.fh.skip_adapt_lf_smooth) smooth_lf(f, w8, h8, lfq);
+}
+
+bool lf_plane(const Frame &f, int c, float *out) {
+	const size_t w8 = (size_t) ceil_div(f.fh.width, 8);
+	std::vector<float> lfq[3];
+	for (const LfGroup &gg : f.lf_groups) if (gg.lfraw[0].size() != (size_t) gg.width8 * (size_t) gg.height8) return false;
+	for (const LfGroup &gg : f.lf_groups) {
+		lf_samples(f, gg, lfq);
+		for (int32_t y = 0; y < gg.height8; ++y)
+			std::copy(lfq[c].begin() + (long) y * gg.width8, lfq[c].begin() + (long) (y + 1) * gg.width8, out + (size_t) (gg.top / 8 + y) * w8 + (size_t) (gg.left / 8));
+	}
+	return true;
+}
+
+// the tail of an LfGroup: its LF image (lf_samples), LLF coefficients of every varblock (j40.h:6668-6683, 5944) from that and the
+// varblock layout. The device does the same at upload (device/lf_tail_kernels: k_lf_dequant_smooth, k_llf) when Frame::defer_lf_tail is set.
 static void lf_tail_on_host(const Frame &f, LfGroup *gg) {
 	if (!gg->tail_pending) return;
 	const int32_t w8 = gg->width8, h8 = gg->height8;
 	std::vector<float> lfq[3];
-	for (int c = 0; c < 3; ++c) {
-		lfq[c].resize((size_t) w8 * (size_t) h8);
-		for (size_t i = 0; i < lfq[c].size(); ++i) lfq[c][i] = (float) gg->lfraw[c][i] * gg->mult_lf[c];
-	}
-	if (!f.fh.skip_adapt_lf_smooth) smooth_lf(f, w8, h8, lfq);
+	lf_samples(f, *gg, lfq);
 	for (int c = 0; c < 3; ++c) gg->llfcoeffs[c].assign((size_t) w8 * (size_t) h8, 0.0f);
 	std::vector<float> scratch(1024);
 	for (const VarblockInfo &vb : gg->varblocks) {
@@ -790,6 +810,7 @@ static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size
 		if (f->toc.single) {
 			f->toc.single_declared_end = f->toc.single_section.offset + f->toc.single_section.size;
 			f->toc.single_section.size = cs_size > f->toc.single_section.offset ? cs_size - f->toc.single_section.offset : 0;
+			f->toc.lf_end = cs_size;   // (one section holds the LF image and the pass group alike: the whole codestream)
 		}
 		clip(f->toc.single_section); clip(f->toc.lf_global); clip(f->toc.hf_global);
 		for (Section &s : f->toc.lf_groups) clip(s);
@@ -800,9 +821,12 @@ static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size
 // Headers and TOC. With a streaming source (Frame::need_bytes) their extent is not known ahead: they are parsed on the prefix that
 // has arrived and, when that runs out ("shrt": every bit read until then was real, so any other error is the stream's own), again
 // on a longer one -- a few hundred bytes for most streams, an embedded ICC profile's worth for some.
+// An LF-only parse (Frame::lf_only) grows the prefix in small steps instead -- 256 bytes, a sixteenth of it past 4 KB -- so that it asks
+// for little past the TOC: the LF sections behind it are what the caller may be waiting for, and nothing more may be asked for.
 static void parse_headers(const uint8_t *cs, size_t cs_size, Frame *f) {
 	if (!f->need_bytes || !f->have_bytes) { parse_headers_within(cs, cs_size, cs_size, f); return; }
-	size_t want = std::min<size_t>(cs_size, 4096);
+	const bool small_steps = f->lf_only;
+	size_t want = std::min<size_t>(cs_size, small_steps ? 256 : 4096);
 	for (;;) {
 		f->need(want);
 		const size_t have = std::min(cs_size, std::max(want, f->have_bytes(f->need_ctx)));
@@ -810,20 +834,22 @@ static void parse_headers(const uint8_t *cs, size_t cs_size, Frame *f) {
 		catch (const DecodeError &e) {
 			if (e.code != (uint32_t) E4("shrt") || have >= cs_size) throw;
 			*f = f->with_same_inputs();
-			want = std::min(cs_size, std::max(have * 2, have + 4096));
+			want = std::min(cs_size, small_steps ? have + std::max<size_t>(256, have / 16) : std::max(have * 2, have + 4096));
 		}
 	}
 }
 
-// LfGlobal and HfGlobal of a frame with several sections
+// LfGlobal and HfGlobal of a frame with several sections (an LF-only parse: LfGlobal alone, HfGlobal's bytes are not asked for)
 static void parse_globals(const uint8_t *cs, Frame *f) {
-	f->need(std::max(f->toc.lf_global.offset + f->toc.lf_global.size, f->toc.hf_global.offset + f->toc.hf_global.size));
+	const size_t lf_global_end = f->toc.lf_global.offset + f->toc.lf_global.size;
+	f->need(f->lf_only ? lf_global_end : std::max(lf_global_end, f->toc.hf_global.offset + f->toc.hf_global.size));
 	{
 		BitReader sr(cs + f->toc.lf_global.offset, f->toc.lf_global.size);
 		read_lf_global(sr, f);
 		// (no check that the section ends here, in none of the sections of a frame that has several: the reference's
 		// j40__finish_section_state runs j40__no_more_bytes on the section's own state and returns the parent's, j40.h:7778-7795)
 	}
+	if (f->lf_only) return;
 	if (f->fh.is_modular) {
 		J40HIP_SHOULD(f->toc.hf_global.size == 0, "excs");
 	} else {
@@ -871,6 +897,7 @@ void parse_frame(const uint8_t *cs, size_t cs_size, Frame *f, int threads) {
 	const double tp0 = timing ? now() : 0;
 	parse_headers(cs, cs_size, f);
 	const double tp1 = timing ? now() : 0;
+	J40HIP_SHOULD(!f->lf_only || !f->fh.is_modular, "TODO");   // (no LF image without Squeeze)
 
 	if (f->toc.single) {
 		// one section holds LfGlobal, HfGlobal, LfGroup and PassGroup back to back, read in the order
@@ -907,7 +934,7 @@ void parse_frame(const uint8_t *cs, size_t cs_size, Frame *f, int threads) {
 	std::atomic<uint32_t> first_err(0);
 	std::vector<uint32_t> errs((size_t) n, 0);
 	std::vector<char> done((size_t) n, 0);
-	if (f->lf_decoder) f->need(cs_size);   // (the device reads the sections out of the whole codestream)
+	if (f->lf_decoder) f->need(f->lf_only ? std::min(f->toc.lf_end, cs_size) : cs_size);   // (the device reads the sections out of the whole codestream)
 	if (f->lf_decoder && !f->fh.is_modular && !f->fh.use_lf_frame && f->fh.jpeg_upsampling == 0 && f->defer_lf_tail) {
 		// the streams of every LfGroup section on the device (device/lf_decode.hip): the host reads what precedes the LF coefficient
 		// stream -- extra precision and the first Modular header, which has to be the plain one --, the device decodes both
@@ -976,7 +1003,7 @@ void parse_frame(const uint8_t *cs, size_t cs_size, Frame *f, int threads) {
 	}
 	(void) first_err;
 	const double tp3 = timing ? now() : 0;
-	if (!f->fh.is_modular) prepare_tables(f);
+	if (!f->fh.is_modular && !f->lf_only) prepare_tables(f);   // (the coefficient orders come from HfGlobal)
 	if (timing) fprintf(stderr, "[j40hip parse] headers + TOC %.2f ms, LfGlobal + HfGlobal %.2f ms, %lld LfGroups on %d threads %.2f ms, tables %.2f ms\n", tp1 - tp0, tp2 - tp1, (long long) n, nthreads, tp3 - tp2, now() - tp3);
 }
 

@@ -64,6 +64,8 @@ struct Toc {
 	std::vector<Section> lf_groups;       // [num_lf_groups]
 	std::vector<Section> pass_groups;     // [num_passes * num_groups], pass-major
 	size_t end_offset = 0;
+	size_t lf_end = 0;                    // the largest end of LfGlobal and the LfGroup sections as the TOC states them (before clipping);
+	                                      // single-section frames: the codestream's size
 };
 
 struct DqMatrix {
@@ -157,12 +159,16 @@ struct Frame {
 	void (*need_bytes)(void *ctx, size_t upto) = nullptr; void *need_ctx = nullptr;
 	size_t (*have_bytes)(void *ctx) = nullptr;   // how many bytes are there now (with need_bytes)
 	void need(size_t upto) const { if (need_bytes) need_bytes(need_ctx, upto); }
+	// The LF preview (J40HIP_PARSE_LF_ONLY): headers, TOC, LfGlobal and the LfGroup sections only -- HfGlobal and the pass groups are
+	// never read nor asked for (frames with several sections; a single section is read whole). VarDCT frames only. Set before parse_frame.
+	bool lf_only = false;
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
 	Frame with_same_inputs() const {
 		Frame g;
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
+		g.lf_only = lf_only;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section
@@ -183,6 +189,9 @@ bool parse_frame_front(const uint8_t *cs, size_t cs_size, Frame *f, std::vector<
 void read_lf_group_raw(BitReader &br, const Frame &f, const LfGroup &gg, LfRaw *out);
 // the LfGroup tail on the host for the groups that still have it pending (dequantise, smooth, LLF): what the device does at upload
 void finish_lf_tail(Frame *f);
+// channel c (X, Y, B) of the LF image over the frame: the dequantised, smoothed sample of every 8x8 cell, ceil(width / 8) x
+// ceil(height / 8) floats row by row -- what the LLF coefficients are made of. Returns false when the frame holds no LF integers.
+bool lf_plane(const Frame &f, int c, float *out);
 
 struct GroupInfo { int32_t ggidx, gx_in_gg, gy_in_gg, gw, gh; };
 GroupInfo group_info(const FrameHeader &fh, int64_t gidx);  // j40.h:7734
