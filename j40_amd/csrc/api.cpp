@@ -132,8 +132,8 @@ void *serve_alloc(void *ctx, int64_t width, int64_t height, size_t *stride_bytes
 // J40HIP_SERVE=1 always serves, =0 never does; default: serve when another call is in progress, or was within the last 200 ms.
 std::atomic<int> g_inside{0};
 std::atomic<int64_t> g_last_overlap_ms{-1000000};
-int serve_policy() { static const int v = [] { const char *e = getenv("J40HIP_SERVE"); return !e || !*e ? 2 : atoi(e) != 0 ? 1 : 0; }(); return v; }
-int device_index() { const char *e = getenv("J40HIP_DEVICE"); return e ? atoi(e) : 0; }
+int serve_policy() { static const int v = [] { const char *e = j40hip::env_str("J40HIP_SERVE"); return !e ? 2 : atoi(e) != 0 ? 1 : 0; }(); return v; }
+int device_index() { return j40hip::env_int("J40HIP_DEVICE", 0, INT_MIN, INT_MAX); }
 
 // ---- j40_from_file's source (the reference's refillable file source and backing buffer, j40.h:1220-1386,
 // 1676-1812). j40_from_file opens the file and reads nothing (j40.h:8342-8361); the bytes are read by the first j40_next_frame, as
@@ -166,7 +166,7 @@ struct FileSource {
 	static void need(void *ctx, size_t upto) { FileSource *s = (FileSource *) ctx; std::unique_lock<std::mutex> lock(s->m); s->cv.wait(lock, [&] { return s->done || s->have >= upto; }); }
 	static size_t have_now(void *ctx) { FileSource *s = (FileSource *) ctx; std::lock_guard<std::mutex> lock(s->m); return s->done ? s->size : s->have; }
 };
-int stream_policy() { static const int v = [] { const char *e = getenv("J40HIP_STREAM"); return !e || !*e || atoi(e) != 0 ? 1 : 0; }(); return v; }
+int stream_policy() { static const int v = j40hip::env_on("J40HIP_STREAM", true) ? 1 : 0; return v; }
 
 // the whole file, now (the served path, pipes, J40HIP_STREAM=0); 0 or the error code
 uint32_t read_whole_file(j40__inner *inner) {
@@ -206,7 +206,7 @@ j40_err advance(j40__inner *inner, int origin) {
 	if (inside.n > 1) g_last_overlap_ms.store(now);
 	const bool u16 = inner->format == J40_U16X4;   // (16-bit images take the single-frame path: the pipeline writes u8x4 only)
 	const bool serve = !u16 && (policy == 1 || (policy == 2 && (inside.n > 1 || now - g_last_overlap_ms.load() < 200)));
-	static const bool timing = getenv("J40HIP_API_TIMING") != nullptr;
+	const bool timing = j40hip::api_timing();
 	uint32_t err = 0;
 	std::unique_ptr<FileSource> src;
 	if (inner->fp) {
@@ -246,7 +246,7 @@ j40_err advance(j40__inner *inner, int origin) {
 	// the device at upload, flags = 1)
 	// (no more threads than the container's CPU quota: a process over its quota has all its threads throttled, the HIP runtime's too;
 	// frames with fewer LfGroups and groups than that get a smaller team: parse_frame, build_vardct_plan)
-	static const int parse_threads = [] { const char *e = getenv("J40HIP_PARSE_THREADS"); return e && atoi(e) > 0 ? atoi(e) : std::max(1, std::min(12, j40hip_cpu_quota())); }();
+	static const int parse_threads = [] { const int v = j40hip::env_int("J40HIP_PARSE_THREADS", 0, 0, INT_MAX); return v > 0 ? v : std::max(1, std::min(12, j40hip_cpu_quota())); }();
 	inner->frame = src ? j40hip_frame_parse_streamed(inner->buf, inner->size, parse_threads, 1u, FileSource::need, FileSource::have_now, src.get(), &err)
 	                   : j40hip_frame_parse_ex(inner->buf, inner->size, parse_threads, 1u, &err);
 	if (read_failed()) return inner->err;   // (also: the rest of the file is there from here on -- the upload copies the codestream)

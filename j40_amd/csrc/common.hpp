@@ -9,6 +9,7 @@
 #include <cstring>
 #include <vector>
 #include <stdexcept>
+#include "env.hpp"
 
 namespace j40hip {
 

@@ -86,7 +86,7 @@ double prof_now() { return std::chrono::duration<double, std::milli>(std::chrono
 // pinning new 12 MB buffers, 40 and more each, for the first twenty seconds, and while memory is being pinned the copies of pixels
 // back to the host crawl: 2.6-5.3 s per 256-frame batch instead of 0.6 s)
 AStage *astage_acquire(size_t bytes) {
-	static const size_t cap = [] { const char *e = getenv("J40HIP_STAGE_BUFFERS"); return (size_t) (e && atoi(e) > 0 ? atoi(e) : 6); }();
+	static const size_t cap = [] { const int v = env_int("J40HIP_STAGE_BUFFERS", 0, 0, 1 << 20); return (size_t) (v > 0 ? v : 6); }();
 	for (auto &s : t_astages) {
 		if (s->pending && hipEventQuery(s->done) != hipSuccess) { (void) hipGetLastError(); continue; }
 		s->pending = false;
@@ -121,7 +121,7 @@ hipEvent_t event_acquire() {
 void event_release(hipEvent_t e) { if (e) { std::lock_guard<std::mutex> lock(g_event_mutex); g_event_pool.push_back(e); } }
 
 } // namespace
-// the pixel-kernel streams every batch of a device shares (stream layout 1, j40hip_stream_layout)
+// the pixel-kernel streams every batch of a device shares (a hardware queue each, every batch's chains in order: j40hip_abatch_create)
 static std::mutex g_shared_side_mutex;
 static hipStream_t g_shared_side[16][4] = {};
 
@@ -249,8 +249,7 @@ static j40hip_aframe *aframe_prepare_body(const void *buf, size_t size, int devi
 	h.bare_codestream = h.cs == (const uint8_t *) buf && h.cs_size == size;
 	if (!parse_frame_front(h.cs, h.cs_size, &fr, &tasks, &extra_prec, &plain)) return nullptr;
 	{   // the restoration filters asked for (J40HIP_RESTORATION) and signalled by the frame: the single-frame path runs them (runtime.hip: decode_restored)
-		static const bool restoration = [] { const char *e = getenv("J40HIP_RESTORATION"); return e && (!strcmp(e, "j40") || atoi(e) > 0); }();
-		if (restoration && (fr.fh.restoration.gab || fr.fh.restoration.epf_iters > 0)) return nullptr;
+		if (j40hip_rt::restoration_env() && (fr.fh.restoration.gab || fr.fh.restoration.epf_iters > 0)) return nullptr;
 	}
 	const double tp1 = prof_now();
 	af->st = static_tables_for(fr, device);
@@ -377,8 +376,7 @@ static j40hip_aframe *aframe_prepare_body(const void *buf, size_t size, int devi
 	for (int c = 0; c < 3; ++c) plan.lfraw[c] = (const int16_t *) (pb + o_raw[c]);
 	plan.xfromy = (const int16_t *) (pb + o_xfy); plan.bfromy = (const int16_t *) (pb + o_bfy);
 	plan.ev_range = (const uint32_t *) (pb + o_evr);
-	static const bool raster_lanes = [] { const char *e = getenv("J40HIP_K1_RASTER"); return e && atoi(e) != 0; }();   // (the lanes in group order, as before: for comparisons)
-	plan.lane_order = raster_lanes ? nullptr : (const uint32_t *) (pb + o_order);
+	plan.lane_order = (const uint32_t *) (pb + o_order);
 
 	DevPlanBuild &bd = af->build;
 	bd = fp.build;
@@ -407,7 +405,7 @@ static j40hip_aframe *aframe_prepare_body(const void *buf, size_t size, int devi
 }
 
 void j40hip_astage_release(void) {
-	if (getenv("J40HIP_ASYNC_TIMING") && t_prof_frames) {
+	if (j40hip_rt::async_timing() && t_prof_frames) {
 		const double n = (double) t_prof_frames;
 		fprintf(stderr, "[j40hip host stage] %lld frames, ms per frame: front parse %.2f, tables + front plan %.2f, staging buffer + plan block %.2f, copy into staging %.2f, LfGroup streams / tasks %.2f, work block + pointers %.2f, enqueue %.2f; staging buffers %zu\n",
 			(long long) t_prof_frames, t_prof[0] / n, t_prof[1] / n, t_prof[2] / n, t_prof[3] / n, t_prof[4] / n, t_prof[5] / n, t_prof[6] / n, t_astages.size());
@@ -434,7 +432,6 @@ struct j40hip_abatch {
 	int32_t nframes = 0;
 	bool have_totals = false; int32_t last_totals[K2_NUM_BATCH_LAUNCHES];   // tiles per pixel-kernel launch of the batch before (k2_batch_grids)
 	float *large_scratch = nullptr;
-	bool shared_side = false;
 	std::vector<hipStream_t> side; std::vector<hipEvent_t> side_done; hipEvent_t fork = nullptr;
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	hipEvent_t k1_ev[2] = {nullptr, nullptr};   // recorded by the device at k_hf_lanes' start and end (hipExtLaunchKernelGGL)
@@ -444,18 +441,11 @@ struct j40hip_abatch {
 };
 
 // How a pipeline's streams are laid over the hardware queues. A process gets four queues per stream priority, streams of one
-// priority share them in creation order, and kernels in one queue run one after the other. Layout 0 (the first form): every batch
-// slot has its own stream and its own four pixel-kernel streams, all of normal priority -- ten and more streams on four queues, so a
-// batch's plan build and entropy decode sat in a queue behind the pixel kernels of the batch before it and the batches ran one
-// after the other. Layout 1: ONE set of four pixel-kernel streams per device at normal priority (a queue each, every batch's chains
-// in order), the slots' streams (plan build, LfGroup tail, entropy decode) at high priority beside the copies.
-// Layout 2 (for comparison): as 1, but every batch on one and the same stream, i.e. one batch after the other: k_hf_lanes then runs
-// without another batch's pixel kernels beside it (48-52 ms instead of 52-75) and the steps take 8-15 % longer (195-200 ms
-// against 169-186).
-int j40hip_stream_layout(void) {
-	static const int v = [] { const char *e = getenv("J40HIP_STREAM_LAYOUT"); return e ? atoi(e) : 1; }();
-	return v;
-}
+// priority share them in creation order, and kernels in one queue run one after the other. With a stream and four pixel-kernel
+// streams of its own per batch slot, all of normal priority -- ten and more streams on four queues -- a batch's plan build and
+// entropy decode sat in a queue behind the pixel kernels of the batch before it and the batches ran one after the other. So: ONE
+// set of four pixel-kernel streams per device at normal priority (a queue each, every batch's chains in order), the slots' streams
+// (plan build, LfGroup tail, entropy decode) at high priority beside the copies (pipeline.hip).
 
 j40hip_abatch *j40hip_abatch_create(int device) {
 	if (hipSetDevice(device) != hipSuccess) return nullptr;
@@ -466,16 +456,15 @@ j40hip_abatch *j40hip_abatch_create(int device) {
 	for (auto &e : b->k1_ev) ok = ok && hipEventCreate(&e) == hipSuccess;
 	ok = ok && hipEventCreateWithFlags(&b->fork, hipEventDisableTiming) == hipSuccess;
 	int nside = 4;   // (kernels.hip: K2_LAUNCH_STREAM)
-	if (const char *e = getenv("J40HIP_SIDE_STREAMS")) nside = std::max(0, std::min(4, atoi(e)));
-	b->shared_side = j40hip_stream_layout() >= 1;
+	nside = env_int("J40HIP_SIDE_STREAMS", nside, 0, 4);
 	for (int i = 0; i < nside && ok; ++i) {
 		hipStream_t st = nullptr; hipEvent_t ev = nullptr;
-		if (b->shared_side) {   // the device's four pixel-kernel streams, shared by every batch (see j40hip_stream_layout)
+		{   // the device's four pixel-kernel streams, shared by every batch
 			std::lock_guard<std::mutex> lock(g_shared_side_mutex);
 			if (device < 16 && !g_shared_side[device][i]) ok = hipStreamCreateWithFlags(&g_shared_side[device][i], hipStreamNonBlocking) == hipSuccess;
 			st = device < 16 ? g_shared_side[device][i] : nullptr;
 			ok = ok && st != nullptr;
-		} else ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
+		}
 		ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
 		if (ok) { b->side.push_back(st); b->side_done.push_back(ev); }
 	}
@@ -497,7 +486,6 @@ void j40hip_abatch_free(j40hip_abatch *b) {
 	for (auto &e : b->ev) if (e) (void) hipEventDestroy(e);
 	for (auto &e : b->k1_ev) if (e) (void) hipEventDestroy(e);
 	for (auto &e : b->side_done) if (e) (void) hipEventDestroy(e);
-	if (!b->shared_side) for (auto &s : b->side) if (s) (void) hipStreamDestroy(s);
 	if (b->fork) (void) hipEventDestroy(b->fork);
 	delete b;
 }
@@ -512,7 +500,7 @@ static uint32_t abatch_launch_body(j40hip_abatch *b, j40hip_aframe *const *frame
 	int32_t total_waves = 0, max_frame_waves = 1, nlf = 0, max_lf_cells = 0; size_t cells_total = 0, max_frame_cells = 0;
 	const double tq0 = prof_now();
 	uint64_t cc0[10] = {0}, cc1[10] = {0};
-	const bool timing = getenv("J40HIP_ASYNC_TIMING") != nullptr;
+	const bool timing = j40hip_rt::async_timing();
 	if (timing) j40hip_cache_counters(cc0);
 	for (int i = 0; i < n; ++i) {
 		j40hip_aframe *f = frames[i];
@@ -522,14 +510,14 @@ static uint32_t abatch_launch_body(j40hip_abatch *b, j40hip_aframe *const *frame
 		total_waves += (f->num_groups + 63) / 64; max_frame_waves = std::max(max_frame_waves, (f->num_groups + 63) / 64); nlf += f->num_lf_groups;
 		max_lf_cells = std::max(max_lf_cells, f->max_lf_cells); cells_total += f->cells; max_frame_cells = std::max(max_frame_cells, f->cells);
 	}
-	if (const char *e = getenv("J40HIP_GENERIC_LANES")) if (atoi(e)) lanes_fast = false;
+	if (j40hip_rt::generic_lanes()) lanes_fast = false;
 	// (eight wavefronts to a workgroup when the launch fills the machine: one copy of the tables per compute unit instead of two
 	// leaves a third of its LDS to whatever else is running -- another batch's pixel kernels, the LfGroup lane decoder -- which
 	// otherwise displaces one of the two workgroups and sends it into a second round: 46 -> 91 ms)
 	int32_t waves_per_wg = lanes_fast ? (total_waves <= 2 * b->cus ? 1 : total_waves <= 4 * b->cus ? 2 : total_waves <= 6 * b->cus || lanes_lds + 8u * HF_LANE_COLS_BYTES > 150u * 1024u ? 4 : 8) : 1;
 	// (a workgroup stays on one frame: with frames of a wavefront or two -- 1920 x 1080 is 40 sections -- larger workgroups would be padding)
 	while (waves_per_wg > 1 && waves_per_wg / 2 >= max_frame_waves) waves_per_wg /= 2;
-	if (const char *e = getenv("J40HIP_WAVES_PER_WG")) if (lanes_fast) waves_per_wg = std::max(1, std::min(lanes_lds + 8u * HF_LANE_COLS_BYTES > 150u * 1024u ? 4 : 8, atoi(e)));
+	if (lanes_fast) waves_per_wg = j40hip_rt::waves_per_wg(waves_per_wg, lanes_lds + 8u * HF_LANE_COLS_BYTES > 150u * 1024u ? 4 : 8);
 	// More sections than the machine has lanes for (2048 wavefronts: eight per compute unit is what the tables' LDS leaves room
 	// for): the QUEUED form -- every frame gets one workgroup of `queue_waves` wavefronts, whose lanes take the frame's sections by
 	// decreasing size, first one each, then from a counter as they finish (k_hf_lanes) -- keeps every lane busy until its frame runs
@@ -537,7 +525,7 @@ static uint32_t abatch_launch_body(j40hip_abatch *b, j40hip_aframe *const *frame
 	// J40HIP_K1_QUEUE_WAVES: 0 never, n > 0 always with n wavefronts per frame (tests), unset: decided here.
 	int32_t queue_waves = 0;
 	{
-		static const int forced = [] { const char *e = getenv("J40HIP_K1_QUEUE_WAVES"); return e ? atoi(e) : -1; }();
+		static const int forced = env_int("J40HIP_K1_QUEUE_WAVES", -1, INT_MIN, INT_MAX);
 		bool single_pass = true;
 		for (int i = 0; i < n; ++i) single_pass = single_pass && frames[i]->num_passes == 1 && frames[i]->sparse;
 		const int32_t capacity = 8 * b->cus;
@@ -565,10 +553,6 @@ static uint32_t abatch_launch_body(j40hip_abatch *b, j40hip_aframe *const *frame
 		// first. A workgroup's wavefront w runs on SIMD w % 4: the second half of every workgroup is reversed, which puts the
 		// longest beside the shortest, the second longest beside the second shortest ... -- four SIMDs with about equal work
 		for (size_t a = first_entry; a + (size_t) waves_per_wg <= work.size(); a += (size_t) waves_per_wg) std::reverse(work.begin() + (long) (a + (size_t) waves_per_wg / 2), work.begin() + (long) (a + (size_t) waves_per_wg));
-		// (... and, bit 1 of `pad`, the second half at a lower priority than the first when two wavefronts share a SIMD: the launch
-		// ends with the wavefronts that have the largest sections, which then wait for nobody. J40HIP_K1_RANK_PRIO=0: all alike)
-		static const bool rank_prio = [] { const char *e = getenv("J40HIP_K1_RANK_PRIO"); return e ? atoi(e) != 0 : false; }();
-		if (rank_prio && waves_per_wg >= 8) for (size_t a = first_entry; a + (size_t) waves_per_wg <= work.size(); a += (size_t) waves_per_wg) for (size_t k = (size_t) waves_per_wg / 2; k < (size_t) waves_per_wg; ++k) work[a + k].pad |= 2;
 	}
 	for (int i = 0; i < n; ++i) {
 		HfLaunchInfo info = frames[i]->hf; info.tables_fit_lds = tables_in_lds;
@@ -630,8 +614,7 @@ static uint32_t abatch_launch_body(j40hip_abatch *b, j40hip_aframe *const *frame
 	else launch_hf_entropy_lanes(d_plans, d_work, (int32_t) work.size(), tables_in_lds, generic_lds, s);
 	(void) hipEventRecord(b->ev[2], s);
 	int32_t grids[K2_NUM_BATCH_LAUNCHES];
-	static const int32_t k2_wgs = [] { const char *e = getenv("J40HIP_K2_WGS"); return e ? std::max(1, atoi(e)) : 32768; }();
-	k2_batch_grids(b->have_totals ? b->last_totals : nullptr, cells_total, n, k2_wgs, grids);
+	k2_batch_grids(b->have_totals ? b->last_totals : nullptr, cells_total, n, K2_WG_SLOTS, grids);
 	launch_vardct_batch(d_k2, n, (int32_t *) (db + o_tiles), (int32_t *) (db + o_verdict + 16 * (size_t) n), grids, b->large_scratch, s, b->side.data(), (int) b->side.size(), b->fork, b->side_done.data());
 	(void) hipEventRecord(b->ev[3], s);
 	launch_plan_verdict(d_builds, d_plans, n, s);
@@ -738,7 +721,7 @@ uint32_t j40hip_alf_launch(j40hip_alf *a, j40hip_aframe *const *frames, int n, h
 	} else launch_lf_lanes((const DevLfLaneSet *) a->dev, dw, (int32_t) waves.size(), lds + 64, s, k0, k1);
 	const double tq3 = prof_now();
 	if (hipEventRecord(a->done, s) != hipSuccess || hipGetLastError() != hipSuccess) return ERR_GPU;
-	if (getenv("J40HIP_ASYNC_TIMING")) fprintf(stderr, "[j40hip lf launch] %d frames, %zu waves: pack %.2f, copy %.2f, launch %.2f, record %.2f ms\n", n, waves.size(), tq1 - tq0, tq2 - tq1, tq3 - tq2, prof_now() - tq3);
+	if (j40hip_rt::async_timing()) fprintf(stderr, "[j40hip lf launch] %d frames, %zu waves: pack %.2f, copy %.2f, launch %.2f, record %.2f ms\n", n, waves.size(), tq1 - tq0, tq2 - tq1, tq3 - tq2, prof_now() - tq3);
 	// (the caller hands the frames to a batch only once j40hip_alf_done says this launch has completed)
 	return 0;
 }

@@ -180,15 +180,7 @@ struct LaneSection {
 // a lane's 4-byte stores, each into a line of its own that its next store reaches hundreds of cycles later, left the L2 as partly
 // written sectors over and over -- 21 GB of writes per 256 8K frames for 4 GB of events. The check runs every J40_LANE_EV_FLUSH-th
 // turn (a turn adds at most one event, so twice that many slots suffice); what is left at a section's end leaves word by word.
-#ifndef J40_LANE_NZ_PERIOD
-#define J40_LANE_NZ_PERIOD 8
-#endif
-#ifndef J40_LANE_STRAIGHT_COEFFS
-#define J40_LANE_STRAIGHT_COEFFS 1
-#endif
-#ifndef J40_LANE_REFILL_SELECTS
-#define J40_LANE_REFILL_SELECTS 0   // (measured with the event ring, whose turns store nothing: call K)
-#endif
+constexpr uint32_t LANE_NZ_PERIOD = 8;   // the general turn (block starts, section starts and ends) runs on every NZ_PERIOD-th turn
 template <bool SCAN, class Source>
 J40_DEV void decode_hf_sections_lane(const LaneFrame &f, const LaneTables &t, const LaneGlobals &G, Source &src, J40_LDS int8_t *cols, int32_t col_stride, int32_t pass, J40_LDS uint32_t *ring = nullptr, int32_t ring_stride = 0) {
 	LaneSection S;
@@ -240,14 +232,9 @@ J40_DEV void decode_hf_sections_lane(const LaneFrame &f, const LaneTables &t, co
 		// (With the event ring: a lane adds at most one event a turn here too -- one that leaves its coefficients in this block takes a
 		// count symbol in the general turn, not a coefficient; the one exception would be a state of exactly zero behind a symbol, which
 		// sends the lane's next coefficient through the general turn in the same turn: the ring's 2 F slots then hold F - 1 + F + 1.)
-		if (SCAN && J40_LANE_STRAIGHT_COEFFS) {
+		if (SCAN) {
 			if (in_coeffs && !done && state != 0) {   // (a state of zero is read afresh, j40.h:2445: the general turn's business, if a stream ever gets there)
-				if (J40_LANE_REFILL_SELECTS) {   // lane_bits_refill as selects (lf_rows_dev.h); the word after next is asked for every turn
-					const bool need = b.nbits <= 32;
-					b.bits |= (uint64_t) (need ? b.ahead : 0u) << (need ? b.nbits : 0);
-					b.nbits += need ? 32 : 0; b.pos += need ? 4u : 0u;
-					b.ahead = lane_load32(b.base, b.pos);
-				} else lane_bits_refill(b);
+				lane_bits_refill(b);
 				const int32_t cctx_now = cctx + t.nnz_ctx2[(nz + (1 << shift) - 1) >> shift] + t.freq_ctx2[i >> shift] + prev;
 				uint32_t e2;
 				const uint32_t cl = t.ctx_map[cctx_now];
@@ -276,7 +263,7 @@ J40_DEV void decode_hf_sections_lane(const LaneFrame &f, const LaneTables &t, co
 			}
 			// (the turn is the same in every lane: a scalar branch seven turns in eight, kept apart from the per-lane test by the empty
 			// statement -- folded into one vector condition, every turn would pay for an `if`)
-			if ((turn % J40_LANE_NZ_PERIOD) != 0) continue;
+			if ((turn % LANE_NZ_PERIOD) != 0) continue;
 #ifdef __HIPCC__
 			asm volatile("");
 #endif
@@ -318,8 +305,8 @@ J40_DEV void decode_hf_sections_lane(const LaneFrame &f, const LaneTables &t, co
 		}
 		// Block starts are rare (3 per block against dozens of coefficient symbols) but with 64 lanes some lane starts a block in
 		// nearly every iteration, and then the whole wavefront walks the block-start code. It is therefore only executed every
-		// NZ_PERIOD-th iteration: a lane that reaches a block start in between sits out until then (J40_LANE_NZ_PERIOD = 1: never)
-		if (!in_coeffs && (turn % J40_LANE_NZ_PERIOD) != 0) continue;
+		// NZ_PERIOD-th iteration: a lane that reaches a block start in between sits out until then
+		if (!in_coeffs && (turn % LANE_NZ_PERIOD) != 0) continue;
 		lane_bits_refill(b);
 		int32_t ctx;
 		if (!in_coeffs) {  // next symbol: number of non-zeros of (block k, channel c_yxb), j40.h:6959-6967

@@ -20,6 +20,7 @@
 #include <mutex>
 #include <vector>
 #include "hostcopy.hpp"
+#include "runtime_shared.hpp"
 
 namespace {
 
@@ -74,7 +75,7 @@ bool wait_signal_bounded(hsa_signal_t s, bool *stuck) {
 // g_m held. Finds the device's agents, measures the engines, keeps the fastest.
 void set_up(int device, DeviceCopier &d) {
 	d.tried = true;
-	const char *env = getenv("J40HIP_COPY_ENGINE");   // "hip": hipMemcpyAsync as before; a number: that SDMA engine, unmeasured
+	const char *env = j40hip::env_str("J40HIP_COPY_ENGINE");   // "hip": hipMemcpyAsync as before; a number: that SDMA engine, unmeasured
 	if (env && !strcmp(env, "hip")) return;
 	if (!g_hsa_up) {
 		if (g_hsa_failed || hsa_init() != HSA_STATUS_SUCCESS) { g_hsa_failed = true; return; }   // (reference-counted: the HIP runtime holds it open already)
@@ -152,7 +153,7 @@ void set_up(int device, DeviceCopier &d) {
 	}
 	if (!stuck) { (void) hipHostFree(host); (void) hipFree(dev); }
 	(void) hipSetDevice(prev);
-	if (getenv("J40HIP_ASYNC_TIMING") || getenv("J40HIP_COPY_REPORT")) {
+	if (j40hip_rt::async_timing() || j40hip::env_str("J40HIP_COPY_REPORT")) {
 		fprintf(stderr, "[j40hip hostcopy] device %d: SDMA engines free 0x%x, recommended 0x%x; device-to-host GB/s:", device, d.free_mask, d.preferred_mask);
 		for (int e = 0; e < 16; ++e) if (d.gbps[e] != 0) fprintf(stderr, " %d:%.1f", e, d.gbps[e]);
 		fprintf(stderr, " -> engine %d; host-to-device GB/s:", d.engine);

@@ -25,6 +25,7 @@
 #include "hf_uni_dev.h"
 #include "restore_dev.h"
 #include "kernels.h"
+#include "../env.hpp"
 
 namespace j40hip {
 
@@ -313,7 +314,6 @@ __global__ void __launch_bounds__(512) k_hf_lanes(const DevPlan *plans, const Hf
 	// blockDim.x / 64 wavefronts per workgroup, all on the same frame (the host pads the work list), sharing its tables
 	const int32_t tid = threadIdx.x, lane = tid & 63;
 	const HfLaneWork w = work[blockIdx.x * (blockDim.x >> 6) + (tid >> 6)];
-	if (__builtin_amdgcn_readfirstlane(w.pad) & 2) __builtin_amdgcn_s_setprio(2);   // (the lighter wavefront of the two on this SIMD: async.hip)
 	const J40_GLOBAL DevPlan &plan = ((const J40_GLOBAL DevPlan *) plans)[w.frame];
 	const J40_GLOBAL DevFrame &df = *(const J40_GLOBAL DevFrame *) plan.frame;
 	const bool active = lane < w.num_groups;
@@ -469,15 +469,11 @@ __device__ __forceinline__ bool k2_bind(K2Iter &it, const K2Frame *batch, const 
 }
 
 // clears `n` floats of LDS tiles (n a multiple of four, the tiles 16-byte aligned: every tile size here is) with 16-byte stores: a
-// quarter of the LDS instructions of a float at a time (J40_K2_ZERO_SCALAR: the older loop, for comparison)
+// quarter of the LDS instructions of a float at a time
 __device__ __forceinline__ void zero_tiles(float *t, int32_t n, int32_t tid, int32_t nthreads) {
-#ifdef J40_K2_ZERO_SCALAR
-	for (int32_t w = tid; w < n; w += nthreads) t[w] = 0.0f;
-#else
 	typedef float f4 __attribute__((ext_vector_type(4)));
 	const f4 z = {0.0f, 0.0f, 0.0f, 0.0f};
 	for (int32_t w = 4 * tid; w < n; w += 4 * nthreads) *(f4 *) (t + w) = z;
-#endif
 }
 
 // exclusive prefix sums of the per-block event counts held by lanes 0..NB-1 of the first wavefront (`mine`, 0 for lanes
@@ -501,8 +497,7 @@ __device__ __forceinline__ void stage_event_prefix(uint32_t mine, uint32_t *pref
 
 // The run's next tile, when it lies in the same frame (k2_run_bind has stepped `it.tile` to it), starts NB records further on: lanes
 // 0 .. NB - 1 fetch the ordinals (`blk`) of its blocks now, one word each, and have them a whole tile's work later -- the next
-// prologue then asks for a block's record and for its entry of block_events side by side (J40_K2_NO_PREFETCH: as before, the entry
-// after the record)
+// prologue then asks for a block's record and for its entry of block_events side by side
 // ---- J40_K2_AHEAD (the default): the records of the run's next TWO tiles and the block_events entries of its next tile are on their
 // way while a tile is worked on, and they travel without registers: global_load_lds_dword has the memory system write a lane's dword
 // to LDS at M0 + 4 * lane. A tile's prologue was a round trip to memory for its records (with the entry of block_events beside it
@@ -575,14 +570,10 @@ template <int NB> struct K2Ahead {
 		} \
 	}
 
-#ifdef J40_K2_NO_PREFETCH
-#define K2_PREFETCH_BLK(NB_) do { next_blk_valid = false; } while (0)
-#else
 #define K2_PREFETCH_BLK(NB_) do { \
 		next_blk_valid = BATCH && it.tile < it.tile_end && it.tile < it.frame_end; \
 		if (next_blk_valid && first + (NB_) + tid < count && tid < (NB_)) next_blk = list[first + (NB_) + tid].blk; \
 	} while (0)
-#endif
 
 // J40_K2_WAVES_PER_EU: the kernels of the small shapes (up to 16 x 8) are asked to fit the registers that eight wavefronts per SIMD
 // leave -- 53-58 instead of 72-77, no spills --, which pays once the prologue's two loads travel together: pixel stage of 256 8K frames
@@ -912,74 +903,8 @@ J40_SPECIAL_KERNEL(k_vardct_special_afv, 3, J40_K2_SPECIAL_WAVES_AFV)
 
 
 // ------------------------------------------------------------------------------------------------
-// K2l: transforms with a 128- or 256-sized side. One workgroup per varblock; the butterfly levels
-// are swept over an HBM scratch (two ping-pong buffers per channel), one __syncthreads per level.
-// Same arithmetic as the recursion: depth d works on sub-vectors of length N >> d (j40.h:5802-5841).
-
-template <class Ptr>   // float * (HBM scratch) or J40_LDS float * (a panel in LDS, idct_panels)
-__device__ void idct_sweeps(Ptr A, Ptr B, int32_t t, int32_t ncols, int32_t stride_k, int32_t stride_col) {
-	// on return the result is in B (A is clobbered); A = input
-	const int32_t N = 1 << t, half = N >> 1;
-	const int32_t tid = threadIdx.x, nthreads = blockDim.x;
-	if (t == 0) { for (int32_t w = tid; w < ncols; w += nthreads) B[w * stride_col] = A[w * stride_col]; __syncthreads(); return; }
-	for (int32_t d = 0; d <= t - 2; ++d) {  // downward: split even / odd
-		const Ptr src = (d & 1) ? B : A; const Ptr dst = (d & 1) ? A : B;
-		const int32_t n = N >> d, hn = n >> 1;
-		for (int32_t w = tid; w < ncols * half; w += nthreads) {
-			const int32_t col = w % ncols, j = w / ncols, o = (j / hn) * n, i = j % hn;
-			const Ptr s = src + col * stride_col; const Ptr q = dst + col * stride_col;
-			q[(o + i) * stride_k] = s[(o + 2 * i) * stride_k];
-			q[(o + hn + i) * stride_k] = i == 0 ? J40_SQRT2F * s[(o + 1) * stride_k] : s[(o + 2 * i - 1) * stride_k] + s[(o + 2 * i + 1) * stride_k];
-		}
-		__syncthreads();
-	}
-	{   // length-2 tails at depth t - 1
-		const int32_t d = t - 1;
-		const Ptr src = (d & 1) ? B : A; const Ptr dst = (d & 1) ? A : B;
-		for (int32_t w = tid; w < ncols * half; w += nthreads) {
-			const int32_t col = w % ncols, o = (w / ncols) * 2;
-			const float p = src[col * stride_col + o * stride_k], q = src[col * stride_col + (o + 1) * stride_k];
-			dst[col * stride_col + o * stride_k] = p + q;
-			dst[col * stride_col + (o + 1) * stride_k] = p - q;
-		}
-		__syncthreads();
-	}
-	for (int32_t d = t - 2; d >= 0; --d) {  // upward: combine halves
-		const Ptr src = (d & 1) ? B : A; const Ptr dst = (d & 1) ? A : B;
-		const int32_t n = N >> d, hn = n >> 1;
-		for (int32_t w = tid; w < ncols * half; w += nthreads) {
-			const int32_t col = w % ncols, j = w / ncols, o = (j / hn) * n, i = j % hn;
-			const Ptr s = src + col * stride_col; const Ptr q = dst + col * stride_col;
-			const float x = s[(o + i) * stride_k], y = s[(o + hn + i) * stride_k];
-			const float m = c_half_secants[hn + i];
-			const float ym = y * m;
-			q[(o + i) * stride_k] = x + ym;
-			q[(o + n - 1 - i) * stride_k] = x - ym;
-		}
-		__syncthreads();
-	}
-}
-
-// The same sweeps with the vectors in LDS: the 1-D transforms of `nvec` vectors of length N = 1 << t (element k of vector v at
-// src[v * stride_col + k * stride_k]; one of the two strides is 1) are taken through LDS a PANEL of M vectors at a time, N * M <=
-// 16384 floats, both ping-pong buffers of the sweeps in LDS (2 * (16384 + 256) floats: the panel's rows are M + 1 apart so that
-// the transposing copy does not hit one bank). The result goes to dst, same layout; src is left alone. Every value takes the same
-// operations in the same order as in idct_sweeps over the HBM scratch (15 levels of 256-point butterflies = 15 round trips through
-// HBM per dimension there, one here).
-__device__ void idct_panels(const float *src, float *dst, int32_t t, int32_t nvec, int32_t stride_k, int32_t stride_col, J40_LDS float *lds) {
-	const int32_t N = 1 << t, M = min(nvec, 16384 >> t), P = M + 1;
-	const int32_t tid = threadIdx.x, nthreads = blockDim.x;
-	J40_LDS float *la = lds, *lb = lds + LARGE_PANEL_FLOATS;
-	for (int32_t v0 = 0; v0 < nvec; v0 += M) {
-		if (stride_k == 1) for (int32_t w = tid; w < N * M; w += nthreads) { const int32_t m = w >> t, k = w & (N - 1); la[k * P + m] = src[(size_t) (v0 + m) * stride_col + k]; }
-		else for (int32_t w = tid; w < N * M; w += nthreads) { const int32_t k = w / M, m = w - k * M; la[k * P + m] = src[(size_t) k * stride_k + v0 + m]; }
-		__syncthreads();
-		idct_sweeps(la, lb, t, M, P, 1);   // result in lb
-		if (stride_k == 1) for (int32_t w = tid; w < N * M; w += nthreads) { const int32_t m = w >> t, k = w & (N - 1); dst[(size_t) (v0 + m) * stride_col + k] = lb[k * P + m]; }
-		else for (int32_t w = tid; w < N * M; w += nthreads) { const int32_t k = w / M, m = w - k * M; dst[(size_t) k * stride_k + v0 + m] = lb[k * P + m]; }
-		__syncthreads();
-	}
-}
+// K2l: transforms with a 128- or 256-sized side. One workgroup per varblock (large_dev.h); the workgroup's scratch in HBM
+// holds two buffers per channel. Same arithmetic as the recursion: depth d works on sub-vectors of length N >> d (j40.h:5802-5841).
 
 // what large_dev.h's passes run on: every lane makes the call, a barrier follows (stores to the workgroup's scratch in HBM are
 // visible to its other lanes behind it)
@@ -987,16 +912,15 @@ struct WorkgroupExec {
 	template <class F> __device__ __forceinline__ void run(F f) { f((int32_t) threadIdx.x, (int32_t) blockDim.x); __threadfence_block(); __syncthreads(); }
 };
 
-// REG64: the top levels of the recursion in LDS, 64-point sub-vectors in registers (large_dev.h); a tile that fits one LDS buffer
-// (128x128, 128x64, 64x128) takes both dimensions there and makes ONE trip through the scratch per channel. !REG64: round 3's
-// form -- every level of the butterflies as a sweep over an LDS panel, two trips per channel (J40HIP_LARGE_IDCT=sweeps).
+// The top levels of the recursion in LDS, 64-point sub-vectors in registers (large_dev.h); a tile that fits one LDS buffer
+// (128x128, 128x64, 64x128) takes both dimensions there and makes ONE trip through the scratch per channel.
 // 512 lanes: two wavefronts per SIMD under the 133 KB of LDS -- the levels, the scatter and the colour conversion run twice as wide, the
 // 256 64-point sub-vectors of a pass keep half of them busy (43 against 51 ms for the pixel stage of the maxlog-8 bench stream;
 // the batch-wide instantiation then spills 1 KB per lane to scratch and is faster all the same)
 #ifndef J40_LARGE_THREADS
 #define J40_LARGE_THREADS 512
 #endif
-template <bool BATCH, bool REG64, OutMode OUT = OutMode::RGBA8>
+template <bool BATCH, OutMode OUT = OutMode::RGBA8>
 __global__ void __launch_bounds__(J40_LARGE_THREADS) k_vardct_large(DevPlan plan_arg, const DevVarblock *list, int32_t count, float *scratch, uint8_t *rgba, size_t stride_bytes, const K2Frame *batch, const int32_t *tile_prefix, int32_t nframes,
 		int32_t class_a, int32_t class_b) {
 	const int32_t tid = threadIdx.x, nthreads = blockDim.x;
@@ -1014,40 +938,8 @@ __global__ void __launch_bounds__(J40_LARGE_THREADS) k_vardct_large(DevPlan plan
 		const int32_t R = 1 << log_rows, C = 1 << log_columns, size = R * C;
 		const ColourConsts cc = load_colour_consts(f);
 		const VbGeom g = varblock_geometry(plan, vb);
-		LargeSamples S;
-		if constexpr (REG64) {
-			WorkgroupExec ex;
-			S = large_block(ex, plan, vb, g, panels, A, B, c_half_secants);
-		} else {
-			const int32_t long_side = R > C ? R : C, vh8 = (R < C ? R : C) / 8, vw8 = long_side / 8;
-			const int32_t param_idx = vb.dctsel == 21 ? 13 : vb.dctsel <= 23 ? 14 : vb.dctsel == 24 ? 15 : 16;
-			const float *dq = plan.pool_f32 + f.dq_off[param_idx];
-			if (f.sparse_coeffs) {   // the tiles live in the HBM scratch here (stores are visible to the workgroup after a barrier + fence)
-				for (int32_t i = tid; i < size; i += nthreads) { A[i] = 0.0f; A[65536 + i] = 0.0f; A[2 * 65536 + i] = 0.0f; }
-				__threadfence_block(); __syncthreads();
-				const uint16_t *order = plan.pool_u16 + f.order_off[DEV_DCT_SELECT[vb.dctsel][2] * 3];
-				const TileMap map = {R, C, C, 0};
-				const float qbias[3] = {f.quant_bias[0], f.quant_bias[1], f.quant_bias[2]};
-				tile_scatter_events(plan, g, plan.block_events + 4 * (size_t) vb.blk, order, plan.pool_f32 + f.dq_scan_off[param_idx], size, map, A, 65536, qbias, f.quant_bias_num, tid, nthreads);
-				tile_fill_llf(plan, g, long_side, vh8, vw8, map, A, 65536, f.kx_lf, f.kb_lf, tid, nthreads);
-				__threadfence_block();
-			} else {
-				for (int32_t i = tid; i < size; i += nthreads) {
-					float v[3];
-					load_coeff3(plan, g, dq, size, i, long_side, vh8, vw8, v);
-					const int32_t r = C > R ? i / C : i % R, c = C > R ? i % C : i / R;
-					A[r * C + c] = v[0]; A[65536 + r * C + c] = v[1]; A[2 * 65536 + r * C + c] = v[2];
-				}
-			}
-			__syncthreads();
-			for (int ch = 0; ch < 3; ++ch) {
-				idct_panels(A + ch * 65536, B + ch * 65536, log_columns, R, 1, C, panels);   // along c for every r: A -> B
-				__threadfence_block(); __syncthreads();
-				idct_panels(B + ch * 65536, A + ch * 65536, log_rows, C, C, 1, panels);      // along r for every x: B -> A
-			}
-			__threadfence_block(); __syncthreads();
-			for (int ch = 0; ch < 3; ++ch) { S.p[ch] = A + ch * 65536; S.pitch[ch] = C; }
-		}
+		WorkgroupExec ex;
+		const LargeSamples S = large_block(ex, plan, vb, g, panels, A, B, c_half_secants);
 		for (int32_t i = tid; i < size; i += nthreads) {
 			const int32_t y = i >> log_columns, x = i & (C - 1);
 			if (y >= g.effh || x >= g.effw) continue;
@@ -1066,7 +958,7 @@ __global__ void __launch_bounds__(J40_LARGE_THREADS) k_vardct_large(DevPlan plan
 
 // does launch_hf_entropy take the fast path (k_hf_entropy_fast) for this frame?
 bool hf_entropy_fast_path(const DevPlan &plan, const HfLaunchInfo &info) {
-	static const bool allowed = [] { const char *e = getenv("J40HIP_K1_FAST"); return !e || atoi(e) != 0; }();
+	static const bool allowed = env_on("J40HIP_K1_FAST", true);   // (=0: never)
 	auto align16 = [](uint32_t v) { return (v + 15u) & ~15u; };
 	const uint32_t tables = align16(align16(info.max_num_dist) + info.max_table_bytes), wave_bytes = align16(32 * 32 * 3 + 1024 * (uint32_t) sizeof(DevGroupBlock));
 	return allowed && info.lanes_fast && plan.events && info.max_clusters <= 64 && tables + HF_WAVES * wave_bytes <= 150u * 1024u;
@@ -1111,17 +1003,8 @@ void launch_hf_entropy(const DevPlan &plan, const HfLaunchInfo &info, int32_t fi
 	if (num_groups <= 0) return;
 	HfLdsLayout lay;
 	auto align16 = [](uint32_t v) { return (v + 15u) & ~15u; };
-	{
-		// single-pass frames (sparse coefficients) with the throughput kernel's kind of tables: the fast path (J40HIP_K1_FAST=0: never)
-		static const bool allowed = [] { const char *e = getenv("J40HIP_K1_FAST"); return !e || atoi(e) != 0; }();
-		const uint32_t tables = align16(align16(info.max_num_dist) + info.max_table_bytes), wave_bytes = align16(32 * 32 * 3 + 1024 * (uint32_t) sizeof(DevGroupBlock));
-		if (allowed && info.lanes_fast && plan.events && info.max_clusters <= 64 && tables + HF_WAVES * wave_bytes <= 150u * 1024u) {
-			static bool configured = false;
-			if (!configured) { (void) hipFuncSetAttribute((const void *) k_hf_entropy_fast, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); configured = true; }
-			hipLaunchKernelGGL(k_hf_entropy_fast, dim3((unsigned) ((num_groups + HF_WAVES - 1) / HF_WAVES)), dim3(64 * HF_WAVES), tables + HF_WAVES * wave_bytes, stream, plan, first_group, num_groups, tables, wave_bytes, (const uint32_t *) nullptr);
-			return;
-		}
-	}
+	// single-pass frames (sparse coefficients) with the throughput kernel's kind of tables: the fast path
+	if (hf_entropy_fast_path(plan, info)) { launch_hf_entropy_fast_ordered(plan, info, nullptr, first_group, num_groups, stream); return; }
 	uint32_t off = 0;
 	lay.off_bctx = off; off = align16(off + info.block_ctx_size);
 	lay.off_nnz = off; off += 128;
@@ -1167,18 +1050,15 @@ static void launch_dct(const DevPlan &plan, const DevVarblock *list, int32_t cou
 	else hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, false>), dim3((unsigned) blocks), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, nullptr, 1, 0, 0);
 }
 
-// J40HIP_K2_WIDE: bit 0: the batched 8x8 DCT takes 32 blocks per workgroup instead of 16, bit 1: 16x8 / 8x16 take 16 instead of 8 (experiments)
-static int k2_wide() { static const int v = [] { const char *e = getenv("J40HIP_K2_WIDE"); return e ? atoi(e) : 0; }(); return v; }
-
 // list = varblocks of one DctSelect value (of a run of values for the 8x8 specials and for the 128/256-sized transforms)
 static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
 	if (count <= 0 && !bl.batch) return;
 	switch (dctsel) {
-	case 0: if (bl.batch && (k2_wide() & 1)) launch_dct<3, 3, 32>(plan, list, count, 0, 0, rgba, stride, bl, stream); else launch_dct<3, 3, 16>(plan, list, count, 0, 0, rgba, stride, bl, stream); break;
+	case 0: launch_dct<3, 3, 16>(plan, list, count, 0, 0, rgba, stride, bl, stream); break;
 	case 4: launch_dct<4, 4, 8>(plan, list, count, 4, 2, rgba, stride, bl, stream); break;
 	case 5: launch_dct<5, 5, 2>(plan, list, count, 5, 3, rgba, stride, bl, stream); break;
-	case 6: if (bl.batch && (k2_wide() & 2)) launch_dct<4, 3, 16>(plan, list, count, 6, 4, rgba, stride, bl, stream); else launch_dct<4, 3, 8>(plan, list, count, 6, 4, rgba, stride, bl, stream); break;
-	case 7: if (bl.batch && (k2_wide() & 2)) launch_dct<3, 4, 16>(plan, list, count, 6, 4, rgba, stride, bl, stream); else launch_dct<3, 4, 8>(plan, list, count, 6, 4, rgba, stride, bl, stream); break;
+	case 6: launch_dct<4, 3, 8>(plan, list, count, 6, 4, rgba, stride, bl, stream); break;
+	case 7: launch_dct<3, 4, 8>(plan, list, count, 6, 4, rgba, stride, bl, stream); break;
 	case 8: launch_dct<5, 3, 4>(plan, list, count, 7, 5, rgba, stride, bl, stream); break;
 	case 9: launch_dct<3, 5, 4>(plan, list, count, 7, 5, rgba, stride, bl, stream); break;
 	case 10: launch_dct<5, 4, 4>(plan, list, count, 8, 6, rgba, stride, bl, stream); break;
@@ -1201,26 +1081,20 @@ static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const 
 			constexpr size_t lds_bytes = 2 * (size_t) LARGE_PANEL_FLOATS * sizeof(float);
 			static bool configured = false;
 			if (!configured) {
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, true, OutMode::XYB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, true, OutMode::RGBA16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
+				(void) hipFuncSetAttribute((const void *) k_vardct_large<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
+				(void) hipFuncSetAttribute((const void *) k_vardct_large<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
+				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, OutMode::XYB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
+				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, OutMode::RGBA16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
 				configured = true;
 			}
-			// (J40HIP_LARGE_IDCT=sweeps: round 3's kernel, every butterfly level as a sweep over an LDS panel -- kept for comparison)
-			static const bool reg64 = [] { const char *e = getenv("J40HIP_LARGE_IDCT"); return !(e && !strcmp(e, "sweeps")); }();
 			if (bl.batch) {
-				if (reg64) hipLaunchKernelGGL((k_vardct_large<true, true>), dim3((unsigned) bl.grid), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
-				else hipLaunchKernelGGL((k_vardct_large<true, false>), dim3((unsigned) bl.grid), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
+				hipLaunchKernelGGL((k_vardct_large<true>), dim3((unsigned) bl.grid), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
 			} else if (bl.out == OutMode::XYB) {
-				hipLaunchKernelGGL((k_vardct_large<false, true, OutMode::XYB>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
-			} else if (bl.out == OutMode::RGBA16) {   // (the LDS form of the transforms, as XYB: same values as the sweeps)
-				hipLaunchKernelGGL((k_vardct_large<false, true, OutMode::RGBA16>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
+				hipLaunchKernelGGL((k_vardct_large<false, OutMode::XYB>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
+			} else if (bl.out == OutMode::RGBA16) {
+				hipLaunchKernelGGL((k_vardct_large<false, OutMode::RGBA16>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
 			} else {
-				if (reg64) hipLaunchKernelGGL((k_vardct_large<false, true>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
-				else hipLaunchKernelGGL((k_vardct_large<false, false>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
+				hipLaunchKernelGGL((k_vardct_large<false>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
 			}
 		}
 		break;
@@ -1287,10 +1161,7 @@ void launch_vardct_frame_xyb(const DevPlan &plan, const int32_t *class_start, co
 	{18, 19, 1, 64}, {19, 20, 1, 32}, {20, 21, 1, 32}, {21, 27, 1, 128}
 struct K2BatchLaunch { int16_t a, b, per_wg, min_cells; };
 struct K2Table { K2BatchLaunch l[K2_NUM_BATCH_LAUNCHES]; };
-static const K2Table &k2_table() {
-	static const K2Table t = [] { K2Table t = {{J40_K2_LAUNCH_TABLE}}; if (k2_wide() & 1) t.l[0].per_wg = 32; if (k2_wide() & 2) t.l[5].per_wg = t.l[6].per_wg = 16; return t; }();
-	return t;
-}
+static const K2Table K2_TABLE = {{J40_K2_LAUNCH_TABLE}};
 
 // tile_prefix[l * (nframes + 1) + f] = tiles of launch l in the frames before f; totals[l] = all of them; one thread per launch
 __global__ void k_k2_tiles(const K2Frame *frames, int32_t nframes, int32_t *tile_prefix, int32_t *totals, K2Table table) {
@@ -1316,16 +1187,11 @@ __global__ void k_k2_tiles(const K2Frame *frames, int32_t nframes, int32_t *tile
 // to the classes' work were measured: 176 ms per 256 frames against 81 -- only four kernels ran at a time, each with a fraction of
 // the machine.)
 // (the second launch of the specials goes behind the 8x8 DCT: beside the first it made its chain the longest by 15 ms, alone at the
-// end with two workgroups per compute unit. J40HIP_K2_CHAINS=<16 digits>: another assignment, for experiments)
-static const int8_t *k2_launch_stream() {
-	static int8_t chain[K2_NUM_BATCH_LAUNCHES] = {0, 1, 0, 1, 2, 3, 3, 2, 3, 3, 3, 3, 2, 2, 2, 2};
-	static const bool once = [] { const char *e = getenv("J40HIP_K2_CHAINS"); if (e && strlen(e) == K2_NUM_BATCH_LAUNCHES) for (int i = 0; i < K2_NUM_BATCH_LAUNCHES; ++i) chain[i] = (int8_t) ((e[i] - '0') & 3); return true; }();
-	(void) once;
-	return chain;
-}
+// end with two workgroups per compute unit)
+static constexpr int8_t K2_LAUNCH_STREAM[K2_NUM_BATCH_LAUNCHES] = {0, 1, 0, 1, 2, 3, 3, 2, 3, 3, 3, 3, 2, 2, 2, 2};
 void k2_batch_grids(const int32_t *last_totals, size_t cells_total, int32_t nframes, int32_t wg_slots, int32_t *grids) {
 	for (int l = 0; l < K2_NUM_BATCH_LAUNCHES; ++l) {
-		const auto &L = k2_table().l[l];
+		const auto &L = K2_TABLE.l[l];
 		const size_t bound = last_totals ? (size_t) last_totals[l] + (size_t) last_totals[l] / 4 + 8 : cells_total / (size_t) (L.min_cells * L.per_wg) + (size_t) nframes;   // tiles, about
 		int64_t g = std::min<int64_t>((int64_t) bound, wg_slots);
 		// (the 128/256-sized transforms' workgroups want 133 KB of LDS each: a launch waits for compute units to drain even when it
@@ -1339,11 +1205,11 @@ void k2_batch_grids(const int32_t *last_totals, size_t cells_total, int32_t nfra
 // them); totals_dev: K2_NUM_BATCH_LAUNCHES ints, the tiles each launch found
 void launch_vardct_batch(const K2Frame *frames_dev, int32_t nframes, int32_t *tile_prefix_dev, int32_t *totals_dev, const int32_t *grids, float *large_scratch, hipStream_t stream, hipStream_t *side, int nside, hipEvent_t fork, hipEvent_t *side_done) {
 	const DevPlan none = DevPlan();
-	hipLaunchKernelGGL(k_k2_tiles, dim3(1), dim3(32), 0, stream, frames_dev, nframes, tile_prefix_dev, totals_dev, k2_table());
+	hipLaunchKernelGGL(k_k2_tiles, dim3(1), dim3(32), 0, stream, frames_dev, nframes, tile_prefix_dev, totals_dev, K2_TABLE);
 	if (nside > 0) { (void) hipEventRecord(fork, stream); for (int k = 0; k < nside; ++k) (void) hipStreamWaitEvent(side[k], fork, 0); }
 	for (int l = 0; l < K2_NUM_BATCH_LAUNCHES; ++l) {
-		const auto &L = k2_table().l[l];
-		launch_vardct_class_impl(none, L.a, nullptr, 0, large_scratch, nullptr, 0, K2Launch{frames_dev, tile_prefix_dev + (size_t) l * (size_t) (nframes + 1), nframes, L.a, L.b, grids[l], OutMode::RGBA8}, nside > 0 ? side[k2_launch_stream()[l] % nside] : stream);
+		const auto &L = K2_TABLE.l[l];
+		launch_vardct_class_impl(none, L.a, nullptr, 0, large_scratch, nullptr, 0, K2Launch{frames_dev, tile_prefix_dev + (size_t) l * (size_t) (nframes + 1), nframes, L.a, L.b, grids[l], OutMode::RGBA8}, nside > 0 ? side[K2_LAUNCH_STREAM[l] % nside] : stream);
 	}
 	if (nside > 0) for (int k = 0; k < nside; ++k) { (void) hipEventRecord(side_done[k], side[k]); (void) hipStreamWaitEvent(stream, side_done[k], 0); }
 }

@@ -13,6 +13,7 @@
 #include "lf_lanes_dev.h"
 #include "lf_rows_dev.h"
 #include "kernels.h"
+#include "../env.hpp"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -38,7 +39,7 @@ __global__ void __launch_bounds__(64) k_lf_groups(const DevLfTask *tasks) {
 	int32_t nb_varblocks = 0;
 	// the LF coefficient image
 	for (int32_t c = 0; c < 3 && !b.err && !err; ++c)
-		coop_decode_channel<0, true>(b, state, err, t, alias, log_bucket, c, sidx0, c == 0 ? lf_out[0] : c == 1 ? lf_out[1] : lf_out[2], w8, w8, h8, nullptr, 0, lane);
+		coop_decode_channel<true>(b, state, err, t, alias, log_bucket, c, sidx0, c == 0 ? lf_out[0] : c == 1 ? lf_out[1] : lf_out[2], w8, w8, h8, nullptr, 0, lane);
 	status = b.err ? b.err : err;
 	if (!status) status = coop_finish_code(b, state, lane);
 	if (!status) {
@@ -50,10 +51,10 @@ __global__ void __launch_bounds__(64) k_lf_groups(const DevLfTask *tasks) {
 	}
 	if (!status) {   // the HF metadata image
 		state = 0;
-		coop_decode_channel<0, true>(b, state, err, t, alias, log_bucket, 0, sidx2, out_xfromy, w64, w64, h64, nullptr, 0, lane);
-		if (!b.err && !err) coop_decode_channel<0, true>(b, state, err, t, alias, log_bucket, 1, sidx2, out_bfromy, w64, w64, h64, nullptr, 0, lane);
-		if (!b.err && !err) coop_decode_channel<0, true>(b, state, err, t, alias, log_bucket, 2, sidx2, out_info, nb_varblocks, nb_varblocks, 2, nullptr, 0, lane);
-		if (!b.err && !err) coop_decode_channel<0, true>(b, state, err, t, alias, log_bucket, 3, sidx2, out_sharp, w8, w8, h8, nullptr, 0, lane);
+		coop_decode_channel<true>(b, state, err, t, alias, log_bucket, 0, sidx2, out_xfromy, w64, w64, h64, nullptr, 0, lane);
+		if (!b.err && !err) coop_decode_channel<true>(b, state, err, t, alias, log_bucket, 1, sidx2, out_bfromy, w64, w64, h64, nullptr, 0, lane);
+		if (!b.err && !err) coop_decode_channel<true>(b, state, err, t, alias, log_bucket, 2, sidx2, out_info, nb_varblocks, nb_varblocks, 2, nullptr, 0, lane);
+		if (!b.err && !err) coop_decode_channel<true>(b, state, err, t, alias, log_bucket, 3, sidx2, out_sharp, w8, w8, h8, nullptr, 0, lane);
 		status = b.err ? b.err : err;
 		if (!status) status = coop_finish_code(b, state, lane);
 	}
@@ -61,8 +62,7 @@ __global__ void __launch_bounds__(64) k_lf_groups(const DevLfTask *tasks) {
 }
 
 // One LfGroup section per LANE (lf_lanes_dev.h); a wavefront takes the sections of several frames (DevLfWave), each frame's tree and
-// small code tables staged in LDS, every lane pointing at its own frame's copy. ALIAS_LDS: the alias tables as well.
-template <bool ALIAS_LDS>
+// small code tables staged in LDS, every lane pointing at its own frame's copy (the alias tables stay in global memory: lf_lanes_dev.h).
 __global__ void __launch_bounds__(64) k_lf_lanes(const DevLfLaneSet *sets, const DevLfWave *waves) {
 	extern __shared__ __attribute__((aligned(16))) uint8_t lfl_lds[];
 	const J40_GLOBAL DevLfWave &wv = ((const J40_GLOBAL DevLfWave *) waves)[blockIdx.x];
@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(64) k_lf_lanes(const DevLfLaneSet *sets, const
 	J40_LDS uint8_t *lds = (J40_LDS uint8_t *) lfl_lds;
 	// this lane's section and tables
 	const J40_GLOBAL DevLfTask *task = nullptr;
-	LfLaneTablesT<ALIAS_LDS> T;
+	LfLaneTables T;
 	T.ctx_map = nullptr; T.cluster_cfg = nullptr; T.alias = nullptr; T.log_alpha = 5; T.log_bucket = 7;
 	LfLaneFrame F;
 	F.tree = nullptr; F.uses = 0;
@@ -83,7 +83,6 @@ __global__ void __launch_bounds__(64) k_lf_lanes(const DevLfLaneSet *sets, const
 		J40_LDS int32_t *l_tree = (J40_LDS int32_t *) (lds + at);
 		J40_LDS uint8_t *l_map = lds + at + align16(16u * (uint32_t) num_nodes);
 		J40_LDS uint32_t *l_cfg = (J40_LDS uint32_t *) (l_map + align16((uint32_t) num_dist));
-		J40_LDS uint64_t *l_alias = (J40_LDS uint64_t *) ((J40_LDS uint8_t *) l_cfg + align16(4u * (uint32_t) num_clusters));
 		{
 			const J40_GLOBAL int32_t *tsrc = (const J40_GLOBAL int32_t *) set.tree;
 			for (int32_t i = lane; i < 4 * num_nodes; i += 64) l_tree[i] = tsrc[i];
@@ -91,19 +90,15 @@ __global__ void __launch_bounds__(64) k_lf_lanes(const DevLfLaneSet *sets, const
 			for (int32_t i = lane; i < num_dist; i += 64) l_map[i] = msrc[i];
 			const J40_GLOBAL uint32_t *csrc = (const J40_GLOBAL uint32_t *) set.cluster_cfg;
 			for (int32_t i = lane; i < num_clusters; i += 64) l_cfg[i] = csrc[i];
-			if constexpr (ALIAS_LDS) {
-				const J40_GLOBAL uint64_t *asrc = (const J40_GLOBAL uint64_t *) set.alias;
-				for (int32_t i = lane; i < (num_clusters << log_alpha); i += 64) l_alias[i] = asrc[i];
-			}
 		}
 		if (lane >= lane0 && lane < lane0 + count) {
 			task = (const J40_GLOBAL DevLfTask *) set.tasks + (first + lane - lane0);
 			T.ctx_map = l_map; T.cluster_cfg = l_cfg; T.log_alpha = log_alpha; T.log_bucket = 12 - log_alpha;
-			if constexpr (ALIAS_LDS) T.alias = l_alias; else T.alias = (const J40_GLOBAL uint64_t *) set.alias;
+			T.alias = (const J40_GLOBAL uint64_t *) set.alias;
 			F.tree = (const J40_LDS DevTreeNode *) l_tree; F.uses = set.uses;
 		}
 		lane0 += count;
-		at += align16(set.lds_bytes) + (ALIAS_LDS ? 8u * ((uint32_t) num_clusters << log_alpha) : 0u);
+		at += align16(set.lds_bytes);
 	}
 	__syncthreads();
 	const bool active = task != nullptr;
@@ -329,23 +324,15 @@ __global__ void __launch_bounds__(64) k_lf_predict(const DevLfLaneSet *sets, con
 	}
 }
 
-// J40HIP_LF_ALIAS_LDS=1: the alias tables staged in LDS too (frames whose tables do not fit: the host decodes their sections)
-bool lf_lanes_alias_in_lds() {
-	static const bool v = [] { const char *e = getenv("J40HIP_LF_ALIAS_LDS"); return e && atoi(e) != 0; }();
-	return v;
-}
-
 // packs the sections of `sets` into wavefronts (host side): fills `waves`, returns the LDS bytes a wavefront needs at most
 uint32_t pack_lf_waves(const DevLfLaneSet *sets_host, int32_t num_sets, std::vector<DevLfWave> *waves, const std::vector<int32_t> *only) {
-	// (J40HIP_LF_LDS_KB: the LDS a wavefront's frames may take together -- with the alias tables in LDS, 30 keeps it to one 8K frame per
-	// wavefront and two such workgroups beside a coefficient decoder's 99 KB on a compute unit)
-	static const uint32_t budget = [] { const char *e = getenv("J40HIP_LF_LDS_KB"); return (e && atoi(e) > 0 ? (uint32_t) atoi(e) : 56u) * 1024u; }();
+	const uint32_t budget = LF_LANES_LDS_BUDGET;   // what a wavefront's frames may take together
 	uint32_t most = 0, used = 0; int32_t lanes = 0;
 	DevLfWave cur; memset(&cur, 0, sizeof cur);
 	auto flush = [&] { if (cur.num_parts) { waves->push_back(cur); most = std::max(most, used); } memset(&cur, 0, sizeof cur); used = 0; lanes = 0; };
 	for (int32_t k = 0; k < (only ? (int32_t) only->size() : num_sets); ++k) {
 		const int32_t i = only ? (*only)[(size_t) k] : k;   // (`only`: just these sets -- the ones k_lf_rows could not take)
-		const uint32_t need = ((sets_host[i].lds_bytes + 15u) & ~15u) + (lf_lanes_alias_in_lds() ? 8u * ((uint32_t) sets_host[i].num_clusters << sets_host[i].log_alpha) : 0u);
+		const uint32_t need = (sets_host[i].lds_bytes + 15u) & ~15u;
 		for (int32_t first = 0; first < sets_host[i].ntasks; ) {
 			if (lanes >= 64 || cur.num_parts >= LF_WAVE_PARTS || (cur.num_parts && used + need > budget)) flush();
 			const int32_t count = std::min(64 - lanes, sets_host[i].ntasks - first);
@@ -360,16 +347,15 @@ uint32_t pack_lf_waves(const DevLfLaneSet *sets_host, int32_t num_sets, std::vec
 void launch_lf_lanes(const DevLfLaneSet *sets, const DevLfWave *waves, int32_t num_waves, uint32_t lds_bytes, hipStream_t stream, hipEvent_t started, hipEvent_t stopped) {
 	if (num_waves <= 0) return;
 	static bool configured = false;
-	if (!configured) { (void) hipFuncSetAttribute((const void *) k_lf_lanes<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); (void) hipFuncSetAttribute((const void *) k_lf_lanes<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); configured = true; }
-	if (lf_lanes_alias_in_lds()) hipLaunchKernelGGL(k_lf_lanes<true>, dim3((unsigned) num_waves), dim3(64), lds_bytes, stream, sets, waves);
-	else if (started || stopped) hipExtLaunchKernelGGL(k_lf_lanes<false>, dim3((unsigned) num_waves), dim3(64), lds_bytes, stream, started, stopped, 0, sets, waves);
-	else hipLaunchKernelGGL(k_lf_lanes<false>, dim3((unsigned) num_waves), dim3(64), lds_bytes, stream, sets, waves);
+	if (!configured) { (void) hipFuncSetAttribute((const void *) k_lf_lanes, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); configured = true; }
+	if (started || stopped) hipExtLaunchKernelGGL(k_lf_lanes, dim3((unsigned) num_waves), dim3(64), lds_bytes, stream, started, stopped, 0, sets, waves);
+	else hipLaunchKernelGGL(k_lf_lanes, dim3((unsigned) num_waves), dim3(64), lds_bytes, stream, sets, waves);
 }
 
 // J40HIP_LF_KERNEL=lanes: the older decoder (alias entries and rows in global memory) for every launch; default: k_lf_rows, for
 // every frame whose tables fit its LDS budget
 static int lf_rows_mode() {
-	static const int v = [] { const char *e = getenv("J40HIP_LF_KERNEL"); return e && strcmp(e, "lanes") == 0 ? 0 : 1; }();
+	static const int v = [] { const char *e = env_str("J40HIP_LF_KERNEL"); return e && strcmp(e, "lanes") == 0 ? 0 : 1; }();
 	return v;
 }
 bool lf_rows_enabled() { return lf_rows_mode() != 0; }
@@ -379,7 +365,7 @@ bool lf_rows_enabled() { return lf_rows_mode() != 0; }
 // wavefront's tables and windows may take together (default 48: one 8K frame of seven clusters x 256 buckets -- 28.5 KB of tables + 12 windows =
 // 35 KB -- so that such a workgroup still fits beside the coefficient decoder's 99 KB on a compute unit)
 uint32_t pack_lf_row_waves(const DevLfLaneSet *sets_host, int32_t num_sets, std::vector<DevLfWave> *waves, std::vector<int32_t> *oversized) {
-	static const uint32_t budget = [] { const char *e = getenv("J40HIP_LF_ROWS_LDS_KB"); return (e && atoi(e) > 0 ? (uint32_t) atoi(e) : 48u) * 1024u; }();
+	static const uint32_t budget = [] { const int kb = env_int("J40HIP_LF_ROWS_LDS_KB", 0, 0, 1 << 20); return (kb > 0 ? (uint32_t) kb : 48u) * 1024u; }();
 	const uint32_t win_bytes = 2u * LF_ROW_PITCH;
 	uint32_t most = 0, used = 0; int32_t lanes = 0;
 	DevLfWave cur; memset(&cur, 0, sizeof cur);
@@ -404,7 +390,7 @@ uint32_t pack_lf_row_waves(const DevLfLaneSet *sets_host, int32_t num_sets, std:
 
 // J40HIP_LF_RAW=0: every channel predicted by the lane that parses it, as before round 6 (A/B runs, tests)
 static bool lf_rows_raw() {
-	static const bool v = [] { const char *e = getenv("J40HIP_LF_RAW"); return !(e && atoi(e) == 0 && e[0] != 0); }();
+	static const bool v = env_on("J40HIP_LF_RAW", true);
 	return v;
 }
 // k_lf_rows, then -- when it leaves leaf-only channels as residuals -- k_lf_predict; `started` / `stopped`: the device's clock before

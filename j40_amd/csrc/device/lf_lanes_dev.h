@@ -25,16 +25,10 @@ namespace j40hip {
 // the alias tables (num_clusters << log_alpha entries of 8 bytes: 14 KB for seven clusters of 256 buckets) are read where the
 // host put them: staged in LDS they let a wavefront hold three frames (36 of 64 lanes), and two such workgroups on a compute
 // unit left no room for the coefficient decoder's (k_hf_lanes, 99 KB), which then ran its workgroups in two rounds.
-template <bool ALIAS_LDS> struct LfLaneTablesT {
+struct LfLaneTables {
 	const J40_LDS uint8_t *ctx_map;
 	const J40_LDS uint32_t *cluster_cfg;
 	const J40_GLOBAL uint64_t *alias;
-	int32_t log_alpha, log_bucket;
-};
-template <> struct LfLaneTablesT<true> {
-	const J40_LDS uint8_t *ctx_map;
-	const J40_LDS uint32_t *cluster_cfg;
-	const J40_LDS uint64_t *alias;
 	int32_t log_alpha, log_bucket;
 };
 

@@ -24,9 +24,6 @@
 
 namespace j40hip {
 
-// MODE 0: neighbours, properties and prediction on the vector ALU; MODE 1: neighbours and prediction on the scalar unit, only the
-// fifteen property values (which feed per-lane selects anyway) on the vector ALU
-template <int MODE>
 __global__ void __launch_bounds__(64) k_modular_coop(DevModPlan plan, int32_t first_section, int32_t rows_width) {
 	extern __shared__ int32_t coop_rows[];   // [3][rows_width]: the three most recent rows of the channel being decoded
 	const uint32_t lane = threadIdx.x;
@@ -49,7 +46,7 @@ __global__ void __launch_bounds__(64) k_modular_coop(DevModPlan plan, int32_t fi
 		const ModChan chan = mod_channel(plan, sec, cidx);
 		const int32_t stride = coop_sc(chan.stride), gw = coop_sc(chan.gw), gh = coop_sc(chan.gh);
 		if (gw <= 0 || gh <= 0) continue;
-		coop_decode_channel<MODE>(b, state, err, t, alias, log_bucket, cidx, sidx, coop_sc_ptr(chan.base), stride, gw, gh, coop_rows, rows_width, lane);
+		coop_decode_channel(b, state, err, t, alias, log_bucket, cidx, sidx, coop_sc_ptr(chan.base), stride, gw, gh, coop_rows, rows_width, lane);
 	}
 	uint32_t status = b.err ? b.err : err;
 	if (!status) status = coop_finish_code(b, state, lane);
@@ -66,9 +63,7 @@ __global__ void __launch_bounds__(64) k_modular_coop(DevModPlan plan, int32_t fi
 void launch_modular_coop(const DevModPlan &plan, int32_t first_section, int32_t num_sections, int32_t max_width, hipStream_t stream) {
 	if (num_sections <= 0) return;
 	const int32_t rows_width = ((max_width + 63) & ~63) + 64;
-	static const int mode = [] { const char *e = getenv("J40HIP_COOP_MODE"); return e ? atoi(e) : 0; }();
-	if (mode == 1) hipLaunchKernelGGL(k_modular_coop<1>, dim3((unsigned) num_sections), dim3(64), (size_t) rows_width * 12, stream, plan, first_section, rows_width);
-	else hipLaunchKernelGGL(k_modular_coop<0>, dim3((unsigned) num_sections), dim3(64), (size_t) rows_width * 12, stream, plan, first_section, rows_width);
+	hipLaunchKernelGGL(k_modular_coop, dim3((unsigned) num_sections), dim3(64), (size_t) rows_width * 12, stream, plan, first_section, rows_width);
 }
 
 } // namespace j40hip

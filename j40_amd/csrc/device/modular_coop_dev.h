@@ -96,10 +96,10 @@ J40_DEV CoopTreeRegs coop_load_tree(const DevCoopTree *tree, uint32_t lane) {
 
 // One channel (gw x gh samples, rows `stride` apart at `base`) of the stream `b` / `state`, decoded by the whole wavefront.
 // coop_rows: [3][rows_width] int32 in LDS, rows_width >= align64(gw) + 64. Every argument but `t`'s per-lane members and `lane`
-// is wave-uniform. MODE: see k_modular_coop. PLANE_ROWS: the two rows above are read back from the output plane (coalesced
+// is wave-uniform. PLANE_ROWS: the two rows above are read back from the output plane (coalesced
 // 128-byte pieces, once per 64 samples) instead of an LDS ring -- for channels too wide for LDS (the varblock-info channel of an
 // LfGroup is two rows of up to 65536 samples); coop_rows is then unused.
-template <int MODE, bool PLANE_ROWS = false>
+template <bool PLANE_ROWS = false>
 J40_DEV void coop_decode_channel(CoopBits &b, uint32_t &state, uint32_t &err, const CoopTreeRegs &t, CoopConstU64 alias, int32_t log_bucket,
 		int32_t cidx, int32_t sidx, int16_t *base, int32_t stride, int32_t gw, int32_t gh, int32_t *coop_rows, int32_t rows_width, uint32_t lane) {
 	const uint32_t used = t.used;
@@ -127,7 +127,7 @@ J40_DEV void coop_decode_channel(CoopBits &b, uint32_t &state, uint32_t &err, co
 				// does as soon as the column index and the values read from the rows are not known to be uniform. The
 				// entropy side (rANS state, bit accumulator, hybrid integer) stays on the scalar unit.
 				int32_t x = xb + i, vnn = coop_rl(vpp, i), r_next = i + 3 < 64 ? coop_rl(vprev, i + 3) : coop_rl(vprev2, i + 3 - 64);
-				if (MODE == 0) { asm("" : "+v"(x)); asm("" : "+v"(vnn)); asm("" : "+v"(r_next)); }
+				asm("" : "+v"(x)); asm("" : "+v"(vnn)); asm("" : "+v"(r_next));
 				const int32_t pw = x > 0 ? c_w : y > 0 ? r_n : 0;
 				const int32_t pn = y > 0 ? r_n : pw;
 				const int32_t pnw = x > 0 && y > 0 ? r_nw : pw;
@@ -137,8 +137,7 @@ J40_DEV void coop_decode_channel(CoopBits &b, uint32_t &state, uint32_t &err, co
 				const int32_t pww = x > 1 ? c_ww : pw;
 				const int32_t pnww = x > 1 && y > 0 ? r_nww : pww;
 				// every branch's outcome: the value of the property this lane's node tests (j40.h:4141-4155), then one compare
-				int32_t qx = x, qw = pw, qn = pn, qnw = pnw, qne = pne, qnn = pnn, qww = pww, qnww = pnww;
-				if (MODE == 1) { asm("" : "+v"(qx)); asm("" : "+v"(qw)); asm("" : "+v"(qn)); asm("" : "+v"(qnw)); asm("" : "+v"(qne)); asm("" : "+v"(qnn)); asm("" : "+v"(qww)); asm("" : "+v"(qnww)); }
+				const int32_t qx = x, qw = pw, qn = pn, qnw = pnw, qne = pne, qnn = pnn, qww = pww, qnww = pnww;
 				int32_t myval = 0;
 				if (used & (1u << 0)) myval = t.my_prop == 0 ? cidx : myval;
 				if (used & (1u << 1)) myval = t.my_prop == 1 ? sidx : myval;

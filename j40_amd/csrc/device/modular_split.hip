@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "modular_split_dev.h"
 #include "kernels.h"
+#include "../env.hpp"
 
 namespace j40hip {
 
@@ -284,7 +285,7 @@ __global__ void k_modular_split_status(DevModPlan plan, int32_t first_section, i
 
 void launch_modular_split(const DevModPlan &plan, int32_t first_section, int32_t num_sections, const ModLaunchInfo &info, hipStream_t stream) {
 	if (num_sections <= 0 || info.split_sections <= 0) return;
-	static const bool once = [] { const char *e = getenv("J40HIP_SPLIT_NO_FAST"); const bool v = e && atoi(e) != 0; if (v) (void) hipMemcpyToSymbol(HIP_SYMBOL(g_split_no_fast), &v, sizeof v); return true; }();
+	static const bool once = [] { const bool v = env_on("J40HIP_SPLIT_NO_FAST", false); if (v) (void) hipMemcpyToSymbol(HIP_SYMBOL(g_split_no_fast), &v, sizeof v); return true; }();
 	(void) once;
 	auto align16 = [](uint32_t v) { return (v + 15u) & ~15u; };
 	const uint32_t lds = align16((uint32_t) info.num_tree_nodes * (uint32_t) sizeof(DevTreeNode)) + align16((uint32_t) info.num_dist + 4)

@@ -139,7 +139,6 @@ struct j40hip_pipeline {
 	std::deque<int> in_flight;          // slot indices, oldest first
 	hipStream_t copy_stream = nullptr;  // every copy of pixels back to host memory, in launch order: one DMA queue at the link's rate
 	bool sdma_copies = false;           // host output goes back on the SDMA engine measured for the device (hostcopy.hpp)
-	std::vector<hipStream_t> copy_streams;   // copy_stream first; J40HIP_COPY_STREAMS=n: the groups of a batch's copies go to n streams in turn
 	// device images for host output, recycled by size
 	std::mutex image_m;
 	std::vector<std::pair<void *, size_t>> free_images;
@@ -289,7 +288,7 @@ void worker_main(j40hip_pipeline *p, int) {
 		lock.unlock();
 		post_ms += now_ms() - t2; busy_ms += t2 - t0; ++nframes;
 	}
-	if (getenv("J40HIP_ASYNC_TIMING") && nframes) fprintf(stderr, "[j40hip worker] %lld frames, ms per frame: waiting for a job %.2f, working %.2f, handing over %.2f\n", (long long) nframes, wait_ms / (double) nframes, busy_ms / (double) nframes, post_ms / (double) nframes);
+	if (j40hip_rt::async_timing() && nframes) fprintf(stderr, "[j40hip worker] %lld frames, ms per frame: waiting for a job %.2f, working %.2f, handing over %.2f\n", (long long) nframes, wait_ms / (double) nframes, busy_ms / (double) nframes, post_ms / (double) nframes);
 	(void) hipStreamSynchronize(stream);
 	j40hip_astage_release();
 	j40hip_thread_release();
@@ -401,7 +400,7 @@ bool progress(j40hip_pipeline *p, Slot &slot, bool block) {
 		}
 		++slot.next_group;
 	}
-	static const bool timing = getenv("J40HIP_ASYNC_TIMING") != nullptr;
+	static const bool timing = j40hip_rt::async_timing();
 	if (timing) fprintf(stderr, "[j40hip batch] %zu frames in %d groups: launched at %.1f, kernels + verdicts through after %.1f ms, last pixels back after another %.1f ms\n", slot.jobs.size(), ngroups, slot.t_launch, slot.t_harvest - slot.t_launch, now_ms() - slot.t_harvest);
 	slot.jobs.clear(); slot.group_end.clear(); slot.next_group = 0; slot.busy = false; slot.launch_err = 0; slot.failed = false; slot.harvested = false; slot.copies_deferred = false;
 	return true;
@@ -436,17 +435,16 @@ uint32_t launch_batch(j40hip_pipeline *p, std::vector<Job *> &take, int si) {
 	if (hipEventRecord(slot.kdone, slot.stream) != hipSuccess && !slot.launch_err) slot.launch_err = E_GPU;
 	const int n = (int) take.size();
 	// groups: without copies the whole batch is one group that ends with the kernels; with copies about sixteen per batch
-	static const int groups = [] { const char *e = getenv("J40HIP_COPY_GROUPS"); return e && atoi(e) > 0 ? atoi(e) : 16; }();
+	static const int groups = [] { const int v = j40hip::env_int("J40HIP_COPY_GROUPS", 0, 0, 1 << 20); return v > 0 ? v : 16; }();
 	const int per_group = host_out ? std::max(1, (n + groups - 1) / groups) : n;
 	hipStream_t gs = host_out ? p->copy_stream : slot.stream;
 	// host output: on the SDMA engine measured for this device, issued when the kernels are seen to be through (issue_copies) -- or,
-	// without it (J40HIP_COPY_ENGINE=hip, no HSA), hipMemcpyAsync on the copy stream(s) behind the batch's kernels
+	// without it (J40HIP_COPY_ENGINE=hip, no HSA), hipMemcpyAsync on the copy stream behind the batch's kernels
 	slot.copies_deferred = host_out && p->sdma_copies;
-	if (host_out && !slot.copies_deferred) for (hipStream_t cs : p->copy_streams) if (!slot.launch_err && hipStreamWaitEvent(cs, slot.kdone, 0) != hipSuccess) slot.launch_err = E_GPU;
+	if (host_out && !slot.copies_deferred && !slot.launch_err && hipStreamWaitEvent(p->copy_stream, slot.kdone, 0) != hipSuccess) slot.launch_err = E_GPU;
 	for (int i = 0; i < n; ++i) {
 		Job *j = take[(size_t) i];
 		if (slot.copies_deferred) { if ((i + 1) % per_group == 0 || i + 1 == n) slot.group_end.push_back(i + 1); continue; }
-		if (host_out) gs = p->copy_streams[slot.group_end.size() % p->copy_streams.size()];   // (a group's copies and its event on one stream)
 		if (!slot.launch_err && !j->device_output && hipMemcpyAsync(j->rgba, j->dev_rgba, j->stride * (size_t) j->height, hipMemcpyDeviceToHost, gs) != hipSuccess) j->status = E_GPU;
 		if ((i + 1) % per_group == 0 || i + 1 == n) {
 			const size_t g = slot.group_end.size();
@@ -456,7 +454,7 @@ uint32_t launch_batch(j40hip_pipeline *p, std::vector<Job *> &take, int si) {
 			slot.group_end.push_back(i + 1);
 		}
 	}
-	if (slot.launch_err) { (void) hipStreamSynchronize(slot.stream); if (host_out) for (hipStream_t cs : p->copy_streams) (void) hipStreamSynchronize(cs); }   // (whatever did get enqueued: nothing may run on memory that is handed back)
+	if (slot.launch_err) { (void) hipStreamSynchronize(slot.stream); if (host_out) (void) hipStreamSynchronize(p->copy_stream); }   // (whatever did get enqueued: nothing may run on memory that is handed back)
 	p->in_flight.push_back(si);
 	return slot.launch_err;
 }
@@ -464,7 +462,7 @@ uint32_t launch_batch(j40hip_pipeline *p, std::vector<Job *> &take, int si) {
 void gpu_main(j40hip_pipeline *p) {
 	if (hipSetDevice(p->device) != hipSuccess) { p->gpu_thread_dead = true; return; }
 	double t_lf = 0, t_launch = 0, t_retire = 0, t_idle = 0, t_lock = 0; int64_t n_launch = 0, n_lf = 0;   // (J40HIP_ASYNC_TIMING)
-	struct Report { double &a, &b, &c, &d, &e; int64_t &n, &m; ~Report() { if (getenv("J40HIP_ASYNC_TIMING")) fprintf(stderr, "[j40hip gpu thread] ms: LfGroup launches %.1f (%lld), batch launches %.1f (%lld), retiring %.1f, waiting %.1f, for the lock %.1f\n", a, (long long) m, b, (long long) n, c, d, e); } } report{t_lf, t_launch, t_retire, t_idle, t_lock, n_launch, n_lf};
+	struct Report { double &a, &b, &c, &d, &e; int64_t &n, &m; ~Report() { if (j40hip_rt::async_timing()) fprintf(stderr, "[j40hip gpu thread] ms: LfGroup launches %.1f (%lld), batch launches %.1f (%lld), retiring %.1f, waiting %.1f, for the lock %.1f\n", a, (long long) m, b, (long long) n, c, d, e); } } report{t_lf, t_launch, t_retire, t_idle, t_lock, n_launch, n_lf};
 	// slots with something to hand back, oldest first; free slots leave the list
 	auto retire_ready = [&](bool block_on_oldest) {
 		const double tr = now_ms();
@@ -616,51 +614,30 @@ j40hip_pipeline *j40hip_pipeline_create_ex(int device, int host_threads, int bat
 		p->max_in_flight = max_in_flight < 1 ? 2 : max_in_flight > 8 ? 8 : max_in_flight;
 		// (a frame in this stage holds about 12 MB of device memory; eight batches' worth, at most 2048 frames or two batches')
 		p->lf_cap = p->lf_mode == 2 ? 0 : std::min<int64_t>((int64_t) p->batch_frames * 8, std::max<int64_t>(2048, (int64_t) p->batch_frames * 2));
-		if (const char *e = getenv("J40HIP_LF_CAP")) p->lf_cap = atoll(e);
+		p->lf_cap = j40hip::env_int("J40HIP_LF_CAP", (int) p->lf_cap, INT_MIN, INT_MAX);
 		// LfGroup launches in flight at once, and frames per launch. A launch lasts 0.4-0.8 s whatever it carries and occupies a hardware
 		// queue of its own for that long; with four of them active beside the batches' streams, the pixel-kernel streams and the copy
 		// stream the process has more active queues than the device schedules at once, and the copies back -- blit kernels on their
 		// queue -- crawled (2.6-5.3 s per 256-frame batch instead of 0.6 s for the first twenty seconds of a long run, until the
 		// LfGroup stage had run ahead: DESIGN.md section 5). Two flights of up to four batches' worth each.
 		p->lf_flights_used = 2; p->lf_flight_frames = (int64_t) p->batch_frames * 4;
-		if (const char *e = getenv("J40HIP_LF_FLIGHTS")) p->lf_flights_used = std::max(1, std::min(4, atoi(e)));
-		if (const char *e = getenv("J40HIP_LF_FLIGHT_FRAMES")) p->lf_flight_frames = std::max<int64_t>(1, atoll(e));
-		if (const char *e = getenv("J40HIP_LF_WAIT_MS")) p->lf_wait_ms = std::max(0.0, atof(e));
-		if (const char *e = getenv("J40HIP_LF_WAIT_BURST")) p->lf_wait_burst = std::max(1.0, atof(e));
-		p->lf_auto_min = p->batch_frames / 4;
-		if (const char *e = getenv("J40HIP_LF_AUTO_MIN")) p->lf_auto_min = std::max<int64_t>(0, atoll(e));
+		p->lf_flights_used = j40hip::env_int("J40HIP_LF_FLIGHTS", p->lf_flights_used, 1, 4);
+		p->lf_flight_frames = j40hip::env_int("J40HIP_LF_FLIGHT_FRAMES", (int) p->lf_flight_frames, 1, INT_MAX);
+		if (const char *e = j40hip::env_str("J40HIP_LF_WAIT_MS")) p->lf_wait_ms = std::max(0.0, atof(e));
+		if (const char *e = j40hip::env_str("J40HIP_LF_WAIT_BURST")) p->lf_wait_burst = std::max(1.0, atof(e));
+		p->lf_auto_min = j40hip::env_int("J40HIP_LF_AUTO_MIN", (int) (p->batch_frames / 4), 0, INT_MAX);
 		p->slots.resize((size_t) p->max_in_flight + 1);
 		for (Slot &s : p->slots) {
 			bool made = false;
-			if (j40hip_stream_layout() == 2 && &s != &p->slots[0]) { s.stream = p->slots[0].stream; made = true; }   // layout 2: every batch on ONE stream (one after the other), the pixel-kernel streams shared as in 1
-			else if (j40hip_stream_layout() >= 1) { int lo = 0, hi = 0; made = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, hi) == hipSuccess; if (!made) (void) hipGetLastError(); }
+			// (high priority: async.hip, "How a pipeline's streams are laid over the hardware queues")
+			{ int lo = 0, hi = 0; made = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, hi) == hipSuccess; if (!made) (void) hipGetLastError(); }
 			if (!made && hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess) { *err = E_GPU; break; }
 			if (hipEventCreateWithFlags(&s.kdone, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) { *err = E_GPU; break; }
 		}
 		if (!*err) {
-			// (J40HIP_COPY_PRIORITY: low | normal | high -- which set of hardware queues the copy stream's event markers go through)
+			// (the copy stream at the middle priority: its event markers go through a set of hardware queues of their own)
 			int lo = 0, hi = 0; (void) hipDeviceGetStreamPriorityRange(&lo, &hi);
-			const char *e = getenv("J40HIP_COPY_PRIORITY");
-			const int prio = e && !strcmp(e, "low") ? lo : e && !strcmp(e, "high") ? hi : (lo + hi) / 2;
-			// (J40HIP_COPY_STREAM=mask: a stream with a CU mask -- all CUs -- has a hardware queue of its own, shared with no other stream;
-			// J40HIP_COPY_STREAMS=n: n such streams, a batch's copy groups dealt out in turn)
-			const char *kind = getenv("J40HIP_COPY_STREAM");
-			const int ncopy = [] { const char *c = getenv("J40HIP_COPY_STREAMS"); return c && atoi(c) > 0 ? std::min(8, atoi(c)) : 1; }();
-			for (int k = 0; k < ncopy && !*err; ++k) {
-				hipStream_t cs = nullptr;
-				if (kind && !strcmp(kind, "mask")) {
-					hipDeviceProp_t pr;
-					if (hipGetDeviceProperties(&pr, p->device) == hipSuccess) {
-						const int cus = pr.multiProcessorCount;
-						std::vector<uint32_t> mask((size_t) (cus + 31) / 32, 0xffffffffu);
-						if (cus % 32) mask.back() = (1u << (cus % 32)) - 1u;
-						if (hipExtStreamCreateWithCUMask(&cs, (uint32_t) mask.size(), mask.data()) != hipSuccess) { (void) hipGetLastError(); cs = nullptr; }
-					}
-				}
-				if (!cs && hipStreamCreateWithPriority(&cs, hipStreamNonBlocking, prio) != hipSuccess) { (void) hipGetLastError(); if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) *err = E_GPU; }
-				if (cs) p->copy_streams.push_back(cs);
-			}
-			if (!p->copy_streams.empty()) p->copy_stream = p->copy_streams[0];
+			if (hipStreamCreateWithPriority(&p->copy_stream, hipStreamNonBlocking, (lo + hi) / 2) != hipSuccess) { (void) hipGetLastError(); if (hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking) != hipSuccess) *err = E_GPU; }
 			p->sdma_copies = j40hip_rt::hostcopy_engine(p->device, nullptr, nullptr) >= 0;   // (measures the engines on the process's first pipeline)
 		}
 		{   // The LfGroup launches run for a quarter of a second each. Streams of one priority share a handful of hardware queues, and a
@@ -703,9 +680,9 @@ void j40hip_pipeline_free(j40hip_pipeline *p) {
 	for (Slot &s : p->slots) {
 		for (hipEvent_t e : s.group_ev) if (e) (void) hipEventDestroy(e);
 		if (s.kdone) (void) hipEventDestroy(s.kdone);
-		if (s.stream && (&s == &p->slots[0] || s.stream != p->slots[0].stream)) (void) hipStreamDestroy(s.stream);
+		if (s.stream) (void) hipStreamDestroy(s.stream);
 	}
-	for (hipStream_t cs : p->copy_streams) if (cs) (void) hipStreamDestroy(cs);
+	if (p->copy_stream) (void) hipStreamDestroy(p->copy_stream);
 	delete p;
 }
 
@@ -841,7 +818,7 @@ j40hip_pipeline *j40hip_serve_pipeline(int device, uint32_t *err) {
 	if (device < 0 || device >= 16) { *err = E_GPU; return nullptr; }
 	std::lock_guard<std::mutex> lock(g_serve_mutex);
 	if (g_serve[device]) return g_serve[device];
-	auto env_int = [](const char *name, int dflt) { const char *e = getenv(name); return e && *e ? atoi(e) : dflt; };
+	auto env_int = [](const char *name, int dflt) { return j40hip::env_int(name, dflt, INT_MIN, INT_MAX); };
 	// (half of the container's CPU quota: the callers, the launching thread and the HIP runtime's own threads need the rest -- a
 	// process that runs into its quota has ALL its threads throttled and the copies back crawl. 64 callers over 8K streams on a
 	// 16-CPU quota: 9.9 Gpixel/s with 6 or 8 pipeline threads, 8.2 with 12, 6.4 with 16, 6.2 with 4)
@@ -851,12 +828,12 @@ j40hip_pipeline *j40hip_serve_pipeline(int device, uint32_t *err) {
 	// with the device, 128 callers 3.9 (p90 1.4 s) against 7.7 (p90 0.57 s). So "auto": a burst of at least twelve frames per pipeline
 	// thread goes to the device (and what arrives while its stage is busy follows), smaller ones stay with the host threads.
 	uint32_t lf = 0;
-	if (const char *e = getenv("J40HIP_SERVE_LF")) lf = !strcmp(e, "device") ? 1u : !strcmp(e, "auto") ? 0u : 2u;
+	if (const char *e = j40hip::env_str("J40HIP_SERVE_LF")) lf = !strcmp(e, "device") ? 1u : !strcmp(e, "auto") ? 0u : 2u;
 	j40hip_pipeline *p = j40hip_pipeline_create_ex(device, threads, std::max(1, env_int("J40HIP_SERVE_BATCH", 64)), env_int("J40HIP_SERVE_IN_FLIGHT", 6), lf | 8u, err);
 	if (!p) return nullptr;
-	if (!getenv("J40HIP_LF_AUTO_MIN")) { std::unique_lock<std::mutex> plock(p->m); p->lf_auto_min = 12 * (int64_t) threads; }
-	const char *w = getenv("J40HIP_SERVE_WAIT_MS");
-	j40hip_pipeline_set_max_wait_ms(p, w && *w ? atof(w) : 100.0);
+	if (!j40hip::env_str("J40HIP_LF_AUTO_MIN")) { std::unique_lock<std::mutex> plock(p->m); p->lf_auto_min = 12 * (int64_t) threads; }
+	const char *w = j40hip::env_str("J40HIP_SERVE_WAIT_MS");
+	j40hip_pipeline_set_max_wait_ms(p, w ? atof(w) : 100.0);
 	return g_serve[device] = p;
 }
 

@@ -368,6 +368,9 @@ struct DevLfLaneSet {
 // sections of one DevLfLaneSet; the tables of every part are staged in LDS side by side.
 enum { LF_WAVE_PARTS = 16 };
 struct DevLfWave { int32_t num_parts, pad; struct { int32_t set, first_task, count, pad; } part[LF_WAVE_PARTS]; };
+// what the frames of one wavefront of k_lf_lanes may take of LDS together: the packer (lf_decode.hip) and the front plan's "can the
+// lane decoder take this frame" (plan_front.cpp) have to agree on it
+constexpr uint32_t LF_LANES_LDS_BUDGET = 56u * 1024u;
 // Readable bytes behind a frame's codestream on the device: the lane decoders ask for up to three words past the position they stop
 // at, and k_lf_rows' straight-line runs look at their position only when a run is over (lf_rows_dev.h, lf_row_deferred): a run is at
 // most 255 samples of at most 32 bits each

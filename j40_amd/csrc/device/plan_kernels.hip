@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include "plan_dev.h"
 #include "kernels.h"
+#include "../env.hpp"
+#include <climits>
 #include <algorithm>
 
 namespace j40hip {
@@ -286,8 +288,8 @@ void launch_clear_block_events(const DevPlan *plans, const DevPlanBuild *builds,
 
 void launch_plan_build(const DevPlanBuild *builds, const DevBatchLf *lfs, int32_t nframes, int32_t nlf, int32_t max_lf_cells, hipStream_t stream) {
 	if (nframes <= 0 || nlf <= 0) return;
-	static const bool lanes_form = [] { const char *e = getenv("J40HIP_PLAN_PLACE_LANES"); return e && atoi(e); }();
-	static const int form = [] { const char *e = getenv("J40HIP_PLAN_PLACE_FORM"); return e ? atoi(e) : 0; }();
+	static const bool lanes_form = env_on("J40HIP_PLAN_PLACE_LANES", false);
+	static const int form = env_int("J40HIP_PLAN_PLACE_FORM", 0, INT_MIN, INT_MAX);
 	if (lanes_form) hipLaunchKernelGGL(k_plan_place_lanes, dim3((unsigned) ((nlf + 63) / 64)), dim3(64), 0, stream, builds, lfs, nlf);
 	else if (form == 1) hipLaunchKernelGGL(k_plan_place_walk, dim3((unsigned) nlf), dim3(64), 0, stream, builds, lfs, nlf);
 	else hipLaunchKernelGGL(k_plan_place, dim3((unsigned) nlf), dim3(64), 0, stream, builds, lfs, nlf);

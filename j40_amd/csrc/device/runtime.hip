@@ -66,7 +66,7 @@ size_t cache_limit_bytes(int device) {   // (never called with g_cache_mutex hel
 	if (device < 0 || device >= 16) return 0;
 	{ std::lock_guard<std::mutex> lock(g_limit_mutex); if (g_limit_known[device]) return g_limit[device]; }
 	size_t limit = (size_t) 48 << 30;
-	if (const char *e = getenv("J40HIP_CACHE_GB")) limit = (size_t) std::max(0, atoi(e)) << 30;
+	if (const int gb = env_int("J40HIP_CACHE_GB", -1, 0, INT_MAX); gb >= 0) limit = (size_t) gb << 30;
 	else {
 		int cur = -1; size_t free_b = 0, total_b = 0;
 		const bool switched = hipGetDevice(&cur) == hipSuccess && cur != device && hipSetDevice(device) == hipSuccess;
@@ -178,14 +178,14 @@ std::vector<PinnedIdle> g_pinned_idle;   // oldest first
 size_t g_pinned_idle_bytes = 0;
 size_t pinned_limit() {
 	static const size_t v = [] {
-		if (const char *e = getenv("J40HIP_PINNED_POOL_GB")) return (size_t) std::max(0, atoi(e)) << 30;
+		if (const int gb = env_int("J40HIP_PINNED_POOL_GB", -1, 0, INT_MAX); gb >= 0) return (size_t) gb << 30;
 		const long pages = sysconf(_SC_PHYS_PAGES), page = sysconf(_SC_PAGESIZE);
 		const size_t ram = pages > 0 && page > 0 ? (size_t) pages * (size_t) page : (size_t) 128 << 30;
 		return std::min((size_t) 32 << 30, ram / 4);
 	}();
 	return v;
 }
-double pinned_idle_seconds() { static const double v = [] { const char *e = getenv("J40HIP_PINNED_IDLE_S"); return e && atof(e) > 0 ? atof(e) : 30.0; }(); return v; }
+double pinned_idle_seconds() { static const double v = [] { const char *e = env_str("J40HIP_PINNED_IDLE_S"); return e && atof(e) > 0 ? atof(e) : 30.0; }(); return v; }
 double pinned_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // (under g_pinned_mutex) moves to `gone`: planes idle for too long, then the oldest ones until `incoming` more bytes fit the bound
 void pinned_make_room(size_t incoming, std::vector<void *> *gone) {
@@ -819,7 +819,7 @@ static uint32_t upload_impl(j40hip_frame *h, int device, hipStream_t s) {
 	HostPlan &hp = t_host_plan;   // (this thread's, storage kept from frame to frame)
 	hp.reset();
 	hp.force_dense = h->force_dense;
-	static const bool timing = getenv("J40HIP_API_TIMING") != nullptr;   // (where an upload's time goes: plan build, staging, copy + LfGroup tail)
+	const bool timing = api_timing();   // (where an upload's time goes: plan build, staging, copy + LfGroup tail)
 	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double tu0 = timing ? now() : 0;
 	if (uint32_t e = build_vardct_plan(h->frame, h->cs, h->cs_size, &hp, h->threads)) return e;
@@ -1043,8 +1043,7 @@ static uint32_t validate_trailers(j40hip_frame *h, hipStream_t s) {
 // filters a VarDCT frame signals; =j40 (2) runs them exactly as j40's routines stand, aliased line buffers and all (restore_dev.h).
 static int restoration_mode(const j40hip_frame *h) {
 	if (h->restoration >= 0) return h->restoration;
-	static const int env = [] { const char *e = getenv("J40HIP_RESTORATION"); return !e ? 0 : !strcmp(e, "j40") ? 2 : atoi(e) > 0 ? 1 : 0; }();
-	return env;
+	return j40hip_rt::restoration_env();
 }
 static bool surely_nonzero(float x) { return std::isfinite(x) && std::fabs(x) >= 1e-8f; }   // j40.h:625
 // the kernels' parameters from the frame header's; 0 or the reference routines' own complaints: "gab0" (j40.h:7289), "epf0" (j40.h:7384)
@@ -1102,7 +1101,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	if (r.epf_iters > 0 && !st->d_sharp) st->d_sharp = st->upload(sharp.data(), sharp.size(), s, ok);
 	if (!ok) return ERR_MEM;
 	hipEvent_t e0 = nullptr, e1 = nullptr;
-	static const bool timed = getenv("J40HIP_RESTORATION_TIMING") != nullptr;
+	static const bool timed = env_str("J40HIP_RESTORATION_TIMING") != nullptr;
 	launch_vardct_frame_xyb(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, st->d_xyb, (size_t) W * 4, s);
 	if (timed && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) (void) hipEventRecord(e0, s);
 	uint32_t *sharp_or = (uint32_t *) (st->d_sigma + cells);   // (the device's own OR of the sharpness values: unused, the host checked)
@@ -1229,13 +1228,13 @@ static uint32_t batch_assign(j40hip_batch *b, j40hip_frame *const *frames, int64
 	// share one copy of their frame's tables in LDS: with few wavefronts in the batch, one per workgroup spreads them
 	// over the CUs; with many, sharing keeps the tables from capping the wavefronts a CU can hold.
 	int32_t lanes = 64, total_waves = 0;
-	if (const char *e = getenv("J40HIP_LANES_PER_WAVE")) lanes = std::max(1, std::min(64, atoi(e)));
+	lanes = env_int("J40HIP_LANES_PER_WAVE", lanes, 1, 64);
 	for (j40hip_frame *h : b->frames) total_waves += (h->frame.fh.num_groups + lanes - 1) / lanes;
 	static int cus_of[16];   // (hipGetDeviceProperties takes milliseconds)
 	if (b->device >= 0 && b->device < 16 && !cus_of[b->device]) { hipDeviceProp_t prop; cus_of[b->device] = hipGetDeviceProperties(&prop, b->device) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256; }
 	const int cus = b->device >= 0 && b->device < 16 ? cus_of[b->device] : 256;
 	b->waves_per_wg = total_waves <= 2 * cus ? 1 : total_waves <= 4 * cus ? 2 : 4;
-	if (const char *e = getenv("J40HIP_WAVES_PER_WG")) b->waves_per_wg = std::max(1, std::min(4, atoi(e)));
+	b->waves_per_wg = j40hip_rt::waves_per_wg(b->waves_per_wg, 4);
 	std::vector<HfLaneWork> &work = b->work_host;
 	for (size_t i = 0; i < b->frames.size(); ++i) {
 		const int32_t groups = b->frames[i]->frame.fh.num_groups;
@@ -1262,7 +1261,7 @@ static uint32_t batch_assign(j40hip_batch *b, j40hip_frame *const *frames, int64
 	// side streams for the pixel kernels: made once, as many as the largest membership so far asks for
 	{
 		int nside = (int) std::min<size_t>(16, b->frames.size());
-		if (const char *e = getenv("J40HIP_SIDE_STREAMS")) nside = std::max(0, std::min(32, atoi(e)));
+		nside = env_int("J40HIP_SIDE_STREAMS", nside, 0, 32);
 		if (nside < 2) nside = 0;
 		while ((int) b->side.size() < nside) {
 			hipStream_t st = nullptr; hipEvent_t ev = nullptr;
@@ -1323,7 +1322,7 @@ static uint32_t batch_enqueue(j40hip_batch *b, void *const *rgba_dev, const size
 		// each section's status unconditionally -- 256 tiny fills were 4 % of a step)
 	}
 	if (ev) (void) hipEventRecord(ev[1], s);
-	if (b->lanes_fast && !getenv("J40HIP_GENERIC_LANES")) launch_hf_lanes(b->d_plans, b->d_work, b->num_work, b->waves_per_wg, b->lanes_lds_bytes, s);
+	if (b->lanes_fast && !j40hip_rt::generic_lanes()) launch_hf_lanes(b->d_plans, b->d_work, b->num_work, b->waves_per_wg, b->lanes_lds_bytes, s);
 	else launch_hf_entropy_lanes(b->d_plans, b->d_work, b->num_work, b->tables_in_lds, b->lds_bytes, s);
 	if (ev) (void) hipEventRecord(ev[2], s);
 	if (b->side_in_use == 0) {
@@ -1476,8 +1475,7 @@ static void two_phase_shutdown() {
 static void two_phase_plan(j40hip_frame *h, size_t image_bytes) {
 	j40hip_device_state *st = h->dev;
 	st->two_k = 0;
-	const char *env = getenv("J40HIP_TWO_PHASE");   // (looked at per upload: tests switch it between frames)
-	const bool allowed = !env || atoi(env) != 0;
+	const bool allowed = env_on("J40HIP_TWO_PHASE", true);   // (looked at per upload: tests switch it between frames)
 	const Frame &fr = h->frame;
 	const int64_t ng = fr.fh.num_groups;
 	if (!allowed || st->is_modular || !st->plan.events || !st->plan.block_events || st->has_trailers || fr.toc.single || fr.fh.num_passes != 1 || ng < 64 || image_bytes < ((size_t) 16 << 20)) return;
@@ -1515,7 +1513,7 @@ static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host
 	if (!two_phase_borrow(st->device, &tp)) return 0;
 	struct GiveBack { const TwoPhaseStream &t; ~GiveBack() { (void) hipStreamSynchronize(t.s); two_phase_return(t); } } give_back{tp};   // (whatever way the decode ends: nothing of it is left on the stream)
 	*done = true;
-	static const bool timing = getenv("J40HIP_API_TIMING") != nullptr;
+	const bool timing = api_timing();
 	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double t0 = timing ? now() : 0;
 	const DevPlan &plan = st->plan;

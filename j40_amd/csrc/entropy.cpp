@@ -111,7 +111,7 @@ static void build_prefix_table(const std::vector<int32_t> &lengths, Cluster *out
 }
 
 bool rfc_simple_code_order() {
-	static const bool on = [] { const char *e = getenv("J40HIP_RFC_SIMPLE_CODES"); return e && atoi(e) != 0; }();
+	static const bool on = env_on("J40HIP_RFC_SIMPLE_CODES", false);
 	return on;
 }
 

@@ -892,7 +892,7 @@ bool parse_frame_front(const uint8_t *cs, size_t cs_size, Frame *f, std::vector<
 }
 
 void parse_frame(const uint8_t *cs, size_t cs_size, Frame *f, int threads) {
-	static const bool timing = getenv("J40HIP_API_TIMING") != nullptr;   // (where a parse's time goes)
+	const bool timing = api_timing();   // (where a parse's time goes)
 	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double tp0 = timing ? now() : 0;
 	parse_headers(cs, cs_size, f);

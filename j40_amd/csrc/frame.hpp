@@ -11,6 +11,9 @@
 
 namespace j40hip {
 
+// J40HIP_API_TIMING=1: the single-image path prints where its time goes (parse, upload, decode); read once
+inline bool api_timing() { static const bool v = env_str("J40HIP_API_TIMING") != nullptr; return v; }
+
 struct ExtraChannel { int32_t type = 0, bpp = 8, exp_bits = 0, dim_shift = 0; bool alpha_associated = false; };
 enum { EC_ALPHA = 0, EC_SPOT = 2, EC_BLACK = 4, EC_CFA = 5 };
 

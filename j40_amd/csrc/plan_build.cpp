@@ -94,7 +94,7 @@ bool fill_event_ranges(const std::vector<DevSection> &sections, int32_t num_grou
 	if (!sparse) return true;
 	for (int32_t g = 0; g < num_groups; ++g) {
 		const DevSection &d = sections[(size_t) g];
-		static const size_t per_byte = getenv("J40HIP_EVENTS_PER_BYTE") ? (size_t) atoi(getenv("J40HIP_EVENTS_PER_BYTE")) : 4;   // tests shrink it to reach the fallback
+		static const size_t per_byte = (size_t) env_int("J40HIP_EVENTS_PER_BYTE", 4, INT_MIN, INT_MAX);   // tests shrink it to reach the fallback
 		const size_t worst = (size_t) d.gw8 * (size_t) d.gh8 * 64 * 3, cap = std::min(worst, (size_t) d.size * per_byte + 256);
 		*ev_capacity = (*ev_capacity + 31) & ~(size_t) 31;   // regions start on a 128-byte line: the entropy kernel writes them in aligned pieces (hf_lanes_dev.h)
 		ev_range->push_back((uint32_t) *ev_capacity);
@@ -158,7 +158,7 @@ void fill_frame_constants(const Frame &fr, DevFrame *out) {
 }
 
 uint32_t build_vardct_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, HostPlan *hp, int threads) {
-	static const bool timing = getenv("J40HIP_PLAN_TIMING") != nullptr;
+	static const bool timing = env_str("J40HIP_PLAN_TIMING") != nullptr;
 	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double tb0 = timing ? now() : 0; double tbA = 0, tbB = 0, tbC = 0;
 	if (cs_size + 16 >= ((size_t) 1 << 29)) return ERR_TODO;   // the kernels address the codestream with 32-bit BIT positions
@@ -458,7 +458,7 @@ bool build_lf_coop(const Frame &fr, DevCoopTree *tree, std::vector<uint64_t> *al
 // which sections k_modular_coop decodes: those whose tree / code spec it can take and whose channels are not wider than its row
 // buffers allow
 static void assign_coop(HostModPlan *hp) {
-	static const bool off = [] { const char *e = getenv("J40HIP_NO_COOP"); return e && atoi(e); }();
+	static const bool off = env_on("J40HIP_NO_COOP", false);
 	std::vector<std::pair<uint64_t, int32_t>> known;   // (tree_off, spec_idx) -> coop tree or -1
 	hp->coop_width = 0; hp->coop_sections = 0;
 	std::vector<int32_t> section_width;   // widest channel of the sections k_modular_coop could take, -1 for the others
@@ -491,7 +491,7 @@ static void assign_coop(HostModPlan *hp) {
 	// alias tables are staged in LDS once per workgroup) -- the one most sections use. OFF unless J40HIP_QUAD_MIN=<sections> is set:
 	// measured on 16384 x 16384 (4096 sections) it only ties k_modular_coop (222 vs 226 ms) -- one wavefront per SIMD is bound by the
 	// latency of its own dependent chain; it needs >= 8192 sections (two wavefronts per SIMD) to pay. Kept as a tested variant.
-	static const int32_t quad_min = [] { const char *e = getenv("J40HIP_QUAD_MIN"); return e ? atoi(e) : -1; }();
+	static const int32_t quad_min = env_int("J40HIP_QUAD_MIN", -1, INT_MIN, INT_MAX);
 	hp->quad_sections = 0; hp->quad_spec = 0; hp->quad_width = 0;
 	for (DevModSection &s : hp->sections) s.quad = 0;
 	if (quad_min >= 0 && hp->coop_sections >= std::max(quad_min, 1)) {
@@ -516,7 +516,7 @@ static void recount_coop(HostModPlan *hp);
 // sample is -- properties 0-3 -- and predicts without the weighted predictor; fast lossless encoders write nothing else (one gradient
 // leaf per channel). They leave k_modular_coop's list. J40HIP_NO_SPLIT=1: none (the one-pass kernels, for comparison).
 static void assign_split(HostModPlan *hp) {
-	static const bool off = [] { const char *e = getenv("J40HIP_NO_SPLIT"); return e && atoi(e); }();
+	static const bool off = env_on("J40HIP_NO_SPLIT", false);
 	hp->split_sections = 0; hp->split_width = 0; hp->split_channels = 0; hp->split_samples = 0;
 	std::vector<std::pair<uint64_t, int32_t>> known;   // (tree_off, tree_nodes) -> 0 no, 1 yes, 2 yes and it tests the column
 	auto tree_kind = [&](uint32_t tree_off, int32_t tree_nodes, int32_t spec_idx) {

@@ -31,6 +31,32 @@ def test_library_exports_declared_abi(built):
         assert hasattr(L, name), "libj40hip.so does not export %s" % name
 
 
+def test_environment_switches_are_the_documented_ones():
+    """INTEGRATION.md's "Environment switches" paragraph lists exactly the J40HIP_* variables the library reads, and the tests and
+    bench.py set none that it does not read (J40HIP_LIB selects the library itself; J40HIP_API is the headers' export macro)."""
+    import glob
+    literal = re.compile(r"[\"'](J40HIP_[A-Z0-9_]+)[\"']")
+    read = set()
+    for pat in ("j40_amd/csrc/*", "j40_amd/csrc/device/*", "j40_amd/*.py"):
+        for path in glob.glob(os.path.join(ROOT, pat)):
+            if os.path.isfile(path):
+                read |= set(literal.findall(open(path, errors="replace").read()))
+    read -= {"J40HIP_LIB", "J40HIP_API"}
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    para = text[text.index("Environment switches:"):]
+    para = para[:para.index("\n\n")]
+    documented = set(re.findall(r"J40HIP_[A-Z0-9_]*[A-Z0-9]", para))
+    assert len(read) >= 40
+    assert read == documented, "read but not documented: %s; documented but not read: %s" % (sorted(read - documented), sorted(documented - read))
+    put = set()
+    sources = glob.glob(os.path.join(ROOT, "tests", "*.py")) + [os.path.join(ROOT, "bench.py")]
+    for path in sources:
+        if os.path.basename(path) != "test_host.py":
+            put |= set(literal.findall(open(path).read()))
+    put -= {"J40HIP_LIB", "J40HIP_API"}
+    assert put and put <= read, "set by tests or bench.py, read by nothing: %s" % sorted(put - read)
+
+
 def test_public_struct_layout(built):
     import j40_amd
     # j40_image: u32 magic + pointer-sized union; j40_frame: 2 x u32 + pointer; pixels: 3 x i32 + pointer

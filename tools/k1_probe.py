@@ -24,4 +24,4 @@ for i in range(steps): b.decode_recorded(ptrs, strides, s, i)
 torch.cuda.synchronize(); dt = time.time() - t0
 k1 = sum(b.elapsed(i)[0] for i in range(steps)) / steps; k2 = sum(b.elapsed(i)[1] for i in range(steps)) / steps
 assert torch.equal(ref, outs[0])
-print("R=%d gen=%s wpw=%s: K1 %.2f ms, K2 %.2f ms, step %.2f ms, %.0f Mpx/s" % (R, os.environ.get("J40HIP_LANES_GEN", "2"), os.environ.get("J40HIP_WAVES_PER_WG", "auto"), k1, k2, dt / steps * 1e3, R * W * H * steps / dt / 1e6), flush=True)
+print("R=%d wpw=%s: K1 %.2f ms, K2 %.2f ms, step %.2f ms, %.0f Mpx/s" % (R, os.environ.get("J40HIP_WAVES_PER_WG", "auto"), k1, k2, dt / steps * 1e3, R * W * H * steps / dt / 1e6), flush=True)

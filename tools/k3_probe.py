@@ -1,4 +1,4 @@
-"""times the Modular section kernel (K3) on a few frames; J40HIP_K3_LANES=1 selects the one-section-per-lane form"""
+"""times the Modular section kernel (K3) on a few frames"""
 import sys, os, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")); sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 import torch, numpy as np, j40_amd

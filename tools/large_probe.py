@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The pixel stage on streams full of 128- and 256-sized transforms (k_vardct_large): N 8K coefficient-domain frames with maxlog = 8 per
-step and per entropy launch through the pipeline, the RGBA left in HBM. J40HIP_LARGE_IDCT=sweeps selects round 3's kernel.
+step and per entropy launch through the pipeline, the RGBA left in HBM.
 usage: python tools/large_probe.py [frames per launch = 64] [steps = 3] [distinct streams = 16]"""
 import ctypes as C, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,7 +23,7 @@ el, tk = run_pipeline_steps(pipe, sb, ss, so, W * 4, True, steps, torch, dev, No
 st = pipe.stats()
 assert all(pipe.result(t) == "" for t in tk)
 n = max(st["launches"], 1)
-print(json.dumps({"large_idct": os.environ.get("J40HIP_LARGE_IDCT", "levels + 64-point registers"), "frames_per_step": B, "steps": steps, "mpixels_per_s": round(W * H * B * steps / el / 1e6, 1),
+print(json.dumps({"frames_per_step": B, "steps": steps, "mpixels_per_s": round(W * H * B * steps / el / 1e6, 1),
                   "ms_per_step": round(el / steps * 1e3, 2), "k_hf_lanes_ms_per_launch": round(st["k1_kernel_ms"] / n, 3), "frames_per_launch": st["launch_frames"] / n,
                   "pixel_kernels_ms_per_launch": round(st["k2_ms"] / n, 3)}))
 pipe.close()
