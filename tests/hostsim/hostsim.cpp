@@ -232,10 +232,28 @@ extern "C" __attribute__((visibility("default"))) void hostsim_set_group_range(i
 // decodes a stream with the device functions on the CPU.
 //   rgba: width*height*4 bytes; coeffs_out (optional): 3 arrays of total_cells*64 floats concatenated
 // returns 0 or the first error code
+static uint32_t g_first_attempt = 0;
+// the status of the last hostsim_decode's attempt with event lists where that was "evof" and the frame was decoded again with dense planes
+// (0 otherwise): lets a test see that a stream really leaves the events
+extern "C" __attribute__((visibility("default"))) uint32_t hostsim_first_attempt_status(void) { return g_first_attempt; }
+
+static uint32_t hostsim_decode_once(const uint8_t *buf, size_t size, uint8_t *rgba, float *coeffs_out, int only_entropy, bool force_dense);
+
+// A single-pass frame whose attempt with event lists ends in ERR_EVOF (a section's region full, a value beyond int16) is decoded again
+// with dense coefficient planes, as runtime.hip does it (j40hip_frame_decode_to_host). The latency kernel's fast path (bit 4) knows
+// events only; the runtime's second attempt goes through the general kernel, so does this one.
 extern "C" __attribute__((visibility("default"))) uint32_t hostsim_decode(const uint8_t *buf, size_t size, uint8_t *rgba, float *coeffs_out, int only_entropy) {
+	g_first_attempt = 0;
+	uint32_t e = hostsim_decode_once(buf, size, rgba, coeffs_out, only_entropy, false);
+	if (e == (uint32_t) ERR_EVOF) { g_first_attempt = e; e = hostsim_decode_once(buf, size, rgba, coeffs_out, only_entropy & ~16, true); }
+	return e;
+}
+
+static uint32_t hostsim_decode_once(const uint8_t *buf, size_t size, uint8_t *rgba, float *coeffs_out, int only_entropy, bool force_dense) {
 	Frame fr;
 	const uint8_t *cs; size_t cs_size; std::vector<uint8_t> storage;
 	HostPlan hp;
+	hp.force_dense = force_dense;
 	try {
 		extract_codestream(buf, size, &cs, &cs_size, &storage);
 		parse_frame(cs, cs_size, &fr, 1);

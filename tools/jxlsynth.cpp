@@ -237,6 +237,30 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	const int small_clusters = opt.geti("simpleclusters", 0); // <= 8 clusters: simple cluster-map form
 	const int log_alpha = opt.geti("logalpha", 7);
 	const int container = opt.geti("container", 0);
+	// coefficient statistics outside what an encoder writes at d1 (all default to that):
+	//   bigshare=p bigbits=k  with probability p a non-zero's magnitude is drawn from [2^(k-1), 2^k): uniform, except that one draw in
+	//                         eight takes one of the two ends so that the boundary values themselves always occur. Packed, such a
+	//                         value has k + 1 bits; the reference's hybrid integers hold 30 (j40.h:2308-2319), so k = 30 is the
+	//                         first it refuses ("iovf")
+	//   flat=v                every non-zero coefficient is v: next to no entropy per non-zero
+	//   hybrid=s,m,l          split_exp, msb_in_token, lsb_in_token of every HF cluster (default: {4,2,0} and {4,1,1} alternating)
+	//   extraprec=0..3        the LfGroups' extra_precision; the LF integers grow by 2^extraprec so that the picture stays what it is
+	const double bigshare = opt.getd("bigshare", 0.0);
+	const int bigbits = opt.geti("bigbits", 0), flat = opt.geti("flat", 0), extra_prec = opt.geti("extraprec", 0);
+	if (bigshare < 0 || bigshare > 1) die("vardct: bigshare is a probability");
+	if (bigshare > 0 && (bigbits < 7 || bigbits > 30)) die("vardct: bigshare wants bigbits=7..30 (a magnitude below 2^bigbits packs into bigbits + 1 bits; the writer's tokens hold 32)");
+	if (bigbits && bigshare <= 0) die("vardct: bigbits without bigshare changes nothing");
+	if (flat && bigshare > 0) die("vardct: flat fixes every non-zero's value; it does not combine with bigshare");
+	if (extra_prec < 0 || extra_prec > 3) die("vardct: extraprec is a 2-bit field (0..3)");
+	if (opt.geti("forward", 0) && (bigshare > 0 || flat || opt.kv.count("hybrid"))) die("vardct: forward=1 takes its coefficients from the picture; bigshare / flat / hybrid belong to the synthetic statistics");
+	if (global_scale < 1 || global_scale > 8193 + 65535) dief("vardct: global_scale=%d is outside its code U32(1+u(11), 2049+u(11), 4097+u(12), 8193+u(16)): 1..73728", global_scale);
+	if (quant_lf < 1 || quant_lf > 65536) dief("vardct: quant_lf=%d is outside its code U32(16, 1+u(5), 1+u(8), 1+u(16)): 1..65536", quant_lf);
+	HybridCfg forced_cfg; bool have_forced_cfg = false;
+	if (opt.kv.count("hybrid")) {
+		const std::string h = opt.gets("hybrid", "");
+		if (sscanf(h.c_str(), "%d,%d,%d", &forced_cfg.split_exp, &forced_cfg.msb, &forced_cfg.lsb) != 3) die("vardct: hybrid=<split_exp>,<msb>,<lsb>");
+		have_forced_cfg = true;
+	}
 
 	const int gcols = (W + 255) / 256, grows = (H + 255) / 256, num_groups = gcols * grows;
 	const int ggcols = (W + 2047) / 2048, ggrows = (H + 2047) / 2048, num_lf_groups = ggcols * ggrows;
@@ -267,7 +291,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	};
 	// LF dequant steps (j40.h:6562): m_lf_scaled / (global_scale * quant_lf) * 65536
 	const double m_lf[3] = {1.0 / 4096, 1.0 / 512, 1.0 / 256};
-	double lfstep[3]; for (int c = 0; c < 3; ++c) lfstep[c] = m_lf[c] / ((double) global_scale * quant_lf) * 65536.0;
+	double lfstep[3]; for (int c = 0; c < 3; ++c) lfstep[c] = m_lf[c] / ((double) global_scale * quant_lf) * (double) (65536 >> extra_prec);
 
 	// ---- forward=1: the picture's XYB samples (planes padded to whole cells, edges replicated) ----
 	const int forward = opt.geti("forward", 0);
@@ -388,6 +412,9 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			double yq = (double) gg.lfq[0].at(x, y) * lfstep[1];
 			gg.lfq[1].at(x, y) = (int32_t) lrint((xyb[0] - kx_lf * yq) / lfstep[0]);
 			gg.lfq[2].at(x, y) = (int32_t) lrint((xyb[2] - kb_lf * yq) / lfstep[2]);
+			for (int c = 0; c < 3; ++c) if (abs(gg.lfq[c].at(x, y)) > 32767)
+				dief("vardct: global_scale=%d quant_lf=%d extraprec=%d make the LF step so fine (%.3g) that an LF integer reaches %d; the LfGroup's channels are "
+				     "16-bit here, keep global_scale * quant_lf << extraprec below about 3.5 million (times the picture's brightest Y)", global_scale, quant_lf, extra_prec, lfstep[c == 0 ? 1 : c == 1 ? 0 : 2], gg.lfq[c].at(x, y));
 		}
 		gg.lfidx.assign((size_t) gg.w8 * (size_t) gg.h8, 0);
 		for (int y = 0; y < gg.h8; ++y) for (int x = 0; x < gg.w8; ++x) {  // j40.h:6566-6570
@@ -585,7 +612,19 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.lz_min_symbol = 224; cs.lz_min_length = 3; cs.lz_len_cfg = HybridCfg{0, 0, 0};
 		cs.use_prefix = hf_prefix != 0;
 		cs.log_alpha = (hf_lz77 || hf_prefix) ? 8 : log_alpha;
+		if (!hf_prefix && (cs.log_alpha < 5 || cs.log_alpha > 8)) dief("vardct: logalpha=%d; an rANS alphabet has 2^5..2^8 symbols", cs.log_alpha);
 		for (int c = 0; c < nclusters; ++c) cs.cfg[(size_t) c] = (c & 1) && !hf_lz77 ? HybridCfg{4, 1, 1} : HybridCfg{4, 2, 0};
+		if (have_forced_cfg) {
+			// j40.h:2297-2311: split_exp is read with at_most(log_alpha_size) (15 for prefix codes), msb with at_most(split_exp), lsb with
+			// at_most(split_exp - msb), and the last two are not coded at all when split_exp == log_alpha_size
+			const int las = hf_prefix ? 15 : cs.log_alpha;
+			const HybridCfg &h = forced_cfg;
+			if (h.split_exp < 0 || h.split_exp > las) dief("vardct: hybrid: split_exp=%d, but it is coded in 0..%d (the code's log_alpha_size; logalpha=5..8 for rANS)", h.split_exp, las);
+			if (h.msb < 0 || h.msb > h.split_exp) dief("vardct: hybrid: msb=%d, but msb_in_token <= split_exp=%d", h.msb, h.split_exp);
+			if (h.lsb < 0 || h.lsb > h.split_exp - h.msb) dief("vardct: hybrid: lsb=%d, but lsb_in_token <= split_exp - msb=%d", h.lsb, h.split_exp - h.msb);
+			if (h.split_exp == las && (h.msb || h.lsb)) dief("vardct: hybrid: with split_exp == log_alpha_size (%d) msb and lsb are not coded and read as 0; no token beyond the split exists then", las);
+			for (int c = 0; c < nclusters; ++c) cs.cfg[(size_t) c] = h;
+		}
 		hf_enc[(size_t) pass].reserve((size_t) num_groups);
 	}
 	// custom coefficient orders: Lehmer codes per (pass, order, channel); the writer only needs them
@@ -669,7 +708,14 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 					for (int i = first; i < size && pk > 2e-3; ++i) {
 						if (rng.unit() < pk) {
 							int mag = 1; while (mag < 40 && rng.unit() < cont) ++mag;
-							coefs.push_back({i, rng.below(2) ? mag : -mag});
+							int v = rng.below(2) ? mag : -mag;
+							if (bigshare > 0 && rng.unit() < bigshare) {
+								const uint32_t lo = 1u << (bigbits - 1), pick = rng.below(8);
+								const uint32_t m = pick == 0 ? lo : pick == 1 ? 2 * lo - 1 : lo + (uint32_t) (rng.next() >> 20) % lo;
+								v = v < 0 ? -(int) m : (int) m;
+							}
+							if (flat) v = flat;
+							coefs.push_back({i, v});
 						}
 						pk *= dk; cont = 0.3 + (cont - 0.3) * pow(dk, 0.6);
 					}
@@ -702,6 +748,9 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 				const CodeSpecW &cs = cspec[(size_t) pass];
 				std::vector<StreamEncoder::Item> out;
 				const auto &it = enc.items;
+				for (const auto &item : it) if ((int) item.token >= cs.lz_min_symbol)
+					dief("vardct: hflz77=1 reads tokens from %d on as copy lengths, but a literal needs token %u under hybrid integers {%d,%d,%d}",
+					     cs.lz_min_symbol, item.token, cs.cfg[item.cluster].split_exp, cs.cfg[item.cluster].msb, cs.cfg[item.cluster].lsb);
 				for (size_t i = 0; i < it.size(); ) {
 					size_t j = i + 1;
 					while (j < it.size() && it[j].token == it[i].token && it[i].nextra == 0 && it[j].nextra == 0 && it[i].token < 16) ++j;
@@ -719,6 +768,17 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 				enc.items.swap(out);
 			}
 			count_stream(cspec[(size_t) pass], enc);
+		}
+	}
+
+	for (int pass = 0; pass < num_passes; ++pass) {   // say why a combination cannot be written before the writer trips over it
+		const CodeSpecW &cs = cspec[(size_t) pass];
+		for (int c = 0; c < cs.num_clusters; ++c) {
+			const int ntok = (int) cs.freq[(size_t) c].size();
+			if (ntok > cs.alphabet_limit())
+				dief("vardct: an HF cluster with hybrid integers {%d,%d,%d} needs token %d, but the alphabet has %d symbols (logalpha=%d): raise logalpha, "
+				     "or lower what is coded (density, maxlog: a block's non-zero count; cont, bigbits: the magnitudes) or the hybrid split",
+				     cs.cfg[(size_t) c].split_exp, cs.cfg[(size_t) c].msb, cs.cfg[(size_t) c].lsb, ntok - 1, cs.alphabet_limit(), cs.log_alpha);
 		}
 	}
 
@@ -755,7 +815,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	for (int ggi = 0; ggi < num_lf_groups; ++ggi) {  // LfGroup (j40.h:6722)
 		LfGroupW &gg = ggs[(size_t) ggi];
 		BitWriter bw;
-		bw.put(0, 2);                                            // extra_precision
+		bw.put((uint64_t) extra_prec, 2);                        // extra_precision
 		write_modular_header(bw, true, nullptr, {});
 		lfq_enc[(size_t) ggi].flush(bw);
 		bw.put((uint64_t) (gg.vbs.size() - 1), ceil_lg((uint32_t) (gg.w8 * gg.h8)));

@@ -5,6 +5,7 @@
 // test/bench input is produced by this writer. It emits exactly the syntax the reference reader
 // consumes; each routine cites the reader it is the inverse of (file:line into /root/reference).
 #pragma once
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +18,9 @@
 namespace synth {
 
 [[noreturn]] inline void die(const char *msg) { fprintf(stderr, "jxlsynth: %s\n", msg); exit(2); }
+[[noreturn]] __attribute__((format(printf, 1, 2))) inline void dief(const char *fmt, ...) {
+	va_list ap; va_start(ap, fmt); fprintf(stderr, "jxlsynth: "); vfprintf(stderr, fmt, ap); fprintf(stderr, "\n"); va_end(ap); exit(2);
+}
 
 inline int floor_lg(uint32_t x) { return 31 - __builtin_clz(x); }            // x > 0
 inline int ceil_lg(uint32_t x) { return x > 1 ? 32 - __builtin_clz(x - 1) : 0; }  // x > 0
