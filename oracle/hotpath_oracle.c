@@ -113,7 +113,12 @@ static void ocode_free(ocode *c) {
 	if (c->alias) { for (i = 0; i < c->spec->num_clusters; ++i) free(c->alias[i]); free(c->alias); }
 	free(c->window);
 }
-static void ocode_restart(ocode *c) { c->ans_state = 0; c->num_to_copy = c->copy_pos = c->num_decoded = 0; }
+// (a new stream starts on a window of zeros: a copy from before its first integer reads them, j40.h:2854-2860, and must not
+// see what the stream before it left here)
+static void ocode_restart(ocode *c) {
+	if (c->window && c->num_decoded > 0) memset(c->window, 0, sizeof(int32_t) * (size_t) (c->num_decoded < (1 << 20) ? c->num_decoded : (1 << 20)));
+	c->ans_state = 0; c->num_to_copy = c->copy_pos = c->num_decoded = 0;
+}
 
 static int32_t hybrid(obits *b, int32_t token, int split_exp, int msb, int lsb) {
 	int32_t split = 1 << split_exp, max_token = split + ((30 - split_exp) << (lsb + msb)) - 1, in_token, midbits, mid, top, lo, hi;

@@ -37,6 +37,17 @@ def main():
     cases.append(("modular_wide_tree_48_leaves", "modular", 300, 200, 91, dict(tree=5)))
     cases.append(("modular_squeeze_default_list", "modular", 300, 200, 92, dict(squeeze=1, tree=1)))
     cases.append(("modular_squeeze_explicit_list_alpha", "modular", 300, 200, 93, dict(squeeze=3, alpha=1)))
+    # streams outside an encoder's habits (tests/test_modular_stress.py): every special LZ77 distance code under a multiplier of 200
+    # and under one of 5 (where the clamp to 1 acts), weighted-predictor parameters per pass group, a palette predicted by the
+    # weighted predictor with parameters of its own, 15-bit noise, and a residual that takes a sample beyond int16: that entry pins the
+    # reference's error code ("error") instead of pixels
+    forced = dict(lz77=1, tree=4, rct=-1, lzforce="specials")
+    cases.append(("modular_lz77_special_distances_width_200", "modular", 200, 100, 101, dict(forced)))
+    cases.append(("modular_lz77_special_distances_width_5", "modular", 5, 200, 102, dict(forced, prefix=1)))
+    cases.append(("modular_wp_parameters_per_group", "modular", 200, 150, 103, dict(tree=2, wp="random", wpat="both", groupshift=7)))
+    cases.append(("modular_palette_predictor_6_custom_wp", "modular", 300, 200, 104, dict(palette=3, dpred=6, wp="max")))
+    cases.append(("modular_noise_15_bit", "modular", 96, 64, 105, dict(bpp=15, rct=-1, noise=32767, tree=1)))
+    cases.append(("modular_sample_overflow", "modular", 96, 64, 106, dict(povf=3000, prefix=1)))
     for name, mode, w, h, seed, opts in cases:
         data = synth(mode, w, h, seed, **opts)
         with open(os.path.join(HERE, name + ".jxl"), "wb") as fp:
@@ -46,6 +57,11 @@ def main():
             err, rgba = ref.decode(synth(mode, w, h, seed, **{k: v for k, v in opts.items() if k != "squeeze"}))
         else:
             err, rgba = ref.decode(data)
+        if "povf" in opts:
+            assert err == "povf", (name, err)
+            manifest[name] = dict(mode=mode, width=w, height=h, seed=seed, opts=opts, bytes=len(data), stream_sha256=hashlib.sha256(data).hexdigest(), error=err)
+            print(name, len(data), "bytes, the reference answers", err)
+            continue
         assert err == "", (name, err)
         entry = dict(mode=mode, width=w, height=h, seed=seed, opts=opts, bytes=len(data), stream_sha256=hashlib.sha256(data).hexdigest(), rgba_sha256=sha(rgba))
         if "squeeze" in opts:

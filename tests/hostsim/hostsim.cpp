@@ -85,6 +85,7 @@ void idct_cols_dyn(float *t, int n, int cols, int pitch, const float *hs) {
 
 // group range for the next hostsim_decode calls (mirrors j40hip_frame_set_group_range; count < 0: every group)
 static int64_t g_first_group = 0, g_group_count = -1;
+static int32_t g_neighbour_flip = 0;
 
 // Modular frames: K3 / K4 / K5 device functions with the runtime's orchestration (device/runtime.hip)
 static uint32_t hostsim_decode_modular(const Frame &fr, const uint8_t *cs, size_t cs_size, uint8_t *rgba) {
@@ -109,7 +110,7 @@ static uint32_t hostsim_decode_modular(const Frame &fr, const uint8_t *cs, size_
 	std::vector<DevSubPlane> subp(hp.sub_w.size());
 	for (size_t k = 0; k < hp.sub_w.size(); ++k) { sub_store[k].assign((size_t) hp.sub_w[k] * (size_t) hp.sub_h[k] + 1, 0); subp[k] = DevSubPlane{sub_store[k].data(), hp.sub_w[k], hp.sub_h[k], hp.sub_meta[k], 0}; }
 	plan.sub_planes = subp.data();
-	std::vector<int32_t> wps((size_t) hp.sections.size() * (size_t) (2 * hp.frame.max_width * 5) + 16), window(hp.lz_window_size ? (size_t) hp.sections.size() * hp.lz_window_size : 0);
+	std::vector<int32_t> wps((size_t) hp.sections.size() * (size_t) (2 * hp.frame.max_width * 5) + 16), window(hp.lz_window_size ? (size_t) hp.sections.size() * hp.lz_window_size : 0, 0x5a5a5a5a);   // (device memory is not zeroed: what a copy reads before the first integer must come from the decoder's rule, not from here)
 	std::vector<uint32_t> status(hp.sections.size() + 1, 0);
 	plan.wp_scratch = hp.frame.tree_uses_wp ? wps.data() : nullptr;
 	plan.lz_window = window.empty() ? nullptr : window.data(); plan.lz_window_size = hp.lz_window_size; plan.status = status.data();
@@ -128,7 +129,7 @@ static uint32_t hostsim_decode_modular(const Frame &fr, const uint8_t *cs, size_
 		if (hp.sections[(size_t) sct].preset_status) { status[(size_t) sct] = hp.sections[(size_t) sct].preset_status; continue; }
 		ModTables mt = mod_tables_in_hbm(plan, sct);
 		mt.rows = ring.data(); mt.rows_width = hp.frame.max_width + 4; mt.wp_errors = wperr.data(); mt.wp_errors_width = hp.frame.max_width;   // as the kernel lays them out in LDS
-		status[(size_t) sct] = (sct & 1) ? decode_modular_section<false, true>(plan, mt, sct) : decode_modular_section<false, false>(plan, mt, sct);   // both neighbour sources
+		status[(size_t) sct] = ((sct ^ g_neighbour_flip) & 1) ? decode_modular_section<false, true>(plan, mt, sct) : decode_modular_section<false, false>(plan, mt, sct);   // both neighbour sources
 	}
 	{   // like j40hip_frame_status: the reference reports the first failing section in file order (j40.h:5608)
 		uint32_t first = 0, first_off = 0xffffffffu;
@@ -226,6 +227,10 @@ static uint32_t hostsim_decode_modular(const Frame &fr, const uint8_t *cs, size_
 	}
 	return 0;
 }
+
+// which of decode_modular_section's two neighbour sources the even sections take (0: as above; 1: the other way round, so that a
+// frame of one section sees both)
+extern "C" __attribute__((visibility("default"))) void hostsim_set_neighbour_flip(int32_t flip) { g_neighbour_flip = flip & 1; }
 
 extern "C" __attribute__((visibility("default"))) void hostsim_set_group_range(int64_t first, int64_t count) { g_first_group = first; g_group_count = count; }
 

@@ -158,6 +158,18 @@ VARDCT_STRESS_CASES = [
     ("mix_dense_12_bits_cfl", "mix", dict(_BASE, bpp=12, cfl=1), dict()),
     ("mix_big_16_custom_dequant_alpha", "mix") + _big(16, dq=2, alpha=1),
     ("mix_flat_alpha_extra_precision", "mix", dict(_DENSE, flat=1, alpha=1, extraprec=2), dict(evof=1)),
+    # LZ77 copies beyond "the value before": the generator's matcher over the coefficient streams (no distance multiplier there: every
+    # distance is coded plain), and weighted-predictor parameters other than the defaults in the Modular headers of a VarDCT frame
+    # (LfGroup's two sub-images, raw dequantisation matrices, alpha sub-images; lftree=4: predictor 6 and property 15 everywhere).
+    # `stats`: floors on the generator's stats=1 line, asserted by tests/test_modular_stress.py
+    ("lz77_overlap", "lz77", dict(hflz77=1, hflzmode="overlap"), dict(unsaturated=1, stats=dict(overlapping_copies=1000, max_distance=10000))),
+    ("lz77_plain_prefix_minlen_5_long_distances", "lz77", dict(hflz77=1, hflzmode="plain", hfprefix=1, hflzminlen=5, hflzdistcfg="0,0,0"), dict(unsaturated=1, stats=dict(plain_copies=1000, max_distance=10000))),
+    ("lz77_overlap_dense_two_passes", "lz77", dict(_BASE, hflz77=1, hflzmode="overlap", passes=2), dict(unsaturated=1, stats=dict(overlapping_copies=1000))),
+    ("lz77_plain_all_transforms_bctx", "lz77", dict(hflz77=1, hflzmode="plain", maxlog=8, bctx=1), dict(stats=dict(plain_copies=1000))),
+    ("wp_tree_default_parameters", "wp", dict(lftree=4), dict(unsaturated=1, stats=dict(wp_predicted_samples=1000, wp_property_tests=1000))),
+    ("wp_every_sub_image_its_own", "wp", dict(lftree=4, wp="random", wpat="both", alpha=1, dq=2), dict(stats=dict(wp_non_default_headers=11, wp_distinct_sets=8, wp_predicted_samples=10000))),
+    ("wp_global_header_alone", "wp", dict(lftree=4, wp="max", wpat="global", alpha=1), dict(stats=dict(wp_non_default_headers=1, wp_predicted_samples=10000))),
+    ("wp_sub_images_alike_p3d_p3e", "wp", dict(lftree=4, wp="16,10,0,0,0,31,31,13,12,12,12", wpat="group", dq=2), dict(stats=dict(wp_non_default_headers=4, wp_predicted_samples=1000))),
 ]
 
 
@@ -168,3 +180,180 @@ def stress_size(opts):
 def stress_stream(opts):
     w, h = stress_size(opts)
     return synth("vardct", w, h, STRESS_SEED, **opts)
+
+
+# ---- Modular streams outside an encoder's habits (tests/test_modular_stress.py) ----
+# Every MODULAR_CASES stream with LZ77 copies uses ONE distance code (special code 1, the value before), min_length 3, min_symbol 224
+# and the length configuration {0,0,0}; every weighted predictor runs on the default parameters; samples are smooth, inside
+# [0, 2^bpp) and at most 14 bits deep. These rows leave that regime. A row is (name, family, (width, height), options, traits);
+# the seed is STRESS_SEED. Traits are conditions on what tools/jxlsynth reports with stats=1 (synth_stats), so that a row cannot
+# silently stop doing what it is there for:
+#   error      the reference's error code ("" when absent)
+#   at_least   stat -> floor
+#   exactly    stat -> value
+# Forced copies (lzforce=) define the samples they cover: with the zero predictor in one leaf (tree=4) a sample is its residual, and
+# the tests compare decoders, not pictures.
+_F = dict(lz77=1, tree=4, rct=-1)
+_ALL = dict(exactly=dict(distinct_special_codes=120, clamped_distances=0), at_least=dict(copies_crossing_rows=1, copies_crossing_channels=1, overlapping_copies=1))
+_EARLY = dict(exactly=dict(first_symbol_copies=1), at_least=dict(clamped_distances=20, plain_copies=10, special_copies=10))
+_TILED = dict(tile="37,11")
+
+
+def _specials(w, h, **more):
+    return ("specials_%dx%d%s" % (w, h, "".join("_%s_%s" % (k, str(v).replace(",", "")) for k, v in sorted(more.items()))), "lz_forced", (w, h), dict(_F, lzforce="specials", **more), _ALL)
+
+
+MODULAR_STRESS_CASES = [
+    # all 120 special codes, unclamped, under multipliers from 1 (where max(1, ...) acts on most of the table) to 200; 63 / 64 / 65:
+    # where the sixty-four-at-a-time walk and 64-lane copies meet row ends
+    _specials(200, 100), _specials(200, 100, prefix=1), _specials(5, 200, prefix=1), _specials(1, 1000, groupshift=10), _specials(2, 450, groupshift=9, prefix=1),
+    _specials(7, 200), _specials(8, 200, prefix=1), _specials(63, 70, prefix=1), _specials(64, 70), _specials(64, 70, prefix=1), _specials(65, 70, prefix=1),
+    _specials(64, 64, alpha=1, prefix=1),
+    # pass groups of their own widths (128 and 44): every section its own multiplier
+    ("specials_groups_128_and_44", "lz_forced", (300, 200), dict(_F, lzforce="specials", groupshift=7, prefix=1), dict(exactly=dict(distinct_special_codes=120), at_least=dict(copies_crossing_rows=1))),
+    ("specials_two_passes", "lz_forced", (300, 200), dict(_F, lzforce="specials", passes=2), dict(exactly=dict(distinct_special_codes=120))),
+    # the header's other selectors
+    _specials(200, 100, lzminlen=4), _specials(200, 100, lzminlen=7, prefix=1), _specials(200, 100, lzminlen=40, prefix=1), _specials(200, 100, lzminlen=264),
+    _specials(200, 100, lzminsym=100), _specials(200, 100, lzminsym=512, prefix=1), _specials(200, 100, lzminsym=4096, prefix=1), _specials(200, 100, lzminsym=10, hybrid="0,0,0"),
+    _specials(200, 100, lzlencfg="4,2,0", prefix=1), _specials(200, 100, lzlencfg="2,1,1", lzminsym=100), _specials(200, 100, lzlencfg="8,0,0", prefix=1),
+    _specials(200, 100, lzdistcfg="0,0,0", prefix=1), _specials(200, 100, lzdistcfg="0,0,0"), _specials(200, 100, lzdistcfg="7,3,2", prefix=1),
+    # a copy as the first symbol (zeros), then distances beyond what has been decoded
+    ("early_65x64_prefix", "lz_forced", (65, 64), dict(_F, lzforce="early", prefix=1), _EARLY),
+    ("early_8x100", "lz_forced", (8, 100), dict(_F, lzforce="early"), _EARLY),
+    ("early_groups", "lz_forced", (300, 200), dict(_F, lzforce="early", groupshift=7, prefix=1), dict(exactly=dict(first_symbol_copies=6), at_least=dict(clamped_distances=100))),
+    ("early_alpha_single", "lz_forced", (256, 256), dict(_F, lzforce="early", alpha=1, prefix=1), _EARLY),
+    # a last copy longer than what the section still needs
+    ("over_63x40", "lz_forced", (63, 40), dict(_F, lzforce="over"), dict(exactly=dict(copies_beyond_need=1))),
+    ("over_200x100_prefix", "lz_forced", (200, 100), dict(_F, lzforce="over", prefix=1), dict(exactly=dict(copies_beyond_need=1, distinct_special_codes=120))),
+    ("over_groups", "lz_forced", (300, 200), dict(_F, lzforce="over", groupshift=7, prefix=1), dict(exactly=dict(copies_beyond_need=6))),
+    # a section of 3 * 2^20 integers: the reference's window has wrapped, plain distances just below, at and above 2^20
+    ("far_1030_group_1024", "lz_forced", (1030, 1030), dict(_F, lzforce="far", groupshift=10, prefix=1), dict(at_least=dict(copies_near_2_20=100, max_section_integers=3 << 20), exactly=dict(max_distance=1 << 20))),
+    # forced copies under an RCT whose inverse then wraps (15-bit samples taken as already transformed)
+    ("specials_15_bit_rct_13", "lz_forced", (200, 100), dict(lz77=1, tree=4, rct=13, bpp=15, lzforce="specials", prefix=1), dict(exactly=dict(distinct_special_codes=120), at_least=dict(rct_wraps=1000))),
+
+    # the matcher on a picture that repeats with the period (37, 11) but for 2 % of its samples
+    ("match_special", "lz_match", (600, 300), dict(_TILED, lz77=1, lzmode="special", prefix=1), dict(exactly=dict(distinct_special_codes=120), at_least=dict(plain_copies=1000, copies_crossing_rows=100, overlapping_copies=100))),
+    ("match_special_rans", "lz_match", (600, 300), dict(_TILED, lz77=1, lzmode="special"), dict(exactly=dict(distinct_special_codes=120))),
+    ("match_plain", "lz_match", (600, 300), dict(_TILED, lz77=1, lzmode="plain"), dict(exactly=dict(special_copies=0), at_least=dict(plain_copies=10000, distance_one_copies=100))),
+    ("match_plain_prefix_long_distances", "lz_match", (600, 300), dict(_TILED, lz77=1, lzmode="plain", prefix=1, lzdistcfg="0,0,0"), dict(exactly=dict(special_copies=0), at_least=dict(max_distance=100000))),
+    ("match_overlap_single_alpha", "lz_match", (256, 256), dict(tile="5,3", lz77=1, lzmode="overlap", prefix=1, alpha=1), dict(at_least=dict(overlapping_copies=1000, max_length=1000))),
+    ("match_overlap_65", "lz_match", (65, 65), dict(tile="7,3", lz77=1, lzmode="overlap", prefix=1, rct=-1), dict(at_least=dict(overlapping_copies=20, copies_crossing_rows=20))),
+    ("match_overlap_63_rans", "lz_match", (63, 65), dict(tile="7,3", lz77=1, lzmode="overlap", rct=-1), dict(at_least=dict(overlapping_copies=20, copies_crossing_rows=20))),
+    ("match_special_minlen_5_property_tree", "lz_match", (600, 300), dict(_TILED, lz77=1, lzmode="special", tree=1, lzminlen=5), dict(at_least=dict(special_copies=1000))),
+    ("match_special_wp_tree_custom_wp", "lz_match", (600, 300), dict(_TILED, lz77=1, lzmode="special", tree=2, prefix=1, wp="random", wpat="both"), dict(at_least=dict(special_copies=1000))),
+    ("match_overlap_local_trees_two_passes", "lz_match", (520, 300), dict(tile="9,4", lz77=1, lzmode="overlap", localtree=2, passes=2, alpha=1, prefix=1), dict(at_least=dict(overlapping_copies=100))),
+    ("match_special_local_palette_group128", "lz_match", (520, 300), dict(_TILED, lz77=1, lzmode="special", localpalette=2, alpha=1, prefix=1, groupshift=7), dict(at_least=dict(special_copies=1000))),
+    ("match_plain_14_bit", "lz_match", (300, 200), dict(_TILED, lz77=1, lzmode="plain", bpp=14, prefix=1, rct=13), dict(at_least=dict(plain_copies=1000))),
+
+    # weighted-predictor parameters: in the global header (what LfGlobal codes: the whole frame where it has one group), in the
+    # pass-group headers, or in both with values per group -- only the last tells the global header's from a section's own
+    ("wp_random_single", "wp", (256, 256), dict(tree=2, wp="random"), dict()),
+    ("wp_max_single_alpha", "wp", (256, 256), dict(tree=2, wp="max", alpha=1), dict()),
+    ("wp_zero_single", "wp", (256, 256), dict(tree=2, wp="zero"), dict()),
+    ("wp_p3d_p3e_only", "wp", (256, 256), dict(tree=2, wp="16,10,0,0,0,31,31,13,12,12,12"), dict()),
+    ("wp_one_weight", "wp", (200, 256), dict(tree=2, wp="16,10,7,7,7,5,9,0,0,15,0"), dict()),
+    ("wp_global_only_groups_default", "wp", (600, 300), dict(tree=2, wp="random", wpat="global"), dict()),
+    ("wp_groups_only", "wp", (600, 300), dict(tree=2, wp="max", wpat="group"), dict()),
+    ("wp_both", "wp", (600, 300), dict(tree=2, wp="random", wpat="both"), dict()),
+    ("wp_both_local_wp_trees", "wp", (600, 300), dict(localtree=2, wp="random", wpat="both"), dict()),
+    ("wp_both_two_passes_group128", "wp", (520, 520), dict(tree=2, wp="3,29,1,30,2,28,17,1,15,2,14", wpat="both", passes=2, groupshift=7), dict()),
+    ("wp_both_14_bit_rct_13", "wp", (300, 200), dict(tree=2, wp="random", wpat="both", bpp=14, rct=13), dict()),
+    ("wp_both_15_bit_noise", "wp", (300, 200), dict(tree=2, wp="max", wpat="both", bpp=15, rct=-1, noise=32767), dict()),
+    ("wp_both_local_rct_extra_channels", "wp", (600, 300), dict(tree=2, wp="random", wpat="both", extra=3, alpha=1, localrct=7), dict()),
+    # palettes whose delta entries are predicted: the weighted predictor with parameters of the header that lists the palette, and
+    # each of the other predictors
+    ("palette_dpred_6_default_wp", "palette", (300, 200), dict(palette=3, dpred=6), dict()),
+    ("palette_dpred_6_max", "palette", (300, 200), dict(palette=3, dpred=6, wp="max"), dict()),
+    ("palette_dpred_6_random_wp_tree", "palette", (160, 120), dict(palette=3, dpred=6, wp="random", tree=2), dict()),
+    ("palette_dpred_6_prefix", "palette", (300, 200), dict(palette=3, dpred=6, wp="random", prefix=1), dict()),
+    ("palette_dpred_6_single_group", "palette", (200, 150), dict(palette=3, dpred=6, wp="5,27,30,1,19,8,31,2,15,9,4"), dict()),
+    ("local_palette_dpred_6_both", "palette", (600, 300), dict(localpalette=3, dpred=6, wp="random", wpat="both", tree=2, rct=-1), dict()),
+    ("local_palette_dpred_6_groups_two_passes", "palette", (600, 300), dict(localpalette=3, dpred=6, wp="max", wpat="group", passes=2), dict()),
+] + [
+    ("palette_dpred_%d" % k, "palette", (160, 120), dict(palette=3, dpred=k), dict()) for k in (0, 1, 2, 3, 4, 7, 8, 9, 10, 11, 12, 13)
+] + [
+    ("local_palette_dpred_%d" % k, "palette", (300, 200), dict(localpalette=3, dpred=k, groupshift=7), dict()) for k in (1, 4, 12, 13)
+] + [
+    # samples over the whole range of their depth, and beyond it
+    ("noise_15_bit", "range", (300, 200), dict(bpp=15, rct=-1, noise=32767), dict(at_least=dict(longest_symbol_bits=13))),
+    ("noise_15_bit_property_tree_prefix", "range", (300, 200), dict(bpp=15, rct=-1, noise=32767, tree=1, prefix=1), dict(at_least=dict(longest_symbol_bits=20))),
+    ("noise_15_bit_wide_tree", "range", (300, 200), dict(bpp=14, rct=-1, noise=16383, tree=5), dict()),
+    ("noise_15_bit_rct_wraps", "range", (300, 200), dict(bpp=15, rct=13, noise=32767, tree=1), dict(at_least=dict(rct_wraps=1000, samples_outside_range=1000))),
+    ("noise_15_bit_rct_10_wraps", "range", (300, 200), dict(bpp=15, rct=10, noise=32767), dict(at_least=dict(rct_wraps=1000))),
+    ("noise_15_bit_rct_19_wraps_prefix_lz77", "range", (300, 200), dict(bpp=15, rct=19, noise=32767, prefix=1, lz77=1), dict(at_least=dict(rct_wraps=1000))),
+    ("noise_signed_int16", "range", (300, 200), dict(rct=-1, noise=40000, range="-32768,32767", tree=4), dict(at_least=dict(samples_outside_range=100000))),
+    ("noise_signed_int16_alpha_12_bit_gradient", "range", (256, 256), dict(rct=-1, noise=40000, range="-32768,32767", alpha=1, prefix=1, lz77=1), dict(at_least=dict(samples_outside_range=100000))),
+    ("noise_12_bit_signed", "range", (300, 200), dict(bpp=12, rct=-1, noise=9000, range="-5000,9000", tree=1), dict(at_least=dict(samples_outside_range=10000))),
+    ("hybrid_000_prefix_noise", "range", (300, 200), dict(bpp=15, rct=-1, noise=32767, prefix=1, hybrid="0,0,0"), dict(at_least=dict(longest_symbol_bits=16))),   # (15 extra bits from residuals of 2^14 on, and a code of at least one)
+    ("hybrid_000_rans_noise", "range", (300, 200), dict(bpp=15, rct=-1, noise=32767, hybrid="0,0,0"), dict(at_least=dict(longest_symbol_bits=15))),
+    ("hybrid_522_rans", "range", (300, 200), dict(bpp=12, noise=500, hybrid="5,2,2"), dict()),
+    ("hybrid_1232_prefix", "range", (300, 200), dict(bpp=15, rct=-1, noise=32767, prefix=1, hybrid="12,3,2"), dict()),
+    # lossy-Modular style leaves: multipliers 37 and 1000, offsets +-500
+    ("coarse_leaves_position_tree", "range", (300, 200), dict(tree=6, bpp=12), dict()),
+    ("coarse_leaves_position_tree_prefix_lz77", "range", (300, 200), dict(tree=6, bpp=14, prefix=1, lz77=1, lzmode="special", noise=3000), dict(at_least=dict(copies=10))),
+    ("coarse_leaves_neighbour_tree", "range", (300, 200), dict(tree=7, bpp=12), dict()),
+    ("coarse_leaves_neighbour_tree_15_bit_noise", "range", (300, 200), dict(tree=7, bpp=15, rct=-1, noise=32767), dict()),
+
+    # a sample beyond int16: the reference's code from every decoder
+    ("overflow_prefix", "overflow", (300, 200), dict(povf=5000, prefix=1), dict(error="povf")),
+    ("overflow_first_sample", "overflow", (300, 200), dict(povf=0), dict(error="povf")),
+    ("overflow_negative_wp_tree", "overflow", (300, 200), dict(povf=777, povfto=-40000, tree=2), dict(error="povf")),
+    ("overflow_single_section_alpha_prefix_lz77", "overflow", (256, 256), dict(povf=100000, alpha=1, prefix=1, lz77=1), dict(error="povf")),
+    ("overflow_matcher", "overflow", (300, 200), dict(povf=20000, prefix=1, lz77=1, lzmode="special", tile="37,11"), dict(error="povf")),
+    ("overflow_wide_tree", "overflow", (300, 200), dict(povf=3000, tree=5), dict(error="povf")),
+    ("overflow_29_bit_residual", "overflow", (300, 200), dict(povf=5000, povfto=1 << 29, prefix=1, hybrid="0,0,0"), dict(error="povf", at_least=dict(longest_symbol_bits=33))),
+    ("overflow_28_bit_residual_negative_rans", "overflow", (300, 200), dict(povf=5000, povfto=-(1 << 28), hybrid="0,0,0"), dict(error="povf")),
+    ("overflow_30_bit_residual_refused", "overflow", (300, 200), dict(povf=5000, povfto=-(1 << 30), prefix=1, hybrid="0,0,0"), dict(error="iovf", at_least=dict(longest_symbol_bits=33))),
+]
+
+
+def _wp_traits(opts):
+    """what a row with weighted-predictor options promises about its headers and trees (the generator's stats=1 line):
+    wpat=global: one header with parameters of its own; group: several, all alike; both: at least three different sets. A tree with
+    predictor 6 / property 15 (tree=2, localtree=2) really predicts with it; a palette with delta entries lists the asked predictor"""
+    t = dict(at_least={}, exactly={}, every={})
+    if "wp" in opts:
+        at = opts.get("wpat", "global")
+        if at == "global":
+            t["exactly"].update(wp_non_default_headers=1)
+        elif at == "group":
+            t["at_least"].update(wp_non_default_headers=2)
+            t["exactly"].update(wp_distinct_sets=1)
+        else:
+            t["at_least"].update(wp_non_default_headers=3, wp_distinct_sets=3)
+    else:
+        t["exactly"].update(wp_headers=0)
+    if opts.get("tree") == 2 or opts.get("localtree") == 2:
+        t["at_least"].update(wp_predicted_samples=1000, wp_property_tests=1000)
+    if "dpred" in opts:
+        t["every"].update(palette_d_pred=opts["dpred"])
+    return t
+
+
+def _merged(a, b):
+    return {k: dict(a.get(k, {}), **b.get(k, {})) if isinstance(b.get(k, a.get(k)), dict) else b.get(k, a.get(k)) for k in set(a) | set(b)}
+
+
+MODULAR_STRESS_CASES = [(n, f, size, o, _merged(t, _wp_traits(o)) if f in ("wp", "palette") or "wp" in o else t) for n, f, size, o, t in MODULAR_STRESS_CASES]
+
+
+# Squeeze: a section's channels have different widths, so "the widest channel behind the meta channels" (the LZ77 distance
+# multiplier) is none of the easy answers. The reference stops at Squeeze with TODO: these rows are pinned by its decode of the same
+# picture coded without Squeeze (a lossless round trip, as in tests/test_squeeze.py). (name, (width, height), options)
+MODULAR_STRESS_SQUEEZE = [
+    ("match_special_squeeze_prefix", (300, 200), dict(tile="9,4", lz77=1, lzmode="special", squeeze=1, tree=1, prefix=1)),
+    ("match_special_squeeze_rans_alpha", (600, 300), dict(tile="9,4", lz77=1, lzmode="special", squeeze=1, tree=1, alpha=1)),
+    ("match_special_squeeze_position_tree", (300, 200), dict(tile="9,4", lz77=1, lzmode="special", squeeze=3, prefix=1)),
+]
+
+
+def synth_stats(mode, w, h, seed, **opts):
+    """what the generator says the stream contains (its stats=1 line); streams.synth's files are not touched"""
+    import json
+    import tempfile
+    with tempfile.NamedTemporaryFile(suffix=".jxl") as tmp:
+        r = subprocess.run([SYNTH, mode, str(w), str(h), str(seed), tmp.name] + ["%s=%s" % kv for kv in sorted(opts.items())] + ["stats=1"],
+                           check=True, stderr=subprocess.DEVNULL, stdout=subprocess.PIPE)
+        with open(tmp.name, "rb") as fp:
+            data = fp.read()
+    return json.loads(r.stdout.decode()), data

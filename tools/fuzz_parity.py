@@ -59,6 +59,17 @@ def pick_vardct(r):
         o["alpha"] = 1
         if r.random() < .4: o["fullheader"] = 1; o["noxyb"] = r.choice([0, 1])
     elif r.random() < .15: o["bpp"] = r.choice([9, 10, 12, 15])
+    # LZ77 copies at distances other than "the value before"; the weighted predictor, with parameters of its own, in the frame's Modular
+    # sub-images (the generator's refusals decide what combines)
+    if "hflz77" in o and r.random() < .6:
+        o["hflzmode"] = r.choice(["plain", "overlap"])
+        if r.random() < .3: o["hflzminlen"] = r.choice([4, 5, 9, 40])
+        if r.random() < .3: o["hflzdistcfg"] = r.choice(["0,0,0", "4,0,0", "5,2,2"])
+    if r.random() < .2:
+        o["lftree"] = 4
+        if r.random() < .7:
+            o["wp"] = r.choice(["random", "max", "zero"])
+            o["wpat"] = r.choice(["group", "both", "global"])    # (global / both: refused without alpha)
     # an encode of a picture instead of coefficient-domain synthesis (the generator takes it with one pass, transforms up to 64x64,
     # default chroma-from-luma)
     if r.random() < .3 and "passes" not in o and "cfl" not in o and o.get("maxlog", 6) <= 6:
@@ -85,6 +96,26 @@ def pick_modular(r):
     if r.random() < .3: o["alpha"] = 1
     elif r.random() < .2: o["bpp"] = r.choice([9, 10, 12, 14])
     if r.random() < .1: o["xyb"] = 1
+    # streams outside an encoder's habits (tests/test_modular_stress.py); the generator's own refusals decide which of them combine
+    if "lz77" in o and r.random() < .6:
+        if r.random() < .3 and "palette" not in o and "localpalette" not in o and "localtree" not in o:
+            o["tree"] = 4; o["lzforce"] = r.choice(["specials", "early", "over"])
+        else:
+            o["lzmode"] = r.choice(["special", "plain", "overlap"])
+            o["tile"] = "%d,%d" % (r.randrange(1, 60), r.randrange(1, 20))
+        if r.random() < .3: o["lzminlen"] = r.choice([4, 5, 8, 9, 40])
+        if r.random() < .3: o["lzminsym"] = r.choice([512, 4096] if "prefix" in o else [100, 200])
+        if r.random() < .3: o["lzdistcfg"] = r.choice(["0,0,0", "4,0,0", "7,3,2" if "prefix" in o else "5,2,2"])
+    if r.random() < .3 and (o.get("tree") == 2 or o.get("localtree") == 2 or o.get("palette") == 3 or o.get("localpalette") == 3):
+        o["wp"] = r.choice(["random", "max", "zero"])
+        if r.random() < .6: o["wpat"] = r.choice(["group", "both"])      # (refused for a frame of one group)
+        if o.get("palette") == 3 or o.get("localpalette") == 3: o["dpred"] = r.choice([6, 6, 6] + list(range(14)))
+    if r.random() < .15 and "alpha" not in o and "palette" not in o and "localpalette" not in o and "lzforce" not in o:
+        o["bpp"] = 15; o["noise"] = r.choice([300, 5000, 32767])
+        if r.random() < .7 or "rct" not in o: o["rct"] = -1                # (a forward RCT of such samples leaves int16: refused)
+        o.pop("localrct", None)
+    if r.random() < .1 and o.get("tree") is None: o["tree"] = r.choice([6, 7])
+    if r.random() < .05 and "lzforce" not in o: o["povf"] = r.randrange(0, 5000)
     return o
 
 

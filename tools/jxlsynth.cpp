@@ -19,6 +19,7 @@
 #include "jxlsynth_common.hpp"
 #include "jxlsynth_modular.hpp"
 #include "jxlsynth_forward.hpp"
+#include "jxlsynth_lz77.hpp"
 #include <cmath>
 #include <map>
 #include <functional>
@@ -34,6 +35,33 @@ struct Options {
 	double getd(const char *k, double def) const { auto it = kv.find(k); return it == kv.end() ? def : atof(it->second.c_str()); }
 	std::string gets(const char *k, const char *def) const { auto it = kv.find(k); return it == kv.end() ? def : it->second; }
 };
+
+// wp=random|max|zero|<eleven numbers>: weighted-predictor parameters other than the defaults (false: the option is absent)
+static bool parse_wp(const Options &opt, uint64_t seed, WPParams &wp_base, const char *mode) {
+	if (!opt.kv.count("wp")) return false;
+	const std::string v = opt.gets("wp", "");
+	int *f[11] = {&wp_base.p1, &wp_base.p2, &wp_base.p3[0], &wp_base.p3[1], &wp_base.p3[2], &wp_base.p3[3], &wp_base.p3[4], &wp_base.w[0], &wp_base.w[1], &wp_base.w[2], &wp_base.w[3]};
+	if (v == "random") { SplitMix64 r(seed ^ 0x57505750ull); for (int i = 0; i < 11; ++i) *f[i] = (int) r.below(i < 7 ? 32 : 16); }
+	else if (v == "max") for (int i = 0; i < 11; ++i) *f[i] = i < 7 ? 31 : 15;
+	else if (v == "zero") for (int i = 0; i < 11; ++i) *f[i] = 0;
+	else if (sscanf(v.c_str(), "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10]) != 11) dief("%s: wp=random|max|zero|p1,p2,p3a,p3b,p3c,p3d,p3e,w0,w1,w2,w3", mode);
+	for (int i = 0; i < 11; ++i) if (*f[i] < 0 || *f[i] > (i < 7 ? 31 : 15)) dief("%s: wp: p1, p2, p3* are 5-bit and w* 4-bit fields", mode);
+	return true;
+}
+
+// (stats=1) the headers that carry weighted-predictor parameters of their own, and the use the writer's trees made of the predictor
+static std::string wp_stats_json() {
+	std::vector<std::array<int, 11>> sets = wp_headers_written();
+	const size_t headers = sets.size();
+	size_t non_default = 0;
+	for (const auto &a : sets) { WPParams p; p.p1 = a[0]; p.p2 = a[1]; for (int i = 0; i < 5; ++i) p.p3[i] = a[2 + i]; for (int i = 0; i < 4; ++i) p.w[i] = a[7 + i]; non_default += !wp_is_default(p); }
+	std::sort(sets.begin(), sets.end());
+	sets.erase(std::unique(sets.begin(), sets.end()), sets.end());
+	char tmp[256];
+	snprintf(tmp, sizeof tmp, "\"wp_headers\": %zu, \"wp_non_default_headers\": %zu, \"wp_distinct_sets\": %zu, \"wp_predicted_samples\": %llu, \"wp_property_tests\": %llu",
+	         headers, non_default, sets.size(), (unsigned long long) wp_predicted_samples(), (unsigned long long) wp_property_tests());
+	return tmp;
+}
 
 // ------------------------------------------------------------------------------------------------
 // procedural source picture (deterministic, cheap): low-frequency sinusoids + value noise +
@@ -119,7 +147,7 @@ static uint32_t f16_bits(float v) {
 // dq=1: the dequantisation matrices of HfGlobal in their coded forms (j40.h:4696-4760) instead of "all default": band
 // parameters for DCT8, the Hornuss, DCT2x2, DCT4x4, DCT4x8 and AFV forms (the reference accepts the coded forms only for the
 // 8x8 matrices, band parameters included: HOW[6].requires8x8, j40.h:4751); values near the library's, rounded to halves. Scaled parameters are stored divided by 64.
-static void write_dq_matrices(BitWriter &bw, std::vector<std::pair<int, StreamEncoder>> &raw) {
+static void write_dq_matrices(BitWriter &bw, std::vector<std::pair<int, StreamEncoder>> &raw, const std::function<const WPParams *(int)> &wp_of) {
 	auto params = [&](const std::vector<std::array<float, 3>> &p, size_t first, size_t count, size_t scaled) {   // channel-major, as read (j40.h:4738)
 		for (int c = 0; c < 3; ++c) for (size_t j = 0; j < count; ++j) bw.put(f16_bits(p[first + j][(size_t) c] / (j < scaled ? 64.0f : 1.0f)), 16);
 	};
@@ -146,7 +174,7 @@ static void write_dq_matrices(BitWriter &bw, std::vector<std::pair<int, StreamEn
 			if (!enc) { bw.put(0, 3); break; }   // library
 			// raw (j40.h:4712-4745): a denominator, then the weights times it as a three-channel Modular image
 			bw.put(7, 3); bw.put(f16_bits(2.0f), 16);
-			write_modular_header(bw, true, nullptr, {});
+			write_modular_header(bw, true, wp_of(100 + idx), {});
 			enc->flush(bw);
 		} }
 	}
@@ -470,7 +498,30 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 
 	// ---- global MA tree: splits on stream index (property 1) and channel (property 0) ----
 	MATree tree;
-	if (opt.geti("lftree", 0) == 2) {
+	// wp= (with lftree=4, the tree that uses the weighted predictor): parameters other than the defaults in the Modular headers this
+	// writer emits -- wpat=global: the global header alone (it exists with alpha=1 and decodes nothing: whoever takes ITS values for a
+	// sub-image is wrong), group (default): every sub-image header (LfGroup's two, the raw dequantisation matrices, the alpha
+	// sub-images) the same values, both: the global header and values of its own in every sub-image header
+	WPParams wp_base;
+	const bool custom_wp = parse_wp(opt, seed, wp_base, "vardct");
+	const std::string wpat = opt.gets("wpat", "group");
+	if (custom_wp && opt.geti("lftree", 0) != 4) die("vardct: wp= changes nothing unless the tree uses the weighted predictor: lftree=4");
+	if (!custom_wp && opt.kv.count("wpat")) die("vardct: wpat places the parameters wp= gives");
+	if (custom_wp && wpat != "global" && wpat != "group" && wpat != "both") die("vardct: wpat=global|group|both");
+	if (custom_wp && wpat != "group" && !opt.geti("alpha", 0)) die("vardct: the global Modular header exists with extra channels only: wpat=global|both want alpha=1");
+	std::map<int, WPParams> wp_store;   // header id -> its parameters: LfGroup gg 2 gg (LF image) and 2 gg + 1 (metadata), raw matrix idx 100 + idx, alpha of group g 200 + g
+	const std::function<const WPParams *(int)> wp_of = [&](int k) -> const WPParams * {
+		if (!custom_wp || wpat == "global") return nullptr;
+		if (!wp_store.count(k)) wp_store[k] = wpat == "both" ? wp_derived(wp_base, k) : wp_base;
+		return &wp_store[k];
+	};
+	const WPParams wp_default;
+	auto wp_in = [&](int k) -> const WPParams & { const WPParams *p = wp_of(k); return p ? *p : wp_default; };
+	if (opt.geti("lftree", 0) == 4) {
+		// lftree=4: the weighted predictor and its error property on every channel of every sub-image
+		int a = tree.branch(15, 4, tree.leaf(6), tree.leaf(6, 1)), b = tree.branch(15, -4, tree.leaf(5), tree.leaf(6));
+		tree.finalise(tree.branch(0, 0, a, b));
+	} else if (opt.geti("lftree", 0) == 2) {
 		// lftree=2: every LfGroup channel under ONE test of a sample property over two leaves that predict alike (what libjxl's fixed LF
 		// trees look like, with other properties and predictors), offsets and multipliers on some
 		auto pair = [&](int prop, int thr, int pred, int off = 0, int mshift = 0, int mbits = 0) { int a = tree.leaf(pred, off, mshift, mbits), b = tree.leaf(pred, off, mshift, mbits); return tree.branch(prop, thr, a, b); };
@@ -533,15 +584,14 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		gspec.log_alpha = 8;
 		for (auto &c : gspec.cfg) c = HybridCfg{4, 2, 0};
 	}
-	WPParams wpp;
 	std::vector<StreamEncoder> lfq_enc, meta_enc;
 	for (int ggi = 0; ggi < num_lf_groups; ++ggi) {
 		LfGroupW &gg = ggs[(size_t) ggi];
 		lfq_enc.emplace_back(gspec); meta_enc.emplace_back(gspec);
 		std::vector<Channel> ch{gg.lfq[0], gg.lfq[1], gg.lfq[2]};
-		for (int c = 0; c < 3; ++c) encode_channel(tree, ch, c, 1 + ggi, wpp, lfq_enc.back());
+		for (int c = 0; c < 3; ++c) encode_channel(tree, ch, c, 1 + ggi, wp_in(2 * ggi), lfq_enc.back());
 		std::vector<Channel> mc{gg.xfromy, gg.bfromy, gg.blockinfo, gg.sharp};
-		for (int c = 0; c < 4; ++c) encode_channel(tree, mc, c, 1 + 2 * num_lf_groups + ggi, wpp, meta_enc.back());
+		for (int c = 0; c < 4; ++c) encode_channel(tree, mc, c, 1 + 2 * num_lf_groups + ggi, wp_in(2 * ggi + 1), meta_enc.back());
 		count_stream(gspec, lfq_enc.back()); count_stream(gspec, meta_enc.back());
 	}
 
@@ -552,7 +602,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		std::vector<Channel> mc;
 		for (int c = 0; c < 3; ++c) { Channel m(ncols, nrows); for (int y = 0; y < nrows; ++y) for (int x = 0; x < ncols; ++x) m.at(x, y) = 300 + 90 * (x + y) * (c + 1) + 17 * ((x * 5 + y * 3 + c) & 7); mc.push_back(m); }
 		dq_raw.emplace_back(idx, StreamEncoder(gspec));
-		for (int c = 0; c < 3; ++c) encode_channel(tree, mc, c, 1 + 3 * num_lf_groups + idx, wpp, dq_raw.back().second);
+		for (int c = 0; c < 3; ++c) encode_channel(tree, mc, c, 1 + 3 * num_lf_groups + idx, wp_in(100 + idx), dq_raw.back().second);
 		count_stream(gspec, dq_raw.back().second);
 	}
 
@@ -572,7 +622,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			std::vector<Channel> sub(1, Channel(gw, gh));
 			for (int y = 0; y < gh; ++y) for (int x = 0; x < gw; ++x) sub[0].at(x, y) = alpha.at(gx + x, gy + y);
 			alpha_enc.emplace_back(gspec);
-			encode_channel(tree, sub, 0, 1 + 3 * num_lf_groups + 17 + g, wpp, alpha_enc.back());
+			encode_channel(tree, sub, 0, 1 + 3 * num_lf_groups + 17 + g, wp_in(200 + g), alpha_enc.back());
 			count_stream(gspec, alpha_enc.back());
 		}
 	}
@@ -581,6 +631,20 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	const int ctx_per_preset = 495 * nb_block_ctx;
 	const int hf_prefix = opt.geti("hfprefix", 0);          // HF coefficient streams with prefix codes instead of rANS
 	const int hf_lz77 = opt.geti("hflz77", 0);              // ... with LZ77 copies for runs of equal small values
+	// hflzmode=plain|overlap (with hflz77=1): the matcher instead of the run-length pass -- the longest match at any distance / matches
+	// that overlap themselves (1 < distance < length) first; hflzminlen=, hflzdistcfg=a,b,c: the header's min_length, the distance
+	// cluster's hybrid integers. (Special distance codes exist under a distance multiplier only: Modular streams, lzmode=special.)
+	int hf_lzmode = LZ_RUNS;
+	{
+		const std::string m = opt.gets("hflzmode", "runs");
+		hf_lzmode = m == "runs" ? LZ_RUNS : m == "plain" ? LZ_PLAIN : m == "overlap" ? LZ_OVERLAP : -1;
+		if (m == "special") die("vardct: coefficient streams have no distance multiplier and so no special distance codes: hflzmode=runs|plain|overlap");
+		if (hf_lzmode < 0) die("vardct: hflzmode=runs|plain|overlap");
+		if ((hf_lzmode != LZ_RUNS || opt.kv.count("hflzminlen") || opt.kv.count("hflzdistcfg")) && !hf_lz77) die("vardct: hflzmode / hflzminlen / hflzdistcfg describe LZ77 copies: they want hflz77=1");
+	}
+	const int hf_lzminlen = opt.geti("hflzminlen", 3);
+	if (hf_lzminlen < 3 || hf_lzminlen > 264) die("vardct: hflzminlen 3..264");
+	LzStats hf_lzstats;
 	std::vector<CodeSpecW> cspec((size_t) num_passes);
 	std::vector<std::vector<StreamEncoder>> hf_enc((size_t) num_passes);
 	std::vector<int> group_preset((size_t) num_groups);
@@ -609,11 +673,18 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		}
 		if (hf_lz77) { map.push_back((uint8_t) nclusters); ++nclusters; cs.lz77 = true; }   // the distance context gets its own cluster
 		cs.init(nctx, map, nclusters);
-		cs.lz_min_symbol = 224; cs.lz_min_length = 3; cs.lz_len_cfg = HybridCfg{0, 0, 0};
+		cs.lz_min_symbol = 224; cs.lz_min_length = hf_lzminlen; cs.lz_len_cfg = HybridCfg{0, 0, 0};
 		cs.use_prefix = hf_prefix != 0;
 		cs.log_alpha = (hf_lz77 || hf_prefix) ? 8 : log_alpha;
 		if (!hf_prefix && (cs.log_alpha < 5 || cs.log_alpha > 8)) dief("vardct: logalpha=%d; an rANS alphabet has 2^5..2^8 symbols", cs.log_alpha);
 		for (int c = 0; c < nclusters; ++c) cs.cfg[(size_t) c] = (c & 1) && !hf_lz77 ? HybridCfg{4, 1, 1} : HybridCfg{4, 2, 0};
+		if (opt.kv.count("hflzdistcfg")) {
+			HybridCfg d;
+			const int las = hf_prefix ? 15 : 8;
+			if (sscanf(opt.gets("hflzdistcfg", "").c_str(), "%d,%d,%d", &d.split_exp, &d.msb, &d.lsb) != 3 || d.split_exp < 0 || d.split_exp >= las || d.msb < 0 || d.msb > d.split_exp || d.lsb < 0 || d.lsb > d.split_exp - d.msb)
+				dief("vardct: hflzdistcfg=<split_exp>,<msb>,<lsb> with split_exp < %d, msb <= split_exp, lsb <= split_exp - msb", las);
+			cs.cfg[(size_t) nclusters - 1] = d;
+		}
 		if (have_forced_cfg) {
 			// j40.h:2297-2311: split_exp is read with at_most(log_alpha_size) (15 for prefix codes), msb with at_most(split_exp), lsb with
 			// at_most(split_exp - msb), and the last two are not coded at all when split_exp == log_alpha_size
@@ -651,6 +722,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		for (int g = 0; g < num_groups; ++g) {
 			hf_enc[(size_t) pass].emplace_back(cspec[(size_t) pass]);
 			StreamEncoder &enc = hf_enc[(size_t) pass].back();
+			std::vector<Tok> hf_src;
+			if (hf_lz77 && hf_lzmode != LZ_RUNS) enc.src = &hf_src;
 			const int grow = g / gcols, gcol = g % gcols, ggi = (grow / 8) * ggcols + gcol / 8;
 			const LfGroupW &gg = ggs[(size_t) ggi];
 			const int gx8 = (gcol % 8) * 32, gy8 = (grow % 8) * 32;
@@ -742,7 +815,16 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 					}
 				}
 			}
-			if (hf_lz77) {
+			if (hf_lz77 && hf_lzmode != LZ_RUNS) {
+				// the matcher of jxlsynth_lz77.hpp over this stream's integers (coefficient streams have no distance multiplier: the
+				// symbol codes distance - 1, j40.h:2829); nothing here lies in rows or channels
+				std::vector<uint32_t> ctxs, vals;
+				for (const Tok &t : hf_src) { ctxs.push_back(t.ctx); vals.push_back(t.value); }
+				const std::vector<uint32_t> nowhere(vals.size(), 0);
+				LzParams lp; lp.mode = hf_lzmode; lp.dist_mult = 0;
+				enc.items.clear(); enc.src = nullptr;
+				lz77_match(enc, cspec[(size_t) pass], lp, ctxs, vals, nowhere, nowhere, hf_lzstats);
+			} else if (hf_lz77) {
 				// run-length pass: a run of >= 3 identical small values after its first occurrence becomes one copy with
 				// distance 1 (dist_mult is 0 for coefficient streams, so the coded distance value is distance - 1, j40.h:2851)
 				const CodeSpecW &cs = cspec[(size_t) pass];
@@ -762,6 +844,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 						const uint32_t lzcl = cs.cluster_map[(size_t) cs.total_dist() - 1];
 						HToken d = hybrid_encode(0, cs.cfg[lzcl]);
 						out.push_back({lzcl, d.token, d.extra, (uint8_t) d.nextra});
+						++hf_lzstats.copies; ++hf_lzstats.plain_copies; ++hf_lzstats.distance_one; hf_lzstats.max_distance = std::max<uint64_t>(hf_lzstats.max_distance, 1);
 						i = j;
 					} else i = i + 1;
 				}
@@ -806,7 +889,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		write_code_spec(bw, treespec); tree_enc.flush(bw);
 		write_code_spec(bw, gspec);
 		if (with_alpha) {   // the global Modular image (extra channels only): header, no channel decoded here (j40.h:6329-6338)
-			write_modular_header(bw, true, nullptr, {});
+			write_modular_header(bw, true, custom_wp && wpat != "group" ? &wp_base : nullptr, {});
 			StreamEncoder none(gspec); none.flush(bw);
 		}
 		bw.pad();
@@ -816,17 +899,17 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		LfGroupW &gg = ggs[(size_t) ggi];
 		BitWriter bw;
 		bw.put((uint64_t) extra_prec, 2);                        // extra_precision
-		write_modular_header(bw, true, nullptr, {});
+		write_modular_header(bw, true, wp_of(2 * ggi), {});
 		lfq_enc[(size_t) ggi].flush(bw);
 		bw.put((uint64_t) (gg.vbs.size() - 1), ceil_lg((uint32_t) (gg.w8 * gg.h8)));
-		write_modular_header(bw, true, nullptr, {});
+		write_modular_header(bw, true, wp_of(2 * ggi + 1), {});
 		meta_enc[(size_t) ggi].flush(bw);
 		bw.pad();
 		sections.push_back(bw.bytes);
 	}
 	{   // HfGlobal + HfPass (j40.h:6819)
 		BitWriter bw;
-		if (opt.geti("dq", 0)) { bw.put(0, 1); write_dq_matrices(bw, dq_raw); }
+		if (opt.geti("dq", 0)) { bw.put(0, 1); write_dq_matrices(bw, dq_raw, wp_of); }
 		else bw.put(1, 1);                                       // all dequantisation matrices default
 		bw.put((uint64_t) (num_presets - 1), ceil_lg((uint32_t) num_groups));
 		for (int pass = 0; pass < num_passes; ++pass) {
@@ -854,7 +937,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		BitWriter bw;
 		bw.put((uint64_t) group_preset[(size_t) g], ceil_lg((uint32_t) num_presets));
 		hf_enc[(size_t) pass][(size_t) g].flush(bw);
-		if (with_alpha) { write_modular_header(bw, true, nullptr, {}); alpha_enc[(size_t) g].flush(bw); }
+		if (with_alpha) { write_modular_header(bw, true, wp_of(200 + g), {}); alpha_enc[(size_t) g].flush(bw); }
 		bw.pad();
 		sections.push_back(bw.bytes);
 	}
@@ -983,6 +1066,10 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	}
 	if (!write_file(out, file)) die("cannot write output");
 	double bpp = 8.0 * (double) file.size() / ((double) W * H);
+	if (opt.geti("stats", 0))
+		printf("{\"copies\": %llu, \"plain_copies\": %llu, \"overlapping_copies\": %llu, \"distance_one_copies\": %llu, \"max_distance\": %llu, \"max_length\": %llu, %s}\n",
+		       (unsigned long long) hf_lzstats.copies, (unsigned long long) hf_lzstats.plain_copies, (unsigned long long) hf_lzstats.overlapping, (unsigned long long) hf_lzstats.distance_one,
+		       (unsigned long long) hf_lzstats.max_distance, (unsigned long long) hf_lzstats.max_length, wp_stats_json().c_str());
 	fprintf(stderr, "vardct %dx%d: %zu bytes (%.3f bpp), %d groups, %d LF groups, %d passes\n", W, H, file.size(), bpp, num_groups, num_lf_groups, num_passes);
 	return 0;
 }
@@ -1025,11 +1112,54 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	if (bpp < 8 || bpp > 15) die("modular: bpp 8..15");
 	if (bpp != 8 && alpha) die("modular: the default alpha channel has 8 bits; the reference refuses a different colour depth");
 	const int gdim = 1 << group_shift;
+	// ---- streams outside an encoder's habits (tests/test_modular_stress.py); every option defaults to what was written before ----
+	// lzmode=special|plain|overlap (with lz77=1): a matcher over the decoded integers instead of the run-length pass; it prefers
+	// distances a special code stands for / codes every distance plain / prefers copies that overlap themselves (1 < distance < length).
+	// lzforce=specials|early|over|far: copies that define the samples they cover (jxlsynth_lz77.hpp; tree=4, no palette).
+	// lzminlen=, lzminsym=, lzlencfg=a,b,c, lzdistcfg=a,b,c: the header's other selectors and hybrid-integer configurations;
+	// hybrid=a,b,c: the configuration of the residual clusters.
+	LzParams lzp;
+	{
+		const std::string m = opt.gets("lzmode", "runs"), f = opt.gets("lzforce", "none");
+		lzp.mode = m == "runs" ? LZ_RUNS : m == "special" ? LZ_SPECIAL : m == "plain" ? LZ_PLAIN : m == "overlap" ? LZ_OVERLAP : -1;
+		lzp.force = f == "none" ? FORCE_NONE : f == "specials" ? FORCE_SPECIALS : f == "early" ? FORCE_EARLY : f == "over" ? FORCE_OVER : f == "far" ? FORCE_FAR : -1;
+		if (lzp.mode < 0) die("modular: lzmode=runs|special|plain|overlap");
+		if (lzp.force < 0) die("modular: lzforce=none|specials|early|over|far");
+		if ((lzp.mode != LZ_RUNS || lzp.force != FORCE_NONE || opt.kv.count("lzminlen") || opt.kv.count("lzminsym") || opt.kv.count("lzlencfg") || opt.kv.count("lzdistcfg")) && !lz77)
+			die("modular: lzmode / lzforce / lzminlen / lzminsym / lzlencfg / lzdistcfg describe LZ77 copies: they want lz77=1");
+		if (lzp.force != FORCE_NONE && (tree_kind != 4 || palette || opt.geti("squeeze", 0) || opt.geti("localpalette", 0) || opt.geti("localtree", 0)))
+			die("modular: lzforce defines samples by the copies that cover them: that needs the zero predictor in one leaf (tree=4) and neither palette, squeeze nor local trees");
+		if (lzp.force != FORCE_NONE && lzp.mode != LZ_RUNS) die("modular: lzforce writes its own copies; lzmode chooses among matches of a picture");
+		lzp.literal_range = 1u << bpp;
+	}
+	auto parse_cfg = [&](const char *key, HybridCfg def, int log_alpha_size) {
+		if (!opt.kv.count(key)) return def;
+		HybridCfg c;
+		if (sscanf(opt.gets(key, "").c_str(), "%d,%d,%d", &c.split_exp, &c.msb, &c.lsb) != 3) dief("modular: %s=<split_exp>,<msb>,<lsb>", key);
+		if (c.split_exp < 0 || c.split_exp > log_alpha_size || c.msb < 0 || c.msb > c.split_exp || c.lsb < 0 || c.lsb > c.split_exp - c.msb) dief("modular: %s: split_exp <= %d, msb <= split_exp, lsb <= split_exp - msb", key, log_alpha_size);
+		if (c.split_exp == log_alpha_size && (c.msb || c.lsb)) dief("modular: %s: split_exp == %d leaves msb and lsb uncoded (0)", key, log_alpha_size);
+		return c;
+	};
+	const int lz_min_length = opt.geti("lzminlen", 3), lz_min_symbol = opt.geti("lzminsym", 224);
+	if (lz_min_length < 3 || lz_min_length > 264) die("modular: lzminlen 3..264 (U32(3, 4, 5 + u(2), 9 + u(8)))");
+	if (lz_min_symbol != 224 && lz_min_symbol != 512 && lz_min_symbol != 4096 && (lz_min_symbol < 8 || lz_min_symbol >= 8 + 32768)) die("modular: lzminsym 224, 512, 4096 or 8 + u(15)");
+	if (!use_prefix && lz77 && lz_min_symbol >= 256) die("modular: rANS alphabets end at 256 here: lzminsym >= 256 wants prefix=1");
+	// wp=random|max|zero|<eleven numbers>: weighted-predictor parameters other than the defaults; wpat=global (the global Modular header:
+	// what LfGlobal codes, and a global palette's prediction), group (every pass-group header, the same values) or both (the global
+	// header, and in every pass-group header values of its own derived from the group's index)
+	WPParams wp_base;
+	const bool custom_wp = parse_wp(opt, seed, wp_base, "modular");
+	const std::string wpat = opt.gets("wpat", "global");
+	if (custom_wp) {
+		if (wpat != "global" && wpat != "group" && wpat != "both") die("modular: wpat=global|group|both");
+		if (opt.geti("squeeze", 0)) die("modular: wp does not combine with squeeze (the sections' headers are shared there)");
+	} else if (opt.kv.count("wpat")) die("modular: wpat places the parameters wp= gives");
 	// repeat=K: the frame is the (W/K) x (H/K) picture tiled K x K times. Only the base picture is synthesised and encoded; its
 	// group sections are reused (no tree here looks at the stream index), which makes 16384 x 16384 streams cheap to write
 	const int num_passes = opt.geti("passes", 1);
 	const int repeat = opt.geti("repeat", 1);
 	if (repeat > 1 && num_passes > 1) die("repeat and passes do not combine");
+	if (repeat > 1 && (lzp.mode != LZ_RUNS || lzp.force != FORCE_NONE)) die("modular: lzmode / lzforce do not combine with repeat (the base picture's sections would be written for a narrower frame's distance multiplier)");
 	// squeeze=1: a Squeeze transform with the default parameter list behind the RCT (the "progressive" lossless form); 2: the same list
 	// written out explicitly; 3: a short explicit list with residual channels appended (not in place) and partial channel ranges.
 	// Squeeze couples neighbouring groups, so with repeat=K the base picture is tiled first and the whole frame is transformed;
@@ -1048,6 +1178,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	const int gcols = (W + gdim - 1) / gdim, grows = (H + gdim - 1) / gdim, num_groups = gcols * grows;
 	const int num_lf_groups = ((W + 8 * gdim - 1) / (8 * gdim)) * ((H + 8 * gdim - 1) / (8 * gdim));
 	const bool single = num_groups == 1;
+	if (custom_wp && single && wpat != "global") die("modular: a frame of one group has no pass-group headers: wpat=global");
 	if (single && opt.geti("passes", 1) > 1) die("modular: one group with several passes is not generated (the frame would not be a single section)");
 	// extra=K: K more extra channels (type depth, same bit depth) ahead of the alpha channel, so that alpha is not the first one
 	const int extra = opt.geti("extra", 0);
@@ -1061,13 +1192,27 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	std::vector<Channel> ch;
 	for (int c = 0; c < nch; ++c) ch.emplace_back(pic_w, pic_h);
 	const int colour0 = 0;               // index of the first colour channel
+	// tile=px,py: the picture repeats with that period (matches in the same row, in rows above and diagonal ones), tilenoise=K per
+	// mille of the samples differ from their tile's; noise=A adds uniform noise of that amplitude; range=lo,hi clamps the samples
+	// there instead of to [0, 2^bpp) (samples the RCT has not been applied to may be anything in int16)
+	int tile_px = 0, tile_py = 0;
+	if (opt.kv.count("tile") && (sscanf(opt.gets("tile", "").c_str(), "%d,%d", &tile_px, &tile_py) != 2 || tile_px < 1 || tile_py < 1)) die("modular: tile=<px>,<py>");
+	const int tile_noise = opt.geti("tilenoise", 20), noise = opt.geti("noise", 0);
+	int range_lo = 0, range_hi = (1 << bpp) - 1;
+	if (opt.kv.count("range") && (sscanf(opt.gets("range", "").c_str(), "%d,%d", &range_lo, &range_hi) != 2 || range_lo > range_hi || range_lo < -32768 || range_hi > 32767)) die("modular: range=<lo>,<hi> within int16");
+	if (noise < 0 || noise > 65535) die("modular: noise 0..65535");
 	for (int y = 0; y < pic_h; ++y) for (int x = 0; x < pic_w; ++x) {
-		float rgb[3]; pic.rgb((float) x, (float) y, rgb);
+		const int xs = tile_px ? x % tile_px : x, ys = tile_py ? y % tile_py : y;
+		float rgb[3]; pic.rgb((float) xs, (float) ys, rgb);
 		// flat regions + a bit of texture so that run-lengths and the predictors both get work
 		for (int c = 0; c < 3; ++c) {
 			int v = (int) (rgb[c] * 255.0f);
-			v = (v / 6) * 6 + (int) (Picture::hash01((uint64_t) x * 7919 + (uint64_t) y * 104729 + (uint64_t) c + seed) < 0.08f);
-			ch[(size_t) (colour0 + c)].at(x, y) = std::min(255, std::max(0, v)) * ((1 << bpp) - 1) / 255;
+			v = (v / 6) * 6 + (int) (Picture::hash01((uint64_t) xs * 7919 + (uint64_t) ys * 104729 + (uint64_t) c + seed) < 0.08f);
+			v = std::min(255, std::max(0, v)) * ((1 << bpp) - 1) / 255;
+			if (tile_px && Picture::hash01((uint64_t) x * 611953 + (uint64_t) y * 15485863 + (uint64_t) c * 31 + seed) * 1000.0f < (float) tile_noise) v ^= 1 + (int) (Picture::hash01((uint64_t) x * 31 + (uint64_t) y * 17 + seed) * 6.0f);
+			if (noise) v += (int) (Picture::hash01((uint64_t) x * 2654435761ull + (uint64_t) y * 40503 + (uint64_t) c * 977 + seed * 13) * (float) (2 * noise + 1)) - noise;
+			if (tile_px || noise || opt.kv.count("range")) v = std::min(range_hi, std::max(range_lo, v));
+			ch[(size_t) (colour0 + c)].at(x, y) = v;
 		}
 		for (int k = 0; k < extra; ++k) ch[(size_t) (3 + k)].at(x, y) = (((x >> 3) * (k + 2) + (y >> 2)) & 31) * ((1 << bpp) - 1) / 31;
 		if (alpha) ch[(size_t) (3 + extra)].at(x, y) = ((x / 37 + y / 29) & 3) == 0 ? 128 + ((x * 3 + y) & 63) : 255;
@@ -1090,6 +1235,11 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	simple4_mode() = opt.geti("simple4", 0);
 
 	// ---- global transforms (coded order = forward order; the decoder undoes them last to first) ----
+	// dpred=0..13: the predictor of a palette's delta entries (palette=3 / localpalette=3; 6 is the weighted one, with the parameters
+	// of the header that lists the palette)
+	const int dpred = opt.geti("dpred", 5);
+	if (dpred < 0 || dpred > 13) die("modular: dpred 0..13");
+	if (opt.kv.count("dpred") && palette != 3 && opt.geti("localpalette", 0) != 3) die("modular: dpred belongs to a palette with delta entries (palette=3 or localpalette=3)");
 	std::vector<TransformW> transforms;
 	if (palette) {
 		// replace the colour channels by a palette (meta channel 0) + an index channel
@@ -1108,7 +1258,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		next.push_back(idx);
 		for (int c = 3; c < nch; ++c) next.push_back(ch[(size_t) c]);
 		ch.swap(next);
-		TransformW t; t.kind = 1; t.begin_c = colour0; t.num_c = 3; t.nb_colours = nb_colours; t.nb_deltas = nb_deltas; t.d_pred = palette == 3 ? 5 : 0;
+		TransformW t; t.kind = 1; t.begin_c = colour0; t.num_c = 3; t.nb_colours = nb_colours; t.nb_deltas = nb_deltas; t.d_pred = palette == 3 ? dpred : 0;
 		transforms.push_back(t);
 	} else if (rct >= 0) {
 		if (rct / 7 == 0 && rct % 7 != 2) forward_rct(ch, colour0, rct);   // other types: the picture is taken as already transformed
@@ -1153,6 +1303,14 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 			int a = tree.branch(15, 8, l0, l1);       // max weighted-predictor error
 			int b = tree.branch(15, -8, l2, l3);
 			root = tree.branch(0, 1, a, b);
+		} else if (tree_kind == 6 || tree_kind == 7) {
+			// lossy-Modular style leaves: multipliers 37 and 1000, offsets +-500. 6 walks a sample's position only (the two-pass decoder's
+			// kind of tree, the leaf changing along a row), 7 looks at neighbours as well
+			int l0 = tree.leaf(5, 500, 0, 36), l1 = tree.leaf(1, -500, 3, 124), l2 = tree.leaf(2, 0, 0, 36), l3 = tree.leaf(13, -3, 1, 0), l4 = tree.leaf(4, 250, 0, 36);
+			int a = tree.branch(3, 40, l0, l1);                                        // x
+			int b = tree.branch(tree_kind == 6 ? 2 : 5, 33, l2, l3);                   // y / |W|
+			int c = tree.branch(tree_kind == 6 ? 3 : 9, tree_kind == 6 ? 9 : 120, b, l4);   // x / W + N - NW
+			root = tree.branch(0, 0, a, c);                                            // channel index
 		} else if (tree_kind == 5) {
 			// a wide tree: every property 0..14, every predictor but the weighted one, offsets and multipliers; 48 leaves
 			static const int PREDS[13] = {5, 1, 2, 3, 4, 0, 7, 8, 9, 10, 11, 12, 13};
@@ -1193,9 +1351,10 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		if (lz77) { map[(size_t) nctx] = (uint8_t) ncl; nclusters = ncl + 1; }   // the distance context gets its own cluster
 		sp.lz77 = lz77 != 0;
 		sp.init(nctx, map, nclusters);
-		sp.lz_min_symbol = 224; sp.lz_min_length = 3; sp.lz_len_cfg = HybridCfg{0, 0, 0};
+		sp.lz_min_symbol = lz_min_symbol; sp.lz_min_length = lz_min_length; sp.lz_len_cfg = parse_cfg("lzlencfg", HybridCfg{0, 0, 0}, 8);
 		sp.use_prefix = use_prefix != 0; sp.log_alpha = 8;
-		for (auto &c : sp.cfg) c = use_prefix ? HybridCfg{4, 2, 0} : HybridCfg{4, 1, 1};
+		for (auto &c : sp.cfg) c = parse_cfg("hybrid", use_prefix ? HybridCfg{4, 2, 0} : HybridCfg{4, 1, 1}, use_prefix ? 15 : 8);
+		if (lz77) sp.cfg[(size_t) ncl] = parse_cfg("lzdistcfg", sp.cfg[(size_t) ncl], use_prefix ? 15 : 8);
 		return sp;
 	};
 	CodeSpecW gspec = make_spec(tree);
@@ -1215,17 +1374,62 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	if (local_tree) { tree_tokens(ltree, ltree_enc); count_stream(treespec, ltree_enc); }
 	const StreamEncoder ltree_saved = ltree_enc;   // flush() consumes the items
 	const CodeSpecW lspec_proto = make_spec(ltree);
-	WPParams wpp;
+	// the parameters of the header a section reads: LfGlobal's is the global one, a pass group's its own
+	const WPParams wp_default;
+	auto group_wp = [&](int g) {
+		return wpat == "both" ? wp_derived(wp_base, g) : wp_base;
+	};
+	const WPParams *global_wp = custom_wp && wpat != "group" ? &wp_base : nullptr;
+	const bool groups_have_wp = custom_wp && wpat != "global";
 	const CodeSpecW &gspec_ref = gspec;
+	LzStats lzstats;
+	// povf=K: sample K of every section (decode order) is coded beyond int16, as povfto= (default 40000; up to +-2^30: a residual of
+	// thirty bits); povfsection=N: only in the N-th stream the writer codes (from 0; default: every stream)
+	const int povf_all = opt.geti("povf", -1);
+	const bool povf_everywhere = !opt.kv.count("povfsection");
+	int povf_section = opt.geti("povfsection", 0), coded_streams = 0;
+	const int64_t povf_to = opt.geti("povfto", 40000);
+	if (povf_to >= -32768 && povf_to <= 32767) die("modular: povfto lies outside int16");
+	if (povf_to < -(1 << 30) || povf_to > (1 << 30)) die("modular: povfto within +-2^30 (the residual is a 32-bit hybrid integer)");
+	if (povf_all >= 0 && lzp.force != FORCE_NONE) die("modular: povf works on a coded picture, lzforce has none");
 
 	// encodes the listed channels (sub-rectangles already cut out) into one stream; LZ77 replaces runs
 	// of equal tokens ("previous symbol" = distance code 1 with a non-zero dist_mult, j40.h:2834)
-	auto encode_image = [&](std::vector<Channel> &chs, int first, int64_t sidx, StreamEncoder &enc, bool local = false) {
+	auto encode_image = [&](std::vector<Channel> &chs, int first, int64_t sidx, StreamEncoder &enc, bool local = false, const WPParams *wpp_in = nullptr, int64_t dist_mult = 0) {
+		const WPParams &wpp = wpp_in ? *wpp_in : wp_default;
+		const int povf = povf_everywhere || coded_streams++ == povf_section ? povf_all : -1;
 		const MATree &use_tree = local ? ltree : tree;
 		const CodeSpecW &gspec = local ? lspec_proto : gspec_ref;   // same cluster layout rules, the section's own contexts
 		StreamEncoder raw(gspec);
-		for (int c = first; c < (int) chs.size(); ++c) encode_channel(use_tree, chs, c, sidx, wpp, raw);
-		if (!lz77) { enc.items = raw.items; return; }
+		std::vector<Tok> src;
+		if (lz77 && lzp.mode != LZ_RUNS) raw.src = &src;
+		if (lz77 && (lzp.mode != LZ_RUNS || lzp.force != FORCE_NONE)) {
+			// where each integer lies; `dist_mult`: the reader's multiplier, the widest channel behind the meta channels of the image the
+			// header describes -- the WHOLE frame's where this is LfGlobal's stream, the section's own otherwise (j40.h:3840-3844)
+			std::vector<uint32_t> row_of, chan_of;
+			uint32_t row = 0;
+			LzParams lp = lzp;
+			for (int c = first; c < (int) chs.size(); ++c) {
+				for (int y = 0; y < chs[(size_t) c].h; ++y, ++row) for (int x = 0; x < chs[(size_t) c].w; ++x) { row_of.push_back(row); chan_of.push_back((uint32_t) c); }
+			}
+			lp.dist_mult = dist_mult;
+			if (row_of.empty()) return;
+			if (dist_mult <= 0) die("modular: lzmode / lzforce: this stream's distance multiplier is not known to the writer");
+			if (lzp.force != FORCE_NONE) {
+				const std::vector<uint32_t> win = lz77_forced(enc, gspec, lp, 0, row_of.size(), rng, row_of, chan_of, lzstats);
+				size_t k = 0;
+				for (int c = first; c < (int) chs.size(); ++c) for (int32_t &v : chs[(size_t) c].px) { const uint32_t u = win[k++]; v = (u & 1) ? -(int32_t) ((u + 1) >> 1) : (int32_t) (u >> 1); }
+				return;
+			}
+			int64_t povf_in = povf;
+			for (int c = first; c < (int) chs.size(); ++c) encode_channel(use_tree, chs, c, sidx, wpp, raw, povf >= 0 ? &povf_in : nullptr, povf_to);
+			std::vector<uint32_t> ctxs, vals;
+			for (const Tok &t : src) { ctxs.push_back(t.ctx); vals.push_back(t.value); }
+			lz77_match(enc, gspec, lp, ctxs, vals, row_of, chan_of, lzstats);
+			return;
+		}
+		{ int64_t povf_in = povf; for (int c = first; c < (int) chs.size(); ++c) encode_channel(use_tree, chs, c, sidx, wpp, raw, povf >= 0 ? &povf_in : nullptr, povf_to); }
+		if (!lz77) { enc.items = raw.items; if (povf >= 0 && (size_t) povf < enc.items.size()) enc.mark_item = (size_t) povf; return; }
 		// run-length pass over the residual tokens: a run of >= 3 identical (cluster, token, extra) items
 		// after its first occurrence becomes one copy with distance 1
 		const auto &it = raw.items;
@@ -1242,21 +1446,25 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 				uint32_t lzcl = gspec.cluster_map[(size_t) gspec.total_dist() - 1];
 				HToken d = hybrid_encode(1, gspec.cfg[lzcl]);   // special distance code 1 = previous symbol
 				enc.items.push_back({lzcl, d.token, d.extra, (uint8_t) d.nextra});
+				++lzstats.copies; ++lzstats.special_copies; ++lzstats.distance_one; lzstats.code_seen[1] = true; lzstats.max_length = std::max<uint64_t>(lzstats.max_length, run);
 				i = j;
 			} else i = i + 1;
 		}
 	};
 
 	std::vector<StreamEncoder> encs;
+	bool samples_known = !palette && !squeeze && povf_all < 0;   // (stats: `ch` ends up holding what a reader decodes, before the global RCT is undone)
 	std::vector<std::vector<TransformW>> group_tr;
 	const int local_rct = opt.geti("localrct", -1);
 	const int local_palette = opt.geti("localpalette", 0);
 	std::vector<uint8_t> section_is_group;
 	// squeeze, frames larger than a group: which encoder (index into encs) holds each LfGroup / pass-group section; -1 = nothing coded there
 	std::vector<int> sq_lf_enc, sq_group_enc;
+	int64_t frame_dist_mult = 0;
+	for (int c = nb_meta; c < total_ch; ++c) frame_dist_mult = std::max<int64_t>(frame_dist_mult, ch[(size_t) c].w);
 	if (single) {
 		encs.emplace_back(gspec);
-		encode_image(ch, 0, 0, encs.back());
+		encode_image(ch, 0, 0, encs.back(), false, global_wp, frame_dist_mult);
 	} else if (squeeze) {
 		// The decoder deals the channels out by size and shift (ISO 18181-1): LfGlobal takes the meta channels and the channels behind
 		// them that fit one group; an LfGroup section the channels shifted by >= 3 both ways, over its 8-groups-wide area; a pass-group
@@ -1264,7 +1472,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		int num_gm = nb_meta;
 		while (num_gm < total_ch && ch[(size_t) num_gm].w <= gdim && ch[(size_t) num_gm].h <= gdim) ++num_gm;
 		encs.emplace_back(gspec);
-		{ std::vector<Channel> head(ch.begin(), ch.begin() + num_gm); if (num_gm) encode_image(head, 0, 0, encs.back()); }
+		{ std::vector<Channel> head(ch.begin(), ch.begin() + num_gm); if (num_gm) encode_image(head, 0, 0, encs.back(), false, nullptr, frame_dist_mult); }
 		std::map<uint64_t, int> seen;   // content hash of a section's channels -> its encoder
 		auto cut = [&](bool lf, int left, int top, int dim, int64_t sidx) -> int {
 			std::vector<Channel> sub;
@@ -1285,7 +1493,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 			auto it = seen.find(hsh);
 			if (it != seen.end()) return it->second;
 			encs.emplace_back(gspec);
-			encode_image(sub, 0, sidx, encs.back());
+			{ int64_t widest = 0; for (const Channel &s2 : sub) widest = std::max<int64_t>(widest, s2.w); encode_image(sub, 0, sidx, encs.back(), false, nullptr, widest); }
 			seen[hsh] = (int) encs.size() - 1;
 			return (int) encs.size() - 1;
 		};
@@ -1295,7 +1503,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	} else {
 		// meta channels (palette) are decoded inside LfGlobal (num_gm_channels = nb_meta_channels, j40.h:6332)
 		encs.emplace_back(gspec);
-		if (nb_meta) { std::vector<Channel> meta(ch.begin(), ch.begin() + nb_meta); encode_image(meta, 0, 0, encs.back()); }
+		if (nb_meta) { std::vector<Channel> meta(ch.begin(), ch.begin() + nb_meta); encode_image(meta, 0, 0, encs.back(), false, global_wp, frame_dist_mult); }
 		// passes=P: every pass codes the whole group again (the reference decodes and pastes all channels in each pass,
 		// j40.h:7025-7033, so the last pass is what stays); earlier passes carry a perturbed picture
 		for (int pass = 0; pass < num_passes; ++pass) for (int g = 0; g < num_groups; ++g) {
@@ -1325,7 +1533,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 				std::vector<Channel> next{pal, idx};
 				for (size_t c = 3; c < sub.size(); ++c) next.push_back(sub[c]);
 				sub.swap(next);
-				TransformW t; t.kind = 1; t.begin_c = 0; t.num_c = 3; t.nb_colours = nb_colours; t.nb_deltas = nb_deltas; t.d_pred = local_palette == 3 ? 5 : 0;
+				TransformW t; t.kind = 1; t.begin_c = 0; t.num_c = 3; t.nb_colours = nb_colours; t.nb_deltas = nb_deltas; t.d_pred = local_palette == 3 ? dpred : 0;
 				group_tr.back().push_back(t);
 			}
 			if (local_rct >= 0 && sub.size() >= 3 && !own_palette) {
@@ -1337,9 +1545,12 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 					if (t2 / 7 == 0 && t2 % 7 != 2) forward_rct(sub, b.begin_c, t2);
 				}
 			}
+			if (group_tr.back().size()) samples_known = false;
 			encs.emplace_back(gspec);
 			// stream index of a pass group (j40.h:7013): 1 + 3 * num_lf_groups + 17 + pass * num_groups + gidx
-			encode_image(sub, 0, 1 + 3 * num_lf_groups + 17 + pass * num_groups + g, encs.back(), local);
+			const WPParams gwp = group_wp(pass * num_groups + g);
+			encode_image(sub, 0, 1 + 3 * num_lf_groups + 17 + pass * num_groups + g, encs.back(), local, groups_have_wp ? &gwp : nullptr, gw);
+			if (samples_known && pass + 1 == num_passes) for (int c = nb_meta; c < total_ch; ++c) for (int y = 0; y < gh; ++y) for (int x = 0; x < gw; ++x) ch[(size_t) c].at(gx + x, gy + y) = sub[(size_t) (c - nb_meta)].at(x, y);
 		}
 	}
 	std::vector<CodeSpecW> lspec(encs.size(), lspec_proto);
@@ -1349,6 +1560,17 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	}
 
 	// ---- sections ----
+	// (stats) the overflowing residual of povf= in streams without LZ77: section, first of its extra bits within it, their number, their value
+	struct PovfMark { size_t section, bit, nbits; uint32_t extra; };
+	std::vector<PovfMark> povf_marks;
+	int longest_symbol_bits = 0;   // (stats) prefix codes: code length + extra bits of one token; rANS: the extra bits alone
+	auto note_bits = [&](const StreamEncoder &e) {
+		for (const auto &it : e.items) {
+			int bits = it.nextra;
+			if (e.spec->use_prefix && e.spec->pfx[it.cluster].alphabet > 1) bits += e.spec->pfx[it.cluster].len[it.token];
+			longest_symbol_bits = std::max(longest_symbol_bits, bits);
+		}
+	};
 	std::vector<std::vector<uint8_t>> sections;
 	{
 		BitWriter bw;
@@ -1356,8 +1578,10 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		bw.put(1, 1);                 // global tree present
 		write_code_spec(bw, treespec); tree_enc.flush(bw);
 		write_code_spec(bw, gspec);
-		write_modular_header(bw, true, nullptr, transforms);
+		write_modular_header(bw, true, global_wp, transforms);
+		note_bits(encs[0]);
 		encs[0].flush(bw);
+		if (encs[0].mark_nbits >= 0) povf_marks.push_back({0, encs[0].mark_bit, (size_t) encs[0].mark_nbits, encs[0].mark_extra});
 		bw.pad();
 		sections.push_back(bw.bytes);
 	}
@@ -1370,6 +1594,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 			if (done[(size_t) e].empty()) {
 				BitWriter bw;
 				write_modular_header(bw, true, nullptr, {});
+				note_bits(encs[(size_t) e]);
 				encs[(size_t) e].flush(bw);
 				bw.pad();
 				done[(size_t) e] = bw.bytes;
@@ -1384,13 +1609,17 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		sections.push_back({});       // HfGlobal must be empty for Modular frames (j40.h:7825)
 		for (int g = 0; g < num_passes * num_groups; ++g) {
 			BitWriter bw;
+			const WPParams gwp = group_wp(g);
+			const WPParams *own_wp = groups_have_wp ? &gwp : nullptr;
 			if (local_tree && (((size_t) g + 1) & 1)) {
-				write_modular_header(bw, false, nullptr, group_tr[(size_t) g]);
+				write_modular_header(bw, false, own_wp, group_tr[(size_t) g]);
 				StreamEncoder te = ltree_saved;
 				write_code_spec(bw, treespec); te.flush(bw);
 				write_code_spec(bw, lspec[(size_t) g + 1]);
-			} else write_modular_header(bw, true, nullptr, group_tr[(size_t) g]);
+			} else write_modular_header(bw, true, own_wp, group_tr[(size_t) g]);
+			note_bits(encs[(size_t) g + 1]);
 			encs[(size_t) g + 1].flush(bw);
+			if (encs[(size_t) g + 1].mark_nbits >= 0) povf_marks.push_back({sections.size(), encs[(size_t) g + 1].mark_bit, (size_t) encs[(size_t) g + 1].mark_nbits, encs[(size_t) g + 1].mark_extra});
 			bw.pad();
 			sections.push_back(bw.bytes);
 		}
@@ -1465,6 +1694,46 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		file.insert(file.end(), cs.bytes.begin(), cs.bytes.end());
 	}
 	if (!write_file(out, file)) die("cannot write output");
+	if (opt.geti("stats", 0)) {
+		// what a reader makes of the colour channels once the global RCT is undone, in the reference's 16-bit arithmetic: how many samples
+		// leave int16 on the way (they wrap) and how many end outside [0, 2^bpp) (the output clamps them); -1: not worked out for this stream
+		long long wraps = -1, outside = -1;
+		if (samples_known && !single && num_groups * num_passes + 1 != (int) encs.size()) samples_known = false;
+		if (samples_known && total_ch >= 3) {
+			wraps = outside = 0;
+			const int type = rct >= 0 ? rct % 7 : 0;
+			const size_t n = ch[0].px.size();
+			for (size_t i = 0; i < n; ++i) {
+				const int64_t A = ch[0].px[i], B = ch[1].px[i], C = ch[2].px[i];
+				int64_t v[4] = {A, B, C, 0};   // (the three outputs, and the one intermediate of type 6)
+				if (type == 6) { v[3] = A - (C >> 1); v[1] = C + v[3]; v[2] = v[3] - (B >> 1); v[0] = v[2] + B; }
+				else { if (type & 1) v[2] = C + A; if ((type >> 1) == 1) v[1] = B + A; if ((type >> 1) == 2) v[1] = B + ((A + v[2]) >> 1); }
+				bool wrapped = false;
+				for (int k = 0; k < 4; ++k) wrapped |= v[k] < -32768 || v[k] > 32767;
+				wraps += wrapped;
+				for (int k = 0; k < 3; ++k) { const int16_t w16 = (int16_t) (uint16_t) (uint64_t) v[k]; outside += w16 < 0 || w16 > (1 << bpp) - 1; }
+			}
+		}
+		// povf_extra_bits: [bit of the file, number of bits, value] per marked residual (sections stored in order, no container)
+		std::string povf_list;
+		if (!container && !opt.geti("permute", 0)) for (const PovfMark &m : povf_marks) {
+			size_t behind = 0;
+			for (size_t k = m.section; k < sections.size(); ++k) behind += sections[k].size();
+			char tmp[96]; snprintf(tmp, sizeof tmp, "%s[%zu, %zu, %u]", povf_list.empty() ? "" : ", ", 8 * (file.size() - behind) + m.bit, m.nbits, m.extra);
+			povf_list += tmp;
+		}
+		std::string dpred_list;   // the predictor of every palette with delta entries, global first
+		for (const TransformW &t : transforms) if (t.kind == 1 && t.nb_deltas) dpred_list += (dpred_list.empty() ? "" : ", ") + std::to_string(t.d_pred);
+		for (const auto &trs : group_tr) for (const TransformW &t : trs) if (t.kind == 1 && t.nb_deltas) dpred_list += (dpred_list.empty() ? "" : ", ") + std::to_string(t.d_pred);
+		printf("{\"copies\": %llu, \"special_copies\": %llu, \"distinct_special_codes\": %d, \"plain_copies\": %llu, \"overlapping_copies\": %llu, "
+		       "\"copies_crossing_rows\": %llu, \"copies_crossing_channels\": %llu, \"clamped_distances\": %llu, \"first_symbol_copies\": %llu, "
+		       "\"copies_beyond_need\": %llu, \"distance_one_copies\": %llu, \"copies_near_2_20\": %llu, \"max_distance\": %llu, \"max_length\": %llu, \"max_section_integers\": %llu, "
+		       "\"longest_symbol_bits\": %d, \"rct_wraps\": %lld, \"samples_outside_range\": %lld, \"sections\": %zu, \"povf_extra_bits\": [%s], \"palette_d_pred\": [%s], %s}\n",
+		       (unsigned long long) lzstats.copies, (unsigned long long) lzstats.special_copies, lzstats.distinct_codes(), (unsigned long long) lzstats.plain_copies, (unsigned long long) lzstats.overlapping,
+		       (unsigned long long) lzstats.cross_row, (unsigned long long) lzstats.cross_channel, (unsigned long long) lzstats.clamped, (unsigned long long) lzstats.first_symbol_copies,
+		       (unsigned long long) lzstats.beyond_need, (unsigned long long) lzstats.distance_one, (unsigned long long) lzstats.far_copies, (unsigned long long) lzstats.max_distance, (unsigned long long) lzstats.max_length,
+		       (unsigned long long) lzstats.max_section_integers, longest_symbol_bits, wraps, outside, sections.size(), povf_list.c_str(), dpred_list.c_str(), wp_stats_json().c_str());
+	}
 	fprintf(stderr, "modular %dx%d: %zu bytes (%.3f bpp), %d groups%s\n", Wfull, Hfull, file.size(), 8.0 * (double) file.size() / ((double) Wfull * Hfull), gcols_full * grows_full, single ? " (single section)" : "");
 	return 0;
 }

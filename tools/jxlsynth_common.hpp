@@ -433,8 +433,12 @@ struct StreamEncoder {
 	const CodeSpecW *spec;
 	struct Item { uint32_t cluster, token, extra; uint8_t nextra; };
 	std::vector<Item> items;
+	// mark_item: flush() notes where that item's extra bits start in its writer, how many they are and their value (`stats=1`)
+	size_t mark_item = (size_t) -1, mark_bit = 0; int mark_nbits = -1; uint32_t mark_extra = 0;
+	std::vector<Tok> *src = nullptr;   // where set: every add() is noted here as well (the LZ77 matcher works on the integers)
 	explicit StreamEncoder(const CodeSpecW &s) : spec(&s) {}
 	void add(uint32_t ctx, uint32_t value) {
+		if (src) src->push_back({ctx, value});
 		uint32_t cl = spec->cluster_map[ctx];
 		HToken t = hybrid_encode(value, spec->cfg[cl]);
 		items.push_back({cl, t.token, t.extra, (uint8_t) t.nextra});
@@ -454,6 +458,7 @@ struct StreamEncoder {
 			for (const Item &it : items) {
 				const PrefixCode &pc = spec->pfx[it.cluster];
 				if (pc.alphabet > 1) pc.put_symbol(bw, (int) it.token);
+				if ((size_t) (&it - items.data()) == mark_item) { mark_bit = bw.bitpos(); mark_nbits = it.nextra; mark_extra = it.extra; }
 				bw.put(it.extra, it.nextra);
 			}
 		} else {
@@ -470,6 +475,7 @@ struct StreamEncoder {
 			bw.put(x & 0xffff, 16); bw.put(x >> 16, 16);
 			for (size_t k = 0; k < items.size(); ++k) {
 				if (word[k] != 0xffffffffu) bw.put(word[k], 16);
+				if (k == mark_item) { mark_bit = bw.bitpos(); mark_nbits = items[k].nextra; mark_extra = items[k].extra; }
 				bw.put(items[k].extra, items[k].nextra);
 			}
 		}

@@ -79,6 +79,19 @@ struct Channel {
 struct WPParams { int p1 = 16, p2 = 10, p3[5] = {7, 7, 7, 0, 0}, w[4] = {13, 12, 12, 12}; };
 
 // weighted ("self-correcting") predictor state, restating what the decoder keeps (j40.h:3997-4111)
+// (stats=1) how often the writer's walk used the weighted predictor: leaves with predictor 6 / tests of property 15
+inline uint64_t &wp_predicted_samples() { static uint64_t n = 0; return n; }
+inline uint64_t &wp_property_tests() { static uint64_t n = 0; return n; }
+inline bool wp_is_default(const WPParams &p) { const WPParams d; return p.p1 == d.p1 && p.p2 == d.p2 && !memcmp(p.p3, d.p3, sizeof d.p3) && !memcmp(p.w, d.w, sizeof d.w); }
+// the k-th header's own parameters where every header is to differ from the base and from its neighbours
+inline WPParams wp_derived(const WPParams &base, int k) {
+	WPParams p = base;
+	p.p1 = (p.p1 + 3 * k + 1) & 31; p.p2 = (p.p2 + 5 * k + 2) & 31;
+	for (int i = 0; i < 5; ++i) p.p3[i] = (p.p3[i] + (i + 2) * (k + 1)) & 31;
+	for (int i = 0; i < 4; ++i) p.w[i] = (p.w[i] + (i + 1) * (k + 1)) & 15;
+	return p;
+}
+
 struct WPState {
 	int width = 0; WPParams params; bool on = false;
 	std::vector<std::array<int64_t, 5>> err;   // two rows
@@ -168,7 +181,9 @@ inline int64_t predict(int pred, const Neigh &p, const WPState &wp) {  // j40.h:
 // walk. `chans`/`cidx` give access to previous channels for properties >= 16; `sidx` is the stream
 // index property. `lossy_quant` > 1 quantises residuals (the channel is updated with what the
 // decoder will reconstruct, so later predictions stay in sync).
-inline void encode_channel(const MATree &tree, std::vector<Channel> &chans, int cidx, int64_t sidx, const WPParams &wpp, StreamEncoder &enc) {
+// `povf_in` (optional): that many samples from now the coded residual takes the sample beyond int16, where the
+// reader stops with "povf" (j40.h:4225); what is coded behind it no reader looks at. `povf_to`: the value it is meant to take.
+inline void encode_channel(const MATree &tree, std::vector<Channel> &chans, int cidx, int64_t sidx, const WPParams &wpp, StreamEncoder &enc, int64_t *povf_in = nullptr, int64_t povf_to = 40000) {
 	Channel &c = chans[(size_t) cidx];
 	if (c.w == 0 || c.h == 0) return;
 	WPState wp;
@@ -199,6 +214,7 @@ inline void encode_channel(const MATree &tree, std::vector<Channel> &chans, int 
 			case 13: val = p.n - p.nn; break;
 			case 14: val = p.w - p.ww; break;
 			case 15:
+				++wp_property_tests();
 				val = wp.te_w;
 				if (std::llabs(val) < std::llabs(wp.te_n)) val = wp.te_n;
 				if (std::llabs(val) < std::llabs(wp.te_nw)) val = wp.te_nw;
@@ -221,11 +237,20 @@ inline void encode_channel(const MATree &tree, std::vector<Channel> &chans, int 
 		const TreeNode &lf = tree.nodes[(size_t) id];
 		int64_t mult = (int64_t) (lf.mul_bits + 1) << lf.mul_shift;
 		int64_t pr = predict(lf.predictor, p, wp);
+		if (lf.predictor == 6) ++wp_predicted_samples();
 		int64_t target = c.at(x, y);
+		const bool overflow_here = povf_in && (*povf_in)-- == 0;
+		if (overflow_here) target = povf_to;
 		int64_t diff = target - pr - lf.offset;
 		int64_t q = mult == 1 ? diff : (diff >= 0 ? (diff + mult / 2) / mult : -((-diff + mult / 2) / mult));
 		int64_t recon = q * mult + lf.offset + pr;
-		if (recon < -32768 || recon > 32767) die("modular sample out of int16 range");
+		if (overflow_here) { while (recon >= -32768 && recon <= 32767) recon = (povf_to < 0 ? --q : ++q) * mult + lf.offset + pr; }
+		else if (mult > 1) {   // a coarse leaf may round past the end of the range: one step back
+			while (recon > 32767) recon = --q * mult + lf.offset + pr;
+			while (recon < -32768) recon = ++q * mult + lf.offset + pr;
+		}
+		if (!overflow_here && (recon < -32768 || recon > 32767)) die("modular sample out of int16 range");
+		if (overflow_here) recon = 32767;
 		c.at(x, y) = (int32_t) recon;
 		enc.add((uint32_t) lf.ctx, pack_signed((int32_t) q));
 		wp.after(x, y, recon);
@@ -313,7 +338,10 @@ struct TransformW {
 };
 
 // Modular header (j40.h:3730-3819)
+// (stats=1) the parameter sets written into headers, one entry per header that carries its own
+inline std::vector<std::array<int, 11>> &wp_headers_written() { static std::vector<std::array<int, 11>> v; return v; }
 inline void write_modular_header(BitWriter &bw, bool use_global_tree, const WPParams *custom_wp, const std::vector<TransformW> &tr) {
+	if (custom_wp) wp_headers_written().push_back({custom_wp->p1, custom_wp->p2, custom_wp->p3[0], custom_wp->p3[1], custom_wp->p3[2], custom_wp->p3[3], custom_wp->p3[4], custom_wp->w[0], custom_wp->w[1], custom_wp->w[2], custom_wp->w[3]});
 	bw.put(use_global_tree ? 1 : 0, 1);
 	if (!custom_wp) bw.put(1, 1);
 	else {
