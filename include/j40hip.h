@@ -260,6 +260,33 @@ J40HIP_API uint32_t j40hip_frame_decode(j40hip_frame *f, void *rgba_dev, size_t 
 J40HIP_API uint32_t j40hip_frame_set_output_format(j40hip_frame *f, int32_t format);
 J40HIP_API int32_t j40hip_frame_output_format(const j40hip_frame *f);
 
+/* ---- the alpha channel of VarDCT frames. A lossy image with transparency carries its alpha as an extra channel, a Modular sub-image
+ *      behind the HF coefficients of every pass-group section. The reference decodes these and drops them (j40__combine_vardct,
+ *      j40.h:7868): its pixels have A = 255, and so have this library's by DEFAULT (mode 0, drop). Mode 1, keep: A is the first extra
+ *      channel of type alpha, rendered as the reference renders a Modular frame's alpha (j40.h:7950): the sample p clamped to
+ *      [0, maxpixel = 2^bpp - 1], then (p * 255 + 2^(bpp - 1)) / maxpixel, or the J40HIP_U16X4 rule for 16-bit output. R, G, B and
+ *      every status code are those of drop mode.
+ *      Served: frames of one pass and more than one group (the extra channels in the pass-group sections, any number of them, alpha
+ *      at any index), 8..15 bits, no transform in the global Modular header, an alpha channel the reference's render accepts (the
+ *      image's depth and sample type, not subsampled, not associated). Reversible colour transforms a section's own header lists are
+ *      undone; any other transform there makes a keep-mode decode "TODO".
+ *      set: mode -1 follows the environment (J40HIP_ALPHA=1 keeps; the default), 0 drops, 1 keeps. Returns 0; "TODO", the frame left
+ *      as it was, when mode 1 is asked of a frame outside the above; "Ual?" for a frame without an alpha channel and for a Modular
+ *      frame, whose alpha is always rendered. With the environment variable alone a frame outside the above decodes opaque as before.
+ *      Every single-frame entry point that writes full-size pixels honours it: j40hip_frame_decode / _timed / _decode_to_host (these
+ *      synchronise for such frames anyway), with the restoration filters (the merge comes last), with a group range (only that
+ *      range's sub-images and rectangles). In a batch the alpha of a keep-mode member is merged when j40hip_frame_status is read, where
+ *      its sub-images are validated: into the buffer and stride given at the batch decode, which must stay valid until then; A is 255
+ *      before. LF previews stay opaque (the LF sections carry no alpha).
+ *      j40hip_frame_alpha: out[0] the index of the alpha extra channel or -1, out[1] its bpp, out[2] the mode in force (1: the next
+ *      decode keeps alpha), out[3] whether the last decode wrote it. ---- */
+J40HIP_API uint32_t j40hip_frame_set_alpha(j40hip_frame *f, int mode);
+J40HIP_API void j40hip_frame_alpha(const j40hip_frame *f, int32_t out[4]);
+/* known-answer / measuring hook: k_alpha_merge alone. plane_dev: int16 samples of an alpha channel of `bpp` bits (8..15), `pitch` of
+ * them a row, in device memory; they become the A of rectangle (x0, y0, w, h) of the pixels at rgba_dev (format J40HIP_U8X4 or
+ * J40HIP_U16X4, rows pixel-aligned). Asynchronous on `stream`. 0, "rnge" for a bpp or rectangle out of range, "Ufm?". */
+J40HIP_API uint32_t j40hip_kat_device_alpha_merge(void *rgba_dev, size_t stride_bytes, const int16_t *plane_dev, int32_t pitch, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bpp, int32_t format, void *stream);
+
 /* After the stream has been synchronised: first failing section in TOC order -> its 4-char code
  * ("coef", "shrt", "excs", "ans?" ...), 0 if every section decoded cleanly (j40.h:530-534). */
 J40HIP_API uint32_t j40hip_frame_status(j40hip_frame *f);

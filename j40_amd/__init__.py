@@ -118,6 +118,8 @@ def lib():
         "j40hip_stage_dump_group_blocks": (i64, [vp, i64, vp, i64]), "j40hip_stage_dump_sorted_varblocks": (i64, [vp, vp, vp, vp, i64]), "j40hip_stage_dump_rgba": (C.c_int, [vp, vp]),
         "j40hip_copy_engine": (C.c_int, [C.c_int, vp, vp]),
         "j40hip_frame_restoration": (None, [vp, vp]), "j40hip_frame_set_restoration": (None, [vp, C.c_int]), "j40hip_frame_sharpness": (C.c_int, [vp, i64, vp]),
+        "j40hip_frame_set_alpha": (u32, [vp, C.c_int]), "j40hip_frame_alpha": (None, [vp, vp]),
+        "j40hip_kat_device_alpha_merge": (u32, [vp, sz, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
         "j40hip_frame_read_xyb": (u32, [vp, C.c_int, vp]), "j40hip_frame_restoration_ms": (C.c_float, [vp]),
         "j40hip_kat_device_restoration": (u32, [vp, i32, i32, vp, vp, vp, C.c_int, C.c_int, vp]),
         "j40hip_frame_lf_end": (i64, [vp]), "j40hip_frame_lf_size": (None, [vp, C.POINTER(i32), C.POINTER(i32)]),
@@ -212,8 +214,30 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4):
-    """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4"""
+def decode(data: bytes, fmt=J40_U8X4, alpha=False):
+    """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
+    The public API writes a VarDCT frame's alpha as the environment says (J40HIP_ALPHA=1 keeps it, else A is opaque like the
+    reference's). alpha=True keeps it for this call whatever the environment says: the frame goes through the thin C-ABI with
+    Frame.set_alpha(1) on device 0 -- "TODO" / "Ual?" where that refuses (Frame.set_alpha)."""
+    if alpha:
+        try:
+            fr = Frame(data)
+        except J40Error as e:
+            return e.code, None
+        try:
+            code = fr.set_alpha(1)
+            if code:
+                return code, None
+            fr.set_output_format(fmt)
+            fr.upload(0)
+            err, out = fr.decode_to_host()
+            if not err:   # bytes behind the frame, as the public API looks for them
+                err = err4(lib().j40hip_frame_after_frame_status(fr.h))
+            return err, (None if err else out)
+        except J40Error as e:
+            return e.code, None
+        finally:
+            fr.close()
     img = from_memory(data)
     img.output_format(J40_RGBA, fmt)
     out = None
@@ -472,6 +496,19 @@ class Frame:
     def set_restoration(self, mode):
         """-1: as J40HIP_RESTORATION says, 0: off (what j40 does), 1: the filters the frame signals, 2: exactly as j40's routines stand"""
         lib().j40hip_frame_set_restoration(self.h, int(mode))
+
+    # ---- the alpha channel of VarDCT frames (include/j40hip.h) ----
+    def set_alpha(self, mode):
+        """-1: as J40HIP_ALPHA says (default), 0: drop (A = 255, the reference's pixels), 1: keep the alpha extra channel. Returns "" or
+        the refusal: "TODO" (mode 1 on a frame keep mode does not serve; the frame is left as it was), "Ual?" (no alpha channel, or a
+        Modular frame, whose alpha is always rendered)"""
+        return err4(lib().j40hip_frame_set_alpha(self.h, int(mode)))
+
+    def alpha(self):
+        """{"index": the alpha extra channel or -1, "bpp": its depth, "mode": 1 when the next decode keeps alpha, "written": the last decode did}"""
+        a = np.zeros(4, np.int32)
+        lib().j40hip_frame_alpha(self.h, a.ctypes.data)
+        return dict(zip(["index", "bpp", "mode", "written"], a.tolist()))
 
     def sharpness(self, gg):
         gi = self.lf_group_info(gg)

@@ -18,6 +18,8 @@ struct j40hip_frame {
 	j40hip_device_state *dev = nullptr;
 	bool force_dense = false;        // upload with dense coefficient planes (set after a decode ran out of event space, ERR_EVOF)
 	int restoration = -1;            // the restoration filters (j40hip_frame_set_restoration): -1 as J40HIP_RESTORATION says, 0 off, 1 on, 2 as j40's routines stand
+	int alpha = -1;                  // the alpha channel of a VarDCT frame (j40hip_frame_set_alpha): -1 as J40HIP_ALPHA says, 0 dropped (A = 255, the reference's pixels), 1 kept
+	bool alpha_written = false;      // the last decode merged the alpha channel into its pixels
 	int32_t output_format = J40HIP_U8X4;   // what the decode entry points write (j40hip_frame_set_output_format): u8x4 or u16x4
 	int threads = 1;                 // what the frame was parsed with: the plan build at upload may use as many (plan_build.cpp)
 	// backing storage of the plan views (include/j40hip.h)
@@ -38,6 +40,14 @@ struct j40hip_frame {
 		std::vector<std::vector<float>> vb_hfmul_inv;
 	} views;
 };
+
+// the alpha mode in force: kept only where asked for (or J40HIP_ALPHA=1) AND the frame is one keep mode serves (plan_build.cpp:
+// alpha_keep_scope) -- with the environment variable alone every other frame decodes opaque as before
+inline bool j40hip_alpha_kept(const j40hip_frame *h) {
+	int32_t index;
+	const bool asked = h->alpha >= 0 ? h->alpha == 1 : j40hip::alpha_env();
+	return asked && !h->from_view && j40hip::alpha_keep_scope(h->frame, &index) == 0;
+}
 
 extern "C" j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads, uint32_t flags, j40hip::LfDeviceDecoder lf_decoder, void *lf_ctx, uint32_t *err);
 

@@ -159,6 +159,26 @@ uint32_t j40hip_frame_after_frame_status(const j40hip_frame *h) {
 	return end < std::min<size_t>(h->cs_size, 0x10000) ? E4("excs") : 0;
 }
 
+// ---- the alpha channel of VarDCT frames (include/j40hip.h) ----
+uint32_t j40hip_frame_set_alpha(j40hip_frame *h, int mode) {
+	if (!h) return j40hip::ERR_RNGE;
+	int32_t index;
+	uint32_t e = j40hip::alpha_keep_scope(h->frame, &index);
+	if (!e && h->from_view) e = j40hip::ERR_TODO;   // (no global tree to decode the sub-images with)
+	if (e && e != (uint32_t) j40hip::ERR_TODO) return e;   // "Ual?": nothing to keep or drop
+	if (mode > 0 && e) return e;
+	h->alpha = mode < 0 ? -1 : mode > 0 ? 1 : 0;
+	return 0;
+}
+void j40hip_frame_alpha(const j40hip_frame *h, int32_t out[4]) {
+	if (!out) return;
+	out[0] = -1; out[1] = out[2] = out[3] = 0;
+	if (!h) return;
+	for (size_t i = 0; i < h->frame.im.ec.size(); ++i) if (h->frame.im.ec[i].type == j40hip::EC_ALPHA) { out[0] = (int32_t) i; out[1] = h->frame.im.ec[i].bpp; break; }
+	out[2] = j40hip_alpha_kept(h) ? 1 : 0;
+	out[3] = h->alpha_written ? 1 : 0;
+}
+
 void j40hip_frame_free(j40hip_frame *f) {
 	if (!f) return;
 	j40hip_release_device(f);

@@ -83,6 +83,8 @@ void launch_inverse_palette_predicted(const int16_t *idx, const int16_t *pal, in
 		int32_t nb_colours, int32_t nb_deltas, int32_t d_pred, int32_t bpp, const int8_t *wpp_dev, int32_t *wp_scratch, uint32_t *status, hipStream_t stream);
 void launch_inverse_squeeze(const int16_t *avg, const int16_t *res, int16_t *out, int32_t aw, int32_t ah, int32_t rw, int32_t rh, bool horizontal, hipStream_t stream);
 void launch_pack_planes_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
+// alpha_kernels.hip: the kept alpha channel of a VarDCT frame into rectangle (x0, y0, w, h) of pixels already written
+void launch_alpha_merge(const int16_t *plane, int32_t pitch, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16);
 void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
 
 } // namespace j40hip

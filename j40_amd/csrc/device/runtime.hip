@@ -374,6 +374,21 @@ struct j40hip_device_state {
 	bool lfp_ready = false;
 	std::vector<uint8_t> lfp_host;
 
+	// the kept alpha channel (j40hip_frame_set_alpha; keep_alpha below): the keep-mode trailer plan, the frame-wide planes of the extra
+	// channels and the Modular decode's scratch in ONE block of the device memory cache, laid out at the first decode that keeps alpha
+	// and used again by every later decode of the same group range (a stream's sections end where they ended before)
+	struct AlphaKeep {
+		void *block = nullptr; size_t block_bytes = 0;
+		bool ready = false; int64_t first_group = -1, num_groups = -1;
+		DevModPlan plan; ModLaunchInfo info; int32_t num_sections = 0; bool local_rcts = false;
+		const int16_t *alpha_plane = nullptr;
+		std::vector<int32_t> section_of;                          // plan section -> the frame's section
+		std::vector<std::pair<int32_t, uint32_t>> header_errors;  // sections whose sub-image header did not parse
+		std::vector<uint8_t> staging;                             // what was copied into the block (the copy is asynchronous)
+	} alpha;
+	// a batch decoded the frame (trailers_pending): where, for the merge at j40hip_frame_status
+	void *pending_rgba = nullptr; size_t pending_stride = 0;
+
 	template <typename T> T *upload(const T *src, size_t n, hipStream_t s, bool &ok) {
 		DeviceBuffer b;
 		if (!b.alloc(sizeof(T) * n)) { ok = false; return nullptr; }
@@ -400,6 +415,10 @@ extern "C" void j40hip_release_device(j40hip_frame *f) {
 	if (f->dev->two_block) {
 		if (!f->dev->idle) (void) hipDeviceSynchronize();
 		cache_release(f->dev->device, f->dev->two_block, f->dev->two_block_bytes, false);
+	}
+	if (f->dev->alpha.block) {
+		if (!f->dev->idle) (void) hipDeviceSynchronize();
+		cache_release(f->dev->device, f->dev->alpha.block, f->dev->alpha.block_bytes, false);
 	}
 	for (auto &b : f->dev->buffers) b.release();
 	for (auto &e : f->dev->ev) if (e) (void) hipEventDestroy(e);
@@ -1037,6 +1056,116 @@ static uint32_t validate_trailers(j40hip_frame *h, hipStream_t s) {
 	return ok ? 0 : ERR_GPU;
 }
 
+// The alpha mode in force (j40hip_frame_set_alpha; -1: J40HIP_ALPHA) for a frame keep mode can serve -- elsewhere the environment
+// variable leaves the decode as it was (capi.hpp: j40hip_alpha_kept).
+// keep_alpha: validate_trailers for such a frame. The same Modular decode of every section's sub-image, but into frame-wide planes
+// (build_trailer_plan's keep mode), then k_alpha_merge of the alpha channel's plane into the pixels at `rgba_dev`, which the pixel
+// kernels have written opaque on the same stream. A ranged decode takes only its groups' sections and rectangles. The plan, the
+// planes and the scratch live with the frame (AlphaKeep): the first decode waits for the entropy kernel's end bits and lays them
+// out, later ones only launch. *fallback: nothing was done because a section lists transforms of its own that keep mode does not
+// undo, and the mode came from the environment -- the caller validates the sub-images as in drop mode.
+static uint32_t keep_alpha(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, bool *fallback) {
+	*fallback = false;
+	j40hip_device_state *st = h->dev;
+	j40hip_device_state::AlphaKeep &ak = st->alpha;
+	const Frame &fr = h->frame;
+	const size_t n = (size_t) st->total_sections;
+	int32_t alpha_index = -1;
+	if (uint32_t e = alpha_keep_scope(fr, &alpha_index)) return e;
+	const bool whole = st->first_group == 0 && st->num_groups == fr.fh.num_groups;
+	std::vector<uint32_t> status(n);
+	if (!ak.ready || ak.first_group != st->first_group || ak.num_groups != st->num_groups) {
+		ak.ready = false;
+		std::vector<uint32_t> end_bits(n);
+		if (hipMemcpyAsync(end_bits.data(), st->plan.section_end_bit, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s) != hipSuccess) return ERR_GPU;
+		if (hipMemcpyAsync(status.data(), st->plan.status, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s) != hipSuccess) return ERR_GPU;
+		if (hipStreamSynchronize(s) != hipSuccess) return ERR_GPU;
+		HostModPlan hp;
+		ak.header_errors.clear(); ak.section_of.clear();
+		if (uint32_t e = build_trailer_plan(fr, h->cs, h->cs_size, end_bits.data(), status.data(), &hp, &ak.header_errors, &ak.section_of, true, (int32_t) st->first_group, whole ? -1 : (int32_t) st->num_groups)) {
+			if (e == (uint32_t) ERR_TODO && h->alpha < 0) { *fallback = true; return 0; }
+			return e;
+		}
+		// one block: what is uploaded first, the planes and the scratch behind it
+		size_t at = 0;
+		auto place = [&](size_t bytes) { const size_t off = at; at = (at + bytes + 255) & ~(size_t) 255; return off; };
+		const size_t plane_samples = ((size_t) fr.fh.width * (size_t) fr.fh.height + 7) & ~(size_t) 7, nplanes = hp.plane_w.size(), nsec = hp.sections.size();
+		const size_t o_frame = place(sizeof(DevModFrame)), o_u8 = place(hp.pool_u8.size()), o_i32 = place(4 * hp.pool_i32.size()), o_u64 = place(8 * hp.pool_u64.size());
+		const size_t o_clusters = place(sizeof(hp.clusters[0]) * hp.clusters.size()), o_spec = place(sizeof(hp.specs[0]) * hp.specs.size()), o_tree = place(sizeof(hp.tree[0]) * hp.tree.size());
+		const size_t o_sections = place(sizeof(DevModSection) * nsec), o_coop = place(sizeof(DevCoopTree) * hp.coop_trees.size()), o_rct = place(4 * hp.local_rct.size()), o_refs = place(sizeof(DevPlaneRef) * nplanes);
+		const size_t upload_bytes = at;
+		const size_t o_planes = place(2 * plane_samples * nplanes);
+		const size_t o_wp = place(hp.frame.tree_uses_wp ? 4 * (nsec * (size_t) (2 * hp.frame.max_width * 5) + 16) : 0);
+		const size_t o_lz = place(hp.lz_window_size ? 4 * nsec * (size_t) hp.lz_window_size : 0);
+		const size_t o_status = place(4 * (nsec + 1));
+		const size_t o_res = place(hp.split_sections ? 4 * (hp.split_samples + 64) : 0), o_split = place(hp.split_sections ? 4 * (3 * nsec + 4) : 0);
+		if (ak.block && ak.block_bytes < at) { (void) hipDeviceSynchronize(); cache_release(st->device, ak.block, ak.block_bytes, false); ak.block = nullptr; }
+		if (!ak.block) { bool clean = false; ak.block = cache_acquire(st->device, at, &ak.block_bytes, &clean); }
+		if (!ak.block) return ERR_MEM;
+		uint8_t *base = (uint8_t *) ak.block;
+		std::vector<DevPlaneRef> refs(nplanes);
+		for (size_t k = 0; k < nplanes; ++k) refs[k] = DevPlaneRef{(int16_t *) (base + o_planes) + k * plane_samples, hp.plane_w[k], hp.plane_h[k], 0, 0};
+		ak.staging.assign(upload_bytes, 0);
+		auto stage = [&](size_t off, const void *src, size_t bytes) { if (bytes) memcpy(ak.staging.data() + off, src, bytes); };
+		stage(o_frame, &hp.frame, sizeof(DevModFrame)); stage(o_u8, hp.pool_u8.data(), hp.pool_u8.size()); stage(o_i32, hp.pool_i32.data(), 4 * hp.pool_i32.size()); stage(o_u64, hp.pool_u64.data(), 8 * hp.pool_u64.size());
+		stage(o_clusters, hp.clusters.data(), sizeof(hp.clusters[0]) * hp.clusters.size()); stage(o_spec, hp.specs.data(), sizeof(hp.specs[0]) * hp.specs.size()); stage(o_tree, hp.tree.data(), sizeof(hp.tree[0]) * hp.tree.size());
+		stage(o_sections, hp.sections.data(), sizeof(DevModSection) * nsec); stage(o_coop, hp.coop_trees.data(), sizeof(DevCoopTree) * hp.coop_trees.size()); stage(o_rct, hp.local_rct.data(), 4 * hp.local_rct.size());
+		stage(o_refs, refs.data(), sizeof(DevPlaneRef) * nplanes);
+		if (hipMemcpyAsync(base, ak.staging.data(), upload_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return ERR_GPU;
+		DevModPlan &plan = ak.plan;
+		memset(&plan, 0, sizeof plan);
+		plan.frame = (const DevModFrame *) (base + o_frame); plan.codestream = st->plan.codestream;
+		plan.pool_u8 = base + o_u8; plan.pool_i32 = (const int32_t *) (base + o_i32); plan.pool_u64 = (const uint64_t *) (base + o_u64);
+		plan.clusters = (const DevCluster *) (base + o_clusters); plan.spec = (const DevCodeSpec *) (base + o_spec); plan.tree = (const DevTreeNode *) (base + o_tree);
+		plan.sections = (const DevModSection *) (base + o_sections);
+		if (!hp.coop_trees.empty()) plan.coop_trees = (const DevCoopTree *) (base + o_coop);
+		if (!hp.local_rct.empty()) plan.local_rct = (const int32_t *) (base + o_rct);
+		plan.planes = (const DevPlaneRef *) (base + o_refs);
+		if (hp.frame.tree_uses_wp) plan.wp_scratch = (int32_t *) (base + o_wp);
+		plan.lz_window_size = hp.lz_window_size;
+		if (hp.lz_window_size) plan.lz_window = (int32_t *) (base + o_lz);
+		plan.status = (uint32_t *) (base + o_status);
+		if (hp.split_sections) { plan.residuals = (int32_t *) (base + o_res); plan.split_state = (uint32_t *) (base + o_split); }
+		ak.info = ModLaunchInfo{hp.max_tree_nodes, hp.max_num_dist, hp.max_clusters, hp.max_table_bytes, hp.frame.max_width, hp.any_wp ? 1 : 0, hp.coop_width, hp.coop_sections + hp.split_sections == (int32_t) hp.sections.size(), hp.quad_sections, hp.quad_spec, hp.quad_width, hp.coop_sections, hp.quad_sections ? hp.specs[(size_t) hp.quad_spec].table_span : 0u, hp.split_sections, hp.split_width, hp.split_channels};
+		ak.num_sections = (int32_t) nsec; ak.local_rcts = !hp.local_rct.empty();
+		ak.alpha_plane = refs[(size_t) alpha_index].ptr;
+		ak.first_group = st->first_group; ak.num_groups = st->num_groups;
+		ak.ready = true;
+	} else if (hipMemcpyAsync(status.data(), st->plan.status, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s) != hipSuccess) return ERR_GPU;
+	std::vector<uint32_t> found((size_t) ak.num_sections, 0);
+	if (ak.num_sections) {
+		if (hipMemsetAsync(ak.plan.status, 0, sizeof(uint32_t) * ((size_t) ak.num_sections + 1), s) != hipSuccess) return ERR_GPU;
+		launch_modular_sections(ak.plan, 0, ak.num_sections, ak.info, s);
+		if (ak.local_rcts) launch_section_inverse_rcts(ak.plan, 0, ak.num_sections, s);
+	}
+	if (whole) launch_alpha_merge(ak.alpha_plane, fr.fh.width, 0, 0, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
+	else {
+		int32_t rects[3][4];
+		const int nr = group_range_rects((int32_t) st->first_group, (int32_t) st->num_groups, fr.fh.width, fr.fh.height, fr.fh.group_size_shift, rects);
+		for (int k = 0; k < nr; ++k) launch_alpha_merge(ak.alpha_plane, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
+	}
+	h->alpha_written = true;
+	bool ok = hipGetLastError() == hipSuccess;
+	if (ok && ak.num_sections) ok = hipMemcpyAsync(found.data(), ak.plan.status, sizeof(uint32_t) * found.size(), hipMemcpyDeviceToHost, s) == hipSuccess;
+	if (ok) ok = hipStreamSynchronize(s) == hipSuccess;
+	if (!ok) { ak.ready = false; return ERR_GPU; }
+	bool any = false;
+	for (size_t i = 0; i < found.size(); ++i) if (found[i]) { status[(size_t) ak.section_of[i]] = found[i]; any = true; }
+	for (const auto &e : ak.header_errors) { status[(size_t) e.first] = e.second; any = true; }
+	if (any) ok = hipMemcpyAsync(st->plan.status, status.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+	return ok ? 0 : ERR_GPU;
+}
+
+// the extra channels' sub-images behind a decode's coefficients: kept (the alpha channel merged into `rgba_dev`) or only validated
+static uint32_t finish_trailers(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, bool whole) {
+	if (j40hip_alpha_kept(h) && rgba_dev) {
+		bool fallback = false;
+		const uint32_t e = keep_alpha(h, rgba_dev, stride_bytes, s, &fallback);
+		if (!fallback) return e;
+	}
+	return whole ? validate_trailers(h, s) : 0;
+}
+
 // ---- restoration filters (device/restore_dev.h, restore_kernels.h) ----
 // Off unless asked for: j40 parses the frame header's RestorationFilter bundle and ignores it (j40.h:5339-5366; its j40__gaborish /
 // j40__epf are never called), and the default decode matches j40. J40HIP_RESTORATION=1 (or j40hip_frame_set_restoration(f, 1)) runs the
@@ -1132,7 +1261,7 @@ static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes
 	const DevPlan &plan = st->plan;
 	const Frame &fr = h->frame;
 	const bool whole = st->first_group == 0 && st->num_groups == fr.fh.num_groups;
-	st->trailers_pending = false;
+	st->trailers_pending = false; h->alpha_written = false;
 	if (ms3) (void) hipEventRecord(st->ev[0], s);
 	if (uint32_t e = clear_before_decode(st, s)) return e;
 	if (hipMemsetAsync(plan.status, 0, sizeof(uint32_t) * (size_t) st->total_sections, s) != hipSuccess) return ERR_GPU;
@@ -1161,7 +1290,7 @@ static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes
 		ms3[0] = b; ms3[1] = c; ms3[2] = a;
 	}
 	if (hipGetLastError() != hipSuccess) return ERR_GPU;
-	if (st->has_trailers && whole) return validate_trailers(h, s);   // (synchronises `s`)
+	if (st->has_trailers) return finish_trailers(h, rgba_dev, stride_bytes, s, whole);   // (synchronises `s`)
 	return 0;
 }
 
@@ -1314,9 +1443,11 @@ static uint32_t batch_enqueue(j40hip_batch *b, void *const *rgba_dev, const size
 		}
 	}
 	if (ev) (void) hipEventRecord(ev[0], s);
-	for (j40hip_frame *h : b->frames) {
+	for (size_t i = 0; i < b->frames.size(); ++i) {
+		j40hip_frame *h = b->frames[i];
 		j40hip_device_state *st = h->dev;
 		st->trailers_pending = st->has_trailers;
+		st->pending_rgba = rgba_dev[i]; st->pending_stride = stride_bytes[i]; h->alpha_written = false;   // (a kept alpha is merged when the status is read)
 		if (uint32_t e = clear_before_decode(st, s)) return e;
 		// (no need to clear the status words: a batch decodes every section of every frame and the entropy kernels store
 		// each section's status unconditionally -- 256 tiny fills were 4 % of a step)
@@ -1419,7 +1550,7 @@ static uint32_t j40hip_frame_status_body(j40hip_frame *h) {
 		// sub-images behind the coefficients are checked now, so that both modes report damage in them like the reference
 		st->trailers_pending = false;
 		if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
-		if (uint32_t e = validate_trailers(h, nullptr)) return e;
+		if (uint32_t e = finish_trailers(h, st->pending_rgba, st->pending_stride, nullptr, true)) return e;
 	}
 	st->status_host.assign((size_t) st->total_sections, 0);
 	if (hipMemcpy(st->status_host.data(), st->plan.status, sizeof(uint32_t) * st->status_host.size(), hipMemcpyDeviceToHost) != hipSuccess) return ERR_GPU;
@@ -1610,6 +1741,13 @@ extern "C" uint32_t j40hip_frame_set_output_format(j40hip_frame *h, int32_t form
 	if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
 	h->output_format = format;
 	return 0;
+}
+extern "C" uint32_t j40hip_kat_device_alpha_merge(void *rgba_dev, size_t stride_bytes, const int16_t *plane_dev, int32_t pitch, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bpp, int32_t format, void *stream) {
+	if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
+	if (!rgba_dev || !plane_dev || bpp < 8 || bpp > 15 || x0 < 0 || y0 < 0 || w < 0 || h < 0 || pitch < 0 || (int64_t) x0 + w > pitch) return ERR_RNGE;
+	if (stride_bytes < (size_t) (x0 + w) * (format == J40HIP_U16X4 ? 8 : 4)) return ERR_RNGE;
+	launch_alpha_merge(plane_dev, pitch, x0, y0, w, h, bpp, (uint8_t *) rgba_dev, stride_bytes, (hipStream_t) stream, format == J40HIP_U16X4);
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 }
 extern "C" int32_t j40hip_frame_output_format(const j40hip_frame *h) { return h ? h->output_format : 0; }
 extern "C" void j40hip_frame_set_restoration(j40hip_frame *h, int mode) { if (h) h->restoration = mode < 0 ? -1 : mode > 2 ? 2 : mode; }

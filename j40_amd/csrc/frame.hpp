@@ -14,6 +14,9 @@ namespace j40hip {
 // J40HIP_API_TIMING=1: the single-image path prints where its time goes (parse, upload, decode); read once
 inline bool api_timing() { static const bool v = env_str("J40HIP_API_TIMING") != nullptr; return v; }
 
+// J40HIP_ALPHA=1: VarDCT frames keep their alpha channel where j40hip_frame_set_alpha(f, 1) would be taken (include/j40hip.h); read once
+inline bool alpha_env() { static const bool v = [] { const char *e = env_str("J40HIP_ALPHA"); return e && atoi(e) > 0; }(); return v; }
+
 struct ExtraChannel { int32_t type = 0, bpp = 8, exp_bits = 0, dim_shift = 0; bool alpha_associated = false; };
 enum { EC_ALPHA = 0, EC_SPOT = 2, EC_BLACK = 4, EC_CFA = 5 };
 

@@ -793,14 +793,37 @@ uint32_t build_modular_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, 
 	return 0;
 }
 
+// Whether the alpha channel of a VarDCT frame can be kept (j40hip_frame_set_alpha) and which extra channel it is: the first one of
+// type alpha, held to what the reference's render asks of a Modular frame's alpha (j40.h:7926-7935). "Ual?": a Modular frame (its
+// alpha is always rendered) or no alpha channel; "TODO": an alpha channel or a frame outside what the keep-mode plan below lays out.
+uint32_t alpha_keep_scope(const Frame &fr, int32_t *index) {
+	*index = -1;
+	if (fr.fh.is_modular) return E4("Ual?");
+	for (size_t i = 0; i < fr.im.ec.size() && *index < 0; ++i) if (fr.im.ec[i].type == EC_ALPHA) *index = (int32_t) i;
+	if (*index < 0) return E4("Ual?");
+	const ExtraChannel &ec = fr.im.ec[(size_t) *index];
+	if (ec.bpp != fr.im.bpp || ec.exp_bits != fr.im.exp_bits || ec.dim_shift || ec.alpha_associated) return ERR_TODO;
+	if (fr.im.bpp < 8 || fr.im.bpp > 15 || fr.im.exp_bits || !fr.im.modular_16bit_buffers) return ERR_TODO;
+	// the extra channels in the pass-group sections of a single pass, no transform over the frame-wide image
+	if (fr.lf_only || fr.toc.single || fr.fh.num_passes != 1 || fr.num_gm_channels != 0 || fr.gmodular.nb_meta_channels != 0) return ERR_TODO;
+	if (!fr.gmodular.transforms.empty() || fr.gmodular.channel.size() != fr.im.ec.size() || fr.gmodular.channel.size() > (size_t) MOD_MAX_CHANNELS) return ERR_TODO;
+	return 0;
+}
+
 // VarDCT frames with extra channels: after its HF coefficients every pass-group section carries the extra channels of the group
 // as a Modular sub-image (j40.h:7024-7033). The reference decodes it and later drops it with the rest of the Modular image
 // (j40__combine_vardct, j40.h:7868), so it never reaches the pixels, but damage in it is reported. The entropy kernel leaves the
 // bit where each section's coefficients end; this lays out a Modular decode of what follows, into planes nobody reads.
 // end_bits / k1_status: per section (pass-major), from the device. Sections that already failed are left out; a header that does
 // not parse yields that section's error in trailer_errors (section index, code).
+//
+// keep (the alpha channel is wanted, j40hip_frame_set_alpha): the sections decode into frame-wide planes instead, one per extra channel
+// (HostModPlan::plane_w / plane_h), each section over its group's rectangle -- what a Modular frame's pass-group sections do in
+// build_modular_plan; reversible colour transforms a section's own header lists are undone over its rectangle like there
+// (DevModSection::local_off), any other transform of a section's own is "TODO". first_group / group_count: the groups a ranged
+// decode went through (the others' end bits mean nothing); -1: all.
 uint32_t build_trailer_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, const uint32_t *end_bits, const uint32_t *k1_status, HostModPlan *hp,
-		std::vector<std::pair<int32_t, uint32_t>> *trailer_errors, std::vector<int32_t> *section_of) {
+		std::vector<std::pair<int32_t, uint32_t>> *trailer_errors, std::vector<int32_t> *section_of, bool keep, int32_t first_group, int32_t group_count) {
 	const Modular &gm = fr.gmodular;
 	if (cs_size + 16 >= ((size_t) 1 << 29)) return ERR_TODO;   // the kernels address the codestream with 32-bit BIT positions
 	const int32_t nch = (int32_t) gm.channel.size();
@@ -812,8 +835,15 @@ uint32_t build_trailer_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, 
 	hp->pool_u8.resize(hp->pool_u8.size() + 16, 0);
 	auto wp_bytes = [](const WPParams &wp, int8_t *out) { out[0] = wp.p1; out[1] = wp.p2; for (int i = 0; i < 5; ++i) out[2 + i] = wp.p3[i]; for (int i = 0; i < 4; ++i) out[7 + i] = wp.w[i]; out[11] = 0; };
 	const int32_t num_groups = (int32_t) fr.fh.num_groups;
+	const int32_t nextra = nch - fr.num_gm_channels;
+	if (keep) {
+		if (fr.num_gm_channels != 0 || fr.fh.num_passes != 1 || fr.toc.single) return ERR_TODO;
+		df.num_channels = nextra;
+		for (int32_t c = 0; c < nextra; ++c) { hp->plane_w.push_back(fr.fh.width); hp->plane_h.push_back(fr.fh.height); hp->plane_meta.push_back(0); }
+	}
 	for (int32_t pass = 0; pass < fr.fh.num_passes; ++pass) for (int32_t g = 0; g < num_groups; ++g) {
 		const int32_t idx = pass * num_groups + g;
+		if (group_count >= 0 && (g < first_group || g >= first_group + group_count)) continue;
 		if (k1_status[idx]) continue;
 		const Section &ps = fr.toc.single ? fr.toc.single_section : fr.toc.pass_groups[(size_t) idx];
 		const GroupInfo gi = group_info(fr.fh, g);
@@ -831,8 +861,21 @@ uint32_t build_trailer_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, 
 		s.gx = s.gy = 0; s.gw = gi.gw; s.gh = gi.gh;
 		s.sidx = (int32_t) (1 + 3 * fr.fh.num_lf_groups + 17 + idx);
 		s.first_channel = 0; s.num_channels = (int32_t) m.channel.size();
+		if (keep) {
+			const LfGroup &gg = fr.lf_groups[(size_t) gi.ggidx];
+			s.sub_off = -1; s.gx = gg.left + gi.gx_in_gg; s.gy = gg.top + gi.gy_in_gg;
+			if (s.num_channels != nextra) return ERR_TODO;   // (a palette of the section's own: another channel list)
+			s.local_off = (int32_t) (hp->local_rct.size() / 2);
+			for (const Transform &t : m.transforms) {
+				if (t.kind != Transform::RCT || t.begin_c < 0 || t.begin_c + 3 > nextra) return ERR_TODO;
+				hp->local_rct.push_back(t.begin_c); hp->local_rct.push_back(t.rct_type);
+				++s.local_count;
+			}
+			max_width = std::max(max_width, gi.gw);
+		} else {
 		s.sub_off = (int32_t) hp->sub_w.size();   // everything lands in planes of the section's own
 		for (const Plane &p : m.channel) { hp->sub_w.push_back(p.width); hp->sub_h.push_back(p.height); hp->sub_meta.push_back(p.vshift < 0); max_width = std::max(max_width, p.width); }
+		}
 		wp_bytes(m.wp, s.wp);
 		attach_tables(fr, hp, global_spec, global_tree_off, m, &s);
 		hp->sections.push_back(s);
@@ -845,7 +888,12 @@ uint32_t build_trailer_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, 
 	hp->lz_window_size = 0;
 	if (hp->any_lz77) {
 		size_t most = 0;
-		for (const DevModSection &s : hp->sections) { size_t n = 0; for (int32_t c = 0; c < s.num_channels; ++c) n += (size_t) hp->sub_w[(size_t) (s.sub_off + c)] * (size_t) hp->sub_h[(size_t) (s.sub_off + c)]; most = std::max(most, n); }
+		for (const DevModSection &s : hp->sections) {
+			size_t n = 0;
+			if (s.sub_off < 0) n = (size_t) s.num_channels * (size_t) s.gw * (size_t) s.gh;
+			else for (int32_t c = 0; c < s.num_channels; ++c) n += (size_t) hp->sub_w[(size_t) (s.sub_off + c)] * (size_t) hp->sub_h[(size_t) (s.sub_off + c)];
+			most = std::max(most, n);
+		}
 		hp->lz_window_size = (uint32_t) std::min<size_t>(most + 16, (size_t) 1 << 26);
 	}
 	assign_coop(hp);

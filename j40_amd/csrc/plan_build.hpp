@@ -108,8 +108,9 @@ uint32_t build_modular_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, 
 
 // VarDCT frames with extra channels: the Modular sub-images behind the HF coefficients of every pass-group section, laid out for
 // K3 (plan_build.cpp); sections: those whose coefficients decoded, section_of[i] = their index in the frame
+uint32_t alpha_keep_scope(const Frame &fr, int32_t *index);
 uint32_t build_trailer_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, const uint32_t *end_bits, const uint32_t *k1_status, HostModPlan *hp,
-		std::vector<std::pair<int32_t, uint32_t>> *trailer_errors, std::vector<int32_t> *section_of);
+		std::vector<std::pair<int32_t, uint32_t>> *trailer_errors, std::vector<int32_t> *section_of, bool keep = false, int32_t first_group = 0, int32_t group_count = -1);
 
 // pieces of build_vardct_plan shared with the pipeline's front plan (plan_front.cpp)
 void fill_frame_constants(const Frame &fr, DevFrame *out);

@@ -578,10 +578,15 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 
 	CodeSpecW gspec;  // global code spec shared by every LF-group Modular stream
 	{
-		std::vector<uint8_t> map((size_t) tree.num_ctx);
-		for (int i = 0; i < tree.num_ctx; ++i) map[(size_t) i] = (uint8_t) i;
-		gspec.init(tree.num_ctx, map, tree.num_ctx);
+		// gprefix=1: the global code is a prefix code; glz77=1: it has LZ77 enabled (the distance context in a cluster of its own), and
+		// the extra channels' sub-images (alpha=1) use it: runs of equal small tokens become copies of the previous symbol
+		const int glz77 = opt.geti("glz77", 0);
+		std::vector<uint8_t> map((size_t) (tree.num_ctx + (glz77 ? 1 : 0)));
+		for (size_t i = 0; i < map.size(); ++i) map[i] = (uint8_t) i;
+		gspec.lz77 = glz77 != 0;
+		gspec.init(tree.num_ctx, map, (int) map.size());
 		gspec.log_alpha = 8;
+		gspec.use_prefix = opt.geti("gprefix", 0) != 0;
 		for (auto &c : gspec.cfg) c = HybridCfg{4, 2, 0};
 	}
 	std::vector<StreamEncoder> lfq_enc, meta_enc;
@@ -609,20 +614,57 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	// ---- optional alpha extra channel: a Modular sub-image per pass group, coded after the group's HF coefficients
 	//      (j40.h:7024-7034) with the global tree and code spec ----
 	const int with_alpha = opt.geti("alpha", 0);
+	// With alpha=1: extra=N puts N depth channels ahead of the alpha channel (coded in the same sub-images, so that alpha is not
+	// extra channel 0); bpp=9..15 codes alpha at the image's depth, its samples over the whole range; alphabpp= gives alpha a depth
+	// of its own and alphaassoc=1 flags it associated (two things the reference's render answers with "TODO" in a Modular frame).
+	const int ec_extra = with_alpha ? opt.geti("extra", 0) : 0;
+	const int ec_bpp = opt.geti("bpp", 8), alpha_bpp = opt.geti("alphabpp", ec_bpp), alpha_assoc = opt.geti("alphaassoc", 0);
+	const int num_ec = with_alpha ? ec_extra + 1 : 0;
 	if (with_alpha && num_passes > 1) die("vardct: alpha with several passes is not generated");
+	if (ec_extra < 0 || ec_extra > 3) die("vardct: extra=0..3 (four extra channels with alpha, j40.h:3171)");
+	if (with_alpha && (alpha_bpp < 8 || alpha_bpp > 15)) die("vardct: alphabpp=8..15 (16-bit buffers)");
+	if (!with_alpha && (opt.kv.count("alphabpp") || alpha_assoc)) die("vardct: alphabpp= and alphaassoc= want alpha=1");
 	std::vector<StreamEncoder> alpha_enc;
 	if (with_alpha) {
 		Channel alpha(W, H);
+		const int amax = (1 << alpha_bpp) - 1, emax = (1 << ec_bpp) - 1;
 		for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) {
 			int v = (x * 3 + y * 2) / 4 + (int) rng.below(5) - 2 + (((x / 40) + (y / 24)) % 3 == 0 ? 90 : 0);
-			alpha.at(x, y) = std::max(0, std::min(255, v));
+			v = std::max(0, std::min(255, v));
+			if (alpha_bpp != 8) v = std::min(amax, v * amax / 255 + ((x * 7 + y * 13) & ((1 << (alpha_bpp - 8)) - 1)));
+			alpha.at(x, y) = v;
 		}
 		for (int g = 0; g < num_groups; ++g) {
 			const int gx = (g % gcols) * 256, gy = (g / gcols) * 256, gw = std::min(256, W - gx), gh = std::min(256, H - gy);
-			std::vector<Channel> sub(1, Channel(gw, gh));
-			for (int y = 0; y < gh; ++y) for (int x = 0; x < gw; ++x) sub[0].at(x, y) = alpha.at(gx + x, gy + y);
+			std::vector<Channel> sub((size_t) num_ec, Channel(gw, gh));
+			for (int y = 0; y < gh; ++y) for (int x = 0; x < gw; ++x) {
+				for (int k = 0; k < ec_extra; ++k) sub[(size_t) k].at(x, y) = (((((gx + x) >> 3) * (k + 2) + ((gy + y) >> 2)) & 31) * emax) / 31;
+				sub[(size_t) ec_extra].at(x, y) = alpha.at(gx + x, gy + y);
+			}
 			alpha_enc.emplace_back(gspec);
-			encode_channel(tree, sub, 0, 1 + 3 * num_lf_groups + 17 + g, wp_in(200 + g), alpha_enc.back());
+			if (!gspec.lz77) for (int c = 0; c < num_ec; ++c) encode_channel(tree, sub, c, 1 + 3 * num_lf_groups + 17 + g, wp_in(200 + g), alpha_enc.back());
+			else {
+				// glz77=1: a run of >= 3 further items equal to one item becomes a copy at special distance code 1, the previous symbol
+				// (the sub-image's distance multiplier, its width, is not zero; j40.h:2834) -- the Modular mode's run-length pass
+				StreamEncoder raw(gspec);
+				for (int c = 0; c < num_ec; ++c) encode_channel(tree, sub, c, 1 + 3 * num_lf_groups + 17 + g, wp_in(200 + g), raw);
+				StreamEncoder &enc = alpha_enc.back();
+				const auto &it = raw.items;
+				for (size_t i = 0; i < it.size(); ) {
+					size_t j = i + 1;
+					while (j < it.size() && it[j].token == it[i].token && it[i].nextra == 0 && it[j].nextra == 0 && it[i].token < 16) ++j;
+					enc.items.push_back(it[i]);
+					const size_t run = j - i - 1;
+					if (run >= 3 && it[i].token < 16) {   // (split_exp 4: a token below 16 is its own value)
+						HToken t = hybrid_encode((uint32_t) run - (uint32_t) gspec.lz_min_length, gspec.lz_len_cfg);
+						enc.items.push_back({it[i + 1].cluster, t.token + (uint32_t) gspec.lz_min_symbol, t.extra, (uint8_t) t.nextra});
+						const uint32_t lzcl = gspec.cluster_map[(size_t) gspec.total_dist() - 1];
+						HToken d = hybrid_encode(1, gspec.cfg[lzcl]);
+						enc.items.push_back({lzcl, d.token, d.extra, (uint8_t) d.nextra});
+						i = j;
+					} else i = i + 1;
+				}
+			}
 			count_stream(gspec, alpha_enc.back());
 		}
 	}
@@ -948,10 +990,36 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	write_size_header(cs, W, H);
 	const int icc_bytes = opt.geti("icc", 0);                // > 0: ColourEncoding with want_icc and an ICC stream of that many coded bytes
 	const int img_bpp = opt.geti("bpp", 8);   // 9..15: the renderer's scaling to 8 bits and the long way through the transfer curve get work
-	if (img_bpp != 8 && (icc_bytes || with_alpha)) die("vardct: bpp combines with neither icc nor alpha here");
+	if (img_bpp != 8 && icc_bytes) die("vardct: bpp does not combine with icc here");
 	const int noxyb = opt.geti("noxyb", 0);
 	if (noxyb && (!with_alpha || icc_bytes || !nonzero_header || x_qm != 3 || b_qm != 2)) die("vardct: noxyb wants alpha=1 fullheader=1 and the default qm scales");
-	if (img_bpp != 8) {
+	if (with_alpha && (img_bpp != 8 || ec_extra || alpha_bpp != 8 || alpha_assoc)) {
+		cs.put(0, 1);                       // ImageMetadata: not all_default
+		cs.put(0, 1);                       // no extra fields
+		write_bit_depth(cs, img_bpp);
+		cs.put(1, 1);                       // modular_16bit_buffers
+		if (num_ec == 1) cs.put(1, 2); else { cs.put(2, 2); cs.put((uint64_t) (num_ec - 2), 4); }   // num_extra_channels (j40.h:3170)
+		for (int k = 0; k < ec_extra; ++k) {
+			cs.put(0, 1);                   // not the default alpha
+			cs.put(1, 2);                   // type: enum selector 1 = depth
+			write_bit_depth(cs, img_bpp);
+			cs.put(0, 2);                   // dim_shift 0
+			cs.put(0, 2);                   // no name
+		}
+		if (alpha_bpp == 8 && !alpha_assoc) cs.put(1, 1);   // d_alpha
+		else {
+			cs.put(0, 1);
+			cs.put(0, 2);                   // type: enum selector 0 = alpha
+			write_bit_depth(cs, alpha_bpp);
+			cs.put(0, 2);                   // dim_shift 0
+			cs.put(0, 2);                   // no name
+			cs.put((uint64_t) (alpha_assoc ? 1 : 0), 1);   // alpha_associated (j40.h:3188)
+		}
+		cs.put(noxyb ? 0 : 1, 1);           // xyb_encoded
+		cs.put(1, 1);                       // ColourEncoding.all_default
+		cs.put(0, 2);                       // extensions
+		cs.put(1, 1);                       // default_m
+	} else if (img_bpp != 8) {
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		cs.put(0, 1);                       // no extra fields
 		write_bit_depth(cs, img_bpp);
@@ -997,7 +1065,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.u64(skip_smooth ? 128 : 0);      // flags
 		if (noxyb) cs.put(0, 1);            // do_ycbcr (read only without xyb_encoded)
 		cs.put(0, 2);                       // log_upsampling
-		for (int i = 0; i < with_alpha; ++i) cs.put(0, 2);   // ec_log_upsampling
+		for (int i = 0; i < num_ec; ++i) cs.put(0, 2);   // ec_log_upsampling
 		if (!noxyb) { cs.put((uint64_t) x_qm, 3); cs.put((uint64_t) b_qm, 3); }
 		cs.u32(num_passes, 1, 0, 2, 0, 3, 0, 4, 3);
 		if (num_passes > 1) {
@@ -1005,7 +1073,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			for (int i = 0; i < num_passes - 1; ++i) cs.put(0, 2);  // shift[i]
 		}
 		cs.put(0, 1);                       // have_crop
-		for (int i = -1; i < with_alpha; ++i) cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 2);  // blend mode: replace (the frame's, then each extra channel's, j40.h:5299)
+		for (int i = -1; i < num_ec; ++i) cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 2);  // blend mode: replace (the frame's, then each extra channel's, j40.h:5299)
 		cs.put(1, 1);                       // is_last
 		cs.u32(0, 0, 0, 0, 4, 16, 5, 48, 10);  // name length 0
 		// RestorationFilter (j40.h:5339-5366). gab=1: Gaborish with the default weights, gab=2: custom weights; epf=1..3: iterations of the
