@@ -13,7 +13,7 @@ CXXFLAGS += -DJ40_LANE_EV_FLUSH=$(EVENT_RING)
 HIPFLAGS = --offload-arch=$(ARCH) -std=c++17 -O3 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fvisibility=hidden -Wall -DJ40_LANE_EV_FLUSH=$(EVENT_RING) $(EXTRA_HIPFLAGS)
 SRC = j40_amd/csrc
 HOST_OBJS = build/obj/plan_build.o build/obj/plan_front.o build/obj/entropy.o build/obj/modular.o build/obj/tables.o build/obj/frame.o build/obj/capi_host.o build/obj/api.o
-DEV_OBJS = build/obj/kernels.o build/obj/modular_kernels.o build/obj/runtime.o build/obj/pipeline.o build/obj/lf_tail_kernels.o build/obj/modular_coop.o build/obj/modular_quad.o build/obj/modular_split.o build/obj/lf_decode.o build/obj/plan_kernels.o build/obj/async.o build/obj/hostcopy.o build/obj/lf_preview.o build/obj/alpha_kernels.o
+DEV_OBJS = build/obj/kernels.o build/obj/modular_kernels.o build/obj/runtime.o build/obj/pipeline.o build/obj/lf_tail_kernels.o build/obj/modular_coop.o build/obj/modular_quad.o build/obj/modular_split.o build/obj/lf_decode.o build/obj/plan_kernels.o build/obj/async.o build/obj/hostcopy.o build/obj/lf_preview.o build/obj/alpha_kernels.o build/obj/region_kernels.o
 
 .PHONY: all lib tools oracle hostsim clean
 all: lib tools hostsim oracle
@@ -37,7 +37,7 @@ build/obj/lf_decode.o: EXTRA_HIPFLAGS += -mllvm -amdgpu-sched-strategy=max-ilp
 build/libj40hip.so: $(HOST_OBJS) $(DEV_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -lpthread -lhsa-runtime64
 
-hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/liboracle_driver.so build/api_threads
+hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/liboracle_driver.so build/api_threads
 # test-only glue: parses a stream with the product's host parser, takes the plan view and hands it to
 # the CPU oracle (oracle/libj40oracle.so)
 build/liboracle_driver.so: tests/oracle_driver.c build/libj40hip.so oracle/hotpath_oracle.c include/j40hip.h
@@ -63,6 +63,12 @@ ALPHASIM_SRC = tests/hostsim/alpha_sim.cpp $(SRC)/plan_build.cpp $(SRC)/plan_fro
 build/libhostsim_alpha.so: $(ALPHASIM_SRC) $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp) include/j40hip.h
 	@mkdir -p build
 	$(CXX) $(HOSTSIM_FLAGS) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -o $@ $(ALPHASIM_SRC) -lpthread
+
+# region decode on the CPU (tests/test_region.py): device/region_dev.h's index, gather and crop functions over the host plan's varblock list
+REGIONSIM_SRC = tests/hostsim/region_sim.cpp $(SRC)/plan_build.cpp $(SRC)/plan_front.cpp $(SRC)/entropy.cpp $(SRC)/modular.cpp $(SRC)/tables.cpp $(SRC)/frame.cpp
+build/libhostsim_region.so: $(REGIONSIM_SRC) $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp) include/j40hip.h
+	@mkdir -p build
+	$(CXX) $(HOSTSIM_FLAGS) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -o $@ $(REGIONSIM_SRC) -lpthread
 
 build/jxlsynth: tools/jxlsynth.cpp $(wildcard tools/*.hpp) $(SRC)/tables.cpp $(SRC)/device/special8_dev.h $(SRC)/device/idct_dev.h
 	@mkdir -p build

@@ -287,6 +287,31 @@ J40HIP_API void j40hip_frame_alpha(const j40hip_frame *f, int32_t out[4]);
  * J40HIP_U16X4, rows pixel-aligned). Asynchronous on `stream`. 0, "rnge" for a bpp or rectangle out of range, "Ufm?". */
 J40HIP_API uint32_t j40hip_kat_device_alpha_merge(void *rgba_dev, size_t stride_bytes, const int16_t *plane_dev, int32_t pitch, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bpp, int32_t format, void *stream);
 
+/* ---- region decode: a rectangle of the frame from the pass groups that cover it ("Region decode"). A pass group is
+ *      entropy-coded in a section of its own and no varblock straddles a group, so rectangle (x0, y0, w, h) needs the sections and
+ *      varblocks of its COVER only: group columns x0 >> shift .. (x0 + w - 1) >> shift, rows likewise (shift = group_size_shift).
+ *      set: any parsed frame, uploaded or not; it holds from the next decode on, across uploads. The rectangle must lie inside the
+ *      frame with w, h > 0, else "rnge"; (0, 0, 0, 0) and the full-frame rectangle clear the region (the frame then decodes exactly as
+ *      without one). An LF-only frame: "Ulf?". A region and a partial group range (j40hip_frame_set_group_range) exclude each other:
+ *      whichever setter comes second returns "Urg?". A refused call leaves the frame as it was. j40hip_batch_create refuses a member
+ *      with a region ("Urg?"); pipelines own their frames and never see one.
+ *      With a region j40hip_frame_decode / _timed / _decode_to_host write w x h pixels of the frame's format, pixel (i, j) being pixel
+ *      (x0 + i, y0 + j) of the whole decode, bit for bit; stride_bytes below 4 * w (u8) or 8 * w (u16) is "rnge" for both formats;
+ *      nothing outside the w pixels of each of the h rows is written; j40hip_frame_decode_to_host copies only the region back, keeps the
+ *      "evof" retry and never decodes in two phases. Only the cover's sections are entropy-decoded (every pass of them; a Modular
+ *      frame's LfGlobal section too) and only the cover's varblocks go through the pixel kernels, so j40hip_frame_status is the verdict
+ *      over THOSE sections: damage in a section outside the cover is not seen. A partial cover of a VarDCT frame in drop mode does not
+ *      validate the extra channels' sub-images (as with a group range).
+ *      Where the work cannot be limited to the cover it is widened to every group, and the rectangle cut out of the whole picture: a
+ *      Modular frame with a Squeeze step, a palette with predicted deltas or without one section per group; restoration filters in
+ *      force on a frame that signals them; keep-alpha mode. A region is served wherever the whole frame is.
+ *      j40hip_frame_region: out[0..3] the rectangle (0, 0, width, height without a region), out[4..7] its cover in groups (first
+ *      column, first row, columns, rows), out[8] a region is set, and of the last decode with it: out[9] it was widened to the whole
+ *      frame, out[10] the pass-group sections it launched (a Modular frame's LfGlobal section included), out[11] the varblocks its
+ *      pixel kernels took (0 for Modular frames). ---- */
+J40HIP_API uint32_t j40hip_frame_set_region(j40hip_frame *f, int32_t x0, int32_t y0, int32_t w, int32_t h);
+J40HIP_API void j40hip_frame_region(const j40hip_frame *f, int32_t out[12]);
+
 /* After the stream has been synchronised: first failing section in TOC order -> its 4-char code
  * ("coef", "shrt", "excs", "ans?" ...), 0 if every section decoded cleanly (j40.h:530-534). */
 J40HIP_API uint32_t j40hip_frame_status(j40hip_frame *f);

@@ -119,6 +119,7 @@ def lib():
         "j40hip_copy_engine": (C.c_int, [C.c_int, vp, vp]),
         "j40hip_frame_restoration": (None, [vp, vp]), "j40hip_frame_set_restoration": (None, [vp, C.c_int]), "j40hip_frame_sharpness": (C.c_int, [vp, i64, vp]),
         "j40hip_frame_set_alpha": (u32, [vp, C.c_int]), "j40hip_frame_alpha": (None, [vp, vp]),
+        "j40hip_frame_set_region": (u32, [vp, i32, i32, i32, i32]), "j40hip_frame_region": (None, [vp, vp]),
         "j40hip_kat_device_alpha_merge": (u32, [vp, sz, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
         "j40hip_frame_read_xyb": (u32, [vp, C.c_int, vp]), "j40hip_frame_restoration_ms": (C.c_float, [vp]),
         "j40hip_kat_device_restoration": (u32, [vp, i32, i32, vp, vp, vp, C.c_int, C.c_int, vp]),
@@ -246,6 +247,30 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False):
     err = img.error()
     img.free()
     return err, out
+
+
+def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0):
+    """rectangle (x, y, w, h) of the image through the thin C-ABI: returns (err4, ndarray [h, w, 4] or None), uint8 or uint16 with
+    fmt=J40_U16X4 -- the crop of what decode() returns, decoded from the pass groups that cover it (Frame.set_region). The verdict is
+    the one over the sections that were decoded, then the public API's look behind the frame."""
+    try:
+        fr = Frame(data)
+    except J40Error as e:
+        return e.code, None
+    try:
+        code = fr.set_region(x, y, w, h)
+        if code:
+            return code, None
+        fr.set_output_format(fmt)
+        fr.upload(device)
+        err, out = fr.decode_to_host()
+        if not err:   # bytes behind the frame, as the public API looks for them
+            err = err4(lib().j40hip_frame_after_frame_status(fr.h))
+        return err, (None if err else out)
+    except J40Error as e:
+        return e.code, None
+    finally:
+        fr.close()
 
 
 def decode_timed(buf, size, want_pixels=False):
@@ -476,11 +501,32 @@ class Frame:
         return int(lib().j40hip_frame_output_format(self.h))
 
     def decode_to_host(self):
-        """(err4, pixels [h, w, 4]): uint8, or uint16 when the frame is set to J40_U16X4"""
+        """(err4, pixels [h, w, 4]): uint8, or uint16 when the frame is set to J40_U16X4; with a region set (set_region) h and w are
+        the rectangle's and only it comes back from the device"""
         u16 = self.output_format() == J40_U16X4
-        out = np.zeros((self.height, self.width, 4), np.uint16 if u16 else np.uint8)
-        code = lib().j40hip_frame_decode_to_host(self.h, out.ctypes.data, self.width * (8 if u16 else 4))
+        r = self.region()
+        w, h = (r["w"], r["h"]) if r["set"] else (self.width, self.height)
+        out = np.zeros((h, w, 4), np.uint16 if u16 else np.uint8)
+        code = lib().j40hip_frame_decode_to_host(self.h, out.ctypes.data, w * (8 if u16 else 4))
         return err4(code), out
+
+    # ---- region decode (include/j40hip.h) ----
+    def set_region(self, x, y, w, h):
+        """the decode entry points write rectangle (x, y, w, h) of the frame, w x h pixels, from the pass groups that cover it
+        (j40hip_frame_set_region). Returns "" or the refusal: "rnge" (not inside the frame), "Ulf?" (an LF-only frame), "Urg?" (a
+        partial group range is set); (0, 0, 0, 0) and the full frame clear the region"""
+        return err4(lib().j40hip_frame_set_region(self.h, int(x), int(y), int(w), int(h)))
+
+    def clear_region(self):
+        return self.set_region(0, 0, 0, 0)
+
+    def region(self):
+        """j40hip_frame_region: the rectangle x, y, w, h (the whole frame without a region); its cover in groups gx0, gy0, gcols, grows;
+        set; and of the last decode with a region: widened (to every group), sections (pass-group sections launched), varblocks (what
+        the pixel kernels took; 0 for Modular frames)"""
+        a = np.zeros(12, np.int32)
+        lib().j40hip_frame_region(self.h, a.ctypes.data)
+        return dict(zip(["x", "y", "w", "h", "gx0", "gy0", "gcols", "grows", "set", "widened", "sections", "varblocks"], a.tolist()))
 
     def two_phase_sections(self):
         """how decode_to_host last went: k > 0 = two phases with the k longest sections beside the others, 0 = one, -1 = not yet"""

@@ -21,6 +21,12 @@ struct j40hip_frame {
 	int alpha = -1;                  // the alpha channel of a VarDCT frame (j40hip_frame_set_alpha): -1 as J40HIP_ALPHA says, 0 dropped (A = 255, the reference's pixels), 1 kept
 	bool alpha_written = false;      // the last decode merged the alpha channel into its pixels
 	int32_t output_format = J40HIP_U8X4;   // what the decode entry points write (j40hip_frame_set_output_format): u8x4 or u16x4
+	// region decode (j40hip_frame_set_region): the rectangle the decode entry points write instead of the whole frame, and what the last
+	// decode with it cost (j40hip_frame_region's fields 9-11)
+	bool region_set = false;
+	int32_t region[4] = {0, 0, 0, 0};                              // x0, y0, w, h
+	int32_t region_widened = 0, region_sections = 0, region_varblocks = 0;
+	bool partial_range = false;      // j40hip_frame_set_group_range narrowed the uploaded frame to some of its groups (excludes a region)
 	int threads = 1;                 // what the frame was parsed with: the plan build at upload may use as many (plan_build.cpp)
 	// backing storage of the plan views (include/j40hip.h)
 	struct Views {

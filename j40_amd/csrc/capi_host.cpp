@@ -5,6 +5,7 @@
 #include <type_traits>
 #include "capi.hpp"
 #include "tables.hpp"
+#include "device/region_dev.h"
 
 using namespace j40hip;
 
@@ -177,6 +178,34 @@ void j40hip_frame_alpha(const j40hip_frame *h, int32_t out[4]) {
 	for (size_t i = 0; i < h->frame.im.ec.size(); ++i) if (h->frame.im.ec[i].type == j40hip::EC_ALPHA) { out[0] = (int32_t) i; out[1] = h->frame.im.ec[i].bpp; break; }
 	out[2] = j40hip_alpha_kept(h) ? 1 : 0;
 	out[3] = h->alpha_written ? 1 : 0;
+}
+
+// ---- region decode (include/j40hip.h) ----
+uint32_t j40hip_frame_set_region(j40hip_frame *h, int32_t x0, int32_t y0, int32_t w, int32_t hh) {
+	if (!h) return j40hip::ERR_RNGE;
+	if (h->frame.lf_only) return E4("Ulf?");
+	const int32_t W = h->frame.fh.width, H = h->frame.fh.height;
+	const bool clear = x0 == 0 && y0 == 0 && ((w == 0 && hh == 0) || (w == W && hh == H));
+	if (!clear) {
+		if (x0 < 0 || y0 < 0 || w <= 0 || hh <= 0 || (int64_t) x0 + w > W || (int64_t) y0 + hh > H) return j40hip::ERR_RNGE;
+		if (h->partial_range) return E4("Urg?");
+	}
+	h->region_set = !clear;
+	h->region[0] = clear ? 0 : x0; h->region[1] = clear ? 0 : y0; h->region[2] = clear ? 0 : w; h->region[3] = clear ? 0 : hh;
+	h->region_widened = h->region_sections = h->region_varblocks = 0;
+	return 0;
+}
+void j40hip_frame_region(const j40hip_frame *h, int32_t out[12]) {
+	if (!out) return;
+	memset(out, 0, sizeof(int32_t) * 12);
+	if (!h) return;
+	const j40hip::FrameHeader &fh = h->frame.fh;
+	out[2] = fh.width; out[3] = fh.height;
+	if (h->region_set) for (int i = 0; i < 4; ++i) out[i] = h->region[i];
+	const j40hip::RegionCover c = j40hip::region_cover(out[0], out[1], out[2], out[3], fh.group_size_shift, fh.gcolumns);
+	out[4] = c.gx0; out[5] = c.gy0; out[6] = c.cols; out[7] = c.rows;
+	out[8] = h->region_set ? 1 : 0;
+	out[9] = h->region_widened; out[10] = h->region_sections; out[11] = h->region_varblocks;
 }
 
 void j40hip_frame_free(j40hip_frame *f) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "plan.h"
 #include "restore_dev.h"
+#include "region_dev.h"
 
 namespace j40hip {
 
@@ -86,5 +87,14 @@ void launch_pack_planes_rect(const int16_t *r, const int16_t *g, const int16_t *
 // alpha_kernels.hip: the kept alpha channel of a VarDCT frame into rectangle (x0, y0, w, h) of pixels already written
 void launch_alpha_merge(const int16_t *plane, int32_t pitch, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16);
 void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
+
+// region decode (device/region_kernels.hip, region_dev.h). launch_region_index: the group-major index of the `count` varblocks of
+// `sorted` -- cursor: nkeys = groups * REGION_KEYS words of scratch, seg_start: nkeys + 1 words, index: count words.
+// launch_region_gather: the cover's varblocks, class by class from class_start[28], into `list` with their positions counted from the
+// cover's origin, and the cover's groups into `order`. launch_region_crop: w x h pixels of pixel_bytes (4 or 8) from src to dst, both
+// pointing at the rectangle's first pixel
+void launch_region_index(const DevVarblock *sorted, uint32_t count, int32_t shift, int32_t gcolumns, uint32_t nkeys, uint32_t *cursor, uint32_t *seg_start, uint32_t *index, hipStream_t stream);
+void launch_region_gather(const DevVarblock *sorted, const uint32_t *index, const uint32_t *seg_start, const RegionCover &cover, const int32_t *class_start, DevVarblock *list, uint32_t *order, hipStream_t stream);
+void launch_region_crop(const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int32_t w, int32_t h, int32_t pixel_bytes, hipStream_t stream);
 
 } // namespace j40hip

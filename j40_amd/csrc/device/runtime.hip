@@ -386,6 +386,19 @@ struct j40hip_device_state {
 		std::vector<std::pair<int32_t, uint32_t>> header_errors;  // sections whose sub-image header did not parse
 		std::vector<uint8_t> staging;                             // what was copied into the block (the copy is asynchronous)
 	} alpha;
+	// region decode (j40hip_frame_set_region; decode_region below). The group-major index of d_vb_sorted, built on the device at the
+	// first region decode of this upload (region_dev.h): seg_start, where every (group, class) segment of `index` starts, and on the
+	// host only the segments' sizes. Per region: the cover's varblocks (list, class_start) and its groups (order), gathered on the
+	// device when the cover changes. staging: the cover-sized image the pixel kernels write before the rectangle is cut out, one block
+	// of the device memory cache, grown on demand, given back with the frame.
+	struct Region {
+		bool index_ready = false;
+		uint32_t *d_cursor = nullptr, *d_seg_start = nullptr, *d_index = nullptr, *d_order = nullptr;
+		std::vector<uint32_t> counts;                 // [num_groups * REGION_KEYS]
+		DevVarblock *d_list = nullptr; size_t list_capacity = 0;
+		int32_t class_start[REGION_KEYS]; RegionCover gathered = {0, 0, 0, 0, 0, 0};   // (what d_list and d_order hold: cols = 0, nothing)
+		void *staging = nullptr; size_t staging_bytes = 0;
+	} region;
 	// a batch decoded the frame (trailers_pending): where, for the merge at j40hip_frame_status
 	void *pending_rgba = nullptr; size_t pending_stride = 0;
 
@@ -419,6 +432,10 @@ extern "C" void j40hip_release_device(j40hip_frame *f) {
 	if (f->dev->alpha.block) {
 		if (!f->dev->idle) (void) hipDeviceSynchronize();
 		cache_release(f->dev->device, f->dev->alpha.block, f->dev->alpha.block_bytes, false);
+	}
+	if (f->dev->region.staging) {
+		if (!f->dev->idle) (void) hipDeviceSynchronize();
+		cache_release(f->dev->device, f->dev->region.staging, f->dev->region.staging_bytes, false);
 	}
 	for (auto &b : f->dev->buffers) b.release();
 	for (auto &e : f->dev->ev) if (e) (void) hipEventDestroy(e);
@@ -598,10 +615,32 @@ static size_t pixel_bytes(const j40hip_frame *h) { return out16(h) ? 8 : 4; }
 // a 16-bit frame's rows must hold 8 * width bytes: "rnge" before anything is launched (the u8 entry points keep their old contract)
 static bool stride_too_small(const j40hip_frame *h, size_t stride_bytes) { return out16(h) && stride_bytes < 8 * (size_t) h->frame.fh.width; }
 
-static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
+// a Modular frame's groups can be decoded apart from each other when every group has a section of its own and no frame-wide inverse
+// transform reads across groups (j40hip_frame_set_group_range's rule; a region is otherwise widened to every group)
+static bool modular_groups_independent(const j40hip_frame *h) {
+	const j40hip_device_state *st = h->dev;
+	if (st->mod_sections_per_pass != (int32_t) h->frame.fh.num_groups) return false;
+	for (const auto &op : st->mod_ops) if (op.kind == 2 || op.kind == 4) return false;
+	return true;
+}
+
+// region (j40hip_frame_set_region): null, or the rectangle {x0, y0, w, h} that becomes the w x h pixels at rgba_dev -- the sections of
+// its cover only (LfGlobal's too), one launch per row of the cover's groups and pass, the frame-wide per-pixel transforms over the
+// cover's rows, and the rectangle packed with the destination moved back by its origin; every section where the groups depend on
+// each other
+static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, const int32_t *region = nullptr) {
 	j40hip_device_state *st = h->dev;
 	const DevModPlan &plan = st->mod;
 	const Frame &fr = h->frame;
+	RegionCover cover = {0, 0, 0, 0, 0, 0};
+	bool covered = false;   // only the cover's groups are decoded
+	if (region) {
+		cover = region_cover(region[0], region[1], region[2], region[3], fr.fh.group_size_shift, fr.fh.gcolumns);
+		const bool independent = modular_groups_independent(h);
+		covered = independent && region_cover_groups(cover) != (int32_t) fr.fh.num_groups;
+		h->region_widened = independent ? 0 : 1; h->region_varblocks = 0;
+		h->region_sections = covered ? st->mod_sections - st->mod_sections_per_pass * st->mod_passes + st->mod_passes * region_cover_groups(cover) : st->mod_sections;
+	}
 	if (ms3) (void) hipEventRecord(st->ev[0], s);
 	if (hipMemsetAsync(plan.status, 0, sizeof(uint32_t) * ((size_t) st->total_sections + 1), s) != hipSuccess) return ERR_GPU;
 	if (ms3) (void) hipEventRecord(st->ev[1], s);
@@ -611,21 +650,37 @@ static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_by
 	// (sharded decodes, j40hip_frame_set_group_range: LfGlobal's section and this process' groups of every pass)
 	const bool ranged = per_pass > 0 && !(st->first_group == 0 && st->num_groups == (int64_t) per_pass);
 	const int32_t g0 = ranged ? (int32_t) st->first_group : 0, gn = ranged ? (int32_t) st->num_groups : per_pass;
+	if (covered) {
+		launch_modular_sections(plan, 0, lead, st->mod_info, s);
+		for (int32_t p = 0; p < st->mod_passes; ++p) for (int32_t r = 0; r < cover.rows; ++r) launch_modular_sections(plan, lead + p * per_pass + (cover.gy0 + r) * cover.gcolumns + cover.gx0, cover.cols, st->mod_info, s);
+		if (st->mod_local_rcts) for (int32_t r = 0; r < cover.rows; ++r) launch_section_inverse_rcts(plan, lead + (st->mod_passes - 1) * per_pass + (cover.gy0 + r) * cover.gcolumns + cover.gx0, cover.cols, s);
+	} else {
 	if (ranged) { launch_modular_sections(plan, 0, lead, st->mod_info, s); launch_modular_sections(plan, lead + g0, gn, st->mod_info, s); }
 	else launch_modular_sections(plan, 0, lead + per_pass, st->mod_info, s);
 	for (int32_t p = 1; p < st->mod_passes; ++p) launch_modular_sections(plan, lead + p * per_pass + g0, gn, st->mod_info, s);
 	if (st->mod_local_rcts) launch_section_inverse_rcts(plan, lead + (st->mod_passes - 1) * per_pass + g0, gn, s);
+	}
 	if (ms3) (void) hipEventRecord(st->ev[2], s);
+	// (a covered region: the frame-wide per-pixel transforms over the rows of the cover's groups only)
+	const size_t frame_samples = (size_t) fr.fh.width * (size_t) fr.fh.height;
+	const size_t band_off = covered ? ((size_t) cover.gy0 << cover.shift) * (size_t) fr.fh.width : 0;
+	const size_t band_n = covered ? (size_t) (std::min<int64_t>(fr.fh.height, (int64_t) (cover.gy0 + cover.rows) << cover.shift) - ((int64_t) cover.gy0 << cover.shift)) * (size_t) fr.fh.width : 0;
 	for (const std::vector<j40hip_device_state::ModOp> *ops : {&st->mod_sub_ops, &st->mod_ops}) for (const auto &op : *ops) {
 		if (ranged && op.group >= 0 && (op.group < g0 || op.group >= g0 + gn)) continue;   // the sub-image of a group this process did not decode
-		if (op.kind == 0) launch_inverse_rct(op.a, op.b, op.c, op.n, op.p0, s);
+		if (covered && op.group >= 0 && (op.group % cover.gcolumns < cover.gx0 || op.group % cover.gcolumns >= cover.gx0 + cover.cols || op.group / cover.gcolumns < cover.gy0 || op.group / cover.gcolumns >= cover.gy0 + cover.rows)) continue;
+		if (covered && op.group < 0 && op.n == frame_samples && op.kind == 0) launch_inverse_rct(op.a + band_off, op.b + band_off, op.c + band_off, band_n, op.p0, s);
+		else if (covered && op.group < 0 && op.n == frame_samples && op.kind == 1) launch_inverse_palette_plain(op.src + band_off, op.aux, op.a + band_off, band_n, op.p0, op.p1, fr.im.bpp, s);
+		else if (op.kind == 0) launch_inverse_rct(op.a, op.b, op.c, op.n, op.p0, s);
 		else if (op.kind == 1) launch_inverse_palette_plain(op.src, op.aux, op.a, op.n, op.p0, op.p1, fr.im.bpp, s);
 		else if (op.kind == 2) launch_inverse_palette_predicted(op.src, op.aux, op.p0, op.dst_list, op.p1, op.p2, op.p3, op.p4, op.p5 & 0xffffff, op.p5 >> 24, fr.im.bpp, op.wpp, st->pal_wp_scratch, st->mod_extra_status, s);
 		else if (op.kind == 4) launch_inverse_squeeze(op.src, op.aux, op.a, op.p0, op.p1, op.p2, op.p3, op.p4 != 0, s);
 		else launch_paste_plane(op.src, op.p0, op.p1, op.a, op.p2, s);
 	}
 	const int16_t *alpha = st->alpha_channel >= 0 ? st->final_planes[(size_t) st->alpha_channel] : nullptr;
-	if (ranged) {   // only this process' pixels are written
+	if (region) {   // the rectangle alone; pixel (x0, y0) of the frame is the first one at rgba_dev
+		uint8_t *moved = (uint8_t *) rgba_dev - ((size_t) region[1] * stride_bytes + (size_t) region[0] * pixel_bytes(h));
+		launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, region[0], region[1], region[2], region[3], fr.im.bpp, moved, stride_bytes, s, out16(h));
+	} else if (ranged) {   // only this process' pixels are written
 		int32_t rects[3][4];
 		const int nr = group_range_rects(g0, gn, fr.fh.width, fr.fh.height, fr.fh.group_size_shift, rects);
 		for (int k = 0; k < nr; ++k) launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
@@ -832,6 +887,7 @@ static uint32_t upload_lf_only(j40hip_frame *h, int device, hipStream_t s);
 static uint32_t upload_impl(j40hip_frame *h, int device, hipStream_t s) {
 	if (!h) return ERR_GPU;
 	if (h->dev) j40hip_release_device(h);
+	h->partial_range = false;   // (an upload decodes every group again)
 	if (j40hip_device_count() <= device || hipSetDevice(device) != hipSuccess) return ERR_GPU;
 	if (h->frame.lf_only) return upload_lf_only(h, device, s);
 	if (h->frame.fh.is_modular) return upload_modular(h, device);
@@ -946,9 +1002,12 @@ static uint32_t j40hip_frame_upload_body(j40hip_frame *h, int device) { return u
 
 extern "C" void j40hip_frame_force_dense(j40hip_frame *h, int dense) { if (h) h->force_dense = dense != 0; }
 
+constexpr uint32_t ERR_URG = ERR4('U', 'r', 'g', '?');   // a region (j40hip_frame_set_region) where only whole frames or group ranges are served, or the other way round
+
 static uint32_t j40hip_frame_set_group_range_body(j40hip_frame *h, int64_t first_group, int64_t num_groups) {
 	if (!h || !h->dev) return ERR_GPU;
 	if (first_group < 0 || num_groups < 0 || first_group + num_groups > h->frame.fh.num_groups) return ERR_RNGE;
+	if (h->region_set && !(first_group == 0 && num_groups == h->frame.fh.num_groups)) return ERR_URG;   // a region and a partial range exclude each other
 	j40hip_device_state *st = h->dev;
 	if (st->is_modular) {
 		// Modular frames: the groups' sections are independent of each other (no predictor looks across a group's edge), and so are
@@ -959,11 +1018,12 @@ static uint32_t j40hip_frame_set_group_range_body(j40hip_frame *h, int64_t first
 			if (st->mod_sections_per_pass != (int32_t) h->frame.fh.num_groups) return ERR_TODO;
 			for (const auto &op : st->mod_ops) if (op.kind == 2 || op.kind == 4) return ERR_TODO;
 		}
-		st->first_group = first_group; st->num_groups = num_groups;
+		st->first_group = first_group; st->num_groups = num_groups; h->partial_range = !whole;
 		return 0;
 	}
 	st->first_group = first_group; st->num_groups = num_groups;
-	if (first_group == 0 && num_groups == h->frame.fh.num_groups) return 0;
+	h->partial_range = !(first_group == 0 && num_groups == h->frame.fh.num_groups);
+	if (!h->partial_range) return 0;
 	// varblocks never straddle a group (the largest transform is one group wide), so the pixel kernels' work lists are
 	// the full lists filtered by the group of each block's top-left pixel
 	const FrameHeader &fh = h->frame.fh;
@@ -1251,9 +1311,12 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 // an LF-only frame (J40HIP_PARSE_LF_ONLY) has nothing but its LF image: the full decode's entry points refuse it
 constexpr uint32_t ERR_ULF = ERR4('U', 'l', 'f', '?');
 
-static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
+static uint32_t decode_region(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3);
+
+static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, bool whole_frame = false) {
 	if (h && h->frame.lf_only) return ERR_ULF;
 	if (!h || !h->dev) return ERR_GPU;
+	if (h->region_set && !whole_frame) return decode_region(h, rgba_dev, stride_bytes, s, ms3);   // (whole_frame: decode_region's own call, for a widened region)
 	if (stride_too_small(h, stride_bytes)) return ERR_RNGE;
 	j40hip_device_state *st = h->dev;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
@@ -1291,6 +1354,137 @@ static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes
 	}
 	if (hipGetLastError() != hipSuccess) return ERR_GPU;
 	if (st->has_trailers) return finish_trailers(h, rgba_dev, stride_bytes, s, whole);   // (synchronises `s`)
+	return 0;
+}
+
+// ---- region decode (j40hip_frame_set_region, include/j40hip.h; device/region_dev.h, region_kernels.hip) ----
+// The staging image of `bytes` bytes, kept with the frame and grown on demand (nothing is allocated on the path of a later decode, so
+// the asynchronous entry point stays asynchronous).
+static uint8_t *region_staging(j40hip_device_state *st, size_t bytes) {
+	j40hip_device_state::Region &rg = st->region;
+	if (rg.staging && rg.staging_bytes < bytes) { (void) hipDeviceSynchronize(); cache_release(st->device, rg.staging, rg.staging_bytes, false); rg.staging = nullptr; }
+	if (!rg.staging) { bool clean = false; rg.staging = cache_acquire(st->device, bytes, &rg.staging_bytes, &clean); }
+	return (uint8_t *) rg.staging;
+}
+// An image of img_w x img_h pixels in the staging block whose pixel (off_x, *) sits within 16 bytes like the destination's rows do, so
+// that k_region_crop moves every row in 16-byte pieces; *stride: its row stride. Null: no memory.
+static uint8_t *region_image(j40hip_frame *h, const void *dst, size_t dst_stride, int32_t img_w, int32_t img_h, int32_t off_x, size_t *stride) {
+	const size_t pb = pixel_bytes(h), row = ((size_t) img_w * pb + 15) & ~(size_t) 15;
+	const bool alike = (uintptr_t) dst % pb == 0 && dst_stride % pb == 0;   // (else the rows stay pixel by pixel)
+	*stride = row + (alike ? dst_stride & 15 : 0);
+	const size_t lead = alike ? ((uintptr_t) dst - (size_t) off_x * pb) & 15 : 0;
+	uint8_t *base = region_staging(h->dev, lead + *stride * (size_t) img_h + 16);
+	return base ? base + lead : nullptr;
+}
+
+// the group-major index of the varblock list, once per upload: three kernels and one copy back of the segments' starts
+static uint32_t region_index(j40hip_frame *h, hipStream_t s) {
+	j40hip_device_state *st = h->dev;
+	j40hip_device_state::Region &rg = st->region;
+	if (rg.index_ready) return 0;
+	const FrameHeader &fh = h->frame.fh;
+	const size_t nkeys = (size_t) fh.num_groups * REGION_KEYS;
+	bool ok = true;
+	if (!rg.d_order) {
+		rg.d_cursor = st->scratch<uint32_t>(nkeys, ok); rg.d_seg_start = st->scratch<uint32_t>(nkeys + 1, ok);
+		rg.d_index = st->scratch<uint32_t>(std::max<size_t>(st->vb_count, 1), ok); rg.d_order = st->scratch<uint32_t>((size_t) fh.num_groups, ok);
+		if (!ok) { rg.d_order = nullptr; return ERR_MEM; }
+	}
+	launch_region_index(st->d_vb_sorted, (uint32_t) st->vb_count, fh.group_size_shift, fh.gcolumns, (uint32_t) nkeys, rg.d_cursor, rg.d_seg_start, rg.d_index, s);
+	std::vector<uint32_t> starts(nkeys + 1);
+	if (hipMemcpyAsync(starts.data(), rg.d_seg_start, sizeof(uint32_t) * starts.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return ERR_GPU;
+	if (starts[nkeys] != (uint32_t) st->vb_count) return ERR_GPU;
+	rg.counts.resize(nkeys);
+	for (size_t k = 0; k < nkeys; ++k) rg.counts[k] = starts[k + 1] - starts[k];
+	rg.index_ready = true;
+	return 0;
+}
+
+// the cover's varblocks and groups into the region's lists; nothing to do when the last region had the same cover
+static uint32_t region_gather(j40hip_frame *h, const RegionCover &cover, hipStream_t s) {
+	j40hip_device_state *st = h->dev;
+	j40hip_device_state::Region &rg = st->region;
+	if (uint32_t e = region_index(h, s)) return e;
+	const RegionCover &g = rg.gathered;
+	if (g.cols == cover.cols && g.rows == cover.rows && g.gx0 == cover.gx0 && g.gy0 == cover.gy0) return 0;
+	// class_start from the host's count table: per class, the cover's groups summed
+	int32_t at = 0;
+	for (int d = 0; d < REGION_KEYS; ++d) {
+		rg.class_start[d] = at;
+		for (int32_t i = 0; i < region_cover_groups(cover); ++i) at += (int32_t) rg.counts[(size_t) region_cover_group(cover, i) * REGION_KEYS + (size_t) d];
+	}
+	const size_t total = (size_t) rg.class_start[REGION_KEYS - 1];   // (class 27 does not exist: the last entry is the end)
+	if (total > rg.list_capacity) {
+		bool ok = true;
+		const size_t want = std::min(st->vb_count, total + total / 2);
+		rg.gathered.cols = 0;
+		rg.d_list = st->scratch<DevVarblock>(want, ok);
+		if (!ok) { rg.d_list = nullptr; rg.list_capacity = 0; return ERR_MEM; }
+		rg.list_capacity = want;
+	}
+	launch_region_gather(st->d_vb_sorted, rg.d_index, rg.d_seg_start, cover, rg.class_start, rg.d_list, rg.d_order, s);
+	rg.gathered = cover;
+	return 0;
+}
+
+static uint32_t decode_region(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
+	j40hip_device_state *st = h->dev;
+	const Frame &fr = h->frame;
+	const int32_t x0 = h->region[0], y0 = h->region[1], w = h->region[2], hh = h->region[3];
+	const size_t pb = pixel_bytes(h);
+	if (stride_bytes < pb * (size_t) w) return ERR_RNGE;
+	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
+	if (st->is_modular) return decode_modular(h, rgba_dev, stride_bytes, s, ms3, h->region);
+	const int32_t W = fr.fh.width, H = fr.fh.height, shift = fr.fh.group_size_shift;
+	const RegionCover cover = region_cover(x0, y0, w, hh, shift, fr.fh.gcolumns);
+	const int32_t ncover = region_cover_groups(cover);
+	const int rmode = restoration_mode(h);
+	const bool widen = (rmode && (fr.fh.restoration.gab || fr.fh.restoration.epf_iters > 0)) || (st->has_trailers && j40hip_alpha_kept(h));
+	if (widen) {
+		// the filters read across groups, the kept alpha is merged into full-size pixels: the whole frame as ever, into a staging image
+		size_t img_stride = 0;
+		uint8_t *img = region_image(h, rgba_dev, stride_bytes, W, H, x0, &img_stride);
+		if (!img) return ERR_MEM;
+		h->region_widened = 1; h->region_sections = st->total_sections; h->region_varblocks = (int32_t) st->vb_count;
+		if (uint32_t e = decode_impl(h, img, img_stride, s, ms3, true)) return e;
+		launch_region_crop(img + (size_t) y0 * img_stride + (size_t) x0 * pb, img_stride, (uint8_t *) rgba_dev, stride_bytes, w, hh, (int32_t) pb, s);
+		return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+	}
+	const DevPlan &plan = st->plan;
+	const bool all = ncover == (int32_t) fr.fh.num_groups;   // (the whole frame's lists and launches serve; also every single-section frame)
+	if (!all) if (uint32_t e = region_gather(h, cover, s)) return e;
+	const DevVarblock *list = all ? st->d_vb_sorted : st->region.d_list;
+	const int32_t *class_start = all ? st->class_start : st->region.class_start;
+	// the cover in pixels, and where its image goes: straight into the caller's when the rectangle is its cover
+	const int32_t cx0 = cover.gx0 << shift, cy0 = cover.gy0 << shift;
+	const int32_t cw = (int32_t) std::min<int64_t>(W, (int64_t) (cover.gx0 + cover.cols) << shift) - cx0, ch = (int32_t) std::min<int64_t>(H, (int64_t) (cover.gy0 + cover.rows) << shift) - cy0;
+	const bool direct = x0 == cx0 && y0 == cy0 && w == cw && hh == ch;
+	size_t img_stride = stride_bytes;
+	uint8_t *img = direct ? (uint8_t *) rgba_dev : region_image(h, rgba_dev, stride_bytes, cw, ch, x0 - cx0, &img_stride);
+	if (!img) return ERR_MEM;
+	st->trailers_pending = false; h->alpha_written = false; st->restore_ran = 0; st->restore_err = 0;
+	h->region_widened = 0; h->region_sections = all ? st->total_sections : fr.fh.num_passes * ncover; h->region_varblocks = class_start[REGION_KEYS - 1];
+	if (ms3) (void) hipEventRecord(st->ev[0], s);
+	if (uint32_t e = clear_before_decode(st, s)) return e;
+	if (hipMemsetAsync(plan.status, 0, sizeof(uint32_t) * (size_t) st->total_sections, s) != hipSuccess) return ERR_GPU;
+	if (ms3) (void) hipEventRecord(st->ev[1], s);
+	// the cover's sections: through the fast kernel's order list, or a launch per row of the cover's groups (k_hf_entropy takes
+	// a run of groups and every pass of them)
+	if (all) launch_hf_entropy(plan, st->hf, 0, (int32_t) fr.fh.num_groups, s);
+	else if (hf_entropy_fast_path(plan, st->hf)) launch_hf_entropy_fast_ordered(plan, st->hf, st->region.d_order, 0, ncover, s);
+	else for (int32_t r = 0; r < cover.rows; ++r) launch_hf_entropy(plan, st->hf, (cover.gy0 + r) * cover.gcolumns + cover.gx0, cover.cols, s);
+	if (ms3) (void) hipEventRecord(st->ev[2], s);
+	launch_vardct_frame(plan, class_start, list, st->d_large_scratch, img, img_stride, s, out16(h));
+	if (!direct) launch_region_crop(img + (size_t) (y0 - cy0) * img_stride + (size_t) (x0 - cx0) * pb, img_stride, (uint8_t *) rgba_dev, stride_bytes, w, hh, (int32_t) pb, s);
+	if (ms3) {
+		(void) hipEventRecord(st->ev[3], s);
+		if (hipEventSynchronize(st->ev[3]) != hipSuccess) return ERR_GPU;
+		float a = 0, b = 0, c = 0;
+		(void) hipEventElapsedTime(&a, st->ev[0], st->ev[1]); (void) hipEventElapsedTime(&b, st->ev[1], st->ev[2]); (void) hipEventElapsedTime(&c, st->ev[2], st->ev[3]);
+		ms3[0] = b; ms3[1] = c; ms3[2] = a;
+	}
+	if (hipGetLastError() != hipSuccess) return ERR_GPU;
+	if (st->has_trailers && all) return validate_trailers(h, s);   // (drop mode; a partial cover does not validate the sub-images, like a group range)
 	return 0;
 }
 
@@ -1344,6 +1538,7 @@ static uint32_t batch_assign(j40hip_batch *b, j40hip_frame *const *frames, int64
 		j40hip_frame *h = frames[i];
 		if (h && h->frame.lf_only) return ERR_ULF;
 		if (!h || !h->dev) return ERR_GPU;
+		if (h->region_set) return ERR_URG;         // a batch writes whole frames
 		if (h->dev->is_modular) return ERR_TODO;   // Modular frames: decode them one by one
 		if (i == 0) b->device = h->dev->device;
 		else if (h->dev->device != b->device) return ERR_RNGE;
@@ -1702,17 +1897,18 @@ static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host
 static uint32_t j40hip_frame_decode_to_host_body(j40hip_frame *h, void *rgba_host, size_t stride_bytes) {
 	if (h && h->frame.lf_only) return ERR_ULF;
 	if (!h || !h->dev) return ERR_GPU;
-	if (stride_too_small(h, stride_bytes)) return ERR_RNGE;
+	const bool region = h->region_set;   // (only the rectangle's rows exist on either side, and they go the one-phase way)
+	if (region ? stride_bytes < pixel_bytes(h) * (size_t) h->region[2] : stride_too_small(h, stride_bytes)) return ERR_RNGE;
 	const Frame &fr = h->frame;
 	const int device = h->dev->device;
 	if (hipSetDevice(device) != hipSuccess) return ERR_GPU;
 	// the device image uses the caller's row stride, so one contiguous copy brings it back
-	const size_t bytes = stride_bytes * (size_t) fr.fh.height;
+	const size_t bytes = stride_bytes * (size_t) (region ? h->region[3] : fr.fh.height);
 	size_t got = 0; bool clean = false;
 	void *d = cache_acquire(device, bytes, &got, &clean);
 	if (!d) return ERR_GPU;
 	bool two_phase = false;
-	uint32_t err = decode_two_phase(h, (uint8_t *) d, (uint8_t *) rgba_host, stride_bytes, &two_phase);
+	uint32_t err = region ? 0 : decode_two_phase(h, (uint8_t *) d, (uint8_t *) rgba_host, stride_bytes, &two_phase);
 	if (two_phase && err != ERR_EVOF) {   // (the pixels are in rgba_host, or the frame has failed; "evof": the dense form below)
 		(void) hipDeviceSynchronize();
 		cache_release(device, d, got, false);
