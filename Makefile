@@ -37,7 +37,10 @@ build/obj/lf_decode.o: EXTRA_HIPFLAGS += -mllvm -amdgpu-sched-strategy=max-ilp
 build/libj40hip.so: $(HOST_OBJS) $(DEV_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -lpthread -lhsa-runtime64
 
-hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/liboracle_driver.so build/api_threads
+# the stand-alone layout programs (below) belong to hostsim wherever tests/hostsim holds their source; the libraries do not need it
+LAYOUTMAIN = $(if $(wildcard tests/hostsim/mod_layout_main.cpp),build/mod_layout_main build/mod_layout_main_san)
+HOSTSIM_HDR = $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp) $(wildcard tests/hostsim/*.hpp)
+hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN)
 # test-only glue: parses a stream with the product's host parser, takes the plan view and hands it to
 # the CPU oracle (oracle/libj40oracle.so)
 build/liboracle_driver.so: tests/oracle_driver.c build/libj40hip.so oracle/hotpath_oracle.c include/j40hip.h
@@ -51,18 +54,29 @@ build/api_threads: tests/api_threads.c include/j40.h build/libj40hip.so
 # device functions compiled for the CPU, test infrastructure only (tests/hostsim)
 HOSTSIM_SRC = tests/hostsim/hostsim.cpp $(SRC)/plan_build.cpp $(SRC)/plan_front.cpp $(SRC)/entropy.cpp $(SRC)/modular.cpp $(SRC)/tables.cpp $(SRC)/frame.cpp
 HOSTSIM_FLAGS = -std=c++17 -O2 -fPIC -shared -ffp-contract=off -Wall -Wextra -Wno-unused-function -Wno-unknown-pragmas
-build/libhostsim.so: $(HOSTSIM_SRC) $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp)
+build/libhostsim.so: $(HOSTSIM_SRC) $(HOSTSIM_HDR)
 	@mkdir -p build
 	$(CXX) $(HOSTSIM_FLAGS) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -o $@ $(HOSTSIM_SRC) -lpthread
-build/libhostsim_ring8.so: $(HOSTSIM_SRC) $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp)
+build/libhostsim_ring8.so: $(HOSTSIM_SRC) $(HOSTSIM_HDR)
 	@mkdir -p build
 	$(CXX) $(HOSTSIM_FLAGS) -DJ40_LANE_EV_FLUSH=8 -o $@ $(HOSTSIM_SRC) -lpthread
 
 # the kept alpha channel of VarDCT frames on the CPU (tests/test_alpha.py): entropy decode, keep-mode trailer plan, device/alpha_dev.h's merge
 ALPHASIM_SRC = tests/hostsim/alpha_sim.cpp $(SRC)/plan_build.cpp $(SRC)/plan_front.cpp $(SRC)/entropy.cpp $(SRC)/modular.cpp $(SRC)/tables.cpp $(SRC)/frame.cpp
-build/libhostsim_alpha.so: $(ALPHASIM_SRC) $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp) include/j40hip.h
+build/libhostsim_alpha.so: $(ALPHASIM_SRC) $(HOSTSIM_HDR) include/j40hip.h
 	@mkdir -p build
 	$(CXX) $(HOSTSIM_FLAGS) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -o $@ $(ALPHASIM_SRC) -lpthread
+
+# the Modular plan's layout (mod_layout.hpp) checked on the CPU (tests/test_mod_layout.py): the decodes of hostsim.cpp and alpha_sim.cpp as a
+# program of its own, plain and with the host sanitizers (an executable: never loaded into Python)
+LAYOUTMAIN_SRC = tests/hostsim/mod_layout_main.cpp tests/hostsim/alpha_sim.cpp $(HOSTSIM_SRC)
+LAYOUTMAIN_FLAGS = $(filter-out -fPIC -shared,$(HOSTSIM_FLAGS)) -DJ40_LANE_EV_FLUSH=$(EVENT_RING)
+build/mod_layout_main: $(LAYOUTMAIN_SRC) $(HOSTSIM_HDR) include/j40hip.h
+	@mkdir -p build
+	$(CXX) $(LAYOUTMAIN_FLAGS) -o $@ $(LAYOUTMAIN_SRC) -lpthread
+build/mod_layout_main_san: $(LAYOUTMAIN_SRC) $(HOSTSIM_HDR) include/j40hip.h
+	@mkdir -p build
+	$(CXX) $(LAYOUTMAIN_FLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(LAYOUTMAIN_SRC) -lpthread
 
 # region decode on the CPU (tests/test_region.py): device/region_dev.h's index, gather and crop functions over the host plan's varblock list
 REGIONSIM_SRC = tests/hostsim/region_sim.cpp $(SRC)/plan_build.cpp $(SRC)/plan_front.cpp $(SRC)/entropy.cpp $(SRC)/modular.cpp $(SRC)/tables.cpp $(SRC)/frame.cpp

@@ -15,6 +15,7 @@
 #include "../capi.hpp"
 #include "../tables.hpp"
 #include "../plan_build.hpp"
+#include "../mod_layout.hpp"
 #include "kernels.h"
 #include "runtime_shared.hpp"
 #include "hostcopy.hpp"
@@ -457,49 +458,25 @@ static uint32_t upload_modular(j40hip_frame *h, int device) {
 	st->first_group = 0; st->num_groups = h->frame.fh.num_groups;   // (j40hip_frame_set_group_range narrows it)
 	hipStream_t s = nullptr;
 	bool ok = true;
-	DevModPlan &plan = st->mod;
-	memset(&plan, 0, sizeof plan);
-	plan.frame = st->upload(&hp.frame, 1, s, ok);
-	plan.codestream = st->upload(hp.codestream.data(), hp.codestream.size(), s, ok);
-	plan.pool_u8 = st->upload(hp.pool_u8.data(), hp.pool_u8.size(), s, ok);
-	plan.pool_i32 = st->upload(hp.pool_i32.data(), hp.pool_i32.size(), s, ok);
-	plan.pool_u64 = st->upload(hp.pool_u64.data(), hp.pool_u64.size(), s, ok);
-	plan.clusters = st->upload(hp.clusters.data(), hp.clusters.size(), s, ok);
-	plan.spec = st->upload(hp.specs.data(), hp.specs.size(), s, ok);
-	plan.tree = st->upload(hp.tree.data(), hp.tree.size(), s, ok);
-	plan.sections = st->upload(hp.sections.data(), hp.sections.size(), s, ok);
-	if (!hp.coop_trees.empty()) plan.coop_trees = st->upload(hp.coop_trees.data(), hp.coop_trees.size(), s, ok);
+	// the plan's tables, the coded channels' planes, the sub-images' planes and the scratch: one allocation, laid out by ModPlanLayout
+	// (a squeezed 16384 x 16384 frame has 70+ planes); the codestream beside it
+	const ModPlanLayout lay(hp, 0);
+	uint8_t *base = st->scratch<uint8_t>(lay.total_bytes, ok);
+	if (!ok) { j40hip_release_device(h); return ERR_GPU; }
+	std::vector<uint8_t> staging(lay.upload_bytes);   // (lives until the stream is synchronised below)
+	lay.stage(hp, staging.data(), base);
+	if (hipMemcpyAsync(base, staging.data(), lay.upload_bytes, hipMemcpyHostToDevice, s) != hipSuccess) ok = false;
+	const DevModPlan &plan = st->mod = lay.bind(base, st->upload(hp.codestream.data(), hp.codestream.size(), s, ok));
 	st->mod_local_rcts = !hp.local_rct.empty();
-	if (st->mod_local_rcts) plan.local_rct = st->upload(hp.local_rct.data(), hp.local_rct.size(), s, ok);
 	st->mod_sections = (int32_t) hp.sections.size(); st->mod_passes = hp.num_passes; st->mod_sections_per_pass = hp.sections_per_pass;
-	st->mod_info = {hp.max_tree_nodes, hp.max_num_dist, hp.max_clusters, hp.max_table_bytes, hp.frame.max_width, hp.any_wp ? 1 : 0, hp.coop_width, hp.coop_sections + hp.split_sections == (int32_t) hp.sections.size(), hp.quad_sections, hp.quad_spec, hp.quad_width, hp.coop_sections, hp.quad_sections ? hp.specs[(size_t) hp.quad_spec].table_span : 0u, hp.split_sections, hp.split_width, hp.split_channels};
+	st->mod_info = mod_launch_info(hp);
 	for (const DevModSection &sec : hp.sections) st->mod_section_offsets.push_back(sec.byte_off);
-	const int32_t nch = hp.frame.num_channels;
 	struct Ref { int16_t *p; int32_t w, h; };
 	std::vector<Ref> planes;
-	{
-		// the coded channels: one allocation, each plane at a 256-byte aligned offset (a squeezed 16384 x 16384 frame has 70+ of them)
-		std::vector<size_t> at((size_t) nch); size_t total = 0;
-		for (int32_t c = 0; c < nch; ++c) { at[(size_t) c] = total; total += ((size_t) std::max(hp.plane_w[(size_t) c], 0) * (size_t) std::max(hp.plane_h[(size_t) c], 0) * 2 + 2 + 255) & ~(size_t) 255; }
-		uint8_t *blockp = (uint8_t *) st->scratch<uint8_t>(total ? total : 256, ok);
-		std::vector<DevPlaneRef> refs((size_t) nch);
-		for (int32_t c = 0; c < nch; ++c) {
-			int16_t *p = blockp ? (int16_t *) (blockp + at[(size_t) c]) : nullptr;
-			refs[(size_t) c] = DevPlaneRef{p, hp.plane_w[(size_t) c], hp.plane_h[(size_t) c], hp.plane_meta[(size_t) c], 0};
-			planes.push_back({p, hp.plane_w[(size_t) c], hp.plane_h[(size_t) c]});
-		}
-		plan.planes = st->upload(refs.data(), refs.size(), s, ok);
-		if (!hp.chan_rects.empty()) plan.chan_rects = st->upload(hp.chan_rects.data(), hp.chan_rects.size(), s, ok);
-	}
+	for (size_t c = 0; c < lay.num_planes; ++c) planes.push_back({lay.plane(base, c), hp.plane_w[c], hp.plane_h[c]});
 	bool palette_wp = false;
 	for (const Transform &t : hp.transforms) palette_wp |= t.kind == Transform::PALETTE && t.nb_deltas > 0 && t.d_pred == 6;
-	if (hp.frame.tree_uses_wp) plan.wp_scratch = st->scratch<int32_t>((size_t) hp.sections.size() * (size_t) (2 * hp.frame.max_width * 5) + 16, ok);
 	if (palette_wp) st->pal_wp_scratch = st->scratch<int32_t>((size_t) 2 * (size_t) hp.frame.width * 5 + 16, ok);
-	plan.lz_window_size = hp.lz_window_size;
-	if (hp.lz_window_size) plan.lz_window = st->scratch<int32_t>((size_t) hp.sections.size() * hp.lz_window_size, ok);
-	plan.status = st->scratch<uint32_t>(hp.sections.size() + 1, ok);
-	// sections decoded in two passes (modular_split.hip): their residual tokens -- also their LZ77 windows -- and the passes' notes
-	if (hp.split_sections) { plan.residuals = st->scratch<int32_t>(hp.split_samples + 64, ok); plan.split_state = st->scratch<uint32_t>(3 * hp.sections.size() + 4, ok); }
 	st->mod_extra_status = const_cast<uint32_t *>(plan.status) + hp.sections.size();
 	st->total_sections = (int32_t) hp.sections.size();
 
@@ -563,19 +540,13 @@ static uint32_t upload_modular(j40hip_frame *h, int device) {
 		for (size_t k = ops_before; k < ops.size(); ++k) ops[k].group = group;
 	};
 	if (!hp.sub_images.empty()) {
-		std::vector<DevSubPlane> subp(hp.sub_w.size());
 		int32_t widest = hp.frame.width;
-		for (size_t k = 0; k < subp.size(); ++k) {
-			const size_t n = (size_t) hp.sub_w[k] * (size_t) hp.sub_h[k];
-			subp[k] = DevSubPlane{st->scratch<int16_t>(n ? n : 1, ok), hp.sub_w[k], hp.sub_h[k], hp.sub_meta[k], 0};
-			widest = std::max(widest, hp.sub_w[k]);
-		}
-		plan.sub_planes = st->upload(subp.data(), subp.size(), s, ok);
+		for (size_t k = 0; k < lay.num_subs; ++k) widest = std::max(widest, hp.sub_w[k]);
 		for (const HostModPlan::SubImage &si : hp.sub_images) {
 			if (!si.paste) continue;
 			for (const Transform &t : si.transforms) palette_wp |= t.kind == Transform::PALETTE && t.nb_deltas > 0 && t.d_pred == 6;
 			std::vector<Ref> sp;
-			for (int32_t k = 0; k < si.num_planes; ++k) sp.push_back({subp[(size_t) (si.first_plane + k)].ptr, subp[(size_t) (si.first_plane + k)].w, subp[(size_t) (si.first_plane + k)].h});
+			for (size_t k = (size_t) si.first_plane; k < (size_t) (si.first_plane + si.num_planes); ++k) sp.push_back({lay.sub_plane(base, k), hp.sub_w[k], hp.sub_h[k]});
 			// (sections: LfGlobal's first, then passes x groups)
 			const int32_t lead_sections = (int32_t) hp.sections.size() - hp.sections_per_pass * hp.num_passes;
 			const int32_t sub_group = si.section >= lead_sections && hp.sections_per_pass > 0 ? (si.section - lead_sections) % hp.sections_per_pass : -1;
@@ -1072,47 +1043,31 @@ static uint32_t validate_trailers(j40hip_frame *h, hipStream_t s) {
 	std::vector<std::pair<int32_t, uint32_t>> header_errors;
 	std::vector<int32_t> section_of;
 	if (uint32_t e = build_trailer_plan(fr, h->cs, h->cs_size, end_bits.data(), status.data(), &hp, &header_errors, &section_of)) return e;
-	j40hip_device_state tmp;   // owns the buffers of this validation only
-	tmp.device = st->device;
 	bool ok = true;
 	std::vector<uint32_t> found(hp.sections.size(), 0);
 	if (!hp.sections.empty()) {
-		DevModPlan plan;
-		memset(&plan, 0, sizeof plan);
-		plan.frame = tmp.upload(&hp.frame, 1, s, ok);
-		plan.codestream = st->plan.codestream;
-		plan.pool_u8 = tmp.upload(hp.pool_u8.data(), hp.pool_u8.size(), s, ok);
-		plan.pool_i32 = tmp.upload(hp.pool_i32.data(), hp.pool_i32.size(), s, ok);
-		plan.pool_u64 = tmp.upload(hp.pool_u64.data(), hp.pool_u64.size(), s, ok);
-		plan.clusters = tmp.upload(hp.clusters.data(), hp.clusters.size(), s, ok);
-		plan.spec = tmp.upload(hp.specs.data(), hp.specs.size(), s, ok);
-		plan.tree = tmp.upload(hp.tree.data(), hp.tree.size(), s, ok);
-		plan.sections = tmp.upload(hp.sections.data(), hp.sections.size(), s, ok);
-		if (!hp.coop_trees.empty()) plan.coop_trees = tmp.upload(hp.coop_trees.data(), hp.coop_trees.size(), s, ok);
-		std::vector<DevSubPlane> subp(hp.sub_w.size());
-		size_t total = 0;
-		for (size_t k = 0; k < subp.size(); ++k) total += (size_t) hp.sub_w[k] * (size_t) hp.sub_h[k] + 1;
-		int16_t *pool = tmp.scratch<int16_t>(total + 1, ok);
-		for (size_t k = 0, at = 0; k < subp.size() && pool; ++k) { subp[k] = DevSubPlane{pool + at, hp.sub_w[k], hp.sub_h[k], hp.sub_meta[k], 0}; at += (size_t) hp.sub_w[k] * (size_t) hp.sub_h[k] + 1; }
-		plan.sub_planes = tmp.upload(subp.data(), subp.size(), s, ok);
-		if (hp.frame.tree_uses_wp) plan.wp_scratch = tmp.scratch<int32_t>(hp.sections.size() * (size_t) (2 * hp.frame.max_width * 5) + 16, ok);
-		plan.lz_window_size = hp.lz_window_size;
-		if (hp.lz_window_size) plan.lz_window = tmp.scratch<int32_t>(hp.sections.size() * hp.lz_window_size, ok);
-		plan.status = tmp.scratch<uint32_t>(hp.sections.size() + 1, ok);
-		if (hp.split_sections) { plan.residuals = tmp.scratch<int32_t>(hp.split_samples + 64, ok); plan.split_state = tmp.scratch<uint32_t>(3 * hp.sections.size() + 4, ok); }
+		// one block of the device memory cache, given back once the stream has been synchronised
+		const ModPlanLayout lay(hp, 0);
+		size_t block_bytes = 0; bool clean = false;
+		uint8_t *base = (uint8_t *) cache_acquire(st->device, lay.total_bytes, &block_bytes, &clean);
+		if (!base) return ERR_GPU;
+		std::vector<uint8_t> staging(lay.upload_bytes);
+		lay.stage(hp, staging.data(), base);
+		const DevModPlan plan = lay.bind(base, st->plan.codestream);
+		ok = hipMemcpyAsync(base, staging.data(), lay.upload_bytes, hipMemcpyHostToDevice, s) == hipSuccess
+			&& hipMemsetAsync(plan.status, 0, sizeof(uint32_t) * (found.size() + 1), s) == hipSuccess;   // (recycled memory, as in decode_modular and keep_alpha)
 		if (ok) {
-			const ModLaunchInfo info = {hp.max_tree_nodes, hp.max_num_dist, hp.max_clusters, hp.max_table_bytes, hp.frame.max_width, hp.any_wp ? 1 : 0, hp.coop_width, hp.coop_sections + hp.split_sections == (int32_t) hp.sections.size(), hp.quad_sections, hp.quad_spec, hp.quad_width, hp.coop_sections, hp.quad_sections ? hp.specs[(size_t) hp.quad_spec].table_span : 0u, hp.split_sections, hp.split_width, hp.split_channels};
-			launch_modular_sections(plan, 0, (int32_t) hp.sections.size(), info, s);
-			ok = hipMemcpyAsync(found.data(), plan.status, sizeof(uint32_t) * found.size(), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+			launch_modular_sections(plan, 0, (int32_t) hp.sections.size(), mod_launch_info(hp), s);
+			ok = hipMemcpyAsync(found.data(), plan.status, sizeof(uint32_t) * found.size(), hipMemcpyDeviceToHost, s) == hipSuccess;
 		}
+		if (hipStreamSynchronize(s) != hipSuccess) ok = false;
+		cache_release(st->device, base, block_bytes, false);
 	}
 	bool any = false;
 	for (size_t i = 0; i < found.size(); ++i) if (found[i]) { status[(size_t) section_of[i]] = found[i]; any = true; }
 	for (const auto &e : header_errors) { status[(size_t) e.first] = e.second; any = true; }
 	if (ok && any) ok = hipMemcpyAsync(st->plan.status, status.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
 	else if (ok) ok = hipStreamSynchronize(s) == hipSuccess;
-	for (auto &b : tmp.buffers) b.release();
-	tmp.buffers.clear();
 	return ok ? 0 : ERR_GPU;
 }
 
@@ -1146,49 +1101,19 @@ static uint32_t keep_alpha(j40hip_frame *h, void *rgba_dev, size_t stride_bytes,
 			if (e == (uint32_t) ERR_TODO && h->alpha < 0) { *fallback = true; return 0; }
 			return e;
 		}
-		// one block: what is uploaded first, the planes and the scratch behind it
-		size_t at = 0;
-		auto place = [&](size_t bytes) { const size_t off = at; at = (at + bytes + 255) & ~(size_t) 255; return off; };
-		const size_t plane_samples = ((size_t) fr.fh.width * (size_t) fr.fh.height + 7) & ~(size_t) 7, nplanes = hp.plane_w.size(), nsec = hp.sections.size();
-		const size_t o_frame = place(sizeof(DevModFrame)), o_u8 = place(hp.pool_u8.size()), o_i32 = place(4 * hp.pool_i32.size()), o_u64 = place(8 * hp.pool_u64.size());
-		const size_t o_clusters = place(sizeof(hp.clusters[0]) * hp.clusters.size()), o_spec = place(sizeof(hp.specs[0]) * hp.specs.size()), o_tree = place(sizeof(hp.tree[0]) * hp.tree.size());
-		const size_t o_sections = place(sizeof(DevModSection) * nsec), o_coop = place(sizeof(DevCoopTree) * hp.coop_trees.size()), o_rct = place(4 * hp.local_rct.size()), o_refs = place(sizeof(DevPlaneRef) * nplanes);
-		const size_t upload_bytes = at;
-		const size_t o_planes = place(2 * plane_samples * nplanes);
-		const size_t o_wp = place(hp.frame.tree_uses_wp ? 4 * (nsec * (size_t) (2 * hp.frame.max_width * 5) + 16) : 0);
-		const size_t o_lz = place(hp.lz_window_size ? 4 * nsec * (size_t) hp.lz_window_size : 0);
-		const size_t o_status = place(4 * (nsec + 1));
-		const size_t o_res = place(hp.split_sections ? 4 * (hp.split_samples + 64) : 0), o_split = place(hp.split_sections ? 4 * (3 * nsec + 4) : 0);
-		if (ak.block && ak.block_bytes < at) { (void) hipDeviceSynchronize(); cache_release(st->device, ak.block, ak.block_bytes, false); ak.block = nullptr; }
-		if (!ak.block) { bool clean = false; ak.block = cache_acquire(st->device, at, &ak.block_bytes, &clean); }
+		// one block (ModPlanLayout): what is uploaded first, the frame-wide planes and the scratch behind it
+		const ModPlanLayout lay(hp, 0);
+		if (ak.block && ak.block_bytes < lay.total_bytes) { (void) hipDeviceSynchronize(); cache_release(st->device, ak.block, ak.block_bytes, false); ak.block = nullptr; }
+		if (!ak.block) { bool clean = false; ak.block = cache_acquire(st->device, lay.total_bytes, &ak.block_bytes, &clean); }
 		if (!ak.block) return ERR_MEM;
 		uint8_t *base = (uint8_t *) ak.block;
-		std::vector<DevPlaneRef> refs(nplanes);
-		for (size_t k = 0; k < nplanes; ++k) refs[k] = DevPlaneRef{(int16_t *) (base + o_planes) + k * plane_samples, hp.plane_w[k], hp.plane_h[k], 0, 0};
-		ak.staging.assign(upload_bytes, 0);
-		auto stage = [&](size_t off, const void *src, size_t bytes) { if (bytes) memcpy(ak.staging.data() + off, src, bytes); };
-		stage(o_frame, &hp.frame, sizeof(DevModFrame)); stage(o_u8, hp.pool_u8.data(), hp.pool_u8.size()); stage(o_i32, hp.pool_i32.data(), 4 * hp.pool_i32.size()); stage(o_u64, hp.pool_u64.data(), 8 * hp.pool_u64.size());
-		stage(o_clusters, hp.clusters.data(), sizeof(hp.clusters[0]) * hp.clusters.size()); stage(o_spec, hp.specs.data(), sizeof(hp.specs[0]) * hp.specs.size()); stage(o_tree, hp.tree.data(), sizeof(hp.tree[0]) * hp.tree.size());
-		stage(o_sections, hp.sections.data(), sizeof(DevModSection) * nsec); stage(o_coop, hp.coop_trees.data(), sizeof(DevCoopTree) * hp.coop_trees.size()); stage(o_rct, hp.local_rct.data(), 4 * hp.local_rct.size());
-		stage(o_refs, refs.data(), sizeof(DevPlaneRef) * nplanes);
-		if (hipMemcpyAsync(base, ak.staging.data(), upload_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return ERR_GPU;
-		DevModPlan &plan = ak.plan;
-		memset(&plan, 0, sizeof plan);
-		plan.frame = (const DevModFrame *) (base + o_frame); plan.codestream = st->plan.codestream;
-		plan.pool_u8 = base + o_u8; plan.pool_i32 = (const int32_t *) (base + o_i32); plan.pool_u64 = (const uint64_t *) (base + o_u64);
-		plan.clusters = (const DevCluster *) (base + o_clusters); plan.spec = (const DevCodeSpec *) (base + o_spec); plan.tree = (const DevTreeNode *) (base + o_tree);
-		plan.sections = (const DevModSection *) (base + o_sections);
-		if (!hp.coop_trees.empty()) plan.coop_trees = (const DevCoopTree *) (base + o_coop);
-		if (!hp.local_rct.empty()) plan.local_rct = (const int32_t *) (base + o_rct);
-		plan.planes = (const DevPlaneRef *) (base + o_refs);
-		if (hp.frame.tree_uses_wp) plan.wp_scratch = (int32_t *) (base + o_wp);
-		plan.lz_window_size = hp.lz_window_size;
-		if (hp.lz_window_size) plan.lz_window = (int32_t *) (base + o_lz);
-		plan.status = (uint32_t *) (base + o_status);
-		if (hp.split_sections) { plan.residuals = (int32_t *) (base + o_res); plan.split_state = (uint32_t *) (base + o_split); }
-		ak.info = ModLaunchInfo{hp.max_tree_nodes, hp.max_num_dist, hp.max_clusters, hp.max_table_bytes, hp.frame.max_width, hp.any_wp ? 1 : 0, hp.coop_width, hp.coop_sections + hp.split_sections == (int32_t) hp.sections.size(), hp.quad_sections, hp.quad_spec, hp.quad_width, hp.coop_sections, hp.quad_sections ? hp.specs[(size_t) hp.quad_spec].table_span : 0u, hp.split_sections, hp.split_width, hp.split_channels};
-		ak.num_sections = (int32_t) nsec; ak.local_rcts = !hp.local_rct.empty();
-		ak.alpha_plane = refs[(size_t) alpha_index].ptr;
+		ak.staging.assign(lay.upload_bytes, 0);
+		lay.stage(hp, ak.staging.data(), base);
+		if (hipMemcpyAsync(base, ak.staging.data(), lay.upload_bytes, hipMemcpyHostToDevice, s) != hipSuccess) return ERR_GPU;
+		ak.plan = lay.bind(base, st->plan.codestream);
+		ak.info = mod_launch_info(hp);
+		ak.num_sections = (int32_t) hp.sections.size(); ak.local_rcts = !hp.local_rct.empty();
+		ak.alpha_plane = lay.plane(base, (size_t) alpha_index);
 		ak.first_group = st->first_group; ak.num_groups = st->num_groups;
 		ak.ready = true;
 	} else if (hipMemcpyAsync(status.data(), st->plan.status, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s) != hipSuccess) return ERR_GPU;

@@ -13,6 +13,7 @@
 #include "../../j40_amd/csrc/device/modular_dev.h"
 #include "../../j40_amd/csrc/device/alpha_dev.h"
 #include "../../include/j40hip.h"
+#include "mod_block.hpp"
 
 using namespace j40hip;
 
@@ -25,12 +26,17 @@ ALPHA_SIM_API uint32_t alpha_sim_scale(int32_t p, int32_t bpp, int32_t fmt) {
 	return out16 ? alpha_value<true>(p, s) : alpha_value<false>(p, s);
 }
 
+// the Modular block of the last alpha_sim_decode (mod_block.hpp): guard bytes that no longer read 0x5a; the bytes of the regions called `name`
+ALPHA_SIM_API int64_t alpha_sim_guard_damage(void) { return (int64_t) g_guard_damage; }
+ALPHA_SIM_API int64_t alpha_sim_region_bytes(const char *name) { return mod_block_region_bytes(name); }
+
 // Merges the stream's alpha channel over the caller's pixels (width x height of format `fmt`, `stride` bytes a row; R, G, B are
 // left as they are). Returns 0, the stream's error code, "Ual?" / "TODO" as j40hip_frame_set_alpha(f, 1) would.
 ALPHA_SIM_API uint32_t alpha_sim_decode(const uint8_t *buf, size_t size, uint8_t *rgba, size_t stride, int32_t fmt) {
 	Frame fr;
 	const uint8_t *cs; size_t cs_size; std::vector<uint8_t> storage;
 	HostPlan hp;
+	mod_block_reset();
 	try {
 		extract_codestream(buf, size, &cs, &cs_size, &storage);
 		parse_frame(cs, cs_size, &fr, 1);
@@ -69,18 +75,8 @@ ALPHA_SIM_API uint32_t alpha_sim_decode(const uint8_t *buf, size_t size, uint8_t
 	std::vector<int32_t> section_of;
 	if (uint32_t e = build_trailer_plan(fr, hp.codestream.data(), hp.codestream.size() - 16, end_bits.data(), status.data(), &tp, &header_errors, &section_of, true)) return e;
 	const int32_t W = fr.fh.width, H = fr.fh.height;
-	std::vector<std::vector<int16_t>> store(tp.plane_w.size());
-	std::vector<DevPlaneRef> planes(tp.plane_w.size());
-	for (size_t k = 0; k < planes.size(); ++k) { store[k].assign((size_t) W * (size_t) H + 4, 0); planes[k] = DevPlaneRef{store[k].data(), W, H, 0, 0}; }
-	DevModPlan mp;
-	memset(&mp, 0, sizeof mp);
-	mp.frame = &tp.frame; mp.codestream = hp.codestream.data(); mp.pool_u8 = tp.pool_u8.data(); mp.pool_i32 = tp.pool_i32.data(); mp.pool_u64 = tp.pool_u64.data();
-	mp.clusters = tp.clusters.data(); mp.spec = tp.specs.data(); mp.tree = tp.tree.data(); mp.sections = tp.sections.data();
-	mp.planes = planes.data(); mp.local_rct = tp.local_rct.data();
-	std::vector<int32_t> wps(tp.sections.size() * (size_t) (2 * tp.frame.max_width * 5) + 16), win(tp.lz_window_size ? tp.sections.size() * tp.lz_window_size : 0);
-	std::vector<uint32_t> tstatus(tp.sections.size() + 1, 0);
-	mp.wp_scratch = tp.frame.tree_uses_wp ? wps.data() : nullptr;
-	mp.lz_window = win.empty() ? nullptr : win.data(); mp.lz_window_size = tp.lz_window_size; mp.status = tstatus.data();
+	ModBlock blk(tp, hp.codestream.data());   // the block runtime.hip's keep_alpha lays out
+	const DevModPlan &mp = blk.plan;
 	for (int32_t i = 0; i < tp.frame.num_sections; ++i) {
 		const ModTables mt = mod_tables_in_hbm(mp, i);
 		if (const uint32_t e = decode_modular_section<false, false>(mp, mt, i)) status[(size_t) section_of[(size_t) i]] = e;
@@ -94,7 +90,7 @@ ALPHA_SIM_API uint32_t alpha_sim_decode(const uint8_t *buf, size_t size, uint8_t
 	}
 	const bool out16 = fmt == J40HIP_U16X4;
 	const AlphaScale s = alpha_scale_make(fr.im.bpp, out16);
-	const int16_t *alpha = store[(size_t) index].data();
+	const int16_t *alpha = blk.lay.plane(blk.base, (size_t) index);
 	for (int32_t y = 0; y < H; ++y) {
 		if (out16) alpha_merge_row<true>(rgba + (size_t) y * stride, alpha + (size_t) y * (size_t) W, W, s);
 		else alpha_merge_row<false>(rgba + (size_t) y * stride, alpha + (size_t) y * (size_t) W, W, s);

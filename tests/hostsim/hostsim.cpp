@@ -18,6 +18,7 @@
 #include "../../j40_amd/csrc/device/k2_iter_dev.h"
 #include "../../j40_amd/csrc/device/modular_dev.h"
 #include "../../j40_amd/csrc/device/squeeze_dev.h"
+#include "mod_block.hpp"
 
 using namespace j40hip;
 
@@ -91,29 +92,12 @@ static int32_t g_neighbour_flip = 0;
 static uint32_t hostsim_decode_modular(const Frame &fr, const uint8_t *cs, size_t cs_size, uint8_t *rgba) {
 	HostModPlan hp;
 	if (uint32_t e = build_modular_plan(fr, cs, cs_size, &hp)) return e;
-	const int32_t nch = hp.frame.num_channels;
-	std::vector<std::vector<int16_t>> store((size_t) nch);
-	DevModPlan plan;
-	memset(&plan, 0, sizeof plan);
-	plan.frame = &hp.frame; plan.codestream = hp.codestream.data(); plan.pool_u8 = hp.pool_u8.data(); plan.pool_i32 = hp.pool_i32.data(); plan.pool_u64 = hp.pool_u64.data();
-	plan.clusters = hp.clusters.data(); plan.spec = hp.specs.data(); plan.tree = hp.tree.data(); plan.sections = hp.sections.data();
+	ModBlock blk(hp, hp.codestream.data());   // the block runtime.hip's upload_modular lays out
+	const DevModPlan &plan = blk.plan;
+	uint32_t *status = plan.status;   // [num_sections + 1]
 	struct Ref { int16_t *p; int32_t w, h; };
 	std::vector<Ref> planes;
-	std::vector<DevPlaneRef> refs((size_t) nch);
-	for (int32_t c = 0; c < nch; ++c) {
-		store[(size_t) c].assign((size_t) std::max(hp.plane_w[(size_t) c], 0) * (size_t) std::max(hp.plane_h[(size_t) c], 0) + 1, 0);
-		refs[(size_t) c] = DevPlaneRef{store[(size_t) c].data(), hp.plane_w[(size_t) c], hp.plane_h[(size_t) c], hp.plane_meta[(size_t) c], 0};
-		planes.push_back({refs[(size_t) c].ptr, refs[(size_t) c].w, refs[(size_t) c].h});
-	}
-	plan.planes = refs.data(); plan.chan_rects = hp.chan_rects.data();
-	std::vector<std::vector<int16_t>> sub_store(hp.sub_w.size());
-	std::vector<DevSubPlane> subp(hp.sub_w.size());
-	for (size_t k = 0; k < hp.sub_w.size(); ++k) { sub_store[k].assign((size_t) hp.sub_w[k] * (size_t) hp.sub_h[k] + 1, 0); subp[k] = DevSubPlane{sub_store[k].data(), hp.sub_w[k], hp.sub_h[k], hp.sub_meta[k], 0}; }
-	plan.sub_planes = subp.data();
-	std::vector<int32_t> wps((size_t) hp.sections.size() * (size_t) (2 * hp.frame.max_width * 5) + 16), window(hp.lz_window_size ? (size_t) hp.sections.size() * hp.lz_window_size : 0, 0x5a5a5a5a);   // (device memory is not zeroed: what a copy reads before the first integer must come from the decoder's rule, not from here)
-	std::vector<uint32_t> status(hp.sections.size() + 1, 0);
-	plan.wp_scratch = hp.frame.tree_uses_wp ? wps.data() : nullptr;
-	plan.lz_window = window.empty() ? nullptr : window.data(); plan.lz_window_size = hp.lz_window_size; plan.status = status.data();
+	for (size_t c = 0; c < blk.lay.num_planes; ++c) planes.push_back({blk.lay.plane(blk.base, c), hp.plane_w[c], hp.plane_h[c]});
 	std::vector<int32_t> ring(3 * ((size_t) hp.frame.max_width + 4) + 8, 0x7fff0000), wperr(10 * (size_t) hp.frame.max_width + 8);
 	// a group range (hostsim_set_group_range, mirrors j40hip_frame_set_group_range for Modular frames): LfGlobal's section and the
 	// range's groups of every pass are decoded, and only the range's rectangles are written
@@ -135,9 +119,8 @@ static uint32_t hostsim_decode_modular(const Frame &fr, const uint8_t *cs, size_
 		uint32_t first = 0, first_off = 0xffffffffu;
 		for (size_t i = 0; i < hp.sections.size(); ++i) if (status[i] && hp.sections[i].byte_off < first_off) { first = status[i]; first_off = hp.sections[i].byte_off; }
 		if (first) return first;
-		if (status.back()) return status.back();
+		if (status[hp.sections.size()]) return status[hp.sections.size()];
 	}
-	plan.local_rct = hp.local_rct.data();
 	for (int32_t sct = 0; sct < hp.frame.num_sections; ++sct) if (in_range(sct)) for (int32_t lane = 0; lane < 3; ++lane) section_inverse_rcts(plan, sct, lane, 3);
 	static const uint8_t PERM[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {1, 0, 2}, {2, 1, 0}};
 	std::vector<std::vector<int16_t>> extra;
@@ -205,7 +188,7 @@ static uint32_t hostsim_decode_modular(const Frame &fr, const uint8_t *cs, size_
 	// sections with a palette of their own: their sub-image's transforms, then the paste over the section's rectangle (j40.h:7030-7032)
 	for (const HostModPlan::SubImage &si : hp.sub_images) if (si.paste) {
 		std::vector<Ref> sp;
-		for (int32_t k = 0; k < si.num_planes; ++k) sp.push_back({subp[(size_t) (si.first_plane + k)].ptr, hp.sub_w[(size_t) (si.first_plane + k)], hp.sub_h[(size_t) (si.first_plane + k)]});
+		for (int32_t k = 0; k < si.num_planes; ++k) sp.push_back({blk.lay.sub_plane(blk.base, (size_t) (si.first_plane + k)), hp.sub_w[(size_t) (si.first_plane + k)], hp.sub_h[(size_t) (si.first_plane + k)]});
 		if (uint32_t e = undo(sp, si.transforms, si.wp)) return e;
 		const DevModSection &sec = hp.sections[(size_t) si.section];
 		for (size_t c = 0; c < sp.size(); ++c) {
@@ -249,10 +232,15 @@ static uint32_t hostsim_decode_once(const uint8_t *buf, size_t size, uint8_t *rg
 // events only; the runtime's second attempt goes through the general kernel, so does this one.
 extern "C" __attribute__((visibility("default"))) uint32_t hostsim_decode(const uint8_t *buf, size_t size, uint8_t *rgba, float *coeffs_out, int only_entropy) {
 	g_first_attempt = 0;
+	mod_block_reset();
 	uint32_t e = hostsim_decode_once(buf, size, rgba, coeffs_out, only_entropy, false);
 	if (e == (uint32_t) ERR_EVOF) { g_first_attempt = e; e = hostsim_decode_once(buf, size, rgba, coeffs_out, only_entropy & ~16, true); }
 	return e;
 }
+
+// the Modular blocks of the last hostsim_decode (mod_block.hpp): guard bytes that no longer read 0x5a; the bytes of the regions called `name`
+extern "C" __attribute__((visibility("default"))) int64_t hostsim_guard_damage(void) { return (int64_t) g_guard_damage; }
+extern "C" __attribute__((visibility("default"))) int64_t hostsim_region_bytes(const char *name) { return mod_block_region_bytes(name); }
 
 static uint32_t hostsim_decode_once(const uint8_t *buf, size_t size, uint8_t *rgba, float *coeffs_out, int only_entropy, bool force_dense) {
 	Frame fr;
@@ -374,24 +362,14 @@ static uint32_t hostsim_decode_once(const uint8_t *buf, size_t size, uint8_t *rg
 			for (uint32_t e = 0; e < n; ++e) { const CoeffEvent &ev = events[be[0] + skip + e]; dst[(size_t) vb.coeff_base + (size_t) order[coeff_event_pos(ev)]] = (float) coeff_event_value(ev); }
 		}
 	}
-	// the Modular sub-images behind the coefficients (VarDCT frames with extra channels), as runtime.hip's validate_trailers does
+	// the Modular sub-images behind the coefficients (VarDCT frames with extra channels), in the block runtime.hip's validate_trailers lays out
 	if (hp.frame.sections_have_trailer && !(only_entropy & 4) && g_group_count < 0) {
 		HostModPlan tp;
 		std::vector<std::pair<int32_t, uint32_t>> header_errors;
 		std::vector<int32_t> section_of;
 		if (uint32_t e = build_trailer_plan(fr, hp.codestream.data(), hp.codestream.size() - 16, end_bits.data(), status.data(), &tp, &header_errors, &section_of)) return e;
-		DevModPlan mp;
-		memset(&mp, 0, sizeof mp);
-		mp.frame = &tp.frame; mp.codestream = hp.codestream.data(); mp.pool_u8 = tp.pool_u8.data(); mp.pool_i32 = tp.pool_i32.data(); mp.pool_u64 = tp.pool_u64.data();
-		mp.clusters = tp.clusters.data(); mp.spec = tp.specs.data(); mp.tree = tp.tree.data(); mp.sections = tp.sections.data();
-		std::vector<std::vector<int16_t>> store(tp.sub_w.size());
-		std::vector<DevSubPlane> subp(tp.sub_w.size());
-		for (size_t k = 0; k < subp.size(); ++k) { store[k].assign((size_t) tp.sub_w[k] * (size_t) tp.sub_h[k] + 1, 0); subp[k] = DevSubPlane{store[k].data(), tp.sub_w[k], tp.sub_h[k], tp.sub_meta[k], 0}; }
-		mp.sub_planes = subp.data();
-		std::vector<int32_t> wps(tp.sections.size() * (size_t) (2 * tp.frame.max_width * 5) + 16), win(tp.lz_window_size ? tp.sections.size() * tp.lz_window_size : 0);
-		std::vector<uint32_t> tstatus(tp.sections.size() + 1, 0);
-		mp.wp_scratch = tp.frame.tree_uses_wp ? wps.data() : nullptr;
-		mp.lz_window = win.empty() ? nullptr : win.data(); mp.lz_window_size = tp.lz_window_size; mp.status = tstatus.data();
+		ModBlock blk(tp, hp.codestream.data());
+		const DevModPlan &mp = blk.plan;
 		for (int32_t i = 0; i < tp.frame.num_sections; ++i) {
 			const ModTables mt = mod_tables_in_hbm(mp, i);
 			if (const uint32_t e = decode_modular_section<false, false>(mp, mt, i)) status[(size_t) section_of[(size_t) i]] = e;
