@@ -13,7 +13,7 @@ CXXFLAGS += -DJ40_LANE_EV_FLUSH=$(EVENT_RING)
 HIPFLAGS = --offload-arch=$(ARCH) -std=c++17 -O3 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fvisibility=hidden -Wall -DJ40_LANE_EV_FLUSH=$(EVENT_RING) $(EXTRA_HIPFLAGS)
 SRC = j40_amd/csrc
 HOST_OBJS = build/obj/plan_build.o build/obj/plan_front.o build/obj/entropy.o build/obj/modular.o build/obj/tables.o build/obj/frame.o build/obj/capi_host.o build/obj/api.o
-DEV_OBJS = build/obj/kernels.o build/obj/modular_kernels.o build/obj/runtime.o build/obj/pipeline.o build/obj/lf_tail_kernels.o build/obj/modular_coop.o build/obj/modular_quad.o build/obj/modular_split.o build/obj/lf_decode.o build/obj/plan_kernels.o build/obj/async.o build/obj/hostcopy.o build/obj/lf_preview.o build/obj/alpha_kernels.o build/obj/region_kernels.o
+DEV_OBJS = build/obj/kernels.o build/obj/modular_kernels.o build/obj/runtime.o build/obj/runtime_upload.o build/obj/runtime_lf.o build/obj/runtime_batch.o build/obj/runtime_lfp.o build/obj/runtime_debug.o build/obj/device_memory.o build/obj/pipeline.o build/obj/lf_tail_kernels.o build/obj/modular_coop.o build/obj/modular_quad.o build/obj/modular_split.o build/obj/lf_decode.o build/obj/plan_kernels.o build/obj/async.o build/obj/hostcopy.o build/obj/lf_preview.o build/obj/alpha_kernels.o build/obj/region_kernels.o
 
 .PHONY: all lib tools oracle hostsim clean
 all: lib tools hostsim oracle
@@ -26,7 +26,7 @@ build/obj/%.o: $(SRC)/%.cpp $(wildcard $(SRC)/*.hpp) $(wildcard $(SRC)/device/*.
 	@mkdir -p build/obj
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-build/obj/%.o: $(SRC)/device/%.hip $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp) include/j40hip.h
+build/obj/%.o: $(SRC)/device/%.hip $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/device/*.hpp) $(wildcard $(SRC)/*.hpp) include/j40hip.h
 	@mkdir -p build/obj
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

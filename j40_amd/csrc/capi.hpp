@@ -4,7 +4,7 @@
 #include "frame.hpp"
 #include "plan_build.hpp"
 
-struct j40hip_device_state;  // defined in device/runtime.hip
+struct j40hip_device_state;  // defined in device/runtime_state.hpp
 
 struct j40hip_frame {
 	const uint8_t *cs = nullptr;     // codestream bytes (inside the caller's buffer, or cs_storage)
@@ -61,7 +61,7 @@ extern "C" j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, i
 extern "C" void j40hip_release_device(j40hip_frame *f);
 
 // internal to the library (api.cpp <-> the device side): the process-wide serving pipeline of a device (device/pipeline.hip) and
-// the pool of pinned host planes the public API hands out as image pixels (device/runtime.hip)
+// the pool of pinned host planes the public API hands out as image pixels (device/device_memory.hip)
 extern "C" j40hip_pipeline *j40hip_serve_pipeline(int device, uint32_t *err);
 extern "C" void j40hip_serve_shutdown(void);
 // CPUs' worth of time the process may use: the visible CPUs, or the cgroup's quota (v2 cpu.max, v1 cfs_quota_us) when that is less.

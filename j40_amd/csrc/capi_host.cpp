@@ -13,7 +13,7 @@ extern "C" {
 
 j40hip_frame *j40hip_frame_parse_ex(const void *buf, size_t size, int threads, uint32_t flags, uint32_t *err) { return j40hip_frame_parse_with(buf, size, threads, flags, nullptr, nullptr, err); }
 
-// (internal; j40hip_frame_parse_on in device/runtime.hip passes the device's LfGroup decoder)
+// (internal; j40hip_frame_parse_on in device/runtime_lf.hip passes the device's LfGroup decoder)
 j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads, uint32_t flags, LfDeviceDecoder lf_decoder, void *lf_ctx, uint32_t *err) {
 	j40hip_frame *h = new j40hip_frame();
 	uint32_t code = 0;

@@ -1,4 +1,4 @@
-// j40_amd/csrc/device/block_cache.hpp -- the recycling allocator behind the device memory cache (runtime.hip), as a class over an
+// j40_amd/csrc/device/block_cache.hpp -- the recycling allocator behind the device memory cache (device_memory.hip), as a class over an
 // allocation backend so that its bookkeeping can be tested on the CPU (tests/hostsim: a backend with a byte budget).
 //
 // Device memory is recycled across frames: hipMalloc / hipFree of a 1.2 GB working set cost far more than an 8K decode. Blocks go
@@ -12,7 +12,7 @@
 // blocks are idle (and the cache is over its limit, or is trimmed).
 //
 // Not thread-safe: the owner serialises calls (acquire() reports when it wants the backend called OUTSIDE the owner's lock, see
-// runtime.hip -- the backend's allocation is the slow part).
+// device_memory.hip -- the backend's allocation is the slow part).
 #pragma once
 #include <cstddef>
 #include <cstdint>

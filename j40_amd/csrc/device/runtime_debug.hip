@@ -1,0 +1,159 @@
+// j40_amd/csrc/device/runtime_debug.hip -- the small setters and getters of a frame handle, and what the tests read back: stage
+// dumps (j40hip_frame_read_*) and the known-answer hooks (j40hip_kat_device_*)
+#include "runtime_state.hpp"
+
+extern "C" uint32_t j40hip_frame_set_output_format(j40hip_frame *h, int32_t format) {
+	if (!h) return ERR_RNGE;
+	if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
+	h->output_format = format;
+	return 0;
+}
+extern "C" uint32_t j40hip_kat_device_alpha_merge(void *rgba_dev, size_t stride_bytes, const int16_t *plane_dev, int32_t pitch, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bpp, int32_t format, void *stream) {
+	if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
+	if (!rgba_dev || !plane_dev || bpp < 8 || bpp > 15 || x0 < 0 || y0 < 0 || w < 0 || h < 0 || pitch < 0 || (int64_t) x0 + w > pitch) return ERR_RNGE;
+	if (stride_bytes < (size_t) (x0 + w) * (format == J40HIP_U16X4 ? 8 : 4)) return ERR_RNGE;
+	launch_alpha_merge(plane_dev, pitch, x0, y0, w, h, bpp, (uint8_t *) rgba_dev, stride_bytes, (hipStream_t) stream, format == J40HIP_U16X4);
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+}
+extern "C" int32_t j40hip_frame_output_format(const j40hip_frame *h) { return h ? h->output_format : 0; }
+extern "C" void j40hip_frame_set_restoration(j40hip_frame *h, int mode) { if (h) h->restoration = mode < 0 ? -1 : mode > 2 ? 2 : mode; }
+extern "C" void j40hip_frame_restoration(const j40hip_frame *h, j40hip_restoration *out) {
+	if (!h || !out) return;
+	const FrameHeader::Restoration &r = h->frame.fh.restoration;
+	out->gab_enabled = r.gab ? 1 : 0;
+	for (int c = 0; c < 3; ++c) for (int j = 0; j < 2; ++j) out->gab_weights[c][j] = r.gab_weights[c][j];
+	out->epf_iters = r.epf_iters;
+	for (int i = 0; i < 8; ++i) out->epf_sharp_lut[i] = r.sharp_lut[i];
+	for (int c = 0; c < 3; ++c) out->epf_channel_scale[c] = r.channel_scale[c];
+	out->epf_quant_mul = r.quant_mul; out->epf_pass0_sigma_scale = r.pass0_sigma_scale; out->epf_pass2_sigma_scale = r.pass2_sigma_scale;
+	out->epf_border_sad_mul = r.border_sad_mul; out->epf_sigma_for_modular = r.sigma_for_modular;
+}
+// the sharpness map of LfGroup gg as decoded (i16 w8*h8), like j40hip_frame_lf_group_plane's planes
+extern "C" int j40hip_frame_sharpness(const j40hip_frame *h, int64_t gg, int16_t *out) {
+	if (!h || gg < 0 || (size_t) gg >= h->frame.lf_groups.size()) return -1;
+	const LfGroup &g = h->frame.lf_groups[(size_t) gg];
+	if (g.sharpness.size() != (size_t) g.width8 * (size_t) g.height8) return -1;
+	memcpy(out, g.sharpness.data(), g.sharpness.size() * 2);
+	return 0;
+}
+// after a decode that ran the filters (synchronised): stage 0 the samples as the inverse transforms left them, 1 the filtered ones --
+// three planes of width * height floats (X, Y, B); stage 2: the reciprocal-sigma plane (w8 * h8 floats)
+extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out) {
+	if (!h || !h->dev || !h->dev->restore_ran || !h->dev->d_xyb) return ERR_RNGE;
+	j40hip_device_state *st = h->dev;
+	const FrameHeader &fh = h->frame.fh;
+	const size_t plane = (size_t) fh.width * (size_t) fh.height, cells = (size_t) ((fh.width + 7) / 8) * (size_t) ((fh.height + 7) / 8);
+	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
+	if (stage == 2) return hipMemcpy(out, st->d_sigma, cells * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+	if (stage == 1) return hipMemcpy(out, st->d_restored, 3 * plane * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+	// stage 0: the planes the pixel kernels wrote are the filters' first input; they survive only when the result lies in the other buffer
+	// pair at every step's end -- re-run the pixel kernels into the spare buffer instead
+	const float *src = st->d_xyb;
+	const FrameHeader::Restoration &r = fh.restoration;
+	const int steps = (r.gab ? 1 : 0) + (r.epf_iters >= 3 ? 3 : r.epf_iters);
+	if (steps >= 2) {   // d_xyb has been written over by the second step: once more, into whichever buffer the result does not occupy
+		float *spare = st->d_restored == st->d_xyb ? st->d_xyb_tmp : st->d_xyb;
+		launch_vardct_frame_xyb(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, spare, (size_t) fh.width * 4, nullptr);
+		if (hipStreamSynchronize(nullptr) != hipSuccess) return ERR_GPU;
+		src = spare;
+	}
+	return hipMemcpy(out, src, 3 * plane * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+}
+extern "C" float j40hip_frame_restoration_ms(const j40hip_frame *h) { return h && h->dev ? h->dev->restore_ms : 0.0f; }
+// known-answer hook: the filter kernels on caller-supplied planes ([3][h][w] floats, in place), a w8*h8 sharpness map and the HfMul
+// reciprocal of the varblock covering each cell; mode 1 / 2 as j40hip_frame_set_restoration; sigma_out (optional): w8*h8 floats
+extern "C" uint32_t j40hip_kat_device_restoration(float *xyb, int32_t w, int32_t h, const int16_t *sharpness, const float *hfmul_inv, const j40hip_restoration *r, int mode, int device, float *sigma_out) {
+	return guarded([&]() -> uint32_t {
+		if (!xyb || !r || w < 1 || h < 1 || j40hip_device_count() <= device || hipSetDevice(device) != hipSuccess) return ERR_GPU;
+		if (!ensure_constant_tables(device)) return ERR_GPU;
+		FrameHeader fh;
+		fh.width = w; fh.height = h;
+		fh.restoration.gab = r->gab_enabled != 0;
+		for (int c = 0; c < 3; ++c) for (int j = 0; j < 2; ++j) fh.restoration.gab_weights[c][j] = r->gab_weights[c][j];
+		fh.restoration.epf_iters = r->epf_iters;
+		for (int i = 0; i < 8; ++i) fh.restoration.sharp_lut[i] = r->epf_sharp_lut[i];
+		for (int c = 0; c < 3; ++c) fh.restoration.channel_scale[c] = r->epf_channel_scale[c];
+		fh.restoration.quant_mul = r->epf_quant_mul; fh.restoration.pass0_sigma_scale = r->epf_pass0_sigma_scale; fh.restoration.pass2_sigma_scale = r->epf_pass2_sigma_scale;
+		fh.restoration.border_sad_mul = r->epf_border_sad_mul;
+		RestoreParams p;
+		if (uint32_t e = restore_params(fh, mode, &p)) return e;
+		if (fh.restoration.gab && w < 2) return ERR_TODO;
+		const size_t plane = (size_t) w * (size_t) h, cells = (size_t) p.w8 * (size_t) p.h8;
+		if (r->epf_iters > 0) { uint16_t ub = 0; for (size_t i = 0; i < cells; ++i) ub |= (uint16_t) sharpness[i]; if (!(ub < 8)) return ERR4('s', 'h', 'r', 'p'); }
+		j40hip_device_state tmp; tmp.device = device;
+		bool ok = true;
+		float *d_a = tmp.upload(xyb, 3 * plane, nullptr, ok), *d_b = tmp.scratch<float>(3 * plane, ok), *d_sigma = tmp.scratch<float>(cells + 64, ok);
+		if (ok && r->epf_iters > 0) {
+			int16_t *d_sh = tmp.upload(sharpness, cells, nullptr, ok);
+			float *d_hf = tmp.upload(hfmul_inv, cells, nullptr, ok);
+			if (ok) { (void) hipMemsetAsync(d_sigma + cells, 0, 4, nullptr); launch_epf_sigma_cells(d_sh, d_hf, p, d_sigma, (uint32_t *) (d_sigma + cells), nullptr); }
+		}
+		if (ok) {
+			const float *res = launch_restoration(d_a, d_b, (size_t) w, p, fh.restoration.gab, r->epf_iters, d_sigma, nullptr);
+			ok = hipMemcpy(xyb, res, 3 * plane * 4, hipMemcpyDeviceToHost) == hipSuccess;
+			if (ok && sigma_out && r->epf_iters > 0) ok = hipMemcpy(sigma_out, d_sigma, cells * 4, hipMemcpyDeviceToHost) == hipSuccess;
+		}
+		(void) hipDeviceSynchronize();
+		for (auto &b : tmp.buffers) b.release();
+		tmp.buffers.clear();
+		return ok ? 0 : ERR_GPU;
+	});
+}
+
+extern "C" uint32_t j40hip_frame_read_coeffs(j40hip_frame *h, int64_t gg, int c, float *out) {
+	if (!h || !h->dev || h->dev->is_modular) return ERR_GPU;
+	j40hip_device_state *st = h->dev;
+	const LfGroup &g = h->frame.lf_groups[(size_t) gg];
+	size_t base = 0;
+	for (int64_t i = 0; i < gg; ++i) base += h->frame.lf_groups[(size_t) i].blocks.size();
+	if (!st->plan.events) {   // dense planes, canonical order
+		return hipMemcpy(out, st->plan.coeffs[c] + base * 64, sizeof(float) * g.blocks.size() * 64, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+	}
+	// sparse: expand the events of this LF group's blocks into the canonical layout the reference keeps
+	std::vector<uint32_t> table(4 * st->num_blocks);
+	if (hipMemcpy(table.data(), st->plan.block_events, sizeof(uint32_t) * table.size(), hipMemcpyDeviceToHost) != hipSuccess) return ERR_GPU;
+	memset(out, 0, sizeof(float) * g.blocks.size() * 64);
+	std::vector<CoeffEvent> ev;
+	if (!host_vb_sorted(st)) return ERR_GPU;
+	for (const DevVarblock &vb : st->vb_sorted) {
+		if ((size_t) vb.llf_base < base || (size_t) vb.llf_base >= base + g.blocks.size()) continue;   // another LF group's block
+		const uint32_t *be = table.data() + 4 * (size_t) vb.blk;
+		const uint32_t skip = c == 1 ? 0 : c == 0 ? be[1] : be[1] + be[2], n = be[c == 1 ? 1 : c == 0 ? 2 : 3];   // emission order Y, X, B
+		if (!n) continue;
+		ev.resize(n);
+		if (hipMemcpy(ev.data(), st->plan.events + be[0] + skip, sizeof(CoeffEvent) * n, hipMemcpyDeviceToHost) != hipSuccess) return ERR_GPU;
+		const std::vector<int32_t> &order = h->frame.orders[0][DCT_SELECT[vb.dctsel].order_idx][(size_t) c];
+		float *blk = out + ((size_t) vb.llf_base - base) * 64;
+		for (const CoeffEvent &e : ev) blk[order[coeff_event_pos(e)]] = (float) coeff_event_value(e);
+	}
+	return 0;
+}
+
+extern "C" uint32_t j40hip_frame_read_plane_i16(j40hip_frame *h, int c, int16_t *out) {
+	if (!h || !h->dev || !h->dev->is_modular) return ERR_GPU;
+	j40hip_device_state *st = h->dev;
+	if (c < 0 || (size_t) c >= st->final_planes.size()) return ERR_RNGE;
+	const size_t n = (size_t) st->final_w[(size_t) c] * (size_t) st->final_h[(size_t) c];
+	if (hipMemcpy(out, st->final_planes[(size_t) c], n * 2, hipMemcpyDeviceToHost) != hipSuccess) return ERR_GPU;
+	return 0;
+}
+
+// known-answer hooks: n floats through the pixel kernels' sRGB tail on the device (launch(dv, dout)), one sample of T each
+template <typename T, typename L> static uint32_t kat_srgb(const float *v_host, size_t n, T *out_host, L launch) {
+	if (j40hip_device_count() <= 0) return ERR_GPU;
+	float *dv = nullptr; T *dout = nullptr;
+	bool ok = hipMalloc((void **) &dv, n * 4 + 16) == hipSuccess && hipMalloc((void **) &dout, n * sizeof(T) + 16) == hipSuccess;
+	ok = ok && hipMemcpy(dv, v_host, n * 4, hipMemcpyHostToDevice) == hipSuccess;
+	if (ok) { int dev = 0; ok = hipGetDevice(&dev) == hipSuccess && ensure_constant_tables(dev); if (ok) launch(dv, dout); }
+	ok = ok && hipMemcpy(out_host, dout, n * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
+	if (dv) (void) hipFree(dv);
+	if (dout) (void) hipFree(dout);
+	return ok ? 0 : ERR_GPU;
+}
+extern "C" uint32_t j40hip_kat_device_srgb_u8(const float *v_host, size_t n, uint8_t *out_host) {
+	return kat_srgb(v_host, n, out_host, [&](const float *dv, uint8_t *dout) { launch_kat_srgb_u8(dv, n, dout, nullptr); });
+}
+extern "C" uint32_t j40hip_kat_device_srgb_u16(const float *v_host, size_t n, int32_t bpp, uint16_t *out_host) {
+	if (bpp < 8 || bpp > 15) return ERR_RNGE;
+	return kat_srgb(v_host, n, out_host, [&](const float *dv, uint16_t *dout) { launch_kat_srgb_u16(dv, n, bpp, dout, nullptr); });
+}

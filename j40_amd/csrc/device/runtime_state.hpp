@@ -1,0 +1,255 @@
+// j40_amd/csrc/device/runtime_state.hpp -- internal to device_memory.hip and the runtime*.hip units: a frame's device state
+// (j40hip_device_state), the error codes, the small helpers every unit uses and the declarations of what crosses units
+#pragma once
+#include <hip/hip_runtime.h>
+#include <deque>
+#include <condition_variable>
+#include <chrono>
+#include <thread>
+#include <algorithm>
+#include <mutex>
+#include <atomic>
+#include <cmath>
+#include <unistd.h>
+#include "../capi.hpp"
+#include "../tables.hpp"
+#include "../plan_build.hpp"
+#include "../mod_layout.hpp"
+#include "kernels.h"
+#include "runtime_shared.hpp"
+
+using namespace j40hip;      // (an internal header: every unit that includes it is written in these two namespaces)
+using namespace j40hip_rt;
+
+namespace j40hip_rt {
+
+constexpr uint32_t ERR4(char a, char b, char c, char d) { return ((uint32_t) (uint8_t) a << 24) | ((uint32_t) (uint8_t) b << 16) | ((uint32_t) (uint8_t) c << 8) | (uint32_t) (uint8_t) d; }
+constexpr uint32_t ERR_GPU = ERR4('!', 'g', 'p', 'u'), ERR_MEM = ERR4('!', 'm', 'e', 'm');
+constexpr uint32_t ERR_URG = ERR4('U', 'r', 'g', '?');   // a region (j40hip_frame_set_region) where only whole frames or group ranges are served, or the other way round
+constexpr uint32_t ERR_ULF = ERR4('U', 'l', 'f', '?');   // an LF-only frame (J40HIP_PARSE_LF_ONLY) has nothing but its LF image: the full decode's entry points refuse it
+
+// no exception crosses the C ABI: a parse error keeps its code, anything else (std::bad_alloc from a vector, ...) is "!mem"
+template <typename F> uint32_t guarded(F f) {
+	try { return f(); }
+	catch (const DecodeError &e) { return e.code; }
+	catch (const std::exception &) { return ERR_MEM; }
+}
+
+struct DeviceBuffer {
+	void *ptr = nullptr; size_t bytes = 0;
+	bool alloc(size_t n);   // (device_memory.hip)
+	void release() { if (ptr) (void) hipFree(ptr); ptr = nullptr; }
+};
+
+// a temporary block of a synchronous call: back to the cache behind a device-wide wait on every return path (such calls return long
+// before process exit, so this one may have a destructor)
+struct ScopedBlock : CacheBlock { ~ScopedBlock() { release(false); } };
+
+// this thread's pinned buffers and event (device_memory.hip; j40hip_thread_release frees them). No destructors: at process exit the
+// runtime may be gone before the thread's storage.
+extern thread_local PinnedStage t_stage;    // an upload's staged plan
+extern thread_local PinnedStage t_lf_out;   // lf_device_decode's results land here; LfDeviceTask's pointers point into it until the thread's next call
+extern thread_local hipEvent_t t_lf_done;
+extern thread_local HostPlan t_host_plan;   // upload_impl's, storage kept from frame to frame
+
+struct Stager {
+	size_t size = 0; bool ok = true;
+	// deferred: put() notes the copy, flush() makes them all, shared out by bytes over a few threads (an 8K frame's plan is 30 MB: a
+	// millisecond of one core's memcpy on the single-image path); the sources have to live until then
+	bool deferred = false;
+	struct Copy { size_t off; const uint8_t *src; size_t bytes; };
+	std::vector<Copy> copies;
+	template <typename T> size_t put(const T *src, size_t n) {
+		const size_t off = (size + 255) & ~(size_t) 255, end = off + sizeof(T) * n + 16;
+		if (!ok || !t_stage.reserve(end, size)) { ok = false; return 0; }
+		if (n) { if (deferred) copies.push_back({off, (const uint8_t *) src, sizeof(T) * n}); else memcpy(t_stage.ptr + off, src, sizeof(T) * n); }
+		size = end;   // (deferred: a grown buffer keeps the bytes below `size` -- nothing of the noted copies is there yet, and nothing needs to be)
+		return off;
+	}
+	void flush(int threads) {
+		if (!deferred || !ok) { copies.clear(); return; }
+		size_t total = 0;
+		for (const Copy &c : copies) total += c.bytes;
+		const int n = total < ((size_t) 4 << 20) ? 1 : std::max(1, std::min(threads, 8));
+		uint8_t *base = t_stage.ptr;
+		auto work = [&](int t) {
+			const size_t lo = total / (size_t) n * (size_t) t, hi = t + 1 == n ? total : total / (size_t) n * (size_t) (t + 1);
+			size_t at = 0;
+			for (const Copy &c : copies) {
+				const size_t a = std::max(lo, at), b = std::min(hi, at + c.bytes);
+				if (a < b) memcpy(base + c.off + (a - at), c.src + (a - at), b - a);
+				at += c.bytes;
+			}
+		};
+		std::vector<std::thread> pool;
+		try { for (int t = 1; t < n; ++t) pool.emplace_back(work, t); } catch (const std::exception &) {}
+		const int started = (int) pool.size() + 1;
+		work(0);
+		for (int t = started; t < n; ++t) work(t);   // (threads that could not be had: their share here)
+		for (auto &th : pool) th.join();
+		copies.clear();
+	}
+	size_t reserve(size_t bytes) {   // room in the device block that nothing is copied into (the bytes staged for it are whatever is there)
+		const size_t off = (size + 255) & ~(size_t) 255, end = off + bytes + 16;
+		if (!ok || !t_stage.reserve(end, size)) { ok = false; return 0; }
+		size = end;
+		return off;
+	}
+	const uint8_t *data() const { return t_stage.ptr; }
+};
+
+// Four events around the three stages of a decode (clear | entropy | pixels), recorded on `s`; ev null: nothing is recorded or timed
+struct StageMarks {
+	hipEvent_t *ev; hipStream_t s;
+	void mark(int i) const { if (ev) (void) hipEventRecord(ev[i], s); }
+	// waits for the last mark; ms3[0]: entropy, [1]: pixels, [2]: clear
+	uint32_t finish(float *ms3) const {
+		if (!ev) return 0;
+		if (hipEventSynchronize(ev[3]) != hipSuccess) return ERR_GPU;
+		float t[3] = {0, 0, 0};
+		for (int i = 0; i < 3; ++i) (void) hipEventElapsedTime(&t[i], ev[i], ev[i + 1]);
+		ms3[0] = t[1]; ms3[1] = t[2]; ms3[2] = t[0];
+		return 0;
+	}
+};
+
+// Things borrowed for one call and handed back afterwards (T has a member `device`): the idle ones of every device, until
+// j40hip_shutdown drains them
+template <typename T> struct IdlePool {
+	std::mutex m; std::vector<T> idle;
+	bool take(int device, T *out) {
+		std::lock_guard<std::mutex> lock(m);
+		for (size_t i = 0; i < idle.size(); ++i) if (idle[i].device == device) { *out = idle[i]; idle.erase(idle.begin() + (long) i); return true; }
+		return false;
+	}
+	void give(const T &t) { std::lock_guard<std::mutex> lock(m); idle.push_back(t); }
+	template <typename F> void drain(F destroy) {
+		std::vector<T> all;
+		{ std::lock_guard<std::mutex> lock(m); all.swap(idle); }
+		for (T &t : all) destroy(t);
+	}
+};
+
+} // namespace j40hip_rt
+
+struct j40hip_device_state {
+	int device = 0;
+	std::vector<DeviceBuffer> buffers;
+	CacheBlock plan_block, work_block;                    // VarDCT frames: the uploaded plan and the working set (recycled, see cache_acquire)
+	bool force_dense = false;                             // dense coefficient planes although the frame has one pass (after ERR_EVOF)
+	size_t num_blocks = 0;                                // entries of plan.block_events / 4
+	DevPlan plan;
+	bool is_modular = false;
+	int64_t first_group = 0, num_groups = 0;       // range decoded by this process
+	std::vector<DevVarblock> vb_sorted;             // by DctSelect; host copy, fetched from the device on demand (host_vb_sorted)
+	size_t vb_count = 0;
+	int32_t class_start[28];
+	DevVarblock *d_vb_sorted = nullptr;
+	// sharded decode (j40hip_frame_set_group_range): the varblocks of the selected groups, same layout as vb_sorted
+	DevVarblock *d_vb_range = nullptr; int32_t range_class_start[28]; size_t vb_range_capacity = 0;
+	float *d_large_scratch = nullptr;
+	size_t coeff_floats = 0;
+	int32_t total_sections = 0;
+	HfLaunchInfo hf;
+	// Modular frames
+	DevModPlan mod;
+	int32_t mod_sections = 0, mod_passes = 1, mod_sections_per_pass = 0;   // sections = LfGlobal's (0 or 1) + passes * per_pass
+	bool mod_local_rcts = false;
+	bool has_trailers = false;           // VarDCT frame whose sections go on with the extra channels' Modular sub-image
+	bool idle = false;                   // j40hip_frame_mark_idle: nothing is pending on this frame's memory, freeing it needs no device-wide wait
+	bool trailers_pending = false;       // ... decoded by a batch since: j40hip_frame_status validates the sub-images before it reports
+	ModLaunchInfo mod_info = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	std::vector<uint32_t> mod_section_offsets;
+	// group: the group whose section's sub-image the op belongs to (mod_sub_ops; a ranged decode skips the ops of groups it did not decode), -1: the frame's
+	struct ModOp { int kind; int16_t *a, *b, *c; const int16_t *src, *aux; size_t n; int32_t p0, p1, p2, p3, p4, p5; int16_t *const *dst_list; const int8_t *wpp; int32_t group; };
+	std::vector<ModOp> mod_ops;          // inverse transforms of the frame, in execution order
+	std::vector<ModOp> mod_sub_ops;      // before them: inverse transforms of the sections' own sub-images and their paste (kind 3)
+	std::vector<int16_t *> final_planes; // channel list after the inverse transforms
+	std::vector<int32_t> final_w, final_h;
+	int32_t alpha_channel = -1;
+	int32_t *pal_wp_scratch = nullptr;
+	uint32_t *mod_extra_status = nullptr;
+	std::vector<uint32_t> status_host;
+	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+	// the single-image path's two phases (decode_two_phase): the groups by decreasing section size, the `two_k` first of them decoded
+	// beside the rest with their block_events entries in a table of their own; -1: not looked at yet, 0: not for this frame
+	int32_t two_k = -1;
+	uint32_t *d_two_order = nullptr, *d_two_shadow = nullptr;   // (one block of the device memory cache: two_block)
+	CacheBlock two_block;
+	std::vector<uint32_t> two_order;
+	hipStream_t two_stream = nullptr; hipEvent_t two_ev[3] = {nullptr, nullptr, nullptr};
+	// the restoration filters (decode_impl, restore_*): made at the first decode that runs them, kept with the frame
+	float *d_xyb = nullptr, *d_xyb_tmp = nullptr, *d_sigma = nullptr; int16_t *d_sharp = nullptr;
+	const float *d_restored = nullptr;   // where the last decode's filtered planes lie (d_xyb or d_xyb_tmp)
+	uint32_t restore_err = 0;            // the last decode's "gab0" / "epf0" / "shrp" (reported behind the sections' codes)
+	int restore_ran = 0;                 // the mode the last decode ran the filters in (0: it did not)
+	float restore_ms = 0;
+	// the LF preview (lf_preview.hip): the frame's LfGroups and LF integers as the preview kernel reads them -- the integers are the
+	// plan's when it holds them (parsed with flags & 1), else in an allocation of their own (LF-only frames at upload, other frames at
+	// their first preview); lfp_host is what was copied, kept with the frame because the copy is asynchronous
+	DevLfpFrame lfp = {};
+	bool lfp_ready = false;
+	std::vector<uint8_t> lfp_host;
+
+	// the kept alpha channel (j40hip_frame_set_alpha; keep_alpha below): the keep-mode trailer plan, the frame-wide planes of the extra
+	// channels and the Modular decode's scratch in ONE block of the device memory cache, laid out at the first decode that keeps alpha
+	// and used again by every later decode of the same group range (a stream's sections end where they ended before)
+	struct AlphaKeep {
+		CacheBlock block;
+		bool ready = false; int64_t first_group = -1, num_groups = -1;
+		DevModPlan plan; ModLaunchInfo info; int32_t num_sections = 0; bool local_rcts = false;
+		const int16_t *alpha_plane = nullptr;
+		std::vector<int32_t> section_of;                          // plan section -> the frame's section
+		std::vector<std::pair<int32_t, uint32_t>> header_errors;  // sections whose sub-image header did not parse
+		std::vector<uint8_t> staging;                             // what was copied into the block (the copy is asynchronous)
+	} alpha;
+	// region decode (j40hip_frame_set_region; decode_region below). The group-major index of d_vb_sorted, built on the device at the
+	// first region decode of this upload (region_dev.h): seg_start, where every (group, class) segment of `index` starts, and on the
+	// host only the segments' sizes. Per region: the cover's varblocks (list, class_start) and its groups (order), gathered on the
+	// device when the cover changes. staging: the cover-sized image the pixel kernels write before the rectangle is cut out, one block
+	// of the device memory cache, grown on demand, given back with the frame.
+	struct Region {
+		bool index_ready = false;
+		uint32_t *d_cursor = nullptr, *d_seg_start = nullptr, *d_index = nullptr, *d_order = nullptr;
+		std::vector<uint32_t> counts;                 // [num_groups * REGION_KEYS]
+		DevVarblock *d_list = nullptr; size_t list_capacity = 0;
+		int32_t class_start[REGION_KEYS]; RegionCover gathered = {0, 0, 0, 0, 0, 0};   // (what d_list and d_order hold: cols = 0, nothing)
+		CacheBlock staging;
+	} region;
+	// a batch decoded the frame (trailers_pending): where, for the merge at j40hip_frame_status
+	void *pending_rgba = nullptr; size_t pending_stride = 0;
+
+	template <typename T> T *upload(const T *src, size_t n, hipStream_t s, bool &ok) {
+		DeviceBuffer b;
+		if (!b.alloc(sizeof(T) * n)) { ok = false; return nullptr; }
+		buffers.push_back(b);
+		if (n && hipMemcpyAsync(b.ptr, src, sizeof(T) * n, hipMemcpyHostToDevice, s) != hipSuccess) ok = false;
+		return (T *) b.ptr;
+	}
+	template <typename T> T *scratch(size_t n, bool &ok) {
+		DeviceBuffer b;
+		if (!b.alloc(sizeof(T) * n)) { ok = false; return nullptr; }
+		buffers.push_back(b);
+		return (T *) b.ptr;
+	}
+};
+
+namespace j40hip_rt {
+
+// the frame's output format (j40hip_frame_set_output_format): 16-bit RGBA, 8 bytes a pixel, or the default u8x4
+inline bool out16(const j40hip_frame *h) { return h->output_format == J40HIP_U16X4; }
+inline size_t pixel_bytes(const j40hip_frame *h) { return out16(h) ? 8 : 4; }
+// a 16-bit frame's rows must hold 8 * width bytes: "rnge" before anything is launched (the u8 entry points keep their old contract)
+inline bool stride_too_small(const j40hip_frame *h, size_t stride_bytes) { return out16(h) && stride_bytes < 8 * (size_t) h->frame.fh.width; }
+
+// what crosses units
+bool host_vb_sorted(j40hip_device_state *st);                                  // runtime_upload.hip
+uint32_t upload_lf_only(j40hip_frame *h, int device, hipStream_t s);           // runtime_lfp.hip
+bool modular_groups_independent(const j40hip_frame *h);                        // runtime.hip
+uint32_t clear_before_decode(j40hip_device_state *st, hipStream_t s);          // runtime.hip
+uint32_t restore_params(const FrameHeader &fh, int mode, RestoreParams *p);    // runtime.hip
+void lf_services_shutdown();   // runtime_lf.hip, runtime.hip, runtime_lfp.hip: j40hip_shutdown's steps
+void two_phase_shutdown();
+void lfp_args_shutdown();
+
+} // namespace j40hip_rt

@@ -1,5 +1,5 @@
 // j40_amd/csrc/plan_build.hpp -- flattens a parsed Frame into the pointer-free plan the kernels read
-// (device/plan.h). Pure host code: runtime.hip uploads the arrays to HBM; tests/hostsim points a
+// (device/plan.h). Pure host code: runtime_upload.hip uploads the arrays to HBM; tests/hostsim points a
 // DevPlan at them directly to single-step the device functions on the CPU.
 #pragma once
 #include "frame.hpp"

@@ -92,7 +92,7 @@ static int32_t g_neighbour_flip = 0;
 static uint32_t hostsim_decode_modular(const Frame &fr, const uint8_t *cs, size_t cs_size, uint8_t *rgba) {
 	HostModPlan hp;
 	if (uint32_t e = build_modular_plan(fr, cs, cs_size, &hp)) return e;
-	ModBlock blk(hp, hp.codestream.data());   // the block runtime.hip's upload_modular lays out
+	ModBlock blk(hp, hp.codestream.data());   // the block runtime_upload.hip's upload_modular lays out
 	const DevModPlan &plan = blk.plan;
 	uint32_t *status = plan.status;   // [num_sections + 1]
 	struct Ref { int16_t *p; int32_t w, h; };
@@ -134,7 +134,7 @@ static uint32_t hostsim_decode_modular(const Frame &fr, const uint8_t *cs, size_
 			const size_t n = (size_t) c[0].w * (size_t) c[0].h;
 			for (size_t i = 0; i < n; ++i) inverse_rct_pixel(t.rct_type % 7, c[0].p[i], c[1].p[i], c[2].p[i]);
 			for (int i = 0; i < 3; ++i) planes[(size_t) (t.begin_c + PERM[t.rct_type / 7][i])] = c[i];
-		} else if (t.kind == Transform::SQUEEZE) {   // as the runtime schedules it: a new plane per squeezed channel (device/runtime.hip)
+		} else if (t.kind == Transform::SQUEEZE) {   // as the runtime schedules it: a new plane per squeezed channel (device/runtime_upload.hip)
 			const int32_t nc = (int32_t) planes.size(), end_c = t.begin_c + t.num_c, offset = t.in_place ? end_c : nc - t.num_c;
 			for (int32_t c = t.begin_c; c < end_c; ++c) {
 				const Ref avg = planes[(size_t) c], res = planes[(size_t) (offset + c - t.begin_c)];
@@ -1192,7 +1192,7 @@ extern "C" __attribute__((visibility("default"))) void hostsim_unsqueeze_line(co
 }
 
 // ---- the device memory cache's bookkeeping (device/block_cache.hpp) on the CPU: a backend with a byte budget stands in for
-// hipMalloc / hipFree, the driver below is runtime.hip's cache_acquire / cache_release / cache_trim line for line ----
+// hipMalloc / hipFree, the driver below is device_memory.hip's cache_acquire / cache_release / cache_trim line for line ----
 #include "../../j40_amd/csrc/device/block_cache.hpp"
 #include <map>
 #include <random>

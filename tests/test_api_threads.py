@@ -99,7 +99,7 @@ def test_64_threads_over_8k_streams_through_the_public_api(built, ref, tmp_path)
 
 @pytest.mark.gpu
 def test_pinned_plane_pool_is_bounded_evicts_the_oldest_and_expires(built):
-    """the pool of pinned image planes behind j40_frame_pixels_u8x4 (runtime.hip: j40hip_pinned_acquire / _release; a drop-in caller
+    """the pool of pinned image planes behind j40_frame_pixels_u8x4 (device_memory.hip: j40hip_pinned_acquire / _release; a drop-in caller
     never calls j40hip_shutdown): what sits idle never exceeds the bound, a new plane size displaces the planes idle longest instead
     of being pinned and unpinned per image, a plane of a size in the pool is reused, idle planes are unpinned after the idle time"""
     code = r'''

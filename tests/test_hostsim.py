@@ -414,7 +414,7 @@ def test_lz77_distance_multiplier_of_lf_global_is_the_whole_images(sim, ref):
 
 
 def test_device_memory_cache_bookkeeping(sim):
-    """device/block_cache.hpp (free list, size classes, slabs) driven like runtime.hip drives it, over a backend with a byte budget:
+    """device/block_cache.hpp (free list, size classes, slabs) driven like device_memory.hip drives it, over a backend with a byte budget:
     random acquire / release / trim sequences keep every invariant (no overlapping blocks, byte counts, slabs freed only when idle,
     a failed allocation retried after a trim), with a roomy and with a tight budget and cache limit"""
     sim.hostsim_block_cache_selftest.restype = C.c_int32

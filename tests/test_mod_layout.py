@@ -1,7 +1,7 @@
 """The layout of a Modular plan's memory (j40_amd/csrc/mod_layout.hpp: ModPlanLayout), checked on the CPU.
 
-runtime.hip lays out three kinds of block with it: a Modular frame (upload_modular), and the extra-channel sub-images of a VarDCT
-frame in drop mode (validate_trailers) and in keep mode (keep_alpha). tests/hostsim lays out the same three blocks in host memory
+The runtime lays out three kinds of block with it: a Modular frame (runtime_upload.hip: upload_modular), and in runtime.hip the
+extra-channel sub-images of a VarDCT frame in drop mode (validate_trailers) and in keep mode (keep_alpha). tests/hostsim lays out the same three blocks in host memory
 (mod_block.hpp): exactly total_bytes from malloc, 64 guard bytes behind every region, the scratch regions and the guards filled
 with 0x5a. A region the layout sizes too small therefore shows here as a damaged guard, or -- in build/mod_layout_main_san, the
 same decodes as a program of its own under the address and undefined-behaviour sanitizers -- as a report at the byte it happens.
