@@ -406,6 +406,69 @@ J40HIP_API uint32_t j40hip_batch_wait_stage(j40hip_batch *b, int32_t slot, int32
 /* a batch object re-used for other members (keeps its device arrays, streams and events); the previous members' decodes must be complete */
 J40HIP_API uint32_t j40hip_batch_reset(j40hip_batch *b, j40hip_frame *const *frames, int64_t n);
 
+/* ---- frame sequences: animations and layered stills ("Several frames"). A codestream whose first frame is not its
+ *      last holds several coded frames; each one is placed on the canvas -- the image's width x height -- and the canvas is shown
+ *      (duration > 0, or the last frame) and/or saved into one of four reference slots for later frames to draw over. Served: frames
+ *      of type 0 and 3 whose blend mode is Replace for the colour channels and every extra channel, with any crop (negative offsets,
+ *      beyond the canvas), any source slot, any save_as_reference; animations (have_animation, durations; timecodes skipped) and
+ *      layers. Refused with "TODO", reported for the frame it comes from: any other blend mode, frame types 1 and 2, use_lf_frame, and
+ *      whatever a single frame is refused for.
+ *      A shown or saved canvas, per pixel: inside the frame's rectangle (x0, y0, w, h) clipped to the canvas the frame's pixel;
+ *      elsewhere the pixel of slot src_ref_frame, or the empty pixel (0, 0, 0, A0) when that slot was never saved -- A0 = 0 when the
+ *      decode renders an alpha channel (a Modular image that has one, a VarDCT image in keep-alpha mode), full scale otherwise. It is
+ *      saved into slot save_as_reference when !is_last && (duration == 0 || save_as_reference != 0). Slots hold rendered pixels in
+ *      the sequence's output format.
+ *      j40hip_sequence_open reads the signature, image header and the header and TOC of every coded frame (`buf` is borrowed until
+ *      j40hip_sequence_free; a container's boxes are put together once); no device needed. A stream whose first frame is its last is
+ *      not a sequence: NULL and "Usq?" (use j40hip_frame_parse). NULL and the code when the image header or the first frame's header
+ *      fails. A later frame whose header or TOC fails, or that is refused, ends the index: it is the last row and carries its code.
+ *      flags as j40hip_frame_parse_ex (bit 0), applied to every frame handle. ---- */
+typedef struct j40hip_sequence j40hip_sequence;
+J40HIP_API j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads, uint32_t flags, uint32_t *err);
+J40HIP_API void j40hip_sequence_free(j40hip_sequence *s);
+J40HIP_API int64_t j40hip_sequence_num_frames(const j40hip_sequence *s);   /* coded frames (rows of the index) */
+J40HIP_API int64_t j40hip_sequence_num_shown(const j40hip_sequence *s);    /* displayed frames */
+/* out21: [0..3] x0, y0, w, h of the frame on the canvas, [4] duration in ticks, [5] is_last, [6] shown, [7] type, [8] the colour
+ * channels' blend mode, [9] source slot, [10] save_as_reference, [11] whether the canvas is saved, [12] byte offset of the frame
+ * header in the codestream and [13] of the end of its last section, [14] of its first section, [15] 0 or the code the frame is refused
+ * with ("shrt": the stream ends before the frame does), [16] ticks per second numerator and [17] denominator, [18] loops (0: for
+ * ever), [19] canvas width, [20] height. k out of range: zeros. */
+J40HIP_API void j40hip_sequence_frame_info(const j40hip_sequence *s, int64_t k, int64_t *out21);
+/* Coded frame k, fully parsed at the first call: an ordinary frame handle of the frame's own (crop) size over a copy of the frame's
+ * own bytes, owned by the sequence (do not free it). Every single-frame and batch entry point takes it -- upload, decode, region,
+ * LF preview, alpha mode, status. NULL and the code for a frame that is refused or does not parse. */
+J40HIP_API j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err);
+/* parses and uploads every coded frame to `device` (its own bytes each, not the whole file) and takes the device memory of the
+ * playback: every slot the index saves into and one staging image large enough for each cropped frame. A frame that does not parse
+ * ends the index there, as a refused one does at j40hip_sequence_open: it becomes the last row and carries its code, the frames
+ * before it play. Returns the code of a frame that fails to upload, "!gpu" when the device is out of memory. */
+J40HIP_API uint32_t j40hip_sequence_upload(j40hip_sequence *s, int device);
+/* J40HIP_U8X4 or J40HIP_U16X4 for every frame and the canvas; "Ufm?" otherwise; "Uof?" once the playback has begun (rewind first).
+ * After an upload a change takes the slots and the staging image again and may wait for the device. */
+J40HIP_API uint32_t j40hip_sequence_set_output_format(j40hip_sequence *s, int32_t format);
+/* Decodes the coded frames up to and including the next displayed one and leaves that frame's canvas in rgba_dev: canvas-sized, rows
+ * of stride_bytes (at least 4 or 8 bytes a pixel, else "rnge"), pixel-aligned. Frames that are saved are composed in their slot --
+ * where that slot is also the source (out == src for the compose kernel) only the rectangle is written -- and copied out when they
+ * are shown; up to four canvas-sized slots and one staging image come from the device memory cache at j40hip_sequence_upload and go
+ * back at j40hip_sequence_free. A frame that covers the canvas exactly decodes straight into its destination. Everything is enqueued
+ * on `stream`; nothing is waited for and no memory is taken (frames in keep-alpha mode synchronise as j40hip_frame_decode does). Returns 0; "Useq" when no
+ * displayed frame is left; the code of a frame that is refused or fails to upload ("!gpu": not uploaded). Section failures surface
+ * in j40hip_sequence_status once the stream has been synchronised. */
+J40HIP_API uint32_t j40hip_sequence_next(j40hip_sequence *s, void *rgba_dev, size_t stride_bytes, void *stream);
+/* ... into host memory, synchronously, every coded frame's status checked as it is decoded (an "evof" frame is decoded again with
+ * dense planes): 0, "Useq", or the failing frame's code -- the canvas is then not written */
+J40HIP_API uint32_t j40hip_sequence_next_to_host(j40hip_sequence *s, void *rgba_host, size_t stride_bytes);
+J40HIP_API void j40hip_sequence_rewind(j40hip_sequence *s);   /* the next j40hip_sequence_next starts over at frame 0 with no slot saved */
+/* After the stream has been synchronised: the first failing section over the frames decoded since the last rewind, frame by frame in
+ * order -> its code, and in *out_frame (optional) which coded frame; 0 and -1 when all of them decoded cleanly */
+J40HIP_API uint32_t j40hip_sequence_status(j40hip_sequence *s, int64_t *out_frame);
+/* known-answer / measuring hook: k_frame_compose alone (device/compose_kernels.hip). The frame image frame_dev (w x h pixels, its
+ * pixel (0, 0) at canvas pixel (x0, y0)) onto the W x H canvas at out_dev; outside the rectangle the pixels of src_dev or, src_dev
+ * NULL, the empty pixel whose bytes are empty_lo (u8x4) or empty_lo, empty_hi (u16x4) as little-endian words. out_dev == src_dev (and
+ * equal strides): only the rectangle is written. All rows pixel-aligned. Asynchronous on `stream`. 0, "rnge", "Ufm?". */
+J40HIP_API uint32_t j40hip_kat_device_compose(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, const void *frame_dev, size_t frame_stride,
+		int32_t W, int32_t H, int32_t x0, int32_t y0, int32_t w, int32_t h, uint32_t empty_lo, uint32_t empty_hi, int32_t format, void *stream);
+
 /* ---- building blocks for pipelines ---- */
 /* j40hip_frame_upload with the copies enqueued on `stream` (the plan is staged in pinned memory owned by the calling thread, so the
  * copy is a real asynchronous DMA beside other streams' kernels); returns when they have completed */

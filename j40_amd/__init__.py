@@ -14,6 +14,7 @@ path. Function names mirror the reference's public API (j40.h:233-272):
 `Frame` exposes the thin C-ABI of include/j40hip.h (parse / upload / decode on a stream / status /
 stage dumps) for the parity tests, bench.py and the multi-GPU driver.
 """
+import weakref
 import ctypes as C
 import os
 import numpy as np
@@ -117,6 +118,12 @@ def lib():
         "j40hip_stage_dump_varblocks": (C.c_int, [vp, i64, vp, vp, vp]), "j40hip_stage_dump_llf": (C.c_int, [vp, i64, C.c_int, vp]),
         "j40hip_stage_dump_group_blocks": (i64, [vp, i64, vp, i64]), "j40hip_stage_dump_sorted_varblocks": (i64, [vp, vp, vp, vp, i64]), "j40hip_stage_dump_rgba": (C.c_int, [vp, vp]),
         "j40hip_copy_engine": (C.c_int, [C.c_int, vp, vp]),
+        "j40hip_sequence_open": (vp, [vp, sz, C.c_int, u32, C.POINTER(u32)]), "j40hip_sequence_free": (None, [vp]),
+        "j40hip_sequence_num_frames": (i64, [vp]), "j40hip_sequence_num_shown": (i64, [vp]), "j40hip_sequence_frame_info": (None, [vp, i64, vp]),
+        "j40hip_sequence_frame": (vp, [vp, i64, C.POINTER(u32)]), "j40hip_sequence_upload": (u32, [vp, C.c_int]),
+        "j40hip_sequence_set_output_format": (u32, [vp, i32]), "j40hip_sequence_next": (u32, [vp, vp, sz, vp]),
+        "j40hip_sequence_next_to_host": (u32, [vp, vp, sz]), "j40hip_sequence_rewind": (None, [vp]), "j40hip_sequence_status": (u32, [vp, C.POINTER(i64)]),
+        "j40hip_kat_device_compose": (u32, [vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, u32, u32, i32, vp]),
         "j40hip_frame_restoration": (None, [vp, vp]), "j40hip_frame_set_restoration": (None, [vp, C.c_int]), "j40hip_frame_sharpness": (C.c_int, [vp, i64, vp]),
         "j40hip_frame_set_alpha": (u32, [vp, C.c_int]), "j40hip_frame_alpha": (None, [vp, vp]),
         "j40hip_frame_set_region": (u32, [vp, i32, i32, i32, i32]), "j40hip_frame_region": (None, [vp, vp]),
@@ -437,10 +444,22 @@ class Frame:
             self._chk(err.value or int.from_bytes(b"!mem", "big"), "in j40hip_frame_lf_bundle")
         return out.raw
 
+    @classmethod
+    def _borrowed(cls, handle, owner):
+        """a frame handle somebody else owns (a Sequence's coded frame): every method works, close() leaves the handle alone"""
+        self = cls.__new__(cls)
+        self.h, self._owner = handle, owner
+        info = np.zeros(32, np.int64)
+        lib().j40hip_frame_info(self.h, info.ctypes.data)
+        self.info = dict(zip(INFO_FIELDS, info.tolist()))
+        self.width, self.height = self.info["width"], self.info["height"]
+        self.codestream_size = lib().j40hip_frame_codestream_size(self.h)
+        return self
+
     def close(self):
-        if self.h:
+        if self.h and getattr(self, "_owner", None) is None:
             lib().j40hip_frame_free(self.h)
-            self.h = None
+        self.h = None
 
     def __del__(self):
         try:
@@ -713,6 +732,132 @@ def decode_lf_many(datas, fmt=J40_U8X4, device=0):
     finally:
         for f in frames:
             f.close()
+
+
+SEQUENCE_FRAME_FIELDS = ("x0", "y0", "w", "h", "duration", "is_last", "shown", "type", "blend", "src", "save_as_reference", "saved",
+                         "offset", "end", "first_section", "code", "tps_num", "tps_den", "loops", "canvas_w", "canvas_h")
+
+
+class Sequence:
+    """the coded frames of one codestream -- an animation or a layered still -- and their playback (j40hip_sequence, include/j40hip.h):
+    an index over headers and TOCs on the host, every coded frame an ordinary Frame, the displayed canvases composed on the device"""
+
+    def __init__(self, data: bytes, threads: int = 4, flags: int = 0):
+        L = lib()
+        self._buf = C.create_string_buffer(data, len(data))
+        err = C.c_uint32()
+        self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags, C.byref(err))
+        if not self.h:
+            raise J40Error(err4(err.value), "in j40hip_sequence_open")
+        self.num_frames, self.num_shown = int(L.j40hip_sequence_num_frames(self.h)), int(L.j40hip_sequence_num_shown(self.h))
+        first = self.frame_info(0)
+        self.width, self.height = first["canvas_w"], first["canvas_h"]
+        self.tps, self.loops = (first["tps_num"], first["tps_den"]), first["loops"]
+        self.fmt = J40_U8X4
+        self._lent = []   # (k, weak reference) of every Frame handed out by frame(): their handles die with the sequence's
+
+    def _recall(self, first=0):
+        """the Frames handed out for coded frames first.. lose their handles: the sequence is about to free them"""
+        for k, ref in self._lent:
+            fr = ref()
+            if fr is not None and k >= first:
+                fr.h = None
+        self._lent = [(k, ref) for k, ref in self._lent if k < first and ref() is not None]
+
+    def close(self):
+        """frees the sequence and every coded frame's handle; a Frame obtained from frame() is closed with it (its h becomes None)"""
+        if self.h:
+            self._recall()
+            lib().j40hip_sequence_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def frame_info(self, k):
+        """the index row of coded frame k as a dict (SEQUENCE_FRAME_FIELDS; `code` as text)"""
+        out = np.zeros(21, np.int64)
+        lib().j40hip_sequence_frame_info(self.h, k, out.ctypes.data)
+        d = dict(zip(SEQUENCE_FRAME_FIELDS, out.tolist()))
+        d["code"] = err4(d["code"])
+        return d
+
+    def frame(self, k):
+        """coded frame k as a Frame the sequence owns: crop-sized, for every single-frame and batch entry point. It lives as long as the
+        sequence: close() of the sequence closes it too"""
+        err = C.c_uint32()
+        h = lib().j40hip_sequence_frame(self.h, k, C.byref(err))
+        if not h:
+            raise J40Error(err4(err.value), "in j40hip_sequence_frame")
+        fr = Frame._borrowed(h, self)
+        self._lent.append((k, weakref.ref(fr)))
+        return fr
+
+    def upload(self, device=0):
+        """every coded frame parsed and uploaded. A frame that does not parse ends the index there (num_frames and num_shown shrink,
+        Frames handed out for the rows behind it are closed); the playback reports its code when it gets there"""
+        L = lib()
+        code = L.j40hip_sequence_upload(self.h, device)
+        self.num_frames, self.num_shown = int(L.j40hip_sequence_num_frames(self.h)), int(L.j40hip_sequence_num_shown(self.h))
+        self._recall(self.num_frames)
+        if code:
+            raise J40Error(err4(code), "in j40hip_sequence_upload")
+
+    def set_output_format(self, fmt):
+        code = lib().j40hip_sequence_set_output_format(self.h, int(fmt))
+        if code:
+            raise J40Error(err4(code), "in j40hip_sequence_set_output_format")
+        self.fmt = int(fmt)
+
+    def next(self, rgba_ptr, stride_bytes, stream=0):
+        """the next displayed canvas into device memory, asynchronously; returns the code as text ("" or "Useq", ...)"""
+        return err4(lib().j40hip_sequence_next(self.h, rgba_ptr, stride_bytes, stream))
+
+    def next_to_host(self):
+        """(err4, canvas [height, width, 4] or None): the next displayed canvas; "Useq" when none is left"""
+        u16 = self.fmt == J40_U16X4
+        out = np.zeros((self.height, self.width, 4), np.uint16 if u16 else np.uint8)
+        code = err4(lib().j40hip_sequence_next_to_host(self.h, out.ctypes.data, self.width * (8 if u16 else 4)))
+        return code, (None if code else out)
+
+    def rewind(self):
+        lib().j40hip_sequence_rewind(self.h)
+
+    def status(self):
+        """(err4, coded frame) of the first failing section over the frames decoded so far; ("", -1) when there is none"""
+        k = C.c_int64(-1)
+        code = lib().j40hip_sequence_status(self.h, C.byref(k))
+        return err4(code), int(k.value)
+
+
+def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0):
+    """every displayed frame of an animation or a layered still: ([(rgba ndarray [height, width, 4], duration in ticks), ...],
+    (tps_num, tps_den, loops)). alpha=True: VarDCT frames keep their alpha channel (Frame.set_alpha(1); J40Error where that refuses).
+    A frame that fails raises J40Error with its code. A stream whose first frame is its last is not a sequence ("Usq?"): decode()."""
+    seq = Sequence(data)
+    try:
+        seq.set_output_format(fmt)
+        if alpha:
+            for k in range(seq.num_frames):
+                code = seq.frame(k).set_alpha(1)
+                if code:
+                    raise J40Error(code, "in j40hip_frame_set_alpha")
+        seq.upload(device)
+        durations = [seq.frame_info(k)["duration"] for k in range(seq.num_frames) if seq.frame_info(k)["shown"]]
+        frames = []
+        while True:
+            code, px = seq.next_to_host()
+            if code == "Useq":
+                break
+            if code:
+                raise J40Error(code, "in j40hip_sequence_next_to_host")
+            frames.append((px, durations[len(frames)]))
+        return frames, (seq.tps[0], seq.tps[1], seq.loops)
+    finally:
+        seq.close()
 
 
 class Batch:

@@ -60,6 +60,8 @@ struct j40__inner {
 	int decoded, rendered;
 	uint8_t *pixels; size_t pixels_bytes; int32_t width, height, stride_bytes;   // image-owned plane: pinned host memory from the library's pool
 	int32_t format;                                          // J40_U8X4 (default) or J40_U16X4: what j40_output_format asked for
+	j40hip_sequence *seq;                                    // J40HIP_FRAMES=1 and a stream whose first frame is not its last: the frames come from here
+	int seq_checked, seq_ended;
 };
 
 namespace {
@@ -90,6 +92,7 @@ j40_err check_image(j40_image *image, int neworigin, j40__inner **out) {  // j40
 
 void free_inner(j40__inner *inner) {
 	if (inner->frame) j40hip_frame_free(inner->frame);
+	if (inner->seq) j40hip_sequence_free(inner->seq);
 	if (inner->freefunc && inner->buf) inner->freefunc(inner->buf);
 	free(inner->owned);
 	if (inner->fp) fclose(inner->fp);
@@ -197,9 +200,46 @@ uint32_t read_whole_file(j40__inner *inner) {
 	return 0;
 }
 
+// J40HIP_FRAMES=1: streams whose first frame is not their last -- animations, layered stills -- are served frame by frame
+// (j40hip_sequence); looked at when an image is first advanced. Without it such a stream is "TODO", as in the reference.
+bool frames_policy() { return j40hip::env_on("J40HIP_FRAMES", false); }
+int parse_thread_count() {
+	static const int v = [] { const int e = j40hip::env_int("J40HIP_PARSE_THREADS", 0, 0, INT_MAX); return e > 0 ? e : std::max(1, std::min(12, j40hip_cpu_quota())); }();
+	return v;
+}
+
+// The next displayed frame of a sequence into the image-owned plane, canvas-sized: 1, or 0 when no frame is left or one has failed
+// (the error is sticky, as any is). The plane holds the frame until the next call. Such images never go to the serving pipeline.
+int next_sequence_frame(j40__inner *inner, int origin) {
+	if (inner->seq_ended) return 0;
+	uint32_t err = 0;
+	if (!inner->pixels) {
+		int64_t info[21];
+		j40hip_sequence_frame_info(inner->seq, 0, info);
+		if (j40hip_device_count() <= device_index()) err = code4("!gpu");   // (before the plane: pinned memory needs the device too)
+		if (!err) err = make_plane(inner, info[19], info[20], inner->format == J40_U16X4 ? 8 : 4);
+		if (!err) err = j40hip_sequence_set_output_format(inner->seq, inner->format);
+		if (!err) err = j40hip_sequence_upload(inner->seq, device_index());
+	}
+	if (!err) err = j40hip_sequence_next_to_host(inner->seq, inner->pixels, (size_t) inner->stride_bytes);
+	if (err == code4("Useq")) { inner->seq_ended = 1; return 0; }
+	if (err) { inner->origin = origin; inner->err = err; return 0; }
+	inner->decoded = inner->rendered = 1;
+	return 1;
+}
+
 // the whole decode: RGBA into the image-owned plane
 j40_err advance(j40__inner *inner, int origin) {
-	if (inner->decoded) return 0;
+	if (inner->seq || inner->decoded) return 0;
+	if (!inner->seq_checked && frames_policy()) {
+		// a file is read whole first; a stream that is not a sequence ("Usq?": its first frame is its last), or whose headers fail,
+		// takes the single-frame route below, which decodes it or reports what is wrong with it
+		inner->seq_checked = 1;
+		if (inner->fp) if (uint32_t ferr = read_whole_file(inner)) { inner->origin = origin; inner->err = ferr; return ferr; }
+		uint32_t serr = 0;
+		inner->seq = j40hip_sequence_open(inner->buf, inner->size, parse_thread_count(), 1u, &serr);
+		if (inner->seq) return 0;
+	}
 	struct Inside { int n; Inside() : n(++g_inside) {} ~Inside() { --g_inside; } } inside;
 	const int policy = serve_policy();
 	const int64_t now = (int64_t) now_ms();
@@ -246,7 +286,7 @@ j40_err advance(j40__inner *inner, int origin) {
 	// the device at upload, flags = 1)
 	// (no more threads than the container's CPU quota: a process over its quota has all its threads throttled, the HIP runtime's too;
 	// frames with fewer LfGroups and groups than that get a smaller team: parse_frame, build_vardct_plan)
-	static const int parse_threads = [] { const int v = j40hip::env_int("J40HIP_PARSE_THREADS", 0, 0, INT_MAX); return v > 0 ? v : std::max(1, std::min(12, j40hip_cpu_quota())); }();
+	const int parse_threads = parse_thread_count();
 	inner->frame = src ? j40hip_frame_parse_streamed(inner->buf, inner->size, parse_threads, 1u, FileSource::need, FileSource::have_now, src.get(), &err)
 	                   : j40hip_frame_parse_ex(inner->buf, inner->size, parse_threads, 1u, &err);
 	if (read_failed()) return inner->err;   // (also: the rest of the file is there from here on -- the upload copies the codestream)
@@ -372,6 +412,7 @@ int j40_next_frame(j40_image *image) {
 	j40__inner *inner;
 	if (check_image(image, O_next_frame, &inner)) return 0;
 	if (advance(inner, O_next_frame)) return 0;
+	if (inner->seq) return next_sequence_frame(inner, O_next_frame);   // once per displayed frame, then 0
 	if (inner->rendered) return 0;  // single-frame images: the second call reports "no more frames" (j40.h:8390)
 	inner->rendered = 1;
 	return 1;

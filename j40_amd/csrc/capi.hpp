@@ -47,6 +47,28 @@ struct j40hip_frame {
 	} views;
 };
 
+// the object behind j40hip_sequence (include/j40hip.h): the index over the coded frames of one codestream and, once asked for, their
+// frame handles. The device half (canvas slots, staging image, where the playback stands) lives in device/runtime_seq.hip.
+struct j40hip_sequence_device;
+struct j40hip_sequence {
+	const uint8_t *cs = nullptr;     // the codestream (inside the caller's buffer, or cs_storage: a container's boxes put together once)
+	size_t cs_size = 0;
+	std::vector<uint8_t> cs_storage;
+	j40hip::ImageMeta im;
+	struct Row {
+		j40hip::FrameHeader fh;
+		size_t offset = 0, end = 0, first_section = 0;   // bytes of the codestream: the frame header, the end of the last section, the first section
+		uint32_t code = 0;           // what the frame is refused with; nothing behind such a frame is known
+		bool shown = false, saved = false;
+	};
+	std::vector<Row> rows;
+	std::vector<j40hip_frame *> frames;   // [rows.size()], parsed when first asked for
+	int threads = 1; uint32_t flags = 0;
+	int32_t output_format = J40HIP_U8X4;
+	j40hip_sequence_device *dev = nullptr;
+};
+extern "C" void j40hip_sequence_release_device(j40hip_sequence *s);   // device/runtime_seq.hip
+
 // the alpha mode in force: kept only where asked for (or J40HIP_ALPHA=1) AND the frame is one keep mode serves (plan_build.cpp:
 // alpha_keep_scope) -- with the environment variable alone every other frame decodes opaque as before
 inline bool j40hip_alpha_kept(const j40hip_frame *h) {

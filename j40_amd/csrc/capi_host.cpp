@@ -144,6 +144,100 @@ j40hip_frame *j40hip_frame_from_vardct_view(const j40hip_vardct_view *v, uint32_
 	return h;
 }
 
+// ---- frame sequences: the index over the coded frames of one codestream (include/j40hip.h) ----
+j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads, uint32_t flags, uint32_t *err) {
+	j40hip_sequence *s = new j40hip_sequence();
+	uint32_t code = 0;
+	try {
+		extract_codestream((const uint8_t *) buf, size, &s->cs, &s->cs_size, &s->cs_storage);
+		s->threads = threads < 1 ? 1 : threads > 16 ? 16 : threads; s->flags = flags;
+		size_t at = 0;
+		parse_image_header(s->cs, s->cs_size, &s->im, &at);
+		for (;;) {
+			j40hip_sequence::Row row;
+			Toc toc;
+			row.offset = at;
+			try {
+				parse_sequence_frame_header(s->cs, s->cs_size, at, s->im, &row.fh, &toc);
+				row.first_section = at + toc.first_offset; row.end = at + toc.end_offset;
+				// (a frame whose sections the stream does not hold to their end: whatever follows it cannot be found)
+				if (row.end > s->cs_size) row.code = E4("shrt");
+				// the rendered pixels carry colour and alpha together: one source slot for both
+				if (!row.fh.full_frame) for (const FrameHeader::Blend &b : row.fh.ec_blend) if (b.src_ref != row.fh.blend.src_ref) row.code = row.code ? row.code : (uint32_t) E4("TODO");
+			} catch (const DecodeError &e) { row.code = e.code; }
+			if (s->rows.empty()) {
+				if (row.code) raise(row.code);
+				J40HIP_SHOULD(!row.fh.is_last, "Usq?");   // not a sequence: j40hip_frame_parse's
+			}
+			row.shown = !row.code && (row.fh.duration > 0 || row.fh.is_last);
+			row.saved = !row.code && !row.fh.is_last && (row.fh.duration == 0 || row.fh.save_as_ref != 0);
+			s->rows.push_back(row);
+			if (row.code || row.fh.is_last) break;
+			at = row.end;
+		}
+		s->frames.assign(s->rows.size(), nullptr);
+	} catch (const DecodeError &e) { code = e.code; }
+	catch (const std::exception &) { code = E4("!mem"); }
+	if (err) *err = code;
+	if (code) { delete s; return nullptr; }
+	return s;
+}
+
+void j40hip_sequence_free(j40hip_sequence *s) {
+	if (!s) return;
+	j40hip_sequence_release_device(s);
+	for (j40hip_frame *f : s->frames) j40hip_frame_free(f);
+	delete s;
+}
+int64_t j40hip_sequence_num_frames(const j40hip_sequence *s) { return s ? (int64_t) s->rows.size() : 0; }
+int64_t j40hip_sequence_num_shown(const j40hip_sequence *s) {
+	int64_t n = 0;
+	if (s) for (const j40hip_sequence::Row &r : s->rows) n += r.shown;
+	return n;
+}
+void j40hip_sequence_frame_info(const j40hip_sequence *s, int64_t k, int64_t *out) {
+	if (!out) return;
+	memset(out, 0, sizeof(int64_t) * 21);
+	if (!s || k < 0 || k >= (int64_t) s->rows.size()) return;
+	const j40hip_sequence::Row &r = s->rows[(size_t) k];
+	out[0] = r.fh.x0; out[1] = r.fh.y0; out[2] = r.fh.width; out[3] = r.fh.height;
+	out[4] = r.fh.duration; out[5] = r.fh.is_last; out[6] = r.shown; out[7] = r.fh.type;
+	out[8] = r.fh.blend.mode; out[9] = r.fh.blend.src_ref; out[10] = r.fh.save_as_ref; out[11] = r.saved;
+	out[12] = (int64_t) r.offset; out[13] = (int64_t) r.end; out[14] = (int64_t) r.first_section; out[15] = r.code;
+	out[16] = s->im.anim_tps_num; out[17] = s->im.anim_tps_den; out[18] = s->im.anim_loops; out[19] = s->im.width; out[20] = s->im.height;
+}
+
+j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err) {
+	if (err) *err = 0;
+	if (!s || k < 0 || k >= (int64_t) s->rows.size()) { if (err) *err = E4("rnge"); return nullptr; }
+	if (s->frames[(size_t) k]) return s->frames[(size_t) k];
+	const j40hip_sequence::Row &r = s->rows[(size_t) k];
+	if (r.code && r.code != (uint32_t) E4("shrt")) { if (err) *err = r.code; return nullptr; }   // (a frame cut short fails where its parse or its sections run out)
+	j40hip_frame *h = new j40hip_frame();
+	uint32_t code = 0;
+	try {
+		J40HIP_SHOULD(r.offset < s->cs_size, "shrt");
+		// the frame's own bytes, from its header to the end of its last section (the last frame: to the end of the codestream, which is
+		// what a single-section frame may read)
+		const size_t end = r.fh.is_last || r.code ? s->cs_size : std::min(r.end, s->cs_size);
+		h->cs_storage.assign(s->cs + r.offset, s->cs + end);
+		h->cs_size = h->cs_storage.size();
+		h->cs_storage.resize(h->cs_size + 16, 0);   // (kernels read the bit window up to 16 bytes past a section)
+		h->cs = h->cs_storage.data();
+		h->bare_codestream = true;
+		h->frame.defer_lf_tail = (s->flags & 1u) != 0;
+		h->frame.seq_im = &s->im;
+		parse_frame(h->cs, h->cs_size, &h->frame, s->threads);
+		h->threads = s->threads;
+		h->output_format = s->output_format;
+	} catch (const DecodeError &e) { code = e.code; }
+	catch (const std::exception &) { code = E4("!mem"); }
+	h->frame.seq_im = nullptr;   // (copied into the frame)
+	if (err) *err = code;
+	if (code) { delete h; return nullptr; }
+	return s->frames[(size_t) k] = h;
+}
+
 uint32_t j40hip_frame_after_frame_status(const j40hip_frame *h) {
 	if (!h || h->frame.lf_only) return 0;   // (an LF-only parse never looks behind the LF sections)
 	const size_t end = h->frame.toc.end_offset;

@@ -97,4 +97,10 @@ void launch_region_index(const DevVarblock *sorted, uint32_t count, int32_t shif
 void launch_region_gather(const DevVarblock *sorted, const uint32_t *index, const uint32_t *seg_start, const RegionCover &cover, const int32_t *class_start, DevVarblock *list, uint32_t *order, hipStream_t stream);
 void launch_region_crop(const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int32_t w, int32_t h, int32_t pixel_bytes, hipStream_t stream);
 
+// frame sequences (device/compose_kernels.hip, compose_dev.h): the frame image `frm` (w x h pixels, its pixel (0, 0) canvas pixel
+// (x0, y0); any offsets, clipped here) onto the W x H canvas at `out`; outside the rectangle the pixels of `src` or, src null, the empty
+// pixel (its bytes as one or two little-endian words). src == out: only the rectangle is written. Every row pixel-aligned.
+void launch_frame_compose(uint8_t *out, size_t out_stride, const uint8_t *src, size_t src_stride, const uint8_t *frm, size_t frm_stride, int32_t W, int32_t H,
+		int32_t x0, int32_t y0, int32_t w, int32_t h, uint32_t empty_lo, uint32_t empty_hi, int32_t pixel_bytes, hipStream_t stream);
+
 } // namespace j40hip

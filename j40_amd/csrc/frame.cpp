@@ -170,9 +170,9 @@ static void read_image_metadata(BitReader &br, ImageMeta *im) {  // j40.h:3104
 			if (br.u(1)) { int32_t w, h; read_size_header(br, &w, &h); }
 			if (br.u(1)) J40HIP_RAISE("TODO");  // preview
 			if (br.u(1)) {  // animation
-				(void) br.u32(100, 0, 1000, 0, 1, 10, 1, 30);
-				(void) br.u32(1, 0, 1001, 0, 1, 8, 1, 10);
-				(void) br.u32_64(0, 0, 0, 3, 0, 16, 0, 32);
+				im->anim_tps_num = br.u32(100, 0, 1000, 0, 1, 10, 1, 30);
+				im->anim_tps_den = br.u32(1, 0, 1001, 0, 1, 8, 1, 10);
+				im->anim_loops = (int64_t) br.u32_64(0, 0, 0, 3, 0, 16, 0, 32);
 				im->have_animation = true;
 				im->anim_have_timecodes = br.u(1);
 			}
@@ -259,12 +259,15 @@ static void read_image_metadata(BitReader &br, ImageMeta *im) {  // j40.h:3104
 // ------------------------------------------------------------------------------------------------
 // frame header (j40.h:5163)
 
-static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f) {
+// `sequence`: the frame belongs to a frame sequence, which refuses the types it does not serve as soon as it has read them
+static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f, bool sequence = false) {
 	f->width = im.width; f->height = im.height;
+	f->ec_blend.assign(im.ec.size(), FrameHeader::Blend());
 	br.zero_pad_to_byte();
 	if (!br.u(1)) {
 		bool full_frame = true;
 		f->type = (int32_t) br.u(2);
+		if (sequence) J40HIP_SHOULD(f->type == 0 || f->type == 3, "TODO");
 		f->is_modular = br.u(1);
 		uint64_t flags = br.u64();
 		f->has_noise = flags & 1; f->has_patches = flags >> 1 & 1; f->has_splines = flags >> 4 & 1;
@@ -308,13 +311,15 @@ static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f
 		int64_t duration = 0;
 		if (f->type == 0 || f->type == 3) {
 			for (int32_t i = -1; i < (int32_t) im.ec.size(); ++i) {
+				FrameHeader::Blend &b = i < 0 ? f->blend : f->ec_blend[(size_t) i];
 				int32_t mode = br.u32(0, 0, 1, 0, 2, 0, 3, 2);
 				if (i < 0) blend_mode0 = mode;
+				b.mode = (int8_t) mode;
 				if (!im.ec.empty()) {
-					if (mode == 2 || mode == 3) { (void) br.u32(0, 0, 1, 0, 2, 0, 3, 3); (void) br.u(1); }
-					else if (mode == 4) (void) br.u(1);
+					if (mode == 2 || mode == 3) { b.alpha_chan = (int8_t) br.u32(0, 0, 1, 0, 2, 0, 3, 3); b.clamp = (int8_t) br.u(1); }
+					else if (mode == 4) b.clamp = (int8_t) br.u(1);
 				}
-				if (!full_frame || mode != 0) (void) br.u(2);
+				if (!full_frame || mode != 0) b.src_ref = (int8_t) br.u(2);
 			}
 			if (im.have_animation) {
 				duration = br.u32_64(0, 0, 1, 0, 0, 8, 0, 32);
@@ -325,7 +330,8 @@ static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f
 			f->is_last = false;
 		}
 		if (f->type != 1 && !f->is_last) save_as_ref = (int32_t) br.u(2);
-		if (f->type == 2 || (full_frame && (f->type == 0 || f->type == 3) && blend_mode0 == 0 && (duration == 0 || save_as_ref != 0) && !f->is_last)) (void) br.u(1);
+		if (f->type == 2 || (full_frame && (f->type == 0 || f->type == 3) && blend_mode0 == 0 && (duration == 0 || save_as_ref != 0) && !f->is_last)) f->save_before_ct = br.u(1);
+		f->full_frame = full_frame; f->duration = duration; f->save_as_ref = save_as_ref;
 		skip_name(br);
 		{   // RestorationFilter. The reference reads the conditional fields even when all_default is
 			// set (j40.h:5339-5366); a drop-in has to consume the same bits.
@@ -385,6 +391,7 @@ static void read_toc(BitReader &br, const FrameHeader &fh, Toc *toc) {
 	br.zero_pad_to_byte();
 	size_t off = br.byte_position();
 	for (Section &s : sections) { s.offset = off; off += s.size; }
+	toc->first_offset = sections.empty() ? off : sections[0].offset;
 	toc->end_offset = off;
 	if (nsections == 1) { toc->single = true; toc->single_section = sections[0]; return; }
 	if (!lehmer.empty()) apply_permutation(sections.data(), lehmer);
@@ -794,15 +801,43 @@ static void skip_icc(BitReader &br) {
 
 // signature, image and frame headers, TOC (sections clipped to the bytes that exist), the LfGroups' geometry
 // `limit`: how much of the codestream's cs_size bytes may be read (streaming input: what has arrived; else cs_size)
+static void read_image_header(BitReader &br, ImageMeta *im) {
+	J40HIP_SHOULD(br.u(16) == 0x0aff, "!jxl");
+	read_image_metadata(br, im);
+	if (im->want_icc) skip_icc(br);
+}
+void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame) {
+	BitReader br(cs, cs_size);
+	read_image_header(br, im);
+	br.zero_pad_to_byte();
+	*first_frame = br.byte_position();
+}
+uint32_t sequence_refusal(const FrameHeader &fh) {
+	bool ok = (fh.type == 0 || fh.type == 3) && !fh.use_lf_frame && fh.blend.mode == 0;
+	for (const FrameHeader::Blend &b : fh.ec_blend) ok = ok && b.mode == 0;
+	return ok ? 0 : (uint32_t) E4("TODO");
+}
+void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, FrameHeader *fh, Toc *toc) {
+	J40HIP_SHOULD(offset < cs_size, "shrt");
+	BitReader br(cs + offset, cs_size - offset);
+	read_frame_header(br, im, fh, true);
+	if (uint32_t e = sequence_refusal(*fh)) raise(e);
+	read_toc(br, *fh, toc);
+}
+
 static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size, Frame *f) {
 	memset(f->order_has_lehmer, 0, sizeof f->order_has_lehmer);
 	BitReader br(cs, limit);
-	J40HIP_SHOULD(br.u(16) == 0x0aff, "!jxl");
-	read_image_metadata(br, &f->im);
-	if (f->im.want_icc) skip_icc(br);
-	read_frame_header(br, f->im, &f->fh);
-	J40HIP_SHOULD(f->fh.is_last, "TODO");
-	J40HIP_SHOULD(f->fh.type == 0, "TODO");
+	if (f->seq_im) {   // a sequence's member: its bytes start at the frame header
+		f->im = *f->seq_im;
+		read_frame_header(br, f->im, &f->fh, true);
+		if (uint32_t e = sequence_refusal(f->fh)) raise(e);
+	} else {
+		read_image_header(br, &f->im);
+		read_frame_header(br, f->im, &f->fh);
+		J40HIP_SHOULD(f->fh.is_last, "TODO");
+		J40HIP_SHOULD(f->fh.type == 0, "TODO");
+	}
 	read_toc(br, f->fh, &f->toc);
 	{   // a truncated codestream fails where the reference fails: in the first section (in reading order) that
 		// needs the missing bytes, not up front. Sections are clipped to the bytes that exist; readers raise "shrt".

@@ -24,6 +24,7 @@ struct ImageMeta {
 	int32_t width = 0, height = 0;
 	int32_t bpp = 8, exp_bits = 0;
 	bool have_animation = false, anim_have_timecodes = false;
+	int32_t anim_tps_num = 0, anim_tps_den = 0; int64_t anim_loops = 0;   // ticks per second as a fraction, repetitions (0: for ever); with have_animation
 	bool modular_16bit_buffers = true;
 	std::vector<ExtraChannel> ec;
 	bool xyb_encoded = true, want_icc = false, grey = false;
@@ -45,6 +46,14 @@ struct FrameHeader {
 	int32_t x_qm_scale = 3, b_qm_scale = 2;
 	int32_t num_passes = 1;
 	int32_t x0 = 0, y0 = 0, width = 0, height = 0;
+	// how the frame goes onto the canvas (j40.h:5297-5336). The reference reads these and drops them; frame sequences (capi.hpp: j40hip_sequence) keep them
+	struct Blend { int8_t mode = 0, alpha_chan = 0, clamp = 0, src_ref = 0; };
+	Blend blend;                          // the colour channels'
+	std::vector<Blend> ec_blend;          // every extra channel's
+	bool full_frame = true;               // the frame covers the canvas
+	int64_t duration = 0;                 // ticks (animations)
+	int32_t save_as_ref = 0;
+	bool save_before_ct = false;
 	int32_t grows = 0, gcolumns = 0, ggrows = 0, ggcolumns = 0;
 	int64_t num_groups = 0, num_lf_groups = 0;
 	// RestorationFilter as the reference parses it (defaults j40.h:5196-5208, fields j40.h:5339-5366). The reference reads it and never
@@ -67,6 +76,7 @@ struct Toc {
 	                                      // reference, which reads such a frame from its main state (no section boundary) ...
 	size_t single_declared_end = 0;       // ... and compares where it ended with the TOC entry afterwards (j40__end_of_frame, j40.h:7796)
 	Section lf_global, hf_global;
+	size_t first_offset = 0;              // where the first stored section starts
 	std::vector<Section> lf_groups;       // [num_lf_groups]
 	std::vector<Section> pass_groups;     // [num_passes * num_groups], pass-major
 	size_t end_offset = 0;
@@ -168,13 +178,17 @@ struct Frame {
 	// The LF preview (J40HIP_PARSE_LF_ONLY): headers, TOC, LfGlobal and the LfGroup sections only -- HfGlobal and the pass groups are
 	// never read nor asked for (frames with several sections; a single section is read whole). VarDCT frames only. Set before parse_frame.
 	bool lf_only = false;
+	// A member of a frame sequence (capi.hpp: j40hip_sequence): the bytes handed to parse_frame start at this frame's header, byte aligned, and the
+	// image metadata is this one instead of a parsed one. Frames that are not last, and frames of type 3, are taken; what a sequence
+	// does not serve (sequence_refusal) is "TODO". Set before parse_frame.
+	const ImageMeta *seq_im = nullptr;
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
 	Frame with_same_inputs() const {
 		Frame g;
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
-		g.lf_only = lf_only;
+		g.lf_only = lf_only; g.seq_im = seq_im;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section
@@ -186,6 +200,15 @@ struct Frame {
 // split over several boxes it is reassembled into `storage`
 // stray_tail (optional): 1..7 when that many bytes follow the last box of a container -- too few for a box header
 void extract_codestream(const uint8_t *data, size_t size, const uint8_t **cs, size_t *cs_size, std::vector<uint8_t> *storage, int *stray_tail = nullptr);
+
+// signature, image metadata and ICC profile of a codestream: everything in front of the first frame header. *first_frame: the byte
+// the first frame header starts at
+void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame);
+// header and TOC of the frame that starts at byte `offset` of the codestream, for a sequence's index: nothing behind the TOC is
+// read. The TOC's offsets count from `offset`. Raises what the header or the TOC raise, "TODO" for what sequence_refusal refuses.
+void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, FrameHeader *fh, Toc *toc);
+// 0, or "TODO": the frame is of a kind a sequence does not serve (types 1 and 2, use_lf_frame, a blend mode other than Replace)
+uint32_t sequence_refusal(const FrameHeader &fh);
 
 // parses headers, TOC, LfGlobal, HfGlobal and every LfGroup section. `threads` > 1 decodes LfGroup
 // sections concurrently (they are independent given LfGlobal)

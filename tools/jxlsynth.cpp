@@ -36,6 +36,82 @@ struct Options {
 	std::string gets(const char *k, const char *def) const { auto it = kv.find(k); return it == kv.end() ? def : it->second; }
 };
 
+// ------------------------------------------------------------------------------------------------
+// several frames in one codestream (frames=N; main() runs the mode's writer once per coded frame). While `g_seq` is set a writer
+// produces one coded frame of the sequence instead of a file: the image header carries the canvas' size (and the animation header),
+// the frame header the frame's crop, source slot, duration, is_last and save_as_reference, and the bytes are appended to `cs`
+// (signature and image header with the first frame only). With none of the sequence options the writers never see it.
+struct SeqFrame {
+	int canvas_w = 0, canvas_h = 0;
+	bool anim = false;                // ImageMetadata with the animation header: 10/1 ticks per second, 0 loops
+	bool first = true;                // this frame opens the codestream: signature and image header are written
+	bool have_crop = false; int x0 = 0, y0 = 0;   // (its width and height are the writer's W and H)
+	int blend = 0, src = 0, save = 0;
+	int ec_blend = 0, ec_src = 0;     // the extra channels' blend mode and source slot (the colour channels' unless ecblends= / ecsrcs= say otherwise)
+	long long duration = 0;
+	bool is_last = true;
+	std::vector<uint8_t> *cs = nullptr;   // the codestream so far
+	size_t first_section = 0;         // out: where this frame's first section starts in `cs`
+};
+static SeqFrame *g_seq = nullptr;
+
+// ImageMetadata.extra_fields (j40.h:3147-3163): 0, or for an animation: orientation 1, no intrinsic size, no preview, the animation
+// header (tps 10 / 1, loops 0, no timecodes)
+static void write_extra_fields(BitWriter &cs) {
+	if (!g_seq || !g_seq->anim) { cs.put(0, 1); return; }
+	cs.put(1, 1);
+	cs.put(0, 3); cs.put(0, 1); cs.put(0, 1);   // orientation - 1, have_intrinsic_size, have_preview
+	cs.put(1, 1);                                   // have_animation
+	cs.put(2, 2); cs.put(9, 10);                    // tps_numerator U32(100, 1000, 1 + u(10), 1 + u(30)) = 10
+	cs.put(0, 2);                                   // tps_denominator U32(1, 1001, 1 + u(8), 1 + u(10)) = 1
+	cs.put(0, 2);                                   // num_loops U32(0, u(3), u(16), u(32)) = 0
+	cs.put(0, 1);                                   // have_timecodes
+}
+// ... and what they add behind ColourEncoding: ToneMapping.all_default (j40.h:3234)
+static void write_tone_mapping(BitWriter &cs) { if (g_seq && g_seq->anim) cs.put(1, 1); }
+
+// the frame header from have_crop to save_before_color_transform (j40.h:5285-5336). Outside a sequence: no crop, Replace, is_last.
+static void write_frame_placement(BitWriter &cs, int num_ec, int frame_w, int frame_h) {
+	auto crop_u32 = [&](long long v) { cs.u32(v, 0, 8, 256, 11, 2304, 14, 18688, 30); };
+	auto pack_signed = [](int v) { return v >= 0 ? 2ll * v : -2ll * v - 1; };
+	if (!g_seq) {
+		cs.put(0, 1);                       // have_crop
+		for (int i = -1; i < num_ec; ++i) cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 2);  // blend mode: replace (the frame's, then each extra channel's, j40.h:5299)
+		cs.put(1, 1);                       // is_last
+		return;
+	}
+	const SeqFrame &q = *g_seq;
+	bool full_frame = true;
+	cs.put(q.have_crop ? 1 : 0, 1);
+	if (q.have_crop) {
+		crop_u32(pack_signed(q.x0)); crop_u32(pack_signed(q.y0)); crop_u32(frame_w); crop_u32(frame_h);
+		full_frame = q.x0 <= 0 && q.y0 <= 0 && frame_w + q.x0 >= q.canvas_w && frame_h + q.y0 >= q.canvas_h;
+	}
+	for (int i = -1; i < num_ec; ++i) {
+		const int blend = i < 0 ? q.blend : q.ec_blend, src = i < 0 ? q.src : q.ec_src;
+		cs.u32(blend, 0, 0, 1, 0, 2, 0, 3, 2);
+		if (num_ec > 0) {
+			if (blend == 2 || blend == 3) { cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 3); cs.put(0, 1); }   // alpha channel 0, no clamp
+			else if (blend == 4) cs.put(0, 1);
+		}
+		if (!full_frame || blend != 0) cs.put((uint64_t) src, 2);
+	}
+	if (q.anim) {   // duration U32(0, 1, u(8), u(32))
+		if (q.duration == 0) cs.put(0, 2); else if (q.duration == 1) cs.put(1, 2); else if (q.duration < 256) { cs.put(2, 2); cs.put((uint64_t) q.duration, 8); } else { cs.put(3, 2); cs.put((uint64_t) q.duration, 32); }
+	}
+	cs.put(q.is_last ? 1 : 0, 1);
+	if (!q.is_last) cs.put((uint64_t) q.save, 2);
+	if (full_frame && q.blend == 0 && (q.duration == 0 || q.save != 0) && !q.is_last) cs.put(0, 1);   // save_before_color_transform
+}
+
+// the frame a writer has finished goes behind the codestream so far (every frame ends on a byte: its sections are whole bytes)
+static void seq_append(const BitWriter &frame, const std::vector<std::vector<uint8_t>> &sections) {
+	size_t stored = 0;
+	for (const auto &sec : sections) stored += sec.size();
+	g_seq->cs->insert(g_seq->cs->end(), frame.bytes.begin(), frame.bytes.end());
+	g_seq->first_section = g_seq->cs->size() - stored;
+}
+
 // wp=random|max|zero|<eleven numbers>: weighted-predictor parameters other than the defaults (false: the option is absent)
 static bool parse_wp(const Options &opt, uint64_t seed, WPParams &wp_base, const char *mode) {
 	if (!opt.kv.count("wp")) return false;
@@ -986,16 +1062,19 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 
 	// ---- codestream ----
 	BitWriter cs;
-	cs.put(0xff, 8); cs.put(0x0a, 8);
-	write_size_header(cs, W, H);
+	const bool seq_anim = g_seq && g_seq->anim;
+	if (g_seq && (opt.geti("icc", 0) || !nonzero_header)) die("vardct: frames= wants fullheader=1 and no icc");
 	const int icc_bytes = opt.geti("icc", 0);                // > 0: ColourEncoding with want_icc and an ICC stream of that many coded bytes
 	const int img_bpp = opt.geti("bpp", 8);   // 9..15: the renderer's scaling to 8 bits and the long way through the transfer curve get work
 	if (img_bpp != 8 && icc_bytes) die("vardct: bpp does not combine with icc here");
 	const int noxyb = opt.geti("noxyb", 0);
 	if (noxyb && (!with_alpha || icc_bytes || !nonzero_header || x_qm != 3 || b_qm != 2)) die("vardct: noxyb wants alpha=1 fullheader=1 and the default qm scales");
+	if (!g_seq || g_seq->first) {
+	cs.put(0xff, 8); cs.put(0x0a, 8);
+	write_size_header(cs, g_seq ? g_seq->canvas_w : W, g_seq ? g_seq->canvas_h : H);
 	if (with_alpha && (img_bpp != 8 || ec_extra || alpha_bpp != 8 || alpha_assoc)) {
 		cs.put(0, 1);                       // ImageMetadata: not all_default
-		cs.put(0, 1);                       // no extra fields
+		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		write_bit_depth(cs, img_bpp);
 		cs.put(1, 1);                       // modular_16bit_buffers
 		if (num_ec == 1) cs.put(1, 2); else { cs.put(2, 2); cs.put((uint64_t) (num_ec - 2), 4); }   // num_extra_channels (j40.h:3170)
@@ -1017,16 +1096,18 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		}
 		cs.put(noxyb ? 0 : 1, 1);           // xyb_encoded
 		cs.put(1, 1);                       // ColourEncoding.all_default
+		write_tone_mapping(cs);
 		cs.put(0, 2);                       // extensions
 		cs.put(1, 1);                       // default_m
-	} else if (img_bpp != 8) {
+	} else if (img_bpp != 8 || (seq_anim && !with_alpha)) {
 		cs.put(0, 1);                       // ImageMetadata: not all_default
-		cs.put(0, 1);                       // no extra fields
+		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		write_bit_depth(cs, img_bpp);
 		cs.put(1, 1);                       // modular_16bit_buffers
 		cs.put(0, 2);                       // no extra channels
 		cs.put(1, 1);                       // xyb_encoded
 		cs.put(1, 1);                       // ColourEncoding.all_default
+		write_tone_mapping(cs);
 		cs.put(0, 2);                       // extensions
 		cs.put(1, 1);                       // default_m
 	} else if (!icc_bytes && !with_alpha) {
@@ -1034,17 +1115,18 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(1, 1);   // default_m
 	} else if (!icc_bytes) {
 		cs.put(0, 1);                       // ImageMetadata: not all_default
-		cs.put(0, 1);                       // no extra fields
+		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		cs.put(0, 1); cs.put(0, 2);         // integer samples, 8 bits
 		cs.put(1, 1);                       // modular_16bit_buffers
 		cs.put(1, 2); cs.put(1, 1);         // one extra channel, d_alpha
 		cs.put(noxyb ? 0 : 1, 1);           // xyb_encoded (noxyb=1: the reference runs the XYB inverse on VarDCT frames regardless, j40.h:7206)
 		cs.put(1, 1);                       // ColourEncoding.all_default
+		write_tone_mapping(cs);
 		cs.put(0, 2);                       // extensions
 		cs.put(1, 1);                       // default_m
 	} else {
 		cs.put(0, 1);                       // ImageMetadata: not all_default
-		cs.put(0, 1);                       // no extra fields
+		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		cs.put(0, 1); cs.put(0, 2);         // integer samples, 8 bits
 		cs.put(1, 1);                       // modular_16bit_buffers
 		cs.put(0, 2);                       // no extra channels
@@ -1052,9 +1134,11 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(0, 1);                       // ColourEncoding: not all_default
 		cs.put(1, 1);                       // want_icc
 		cs.put(0, 2);                       // colour_space = RGB (enum selector 0)
+		write_tone_mapping(cs);
 		cs.put(0, 2);                       // extensions
 		cs.put(1, 1);                       // default_m
 		write_icc_stream(cs, rng, icc_bytes);
+	}
 	}
 	cs.pad();       // frame header starts byte aligned (j40.h:5228)
 	if (!nonzero_header) cs.put(1, 1);  // FrameHeader.all_default
@@ -1072,9 +1156,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 1);                  // num_ds = 0
 			for (int i = 0; i < num_passes - 1; ++i) cs.put(0, 2);  // shift[i]
 		}
-		cs.put(0, 1);                       // have_crop
-		for (int i = -1; i < num_ec; ++i) cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 2);  // blend mode: replace (the frame's, then each extra channel's, j40.h:5299)
-		cs.put(1, 1);                       // is_last
+		write_frame_placement(cs, num_ec, W, H);   // have_crop, blend modes, is_last
 		cs.u32(0, 0, 0, 0, 4, 16, 5, 48, 10);  // name length 0
 		// RestorationFilter (j40.h:5339-5366). gab=1: Gaborish with the default weights, gab=2: custom weights; epf=1..3: iterations of the
 		// edge-preserving filter, always with a custom sharpness table (the default table's first entry is 0, which the reference's
@@ -1107,6 +1189,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	}
 	// TOC (j40.h:5505-5531)
 	write_toc_and_sections(cs, sections, opt.geti("permute", 0), rng, opt.geti("slack", 0));
+	if (g_seq) { seq_append(cs, sections); return 0; }
 
 	std::vector<uint8_t> file;
 	if (!container) file = cs.bytes;
@@ -1701,10 +1784,12 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 
 	// ---- codestream ----
 	BitWriter cs;
+	if (g_seq && (opt.geti("icc", 0) || repeat > 1)) die("modular: frames= does not combine with icc or repeat");
+	if (!g_seq || g_seq->first) {
 	cs.put(0xff, 8); cs.put(0x0a, 8);
-	write_size_header(cs, Wfull, Hfull);
+	write_size_header(cs, g_seq ? g_seq->canvas_w : Wfull, g_seq ? g_seq->canvas_h : Hfull);
 	cs.put(0, 1);                       // ImageMetadata: not all_default
-	cs.put(0, 1);                       // no extra fields
+	write_extra_fields(cs);             // no extra fields (an animation: its header)
 	write_bit_depth(cs, bpp);
 	cs.put(1, 1);                       // modular_16bit_buffers
 	{   // num_extra_channels U32(0, 1, 2 + u(4), 1 + u(12)), then one ExtraChannelInfo each (j40.h:3247-3290)
@@ -1721,14 +1806,16 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	}
 	// xyb=1 / ycbcr=1: the frame is flagged XYB / YCbCr; the reference applies no colour transform to Modular
 	// frames (j40.h:8209-8210, 7910) and renders the three channels as they are
-	const int flag_xyb = opt.geti("xyb", 0), flag_ycbcr = opt.geti("ycbcr", 0);
-	cs.put(flag_xyb ? 1 : 0, 1);        // xyb_encoded
+	cs.put(opt.geti("xyb", 0) ? 1 : 0, 1);   // xyb_encoded
 	const int icc_bytes = opt.geti("icc", 0);
 	if (!icc_bytes) cs.put(1, 1);       // ColourEncoding.all_default (sRGB)
 	else { cs.put(0, 1); cs.put(1, 1); cs.put(0, 2); }   // want_icc, colour_space = RGB
+	write_tone_mapping(cs);
 	cs.put(0, 2);                       // extensions
 	cs.put(1, 1);                       // default_m
 	if (icc_bytes) write_icc_stream(cs, rng, icc_bytes);
+	}
+	const int flag_xyb = opt.geti("xyb", 0), flag_ycbcr = opt.geti("ycbcr", 0);
 	cs.pad();
 	cs.put(0, 1);                       // FrameHeader: not all_default
 	cs.put(0, 2);                       // regular frame
@@ -1744,14 +1831,12 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 1);                  // num_ds = 0
 		for (int i = 0; i < num_passes - 1; ++i) cs.put(0, 2);  // shift[i]
 	}
-	cs.put(0, 1);                       // have_crop
-	cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 2);  // blend mode (colour)
-	for (int k = 0; k < extra + (alpha ? 1 : 0); ++k) cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 2);  // blend mode (extra channels)
-	cs.put(1, 1);                       // is_last
+	write_frame_placement(cs, extra + (alpha ? 1 : 0), Wfull, Hfull);   // have_crop, blend modes (colour, extra channels), is_last
 	cs.u32(0, 0, 0, 0, 4, 16, 5, 48, 10);
 	cs.put(0, 1); cs.put(0, 1); cs.put(0, 2); cs.u64(0);   // restoration: explicit, gab off, epf 0, no extensions
 	cs.u64(0);                          // frame extensions
 	write_toc_and_sections(cs, sections, opt.geti("permute", 0), rng, opt.geti("slack", 0));
+	if (g_seq) { seq_append(cs, sections); return 0; }
 	std::vector<uint8_t> file = cs.bytes;
 	if (container) {
 		static const uint8_t HEAD[32] = {0, 0, 0, 0x0c, 'J', 'X', 'L', ' ', 0x0d, 0x0a, 0x87, 0x0a, 0, 0, 0, 0x14, 'f', 't', 'y', 'p', 'j', 'x', 'l', ' ', 0, 0, 0, 0, 'j', 'x', 'l', ' '};
@@ -1807,13 +1892,102 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 }
 
 
+// ------------------------------------------------------------------------------------------------
+// frames=N: N coded frames under one image header of W x H (the canvas). Frame k's picture and statistics come from seed SEED + k and
+// its crop's size; every other option of the mode holds for each frame alike.
+//   anim=1             the image header carries the animation header (10/1 ticks per second, 0 loops) and every frame a duration
+//   durations=d0,d1,.. per-frame durations in ticks (default 1 with anim=1; without anim there is no such field: 0)
+//   crops=x,y,w,h;...  per-frame crops; an empty entry is the full frame
+//   srcs= saves=       per-frame source slots and save_as_reference values (default 0)
+//   blends=            per-frame blend mode, all channels alike (default 0, Replace: the only one a decoder here serves)
+//   ecblends= ecsrcs=  per-frame blend mode and source slot of the extra channels alone (default: the colour channels')
+//   only=k             coded frame k alone, as a last frame, under the same image header, with the same crop and the same section bytes
+// The last frame is is_last. stats=1 prints frames, shown, saved_slots and every frame's offsets instead of the mode's own statistics.
+static std::vector<std::string> split_list(const std::string &v, char sep) {
+	std::vector<std::string> out;
+	size_t at = 0;
+	if (v.empty()) return out;
+	for (;;) { const size_t e = v.find(sep, at); out.push_back(v.substr(at, e == std::string::npos ? e : e - at)); if (e == std::string::npos) break; at = e + 1; }
+	return out;
+}
+static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *out, const Options &opt_in) {
+	const int N = opt_in.geti("frames", 1), only = opt_in.geti("only", -1), container = opt_in.geti("container", 0);
+	if (N < 1 || N > 64) die("frames=1..64");
+	if (only >= N) die("only= names a frame the sequence does not have");
+	const bool anim = opt_in.geti("anim", 0) != 0;
+	const std::vector<std::string> durs = split_list(opt_in.gets("durations", ""), ','), crops = split_list(opt_in.gets("crops", ""), ';'),
+		srcs = split_list(opt_in.gets("srcs", ""), ','), saves = split_list(opt_in.gets("saves", ""), ','), blends = split_list(opt_in.gets("blends", ""), ','),
+		ecblends = split_list(opt_in.gets("ecblends", ""), ','), ecsrcs = split_list(opt_in.gets("ecsrcs", ""), ',');
+	if (!durs.empty() && !anim) die("durations= wants anim=1 (frames of a still have no duration)");
+	Options opt = opt_in;
+	for (const char *k : {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "container", "stats"}) opt.kv.erase(k);
+	if (vardct && !opt.kv.count("fullheader")) opt.kv["fullheader"] = "1";
+	auto at = [](const std::vector<std::string> &v, int k, int def) { return k < (int) v.size() && !v[(size_t) k].empty() ? atoi(v[(size_t) k].c_str()) : def; };
+	std::vector<uint8_t> cs;
+	std::string rows;
+	int shown = 0; unsigned saved_slots = 0;
+	for (int k = 0; k < N; ++k) {
+		SeqFrame q;
+		q.canvas_w = W; q.canvas_h = H; q.anim = anim; q.cs = &cs;
+		int fw = W, fh = H;
+		if (k < (int) crops.size() && !crops[(size_t) k].empty()) {
+			if (sscanf(crops[(size_t) k].c_str(), "%d,%d,%d,%d", &q.x0, &q.y0, &fw, &fh) != 4 || fw < 1 || fh < 1) die("crops=x,y,w,h;... (an empty entry: the full frame)");
+			q.have_crop = true;
+		}
+		q.blend = at(blends, k, 0); q.src = at(srcs, k, 0); q.save = at(saves, k, 0); q.duration = anim ? at(durs, k, 1) : 0;
+		q.ec_blend = at(ecblends, k, q.blend); q.ec_src = at(ecsrcs, k, q.src);
+		if (q.blend < 0 || q.blend > 4 || q.src < 0 || q.src > 3 || q.ec_blend < 0 || q.ec_blend > 4 || q.ec_src < 0 || q.ec_src > 3 || q.save < 0 || q.save > 3 || q.duration < 0) die("blends 0..4, srcs and saves 0..3, durations >= 0");
+		q.is_last = only >= 0 || k == N - 1;
+		if (q.duration > 0 || q.is_last) ++shown;
+		if (!q.is_last && (q.duration == 0 || q.save != 0)) saved_slots |= 1u << q.save;
+		if (only >= 0 && k != only) continue;
+		q.first = cs.empty();
+		g_seq = &q;
+		const int e = vardct ? run_vardct(fw, fh, seed + (uint64_t) k, out, opt) : run_modular(fw, fh, seed + (uint64_t) k, out, opt);
+		g_seq = nullptr;
+		if (e) return e;
+		// (the first frame's bytes start with the signature and the image header: its frame header is found by a reader, not here)
+		char tmp[160]; snprintf(tmp, sizeof tmp, "%s{\"frame\": %d, \"first_section\": %zu, \"end\": %zu}", rows.empty() ? "" : ", ", k, q.first_section, cs.size());
+		rows += tmp;
+	}
+	std::vector<uint8_t> file;
+	if (!container) file = cs;
+	else {   // ISOBMFF wrapping (j40.h:1479): one jxlc box, or (container=2) the codestream split over two jxlp boxes around another box
+		static const uint8_t HEAD[32] = {0, 0, 0, 0x0c, 'J', 'X', 'L', ' ', 0x0d, 0x0a, 0x87, 0x0a, 0, 0, 0, 0x14, 'f', 't', 'y', 'p', 'j', 'x', 'l', ' ', 0, 0, 0, 0, 'j', 'x', 'l', ' '};
+		file.assign(HEAD, HEAD + 32);
+		auto box = [&](const char *type, const uint8_t *p, size_t n, bool indexed, uint32_t idx) {
+			const size_t total = 8 + n + (indexed ? 4 : 0);
+			const uint8_t hd[8] = {(uint8_t) (total >> 24), (uint8_t) (total >> 16), (uint8_t) (total >> 8), (uint8_t) total, (uint8_t) type[0], (uint8_t) type[1], (uint8_t) type[2], (uint8_t) type[3]};
+			file.insert(file.end(), hd, hd + 8);
+			if (indexed) { const uint8_t ix[4] = {(uint8_t) (idx >> 24), (uint8_t) (idx >> 16), (uint8_t) (idx >> 8), (uint8_t) idx}; file.insert(file.end(), ix, ix + 4); }
+			file.insert(file.end(), p, p + n);
+		};
+		if (container == 1) box("jxlc", cs.data(), cs.size(), false, 0);
+		else {   // (the reference takes a jxlp index WITHOUT the top bit as the last one, j40.h:1557)
+			const size_t cut = cs.size() / 3;
+			static const uint8_t junk[5] = {1, 2, 3, 4, 5};
+			box("jxlp", cs.data(), cut, true, 0x80000000u);
+			box("xml ", junk, 5, false, 0);
+			box("jxlp", cs.data() + cut, cs.size() - cut, true, 1);
+		}
+	}
+	if (!write_file(out, file)) die("cannot write output");
+	if (opt_in.geti("stats", 0)) printf("{\"frames\": %d, \"shown\": %d, \"saved_slots\": %d, \"written\": [%s]}\n", only >= 0 ? 1 : N, only >= 0 ? 1 : shown, only >= 0 ? 0 : __builtin_popcount(saved_slots), rows.c_str());
+	fprintf(stderr, "%s %dx%d: %zu bytes, %d coded frame(s)%s\n", vardct ? "vardct" : "modular", W, H, file.size(), only >= 0 ? 1 : N, anim ? ", animation" : "");
+	return 0;
+}
+
 int main(int argc, char **argv) {
 	if (argc < 6) { fprintf(stderr, "usage: %s vardct|modular W H SEED OUT [key=value ...]\n", argv[0]); return 1; }
 	Options opt;
 	for (int i = 6; i < argc; ++i) { std::string a = argv[i]; size_t eq = a.find('='); if (eq == std::string::npos) die("options are key=value"); opt.kv[a.substr(0, eq)] = a.substr(eq + 1); }
 	int W = atoi(argv[2]), H = atoi(argv[3]); uint64_t seed = strtoull(argv[4], nullptr, 0);
 	if (W <= 0 || H <= 0) die("bad dimensions");
-	if (!strcmp(argv[1], "vardct")) return run_vardct(W, H, seed, argv[5], opt);
-	if (!strcmp(argv[1], "modular")) return run_modular(W, H, seed, argv[5], opt);
-	die("unknown mode");
+	const bool vardct = !strcmp(argv[1], "vardct");
+	if (!vardct && strcmp(argv[1], "modular")) die("unknown mode");
+	static const char *const SEQ_KEYS[] = {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only"};
+	bool sequence = false;
+	for (const char *k : SEQ_KEYS) sequence = sequence || opt.kv.count(k);
+	if (!sequence) return vardct ? run_vardct(W, H, seed, argv[5], opt) : run_modular(W, H, seed, argv[5], opt);
+	return run_sequence(vardct, W, H, seed, argv[5], opt);
 }
