@@ -40,7 +40,7 @@ build/libj40hip.so: $(HOST_OBJS) $(DEV_OBJS)
 # the stand-alone layout programs (below) belong to hostsim wherever tests/hostsim holds their source; the libraries do not need it
 LAYOUTMAIN = $(if $(wildcard tests/hostsim/mod_layout_main.cpp),build/mod_layout_main build/mod_layout_main_san)
 HOSTSIM_HDR = $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp) $(wildcard tests/hostsim/*.hpp)
-hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/libhostsim_compose.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN)
+hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/libhostsim_compose.so build/libhostsim_blend.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN)
 # test-only glue: parses a stream with the product's host parser, takes the plan view and hands it to
 # the CPU oracle (oracle/libj40oracle.so)
 build/liboracle_driver.so: tests/oracle_driver.c build/libj40hip.so oracle/hotpath_oracle.c include/j40hip.h
@@ -88,6 +88,11 @@ build/libhostsim_region.so: $(REGIONSIM_SRC) $(wildcard $(SRC)/device/*.h) $(wil
 build/libhostsim_compose.so: tests/hostsim/compose_sim.cpp $(SRC)/device/compose_dev.h $(SRC)/device/region_dev.h $(SRC)/device/plan.h
 	@mkdir -p build
 	$(CXX) $(HOSTSIM_FLAGS) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -o $@ tests/hostsim/compose_sim.cpp
+
+# ... and its blend modes (tests/test_blend.py): device/compose_dev.h's blend_row, the float32 arithmetic uncontracted as on the device
+build/libhostsim_blend.so: tests/hostsim/blend_sim.cpp $(SRC)/device/compose_dev.h $(SRC)/device/region_dev.h $(SRC)/device/plan.h
+	@mkdir -p build
+	$(CXX) $(HOSTSIM_FLAGS) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -o $@ tests/hostsim/blend_sim.cpp
 
 build/jxlsynth: tools/jxlsynth.cpp $(wildcard tools/*.hpp) $(SRC)/tables.cpp $(SRC)/device/special8_dev.h $(SRC)/device/idct_dev.h
 	@mkdir -p build

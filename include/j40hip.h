@@ -413,6 +413,14 @@ J40HIP_API uint32_t j40hip_batch_reset(j40hip_batch *b, j40hip_frame *const *fra
  *      beyond the canvas), any source slot, any save_as_reference; animations (have_animation, durations; timecodes skipped) and
  *      layers. Refused with "TODO", reported for the frame it comes from: any other blend mode, frame types 1 and 2, use_lf_frame, and
  *      whatever a single frame is refused for.
+ *      With J40HIP_SEQ_BLEND (or J40HIP_BLEND=1 in the environment) the blend modes Add, Blend, MulAdd and Mul are served as well,
+ *      for the colour channels and for the alpha channel the pixels carry (the first extra channel of type alpha), each with a mode
+ *      of its own; the entries of the other extra channels are not looked at, `clamp` is read and changes nothing (a rendered alpha
+ *      lies in [0, 1]). The arithmetic works on rendered pixels -- the slots' and the frame's, one float32 operation a step,
+ *      INTEGRATION.md "Several frames" states it in full -- so every blended layer rounds once: PARITY UNPINNED against a decoder
+ *      that keeps unrounded samples in its slots. Still "TODO" then: a Blend or MulAdd, of the colour channels or of that alpha
+ *      channel, whose alpha_chan is another channel; a source slot of any extra channel that differs from the colour channels'
+ *      (switch or not, for every entry that carries a slot: a cropped frame's, a full frame's with a mode other than Replace).
  *      A shown or saved canvas, per pixel: inside the frame's rectangle (x0, y0, w, h) clipped to the canvas the frame's pixel;
  *      elsewhere the pixel of slot src_ref_frame, or the empty pixel (0, 0, 0, A0) when that slot was never saved -- A0 = 0 when the
  *      decode renders an alpha channel (a Modular image that has one, a VarDCT image in keep-alpha mode), full scale otherwise. It is
@@ -422,7 +430,8 @@ J40HIP_API uint32_t j40hip_batch_reset(j40hip_batch *b, j40hip_frame *const *fra
  *      j40hip_sequence_free; a container's boxes are put together once); no device needed. A stream whose first frame is its last is
  *      not a sequence: NULL and "Usq?" (use j40hip_frame_parse). NULL and the code when the image header or the first frame's header
  *      fails. A later frame whose header or TOC fails, or that is refused, ends the index: it is the last row and carries its code.
- *      flags as j40hip_frame_parse_ex (bit 0), applied to every frame handle. ---- */
+ *      flags: bit 0 as j40hip_frame_parse_ex's, applied to every frame handle; bit 1 J40HIP_SEQ_BLEND. ---- */
+#define J40HIP_SEQ_BLEND 2u   /* j40hip_sequence_open: serve the blend modes Add (1), Blend (2), MulAdd (3) and Mul (4) too */
 typedef struct j40hip_sequence j40hip_sequence;
 J40HIP_API j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads, uint32_t flags, uint32_t *err);
 J40HIP_API void j40hip_sequence_free(j40hip_sequence *s);
@@ -434,6 +443,11 @@ J40HIP_API int64_t j40hip_sequence_num_shown(const j40hip_sequence *s);    /* di
  * with ("shrt": the stream ends before the frame does), [16] ticks per second numerator and [17] denominator, [18] loops (0: for
  * ever), [19] canvas width, [20] height. k out of range: zeros. */
 J40HIP_API void j40hip_sequence_frame_info(const j40hip_sequence *s, int64_t k, int64_t *out21);
+/* How coded frame k goes onto the canvas. out8: [0] the colour channels' blend mode (0 Replace, 1 Add, 2 Blend, 3 MulAdd, 4 Mul),
+ * [1] the rendered alpha channel's (0 without one), [2] the colour channels' alpha_chan and [3] clamp, [4] the alpha channel's own
+ * alpha_chan and [5] clamp, [6] the source slot, [7] whether the frame goes through k_frame_blend (J40HIP_SEQ_BLEND, a mode other
+ * than Replace in [0] or [1], and the frame is not refused). k out of range: zeros. */
+J40HIP_API void j40hip_sequence_frame_blend(const j40hip_sequence *s, int64_t k, int32_t *out8);
 /* Coded frame k, fully parsed at the first call: an ordinary frame handle of the frame's own (crop) size over a copy of the frame's
  * own bytes, owned by the sequence (do not free it). Every single-frame and batch entry point takes it -- upload, decode, region,
  * LF preview, alpha mode, status. NULL and the code for a frame that is refused or does not parse. */
@@ -450,7 +464,8 @@ J40HIP_API uint32_t j40hip_sequence_set_output_format(j40hip_sequence *s, int32_
  * of stride_bytes (at least 4 or 8 bytes a pixel, else "rnge"), pixel-aligned. Frames that are saved are composed in their slot --
  * where that slot is also the source (out == src for the compose kernel) only the rectangle is written -- and copied out when they
  * are shown; up to four canvas-sized slots and one staging image come from the device memory cache at j40hip_sequence_upload and go
- * back at j40hip_sequence_free. A frame that covers the canvas exactly decodes straight into its destination. Everything is enqueued
+ * back at j40hip_sequence_free. A frame that covers the canvas exactly decodes straight into its destination -- unless it has a blend
+ * mode other than Replace: such a frame, whatever it covers, decodes into the staging image and goes through k_frame_blend. Everything is enqueued
  * on `stream`; nothing is waited for and no memory is taken (frames in keep-alpha mode synchronise as j40hip_frame_decode does). Returns 0; "Useq" when no
  * displayed frame is left; the code of a frame that is refused or fails to upload ("!gpu": not uploaded). Section failures surface
  * in j40hip_sequence_status once the stream has been synchronised. */
@@ -468,6 +483,12 @@ J40HIP_API uint32_t j40hip_sequence_status(j40hip_sequence *s, int64_t *out_fram
  * equal strides): only the rectangle is written. All rows pixel-aligned. Asynchronous on `stream`. 0, "rnge", "Ufm?". */
 J40HIP_API uint32_t j40hip_kat_device_compose(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, const void *frame_dev, size_t frame_stride,
 		int32_t W, int32_t H, int32_t x0, int32_t y0, int32_t w, int32_t h, uint32_t empty_lo, uint32_t empty_hi, int32_t format, void *stream);
+
+/* ... and k_frame_blend alone: the same arguments and checks, then the colour channels' and the alpha channel's blend mode (0..4,
+ * else "rnge"). Inside the rectangle the canvas pixel is the blend of the frame's pixel over src_dev's (or the empty pixel);
+ * out_dev == src_dev blends in place. */
+J40HIP_API uint32_t j40hip_kat_device_blend(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, const void *frame_dev, size_t frame_stride,
+		int32_t W, int32_t H, int32_t x0, int32_t y0, int32_t w, int32_t h, uint32_t empty_lo, uint32_t empty_hi, int32_t format, int32_t colour_mode, int32_t alpha_mode, void *stream);
 
 /* ---- building blocks for pipelines ---- */
 /* j40hip_frame_upload with the copies enqueued on `stream` (the plan is staged in pinned memory owned by the calling thread, so the

@@ -124,6 +124,8 @@ def lib():
         "j40hip_sequence_set_output_format": (u32, [vp, i32]), "j40hip_sequence_next": (u32, [vp, vp, sz, vp]),
         "j40hip_sequence_next_to_host": (u32, [vp, vp, sz]), "j40hip_sequence_rewind": (None, [vp]), "j40hip_sequence_status": (u32, [vp, C.POINTER(i64)]),
         "j40hip_kat_device_compose": (u32, [vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, u32, u32, i32, vp]),
+        "j40hip_sequence_frame_blend": (None, [vp, i64, vp]),
+        "j40hip_kat_device_blend": (u32, [vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, u32, u32, i32, i32, i32, vp]),
         "j40hip_frame_restoration": (None, [vp, vp]), "j40hip_frame_set_restoration": (None, [vp, C.c_int]), "j40hip_frame_sharpness": (C.c_int, [vp, i64, vp]),
         "j40hip_frame_set_alpha": (u32, [vp, C.c_int]), "j40hip_frame_alpha": (None, [vp, vp]),
         "j40hip_frame_set_region": (u32, [vp, i32, i32, i32, i32]), "j40hip_frame_region": (None, [vp, vp]),
@@ -734,19 +736,22 @@ def decode_lf_many(datas, fmt=J40_U8X4, device=0):
             f.close()
 
 
+SEQ_BLEND = 2   # j40hip_sequence_open's flag J40HIP_SEQ_BLEND: the blend modes Add, Blend, MulAdd and Mul are served
+SEQUENCE_BLEND_FIELDS = ("mode", "alpha_mode", "alpha_chan", "clamp", "alpha_alpha_chan", "alpha_clamp", "src", "blended")
 SEQUENCE_FRAME_FIELDS = ("x0", "y0", "w", "h", "duration", "is_last", "shown", "type", "blend", "src", "save_as_reference", "saved",
                          "offset", "end", "first_section", "code", "tps_num", "tps_den", "loops", "canvas_w", "canvas_h")
 
 
 class Sequence:
     """the coded frames of one codestream -- an animation or a layered still -- and their playback (j40hip_sequence, include/j40hip.h):
-    an index over headers and TOCs on the host, every coded frame an ordinary Frame, the displayed canvases composed on the device"""
+    an index over headers and TOCs on the host, every coded frame an ordinary Frame, the displayed canvases composed on the device.
+    blend=True (or J40HIP_BLEND=1): frames with the blend modes Add, Blend, MulAdd and Mul are served too, else "TODO" for such a frame"""
 
-    def __init__(self, data: bytes, threads: int = 4, flags: int = 0):
+    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False):
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags, C.byref(err))
+        self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags | (SEQ_BLEND if blend else 0), C.byref(err))
         if not self.h:
             raise J40Error(err4(err.value), "in j40hip_sequence_open")
         self.num_frames, self.num_shown = int(L.j40hip_sequence_num_frames(self.h)), int(L.j40hip_sequence_num_shown(self.h))
@@ -784,6 +789,13 @@ class Sequence:
         d = dict(zip(SEQUENCE_FRAME_FIELDS, out.tolist()))
         d["code"] = err4(d["code"])
         return d
+
+    def frame_blend(self, k):
+        """how coded frame k goes onto the canvas, as a dict (SEQUENCE_BLEND_FIELDS): the colour channels' blend mode and the rendered
+        alpha channel's, their alpha_chan and clamp, the source slot, whether the frame goes through the blend kernel"""
+        out = np.zeros(8, np.int32)
+        lib().j40hip_sequence_frame_blend(self.h, k, out.ctypes.data)
+        return dict(zip(SEQUENCE_BLEND_FIELDS, out.tolist()))
 
     def frame(self, k):
         """coded frame k as a Frame the sequence owns: crop-sized, for every single-frame and batch entry point. It lives as long as the
@@ -833,11 +845,12 @@ class Sequence:
         return err4(code), int(k.value)
 
 
-def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0):
+def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False):
     """every displayed frame of an animation or a layered still: ([(rgba ndarray [height, width, 4], duration in ticks), ...],
     (tps_num, tps_den, loops)). alpha=True: VarDCT frames keep their alpha channel (Frame.set_alpha(1); J40Error where that refuses).
+    blend=True: frames with a blend mode other than Replace are composed too (Sequence's blend=), else such a frame raises "TODO".
     A frame that fails raises J40Error with its code. A stream whose first frame is its last is not a sequence ("Usq?"): decode()."""
-    seq = Sequence(data)
+    seq = Sequence(data, blend=blend)
     try:
         seq.set_output_format(fmt)
         if alpha:

@@ -60,10 +60,16 @@ struct j40hip_sequence {
 		size_t offset = 0, end = 0, first_section = 0;   // bytes of the codestream: the frame header, the end of the last section, the first section
 		uint32_t code = 0;           // what the frame is refused with; nothing behind such a frame is known
 		bool shown = false, saved = false;
+		// blend modes (J40HIP_SEQ_BLEND): the rendered alpha channel's mode, the one source slot of the entries that carry one, and
+		// whether the frame goes through k_frame_blend (a mode other than Replace in the colour channels or the rendered alpha)
+		int8_t alpha_mode = 0, src = 0;
+		bool blended = false;
 	};
 	std::vector<Row> rows;
 	std::vector<j40hip_frame *> frames;   // [rows.size()], parsed when first asked for
 	int threads = 1; uint32_t flags = 0;
+	bool blend = false;              // the blend modes other than Replace are served (J40HIP_SEQ_BLEND or J40HIP_BLEND=1)
+	int32_t alpha_ec = -1;           // the extra channel that is rendered as A (rendered_alpha_channel); -1: none
 	int32_t output_format = J40HIP_U8X4;
 	j40hip_sequence_device *dev = nullptr;
 };

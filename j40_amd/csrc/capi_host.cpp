@@ -151,19 +151,30 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 	try {
 		extract_codestream((const uint8_t *) buf, size, &s->cs, &s->cs_size, &s->cs_storage);
 		s->threads = threads < 1 ? 1 : threads > 16 ? 16 : threads; s->flags = flags;
+		s->blend = (flags & J40HIP_SEQ_BLEND) != 0 || env_on("J40HIP_BLEND", false);   // (looked at with every sequence that is opened)
 		size_t at = 0;
 		parse_image_header(s->cs, s->cs_size, &s->im, &at);
+		s->alpha_ec = rendered_alpha_channel(s->im);
 		for (;;) {
 			j40hip_sequence::Row row;
 			Toc toc;
 			row.offset = at;
 			try {
-				parse_sequence_frame_header(s->cs, s->cs_size, at, s->im, &row.fh, &toc);
+				parse_sequence_frame_header(s->cs, s->cs_size, at, s->im, s->blend, &row.fh, &toc);
 				row.first_section = at + toc.first_offset; row.end = at + toc.end_offset;
 				// (a frame whose sections the stream does not hold to their end: whatever follows it cannot be found)
 				if (row.end > s->cs_size) row.code = E4("shrt");
-				// the rendered pixels carry colour and alpha together: one source slot for both
-				if (!row.fh.full_frame) for (const FrameHeader::Blend &b : row.fh.ec_blend) if (b.src_ref != row.fh.blend.src_ref) row.code = row.code ? row.code : (uint32_t) E4("TODO");
+				// the rendered pixels carry colour and alpha together: one source slot for every entry that carries one (a cropped
+				// frame's all do, a full frame's those with a mode other than Replace)
+				auto carries = [&](const FrameHeader::Blend &b) { return !row.fh.full_frame || b.mode != 0; };
+				int slot = carries(row.fh.blend) ? row.fh.blend.src_ref : -1;
+				for (const FrameHeader::Blend &b : row.fh.ec_blend) if (carries(b)) {
+					if (slot < 0) slot = b.src_ref;
+					if (b.src_ref != slot) row.code = row.code ? row.code : (uint32_t) E4("TODO");
+				}
+				row.src = (int8_t) (slot < 0 ? 0 : slot);
+				row.alpha_mode = s->alpha_ec >= 0 ? row.fh.ec_blend[(size_t) s->alpha_ec].mode : 0;
+				row.blended = s->blend && (row.fh.blend.mode != 0 || row.alpha_mode != 0);
 			} catch (const DecodeError &e) { row.code = e.code; }
 			if (s->rows.empty()) {
 				if (row.code) raise(row.code);
@@ -207,6 +218,16 @@ void j40hip_sequence_frame_info(const j40hip_sequence *s, int64_t k, int64_t *ou
 	out[16] = s->im.anim_tps_num; out[17] = s->im.anim_tps_den; out[18] = s->im.anim_loops; out[19] = s->im.width; out[20] = s->im.height;
 }
 
+void j40hip_sequence_frame_blend(const j40hip_sequence *s, int64_t k, int32_t *out) {
+	if (!out) return;
+	memset(out, 0, sizeof(int32_t) * 8);
+	if (!s || k < 0 || k >= (int64_t) s->rows.size()) return;
+	const j40hip_sequence::Row &r = s->rows[(size_t) k];
+	const FrameHeader::Blend none, &a = s->alpha_ec >= 0 && (size_t) s->alpha_ec < r.fh.ec_blend.size() ? r.fh.ec_blend[(size_t) s->alpha_ec] : none;
+	out[0] = r.fh.blend.mode; out[1] = a.mode; out[2] = r.fh.blend.alpha_chan; out[3] = r.fh.blend.clamp;
+	out[4] = a.alpha_chan; out[5] = a.clamp; out[6] = r.src; out[7] = r.blended && !r.code;
+}
+
 j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err) {
 	if (err) *err = 0;
 	if (!s || k < 0 || k >= (int64_t) s->rows.size()) { if (err) *err = E4("rnge"); return nullptr; }
@@ -226,7 +247,7 @@ j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err
 		h->cs = h->cs_storage.data();
 		h->bare_codestream = true;
 		h->frame.defer_lf_tail = (s->flags & 1u) != 0;
-		h->frame.seq_im = &s->im;
+		h->frame.seq_im = &s->im; h->frame.seq_blend = s->blend;
 		parse_frame(h->cs, h->cs_size, &h->frame, s->threads);
 		h->threads = s->threads;
 		h->output_format = s->output_format;

@@ -102,5 +102,9 @@ void launch_region_crop(const uint8_t *src, size_t src_stride, uint8_t *dst, siz
 // pixel (its bytes as one or two little-endian words). src == out: only the rectangle is written. Every row pixel-aligned.
 void launch_frame_compose(uint8_t *out, size_t out_stride, const uint8_t *src, size_t src_stride, const uint8_t *frm, size_t frm_stride, int32_t W, int32_t H,
 		int32_t x0, int32_t y0, int32_t w, int32_t h, uint32_t empty_lo, uint32_t empty_hi, int32_t pixel_bytes, hipStream_t stream);
+// ... in the blend modes (compose_dev.h: BLEND_*, 0..4) cmode for the colour channels and amode for the alpha: inside the rectangle the
+// frame's pixel blended over the source's (or the empty pixel). src == out: the rectangle is blended in place.
+void launch_frame_blend(uint8_t *out, size_t out_stride, const uint8_t *src, size_t src_stride, const uint8_t *frm, size_t frm_stride, int32_t W, int32_t H,
+		int32_t x0, int32_t y0, int32_t w, int32_t h, uint32_t empty_lo, uint32_t empty_hi, int32_t pixel_bytes, int32_t cmode, int32_t amode, hipStream_t stream);
 
 } // namespace j40hip

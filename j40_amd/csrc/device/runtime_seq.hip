@@ -3,7 +3,8 @@
 //
 // A coded frame is an ordinary frame handle (capi_host.cpp: j40hip_sequence_frame) and decodes through j40hip_frame_decode. Where it goes:
 // a frame that covers the canvas exactly decodes straight into its destination; every other one into the staging image, from where
-// k_frame_compose (compose_kernels.hip) puts it onto the canvas. The destination of a frame that is saved is its slot -- a frame that
+// k_frame_compose (compose_kernels.hip) puts it onto the canvas. A frame with a blend mode other than Replace (Row::blended) decodes into
+// the staging image whatever it covers and goes through k_frame_blend. The destination of a frame that is saved is its slot -- a frame that
 // draws over the slot it is saved into touches only its rectangle -- and a shown one is then copied out; a frame that is only shown is
 // composed into the caller's image. All on the caller's stream, in order: one staging image serves every frame.
 #include "runtime_state.hpp"
@@ -31,7 +32,7 @@ size_t slot_bytes(const j40hip_sequence *s) { return s->dev->slot_stride * (size
 // destination's, up to 15 bytes in front of the first one and 16 behind the last
 size_t staging_bound(const j40hip_sequence *s, int32_t w, int32_t h) { return 32 + ((((size_t) w * seq_pixel_bytes(s) + 15) & ~(size_t) 15) + 16) * (size_t) h; }
 
-// Every slot the index saves into and one staging image large enough for each frame that does not cover the canvas exactly, taken
+// Every slot the index saves into and one staging image large enough for each frame that does not cover the canvas exactly or is blended, taken
 // where the host may wait for the device (the upload, a change of the output format): taking or growing a block waits for it
 // (CacheBlock::ensure), and the playback must not.
 bool reserve_blocks(j40hip_sequence *s) {
@@ -41,7 +42,7 @@ bool reserve_blocks(j40hip_sequence *s) {
 	for (const j40hip_sequence::Row &row : s->rows) {
 		if (row.code) break;
 		if (row.saved && !d->slot[row.fh.save_as_ref].ensure(d->device, slot_bytes(s), false)) return false;
-		if (!(row.fh.x0 == 0 && row.fh.y0 == 0 && row.fh.width == s->im.width && row.fh.height == s->im.height)) staging = std::max(staging, staging_bound(s, row.fh.width, row.fh.height));
+		if (row.blended || !(row.fh.x0 == 0 && row.fh.y0 == 0 && row.fh.width == s->im.width && row.fh.height == s->im.height)) staging = std::max(staging, staging_bound(s, row.fh.width, row.fh.height));
 	}
 	return !staging || d->staging.ensure(d->device, staging, false);
 }
@@ -75,7 +76,7 @@ uint32_t play_frame(j40hip_sequence *s, int64_t k, uint8_t *out, size_t out_stri
 	uint8_t *dst = out; size_t dst_stride = out_stride;
 	if (row.saved) { dst = slot_image(s, fh.save_as_ref); dst_stride = d->slot_stride; if (!dst) return ERR_GPU; }
 	if (!dst) return 0;   // neither shown nor saved: nothing of it is ever seen
-	const bool exact = fh.x0 == 0 && fh.y0 == 0 && fh.width == W && fh.height == H;
+	const bool exact = !row.blended && fh.x0 == 0 && fh.y0 == 0 && fh.width == W && fh.height == H;   // decoded where it is wanted
 	const ComposeRect r = compose_clip(W, H, fh.x0, fh.y0, fh.width, fh.height);
 	uint8_t *img = dst; size_t img_stride = dst_stride;
 	if (!exact) { img = staging_image(s, dst, dst_stride, fh.width, fh.height, r.fx, r.cx0, &img_stride); if (!img) return ERR_GPU; }
@@ -94,10 +95,11 @@ uint32_t play_frame(j40hip_sequence *s, int64_t k, uint8_t *out, size_t out_stri
 		if (e) return e;
 	}
 	if (!exact) {
-		const uint8_t *src = d->slot_saved[fh.blend.src_ref] ? (const uint8_t *) d->slot[fh.blend.src_ref].ptr : nullptr;
+		const uint8_t *src = d->slot_saved[row.src] ? (const uint8_t *) d->slot[row.src].ptr : nullptr;
 		const bool a0 = renders_alpha(h);
 		const uint32_t lo = pb == 4 && !a0 ? 0xff000000u : 0u, hi = pb == 8 && !a0 ? 0xffff0000u : 0u;
-		launch_frame_compose(dst, dst_stride, src, d->slot_stride, img, img_stride, W, H, fh.x0, fh.y0, fh.width, fh.height, lo, hi, (int32_t) pb, stream);
+		if (row.blended) launch_frame_blend(dst, dst_stride, src, d->slot_stride, img, img_stride, W, H, fh.x0, fh.y0, fh.width, fh.height, lo, hi, (int32_t) pb, fh.blend.mode, row.alpha_mode, stream);
+		else launch_frame_compose(dst, dst_stride, src, d->slot_stride, img, img_stride, W, H, fh.x0, fh.y0, fh.width, fh.height, lo, hi, (int32_t) pb, stream);
 		if (hipGetLastError() != hipSuccess) return ERR_GPU;
 	}
 	if (row.saved) {
@@ -209,14 +211,33 @@ extern "C" uint32_t j40hip_sequence_status(j40hip_sequence *s, int64_t *out_fram
 	});
 }
 
-extern "C" uint32_t j40hip_kat_device_compose(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, const void *frame_dev, size_t frame_stride,
-		int32_t W, int32_t H, int32_t x0, int32_t y0, int32_t w, int32_t h, uint32_t empty_lo, uint32_t empty_hi, int32_t format, void *stream) {
+namespace {
+// what both hooks refuse before anything is launched
+uint32_t kat_compose_check(const void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, const void *frame_dev, size_t frame_stride,
+		int32_t W, int32_t H, int32_t w, int32_t h, int32_t format) {
 	if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
 	const size_t pb = format == J40HIP_U16X4 ? 8 : 4;
 	if (!out_dev || !frame_dev || W <= 0 || H <= 0 || w <= 0 || h <= 0) return ERR_RNGE;
 	if (out_stride < (size_t) W * pb || frame_stride < (size_t) w * pb || (src_dev && src_stride < (size_t) W * pb)) return ERR_RNGE;
 	if (((uintptr_t) out_dev | (uintptr_t) frame_dev | (uintptr_t) src_dev | out_stride | frame_stride | (src_dev ? src_stride : 0)) % pb) return ERR_RNGE;
 	if (src_dev == out_dev && src_stride != out_stride) return ERR_RNGE;
+	return 0;
+}
+}
+
+extern "C" uint32_t j40hip_kat_device_blend(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, const void *frame_dev, size_t frame_stride,
+		int32_t W, int32_t H, int32_t x0, int32_t y0, int32_t w, int32_t h, uint32_t empty_lo, uint32_t empty_hi, int32_t format, int32_t colour_mode, int32_t alpha_mode, void *stream) {
+	if (uint32_t e = kat_compose_check(out_dev, out_stride, src_dev, src_stride, frame_dev, frame_stride, W, H, w, h, format)) return e;
+	if (colour_mode < 0 || colour_mode > 4 || alpha_mode < 0 || alpha_mode > 4) return ERR_RNGE;
+	launch_frame_blend((uint8_t *) out_dev, out_stride, (const uint8_t *) src_dev, src_stride, (const uint8_t *) frame_dev, frame_stride, W, H, x0, y0, w, h, empty_lo, empty_hi,
+		format == J40HIP_U16X4 ? 8 : 4, colour_mode, alpha_mode, (hipStream_t) stream);
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+}
+
+extern "C" uint32_t j40hip_kat_device_compose(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, const void *frame_dev, size_t frame_stride,
+		int32_t W, int32_t H, int32_t x0, int32_t y0, int32_t w, int32_t h, uint32_t empty_lo, uint32_t empty_hi, int32_t format, void *stream) {
+	if (uint32_t e = kat_compose_check(out_dev, out_stride, src_dev, src_stride, frame_dev, frame_stride, W, H, w, h, format)) return e;
+	const size_t pb = format == J40HIP_U16X4 ? 8 : 4;
 	launch_frame_compose((uint8_t *) out_dev, out_stride, (const uint8_t *) src_dev, src_stride, (const uint8_t *) frame_dev, frame_stride, W, H, x0, y0, w, h, empty_lo, empty_hi, (int32_t) pb, (hipStream_t) stream);
 	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 }

@@ -812,16 +812,27 @@ void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t
 	br.zero_pad_to_byte();
 	*first_frame = br.byte_position();
 }
-uint32_t sequence_refusal(const FrameHeader &fh) {
-	bool ok = (fh.type == 0 || fh.type == 3) && !fh.use_lf_frame && fh.blend.mode == 0;
-	for (const FrameHeader::Blend &b : fh.ec_blend) ok = ok && b.mode == 0;
+int32_t rendered_alpha_channel(const ImageMeta &im) {
+	for (size_t i = 0; i < im.ec.size(); ++i) if (im.ec[i].type == EC_ALPHA) return (int32_t) i;
+	return -1;
+}
+uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec) {
+	bool ok = (fh.type == 0 || fh.type == 3) && !fh.use_lf_frame;
+	if (!blend) {
+		ok = ok && fh.blend.mode == 0;
+		for (const FrameHeader::Blend &b : fh.ec_blend) ok = ok && b.mode == 0;
+	} else if (!fh.ec_blend.empty()) {
+		// (an image without extra channels codes no alpha_chan: every alpha is full scale)
+		auto names_it = [&](const FrameHeader::Blend &b) { return (b.mode != 2 && b.mode != 3) || b.alpha_chan == alpha_ec; };
+		ok = ok && names_it(fh.blend) && (alpha_ec < 0 || names_it(fh.ec_blend[(size_t) alpha_ec]));
+	}
 	return ok ? 0 : (uint32_t) E4("TODO");
 }
-void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, FrameHeader *fh, Toc *toc) {
+void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, FrameHeader *fh, Toc *toc) {
 	J40HIP_SHOULD(offset < cs_size, "shrt");
 	BitReader br(cs + offset, cs_size - offset);
 	read_frame_header(br, im, fh, true);
-	if (uint32_t e = sequence_refusal(*fh)) raise(e);
+	if (uint32_t e = sequence_refusal(*fh, blend, rendered_alpha_channel(im))) raise(e);
 	read_toc(br, *fh, toc);
 }
 
@@ -831,7 +842,7 @@ static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size
 	if (f->seq_im) {   // a sequence's member: its bytes start at the frame header
 		f->im = *f->seq_im;
 		read_frame_header(br, f->im, &f->fh, true);
-		if (uint32_t e = sequence_refusal(f->fh)) raise(e);
+		if (uint32_t e = sequence_refusal(f->fh, f->seq_blend, rendered_alpha_channel(f->im))) raise(e);
 	} else {
 		read_image_header(br, &f->im);
 		read_frame_header(br, f->im, &f->fh);

@@ -182,13 +182,14 @@ struct Frame {
 	// image metadata is this one instead of a parsed one. Frames that are not last, and frames of type 3, are taken; what a sequence
 	// does not serve (sequence_refusal) is "TODO". Set before parse_frame.
 	const ImageMeta *seq_im = nullptr;
+	bool seq_blend = false;   // ... and the sequence serves the blend modes other than Replace (J40HIP_SEQ_BLEND)
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
 	Frame with_same_inputs() const {
 		Frame g;
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
-		g.lf_only = lf_only; g.seq_im = seq_im;
+		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section
@@ -206,9 +207,15 @@ void extract_codestream(const uint8_t *data, size_t size, const uint8_t **cs, si
 void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame);
 // header and TOC of the frame that starts at byte `offset` of the codestream, for a sequence's index: nothing behind the TOC is
 // read. The TOC's offsets count from `offset`. Raises what the header or the TOC raise, "TODO" for what sequence_refusal refuses.
-void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, FrameHeader *fh, Toc *toc);
-// 0, or "TODO": the frame is of a kind a sequence does not serve (types 1 and 2, use_lf_frame, a blend mode other than Replace)
-uint32_t sequence_refusal(const FrameHeader &fh);
+// blend: the sequence serves the blend modes other than Replace (sequence_refusal).
+void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, FrameHeader *fh, Toc *toc);
+// the extra channel whose samples become the pixels' A (plan_build.cpp: alpha_channel): the first one of type alpha; -1: none
+int32_t rendered_alpha_channel(const ImageMeta &im);
+// 0, or "TODO": the frame is of a kind a sequence does not serve -- types 1 and 2, use_lf_frame, and a blend mode other than Replace
+// in any channel. With `blend` the other four modes are served for the colour channels and for extra channel `alpha_ec` (the rendered
+// alpha, -1: none; the other extra channels' entries are not looked at), unless a Blend or MulAdd of either names another alpha
+// channel than `alpha_ec`
+uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec);
 
 // parses headers, TOC, LfGlobal, HfGlobal and every LfGroup section. `threads` > 1 decodes LfGroup
 // sections concurrently (they are independent given LfGlobal)

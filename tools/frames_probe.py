@@ -6,6 +6,10 @@ warm-up, with a device synchronisation inside every clock:
       pixel, so the bar is the copy's time plus the copy's own run-to-run spread over the session; the ratio and the bytes per second
       are recorded.
   (b) the aliased form (out == src: only the rectangle is written) against a copy of the rectangle alone.
+  (d) k_frame_blend alone (j40hip_kat_device_blend, colour and alpha both Blend) on (a)'s and (b)'s case, alternating with them. The
+      yardstick is k_frame_compose's bytes per second in this same session; the blend's bytes count the source inside the rectangle
+      too (it is read there as well). The bar: the blend's bytes per second (median) fall no further below compose's than compose's
+      own min-to-max spread of bytes per second. Recorded under "blend", met or missed per format and form.
   (c) a 16-frame 1920 x 1080 VarDCT animation (frame 0 full, the others cropped): j40hip_sequence_next sixteen times against one
       j40hip_batch over its coded frames plus sixteen composes. Reported, no bar.
 
@@ -48,7 +52,7 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3
 
-    out = {"reps": args.reps, "compose": {}}
+    out = {"reps": args.reps, "compose": {}, "blend": {}}
     W, H, rw, rh, x0, y0 = 7680, 4320, 4096, 2048, 1792, 1136
     for name, fmt, pb in (("u8x4", U8X4, 4), ("u16x4", U16X4, 8)):
         stride = W * pb
@@ -64,7 +68,14 @@ def main():
         def compose_aliased():
             assert L.j40hip_kat_device_compose(slot.data_ptr(), stride, slot.data_ptr(), stride, frame.data_ptr(), rw * pb, W, H, x0, y0, rw, rh, 0, 0, fmt, stream) == 0
 
-        variants = {"compose": compose, "copy_canvas": lambda: canvas.copy_(slot), "compose_aliased": compose_aliased, "copy_rectangle": lambda: rect_dst.copy_(rect_src)}
+        def blend():
+            assert L.j40hip_kat_device_blend(canvas.data_ptr(), stride, slot.data_ptr(), stride, frame.data_ptr(), rw * pb, W, H, x0, y0, rw, rh, 0, 0, fmt, 2, 2, stream) == 0
+
+        def blend_aliased():
+            assert L.j40hip_kat_device_blend(slot.data_ptr(), stride, slot.data_ptr(), stride, frame.data_ptr(), rw * pb, W, H, x0, y0, rw, rh, 0, 0, fmt, 2, 2, stream) == 0
+
+        variants = {"compose": compose, "copy_canvas": lambda: canvas.copy_(slot), "compose_aliased": compose_aliased, "copy_rectangle": lambda: rect_dst.copy_(rect_src),
+                    "blend": blend, "blend_aliased": blend_aliased}
         ms = {k: [] for k in variants}
         for rep in range(args.reps + 3):
             for k, fn in variants.items():
@@ -81,6 +92,18 @@ def main():
         r["compose_within_bar"] = r["compose"]["median_ms"] <= r["bar_ms_copy_median_plus_its_spread"]
         r["aliased_over_rectangle_copy"] = round(r["compose_aliased"]["median_ms"] / r["copy_rectangle"]["median_ms"], 4)
         r["aliased_gbytes_per_s"] = round(2 * rh * rw * pb / r["compose_aliased"]["median_ms"] / 1e6, 1)
+        b = {}
+        for form, kernel, yard, moved, yard_moved in (("canvas", "blend", "compose", 2 * H * stride + rh * rw * pb, 2 * H * stride), ("aliased", "blend_aliased", "compose_aliased", 3 * rh * rw * pb, 2 * rh * rw * pb)):
+            rate = lambda nbytes, ms: nbytes / ms / 1e6
+            y = r[yard]
+            spread = rate(yard_moved, y["min_ms"]) - rate(yard_moved, y["max_ms"])
+            b[form] = dict(r.pop(kernel), bytes_moved=moved)
+            b[form]["gbytes_per_s"] = round(rate(moved, b[form]["median_ms"]), 1)
+            b[form]["compose_gbytes_per_s_this_session"] = round(rate(yard_moved, y["median_ms"]), 1)
+            b[form]["compose_gbytes_per_s_spread"] = round(spread, 1)
+            b[form]["compose_median_ms_this_session"] = y["median_ms"]
+            b[form]["bar_met"] = bool(b[form]["gbytes_per_s"] >= b[form]["compose_gbytes_per_s_this_session"] - b[form]["compose_gbytes_per_s_spread"])
+        out["blend"][name] = b
         out["compose"][name] = r
         del canvas, slot, frame
 

@@ -708,6 +708,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			int v = (x * 3 + y * 2) / 4 + (int) rng.below(5) - 2 + (((x / 40) + (y / 24)) % 3 == 0 ? 90 : 0);
 			v = std::max(0, std::min(255, v));
 			if (alpha_bpp != 8) v = std::min(amax, v * amax / 255 + ((x * 7 + y * 13) & ((1 << (alpha_bpp - 8)) - 1)));
+			// alpharange=1: 0, full scale and everything between (transparent and opaque cells in a diagonal ramp), for the blend modes
+			if (opt.geti("alpharange", 0)) { const int cell = (x / 23 + y / 19) % 5; v = cell == 0 ? 0 : cell == 1 ? amax : ((x * 5 + y * 3) & 255) * amax / 255; }
 			alpha.at(x, y) = v;
 		}
 		for (int g = 0; g < num_groups; ++g) {
@@ -1367,6 +1369,8 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		}
 		for (int k = 0; k < extra; ++k) ch[(size_t) (3 + k)].at(x, y) = (((x >> 3) * (k + 2) + (y >> 2)) & 31) * ((1 << bpp) - 1) / 31;
 		if (alpha) ch[(size_t) (3 + extra)].at(x, y) = ((x / 37 + y / 29) & 3) == 0 ? 128 + ((x * 3 + y) & 63) : 255;
+		// alpharange=1: 0, full scale and everything between (a diagonal ramp with transparent and opaque cells), for the blend modes
+		if (alpha && opt.geti("alpharange", 0)) { const int cell = (x / 23 + y / 19) % 5; ch[(size_t) (3 + extra)].at(x, y) = cell == 0 ? 0 : cell == 1 ? 255 : (x * 5 + y * 3) & 255; }
 	}
 
 	if (squeeze && repeat > 1) {   // lay the tile out over the whole frame
@@ -1899,7 +1903,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 //   durations=d0,d1,.. per-frame durations in ticks (default 1 with anim=1; without anim there is no such field: 0)
 //   crops=x,y,w,h;...  per-frame crops; an empty entry is the full frame
 //   srcs= saves=       per-frame source slots and save_as_reference values (default 0)
-//   blends=            per-frame blend mode, all channels alike (default 0, Replace: the only one a decoder here serves)
+//   blends=            per-frame blend mode, all channels alike (default 0, Replace; 1 Add, 2 Blend, 3 MulAdd, 4 Mul)
 //   ecblends= ecsrcs=  per-frame blend mode and source slot of the extra channels alone (default: the colour channels')
 //   only=k             coded frame k alone, as a last frame, under the same image header, with the same crop and the same section bytes
 // The last frame is is_last. stats=1 prints frames, shown, saved_slots and every frame's offsets instead of the mode's own statistics.
