@@ -312,6 +312,39 @@ J40HIP_API uint32_t j40hip_kat_device_alpha_merge(void *rgba_dev, size_t stride_
 J40HIP_API uint32_t j40hip_frame_set_region(j40hip_frame *f, int32_t x0, int32_t y0, int32_t w, int32_t h);
 J40HIP_API void j40hip_frame_region(const j40hip_frame *f, int32_t out[12]);
 
+/* ---- reduced-size decode: the whole frame at 1:2 or 1:4, averaged in the pixel kernels ("Reduced-size decode"). A frame has
+ *      a scale shift k in {0, 1, 2}, s = 1 << k; the default 0 changes nothing. At k > 0 the decode entry points write ow x oh pixels of
+ *      the frame's format, ow = (width + s - 1) >> k, oh = (height + s - 1) >> k. Sample c (each of R, G, B, A on its own) of pixel (i, j)
+ *      is (S + (n >> 1)) / n in integers: S the sum of sample c of the FULL decode in the same output format -- what the same handle
+ *      writes with k = 0 and every other setting equal (alpha mode, restoration mode, format) -- over the cell x in [i * s, min(width,
+ *      (i + 1) * s)), y in [j * s, min(height, (j + 1) * s)), n the cell's pixels (only cells on the right and bottom edges have fewer
+ *      than s * s). The mean is taken on coded (sRGB) levels, NOT in linear light: that makes the small image an exact function of
+ *      pixels the reference pins. An opaque frame stays A = 255 (65535).
+ *      set: any parsed frame, uploaded or not; it holds from the next decode on, across uploads. A shift outside 0..2: "rnge". A shift
+ *      above 0 is refused with "Usc?" for a frame with a region or a partial group range and for a handle j40hip_sequence_frame handed
+ *      out, with "Ulf?" for an LF-only frame; j40hip_frame_set_region and j40hip_frame_set_group_range on a frame with a shift above 0
+ *      return "Usc?": whichever setter comes second is refused. A refused call leaves the frame as it was. Shift 0 always succeeds.
+ *      At a shift above 0 j40hip_frame_decode / _timed / _decode_to_host write ow x oh pixels; stride_bytes below 4 * ow (u8) or 8 * ow
+ *      (u16) is "rnge" before anything is launched; nothing outside the ow pixels of each of the oh rows is written;
+ *      j40hip_frame_decode_to_host copies only the small image back, keeps the "evof" retry and never decodes in two phases. Every
+ *      section is still entropy-decoded: j40hip_frame_status and every error code are those of the full decode.
+ *      Fused: the VarDCT pixel kernels and the Modular pack kernel average their samples as they colour-convert them and store the
+ *      small image alone -- no full-size pixel is written. Staged: where other kernels write the pixels -- restoration filters in force
+ *      on a frame that signals them, keep-alpha mode on a single frame -- the frame decodes into a full-size image in device memory
+ *      kept with the frame (one block of the device memory cache, given back with the frame) and k_downscale reduces it. A scale is
+ *      served wherever the whole frame is.
+ *      Batches: members must agree on the shift, else "Usc?" where "Uof?" is raised, before any launch; each member gets its own
+ *      ow x oh at its own stride; a member in keep-alpha mode at a shift above 0: "Usc?".
+ *      j40hip_frame_scale: out[0] the shift in force, out[1], out[2] ow, oh at that shift, and of the last decode at a shift above 0:
+ *      out[3] 1 if it went through a full-size staging image, 0 if the kernels wrote the small image directly, -1 if there was none,
+ *      out[4] the bytes of staging image it held (0 when fused). ---- */
+J40HIP_API uint32_t j40hip_frame_set_scale(j40hip_frame *f, int32_t shift);
+J40HIP_API void j40hip_frame_scale(const j40hip_frame *f, int32_t out[5]);
+/* known-answer / measuring hook: k_downscale alone (device/scale_kernels.hip). The full w x h image at src_dev made 1:2 (shift 1) or
+ * 1:4 (shift 2) at out_dev, format J40HIP_U8X4 or J40HIP_U16X4, all rows pixel-aligned. Asynchronous on `stream`. 0, "rnge" (a shift
+ * other than 1 or 2, a stride below the rows' pixels), "Ufm?". */
+J40HIP_API uint32_t j40hip_kat_device_downscale(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, int32_t w, int32_t h, int32_t shift, int32_t format, void *stream);
+
 /* After the stream has been synchronised: first failing section in TOC order -> its 4-char code
  * ("coef", "shrt", "excs", "ans?" ...), 0 if every section decoded cleanly (j40.h:530-534). */
 J40HIP_API uint32_t j40hip_frame_status(j40hip_frame *f);
@@ -538,6 +571,10 @@ J40HIP_API uint32_t j40hip_pipeline_submit(j40hip_pipeline *p, const void *buf, 
  * j40_next_frame (include/j40.h) runs on when several threads are inside the public API at once. */
 typedef void *(*j40hip_output_alloc)(void *ctx, int64_t width, int64_t height, size_t *stride_bytes);
 J40HIP_API uint32_t j40hip_pipeline_run(j40hip_pipeline *p, const void *buf, size_t size, j40hip_output_alloc alloc, void *ctx);
+/* The scale shift (0, 1, 2: j40hip_frame_set_scale) of every image submitted afterwards: the caller's rgba / stride_bytes and the
+ * width and height j40hip_output_alloc is asked for are then the small image's, and so are the device images, the copies back and a
+ * device_output image. "rnge" for a shift outside 0..2, "Usc?" for another shift than the one in force while images are in flight (drain first). */
+J40HIP_API uint32_t j40hip_pipeline_set_scale(j40hip_pipeline *p, int32_t shift);
 /* > 0: a prepared image waits at most `ms` for its batch to fill up while the device has a free batch slot (serving: images arrive
  * one by one); 0 (default): a partial batch is launched only when nothing else is queued */
 J40HIP_API void j40hip_pipeline_set_max_wait_ms(j40hip_pipeline *p, double ms);

@@ -129,6 +129,8 @@ def lib():
         "j40hip_frame_restoration": (None, [vp, vp]), "j40hip_frame_set_restoration": (None, [vp, C.c_int]), "j40hip_frame_sharpness": (C.c_int, [vp, i64, vp]),
         "j40hip_frame_set_alpha": (u32, [vp, C.c_int]), "j40hip_frame_alpha": (None, [vp, vp]),
         "j40hip_frame_set_region": (u32, [vp, i32, i32, i32, i32]), "j40hip_frame_region": (None, [vp, vp]),
+        "j40hip_frame_set_scale": (u32, [vp, i32]), "j40hip_frame_scale": (None, [vp, vp]), "j40hip_pipeline_set_scale": (u32, [vp, i32]),
+        "j40hip_kat_device_downscale": (u32, [vp, sz, vp, sz, i32, i32, i32, i32, vp]),
         "j40hip_kat_device_alpha_merge": (u32, [vp, sz, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
         "j40hip_frame_read_xyb": (u32, [vp, C.c_int, vp]), "j40hip_frame_restoration_ms": (C.c_float, [vp]),
         "j40hip_kat_device_restoration": (u32, [vp, i32, i32, vp, vp, vp, C.c_int, C.c_int, vp]),
@@ -224,18 +226,22 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
+    scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
+    (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
     The public API writes a VarDCT frame's alpha as the environment says (J40HIP_ALPHA=1 keeps it, else A is opaque like the
     reference's). alpha=True keeps it for this call whatever the environment says: the frame goes through the thin C-ABI with
     Frame.set_alpha(1) on device 0 -- "TODO" / "Ual?" where that refuses (Frame.set_alpha)."""
-    if alpha:
+    if alpha or scale:
         try:
             fr = Frame(data)
         except J40Error as e:
             return e.code, None
         try:
-            code = fr.set_alpha(1)
+            code = fr.set_alpha(1) if alpha else ""
+            if not code and scale:
+                code = fr.set_scale(scale)
             if code:
                 return code, None
             fr.set_output_format(fmt)
@@ -525,8 +531,8 @@ class Frame:
         """(err4, pixels [h, w, 4]): uint8, or uint16 when the frame is set to J40_U16X4; with a region set (set_region) h and w are
         the rectangle's and only it comes back from the device"""
         u16 = self.output_format() == J40_U16X4
-        r = self.region()
-        w, h = (r["w"], r["h"]) if r["set"] else (self.width, self.height)
+        r, sc = self.region(), self.scale()
+        w, h = (r["w"], r["h"]) if r["set"] else (sc["width"], sc["height"])   # (shift 0: the frame's own size)
         out = np.zeros((h, w, 4), np.uint16 if u16 else np.uint8)
         code = lib().j40hip_frame_decode_to_host(self.h, out.ctypes.data, w * (8 if u16 else 4))
         return err4(code), out
@@ -548,6 +554,24 @@ class Frame:
         a = np.zeros(12, np.int32)
         lib().j40hip_frame_region(self.h, a.ctypes.data)
         return dict(zip(["x", "y", "w", "h", "gx0", "gy0", "gcols", "grows", "set", "widened", "sections", "varblocks"], a.tolist()))
+
+    # ---- reduced-size decode (include/j40hip.h) ----
+    def set_scale(self, shift):
+        """the decode entry points write the whole frame at 1:2 (shift 1) or 1:4 (shift 2), ceil(width / s) x ceil(height / s) pixels,
+        every sample the rounded mean of its cell of the full decode on coded levels (j40hip_frame_set_scale); 0: full size.
+        Returns "" or the refusal: "rnge" (a shift outside 0..2), "Ulf?" (an LF-only frame), "Usc?" (a region or a partial group
+        range is set, or the handle comes from Sequence.frame)"""
+        shift = int(shift)
+        if not -2 ** 31 <= shift < 2 ** 31:
+            return "rnge"
+        return err4(lib().j40hip_frame_set_scale(self.h, shift))
+
+    def scale(self):
+        """j40hip_frame_scale: shift; width, height at that shift; and of the last decode at a shift above 0: staged (1: through a
+        full-size staging image, 0: the kernels wrote the small image, -1: none yet), staging_bytes"""
+        a = np.zeros(5, np.int32)
+        lib().j40hip_frame_scale(self.h, a.ctypes.data)
+        return dict(zip(["shift", "width", "height", "staged", "staging_bytes"], a.tolist()))
 
     def two_phase_sections(self):
         """how decode_to_host last went: k > 0 = two phases with the k longest sections beside the others, 0 = one, -1 = not yet"""
@@ -1062,6 +1086,11 @@ class Pipeline:
         cb = OUTPUT_ALLOC(alloc)
         code = lib().j40hip_pipeline_run(self.h, buf, len(data), cb, None)
         return err4(code), (got.get("a") if not code else None)
+
+    def set_scale(self, shift):
+        """every image submitted afterwards comes out at 1:2 (1) or 1:4 (2): rgba / stride_bytes of submit, and the arrays run
+        returns, are the small image's (j40hip_pipeline_set_scale). Returns "" or "rnge" / "Usc?" (images in flight: drain first)"""
+        return err4(lib().j40hip_pipeline_set_scale(self.h, int(shift)))
 
     def set_max_wait_ms(self, ms):
         lib().j40hip_pipeline_set_max_wait_ms(self.h, float(ms))

@@ -203,6 +203,9 @@ uint32_t read_whole_file(j40__inner *inner) {
 // J40HIP_FRAMES=1: streams whose first frame is not their last -- animations, layered stills -- are served frame by frame
 // (j40hip_sequence); looked at when an image is first advanced. Without it such a stream is "TODO", as in the reference.
 bool frames_policy() { return j40hip::env_on("J40HIP_FRAMES", false); }
+// J40HIP_SCALE=1|2: every image decodes at 1:2 / 1:4 (j40hip_frame_set_scale): j40_frame_pixels_* then report the small image's width,
+// height and stride. Looked at when an image is first advanced, like J40HIP_FRAMES; unset, 0 or anything else: full size.
+int scale_policy() { const int e = j40hip::env_int("J40HIP_SCALE", 0, INT_MIN, INT_MAX); return e == 1 || e == 2 ? e : 0; }
 int parse_thread_count() {
 	static const int v = [] { const int e = j40hip::env_int("J40HIP_PARSE_THREADS", 0, 0, INT_MAX); return e > 0 ? e : std::max(1, std::min(12, j40hip_cpu_quota())); }();
 	return v;
@@ -231,6 +234,8 @@ int next_sequence_frame(j40__inner *inner, int origin) {
 // the whole decode: RGBA into the image-owned plane
 j40_err advance(j40__inner *inner, int origin) {
 	if (inner->seq || inner->decoded) return 0;
+	const int shift = scale_policy();
+	if (shift && frames_policy()) { inner->origin = origin; return inner->err = code4("Usc?"); }   // sequences are not served at a scale
 	if (!inner->seq_checked && frames_policy()) {
 		// a file is read whole first; a stream that is not a sequence ("Usq?": its first frame is its last), or whose headers fail,
 		// takes the single-frame route below, which decodes it or reports what is wrong with it
@@ -275,7 +280,10 @@ j40_err advance(j40__inner *inner, int origin) {
 	};
 	if (serve) {
 		j40hip_pipeline *p = j40hip_serve_pipeline(device_index(), &err);
-		if (p) err = j40hip_pipeline_run(p, inner->buf, inner->size, serve_alloc, inner);
+		// (the pipeline was made at the scale the environment gave then; an image advanced under another value moves it there, which
+		// the pipeline refuses with "Usc?" while other callers' images are in flight at the old one: both routes give one size)
+		if (p) err = j40hip_pipeline_set_scale(p, shift);
+		if (p && !err) err = j40hip_pipeline_run(p, inner->buf, inner->size, serve_alloc, inner);
 		if (err) { inner->origin = origin; inner->err = err; return err; }
 		inner->decoded = 1;
 		return 0;
@@ -295,9 +303,10 @@ j40_err advance(j40__inner *inner, int origin) {
 	if (!err) {
 		int64_t info[32];
 		j40hip_frame_info(inner->frame, info);
-		err = make_plane(inner, info[0], info[1], u16 ? 8 : 4);
+		err = make_plane(inner, (info[0] + (1 << shift) - 1) >> shift, (info[1] + (1 << shift) - 1) >> shift, u16 ? 8 : 4);
 	}
 	if (!err) err = j40hip_frame_set_output_format(inner->frame, inner->format);
+	if (!err && shift) err = j40hip_frame_set_scale(inner->frame, shift);
 	t2 = now_ms();
 	if (!err) err = j40hip_frame_upload(inner->frame, device_index());
 	t3 = now_ms();

@@ -27,6 +27,11 @@ struct j40hip_frame {
 	int32_t region[4] = {0, 0, 0, 0};                              // x0, y0, w, h
 	int32_t region_widened = 0, region_sections = 0, region_varblocks = 0;
 	bool partial_range = false;      // j40hip_frame_set_group_range narrowed the uploaded frame to some of its groups (excludes a region)
+	// reduced-size decode (j40hip_frame_set_scale): the scale shift the decode entry points write at (0: full size, 1: 1:2, 2: 1:4), and of
+	// the last decode at a shift above 0 whether it went through a full-size staging image and how large that was (j40hip_frame_scale)
+	int32_t scale = 0, scale_staged = -1;
+	int64_t scale_staging_bytes = 0;
+	bool from_sequence = false;      // handed out by j40hip_sequence_frame: the playback owns its size (no scale)
 	int threads = 1;                 // what the frame was parsed with: the plan build at upload may use as many (plan_build.cpp)
 	// backing storage of the plan views (include/j40hip.h)
 	struct Views {

@@ -1,6 +1,8 @@
 // j40_amd/csrc/capi_host.cpp -- host half of the thin C-ABI (include/j40hip.h): parse + stage accessors
 #include <cstdio>
 #include <cstring>
+#include <cstdint>
+#include <algorithm>
 #include <thread>
 #include <type_traits>
 #include "capi.hpp"
@@ -251,6 +253,7 @@ j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err
 		parse_frame(h->cs, h->cs_size, &h->frame, s->threads);
 		h->threads = s->threads;
 		h->output_format = s->output_format;
+		h->from_sequence = true;
 	} catch (const DecodeError &e) { code = e.code; }
 	catch (const std::exception &) { code = E4("!mem"); }
 	h->frame.seq_im = nullptr;   // (copied into the frame)
@@ -304,6 +307,7 @@ uint32_t j40hip_frame_set_region(j40hip_frame *h, int32_t x0, int32_t y0, int32_
 	if (!clear) {
 		if (x0 < 0 || y0 < 0 || w <= 0 || hh <= 0 || (int64_t) x0 + w > W || (int64_t) y0 + hh > H) return j40hip::ERR_RNGE;
 		if (h->partial_range) return E4("Urg?");
+		if (h->scale > 0) return E4("Usc?");   // a region and a scale exclude each other
 	}
 	h->region_set = !clear;
 	h->region[0] = clear ? 0 : x0; h->region[1] = clear ? 0 : y0; h->region[2] = clear ? 0 : w; h->region[3] = clear ? 0 : hh;
@@ -321,6 +325,27 @@ void j40hip_frame_region(const j40hip_frame *h, int32_t out[12]) {
 	out[4] = c.gx0; out[5] = c.gy0; out[6] = c.cols; out[7] = c.rows;
 	out[8] = h->region_set ? 1 : 0;
 	out[9] = h->region_widened; out[10] = h->region_sections; out[11] = h->region_varblocks;
+}
+
+// ---- reduced-size decode (include/j40hip.h) ----
+uint32_t j40hip_frame_set_scale(j40hip_frame *h, int32_t shift) {
+	if (!h || shift < 0 || shift > 2) return j40hip::ERR_RNGE;
+	if (shift > 0) {
+		if (h->frame.lf_only) return E4("Ulf?");
+		if (h->region_set || h->partial_range || h->from_sequence) return E4("Usc?");
+	}
+	if (shift != h->scale) { h->scale_staged = -1; h->scale_staging_bytes = 0; }
+	h->scale = shift;
+	return 0;
+}
+void j40hip_frame_scale(const j40hip_frame *h, int32_t out[5]) {
+	if (!out) return;
+	memset(out, 0, sizeof(int32_t) * 5);
+	out[3] = -1;
+	if (!h) return;
+	const int32_t s = 1 << h->scale;
+	out[0] = h->scale; out[1] = (h->frame.fh.width + s - 1) >> h->scale; out[2] = (h->frame.fh.height + s - 1) >> h->scale;
+	out[3] = h->scale_staged; out[4] = (int32_t) std::min<int64_t>(h->scale_staging_bytes, INT32_MAX);
 }
 
 void j40hip_frame_free(j40hip_frame *f) {

@@ -490,7 +490,7 @@ void j40hip_abatch_free(j40hip_abatch *b) {
 	delete b;
 }
 
-static uint32_t abatch_launch_body(j40hip_abatch *b, j40hip_aframe *const *frames, int n, void *const *rgba_dev, const size_t *stride_bytes, hipStream_t s) {
+static uint32_t abatch_launch_body(j40hip_abatch *b, j40hip_aframe *const *frames, int n, void *const *rgba_dev, const size_t *stride_bytes, hipStream_t s, int32_t shift) {
 	if (!b || n <= 0) return ERR_GPU;
 	if (hipSetDevice(b->device) != hipSuccess) return ERR_GPU;
 	if (b->have_totals && b->nframes > 0) memcpy(b->last_totals, b->verdict_host + 4 * (size_t) b->nframes, sizeof b->last_totals);   // (the launch before has been waited for)
@@ -615,7 +615,7 @@ static uint32_t abatch_launch_body(j40hip_abatch *b, j40hip_aframe *const *frame
 	(void) hipEventRecord(b->ev[2], s);
 	int32_t grids[K2_NUM_BATCH_LAUNCHES];
 	k2_batch_grids(b->have_totals ? b->last_totals : nullptr, cells_total, n, K2_WG_SLOTS, grids);
-	launch_vardct_batch(d_k2, n, (int32_t *) (db + o_tiles), (int32_t *) (db + o_verdict + 16 * (size_t) n), grids, b->large_scratch, s, b->side.data(), (int) b->side.size(), b->fork, b->side_done.data());
+	launch_vardct_batch(d_k2, n, (int32_t *) (db + o_tiles), (int32_t *) (db + o_verdict + 16 * (size_t) n), grids, b->large_scratch, s, b->side.data(), (int) b->side.size(), b->fork, b->side_done.data(), shift);
 	(void) hipEventRecord(b->ev[3], s);
 	launch_plan_verdict(d_builds, d_plans, n, s);
 	if (hipMemcpyAsync(b->verdict_host, db + o_verdict, 16 * (size_t) n + 64, hipMemcpyDeviceToHost, s) != hipSuccess) return ERR_GPU;
@@ -629,8 +629,9 @@ static uint32_t abatch_launch_body(j40hip_abatch *b, j40hip_aframe *const *frame
 	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 }
 
-uint32_t j40hip_abatch_launch(j40hip_abatch *b, j40hip_aframe *const *frames, int n, void *const *rgba_dev, const size_t *stride_bytes, hipStream_t stream) {
-	try { return abatch_launch_body(b, frames, n, rgba_dev, stride_bytes, stream); } catch (const std::exception &) { return ERR_MEM; }
+uint32_t j40hip_abatch_launch(j40hip_abatch *b, j40hip_aframe *const *frames, int n, void *const *rgba_dev, const size_t *stride_bytes, hipStream_t stream, int32_t shift) {
+	if (shift < 0 || shift > 2) return ERR_RNGE;
+	try { return abatch_launch_body(b, frames, n, rgba_dev, stride_bytes, stream, shift); } catch (const std::exception &) { return ERR_MEM; }
 }
 
 void j40hip_abatch_result(const j40hip_abatch *b, int i, uint32_t *code, int *redo) {

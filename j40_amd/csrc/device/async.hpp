@@ -34,7 +34,8 @@ j40hip_abatch *j40hip_abatch_create(int device);
 void j40hip_abatch_free(j40hip_abatch *b);
 // Enqueues the whole decode of `n` prepared frames on `stream`; frames[i] writes RGBA u8x4 to rgba_dev[i] with stride_bytes[i].
 // Returns 0 or "!gpu" / "!mem". The results are readable once `stream` has been waited for.
-uint32_t j40hip_abatch_launch(j40hip_abatch *b, j40hip_aframe *const *frames, int n, void *const *rgba_dev, const size_t *stride_bytes, hipStream_t stream);
+// shift: the scale shift of every frame of the batch (rgba_dev / stride_bytes are then the small images')
+uint32_t j40hip_abatch_launch(j40hip_abatch *b, j40hip_aframe *const *frames, int n, void *const *rgba_dev, const size_t *stride_bytes, hipStream_t stream, int32_t shift = 0);
 // frame i of the last launch: its verdict (0 or the 4-char code of the first failing section in file order) and whether the frame
 // has to be decoded again on the single-frame path (an LfGroup section the device decoder cannot take, or an event region that
 // overflowed)

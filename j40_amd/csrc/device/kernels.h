@@ -19,8 +19,9 @@ void launch_store_group_rects(const uint32_t *order, int32_t k, int32_t gcolumns
 uint32_t hf_lanes_lds_bytes(const HfLaunchInfo &info);
 void launch_hf_entropy_lanes(const DevPlan *plans, const HfLaneWork *work, int32_t num_work, bool tables_in_lds, uint32_t lds_bytes, hipStream_t stream);
 void launch_hf_lanes(const DevPlan *plans, const HfLaneWork *work, int32_t num_work, int32_t waves_per_wg, uint32_t lds_bytes, hipStream_t stream, hipEvent_t started = nullptr, hipEvent_t stopped = nullptr, uint32_t *queue = nullptr);
-// rgba16: the 16-bit output (J40_U16X4, 8 bytes a pixel; idct_dev.h xyb_to_rgba16) instead of u8x4
-void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
+// rgba16: the 16-bit output (J40_U16X4, 8 bytes a pixel; idct_dev.h xyb_to_rgba16) instead of u8x4; shift: the scale shift (1, 2: the
+// kernels write the 1:2 / 1:4 image, scale_dev.h; `rgba` and `stride` are then the small image's)
+void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false, int32_t shift = 0);
 
 
 // every frame of a batch: one persistent launch per class of transforms, spread over `nside` side streams that fork from and join
@@ -28,8 +29,8 @@ void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock 
 // K2_NUM_BATCH_LAUNCHES ints (out: tiles per launch); grids: workgroups per launch, from k2_batch_grids
 enum { K2_NUM_BATCH_LAUNCHES = 16, K2_LARGE_WGS = 256, K2_WG_SLOTS = 32768 };   // K2_WG_SLOTS: the most workgroups a launch gets (k2_batch_grids' wg_slots)
 void k2_batch_grids(const int32_t *last_totals, size_t cells_total, int32_t nframes, int32_t wg_slots, int32_t *grids);
-void launch_vardct_batch(const K2Frame *frames_dev, int32_t nframes, int32_t *tile_prefix_dev, int32_t *totals_dev, const int32_t *grids, float *large_scratch, hipStream_t stream, hipStream_t *side, int nside, hipEvent_t fork, hipEvent_t *side_done);
-void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
+void launch_vardct_batch(const K2Frame *frames_dev, int32_t nframes, int32_t *tile_prefix_dev, int32_t *totals_dev, const int32_t *grids, float *large_scratch, hipStream_t stream, hipStream_t *side, int nside, hipEvent_t fork, hipEvent_t *side_done, int32_t shift = 0);
+void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false, int32_t shift = 0);
 
 // the restoration filters (device/restore_kernels.h, restore_dev.h): the pixel kernels with the samples left in XYB (three float planes of
 // `stride` bytes per row, one behind the other), the reciprocal-sigma plane, Gaborish + the edge-preserving filter's steps between
@@ -86,7 +87,12 @@ void launch_inverse_squeeze(const int16_t *avg, const int16_t *res, int16_t *out
 void launch_pack_planes_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
 // alpha_kernels.hip: the kept alpha channel of a VarDCT frame into rectangle (x0, y0, w, h) of pixels already written
 void launch_alpha_merge(const int16_t *plane, int32_t pitch, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16);
-void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
+// shift: the scale shift; 1, 2: ceil(width / s) x ceil(height / s) pixels, each the mean of its cell's rendered samples (scale_dev.h)
+void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false, int32_t shift = 0);
+
+// reduced-size decode (device/scale_kernels.hip, scale_dev.h): the full W x H image at src made 1:2 (shift 1) or 1:4 (shift 2) at dst,
+// pixel_bytes 4 or 8, every row pixel-aligned
+void launch_downscale(const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int32_t W, int32_t H, int32_t shift, int32_t pixel_bytes, hipStream_t stream);
 
 // region decode (device/region_kernels.hip, region_dev.h). launch_region_index: the group-major index of the `count` varblocks of
 // `sorted` -- cursor: nkeys = groups * REGION_KEYS words of scratch, seg_start: nkeys + 1 words, index: count words.

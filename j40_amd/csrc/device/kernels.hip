@@ -24,6 +24,7 @@
 #include "k2_iter_dev.h"
 #include "hf_uni_dev.h"
 #include "restore_dev.h"
+#include "scale_dev.h"
 #include "kernels.h"
 #include "../env.hpp"
 
@@ -589,11 +590,47 @@ template <int NB> struct K2Ahead {
 // colour tail to four u16 (xyb_to_rgba16, J40_U16X4), 8 bytes per pixel as one store (single-frame launches only)
 enum class OutMode { RGBA8, XYB, RGBA16 };
 template <OutMode OUT> constexpr int out_bytes() { return OUT == OutMode::RGBA16 ? 8 : 4; }   // bytes a pixel (a sample, XYB) takes in the output
+// Reduced-size output (j40hip_frame_set_scale; scale_dev.h), the kernels' second output parameter K = the scale shift: in the colour + pack
+// phase a lane owns an OUTPUT pixel of a block. It reads its s x s samples of the three planes from the tiles, runs the colour tail of the
+// full decode on each, adds the packed pixels up (ScaleAcc) and stores their rounded mean at (py >> K, px >> K) + its place in the block:
+// the bytes k_downscale makes of the full image, without the full image. A varblock starts at a multiple of 8 pixels, so no cell
+// straddles two of them; effw / effh clip the cells of the frame's right and bottom edges. K = 0 is the code it always was.
+template <OutMode OUT> __device__ __forceinline__ typename ScaleAcc<out_bytes<OUT>()>::pixel colour_tail(float sx, float sy, float sb, const ColourConsts &cc, const J40_LDS float *thr) {
+	if constexpr (OUT == OutMode::RGBA16) return xyb_to_rgba16(sx, sy, sb, cc, thr);
+	else return xyb_to_rgba8(sx, sy, sb, cc, thr);
+}
+// the mean of the cw x ch samples at t (three planes `plane` floats apart, `pitch` floats a row), K > 0
+template <OutMode OUT, int K> __device__ __forceinline__ typename ScaleAcc<out_bytes<OUT>()>::pixel scaled_pixel(const float *t, int32_t plane, int32_t pitch, int32_t cw, int32_t ch, const ColourConsts &cc, const J40_LDS float *thr) {
+	ScaleAcc<out_bytes<OUT>()> acc;
+	acc.clear();
+#pragma unroll 1
+	for (int32_t dy = 0; dy < ch; ++dy) {
+#pragma unroll 1
+		for (int32_t dx = 0; dx < cw; ++dx) { const float *q = t + dy * pitch + dx; acc.add(colour_tail<OUT>(q[0], q[plane], q[2 * plane], cc, thr)); }
+	}
+	return acc.mean(cw * ch, K);
+}
+// K = 2, the lane split: a lane per (output pixel, cell row) -- four neighbouring lanes own one output pixel, each runs the colour tail on
+// its row of the cell (row r = lane & 3; a row below the frame's edge adds nothing), and the four partial sums meet by two exchanges
+// between neighbours. Every lane of the four gets the pixel; lane 0 of them stores it. With a lane per output pixel the 8 x 8 classes
+// had 64 output pixels a tile for 256 lanes and 16 tails a lane: the pixel stage ran 18 % slower than at full size. All four lanes of a
+// pixel must make the call (the caller's work count is a multiple of four and its early-outs depend on the pixel alone).
+template <OutMode OUT> __device__ __forceinline__ typename ScaleAcc<out_bytes<OUT>()>::pixel scaled_pixel_by_rows(const float *row, int32_t plane, int32_t cw, bool has_row, int32_t n, const ColourConsts &cc, const J40_LDS float *thr) {
+	ScaleAcc<out_bytes<OUT>()> acc;
+	acc.clear();
+	if (has_row) {
+#pragma unroll 1
+		for (int32_t dx = 0; dx < cw; ++dx) acc.add(colour_tail<OUT>(row[dx], row[plane + dx], row[2 * plane + dx], cc, thr));
+	}
+	acc.lo += __shfl_xor(acc.lo, 1); acc.hi += __shfl_xor(acc.hi, 1);
+	acc.lo += __shfl_xor(acc.lo, 2); acc.hi += __shfl_xor(acc.hi, 2);
+	return acc.mean(n, 2);
+}
 __device__ __forceinline__ void store_xyb(uint8_t *base, size_t off, size_t plane_bytes, float sx, float sy, float sb) {
 	*(float *) (base + off) = sx; *(float *) (base + plane_bytes + off) = sy; *(float *) (base + 2 * plane_bytes + off) = sb;
 }
 
-template <int LOGR, int LOGC, int NB, bool BATCH, OutMode OUT = OutMode::RGBA8>
+template <int LOGR, int LOGC, int NB, bool BATCH, OutMode OUT = OutMode::RGBA8, int K = 0>
 __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU : 1)) k_vardct_dct(DevPlan plan_arg, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, uint8_t *rgba, size_t stride_bytes,
 		const K2Frame *batch, const int32_t *tile_prefix, int32_t nframes, int32_t class_a, int32_t class_b) {
 	constexpr int R = 1 << LOGR, C = 1 << LOGC, P = C + 1, TILE = R * P;
@@ -656,7 +693,7 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 			g.coeff_base = vb.coeff_base; g.llf_base = vb.llf_base;
 			g.mult[1] = vb.mult1; g.mult[0] = vb.mult1 * x_qm_mul; g.mult[2] = vb.mult1 * b_qm_mul;   // (varblock_geometry with the frame's factors at hand; j40.h:7078-7080)
 			g.kx_hf = vb.kx_hf; g.kb_hf = vb.kb_hf; g.px = vb.px; g.py = vb.py; g.effw = vb.effw; g.effh = vb.effh;
-			geom[tid] = g; g_out[tid] = (size_t) g.py * stride_bytes + (size_t) g.px * out_bytes<OUT>();
+			geom[tid] = g; g_out[tid] = (size_t) (g.py >> K) * stride_bytes + (size_t) (g.px >> K) * out_bytes<OUT>();
 			if (sparse) { g_be[tid][0] = be0; g_be[tid][1] = be1; g_be[tid][2] = be2; g_be[tid][3] = be3; nevents = be1 + be2 + be3; }
 		}
 		if (!(BATCH && J40_K2_AHEAD)) K2_PREFETCH_BLK(NB);
@@ -714,6 +751,29 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 		__syncthreads();
 		K2_PHASE(4);
 		// ---- colour + pack: a lane owns pixel position (y, x) for every block of the workgroup ----
+		if constexpr (K == 2) {   // ... 1:4: four lanes an output pixel, a cell row each (scaled_pixel_by_rows)
+			static_assert(OUT != OutMode::XYB, "the XYB planes stay full size");
+			constexpr int OC = C >> 2, ON = N >> 4;
+			for (int32_t w = tid; w < nb * ON * 4; w += nthreads) {   // (nthreads and the count are multiples of four: a pixel's lanes stay together)
+				const int32_t r = w & 3, q = w >> 2, b = q / ON, o = q % ON, oy = o / OC, ox = o % OC;
+				const VbGeom &g = geom[b];
+				const int32_t cw = scale_span(ox, g.effw, 2), ch = scale_span(oy, g.effh, 2);
+				if (cw <= 0 || ch <= 0) continue;
+				const auto px = scaled_pixel_by_rows<OUT>(lds + (size_t) b * 3 * TILE + ((oy << 2) + r) * P + (ox << 2), TILE, cw, r < ch, cw * ch, cc, srgb_thr);
+				if (r == 0) __builtin_nontemporal_store(px, (decltype(px) *) (rgba + g_out[b] + (size_t) oy * stride_bytes + (size_t) ox * out_bytes<OUT>()));
+			}
+		} else if constexpr (K > 0) {   // ... 1:2: output pixel w of the tile's blocks (scaled_pixel)
+			static_assert(OUT != OutMode::XYB, "the XYB planes stay full size");
+			constexpr int OC = C >> K, ON = N >> (2 * K);
+			for (int32_t w = tid; w < nb * ON; w += nthreads) {
+				const int32_t b = w / ON, o = w % ON, oy = o / OC, ox = o % OC;
+				const VbGeom &g = geom[b];
+				const int32_t cw = scale_span(ox, g.effw, K), ch = scale_span(oy, g.effh, K);
+				if (cw <= 0 || ch <= 0) continue;
+				const auto px = scaled_pixel<OUT, K>(lds + (size_t) b * 3 * TILE + (oy << K) * P + (ox << K), TILE, P, cw, ch, cc, srgb_thr);
+				__builtin_nontemporal_store(px, (decltype(px) *) (rgba + g_out[b] + (size_t) oy * stride_bytes + (size_t) ox * out_bytes<OUT>()));
+			}
+		} else {
 #pragma unroll
 		for (int k = 0; k < PER; ++k) {
 			const int32_t p = N >= 256 ? tid + 256 * k : tid % N;
@@ -729,6 +789,7 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 				__builtin_nontemporal_store(px, (uint32_t *) (rgba + g_out[b] + in_block));   // written once, never read here: keep it out of the L2's way (-2 %)
 			}
 		}
+		}   // (K == 0: the full-size tail)
 		K2_PHASE(5);
 		if (!BATCH) break;
 		__syncthreads();   // the next tile reuses geom / the LDS tiles
@@ -773,7 +834,7 @@ template <int SET> __device__ __forceinline__ void special8_set_phase1(int sel, 
 	else if (SET == 2) { if (sel == 12) wide_halves_phase1(lane, mid, dst, hs); else tall_halves_phase1(lane, mid, dst, hs); }
 	else afv_phase1(lane, mid, dst, hs, (sel - 14) & 1, (sel - 14) >> 1);
 }
-template <int NB, bool BATCH, int SET, OutMode OUT = OutMode::RGBA8>
+template <int NB, bool BATCH, int SET, OutMode OUT = OutMode::RGBA8, int K = 0>
 __device__ __forceinline__ void vardct_special_body(DevPlan plan_arg, const DevVarblock *list, int32_t count, uint8_t *rgba, size_t stride_bytes, const K2Frame *batch, const int32_t *tile_prefix, int32_t nframes,
 		int32_t class_a, int32_t class_b) {
 	constexpr int P = SP8_TILE;
@@ -867,6 +928,26 @@ __device__ __forceinline__ void vardct_special_body(DevPlan plan_arg, const DevV
 		}
 		__syncthreads();
 		K2_PHASE(3);
+		if constexpr (K == 2) {   // 1:4: four lanes an output pixel, a cell row each (k_vardct_dct); the block's four pixels on sixteen lanes
+			for (int32_t w = tid; w < nb * 16; w += nthreads) {
+				const int32_t r = w & 3, q = w >> 2, b = q >> 2, oy = (q >> 1) & 1, ox = q & 1;
+				const VbGeom &g = geom[b];
+				const int32_t cw = scale_span(ox, g.effw, 2), ch = scale_span(oy, g.effh, 2);
+				if (cw <= 0 || ch <= 0) continue;
+				const auto px = scaled_pixel_by_rows<OUT>(tiles + (size_t) b * 3 * P + SP8((((oy << 2) + r) << 3) + (ox << 2)), P, cw, r < ch, cw * ch, cc, srgb_thr);
+				if (r == 0) __builtin_nontemporal_store(px, (decltype(px) *) (rgba + (size_t) ((g.py >> 2) + oy) * stride_bytes + (size_t) ((g.px >> 2) + ox) * out_bytes<OUT>()));
+			}
+		} else if constexpr (K > 0) {   // 1:2: a lane an output pixel (k_vardct_dct); the cell's samples are SP8_PITCH apart down a column
+			constexpr int OC = 8 >> K, ON = 64 >> (2 * K);
+			for (int32_t w = tid; w < nb * ON; w += nthreads) {
+				const int32_t b = w / ON, o = w % ON, oy = o / OC, ox = o % OC;
+				const VbGeom &g = geom[b];
+				const int32_t cw = scale_span(ox, g.effw, K), ch = scale_span(oy, g.effh, K);
+				if (cw <= 0 || ch <= 0) continue;
+				const auto px = scaled_pixel<OUT, K>(tiles + (size_t) b * 3 * P + SP8(((oy << K) << 3) + (ox << K)), P, SP8_PITCH, cw, ch, cc, srgb_thr);
+				__builtin_nontemporal_store(px, (decltype(px) *) (rgba + (size_t) ((g.py >> K) + oy) * stride_bytes + (size_t) ((g.px >> K) + ox) * out_bytes<OUT>()));
+			}
+		} else {
 		for (int32_t w = tid; w < nb * 64; w += nthreads) {
 			const int32_t b = w >> 6, i = w & 63, y = i >> 3, x = i & 7;
 			const VbGeom &g = geom[b];
@@ -877,6 +958,7 @@ __device__ __forceinline__ void vardct_special_body(DevPlan plan_arg, const DevV
 			const uint32_t px = xyb_to_rgba8(t[0], t[P], t[2 * P], cc, srgb_thr);
 			*(uint32_t *) (rgba + (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4) = px;
 		}
+		}   // (K == 0: the full-size tail)
 		K2_PHASE(5);
 		if (!BATCH) break;
 		__syncthreads();
@@ -889,12 +971,13 @@ __device__ __forceinline__ void vardct_special_body(DevPlan plan_arg, const DevV
 }
 
 // the three kernels: the sets' transforms need 98 / 106 / 118 registers left alone; sets 1 and 2 fit the 64 that eight wavefronts per
-// SIMD leave (one register spilled / none), the AFV set gets the 96 of five (J40_K2_SPECIAL_WAVES, J40_K2_SPECIAL_WAVES_AFV)
+// SIMD leave (one register spilled / none), the AFV set gets the 96 of five (J40_K2_SPECIAL_WAVES, J40_K2_SPECIAL_WAVES_AFV). The
+// reduced-size modes (K > 0) keep an accumulator and a cell's extent live across the colour tail: one wavefront fewer rather than scratch.
 #define J40_SPECIAL_KERNEL(NAME_, SET_, WAVES_) \
-template <int NB, bool BATCH, OutMode OUT = OutMode::RGBA8> \
-__global__ void __launch_bounds__(J40_K2_SPECIAL_THREADS) __attribute__((amdgpu_waves_per_eu(WAVES_))) NAME_(DevPlan plan_arg, const DevVarblock *list, int32_t count, uint8_t *rgba, size_t stride_bytes, const K2Frame *batch, \
+template <int NB, bool BATCH, OutMode OUT = OutMode::RGBA8, int K = 0> \
+__global__ void __launch_bounds__(J40_K2_SPECIAL_THREADS) __attribute__((amdgpu_waves_per_eu(K > 0 ? WAVES_ - 1 : WAVES_))) NAME_(DevPlan plan_arg, const DevVarblock *list, int32_t count, uint8_t *rgba, size_t stride_bytes, const K2Frame *batch, \
 		const int32_t *tile_prefix, int32_t nframes, int32_t class_a, int32_t class_b) { \
-	vardct_special_body<NB, BATCH, SET_, OUT>(plan_arg, list, count, rgba, stride_bytes, batch, tile_prefix, nframes, class_a, class_b); \
+	vardct_special_body<NB, BATCH, SET_, OUT, K>(plan_arg, list, count, rgba, stride_bytes, batch, tile_prefix, nframes, class_a, class_b); \
 }
 J40_SPECIAL_KERNEL(k_vardct_special_123, 1, J40_K2_SPECIAL_WAVES)
 J40_SPECIAL_KERNEL(k_vardct_special_halves, 2, J40_K2_SPECIAL_WAVES)
@@ -920,7 +1003,7 @@ struct WorkgroupExec {
 #ifndef J40_LARGE_THREADS
 #define J40_LARGE_THREADS 512
 #endif
-template <bool BATCH, OutMode OUT = OutMode::RGBA8>
+template <bool BATCH, OutMode OUT = OutMode::RGBA8, int K = 0>
 __global__ void __launch_bounds__(J40_LARGE_THREADS) k_vardct_large(DevPlan plan_arg, const DevVarblock *list, int32_t count, float *scratch, uint8_t *rgba, size_t stride_bytes, const K2Frame *batch, const int32_t *tile_prefix, int32_t nframes,
 		int32_t class_a, int32_t class_b) {
 	const int32_t tid = threadIdx.x, nthreads = blockDim.x;
@@ -940,6 +1023,19 @@ __global__ void __launch_bounds__(J40_LARGE_THREADS) k_vardct_large(DevPlan plan
 		const VbGeom g = varblock_geometry(plan, vb);
 		WorkgroupExec ex;
 		const LargeSamples S = large_block(ex, plan, vb, g, panels, A, B, c_half_secants);
+		if constexpr (K > 0) {   // reduced size: a lane an output pixel (k_vardct_dct), the samples where large_block left them
+			for (int32_t o = tid; o < size >> (2 * K); o += nthreads) {
+				const int32_t oy = o >> (log_columns - K), ox = o & ((C >> K) - 1), y = oy << K, x = ox << K;
+				const int32_t cw = scale_span(ox, g.effw, K), ch = scale_span(oy, g.effh, K);
+				if (cw <= 0 || ch <= 0) continue;
+				ScaleAcc<out_bytes<OUT>()> acc;
+				acc.clear();
+				for (int32_t dy = 0; dy < ch; ++dy) for (int32_t dx = 0; dx < cw; ++dx)
+					acc.add(colour_tail<OUT>(S.p[0][(y + dy) * S.pitch[0] + x + dx], S.p[1][(y + dy) * S.pitch[1] + x + dx], S.p[2][(y + dy) * S.pitch[2] + x + dx], cc, srgb_thr));
+				const auto px = acc.mean(cw * ch, K);
+				__builtin_nontemporal_store(px, (decltype(px) *) (rgba + (size_t) ((g.py >> K) + oy) * stride_bytes + (size_t) ((g.px >> K) + ox) * out_bytes<OUT>()));
+			}
+		} else {
 		for (int32_t i = tid; i < size; i += nthreads) {
 			const int32_t y = i >> log_columns, x = i & (C - 1);
 			if (y >= g.effh || x >= g.effw) continue;
@@ -948,6 +1044,7 @@ __global__ void __launch_bounds__(J40_LARGE_THREADS) k_vardct_large(DevPlan plan
 			const uint32_t px = xyb_to_rgba8(S.p[0][y * S.pitch[0] + x], S.p[1][y * S.pitch[1] + x], S.p[2][y * S.pitch[2] + x], cc, srgb_thr);
 			*(uint32_t *) (rgba + (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4) = px;
 		}
+		}   // (K == 0: the full-size tail)
 		if (!BATCH) break;
 		__threadfence_block(); __syncthreads();   // the next block reuses the scratch and the LDS tiles
 	}
@@ -1030,10 +1127,41 @@ void launch_hf_entropy(const DevPlan &plan, const HfLaunchInfo &info, int32_t fi
 // `batch` = nullptr: one frame, everything in the kernel arguments. Otherwise a persistent launch over the tiles of one class of
 // `nframes` frames (k2_bind): `grid` workgroups, tile_prefix = this launch's row of the table k_k2_tiles built; plan / list /
 // count / rgba / stride are then ignored, `large_scratch` holds 6 * 65536 floats per workgroup of the launch.
-struct K2Launch { const K2Frame *batch; const int32_t *tile_prefix; int32_t nframes, class_a, class_b, grid; OutMode out; };   // out: XYB / RGBA16 for single-frame launches only
+struct K2Launch { const K2Frame *batch; const int32_t *tile_prefix; int32_t nframes, class_a, class_b, grid; OutMode out; int32_t shift; };   // out: XYB / RGBA16 for single-frame launches only; shift: the scale shift (RGBA8 / RGBA16)
+
+// the reduced-size instantiations (K = 1, 2): single-frame launches in both formats, batch-wide launches in u8x4 (what the pipeline writes)
+template <int LOGR, int LOGC, int NB, bool BATCH, OutMode OUT, int K>
+static void launch_dct_scaled_as(const DevPlan &plan, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
+	constexpr size_t lds_bytes = (size_t) NB * 3 * (1 << LOGR) * ((1 << LOGC) + 1) * sizeof(float);
+	static bool configured = false;
+	if (!configured) { (void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, BATCH, OUT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes); configured = true; }
+	if (BATCH) hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, BATCH, OUT, K>), dim3((unsigned) bl.grid), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
+	else hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, BATCH, OUT, K>), dim3((unsigned) ((count + NB - 1) / NB)), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, nullptr, 1, 0, 0);
+}
+template <int LOGR, int LOGC, int NB>
+static void launch_dct_scaled(const DevPlan &plan, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
+#define J40_DCT_SCALED(BATCH_, OUT_) do { \
+		if (bl.shift == 1) launch_dct_scaled_as<LOGR, LOGC, NB, BATCH_, OUT_, 1>(plan, list, count, param_idx, order_idx, rgba, stride, bl, stream); \
+		else launch_dct_scaled_as<LOGR, LOGC, NB, BATCH_, OUT_, 2>(plan, list, count, param_idx, order_idx, rgba, stride, bl, stream); \
+	} while (0)
+	if (bl.batch) J40_DCT_SCALED(true, OutMode::RGBA8);
+	else if (bl.out == OutMode::RGBA16) J40_DCT_SCALED(false, OutMode::RGBA16);
+	else J40_DCT_SCALED(false, OutMode::RGBA8);
+#undef J40_DCT_SCALED
+}
+template <bool BATCH, OutMode OUT, int K>
+static void launch_large_scaled_as(const DevPlan &plan, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
+	constexpr size_t lds_bytes = 2 * (size_t) LARGE_PANEL_FLOATS * sizeof(float);
+	static bool configured = false;
+	if (!configured) { (void) hipFuncSetAttribute((const void *) k_vardct_large<BATCH, OUT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes); configured = true; }
+	if (BATCH) hipLaunchKernelGGL((k_vardct_large<BATCH, OUT, K>), dim3((unsigned) bl.grid), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
+	else hipLaunchKernelGGL((k_vardct_large<BATCH, OUT, K>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
+}
+
 
 template <int LOGR, int LOGC, int NB>
 static void launch_dct(const DevPlan &plan, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
+	if (bl.shift > 0) { launch_dct_scaled<LOGR, LOGC, NB>(plan, list, count, param_idx, order_idx, rgba, stride, bl, stream); return; }
 	constexpr size_t lds_bytes = (size_t) NB * 3 * (1 << LOGR) * ((1 << LOGC) + 1) * sizeof(float);
 	static bool configured = false;
 	if (!configured) {
@@ -1066,7 +1194,17 @@ static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const 
 	case 18: launch_dct<6, 6, 1>(plan, list, count, 11, 7, rgba, stride, bl, stream); break;
 	case 19: launch_dct<6, 5, 1>(plan, list, count, 12, 8, rgba, stride, bl, stream); break;
 	case 20: launch_dct<5, 6, 1>(plan, list, count, 12, 8, rgba, stride, bl, stream); break;
+#define J40_SPECIAL_SCALED(KERNEL_, BATCH_, OUT_, K_) do { \
+		if (BATCH_) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, BATCH_, OUT_, K_>), dim3((unsigned) bl.grid), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b); \
+		else hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, BATCH_, OUT_, K_>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
+	} while (0)
 #define J40_LAUNCH_SPECIAL(KERNEL_) do { \
+		if (bl.shift > 0) { \
+			if (bl.batch) { if (bl.shift == 1) J40_SPECIAL_SCALED(KERNEL_, true, OutMode::RGBA8, 1); else J40_SPECIAL_SCALED(KERNEL_, true, OutMode::RGBA8, 2); } \
+			else if (bl.out == OutMode::RGBA16) { if (bl.shift == 1) J40_SPECIAL_SCALED(KERNEL_, false, OutMode::RGBA16, 1); else J40_SPECIAL_SCALED(KERNEL_, false, OutMode::RGBA16, 2); } \
+			else { if (bl.shift == 1) J40_SPECIAL_SCALED(KERNEL_, false, OutMode::RGBA8, 1); else J40_SPECIAL_SCALED(KERNEL_, false, OutMode::RGBA8, 2); } \
+			break; \
+		} \
 		if (!bl.batch && bl.out == OutMode::XYB) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, false, OutMode::XYB>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
 		else if (!bl.batch && bl.out == OutMode::RGBA16) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, false, OutMode::RGBA16>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
 		else if (bl.batch) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, true>), dim3((unsigned) bl.grid), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b); \
@@ -1076,7 +1214,14 @@ static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const 
 	case 12: case 13: J40_LAUNCH_SPECIAL(k_vardct_special_halves); break;
 	case 14: case 15: case 16: case 17: J40_LAUNCH_SPECIAL(k_vardct_special_afv); break;
 #undef J40_LAUNCH_SPECIAL
+#undef J40_SPECIAL_SCALED
 	default:
+		if (bl.shift > 0) {
+			if (bl.batch) { if (bl.shift == 1) launch_large_scaled_as<true, OutMode::RGBA8, 1>(plan, list, count, large_scratch, rgba, stride, bl, stream); else launch_large_scaled_as<true, OutMode::RGBA8, 2>(plan, list, count, large_scratch, rgba, stride, bl, stream); }
+			else if (bl.out == OutMode::RGBA16) { if (bl.shift == 1) launch_large_scaled_as<false, OutMode::RGBA16, 1>(plan, list, count, large_scratch, rgba, stride, bl, stream); else launch_large_scaled_as<false, OutMode::RGBA16, 2>(plan, list, count, large_scratch, rgba, stride, bl, stream); }
+			else { if (bl.shift == 1) launch_large_scaled_as<false, OutMode::RGBA8, 1>(plan, list, count, large_scratch, rgba, stride, bl, stream); else launch_large_scaled_as<false, OutMode::RGBA8, 2>(plan, list, count, large_scratch, rgba, stride, bl, stream); }
+			break;
+		}
 		{
 			constexpr size_t lds_bytes = 2 * (size_t) LARGE_PANEL_FLOATS * sizeof(float);
 			static bool configured = false;
@@ -1100,8 +1245,8 @@ static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const 
 		break;
 	}
 }
-void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
-	launch_vardct_class_impl(plan, dctsel, list, count, large_scratch, rgba, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, rgba16 ? OutMode::RGBA16 : OutMode::RGBA8}, stream);
+void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16, int32_t shift) {
+	launch_vardct_class_impl(plan, dctsel, list, count, large_scratch, rgba, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, rgba16 ? OutMode::RGBA16 : OutMode::RGBA8, shift}, stream);
 }
 
 // known-answer hook: the renderer's per-sample tail (sRGB transfer + conversion, j40.h:7213-7240 / 7925-7935)
@@ -1144,14 +1289,14 @@ static bool class_range(int d, int *a, int *b) {
 	*a = d; *b = d == 1 ? 4 : d == 12 ? 14 : d == 14 ? 18 : d + 1;
 	return true;
 }
-void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
+void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16, int32_t shift) {
 	for (int d = 0, a, b; d < 27; ++d) if (class_range(d, &a, &b))
-		launch_vardct_class(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, rgba, stride, stream, rgba16);
+		launch_vardct_class(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, rgba, stride, stream, rgba16, shift);
 }
 // the same with the samples left in XYB: three float planes of the frame from `xyb`, `stride` bytes per row (store_xyb)
 void launch_vardct_frame_xyb(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, float *xyb, size_t stride, hipStream_t stream) {
 	for (int d = 0, a, b; d < 27; ++d) if (class_range(d, &a, &b))
-		launch_vardct_class_impl(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, (uint8_t *) xyb, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, OutMode::XYB}, stream);
+		launch_vardct_class_impl(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, (uint8_t *) xyb, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, OutMode::XYB, 0}, stream);
 }
 
 // ---- the same for every frame of a batch at once: one persistent launch per class ----
@@ -1203,13 +1348,13 @@ void k2_batch_grids(const int32_t *last_totals, size_t cells_total, int32_t nfra
 
 // grids: workgroups per launch (k2_batch_grids); large_scratch: 6 * 65536 floats per workgroup of the last launch (K2_LARGE_WGS of
 // them); totals_dev: K2_NUM_BATCH_LAUNCHES ints, the tiles each launch found
-void launch_vardct_batch(const K2Frame *frames_dev, int32_t nframes, int32_t *tile_prefix_dev, int32_t *totals_dev, const int32_t *grids, float *large_scratch, hipStream_t stream, hipStream_t *side, int nside, hipEvent_t fork, hipEvent_t *side_done) {
+void launch_vardct_batch(const K2Frame *frames_dev, int32_t nframes, int32_t *tile_prefix_dev, int32_t *totals_dev, const int32_t *grids, float *large_scratch, hipStream_t stream, hipStream_t *side, int nside, hipEvent_t fork, hipEvent_t *side_done, int32_t shift) {
 	const DevPlan none = DevPlan();
 	hipLaunchKernelGGL(k_k2_tiles, dim3(1), dim3(32), 0, stream, frames_dev, nframes, tile_prefix_dev, totals_dev, K2_TABLE);
 	if (nside > 0) { (void) hipEventRecord(fork, stream); for (int k = 0; k < nside; ++k) (void) hipStreamWaitEvent(side[k], fork, 0); }
 	for (int l = 0; l < K2_NUM_BATCH_LAUNCHES; ++l) {
 		const auto &L = K2_TABLE.l[l];
-		launch_vardct_class_impl(none, L.a, nullptr, 0, large_scratch, nullptr, 0, K2Launch{frames_dev, tile_prefix_dev + (size_t) l * (size_t) (nframes + 1), nframes, L.a, L.b, grids[l], OutMode::RGBA8}, nside > 0 ? side[K2_LAUNCH_STREAM[l] % nside] : stream);
+		launch_vardct_class_impl(none, L.a, nullptr, 0, large_scratch, nullptr, 0, K2Launch{frames_dev, tile_prefix_dev + (size_t) l * (size_t) (nframes + 1), nframes, L.a, L.b, grids[l], OutMode::RGBA8, shift}, nside > 0 ? side[K2_LAUNCH_STREAM[l] % nside] : stream);
 	}
 	if (nside > 0) for (int k = 0; k < nside; ++k) { (void) hipEventRecord(side_done[k], side[k]); (void) hipStreamWaitEvent(stream, side_done[k], 0); }
 }

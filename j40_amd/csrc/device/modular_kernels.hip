@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include "modular_dev.h"
 #include "squeeze_dev.h"
+#include "scale_dev.h"
 #include "kernels.h"
 
 namespace j40hip {
@@ -203,9 +204,26 @@ __global__ void __launch_bounds__(256) k_unsqueeze_v(const int16_t *__restrict__
 	if (ah > rh) out[(size_t) (2 * rh) * pitch + (size_t) x] = avg[(size_t) rh * pitch + (size_t) x];
 }
 
+// K: the scale shift (scale_dev.h). K > 0: a lane per OUTPUT pixel renders each sample of its cell (clamp, then the 8-bit rule) and stores
+// the mean of the rendered pixels -- no full-size RGBA is written. K = 0 is the kernel it always was.
+template <int K>
 __global__ void __launch_bounds__(256) k_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
 	const size_t n = (size_t) width * (size_t) height;
 	const int32_t opaque = (1 << bpp) - 1;
+	if constexpr (K > 0) {
+		const int32_t ow = scale_out_size(width, K), oh = scale_out_size(height, K);
+		for (size_t o = (size_t) blockIdx.x * blockDim.x + threadIdx.x; o < (size_t) ow * (size_t) oh; o += (size_t) gridDim.x * blockDim.x) {
+			const int32_t oy = (int32_t) (o / (size_t) ow), ox = (int32_t) (o - (size_t) oy * (size_t) ow), cw = scale_span(ox, width, K), ch = scale_span(oy, height, K);
+			ScaleAcc<4> acc;
+			acc.clear();
+			for (int32_t dy = 0; dy < ch; ++dy) for (int32_t dx = 0; dx < cw; ++dx) {
+				const size_t i = (size_t) ((oy << K) + dy) * (size_t) width + (size_t) ((ox << K) + dx);
+				acc.add(pack_rgba8(r[i], g[i], b[i], a ? a[i] : opaque, bpp));
+			}
+			__builtin_nontemporal_store(acc.mean(cw * ch, K), (uint32_t *) (rgba + (size_t) oy * stride_bytes + (size_t) ox * 4));
+		}
+		return;
+	}
 	for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x) {
 		const size_t y = i / (size_t) width, x = i - y * (size_t) width;
 		*(uint32_t *) (rgba + y * stride_bytes + x * 4) = pack_rgba8(r[i], g[i], b[i], a ? a[i] : opaque, bpp);
@@ -223,9 +241,24 @@ __global__ void __launch_bounds__(256) k_pack_planes_rect(const int16_t *r, cons
 }
 
 // the 16-bit forms (J40_U16X4): pack_rgba16, 8 bytes a pixel as one store; alpha without a plane: 65535
+template <int K>
 __global__ void __launch_bounds__(256) k_pack_planes16(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
 	const size_t n = (size_t) width * (size_t) height;
 	const int32_t opaque = (1 << bpp) - 1;
+	if constexpr (K > 0) {   // (k_pack_planes)
+		const int32_t ow = scale_out_size(width, K), oh = scale_out_size(height, K);
+		for (size_t o = (size_t) blockIdx.x * blockDim.x + threadIdx.x; o < (size_t) ow * (size_t) oh; o += (size_t) gridDim.x * blockDim.x) {
+			const int32_t oy = (int32_t) (o / (size_t) ow), ox = (int32_t) (o - (size_t) oy * (size_t) ow), cw = scale_span(ox, width, K), ch = scale_span(oy, height, K);
+			ScaleAcc<8> acc;
+			acc.clear();
+			for (int32_t dy = 0; dy < ch; ++dy) for (int32_t dx = 0; dx < cw; ++dx) {
+				const size_t i = (size_t) ((oy << K) + dy) * (size_t) width + (size_t) ((ox << K) + dx);
+				acc.add(pack_rgba16(r[i], g[i], b[i], a ? a[i] : opaque, bpp));
+			}
+			__builtin_nontemporal_store(acc.mean(cw * ch, K), (uint64_t *) (rgba + (size_t) oy * stride_bytes + (size_t) ox * 8));
+		}
+		return;
+	}
 	for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x) {
 		const size_t y = i / (size_t) width, x = i - y * (size_t) width;
 		__builtin_nontemporal_store(pack_rgba16(r[i], g[i], b[i], a ? a[i] : opaque, bpp), (uint64_t *) (rgba + y * stride_bytes + x * 8));
@@ -285,9 +318,17 @@ void launch_inverse_squeeze(const int16_t *avg, const int16_t *res, int16_t *out
 	if (horizontal) hipLaunchKernelGGL(k_unsqueeze_h, dim3((unsigned) ((ah + 63) / 64)), dim3(64), 0, stream, avg, res, out, aw, ah, rw);
 	else hipLaunchKernelGGL(k_unsqueeze_v, dim3((unsigned) ((aw + 255) / 256)), dim3(256), 0, stream, avg, res, out, aw, ah, rh);
 }
-void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
-	if (rgba16) hipLaunchKernelGGL(k_pack_planes16, dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
-	else hipLaunchKernelGGL(k_pack_planes, dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16, int32_t shift) {
+	if (shift > 0) {
+		const unsigned grid = grid_for((size_t) scale_out_size(width, shift) * (size_t) scale_out_size(height, shift));
+		if (rgba16 && shift == 1) hipLaunchKernelGGL(k_pack_planes16<1>, dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+		else if (rgba16) hipLaunchKernelGGL(k_pack_planes16<2>, dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+		else if (shift == 1) hipLaunchKernelGGL(k_pack_planes<1>, dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+		else hipLaunchKernelGGL(k_pack_planes<2>, dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+		return;
+	}
+	if (rgba16) hipLaunchKernelGGL(k_pack_planes16<0>, dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+	else hipLaunchKernelGGL(k_pack_planes<0>, dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
 }
 
 void launch_pack_planes_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {

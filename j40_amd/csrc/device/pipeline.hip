@@ -101,6 +101,7 @@ struct Slot {
 
 struct j40hip_pipeline {
 	int device = 0, batch_frames = 32, max_in_flight = 2;
+	std::atomic<int32_t> scale{0};      // the scale shift of every image (j40hip_pipeline_set_scale: changed only while nothing is in flight); a Job's width and height are then the small image's
 	double max_wait_ms = 0;             // > 0: a prepared frame waits at most this long for a full batch while a slot is free (serving; j40hip_pipeline_set_max_wait_ms)
 	int lf_mode = 0;                    // LfGroup streams: 0 decided per frame (see above), 1 always the device, 2 always the host threads
 	// mode 0: the device decodes a section in 0.4 s and thousands of them at once (k_lf_lanes: a lane per section, a few dozen
@@ -198,8 +199,10 @@ uint32_t decode_single(j40hip_pipeline *p, Job *j, hipStream_t s) {
 	if (!fr) return err ? err : E_MEM;
 	int64_t info[21];
 	j40hip_frame_info(fr, info);
-	j->width = info[0]; j->height = info[1];
-	err = ensure_output(j);
+	const int32_t shift = p->scale.load();
+	j->width = (info[0] + (1 << shift) - 1) >> shift; j->height = (info[1] + (1 << shift) - 1) >> shift;
+	if (shift > 0) err = j40hip_frame_set_scale(fr, shift);
+	if (!err) err = ensure_output(j);
 	const size_t bytes = j->stride * (size_t) j->height;
 	void *dev = nullptr;
 	if (!err) { dev = j->device_output ? j->rgba : acquire_image(p, bytes); if (!dev) err = E_MEM; }
@@ -261,6 +264,7 @@ void worker_main(j40hip_pipeline *p, int) {
 		bool single = j->af == nullptr;
 		if (j->af) {
 			j40hip_aframe_size(j->af, &j->width, &j->height);
+			{ const int32_t shift = p->scale.load(); j->width = (j->width + (1 << shift) - 1) >> shift; j->height = (j->height + (1 << shift) - 1) >> shift; }
 			j->cells = j40hip_aframe_cells(j->af);
 			if (uint32_t e = ensure_output(j)) {
 				(void) hipStreamSynchronize(stream);   // (its copy is in flight)
@@ -421,7 +425,7 @@ uint32_t launch_batch(j40hip_pipeline *p, std::vector<Job *> &take, int si) {
 		frames.push_back(j->af); outs.push_back(j->dev_rgba); strides.push_back(j->stride);
 	}
 	if (!err && !slot.batch) { slot.batch = j40hip_abatch_create(p->device); if (!slot.batch) err = E_GPU; }
-	if (!err) err = j40hip_abatch_launch(slot.batch, frames.data(), (int) frames.size(), outs.data(), strides.data(), slot.stream);
+	if (!err) err = j40hip_abatch_launch(slot.batch, frames.data(), (int) frames.size(), outs.data(), strides.data(), slot.stream, p->scale.load());
 	if (err == E_MEM) {
 		// (abatch_launch binds the working sets before it enqueues anything, so nothing is in flight; the frames keep what they got)
 		for (Job *j : take) if (!j->device_output && j->dev_rgba) { release_image(p, j->dev_rgba, j->stride * (size_t) j->height); j->dev_rgba = nullptr; }
@@ -746,6 +750,15 @@ uint32_t j40hip_pipeline_run(j40hip_pipeline *p, const void *buf, size_t size, j
 	return w.status;
 }
 
+uint32_t j40hip_pipeline_set_scale(j40hip_pipeline *p, int32_t shift) {
+	if (!p || shift < 0 || shift > 2) return E_RNGE;
+	std::unique_lock<std::mutex> lock(p->m);
+	if (p->scale.load() == shift) return 0;   // (nothing changes: also with images in flight)
+	if (p->completed < p->submitted) return ('U' << 24) | ('s' << 16) | ('c' << 8) | '?';   // jobs in flight were sized at the shift in force
+	p->scale.store(shift);
+	return 0;
+}
+
 void j40hip_pipeline_set_max_wait_ms(j40hip_pipeline *p, double ms) { if (p) { std::unique_lock<std::mutex> lock(p->m); p->max_wait_ms = ms; } }
 
 uint32_t j40hip_pipeline_drain(j40hip_pipeline *p) {
@@ -832,6 +845,7 @@ j40hip_pipeline *j40hip_serve_pipeline(int device, uint32_t *err) {
 	j40hip_pipeline *p = j40hip_pipeline_create_ex(device, threads, std::max(1, env_int("J40HIP_SERVE_BATCH", 64)), env_int("J40HIP_SERVE_IN_FLIGHT", 6), lf | 8u, err);
 	if (!p) return nullptr;
 	if (!j40hip::env_str("J40HIP_LF_AUTO_MIN")) { std::unique_lock<std::mutex> plock(p->m); p->lf_auto_min = 12 * (int64_t) threads; }
+	{ const int shift = env_int("J40HIP_SCALE", 0); if (shift == 1 || shift == 2) (void) j40hip_pipeline_set_scale(p, shift); }   // (api.cpp: scale_policy)
 	const char *w = j40hip::env_str("J40HIP_SERVE_WAIT_MS");
 	j40hip_pipeline_set_max_wait_ms(p, w ? atof(w) : 100.0);
 	return g_serve[device] = p;

@@ -18,7 +18,8 @@ bool j40hip_rt::modular_groups_independent(const j40hip_frame *h) {
 // its cover only (LfGlobal's too), one launch per row of the cover's groups and pass, the frame-wide per-pixel transforms over the
 // cover's rows, and the rectangle packed with the destination moved back by its origin; every section where the groups depend on
 // each other
-static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, const int32_t *region = nullptr) {
+// shift: the scale shift of a whole-frame decode (decode_scaled): the pack kernel writes the small image
+static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, const int32_t *region = nullptr, int32_t shift = 0) {
 	j40hip_device_state *st = h->dev;
 	const DevModPlan &plan = st->mod;
 	const Frame &fr = h->frame;
@@ -75,7 +76,7 @@ static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_by
 		int32_t rects[3][4];
 		const int nr = group_range_rects(g0, gn, fr.fh.width, fr.fh.height, fr.fh.group_size_shift, rects);
 		for (int k = 0; k < nr; ++k) launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
-	} else launch_pack_planes(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
+	} else launch_pack_planes(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h), shift);
 	marks.mark(3);
 	if (uint32_t e = marks.finish(ms3)) return e;
 	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
@@ -311,6 +312,7 @@ struct VardctRun {
 	uint8_t *img; size_t img_stride;     // where they write
 	bool whole;                          // every group is decoded: the restoration filters may run, the extra channels' sub-images can be validated
 	const uint8_t *crop_from; uint8_t *crop_to; size_t crop_stride; int32_t crop_w, crop_h;   // crop_to not null: these pixels of img are then moved there
+	int32_t shift = 0;                   // the scale shift the pixel kernels write at (decode_scaled's fused route: img is the small image)
 };
 
 static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s, float *ms3) {
@@ -333,7 +335,7 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 		// the restoration filters asked for and signalled: the pixel kernels leave the samples in XYB planes, Gaborish and the
 		// edge-preserving filter run over the whole picture, the colour tail follows on the filtered planes (restore_kernels.h)
 		if (uint32_t e = decode_restored(h, run.img, run.img_stride, rmode, s)) return e;
-	} else launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, run.img, run.img_stride, s, out16(h));
+	} else launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, run.img, run.img_stride, s, out16(h), run.shift);
 	if (run.crop_to) launch_region_crop(run.crop_from, run.img_stride, run.crop_to, run.crop_stride, run.crop_w, run.crop_h, (int32_t) pixel_bytes(h), s);
 	marks.mark(3);
 	if (uint32_t e = marks.finish(ms3)) return e;
@@ -343,11 +345,13 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 }
 
 static uint32_t decode_region(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3);
+static uint32_t decode_scaled(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3);
 
 static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, bool whole_frame = false) {
 	if (h && h->frame.lf_only) return ERR_ULF;
 	if (!h || !h->dev) return ERR_GPU;
 	if (h->region_set && !whole_frame) return decode_region(h, rgba_dev, stride_bytes, s, ms3);   // (whole_frame: decode_region's own call, for a widened region)
+	if (h->scale > 0 && !whole_frame) return decode_scaled(h, rgba_dev, stride_bytes, s, ms3);    // (... and decode_scaled's, for a staged combination)
 	if (stride_too_small(h, stride_bytes)) return ERR_RNGE;
 	j40hip_device_state *st = h->dev;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
@@ -465,6 +469,49 @@ static uint32_t decode_region(j40hip_frame *h, void *rgba_dev, size_t stride_byt
 	const VardctRun run = {0, (int32_t) fr.fh.num_groups, all ? nullptr : &cover, list, class_start, img, img_stride, all,
 		direct ? nullptr : img + (size_t) (y0 - cy0) * img_stride + (size_t) (x0 - cx0) * pb, direct ? nullptr : (uint8_t *) rgba_dev, stride_bytes, w, hh};
 	return run_vardct(h, run, s, ms3);
+}
+
+// ---- reduced-size decode (j40hip_frame_set_scale, include/j40hip.h; device/scale_dev.h, scale_kernels.hip) ----
+// The whole frame at scale shift k: ceil(width / s) x ceil(height / s) pixels at rgba_dev. Fused wherever the pixels come out of the
+// pixel kernels (VarDCT) or the pack kernel (Modular): those write the small image and nothing else. Staged where other kernels write
+// full-size pixels -- restoration filters in force on a frame that signals them (k_xyb_to_rgba), keep-alpha mode (k_alpha_merge): the
+// frame decodes as ever into a full-size image kept with the frame, and k_downscale makes the small one of it. Every section is
+// entropy-decoded either way: status and codes are the full decode's. (A region or a partial group range never gets here: the setters
+// exclude them.)
+static uint32_t decode_scaled(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
+	j40hip_device_state *st = h->dev;
+	const Frame &fr = h->frame;
+	const int32_t W = fr.fh.width, H = fr.fh.height, k = h->scale;
+	const size_t pb = pixel_bytes(h);
+	if (scaled_stride_too_small(h, stride_bytes)) return ERR_RNGE;
+	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
+	const int rmode = restoration_mode(h);
+	const bool staged = !st->is_modular && ((rmode && (fr.fh.restoration.gab || fr.fh.restoration.epf_iters > 0)) || (st->has_trailers && j40hip_alpha_kept(h)));
+	if (staged) {
+		const size_t img_stride = ((size_t) W * pb + 15) & ~(size_t) 15, bytes = img_stride * (size_t) H;
+		if (!st->scale_staging.ensure(st->device, bytes, false)) return ERR_MEM;
+		uint8_t *img = (uint8_t *) st->scale_staging.ptr;
+		h->scale_staged = 1; h->scale_staging_bytes = (int64_t) bytes;
+		if (uint32_t e = decode_impl(h, img, img_stride, s, ms3, true)) return e;
+		launch_downscale(img, img_stride, (uint8_t *) rgba_dev, stride_bytes, W, H, k, (int32_t) pb, s);
+		return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+	}
+	h->scale_staged = 0; h->scale_staging_bytes = 0;
+	if (st->is_modular) return decode_modular(h, rgba_dev, stride_bytes, s, ms3, nullptr, k);
+	VardctRun run = {0, (int32_t) fr.fh.num_groups, nullptr, st->d_vb_sorted, st->class_start, (uint8_t *) rgba_dev, stride_bytes, true, nullptr, nullptr, 0, 0, 0};
+	run.shift = k;
+	return run_vardct(h, run, s, ms3);
+}
+
+// known-answer / measuring hook: k_downscale alone
+extern "C" uint32_t j40hip_kat_device_downscale(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, int32_t w, int32_t h, int32_t shift, int32_t format, void *stream) {
+	if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
+	const size_t pb = format == J40HIP_U16X4 ? 8 : 4;
+	if (!out_dev || !src_dev || w <= 0 || h <= 0 || shift < 1 || shift > 2) return ERR_RNGE;
+	const size_t ow = (size_t) ((w + (1 << shift) - 1) >> shift);
+	if (src_stride < pb * (size_t) w || out_stride < pb * ow || src_stride % pb || out_stride % pb || (uintptr_t) out_dev % pb || (uintptr_t) src_dev % pb) return ERR_RNGE;
+	launch_downscale((const uint8_t *) src_dev, src_stride, (uint8_t *) out_dev, out_stride, w, h, shift, (int32_t) pb, (hipStream_t) stream);
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 }
 
 extern "C" uint32_t j40hip_frame_decode(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, void *stream) {
@@ -640,13 +687,13 @@ static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host
 static uint32_t decode_to_host(j40hip_frame *h, void *rgba_host, size_t stride_bytes) {
 	if (h && h->frame.lf_only) return ERR_ULF;
 	if (!h || !h->dev) return ERR_GPU;
-	const bool region = h->region_set;   // (only the rectangle's rows exist on either side, and they go the one-phase way)
-	if (region ? stride_bytes < pixel_bytes(h) * (size_t) h->region[2] : stride_too_small(h, stride_bytes)) return ERR_RNGE;
+	const bool region = h->region_set || h->scale > 0;   // (only the rectangle's rows, or the small image's, exist on either side, and they go the one-phase way)
+	if (h->region_set ? stride_bytes < pixel_bytes(h) * (size_t) h->region[2] : scaled_stride_too_small(h, stride_bytes)) return ERR_RNGE;
 	const Frame &fr = h->frame;
 	const int device = h->dev->device;
 	if (hipSetDevice(device) != hipSuccess) return ERR_GPU;
 	// the device image uses the caller's row stride, so one contiguous copy brings it back
-	const size_t bytes = stride_bytes * (size_t) (region ? h->region[3] : fr.fh.height);
+	const size_t bytes = stride_bytes * (size_t) (h->region_set ? h->region[3] : h->scale > 0 ? scaled_height(h) : fr.fh.height);
 	ScopedBlock block;   // (whatever way the call ends, the image goes back behind a device-wide wait)
 	if (!block.ensure(device, bytes, true)) return ERR_GPU;
 	void *d = block.ptr;

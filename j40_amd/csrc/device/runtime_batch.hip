@@ -128,7 +128,10 @@ static uint32_t batch_enqueue(j40hip_batch *b, void *const *rgba_dev, const size
 	// every member in one output format (mixed batches: "Uof?"), each 16-bit member's rows wide enough: checked before anything is launched
 	for (size_t i = 0; i < b->frames.size(); ++i) {
 		if (b->frames[i]->output_format != b->frames[0]->output_format) return ERR4('U', 'o', 'f', '?');
-		if (stride_too_small(b->frames[i], stride_bytes[i])) return ERR_RNGE;
+		// ... and at one scale shift ("Usc?"); a keep-alpha member's alpha is merged into full-size pixels when its status is read: not at a scale
+		if (b->frames[i]->scale != b->frames[0]->scale) return ERR_USC;
+		if (b->frames[i]->scale > 0 && b->frames[i]->dev && b->frames[i]->dev->has_trailers && j40hip_alpha_kept(b->frames[i])) return ERR_USC;
+		if (scaled_stride_too_small(b->frames[i], stride_bytes[i])) return ERR_RNGE;
 	}
 	if (hipSetDevice(b->device) != hipSuccess) return ERR_GPU;
 	// a member that was uploaded again since the batch was made (j40hip_frame_force_dense + j40hip_frame_upload after "evof")
@@ -154,7 +157,7 @@ static uint32_t batch_enqueue(j40hip_batch *b, void *const *rgba_dev, const size
 		j40hip_frame *h = b->frames[i];
 		j40hip_device_state *st = h->dev;
 		st->trailers_pending = st->has_trailers;
-		st->pending_rgba = rgba_dev[i]; st->pending_stride = stride_bytes[i]; h->alpha_written = false;   // (a kept alpha is merged when the status is read)
+		st->pending_rgba = h->scale > 0 ? nullptr : rgba_dev[i]; st->pending_stride = stride_bytes[i]; h->alpha_written = false;   // (a kept alpha is merged when the status is read -- never into a small image: the sub-images are validated all the same)
 		if (uint32_t e = clear_before_decode(st, s)) return e;
 		// (no need to clear the status words: a batch decodes every section of every frame and the entropy kernels store
 		// each section's status unconditionally -- 256 tiny fills were 4 % of a step)
@@ -166,14 +169,14 @@ static uint32_t batch_enqueue(j40hip_batch *b, void *const *rgba_dev, const size
 	if (b->side_in_use == 0) {
 		for (size_t i = 0; i < b->frames.size(); ++i) {
 			j40hip_device_state *st = b->frames[i]->dev;
-			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev[i], stride_bytes[i], s, out16(b->frames[i]));
+			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev[i], stride_bytes[i], s, out16(b->frames[i]), b->frames[i]->scale);
 		}
 	} else {
 		if (hipEventRecord(b->fork, s) != hipSuccess) return ERR_GPU;
 		for (int k = 0; k < b->side_in_use; ++k) if (hipStreamWaitEvent(b->side[(size_t) k], b->fork, 0) != hipSuccess) return ERR_GPU;
 		for (size_t i = 0; i < b->frames.size(); ++i) {
 			j40hip_device_state *st = b->frames[i]->dev;
-			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev[i], stride_bytes[i], b->side[i % (size_t) b->side_in_use], out16(b->frames[i]));
+			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev[i], stride_bytes[i], b->side[i % (size_t) b->side_in_use], out16(b->frames[i]), b->frames[i]->scale);
 		}
 		for (size_t k = 0; k < (size_t) b->side_in_use; ++k) {
 			if (hipEventRecord(b->side_done[k], b->side[k]) != hipSuccess || hipStreamWaitEvent(s, b->side_done[k], 0) != hipSuccess) return ERR_GPU;

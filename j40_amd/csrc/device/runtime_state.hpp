@@ -26,6 +26,7 @@ namespace j40hip_rt {
 constexpr uint32_t ERR4(char a, char b, char c, char d) { return ((uint32_t) (uint8_t) a << 24) | ((uint32_t) (uint8_t) b << 16) | ((uint32_t) (uint8_t) c << 8) | (uint32_t) (uint8_t) d; }
 constexpr uint32_t ERR_GPU = ERR4('!', 'g', 'p', 'u'), ERR_MEM = ERR4('!', 'm', 'e', 'm');
 constexpr uint32_t ERR_URG = ERR4('U', 'r', 'g', '?');   // a region (j40hip_frame_set_region) where only whole frames or group ranges are served, or the other way round
+constexpr uint32_t ERR_USC = ERR4('U', 's', 'c', '?');   // a scale (j40hip_frame_set_scale) where only full-size frames are served, or the other way round
 constexpr uint32_t ERR_ULF = ERR4('U', 'l', 'f', '?');   // an LF-only frame (J40HIP_PARSE_LF_ONLY) has nothing but its LF image: the full decode's entry points refuse it
 
 // no exception crosses the C ABI: a parse error keeps its code, anything else (std::bad_alloc from a vector, ...) is "!mem"
@@ -216,6 +217,9 @@ struct j40hip_device_state {
 		int32_t class_start[REGION_KEYS]; RegionCover gathered = {0, 0, 0, 0, 0, 0};   // (what d_list and d_order hold: cols = 0, nothing)
 		CacheBlock staging;
 	} region;
+	// reduced-size decode (j40hip_frame_set_scale; decode_scaled): the full-size image of the staged combinations (restoration filters,
+	// keep-alpha), one block of the device memory cache, grown on demand, given back with the frame
+	CacheBlock scale_staging;
 	// a batch decoded the frame (trailers_pending): where, for the merge at j40hip_frame_status
 	void *pending_rgba = nullptr; size_t pending_stride = 0;
 
@@ -241,6 +245,11 @@ inline bool out16(const j40hip_frame *h) { return h->output_format == J40HIP_U16
 inline size_t pixel_bytes(const j40hip_frame *h) { return out16(h) ? 8 : 4; }
 // a 16-bit frame's rows must hold 8 * width bytes: "rnge" before anything is launched (the u8 entry points keep their old contract)
 inline bool stride_too_small(const j40hip_frame *h, size_t stride_bytes) { return out16(h) && stride_bytes < 8 * (size_t) h->frame.fh.width; }
+// the size the frame's scale shift gives (j40hip_frame_set_scale): ceil(width / s) x ceil(height / s)
+inline int32_t scaled_width(const j40hip_frame *h) { return (h->frame.fh.width + (1 << h->scale) - 1) >> h->scale; }
+inline int32_t scaled_height(const j40hip_frame *h) { return (h->frame.fh.height + (1 << h->scale) - 1) >> h->scale; }
+// at a shift above 0 the rows must hold the small image's pixels, in both formats
+inline bool scaled_stride_too_small(const j40hip_frame *h, size_t stride_bytes) { return h->scale > 0 ? stride_bytes < pixel_bytes(h) * (size_t) scaled_width(h) : stride_too_small(h, stride_bytes); }
 
 // what crosses units
 bool host_vb_sorted(j40hip_device_state *st);                                  // runtime_upload.hip
