@@ -60,6 +60,10 @@ J40HIP_API void j40hip_frame_free(j40hip_frame *f);
  * codestream cut at j40hip_frame_lf_end parses. Such a frame can only be previewed: j40hip_frame_decode / _timed / _decode_to_host and
  * j40hip_batch_create refuse it with "Ulf?". Modular frames: "TODO" (no LF image without Squeeze). */
 #define J40HIP_PARSE_LF_ONLY 2u
+/* flags & J40HIP_PARSE_YCBCR: YCbCr frames are asked for (see j40hip_frame_set_ycbcr): a frame whose channels are subsampled is parsed
+ * instead of refused with "TODO" before its LF image is read, which is where the reference refuses it. J40HIP_YCBCR=1 in the
+ * environment does the same for every parse. */
+#define J40HIP_PARSE_YCBCR 4u
 /* the shortest prefix of the codestream holding headers, TOC, LfGlobal and every LfGroup section (the largest end among those
  * sections, so a permuted TOC is covered); a bare codestream's file prefix. Single-section frames: the whole codestream. */
 J40HIP_API int64_t j40hip_frame_lf_end(const j40hip_frame *f);
@@ -286,6 +290,33 @@ J40HIP_API void j40hip_frame_alpha(const j40hip_frame *f, int32_t out[4]);
  * them a row, in device memory; they become the A of rectangle (x0, y0, w, h) of the pixels at rgba_dev (format J40HIP_U8X4 or
  * J40HIP_U16X4, rows pixel-aligned). Asynchronous on `stream`. 0, "rnge" for a bpp or rectangle out of range, "Ufm?". */
 J40HIP_API uint32_t j40hip_kat_device_alpha_merge(void *rgba_dev, size_t stride_bytes, const int16_t *plane_dev, int32_t pitch, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bpp, int32_t format, void *stream);
+
+/* ---- YCbCr VarDCT frames: losslessly recompressed JPEGs ("YCbCr frames"; DESIGN.md has the rules). Such a frame has
+ *      xyb_encoded = 0 and do_ycbcr = 1: its three channels are Cb, Y, Cr in the slots of X, Y, B, 4:4:4 or with chroma at half the
+ *      resolution along one or both axes (jpeg_upsampling). The reference refuses them (j40.h:7867, 6749) and so does this library
+ *      unless asked: the feature is opt-in, and none of its arithmetic past the inverse transforms is pinned by the reference.
+ *      set: mode -1 follows the environment (J40HIP_YCBCR=1 serves; the default), 0 refuses, 1 serves. It holds from the next upload
+ *      on. A frame with subsampled channels must also have been PARSED with YCbCr frames asked for (J40HIP_PARSE_YCBCR, or the
+ *      environment variable), else its parse has already failed with "TODO".
+ *      Served: j40hip_frame_upload + j40hip_frame_decode / _timed / _decode_to_host of 8..15-bit colour images, both output formats,
+ *      kept alpha included; 4:4:4 frames with every transform, chroma-from-luma and the restoration filters; subsampled frames
+ *      (4:2:0, 4:2:2, 4:4:0) made of DCT8 blocks, with skip_adapt_lf_smooth and without restoration filters signalled.
+ *      "TODO": everything else -- grey images, float samples, LF frames, other subsampled frames -- and every other entry: batches,
+ *      pipelines, LF previews, a region, a scale, a group range, sequences, plan views.
+ *      j40hip_frame_ycbcr: out[0] the frame is a YCbCr VarDCT frame; out[1..6] (hshift, vshift) of Cb, Y, Cr: log2 of how much coarser
+ *      than the finest channel it is sampled; out[7] the last decode went through the YCbCr planes and k_ycbcr_tail. ---- */
+J40HIP_API uint32_t j40hip_frame_set_ycbcr(j40hip_frame *f, int mode);
+J40HIP_API void j40hip_frame_ycbcr(const j40hip_frame *f, int32_t out[8]);
+/* staged hook: plane c (0 Cb, 1 Y, 2 Cr) of the last decode that went through the YCbCr path, as k_ycbcr_tail read it -- the pixel
+ * kernels' samples, or the restoration filters' result where those ran -- tightly packed: width x height floats for a 4:4:4 frame;
+ * for a subsampled one the block grid padded to whole MCUs, ((ceil(width / (8 << mh)) << mh) * 8 >> hshift[c]) x (likewise with
+ * the vertical shifts) floats. 0, "rnge" without such a decode. */
+J40HIP_API uint32_t j40hip_frame_read_ycbcr(j40hip_frame *f, int c, float *out);
+/* known-answer / measuring hook: k_ycbcr_tail alone on caller-supplied planes in device memory. plane_dims: {pitch, width, height} of
+ * plane 0 (Cb), 1 (Y), 2 (Cr) in floats; shifts: {hshift, vshift} of each (0 or 1); every plane must cover width x height at its
+ * resolution. The width x height pixels at out_dev (format J40HIP_U8X4 or J40HIP_U16X4, rows pixel-aligned) are written, nothing
+ * else. bpp 8..15: the depth of the 16-bit output's levels. Asynchronous on `stream`. 0, "rnge", "Ufm?". */
+J40HIP_API uint32_t j40hip_kat_device_ycbcr_tail(const float *const planes_dev[3], const int32_t plane_dims[9], const int32_t shifts[6], int32_t width, int32_t height, int32_t bpp, int32_t format, void *out_dev, size_t stride_bytes, void *stream);
 
 /* ---- region decode: a rectangle of the frame from the pass groups that cover it ("Region decode"). A pass group is
  *      entropy-coded in a section of its own and no varblock straddles a group, so rectangle (x0, y0, w, h) needs the sections and

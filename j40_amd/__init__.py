@@ -23,6 +23,7 @@ J40_RGBA = 0x1755
 J40_U8X4 = 0x0F33
 J40_U16X4 = 0x0F35
 PARSE_LF_ONLY = 2   # J40HIP_PARSE_LF_ONLY (include/j40hip.h): the LF preview's parse
+PARSE_YCBCR = 4     # J40HIP_PARSE_YCBCR: YCbCr frames are asked for (a subsampled one is parsed instead of refused)
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("J40HIP_LIB") or os.path.join(_ROOT, "build", "libj40hip.so")
@@ -128,6 +129,8 @@ def lib():
         "j40hip_kat_device_blend": (u32, [vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, u32, u32, i32, i32, i32, vp]),
         "j40hip_frame_restoration": (None, [vp, vp]), "j40hip_frame_set_restoration": (None, [vp, C.c_int]), "j40hip_frame_sharpness": (C.c_int, [vp, i64, vp]),
         "j40hip_frame_set_alpha": (u32, [vp, C.c_int]), "j40hip_frame_alpha": (None, [vp, vp]),
+        "j40hip_frame_set_ycbcr": (u32, [vp, C.c_int]), "j40hip_frame_ycbcr": (None, [vp, vp]), "j40hip_frame_read_ycbcr": (u32, [vp, C.c_int, vp]),
+        "j40hip_kat_device_ycbcr_tail": (u32, [vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
         "j40hip_frame_set_region": (u32, [vp, i32, i32, i32, i32]), "j40hip_frame_region": (None, [vp, vp]),
         "j40hip_frame_set_scale": (u32, [vp, i32]), "j40hip_frame_scale": (None, [vp, vp]), "j40hip_pipeline_set_scale": (u32, [vp, i32]),
         "j40hip_kat_device_downscale": (u32, [vp, sz, vp, sz, i32, i32, i32, i32, vp]),
@@ -226,20 +229,24 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
     scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
     (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
     The public API writes a VarDCT frame's alpha as the environment says (J40HIP_ALPHA=1 keeps it, else A is opaque like the
     reference's). alpha=True keeps it for this call whatever the environment says: the frame goes through the thin C-ABI with
-    Frame.set_alpha(1) on device 0 -- "TODO" / "Ual?" where that refuses (Frame.set_alpha)."""
-    if alpha or scale:
+    Frame.set_alpha(1) on device 0 -- "TODO" / "Ual?" where that refuses (Frame.set_alpha).
+    ycbcr=True: a YCbCr VarDCT frame (a recompressed JPEG) is served for this call whatever J40HIP_YCBCR says (Frame.set_ycbcr(1)),
+    likewise through the thin C-ABI on device 0; "TODO" for what that does not serve."""
+    if alpha or scale or ycbcr:
         try:
-            fr = Frame(data)
+            fr = Frame(data, ycbcr=bool(ycbcr))
         except J40Error as e:
             return e.code, None
         try:
             code = fr.set_alpha(1) if alpha else ""
+            if not code and ycbcr:
+                code = fr.set_ycbcr(1)
             if not code and scale:
                 code = fr.set_scale(scale)
             if code:
@@ -356,14 +363,16 @@ def kat_device_restoration(planes, sharpness, hfmul_inv, r, mode=1, device=0):
 class Frame:
     """thin C-ABI (include/j40hip.h): host parse, plan upload, hot path on a HIP stream"""
 
-    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False):
+    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False, ycbcr=False):
         """lf_device: a HIP device index -- the LfGroup streams are decoded there instead of on the host (j40hip_frame_parse_on).
         lf_only: parse what the LF preview needs and nothing more (J40HIP_PARSE_LF_ONLY): `data` may end at lf_end(); such a frame
-        can only be previewed (decode_lf_to_host, decode_lf)"""
+        can only be previewed (decode_lf_to_host, decode_lf).
+        ycbcr: YCbCr frames are asked for (J40HIP_PARSE_YCBCR): a frame with subsampled channels is parsed instead of refused; serving
+        it still takes set_ycbcr(1) (or J40HIP_YCBCR=1)"""
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        flags = PARSE_LF_ONLY if lf_only else 0
+        flags = (PARSE_LF_ONLY if lf_only else 0) | (PARSE_YCBCR if ycbcr else 0)
         if lf_device is None:
             self.h = L.j40hip_frame_parse_ex(self._buf, len(data), threads, flags, C.byref(err))
         else:
@@ -600,6 +609,36 @@ class Frame:
         a = np.zeros(4, np.int32)
         lib().j40hip_frame_alpha(self.h, a.ctypes.data)
         return dict(zip(["index", "bpp", "mode", "written"], a.tolist()))
+
+    # ---- YCbCr VarDCT frames (include/j40hip.h) ----
+    def set_ycbcr(self, mode):
+        """-1: as J40HIP_YCBCR says (default), 0: refuse YCbCr frames ("TODO", the reference's answer), 1: serve them. Holds from
+        the next upload on; returns "" """
+        return err4(lib().j40hip_frame_set_ycbcr(self.h, int(mode)))
+
+    def ycbcr(self):
+        """{"ycbcr": the frame is a YCbCr VarDCT frame, "shifts": ((hshift, vshift) of Cb, Y, Cr), "used": the last decode went
+        through the YCbCr planes and k_ycbcr_tail}"""
+        a = np.zeros(8, np.int32)
+        lib().j40hip_frame_ycbcr(self.h, a.ctypes.data)
+        return {"ycbcr": int(a[0]), "shifts": tuple((int(a[1 + 2 * c]), int(a[2 + 2 * c])) for c in range(3)), "used": int(a[7])}
+
+    def ycbcr_plane_shape(self, c):
+        """(rows, columns) of plane c as j40hip_frame_read_ycbcr returns it: the frame's size, or for a subsampled frame the block
+        grid padded to whole MCUs at the channel's resolution"""
+        sh = self.ycbcr()["shifts"]
+        if not any(v for p in sh for v in p):
+            return self.height, self.width
+        mh, mv = max(p[0] for p in sh), max(p[1] for p in sh)
+        fw = -(-self.width // (8 << mh)) << (mh + 3)
+        fh = -(-self.height // (8 << mv)) << (mv + 3)
+        return fh >> sh[c][1], fw >> sh[c][0]
+
+    def read_ycbcr(self, c):
+        """after a decode through the YCbCr path: plane c (0 Cb, 1 Y, 2 Cr) as k_ycbcr_tail read it, float32 [rows, columns]"""
+        a = np.zeros(self.ycbcr_plane_shape(c), np.float32)
+        self._chk(lib().j40hip_frame_read_ycbcr(self.h, int(c), a.ctypes.data), "in j40hip_frame_read_ycbcr")
+        return a
 
     def sharpness(self, gg):
         gi = self.lf_group_info(gg)

@@ -20,6 +20,8 @@ struct j40hip_frame {
 	int restoration = -1;            // the restoration filters (j40hip_frame_set_restoration): -1 as J40HIP_RESTORATION says, 0 off, 1 on, 2 as j40's routines stand
 	int alpha = -1;                  // the alpha channel of a VarDCT frame (j40hip_frame_set_alpha): -1 as J40HIP_ALPHA says, 0 dropped (A = 255, the reference's pixels), 1 kept
 	bool alpha_written = false;      // the last decode merged the alpha channel into its pixels
+	int ycbcr = -1;                  // YCbCr VarDCT frames (j40hip_frame_set_ycbcr): -1 as J40HIP_YCBCR says, 0 refused ("TODO", the reference's answer), 1 served
+	bool ycbcr_used = false;         // the last decode went through the YCbCr planes and k_ycbcr_tail
 	int32_t output_format = J40HIP_U8X4;   // what the decode entry points write (j40hip_frame_set_output_format): u8x4 or u16x4
 	// region decode (j40hip_frame_set_region): the rectangle the decode entry points write instead of the whole frame, and what the last
 	// decode with it cost (j40hip_frame_region's fields 9-11)
@@ -86,6 +88,13 @@ inline bool j40hip_alpha_kept(const j40hip_frame *h) {
 	int32_t index;
 	const bool asked = h->alpha >= 0 ? h->alpha == 1 : j40hip::alpha_env();
 	return asked && !h->from_view && j40hip::alpha_keep_scope(h->frame, &index) == 0;
+}
+
+// YCbCr frames are served: asked for (or J40HIP_YCBCR=1) on a handle of the single-frame decode -- not one a sequence hands out, not
+// one built from a view (whose LF bundle knows nothing of channel sizes)
+inline bool j40hip_ycbcr_on(const j40hip_frame *h) {
+	const bool asked = h->ycbcr >= 0 ? h->ycbcr == 1 : j40hip::ycbcr_env();
+	return asked && !h->from_view && !h->from_sequence;
 }
 
 extern "C" j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads, uint32_t flags, j40hip::LfDeviceDecoder lf_decoder, void *lf_ctx, uint32_t *err);

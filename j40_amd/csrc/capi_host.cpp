@@ -24,6 +24,7 @@ j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads,
 		h->frame.defer_lf_tail = (flags & (1u | J40HIP_PARSE_LF_ONLY)) != 0;
 		h->frame.lf_only = (flags & J40HIP_PARSE_LF_ONLY) != 0;
 		h->frame.lf_decoder = lf_decoder; h->frame.lf_decoder_ctx = lf_ctx;
+		h->frame.allow_ycbcr = (flags & J40HIP_PARSE_YCBCR) != 0 || ycbcr_env();
 		extract_codestream((const uint8_t *) buf, size, &h->cs, &h->cs_size, &h->cs_storage, &h->container_stray_tail);
 		h->bare_codestream = h->cs == (const uint8_t *) buf && h->cs_size == size;
 		parse_frame(h->cs, h->cs_size, &h->frame, threads);
@@ -52,6 +53,7 @@ j40hip_frame *j40hip_frame_parse_streamed(const void *buf, size_t size, int thre
 		h->frame.defer_lf_tail = (flags & (1u | J40HIP_PARSE_LF_ONLY)) != 0;
 		h->frame.lf_only = (flags & J40HIP_PARSE_LF_ONLY) != 0;
 		h->frame.need_bytes = need; h->frame.have_bytes = have; h->frame.need_ctx = ctx;
+		h->frame.allow_ycbcr = (flags & J40HIP_PARSE_YCBCR) != 0 || ycbcr_env();
 		h->cs = p; h->cs_size = size; h->bare_codestream = true;
 		parse_frame(h->cs, h->cs_size, &h->frame, threads);
 		h->threads = threads < 1 ? 1 : threads > 16 ? 16 : threads;
@@ -296,6 +298,22 @@ void j40hip_frame_alpha(const j40hip_frame *h, int32_t out[4]) {
 	for (size_t i = 0; i < h->frame.im.ec.size(); ++i) if (h->frame.im.ec[i].type == j40hip::EC_ALPHA) { out[0] = (int32_t) i; out[1] = h->frame.im.ec[i].bpp; break; }
 	out[2] = j40hip_alpha_kept(h) ? 1 : 0;
 	out[3] = h->alpha_written ? 1 : 0;
+}
+
+// ---- YCbCr VarDCT frames (include/j40hip.h) ----
+uint32_t j40hip_frame_set_ycbcr(j40hip_frame *h, int mode) {
+	if (!h) return j40hip::ERR_RNGE;
+	h->ycbcr = mode < 0 ? -1 : mode > 0 ? 1 : 0;
+	return 0;
+}
+void j40hip_frame_ycbcr(const j40hip_frame *h, int32_t out[8]) {
+	if (!out) return;
+	memset(out, 0, sizeof(int32_t) * 8);
+	if (!h) return;
+	const j40hip::FrameHeader &fh = h->frame.fh;
+	out[0] = !fh.is_modular && fh.do_ycbcr ? 1 : 0;
+	for (int c = 0; c < 3; ++c) { out[1 + 2 * c] = fh.hshift[c]; out[2 + 2 * c] = fh.vshift[c]; }
+	out[7] = h->ycbcr_used ? 1 : 0;
 }
 
 // ---- region decode (include/j40hip.h) ----

@@ -56,7 +56,11 @@ struct HfTables {
 // decodes one (pass, group) section. SCAN: single-pass frames append one event {scan position, value} per non-zero
 // coefficient (DevPlan::events; the pixel kernels undo the order), otherwise accumulate at the canonical position of the
 // dense planes like j40.h:6989.
-template <bool SCAN, bool UNI>
+// SUB: a YCbCr frame with subsampled channels (DevFrame::ycc_shifts; DCT8 blocks only). PARITY UNPINNED -- the reference refuses such
+// frames. Blocks and channels are visited in the same order; a channel is read only at the blocks where it has one (bctx3 bits
+// 12-14 mark where it has none), and its non-zero counts are predicted in its own coordinates (x8 >> hshift, y8 >> vshift) -- a map of
+// its own, which lives in the channel's third of the same scratch. Without SUB nothing of this is compiled in.
+template <bool SCAN, bool UNI, bool SUB = false>
 J40_DEV uint32_t decode_hf_section(const DevPlan &plan, const DevFrame &f, const DevCodeSpec &spec, const HfTables &t, int32_t pass, const DevSection &sec) {
 	const DevLfGroup &gg = plan.lf_groups[sec.ggidx];
 	DevBits b;
@@ -84,17 +88,23 @@ J40_DEV uint32_t decode_hf_section(const DevPlan &plan, const DevFrame &f, const
 			float *coeffs = SCAN ? nullptr : plan.coeffs[c] + cell64 + coeffoff;
 			const uint32_t chan_first = ev_at;
 			const int32_t bctx = (gb.bctx3 >> (4 * c_yxb)) & 15;
+			if (SUB && ((gb.bctx3 >> (12 + c_yxb)) & 1)) {   // the channel has no block here: nothing is read
+				if (SCAN) plan.block_events[4 * (size_t) (t.block_first + (uint32_t) k) + 1 + (size_t) c_yxb] = 0;
+				continue;
+			}
+			const int32_t hs = SUB ? (int32_t) ((f.ycc_shifts >> (2 * c)) & 1u) : 0, vs = SUB ? (int32_t) ((f.ycc_shifts >> (2 * c + 1)) & 1u) : 0;
+			const int32_t cx8 = x8 >> hs, cy8 = y8 >> vs, cpos = SUB ? cy8 * gw8 + cx8 : nzpos;
 			// number of non-zeros, predicted from the left / top blocks (j40.h:6959-6967)
 			int32_t nz;
-			if (x8 > 0) nz = y8 > 0 ? (t.nonzeros[(nzpos - 1) * 3 + c] + t.nonzeros[(nzpos - gw8) * 3 + c] + 1) >> 1 : t.nonzeros[(nzpos - 1) * 3 + c];
-			else nz = y8 > 0 ? t.nonzeros[(nzpos - gw8) * 3 + c] : 32;
+			if (cx8 > 0) nz = cy8 > 0 ? (t.nonzeros[(cpos - 1) * 3 + c] + t.nonzeros[(cpos - gw8) * 3 + c] + 1) >> 1 : t.nonzeros[(cpos - 1) * 3 + c];
+			else nz = cy8 > 0 ? t.nonzeros[(cpos - gw8) * 3 + c] : 32;
 			nz = uni<UNI>(nz);
 			const int32_t nzctx = ctxoff + bctx + (nz < 8 ? nz : 4 + nz / 2) * nb_block_ctx;
 			nz = code_symbol<UNI>(b, code, nzctx, 0, plan.lz_window_size);
 			if (nz > (63 << shift)) { bits_set_error(b, ERR_COEF); break; }
 			const int32_t qnz = (nz + (1 << shift) - 1) >> shift;
 			for (int32_t i = 0; i < (1 << (log_rows - 3)); ++i) for (int32_t j = 0; j < (1 << (log_columns - 3)); ++j)
-				t.nonzeros[(nzpos + i * gw8 + j) * 3 + c] = (int8_t) qnz;
+				t.nonzeros[(cpos + i * gw8 + j) * 3 + c] = (int8_t) qnz;
 			const int32_t cctx = ctxoff + 458 * bctx + 37 * nb_block_ctx;
 			int32_t prev = nz <= (size >> 4);
 			const uint16_t *order = SCAN ? nullptr : plan.pool_u16 + f.order_off[(pass * 13 + order_idx) * 3 + c];
@@ -231,6 +241,7 @@ J40_DEV void decode_hf_group(const DevPlan &plan, int32_t g, bool flat = false) 
 		const DevSection &sec = plan.sections[pass * f.num_groups + g];
 		uint32_t err;
 		if (flat) err = f.sparse_coeffs ? decode_hf_section_flat<true>(plan, f, spec, t, pass, sec) : decode_hf_section_flat<false>(plan, f, spec, t, pass, sec);
+		else if (f.ycc_shifts) err = f.sparse_coeffs ? decode_hf_section<true, false, true>(plan, f, spec, t, pass, sec) : decode_hf_section<false, false, true>(plan, f, spec, t, pass, sec);
 		else err = f.sparse_coeffs ? decode_hf_section<true, false>(plan, f, spec, t, pass, sec) : decode_hf_section<false, false>(plan, f, spec, t, pass, sec);
 		plan.status[pass * f.num_groups + g] = err;
 	}

@@ -36,6 +36,9 @@ void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const 
 // `stride` bytes per row, one behind the other), the reciprocal-sigma plane, Gaborish + the edge-preserving filter's steps between
 // `xyb` and `tmp` (returns where the result lies), the colour tail on planes
 void launch_vardct_frame_xyb(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, float *xyb, size_t stride, hipStream_t stream);
+// a subsampled YCbCr frame (DevFrame::ycc_shifts): its DCT8 blocks into three float planes one behind the other, each of the padded
+// grid's size at its channel's resolution (ycbcr_dev.h: ycc_plane_dims)
+void launch_vardct_frame_ycc(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *planes, hipStream_t stream);
 void launch_epf_sigma(const DevPlan &plan, int32_t num_lf_groups, const int16_t *sharpness, const RestoreParams &p, float *sigma, uint32_t *sharp_or, hipStream_t stream);
 void launch_epf_sigma_cells(const int16_t *sharpness, const float *hfmul_inv, const RestoreParams &p, float *sigma, uint32_t *sharp_or, hipStream_t stream);
 float *launch_restoration(float *xyb, float *tmp, size_t pitch, const RestoreParams &p, bool gab, int32_t epf_iters, const float *sigma, hipStream_t stream);
@@ -87,6 +90,9 @@ void launch_inverse_squeeze(const int16_t *avg, const int16_t *res, int16_t *out
 void launch_pack_planes_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
 // alpha_kernels.hip: the kept alpha channel of a VarDCT frame into rectangle (x0, y0, w, h) of pixels already written
 void launch_alpha_merge(const int16_t *plane, int32_t pitch, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16);
+// ycbcr_kernels.hip: the three float planes of a YCbCr VarDCT frame (ycbcr_dev.h: YcbcrTail) to the picture's width x height pixels
+struct YcbcrTail;
+void launch_ycbcr_tail(const YcbcrTail &t, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16);
 // shift: the scale shift; 1, 2: ceil(width / s) x ceil(height / s) pixels, each the mean of its cell's rendered samples (scale_dev.h)
 void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false, int32_t shift = 0);
 

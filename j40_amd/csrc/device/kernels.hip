@@ -25,6 +25,7 @@
 #include "hf_uni_dev.h"
 #include "restore_dev.h"
 #include "scale_dev.h"
+#include "ycbcr_dev.h"
 #include "kernels.h"
 #include "../env.hpp"
 
@@ -62,7 +63,7 @@ struct HfLdsLayout {
 	uint32_t total;
 };
 
-template <bool TABLES_IN_LDS>
+template <bool TABLES_IN_LDS, bool SUB = false>
 __global__ void __launch_bounds__(64 * HF_WAVES) k_hf_entropy(DevPlan plan, int32_t first_group, int32_t num_groups, HfLdsLayout lay) {
 	extern __shared__ __attribute__((aligned(16))) uint8_t hf_lds[];
 	const DevFrame &f = *plan.frame;
@@ -130,7 +131,7 @@ __global__ void __launch_bounds__(64 * HF_WAVES) k_hf_entropy(DevPlan plan, int3
 			// every lane of the wave runs the same (scalarised) decoder on the same section; duplicate
 			// stores hit the same addresses with the same values
 			const DevSection &sec = plan.sections[pass * f.num_groups + g];
-			const uint32_t err = f.sparse_coeffs ? decode_hf_section<true, true>(plan, f, spec, t, pass, sec) : decode_hf_section<false, true>(plan, f, spec, t, pass, sec);
+			const uint32_t err = f.sparse_coeffs ? decode_hf_section<true, true, SUB>(plan, f, spec, t, pass, sec) : decode_hf_section<false, true, SUB>(plan, f, spec, t, pass, sec);
 			if (lane == 0) plan.status[pass * f.num_groups + g] = err;
 		}
 	}
@@ -588,7 +589,8 @@ template <int NB> struct K2Ahead {
 // The pixel kernels' output mode (a template parameter: each mode is an instantiation of its own, none pays for the others' code):
 // RGBA8 -- the colour tail to one u8x4 word per pixel, the default and the batches' form; XYB -- store_xyb above; RGBA16 -- the
 // colour tail to four u16 (xyb_to_rgba16, J40_U16X4), 8 bytes per pixel as one store (single-frame launches only)
-enum class OutMode { RGBA8, XYB, RGBA16 };
+// YCC -- a subsampled YCbCr frame (DevFrame::ycc_shifts; the 8x8 DCT kernel only, single-frame launches): store_ycc below
+enum class OutMode { RGBA8, XYB, RGBA16, YCC };
 template <OutMode OUT> constexpr int out_bytes() { return OUT == OutMode::RGBA16 ? 8 : 4; }   // bytes a pixel (a sample, XYB) takes in the output
 // Reduced-size output (j40hip_frame_set_scale; scale_dev.h), the kernels' second output parameter K = the scale shift: in the colour + pack
 // phase a lane owns an OUTPUT pixel of a block. It reads its s x s samples of the three planes from the tiles, runs the colour tail of the
@@ -628,6 +630,29 @@ template <OutMode OUT> __device__ __forceinline__ typename ScaleAcc<out_bytes<OU
 }
 __device__ __forceinline__ void store_xyb(uint8_t *base, size_t off, size_t plane_bytes, float sx, float sy, float sb) {
 	*(float *) (base + off) = sx; *(float *) (base + plane_bytes + off) = sy; *(float *) (base + 2 * plane_bytes + off) = sb;
+}
+
+// OutMode::YCC: sample (x, y) of the 8x8 block at pixel (px, py) into the planes of a subsampled YCbCr frame -- three float planes one
+// behind the other from `base`, plane c of the padded grid's size at the channel's resolution (ycbcr_dev.h: ycc_plane_dims). Channel
+// c's block lands at ((bx >> hshift) * 8, (by >> vshift) * 8) of its plane, and only where the channel has a block (bx, by multiples
+// of its 1 << shift); the whole block is stored, the planes reach the padded grid. PARITY UNPINNED ("YCbCr frames").
+// (YccPlanes: the frame's shifts, each plane's row pitch and where it starts, worked out once per workgroup ahead of the stores)
+struct YccPlanes { uint32_t shifts; int32_t pw[3]; size_t off[3]; };
+__device__ __forceinline__ YccPlanes ycc_planes(const DevFrame &f) {
+	YccPlanes p;
+	int32_t ph[3];
+	p.shifts = f.ycc_shifts;
+	ycc_plane_dims(f.width, f.height, p.shifts, p.pw, ph);
+	p.off[0] = 0; p.off[1] = (size_t) p.pw[0] * (size_t) ph[0]; p.off[2] = p.off[1] + (size_t) p.pw[1] * (size_t) ph[1];
+	return p;
+}
+__device__ __forceinline__ void store_ycc(uint8_t *base, const YccPlanes &p, int32_t px, int32_t py, int32_t y, int32_t x, const float s[3]) {
+	const int32_t bx = px >> 3, by = py >> 3;
+#pragma unroll
+	for (int c = 0; c < 3; ++c) {
+		const int32_t hs = (int32_t) ((p.shifts >> (2 * c)) & 1u), vs = (int32_t) ((p.shifts >> (2 * c + 1)) & 1u);
+		if (!(bx & hs) && !(by & vs)) ((float *) base)[p.off[c] + (size_t) (((by >> vs) << 3) + y) * (size_t) p.pw[c] + (size_t) (((bx >> hs) << 3) + x)] = s[c];
+	}
 }
 
 template <int LOGR, int LOGC, int NB, bool BATCH, OutMode OUT = OutMode::RGBA8, int K = 0>
@@ -774,6 +799,8 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 				__builtin_nontemporal_store(px, (decltype(px) *) (rgba + g_out[b] + (size_t) oy * stride_bytes + (size_t) ox * out_bytes<OUT>()));
 			}
 		} else {
+		YccPlanes ycc = {};
+		if constexpr (OUT == OutMode::YCC) ycc = ycc_planes(*plan.frame);
 #pragma unroll
 		for (int k = 0; k < PER; ++k) {
 			const int32_t p = N >= 256 ? tid + 256 * k : tid % N;
@@ -781,6 +808,12 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 			const uint32_t in_block = (uint32_t) y * (uint32_t) stride_bytes + (uint32_t) x * (uint32_t) out_bytes<OUT>();   // a block spans < 4 GB of output
 			for (int32_t b = N >= 256 ? 0 : tid / N; b < nb; b += PAR) {
 				const VbGeom &g = geom[b];
+				if constexpr (OUT == OutMode::YCC) {   // (the whole block: the planes reach the padded grid)
+					const float *t = lds + (size_t) b * 3 * TILE + y * P + x;
+					const float s3[3] = {t[0], t[TILE], t[2 * TILE]};
+					store_ycc(rgba, ycc, g.px, g.py, y, x, s3);
+					continue;
+				}
 				if (y >= g.effh || x >= g.effw) continue;
 				const float *t = lds + (size_t) b * 3 * TILE + y * P + x;
 				if constexpr (OUT == OutMode::XYB) { store_xyb(rgba, g_out[b] + in_block, stride_bytes * (size_t) plan.frame->height, t[0], t[TILE], t[2 * TILE]); continue; }
@@ -1115,6 +1148,14 @@ void launch_hf_entropy(const DevPlan &plan, const HfLaunchInfo &info, int32_t fi
 	lay.wave_bytes = align16(lay.off_wave_blocks + 1024 * (uint32_t) sizeof(DevGroupBlock));
 	lay.total = lay.off_wave + HF_WAVES * lay.wave_bytes;
 	const unsigned blocks = (unsigned) ((num_groups + HF_WAVES - 1) / HF_WAVES);
+	if (info.subsampled) {   // a subsampled YCbCr frame: the instantiation that knows which channel has a block where (hf_dev.h: SUB)
+		if (in_lds) {
+			static bool configured = false;
+			if (!configured) { (void) hipFuncSetAttribute((const void *) k_hf_entropy<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); configured = true; }
+			hipLaunchKernelGGL((k_hf_entropy<true, true>), dim3(blocks), dim3(64 * HF_WAVES), lay.total, stream, plan, first_group, num_groups, lay);
+		} else hipLaunchKernelGGL((k_hf_entropy<false, true>), dim3(blocks), dim3(64 * HF_WAVES), lay.total, stream, plan, first_group, num_groups, lay);
+		return;
+	}
 	if (in_lds) {
 		static bool configured = false;
 		if (!configured) { (void) hipFuncSetAttribute((const void *) k_hf_entropy<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); configured = true; }
@@ -1244,6 +1285,14 @@ static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const 
 		}
 		break;
 	}
+}
+// the DCT8 blocks of a subsampled YCbCr frame (nothing else occurs in one: frame.cpp, ycbcr_scope) into its planes (store_ycc)
+void launch_vardct_frame_ycc(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *planes, hipStream_t stream) {
+	const int32_t count = class_start[1] - class_start[0];
+	if (count <= 0) return;
+	constexpr int NB = 16;
+	constexpr size_t lds_bytes = (size_t) NB * 3 * 8 * 9 * sizeof(float);
+	hipLaunchKernelGGL((k_vardct_dct<3, 3, NB, false, OutMode::YCC>), dim3((unsigned) ((count + NB - 1) / NB)), dim3(256), lds_bytes, stream, plan, sorted + class_start[0], count, 0, 0, (uint8_t *) planes, (size_t) 0, nullptr, nullptr, 1, 0, 0);
 }
 void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16, int32_t shift) {
 	launch_vardct_class_impl(plan, dctsel, list, count, large_scratch, rgba, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, rgba16 ? OutMode::RGBA16 : OutMode::RGBA8, shift}, stream);

@@ -53,7 +53,8 @@ struct DevSection {
 struct DevGroupBlock {
 	uint32_t coeffoff_qfidx;  // as j40__varblock (j40.h:6352): coefficient offset | qf index
 	uint16_t pos_dct;         // bits 0-9: y8 * 32 + x8 inside the group; bits 10-14: DctSelect
-	uint16_t bctx3;           // block context (j40.h:6951-6953, < 16) of channel Y | X << 4 | B << 8, looked up on the host
+	uint16_t bctx3;           // block context (j40.h:6951-6953, < 16) of channel Y | X << 4 | B << 8, looked up on the host;
+	                          // bits 12-14 (subsampled YCbCr frames only, else 0): channel Y / X / B has no block at this position
 };
 
 // work item of the coefficients -> pixels kernels, sorted by DctSelect on the host. Self-contained: everything the kernels
@@ -103,6 +104,10 @@ struct DevFrame {
 	int32_t check_section_end;
 	uint32_t single_declared_end;            // single-section frames: where the TOC says the section ends (byte offset); it is readable to the
 	                                         // end of the codestream, stopping short of this is `shrt`, going past it `excs` (j40.h:7796-7803)
+	// a YCbCr frame with subsampled channels (j40hip_frame_set_ycbcr; 0 for every other frame): hshift | vshift << 1 of channel c (slot
+	// 0 Cb, 1 Y, 2 Cr) at bits 2c. Channel c has a block only where the block's column is a multiple of 1 << hshift and its row of
+	// 1 << vshift (DevGroupBlock::bctx3 bits 12-14 say where it has none); its samples go to a plane of its own size (OutMode::YCC)
+	uint32_t ycc_shifts;
 };
 
 // one non-zero quantised HF coefficient in FOUR bytes: scan position inside its block (a block has at most 256 x 256 positions) in the
@@ -330,6 +335,7 @@ struct HfLaunchInfo {
 	bool tables_fit_lds;
 	bool lanes_fast;             // every pass: rANS without LZ77, and hf_lanes_dev.h's tables fit the LDS budget
 	uint32_t lanes_lds_bytes;    // LDS k_hf_lanes needs for this frame's tables (plus HF_LANE_COLS_BYTES per wavefront)
+	bool subsampled;             // a YCbCr frame with subsampled channels (DevFrame::ycc_shifts): k_hf_entropy's instantiation that skips absent channels, never the fast path
 };
 
 // ---- LfGroup sections of VarDCT frames decoded on the device (lf_decode.hip) ----

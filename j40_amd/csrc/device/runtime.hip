@@ -4,6 +4,7 @@
 // No CPU fallback lives here: without a HIP device every entry point returns "!gpu".
 #include "runtime_state.hpp"
 #include "hostcopy.hpp"
+#include "ycbcr_dev.h"
 
 // a Modular frame's groups can be decoded apart from each other when every group has a section of its own and no frame-wide inverse
 // transform reads across groups (j40hip_frame_set_group_range's rule; a region is otherwise widened to every group)
@@ -252,6 +253,59 @@ uint32_t j40hip_rt::restore_params(const FrameHeader &fh, int mode, RestoreParam
 	}
 	return 0;
 }
+// ---- YCbCr frames (j40hip_frame_set_ycbcr; device/ycbcr_dev.h, ycbcr_kernels.hip) ----
+// k_ycbcr_tail over three full-size planes one behind the other, `pitch` floats a row (a 4:4:4 frame: what launch_vardct_frame_xyb or
+// the restoration filters left)
+static void ycbcr_tail_444(j40hip_frame *h, const float *planes, size_t pitch, uint8_t *img, size_t stride, hipStream_t s) {
+	j40hip_device_state *st = h->dev;
+	const int32_t W = h->frame.fh.width, H = h->frame.fh.height;
+	YcbcrTail t;
+	for (int c = 0; c < 3; ++c) { t.plane[c] = planes + (size_t) c * pitch * (size_t) H; t.pitch[c] = (int32_t) pitch; t.pw[c] = W; t.ph[c] = H; t.hshift[c] = t.vshift[c] = 0; }
+	t.width = W; t.height = H;
+	ycbcr_tail_scale(&t, h->frame.im.bpp, out16(h));
+	launch_ycbcr_tail(t, img, stride, s, out16(h));
+	for (int c = 0; c < 3; ++c) { st->ycc_read.plane[c] = t.plane[c]; st->ycc_read.pitch[c] = t.pitch[c]; st->ycc_read.pw[c] = W; st->ycc_read.ph[c] = H; }
+	h->ycbcr_used = true;
+}
+// The pixel stage of a YCbCr frame: the pixel kernels leave float planes -- a 4:4:4 frame the three full-size planes of OutMode::XYB,
+// rows padded to 16 bytes; a subsampled one a plane per channel at the channel's resolution over the padded grid (OutMode::YCC) --
+// and k_ycbcr_tail makes the pixels of them. The planes are made at the first decode and kept with the frame.
+static uint32_t ycbcr_pixels(j40hip_frame *h, const int32_t *class_start, const DevVarblock *list, uint8_t *img, size_t stride, hipStream_t s) {
+	j40hip_device_state *st = h->dev;
+	const Frame &fr = h->frame;
+	const int32_t W = fr.fh.width, H = fr.fh.height;
+	bool ok = true;
+	if (!fr.fh.subsampled()) {
+		const size_t pitch = ((size_t) W + 3) & ~(size_t) 3;
+		if (!st->d_ycc) st->d_ycc = st->scratch<float>(3 * pitch * (size_t) H, ok);
+		if (!ok) { st->d_ycc = nullptr; return ERR_MEM; }
+		launch_vardct_frame_xyb(st->plan, class_start, list, st->d_large_scratch, st->d_ycc, pitch * 4, s);
+		ycbcr_tail_444(h, st->d_ycc, pitch, img, stride, s);
+		return 0;
+	}
+	uint32_t shifts = 0;
+	for (int c = 0; c < 3; ++c) shifts |= (uint32_t) (fr.fh.hshift[c] | fr.fh.vshift[c] << 1) << (2 * c);
+	YcbcrTail t;
+	ycc_plane_dims(W, H, shifts, t.pw, t.ph);
+	size_t total = 0;
+	for (int c = 0; c < 3; ++c) total += (size_t) t.pw[c] * (size_t) t.ph[c];
+	if (!st->d_ycc) st->d_ycc = st->scratch<float>(total, ok);
+	if (!ok) { st->d_ycc = nullptr; return ERR_MEM; }
+	launch_vardct_frame_ycc(st->plan, class_start, list, st->d_ycc, s);
+	size_t off = 0;
+	for (int c = 0; c < 3; ++c) {
+		t.plane[c] = st->d_ycc + off; t.pitch[c] = t.pw[c]; t.hshift[c] = fr.fh.hshift[c]; t.vshift[c] = fr.fh.vshift[c];
+		off += (size_t) t.pw[c] * (size_t) t.ph[c];
+	}
+	t.width = W; t.height = H;
+	ycbcr_tail_scale(&t, fr.im.bpp, out16(h));
+	if (!ycbcr_tail_valid(t)) return ERR_RNGE;   // (cannot happen: the planes reach the padded grid)
+	launch_ycbcr_tail(t, img, stride, s, out16(h));
+	for (int c = 0; c < 3; ++c) { st->ycc_read.plane[c] = t.plane[c]; st->ycc_read.pitch[c] = t.pitch[c]; st->ycc_read.pw[c] = t.pw[c]; st->ycc_read.ph[c] = t.ph[c]; }
+	h->ycbcr_used = true;
+	return 0;
+}
+
 static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t stride_bytes, int mode, hipStream_t s) {
 	j40hip_device_state *st = h->dev;
 	const Frame &fr = h->frame;
@@ -275,6 +329,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	}
 	if (perr) {   // the filters cannot run: the picture without them, and the complaint behind the sections' own (j40hip_frame_status)
 		st->restore_err = perr;
+		if (st->ycbcr) return ycbcr_pixels(h, st->class_start, st->d_vb_sorted, rgba_dev, stride_bytes, s);
 		launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, rgba_dev, stride_bytes, s, out16(h));
 		return 0;
 	}
@@ -295,14 +350,15 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	}
 	st->d_restored = launch_restoration(st->d_xyb, st->d_xyb_tmp, (size_t) W, p, r.gab, r.epf_iters, st->d_sigma, s);
 	marks.mark(1);
-	launch_xyb_to_rgba(st->d_restored, (size_t) W, st->plan.frame, W, H, rgba_dev, stride_bytes, s, out16(h));
+	if (st->ycbcr) ycbcr_tail_444(h, st->d_restored, (size_t) W, rgba_dev, stride_bytes, s);   // (the filtered planes are Cb, Y, Cr)
+	else launch_xyb_to_rgba(st->d_restored, (size_t) W, st->plan.frame, W, H, rgba_dev, stride_bytes, s, out16(h));
 	st->restore_ran = mode;
 	if (marks.ev && hipEventSynchronize(pair.ev[1]) == hipSuccess) (void) hipEventElapsedTime(&st->restore_ms, pair.ev[0], pair.ev[1]);
 	return 0;
 }
 
 // what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it
-static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
+static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
 
 // One VarDCT decode as decode_impl (whole frames, group ranges) and decode_region (covers) describe it to run_vardct
 struct VardctRun {
@@ -335,6 +391,8 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 		// the restoration filters asked for and signalled: the pixel kernels leave the samples in XYB planes, Gaborish and the
 		// edge-preserving filter run over the whole picture, the colour tail follows on the filtered planes (restore_kernels.h)
 		if (uint32_t e = decode_restored(h, run.img, run.img_stride, rmode, s)) return e;
+	} else if (st->ycbcr) {
+		if (uint32_t e = ycbcr_pixels(h, run.class_start, run.list, run.img, run.img_stride, s)) return e;
 	} else launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, run.img, run.img_stride, s, out16(h), run.shift);
 	if (run.crop_to) launch_region_crop(run.crop_from, run.img_stride, run.crop_to, run.crop_stride, run.crop_w, run.crop_h, (int32_t) pixel_bytes(h), s);
 	marks.mark(3);
@@ -350,6 +408,9 @@ static uint32_t decode_scaled(j40hip_frame *h, void *rgba_dev, size_t stride_byt
 static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, bool whole_frame = false) {
 	if (h && h->frame.lf_only) return ERR_ULF;
 	if (!h || !h->dev) return ERR_GPU;
+	// a YCbCr frame: uploaded with the switch on, decoded only while it stays on, and whole -- a region, a scale and a group range
+	// keep refusing such frames
+	if (h->dev->ycbcr && (!j40hip_ycbcr_on(h) || h->region_set || h->scale > 0 || whole_frame || h->dev->first_group != 0 || h->dev->num_groups != h->frame.fh.num_groups)) return ERR_TODO;
 	if (h->region_set && !whole_frame) return decode_region(h, rgba_dev, stride_bytes, s, ms3);   // (whole_frame: decode_region's own call, for a widened region)
 	if (h->scale > 0 && !whole_frame) return decode_scaled(h, rgba_dev, stride_bytes, s, ms3);    // (... and decode_scaled's, for a staged combination)
 	if (stride_too_small(h, stride_bytes)) return ERR_RNGE;
@@ -596,7 +657,7 @@ static void two_phase_plan(j40hip_frame *h, size_t image_bytes) {
 	const bool allowed = env_on("J40HIP_TWO_PHASE", true);   // (looked at per upload: tests switch it between frames)
 	const Frame &fr = h->frame;
 	const int64_t ng = fr.fh.num_groups;
-	if (!allowed || st->is_modular || !st->plan.events || !st->plan.block_events || st->has_trailers || fr.toc.single || fr.fh.num_passes != 1 || ng < 64 || image_bytes < ((size_t) 16 << 20)) return;
+	if (!allowed || st->is_modular || st->ycbcr || !st->plan.events || !st->plan.block_events || st->has_trailers || fr.toc.single || fr.fh.num_passes != 1 || ng < 64 || image_bytes < ((size_t) 16 << 20)) return;
 	if (st->first_group != 0 || st->num_groups != ng || fr.toc.pass_groups.size() != (size_t) ng) return;
 	if (!hf_entropy_fast_path(st->plan, st->hf)) return;
 	std::vector<uint32_t> order((size_t) ng);

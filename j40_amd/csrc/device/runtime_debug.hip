@@ -1,6 +1,7 @@
 // j40_amd/csrc/device/runtime_debug.hip -- the small setters and getters of a frame handle, and what the tests read back: stage
 // dumps (j40hip_frame_read_*) and the known-answer hooks (j40hip_kat_device_*)
 #include "runtime_state.hpp"
+#include "ycbcr_dev.h"
 
 extern "C" uint32_t j40hip_frame_set_output_format(j40hip_frame *h, int32_t format) {
 	if (!h) return ERR_RNGE;
@@ -36,6 +37,32 @@ extern "C" int j40hip_frame_sharpness(const j40hip_frame *h, int64_t gg, int16_t
 	memcpy(out, g.sharpness.data(), g.sharpness.size() * 2);
 	return 0;
 }
+// known-answer / measuring hook: k_ycbcr_tail alone (include/j40hip.h)
+extern "C" uint32_t j40hip_kat_device_ycbcr_tail(const float *const planes_dev[3], const int32_t plane_dims[9], const int32_t shifts[6], int32_t width, int32_t height, int32_t bpp, int32_t format, void *out_dev, size_t stride_bytes, void *stream) {
+	if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
+	const size_t pb = format == J40HIP_U16X4 ? 8 : 4;
+	if (!planes_dev || !plane_dims || !shifts || !out_dev || bpp < 8 || bpp > 15 || width < 1 || height < 1) return ERR_RNGE;
+	if (stride_bytes < pb * (size_t) width || stride_bytes % pb || (uintptr_t) out_dev % pb) return ERR_RNGE;
+	YcbcrTail t;
+	for (int c = 0; c < 3; ++c) {
+		t.plane[c] = planes_dev[c]; t.pitch[c] = plane_dims[3 * c]; t.pw[c] = plane_dims[3 * c + 1]; t.ph[c] = plane_dims[3 * c + 2];
+		t.hshift[c] = shifts[2 * c]; t.vshift[c] = shifts[2 * c + 1];
+		if ((uintptr_t) planes_dev[c] % 4) return ERR_RNGE;
+	}
+	t.width = width; t.height = height;
+	if (!ycbcr_tail_valid(t)) return ERR_RNGE;
+	ycbcr_tail_scale(&t, bpp, format == J40HIP_U16X4);
+	launch_ycbcr_tail(t, (uint8_t *) out_dev, stride_bytes, (hipStream_t) stream, format == J40HIP_U16X4);
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+}
+// staged hook: plane c of the last decode through the YCbCr path as the tail read it, tightly packed (include/j40hip.h)
+extern "C" uint32_t j40hip_frame_read_ycbcr(j40hip_frame *h, int c, float *out) {
+	if (!h || !h->dev || !h->ycbcr_used || c < 0 || c > 2 || !out || !h->dev->ycc_read.plane[c]) return ERR_RNGE;
+	const j40hip_device_state::YccRead &r = h->dev->ycc_read;
+	if (hipSetDevice(h->dev->device) != hipSuccess) return ERR_GPU;
+	return hipMemcpy2D(out, (size_t) r.pw[c] * 4, r.plane[c], (size_t) r.pitch[c] * 4, (size_t) r.pw[c] * 4, (size_t) r.ph[c], hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+}
+
 // after a decode that ran the filters (synchronised): stage 0 the samples as the inverse transforms left them, 1 the filtered ones --
 // three planes of width * height floats (X, Y, B); stage 2: the reciprocal-sigma plane (w8 * h8 floats)
 extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out) {

@@ -185,6 +185,12 @@ struct j40hip_device_state {
 	uint32_t restore_err = 0;            // the last decode's "gab0" / "epf0" / "shrp" (reported behind the sections' codes)
 	int restore_ran = 0;                 // the mode the last decode ran the filters in (0: it did not)
 	float restore_ms = 0;
+	// a YCbCr frame (j40hip_frame_set_ycbcr; runtime.hip: ycbcr_pixels). ycbcr: the plan was built for one (the switch was on at upload).
+	// d_ycc: the planes the pixel kernels leave for k_ycbcr_tail, made at the first decode, kept with the frame. ycc_read: what the last
+	// decode's tail read (j40hip_frame_read_ycbcr) -- those planes, or the restoration filters' result
+	bool ycbcr = false;
+	float *d_ycc = nullptr;
+	struct YccRead { const float *plane[3] = {nullptr, nullptr, nullptr}; int32_t pitch[3] = {0, 0, 0}, pw[3] = {0, 0, 0}, ph[3] = {0, 0, 0}; } ycc_read;
 	// the LF preview (lf_preview.hip): the frame's LfGroups and LF integers as the preview kernel reads them -- the integers are the
 	// plan's when it holds them (parsed with flags & 1), else in an allocation of their own (LF-only frames at upload, other frames at
 	// their first preview); lfp_host is what was copied, kept with the frame because the copy is asynchronous

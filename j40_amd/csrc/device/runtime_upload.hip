@@ -171,11 +171,12 @@ static uint32_t upload_impl(j40hip_frame *h, int device, hipStream_t s) {
 	const bool timing = api_timing();   // (where an upload's time goes: plan build, staging, copy + LfGroup tail)
 	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double tu0 = timing ? now() : 0;
-	if (uint32_t e = build_vardct_plan(h->frame, h->cs, h->cs_size, &hp, h->threads)) return e;
+	if (uint32_t e = build_vardct_plan(h->frame, h->cs, h->cs_size, &hp, h->threads, j40hip_ycbcr_on(h))) return e;
 	const double tu1 = timing ? now() : 0;
 
 	j40hip_device_state *st = new j40hip_device_state();
 	h->dev = st; st->device = device; st->force_dense = h->force_dense;
+	st->ycbcr = h->frame.fh.do_ycbcr;   // (a plan exists: the switch was on)
 	bool ok = ensure_constant_tables(device);
 	DevPlan &plan = st->plan;
 	memset(&plan, 0, sizeof plan);

@@ -274,7 +274,14 @@ static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f
 		f->use_lf_frame = flags >> 5 & 1; f->skip_adapt_lf_smooth = flags >> 7 & 1;
 		if (!im.xyb_encoded) f->do_ycbcr = br.u(1);
 		if (!f->use_lf_frame) {
-			if (f->do_ycbcr) f->jpeg_upsampling = (int32_t) br.u(6);
+			if (f->do_ycbcr) {
+				f->jpeg_upsampling = (int32_t) br.u(6);
+				// (FrameHeader::hshift: the sampling factors of the three modes, coarser channels shifted against the finest)
+				static const int8_t FACTOR[4][2] = {{1, 1}, {2, 2}, {2, 1}, {1, 2}};
+				int maxh = 1, maxv = 1;
+				for (int c = 0; c < 3; ++c) { const int8_t *m = FACTOR[(f->jpeg_upsampling >> (2 * c)) & 3]; maxh = std::max<int>(maxh, m[0]); maxv = std::max<int>(maxv, m[1]); }
+				for (int c = 0; c < 3; ++c) { const int8_t *m = FACTOR[(f->jpeg_upsampling >> (2 * c)) & 3]; f->hshift[c] = (int8_t) (maxh / m[0] - 1); f->vshift[c] = (int8_t) (maxv / m[1] - 1); }
+			}
 			J40HIP_SHOULD(br.u(2) == 0, "TODO");  // upsampling
 			for (size_t i = 0; i < im.ec.size(); ++i) J40HIP_SHOULD(br.u(2) == 0, "TODO");
 		}
@@ -640,6 +647,22 @@ static void lf_group_finish(Frame *f, LfGroup *gg, int32_t extra_prec, const int
 		gg->mult_lf[c] = f->m_lf_scaled[c] / (float) (f->global_scale * f->quant_lf) * (float) (65536 >> extra_prec);  // j40.h:6562
 		ch[c] = lf[XYB_FROM_STREAM[c]];
 	}
+	// A YCbCr frame with subsampled channels (PARITY UNPINNED, FrameHeader::hshift): channel c's LF image is (w8 >> hshift) x (h8 >> vshift).
+	// Everything behind this point works on the full grid, so each channel is spread over it: the sample of (x, y) goes to cell
+	// (x << hshift, y << vshift), the one cell of its MCU where the channel has a block, and for the LF index -- which stays on the
+	// full grid -- to every cell it covers. With DCT8 alone and no smoothing (ycbcr_scope) a block's LLF coefficient is its cell's sample.
+	std::vector<int16_t> spread[3], covered[3];
+	const bool subsampled = fh.subsampled();
+	if (subsampled) {
+		for (int c = 0; c < 3; ++c) {
+			const int32_t hs = fh.hshift[c], vs = fh.vshift[c], cw = w8 >> hs;
+			spread[c].assign(cells, 0); covered[c].resize(cells);
+			for (int32_t y = 0; y < h8; ++y) for (int32_t x = 0; x < w8; ++x) covered[c][(size_t) y * (size_t) w8 + (size_t) x] = ch[c][(size_t) (y >> vs) * (size_t) cw + (size_t) (x >> hs)];
+			for (int32_t y = 0; y < (h8 >> vs); ++y) for (int32_t x = 0; x < cw; ++x) spread[c][(size_t) (y << vs) * (size_t) w8 + (size_t) (x << hs)] = ch[c][(size_t) y * (size_t) cw + (size_t) x];
+			ch[c] = covered[c].data();
+		}
+		take = nullptr;
+	}
 	// LF index: thresholds counted on the raw integers; note each factor is a channel's own threshold count (j40.h:6566-6570)
 	gg->lfindices.assign(cells, 0);
 	auto add = [&](const int16_t *p, const int32_t *thr, int32_t n) { for (int32_t t = 0; t < n; ++t) for (size_t i = 0; i < cells; ++i) gg->lfindices[i] = (uint8_t) (gg->lfindices[i] + (p[i] > thr[t])); };
@@ -649,6 +672,7 @@ static void lf_group_finish(Frame *f, LfGroup *gg, int32_t extra_prec, const int
 	add(ch[1], f->lf_thr[1], f->nb_lf_thr[1]);
 	for (int c = 0; c < 3; ++c) {
 		if (take) gg->lfraw[c].swap(*take[XYB_FROM_STREAM[c]]);
+		else if (subsampled) gg->lfraw[c].swap(spread[c]);
 		else gg->lfraw[c].assign(ch[c], ch[c] + cells);
 	}
 	gg->tail_pending = true;
@@ -699,15 +723,18 @@ void read_lf_group_raw(BitReader &br, const Frame &f, const LfGroup &gg, LfRaw *
 	const int64_t sidx0 = 1 + gg.idx, sidx2 = 1 + 2 * fh.num_lf_groups + gg.idx;
 	const int32_t w8 = gg.width8, h8 = gg.height8, w64 = gg.width64, h64 = gg.height64;
 	J40HIP_SHOULD(!fh.use_lf_frame, "TODO");
-	J40HIP_SHOULD(fh.jpeg_upsampling == 0, "TODO");
+	// (jpeg_upsampling: refused as the reference refuses it, j40.h:6749, unless YCbCr frames are asked for -- Frame::allow_ycbcr)
+	J40HIP_SHOULD(fh.jpeg_upsampling == 0 || f.allow_ycbcr, "TODO");
+	J40HIP_SHOULD(fh.layout_served(), "TODO");   // (a layout other than 4:4:4, 4:2:0, 4:2:2, 4:4:0: FrameHeader::layout_served)
 
-	// LF image: three channels in Y, X, B order
+	// LF image: three channels in Y, X, B order, each at its own size where the frame subsamples (FrameHeader::hshift)
+	static const int SLOT_OF_STREAM[3] = {1, 0, 2};
 	out->extra_prec = (int32_t) br.u(2);
 	Modular lfm; lfm.bpp = f.im.bpp;
 	lfm.channel.assign(3, Plane());
-	for (Plane &p : lfm.channel) { p.width = w8; p.height = h8; }
+	for (int c = 0; c < 3; ++c) { Plane &p = lfm.channel[(size_t) c]; p.width = w8 >> fh.hshift[SLOT_OF_STREAM[c]]; p.height = h8 >> fh.vshift[SLOT_OF_STREAM[c]]; }
 	decode_modular_image(br, &f.global_tree, &f.global_codespec, sidx0, &lfm);
-	for (int c = 0; c < 3; ++c) J40HIP_SHOULD(lfm.channel[(size_t) c].width == w8 && lfm.channel[(size_t) c].height == h8, "TODO");
+	for (int c = 0; c < 3; ++c) J40HIP_SHOULD(lfm.channel[(size_t) c].width == w8 >> fh.hshift[SLOT_OF_STREAM[c]] && lfm.channel[(size_t) c].height == h8 >> fh.vshift[SLOT_OF_STREAM[c]], "TODO");
 
 	// HF metadata
 	const int32_t nb_varblocks = (int32_t) br.u(ceil_lg32((uint32_t) (w8 * h8))) + 1;
@@ -745,7 +772,30 @@ static void allocate_lf_groups(Frame *f) {  // j40.h:7659
 		gg.width = std::min(ggsize, fh.width - ggx); gg.height = std::min(ggsize, fh.height - ggy);
 		gg.width8 = ceil_div(gg.width, 8); gg.height8 = ceil_div(gg.height, 8);
 		gg.width64 = ceil_div(gg.width, 64); gg.height64 = ceil_div(gg.height, 64);
+		if (fh.subsampled()) {
+			// PARITY UNPINNED: the block grid of a subsampled frame is padded to whole MCUs; group and LfGroup counts stay the picture's
+			const int32_t mh = fh.max_hshift(), mv = fh.max_vshift();
+			const int32_t fw8 = ceil_div(fh.width, 8 << mh) << mh, fh8 = ceil_div(fh.height, 8 << mv) << mv;
+			gg.width8 = std::min(ggsize / 8, fw8 - ggx / 8); gg.height8 = std::min(ggsize / 8, fh8 - ggy / 8);
+			gg.width64 = ceil_div(gg.width8, 8); gg.height64 = ceil_div(gg.height8, 8);
+		}
 	}
+}
+
+uint32_t ycbcr_scope(const Frame &f) {
+	const FrameHeader &fh = f.fh;
+	if (fh.is_modular || !fh.do_ycbcr) return (uint32_t) E4("TODO");   // (nothing of this kind to serve)
+	if (f.im.grey) return (uint32_t) E4("TODO");                       // a grey JPEG has one channel; how its frame is laid out is not known here
+	if (f.im.exp_bits || f.im.bpp < 8) return (uint32_t) E4("TODO");    // float samples and depths below 8: what the pixel kernels refuse for any frame
+	if (fh.use_lf_frame) return (uint32_t) E4("TODO");                 // LF frames are not served at all
+	if (!fh.layout_served()) return (uint32_t) E4("TODO");             // (the parse has refused it already)
+	if (fh.subsampled()) {
+		if (!f.allow_ycbcr) return (uint32_t) E4("TODO");              // (parsed without the switch: cannot happen, the parse refuses)
+		if (f.dct_select_used & ~1u) return (uint32_t) E4("TODO");     // a varblock other than DCT8: how a larger block meets a coarser channel's grid is not known here
+		if (!fh.skip_adapt_lf_smooth) return (uint32_t) E4("TODO");    // the smoothing reads the three channels of a cell together: they are of different sizes
+		if (fh.restoration.gab || fh.restoration.epf_iters > 0) return (uint32_t) E4("TODO");   // the filters run over full-size planes of all three channels
+	}
+	return 0;
 }
 
 static void prepare_tables(Frame *f) {  // j40.h:7694-7732

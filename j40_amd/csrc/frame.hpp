@@ -7,6 +7,7 @@
 // j40__lf_group (6722), j40__hf_global (6819), j40__load_dq_matrix (4828), j40__natural_order (4980).
 #pragma once
 #include "modular.hpp"
+#include <algorithm>
 #include <array>
 
 namespace j40hip {
@@ -16,6 +17,9 @@ inline bool api_timing() { static const bool v = env_str("J40HIP_API_TIMING") !=
 
 // J40HIP_ALPHA=1: VarDCT frames keep their alpha channel where j40hip_frame_set_alpha(f, 1) would be taken (include/j40hip.h); read once
 inline bool alpha_env() { static const bool v = [] { const char *e = env_str("J40HIP_ALPHA"); return e && atoi(e) > 0; }(); return v; }
+
+// J40HIP_YCBCR=1: YCbCr VarDCT frames (recompressed JPEGs) are served where j40hip_frame_set_ycbcr(f, 1) would be taken (include/j40hip.h); read once
+inline bool ycbcr_env() { static const bool v = [] { const char *e = env_str("J40HIP_YCBCR"); return e && atoi(e) > 0; }(); return v; }
 
 struct ExtraChannel { int32_t type = 0, bpp = 8, exp_bits = 0, dim_shift = 0; bool alpha_associated = false; };
 enum { EC_ALPHA = 0, EC_SPOT = 2, EC_BLACK = 4, EC_CFA = 5 };
@@ -42,6 +46,16 @@ struct FrameHeader {
 	bool has_noise = false, has_patches = false, has_splines = false, use_lf_frame = false, skip_adapt_lf_smooth = false;
 	bool do_ycbcr = false;
 	int32_t jpeg_upsampling = 0;
+	// what jpeg_upsampling says of the channels in coded order (slot 0 Cb, 1 Y, 2 Cr): log2 of how much coarser than the finest channel
+	// each is sampled, per axis (0 or 1). PARITY UNPINNED (the reference refuses such frames, j40.h:6749): mode (v >> 2c) & 3 of channel c
+	// means the sampling factors (h, v) = (1, 1), (2, 2), (2, 1), (1, 2); shift = log2(largest factor / the channel's)
+	int8_t hshift[3] = {0, 0, 0}, vshift[3] = {0, 0, 0};
+	bool subsampled() const { return hshift[0] | hshift[1] | hshift[2] | vshift[0] | vshift[1] | vshift[2]; }
+	// the layouts that are served: luma at full resolution, the two chroma channels alike (4:4:4, 4:2:0, 4:2:2, 4:4:0). jpeg_upsampling can
+	// say others -- Y coarser than chroma, Cb and Cr differing --; nothing here was ever made or tested with them, they stay "TODO"
+	bool layout_served() const { return !hshift[1] && !vshift[1] && hshift[0] == hshift[2] && vshift[0] == vshift[2]; }
+	int32_t max_hshift() const { return std::max<int32_t>(hshift[0], std::max(hshift[1], hshift[2])); }
+	int32_t max_vshift() const { return std::max<int32_t>(vshift[0], std::max(vshift[1], vshift[2])); }
 	int32_t group_size_shift = 8;
 	int32_t x_qm_scale = 3, b_qm_scale = 2;
 	int32_t num_passes = 1;
@@ -183,13 +197,16 @@ struct Frame {
 	// does not serve (sequence_refusal) is "TODO". Set before parse_frame.
 	const ImageMeta *seq_im = nullptr;
 	bool seq_blend = false;   // ... and the sequence serves the blend modes other than Replace (J40HIP_SEQ_BLEND)
+	// YCbCr frames are asked for (J40HIP_PARSE_YCBCR or J40HIP_YCBCR=1): a frame with subsampled channels is parsed -- its block grid padded
+	// to whole MCUs, every LF channel at its own size -- instead of refused with "TODO" before its LF image is read. Set before parse_frame.
+	bool allow_ycbcr = false;
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
 	Frame with_same_inputs() const {
 		Frame g;
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
-		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend;
+		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section
@@ -228,6 +245,9 @@ void finish_lf_tail(Frame *f);
 // channel c (X, Y, B) of the LF image over the frame: the dequantised, smoothed sample of every 8x8 cell, ceil(width / 8) x
 // ceil(height / 8) floats row by row -- what the LLF coefficients are made of. Returns false when the frame holds no LF integers.
 bool lf_plane(const Frame &f, int c, float *out);
+
+// 0 when the single-frame decode serves this YCbCr VarDCT frame once it is asked to (j40hip_frame_set_ycbcr), else "TODO"
+uint32_t ycbcr_scope(const Frame &f);
 
 struct GroupInfo { int32_t ggidx, gx_in_gg, gy_in_gg, gw, gh; };
 GroupInfo group_info(const FrameHeader &fh, int64_t gidx);  // j40.h:7734

@@ -83,6 +83,11 @@ void fill_sections(const Frame &fr, std::vector<DevSection> *sections) {
 		}
 		d.ggidx = gi.ggidx; d.gx8 = gi.gx_in_gg / 8; d.gy8 = gi.gy_in_gg / 8;
 		d.gw8 = ceil_div(gi.gw, 8); d.gh8 = ceil_div(gi.gh, 8);
+		if (fr.fh.subsampled()) {   // (the group's cells come from the padded grid: frame.cpp, allocate_lf_groups)
+			const LfGroup &gg = fr.lf_groups[(size_t) gi.ggidx];
+			const int32_t gdim8 = 1 << (fr.fh.group_size_shift - 3);
+			d.gw8 = std::min(gdim8, gg.width8 - d.gx8); d.gh8 = std::min(gdim8, gg.height8 - d.gy8);
+		}
 		d.gx = fr.lf_groups[(size_t) gi.ggidx].left + gi.gx_in_gg; d.gy = fr.lf_groups[(size_t) gi.ggidx].top + gi.gy_in_gg; d.gw = gi.gw; d.gh = gi.gh;
 	}
 }
@@ -109,6 +114,7 @@ bool fill_event_ranges(const std::vector<DevSection> &sections, int32_t num_grou
 void fill_hf_launch_info(const std::vector<DevCodeSpec> &coeff_specs, uint32_t block_ctx_size, size_t coeff_floats, HfLaunchInfo *out) {
 	HfLaunchInfo &hf = *out;
 	hf.block_ctx_size = block_ctx_size; hf.max_num_dist = hf.max_clusters = hf.max_table_bytes = 0;
+	hf.subsampled = false;
 	for (const DevCodeSpec &sp : coeff_specs) {
 		hf.max_num_dist = std::max<uint32_t>(hf.max_num_dist, (uint32_t) sp.num_dist);
 		hf.max_clusters = std::max<uint32_t>(hf.max_clusters, (uint32_t) sp.num_clusters);
@@ -154,10 +160,11 @@ void fill_frame_constants(const Frame &fr, DevFrame *out) {
 	df.base_corr_x = fr.base_corr_x; df.base_corr_b = fr.base_corr_b; df.inv_colour_factor = fr.inv_colour_factor;
 	for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) df.opsin_inv_mat[i * 3 + j] = fr.im.opsin_inv_mat[i][j];
 	df.itscale = 255.0f / fr.im.intensity_target;
+	df.ycc_shifts = 0;   // (a subsampled YCbCr frame: build_vardct_plan)
 
 }
 
-uint32_t build_vardct_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, HostPlan *hp, int threads) {
+uint32_t build_vardct_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, HostPlan *hp, int threads, bool ycbcr) {
 	static const bool timing = env_str("J40HIP_PLAN_TIMING") != nullptr;
 	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double tb0 = timing ? now() : 0; double tbA = 0, tbB = 0, tbC = 0;
@@ -165,7 +172,8 @@ uint32_t build_vardct_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, H
 	if (fr.fh.is_modular) return ERR_TODO;
 	// same limits as j40.h:7867, 7917-7921. (A VarDCT frame of an image without xyb_encoded passes them: the reference
 	// runs the XYB inverse with the default opsin matrix on it all the same, j40.h:7206-7233, and so does K2.)
-	if (fr.im.grey || fr.fh.do_ycbcr) return ERR_TODO;
+	// A YCbCr frame only for the caller that asks for it (the single-frame decode with j40hip_frame_set_ycbcr) and within ycbcr_scope
+	if (fr.im.grey || (fr.fh.do_ycbcr && !(ycbcr && ycbcr_scope(fr) == 0))) return ERR_TODO;
 	if (fr.im.bpp < 8 || fr.im.exp_bits) return ERR_TODO;
 
 	DevFrame &df = hp->frame;
@@ -210,6 +218,11 @@ uint32_t build_vardct_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, H
 	// (j40_next_frame's single-image path: 8 ms of one core per 8K frame otherwise, a quarter of the call) -- the same bytes either way.
 	const size_t nlf = fr.lf_groups.size();
 	const int32_t num_groups = (int32_t) fr.fh.num_groups;
+	const bool subsampled = fr.fh.do_ycbcr && fr.fh.subsampled();
+	if (subsampled) {
+		for (int c = 0; c < 3; ++c) df.ycc_shifts |= (uint32_t) (fr.fh.hshift[c] | fr.fh.vshift[c] << 1) << (2 * c);
+		df.kx_lf = df.kb_lf = 0.0f;   // (no chroma-from-luma, LF included)
+	}
 	size_t nvb = 0, ncell = 0, nc64 = 0;
 	hp->lf_groups.assign(nlf, DevLfGroup());
 	bool any_tail = false, all_tail = true;
@@ -325,6 +338,10 @@ uint32_t build_vardct_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, H
 					const int32_t bctx0 = (DCT_SELECT[dctsel].order_idx * nb_qf1 + (int32_t) (gb.coeffoff_qfidx & 15u)) * lfidx_size + gg.lfindices[cell];
 					uint32_t v = 0;
 					for (int32_t c_yxb = 0; c_yxb < 3; ++c_yxb) v |= (uint32_t) (fr.block_ctx_map[(size_t) (bctx0 + 13 * nb_qf1 * lfidx_size * c_yxb)] & 15) << (4 * c_yxb);
+					if (subsampled) for (int32_t c_yxb = 0; c_yxb < 3; ++c_yxb) {   // bits 12-14: the channel has no block here (hf_dev.h: SUB)
+						const int c = c_yxb == 0 ? 1 : c_yxb == 1 ? 0 : 2;
+						if (((d.gx8 + x8) & ((1 << fr.fh.hshift[c]) - 1)) || ((d.gy8 + y8) & ((1 << fr.fh.vshift[c]) - 1))) v |= 1u << (12 + c_yxb);
+					}
 					gb.bctx3 = (uint16_t) v;
 				}
 				ordinal[(size_t) d.ggidx][(size_t) (blk & 0xfffff)] = (int32_t) at;
@@ -353,8 +370,10 @@ uint32_t build_vardct_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, H
 				const size_t c64 = (size_t) (vb.y8 / 8) * (size_t) gg.width64 + (size_t) (vb.x8 / 8);
 				dv.kx_hf = fr.base_corr_x + fr.inv_colour_factor * (float) gg.xfromy[c64];   // j40.h:7138-7143, one factor per varblock
 				dv.kb_hf = fr.base_corr_b + fr.inv_colour_factor * (float) gg.bfromy[c64];
+				if (subsampled) dv.kx_hf = dv.kb_hf = 0.0f;   // chroma-from-luma is not applied to a subsampled frame: the maps are read and ignored
 				dv.px = gg.left + vb.x8 * 8; dv.py = gg.top + vb.y8 * 8;
 				dv.effh = (uint16_t) std::min(gg.height - vb.y8 * 8, 1 << ds.log_rows); dv.effw = (uint16_t) std::min(gg.width - vb.x8 * 8, 1 << ds.log_columns);
+				if (subsampled) dv.effw = dv.effh = 8;   // (the planes reach the padded grid, beyond gg.width: every block is stored whole)
 				dv.dctsel = (uint8_t) vb.dctsel;
 				dv.pad[0] = (uint8_t) g; dv.pad[1] = (uint8_t) (g >> 8); dv.pad[2] = (uint8_t) (g >> 16);
 				dv.blk = ordinal[g][v];   // the block's ordinal in group_blocks / block_events
@@ -377,6 +396,7 @@ uint32_t build_vardct_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, H
 	for (const DevCodeSpec &sp : hp->coeff_specs) any_lz77 |= sp.lz77_enabled != 0;
 	hp->lz_window_size = any_lz77 ? 3 * 65536 + 3 * 1024 + 16 : 0;  // bound on the integers one pass-group stream decodes
 	fill_hf_launch_info(hp->coeff_specs, (uint32_t) fr.block_ctx_map.size(), hp->coeff_floats, &hp->hf);
+	if (subsampled) { hp->hf.subsampled = true; hp->hf.lanes_fast = false; }   // (k_hf_entropy alone knows the presence rule)
 	hp->max_large = 0;
 	for (int d = 21; d < 27; ++d) hp->max_large = std::max(hp->max_large, hp->class_start[d + 1] - hp->class_start[d]);
 	if (timing) fprintf(stderr, "[j40hip plan] before the team %.2f ms, phase A %.2f, B %.2f, C + join %.2f, after %.2f\n", tb1 - tb0, tbA - tb1, tbB - tbA, tbC - tbB, now() - tbC);

@@ -56,7 +56,8 @@ bool build_lf_coop(const Frame &fr, DevCoopTree *tree, std::vector<uint64_t> *al
 
 // returns 0 or a 4-char error code ("TODO" for frame kinds the hot path does not cover)
 // threads: how many may work on the frame-wide arrays together (1: the calling thread alone; the arrays are the same either way)
-uint32_t build_vardct_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, HostPlan *out, int threads = 1);
+// ycbcr: the caller serves YCbCr frames (frame.hpp: ycbcr_scope); every other caller gets "TODO" for them as ever
+uint32_t build_vardct_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, HostPlan *out, int threads = 1, bool ycbcr = false);
 
 // single-pass frames keep HF coefficients in scan order on the device (DevFrame::scan_order_coeffs);
 // this rewrites LF group `gg`, channel c in place into the canonical layout the reference uses

@@ -335,9 +335,26 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	const int num_presets = opt.geti("presets", 1);
 	const int custom_orders = opt.geti("orders", 0);
 	const int num_passes = opt.geti("passes", 1);
-	const int nonzero_header = opt.geti("fullheader", (num_passes > 1) ? 1 : 0);
+	// ycbcr=1: a YCbCr frame as a recompressed JPEG is one -- implies noxyb=1 and the full frame header, sets do_ycbcr; unlike noxyb
+	// alone it does not need alpha=1, and a frame of one group is written as the single section it is. subsampling=444|420|422|440
+	// writes jpeg_upsampling (channel c's mode at bits 2c, coded order Cb, Y, Cr; modes 0..3 = sampling factors (1,1), (2,2), (2,1),
+	// (1,2)): the block grid padded to whole MCUs, every LF channel at its own size, DCT8 only, skip_adapt_lf_smooth, no filters, zero
+	// chroma-from-luma maps, per block only the channels present. flatchroma=1: Cb and Cr constant. dct8only=1, hfmul=N, nocfl=1: what
+	// a subsampled stream has anyway, for its 4:4:4 twins (every varblock DCT8; one HfMul; chroma-from-luma coded as all zero).
+	const int ycbcr = opt.geti("ycbcr", 0);
+	const std::string subsampling = opt.gets("subsampling", "444");
+	if (subsampling != "444" && subsampling != "420" && subsampling != "422" && subsampling != "440") die("vardct: subsampling=444|420|422|440");
+	const bool subsampled = subsampling != "444";
+	if (subsampled && !ycbcr) die("vardct: subsampling wants ycbcr=1");
+	// slot order X (Cb), Y, B (Cr)
+	const int sub_h = subsampling == "420" || subsampling == "422" ? 1 : 0, sub_v = subsampling == "420" || subsampling == "440" ? 1 : 0;
+	const int hs[3] = {sub_h, 0, sub_h}, vs[3] = {sub_v, 0, sub_v};
+	const int jpeg_upsampling = subsampling == "420" ? 4 : subsampling == "422" ? 8 : subsampling == "440" ? 12 : 0;
+	const int dct8only = opt.geti("dct8only", subsampled ? 1 : 0), fixed_hfmul = opt.geti("hfmul", 0), nocfl = opt.geti("nocfl", 0), flatchroma = opt.geti("flatchroma", 0);
+	if (fixed_hfmul < 0 || fixed_hfmul > 256) die("vardct: hfmul=1..256");
+	const int nonzero_header = opt.geti("fullheader", (num_passes > 1 || ycbcr) ? 1 : 0);
 	const int x_qm = opt.geti("xqm", 3), b_qm = opt.geti("bqm", 2);
-	const int skip_smooth = opt.geti("nosmooth", 0);
+	const int skip_smooth = opt.geti("nosmooth", subsampled ? 1 : 0);
 	const int small_clusters = opt.geti("simpleclusters", 0); // <= 8 clusters: simple cluster-map form
 	const int log_alpha = opt.geti("logalpha", 7);
 	const int container = opt.geti("container", 0);
@@ -368,7 +385,9 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 
 	const int gcols = (W + 255) / 256, grows = (H + 255) / 256, num_groups = gcols * grows;
 	const int ggcols = (W + 2047) / 2048, ggrows = (H + 2047) / 2048, num_lf_groups = ggcols * ggrows;
-	if (num_groups < 2 && num_passes == 1) die("vardct: need at least 2 groups (single-section VarDCT order quirk, SURVEY section 0 fact 8)");
+	const bool single_section = num_groups < 2 && num_passes == 1;
+	if (single_section && !(ycbcr || opt.geti("noxyb", 0))) die("vardct: need at least 2 groups (single-section VarDCT order quirk, SURVEY section 0 fact 8)");
+	if (single_section && opt.geti("alpha", 0)) die("vardct: a single-section frame carries its extra channels in LfGlobal, which is not generated: alpha=0");
 
 	Picture pic(W, H, seed);
 
@@ -400,11 +419,19 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	// ---- forward=1: the picture's XYB samples (planes padded to whole cells, edges replicated) ----
 	const int forward = opt.geti("forward", 0);
 	if (forward && (num_passes > 1 || max_log > 6 || opt.geti("cfl", 0))) die("vardct: forward=1 takes one pass, transforms up to 64x64, default chroma-from-luma");
-	const int PW = (W + 7) / 8 * 8, PH = (H + 7) / 8 * 8;
+	if (nocfl && opt.geti("cfl", 0)) die("vardct: nocfl=1 and cfl=1 exclude each other");
+	if (subsampled && (opt.geti("cfl", 0) || (opt.kv.count("dct8only") && !dct8only))) die("vardct: a subsampled stream has DCT8 blocks only and no chroma-from-luma");
+	// the block grid in samples: padded to whole MCUs where channels are subsampled; plane c is pwc[c] x phc[c]
+	const int PW = (W + (8 << sub_h) - 1) / (8 << sub_h) * (8 << sub_h), PH = (H + (8 << sub_v) - 1) / (8 << sub_v) * (8 << sub_v);
+	const int pwc[3] = {PW >> hs[0], PW >> hs[1], PW >> hs[2]}, phc[3] = {PH >> vs[0], PH >> vs[1], PH >> vs[2]};
 	std::vector<float> plane[3];
 	std::unique_ptr<synthfwd::Forward> fwdx;
-	if (forward) {
-		fwdx.reset(new synthfwd::Forward());
+	// forward=1: the procedural picture of WC x HC pixels into three planes of OW x OH samples (edges replicated). A subsampled
+	// stream evaluates it PER PLANE at the plane's own coordinates: sample (i, j) of plane c is pic(c, i, j) whatever the shift, so
+	// the chroma planes of a 4:2:0 stream of 2W x 2H are those of a 4:4:4 stream of W x H.
+	auto make_planes = [&](const int WC, const int HC, const int OW, const int OH, std::vector<float> out[3], const bool primary) {
+		const int LW = (WC + 7) / 8 * 8, LH = (HC + 7) / 8 * 8;   // what the lattices are sized from: the picture's own size
+		Picture fpic(WC, HC, seed);
 		// 1/f detail: octaves of lattice noise from 256-pixel cells down to 2-pixel cells, amplitude falling with the cell size,
 		// its strength modulated by a slowly varying mask (calm and busy regions, like sky and foliage)
 		const double detail = opt.getd("detail", 2.4), beta = opt.getd("beta", 0.35);
@@ -412,12 +439,12 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		std::vector<Lattice> lat;
 		SplitMix64 lr(seed ^ 0xD37A11ull);
 		for (int cell = 256; cell >= 2; cell /= 2) {
-			Lattice l; l.cell = cell; l.w = PW / cell + 2; l.h = PH / cell + 2; l.amp = (float) (0.2 * detail * pow((double) cell / 256.0, beta));
+			Lattice l; l.cell = cell; l.w = LW / cell + 2; l.h = LH / cell + 2; l.amp = (float) (0.2 * detail * pow((double) cell / 256.0, beta));
 			l.v.resize((size_t) l.w * (size_t) l.h);
 			for (auto &v : l.v) v = (float) lr.unit() - 0.5f;
 			lat.push_back(std::move(l));
 		}
-		Lattice mask; mask.cell = 512; mask.w = PW / 512 + 2; mask.h = PH / 512 + 2; mask.amp = 1.0f; mask.v.resize((size_t) mask.w * (size_t) mask.h);
+		Lattice mask; mask.cell = 512; mask.w = LW / 512 + 2; mask.h = LH / 512 + 2; mask.amp = 1.0f; mask.v.resize((size_t) mask.w * (size_t) mask.h);
 		for (auto &v : mask.v) { const double u = lr.unit(); v = (float) (0.12 + 1.5 * u * u); }
 		auto sample = [](const Lattice &l, int x, int y) {
 			const float u = (float) x / (float) l.cell, v = (float) y / (float) l.cell;
@@ -425,30 +452,30 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			const float *p = l.v.data() + (size_t) iv * (size_t) l.w + (size_t) iu;
 			return (p[0] * (1 - fu) + p[1] * fu) * (1 - fv) + (p[l.w] * (1 - fu) + p[l.w + 1] * fu) * fv;
 		};
-		for (int c = 0; c < 3; ++c) plane[c].resize((size_t) PW * (size_t) PH);
-		const std::string dumpsrc = opt.gets("dumpsrc", "");   // the source picture as sRGB u8 x 3, for the fidelity test
-		std::vector<uint8_t> srcdump(dumpsrc.empty() ? 0 : (size_t) W * (size_t) H * 3);
+		for (int c = 0; c < 3; ++c) out[c].resize((size_t) OW * (size_t) OH);
+		const std::string dumpsrc = primary ? opt.gets("dumpsrc", "") : std::string();   // the source picture as sRGB u8 x 3, for the fidelity test
+		std::vector<uint8_t> srcdump(dumpsrc.empty() ? 0 : (size_t) WC * (size_t) HC * 3);
 		static const float CHROMA[3] = {1.0f, 0.92f, 0.8f};
 		// the smooth part of the picture on a grid of 4-pixel cells (it has no feature below ~100 pixels), sRGB -> linear by table
-		const int GW = PW / 4 + 2, GH = PH / 4 + 2;
+		const int GW = LW / 4 + 2, GH = LH / 4 + 2;
 		std::vector<float> coarse((size_t) GW * (size_t) GH * 3);
-		for (int gy = 0; gy < GH; ++gy) for (int gx = 0; gx < GW; ++gx) pic.smooth((float) (gx * 4), (float) (gy * 4), &coarse[((size_t) gy * (size_t) GW + (size_t) gx) * 3]);
+		for (int gy = 0; gy < GH; ++gy) for (int gx = 0; gx < GW; ++gx) fpic.smooth((float) (gx * 4), (float) (gy * 4), &coarse[((size_t) gy * (size_t) GW + (size_t) gx) * 3]);
 		std::vector<float> to_linear(4097);
 		for (int i = 0; i <= 4096; ++i) { const double v = i / 4096.0; to_linear[(size_t) i] = (float) (v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4)); }
-		for (int y = 0; y < PH; ++y) for (int x = 0; x < PW; ++x) {
-			const int sx = std::min(x, W - 1), sy = std::min(y, H - 1);
+		for (int y = 0; y < OH; ++y) for (int x = 0; x < OW; ++x) {
+			const int sx = std::min(x, WC - 1), sy = std::min(y, HC - 1);
 			float rgb[3]; double xyb[3];
 			{
 				const int gx = sx >> 2, gy = sy >> 2; const float fu = (float) (sx & 3) * 0.25f, fv = (float) (sy & 3) * 0.25f;
 				const float *p = &coarse[((size_t) gy * (size_t) GW + (size_t) gx) * 3];
 				for (int c = 0; c < 3; ++c) rgb[c] = (p[c] * (1 - fu) + p[3 + c] * fu) * (1 - fv) + (p[(size_t) GW * 3 + c] * (1 - fu) + p[(size_t) GW * 3 + 3 + c] * fu) * fv;
-				pic.add_rects((float) sx, (float) sy, rgb);
+				fpic.add_rects((float) sx, (float) sy, rgb);
 			}
 			float n = 0;
 			for (const Lattice &l : lat) n += l.amp * sample(l, sx, sy);
 			n *= sample(mask, sx, sy);
 			for (int c = 0; c < 3; ++c) rgb[c] = std::min(0.97f, std::max(0.03f, rgb[c] + n * CHROMA[c]));
-			if (!dumpsrc.empty() && x < W && y < H) for (int c = 0; c < 3; ++c) srcdump[((size_t) y * (size_t) W + (size_t) x) * 3 + (size_t) c] = (uint8_t) lrintf(rgb[c] * 255.0f);
+			if (!dumpsrc.empty() && x < WC && y < HC) for (int c = 0; c < 3; ++c) srcdump[((size_t) y * (size_t) WC + (size_t) x) * 3 + (size_t) c] = (uint8_t) lrintf(rgb[c] * 255.0f);
 			{   // to_xyb with the table for the transfer function (quantise the sample to the table's grid first: what is
 				// dumped as the source is an 8-bit picture anyway)
 				double lin[3], mix[3];
@@ -456,9 +483,19 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 				for (int c = 0; c < 3; ++c) mix[c] = cbrt(fwd[c][0] * lin[0] + fwd[c][1] * lin[1] + fwd[c][2] * lin[2] - bias) + cbias;
 				xyb[0] = (mix[0] - mix[1]) * 0.5; xyb[1] = (mix[0] + mix[1]) * 0.5; xyb[2] = mix[2];
 			}
-			for (int c = 0; c < 3; ++c) plane[c][(size_t) y * (size_t) PW + (size_t) x] = (float) xyb[c];
+			for (int c = 0; c < 3; ++c) out[c][(size_t) y * (size_t) OW + (size_t) x] = (float) xyb[c];
 		}
 		if (!dumpsrc.empty()) { FILE *fp = fopen(dumpsrc.c_str(), "wb"); if (!fp || fwrite(srcdump.data(), 1, srcdump.size(), fp) != srcdump.size()) die("cannot write dumpsrc"); fclose(fp); }
+	};
+	if (forward) {
+		fwdx.reset(new synthfwd::Forward());
+		if (!subsampled) make_planes(W, H, PW, PH, plane, true);
+		else {
+			std::vector<float> tmp[3];
+			make_planes(W, H, PW, PH, tmp, true); plane[1].swap(tmp[1]);
+			make_planes((W + (1 << sub_h) - 1) >> sub_h, (H + (1 << sub_v) - 1) >> sub_v, pwc[0], phc[0], tmp, false); plane[0].swap(tmp[0]); plane[2].swap(tmp[2]);
+		}
+		if (flatchroma) { for (auto &v : plane[0]) v = 0.0625f; for (auto &v : plane[2]) v = -0.046875f; }
 	}
 	// activity of a cell: variance of its Y samples
 	std::vector<float> activity(forward ? (size_t) (PW / 8) * (size_t) (PH / 8) : 0);
@@ -470,7 +507,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	auto cell_activity = [&](int cx, int cy) { return (double) activity[(size_t) cy * (size_t) (PW / 8) + (size_t) cx]; };
 
 	const int custom_cfl = opt.geti("cfl", 0);
-	const double kx_lf = custom_cfl ? 0.125 + 3.0 / 128.0 : 0.0, kb_lf = custom_cfl ? 0.75 - 2.0 / 128.0 : 1.0;
+	// (nocfl=1 codes an all-zero correlation; a subsampled frame's decoder applies none whatever the header says)
+	const double kx_lf = custom_cfl ? 0.125 + 3.0 / 128.0 : 0.0, kb_lf = custom_cfl ? 0.75 - 2.0 / 128.0 : (nocfl || subsampled) ? 0.0 : 1.0;
 
 	// ---- block context configuration ----
 	int nb_lf_thr[3] = {0, 0, 0}, lf_thr[3][4] = {{0}}, nb_qf_thr = 0, qf_thr[4] = {0};
@@ -494,14 +532,29 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	// ---- per LF group: LF image, varblock layout, HF metadata ----
 	std::vector<LfGroupW> ggs((size_t) num_lf_groups);
 	std::vector<int> forced;  // transform types still to be placed once (coverage)
-	if (coverage) for (int t = 0; t < 27; ++t) if (std::max(DCTSEL[t][0], DCTSEL[t][1]) <= max_log) forced.push_back(t);
+	if (coverage && !dct8only) for (int t = 0; t < 27; ++t) if (std::max(DCTSEL[t][0], DCTSEL[t][1]) <= max_log) forced.push_back(t);
 	// weights of the random mix (8x8-class transforms dominate, like a d1 encode)
 	const int mixw[27] = {40, 3, 2, 3, 14, 6, 6, 6, 2, 2, 3, 3, 3, 3, 1, 1, 1, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1};
 	for (int ggy = 0, ggi = 0; ggy < ggrows; ++ggy) for (int ggx = 0; ggx < ggcols; ++ggx, ++ggi) {
 		LfGroupW &gg = ggs[(size_t) ggi];
 		gg.left = ggx * 2048; gg.top = ggy * 2048; gg.w = std::min(2048, W - gg.left); gg.h = std::min(2048, H - gg.top);
 		gg.w8 = (gg.w + 7) / 8; gg.h8 = (gg.h + 7) / 8; gg.w64 = (gg.w + 63) / 64; gg.h64 = (gg.h + 63) / 64;
-		for (int c = 0; c < 3; ++c) gg.lfq[c] = Channel(gg.w8, gg.h8);
+		if (subsampled) { gg.w8 = std::min(256, PW / 8 - gg.left / 8); gg.h8 = std::min(256, PH / 8 - gg.top / 8); gg.w64 = (gg.w8 + 7) / 8; gg.h64 = (gg.h8 + 7) / 8; }
+		static const int SLOT_OF_STREAM[3] = {1, 0, 2};
+		for (int c = 0; c < 3; ++c) gg.lfq[c] = Channel(gg.w8 >> hs[SLOT_OF_STREAM[c]], gg.h8 >> vs[SLOT_OF_STREAM[c]]);
+		if (subsampled) {
+			// every channel's LF image at its own size: the cell's mean (forward=1) or the picture at the cell's centre, in the plane's own coordinates
+			for (int k = 0; k < 3; ++k) {
+				const int c = SLOT_OF_STREAM[k], cw = gg.w8 >> hs[c], chh = gg.h8 >> vs[c], left = gg.left >> hs[c], top = gg.top >> vs[c];
+				for (int y = 0; y < chh; ++y) for (int x = 0; x < cw; ++x) {
+					double v;
+					if (forward) { double m = 0; for (int j = 0; j < 8; ++j) for (int i = 0; i < 8; ++i) m += plane[c][(size_t) (top + y * 8 + j) * (size_t) pwc[c] + (size_t) (left + x * 8 + i)]; v = m / 64; }
+					else { float rgb[3]; double xyb[3]; pic.rgb((float) (left + x * 8) + 3.5f, (float) (top + y * 8) + 3.5f, rgb); to_xyb(rgb, xyb); v = flatchroma && c != 1 ? (c == 0 ? 0.0625 : -0.046875) : xyb[c]; }
+					gg.lfq[k].at(x, y) = (int32_t) lrint(v / lfstep[c]);
+					if (abs(gg.lfq[k].at(x, y)) > 32767) die("vardct: an LF integer leaves the LfGroup's 16-bit channels");
+				}
+			}
+		} else
 		for (int y = 0; y < gg.h8; ++y) for (int x = 0; x < gg.w8; ++x) {
 			float rgb[3]; double xyb[3];
 			if (forward) {   // the cell's mean
@@ -509,6 +562,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			} else {
 				pic.rgb((float) (gg.left + x * 8) + 3.5f, (float) (gg.top + y * 8) + 3.5f, rgb);
 				to_xyb(rgb, xyb);
+				if (flatchroma) { xyb[0] = 0.0625; xyb[2] = -0.046875; }
 			}
 			gg.lfq[0].at(x, y) = (int32_t) lrint(xyb[1] / lfstep[1]);  // streamed order: Y, X, B
 			gg.lfq[1].at(x, y) = (int32_t) lrint(xyb[0] / lfstep[0]);
@@ -523,7 +577,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		gg.lfidx.assign((size_t) gg.w8 * (size_t) gg.h8, 0);
 		for (int y = 0; y < gg.h8; ++y) for (int x = 0; x < gg.w8; ++x) {  // j40.h:6566-6570
 			auto cnt = [&](int v, const int *thr, int n) { int k = 0; for (int t = 0; t < n; ++t) k += v > thr[t]; return k; };
-			int xi = cnt(gg.lfq[1].at(x, y), lf_thr[0], nb_lf_thr[0]), yi = cnt(gg.lfq[0].at(x, y), lf_thr[1], nb_lf_thr[1]), bi = cnt(gg.lfq[2].at(x, y), lf_thr[2], nb_lf_thr[2]);
+			// (a subsampled channel: the cell looks at the channel's sample that covers it)
+			int xi = cnt(gg.lfq[1].at(x >> hs[0], y >> vs[0]), lf_thr[0], nb_lf_thr[0]), yi = cnt(gg.lfq[0].at(x, y), lf_thr[1], nb_lf_thr[1]), bi = cnt(gg.lfq[2].at(x >> hs[2], y >> vs[2]), lf_thr[2], nb_lf_thr[2]);
 			gg.lfidx[(size_t) y * (size_t) gg.w8 + (size_t) x] = (uint8_t) ((xi * (nb_lf_thr[0] + 1) + bi) * (nb_lf_thr[2] + 1) + yi);
 		}
 		gg.blocks.assign((size_t) gg.w8 * (size_t) gg.h8, 0);
@@ -544,6 +599,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 				for (int k = 0; k < 27; ++k) if (std::max(DCTSEL[k][0], DCTSEL[k][1]) <= max_log) { if (pick < mixw[k]) { t = k; break; } pick -= mixw[k]; }
 				if (!fits(t)) t = 0;
 			}
+			if (dct8only) t = 0;
+			if (opt.geti("subdct16", 0) && x0 == 0 && y0 == 0 && ggi == 0 && fits(4)) t = 4;   // (a stream the decoder has to refuse: a DCT16 block in a subsampled frame)
 			int hfmul_m1 = 3 + (int) rng.below(10);
 			if (forward) {
 				// what an encoder's heuristics amount to: large transforms only over calm content, the 8x8 specials only where there
@@ -553,19 +610,20 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 				if (DCTSEL[t][0] == 3 && DCTSEL[t][1] == 3) {
 					const double a = worst(t);
 					if (a < 2e-5) t = 0;
-					else if (t == 0 && a > 4e-4 && rng.below(3) == 0) { static const int SP[9] = {1, 2, 3, 12, 13, 14, 15, 16, 17}; t = SP[rng.below(9)]; }
+					else if (!dct8only && t == 0 && a > 4e-4 && rng.below(3) == 0) { static const int SP[9] = {1, 2, 3, 12, 13, 14, 15, 16, 17}; t = SP[rng.below(9)]; }
 				}
 				const double a = worst(t);
 				hfmul_m1 = (a < 1e-5 ? 8 : a < 1e-4 ? 7 : a < 1e-3 ? 6 : 5) - 1;
 			}
+			if (fixed_hfmul) hfmul_m1 = fixed_hfmul - 1;
 			int vw8 = 1 << (DCTSEL[t][1] - 3), vh8 = 1 << (DCTSEL[t][0] - 3), voff = (int) gg.vbs.size();
 			for (int y = y0; y < y0 + vh8; ++y) for (int x = x0; x < x0 + vw8; ++x) gg.blocks[(size_t) y * (size_t) gg.w8 + (size_t) x] = 1 << 20 | voff;
 			gg.blocks[(size_t) y0 * (size_t) gg.w8 + (size_t) x0] = (t + 2) << 20 | voff;
 			gg.vbs.push_back({x0, y0, t, hfmul_m1});
 		}
 		gg.xfromy = Channel(gg.w64, gg.h64); gg.bfromy = Channel(gg.w64, gg.h64);
-		for (auto &v : gg.xfromy.px) v = forward ? 0 : (int32_t) rng.below(9) - 4;
-		for (auto &v : gg.bfromy.px) v = forward ? 0 : (int32_t) rng.below(13) - 6;
+		for (auto &v : gg.xfromy.px) v = forward || subsampled || nocfl ? 0 : (int32_t) rng.below(9) - 4;
+		for (auto &v : gg.bfromy.px) v = forward || subsampled || nocfl ? 0 : (int32_t) rng.below(13) - 6;
 		gg.blockinfo = Channel((int) gg.vbs.size(), 2);
 		for (size_t i = 0; i < gg.vbs.size(); ++i) { gg.blockinfo.at((int) i, 0) = gg.vbs[i].dctsel; gg.blockinfo.at((int) i, 1) = gg.vbs[i].hfmul_m1; }
 		gg.sharp = Channel(gg.w8, gg.h8);
@@ -848,7 +906,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			const LfGroupW &gg = ggs[(size_t) ggi];
 			const int gx8 = (gcol % 8) * 32, gy8 = (grow % 8) * 32;
 			const int gw = std::min(W, (gcol + 1) * 256) - gcol * 256, gh = std::min(H, (grow + 1) * 256) - grow * 256;
-			const int gw8 = (gw + 7) / 8, gh8 = (gh + 7) / 8;
+			// (a subsampled frame: the group's cells come from the padded grid)
+			const int gw8 = subsampled ? std::min(32, gg.w8 - gx8) : (gw + 7) / 8, gh8 = subsampled ? std::min(32, gg.h8 - gy8) : (gh + 7) / 8;
 			const int ctxoff = ctx_per_preset * group_preset[(size_t) g];
 			std::vector<std::array<int8_t, 3>> nonzeros((size_t) gw8 * (size_t) gh8, std::array<int8_t, 3>{0, 0, 0});
 			for (int y8 = 0; y8 < gh8; ++y8) for (int x8 = 0; x8 < gw8; ++x8) {
@@ -861,9 +920,12 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 				int qfidx = 0; for (int j = 0; j < nb_qf_thr; ++j) qfidx += vb.hfmul_m1 >= qf_thr[j];
 				int lfidx = gg.lfidx[(size_t) (gy8 + y8) * (size_t) gg.w8 + (size_t) (gx8 + x8)];
 				int bctx0 = (order_idx * (nb_qf_thr + 1) + qfidx) * lfidx_size + lfidx, bctxc = 13 * (nb_qf_thr + 1) * lfidx_size;
-				const int nzpos = y8 * gw8 + x8;
 				for (int cyxb = 0; cyxb < 3; ++cyxb) {
 					const int c = cyxb == 0 ? 1 : cyxb == 1 ? 0 : 2;
+					// a subsampled channel has a block only where the block's column and row are multiples of its 1 << shift; its non-zero
+					// counts are predicted in its own coordinates (a map of its own: the channel's entries at (x8 >> hs, y8 >> vs))
+					if (((gx8 + x8) & ((1 << hs[c]) - 1)) || ((gy8 + y8) & ((1 << vs[c]) - 1))) continue;
+					const int cx8 = x8 >> hs[c], cy8 = y8 >> vs[c], cpos = cy8 * gw8 + cx8;
 					const int bctx = bctx_map[(size_t) (bctx0 + bctxc * cyxb)];
 					// choose the non-zero positions: Bernoulli with frequency decay; X/B sparser than Y
 					const int size = 1 << log_size, first = size >> 6;
@@ -875,9 +937,9 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 						// X and B code what is left after the decoder's chroma-from-luma term (default factors: 0 and 1 times the
 						// dequantised Y coefficient, j40.h:7138-7143, 7159-7171)
 						const int R = 1 << log_rows, C = 1 << log_cols;
-						const int px0 = gg.left + (gx8 + x8) * 8, py0 = gg.top + (gy8 + y8) * 8;
+						const int px0 = ((gg.left >> 3) + gx8 + x8) >> hs[c] << 3, py0 = ((gg.top >> 3) + gy8 + y8) >> vs[c] << 3;   // (in the plane's own coordinates)
 						fpix.resize((size_t) size); fcoef.resize((size_t) size);
-						for (int y = 0; y < R; ++y) for (int x = 0; x < C; ++x) fpix[(size_t) (y * C + x)] = plane[c][(size_t) (py0 + y) * (size_t) PW + (size_t) (px0 + x)];
+						for (int y = 0; y < R; ++y) for (int x = 0; x < C; ++x) fpix[(size_t) (y * C + x)] = plane[c][(size_t) (py0 + y) * (size_t) pwc[c] + (size_t) (px0 + x)];
 						fwdx->analyse(dctsel, fpix.data(), fcoef.data());
 						const float mult1 = 65536.0f / (float) global_scale / (float) (vb.hfmul_m1 + 1);
 						const float mult_c = c == 1 ? mult1 : c == 0 ? mult1 * powf(0.8f, (float) (x_qm - 2)) : mult1 * powf(0.8f, (float) (b_qm - 2));
@@ -888,7 +950,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 						for (int i = first; i < size; ++i) {
 							const int pos = ord[(size_t) i];
 							float target = fcoef[(size_t) pos];
-							if (c == 2) target -= fydeq[(size_t) pos];
+							if (c == 2 && !nocfl && !subsampled) target -= fydeq[(size_t) pos];
 							const float scaled = target * wt[(size_t) pos] / mult_c;
 							const int q = fabsf(scaled) < dead ? 0 : (int) lrintf(scaled);
 							if (c == 1 && q) fydeq[(size_t) pos] = synthfwd::dequant((float) q, 1, mult_c, wt[(size_t) pos]);
@@ -916,13 +978,13 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 					int nz = (int) coefs.size();
 					if (nz > (63 << (log_size - 6))) { coefs.resize((size_t) (63 << (log_size - 6))); nz = (int) coefs.size(); }
 					int pred;
-					if (x8 > 0) pred = y8 > 0 ? (nonzeros[(size_t) nzpos - 1][(size_t) c] + nonzeros[(size_t) (nzpos - gw8)][(size_t) c] + 1) >> 1 : nonzeros[(size_t) nzpos - 1][(size_t) c];
-					else pred = y8 > 0 ? nonzeros[(size_t) (nzpos - gw8)][(size_t) c] : 32;
+					if (cx8 > 0) pred = cy8 > 0 ? (nonzeros[(size_t) cpos - 1][(size_t) c] + nonzeros[(size_t) (cpos - gw8)][(size_t) c] + 1) >> 1 : nonzeros[(size_t) cpos - 1][(size_t) c];
+					else pred = cy8 > 0 ? nonzeros[(size_t) (cpos - gw8)][(size_t) c] : 32;
 					int nzctx = ctxoff + bctx + (pred < 8 ? pred : 4 + pred / 2) * nb_block_ctx;
 					enc.add((uint32_t) nzctx, (uint32_t) nz);
 					int qnz = (nz + (1 << (log_size - 6)) - 1) >> (log_size - 6);
 					for (int i = 0; i < (1 << (log_rows - 3)); ++i) for (int j = 0; j < (1 << (log_cols - 3)); ++j)
-						if (y8 + i < gh8 && x8 + j < gw8) nonzeros[(size_t) (nzpos + i * gw8 + j)][(size_t) c] = (int8_t) qnz;
+						if (cy8 + i < gh8 && cx8 + j < gw8) nonzeros[(size_t) (cpos + i * gw8 + j)][(size_t) c] = (int8_t) qnz;
 					const int cctx = ctxoff + 458 * bctx + 37 * nb_block_ctx;
 					int prev = nz <= (1 << (log_size - 4)), remaining = nz;
 					size_t next = 0;
@@ -987,8 +1049,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 
 	// ---- assemble sections ----
 	std::vector<std::vector<uint8_t>> sections;
-	{   // LfGlobal (j40.h:6257)
-		BitWriter bw;
+	auto write_lf_global = [&](BitWriter &bw) {   // LfGlobal (j40.h:6257)
 		bw.put(1, 1);                                            // LF channel dequantisation: default
 		bw.u32(global_scale, 1, 11, 2049, 11, 4097, 12, 8193, 16);
 		bw.u32(quant_lf, 16, 0, 1, 5, 1, 8, 1, 16);
@@ -1003,7 +1064,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			for (int j = 0; j < nb_qf_thr; ++j) bw.u32(qf_thr[j] - 1, 0, 2, 4, 3, 12, 5, 44, 8);
 			write_cluster_map(bw, bctx_map, nb_block_ctx);
 		}
-		if (!custom_cfl) bw.put(1, 1);                   // LF channel correlation: default
+		if (nocfl) { bw.put(0, 1); bw.u32(84, 84, 0, 256, 0, 2, 8, 258, 16); bw.f16(0.0f); bw.f16(0.0f); bw.put(127, 8); bw.put(127, 8); }   // all zero
+		else if (!custom_cfl) bw.put(1, 1);                   // LF channel correlation: default
 		else { bw.put(0, 1); bw.u32(128, 84, 0, 256, 0, 2, 8, 258, 16); bw.f16(0.125f); bw.f16(0.75f); bw.put(127 + 3, 8); bw.put(127 - 2, 8); }
 		bw.put(1, 1);                                            // global tree present
 		write_code_spec(bw, treespec); tree_enc.flush(bw);
@@ -1012,23 +1074,17 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			write_modular_header(bw, true, custom_wp && wpat != "group" ? &wp_base : nullptr, {});
 			StreamEncoder none(gspec); none.flush(bw);
 		}
-		bw.pad();
-		sections.push_back(bw.bytes);
-	}
-	for (int ggi = 0; ggi < num_lf_groups; ++ggi) {  // LfGroup (j40.h:6722)
+	};
+	auto write_lf_group = [&](BitWriter &bw, int ggi) {  // LfGroup (j40.h:6722)
 		LfGroupW &gg = ggs[(size_t) ggi];
-		BitWriter bw;
 		bw.put((uint64_t) extra_prec, 2);                        // extra_precision
 		write_modular_header(bw, true, wp_of(2 * ggi), {});
 		lfq_enc[(size_t) ggi].flush(bw);
 		bw.put((uint64_t) (gg.vbs.size() - 1), ceil_lg((uint32_t) (gg.w8 * gg.h8)));
 		write_modular_header(bw, true, wp_of(2 * ggi + 1), {});
 		meta_enc[(size_t) ggi].flush(bw);
-		bw.pad();
-		sections.push_back(bw.bytes);
-	}
-	{   // HfGlobal + HfPass (j40.h:6819)
-		BitWriter bw;
+	};
+	auto write_hf_global = [&](BitWriter &bw) {   // HfGlobal + HfPass (j40.h:6819)
 		if (opt.geti("dq", 0)) { bw.put(0, 1); write_dq_matrices(bw, dq_raw, wp_of); }
 		else bw.put(1, 1);                                       // all dequantisation matrices default
 		bw.put((uint64_t) (num_presets - 1), ceil_lg((uint32_t) num_groups));
@@ -1050,16 +1106,24 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			}
 			write_code_spec(bw, cspec[(size_t) pass]);
 		}
-		bw.pad();
-		sections.push_back(bw.bytes);
-	}
-	for (int pass = 0; pass < num_passes; ++pass) for (int g = 0; g < num_groups; ++g) {  // PassGroup (j40.h:7007)
-		BitWriter bw;
+	};
+	auto write_pass_group = [&](BitWriter &bw, int pass, int g) {  // PassGroup (j40.h:7007)
 		bw.put((uint64_t) group_preset[(size_t) g], ceil_lg((uint32_t) num_presets));
 		hf_enc[(size_t) pass][(size_t) g].flush(bw);
 		if (with_alpha) { write_modular_header(bw, true, wp_of(200 + g), {}); alpha_enc[(size_t) g].flush(bw); }
+	};
+	if (single_section) {
+		// one group, one pass: a single section, read in the order LfGlobal, HfGlobal, LfGroup, PassGroup (j40.h:8189-8199) with no
+		// padding between them
+		BitWriter bw;
+		write_lf_global(bw); write_hf_global(bw); write_lf_group(bw, 0); write_pass_group(bw, 0, 0);
 		bw.pad();
 		sections.push_back(bw.bytes);
+	} else {
+		{ BitWriter bw; write_lf_global(bw); bw.pad(); sections.push_back(bw.bytes); }
+		for (int ggi = 0; ggi < num_lf_groups; ++ggi) { BitWriter bw; write_lf_group(bw, ggi); bw.pad(); sections.push_back(bw.bytes); }
+		{ BitWriter bw; write_hf_global(bw); bw.pad(); sections.push_back(bw.bytes); }
+		for (int pass = 0; pass < num_passes; ++pass) for (int g = 0; g < num_groups; ++g) { BitWriter bw; write_pass_group(bw, pass, g); bw.pad(); sections.push_back(bw.bytes); }
 	}
 
 	// ---- codestream ----
@@ -1069,8 +1133,9 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	const int icc_bytes = opt.geti("icc", 0);                // > 0: ColourEncoding with want_icc and an ICC stream of that many coded bytes
 	const int img_bpp = opt.geti("bpp", 8);   // 9..15: the renderer's scaling to 8 bits and the long way through the transfer curve get work
 	if (img_bpp != 8 && icc_bytes) die("vardct: bpp does not combine with icc here");
-	const int noxyb = opt.geti("noxyb", 0);
-	if (noxyb && (!with_alpha || icc_bytes || !nonzero_header || x_qm != 3 || b_qm != 2)) die("vardct: noxyb wants alpha=1 fullheader=1 and the default qm scales");
+	const int noxyb = opt.geti("noxyb", 0) || ycbcr;
+	if (noxyb && (icc_bytes || !nonzero_header || x_qm != 3 || b_qm != 2)) die("vardct: noxyb wants fullheader=1, no icc and the default qm scales");
+	if (noxyb && g_seq && !with_alpha) die("vardct: noxyb in frames= wants alpha=1");
 	if (!g_seq || g_seq->first) {
 	cs.put(0xff, 8); cs.put(0x0a, 8);
 	write_size_header(cs, g_seq ? g_seq->canvas_w : W, g_seq ? g_seq->canvas_h : H);
@@ -1101,13 +1166,23 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		write_tone_mapping(cs);
 		cs.put(0, 2);                       // extensions
 		cs.put(1, 1);                       // default_m
-	} else if (img_bpp != 8 || (seq_anim && !with_alpha)) {
+	} else if (img_bpp != 8 || (seq_anim && !with_alpha) || (noxyb && !with_alpha)) {
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		write_bit_depth(cs, img_bpp);
 		cs.put(1, 1);                       // modular_16bit_buffers
 		cs.put(0, 2);                       // no extra channels
-		cs.put(1, 1);                       // xyb_encoded
+		cs.put(noxyb ? 0 : 1, 1);           // xyb_encoded
+		if (noxyb && opt.geti("grey", 0)) {
+			// grey=1 (with noxyb / ycbcr, no alpha): the colour encoding says grey, D65, sRGB transfer, relative intent -- a stream the
+			// decoder refuses (the frame still codes three channels)
+			cs.put(0, 1); cs.put(0, 1);     // ColourEncoding: not all_default, no ICC profile
+			cs.put(1, 2);                   // colour_space = grey (enum value 1)
+			cs.put(1, 2);                   // white_point = D65
+			cs.put(0, 1);                   // no gamma
+			cs.put(2, 2); cs.put(11, 4);    // transfer function 13 (sRGB): enum selector 2, 2 + 11
+			cs.put(1, 2);                   // rendering intent 1
+		} else
 		cs.put(1, 1);                       // ColourEncoding.all_default
 		write_tone_mapping(cs);
 		cs.put(0, 2);                       // extensions
@@ -1149,7 +1224,9 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(0, 2);                       // regular frame
 		cs.put(0, 1);                       // VarDCT
 		cs.u64(skip_smooth ? 128 : 0);      // flags
-		if (noxyb) cs.put(0, 1);            // do_ycbcr (read only without xyb_encoded)
+		if (noxyb) cs.put(ycbcr ? 1 : 0, 1);   // do_ycbcr (read only without xyb_encoded)
+		// (jpegup=N: the header says N whatever the stream holds -- a layout the decoder has to refuse before it reads anything of it)
+		if (ycbcr) cs.put((uint64_t) opt.geti("jpegup", jpeg_upsampling), 6);   // jpeg_upsampling (read with do_ycbcr)
 		cs.put(0, 2);                       // log_upsampling
 		for (int i = 0; i < num_ec; ++i) cs.put(0, 2);   // ec_log_upsampling
 		if (!noxyb) { cs.put((uint64_t) x_qm, 3); cs.put((uint64_t) b_qm, 3); }
