@@ -3,7 +3,8 @@
 // where a channel is shifted, the colour conversion, the pack. Compiled for the device by ycbcr_kernels.hip and for the CPU by
 // tests/hostsim/ycbcr_sim.cpp: the same functions.
 //
-// PARITY UNPINNED ("YCbCr frames"): the reference refuses such frames (j40.h:7867), so none of this arithmetic is its own.
+// The reference refuses such frames (j40.h:7867), so none of this arithmetic is its own; it is pinned to JPEG's definition on the
+// integers of real JPEG files (tests/test_jpeg_transcode.py; DESIGN.md, "YCbCr frames", also for what stays PARITY UNPINNED).
 //   upsampling  by 2 per shifted axis, horizontal first, then vertical on the horizontally upsampled values:
 //               out[2i] = 0.75 in[i] + 0.25 in[i-1], out[2i+1] = 0.75 in[i] + 0.25 in[i+1]; in[-1] = in[0] and in[n] = in[n-1] at the
 //               PLANE's border only (the plane reaches the padded block grid, beyond the picture)

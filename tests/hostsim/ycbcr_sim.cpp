@@ -100,12 +100,13 @@ YCBCR_SIM_API void ycbcr_sim_info(const uint8_t *buf, size_t size, int32_t allow
 // The whole decode with the switch on: planes[c] (tightly packed, the size ycbcr_sim_info reports) as the tail reads them, and the
 // pixels (width x height, `stride` bytes a row; out16: u16x4). Returns the frame's code. A frame that is not YCbCr (a twin coded
 // without do_ycbcr) leaves the same planes and no pixels: what the pixel kernels' OutMode::XYB stores.
-YCBCR_SIM_API uint32_t ycbcr_sim_decode(const uint8_t *buf, size_t size, float *plane0, float *plane1, float *plane2, uint8_t *rgba, size_t stride, int32_t out16) {
-	Parsed p;
-	if (uint32_t e = parse(buf, size, true, &p)) return e;
+// (`dense`: the plan without coefficient events, the form the runtime uploads again after "evof" -- a section whose events do not fit
+// their region or a coefficient beyond int16, as every coefficient of a jpegdata= stream is)
+static uint32_t decode_with(const Parsed &p, bool dense, float *plane0, float *plane1, float *plane2, uint8_t *rgba, size_t stride, int32_t out16) {
 	const Frame &fr = p.fr;
 	if (fr.fh.is_modular) return ERR_TODO;
 	HostPlan hp;
+	hp.force_dense = dense;
 	if (uint32_t e = build_vardct_plan(fr, p.cs, p.cs_size, &hp, 1, true)) return e;
 	std::vector<float> coeff_store(3 * hp.coeff_floats, 0.0f);
 	std::vector<int8_t> nonzeros((size_t) hp.frame.num_groups * 32 * 32 * 3);
@@ -193,4 +194,11 @@ YCBCR_SIM_API uint32_t ycbcr_sim_decode(const uint8_t *buf, size_t size, float *
 	int32_t dims[9], shifts[6];
 	for (int c = 0; c < 3; ++c) { dims[3 * c] = pw[c]; dims[3 * c + 1] = pw[c]; dims[3 * c + 2] = ph[c]; shifts[2 * c] = fr.fh.hshift[c]; shifts[2 * c + 1] = fr.fh.vshift[c]; }
 	return ycbcr_sim_tail(plane0, plane1, plane2, dims, shifts, fr.fh.width, fr.fh.height, fr.im.bpp, out16, rgba, stride) ? (uint32_t) ERR_RNGE : 0;
+}
+
+YCBCR_SIM_API uint32_t ycbcr_sim_decode(const uint8_t *buf, size_t size, float *plane0, float *plane1, float *plane2, uint8_t *rgba, size_t stride, int32_t out16) {
+	Parsed p;
+	if (uint32_t e = parse(buf, size, true, &p)) return e;
+	const uint32_t e = decode_with(p, false, plane0, plane1, plane2, rgba, stride, out16);
+	return e == (uint32_t) ERR_EVOF ? decode_with(p, true, plane0, plane1, plane2, rgba, stride, out16) : e;
 }

@@ -375,11 +375,23 @@ VARDCT_REFUSALS = [
     (dict(lftree=4, wpat="both"), "wpat places the parameters wp= gives"),
     (dict(lftree=4, wp="max", wpat="both"), "want alpha=1"),
     (dict(lftree=4, wp="1,2"), "wp=random|max|zero|"),
+    # jpegdata= (a JPEG file's integers, tests/test_jpeg_transcode.py) fixes everything else about the frame; the combinations are refused
+    # before the dump is opened, a dump of another size than the command line's once it is
+    (dict(jpegdata="missing.jpgd", forward=1), "forward=1 takes them from the picture"),
+    (dict(jpegdata="missing.jpgd", passes=2), "jpegdata= writes one pass"),
+    (dict(jpegdata="missing.jpgd", cfl=1), "jpegdata= and cfl=1 exclude each other"),
+    (dict(jpegdata="missing.jpgd", maxlog=4), "jpegdata= fixes what maxlog= would say"),
+    (dict(jpegdata="missing.jpgd", subsampling="420"), "jpegdata= fixes what subsampling= would say"),
+    (dict(jpegdata="missing.jpgd"), "cannot be read"),
+    (dict(jpegdata="8x8"), "holds a picture of 8 x 8, the command line says 520 x 264"),
 ]
 
 
 @pytest.mark.parametrize("opts,words", VARDCT_REFUSALS, ids=["_".join("%s-%s" % kv for kv in sorted(o.items())).replace(",", ".") for o, _ in VARDCT_REFUSALS])
 def test_generator_says_why_it_refuses_vardct_options(built, tmp_path, opts, words):
+    if opts.get("jpegdata") == "8x8":   # a real dump: the 8 x 8 fixture's
+        import jpeg_ref
+        opts = dict(opts, jpegdata=jpeg_ref.dump_path(jpeg_ref.parse(jpeg_ref.fixture("q90_444_8x8")[0]), "q90_444_8x8"))
     r = subprocess.run([SYNTH, "vardct", "520", "264", "7", str(tmp_path / "x.jxl")] + ["%s=%s" % kv for kv in sorted(opts.items())], capture_output=True, text=True)
     assert r.returncode == 2 and words in r.stderr, r.stderr
     assert not (tmp_path / "x.jxl").exists()

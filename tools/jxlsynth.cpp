@@ -325,9 +325,68 @@ struct LfGroupW {
 	std::vector<uint8_t> lfidx;
 };
 
+// jpegdata=PATH (vardct): the quantised integers of a baseline JPEG file, as tests/jpeg_ref.py's write_dump lays them out. Little-endian:
+// int32 magic "JPGD", width, height; per component Y, Cb, Cr: int32 h factor, v factor, blocks_x, blocks_y (the whole-MCU block grid);
+// per component 64 x uint16 quantisation table [v][u] (v: vertical frequency); per component blocks_y x blocks_x x 64 x int16
+// coefficients [by][bx][v][u], DC differences undone.
+struct JpegDump {
+	bool present = false;
+	std::string subsampling;
+	struct Comp { int h, v, bx, by; uint16_t table[64]; std::vector<int16_t> coef; } comp[3];
+	// slot c (0 = Cb, 1 = Y, 2 = Cr: the frame's channels X, Y, B) -> component
+	const Comp &slot(int c) const { return comp[c == 1 ? 0 : c == 0 ? 1 : 2]; }
+};
+// What the stream has to be for the decoder's own rule to give q * Q / (8 * 255) for the JPEG integer q under table entry Q (the
+// derivation: DESIGN.md, "YCbCr frames"). The decoder computes adj(n) * mult_c / (px / denom) with mult_1 = 65536 / (global_scale *
+// HfMul), mult_0 = 0.8 mult_1 (x_qm_scale keeps its default 3 in a frame that is not XYB), adj(n) = n - 0.145 / n: the weight DIVIDES, its
+// integer px cannot be proportional to 1 / Q for every Q, and the bias cannot be switched off. So Q is split, Q = g * f with
+// g = gcd(Q, 32640): px = 32640 / g goes into the raw matrix, f into the integer, n = K_c * q * f with K = 2560, 2048, 2048 -- large
+// enough that 0.145 / n^2 < 2^-24.
+static const int JPEG_L = 32640, JPEG_GLOBAL_SCALE = 2048, JPEG_QUANT_LF = 255, JPEG_K[3] = {2560, 2048, 2048}, JPEG_LF_K[3] = {16, 2, 1};
+static const float JPEG_DENOM = 1.0f / 4096.0f;
+static int jpeg_gcd(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
+
+static JpegDump load_jpeg_dump(const Options &opt, int W, int H) {
+	JpegDump jd;
+	if (!opt.kv.count("jpegdata")) return jd;
+	const char *why = "it implies ycbcr=1, the file's subsampling, DCT8 blocks, one HfMul, one pass, zero chroma-from-luma, skip_adapt_lf_smooth, no filters, 8 bits and its own global_scale and quant_lf";
+	if (opt.geti("forward", 0)) dief("vardct: jpegdata= carries a JPEG's integers, forward=1 takes them from the picture (%s)", why);
+	if (opt.geti("passes", 1) > 1) dief("vardct: jpegdata= writes one pass (%s)", why);
+	if (opt.geti("cfl", 0)) dief("vardct: jpegdata= and cfl=1 exclude each other (%s)", why);
+	for (const char *k : {"maxlog", "ycbcr", "subsampling", "global_scale", "quant_lf", "hfmul", "dct8only", "nocfl", "nosmooth", "dq", "gab", "epf", "bpp", "extraprec", "bigshare", "flat", "noxyb", "grey", "flatchroma", "jpegup"})
+		if (opt.kv.count(k)) dief("vardct: jpegdata= fixes what %s= would say (%s)", k, why);
+	const std::string path = opt.gets("jpegdata", "");
+	FILE *fp = fopen(path.c_str(), "rb");
+	if (!fp) dief("vardct: jpegdata=%s cannot be read", path.c_str());
+	int32_t head[3 + 12];
+	if (fread(head, 4, 15, fp) != 15 || head[0] != 0x4447504A) die("vardct: jpegdata= is not a dump of tests/jpeg_ref.py (magic JPGD)");
+	if (head[1] != W || head[2] != H) dief("vardct: the dump of jpegdata= holds a picture of %d x %d, the command line says %d x %d", head[1], head[2], W, H);
+	for (int i = 0; i < 3; ++i) { JpegDump::Comp &c = jd.comp[i]; c.h = head[3 + 4 * i]; c.v = head[4 + 4 * i]; c.bx = head[5 + 4 * i]; c.by = head[6 + 4 * i]; }
+	const int yh = jd.comp[0].h, yv = jd.comp[0].v;
+	if (jd.comp[1].h != 1 || jd.comp[1].v != 1 || jd.comp[2].h != 1 || jd.comp[2].v != 1 || yh < 1 || yh > 2 || yv < 1 || yv > 2) die("vardct: jpegdata=: sampling factors other than 4:4:4, 4:2:0, 4:2:2, 4:4:0");
+	jd.subsampling = yh == 2 ? (yv == 2 ? "420" : "422") : (yv == 2 ? "440" : "444");
+	const int mx = (W + 8 * yh - 1) / (8 * yh), my = (H + 8 * yv - 1) / (8 * yv);
+	for (int i = 0; i < 3; ++i) if (jd.comp[i].bx != mx * jd.comp[i].h || jd.comp[i].by != my * jd.comp[i].v) die("vardct: jpegdata=: a component's block grid is not the whole-MCU grid of the picture's size");
+	for (int i = 0; i < 3; ++i) {
+		if (fread(jd.comp[i].table, 2, 64, fp) != 64) die("vardct: jpegdata=: the file ends inside the tables");
+		for (int k = 0; k < 64; ++k) if (jd.comp[i].table[k] < 1 || jd.comp[i].table[k] > 255) die("vardct: jpegdata=: a table entry outside 1..255");
+	}
+	for (int i = 0; i < 3; ++i) {
+		JpegDump::Comp &c = jd.comp[i];
+		c.coef.resize((size_t) c.bx * (size_t) c.by * 64);
+		if (fread(c.coef.data(), 2, c.coef.size(), fp) != c.coef.size()) die("vardct: jpegdata=: the file ends inside the coefficients");
+	}
+	if (fgetc(fp) != EOF) die("vardct: jpegdata=: bytes behind the coefficients");
+	fclose(fp);
+	jd.present = true;
+	return jd;
+}
+
 static int run_vardct(int W, int H, uint64_t seed, const char *out, const Options &opt) {
 	SplitMix64 rng(seed * 0x100000001b3ull + 12345);
-	const int global_scale = opt.geti("global_scale", 8192), quant_lf = opt.geti("quant_lf", 4);
+	const JpegDump jd = load_jpeg_dump(opt, W, H);
+	const bool jpeg = jd.present;
+	const int global_scale = jpeg ? JPEG_GLOBAL_SCALE : opt.geti("global_scale", 8192), quant_lf = jpeg ? JPEG_QUANT_LF : opt.geti("quant_lf", 4);
 	const double density = opt.getd("density", 0.80), decay = opt.getd("decay", 0.84);
 	const int max_log = opt.geti("maxlog", 6);              // largest transform side (log2) used in the mix
 	const int coverage = opt.geti("coverage", opt.geti("forward", 0) ? 0 : 1);           // 1: force every transform type <= maxlog at least once per frame
@@ -341,8 +400,13 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	// (1,2)): the block grid padded to whole MCUs, every LF channel at its own size, DCT8 only, skip_adapt_lf_smooth, no filters, zero
 	// chroma-from-luma maps, per block only the channels present. flatchroma=1: Cb and Cr constant. dct8only=1, hfmul=N, nocfl=1: what
 	// a subsampled stream has anyway, for its 4:4:4 twins (every varblock DCT8; one HfMul; chroma-from-luma coded as all zero).
-	const int ycbcr = opt.geti("ycbcr", 0);
-	const std::string subsampling = opt.gets("subsampling", "444");
+	// jpegdata=PATH: the frame a JPEG file's quantised integers make (the dump of tests/jpeg_ref.py, laid out above load_jpeg_dump). It
+	// implies ycbcr=1, the file's subsampling, dct8only=1, hfmul=1, nocfl=1, nosmooth=1, no filters, 8 bits, global_scale 2048 and
+	// quant_lf 255, and writes: DCT8's dequantisation matrix in raw form (denominator 2^-12, 32640 / gcd(Q, 32640) per entry, the
+	// table transposed -- the stream's canonical index is 8 * horizontal + vertical frequency --, channels Cb, Y, Cr), the AC integers
+	// times K_c * Q / gcd(Q, 32640) in the HF streams, the DC integers times Q_00 * (16, 2, 1 for Cb, Y, Cr) in the LF image.
+	const int ycbcr = jpeg ? 1 : opt.geti("ycbcr", 0);
+	const std::string subsampling = jpeg ? jd.subsampling : opt.gets("subsampling", "444");
 	if (subsampling != "444" && subsampling != "420" && subsampling != "422" && subsampling != "440") die("vardct: subsampling=444|420|422|440");
 	const bool subsampled = subsampling != "444";
 	if (subsampled && !ycbcr) die("vardct: subsampling wants ycbcr=1");
@@ -350,11 +414,11 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	const int sub_h = subsampling == "420" || subsampling == "422" ? 1 : 0, sub_v = subsampling == "420" || subsampling == "440" ? 1 : 0;
 	const int hs[3] = {sub_h, 0, sub_h}, vs[3] = {sub_v, 0, sub_v};
 	const int jpeg_upsampling = subsampling == "420" ? 4 : subsampling == "422" ? 8 : subsampling == "440" ? 12 : 0;
-	const int dct8only = opt.geti("dct8only", subsampled ? 1 : 0), fixed_hfmul = opt.geti("hfmul", 0), nocfl = opt.geti("nocfl", 0), flatchroma = opt.geti("flatchroma", 0);
+	const int dct8only = jpeg ? 1 : opt.geti("dct8only", subsampled ? 1 : 0), fixed_hfmul = jpeg ? 1 : opt.geti("hfmul", 0), nocfl = jpeg ? 1 : opt.geti("nocfl", 0), flatchroma = opt.geti("flatchroma", 0);
 	if (fixed_hfmul < 0 || fixed_hfmul > 256) die("vardct: hfmul=1..256");
 	const int nonzero_header = opt.geti("fullheader", (num_passes > 1 || ycbcr) ? 1 : 0);
 	const int x_qm = opt.geti("xqm", 3), b_qm = opt.geti("bqm", 2);
-	const int skip_smooth = opt.geti("nosmooth", subsampled ? 1 : 0);
+	const int skip_smooth = jpeg ? 1 : opt.geti("nosmooth", subsampled ? 1 : 0);
 	const int small_clusters = opt.geti("simpleclusters", 0); // <= 8 clusters: simple cluster-map form
 	const int log_alpha = opt.geti("logalpha", 7);
 	const int container = opt.geti("container", 0);
@@ -542,7 +606,20 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		if (subsampled) { gg.w8 = std::min(256, PW / 8 - gg.left / 8); gg.h8 = std::min(256, PH / 8 - gg.top / 8); gg.w64 = (gg.w8 + 7) / 8; gg.h64 = (gg.h8 + 7) / 8; }
 		static const int SLOT_OF_STREAM[3] = {1, 0, 2};
 		for (int c = 0; c < 3; ++c) gg.lfq[c] = Channel(gg.w8 >> hs[SLOT_OF_STREAM[c]], gg.h8 >> vs[SLOT_OF_STREAM[c]]);
-		if (subsampled) {
+		if (jpeg) {
+			// the DC integers, scaled so that the LF rule gives d * Q_00 / (8 * 255): mult_lf = (1/4096, 1/512, 1/256) * 65536 / (2048 * 255)
+			for (int k = 0; k < 3; ++k) {
+				const int c = SLOT_OF_STREAM[k];
+				const JpegDump::Comp &jc = jd.slot(c);
+				for (int y = 0; y < gg.lfq[k].h; ++y) for (int x = 0; x < gg.lfq[k].w; ++x) {
+					const int bx = (gg.left >> 3 >> hs[c]) + x, by = (gg.top >> 3 >> vs[c]) + y;
+					if (bx >= jc.bx || by >= jc.by) die("vardct: jpegdata=: the LF image reaches beyond the component's block grid");
+					const int64_t v = (int64_t) jc.coef[((size_t) by * (size_t) jc.bx + (size_t) bx) * 64] * jc.table[0] * JPEG_LF_K[c];
+					if (v < -32767 || v > 32767) die("vardct: jpegdata=: a DC value leaves the LfGroup's 16-bit channels");
+					gg.lfq[k].at(x, y) = (int32_t) v;
+				}
+			}
+		} else if (subsampled) {
 			// every channel's LF image at its own size: the cell's mean (forward=1) or the picture at the cell's centre, in the plane's own coordinates
 			for (int k = 0; k < 3; ++k) {
 				const int c = SLOT_OF_STREAM[k], cw = gg.w8 >> hs[c], chh = gg.h8 >> vs[c], left = gg.left >> hs[c], top = gg.top >> vs[c];
@@ -745,6 +822,14 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		count_stream(gspec, dq_raw.back().second);
 	}
 
+	if (jpeg) {   // DCT8's matrix from the file's tables: entry (x, y) of channel c weighs canonical index 8 y + x = 8 * horizontal + vertical frequency
+		std::vector<Channel> mc;
+		for (int c = 0; c < 3; ++c) { Channel m(8, 8); for (int u = 0; u < 8; ++u) for (int v = 0; v < 8; ++v) { const int q = jd.slot(c).table[v * 8 + u]; m.at(v, u) = JPEG_L / jpeg_gcd(q, JPEG_L); } mc.push_back(m); }
+		dq_raw.emplace_back(0, StreamEncoder(gspec));
+		for (int c = 0; c < 3; ++c) encode_channel(tree, mc, c, 1 + 3 * num_lf_groups + 0, wp_in(100), dq_raw.back().second);
+		count_stream(gspec, dq_raw.back().second);
+	}
+
 	// ---- optional alpha extra channel: a Modular sub-image per pass group, coded after the group's HF coefficients
 	//      (j40.h:7024-7034) with the global tree and code spec ----
 	const int with_alpha = opt.geti("alpha", 0);
@@ -896,6 +981,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	}
 
 	std::vector<float> fpix, fcoef, fydeq;   // forward=1: one block's samples, coefficients, dequantised Y coefficients
+	std::vector<int32_t> jpeg_order;         // jpegdata=: scan position -> canonical index of DCT8
+	if (jpeg) j40hip::natural_order(3, 3, &jpeg_order);
 	for (int pass = 0; pass < num_passes; ++pass) {
 		for (int g = 0; g < num_groups; ++g) {
 			hf_enc[(size_t) pass].emplace_back(cspec[(size_t) pass]);
@@ -932,7 +1019,21 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 					double p = density * (c == 1 ? 1.0 : c == 0 ? 0.35 : 0.55) / (double) num_passes;
 					std::vector<std::pair<int, int>> coefs;  // (scan index, value)
 					double pk = p; const double dk = pow(decay, 64.0 / (double) size);
-					if (forward) {
+					if (jpeg) {
+						// the block's AC integers in the stream's scan order: scan position i holds canonical index 8 u + v (u: horizontal,
+						// v: vertical frequency), the file's coefficient [v][u]
+						const JpegDump::Comp &jc = jd.slot(c);
+						const int bx = ((gg.left >> 3) + gx8 + x8) >> hs[c], by = ((gg.top >> 3) + gy8 + y8) >> vs[c];
+						if (bx >= jc.bx || by >= jc.by) die("vardct: jpegdata=: a block beyond the component's block grid");
+						const int16_t *q = &jc.coef[((size_t) by * (size_t) jc.bx + (size_t) bx) * 64];
+						for (int i = first; i < size; ++i) {
+							const int pos = jpeg_order[(size_t) i], at = (pos & 7) * 8 + (pos >> 3);
+							if (!q[at]) continue;
+							const int64_t n = (int64_t) q[at] * (jc.table[at] / jpeg_gcd(jc.table[at], JPEG_L)) * JPEG_K[c];
+							if (n < -(1 << 28) || n > (1 << 28)) die("vardct: jpegdata=: a scaled coefficient leaves the 29 bits a hybrid integer holds here");
+							coefs.push_back({i, (int) n});
+						}
+					} else if (forward) {
 						// the block's samples -> coefficients -> quantised with the weights the decoder divides by (j40.h:7086-7094);
 						// X and B code what is left after the decoder's chroma-from-luma term (default factors: 0 and 1 times the
 						// dequantised Y coefficient, j40.h:7138-7143, 7159-7171)
@@ -1085,7 +1186,13 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		meta_enc[(size_t) ggi].flush(bw);
 	};
 	auto write_hf_global = [&](BitWriter &bw) {   // HfGlobal + HfPass (j40.h:6819)
-		if (opt.geti("dq", 0)) { bw.put(0, 1); write_dq_matrices(bw, dq_raw, wp_of); }
+		if (jpeg) {   // DCT8 raw, the sixteen others from the library
+			bw.put(0, 1);
+			bw.put(7, 3); bw.put(f16_bits(JPEG_DENOM), 16);
+			write_modular_header(bw, true, wp_of(100), {});
+			dq_raw[0].second.flush(bw);
+			for (int idx = 1; idx < 17; ++idx) bw.put(0, 3);
+		} else if (opt.geti("dq", 0)) { bw.put(0, 1); write_dq_matrices(bw, dq_raw, wp_of); }
 		else bw.put(1, 1);                                       // all dequantisation matrices default
 		bw.put((uint64_t) (num_presets - 1), ceil_lg((uint32_t) num_groups));
 		for (int pass = 0; pass < num_passes; ++pass) {
