@@ -13,7 +13,7 @@ CXXFLAGS += -DJ40_LANE_EV_FLUSH=$(EVENT_RING)
 HIPFLAGS = --offload-arch=$(ARCH) -std=c++17 -O3 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fvisibility=hidden -Wall -DJ40_LANE_EV_FLUSH=$(EVENT_RING) $(EXTRA_HIPFLAGS)
 SRC = j40_amd/csrc
 HOST_OBJS = build/obj/plan_build.o build/obj/plan_front.o build/obj/entropy.o build/obj/modular.o build/obj/tables.o build/obj/frame.o build/obj/capi_host.o build/obj/api.o
-DEV_OBJS = build/obj/kernels.o build/obj/modular_kernels.o build/obj/runtime.o build/obj/runtime_upload.o build/obj/runtime_lf.o build/obj/runtime_batch.o build/obj/runtime_lfp.o build/obj/runtime_debug.o build/obj/device_memory.o build/obj/pipeline.o build/obj/lf_tail_kernels.o build/obj/modular_coop.o build/obj/modular_quad.o build/obj/modular_split.o build/obj/lf_decode.o build/obj/plan_kernels.o build/obj/async.o build/obj/hostcopy.o build/obj/lf_preview.o build/obj/alpha_kernels.o build/obj/region_kernels.o build/obj/compose_kernels.o build/obj/runtime_seq.o build/obj/scale_kernels.o build/obj/ycbcr_kernels.o
+DEV_OBJS = build/obj/kernels.o build/obj/modular_kernels.o build/obj/runtime.o build/obj/runtime_upload.o build/obj/runtime_lf.o build/obj/runtime_batch.o build/obj/runtime_lfp.o build/obj/runtime_debug.o build/obj/device_memory.o build/obj/pipeline.o build/obj/lf_tail_kernels.o build/obj/modular_coop.o build/obj/modular_quad.o build/obj/modular_split.o build/obj/lf_decode.o build/obj/plan_kernels.o build/obj/async.o build/obj/hostcopy.o build/obj/lf_preview.o build/obj/alpha_kernels.o build/obj/region_kernels.o build/obj/compose_kernels.o build/obj/runtime_seq.o build/obj/scale_kernels.o build/obj/ycbcr_kernels.o build/obj/orient_kernels.o
 
 .PHONY: all lib tools oracle hostsim clean
 all: lib tools hostsim oracle
@@ -43,7 +43,8 @@ LAYOUTMAIN = $(if $(wildcard tests/hostsim/mod_layout_main.cpp),build/mod_layout
 SCALEMAIN = $(if $(wildcard tests/hostsim/scale_main.cpp),build/scale_main build/scale_main_san)
 HOSTSIM_HDR = $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp) $(wildcard tests/hostsim/*.hpp)
 YCBCRMAIN = $(if $(wildcard tests/hostsim/ycbcr_main.cpp),build/ycbcr_main build/ycbcr_main_san)
-hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/libhostsim_compose.so build/libhostsim_blend.so build/libhostsim_scale.so build/libhostsim_ycbcr.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN) $(SCALEMAIN) $(YCBCRMAIN)
+ORIENTMAIN = $(if $(wildcard tests/hostsim/orient_main.cpp),build/orient_main build/orient_main_san)
+hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/libhostsim_compose.so build/libhostsim_blend.so build/libhostsim_scale.so build/libhostsim_ycbcr.so build/libhostsim_orient.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN) $(SCALEMAIN) $(YCBCRMAIN) $(ORIENTMAIN)
 # test-only glue: parses a stream with the product's host parser, takes the plan view and hands it to
 # the CPU oracle (oracle/libj40oracle.so)
 build/liboracle_driver.so: tests/oracle_driver.c build/libj40hip.so oracle/hotpath_oracle.c include/j40hip.h
@@ -124,6 +125,19 @@ build/ycbcr_main: $(YCBCRMAIN_SRC) $(HOSTSIM_HDR) include/j40hip.h
 build/ycbcr_main_san: $(YCBCRMAIN_SRC) $(HOSTSIM_HDR) include/j40hip.h
 	@mkdir -p build
 	$(CXX) $(filter-out -fPIC -shared,$(HOSTSIM_FLAGS)) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(YCBCRMAIN_SRC) -lpthread
+
+# oriented output on the CPU (tests/test_orient.py): device/orient_dev.h's row and tile functions over an image in host memory ...
+build/libhostsim_orient.so: tests/hostsim/orient_sim.cpp $(SRC)/device/orient_dev.h
+	@mkdir -p build
+	$(CXX) $(HOSTSIM_FLAGS) -o $@ tests/hostsim/orient_sim.cpp
+# ... and as a program of its own, plain and with the host sanitizers (an executable: never loaded into Python)
+ORIENTMAIN_SRC = tests/hostsim/orient_main.cpp tests/hostsim/orient_sim.cpp
+build/orient_main: $(ORIENTMAIN_SRC) $(SRC)/device/orient_dev.h
+	@mkdir -p build
+	$(CXX) $(filter-out -fPIC -shared,$(HOSTSIM_FLAGS)) -o $@ $(ORIENTMAIN_SRC)
+build/orient_main_san: $(ORIENTMAIN_SRC) $(SRC)/device/orient_dev.h
+	@mkdir -p build
+	$(CXX) $(filter-out -fPIC -shared,$(HOSTSIM_FLAGS)) -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(ORIENTMAIN_SRC)
 
 build/jxlsynth: tools/jxlsynth.cpp $(wildcard tools/*.hpp) $(SRC)/tables.cpp $(SRC)/device/special8_dev.h $(SRC)/device/idct_dev.h
 	@mkdir -p build

@@ -376,6 +376,52 @@ J40HIP_API void j40hip_frame_scale(const j40hip_frame *f, int32_t out[5]);
  * other than 1 or 2, a stride below the rows' pixels), "Ufm?". */
 J40HIP_API uint32_t j40hip_kat_device_downscale(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, int32_t w, int32_t h, int32_t shift, int32_t format, void *stream);
 
+/* ---- oriented output: the picture turned as the image metadata's orientation says, by k_orient ("Orientation"). The
+ *      codestream stores a W x H frame and an orientation o in 1..8 (the EXIF numbering; 1 where the stream has none). Off by default:
+ *      every entry point then writes stored order, as the reference does. Applied, the decode entry points write ow x oh pixels, and
+ *      pixel (i, j) is P(x, y), P the image the same handle writes with the mode off and every other setting equal (format, alpha mode,
+ *      restoration mode, YCbCr mode, a region, a scale shift), W x H that image's size:
+ *        o  ow x oh  (x, y)                      o  ow x oh  (x, y)
+ *        1  W x H    (i, j)                      5  H x W    (j, i)
+ *        2  W x H    (W - 1 - i, j)              6  H x W    (j, H - 1 - i)
+ *        3  W x H    (W - 1 - i, H - 1 - j)      7  H x W    (W - 1 - j, H - 1 - i)
+ *        4  W x H    (i, H - 1 - j)              8  H x W    (W - 1 - j, i)
+ *      The orientation is applied last: a scaled oriented decode is the oriented small image (not the small image of the oriented
+ *      one: the two differ in the edge cells), and a region stays a rectangle in stored coordinates (j40hip_frame_orient_rect maps one).
+ *      set: mode -1 follows the environment (J40HIP_ORIENT=1 applies the orientation; the default), 0 is stored order, 1 applies it. Any
+ *      parsed frame, uploaded or not; it holds from the next decode on, across uploads. A handle j40hip_sequence_frame handed out refuses
+ *      mode 1 with "Uor?" and is never oriented by the environment; a refused call leaves the frame as it was.
+ *      A partial group range (j40hip_frame_set_group_range: the decode writes that range's rectangles and leaves the rest of the
+ *      caller's image alone) and an orientation in force exclude each other, since there is no whole stored-order image to turn:
+ *      mode 1 on a frame with a partial range and o other than 1 is "Uor?", j40hip_frame_set_group_range with a partial range on a
+ *      frame whose orientation is in force is "Uor?" (whichever comes second), and, because the environment can put an orientation
+ *      in force behind a range that was already set, the decode entry points themselves return "Uor?" for the combination before
+ *      anything is launched or written.
+ *      In force (applied, and o other than 1), j40hip_frame_decode / _timed / _decode_to_host and j40hip_frame_decode_lf /
+ *      _decode_lf_to_host (the preview: W x H its (width + 7) / 8 x (height + 7) / 8) decode as ever into a stored-order staging image
+ *      of exactly W x H pixels in device memory, kept with the frame (one block of the device memory cache, given back with the frame),
+ *      and k_orient writes the caller's ow x oh pixels behind it on the same stream. rgba_dev and stride_bytes need no alignment (as in
+ *      stored order; pixels that are not aligned to their size are stored byte by byte); stride_bytes below 4 * ow (u8) or 8 * ow (u16)
+ *      is "rnge" before anything is launched; nothing outside the ow pixels of each of the oh rows is written. The three figures of
+ *      j40hip_frame_decode_timed are the stored-order decode's stages: k_orient runs behind the last mark and is in none of them. j40hip_frame_decode_to_host copies the oriented image back, keeps the "evof" retry and
+ *      never decodes in two phases. Status and error codes are the stored-order decode's. With o = 1 or the mode off nothing is staged
+ *      and the path is the stored-order one.
+ *      Entries that write stored order only refuse a frame whose orientation is in force with "Uor?": j40hip_batch_create /
+ *      j40hip_batch_reset and j40hip_frames_decode_lf. Pipelines and sequences write stored order whatever the environment says.
+ *      j40hip_frame_orientation: out[0] the stream's orientation 1..8, out[1] 1 if the next decode applies one other than 1, out[2],
+ *      out[3] ow, oh the next decode writes (region and scale counted), out[4] 1 if the last decode went through k_orient, out[5] the
+ *      bytes of staging image it held (0 otherwise).
+ *      j40hip_frame_orient_rect: rectangle in = {x0, y0, w, h} of the whole frame from displayed (oriented by the stream's o, whatever
+ *      the mode) to stored coordinates (to_stored != 0) or back; "rnge" if it does not lie inside the frame it is given in. ---- */
+J40HIP_API uint32_t j40hip_frame_set_orientation(j40hip_frame *f, int mode);
+J40HIP_API void j40hip_frame_orientation(const j40hip_frame *f, int32_t out[6]);
+J40HIP_API uint32_t j40hip_frame_orient_rect(const j40hip_frame *f, int to_stored, const int32_t in[4], int32_t out[4]);
+/* known-answer / measuring hook: k_orient alone (device/orient_kernels.hip). The w x h image at src_dev written in `orientation` (1..8;
+ * 1 is a plain copy) at out_dev, w x h pixels up to 4 and h x w from 5 on, format J40HIP_U8X4 or J40HIP_U16X4, all rows pixel-aligned.
+ * The source must be pixel-aligned (pointer and stride); the output may sit anywhere. Asynchronous on `stream`. 0, "rnge" (an orientation
+ * outside 1..8, a stride below the rows' pixels, a source that is not pixel-aligned), "Ufm?". */
+J40HIP_API uint32_t j40hip_kat_device_orient(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, int32_t w, int32_t h, int32_t orientation, int32_t format, void *stream);
+
 /* After the stream has been synchronised: first failing section in TOC order -> its 4-char code
  * ("coef", "shrt", "excs", "ans?" ...), 0 if every section decoded cleanly (j40.h:530-534). */
 J40HIP_API uint32_t j40hip_frame_status(j40hip_frame *f);

@@ -134,6 +134,8 @@ def lib():
         "j40hip_frame_set_region": (u32, [vp, i32, i32, i32, i32]), "j40hip_frame_region": (None, [vp, vp]),
         "j40hip_frame_set_scale": (u32, [vp, i32]), "j40hip_frame_scale": (None, [vp, vp]), "j40hip_pipeline_set_scale": (u32, [vp, i32]),
         "j40hip_kat_device_downscale": (u32, [vp, sz, vp, sz, i32, i32, i32, i32, vp]),
+        "j40hip_frame_set_orientation": (u32, [vp, C.c_int]), "j40hip_frame_orientation": (None, [vp, vp]), "j40hip_frame_orient_rect": (u32, [vp, C.c_int, vp, vp]),
+        "j40hip_kat_device_orient": (u32, [vp, sz, vp, sz, i32, i32, i32, i32, vp]),
         "j40hip_kat_device_alpha_merge": (u32, [vp, sz, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
         "j40hip_frame_read_xyb": (u32, [vp, C.c_int, vp]), "j40hip_frame_restoration_ms": (C.c_float, [vp]),
         "j40hip_kat_device_restoration": (u32, [vp, i32, i32, vp, vp, vp, C.c_int, C.c_int, vp]),
@@ -229,7 +231,7 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
     scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
     (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
@@ -237,8 +239,10 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False):
     reference's). alpha=True keeps it for this call whatever the environment says: the frame goes through the thin C-ABI with
     Frame.set_alpha(1) on device 0 -- "TODO" / "Ual?" where that refuses (Frame.set_alpha).
     ycbcr=True: a YCbCr VarDCT frame (a recompressed JPEG) is served for this call whatever J40HIP_YCBCR says (Frame.set_ycbcr(1)),
-    likewise through the thin C-ABI on device 0; "TODO" for what that does not serve."""
-    if alpha or scale or ycbcr:
+    likewise through the thin C-ABI on device 0; "TODO" for what that does not serve.
+    orient=True: the picture in the orientation the stream carries (Frame.set_orientation(1)), [ow, oh] swapped for orientations 5 to
+    8, whatever J40HIP_ORIENT says; likewise through the thin C-ABI on device 0."""
+    if alpha or scale or ycbcr or orient:
         try:
             fr = Frame(data, ycbcr=bool(ycbcr))
         except J40Error as e:
@@ -249,6 +253,8 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False):
                 code = fr.set_ycbcr(1)
             if not code and scale:
                 code = fr.set_scale(scale)
+            if not code and orient:
+                code = fr.set_orientation(1)
             if code:
                 return code, None
             fr.set_output_format(fmt)
@@ -271,15 +277,24 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False):
     return err, out
 
 
-def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0):
+def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False):
     """rectangle (x, y, w, h) of the image through the thin C-ABI: returns (err4, ndarray [h, w, 4] or None), uint8 or uint16 with
     fmt=J40_U16X4 -- the crop of what decode() returns, decoded from the pass groups that cover it (Frame.set_region). The verdict is
-    the one over the sections that were decoded, then the public API's look behind the frame."""
+    the one over the sections that were decoded, then the public API's look behind the frame.
+    orient=True: (x, y, w, h) is a rectangle of the DISPLAYED picture -- the frame in the orientation its stream carries; it is mapped
+    to stored coordinates (Frame.orient_rect) and the result is the crop of the oriented whole picture, [h, w, 4]."""
     try:
         fr = Frame(data)
     except J40Error as e:
         return e.code, None
     try:
+        if orient:
+            code, stored = fr.orient_rect((x, y, w, h), to_stored=True)
+            if not code:
+                code = fr.set_orientation(1)
+            if code:
+                return code, None
+            x, y, w, h = stored
         code = fr.set_region(x, y, w, h)
         if code:
             return code, None
@@ -339,6 +354,31 @@ class Restoration(C.Structure):
     def params15(self):
         """sharp_lut[8], channel_scale[3], quant_mul, pass0, pass2, border_sad_mul: what the checkers' filter entry points take"""
         return np.array(list(self.epf_sharp_lut) + list(self.epf_channel_scale) + [self.epf_quant_mul, self.epf_pass0_sigma_scale, self.epf_pass2_sigma_scale, self.epf_border_sad_mul], np.float32)
+
+
+def kat_device_orient(src, orientation, fmt=None, pad=0, device=0):
+    """k_orient alone (j40hip_kat_device_orient): src [h, w, 4] uint8 or uint16 -> (err4, [oh, ow, 4] of the same dtype, guard) -- the
+    output's rows carry `pad` guard bytes filled with 0xA5 beforehand; guard: they all came back untouched. fmt: the format to ask
+    for (default: the array's own)"""
+    import torch
+    src = np.ascontiguousarray(src)
+    h, w = src.shape[:2]
+    pb = 4 * src.dtype.itemsize
+    if fmt is None:
+        fmt = J40_U16X4 if pb == 8 else J40_U8X4
+    ow, oh = (h, w) if 5 <= orientation <= 8 else (w, h)
+    stride = ow * pb + pad
+    dev = "cuda:%d" % device
+    d_src = torch.from_numpy(src.view(np.uint8).reshape(-1)).to(dev)
+    d_out = torch.full((oh * stride,), 0xA5, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(device)
+    code = err4(lib().j40hip_kat_device_orient(d_out.data_ptr(), stride, d_src.data_ptr(), w * pb, w, h, int(orientation), int(fmt), stream.cuda_stream))
+    stream.synchronize()
+    if code:
+        return code, None, True
+    host = d_out.cpu().numpy().reshape(oh, stride)
+    guard = bool((host[:, ow * pb:] == 0xA5).all())
+    return "", np.ascontiguousarray(host[:, :ow * pb]).view(src.dtype).reshape(oh, ow, 4), guard
 
 
 def kat_device_srgb_u16(values, bpp):
@@ -540,8 +580,8 @@ class Frame:
         """(err4, pixels [h, w, 4]): uint8, or uint16 when the frame is set to J40_U16X4; with a region set (set_region) h and w are
         the rectangle's and only it comes back from the device"""
         u16 = self.output_format() == J40_U16X4
-        r, sc = self.region(), self.scale()
-        w, h = (r["w"], r["h"]) if r["set"] else (sc["width"], sc["height"])   # (shift 0: the frame's own size)
+        o = self.orientation()
+        w, h = o["width"], o["height"]   # (region, scale and orientation counted; none of them: the frame's own size)
         out = np.zeros((h, w, 4), np.uint16 if u16 else np.uint8)
         code = lib().j40hip_frame_decode_to_host(self.h, out.ctypes.data, w * (8 if u16 else 4))
         return err4(code), out
@@ -581,6 +621,35 @@ class Frame:
         a = np.zeros(5, np.int32)
         lib().j40hip_frame_scale(self.h, a.ctypes.data)
         return dict(zip(["shift", "width", "height", "staged", "staging_bytes"], a.tolist()))
+
+    # ---- oriented output (include/j40hip.h) ----
+    def set_orientation(self, mode):
+        """1: the decode entry points write the picture in the orientation the stream carries (EXIF numbering 1..8; ow x oh is h x w
+        from 5 on), applied last by k_orient to what the handle writes in stored order; 0: stored order; -1 (the default): as
+        J40HIP_ORIENT says (j40hip_frame_set_orientation). Returns "" or "Uor?" (mode 1 on a handle from Sequence.frame, or on a frame
+        with a partial group range whose stream carries an orientation other than 1)"""
+        return err4(lib().j40hip_frame_set_orientation(self.h, int(mode)))
+
+    def orientation(self):
+        """j40hip_frame_orientation: orientation (the stream's, 1..8); applied (the next decode applies one other than 1); width, height
+        the next decode writes (region and scale counted); and of the last decode: went_through_k_orient, staging_bytes"""
+        a = np.zeros(6, np.int32)
+        lib().j40hip_frame_orientation(self.h, a.ctypes.data)
+        return dict(zip(["orientation", "applied", "width", "height", "went_through_k_orient", "staging_bytes"], a.tolist()))
+
+    def orient_rect(self, rect, to_stored=True):
+        """(err4, (x, y, w, h)): rectangle `rect` of the whole frame mapped from displayed to stored coordinates (to_stored) or back
+        (j40hip_frame_orient_rect); "rnge" and None if it lies outside the frame"""
+        try:
+            a = np.array([int(v) for v in rect], np.int64)
+        except (TypeError, ValueError):
+            return "rnge", None
+        if a.shape != (4,) or (a < -2 ** 31).any() or (a >= 2 ** 31).any():
+            return "rnge", None
+        a = a.astype(np.int32)
+        out = np.zeros(4, np.int32)
+        code = err4(lib().j40hip_frame_orient_rect(self.h, 1 if to_stored else 0, a.ctypes.data, out.ctypes.data))
+        return code, (None if code else tuple(out.tolist()))
 
     def two_phase_sections(self):
         """how decode_to_host last went: k > 0 = two phases with the k longest sections beside the others, 0 = one, -1 = not yet"""
@@ -746,8 +815,12 @@ class Frame:
         self._chk(lib().j40hip_frame_decode_lf(self.h, rgba_ptr, stride_bytes, stream), "in j40hip_frame_decode_lf")
 
     def decode_lf_to_host(self):
-        """the preview [h8, w8, 4]: uint8, or uint16 when the frame is set to J40_U16X4 (raises J40Error on failure)"""
+        """the preview [h8, w8, 4]: uint8, or uint16 when the frame is set to J40_U16X4 (raises J40Error on failure); [w8, h8, 4] where
+        an orientation from 5 on is in force (set_orientation)"""
         w8, h8 = self.lf_size()
+        o = self.orientation()
+        if o["applied"] and o["orientation"] >= 5:
+            w8, h8 = h8, w8
         u16 = self.output_format() == J40_U16X4
         out = np.zeros((h8, w8, 4), np.uint16 if u16 else np.uint8)
         self._chk(lib().j40hip_frame_decode_lf_to_host(self.h, out.ctypes.data, w8 * (8 if u16 else 4)), "in j40hip_frame_decode_lf_to_host")

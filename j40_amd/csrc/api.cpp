@@ -41,6 +41,7 @@ const struct { const char *err, *msg; } ERROR_STRINGS[] = {
 	{"fblk", "Black extra channel is disallowed"}, {"fm32", "32-bit buffers for modular encoding are disallowed"},
 	{"TODO", "Unimplemented feature encountered"}, {"TEST", "Testing-only error occurred"},
 	{"!gpu", "No usable HIP device (the hot path has no CPU fallback)"},
+	{"Uor?", "Image orientation is in force where only stored order is served"},
 };
 
 uint32_t code4(const char *s) { return ((uint32_t) (uint8_t) s[0] << 24) | ((uint32_t) (uint8_t) s[1] << 16) | ((uint32_t) (uint8_t) s[2] << 8) | (uint32_t) (uint8_t) s[3]; }
@@ -206,6 +207,10 @@ bool frames_policy() { return j40hip::env_on("J40HIP_FRAMES", false); }
 // J40HIP_SCALE=1|2: every image decodes at 1:2 / 1:4 (j40hip_frame_set_scale): j40_frame_pixels_* then report the small image's width,
 // height and stride. Looked at when an image is first advanced, like J40HIP_FRAMES; unset, 0 or anything else: full size.
 int scale_policy() { const int e = j40hip::env_int("J40HIP_SCALE", 0, INT_MIN, INT_MAX); return e == 1 || e == 2 ? e : 0; }
+// J40HIP_ORIENT=1: every image comes out in its orientation (j40hip_frame_set_orientation's default mode follows the same variable):
+// j40_frame_pixels_* then report the oriented picture's width, height and stride. Such images take the single-frame route -- the
+// serving pipeline writes stored order -- and sequences are not served.
+bool orient_policy() { return j40hip::orient_env(); }
 int parse_thread_count() {
 	static const int v = [] { const int e = j40hip::env_int("J40HIP_PARSE_THREADS", 0, 0, INT_MAX); return e > 0 ? e : std::max(1, std::min(12, j40hip_cpu_quota())); }();
 	return v;
@@ -236,6 +241,7 @@ j40_err advance(j40__inner *inner, int origin) {
 	if (inner->seq || inner->decoded) return 0;
 	const int shift = scale_policy();
 	if (shift && frames_policy()) { inner->origin = origin; return inner->err = code4("Usc?"); }   // sequences are not served at a scale
+	if (orient_policy() && frames_policy()) { inner->origin = origin; return inner->err = code4("Uor?"); }   // ... nor in an orientation
 	if (!inner->seq_checked && frames_policy()) {
 		// a file is read whole first; a stream that is not a sequence ("Usq?": its first frame is its last), or whose headers fail,
 		// takes the single-frame route below, which decodes it or reports what is wrong with it
@@ -250,7 +256,7 @@ j40_err advance(j40__inner *inner, int origin) {
 	const int64_t now = (int64_t) now_ms();
 	if (inside.n > 1) g_last_overlap_ms.store(now);
 	const bool u16 = inner->format == J40_U16X4;   // (16-bit images take the single-frame path: the pipeline writes u8x4 only)
-	const bool serve = !u16 && (policy == 1 || (policy == 2 && (inside.n > 1 || now - g_last_overlap_ms.load() < 200)));
+	const bool serve = !u16 && !orient_policy() && (policy == 1 || (policy == 2 && (inside.n > 1 || now - g_last_overlap_ms.load() < 200)));
 	const bool timing = j40hip::api_timing();
 	uint32_t err = 0;
 	std::unique_ptr<FileSource> src;
@@ -303,7 +309,11 @@ j40_err advance(j40__inner *inner, int origin) {
 	if (!err) {
 		int64_t info[32];
 		j40hip_frame_info(inner->frame, info);
-		err = make_plane(inner, (info[0] + (1 << shift) - 1) >> shift, (info[1] + (1 << shift) - 1) >> shift, u16 ? 8 : 4);
+		int64_t pw = (info[0] + (1 << shift) - 1) >> shift, ph = (info[1] + (1 << shift) - 1) >> shift;
+		int32_t orient[6];
+		j40hip_frame_orientation(inner->frame, orient);
+		if (orient[1] && orient[0] >= 5) std::swap(pw, ph);   // (J40HIP_ORIENT=1 and a stream that turns rows into columns)
+		err = make_plane(inner, pw, ph, u16 ? 8 : 4);
 	}
 	if (!err) err = j40hip_frame_set_output_format(inner->frame, inner->format);
 	if (!err && shift) err = j40hip_frame_set_scale(inner->frame, shift);

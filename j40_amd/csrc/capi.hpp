@@ -33,7 +33,12 @@ struct j40hip_frame {
 	// the last decode at a shift above 0 whether it went through a full-size staging image and how large that was (j40hip_frame_scale)
 	int32_t scale = 0, scale_staged = -1;
 	int64_t scale_staging_bytes = 0;
-	bool from_sequence = false;      // handed out by j40hip_sequence_frame: the playback owns its size (no scale)
+	bool from_sequence = false;      // handed out by j40hip_sequence_frame: the playback owns its size (no scale, no orientation)
+	// oriented output (j40hip_frame_set_orientation): -1 as J40HIP_ORIENT says, 0 stored order, 1 the image's orientation applied; and of
+	// the last decode whether it went through k_orient and the bytes of stored-order staging image it held (j40hip_frame_orientation)
+	int orient = -1;
+	int32_t orient_applied = 0;
+	int64_t orient_staging_bytes = 0;
 	int threads = 1;                 // what the frame was parsed with: the plan build at upload may use as many (plan_build.cpp)
 	// backing storage of the plan views (include/j40hip.h)
 	struct Views {
@@ -95,6 +100,22 @@ inline bool j40hip_alpha_kept(const j40hip_frame *h) {
 inline bool j40hip_ycbcr_on(const j40hip_frame *h) {
 	const bool asked = h->ycbcr >= 0 ? h->ycbcr == 1 : j40hip::ycbcr_env();
 	return asked && !h->from_view && !h->from_sequence;
+}
+
+// the orientation the next decode writes in: the stream's where the mode (or J40HIP_ORIENT=1) applies it, else 1 (stored order). A handle
+// a sequence hands out is never oriented: the playback writes stored order
+inline int32_t j40hip_orientation_in_force(const j40hip_frame *h) {
+	const bool asked = h->orient >= 0 ? h->orient == 1 : j40hip::orient_env();
+	return asked && !h->from_sequence ? h->frame.im.orientation : 1;
+}
+
+// The size of the stored-order image the next decode makes, which the orientation is applied to: the region's rectangle, else the frame
+// at its scale shift (ceil(width / s) x ceil(height / s); shift 0: the frame). The one statement of it: j40hip_frame_orientation reports
+// from it and decode_oriented sizes its staging image from it.
+inline void j40hip_stored_out_size(const j40hip_frame *h, int32_t *W, int32_t *H) {
+	const int32_t s = 1 << h->scale;
+	*W = h->region_set ? h->region[2] : (h->frame.fh.width + s - 1) >> h->scale;
+	*H = h->region_set ? h->region[3] : (h->frame.fh.height + s - 1) >> h->scale;
 }
 
 extern "C" j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads, uint32_t flags, j40hip::LfDeviceDecoder lf_decoder, void *lf_ctx, uint32_t *err);

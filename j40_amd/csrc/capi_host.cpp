@@ -8,6 +8,7 @@
 #include "capi.hpp"
 #include "tables.hpp"
 #include "device/region_dev.h"
+#include "device/orient_dev.h"
 
 using namespace j40hip;
 
@@ -364,6 +365,38 @@ void j40hip_frame_scale(const j40hip_frame *h, int32_t out[5]) {
 	const int32_t s = 1 << h->scale;
 	out[0] = h->scale; out[1] = (h->frame.fh.width + s - 1) >> h->scale; out[2] = (h->frame.fh.height + s - 1) >> h->scale;
 	out[3] = h->scale_staged; out[4] = (int32_t) std::min<int64_t>(h->scale_staging_bytes, INT32_MAX);
+}
+
+// ---- oriented output (include/j40hip.h; device/orient_dev.h has the arithmetic) ----
+uint32_t j40hip_frame_set_orientation(j40hip_frame *h, int mode) {
+	if (!h) return j40hip::ERR_RNGE;
+	if (mode > 0 && h->from_sequence) return E4("Uor?");   // the playback writes stored order
+	if (mode > 0 && h->partial_range && h->frame.im.orientation != 1) return E4("Uor?");   // a partial group range writes its own rectangles of the stored image: nothing whole to turn
+	h->orient = mode < 0 ? -1 : mode > 0 ? 1 : 0;
+	return 0;
+}
+void j40hip_frame_orientation(const j40hip_frame *h, int32_t out[6]) {
+	if (!out) return;
+	memset(out, 0, sizeof(int32_t) * 6);
+	out[0] = 1;
+	if (!h) return;
+	const int32_t o = j40hip_orientation_in_force(h);
+	int32_t W, H;
+	j40hip_stored_out_size(h, &W, &H);
+	out[0] = h->frame.im.orientation; out[1] = o != 1 ? 1 : 0;
+	j40hip::orient_out_size(W, H, o, &out[2], &out[3]);
+	out[4] = h->orient_applied; out[5] = (int32_t) std::min<int64_t>(h->orient_staging_bytes, INT32_MAX);
+}
+uint32_t j40hip_frame_orient_rect(const j40hip_frame *h, int to_stored, const int32_t in[4], int32_t out[4]) {
+	if (!h || !in || !out) return j40hip::ERR_RNGE;
+	const int32_t W = h->frame.fh.width, H = h->frame.fh.height, o = h->frame.im.orientation;
+	int32_t lw, lh;   // the image the rectangle lies in
+	if (to_stored) j40hip::orient_out_size(W, H, o, &lw, &lh); else { lw = W; lh = H; }
+	if (in[0] < 0 || in[1] < 0 || in[2] <= 0 || in[3] <= 0 || (int64_t) in[0] + in[2] > lw || (int64_t) in[1] + in[3] > lh) return j40hip::ERR_RNGE;
+	int32_t r[4];
+	if (to_stored) j40hip::orient_rect_to_stored(W, H, o, in, r); else j40hip::orient_rect_to_displayed(W, H, o, in, r);
+	memcpy(out, r, sizeof r);
+	return 0;
 }
 
 void j40hip_frame_free(j40hip_frame *f) {

@@ -100,6 +100,10 @@ void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, co
 // pixel_bytes 4 or 8, every row pixel-aligned
 void launch_downscale(const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int32_t W, int32_t H, int32_t shift, int32_t pixel_bytes, hipStream_t stream);
 
+// oriented output (device/orient_kernels.hip, orient_dev.h): the W x H image at src written in orientation 1..8 (the EXIF numbering) at dst,
+// W x H pixels for orientations up to 4 and H x W from 5 on; pixel_bytes 4 or 8, every row of both pixel-aligned
+void launch_orient(const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int32_t W, int32_t H, int32_t orientation, int32_t pixel_bytes, hipStream_t stream);
+
 // region decode (device/region_kernels.hip, region_dev.h). launch_region_index: the group-major index of the `count` varblocks of
 // `sorted` -- cursor: nkeys = groups * REGION_KEYS words of scratch, seg_start: nkeys + 1 words, index: count words.
 // launch_region_gather: the cover's varblocks, class by class from class_start[28], into `list` with their positions counted from the

@@ -5,6 +5,7 @@
 #include "runtime_state.hpp"
 #include "hostcopy.hpp"
 #include "ycbcr_dev.h"
+#include "orient_dev.h"
 
 // a Modular frame's groups can be decoded apart from each other when every group has a section of its own and no frame-wide inverse
 // transform reads across groups (j40hip_frame_set_group_range's rule; a region is otherwise widened to every group)
@@ -575,12 +576,65 @@ extern "C" uint32_t j40hip_kat_device_downscale(void *out_dev, size_t out_stride
 	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 }
 
+// ---- oriented output (j40hip_frame_set_orientation, include/j40hip.h; device/orient_dev.h, orient_kernels.hip) ----
+// The head of the single-frame decode entries. With the image's orientation in force and other than 1 the decode -- whatever it is: VarDCT,
+// Modular, YCbCr, filters, kept alpha, a region, a scale, either format -- is pointed at a stored-order staging image of exactly its W x H
+// pixels, one block of the device memory cache kept with the frame, and k_orient then writes the caller's buffer on the same stream: the
+// orientation is applied last, to the pixels the handle writes with the mode off. Else nothing is staged and the path is decode_impl's.
+// the staging image of W x H pixels; null: no memory
+static uint8_t *orient_image(j40hip_frame *h, int32_t W, int32_t H, size_t *stride) {
+	j40hip_device_state *st = h->dev;
+	*stride = pixel_bytes(h) * (size_t) W;
+	const size_t bytes = *stride * (size_t) H;
+	if (!st->orient_staging.ensure(st->device, bytes, false)) return nullptr;
+	h->orient_staging_bytes = (int64_t) bytes;
+	return (uint8_t *) st->orient_staging.ptr;
+}
+static uint32_t decode_oriented(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
+	if (!h || !h->dev || h->frame.lf_only) return decode_impl(h, rgba_dev, stride_bytes, s, ms3);   // (its refusals)
+	h->orient_applied = 0; h->orient_staging_bytes = 0;
+	const int32_t o = j40hip_orientation_in_force(h);
+	if (o == 1) return decode_impl(h, rgba_dev, stride_bytes, s, ms3);
+	// a partial group range writes its own rectangles and leaves the caller's other pixels alone: there is no whole stored-order image
+	// to turn, and the staging block's other pixels are whatever the block held. Refused before anything is launched.
+	if (h->partial_range) return ERR_UOR;
+	int32_t W, H, ow, oh;
+	j40hip_stored_out_size(h, &W, &H);
+	orient_out_size(W, H, o, &ow, &oh);
+	const size_t pb = pixel_bytes(h);
+	if (!rgba_dev || stride_bytes < pb * (size_t) ow) return ERR_RNGE;   // before anything is launched (any alignment of pointer and stride serves, as in stored order)
+	if (hipSetDevice(h->dev->device) != hipSuccess) return ERR_GPU;
+	size_t img_stride = 0;
+	uint8_t *img = orient_image(h, W, H, &img_stride);
+	if (!img) return ERR_MEM;
+	if (uint32_t e = decode_impl(h, img, img_stride, s, ms3)) return e;
+	launch_orient(img, img_stride, (uint8_t *) rgba_dev, stride_bytes, W, H, o, (int32_t) pb, s);
+	h->orient_applied = 1;
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+}
+
+// known-answer / measuring hook: k_orient alone
+extern "C" uint32_t j40hip_kat_device_orient(void *out_dev, size_t out_stride, const void *src_dev, size_t src_stride, int32_t w, int32_t h, int32_t orientation, int32_t format, void *stream) {
+	if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
+	const size_t pb = format == J40HIP_U16X4 ? 8 : 4;
+	if (!out_dev || !src_dev || w <= 0 || h <= 0 || w > (1 << 28) || h > (1 << 28) || !orient_valid(orientation)) return ERR_RNGE;
+	int32_t ow, oh;
+	orient_out_size(w, h, orientation, &ow, &oh);
+	if (src_stride < pb * (size_t) w || out_stride < pb * (size_t) ow || src_stride % pb || (uintptr_t) src_dev % pb) return ERR_RNGE;   // (the source pixel-aligned; the output anywhere)
+	if (orientation == 1) {
+		if (hipMemcpy2DAsync(out_dev, out_stride, src_dev, src_stride, pb * (size_t) w, (size_t) h, hipMemcpyDeviceToDevice, (hipStream_t) stream) != hipSuccess) return ERR_GPU;
+		return 0;
+	}
+	launch_orient((const uint8_t *) src_dev, src_stride, (uint8_t *) out_dev, out_stride, w, h, orientation, (int32_t) pb, (hipStream_t) stream);
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+}
+
 extern "C" uint32_t j40hip_frame_decode(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, void *stream) {
-	return guarded([&] { return decode_impl(h, rgba_dev, stride_bytes, (hipStream_t) stream, nullptr); });
+	return guarded([&] { return decode_oriented(h, rgba_dev, stride_bytes, (hipStream_t) stream, nullptr); });
 }
 
 extern "C" uint32_t j40hip_frame_decode_timed(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, void *stream, float *ms3) {
-	return guarded([&] { return decode_impl(h, rgba_dev, stride_bytes, (hipStream_t) stream, ms3); });
+	return guarded([&] { return decode_oriented(h, rgba_dev, stride_bytes, (hipStream_t) stream, ms3); });
 }
 
 // Status words reduced to a frame's verdict: the code of the first failing section in the order the reference reads them, which is the
@@ -748,13 +802,19 @@ static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host
 static uint32_t decode_to_host(j40hip_frame *h, void *rgba_host, size_t stride_bytes) {
 	if (h && h->frame.lf_only) return ERR_ULF;
 	if (!h || !h->dev) return ERR_GPU;
-	const bool region = h->region_set || h->scale > 0;   // (only the rectangle's rows, or the small image's, exist on either side, and they go the one-phase way)
-	if (h->region_set ? stride_bytes < pixel_bytes(h) * (size_t) h->region[2] : scaled_stride_too_small(h, stride_bytes)) return ERR_RNGE;
+	h->orient_applied = 0; h->orient_staging_bytes = 0;
+	const int32_t orientation = j40hip_orientation_in_force(h);   // (other than 1: the oriented image's rows, made by decode_oriented the one-phase way)
+	const bool region = h->region_set || h->scale > 0 || orientation != 1;   // (only the rectangle's rows, or the small image's, exist on either side, and they go the one-phase way)
+	int32_t sw, sh, ow, oh;
+	j40hip_stored_out_size(h, &sw, &sh);
+	orient_out_size(sw, sh, orientation, &ow, &oh);
+	if (orientation != 1 && h->partial_range) return ERR_UOR;   // (decode_oriented's refusal, before the block is taken)
+	if (orientation != 1 ? stride_bytes < pixel_bytes(h) * (size_t) ow : h->region_set ? stride_bytes < pixel_bytes(h) * (size_t) h->region[2] : scaled_stride_too_small(h, stride_bytes)) return ERR_RNGE;
 	const Frame &fr = h->frame;
 	const int device = h->dev->device;
 	if (hipSetDevice(device) != hipSuccess) return ERR_GPU;
 	// the device image uses the caller's row stride, so one contiguous copy brings it back
-	const size_t bytes = stride_bytes * (size_t) (h->region_set ? h->region[3] : h->scale > 0 ? scaled_height(h) : fr.fh.height);
+	const size_t bytes = stride_bytes * (size_t) (orientation != 1 ? oh : h->region_set ? h->region[3] : h->scale > 0 ? scaled_height(h) : fr.fh.height);
 	ScopedBlock block;   // (whatever way the call ends, the image goes back behind a device-wide wait)
 	if (!block.ensure(device, bytes, true)) return ERR_GPU;
 	void *d = block.ptr;
@@ -762,13 +822,13 @@ static uint32_t decode_to_host(j40hip_frame *h, void *rgba_host, size_t stride_b
 	uint32_t err = region ? 0 : decode_two_phase(h, (uint8_t *) d, (uint8_t *) rgba_host, stride_bytes, &two_phase);
 	if (two_phase && err != ERR_EVOF) return err;   // (the pixels are in rgba_host, or the frame has failed; "evof": the dense form below)
 	if (two_phase) (void) hipDeviceSynchronize();
-	err = decode_impl(h, d, stride_bytes, nullptr, nullptr);
+	err = decode_oriented(h, d, stride_bytes, nullptr, nullptr);
 	if (!err && hipStreamSynchronize(nullptr) != hipSuccess) err = ERR_GPU;
 	if (!err) err = j40hip_frame_status(h);
 	if (err == ERR_EVOF) {   // a section with more non-zero coefficients than its event region holds: decode with dense planes
 		h->force_dense = true;
 		err = j40hip_frame_upload(h, device);
-		if (!err) err = decode_impl(h, d, stride_bytes, nullptr, nullptr);
+		if (!err) err = decode_oriented(h, d, stride_bytes, nullptr, nullptr);
 		if (!err && hipStreamSynchronize(nullptr) != hipSuccess) err = ERR_GPU;
 		if (!err) err = j40hip_frame_status(h);
 	}

@@ -50,6 +50,7 @@ static uint32_t batch_assign(j40hip_batch *b, j40hip_frame *const *frames, int64
 		if (h && h->frame.lf_only) return ERR_ULF;
 		if (!h || !h->dev) return ERR_GPU;
 		if (h->region_set) return ERR_URG;         // a batch writes whole frames
+		if (j40hip_orientation_in_force(h) != 1) return ERR_UOR;   // ... in stored order
 		if (h->dev->is_modular) return ERR_TODO;   // Modular frames: decode them one by one
 		if (h->dev->ycbcr) return ERR_TODO;        // YCbCr frames (j40hip_frame_set_ycbcr): the single-frame decode alone serves them
 		if (i == 0) b->device = h->dev->device;

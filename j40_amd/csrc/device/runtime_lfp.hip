@@ -1,6 +1,7 @@
 // j40_amd/csrc/device/runtime_lfp.hip -- the LF preview (lf_preview.hip; include/j40hip.h, j40hip_frame_decode_lf): a frame's 1:8
 // picture from its LF sections alone
 #include "runtime_state.hpp"
+#include "orient_dev.h"
 
 // does the frame hold LF integers: parsed from a bitstream (frames built from a plan view carry LLF coefficients only)
 static bool lfp_has_integers(const j40hip_frame *h) {
@@ -134,23 +135,53 @@ static uint32_t lfp_launch(j40hip_frame *const *frames, int64_t n, void *const *
 }
 
 extern "C" uint32_t j40hip_frames_decode_lf(j40hip_frame *const *frames, int64_t n, void *const *rgba_dev, const size_t *stride_bytes, void *stream) {
+	// many previews in one launch are written in stored order: a member whose orientation is in force is refused before anything is launched
+	for (int64_t i = 0; frames && i < n; ++i) if (frames[i] && j40hip_orientation_in_force(frames[i]) != 1) return ERR_UOR;
 	return guarded([&] { return lfp_launch(frames, n, rgba_dev, stride_bytes, (hipStream_t) stream, false, 0); });
 }
 
+// the preview of one frame, in the image's orientation where that is in force (j40hip_frame_set_orientation): the stored-order preview
+// goes to the frame's staging block and k_orient writes `rgba_dev` behind it on `s`, as decode_oriented does for the full decode
+static uint32_t lfp_one(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s) {
+	if (!h || !h->dev) return ERR_GPU;
+	h->orient_applied = 0; h->orient_staging_bytes = 0;
+	const int32_t o = j40hip_orientation_in_force(h);
+	if (o == 1) return lfp_launch(&h, 1, &rgba_dev, &stride_bytes, s, false, 0);
+	if (h->frame.fh.is_modular || h->dev->is_modular) return ERR_TODO;   // (lfp_launch's own refusal, before anything is staged)
+	j40hip_device_state *st = h->dev;
+	const int32_t W = (h->frame.fh.width + 7) / 8, H = (h->frame.fh.height + 7) / 8;
+	int32_t ow, oh;
+	orient_out_size(W, H, o, &ow, &oh);
+	const size_t pb = pixel_bytes(h);
+	if (!rgba_dev || stride_bytes < pb * (size_t) ow) return ERR_RNGE;
+	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
+	size_t img_stride = pb * (size_t) W;
+	const size_t bytes = img_stride * (size_t) H;
+	if (!st->orient_staging.ensure(st->device, bytes, false)) return ERR_MEM;
+	void *img = st->orient_staging.ptr;
+	h->orient_staging_bytes = (int64_t) bytes;
+	if (uint32_t e = lfp_launch(&h, 1, &img, &img_stride, s, false, 0)) return e;
+	launch_orient((const uint8_t *) img, img_stride, (uint8_t *) rgba_dev, stride_bytes, W, H, o, (int32_t) pb, s);
+	h->orient_applied = 1;
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+}
+
 extern "C" uint32_t j40hip_frame_decode_lf(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, void *stream) {
-	return guarded([&] { return lfp_launch(&h, 1, &rgba_dev, &stride_bytes, (hipStream_t) stream, false, 0); });
+	return guarded([&] { return lfp_one(h, rgba_dev, stride_bytes, (hipStream_t) stream); });
 }
 
 // the preview (or a plane) in a device buffer of the cache, then to the host; synchronous
 static uint32_t lfp_to_host(j40hip_frame *h, void *host, size_t stride_bytes, bool plane, int32_t channel) {
 	if (!h || !h->dev) return ERR_GPU;
 	if (!host) return ERR_RNGE;
-	const size_t bytes = stride_bytes * (size_t) ((h->frame.fh.height + 7) / 8);
+	// (the preview proper comes back in the image's orientation where that is in force: lfp_one; a plane never does)
+	const bool turned = !plane && orient_transposes(j40hip_orientation_in_force(h));
+	const size_t bytes = stride_bytes * (size_t) (((turned ? h->frame.fh.width : h->frame.fh.height) + 7) / 8);
 	if (hipSetDevice(h->dev->device) != hipSuccess) return ERR_GPU;
 	ScopedBlock block;
 	if (!block.ensure(h->dev->device, bytes, true)) return ERR_GPU;
 	void *d = block.ptr;
-	uint32_t err = lfp_launch(&h, 1, &d, &stride_bytes, nullptr, plane, channel);
+	uint32_t err = plane ? lfp_launch(&h, 1, &d, &stride_bytes, nullptr, true, channel) : lfp_one(h, d, stride_bytes, nullptr);
 	if (!err && hipStreamSynchronize(nullptr) != hipSuccess) err = ERR_GPU;
 	if (!err && hipMemcpy(host, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) err = ERR_GPU;
 	return err;

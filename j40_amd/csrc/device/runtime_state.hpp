@@ -27,6 +27,7 @@ constexpr uint32_t ERR4(char a, char b, char c, char d) { return ((uint32_t) (ui
 constexpr uint32_t ERR_GPU = ERR4('!', 'g', 'p', 'u'), ERR_MEM = ERR4('!', 'm', 'e', 'm');
 constexpr uint32_t ERR_URG = ERR4('U', 'r', 'g', '?');   // a region (j40hip_frame_set_region) where only whole frames or group ranges are served, or the other way round
 constexpr uint32_t ERR_USC = ERR4('U', 's', 'c', '?');   // a scale (j40hip_frame_set_scale) where only full-size frames are served, or the other way round
+constexpr uint32_t ERR_UOR = ERR4('U', 'o', 'r', '?');   // an orientation in force (j40hip_frame_set_orientation) where only stored order is served
 constexpr uint32_t ERR_ULF = ERR4('U', 'l', 'f', '?');   // an LF-only frame (J40HIP_PARSE_LF_ONLY) has nothing but its LF image: the full decode's entry points refuse it
 
 // no exception crosses the C ABI: a parse error keeps its code, anything else (std::bad_alloc from a vector, ...) is "!mem"
@@ -226,6 +227,9 @@ struct j40hip_device_state {
 	// reduced-size decode (j40hip_frame_set_scale; decode_scaled): the full-size image of the staged combinations (restoration filters,
 	// keep-alpha), one block of the device memory cache, grown on demand, given back with the frame
 	CacheBlock scale_staging;
+	// oriented output (j40hip_frame_set_orientation; decode_oriented): the stored-order image k_orient reads, one block of the device
+	// memory cache, grown on demand, given back with the frame
+	CacheBlock orient_staging;
 	// a batch decoded the frame (trailers_pending): where, for the merge at j40hip_frame_status
 	void *pending_rgba = nullptr; size_t pending_stride = 0;
 

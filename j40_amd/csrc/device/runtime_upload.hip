@@ -6,7 +6,7 @@ extern "C" void j40hip_release_device(j40hip_frame *f) {
 	if (!f || !f->dev) return;
 	(void) hipSetDevice(f->dev->device);
 	bool idle = f->dev->idle;   // else one device-wide wait, ahead of the first block that goes back: nothing may still be running on memory that is handed to another frame
-	for (CacheBlock *b : {&f->dev->plan_block, &f->dev->work_block, &f->dev->two_block, &f->dev->alpha.block, &f->dev->region.staging, &f->dev->scale_staging}) if (b->ptr) { b->release(idle); idle = true; }
+	for (CacheBlock *b : {&f->dev->plan_block, &f->dev->work_block, &f->dev->two_block, &f->dev->alpha.block, &f->dev->region.staging, &f->dev->scale_staging, &f->dev->orient_staging}) if (b->ptr) { b->release(idle); idle = true; }
 	for (auto &b : f->dev->buffers) b.release();
 	for (auto &e : f->dev->ev) if (e) (void) hipEventDestroy(e);
 	delete f->dev;
@@ -277,6 +277,7 @@ static uint32_t j40hip_frame_set_group_range_body(j40hip_frame *h, int64_t first
 	if (first_group < 0 || num_groups < 0 || first_group + num_groups > h->frame.fh.num_groups) return ERR_RNGE;
 	if (h->region_set && !(first_group == 0 && num_groups == h->frame.fh.num_groups)) return ERR_URG;   // a region and a partial range exclude each other
 	if (h->scale > 0 && !(first_group == 0 && num_groups == h->frame.fh.num_groups)) return ERR_USC;     // ... and so do a scale and a partial range
+	if (j40hip_orientation_in_force(h) != 1 && !(first_group == 0 && num_groups == h->frame.fh.num_groups)) return ERR_UOR;   // ... and an orientation in force and one
 	j40hip_device_state *st = h->dev;
 	if (st->is_modular) {
 		// Modular frames: the groups' sections are independent of each other (no predictor looks across a group's edge), and so are

@@ -166,7 +166,7 @@ static void read_image_metadata(BitReader &br, ImageMeta *im) {  // j40.h:3104
 	if (!br.u(1)) {  // !all_default
 		bool extra_fields = br.u(1);
 		if (extra_fields) {
-			(void) br.u(3);  // orientation
+			im->orientation = 1 + (int32_t) br.u(3);
 			if (br.u(1)) { int32_t w, h; read_size_header(br, &w, &h); }
 			if (br.u(1)) J40HIP_RAISE("TODO");  // preview
 			if (br.u(1)) {  // animation

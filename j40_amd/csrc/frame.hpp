@@ -18,6 +18,8 @@ inline bool api_timing() { static const bool v = env_str("J40HIP_API_TIMING") !=
 // J40HIP_ALPHA=1: VarDCT frames keep their alpha channel where j40hip_frame_set_alpha(f, 1) would be taken (include/j40hip.h); read once
 inline bool alpha_env() { static const bool v = [] { const char *e = env_str("J40HIP_ALPHA"); return e && atoi(e) > 0; }(); return v; }
 
+// J40HIP_ORIENT=1: single-frame decodes apply the image's orientation where j40hip_frame_set_orientation(f, 1) would be taken (include/j40hip.h); read once
+inline bool orient_env() { static const bool v = [] { const char *e = env_str("J40HIP_ORIENT"); return e && atoi(e) > 0; }(); return v; }
 // J40HIP_YCBCR=1: YCbCr VarDCT frames (recompressed JPEGs) are served where j40hip_frame_set_ycbcr(f, 1) would be taken (include/j40hip.h); read once
 inline bool ycbcr_env() { static const bool v = [] { const char *e = env_str("J40HIP_YCBCR"); return e && atoi(e) > 0; }(); return v; }
 
@@ -27,6 +29,7 @@ enum { EC_ALPHA = 0, EC_SPOT = 2, EC_BLACK = 4, EC_CFA = 5 };
 struct ImageMeta {
 	int32_t width = 0, height = 0;
 	int32_t bpp = 8, exp_bits = 0;
+	int32_t orientation = 1;   // 1..8, the EXIF numbering (the stream holds orientation - 1 in its extra fields; 1 where it has none)
 	bool have_animation = false, anim_have_timecodes = false;
 	int32_t anim_tps_num = 0, anim_tps_den = 0; int64_t anim_loops = 0;   // ticks per second as a fraction, repetitions (0: for ever); with have_animation
 	bool modular_16bit_buffers = true;

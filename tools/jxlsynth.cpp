@@ -55,12 +55,17 @@ struct SeqFrame {
 };
 static SeqFrame *g_seq = nullptr;
 
+// orientation=N (1..8, every mode): ImageMetadata.extra_fields carries orientation - 1; 0: the option was not given
+static int g_orientation = 0;
 // ImageMetadata.extra_fields (j40.h:3147-3163): 0, or for an animation: orientation 1, no intrinsic size, no preview, the animation
-// header (tps 10 / 1, loops 0, no timecodes)
+// header (tps 10 / 1, loops 0, no timecodes); with orientation=N: extra fields with that orientation (and, outside an animation,
+// nothing else)
 static void write_extra_fields(BitWriter &cs) {
-	if (!g_seq || !g_seq->anim) { cs.put(0, 1); return; }
+	const bool anim = g_seq && g_seq->anim;
+	if (!anim && !g_orientation) { cs.put(0, 1); return; }
 	cs.put(1, 1);
-	cs.put(0, 3); cs.put(0, 1); cs.put(0, 1);   // orientation - 1, have_intrinsic_size, have_preview
+	cs.put((uint64_t) (g_orientation ? g_orientation - 1 : 0), 3); cs.put(0, 1); cs.put(0, 1);   // orientation - 1, have_intrinsic_size, have_preview
+	if (!anim) { cs.put(0, 1); return; }            // have_animation
 	cs.put(1, 1);                                   // have_animation
 	cs.put(2, 2); cs.put(9, 10);                    // tps_numerator U32(100, 1000, 1 + u(10), 1 + u(30)) = 10
 	cs.put(0, 2);                                   // tps_denominator U32(1, 1001, 1 + u(8), 1 + u(10)) = 1
@@ -68,7 +73,7 @@ static void write_extra_fields(BitWriter &cs) {
 	cs.put(0, 1);                                   // have_timecodes
 }
 // ... and what they add behind ColourEncoding: ToneMapping.all_default (j40.h:3234)
-static void write_tone_mapping(BitWriter &cs) { if (g_seq && g_seq->anim) cs.put(1, 1); }
+static void write_tone_mapping(BitWriter &cs) { if ((g_seq && g_seq->anim) || g_orientation) cs.put(1, 1); }
 
 // the frame header from have_crop to save_before_color_transform (j40.h:5285-5336). Outside a sequence: no crop, Replace, is_last.
 static void write_frame_placement(BitWriter &cs, int num_ec, int frame_w, int frame_h) {
@@ -1273,7 +1278,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		write_tone_mapping(cs);
 		cs.put(0, 2);                       // extensions
 		cs.put(1, 1);                       // default_m
-	} else if (img_bpp != 8 || (seq_anim && !with_alpha) || (noxyb && !with_alpha)) {
+	} else if (img_bpp != 8 || (seq_anim && !with_alpha) || (noxyb && !with_alpha) || (g_orientation && !with_alpha && !icc_bytes)) {   // (orientation=N: the metadata written out where it would be all_default)
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		write_bit_depth(cs, img_bpp);
@@ -2173,6 +2178,11 @@ int main(int argc, char **argv) {
 	if (W <= 0 || H <= 0) die("bad dimensions");
 	const bool vardct = !strcmp(argv[1], "vardct");
 	if (!vardct && strcmp(argv[1], "modular")) die("unknown mode");
+	if (opt.kv.count("orientation")) {
+		g_orientation = opt.geti("orientation", 0);
+		if (g_orientation < 1 || g_orientation > 8) die("orientation=1..8");
+		opt.kv.erase("orientation");
+	}
 	static const char *const SEQ_KEYS[] = {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only"};
 	bool sequence = false;
 	for (const char *k : SEQ_KEYS) sequence = sequence || opt.kv.count(k);
