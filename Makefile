@@ -44,7 +44,9 @@ SCALEMAIN = $(if $(wildcard tests/hostsim/scale_main.cpp),build/scale_main build
 HOSTSIM_HDR = $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp) $(wildcard tests/hostsim/*.hpp)
 YCBCRMAIN = $(if $(wildcard tests/hostsim/ycbcr_main.cpp),build/ycbcr_main build/ycbcr_main_san)
 ORIENTMAIN = $(if $(wildcard tests/hostsim/orient_main.cpp),build/orient_main build/orient_main_san)
-hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/libhostsim_compose.so build/libhostsim_blend.so build/libhostsim_scale.so build/libhostsim_ycbcr.so build/libhostsim_orient.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN) $(SCALEMAIN) $(YCBCRMAIN) $(ORIENTMAIN)
+WIDESIM = $(if $(wildcard tests/hostsim/wide_sim.cpp),build/libwidesim.so)
+WIDEMAIN = $(if $(wildcard tests/hostsim/wide_main.cpp),build/wide_main build/wide_main_san)
+hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/libhostsim_compose.so build/libhostsim_blend.so build/libhostsim_scale.so build/libhostsim_ycbcr.so build/libhostsim_orient.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN) $(SCALEMAIN) $(YCBCRMAIN) $(ORIENTMAIN) $(WIDESIM) $(WIDEMAIN)
 # test-only glue: parses a stream with the product's host parser, takes the plan view and hands it to
 # the CPU oracle (oracle/libj40oracle.so)
 build/liboracle_driver.so: tests/oracle_driver.c build/libj40hip.so oracle/hotpath_oracle.c include/j40hip.h
@@ -138,6 +140,21 @@ build/orient_main: $(ORIENTMAIN_SRC) $(SRC)/device/orient_dev.h
 build/orient_main_san: $(ORIENTMAIN_SRC) $(SRC)/device/orient_dev.h
 	@mkdir -p build
 	$(CXX) $(filter-out -fPIC -shared,$(HOSTSIM_FLAGS)) -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(ORIENTMAIN_SRC)
+
+# wide Modular frames on the CPU (tests/test_wide_modular.py): the Modular device functions instantiated with int32 samples over a plan
+# laid out with guard bytes ...
+WIDESIM_SRC = tests/hostsim/wide_sim.cpp $(SRC)/plan_build.cpp $(SRC)/plan_front.cpp $(SRC)/entropy.cpp $(SRC)/modular.cpp $(SRC)/tables.cpp $(SRC)/frame.cpp
+build/libwidesim.so: $(WIDESIM_SRC) $(HOSTSIM_HDR) include/j40hip.h
+	@mkdir -p build
+	$(CXX) $(HOSTSIM_FLAGS) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -o $@ $(WIDESIM_SRC) -lpthread
+# ... and as a program of its own, plain and with the host sanitizers (an executable: never loaded into Python)
+WIDEMAIN_SRC = tests/hostsim/wide_main.cpp $(WIDESIM_SRC)
+build/wide_main: $(WIDEMAIN_SRC) $(HOSTSIM_HDR) include/j40hip.h
+	@mkdir -p build
+	$(CXX) $(filter-out -fPIC -shared,$(HOSTSIM_FLAGS)) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -o $@ $(WIDEMAIN_SRC) -lpthread
+build/wide_main_san: $(WIDEMAIN_SRC) $(HOSTSIM_HDR) include/j40hip.h
+	@mkdir -p build
+	$(CXX) $(filter-out -fPIC -shared,$(HOSTSIM_FLAGS)) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(WIDEMAIN_SRC) -lpthread
 
 build/jxlsynth: tools/jxlsynth.cpp $(wildcard tools/*.hpp) $(SRC)/tables.cpp $(SRC)/device/special8_dev.h $(SRC)/device/idct_dev.h
 	@mkdir -p build

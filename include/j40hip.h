@@ -64,6 +64,12 @@ J40HIP_API void j40hip_frame_free(j40hip_frame *f);
  * instead of refused with "TODO" before its LF image is read, which is where the reference refuses it. J40HIP_YCBCR=1 in the
  * environment does the same for every parse. */
 #define J40HIP_PARSE_YCBCR 4u
+/* flags & J40HIP_PARSE_WIDE: wide Modular frames are asked for (see j40hip_frame_wide): an image whose metadata says
+ * modular_16bit_buffers = 0 -- every 16-bit lossless image, and what libjxl writes for every image deeper than 12 bits -- is parsed
+ * instead of refused with "fm32", which is where the reference refuses it (j40.h:3169). A Modular frame of such an image is then decoded
+ * with 32-bit sample planes; a VarDCT frame of one is "TODO" at parse. J40HIP_WIDE=1 in the environment does the same for every parse,
+ * and j40hip_sequence_open takes the flag too. */
+#define J40HIP_PARSE_WIDE 8u
 /* the shortest prefix of the codestream holding headers, TOC, LfGlobal and every LfGroup section (the largest end among those
  * sections, so a permuted TOC is covered); a bare codestream's file prefix. Single-section frames: the whole codestream. */
 J40HIP_API int64_t j40hip_frame_lf_end(const j40hip_frame *f);
@@ -307,6 +313,13 @@ J40HIP_API uint32_t j40hip_kat_device_alpha_merge(void *rgba_dev, size_t stride_
  *      than the finest channel it is sampled; out[7] the last decode went through the YCbCr planes and k_ycbcr_tail. ---- */
 J40HIP_API uint32_t j40hip_frame_set_ycbcr(j40hip_frame *f, int mode);
 J40HIP_API void j40hip_frame_ycbcr(const j40hip_frame *f, int32_t out[8]);
+/* ---- wide Modular frames ("16-bit images"): Modular frames of images with 32-bit Modular buffers, integer samples of
+ *      8..16 bits, alpha at the same depth. Opt-in at parse (J40HIP_PARSE_WIDE / J40HIP_WIDE=1). Served: everything a narrow Modular frame
+ *      is served with -- both output formats, a region, a scale, an orientation, a group range, sequences. "TODO": VarDCT frames of such
+ *      images, batches, pipelines. Pinned by lossless round trips and by equality with the narrow path, not by the reference.
+ *      j40hip_frame_wide: out[0] the image has 32-bit buffers; out[1] its bit depth; out[2] the last decode ran the int32 kernels;
+ *      out[3] bytes per sample of the frame's planes on the device (2 or 4; 0 before an upload). ---- */
+J40HIP_API void j40hip_frame_wide(const j40hip_frame *f, int32_t out[4]);
 /* staged hook: plane c (0 Cb, 1 Y, 2 Cr) of the last decode that went through the YCbCr path, as k_ycbcr_tail read it -- the pixel
  * kernels' samples, or the restoration filters' result where those ran -- tightly packed: width x height floats for a 4:4:4 frame;
  * for a subsampled one the block grid padded to whole MCUs, ((ceil(width / (8 << mh)) << mh) * 8 >> hshift[c]) x (likewise with
@@ -455,6 +468,8 @@ J40HIP_API uint32_t j40hip_frame_read_lf(j40hip_frame *f, int c, float *out);
 J40HIP_API uint32_t j40hip_frame_read_coeffs(j40hip_frame *f, int64_t gg, int c, float *out);
 /*   int16 sample planes (Modular frames) before packing: channel c, w*h */
 J40HIP_API uint32_t j40hip_frame_read_plane_i16(j40hip_frame *f, int c, int16_t *out);
+/*   the same of a wide frame (int32 planes); each answers "TODO" for a frame of the other kind */
+J40HIP_API uint32_t j40hip_frame_read_plane_i32(j40hip_frame *f, int c, int32_t *out);
 
 /* ---- restoration filters: Gaborish and the edge-preserving filter between the inverse transforms and the colour
  *      conversion, over the whole picture. The reference parses the frame header's RestorationFilter bundle (j40.h:5339-5366) and never
@@ -540,7 +555,8 @@ J40HIP_API uint32_t j40hip_batch_reset(j40hip_batch *b, j40hip_frame *const *fra
  *      j40hip_sequence_free; a container's boxes are put together once); no device needed. A stream whose first frame is its last is
  *      not a sequence: NULL and "Usq?" (use j40hip_frame_parse). NULL and the code when the image header or the first frame's header
  *      fails. A later frame whose header or TOC fails, or that is refused, ends the index: it is the last row and carries its code.
- *      flags: bit 0 as j40hip_frame_parse_ex's, applied to every frame handle; bit 1 J40HIP_SEQ_BLEND. ---- */
+ *      flags: bit 0 as j40hip_frame_parse_ex's, applied to every frame handle; bit 1 J40HIP_SEQ_BLEND; J40HIP_PARSE_WIDE (8) as
+ *      j40hip_frame_parse_ex's: an image with 32-bit Modular buffers is opened and its Modular frames are served. ---- */
 #define J40HIP_SEQ_BLEND 2u   /* j40hip_sequence_open: serve the blend modes Add (1), Blend (2), MulAdd (3) and Mul (4) too */
 typedef struct j40hip_sequence j40hip_sequence;
 J40HIP_API j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads, uint32_t flags, uint32_t *err);

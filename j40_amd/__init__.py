@@ -24,6 +24,7 @@ J40_U8X4 = 0x0F33
 J40_U16X4 = 0x0F35
 PARSE_LF_ONLY = 2   # J40HIP_PARSE_LF_ONLY (include/j40hip.h): the LF preview's parse
 PARSE_YCBCR = 4     # J40HIP_PARSE_YCBCR: YCbCr frames are asked for (a subsampled one is parsed instead of refused)
+PARSE_WIDE = 8      # J40HIP_PARSE_WIDE: wide Modular frames are asked for (an image with 32-bit Modular buffers is parsed instead of "fm32")
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("J40HIP_LIB") or os.path.join(_ROOT, "build", "libj40hip.so")
@@ -130,6 +131,7 @@ def lib():
         "j40hip_frame_restoration": (None, [vp, vp]), "j40hip_frame_set_restoration": (None, [vp, C.c_int]), "j40hip_frame_sharpness": (C.c_int, [vp, i64, vp]),
         "j40hip_frame_set_alpha": (u32, [vp, C.c_int]), "j40hip_frame_alpha": (None, [vp, vp]),
         "j40hip_frame_set_ycbcr": (u32, [vp, C.c_int]), "j40hip_frame_ycbcr": (None, [vp, vp]), "j40hip_frame_read_ycbcr": (u32, [vp, C.c_int, vp]),
+        "j40hip_frame_wide": (None, [vp, vp]), "j40hip_frame_read_plane_i32": (u32, [vp, C.c_int, vp]),
         "j40hip_kat_device_ycbcr_tail": (u32, [vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
         "j40hip_frame_set_region": (u32, [vp, i32, i32, i32, i32]), "j40hip_frame_region": (None, [vp, vp]),
         "j40hip_frame_set_scale": (u32, [vp, i32]), "j40hip_frame_scale": (None, [vp, vp]), "j40hip_pipeline_set_scale": (u32, [vp, i32]),
@@ -231,7 +233,7 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
     scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
     (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
@@ -241,10 +243,12 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     ycbcr=True: a YCbCr VarDCT frame (a recompressed JPEG) is served for this call whatever J40HIP_YCBCR says (Frame.set_ycbcr(1)),
     likewise through the thin C-ABI on device 0; "TODO" for what that does not serve.
     orient=True: the picture in the orientation the stream carries (Frame.set_orientation(1)), [ow, oh] swapped for orientations 5 to
-    8, whatever J40HIP_ORIENT says; likewise through the thin C-ABI on device 0."""
-    if alpha or scale or ycbcr or orient:
+    8, whatever J40HIP_ORIENT says; likewise through the thin C-ABI on device 0.
+    wide=True: an image with 32-bit Modular buffers (every 16-bit lossless image) is served for this call whatever J40HIP_WIDE says
+    (PARSE_WIDE), likewise through the thin C-ABI on device 0; its VarDCT frames are "TODO"."""
+    if alpha or scale or ycbcr or orient or wide:
         try:
-            fr = Frame(data, ycbcr=bool(ycbcr))
+            fr = Frame(data, ycbcr=bool(ycbcr), wide=bool(wide))
         except J40Error as e:
             return e.code, None
         try:
@@ -277,14 +281,15 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     return err, out
 
 
-def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False):
+def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False, wide=False):
     """rectangle (x, y, w, h) of the image through the thin C-ABI: returns (err4, ndarray [h, w, 4] or None), uint8 or uint16 with
     fmt=J40_U16X4 -- the crop of what decode() returns, decoded from the pass groups that cover it (Frame.set_region). The verdict is
     the one over the sections that were decoded, then the public API's look behind the frame.
     orient=True: (x, y, w, h) is a rectangle of the DISPLAYED picture -- the frame in the orientation its stream carries; it is mapped
-    to stored coordinates (Frame.orient_rect) and the result is the crop of the oriented whole picture, [h, w, 4]."""
+    to stored coordinates (Frame.orient_rect) and the result is the crop of the oriented whole picture, [h, w, 4].
+    wide=True: as decode()'s."""
     try:
-        fr = Frame(data)
+        fr = Frame(data, wide=bool(wide))
     except J40Error as e:
         return e.code, None
     try:
@@ -403,16 +408,18 @@ def kat_device_restoration(planes, sharpness, hfmul_inv, r, mode=1, device=0):
 class Frame:
     """thin C-ABI (include/j40hip.h): host parse, plan upload, hot path on a HIP stream"""
 
-    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False, ycbcr=False):
+    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False, ycbcr=False, wide=False):
         """lf_device: a HIP device index -- the LfGroup streams are decoded there instead of on the host (j40hip_frame_parse_on).
         lf_only: parse what the LF preview needs and nothing more (J40HIP_PARSE_LF_ONLY): `data` may end at lf_end(); such a frame
         can only be previewed (decode_lf_to_host, decode_lf).
         ycbcr: YCbCr frames are asked for (J40HIP_PARSE_YCBCR): a frame with subsampled channels is parsed instead of refused; serving
-        it still takes set_ycbcr(1) (or J40HIP_YCBCR=1)"""
+        it still takes set_ycbcr(1) (or J40HIP_YCBCR=1)
+        wide: wide Modular frames are asked for (J40HIP_PARSE_WIDE): an image with 32-bit Modular buffers is parsed instead of refused
+        with "fm32", and its Modular frame is decoded with int32 sample planes (wide())"""
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        flags = (PARSE_LF_ONLY if lf_only else 0) | (PARSE_YCBCR if ycbcr else 0)
+        flags = (PARSE_LF_ONLY if lf_only else 0) | (PARSE_YCBCR if ycbcr else 0) | (PARSE_WIDE if wide else 0)
         if lf_device is None:
             self.h = L.j40hip_frame_parse_ex(self._buf, len(data), threads, flags, C.byref(err))
         else:
@@ -692,6 +699,19 @@ class Frame:
         lib().j40hip_frame_ycbcr(self.h, a.ctypes.data)
         return {"ycbcr": int(a[0]), "shifts": tuple((int(a[1 + 2 * c]), int(a[2 + 2 * c])) for c in range(3)), "used": int(a[7])}
 
+    def wide(self):
+        """{"wide": the image has 32-bit Modular buffers, "bpp": its bit depth, "used": the last decode ran the int32 kernels,
+        "sample_bytes": bytes per sample of the uploaded frame's planes (0 before an upload)}"""
+        a = np.zeros(4, np.int32)
+        lib().j40hip_frame_wide(self.h, a.ctypes.data)
+        return {"wide": int(a[0]), "bpp": int(a[1]), "used": int(a[2]), "sample_bytes": int(a[3])}
+
+    def read_plane_i32(self, c, shape):
+        """after a decode of a wide frame: channel c of the frame's planes (after the inverse transforms), int32 [shape]"""
+        a = np.zeros(shape, np.int32)
+        self._chk(lib().j40hip_frame_read_plane_i32(self.h, int(c), a.ctypes.data), "in j40hip_frame_read_plane_i32")
+        return a
+
     def ycbcr_plane_shape(self, c):
         """(rows, columns) of plane c as j40hip_frame_read_ycbcr returns it: the frame's size, or for a subsampled frame the block
         grid padded to whole MCUs at the channel's resolution"""
@@ -883,11 +903,11 @@ class Sequence:
     an index over headers and TOCs on the host, every coded frame an ordinary Frame, the displayed canvases composed on the device.
     blend=True (or J40HIP_BLEND=1): frames with the blend modes Add, Blend, MulAdd and Mul are served too, else "TODO" for such a frame"""
 
-    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False):
+    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False):
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags | (SEQ_BLEND if blend else 0), C.byref(err))
+        self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags | (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0), C.byref(err))
         if not self.h:
             raise J40Error(err4(err.value), "in j40hip_sequence_open")
         self.num_frames, self.num_shown = int(L.j40hip_sequence_num_frames(self.h)), int(L.j40hip_sequence_num_shown(self.h))
@@ -981,12 +1001,13 @@ class Sequence:
         return err4(code), int(k.value)
 
 
-def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False):
+def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False):
     """every displayed frame of an animation or a layered still: ([(rgba ndarray [height, width, 4], duration in ticks), ...],
     (tps_num, tps_den, loops)). alpha=True: VarDCT frames keep their alpha channel (Frame.set_alpha(1); J40Error where that refuses).
     blend=True: frames with a blend mode other than Replace are composed too (Sequence's blend=), else such a frame raises "TODO".
+    wide=True: an image with 32-bit Modular buffers is served (Sequence's wide=; its Modular frames only).
     A frame that fails raises J40Error with its code. A stream whose first frame is its last is not a sequence ("Usq?"): decode()."""
-    seq = Sequence(data, blend=blend)
+    seq = Sequence(data, blend=blend, wide=wide)
     try:
         seq.set_output_format(fmt)
         if alpha:

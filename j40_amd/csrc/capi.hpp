@@ -21,6 +21,7 @@ struct j40hip_frame {
 	int alpha = -1;                  // the alpha channel of a VarDCT frame (j40hip_frame_set_alpha): -1 as J40HIP_ALPHA says, 0 dropped (A = 255, the reference's pixels), 1 kept
 	bool alpha_written = false;      // the last decode merged the alpha channel into its pixels
 	int ycbcr = -1;                  // YCbCr VarDCT frames (j40hip_frame_set_ycbcr): -1 as J40HIP_YCBCR says, 0 refused ("TODO", the reference's answer), 1 served
+	bool wide_used = false;          // the last decode ran the int32 instantiations of the Modular kernels (a wide frame, j40hip_frame_wide)
 	bool ycbcr_used = false;         // the last decode went through the YCbCr planes and k_ycbcr_tail
 	int32_t output_format = J40HIP_U8X4;   // what the decode entry points write (j40hip_frame_set_output_format): u8x4 or u16x4
 	// region decode (j40hip_frame_set_region): the rectangle the decode entry points write instead of the whole frame, and what the last

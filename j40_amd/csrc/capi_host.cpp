@@ -26,6 +26,7 @@ j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads,
 		h->frame.lf_only = (flags & J40HIP_PARSE_LF_ONLY) != 0;
 		h->frame.lf_decoder = lf_decoder; h->frame.lf_decoder_ctx = lf_ctx;
 		h->frame.allow_ycbcr = (flags & J40HIP_PARSE_YCBCR) != 0 || ycbcr_env();
+		h->frame.allow_wide = (flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
 		extract_codestream((const uint8_t *) buf, size, &h->cs, &h->cs_size, &h->cs_storage, &h->container_stray_tail);
 		h->bare_codestream = h->cs == (const uint8_t *) buf && h->cs_size == size;
 		parse_frame(h->cs, h->cs_size, &h->frame, threads);
@@ -55,6 +56,7 @@ j40hip_frame *j40hip_frame_parse_streamed(const void *buf, size_t size, int thre
 		h->frame.lf_only = (flags & J40HIP_PARSE_LF_ONLY) != 0;
 		h->frame.need_bytes = need; h->frame.have_bytes = have; h->frame.need_ctx = ctx;
 		h->frame.allow_ycbcr = (flags & J40HIP_PARSE_YCBCR) != 0 || ycbcr_env();
+		h->frame.allow_wide = (flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
 		h->cs = p; h->cs_size = size; h->bare_codestream = true;
 		parse_frame(h->cs, h->cs_size, &h->frame, threads);
 		h->threads = threads < 1 ? 1 : threads > 16 ? 16 : threads;
@@ -158,7 +160,7 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 		s->threads = threads < 1 ? 1 : threads > 16 ? 16 : threads; s->flags = flags;
 		s->blend = (flags & J40HIP_SEQ_BLEND) != 0 || env_on("J40HIP_BLEND", false);   // (looked at with every sequence that is opened)
 		size_t at = 0;
-		parse_image_header(s->cs, s->cs_size, &s->im, &at);
+		parse_image_header(s->cs, s->cs_size, &s->im, &at, (flags & J40HIP_PARSE_WIDE) != 0 || wide_env());
 		s->alpha_ec = rendered_alpha_channel(s->im);
 		for (;;) {
 			j40hip_sequence::Row row;
@@ -252,7 +254,7 @@ j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err
 		h->cs = h->cs_storage.data();
 		h->bare_codestream = true;
 		h->frame.defer_lf_tail = (s->flags & 1u) != 0;
-		h->frame.seq_im = &s->im; h->frame.seq_blend = s->blend;
+		h->frame.seq_im = &s->im; h->frame.seq_blend = s->blend; h->frame.allow_wide = (s->flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
 		parse_frame(h->cs, h->cs_size, &h->frame, s->threads);
 		h->threads = s->threads;
 		h->output_format = s->output_format;
@@ -727,6 +729,7 @@ int32_t j40hip_frame_split_sections(j40hip_frame *h) {
 
 uint32_t j40hip_frame_modular_view(j40hip_frame *h, j40hip_modular_view *v) {
 	HostModPlan hp;
+	if (h->frame.wide()) return E4("TODO");   // (the view describes int16 planes: a wide frame's plan has no view)
 	if (uint32_t e = build_modular_plan(h->frame, h->cs, h->cs_size, &hp)) return e;
 	finish_lf_tail(&h->frame);
 	const Frame &f = h->frame;

@@ -79,22 +79,24 @@ uint32_t pack_lf_row_waves(const DevLfLaneSet *sets_host, int32_t num_sets, std:
 void launch_lf_rows(const DevLfLaneSet *sets, const DevLfWave *waves, int32_t num_waves, uint32_t lds_bytes, hipStream_t stream, hipEvent_t started = nullptr, hipEvent_t stopped = nullptr);
 void launch_modular_quad(const DevModPlan &plan, int32_t first_section, int32_t num_sections, int32_t spec_idx, uint32_t table_span, int32_t max_width, hipStream_t stream);
 void launch_modular_split(const DevModPlan &plan, int32_t first_section, int32_t num_sections, const ModLaunchInfo &info, hipStream_t stream);
-void launch_modular_coop(const DevModPlan &plan, int32_t first_section, int32_t num_sections, int32_t max_width, hipStream_t stream);
-void launch_section_inverse_rcts(const DevModPlan &plan, int32_t first_section, int32_t num_sections, hipStream_t stream);
-void launch_paste_plane(const int16_t *src, int32_t w, int32_t h, int16_t *dst, int32_t dst_stride, hipStream_t stream);
-void launch_inverse_rct(int16_t *a, int16_t *b, int16_t *c, size_t n, int32_t type7, hipStream_t stream);
-void launch_inverse_palette_plain(const int16_t *idx, const int16_t *palrow, int16_t *dst, size_t n, int32_t i, int32_t nb_colours, int32_t bpp, hipStream_t stream);
-void launch_inverse_palette_predicted(const int16_t *idx, const int16_t *pal, int32_t pal_stride, int16_t *const *dst_dev, int32_t num_c, int32_t width, int32_t height,
+void launch_modular_coop(const DevModPlan &plan, int32_t first_section, int32_t num_sections, int32_t max_width, hipStream_t stream, bool wide = false);
+// the planes arrive as PlanePtr (plan.h): address + bytes per sample; planes of one call have the same sample size, which picks the instantiation
+void launch_section_inverse_rcts(const DevModPlan &plan, int32_t first_section, int32_t num_sections, hipStream_t stream, bool wide = false);
+void launch_paste_plane(PlanePtr src, int32_t w, int32_t h, PlanePtr dst, int32_t dst_stride, hipStream_t stream);
+void launch_inverse_rct(PlanePtr a, PlanePtr b, PlanePtr c, size_t n, int32_t type7, hipStream_t stream);
+void launch_inverse_palette_plain(PlanePtr idx, PlanePtr palrow, PlanePtr dst, size_t n, int32_t i, int32_t nb_colours, int32_t bpp, hipStream_t stream);
+void launch_inverse_palette_predicted(PlanePtr idx, PlanePtr pal, int32_t pal_stride, void *const *dst_dev, int32_t num_c, int32_t width, int32_t height,
 		int32_t nb_colours, int32_t nb_deltas, int32_t d_pred, int32_t bpp, const int8_t *wpp_dev, int32_t *wp_scratch, uint32_t *status, hipStream_t stream);
-void launch_inverse_squeeze(const int16_t *avg, const int16_t *res, int16_t *out, int32_t aw, int32_t ah, int32_t rw, int32_t rh, bool horizontal, hipStream_t stream);
-void launch_pack_planes_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
+void launch_inverse_squeeze(PlanePtr avg, PlanePtr res, PlanePtr out, int32_t aw, int32_t ah, int32_t rw, int32_t rh, bool horizontal, hipStream_t stream);
+// a: a null address where the frame has no alpha plane
+void launch_pack_planes_rect(PlanePtr r, PlanePtr g, PlanePtr b, PlanePtr a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
 // alpha_kernels.hip: the kept alpha channel of a VarDCT frame into rectangle (x0, y0, w, h) of pixels already written
 void launch_alpha_merge(const int16_t *plane, int32_t pitch, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16);
 // ycbcr_kernels.hip: the three float planes of a YCbCr VarDCT frame (ycbcr_dev.h: YcbcrTail) to the picture's width x height pixels
 struct YcbcrTail;
 void launch_ycbcr_tail(const YcbcrTail &t, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16);
 // shift: the scale shift; 1, 2: ceil(width / s) x ceil(height / s) pixels, each the mean of its cell's rendered samples (scale_dev.h)
-void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false, int32_t shift = 0);
+void launch_pack_planes(PlanePtr r, PlanePtr g, PlanePtr b, PlanePtr a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false, int32_t shift = 0);
 
 // reduced-size decode (device/scale_kernels.hip, scale_dev.h): the full W x H image at src made 1:2 (shift 1) or 1:4 (shift 2) at dst,
 // pixel_bytes 4 or 8, every row pixel-aligned

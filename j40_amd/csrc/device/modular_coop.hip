@@ -24,6 +24,7 @@
 
 namespace j40hip {
 
+template <typename S>
 __global__ void __launch_bounds__(64) k_modular_coop(DevModPlan plan, int32_t first_section, int32_t rows_width) {
 	extern __shared__ int32_t coop_rows[];   // [3][rows_width]: the three most recent rows of the channel being decoded
 	const uint32_t lane = threadIdx.x;
@@ -43,7 +44,7 @@ __global__ void __launch_bounds__(64) k_modular_coop(DevModPlan plan, int32_t fi
 	uint32_t state = 0, err = 0;
 
 	for (int32_t cidx = 0; cidx < num_channels && !b.err && !err; ++cidx) {
-		const ModChan chan = mod_channel(plan, sec, cidx);
+		const ModChanT<S> chan = mod_channel<S>(plan, sec, cidx);
 		const int32_t stride = coop_sc(chan.stride), gw = coop_sc(chan.gw), gh = coop_sc(chan.gh);
 		if (gw <= 0 || gh <= 0) continue;
 		coop_decode_channel(b, state, err, t, alias, log_bucket, cidx, sidx, coop_sc_ptr(chan.base), stride, gw, gh, coop_rows, rows_width, lane);
@@ -60,10 +61,11 @@ __global__ void __launch_bounds__(64) k_modular_coop(DevModPlan plan, int32_t fi
 	if (lane == 0) plan.status[s] = status;
 }
 
-void launch_modular_coop(const DevModPlan &plan, int32_t first_section, int32_t num_sections, int32_t max_width, hipStream_t stream) {
+void launch_modular_coop(const DevModPlan &plan, int32_t first_section, int32_t num_sections, int32_t max_width, hipStream_t stream, bool wide) {
 	if (num_sections <= 0) return;
 	const int32_t rows_width = ((max_width + 63) & ~63) + 64;
-	hipLaunchKernelGGL(k_modular_coop, dim3((unsigned) num_sections), dim3(64), (size_t) rows_width * 12, stream, plan, first_section, rows_width);
+	if (wide) hipLaunchKernelGGL(k_modular_coop<int32_t>, dim3((unsigned) num_sections), dim3(64), (size_t) rows_width * 12, stream, plan, first_section, rows_width);
+	else hipLaunchKernelGGL(k_modular_coop<int16_t>, dim3((unsigned) num_sections), dim3(64), (size_t) rows_width * 12, stream, plan, first_section, rows_width);
 }
 
 } // namespace j40hip

@@ -60,7 +60,8 @@ J40_DEV uint32_t coop_take(CoopBits &b, int32_t n, uint32_t lane) {   // n in [0
 	return v;
 }
 
-J40_DEV int32_t coop_predict(int32_t predictor, int32_t w, int32_t n, int32_t nw, int32_t ne, int32_t nn, int32_t nee, int32_t ww) {  // j40.h:4080
+template <typename T>   // T: int32_t, or int64_t where the samples are a wide frame's
+J40_DEV T coop_predict(int32_t predictor, T w, T n, T nw, T ne, T nn, T nee, T ww) {  // j40.h:4080
 	switch (predictor) {
 	case 0: return 0;
 	case 1: return w;
@@ -99,15 +100,18 @@ J40_DEV CoopTreeRegs coop_load_tree(const DevCoopTree *tree, uint32_t lane) {
 // is wave-uniform. PLANE_ROWS: the two rows above are read back from the output plane (coalesced
 // 128-byte pieces, once per 64 samples) instead of an LDS ring -- for channels too wide for LDS (the varblock-info channel of an
 // LfGroup is two rows of up to 65536 samples); coop_rows is then unused.
-template <bool PLANE_ROWS = false>
+// S: the plane's sample type. int32_t (a wide frame): the rows in LDS and in registers are 32-bit either way; the property values,
+// the prediction and the sum that becomes the sample take 64 bits, the sample must fit int32, and the store is 256 bytes per 64.
+template <bool PLANE_ROWS = false, typename S = int16_t>
 J40_DEV void coop_decode_channel(CoopBits &b, uint32_t &state, uint32_t &err, const CoopTreeRegs &t, CoopConstU64 alias, int32_t log_bucket,
-		int32_t cidx, int32_t sidx, int16_t *base, int32_t stride, int32_t gw, int32_t gh, int32_t *coop_rows, int32_t rows_width, uint32_t lane) {
+		int32_t cidx, int32_t sidx, S *base, int32_t stride, int32_t gw, int32_t gh, int32_t *coop_rows, int32_t rows_width, uint32_t lane) {
+	typedef typename ModWideOf<S>::type V;
 	const uint32_t used = t.used;
 	for (int32_t y = 0; y < gh && !b.err && !err; ++y) {
-		int16_t *row = base + (size_t) y * (size_t) stride;
+		S *row = base + (size_t) y * (size_t) stride;
 		int32_t *cur = coop_rows + (y % 3) * rows_width;
 		const int32_t *prev = coop_rows + ((y + 2) % 3) * rows_width, *pprev = coop_rows + ((y + 1) % 3) * rows_width;
-		const int16_t *prow = row - stride, *pprow = row - 2 * (size_t) stride;   // PLANE_ROWS (only read where they exist)
+		const S *prow = row - stride, *pprow = row - 2 * (size_t) stride;   // PLANE_ROWS (only read where they exist)
 		auto above = [&](int32_t x0) { const int32_t k = x0 + (int32_t) lane; return PLANE_ROWS ? (y > 0 && k < gw ? (int32_t) prow[k] : 0) : prev[k]; };
 		auto above2 = [&](int32_t x0) { const int32_t k = x0 + (int32_t) lane; return PLANE_ROWS ? (y > 1 && k < gw ? (int32_t) pprow[k] : 0) : pprev[k]; };
 		// the row above, 64 samples per register: vprev = columns xb .. xb + 63, vprev2 = the 64 behind them (NEE and the
@@ -137,8 +141,8 @@ J40_DEV void coop_decode_channel(CoopBits &b, uint32_t &state, uint32_t &err, co
 				const int32_t pww = x > 1 ? c_ww : pw;
 				const int32_t pnww = x > 1 && y > 0 ? r_nww : pww;
 				// every branch's outcome: the value of the property this lane's node tests (j40.h:4141-4155), then one compare
-				const int32_t qx = x, qw = pw, qn = pn, qnw = pnw, qne = pne, qnn = pnn, qww = pww, qnww = pnww;
-				int32_t myval = 0;
+				const int32_t qx = x; const V qw = pw, qn = pn, qnw = pnw, qne = pne, qnn = pnn, qww = pww, qnww = pnww;
+				V myval = 0;
 				if (used & (1u << 0)) myval = t.my_prop == 0 ? cidx : myval;
 				if (used & (1u << 1)) myval = t.my_prop == 1 ? sidx : myval;
 				if (used & (1u << 2)) myval = t.my_prop == 2 ? y : myval;
@@ -182,14 +186,20 @@ J40_DEV void coop_decode_channel(CoopBits &b, uint32_t &state, uint32_t &err, co
 					const int32_t lo = token & ((1 << lsb) - 1), hi = (token >> lsb) & (top - 1);
 					v = ((top | hi) << (midbits + lsb)) | ((mid << lsb) | lo);
 				}
+				if (sizeof(S) == 4) {   // (modular_dev.h, decode_modular_section: the same sum in 64 bits, `povf` outside int32)
+					const int64_t sum = (int64_t) ((v & 1) ? -(v / 2 + 1) : v / 2) * mul + off + (int64_t) coop_predict<V>((int32_t) (la & 15), qw, qn, qnw, qne, qnn, (V) pnee, qww);
+					if (sum < INT32_MIN || sum > INT32_MAX) { err = ERR_POVF; break; }
+					v = (int32_t) sum;
+				} else {
 				v = ((v & 1) ? -(v / 2 + 1) : v / 2) * mul + off;
-				v += coop_predict((int32_t) (la & 15), pw, pn, pnw, pne, pnn, pnee, pww);
+				v += coop_predict<int32_t>((int32_t) (la & 15), pw, pn, pnw, pne, pnn, pnee, pww);
 				if (v < -32768 || v > 32767) { err = ERR_POVF; break; }
+				}
 				vout = (int32_t) lane == i ? v : vout;
 				c_ww = c_w; c_w = v; r_nww = r_nw; r_nw = r_n; r_n = r_ne; r_ne = r_nee; r_nee = r_next;
 				if (b.err) break;
 			}
-			if ((int32_t) lane < nblk) { if (!PLANE_ROWS) cur[xb + (int32_t) lane] = vout; row[xb + (int32_t) lane] = (int16_t) vout; }
+			if ((int32_t) lane < nblk) { if (!PLANE_ROWS) cur[xb + (int32_t) lane] = vout; row[xb + (int32_t) lane] = (S) vout; }
 		}
 	}
 }

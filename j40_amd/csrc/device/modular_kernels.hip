@@ -27,7 +27,8 @@ namespace j40hip {
 // template keeps their address space static, a run-time choice would turn every access into a flat one), so the tree
 // walk, the symbol decode and the neighbour fetch wait on LDS instead of L2 -- a sample that was just stored to the plane is
 // not in the vector L1, and the previous pixel is the next one's W neighbour.
-template <bool IN_LDS>
+// S: the planes' sample type (modular_dev.h); the wide form's weighted-predictor rows are 64-bit cells (wp_width counts samples)
+template <bool IN_LDS, typename S = int16_t>
 __global__ void __launch_bounds__(64) k_modular_sections(DevModPlan plan, int32_t first_section, int32_t rows_width, int32_t wp_width) {
 	extern __shared__ __attribute__((aligned(16))) uint8_t mod_lds[];
 	const int32_t lane = threadIdx.x;
@@ -59,64 +60,70 @@ __global__ void __launch_bounds__(64) k_modular_sections(DevModPlan plan, int32_
 		if (wp_width) { t.wp_errors = l_wp; t.wp_errors_width = wp_width; }
 		__syncthreads();
 	}
-	const uint32_t err = decode_modular_section<true, IN_LDS>(plan, t, s);
+	const uint32_t err = decode_modular_section<true, IN_LDS, S>(plan, t, s);
 	if (lane == 0) plan.status[s] = err;
 }
 
 // one workgroup per section that lists transforms of its own; runs after K3 (kernel boundary = the planes are visible)
+template <typename S>
 __global__ void __launch_bounds__(256) k_section_inverse_rcts(DevModPlan plan, int32_t first_section) {
-	section_inverse_rcts(plan, first_section + (int32_t) blockIdx.x, (int32_t) threadIdx.x, 256);
+	section_inverse_rcts<S>(plan, first_section + (int32_t) blockIdx.x, (int32_t) threadIdx.x, 256);
 }
 
 // rows of a tightly packed sub-image plane over a rectangle of a frame plane (j40__combine_modular_from_pass_group, j40.h:3688)
-__global__ void __launch_bounds__(256) k_paste_plane(const int16_t *src, int32_t w, size_t n, int16_t *dst, int32_t dst_stride) {
+template <typename S>
+__global__ void __launch_bounds__(256) k_paste_plane(const S *src, int32_t w, size_t n, S *dst, int32_t dst_stride) {
 	for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x) {
 		const size_t y = i / (size_t) w, x = i - y * (size_t) w;
 		dst[y * (size_t) dst_stride + x] = src[i];
 	}
 }
 
-__global__ void __launch_bounds__(256) k_inverse_rct(int16_t *a, int16_t *b, int16_t *c, size_t n, int32_t type7) {
+template <typename S>
+__global__ void __launch_bounds__(256) k_inverse_rct(S *a, S *b, S *c, size_t n, int32_t type7) {
 	for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x) {
-		int16_t p0 = a[i], p1 = b[i], p2 = c[i];
+		S p0 = a[i], p1 = b[i], p2 = c[i];
 		inverse_rct_pixel(type7, p0, p1, p2);
 		a[i] = p0; b[i] = p1; c[i] = p2;
 	}
 }
 
 // output channel i of a palette without delta prediction; dst may alias idx (last channel, in place)
-__global__ void __launch_bounds__(256) k_inverse_palette_plain(const int16_t *idx, const int16_t *palrow, int16_t *dst, size_t n, int32_t i, int32_t nb_colours, int32_t bpp) {
+template <typename S>
+__global__ void __launch_bounds__(256) k_inverse_palette_plain(const S *idx, const S *palrow, S *dst, size_t n, int32_t i, int32_t nb_colours, int32_t bpp) {
 	for (size_t k = (size_t) blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t) gridDim.x * blockDim.x)
 		dst[k] = palette_value(idx[k], i, palrow, nb_colours, bpp);
 }
 
 // palette with delta prediction: a delta entry is added to a prediction from already reconstructed
 // neighbours of the same output channel, which makes the channel strictly sequential (j40.h:4469-4476)
-__global__ void __launch_bounds__(64) k_inverse_palette_predicted(const int16_t *idx, const int16_t *pal, int32_t pal_stride, int16_t *const *dst, int32_t num_c,
+template <typename S>
+__global__ void __launch_bounds__(64) k_inverse_palette_predicted(const S *idx, const S *pal, int32_t pal_stride, S *const *dst, int32_t num_c,
 		int32_t width, int32_t height, int32_t nb_colours, int32_t nb_deltas, int32_t d_pred, int32_t bpp, const int8_t *wpp, int32_t *wp_scratch, uint32_t *status) {
 	if (threadIdx.x != 0 || blockIdx.x != 0) return;
-	ModWP wp;
-	wp.on = d_pred == 6; wp.width = width; wp.errors = wp_scratch;
+	typedef typename ModWideOf<S>::type E;
+	ModWPT<E> wp;
+	wp.on = d_pred == 6; wp.width = width; wp.errors = (E *) wp_scratch;
 	wp.p1 = wpp[0]; wp.p2 = wpp[1];
 	for (int i = 0; i < 5; ++i) wp.p3[i] = wpp[2 + i];
 	for (int i = 0; i < 4; ++i) wp.w[i] = wpp[7 + i];
 	uint32_t err = 0;
 	for (int32_t i = 0; i < num_c; ++i) {
-		const int16_t *palrow = nb_colours > 0 ? pal + (size_t) i * (size_t) pal_stride : nullptr;
-		int16_t *out = dst[i];
+		const S *palrow = nb_colours > 0 ? pal + (size_t) i * (size_t) pal_stride : nullptr;
+		S *out = dst[i];
 		if (wp.on) for (int32_t k = 0; k < 2 * width * 5; ++k) wp.errors[k] = 0;
 		for (int k = 0; k < 5; ++k) wp.pred[k] = 0;
 		wp.blend_err_w = wp.blend_err_n = wp.blend_err_nw = wp.blend_err_ne = 0;
 		for (int32_t y = 0; y < height; ++y) {
-			const int16_t *idxline = idx + (size_t) y * (size_t) width;
-			int16_t *line = out + (size_t) y * (size_t) width;
+			const S *idxline = idx + (size_t) y * (size_t) width;
+			S *line = out + (size_t) y * (size_t) width;
 			for (int32_t x = 0; x < width; ++x) {
-				const int16_t index = idxline[x];
+				const S index = idxline[x];
 				const bool is_delta = index < nb_deltas;
-				int16_t val = palette_value(index, i, palrow, nb_colours, bpp);
+				S val = palette_value(index, i, palrow, nb_colours, bpp);
 				const ModNeigh p = mod_neighbours<false>(line, width, width, x, y);
 				wp_before<false>(wp, x, y, p);
-				if (is_delta) val = (int16_t) (val + mod_predict(d_pred, wp, p, &err));
+				if (is_delta) val = (S) (uint32_t) (uint64_t) (val + mod_predict(d_pred, wp, p, &err));   // (wraps to the sample type)
 				wp_after(wp, x, y, val);
 				line[x] = val;
 			}
@@ -130,20 +137,24 @@ __global__ void __launch_bounds__(64) k_inverse_palette_predicted(const int16_t 
 // in dwords: a lane walking its own row hits its own bank), each lane runs the recurrence over its row's piece, and the
 // 2 * SQZ_CHUNK results per row go out as two coalesced 128-byte writes. `left` (the sample before the pair) stays in a register.
 enum { SQZ_CHUNK = 64 };
-__global__ void __launch_bounds__(64) k_unsqueeze_h(const int16_t *__restrict__ avg, const int16_t *__restrict__ res, int16_t *__restrict__ out, int32_t aw, int32_t ah, int32_t rw) {
-	__shared__ int16_t s_avg[64][SQZ_CHUNK + 2], s_res[64][SQZ_CHUNK + 2], s_out[64][2 * SQZ_CHUNK + 2];
-	const int32_t lane = threadIdx.x, y0 = (int32_t) blockIdx.x * 64, rows = min(64, ah - y0), ow = aw + rw;
+template <typename S> constexpr int SQZ_ROWS = sizeof(S) == 2 ? 64 : 32;   // rows a wavefront takes
+template <typename S>
+__global__ void __launch_bounds__(64) k_unsqueeze_h(const S *__restrict__ avg, const S *__restrict__ res, S *__restrict__ out, int32_t aw, int32_t ah, int32_t rw) {
+	// (the staging is sized from the sample: 64 rows of int16, 32 rows of int32 -- 33 KB either way; the pitch stays odd in dwords)
+	constexpr int PAD = sizeof(S) == 2 ? 2 : 1, ROWS = SQZ_ROWS<S>;
+	__shared__ S s_avg[ROWS][SQZ_CHUNK + PAD], s_res[ROWS][SQZ_CHUNK + PAD], s_out[ROWS][2 * SQZ_CHUNK + PAD];
+	const int32_t lane = threadIdx.x, y0 = (int32_t) blockIdx.x * ROWS, rows = min(ROWS, ah - y0), ow = aw + rw;
 	int32_t left = 0;
 	for (int32_t x0 = 0; x0 < aw; x0 += SQZ_CHUNK) {
 		for (int32_t r0 = 0; r0 < rows; r0 += 8) {   // eight rows' requests in flight before the first one is waited for
-			int16_t va[8], vr[8], ve[8];
+			S va[8], vr[8], ve[8];
 #pragma unroll
 			for (int j = 0; j < 8; ++j) {
 				const int32_t r = min(r0 + j, rows - 1);
 				const size_t ra = (size_t) (y0 + r) * (size_t) aw, rr = (size_t) (y0 + r) * (size_t) rw;
-				va[j] = x0 + lane < aw ? avg[ra + (size_t) (x0 + lane)] : (int16_t) 0;
-				ve[j] = lane == 0 && x0 + SQZ_CHUNK < aw ? avg[ra + (size_t) (x0 + SQZ_CHUNK)] : (int16_t) 0;
-				vr[j] = x0 + lane < rw ? res[rr + (size_t) (x0 + lane)] : (int16_t) 0;
+				va[j] = x0 + lane < aw ? avg[ra + (size_t) (x0 + lane)] : (S) 0;
+				ve[j] = lane == 0 && x0 + SQZ_CHUNK < aw ? avg[ra + (size_t) (x0 + SQZ_CHUNK)] : (S) 0;
+				vr[j] = x0 + lane < rw ? res[rr + (size_t) (x0 + lane)] : (S) 0;
 			}
 #pragma unroll
 			for (int j = 0; j < 8; ++j) if (r0 + j < rows) {
@@ -159,8 +170,8 @@ __global__ void __launch_bounds__(64) k_unsqueeze_h(const int16_t *__restrict__ 
 				const int32_t a = s_avg[lane][k], next = x0 + k + 1 < aw ? (int32_t) s_avg[lane][k + 1] : a;
 				int32_t p, q;
 				unsqueeze_pair(a, s_res[lane][k], x0 + k > 0 ? left : a, next, &p, &q);
-				s_out[lane][2 * k] = (int16_t) p; s_out[lane][2 * k + 1] = (int16_t) q;
-				left = (int16_t) q;
+				s_out[lane][2 * k] = (S) p; s_out[lane][2 * k + 1] = (S) q;
+				left = (S) q;
 			}
 			if (aw > rw && aw - 1 >= x0 && aw - 1 < x0 + SQZ_CHUNK) s_out[lane][2 * (aw - 1 - x0)] = s_avg[lane][aw - 1 - x0];   // odd width: the last average passes through
 		}
@@ -178,7 +189,8 @@ __global__ void __launch_bounds__(64) k_unsqueeze_h(const int16_t *__restrict__ 
 // recurrence runs down the column; its inputs do not depend on it, so they are requested SQZ_AHEAD rows ahead of their use (a
 // column of 8192 pairs would otherwise wait for memory 8192 times)
 enum { SQZ_AHEAD = 8 };
-__global__ void __launch_bounds__(256) k_unsqueeze_v(const int16_t *__restrict__ avg, const int16_t *__restrict__ res, int16_t *__restrict__ out, int32_t aw, int32_t ah, int32_t rh) {
+template <typename S>
+__global__ void __launch_bounds__(256) k_unsqueeze_v(const S *__restrict__ avg, const S *__restrict__ res, S *__restrict__ out, int32_t aw, int32_t ah, int32_t rh) {
 	const int32_t x = (int32_t) (blockIdx.x * blockDim.x + threadIdx.x);
 	if (x >= aw) return;
 	const size_t pitch = (size_t) aw;
@@ -196,8 +208,8 @@ __global__ void __launch_bounds__(256) k_unsqueeze_v(const int16_t *__restrict__
 				const int32_t a = a_q[j], next = k + 1 < ah ? a_q[j + 1] : a;
 				int32_t p, q;
 				unsqueeze_pair(a, r_q[j], k > 0 ? left : a, next, &p, &q);
-				out[(size_t) (2 * k) * pitch + (size_t) x] = (int16_t) p; out[(size_t) (2 * k + 1) * pitch + (size_t) x] = (int16_t) q;
-				left = (int16_t) q;
+				out[(size_t) (2 * k) * pitch + (size_t) x] = (S) p; out[(size_t) (2 * k + 1) * pitch + (size_t) x] = (S) q;
+				left = (S) q;
 			}
 		}
 	}
@@ -206,8 +218,8 @@ __global__ void __launch_bounds__(256) k_unsqueeze_v(const int16_t *__restrict__
 
 // K: the scale shift (scale_dev.h). K > 0: a lane per OUTPUT pixel renders each sample of its cell (clamp, then the 8-bit rule) and stores
 // the mean of the rendered pixels -- no full-size RGBA is written. K = 0 is the kernel it always was.
-template <int K>
-__global__ void __launch_bounds__(256) k_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
+template <int K, typename S>
+__global__ void __launch_bounds__(256) k_pack_planes(const S *r, const S *g, const S *b, const S *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
 	const size_t n = (size_t) width * (size_t) height;
 	const int32_t opaque = (1 << bpp) - 1;
 	if constexpr (K > 0) {
@@ -231,7 +243,8 @@ __global__ void __launch_bounds__(256) k_pack_planes(const int16_t *r, const int
 }
 
 // the same over one rectangle of the picture (a group range's, sharded decodes): planes are `plane_width` samples wide
-__global__ void __launch_bounds__(256) k_pack_planes_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
+template <typename S>
+__global__ void __launch_bounds__(256) k_pack_planes_rect(const S *r, const S *g, const S *b, const S *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
 	const size_t n = (size_t) rw * (size_t) rh;
 	const int32_t opaque = (1 << bpp) - 1;
 	for (size_t k = (size_t) blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t) gridDim.x * blockDim.x) {
@@ -241,8 +254,8 @@ __global__ void __launch_bounds__(256) k_pack_planes_rect(const int16_t *r, cons
 }
 
 // the 16-bit forms (J40_U16X4): pack_rgba16, 8 bytes a pixel as one store; alpha without a plane: 65535
-template <int K>
-__global__ void __launch_bounds__(256) k_pack_planes16(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
+template <int K, typename S>
+__global__ void __launch_bounds__(256) k_pack_planes16(const S *r, const S *g, const S *b, const S *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
 	const size_t n = (size_t) width * (size_t) height;
 	const int32_t opaque = (1 << bpp) - 1;
 	if constexpr (K > 0) {   // (k_pack_planes)
@@ -264,7 +277,8 @@ __global__ void __launch_bounds__(256) k_pack_planes16(const int16_t *r, const i
 		__builtin_nontemporal_store(pack_rgba16(r[i], g[i], b[i], a ? a[i] : opaque, bpp), (uint64_t *) (rgba + y * stride_bytes + x * 8));
 	}
 }
-__global__ void __launch_bounds__(256) k_pack_planes16_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
+template <typename S>
+__global__ void __launch_bounds__(256) k_pack_planes16_rect(const S *r, const S *g, const S *b, const S *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
 	const size_t n = (size_t) rw * (size_t) rh;
 	const int32_t opaque = (1 << bpp) - 1;
 	for (size_t k = (size_t) blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t) gridDim.x * blockDim.x) {
@@ -276,65 +290,94 @@ __global__ void __launch_bounds__(256) k_pack_planes16_rect(const int16_t *r, co
 static unsigned grid_for(size_t n) { size_t b = (n + 255) / 256; return (unsigned) (b < 1 ? 1 : b > 8192 ? 8192 : b); }
 
 // sections [first_section, first_section + num_sections): the passes of a multi-pass frame are launched one after the other
-void launch_modular_sections(const DevModPlan &plan, int32_t first_section, int32_t num_sections, const ModLaunchInfo &info, hipStream_t stream) {
-	if (num_sections <= 0) return;
-	// the sections the wave-cooperative kernel takes (modular_coop.hip), then the others
-	if (info.quad_sections > 0) launch_modular_quad(plan, first_section, num_sections, info.quad_spec, info.quad_table_span, info.quad_width, stream);
-	if (info.coop_width > 0 && info.quad_sections < info.coop_sections) launch_modular_coop(plan, first_section, num_sections, info.coop_width, stream);
-	if (info.split_sections > 0) launch_modular_split(plan, first_section, num_sections, info, stream);   // (sections with a position-only tree: modular_split.hip)
-	if (info.all_coop) return;
+template <typename S>
+static void launch_sections_of(const DevModPlan &plan, int32_t first_section, int32_t num_sections, const ModLaunchInfo &info, hipStream_t stream) {
 	auto align16 = [](uint32_t v) { return (v + 15u) & ~15u; };
-	const uint32_t wp_bytes = info.uses_wp ? align16(40u * (uint32_t) info.max_width) : 0;
+	const uint32_t wp_bytes = info.uses_wp ? align16((sizeof(S) == 4 ? 80u : 40u) * (uint32_t) info.max_width) : 0;
 	const uint32_t lds = align16((uint32_t) info.num_tree_nodes * (uint32_t) sizeof(DevTreeNode)) + align16((uint32_t) info.num_dist + 4)
 		+ align16((uint32_t) info.num_clusters * (uint32_t) sizeof(DevCluster)) + align16(info.table_bytes) + align16(12u * (uint32_t) (info.max_width + 4)) + wp_bytes + 64;
 	if (lds <= 156u * 1024u) {
 		static bool configured = false;
-		if (!configured) { (void) hipFuncSetAttribute((const void *) k_modular_sections<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); configured = true; }
-		hipLaunchKernelGGL(k_modular_sections<true>, dim3((unsigned) num_sections), dim3(64), lds, stream, plan, first_section, info.max_width + 4, info.uses_wp ? info.max_width : 0);
+		if (!configured) { (void) hipFuncSetAttribute((const void *) k_modular_sections<true, S>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); configured = true; }
+		hipLaunchKernelGGL((k_modular_sections<true, S>), dim3((unsigned) num_sections), dim3(64), lds, stream, plan, first_section, info.max_width + 4, info.uses_wp ? info.max_width : 0);
 	} else {
-		hipLaunchKernelGGL(k_modular_sections<false>, dim3((unsigned) num_sections), dim3(64), 0, stream, plan, first_section, 0, 0);
+		hipLaunchKernelGGL((k_modular_sections<false, S>), dim3((unsigned) num_sections), dim3(64), 0, stream, plan, first_section, 0, 0);
 	}
 }
-void launch_section_inverse_rcts(const DevModPlan &plan, int32_t first_section, int32_t num_sections, hipStream_t stream) {
-	if (num_sections > 0) hipLaunchKernelGGL(k_section_inverse_rcts, dim3((unsigned) num_sections), dim3(256), 0, stream, plan, first_section);
+void launch_modular_sections(const DevModPlan &plan, int32_t first_section, int32_t num_sections, const ModLaunchInfo &info, hipStream_t stream) {
+	if (num_sections <= 0) return;
+	// the sections the wave-cooperative kernel takes (modular_coop.hip), then the others
+	if (info.quad_sections > 0) launch_modular_quad(plan, first_section, num_sections, info.quad_spec, info.quad_table_span, info.quad_width, stream);
+	if (info.coop_width > 0 && info.quad_sections < info.coop_sections) launch_modular_coop(plan, first_section, num_sections, info.coop_width, stream, info.wide != 0);
+	if (info.split_sections > 0) launch_modular_split(plan, first_section, num_sections, info, stream);   // (sections with a position-only tree: modular_split.hip)
+	if (info.all_coop) return;
+	if (info.wide) launch_sections_of<int32_t>(plan, first_section, num_sections, info, stream);
+	else launch_sections_of<int16_t>(plan, first_section, num_sections, info, stream);
 }
-void launch_paste_plane(const int16_t *src, int32_t w, int32_t h, int16_t *dst, int32_t dst_stride, hipStream_t stream) {
+void launch_section_inverse_rcts(const DevModPlan &plan, int32_t first_section, int32_t num_sections, hipStream_t stream, bool wide) {
+	if (num_sections <= 0) return;
+	if (wide) hipLaunchKernelGGL(k_section_inverse_rcts<int32_t>, dim3((unsigned) num_sections), dim3(256), 0, stream, plan, first_section);
+	else hipLaunchKernelGGL(k_section_inverse_rcts<int16_t>, dim3((unsigned) num_sections), dim3(256), 0, stream, plan, first_section);
+}
+void launch_paste_plane(PlanePtr src, int32_t w, int32_t h, PlanePtr dst, int32_t dst_stride, hipStream_t stream) {
 	const size_t n = (size_t) w * (size_t) h;
-	if (n) hipLaunchKernelGGL(k_paste_plane, dim3(grid_for(n)), dim3(256), 0, stream, src, w, n, dst, dst_stride);
+	if (!n) return;
+	if (dst.wide()) hipLaunchKernelGGL(k_paste_plane<int32_t>, dim3(grid_for(n)), dim3(256), 0, stream, (const int32_t *) src.p, w, n, (int32_t *) dst.p, dst_stride);
+	else hipLaunchKernelGGL(k_paste_plane<int16_t>, dim3(grid_for(n)), dim3(256), 0, stream, (const int16_t *) src.p, w, n, (int16_t *) dst.p, dst_stride);
 }
-void launch_inverse_rct(int16_t *a, int16_t *b, int16_t *c, size_t n, int32_t type7, hipStream_t stream) {
-	if (n) hipLaunchKernelGGL(k_inverse_rct, dim3(grid_for(n)), dim3(256), 0, stream, a, b, c, n, type7);
+void launch_inverse_rct(PlanePtr a, PlanePtr b, PlanePtr c, size_t n, int32_t type7, hipStream_t stream) {
+	if (!n) return;
+	if (a.wide()) hipLaunchKernelGGL(k_inverse_rct<int32_t>, dim3(grid_for(n)), dim3(256), 0, stream, (int32_t *) a.p, (int32_t *) b.p, (int32_t *) c.p, n, type7);
+	else hipLaunchKernelGGL(k_inverse_rct<int16_t>, dim3(grid_for(n)), dim3(256), 0, stream, (int16_t *) a.p, (int16_t *) b.p, (int16_t *) c.p, n, type7);
 }
-void launch_inverse_palette_plain(const int16_t *idx, const int16_t *palrow, int16_t *dst, size_t n, int32_t i, int32_t nb_colours, int32_t bpp, hipStream_t stream) {
-	if (n) hipLaunchKernelGGL(k_inverse_palette_plain, dim3(grid_for(n)), dim3(256), 0, stream, idx, palrow, dst, n, i, nb_colours, bpp);
+void launch_inverse_palette_plain(PlanePtr idx, PlanePtr palrow, PlanePtr dst, size_t n, int32_t i, int32_t nb_colours, int32_t bpp, hipStream_t stream) {
+	if (!n) return;
+	if (dst.wide()) hipLaunchKernelGGL(k_inverse_palette_plain<int32_t>, dim3(grid_for(n)), dim3(256), 0, stream, (const int32_t *) idx.p, (const int32_t *) palrow.p, (int32_t *) dst.p, n, i, nb_colours, bpp);
+	else hipLaunchKernelGGL(k_inverse_palette_plain<int16_t>, dim3(grid_for(n)), dim3(256), 0, stream, (const int16_t *) idx.p, (const int16_t *) palrow.p, (int16_t *) dst.p, n, i, nb_colours, bpp);
 }
-void launch_inverse_palette_predicted(const int16_t *idx, const int16_t *pal, int32_t pal_stride, int16_t *const *dst_dev, int32_t num_c, int32_t width, int32_t height,
+void launch_inverse_palette_predicted(PlanePtr idx, PlanePtr pal, int32_t pal_stride, void *const *dst_dev, int32_t num_c, int32_t width, int32_t height,
 		int32_t nb_colours, int32_t nb_deltas, int32_t d_pred, int32_t bpp, const int8_t *wpp_dev, int32_t *wp_scratch, uint32_t *status, hipStream_t stream) {
-	hipLaunchKernelGGL(k_inverse_palette_predicted, dim3(1), dim3(64), 0, stream, idx, pal, pal_stride, dst_dev, num_c, width, height, nb_colours, nb_deltas, d_pred, bpp, wpp_dev, wp_scratch, status);
+	if (idx.wide()) hipLaunchKernelGGL(k_inverse_palette_predicted<int32_t>, dim3(1), dim3(64), 0, stream, (const int32_t *) idx.p, (const int32_t *) pal.p, pal_stride, (int32_t *const *) dst_dev, num_c, width, height, nb_colours, nb_deltas, d_pred, bpp, wpp_dev, wp_scratch, status);
+	else hipLaunchKernelGGL(k_inverse_palette_predicted<int16_t>, dim3(1), dim3(64), 0, stream, (const int16_t *) idx.p, (const int16_t *) pal.p, pal_stride, (int16_t *const *) dst_dev, num_c, width, height, nb_colours, nb_deltas, d_pred, bpp, wpp_dev, wp_scratch, status);
 }
 // avg: aw x ah, res: rw x rh; horizontal: rh == ah, out is (aw + rw) x ah; vertical: rw == aw, out is aw x (ah + rh)
-void launch_inverse_squeeze(const int16_t *avg, const int16_t *res, int16_t *out, int32_t aw, int32_t ah, int32_t rw, int32_t rh, bool horizontal, hipStream_t stream) {
+void launch_inverse_squeeze(PlanePtr avg, PlanePtr res, PlanePtr out, int32_t aw, int32_t ah, int32_t rw, int32_t rh, bool horizontal, hipStream_t stream) {
 	if (aw <= 0 || ah <= 0) return;
-	if (horizontal) hipLaunchKernelGGL(k_unsqueeze_h, dim3((unsigned) ((ah + 63) / 64)), dim3(64), 0, stream, avg, res, out, aw, ah, rw);
-	else hipLaunchKernelGGL(k_unsqueeze_v, dim3((unsigned) ((aw + 255) / 256)), dim3(256), 0, stream, avg, res, out, aw, ah, rh);
-}
-void launch_pack_planes(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16, int32_t shift) {
-	if (shift > 0) {
-		const unsigned grid = grid_for((size_t) scale_out_size(width, shift) * (size_t) scale_out_size(height, shift));
-		if (rgba16 && shift == 1) hipLaunchKernelGGL(k_pack_planes16<1>, dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
-		else if (rgba16) hipLaunchKernelGGL(k_pack_planes16<2>, dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
-		else if (shift == 1) hipLaunchKernelGGL(k_pack_planes<1>, dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
-		else hipLaunchKernelGGL(k_pack_planes<2>, dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+	if (out.wide()) {
+		if (horizontal) hipLaunchKernelGGL(k_unsqueeze_h<int32_t>, dim3((unsigned) ((ah + SQZ_ROWS<int32_t> - 1) / SQZ_ROWS<int32_t>)), dim3(64), 0, stream, (const int32_t *) avg.p, (const int32_t *) res.p, (int32_t *) out.p, aw, ah, rw);
+		else hipLaunchKernelGGL(k_unsqueeze_v<int32_t>, dim3((unsigned) ((aw + 255) / 256)), dim3(256), 0, stream, (const int32_t *) avg.p, (const int32_t *) res.p, (int32_t *) out.p, aw, ah, rh);
 		return;
 	}
-	if (rgba16) hipLaunchKernelGGL(k_pack_planes16<0>, dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
-	else hipLaunchKernelGGL(k_pack_planes<0>, dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+	if (horizontal) hipLaunchKernelGGL(k_unsqueeze_h<int16_t>, dim3((unsigned) ((ah + 63) / 64)), dim3(64), 0, stream, (const int16_t *) avg.p, (const int16_t *) res.p, (int16_t *) out.p, aw, ah, rw);
+	else hipLaunchKernelGGL(k_unsqueeze_v<int16_t>, dim3((unsigned) ((aw + 255) / 256)), dim3(256), 0, stream, (const int16_t *) avg.p, (const int16_t *) res.p, (int16_t *) out.p, aw, ah, rh);
+}
+template <typename S>
+static void launch_pack_of(const S *r, const S *g, const S *b, const S *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16, int32_t shift) {
+	if (shift > 0) {
+		const unsigned grid = grid_for((size_t) scale_out_size(width, shift) * (size_t) scale_out_size(height, shift));
+		if (rgba16 && shift == 1) hipLaunchKernelGGL((k_pack_planes16<1, S>), dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+		else if (rgba16) hipLaunchKernelGGL((k_pack_planes16<2, S>), dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+		else if (shift == 1) hipLaunchKernelGGL((k_pack_planes<1, S>), dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+		else hipLaunchKernelGGL((k_pack_planes<2, S>), dim3(grid), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+		return;
+	}
+	if (rgba16) hipLaunchKernelGGL((k_pack_planes16<0, S>), dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+	else hipLaunchKernelGGL((k_pack_planes<0, S>), dim3(grid_for((size_t) width * (size_t) height)), dim3(256), 0, stream, r, g, b, a, width, height, bpp, rgba, stride);
+}
+void launch_pack_planes(PlanePtr r, PlanePtr g, PlanePtr b, PlanePtr a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16, int32_t shift) {
+	if (r.wide()) launch_pack_of((const int32_t *) r.p, (const int32_t *) g.p, (const int32_t *) b.p, (const int32_t *) a.p, width, height, bpp, rgba, stride, stream, rgba16, shift);
+	else launch_pack_of((const int16_t *) r.p, (const int16_t *) g.p, (const int16_t *) b.p, (const int16_t *) a.p, width, height, bpp, rgba, stride, stream, rgba16, shift);
 }
 
-void launch_pack_planes_rect(const int16_t *r, const int16_t *g, const int16_t *b, const int16_t *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
+template <typename S>
+static void launch_pack_rect_of(const S *r, const S *g, const S *b, const S *a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
+	if (rgba16) hipLaunchKernelGGL(k_pack_planes16_rect<S>, dim3(grid_for((size_t) rw * (size_t) rh)), dim3(256), 0, stream, r, g, b, a, plane_width, x0, y0, rw, rh, bpp, rgba, stride);
+	else hipLaunchKernelGGL(k_pack_planes_rect<S>, dim3(grid_for((size_t) rw * (size_t) rh)), dim3(256), 0, stream, r, g, b, a, plane_width, x0, y0, rw, rh, bpp, rgba, stride);
+}
+void launch_pack_planes_rect(PlanePtr r, PlanePtr g, PlanePtr b, PlanePtr a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
 	if (rw <= 0 || rh <= 0) return;
-	if (rgba16) hipLaunchKernelGGL(k_pack_planes16_rect, dim3(grid_for((size_t) rw * (size_t) rh)), dim3(256), 0, stream, r, g, b, a, plane_width, x0, y0, rw, rh, bpp, rgba, stride);
-	else hipLaunchKernelGGL(k_pack_planes_rect, dim3(grid_for((size_t) rw * (size_t) rh)), dim3(256), 0, stream, r, g, b, a, plane_width, x0, y0, rw, rh, bpp, rgba, stride);
+	if (r.wide()) launch_pack_rect_of((const int32_t *) r.p, (const int32_t *) g.p, (const int32_t *) b.p, (const int32_t *) a.p, plane_width, x0, y0, rw, rh, bpp, rgba, stride, stream, rgba16);
+	else launch_pack_rect_of((const int16_t *) r.p, (const int16_t *) g.p, (const int16_t *) b.p, (const int16_t *) a.p, plane_width, x0, y0, rw, rh, bpp, rgba, stride, stream, rgba16);
 }
 
 } // namespace j40hip

@@ -248,15 +248,25 @@ struct DevCoopTree {
 	int32_t leaf_off[64], leaf_mul[64];
 };
 
-// a coded channel of the frame (or a plane of a section's sub-image): tightly packed int16 rows
-struct DevPlaneRef { int16_t *ptr; int32_t w, h, meta, pad; };
+// a coded channel of the frame (or a plane of a section's sub-image): tightly packed rows of int16 samples -- of int32 samples in a
+// wide frame's plan (DevModFrame::sample_bytes = 4). The pointer is untyped: mod_channel<S> (modular_dev.h) gives it the plan's type
+struct DevPlaneRef { void *ptr; int32_t w, h, meta, pad; };
 // one channel of one section: a rectangle of plane `plane`; shifts = hshift | vshift << 8 of the channel (matched when the MA
 // tree looks for "previous channels" of the same geometry)
 struct DevChanRect { int32_t plane, x0, y0, w, h, shifts; };
 
-struct DevSubPlane { int16_t *ptr; int32_t w, h, meta, pad; };
+struct DevSubPlane { void *ptr; int32_t w, h, meta, pad; };
 
 struct DevTransform { int32_t kind, begin_c, rct_type, num_c, nb_colours, nb_deltas, d_pred, pad; };
+
+// A plane of Modular samples as the host hands it to the launchers (kernels.h) and keeps it in its schedule (runtime_state.hpp): the
+// address and the bytes a sample takes (2: int16_t; 4: int32_t, a wide frame's). Offsets are counted in SAMPLES through at(), so no
+// caller multiplies by a sample size of its own
+struct PlanePtr {
+	uint8_t *p; int32_t sample_bytes;
+	PlanePtr at(size_t samples) const { return PlanePtr{p ? p + samples * (size_t) sample_bytes : nullptr, sample_bytes}; }
+	bool wide() const { return sample_bytes == 4; }
+};
 
 enum { MOD_MAX_CHANNELS = 256 };   // the reference's limit on channels while transforms are undone (j40.h:1173)
 
@@ -268,6 +278,8 @@ struct DevModFrame {
 	int32_t max_width;              // widest rectangle any section decodes (sizes the weighted-predictor rows)
 	int32_t check_section_end;      // see DevFrame::check_section_end
 	uint32_t single_declared_end;   // see DevFrame::single_declared_end
+	int32_t sample_bytes;           // 4: a wide frame (the image has 32-bit Modular buffers): every plane and sub-plane holds int32 samples and the
+	                                // weighted predictor's cells are 64-bit; else (0 or 2) int16 samples
 };
 
 struct DevModPlan {
@@ -286,7 +298,7 @@ struct DevModPlan {
 	                                  // whole and never a "previous channel" of image channels
 	const DevChanRect *chan_rects;    // DevModSection::chan_off
 	const DevCoopTree *coop_trees;    // DevModSection::coop_idx
-	int32_t *wp_scratch;              // [num_sections][2 * max_width * 5] weighted-predictor error rows
+	int32_t *wp_scratch;              // [num_sections][2 * max_width * 5] weighted-predictor error rows (int64 cells in a wide frame's plan)
 	int32_t *lz_window; uint32_t lz_window_size;
 	uint32_t *status;                 // [num_sections]
 	int32_t *residuals;               // the split sections' residual tokens (DevModSection::res_off); also their LZ77 windows
@@ -451,6 +463,7 @@ struct ModLaunchInfo {
 	uint32_t quad_table_span; // alias entries of quad_spec
 	// modular_split.hip: sections flagged `split` (0: none), their widest channel, the most channels one of them codes
 	int32_t split_sections, split_width, split_channels;
+	int32_t wide;   // the plan is a wide frame's: the int32 instantiations of k_modular_sections / k_modular_coop (never quad or split sections)
 };
 
 enum {

@@ -25,6 +25,8 @@ static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_by
 	j40hip_device_state *st = h->dev;
 	const DevModPlan &plan = st->mod;
 	const Frame &fr = h->frame;
+	const bool wide = st->mod_wide;   // int32 planes (the plane pointers carry the sample size themselves)
+	h->wide_used = wide;
 	RegionCover cover = {0, 0, 0, 0, 0, 0};
 	bool covered = false;   // only the cover's groups are decoded
 	if (region) {
@@ -47,30 +49,30 @@ static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_by
 	if (covered) {
 		launch_modular_sections(plan, 0, lead, st->mod_info, s);
 		for (int32_t p = 0; p < st->mod_passes; ++p) for (int32_t r = 0; r < cover.rows; ++r) launch_modular_sections(plan, lead + p * per_pass + (cover.gy0 + r) * cover.gcolumns + cover.gx0, cover.cols, st->mod_info, s);
-		if (st->mod_local_rcts) for (int32_t r = 0; r < cover.rows; ++r) launch_section_inverse_rcts(plan, lead + (st->mod_passes - 1) * per_pass + (cover.gy0 + r) * cover.gcolumns + cover.gx0, cover.cols, s);
+		if (st->mod_local_rcts) for (int32_t r = 0; r < cover.rows; ++r) launch_section_inverse_rcts(plan, lead + (st->mod_passes - 1) * per_pass + (cover.gy0 + r) * cover.gcolumns + cover.gx0, cover.cols, s, wide);
 	} else {
 	if (ranged) { launch_modular_sections(plan, 0, lead, st->mod_info, s); launch_modular_sections(plan, lead + g0, gn, st->mod_info, s); }
 	else launch_modular_sections(plan, 0, lead + per_pass, st->mod_info, s);
 	for (int32_t p = 1; p < st->mod_passes; ++p) launch_modular_sections(plan, lead + p * per_pass + g0, gn, st->mod_info, s);
-	if (st->mod_local_rcts) launch_section_inverse_rcts(plan, lead + (st->mod_passes - 1) * per_pass + g0, gn, s);
+	if (st->mod_local_rcts) launch_section_inverse_rcts(plan, lead + (st->mod_passes - 1) * per_pass + g0, gn, s, wide);
 	}
 	marks.mark(2);
 	// (a covered region: the frame-wide per-pixel transforms over the rows of the cover's groups only)
 	const size_t frame_samples = (size_t) fr.fh.width * (size_t) fr.fh.height;
-	const size_t band_off = covered ? ((size_t) cover.gy0 << cover.shift) * (size_t) fr.fh.width : 0;
+	const size_t band_off = covered ? ((size_t) cover.gy0 << cover.shift) * (size_t) fr.fh.width : 0;   // in samples
 	const size_t band_n = covered ? (size_t) (std::min<int64_t>(fr.fh.height, (int64_t) (cover.gy0 + cover.rows) << cover.shift) - ((int64_t) cover.gy0 << cover.shift)) * (size_t) fr.fh.width : 0;
 	for (const std::vector<j40hip_device_state::ModOp> *ops : {&st->mod_sub_ops, &st->mod_ops}) for (const auto &op : *ops) {
 		if (ranged && op.group >= 0 && (op.group < g0 || op.group >= g0 + gn)) continue;   // the sub-image of a group this process did not decode
 		if (covered && op.group >= 0 && (op.group % cover.gcolumns < cover.gx0 || op.group % cover.gcolumns >= cover.gx0 + cover.cols || op.group / cover.gcolumns < cover.gy0 || op.group / cover.gcolumns >= cover.gy0 + cover.rows)) continue;
-		if (covered && op.group < 0 && op.n == frame_samples && op.kind == 0) launch_inverse_rct(op.a + band_off, op.b + band_off, op.c + band_off, band_n, op.p0, s);
-		else if (covered && op.group < 0 && op.n == frame_samples && op.kind == 1) launch_inverse_palette_plain(op.src + band_off, op.aux, op.a + band_off, band_n, op.p0, op.p1, fr.im.bpp, s);
+		if (covered && op.group < 0 && op.n == frame_samples && op.kind == 0) launch_inverse_rct(op.a.at(band_off), op.b.at(band_off), op.c.at(band_off), band_n, op.p0, s);
+		else if (covered && op.group < 0 && op.n == frame_samples && op.kind == 1) launch_inverse_palette_plain(op.src.at(band_off), op.aux, op.a.at(band_off), band_n, op.p0, op.p1, fr.im.bpp, s);
 		else if (op.kind == 0) launch_inverse_rct(op.a, op.b, op.c, op.n, op.p0, s);
 		else if (op.kind == 1) launch_inverse_palette_plain(op.src, op.aux, op.a, op.n, op.p0, op.p1, fr.im.bpp, s);
 		else if (op.kind == 2) launch_inverse_palette_predicted(op.src, op.aux, op.p0, op.dst_list, op.p1, op.p2, op.p3, op.p4, op.p5 & 0xffffff, op.p5 >> 24, fr.im.bpp, op.wpp, st->pal_wp_scratch, st->mod_extra_status, s);
 		else if (op.kind == 4) launch_inverse_squeeze(op.src, op.aux, op.a, op.p0, op.p1, op.p2, op.p3, op.p4 != 0, s);
 		else launch_paste_plane(op.src, op.p0, op.p1, op.a, op.p2, s);
 	}
-	const int16_t *alpha = st->alpha_channel >= 0 ? st->final_planes[(size_t) st->alpha_channel] : nullptr;
+	const PlanePtr alpha = st->alpha_channel >= 0 ? st->final_planes[(size_t) st->alpha_channel] : PlanePtr{nullptr, st->final_planes[0].sample_bytes};
 	if (region) {   // the rectangle alone; pixel (x0, y0) of the frame is the first one at rgba_dev
 		uint8_t *moved = (uint8_t *) rgba_dev - ((size_t) region[1] * stride_bytes + (size_t) region[0] * pixel_bytes(h));
 		launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, region[0], region[1], region[2], region[3], fr.im.bpp, moved, stride_bytes, s, out16(h));
@@ -359,7 +361,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 }
 
 // what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it
-static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
+static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->wide_used = false; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
 
 // One VarDCT decode as decode_impl (whole frames, group ranges) and decode_region (covers) describe it to run_vardct
 struct VardctRun {

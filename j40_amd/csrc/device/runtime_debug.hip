@@ -161,8 +161,26 @@ extern "C" uint32_t j40hip_frame_read_plane_i16(j40hip_frame *h, int c, int16_t 
 	j40hip_device_state *st = h->dev;
 	if (c < 0 || (size_t) c >= st->final_planes.size()) return ERR_RNGE;
 	const size_t n = (size_t) st->final_w[(size_t) c] * (size_t) st->final_h[(size_t) c];
-	if (hipMemcpy(out, st->final_planes[(size_t) c], n * 2, hipMemcpyDeviceToHost) != hipSuccess) return ERR_GPU;
+	if (st->mod_wide) return ERR_TODO;   // (int32 planes: j40hip_frame_read_plane_i32)
+	if (hipMemcpy(out, st->final_planes[(size_t) c].p, n * 2, hipMemcpyDeviceToHost) != hipSuccess) return ERR_GPU;
 	return 0;
+}
+extern "C" uint32_t j40hip_frame_read_plane_i32(j40hip_frame *h, int c, int32_t *out) {
+	if (!h || !h->dev || !h->dev->is_modular) return ERR_GPU;
+	j40hip_device_state *st = h->dev;
+	if (c < 0 || (size_t) c >= st->final_planes.size()) return ERR_RNGE;
+	if (!st->mod_wide) return ERR_TODO;
+	const size_t n = (size_t) st->final_w[(size_t) c] * (size_t) st->final_h[(size_t) c];
+	if (hipMemcpy(out, st->final_planes[(size_t) c].p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return ERR_GPU;
+	return 0;
+}
+// wide Modular frames (include/j40hip.h)
+extern "C" void j40hip_frame_wide(const j40hip_frame *h, int32_t out[4]) {
+	if (!out) return;
+	memset(out, 0, sizeof(int32_t) * 4);
+	if (!h) return;
+	out[0] = h->frame.wide() ? 1 : 0; out[1] = h->frame.im.bpp; out[2] = h->wide_used ? 1 : 0;
+	out[3] = h->dev && h->dev->is_modular ? (h->dev->mod_wide ? 4 : 2) : 0;
 }
 
 // known-answer hooks: n floats through the pixel kernels' sRGB tail on the device (launch(dv, dout)), one sample of T each

@@ -163,10 +163,11 @@ struct j40hip_device_state {
 	ModLaunchInfo mod_info = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	std::vector<uint32_t> mod_section_offsets;
 	// group: the group whose section's sub-image the op belongs to (mod_sub_ops; a ranged decode skips the ops of groups it did not decode), -1: the frame's
-	struct ModOp { int kind; int16_t *a, *b, *c; const int16_t *src, *aux; size_t n; int32_t p0, p1, p2, p3, p4, p5; int16_t *const *dst_list; const int8_t *wpp; int32_t group; };
+	struct ModOp { int kind; PlanePtr a, b, c, src, aux; size_t n; int32_t p0, p1, p2, p3, p4, p5; void *const *dst_list; const int8_t *wpp; int32_t group; };
 	std::vector<ModOp> mod_ops;          // inverse transforms of the frame, in execution order
 	std::vector<ModOp> mod_sub_ops;      // before them: inverse transforms of the sections' own sub-images and their paste (kind 3)
-	std::vector<int16_t *> final_planes; // channel list after the inverse transforms
+	std::vector<PlanePtr> final_planes;  // channel list after the inverse transforms (address + bytes per sample)
+	bool mod_wide = false;               // a wide frame: every plane above holds int32 samples
 	std::vector<int32_t> final_w, final_h;
 	int32_t alpha_channel = -1;
 	int32_t *pal_wp_scratch = nullptr;

@@ -39,13 +39,16 @@ static uint32_t upload_modular(j40hip_frame *h, int device) {
 	st->mod_local_rcts = !hp.local_rct.empty();
 	st->mod_sections = (int32_t) hp.sections.size(); st->mod_passes = hp.num_passes; st->mod_sections_per_pass = hp.sections_per_pass;
 	st->mod_info = mod_launch_info(hp);
+	st->mod_wide = hp.frame.sample_bytes == 4;
+	const int32_t sb = (int32_t) lay.sample_bytes;   // bytes a sample takes; every offset below is counted in samples (PlanePtr::at)
+	auto new_plane = [&](size_t samples) { return PlanePtr{st->scratch<uint8_t>((size_t) sb * samples, ok), sb}; };
 	for (const DevModSection &sec : hp.sections) st->mod_section_offsets.push_back(sec.byte_off);
-	struct Ref { int16_t *p; int32_t w, h; };
+	struct Ref { PlanePtr p; int32_t w, h; };
 	std::vector<Ref> planes;
-	for (size_t c = 0; c < lay.num_planes; ++c) planes.push_back({lay.plane(base, c), hp.plane_w[c], hp.plane_h[c]});
+	for (size_t c = 0; c < lay.num_planes; ++c) planes.push_back({lay.plane_ptr(base, c), hp.plane_w[c], hp.plane_h[c]});
 	bool palette_wp = false;
 	for (const Transform &t : hp.transforms) palette_wp |= t.kind == Transform::PALETTE && t.nb_deltas > 0 && t.d_pred == 6;
-	if (palette_wp) st->pal_wp_scratch = st->scratch<int32_t>((size_t) 2 * (size_t) hp.frame.width * 5 + 16, ok);
+	if (palette_wp) st->pal_wp_scratch = st->scratch<int32_t>((size_t) (sb / 2) * ((size_t) 2 * (size_t) hp.frame.width * 5 + 16), ok);   // (64-bit cells in a wide frame)
 	st->mod_extra_status = const_cast<uint32_t *>(plan.status) + hp.sections.size();
 	st->total_sections = (int32_t) hp.sections.size();
 
@@ -67,10 +70,10 @@ static uint32_t upload_modular(j40hip_frame *h, int device) {
 				const Ref idx = planes[(size_t) first], pal = planes[0];
 				const size_t n = (size_t) idx.w * (size_t) idx.h;
 				std::vector<Ref> outs;
-				for (int32_t i = 0; i < t.num_c - 1; ++i) outs.push_back({st->scratch<int16_t>(n ? n : 1, ok), idx.w, idx.h});
+				for (int32_t i = 0; i < t.num_c - 1; ++i) outs.push_back({new_plane(n ? n : 1), idx.w, idx.h});
 				outs.push_back(idx);   // the index channel becomes the last colour channel, in place
 				if (t.nb_deltas > 0) {
-					std::vector<int16_t *> ptrs; for (const Ref &o : outs) ptrs.push_back(o.p);
+					std::vector<void *> ptrs; for (const Ref &o : outs) ptrs.push_back(o.p.p);
 					j40hip_device_state::ModOp op; memset(&op, 0, sizeof op);
 					op.kind = 2; op.src = idx.p; op.aux = pal.p; op.p0 = pal.w; op.p1 = t.num_c; op.p2 = idx.w; op.p3 = idx.h; op.p4 = t.nb_colours; op.p5 = t.nb_deltas | (t.d_pred << 24);
 					op.dst_list = st->upload(ptrs.data(), ptrs.size(), s, ok);
@@ -79,7 +82,7 @@ static uint32_t upload_modular(j40hip_frame *h, int device) {
 				} else {
 					for (int32_t i = 0; i < t.num_c; ++i) {
 						j40hip_device_state::ModOp op; memset(&op, 0, sizeof op);
-						op.kind = 1; op.src = idx.p; op.aux = t.nb_colours > 0 ? pal.p + (size_t) i * (size_t) pal.w : nullptr; op.a = outs[(size_t) i].p; op.n = n; op.p0 = i; op.p1 = t.nb_colours;
+						op.kind = 1; op.src = idx.p; op.aux = t.nb_colours > 0 ? pal.p.at((size_t) i * (size_t) pal.w) : PlanePtr{nullptr, sb}; op.a = outs[(size_t) i].p; op.n = n; op.p0 = i; op.p1 = t.nb_colours;
 						ops.push_back(op);
 					}
 				}
@@ -94,10 +97,10 @@ static uint32_t upload_modular(j40hip_frame *h, int device) {
 				if (t.begin_c < 0 || t.num_c < 1 || end_c > nc || offset + t.num_c > nc || offset < end_c) { ok = false; break; }
 				for (int32_t c = t.begin_c; c < end_c; ++c) {
 					const Ref avg = planes[(size_t) c], res = planes[(size_t) (offset + c - t.begin_c)];
-					Ref out = {nullptr, t.horizontal ? avg.w + res.w : avg.w, t.horizontal ? avg.h : avg.h + res.h};
+					Ref out = {PlanePtr{nullptr, sb}, t.horizontal ? avg.w + res.w : avg.w, t.horizontal ? avg.h : avg.h + res.h};
 					if ((t.horizontal ? res.h != avg.h || (res.w != avg.w && res.w != avg.w - 1) : res.w != avg.w || (res.h != avg.h && res.h != avg.h - 1))) { ok = false; break; }
 					const size_t n = (size_t) std::max(out.w, 0) * (size_t) std::max(out.h, 0);
-					out.p = st->scratch<int16_t>(n ? n : 1, ok);
+					out.p = new_plane(n ? n : 1);
 					j40hip_device_state::ModOp op; memset(&op, 0, sizeof op);
 					op.kind = 4; op.src = avg.p; op.aux = res.p; op.a = out.p; op.p0 = avg.w; op.p1 = avg.h; op.p2 = res.w; op.p3 = res.h; op.p4 = t.horizontal ? 1 : 0;
 					ops.push_back(op);
@@ -115,7 +118,7 @@ static uint32_t upload_modular(j40hip_frame *h, int device) {
 			if (!si.paste) continue;
 			for (const Transform &t : si.transforms) palette_wp |= t.kind == Transform::PALETTE && t.nb_deltas > 0 && t.d_pred == 6;
 			std::vector<Ref> sp;
-			for (size_t k = (size_t) si.first_plane; k < (size_t) (si.first_plane + si.num_planes); ++k) sp.push_back({lay.sub_plane(base, k), hp.sub_w[k], hp.sub_h[k]});
+			for (size_t k = (size_t) si.first_plane; k < (size_t) (si.first_plane + si.num_planes); ++k) sp.push_back({lay.sub_plane_ptr(base, k), hp.sub_w[k], hp.sub_h[k]});
 			// (sections: LfGlobal's first, then passes x groups)
 			const int32_t lead_sections = (int32_t) hp.sections.size() - hp.sections_per_pass * hp.num_passes;
 			const int32_t sub_group = si.section >= lead_sections && hp.sections_per_pass > 0 ? (si.section - lead_sections) % hp.sections_per_pass : -1;
@@ -125,11 +128,11 @@ static uint32_t upload_modular(j40hip_frame *h, int device) {
 				const Ref &dst = planes[(size_t) sec.first_channel + c];
 				if (sp[c].w != sec.gw || sp[c].h != sec.gh || (size_t) sec.first_channel + c >= planes.size()) { ok = false; break; }
 				j40hip_device_state::ModOp op; memset(&op, 0, sizeof op);
-				op.kind = 3; op.src = sp[c].p; op.a = dst.p + (size_t) sec.gy * (size_t) dst.w + (size_t) sec.gx; op.p0 = sp[c].w; op.p1 = sp[c].h; op.p2 = dst.w; op.group = sub_group;
+				op.kind = 3; op.src = sp[c].p; op.a = dst.p.at((size_t) sec.gy * (size_t) dst.w + (size_t) sec.gx); op.p0 = sp[c].w; op.p1 = sp[c].h; op.p2 = dst.w; op.group = sub_group;
 				st->mod_sub_ops.push_back(op);
 			}
 		}
-		if (palette_wp && !st->pal_wp_scratch) st->pal_wp_scratch = st->scratch<int32_t>((size_t) 2 * (size_t) widest * 5 + 16, ok);
+		if (palette_wp && !st->pal_wp_scratch) st->pal_wp_scratch = st->scratch<int32_t>((size_t) (sb / 2) * ((size_t) 2 * (size_t) widest * 5 + 16), ok);
 	}
 	{
 		int8_t gwp[12]; const WPParams &wp = h->frame.gmodular.wp;

@@ -10,6 +10,7 @@
 // The recurrence runs along the squeezed axis (out[2k - 1] feeds the next pair); lines across it are independent.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 #ifndef J40_DEV
 #ifdef __HIPCC__
 #define J40_DEV __device__ __forceinline__
@@ -47,17 +48,19 @@ J40_DEV void unsqueeze_pair(int32_t avg, int32_t res, int32_t left, int32_t next
 }
 
 // a whole line of `n_avg` averages and `n_res` residuals (n_res = n_avg or n_avg - 1) with element strides; writes
-// n_avg + n_res samples. Samples are int16 with wrap-around, like every Modular buffer here (j40.h:3169).
+// n_avg + n_res samples. Samples are int16 with wrap-around, like every Modular buffer here (j40.h:3169) -- or int32 where the
+// lines are a wide frame's (the type `out` points at decides).
 template <typename SRC, typename SRC2, typename DST>
 J40_DEV void unsqueeze_line(SRC avg, int32_t avg_stride, SRC2 res, int32_t res_stride, int32_t n_avg, int32_t n_res, DST out, int32_t out_stride) {
+	typedef typename std::remove_cv<typename std::remove_reference<decltype(out[0])>::type>::type T;
 	int32_t left = 0;
 	for (int32_t k = 0; k < n_res; ++k) {
 		const int32_t a = avg[(int64_t) k * avg_stride];
 		const int32_t next = k + 1 < n_avg ? (int32_t) avg[(int64_t) (k + 1) * avg_stride] : a;
 		int32_t p, q;
 		unsqueeze_pair(a, res[(int64_t) k * res_stride], k > 0 ? left : a, next, &p, &q);
-		out[(int64_t) (2 * k) * out_stride] = (int16_t) p; out[(int64_t) (2 * k + 1) * out_stride] = (int16_t) q;
-		left = (int16_t) q;
+		out[(int64_t) (2 * k) * out_stride] = (T) p; out[(int64_t) (2 * k + 1) * out_stride] = (T) q;
+		left = (T) q;
 	}
 	if (n_avg > n_res) out[(int64_t) (2 * n_res) * out_stride] = avg[(int64_t) n_res * avg_stride];
 }

@@ -146,7 +146,7 @@ static void read_customxy(BitReader &br) {
 	(void) br.u32(0, 19, 0x80000, 19, 0x100000, 20, 0x200000, 21);
 }
 
-static void read_image_metadata(BitReader &br, ImageMeta *im) {  // j40.h:3104
+static void read_image_metadata(BitReader &br, ImageMeta *im, bool allow_wide) {  // j40.h:3104
 	static const float OPSIN_INV[3][3] = {
 		{11.031566901960783f, -9.866943921568629f, -0.16462299647058826f},
 		{-3.254147380392157f, 4.418770392156863f, -0.16462299647058826f},
@@ -180,7 +180,7 @@ static void read_image_metadata(BitReader &br, ImageMeta *im) {  // j40.h:3104
 		read_bit_depth(br, &im->bpp, &im->exp_bits);
 		J40HIP_SHOULD(im->bpp <= 16, "fbpp");
 		im->modular_16bit_buffers = br.u(1);
-		J40HIP_SHOULD(im->modular_16bit_buffers, "fm32");
+		J40HIP_SHOULD(im->modular_16bit_buffers || allow_wide, "fm32");   // (Frame::allow_wide; the reference refuses every such image, j40.h:3169)
 		int32_t num_ec = br.u32(0, 0, 1, 0, 2, 4, 1, 12);
 		J40HIP_SHOULD(num_ec <= 4, "elim");
 		im->ec.assign((size_t) num_ec, ExtraChannel());
@@ -851,14 +851,14 @@ static void skip_icc(BitReader &br) {
 
 // signature, image and frame headers, TOC (sections clipped to the bytes that exist), the LfGroups' geometry
 // `limit`: how much of the codestream's cs_size bytes may be read (streaming input: what has arrived; else cs_size)
-static void read_image_header(BitReader &br, ImageMeta *im) {
+static void read_image_header(BitReader &br, ImageMeta *im, bool allow_wide) {
 	J40HIP_SHOULD(br.u(16) == 0x0aff, "!jxl");
-	read_image_metadata(br, im);
+	read_image_metadata(br, im, allow_wide);
 	if (im->want_icc) skip_icc(br);
 }
-void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame) {
+void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame, bool allow_wide) {
 	BitReader br(cs, cs_size);
-	read_image_header(br, im);
+	read_image_header(br, im, allow_wide);
 	br.zero_pad_to_byte();
 	*first_frame = br.byte_position();
 }
@@ -894,11 +894,14 @@ static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size
 		read_frame_header(br, f->im, &f->fh, true);
 		if (uint32_t e = sequence_refusal(f->fh, f->seq_blend, rendered_alpha_channel(f->im))) raise(e);
 	} else {
-		read_image_header(br, &f->im);
+		read_image_header(br, &f->im, f->allow_wide);
 		read_frame_header(br, f->im, &f->fh);
 		J40HIP_SHOULD(f->fh.is_last, "TODO");
 		J40HIP_SHOULD(f->fh.type == 0, "TODO");
 	}
+	// an image with 32-bit Modular buffers: its Modular frames only, and only where they were asked for (its VarDCT frames would need wide LF,
+	// HF-metadata and extra-channel streams; the reference's word for the combination is TODO as well, j40.h:7868)
+	J40HIP_SHOULD(f->im.modular_16bit_buffers || (f->allow_wide && f->fh.is_modular), "TODO");
 	read_toc(br, f->fh, &f->toc);
 	{   // a truncated codestream fails where the reference fails: in the first section (in reading order) that
 		// needs the missing bytes, not up front. Sections are clipped to the bytes that exist; readers raise "shrt".

@@ -21,6 +21,7 @@ inline bool alpha_env() { static const bool v = [] { const char *e = env_str("J4
 // J40HIP_ORIENT=1: single-frame decodes apply the image's orientation where j40hip_frame_set_orientation(f, 1) would be taken (include/j40hip.h); read once
 inline bool orient_env() { static const bool v = [] { const char *e = env_str("J40HIP_ORIENT"); return e && atoi(e) > 0; }(); return v; }
 // J40HIP_YCBCR=1: YCbCr VarDCT frames (recompressed JPEGs) are served where j40hip_frame_set_ycbcr(f, 1) would be taken (include/j40hip.h); read once
+inline bool wide_env() { static const bool v = [] { const char *e = env_str("J40HIP_WIDE"); return e && atoi(e) > 0; }(); return v; }
 inline bool ycbcr_env() { static const bool v = [] { const char *e = env_str("J40HIP_YCBCR"); return e && atoi(e) > 0; }(); return v; }
 
 struct ExtraChannel { int32_t type = 0, bpp = 8, exp_bits = 0, dim_shift = 0; bool alpha_associated = false; };
@@ -203,13 +204,18 @@ struct Frame {
 	// YCbCr frames are asked for (J40HIP_PARSE_YCBCR or J40HIP_YCBCR=1): a frame with subsampled channels is parsed -- its block grid padded
 	// to whole MCUs, every LF channel at its own size -- instead of refused with "TODO" before its LF image is read. Set before parse_frame.
 	bool allow_ycbcr = false;
+	// Wide Modular frames are asked for (J40HIP_PARSE_WIDE or J40HIP_WIDE=1): an image whose metadata says modular_16bit_buffers = 0 is parsed
+	// instead of refused with "fm32" (j40.h:3169), and a Modular frame of it is decoded with int32 sample planes. A VarDCT frame of such an
+	// image is "TODO". Set before parse_frame.
+	bool allow_wide = false;
+	bool wide() const { return !im.modular_16bit_buffers; }
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
 	Frame with_same_inputs() const {
 		Frame g;
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
-		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr;
+		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr; g.allow_wide = allow_wide;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section
@@ -224,7 +230,7 @@ void extract_codestream(const uint8_t *data, size_t size, const uint8_t **cs, si
 
 // signature, image metadata and ICC profile of a codestream: everything in front of the first frame header. *first_frame: the byte
 // the first frame header starts at
-void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame);
+void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame, bool allow_wide = false);
 // header and TOC of the frame that starts at byte `offset` of the codestream, for a sequence's index: nothing behind the TOC is
 // read. The TOC's offsets count from `offset`. Raises what the header or the TOC raise, "TODO" for what sequence_refusal refuses.
 // blend: the sequence serves the blend modes other than Replace (sequence_refusal).

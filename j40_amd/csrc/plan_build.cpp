@@ -514,7 +514,8 @@ static void assign_coop(HostModPlan *hp) {
 	static const int32_t quad_min = env_int("J40HIP_QUAD_MIN", -1, INT_MIN, INT_MAX);
 	hp->quad_sections = 0; hp->quad_spec = 0; hp->quad_width = 0;
 	for (DevModSection &s : hp->sections) s.quad = 0;
-	if (quad_min >= 0 && hp->coop_sections >= std::max(quad_min, 1)) {
+	// (a wide frame's sections never: k_modular_quad and modular_split.hip are int16-only, measured variants for one configuration each)
+	if (quad_min >= 0 && hp->coop_sections >= std::max(quad_min, 1) && hp->frame.sample_bytes != 4) {
 		std::vector<int32_t> votes(hp->specs.size(), 0);
 		for (const DevModSection &s : hp->sections) if (s.coop_idx >= 0) ++votes[(size_t) s.spec_idx];
 		const int32_t spec = (int32_t) (std::max_element(votes.begin(), votes.end()) - votes.begin());
@@ -566,7 +567,7 @@ static void assign_split(HostModPlan *hp) {
 	};
 	for (DevModSection &s : hp->sections) {
 		s.split = 0; s.res_off = 0; s.res_count = 0;
-		if (off || s.uses_wp) continue;
+		if (off || s.uses_wp || hp->frame.sample_bytes == 4) continue;
 		int32_t widest = 0; size_t samples = 0;
 		for (int32_t c = 0; c < s.num_channels; ++c) {
 			int32_t w, h;
@@ -615,13 +616,13 @@ uint32_t build_modular_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, 
 	const int32_t nch = (int32_t) gm.channel.size();
 	if (nch > MOD_MAX_CHANNELS) return ERR_TODO;
 	// what the reference's renderer accepts (j40.h:7917-7936)
-	if (fr.im.bpp < 8 || fr.im.exp_bits || !fr.im.modular_16bit_buffers) return ERR_TODO;
+	if (fr.im.bpp < 8 || fr.im.exp_bits || (!fr.im.modular_16bit_buffers && !fr.allow_wide)) return ERR_TODO;
 	// a Modular frame flagged XYB or YCbCr gets no colour transform in the reference (j40.h:8209-8210 runs only the
 	// Modular inverse transforms, j40.h:7910 renders the first three channels as they are): same here
 	DevModFrame &df = hp->frame;
 	memset(&df, 0, sizeof df);
 	df.width = fr.fh.width; df.height = fr.fh.height; df.num_groups = (int32_t) fr.fh.num_groups; df.bpp = fr.im.bpp;
-	df.num_channels = nch;
+	df.num_channels = nch; df.sample_bytes = fr.wide() ? 4 : 2;
 	df.check_section_end = fr.toc.single;
 	df.single_declared_end = (uint32_t) fr.toc.single_declared_end;
 	// trees and code specs: the global pair once (when a header refers to it), own pairs per section (use_global_tree = 0)

@@ -1248,6 +1248,10 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	const int noxyb = opt.geti("noxyb", 0) || ycbcr;
 	if (noxyb && (icc_bytes || !nonzero_header || x_qm != 3 || b_qm != 2)) die("vardct: noxyb wants fullheader=1, no icc and the default qm scales");
 	if (noxyb && g_seq && !with_alpha) die("vardct: noxyb in frames= wants alpha=1");
+	// wide=1: the metadata says modular_16bit_buffers = 0 and nothing else changes (a stream readers refuse: "fm32", or "TODO" where wide
+	// Modular frames are asked for). The metadata must be written out: bpp != 8 or alpha=1
+	const int vd_wide = opt.geti("wide", 0);
+	if (vd_wide && img_bpp == 8 && !with_alpha) die("vardct: wide=1 wants metadata that is written out: bpp=9..15 or alpha=1");
 	if (!g_seq || g_seq->first) {
 	cs.put(0xff, 8); cs.put(0x0a, 8);
 	write_size_header(cs, g_seq ? g_seq->canvas_w : W, g_seq ? g_seq->canvas_h : H);
@@ -1255,7 +1259,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		write_bit_depth(cs, img_bpp);
-		cs.put(1, 1);                       // modular_16bit_buffers
+		cs.put(vd_wide ? 0 : 1, 1);         // modular_16bit_buffers (wide=1: 0)
 		if (num_ec == 1) cs.put(1, 2); else { cs.put(2, 2); cs.put((uint64_t) (num_ec - 2), 4); }   // num_extra_channels (j40.h:3170)
 		for (int k = 0; k < ec_extra; ++k) {
 			cs.put(0, 1);                   // not the default alpha
@@ -1282,7 +1286,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		write_bit_depth(cs, img_bpp);
-		cs.put(1, 1);                       // modular_16bit_buffers
+		cs.put(vd_wide ? 0 : 1, 1);         // modular_16bit_buffers (wide=1: 0)
 		cs.put(0, 2);                       // no extra channels
 		cs.put(noxyb ? 0 : 1, 1);           // xyb_encoded
 		if (noxyb && opt.geti("grey", 0)) {
@@ -1306,7 +1310,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		cs.put(0, 1); cs.put(0, 2);         // integer samples, 8 bits
-		cs.put(1, 1);                       // modular_16bit_buffers
+		cs.put(vd_wide ? 0 : 1, 1);         // modular_16bit_buffers (wide=1: 0)
 		cs.put(1, 2); cs.put(1, 1);         // one extra channel, d_alpha
 		cs.put(noxyb ? 0 : 1, 1);           // xyb_encoded (noxyb=1: the reference runs the XYB inverse on VarDCT frames regardless, j40.h:7206)
 		cs.put(1, 1);                       // ColourEncoding.all_default
@@ -1317,7 +1321,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		cs.put(0, 1); cs.put(0, 2);         // integer samples, 8 bits
-		cs.put(1, 1);                       // modular_16bit_buffers
+		cs.put(vd_wide ? 0 : 1, 1);         // modular_16bit_buffers (wide=1: 0)
 		cs.put(0, 2);                       // no extra channels
 		cs.put(1, 1);                       // xyb_encoded
 		cs.put(0, 1);                       // ColourEncoding: not all_default
@@ -1447,12 +1451,21 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	const int rct = opt.geti("rct", 6);                   // -1: none
 	const int use_prefix = opt.geti("prefix", 0);
 	const int lz77 = opt.geti("lz77", 0);
-	const int tree_kind = opt.geti("tree", 0);            // 0 gradient, 1 per-channel leaves + property splits, 2 weighted predictor, 3 previous-channel properties
+	const int tree_kind = opt.geti("tree", 0);            // 0 gradient, 1 per-channel leaves + property splits, 2 weighted predictor, 3 previous-channel properties, 8 a first-sample leaf
 	const int palette = opt.geti("palette", 0);           // 0 none, 1 plain palette, 2 with deltas / synthetic colours, 3 with delta prediction
 	const int container = opt.geti("container", 0);
-	const int bpp = opt.geti("bpp", 8);   // 8..15 (16-bit buffers)
-	if (bpp < 8 || bpp > 15) die("modular: bpp 8..15");
-	if (bpp != 8 && alpha) die("modular: the default alpha channel has 8 bits; the reference refuses a different colour depth");
+	// wide=1: the image metadata says modular_16bit_buffers = 0 -- samples are int32 to a reader -- and NOTHING else changes: at bpp <= 15
+	// the same seed and options give the same picture and the same sections. It admits bpp=16 (a 16-bit sample does not fit int16),
+	// an alpha channel at a depth other than 8 (written at the image's depth), range= and povfto= beyond int16, and bias=K (added to
+	// every colour sample before the clamp to range=: pictures near the ends of int32)
+	const int wide = opt.geti("wide", 0);
+	const int bpp = opt.geti("bpp", 8);   // 8..15 (16-bit buffers); 16 with wide=1
+	if (bpp < 8 || bpp > (wide ? 16 : 15)) die("modular: bpp 8..15 (8..16 with wide=1)");
+	if (bpp != 8 && alpha && !wide) die("modular: the default alpha channel has 8 bits; the reference refuses a different colour depth");
+	const bool deep_alpha = wide && alpha && bpp != 8;   // the alpha channel has the image's depth
+	sample_lo() = wide ? INT32_MIN : -32768; sample_hi() = wide ? INT32_MAX : 32767;
+	const int64_t bias = wide ? strtoll(opt.gets("bias", "0").c_str(), nullptr, 10) : 0;
+	if (!wide && opt.kv.count("bias")) die("modular: bias= wants wide=1");
 	const int gdim = 1 << group_shift;
 	// ---- streams outside an encoder's habits (tests/test_modular_stress.py); every option defaults to what was written before ----
 	// lzmode=special|plain|overlap (with lz77=1): a matcher over the decoded integers instead of the run-length pass; it prefers
@@ -1541,25 +1554,28 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	if (opt.kv.count("tile") && (sscanf(opt.gets("tile", "").c_str(), "%d,%d", &tile_px, &tile_py) != 2 || tile_px < 1 || tile_py < 1)) die("modular: tile=<px>,<py>");
 	const int tile_noise = opt.geti("tilenoise", 20), noise = opt.geti("noise", 0);
 	int range_lo = 0, range_hi = (1 << bpp) - 1;
-	if (opt.kv.count("range") && (sscanf(opt.gets("range", "").c_str(), "%d,%d", &range_lo, &range_hi) != 2 || range_lo > range_hi || range_lo < -32768 || range_hi > 32767)) die("modular: range=<lo>,<hi> within int16");
+	if (opt.kv.count("range") && (sscanf(opt.gets("range", "").c_str(), "%d,%d", &range_lo, &range_hi) != 2 || range_lo > range_hi || (!wide && (range_lo < -32768 || range_hi > 32767)))) die("modular: range=<lo>,<hi> within int16 (int32 with wide=1)");
 	if (noise < 0 || noise > 65535) die("modular: noise 0..65535");
 	for (int y = 0; y < pic_h; ++y) for (int x = 0; x < pic_w; ++x) {
 		const int xs = tile_px ? x % tile_px : x, ys = tile_py ? y % tile_py : y;
 		float rgb[3]; pic.rgb((float) xs, (float) ys, rgb);
 		// flat regions + a bit of texture so that run-lengths and the predictors both get work
 		for (int c = 0; c < 3; ++c) {
-			int v = (int) (rgb[c] * 255.0f);
+			int64_t v = (int) (rgb[c] * 255.0f);
 			v = (v / 6) * 6 + (int) (Picture::hash01((uint64_t) xs * 7919 + (uint64_t) ys * 104729 + (uint64_t) c + seed) < 0.08f);
-			v = std::min(255, std::max(0, v)) * ((1 << bpp) - 1) / 255;
+			v = std::min<int64_t>(255, std::max<int64_t>(0, v)) * ((1 << bpp) - 1) / 255;
 			if (tile_px && Picture::hash01((uint64_t) x * 611953 + (uint64_t) y * 15485863 + (uint64_t) c * 31 + seed) * 1000.0f < (float) tile_noise) v ^= 1 + (int) (Picture::hash01((uint64_t) x * 31 + (uint64_t) y * 17 + seed) * 6.0f);
 			if (noise) v += (int) (Picture::hash01((uint64_t) x * 2654435761ull + (uint64_t) y * 40503 + (uint64_t) c * 977 + seed * 13) * (float) (2 * noise + 1)) - noise;
-			if (tile_px || noise || opt.kv.count("range")) v = std::min(range_hi, std::max(range_lo, v));
-			ch[(size_t) (colour0 + c)].at(x, y) = v;
+			v += bias;
+			if (tile_px || noise || opt.kv.count("range")) v = std::min<int64_t>(range_hi, std::max<int64_t>(range_lo, v));
+			ch[(size_t) (colour0 + c)].at(x, y) = (int32_t) v;
 		}
 		for (int k = 0; k < extra; ++k) ch[(size_t) (3 + k)].at(x, y) = (((x >> 3) * (k + 2) + (y >> 2)) & 31) * ((1 << bpp) - 1) / 31;
 		if (alpha) ch[(size_t) (3 + extra)].at(x, y) = ((x / 37 + y / 29) & 3) == 0 ? 128 + ((x * 3 + y) & 63) : 255;
 		// alpharange=1: 0, full scale and everything between (a diagonal ramp with transparent and opaque cells), for the blend modes
 		if (alpha && opt.geti("alpharange", 0)) { const int cell = (x / 23 + y / 19) % 5; ch[(size_t) (3 + extra)].at(x, y) = cell == 0 ? 0 : cell == 1 ? 255 : (x * 5 + y * 3) & 255; }
+		// (wide=1, bpp != 8: the same alpha at the image's depth, its low bits filled so that the whole range occurs)
+		if (deep_alpha) { int32_t &a = ch[(size_t) (3 + extra)].at(x, y); const int amax = (1 << bpp) - 1; a = a == 255 ? amax : a == 0 ? 0 : std::min(amax, a * amax / 255 + ((x * 7 + y * 13) & ((1 << (bpp - 8)) - 1))); }
 	}
 
 	if (squeeze && repeat > 1) {   // lay the tile out over the whole frame
@@ -1584,6 +1600,18 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	const int dpred = opt.geti("dpred", 5);
 	if (dpred < 0 || dpred > 13) die("modular: dpred 0..13");
 	if (opt.kv.count("dpred") && palette != 3 && opt.geti("localpalette", 0) != 3) die("modular: dpred belongs to a palette with delta entries (palette=3 or localpalette=3)");
+	// dumpsrc=PATH: the picture the stream codes, raw little-endian int32 [channels][height][width], colour first, then the extra
+	// channels. Where the writer runs a forward transform for everything it lists and no leaf quantises (`src_exact`), that is the source
+	// picture as synthesised above, and the tool dies unless its own inverses (jxlsynth_modular.hpp, 64-bit) take what it coded back
+	// to it -- a forward transform that is wrong at 18 bits cannot go unnoticed. Elsewhere -- a palette, whose picture IS the look-up;
+	// the RCT types the picture is taken as already transformed for; trees whose leaves have multipliers -- there is no source to
+	// return to, and the dump is what a reader must arrive at: the same inverses on what was coded (Squeeze is exact either way)
+	const std::string dumpsrc = opt.gets("dumpsrc", "");
+	const bool want_src = !dumpsrc.empty();
+	if (want_src && (opt.geti("povf", -1) >= 0 || lzp.force != FORCE_NONE || g_seq)) die("modular: dumpsrc wants a stream that codes a picture: no povf, lzforce or frames=");
+	std::vector<Channel> orig;
+	if (want_src) orig = ch;
+	bool src_exact = !palette && !(rct >= 0 && !(rct / 7 == 0 && rct % 7 != 2)) && !opt.geti("localpalette", 0) && tree_kind != 6 && tree_kind != 7 && tree_kind != 8 && !opt.geti("fourvalues", 0);
 	std::vector<TransformW> transforms;
 	if (palette) {
 		// replace the colour channels by a palette (meta channel 0) + an index channel
@@ -1610,6 +1638,8 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		transforms.push_back(t);
 	}
 	const int nb_meta = palette ? 1 : 0;
+	std::vector<Channel> dec;   // what a reader holds once every section is decoded and pasted, before it undoes the global RCT / palette
+	if (want_src) dec = ch;
 	if (squeeze) {
 		TransformW t; t.kind = 2;
 		std::vector<SqueezeStep> steps = default_squeeze_steps(ch, nb_meta);
@@ -1647,6 +1677,13 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 			int a = tree.branch(15, 8, l0, l1);       // max weighted-predictor error
 			int b = tree.branch(15, -8, l2, l3);
 			root = tree.branch(0, 1, a, b);
+		} else if (tree_kind == 8) {
+			// the first sample of every channel of a section takes a leaf of its own -- zero predictor, multiplier 65536 --, the others the
+			// gradient: a picture far from zero (wide=1 with bias=) is coded with small residuals, where one leaf would need a first
+			// residual beyond the 30 bits a hybrid integer holds. That first sample is quantised to a multiple of 65536
+			int first = tree.leaf(0, 0, 16, 0), l0 = tree.leaf(5), l1 = tree.leaf(5);
+			int a = tree.branch(2, 0, l0, first);     // y
+			root = tree.branch(3, 0, l1, a);          // x
 		} else if (tree_kind == 6 || tree_kind == 7) {
 			// lossy-Modular style leaves: multipliers 37 and 1000, offsets +-500. 6 walks a sample's position only (the two-pass decoder's
 			// kind of tree, the leaf changing along a row), 7 looks at neighbours as well
@@ -1732,9 +1769,10 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	const int povf_all = opt.geti("povf", -1);
 	const bool povf_everywhere = !opt.kv.count("povfsection");
 	int povf_section = opt.geti("povfsection", 0), coded_streams = 0;
-	const int64_t povf_to = opt.geti("povfto", 40000);
-	if (povf_to >= -32768 && povf_to <= 32767) die("modular: povfto lies outside int16");
-	if (povf_to < -(1 << 30) || povf_to > (1 << 30)) die("modular: povfto within +-2^30 (the residual is a 32-bit hybrid integer)");
+	const int64_t povf_to = strtoll(opt.gets("povfto", wide ? "2147483648" : "40000").c_str(), nullptr, 10);
+	if (povf_to >= sample_lo() && povf_to <= sample_hi()) die("modular: povfto lies outside int16 (outside int32 with wide=1)");
+	if (!wide && (povf_to < -(1 << 30) || povf_to > (1 << 30))) die("modular: povfto within +-2^30 (the residual is a 32-bit hybrid integer)");
+	if (wide && (povf_to < -((int64_t) 1 << 32) || povf_to > ((int64_t) 1 << 32))) die("modular: povfto within +-2^32");
 	if (povf_all >= 0 && lzp.force != FORCE_NONE) die("modular: povf works on a coded picture, lzforce has none");
 
 	// encodes the listed channels (sub-rectangles already cut out) into one stream; LZ77 replaces runs
@@ -1809,6 +1847,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	if (single) {
 		encs.emplace_back(gspec);
 		encode_image(ch, 0, 0, encs.back(), false, global_wp, frame_dist_mult);
+		if (want_src && !squeeze) dec = ch;   // (what was coded: a leaf with a multiplier quantises)
 	} else if (squeeze) {
 		// The decoder deals the channels out by size and shift (ISO 18181-1): LfGlobal takes the meta channels and the channels behind
 		// them that fit one group; an LfGroup section the channels shifted by >= 3 both ways, over its 8-groups-wide area; a pass-group
@@ -1847,7 +1886,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	} else {
 		// meta channels (palette) are decoded inside LfGlobal (num_gm_channels = nb_meta_channels, j40.h:6332)
 		encs.emplace_back(gspec);
-		if (nb_meta) { std::vector<Channel> meta(ch.begin(), ch.begin() + nb_meta); encode_image(meta, 0, 0, encs.back(), false, global_wp, frame_dist_mult); }
+		if (nb_meta) { std::vector<Channel> meta(ch.begin(), ch.begin() + nb_meta); encode_image(meta, 0, 0, encs.back(), false, global_wp, frame_dist_mult); if (want_src) for (int c = 0; c < nb_meta; ++c) dec[(size_t) c] = meta[(size_t) c]; }
 		// passes=P: every pass codes the whole group again (the reference decodes and pastes all channels in each pass,
 		// j40.h:7025-7033, so the last pass is what stays); earlier passes carry a perturbed picture
 		for (int pass = 0; pass < num_passes; ++pass) for (int g = 0; g < num_groups; ++g) {
@@ -1883,10 +1922,10 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 			if (local_rct >= 0 && sub.size() >= 3 && !own_palette) {
 				const int t1 = (local_rct + 5 * (g + pass)) % 42, t2 = (3 * t1 + 1) % 42;
 				TransformW a; a.kind = 0; a.begin_c = 0; a.rct_type = t1; group_tr.back().push_back(a);
-				if (t1 / 7 == 0 && t1 % 7 != 2) forward_rct(sub, 0, t1);
+				if (t1 / 7 == 0 && t1 % 7 != 2) forward_rct(sub, 0, t1); else src_exact = false;
 				if (g % 3 == 2) {
 					TransformW b; b.kind = 0; b.begin_c = (int) sub.size() - 3; b.rct_type = t2; group_tr.back().push_back(b);
-					if (t2 / 7 == 0 && t2 % 7 != 2) forward_rct(sub, b.begin_c, t2);
+					if (t2 / 7 == 0 && t2 % 7 != 2) forward_rct(sub, b.begin_c, t2); else src_exact = false;
 				}
 			}
 			if (group_tr.back().size()) samples_known = false;
@@ -1894,8 +1933,34 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 			// stream index of a pass group (j40.h:7013): 1 + 3 * num_lf_groups + 17 + pass * num_groups + gidx
 			const WPParams gwp = group_wp(pass * num_groups + g);
 			encode_image(sub, 0, 1 + 3 * num_lf_groups + 17 + pass * num_groups + g, encs.back(), local, groups_have_wp ? &gwp : nullptr, gw);
+			if (want_src && pass + 1 == num_passes) {   // the group as a reader has it once its own transforms are undone, last to first
+				std::vector<Channel> got = sub;
+				for (size_t k = group_tr.back().size(); k-- > 0; ) {
+					const TransformW &t = group_tr.back()[k];
+					if (t.kind == 1) expect_inverse_palette(got, t.num_c, t.nb_colours, t.nb_deltas, t.d_pred, bpp, groups_have_wp ? gwp : wp_default);
+					else expect_inverse_rct(got, t.begin_c, t.rct_type);
+				}
+				for (int c = nb_meta; c < total_ch; ++c) for (int y = 0; y < gh; ++y) memcpy(&dec[(size_t) c].at(gx, gy + y), &got[(size_t) (c - nb_meta)].at(0, y), sizeof(int32_t) * (size_t) gw);
+			}
 			if (samples_known && pass + 1 == num_passes) for (int c = nb_meta; c < total_ch; ++c) for (int y = 0; y < gh; ++y) for (int x = 0; x < gw; ++x) ch[(size_t) c].at(gx + x, gy + y) = sub[(size_t) (c - nb_meta)].at(x, y);
 		}
+	}
+	if (want_src) {
+		for (size_t k = transforms.size(); k-- > 0; ) {
+			const TransformW &t = transforms[k];
+			if (t.kind == 1) expect_inverse_palette(dec, t.num_c, t.nb_colours, t.nb_deltas, t.d_pred, bpp, global_wp ? *global_wp : wp_default);
+			else if (t.kind == 0) expect_inverse_rct(dec, t.begin_c, t.rct_type);
+		}
+		if (src_exact) {
+			if (orig.size() != dec.size()) die("modular: dumpsrc: the inverse transforms do not return the source picture's channels");
+			for (size_t c = 0; c < orig.size(); ++c) if (orig[c].w != dec[c].w || orig[c].h != dec[c].h || orig[c].px != dec[c].px) die("modular: dumpsrc: the forward transforms do not invert to the source picture");
+		}
+		const std::vector<Channel> &dump = src_exact ? orig : dec;
+		FILE *fp = fopen(dumpsrc.c_str(), "wb");
+		if (!fp) die("cannot write dumpsrc");
+		for (const Channel &c : dump) for (int y = 0; y < Hfull; ++y) for (int x0 = 0; x0 < Wfull; x0 += c.w)   // (repeat=K without squeeze: the base picture tiled)
+			if (fwrite(&c.px[(size_t) (y % c.h) * (size_t) c.w], 4, (size_t) std::min(c.w, Wfull - x0), fp) != (size_t) std::min(c.w, Wfull - x0)) die("cannot write dumpsrc");
+		fclose(fp);
 	}
 	std::vector<CodeSpecW> lspec(encs.size(), lspec_proto);
 	for (size_t i = 0; i < encs.size(); ++i) {
@@ -1984,7 +2049,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	cs.put(0, 1);                       // ImageMetadata: not all_default
 	write_extra_fields(cs);             // no extra fields (an animation: its header)
 	write_bit_depth(cs, bpp);
-	cs.put(1, 1);                       // modular_16bit_buffers
+	cs.put(wide ? 0 : 1, 1);            // modular_16bit_buffers (wide=1: 0, and nothing else differs)
 	{   // num_extra_channels U32(0, 1, 2 + u(4), 1 + u(12)), then one ExtraChannelInfo each (j40.h:3247-3290)
 		const int nec = extra + (alpha ? 1 : 0);
 		if (nec == 0) cs.put(0, 2); else if (nec == 1) cs.put(1, 2); else { cs.put(2, 2); cs.put((uint64_t) (nec - 2), 4); }
@@ -1995,7 +2060,15 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 			cs.put(0, 2);                   // dim_shift 0
 			cs.put(0, 2);                   // no name
 		}
-		if (alpha) cs.put(1, 1);            // d_alpha
+		if (alpha && !deep_alpha) cs.put(1, 1);   // d_alpha
+		else if (alpha) {                   // (wide=1, bpp != 8: an alpha channel of the image's depth)
+			cs.put(0, 1);
+			cs.put(0, 2);                   // type: enum selector 0 = alpha
+			write_bit_depth(cs, bpp);
+			cs.put(0, 2);                   // dim_shift 0
+			cs.put(0, 2);                   // no name
+			cs.put(0, 1);                   // not associated
+		}
 	}
 	// xyb=1 / ycbcr=1: the frame is flagged XYB / YCbCr; the reference applies no colour transform to Modular
 	// frames (j40.h:8209-8210, 7910) and renders the three channels as they are

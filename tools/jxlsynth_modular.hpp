@@ -177,6 +177,88 @@ inline int64_t predict(int pred, const Neigh &p, const WPState &wp) {  // j40.h:
 	die("bad predictor");
 }
 
+// The range of a coded sample: int16 (the image says modular_16bit_buffers = 1), or int32 with wide=1 (it says 0)
+inline int64_t &sample_lo() { static int64_t v = -32768; return v; }
+inline int64_t &sample_hi() { static int64_t v = 32767; return v; }
+inline int32_t wrap_sample(int64_t v) { return sample_hi() == 32767 ? (int32_t) (int16_t) (uint16_t) (uint64_t) v : (int32_t) (uint32_t) (uint64_t) v; }
+
+// ---- the picture a stream codes (dumpsrc=): where the writer did not run a forward transform -- a palette, whose picture IS the
+//      look-up, and the RCT types it takes the picture as already transformed for -- the samples a reader must arrive at are worked
+//      out here, in 64 bits wrapped to the sample type, from ISO 18181-1's statement of the inverse transforms ----
+inline void expect_inverse_rct(std::vector<Channel> &ch, int first, int type) {
+	static const int PERM[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {1, 0, 2}, {2, 1, 0}};
+	Channel *in[3] = {&ch[(size_t) first], &ch[(size_t) first + 1], &ch[(size_t) first + 2]};
+	const size_t n = in[0]->px.size();
+	for (size_t i = 0; i < n; ++i) {
+		const int64_t p0 = in[0]->px[i], p1 = in[1]->px[i], p2 = in[2]->px[i];
+		int64_t a = p0, b = p1, c = p2;
+		switch (type % 7) {
+		case 0: break;
+		case 1: c = p2 + p0; break;
+		case 2: c = p1 + p0; break;                    // (as the decoders here and j40.h:4353 have it)
+		case 3: b = p1 + p0; c = p2 + p0; break;
+		case 4: b = p1 + (p0 / 2 + p2 / 2 + (p0 & p2 & 1)); break;
+		case 5: b = p1 + p0 + (p2 >> 1); c = p2 + p0; break;
+		default: { const int64_t tmp = p0 - (p2 >> 1), q1 = p2 + tmp, q2 = tmp - (p1 >> 1); a = q2 + p1; b = q1; c = q2; }
+		}
+		in[0]->px[i] = wrap_sample(a); in[1]->px[i] = wrap_sample(b); in[2]->px[i] = wrap_sample(c);
+	}
+	Channel out[3] = {*in[0], *in[1], *in[2]};
+	for (int j = 0; j < 3; ++j) ch[(size_t) (first + PERM[type / 7][j])] = out[j];
+}
+// the spec's 72 palette delta triples; index 2k is triple k, 2k + 1 its negation
+static const int EXPECT_PALETTE_DELTAS[72][3] = {
+	{0, 0, 0}, {4, 4, 4}, {11, 0, 0}, {0, 0, -13}, {0, -12, 0}, {-10, -10, -10}, {-18, -18, -18}, {-27, -27, -27},
+	{-18, -18, 0}, {0, 0, -32}, {-32, 0, 0}, {-37, -37, -37}, {0, -32, -32}, {24, 24, 45}, {50, 50, 50}, {-45, -24, -24},
+	{-24, -45, -45}, {0, -24, -24}, {-34, -34, 0}, {-24, 0, -24}, {-45, -45, -24}, {64, 64, 64}, {-32, 0, -32}, {0, -32, 0},
+	{-32, 0, 32}, {-24, -45, -24}, {45, 24, 45}, {24, -24, -45}, {-45, -24, 24}, {80, 80, 80}, {64, 0, 0}, {0, 0, -64},
+	{0, -64, -64}, {-24, -24, 45}, {96, 96, 96}, {64, 64, 0}, {45, -24, -24}, {34, -34, 0}, {112, 112, 112}, {24, -45, -45},
+	{45, 45, -24}, {0, -32, 32}, {24, -24, 45}, {0, 96, 96}, {45, -24, 24}, {24, -45, -24}, {-24, -45, 24}, {0, -64, 0},
+	{96, 0, 0}, {128, 128, 128}, {64, 0, 64}, {144, 144, 144}, {96, 96, 0}, {-36, -36, 36}, {45, -24, -45}, {45, -45, -24},
+	{0, 0, -96}, {0, 128, 128}, {0, 96, 0}, {45, 24, -45}, {-128, 0, 0}, {24, -45, 24}, {-45, 24, -45}, {64, 0, -64},
+	{64, -64, -64}, {96, 0, 96}, {45, -45, 24}, {24, 45, -45}, {64, 64, -64}, {128, 128, 0}, {0, 0, -128}, {-24, 45, -45},
+};
+// `ch` = {palette (meta channel), index channel, the rest}: the index channel becomes num_c colour channels in its place
+inline void expect_inverse_palette(std::vector<Channel> &ch, int num_c, int nb_colours, int nb_deltas, int d_pred, int bpp, const WPParams &wpp) {
+	const Channel pal = ch[0], idx = ch[1];
+	std::vector<Channel> out;
+	for (int i = 0; i < num_c; ++i) {
+		Channel c(idx.w, idx.h);
+		WPState wp;
+		if (nb_deltas > 0 && d_pred == 6) wp.init(idx.w, wpp);
+		for (int y = 0; y < idx.h; ++y) for (int x = 0; x < idx.w; ++x) {
+			int64_t k = wrap_sample(idx.at(x, y)), val;
+			const bool is_delta = k < nb_deltas;
+			if (k < 0) {
+				if (i < 3) {
+					k = wrap_sample(~k % 143);
+					const int64_t entry = k + 1;
+					val = EXPECT_PALETTE_DELTAS[entry >> 1][i];
+					if (entry & 1) val = -val;
+					if (bpp > 8) val = val * ((int64_t) 1 << (std::min(bpp, 24) - 8));
+				} else val = 0;
+			} else if (k < nb_colours) val = pal.at((int) k, i);
+			else {
+				k = wrap_sample(k - nb_colours);
+				if (k < 64) val = (i < 3 ? k >> (2 * i) : 0) * (((int64_t) 1 << bpp) - 1) / 4 + ((int64_t) 1 << std::max(0, bpp - 3));
+				else { k = wrap_sample(k - 64); for (int j = 0; j < i; ++j) k = k / 5; val = (k % 5) * (((int64_t) 1 << bpp) - 1) / 4; }
+			}
+			val = wrap_sample(val);
+			if (nb_deltas > 0) {
+				const Neigh p = neighbours(c, x, y);
+				wp.before(x, y, p.w, p.n, p.nw, p.ne, p.nn);
+				if (is_delta) val = wrap_sample(val + predict(d_pred, p, wp));
+				wp.after(x, y, val);
+			}
+			c.at(x, y) = (int32_t) val;
+		}
+		out.push_back(c);
+	}
+	std::vector<Channel> next(out);
+	for (size_t c = 2; c < ch.size(); ++c) next.push_back(ch[c]);
+	ch.swap(next);
+}
+
 // Encodes one channel of a Modular image into `enc` (decode order), mirroring the decoder's tree
 // walk. `chans`/`cidx` give access to previous channels for properties >= 16; `sidx` is the stream
 // index property. `lossy_quant` > 1 quantises residuals (the channel is updated with what the
@@ -244,13 +326,15 @@ inline void encode_channel(const MATree &tree, std::vector<Channel> &chans, int 
 		int64_t diff = target - pr - lf.offset;
 		int64_t q = mult == 1 ? diff : (diff >= 0 ? (diff + mult / 2) / mult : -((-diff + mult / 2) / mult));
 		int64_t recon = q * mult + lf.offset + pr;
-		if (overflow_here) { while (recon >= -32768 && recon <= 32767) recon = (povf_to < 0 ? --q : ++q) * mult + lf.offset + pr; }
+		const int64_t lo = sample_lo(), hi = sample_hi();   // (int16, or int32 with wide=1)
+		if (overflow_here) { while (recon >= lo && recon <= hi) recon = (povf_to < 0 ? --q : ++q) * mult + lf.offset + pr; }
 		else if (mult > 1) {   // a coarse leaf may round past the end of the range: one step back
-			while (recon > 32767) recon = --q * mult + lf.offset + pr;
-			while (recon < -32768) recon = ++q * mult + lf.offset + pr;
+			while (recon > hi) recon = --q * mult + lf.offset + pr;
+			while (recon < lo) recon = ++q * mult + lf.offset + pr;
 		}
-		if (!overflow_here && (recon < -32768 || recon > 32767)) die("modular sample out of int16 range");
-		if (overflow_here) recon = 32767;
+		if (!overflow_here && (recon < lo || recon > hi)) die(hi == 32767 ? "modular sample out of int16 range" : "modular sample out of int32 range");
+		if (q < -((int64_t) 1 << 31) || q >= ((int64_t) 1 << 31)) die("modular: a residual leaves the 32 bits a packed hybrid integer has (readers refuse more than 30: iovf)");
+		if (overflow_here) recon = hi;
 		c.at(x, y) = (int32_t) recon;
 		enc.add((uint32_t) lf.ctx, pack_signed((int32_t) q));
 		wp.after(x, y, recon);
