@@ -46,7 +46,7 @@ YCBCRMAIN = $(if $(wildcard tests/hostsim/ycbcr_main.cpp),build/ycbcr_main build
 ORIENTMAIN = $(if $(wildcard tests/hostsim/orient_main.cpp),build/orient_main build/orient_main_san)
 WIDESIM = $(if $(wildcard tests/hostsim/wide_sim.cpp),build/libwidesim.so)
 WIDEMAIN = $(if $(wildcard tests/hostsim/wide_main.cpp),build/wide_main build/wide_main_san)
-hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/libhostsim_compose.so build/libhostsim_blend.so build/libhostsim_scale.so build/libhostsim_ycbcr.so build/libhostsim_orient.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN) $(SCALEMAIN) $(YCBCRMAIN) $(ORIENTMAIN) $(WIDESIM) $(WIDEMAIN)
+hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/libhostsim_compose.so build/libhostsim_blend.so build/libhostsim_scale.so build/libhostsim_ycbcr.so build/libhostsim_orient.so build/libhostsim_lfframe.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN) $(SCALEMAIN) $(YCBCRMAIN) $(ORIENTMAIN) $(WIDESIM) $(WIDEMAIN)
 # test-only glue: parses a stream with the product's host parser, takes the plan view and hands it to
 # the CPU oracle (oracle/libj40oracle.so)
 build/liboracle_driver.so: tests/oracle_driver.c build/libj40hip.so oracle/hotpath_oracle.c include/j40hip.h
@@ -89,6 +89,12 @@ REGIONSIM_SRC = tests/hostsim/region_sim.cpp $(SRC)/plan_build.cpp $(SRC)/plan_f
 build/libhostsim_region.so: $(REGIONSIM_SRC) $(wildcard $(SRC)/device/*.h) $(wildcard $(SRC)/*.hpp) include/j40hip.h
 	@mkdir -p build
 	$(CXX) $(HOSTSIM_FLAGS) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -o $@ $(REGIONSIM_SRC) -lpthread
+
+# LF frames on the CPU (tests/test_lf_frames.py): device/lf_frame_dev.h's gather, LF index and block-context functions over the host plan
+LFFRAMESIM_SRC = tests/hostsim/lf_frame_sim.cpp $(SRC)/plan_build.cpp $(SRC)/plan_front.cpp $(SRC)/entropy.cpp $(SRC)/modular.cpp $(SRC)/tables.cpp $(SRC)/frame.cpp
+build/libhostsim_lfframe.so: $(LFFRAMESIM_SRC) $(HOSTSIM_HDR) include/j40hip.h
+	@mkdir -p build
+	$(CXX) $(HOSTSIM_FLAGS) -DJ40_LANE_EV_FLUSH=$(EVENT_RING) -o $@ $(LFFRAMESIM_SRC) -lpthread
 
 # frame composition on the CPU (tests/test_frames.py): device/compose_dev.h's row functions over a canvas in host memory
 build/libhostsim_compose.so: tests/hostsim/compose_sim.cpp $(SRC)/device/compose_dev.h $(SRC)/device/region_dev.h $(SRC)/device/plan.h

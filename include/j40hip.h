@@ -366,7 +366,7 @@ J40HIP_API void j40hip_frame_region(const j40hip_frame *f, int32_t out[12]);
  *      pixels the reference pins. An opaque frame stays A = 255 (65535).
  *      set: any parsed frame, uploaded or not; it holds from the next decode on, across uploads. A shift outside 0..2: "rnge". A shift
  *      above 0 is refused with "Usc?" for a frame with a region or a partial group range and for a handle j40hip_sequence_frame handed
- *      out, with "Ulf?" for an LF-only frame; j40hip_frame_set_region and j40hip_frame_set_group_range on a frame with a shift above 0
+ *      out (other than the main frame of an LF-frame still, see J40HIP_SEQ_LFFRAME), with "Ulf?" for an LF-only frame; j40hip_frame_set_region and j40hip_frame_set_group_range on a frame with a shift above 0
  *      return "Usc?": whichever setter comes second is refused. A refused call leaves the frame as it was. Shift 0 always succeeds.
  *      At a shift above 0 j40hip_frame_decode / _timed / _decode_to_host write ow x oh pixels; stride_bytes below 4 * ow (u8) or 8 * ow
  *      (u16) is "rnge" before anything is launched; nothing outside the ow pixels of each of the oh rows is written;
@@ -403,7 +403,7 @@ J40HIP_API uint32_t j40hip_kat_device_downscale(void *out_dev, size_t out_stride
  *      one: the two differ in the edge cells), and a region stays a rectangle in stored coordinates (j40hip_frame_orient_rect maps one).
  *      set: mode -1 follows the environment (J40HIP_ORIENT=1 applies the orientation; the default), 0 is stored order, 1 applies it. Any
  *      parsed frame, uploaded or not; it holds from the next decode on, across uploads. A handle j40hip_sequence_frame handed out refuses
- *      mode 1 with "Uor?" and is never oriented by the environment; a refused call leaves the frame as it was.
+ *      mode 1 with "Uor?" (other than the main frame of an LF-frame still, see J40HIP_SEQ_LFFRAME) and is never oriented by the environment; a refused call leaves the frame as it was.
  *      A partial group range (j40hip_frame_set_group_range: the decode writes that range's rectangles and leaves the rest of the
  *      caller's image alone) and an orientation in force exclude each other, since there is no whole stored-order image to turn:
  *      mode 1 on a frame with a partial range and o other than 1 is "Uor?", j40hip_frame_set_group_range with a partial range on a
@@ -536,8 +536,8 @@ J40HIP_API uint32_t j40hip_batch_reset(j40hip_batch *b, j40hip_frame *const *fra
  *      (duration > 0, or the last frame) and/or saved into one of four reference slots for later frames to draw over. Served: frames
  *      of type 0 and 3 whose blend mode is Replace for the colour channels and every extra channel, with any crop (negative offsets,
  *      beyond the canvas), any source slot, any save_as_reference; animations (have_animation, durations; timecodes skipped) and
- *      layers. Refused with "TODO", reported for the frame it comes from: any other blend mode, frame types 1 and 2, use_lf_frame, and
- *      whatever a single frame is refused for.
+ *      layers. Refused with "TODO", reported for the frame it comes from: any other blend mode, frame type 2, frame type 1 and
+ *      use_lf_frame (these two unless J40HIP_SEQ_LFFRAME is given, below), and whatever a single frame is refused for.
  *      With J40HIP_SEQ_BLEND (or J40HIP_BLEND=1 in the environment) the blend modes Add, Blend, MulAdd and Mul are served as well,
  *      for the colour channels and for the alpha channel the pixels carry (the first extra channel of type alpha), each with a mode
  *      of its own; the entries of the other extra channels are not looked at, `clamp` is read and changes nothing (a rendered alpha
@@ -556,8 +556,24 @@ J40HIP_API uint32_t j40hip_batch_reset(j40hip_batch *b, j40hip_frame *const *fra
  *      not a sequence: NULL and "Usq?" (use j40hip_frame_parse). NULL and the code when the image header or the first frame's header
  *      fails. A later frame whose header or TOC fails, or that is refused, ends the index: it is the last row and carries its code.
  *      flags: bit 0 as j40hip_frame_parse_ex's, applied to every frame handle; bit 1 J40HIP_SEQ_BLEND; J40HIP_PARSE_WIDE (8) as
- *      j40hip_frame_parse_ex's: an image with 32-bit Modular buffers is opened and its Modular frames are served. ---- */
+ *      j40hip_frame_parse_ex's: an image with 32-bit Modular buffers is opened and its Modular frames are served.
+ *      With J40HIP_SEQ_LFFRAME (or J40HIP_LFFRAME=1 in the environment) LF frames are served: a frame of type 1 with lf_level L in
+ *      1..4 is ceil(image / 8^L) in size, is decoded like any VarDCT frame and never shown nor saved into a reference slot; its three
+ *      XYB planes (float32, as the inverse transforms or -- where the restoration mode runs them -- the restoration filters leave them)
+ *      are kept in LF slot L - 1. A later frame with use_lf_frame (of level L, 0 for the other types) carries no LfCoefficients
+ *      stream: the LF sample of its cell (x8, y8) is sample (x8, y8) of slot L, channel by channel, with no dequantisation factor and
+ *      no adaptive smoothing (k_lf_from_frame); its LF indices count the thresholds t with sample > (float) t * mult_lf of that
+ *      channel at extra_precision 0 (k_lf_frame_bctx then looks the block contexts up again) -- PARITY UNPINNED, like what an LF
+ *      frame stores: the reference refuses such streams. "lfno": the slot was never filled (found at j40hip_sequence_open, it ends the
+ *      index); "lfsz": the stored picture is not ceil(w / 8) x ceil(h / 8). Still "TODO" with the switch: a Modular LF frame, an image
+ *      that is not XYB encoded or has extra channels, use_lf_frame on a YCbCr frame. The main frame of such a still (a regular frame
+ *      with use_lf_frame that covers the canvas) is the one handle of a sequence that takes j40hip_frame_set_scale and
+ *      j40hip_frame_set_orientation, for decodes of its own once the playback has filled its LF slot; the playback refuses it
+ *      ("Usc?" / "Uor?") while either is set. j40hip_sequence_rewind unbinds the handles from the slots ("lfno" until played again). Outside a sequence (j40hip_frame_parse*, batches, the pipeline) such
+ *      streams stay "TODO", and j40hip_frame_decode_lf of a frame with use_lf_frame is "TODO": the LF frame's own handle decodes
+ *      that picture. ---- */
 #define J40HIP_SEQ_BLEND 2u   /* j40hip_sequence_open: serve the blend modes Add (1), Blend (2), MulAdd (3) and Mul (4) too */
+#define J40HIP_SEQ_LFFRAME 16u   /* j40hip_sequence_open: serve LF frames (type 1) and the frames that take their LF image from one (use_lf_frame) */
 typedef struct j40hip_sequence j40hip_sequence;
 J40HIP_API j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads, uint32_t flags, uint32_t *err);
 J40HIP_API void j40hip_sequence_free(j40hip_sequence *s);
@@ -574,6 +590,12 @@ J40HIP_API void j40hip_sequence_frame_info(const j40hip_sequence *s, int64_t k, 
  * alpha_chan and [5] clamp, [6] the source slot, [7] whether the frame goes through k_frame_blend (J40HIP_SEQ_BLEND, a mode other
  * than Replace in [0] or [1], and the frame is not refused). k out of range: zeros. */
 J40HIP_API void j40hip_sequence_frame_blend(const j40hip_sequence *s, int64_t k, int32_t *out8);
+/* LF frames (J40HIP_SEQ_LFFRAME). out4: [0] the row's lf_level (1..4 for an LF frame, else 0), [1] use_lf_frame, [2] the row it takes
+ * its LF image from or -1, [3] 0. k out of range: zeros. */
+J40HIP_API void j40hip_sequence_frame_lf(const j40hip_sequence *s, int64_t k, int32_t *out4);
+/* debug read-back (synchronises the device): plane c (0 X, 1 Y, 2 B) of LF slot `level` - 1 as the playback last filled it, tightly
+ * packed floats of the LF frame's size. "rnge": no such slot, or nothing stored in it since the last rewind. */
+J40HIP_API uint32_t j40hip_sequence_read_lf_slot(j40hip_sequence *s, int32_t level, int32_t c, float *out);
 /* Coded frame k, fully parsed at the first call: an ordinary frame handle of the frame's own (crop) size over a copy of the frame's
  * own bytes, owned by the sequence (do not free it). Every single-frame and batch entry point takes it -- upload, decode, region,
  * LF preview, alpha mode, status. NULL and the code for a frame that is refused or does not parse. */

@@ -127,6 +127,7 @@ def lib():
         "j40hip_sequence_next_to_host": (u32, [vp, vp, sz]), "j40hip_sequence_rewind": (None, [vp]), "j40hip_sequence_status": (u32, [vp, C.POINTER(i64)]),
         "j40hip_kat_device_compose": (u32, [vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, u32, u32, i32, vp]),
         "j40hip_sequence_frame_blend": (None, [vp, i64, vp]),
+        "j40hip_sequence_frame_lf": (None, [vp, i64, vp]), "j40hip_sequence_read_lf_slot": (u32, [vp, i32, i32, vp]),
         "j40hip_kat_device_blend": (u32, [vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, u32, u32, i32, i32, i32, vp]),
         "j40hip_frame_restoration": (None, [vp, vp]), "j40hip_frame_set_restoration": (None, [vp, C.c_int]), "j40hip_frame_sharpness": (C.c_int, [vp, i64, vp]),
         "j40hip_frame_set_alpha": (u32, [vp, C.c_int]), "j40hip_frame_alpha": (None, [vp, vp]),
@@ -233,7 +234,7 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
     scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
     (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
@@ -245,7 +246,41 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     orient=True: the picture in the orientation the stream carries (Frame.set_orientation(1)), [ow, oh] swapped for orientations 5 to
     8, whatever J40HIP_ORIENT says; likewise through the thin C-ABI on device 0.
     wide=True: an image with 32-bit Modular buffers (every 16-bit lossless image) is served for this call whatever J40HIP_WIDE says
-    (PARSE_WIDE), likewise through the thin C-ABI on device 0; its VarDCT frames are "TODO"."""
+    (PARSE_WIDE), likewise through the thin C-ABI on device 0; its VarDCT frames are "TODO".
+    lf_frames=True: a still whose LF image is a frame of its own (LF frames, then the frame with use_lf_frame) is served for this call
+    whatever J40HIP_LFFRAME says: through a Sequence on device 0, the first displayed canvas. It combines with fmt, scale and orient
+    ("TODO" with the other switches): the playback fills the LF slots at full size, then the main frame's own handle -- which keeps
+    its LF source -- is decoded once more at the scale and / or in the orientation, as any frame is (Frame.set_scale,
+    Frame.set_orientation; a refusal where the shown frame is not a full-canvas frame with use_lf_frame). A stream that is no
+    sequence is decoded as without it."""
+    if lf_frames:
+        if alpha or ycbcr or wide:
+            return "TODO", None
+        try:
+            seq = Sequence(data, lf_frames=True)
+        except J40Error as e:
+            if e.code != "Usq?":
+                return e.code, None
+            seq = None
+        if seq is not None:
+            try:
+                seq.set_output_format(fmt)
+                seq.upload(0)
+                err, out = seq.next_to_host()
+                if not err and (scale or orient):
+                    shown = [k for k in range(seq.num_frames) if seq.frame_info(k)["shown"]]
+                    fr = seq.frame(shown[0])
+                    code = fr.set_scale(scale) if scale else ""
+                    if not code and orient:
+                        code = fr.set_orientation(1)
+                    if code:
+                        return code, None
+                    err, out = fr.decode_to_host()
+                return err, (None if err else out)
+            except J40Error as e:
+                return e.code, None
+            finally:
+                seq.close()
     if alpha or scale or ycbcr or orient or wide:
         try:
             fr = Frame(data, ycbcr=bool(ycbcr), wide=bool(wide))
@@ -893,6 +928,7 @@ def decode_lf_many(datas, fmt=J40_U8X4, device=0):
 
 
 SEQ_BLEND = 2   # j40hip_sequence_open's flag J40HIP_SEQ_BLEND: the blend modes Add, Blend, MulAdd and Mul are served
+SEQ_LFFRAME = 16   # ... J40HIP_SEQ_LFFRAME: LF frames (type 1) and the frames with use_lf_frame are served
 SEQUENCE_BLEND_FIELDS = ("mode", "alpha_mode", "alpha_chan", "clamp", "alpha_alpha_chan", "alpha_clamp", "src", "blended")
 SEQUENCE_FRAME_FIELDS = ("x0", "y0", "w", "h", "duration", "is_last", "shown", "type", "blend", "src", "save_as_reference", "saved",
                          "offset", "end", "first_section", "code", "tps_num", "tps_den", "loops", "canvas_w", "canvas_h")
@@ -901,13 +937,16 @@ SEQUENCE_FRAME_FIELDS = ("x0", "y0", "w", "h", "duration", "is_last", "shown", "
 class Sequence:
     """the coded frames of one codestream -- an animation or a layered still -- and their playback (j40hip_sequence, include/j40hip.h):
     an index over headers and TOCs on the host, every coded frame an ordinary Frame, the displayed canvases composed on the device.
-    blend=True (or J40HIP_BLEND=1): frames with the blend modes Add, Blend, MulAdd and Mul are served too, else "TODO" for such a frame"""
+    blend=True (or J40HIP_BLEND=1): frames with the blend modes Add, Blend, MulAdd and Mul are served too, else "TODO" for such a frame.
+    lf_frames=True (or J40HIP_LFFRAME=1): LF frames (type 1) and the frames that take their LF image from one (use_lf_frame) are
+    served too, else "TODO"; an LF frame is a row that is neither shown nor saved (frame_lf)"""
 
-    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False):
+    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False):
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags | (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0), C.byref(err))
+        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0)
+        self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags, C.byref(err))
         if not self.h:
             raise J40Error(err4(err.value), "in j40hip_sequence_open")
         self.num_frames, self.num_shown = int(L.j40hip_sequence_num_frames(self.h)), int(L.j40hip_sequence_num_shown(self.h))
@@ -952,6 +991,21 @@ class Sequence:
         out = np.zeros(8, np.int32)
         lib().j40hip_sequence_frame_blend(self.h, k, out.ctypes.data)
         return dict(zip(SEQUENCE_BLEND_FIELDS, out.tolist()))
+
+    def frame_lf(self, k):
+        """LF frames: coded frame k's lf_level (0: not an LF frame), use_lf_frame and the row it takes its LF image from (-1: none)"""
+        out = np.zeros(4, np.int32)
+        lib().j40hip_sequence_frame_lf(self.h, k, out.ctypes.data)
+        return {"lf_level": int(out[0]), "use_lf_frame": int(out[1]), "lf_src": int(out[2])}
+
+    def read_lf_slot(self, level, w, h):
+        """debug read-back: the picture LF slot level - 1 holds, [3, h, w] float32 (X, Y, B); w x h is the LF frame's size"""
+        out = np.zeros((3, h, w), np.float32)
+        for c in range(3):
+            code = lib().j40hip_sequence_read_lf_slot(self.h, level, c, out[c].ctypes.data)
+            if code:
+                raise J40Error(err4(code), "in j40hip_sequence_read_lf_slot")
+        return out
 
     def frame(self, k):
         """coded frame k as a Frame the sequence owns: crop-sized, for every single-frame and batch entry point. It lives as long as the
@@ -1001,13 +1055,14 @@ class Sequence:
         return err4(code), int(k.value)
 
 
-def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False):
+def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False):
     """every displayed frame of an animation or a layered still: ([(rgba ndarray [height, width, 4], duration in ticks), ...],
     (tps_num, tps_den, loops)). alpha=True: VarDCT frames keep their alpha channel (Frame.set_alpha(1); J40Error where that refuses).
     blend=True: frames with a blend mode other than Replace are composed too (Sequence's blend=), else such a frame raises "TODO".
     wide=True: an image with 32-bit Modular buffers is served (Sequence's wide=; its Modular frames only).
+    lf_frames=True: LF frames and the frames that take their LF image from one are served (Sequence's lf_frames=), else "TODO".
     A frame that fails raises J40Error with its code. A stream whose first frame is its last is not a sequence ("Usq?"): decode()."""
-    seq = Sequence(data, blend=blend, wide=wide)
+    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames)
     try:
         seq.set_output_format(fmt)
         if alpha:

@@ -40,6 +40,11 @@ struct j40hip_frame {
 	int orient = -1;
 	int32_t orient_applied = 0;
 	int64_t orient_staging_bytes = 0;
+	// a frame with use_lf_frame (a sequence with J40HIP_SEQ_LFFRAME): the LF frame's picture its next decodes take their LF samples from --
+	// three device planes of float32 (X, Y, B), lf_src_w x lf_src_h tightly packed, bound by the playback (j40hip_frame_bind_lf_source);
+	// null: nothing bound, such a frame's decode is "lfno"
+	const float *lf_src[3] = {nullptr, nullptr, nullptr};
+	int32_t lf_src_w = 0, lf_src_h = 0;
 	int threads = 1;                 // what the frame was parsed with: the plan build at upload may use as many (plan_build.cpp)
 	// backing storage of the plan views (include/j40hip.h)
 	struct Views {
@@ -77,11 +82,13 @@ struct j40hip_sequence {
 		// whether the frame goes through k_frame_blend (a mode other than Replace in the colour channels or the rendered alpha)
 		int8_t alpha_mode = 0, src = 0;
 		bool blended = false;
+		int32_t lf_src = -1;         // LF frames (J40HIP_SEQ_LFFRAME): the row whose picture this frame's LF samples are (use_lf_frame), -1: none
 	};
 	std::vector<Row> rows;
 	std::vector<j40hip_frame *> frames;   // [rows.size()], parsed when first asked for
 	int threads = 1; uint32_t flags = 0;
 	bool blend = false;              // the blend modes other than Replace are served (J40HIP_SEQ_BLEND or J40HIP_BLEND=1)
+	bool lf_frames = false;          // LF frames and use_lf_frame are served (J40HIP_SEQ_LFFRAME or J40HIP_LFFRAME=1)
 	int32_t alpha_ec = -1;           // the extra channel that is rendered as A (rendered_alpha_channel); -1: none
 	int32_t output_format = J40HIP_U8X4;
 	j40hip_sequence_device *dev = nullptr;
@@ -103,11 +110,21 @@ inline bool j40hip_ycbcr_on(const j40hip_frame *h) {
 	return asked && !h->from_view && !h->from_sequence;
 }
 
+// A handle a sequence hands out for the main frame of a still whose LF image is a frame of its own: a regular frame with use_lf_frame
+// that covers the canvas. Once the playback has filled its LF slot (and bound it) the handle decodes alone like any frame, so it takes
+// a scale and the orientation, which every other handle of a sequence refuses; the playback refuses it while either is set
+inline bool j40hip_lf_still_handle(const j40hip_frame *h) {
+	const j40hip::FrameHeader &fh = h->frame.fh;
+	return h->from_sequence && fh.use_lf_frame && fh.type != 1 && fh.x0 == 0 && fh.y0 == 0 && fh.width == h->frame.im.width && fh.height == h->frame.im.height;
+}
+
 // the orientation the next decode writes in: the stream's where the mode (or J40HIP_ORIENT=1) applies it, else 1 (stored order). A handle
-// a sequence hands out is never oriented: the playback writes stored order
+// a sequence hands out is never oriented: the playback writes stored order -- but for the main frame of an LF-frame still, and that one
+// only where the mode was set on the handle itself (the environment never orients a sequence's handles)
 inline int32_t j40hip_orientation_in_force(const j40hip_frame *h) {
+	if (h->from_sequence) return h->orient == 1 && j40hip_lf_still_handle(h) ? h->frame.im.orientation : 1;
 	const bool asked = h->orient >= 0 ? h->orient == 1 : j40hip::orient_env();
-	return asked && !h->from_sequence ? h->frame.im.orientation : 1;
+	return asked ? h->frame.im.orientation : 1;
 }
 
 // The size of the stored-order image the next decode makes, which the orientation is applied to: the region's rectangle, else the frame
@@ -117,6 +134,13 @@ inline void j40hip_stored_out_size(const j40hip_frame *h, int32_t *W, int32_t *H
 	const int32_t s = 1 << h->scale;
 	*W = h->region_set ? h->region[2] : (h->frame.fh.width + s - 1) >> h->scale;
 	*H = h->region_set ? h->region[3] : (h->frame.fh.height + s - 1) >> h->scale;
+}
+
+// internal (a sequence's playback, device/runtime_seq.hip): the LF frame's picture the next decodes of a frame with use_lf_frame read --
+// device planes X, Y, B of w x h floats each, which must stay where they are until those decodes have run
+inline void j40hip_frame_bind_lf_source(j40hip_frame *h, const float *const planes[3], int32_t w, int32_t hh) {
+	for (int c = 0; c < 3; ++c) h->lf_src[c] = planes[c];
+	h->lf_src_w = w; h->lf_src_h = hh;
 }
 
 extern "C" j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads, uint32_t flags, j40hip::LfDeviceDecoder lf_decoder, void *lf_ctx, uint32_t *err);

@@ -159,15 +159,17 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 		extract_codestream((const uint8_t *) buf, size, &s->cs, &s->cs_size, &s->cs_storage);
 		s->threads = threads < 1 ? 1 : threads > 16 ? 16 : threads; s->flags = flags;
 		s->blend = (flags & J40HIP_SEQ_BLEND) != 0 || env_on("J40HIP_BLEND", false);   // (looked at with every sequence that is opened)
+		s->lf_frames = (flags & J40HIP_SEQ_LFFRAME) != 0 || env_on("J40HIP_LFFRAME", false);
 		size_t at = 0;
 		parse_image_header(s->cs, s->cs_size, &s->im, &at, (flags & J40HIP_PARSE_WIDE) != 0 || wide_env());
 		s->alpha_ec = rendered_alpha_channel(s->im);
+		int32_t lf_row[4] = {-1, -1, -1, -1};   // the row whose picture LF slot k holds when the playback gets here
 		for (;;) {
 			j40hip_sequence::Row row;
 			Toc toc;
 			row.offset = at;
 			try {
-				parse_sequence_frame_header(s->cs, s->cs_size, at, s->im, s->blend, &row.fh, &toc);
+				parse_sequence_frame_header(s->cs, s->cs_size, at, s->im, s->blend, s->lf_frames, &row.fh, &toc);
 				row.first_section = at + toc.first_offset; row.end = at + toc.end_offset;
 				// (a frame whose sections the stream does not hold to their end: whatever follows it cannot be found)
 				if (row.end > s->cs_size) row.code = E4("shrt");
@@ -182,13 +184,24 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 				row.src = (int8_t) (slot < 0 ? 0 : slot);
 				row.alpha_mode = s->alpha_ec >= 0 ? row.fh.ec_blend[(size_t) s->alpha_ec].mode : 0;
 				row.blended = s->blend && (row.fh.blend.mode != 0 || row.alpha_mode != 0);
+				if (row.fh.use_lf_frame && !row.code) {
+					// its LF samples are the picture in LF slot lf_level (0 for a frame that is no LF frame): filled, and of exactly the cells' size
+					const int32_t slot = row.fh.lf_level;
+					if (slot > 3 || lf_row[slot] < 0) row.code = E4("lfno");
+					else {
+						const FrameHeader &src = s->rows[(size_t) lf_row[slot]].fh;
+						if (src.width != (row.fh.width + 7) / 8 || src.height != (row.fh.height + 7) / 8) row.code = E4("lfsz");
+						row.lf_src = lf_row[slot];
+					}
+				}
+				if (row.fh.type == 1 && !row.code) lf_row[row.fh.lf_level - 1] = (int32_t) s->rows.size();
 			} catch (const DecodeError &e) { row.code = e.code; }
 			if (s->rows.empty()) {
 				if (row.code) raise(row.code);
 				J40HIP_SHOULD(!row.fh.is_last, "Usq?");   // not a sequence: j40hip_frame_parse's
 			}
 			row.shown = !row.code && (row.fh.duration > 0 || row.fh.is_last);
-			row.saved = !row.code && !row.fh.is_last && (row.fh.duration == 0 || row.fh.save_as_ref != 0);
+			row.saved = !row.code && !row.fh.is_last && (row.fh.duration == 0 || row.fh.save_as_ref != 0) && row.fh.type != 1;   // (an LF frame goes to its LF slot only)
 			s->rows.push_back(row);
 			if (row.code || row.fh.is_last) break;
 			at = row.end;
@@ -235,6 +248,14 @@ void j40hip_sequence_frame_blend(const j40hip_sequence *s, int64_t k, int32_t *o
 	out[4] = a.alpha_chan; out[5] = a.clamp; out[6] = r.src; out[7] = r.blended && !r.code;
 }
 
+void j40hip_sequence_frame_lf(const j40hip_sequence *s, int64_t k, int32_t *out) {
+	if (!out) return;
+	memset(out, 0, sizeof(int32_t) * 4);
+	if (!s || k < 0 || k >= (int64_t) s->rows.size()) return;
+	const j40hip_sequence::Row &r = s->rows[(size_t) k];
+	out[0] = r.fh.lf_level; out[1] = r.fh.use_lf_frame; out[2] = r.lf_src;
+}
+
 j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err) {
 	if (err) *err = 0;
 	if (!s || k < 0 || k >= (int64_t) s->rows.size()) { if (err) *err = E4("rnge"); return nullptr; }
@@ -254,7 +275,7 @@ j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err
 		h->cs = h->cs_storage.data();
 		h->bare_codestream = true;
 		h->frame.defer_lf_tail = (s->flags & 1u) != 0;
-		h->frame.seq_im = &s->im; h->frame.seq_blend = s->blend; h->frame.allow_wide = (s->flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
+		h->frame.seq_im = &s->im; h->frame.seq_blend = s->blend; h->frame.allow_lf_frame = s->lf_frames; h->frame.allow_wide = (s->flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
 		parse_frame(h->cs, h->cs_size, &h->frame, s->threads);
 		h->threads = s->threads;
 		h->output_format = s->output_format;
@@ -353,7 +374,7 @@ uint32_t j40hip_frame_set_scale(j40hip_frame *h, int32_t shift) {
 	if (!h || shift < 0 || shift > 2) return j40hip::ERR_RNGE;
 	if (shift > 0) {
 		if (h->frame.lf_only) return E4("Ulf?");
-		if (h->region_set || h->partial_range || h->from_sequence) return E4("Usc?");
+		if (h->region_set || h->partial_range || (h->from_sequence && !j40hip_lf_still_handle(h))) return E4("Usc?");   // (the main frame of an LF-frame still: capi.hpp)
 	}
 	if (shift != h->scale) { h->scale_staged = -1; h->scale_staging_bytes = 0; }
 	h->scale = shift;
@@ -372,7 +393,7 @@ void j40hip_frame_scale(const j40hip_frame *h, int32_t out[5]) {
 // ---- oriented output (include/j40hip.h; device/orient_dev.h has the arithmetic) ----
 uint32_t j40hip_frame_set_orientation(j40hip_frame *h, int mode) {
 	if (!h) return j40hip::ERR_RNGE;
-	if (mode > 0 && h->from_sequence) return E4("Uor?");   // the playback writes stored order
+	if (mode > 0 && h->from_sequence && !j40hip_lf_still_handle(h)) return E4("Uor?");   // the playback writes stored order (the main frame of an LF-frame still: capi.hpp)
 	if (mode > 0 && h->partial_range && h->frame.im.orientation != 1) return E4("Uor?");   // a partial group range writes its own rectangles of the stored image: nothing whole to turn
 	h->orient = mode < 0 ? -1 : mode > 0 ? 1 : 0;
 	return 0;

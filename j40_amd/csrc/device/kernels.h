@@ -48,6 +48,10 @@ void launch_xyb_to_rgba(const float *xyb, size_t pitch, const DevFrame *frame_de
 void upload_lf_tail_tables(const float *half_secants, const float *lf2llf, hipStream_t stream);
 void launch_lf_tail(const DevPlan &plan, int32_t num_lf_groups, int32_t max_cells, size_t cells, float *lfs, const DevVarblock *sorted, int32_t count, int32_t first_large, int32_t smooth,
 		const float inv_m_lf[3], hipStream_t stream);
+// ... of a frame with use_lf_frame: k_lf_from_frame (args.src, the thresholds; out and lfindices are filled in here), k_lf_frame_bctx
+// where `bctx` (the frame has LF thresholds), then the LLF kernels as above
+void launch_lf_frame_tail(const DevPlan &plan, int32_t num_lf_groups, int32_t max_cells, size_t cells, float *lfs, const DevVarblock *sorted, int32_t count, int32_t first_large,
+		LfFrameArgs args, bool bctx, int32_t num_groups, hipStream_t stream);
 
 void launch_lf_tail_batch(const DevPlan *plans, const DevPlanBuild *builds, const DevBatchLf *lfs, int32_t nframes, int32_t nlf, int32_t max_lf_cells, size_t max_frame_cells, hipStream_t stream);
 // the LF-dependent half of the plan of every frame of a batch (device/plan_kernels.hip)

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include "hf_dev.h"
 #include "lf_smooth_dev.h"
+#include "lf_frame_dev.h"
 #include "kernels.h"
 
 namespace j40hip {
@@ -216,14 +217,41 @@ __global__ void __launch_bounds__(64) k_llf_large_batch(const DevPlan *plans, co
 		llf_large_one(plan, pb.vb_sorted[v], lfs, lfs + pb.cells, lfs + 2 * (size_t) pb.cells, const_cast<float *>(plan.llf[0]), const_cast<float *>(plan.llf[1]), const_cast<float *>(plan.llf[2]), buf, tmp, threadIdx.x);
 }
 
+// A frame with use_lf_frame (lf_frame_dev.h): the first step of its tail. One lane per cell of an LfGroup, the grid shaped like
+// k_lf_dequant_smooth's; neighbouring lanes read neighbouring floats of a row of the LF frame's planes.
+__global__ void __launch_bounds__(256) k_lf_from_frame(DevPlan plan, LfFrameArgs args) {
+	lf_from_frame_cell(plan.lf_groups[blockIdx.y], (int32_t) (blockIdx.x * blockDim.x + threadIdx.x), args);
+}
+// ... and, where the frame has LF thresholds, the block contexts the plan was built with (LF index 0) looked up again: one lane per
+// block of group blockIdx.y's list (at most 32 x 32 blocks)
+__global__ void __launch_bounds__(256) k_lf_frame_bctx(DevPlan plan, DevGroupBlock *blocks, const uint8_t *lfindices) {
+	lf_frame_bctx_block(plan, blocks, lfindices, (int32_t) blockIdx.y, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// the LLF coefficients of every varblock from the three LF planes at `lfs`
+static void launch_llf(const DevPlan &plan, size_t cells, float *lfs, const DevVarblock *sorted, int32_t count, int32_t first_large, hipStream_t stream) {
+	float *llf0 = const_cast<float *>(plan.llf[0]), *llf1 = const_cast<float *>(plan.llf[1]), *llf2 = const_cast<float *>(plan.llf[2]);
+	if (count > 0) hipLaunchKernelGGL(k_llf_small, dim3((unsigned) ((count + 255) / 256)), dim3(256), 0, stream, plan, sorted, count, lfs, lfs + cells, lfs + 2 * cells, llf0, llf1, llf2);
+	if (count > first_large) hipLaunchKernelGGL(k_llf_large, dim3((unsigned) (count - first_large)), dim3(64), 0, stream, plan, sorted + first_large, count - first_large, lfs, lfs + cells, lfs + 2 * cells, llf0, llf1, llf2);
+}
+
 // the whole tail of one frame on `stream`: lfs = scratch of three planes of `cells` floats (dequantised + smoothed samples)
 void launch_lf_tail(const DevPlan &plan, int32_t num_lf_groups, int32_t max_cells, size_t cells, float *lfs, const DevVarblock *sorted, int32_t count, int32_t first_large, int32_t smooth,
 		const float inv_m_lf[3], hipStream_t stream) {
 	if (num_lf_groups <= 0 || max_cells <= 0) return;
 	hipLaunchKernelGGL(k_lf_dequant_smooth, dim3((unsigned) ((max_cells + 255) / 256), (unsigned) num_lf_groups), dim3(256), 0, stream, plan, lfs, lfs + cells, lfs + 2 * cells, smooth, inv_m_lf[0], inv_m_lf[1], inv_m_lf[2]);
-	float *llf0 = const_cast<float *>(plan.llf[0]), *llf1 = const_cast<float *>(plan.llf[1]), *llf2 = const_cast<float *>(plan.llf[2]);
-	if (count > 0) hipLaunchKernelGGL(k_llf_small, dim3((unsigned) ((count + 255) / 256)), dim3(256), 0, stream, plan, sorted, count, lfs, lfs + cells, lfs + 2 * cells, llf0, llf1, llf2);
-	if (count > first_large) hipLaunchKernelGGL(k_llf_large, dim3((unsigned) (count - first_large)), dim3(64), 0, stream, plan, sorted + first_large, count - first_large, lfs, lfs + cells, lfs + 2 * cells, llf0, llf1, llf2);
+	launch_llf(plan, cells, lfs, sorted, count, first_large, stream);
+}
+
+// the tail of a frame with use_lf_frame: args.out are the three planes at `lfs`; bctx: the frame has LF thresholds (lfidx_size > 1)
+void launch_lf_frame_tail(const DevPlan &plan, int32_t num_lf_groups, int32_t max_cells, size_t cells, float *lfs, const DevVarblock *sorted, int32_t count, int32_t first_large,
+		LfFrameArgs args, bool bctx, int32_t num_groups, hipStream_t stream) {
+	if (num_lf_groups <= 0 || max_cells <= 0) return;
+	args.out[0] = lfs; args.out[1] = lfs + cells; args.out[2] = lfs + 2 * cells;
+	args.lfindices = const_cast<uint8_t *>(plan.lfindices);
+	hipLaunchKernelGGL(k_lf_from_frame, dim3((unsigned) ((max_cells + 255) / 256), (unsigned) num_lf_groups), dim3(256), 0, stream, plan, args);
+	if (bctx && num_groups > 0) hipLaunchKernelGGL(k_lf_frame_bctx, dim3(4, (unsigned) num_groups), dim3(256), 0, stream, plan, const_cast<DevGroupBlock *>(plan.group_blocks), plan.lfindices);
+	launch_llf(plan, cells, lfs, sorted, count, first_large, stream);
 }
 
 // the tails of every frame of a batch: nlf LfGroups in all, the largest of max_lf_cells cells; the largest frame of max_frame_cells

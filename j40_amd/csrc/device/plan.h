@@ -39,6 +39,16 @@ struct DevLfGroup {
 	int32_t pad;
 };
 
+// a frame with use_lf_frame: what k_lf_from_frame takes beside the plan, by value (lf_frame_dev.h)
+struct LfFrameArgs {
+	const float *src[3];          // the LF frame's picture: planes X, Y, B, src_w x src_h floats row by row
+	int32_t src_w, src_h;         // ceil(width / 8) x ceil(height / 8) of the frame that reads it (the host has checked: "lfsz")
+	float *out[3];                // the LF planes of the LfGroup tail, in the plan's cell layout
+	uint8_t *lfindices;           // the plan's (DevPlan::lfindices)
+	int32_t nb_thr[3];            // LF thresholds of channels X, Y, B ...
+	float thr[3][15];             // ... as samples: (float) t * mult_lf[c], mult_lf at extra_precision 0
+};
+
 // one (pass, group) TOC section
 struct DevSection {
 	uint32_t byte_off, size, bit_off;

@@ -14,6 +14,7 @@
 // longer runs.
 #pragma once
 #include "hf_dev.h"
+#include "lf_frame_dev.h"
 
 namespace j40hip {
 
@@ -111,14 +112,7 @@ J40_DEV void plan_emit_varblock(const DevPlanBuild &pb, int32_t g, int32_t v) {
 	DevGroupBlock gb;
 	gb.coeffoff_qfidx = r.coeffoff_qfidx;
 	gb.pos_dct = (uint16_t) (((y8 & 31) * 32 + (x8 & 31)) | (dctsel << 10));
-	{
-		const uint8_t *map = pb.pool_u8 + pb.block_ctx_map_off;
-		const int32_t nb_qf1 = pb.nb_qf_thr + 1, lfidx_size = pb.lfidx_size;
-		const int32_t bctx0 = (order_idx * nb_qf1 + (int32_t) (r.coeffoff_qfidx & 15u)) * lfidx_size + lfidx;
-		uint32_t b3 = 0;
-		for (int32_t c_yxb = 0; c_yxb < 3; ++c_yxb) b3 |= (uint32_t) (map[bctx0 + 13 * nb_qf1 * lfidx_size * c_yxb] & 15) << (4 * c_yxb);
-		gb.bctx3 = (uint16_t) b3;
-	}
+	gb.bctx3 = (uint16_t) block_ctx3(pb.pool_u8 + pb.block_ctx_map_off, order_idx, (int32_t) (r.coeffoff_qfidx & 15u), lfidx, pb.nb_qf_thr + 1, pb.lfidx_size);   // (lf_frame_dev.h)
 	pb.group_blocks[blk] = gb;
 	DevVarblock dv;
 	const int32_t coeffoff = (int32_t) (r.coeffoff_qfidx & ~15u);

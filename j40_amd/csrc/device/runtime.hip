@@ -332,6 +332,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	}
 	if (perr) {   // the filters cannot run: the picture without them, and the complaint behind the sections' own (j40hip_frame_status)
 		st->restore_err = perr;
+		if (!rgba_dev) return 0;   // (planes are wanted, not pixels -- run_vardct's xyb_out: the caller makes the unfiltered ones)
 		if (st->ycbcr) return ycbcr_pixels(h, st->class_start, st->d_vb_sorted, rgba_dev, stride_bytes, s);
 		launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, rgba_dev, stride_bytes, s, out16(h));
 		return 0;
@@ -353,7 +354,8 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	}
 	st->d_restored = launch_restoration(st->d_xyb, st->d_xyb_tmp, (size_t) W, p, r.gab, r.epf_iters, st->d_sigma, s);
 	marks.mark(1);
-	if (st->ycbcr) ycbcr_tail_444(h, st->d_restored, (size_t) W, rgba_dev, stride_bytes, s);   // (the filtered planes are Cb, Y, Cr)
+	if (!rgba_dev) {}   // (planes are wanted, not pixels: d_restored is the result)
+	else if (st->ycbcr) ycbcr_tail_444(h, st->d_restored, (size_t) W, rgba_dev, stride_bytes, s);   // (the filtered planes are Cb, Y, Cr)
 	else launch_xyb_to_rgba(st->d_restored, (size_t) W, st->plan.frame, W, H, rgba_dev, stride_bytes, s, out16(h));
 	st->restore_ran = mode;
 	if (marks.ev && hipEventSynchronize(pair.ev[1]) == hipSuccess) (void) hipEventElapsedTime(&st->restore_ms, pair.ev[0], pair.ev[1]);
@@ -372,7 +374,31 @@ struct VardctRun {
 	bool whole;                          // every group is decoded: the restoration filters may run, the extra channels' sub-images can be validated
 	const uint8_t *crop_from; uint8_t *crop_to; size_t crop_stride; int32_t crop_w, crop_h;   // crop_to not null: these pixels of img are then moved there
 	int32_t shift = 0;                   // the scale shift the pixel kernels write at (decode_scaled's fused route: img is the small image)
+	float *xyb_out = nullptr;            // not null (an LF frame of a sequence, decode_frame_xyb): no pixels, img is null -- the three XYB planes, width * height
+	                                     // floats each, as the inverse transforms or (where they run) the restoration filters leave them, go here
 };
+
+// A frame with use_lf_frame: its LfGroup tail on `s`, ahead of the entropy kernels -- the LF samples and LF indices from the picture the
+// playback has bound (j40hip_frame_bind_lf_source), the block contexts where the frame has LF thresholds, the LLF coefficients
+// (lf_tail_kernels.hip). The thresholds as samples: (float) t * mult_lf[c] with mult_lf at extra_precision 0, frame.cpp's expression.
+static uint32_t lf_frame_tail(j40hip_frame *h, hipStream_t s) {
+	j40hip_device_state *st = h->dev;
+	const Frame &fr = h->frame;
+	if (!h->lf_src[0] || !h->lf_src[1] || !h->lf_src[2] || !st->d_lf_frame) return ERR4('l', 'f', 'n', 'o');
+	if (h->lf_src_w != (fr.fh.width + 7) / 8 || h->lf_src_h != (fr.fh.height + 7) / 8) return ERR4('l', 'f', 's', 'z');
+	LfFrameArgs a;
+	memset(&a, 0, sizeof a);
+	for (int c = 0; c < 3; ++c) {
+		a.src[c] = h->lf_src[c];
+		const float mult_lf = fr.m_lf_scaled[c] / (float) (fr.global_scale * fr.quant_lf) * (float) 65536;
+		a.nb_thr[c] = std::min(fr.nb_lf_thr[c], 15);
+		for (int32_t t = 0; t < a.nb_thr[c]; ++t) a.thr[c][t] = (float) fr.lf_thr[c][t] * mult_lf;
+	}
+	a.src_w = h->lf_src_w; a.src_h = h->lf_src_h;
+	const bool bctx = fr.nb_lf_thr[0] + fr.nb_lf_thr[1] + fr.nb_lf_thr[2] > 0;   // (lfidx_size > 1)
+	launch_lf_frame_tail(st->plan, (int32_t) fr.lf_groups.size(), st->lf_max_cells, st->lf_cells, st->d_lf_frame, st->d_vb_sorted, (int32_t) st->vb_count, st->class_start[18], a, bctx, (int32_t) fr.fh.num_groups, s);
+	return 0;
+}
 
 static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s, float *ms3) {
 	j40hip_device_state *st = h->dev;
@@ -383,6 +409,7 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 	marks.mark(0);
 	if (uint32_t e = clear_before_decode(st, s)) return e;
 	if (hipMemsetAsync(plan.status, 0, sizeof(uint32_t) * (size_t) st->total_sections, s) != hipSuccess) return ERR_GPU;
+	if (h->frame.fh.use_lf_frame) { if (uint32_t e = lf_frame_tail(h, s)) return e; }
 	marks.mark(1);
 	// (k_hf_entropy takes a run of groups and every pass of them)
 	if (!run.cover) launch_hf_entropy(plan, st->hf, run.first_group, run.num_groups, s);
@@ -390,6 +417,16 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 	else for (int32_t row = 0; row < run.cover->rows; ++row) launch_hf_entropy(plan, st->hf, (run.cover->gy0 + row) * run.cover->gcolumns + run.cover->gx0, run.cover->cols, s);
 	marks.mark(2);
 	const int rmode = run.whole ? restoration_mode(h) : 0;
+	if (run.xyb_out) {
+		const size_t W = (size_t) h->frame.fh.width, plane = W * (size_t) h->frame.fh.height;
+		bool filtered = false;
+		if (rmode && (r.gab || r.epf_iters > 0)) {
+			if (uint32_t e = decode_restored(h, nullptr, 0, rmode, s)) return e;
+			filtered = st->restore_ran != 0;   // (else the filters could not run, restore_err says why: the unfiltered planes)
+			if (filtered && hipMemcpyAsync(run.xyb_out, st->d_restored, sizeof(float) * 3 * plane, hipMemcpyDeviceToDevice, s) != hipSuccess) return ERR_GPU;
+		}
+		if (!filtered) launch_vardct_frame_xyb(plan, run.class_start, run.list, st->d_large_scratch, run.xyb_out, W * 4, s);
+	} else
 	if (rmode && (r.gab || r.epf_iters > 0)) {
 		// the restoration filters asked for and signalled: the pixel kernels leave the samples in XYB planes, Gaborish and the
 		// edge-preserving filter run over the whole picture, the colour tail follows on the filtered planes (restore_kernels.h)
@@ -425,6 +462,19 @@ static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes
 	const VardctRun run = {(int32_t) st->first_group, (int32_t) st->num_groups, nullptr, whole ? st->d_vb_sorted : st->d_vb_range, whole ? st->class_start : st->range_class_start,
 		(uint8_t *) rgba_dev, stride_bytes, whole, nullptr, nullptr, 0, 0, 0};
 	return run_vardct(h, run, s, ms3);
+}
+
+// An LF frame of a sequence (runtime_seq.hip: play_frame): the whole VarDCT frame decoded to its three XYB planes at `planes` (width *
+// height floats each, one behind the other), no colour conversion, no pixels. Enqueued on `s` like j40hip_frame_decode.
+uint32_t j40hip_rt::decode_frame_xyb(j40hip_frame *h, float *planes, hipStream_t s) {
+	if (!h || !h->dev || !planes) return ERR_GPU;
+	j40hip_device_state *st = h->dev;
+	// (what keeps it from being three full-size XYB planes: Modular and YCbCr samples, extra channels behind the coefficients, part of a frame)
+	if (h->frame.lf_only || st->is_modular || st->ycbcr || st->has_trailers || h->region_set || h->scale > 0 || h->partial_range) return ERR_TODO;
+	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
+	VardctRun run = {0, (int32_t) h->frame.fh.num_groups, nullptr, st->d_vb_sorted, st->class_start, nullptr, 0, true, nullptr, nullptr, 0, 0, 0};
+	run.xyb_out = planes;
+	return run_vardct(h, run, s, nullptr);
 }
 
 // ---- region decode (j40hip_frame_set_region, include/j40hip.h; device/region_dev.h, region_kernels.hip) ----
@@ -806,7 +856,7 @@ static uint32_t decode_to_host(j40hip_frame *h, void *rgba_host, size_t stride_b
 	if (!h || !h->dev) return ERR_GPU;
 	h->orient_applied = 0; h->orient_staging_bytes = 0;
 	const int32_t orientation = j40hip_orientation_in_force(h);   // (other than 1: the oriented image's rows, made by decode_oriented the one-phase way)
-	const bool region = h->region_set || h->scale > 0 || orientation != 1;   // (only the rectangle's rows, or the small image's, exist on either side, and they go the one-phase way)
+	const bool region = h->region_set || h->scale > 0 || orientation != 1 || h->frame.fh.use_lf_frame;   // (a frame with use_lf_frame: its tail runs in run_vardct) (only the rectangle's rows, or the small image's, exist on either side, and they go the one-phase way)
 	int32_t sw, sh, ow, oh;
 	j40hip_stored_out_size(h, &sw, &sh);
 	orient_out_size(sw, sh, orientation, &ow, &oh);

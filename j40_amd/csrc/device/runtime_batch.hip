@@ -53,6 +53,7 @@ static uint32_t batch_assign(j40hip_batch *b, j40hip_frame *const *frames, int64
 		if (j40hip_orientation_in_force(h) != 1) return ERR_UOR;   // ... in stored order
 		if (h->dev->is_modular) return ERR_TODO;   // Modular frames: decode them one by one
 		if (h->dev->ycbcr) return ERR_TODO;        // YCbCr frames (j40hip_frame_set_ycbcr): the single-frame decode alone serves them
+		if (h->frame.fh.use_lf_frame) return ERR_TODO;   // a frame that takes its LF image from an LF frame: a sequence's playback alone serves it
 		if (i == 0) b->device = h->dev->device;
 		else if (h->dev->device != b->device) return ERR_RNGE;
 		b->frames.push_back(h);

@@ -144,6 +144,7 @@ extern "C" uint32_t j40hip_frames_decode_lf(j40hip_frame *const *frames, int64_t
 // goes to the frame's staging block and k_orient writes `rgba_dev` behind it on `s`, as decode_oriented does for the full decode
 static uint32_t lfp_one(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s) {
 	if (!h || !h->dev) return ERR_GPU;
+	if (h->frame.fh.use_lf_frame) return ERR_TODO;   // (it holds no LF integers: the LF frame's own handle decodes that picture)
 	h->orient_applied = 0; h->orient_staging_bytes = 0;
 	const int32_t o = j40hip_orientation_in_force(h);
 	if (o == 1) return lfp_launch(&h, 1, &rgba_dev, &stride_bytes, s, false, 0);

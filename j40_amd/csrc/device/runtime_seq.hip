@@ -15,6 +15,11 @@ struct j40hip_sequence_device {
 	CacheBlock slot[4], staging;
 	size_t slot_stride = 0;
 	bool slot_saved[4] = {false, false, false, false};
+	// LF frames (J40HIP_SEQ_LFFRAME): LF slot k holds the picture of the last decoded frame of lf_level k + 1 -- three planes of float32
+	// (X, Y, B), lf_w x lf_h each, one behind the other; taken at the upload for the largest LF frame the index sends there
+	CacheBlock lf_slot[4];
+	int32_t lf_w[4] = {0, 0, 0, 0}, lf_h[4] = {0, 0, 0, 0};
+	bool lf_filled[4] = {false, false, false, false};
 	int64_t cursor = 0;          // the next coded frame
 	int64_t decoded = 0;         // coded frames [0, decoded) have been enqueued since the last rewind
 };
@@ -38,13 +43,52 @@ size_t staging_bound(const j40hip_sequence *s, int32_t w, int32_t h) { return 32
 bool reserve_blocks(j40hip_sequence *s) {
 	j40hip_sequence_device *d = s->dev;
 	d->slot_stride = ((size_t) s->im.width * seq_pixel_bytes(s) + 15) & ~(size_t) 15;
-	size_t staging = 0;
+	size_t staging = 0, lf_bytes[4] = {0, 0, 0, 0};
 	for (const j40hip_sequence::Row &row : s->rows) {
 		if (row.code) break;
+		if (row.fh.type == 1) { size_t &b = lf_bytes[row.fh.lf_level - 1]; b = std::max(b, sizeof(float) * 3 * (size_t) row.fh.width * (size_t) row.fh.height); continue; }
 		if (row.saved && !d->slot[row.fh.save_as_ref].ensure(d->device, slot_bytes(s), false)) return false;
 		if (row.blended || !(row.fh.x0 == 0 && row.fh.y0 == 0 && row.fh.width == s->im.width && row.fh.height == s->im.height)) staging = std::max(staging, staging_bound(s, row.fh.width, row.fh.height));
 	}
+	for (int k = 0; k < 4; ++k) if (lf_bytes[k] && !d->lf_slot[k].ensure(d->device, lf_bytes[k], false)) return false;
 	return !staging || d->staging.ensure(d->device, staging, false);
+}
+
+// the LF source of a frame with use_lf_frame: the picture in LF slot `slot` as the playback last filled it ("lfno": it never did)
+uint32_t bind_lf_source(j40hip_sequence *s, j40hip_frame *h, int32_t slot) {
+	j40hip_sequence_device *d = s->dev;
+	if (slot < 0 || slot > 3 || !d->lf_filled[slot] || !d->lf_slot[slot].ptr) return ERR4('l', 'f', 'n', 'o');
+	const size_t plane = (size_t) d->lf_w[slot] * (size_t) d->lf_h[slot];
+	const float *base = (const float *) d->lf_slot[slot].ptr, *planes[3] = {base, base + plane, base + 2 * plane};
+	j40hip_frame_bind_lf_source(h, planes, d->lf_w[slot], d->lf_h[slot]);
+	return 0;
+}
+
+// An LF frame (type 1): its XYB planes into its LF slot, nothing composed. It may take its own LF image from the next coarser level.
+uint32_t play_lf_frame(j40hip_sequence *s, int64_t k, j40hip_frame *h, hipStream_t stream, bool sync) {
+	j40hip_sequence_device *d = s->dev;
+	const FrameHeader &fh = s->rows[(size_t) k].fh;
+	const int slot = fh.lf_level - 1;
+	const size_t bytes = sizeof(float) * 3 * (size_t) fh.width * (size_t) fh.height;
+	if (slot < 0 || slot > 3 || !d->lf_slot[slot].ptr || d->lf_slot[slot].bytes < bytes) return ERR_GPU;   // (reserve_blocks sized it)
+	if (fh.use_lf_frame) { if (uint32_t e = bind_lf_source(s, h, fh.lf_level)) return e; }
+	float *planes = (float *) d->lf_slot[slot].ptr;
+	uint32_t e = decode_frame_xyb(h, planes, stream);
+	if (e) return e;
+	d->decoded = std::max(d->decoded, k + 1);
+	if (sync) {
+		if (hipStreamSynchronize(stream) != hipSuccess) return ERR_GPU;
+		e = j40hip_frame_status(h);
+		if (e == ERR_EVOF) {   // (as play_frame: dense planes)
+			h->force_dense = true;
+			if ((e = j40hip_frame_upload(h, d->device)) != 0 || (e = decode_frame_xyb(h, planes, stream)) != 0) return e;
+			if (hipStreamSynchronize(stream) != hipSuccess) return ERR_GPU;
+			e = j40hip_frame_status(h);
+		}
+		if (e) return e;
+	}
+	d->lf_w[slot] = fh.width; d->lf_h[slot] = fh.height; d->lf_filled[slot] = true;
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 }
 
 uint8_t *slot_image(j40hip_sequence *s, int k) {
@@ -70,6 +114,10 @@ uint32_t play_frame(j40hip_sequence *s, int64_t k, uint8_t *out, size_t out_stri
 	j40hip_frame *h = s->frames[(size_t) k];
 	if (!h || !h->dev || h->dev->device != d->device) return ERR_GPU;
 	const FrameHeader &fh = row.fh;
+	if (fh.type == 1) return play_lf_frame(s, k, h, stream, sync);
+	// (the main frame of an LF-frame still takes a scale and the orientation for decodes of its own, capi.hpp: the canvas is full size, stored order)
+	if (h->scale > 0) return ERR_USC;
+	if (j40hip_orientation_in_force(h) != 1) return ERR_UOR;
 	const int32_t W = s->im.width, H = s->im.height;
 	const size_t pb = seq_pixel_bytes(s);
 	// where the canvas of this frame is made
@@ -80,6 +128,7 @@ uint32_t play_frame(j40hip_sequence *s, int64_t k, uint8_t *out, size_t out_stri
 	const ComposeRect r = compose_clip(W, H, fh.x0, fh.y0, fh.width, fh.height);
 	uint8_t *img = dst; size_t img_stride = dst_stride;
 	if (!exact) { img = staging_image(s, dst, dst_stride, fh.width, fh.height, r.fx, r.cx0, &img_stride); if (!img) return ERR_GPU; }
+	if (fh.use_lf_frame) { if (uint32_t e = bind_lf_source(s, h, fh.lf_level)) return e; }   // (its LfGroup tail reads the LF frame's picture)
 	uint32_t e = j40hip_frame_decode(h, img, img_stride, stream);
 	if (e) return e;
 	d->decoded = std::max(d->decoded, k + 1);   // (enqueued: j40hip_sequence_status looks at it, whatever becomes of it)
@@ -135,6 +184,7 @@ extern "C" void j40hip_sequence_release_device(j40hip_sequence *s) {
 	bool waited = false;
 	auto give = [&](CacheBlock &b) { if (b.ptr) { b.release(waited); waited = true; } };   // (one device-wide wait covers them all)
 	for (CacheBlock &b : s->dev->slot) give(b);
+	for (CacheBlock &b : s->dev->lf_slot) give(b);
 	give(s->dev->staging);
 	delete s->dev;
 	s->dev = nullptr;
@@ -200,6 +250,20 @@ extern "C" void j40hip_sequence_rewind(j40hip_sequence *s) {
 	if (!s || !s->dev) return;
 	s->dev->cursor = s->dev->decoded = 0;
 	for (bool &b : s->dev->slot_saved) b = false;
+	for (bool &b : s->dev->lf_filled) b = false;
+	// (no handle keeps reading a slot that the next playback fills again: a decode of its own is "lfno" until the playback has passed it)
+	static const float *const none[3] = {nullptr, nullptr, nullptr};
+	for (j40hip_frame *h : s->frames) if (h) j40hip_frame_bind_lf_source(h, none, 0, 0);
+}
+
+extern "C" uint32_t j40hip_sequence_read_lf_slot(j40hip_sequence *s, int32_t level, int32_t c, float *out) {
+	return guarded([&]() -> uint32_t {
+		if (!s || !s->dev || level < 1 || level > 4 || c < 0 || c > 2 || !out || !s->dev->lf_filled[level - 1]) return ERR_RNGE;
+		const j40hip_sequence_device *d = s->dev;
+		const size_t plane = (size_t) d->lf_w[level - 1] * (size_t) d->lf_h[level - 1];
+		if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ERR_GPU;
+		return hipMemcpy(out, (const float *) d->lf_slot[level - 1].ptr + (size_t) c * plane, sizeof(float) * plane, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+	});
 }
 
 extern "C" uint32_t j40hip_sequence_status(j40hip_sequence *s, int64_t *out_frame) {

@@ -150,6 +150,9 @@ struct j40hip_device_state {
 	// sharded decode (j40hip_frame_set_group_range): the varblocks of the selected groups, same layout as vb_sorted
 	DevVarblock *d_vb_range = nullptr; int32_t range_class_start[28]; size_t vb_range_capacity = 0;
 	float *d_large_scratch = nullptr;
+	// a frame with use_lf_frame (lf_frame_tail in runtime.hip): three planes of `lf_cells` floats its LfGroup tail runs through at every
+	// decode, taken at upload; lf_max_cells: the cells of its largest LfGroup
+	float *d_lf_frame = nullptr; size_t lf_cells = 0; int32_t lf_max_cells = 0;
 	size_t coeff_floats = 0;
 	int32_t total_sections = 0;
 	HfLaunchInfo hf;
@@ -267,6 +270,7 @@ bool host_vb_sorted(j40hip_device_state *st);                                  /
 uint32_t upload_lf_only(j40hip_frame *h, int device, hipStream_t s);           // runtime_lfp.hip
 bool modular_groups_independent(const j40hip_frame *h);                        // runtime.hip
 uint32_t clear_before_decode(j40hip_device_state *st, hipStream_t s);          // runtime.hip
+uint32_t decode_frame_xyb(j40hip_frame *h, float *planes, hipStream_t s);      // runtime.hip
 uint32_t restore_params(const FrameHeader &fh, int mode, RestoreParams *p);    // runtime.hip
 void lf_services_shutdown();   // runtime_lf.hip, runtime.hip, runtime_lfp.hip: j40hip_shutdown's steps
 void two_phase_shutdown();

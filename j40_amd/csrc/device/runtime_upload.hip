@@ -261,6 +261,11 @@ static uint32_t upload_impl(j40hip_frame *h, int device, hipStream_t s) {
 			}
 		}
 	}
+	if (h->frame.fh.use_lf_frame) {   // its LfGroup tail runs at every decode, on the LF frame's picture: the planes it goes through
+		st->lf_cells = cells;
+		for (const DevLfGroup &g : hp.lf_groups) st->lf_max_cells = std::max(st->lf_max_cells, g.width8 * g.height8);
+		st->d_lf_frame = st->scratch<float>(3 * std::max<size_t>(cells, 1), ok);
+	}
 	st->total_sections = (int32_t) hp.sections.size();
 	st->has_trailers = hp.frame.sections_have_trailer != 0 && !h->from_view;
 	st->first_group = 0; st->num_groups = num_groups;

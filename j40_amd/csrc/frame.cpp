@@ -260,14 +260,15 @@ static void read_image_metadata(BitReader &br, ImageMeta *im, bool allow_wide) {
 // frame header (j40.h:5163)
 
 // `sequence`: the frame belongs to a frame sequence, which refuses the types it does not serve as soon as it has read them
-static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f, bool sequence = false) {
+// `lf_frames`: ... and the sequence serves LF frames (type 1)
+static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f, bool sequence = false, bool lf_frames = false) {
 	f->width = im.width; f->height = im.height;
 	f->ec_blend.assign(im.ec.size(), FrameHeader::Blend());
 	br.zero_pad_to_byte();
 	if (!br.u(1)) {
 		bool full_frame = true;
 		f->type = (int32_t) br.u(2);
-		if (sequence) J40HIP_SHOULD(f->type == 0 || f->type == 3, "TODO");
+		if (sequence) J40HIP_SHOULD(f->type == 0 || f->type == 3 || (lf_frames && f->type == 1), "TODO");
 		f->is_modular = br.u(1);
 		uint64_t flags = br.u64();
 		f->has_noise = flags & 1; f->has_patches = flags >> 1 & 1; f->has_splines = flags >> 4 & 1;
@@ -302,7 +303,9 @@ static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f
 			}
 		}
 		if (f->type == 1) {
-			(void) br.u(2);  // lf_level
+			// an LF frame: the image's size divided by 8, rounding up, once per level (no crop, no blend info, never last, saved nowhere)
+			f->lf_level = (int32_t) br.u(2) + 1;
+			for (int32_t l = 0; l < f->lf_level; ++l) { f->width = ceil_div(f->width, 8); f->height = ceil_div(f->height, 8); }
 		} else if (br.u(1)) {  // have_crop
 			if (f->type != 2) {
 				f->x0 = unpack_signed(br.u32(0, 8, 256, 11, 2304, 14, 18688, 30));
@@ -722,19 +725,24 @@ void read_lf_group_raw(BitReader &br, const Frame &f, const LfGroup &gg, LfRaw *
 	const FrameHeader &fh = f.fh;
 	const int64_t sidx0 = 1 + gg.idx, sidx2 = 1 + 2 * fh.num_lf_groups + gg.idx;
 	const int32_t w8 = gg.width8, h8 = gg.height8, w64 = gg.width64, h64 = gg.height64;
-	J40HIP_SHOULD(!fh.use_lf_frame, "TODO");
+	// (use_lf_frame: refused as the reference refuses it, j40.h:6763, unless LF frames are asked for -- Frame::allow_lf_frame)
+	J40HIP_SHOULD(!fh.use_lf_frame || (f.allow_lf_frame && !fh.do_ycbcr), "TODO");
 	// (jpeg_upsampling: refused as the reference refuses it, j40.h:6749, unless YCbCr frames are asked for -- Frame::allow_ycbcr)
 	J40HIP_SHOULD(fh.jpeg_upsampling == 0 || f.allow_ycbcr, "TODO");
 	J40HIP_SHOULD(fh.layout_served(), "TODO");   // (a layout other than 4:4:4, 4:2:0, 4:2:2, 4:4:0: FrameHeader::layout_served)
 
 	// LF image: three channels in Y, X, B order, each at its own size where the frame subsamples (FrameHeader::hshift)
+	// With use_lf_frame neither extra_precision nor the stream is there: the section starts at nb_varblocks (j40.h:6747, 6766), out->lf stays empty
 	static const int SLOT_OF_STREAM[3] = {1, 0, 2};
-	out->extra_prec = (int32_t) br.u(2);
 	Modular lfm; lfm.bpp = f.im.bpp;
-	lfm.channel.assign(3, Plane());
-	for (int c = 0; c < 3; ++c) { Plane &p = lfm.channel[(size_t) c]; p.width = w8 >> fh.hshift[SLOT_OF_STREAM[c]]; p.height = h8 >> fh.vshift[SLOT_OF_STREAM[c]]; }
-	decode_modular_image(br, &f.global_tree, &f.global_codespec, sidx0, &lfm);
-	for (int c = 0; c < 3; ++c) J40HIP_SHOULD(lfm.channel[(size_t) c].width == w8 >> fh.hshift[SLOT_OF_STREAM[c]] && lfm.channel[(size_t) c].height == h8 >> fh.vshift[SLOT_OF_STREAM[c]], "TODO");
+	out->extra_prec = 0;
+	if (!fh.use_lf_frame) {
+		out->extra_prec = (int32_t) br.u(2);
+		lfm.channel.assign(3, Plane());
+		for (int c = 0; c < 3; ++c) { Plane &p = lfm.channel[(size_t) c]; p.width = w8 >> fh.hshift[SLOT_OF_STREAM[c]]; p.height = h8 >> fh.vshift[SLOT_OF_STREAM[c]]; }
+		decode_modular_image(br, &f.global_tree, &f.global_codespec, sidx0, &lfm);
+		for (int c = 0; c < 3; ++c) J40HIP_SHOULD(lfm.channel[(size_t) c].width == w8 >> fh.hshift[SLOT_OF_STREAM[c]] && lfm.channel[(size_t) c].height == h8 >> fh.vshift[SLOT_OF_STREAM[c]], "TODO");
+	}
 
 	// HF metadata
 	const int32_t nb_varblocks = (int32_t) br.u(ceil_lg32((uint32_t) (w8 * h8))) + 1;
@@ -747,7 +755,7 @@ void read_lf_group_raw(BitReader &br, const Frame &f, const LfGroup &gg, LfRaw *
 	J40HIP_SHOULD(m.channel.size() == 4 && m.channel[2].width == nb_varblocks && m.channel[2].height == 2, "TODO");
 	J40HIP_SHOULD((int32_t) m.channel[0].px.size() == w64 * h64 && (int32_t) m.channel[1].px.size() == w64 * h64, "TODO");
 	out->nb_varblocks = nb_varblocks;
-	for (int c = 0; c < 3; ++c) out->lf[c].swap(lfm.channel[(size_t) c].px);
+	for (int c = 0; c < 3; ++c) { out->lf[c].clear(); if (!fh.use_lf_frame) out->lf[c].swap(lfm.channel[(size_t) c].px); }
 	out->xfromy.swap(m.channel[0].px); out->bfromy.swap(m.channel[1].px); out->info.swap(m.channel[2].px); out->sharp.swap(m.channel[3].px);
 }
 
@@ -755,10 +763,16 @@ static void read_lf_group(BitReader &br, Frame *f, LfGroup *gg) {  // j40.h:6722
 	if (f->fh.is_modular) { gg->loaded = true; return; }  // nothing is read: no channel has shift >= 3 (j40.h:6731)
 	LfRaw raw;
 	read_lf_group_raw(br, *f, *gg, &raw);
+	if (f->fh.use_lf_frame) {
+		// the LF image comes from an LF frame's picture, on the device: the integers are zeros here (so are the LLF coefficients a host
+		// tail makes of them), and every LF index is 0 until k_lf_from_frame has counted the thresholds on the samples
+		for (int c = 0; c < 3; ++c) raw.lf[c].assign((size_t) gg->width8 * (size_t) gg->height8, 0);
+	}
 	const int16_t *lf[3] = {raw.lf[0].data(), raw.lf[1].data(), raw.lf[2].data()};
 	std::vector<int16_t> *take[3] = {&raw.lf[0], &raw.lf[1], &raw.lf[2]};
 	lf_group_finish(f, gg, raw.extra_prec, lf, take, raw.xfromy.data(), raw.bfromy.data(), raw.info.data(), raw.info.data() + raw.nb_varblocks, raw.nb_varblocks);
 	gg->sharpness.swap(raw.sharp);
+	if (f->fh.use_lf_frame) std::fill(gg->lfindices.begin(), gg->lfindices.end(), (uint8_t) 0);   // (a negative threshold counted the zeros)
 }
 
 static void allocate_lf_groups(Frame *f) {  // j40.h:7659
@@ -866,8 +880,10 @@ int32_t rendered_alpha_channel(const ImageMeta &im) {
 	for (size_t i = 0; i < im.ec.size(); ++i) if (im.ec[i].type == EC_ALPHA) return (int32_t) i;
 	return -1;
 }
-uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec) {
+uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, bool lf_frames, bool xyb) {
 	bool ok = (fh.type == 0 || fh.type == 3) && !fh.use_lf_frame;
+	if (lf_frames && (fh.type == 1 || fh.use_lf_frame)) ok = (fh.type == 0 || fh.type == 3 || (fh.type == 1 && !fh.is_modular)) && xyb && !(fh.use_lf_frame && (fh.do_ycbcr || fh.is_modular))
+		&& !(fh.type == 1 && !fh.ec_blend.empty());   // (an LF frame with extra channels behind its coefficients: nothing here keeps or checks them)
 	if (!blend) {
 		ok = ok && fh.blend.mode == 0;
 		for (const FrameHeader::Blend &b : fh.ec_blend) ok = ok && b.mode == 0;
@@ -878,11 +894,11 @@ uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec) {
 	}
 	return ok ? 0 : (uint32_t) E4("TODO");
 }
-void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, FrameHeader *fh, Toc *toc) {
+void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, bool lf_frames, FrameHeader *fh, Toc *toc) {
 	J40HIP_SHOULD(offset < cs_size, "shrt");
 	BitReader br(cs + offset, cs_size - offset);
-	read_frame_header(br, im, fh, true);
-	if (uint32_t e = sequence_refusal(*fh, blend, rendered_alpha_channel(im))) raise(e);
+	read_frame_header(br, im, fh, true, lf_frames);
+	if (uint32_t e = sequence_refusal(*fh, blend, rendered_alpha_channel(im), lf_frames, im.xyb_encoded)) raise(e);
 	read_toc(br, *fh, toc);
 }
 
@@ -891,8 +907,8 @@ static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size
 	BitReader br(cs, limit);
 	if (f->seq_im) {   // a sequence's member: its bytes start at the frame header
 		f->im = *f->seq_im;
-		read_frame_header(br, f->im, &f->fh, true);
-		if (uint32_t e = sequence_refusal(f->fh, f->seq_blend, rendered_alpha_channel(f->im))) raise(e);
+		read_frame_header(br, f->im, &f->fh, true, f->allow_lf_frame);
+		if (uint32_t e = sequence_refusal(f->fh, f->seq_blend, rendered_alpha_channel(f->im), f->allow_lf_frame, f->im.xyb_encoded)) raise(e);
 	} else {
 		read_image_header(br, &f->im, f->allow_wide);
 		read_frame_header(br, f->im, &f->fh);

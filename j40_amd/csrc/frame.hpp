@@ -46,6 +46,7 @@ struct ImageMeta {
 struct FrameHeader {
 	bool is_last = true;
 	int32_t type = 0;
+	int32_t lf_level = 0;   // 1..4 for an LF frame (type 1), whose size is the image's divided by 8 that many times, rounding up; else 0
 	bool is_modular = false;
 	bool has_noise = false, has_patches = false, has_splines = false, use_lf_frame = false, skip_adapt_lf_smooth = false;
 	bool do_ycbcr = false;
@@ -208,6 +209,10 @@ struct Frame {
 	// instead of refused with "fm32" (j40.h:3169), and a Modular frame of it is decoded with int32 sample planes. A VarDCT frame of such an
 	// image is "TODO". Set before parse_frame.
 	bool allow_wide = false;
+	// LF frames are asked for (a sequence opened with J40HIP_SEQ_LFFRAME or J40HIP_LFFRAME=1): a sequence's member of type 1 is taken, and
+	// a frame with use_lf_frame is parsed -- its LfGroup sections start at nb_varblocks, its LF integers and LF indices stay zero (the
+	// device fills both in from the LF frame's picture, device/lf_tail_kernels.hip) -- instead of refused with "TODO". Set before parse_frame.
+	bool allow_lf_frame = false;
 	bool wide() const { return !im.modular_16bit_buffers; }
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
@@ -215,7 +220,7 @@ struct Frame {
 		Frame g;
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
-		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr; g.allow_wide = allow_wide;
+		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr; g.allow_wide = allow_wide; g.allow_lf_frame = allow_lf_frame;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section
@@ -233,15 +238,17 @@ void extract_codestream(const uint8_t *data, size_t size, const uint8_t **cs, si
 void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame, bool allow_wide = false);
 // header and TOC of the frame that starts at byte `offset` of the codestream, for a sequence's index: nothing behind the TOC is
 // read. The TOC's offsets count from `offset`. Raises what the header or the TOC raise, "TODO" for what sequence_refusal refuses.
-// blend: the sequence serves the blend modes other than Replace (sequence_refusal).
-void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, FrameHeader *fh, Toc *toc);
+// blend: the sequence serves the blend modes other than Replace, lf_frames: and LF frames (sequence_refusal).
+void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, bool lf_frames, FrameHeader *fh, Toc *toc);
 // the extra channel whose samples become the pixels' A (plan_build.cpp: alpha_channel): the first one of type alpha; -1: none
 int32_t rendered_alpha_channel(const ImageMeta &im);
 // 0, or "TODO": the frame is of a kind a sequence does not serve -- types 1 and 2, use_lf_frame, and a blend mode other than Replace
 // in any channel. With `blend` the other four modes are served for the colour channels and for extra channel `alpha_ec` (the rendered
 // alpha, -1: none; the other extra channels' entries are not looked at), unless a Blend or MulAdd of either names another alpha
-// channel than `alpha_ec`
-uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec);
+// channel than `alpha_ec`. With `lf_frames` type 1 and use_lf_frame pass, unless the LF frame is a Modular one (nothing renders Modular
+// samples to XYB floats) or of an image with extra channels, the image is not XYB encoded (`xyb`), or the frame with use_lf_frame is a
+// YCbCr or Modular one
+uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, bool lf_frames = false, bool xyb = true);
 
 // parses headers, TOC, LfGlobal, HfGlobal and every LfGroup section. `threads` > 1 decodes LfGroup
 // sections concurrently (they are independent given LfGlobal)

@@ -12,6 +12,7 @@
 //   forward=0  synthesis in the *coefficient domain* (the feature-matrix streams of the tests and the golden fixtures): the
 //              LF image comes from a smooth procedural picture, HF coefficients are sparse with frequency-decaying
 //              magnitudes; every transform type and bitstream feature can be forced into a small frame.
+// lflevels=1|2 writes the LF image as LF frame(s) of its own in front of a main frame with use_lf_frame (run_lf_sequence, below).
 // The reference decoder (oracle/_ref) is the judge of validity; what a stream decodes to is defined by it.
 //
 // usage: jxlsynth vardct  W H SEED OUT [key=value ...]
@@ -54,6 +55,21 @@ struct SeqFrame {
 	size_t first_section = 0;         // out: where this frame's first section starts in `cs`
 };
 static SeqFrame *g_seq = nullptr;
+
+// LF frames (lflevels=1|2; run_lf_sequence): what the VarDCT writer is told about the frame it writes, and what it hands back for the
+// next one. The planes of integers are frame-wide, ceil(W / 8) cells a row, in streamed order Y, X, B.
+struct LfRole {
+	int level = 0;              // > 0: the frame is an LF frame of this level (type 1, lf_level, no placement fields)
+	bool use = false;           // use_lf_frame: no upsampling fields, and its LfGroups hold neither extra_precision nor the LF stream
+	bool replicate = false;     // its LF integers are `src`'s, each over 8 x 8 cells (a flat LF frame's picture under it, or that frame's twin)
+	std::vector<int32_t> src[3]; int src_w = 0;
+	std::vector<int32_t> out[3]; int out_w = 0;   // out: the integers it ended up with
+	std::vector<float> pic[3];  // an LF frame of a picture: its W x H samples (X, Y, B)
+	bool capture = false;       // out: the 8 x 8 cell means of its samples (forward=1), what its decoder's LF chroma-from-luma adds taken off
+	std::vector<float> means[3]; int means_w = 0, means_h = 0;
+	int lfidx_distinct = 0;     // out: how many values its cells' LF index takes
+};
+static LfRole *g_lf = nullptr;
 
 // orientation=N (1..8, every mode): ImageMetadata.extra_fields carries orientation - 1; 0: the option was not given
 static int g_orientation = 0;
@@ -558,6 +574,12 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	};
 	if (forward) {
 		fwdx.reset(new synthfwd::Forward());
+		if (g_lf && !g_lf->pic[0].empty()) {   // an LF frame of a picture: its samples are the next finer frame's cell means (edges replicated)
+			for (int c = 0; c < 3; ++c) {
+				plane[c].resize((size_t) PW * (size_t) PH);
+				for (int y = 0; y < PH; ++y) for (int x = 0; x < PW; ++x) plane[c][(size_t) y * (size_t) PW + (size_t) x] = g_lf->pic[c][(size_t) std::min(y, H - 1) * (size_t) W + (size_t) std::min(x, W - 1)];
+			}
+		} else
 		if (!subsampled) make_planes(W, H, PW, PH, plane, true);
 		else {
 			std::vector<float> tmp[3];
@@ -578,6 +600,18 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	const int custom_cfl = opt.geti("cfl", 0);
 	// (nocfl=1 codes an all-zero correlation; a subsampled frame's decoder applies none whatever the header says)
 	const double kx_lf = custom_cfl ? 0.125 + 3.0 / 128.0 : 0.0, kb_lf = custom_cfl ? 0.75 - 2.0 / 128.0 : (nocfl || subsampled) ? 0.0 : 1.0;
+
+	if (g_lf && g_lf->capture) {
+		if (!forward || subsampled) die("vardct: an LF frame of a picture wants forward=1 and no subsampling");
+		g_lf->means_w = PW / 8; g_lf->means_h = PH / 8;
+		for (int c = 0; c < 3; ++c) g_lf->means[c].assign((size_t) (PW / 8) * (size_t) (PH / 8), 0.0f);
+		for (int cy = 0; cy < PH / 8; ++cy) for (int cx = 0; cx < PW / 8; ++cx) {
+			double m[3] = {0, 0, 0};
+			for (int c = 0; c < 3; ++c) { for (int y = 0; y < 8; ++y) for (int x = 0; x < 8; ++x) m[c] += plane[c][(size_t) (cy * 8 + y) * (size_t) PW + (size_t) (cx * 8 + x)]; m[c] /= 64; }
+			m[0] -= kx_lf * m[1]; m[2] -= kb_lf * m[1];   // (the frame's decoder adds these to the LF it is given, j40.h:7115-7116)
+			for (int c = 0; c < 3; ++c) g_lf->means[c][(size_t) cy * (size_t) (PW / 8) + (size_t) cx] = (float) m[c];
+		}
+	}
 
 	// ---- block context configuration ----
 	int nb_lf_thr[3] = {0, 0, 0}, lf_thr[3][4] = {{0}}, nb_qf_thr = 0, qf_thr[4] = {0};
@@ -639,6 +673,11 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		} else
 		for (int y = 0; y < gg.h8; ++y) for (int x = 0; x < gg.w8; ++x) {
 			float rgb[3]; double xyb[3];
+			if (g_lf && g_lf->replicate) {   // the LF frame's integers, each over 8 x 8 cells
+				const int sx = (gg.left / 8 + x) / 8, sy = (gg.top / 8 + y) / 8;
+				for (int k = 0; k < 3; ++k) gg.lfq[k].at(x, y) = g_lf->src[k][(size_t) sy * (size_t) g_lf->src_w + (size_t) sx];
+				continue;
+			}
 			if (forward) {   // the cell's mean
 				for (int c = 0; c < 3; ++c) { double m = 0; for (int j = 0; j < 8; ++j) for (int i = 0; i < 8; ++i) m += plane[c][(size_t) (gg.top + y * 8 + j) * (size_t) PW + (size_t) (gg.left + x * 8 + i)]; xyb[c] = m / 64; }
 			} else {
@@ -710,6 +749,20 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		for (size_t i = 0; i < gg.vbs.size(); ++i) { gg.blockinfo.at((int) i, 0) = gg.vbs[i].dctsel; gg.blockinfo.at((int) i, 1) = gg.vbs[i].hfmul_m1; }
 		gg.sharp = Channel(gg.w8, gg.h8);
 		for (auto &v : gg.sharp.px) v = (int32_t) rng.below(8);
+	}
+
+	if (g_lf) {
+		if (subsampled || jpeg) die("vardct: LF frames are not written for YCbCr streams");
+		const int fw8 = (W + 7) / 8, fh8 = (H + 7) / 8;
+		bool seen[256] = {false};
+		g_lf->out_w = fw8;
+		for (int k = 0; k < 3; ++k) g_lf->out[k].assign((size_t) fw8 * (size_t) fh8, 0);
+		for (const LfGroupW &gg : ggs) for (int y = 0; y < gg.h8; ++y) for (int x = 0; x < gg.w8; ++x) {
+			for (int k = 0; k < 3; ++k) g_lf->out[k][(size_t) (gg.top / 8 + y) * (size_t) fw8 + (size_t) (gg.left / 8 + x)] = gg.lfq[k].px[(size_t) y * (size_t) gg.w8 + (size_t) x];
+			seen[gg.lfidx[(size_t) y * (size_t) gg.w8 + (size_t) x]] = true;
+		}
+		g_lf->lfidx_distinct = 0;
+		for (bool s : seen) g_lf->lfidx_distinct += s;
 	}
 
 	// ---- global MA tree: splits on stream index (property 1) and channel (property 0) ----
@@ -1183,9 +1236,11 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	};
 	auto write_lf_group = [&](BitWriter &bw, int ggi) {  // LfGroup (j40.h:6722)
 		LfGroupW &gg = ggs[(size_t) ggi];
-		bw.put((uint64_t) extra_prec, 2);                        // extra_precision
-		write_modular_header(bw, true, wp_of(2 * ggi), {});
-		lfq_enc[(size_t) ggi].flush(bw);
+		if (!(g_lf && g_lf->use)) {   // (a frame with use_lf_frame: the section starts at nb_varblocks, j40.h:6747)
+			bw.put((uint64_t) extra_prec, 2);                        // extra_precision
+			write_modular_header(bw, true, wp_of(2 * ggi), {});
+			lfq_enc[(size_t) ggi].flush(bw);
+		}
 		bw.put((uint64_t) (gg.vbs.size() - 1), ceil_lg((uint32_t) (gg.w8 * gg.h8)));
 		write_modular_header(bw, true, wp_of(2 * ggi + 1), {});
 		meta_enc[(size_t) ggi].flush(bw);
@@ -1337,20 +1392,26 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	if (!nonzero_header) cs.put(1, 1);  // FrameHeader.all_default
 	else {
 		cs.put(0, 1);
-		cs.put(0, 2);                       // regular frame
+		const bool lf_frame = g_lf && g_lf->level > 0, use_lf_frame = g_lf && g_lf->use;
+		if ((lf_frame || use_lf_frame) && !g_seq) die("vardct: an LF frame, and a frame with use_lf_frame, is written by lflevels= only");
+		cs.put(lf_frame ? 1 : 0, 2);        // regular frame (an LF frame: type 1)
 		cs.put(0, 1);                       // VarDCT
-		cs.u64(skip_smooth ? 128 : 0);      // flags
+		cs.u64((skip_smooth ? 128 : 0) | (use_lf_frame ? 32 : 0));      // flags
 		if (noxyb) cs.put(ycbcr ? 1 : 0, 1);   // do_ycbcr (read only without xyb_encoded)
 		// (jpegup=N: the header says N whatever the stream holds -- a layout the decoder has to refuse before it reads anything of it)
 		if (ycbcr) cs.put((uint64_t) opt.geti("jpegup", jpeg_upsampling), 6);   // jpeg_upsampling (read with do_ycbcr)
+		if (!use_lf_frame) {                // (not coded with use_lf_frame, j40.h:5262)
 		cs.put(0, 2);                       // log_upsampling
 		for (int i = 0; i < num_ec; ++i) cs.put(0, 2);   // ec_log_upsampling
+		}
 		if (!noxyb) { cs.put((uint64_t) x_qm, 3); cs.put((uint64_t) b_qm, 3); }
 		cs.u32(num_passes, 1, 0, 2, 0, 3, 0, 4, 3);
 		if (num_passes > 1) {
 			cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 1);                  // num_ds = 0
 			for (int i = 0; i < num_passes - 1; ++i) cs.put(0, 2);  // shift[i]
 		}
+		if (lf_frame) cs.put((uint64_t) (g_lf->level - 1), 2);   // lf_level - 1; no crop, no blend info, never last, saved nowhere (j40.h:5285-5336)
+		else
 		write_frame_placement(cs, num_ec, W, H);   // have_crop, blend modes, is_last
 		cs.u32(0, 0, 0, 0, 4, 16, 5, 48, 10);  // name length 0
 		// RestorationFilter (j40.h:5339-5366). gab=1: Gaborish with the default weights, gab=2: custom weights; epf=1..3: iterations of the
@@ -2243,6 +2304,114 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 	return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// lflevels=1|2 (vardct): the LF image of the main frame as a frame of its own. Written under one image header of W x H: the level-2
+// frame (if any, 1/64 of the size), the level-1 frame (1/8; with two levels it has use_lf_frame itself) and the main frame with
+// use_lf_frame, whose LfGroups hold no LF stream. Every other option is the main frame's.
+//   lfkind=flat      (default) every LF frame is DCT8 only with all HF zero, no chroma-from-luma, no smoothing, no filters: its picture
+//                    is its LF integers times the LF step, each over an 8 x 8 square. The coarsest frame's integers come from the
+//                    procedural picture of its own size (seed SEED + level)
+//   lfkind=picture   (with forward=1) the LF frames forward-code the 8 x 8 cell means of the next finer frame's XYB samples; lfgab= and
+//                    lfepf= are the LF frames' gab= and epf=, lfhfmul= their HfMul (default 64, about ten times finer than the main
+//                    frame's: an error in an LF sample is an error in all 64 pixels of its cell, so an encoder spends bits here).
+//                    Not with bctx=1: the LF index of a cell is counted on the samples the LF frame DECODES to, which this writer does
+//                    not know, so it cannot choose the block contexts a decoder will use (with lfkind=flat it knows them exactly)
+//   lftwin=1         (flat) instead, the ordinary one-frame stream whose LfCoefficients are the flat LF frame's integers over 8 x 8
+//                    (two levels: 64 x 64) cells, with nosmooth=1 and extraprec=0: same seed, so the same varblocks and HF sections
+//   only=k           coded frame k (0: the coarsest LF frame) alone, as the regular last frame of an image of its own size. Not the main
+//                    frame (alone it has no LF image; lftwin=1 is its stand-alone form where the LF frames are flat), and not a frame
+//                    with use_lf_frame unless it is flat (then its LF integers are written out, as in a twin)
+//   bctx=1           the custom block-context map with LF thresholds combines with all of it but lfkind=picture (above)
+//   lfcrop=w,h       the main frame is a crop of w x h at (0, 0): a stream a decoder has to refuse, its LF frame is not of its cells' size
+// stats=1 prints the number of coded frames and how many values the main frame's LF index takes.
+static int run_lf_sequence(int W, int H, uint64_t seed, const char *out, const Options &opt_in) {
+	const int levels = opt_in.geti("lflevels", 1), twin = opt_in.geti("lftwin", 0), only = opt_in.geti("only", -1);
+	const std::string kind = opt_in.gets("lfkind", "flat");
+	if (levels < 1 || levels > 2) die("lflevels=1|2");
+	if (kind != "flat" && kind != "picture") die("lfkind=flat|picture");
+	const bool picture = kind == "picture";
+	if (picture && !opt_in.geti("forward", 0)) die("lfkind=picture wants forward=1");
+	if (picture && (twin || opt_in.geti("bctx", 0))) die("lfkind=picture: what its LF frame decodes to is not known here, so neither a twin nor LF thresholds (bctx=1) can be written");
+	if (opt_in.geti("extraprec", 0) || opt_in.geti("container", 0)) die("lflevels: extraprec=0 and no container");
+	if (only >= levels) die("only= names an LF frame here (0: the coarsest); the main frame is nothing without its LF frame");
+	if (only >= 0 && twin) die("only= and lftwin=1 exclude each other");
+	Options main_opt = opt_in;
+	for (const char *k : {"lflevels", "lfkind", "lftwin", "only", "stats", "lfgab", "lfepf", "lfcrop", "lfhfmul"}) main_opt.kv.erase(k);
+	int crop_w = 0, crop_h = 0;
+	if (opt_in.kv.count("lfcrop") && (sscanf(opt_in.gets("lfcrop", "").c_str(), "%d,%d", &crop_w, &crop_h) != 2 || crop_w < 1 || crop_h < 1 || crop_w > W || crop_h > H || picture || twin || only >= 0)) die("lfcrop=w,h within the image, with lfkind=flat and neither lftwin nor only");
+	main_opt.kv["fullheader"] = "1";
+	// (a picture: every frame with use_lf_frame codes no chroma-from-luma, so that the LF frame under it holds the B samples themselves,
+	// coded against its own dequantised Y like any frame's; B - Y in a plane of its own would take Y's coding error on top of its own)
+	if (picture) main_opt.kv["nocfl"] = "1";
+	Options lf_opt = main_opt;
+	for (const char *k : {"gab", "epf", "dumpsrc", "passes", "rfdefault"}) lf_opt.kv.erase(k);
+	lf_opt.kv["nocfl"] = "1"; lf_opt.kv["nosmooth"] = "1"; lf_opt.kv["coverage"] = "0";
+	Options lf_top_opt;   // the coarsest LF frame's: it has no use_lf_frame
+	if (!picture) { lf_opt.kv["dct8only"] = "1"; lf_opt.kv["density"] = "0"; lf_opt.kv["forward"] = "0"; }
+	else {
+		if (opt_in.kv.count("lfgab")) lf_opt.kv["gab"] = opt_in.gets("lfgab", "0");
+		if (opt_in.kv.count("lfepf")) lf_opt.kv["epf"] = opt_in.gets("lfepf", "0");
+		lf_opt.kv["hfmul"] = opt_in.gets("lfhfmul", "64");
+	}
+	lf_top_opt = lf_opt;
+	if (picture) lf_top_opt.kv.erase("nocfl");
+	auto lf_opt_of = [&](int l) -> const Options & { return l == levels ? lf_top_opt : lf_opt; };
+	int fw[3], fh[3];
+	fw[0] = W; fh[0] = H;
+	for (int l = 1; l <= levels; ++l) { fw[l] = (fw[l - 1] + 7) / 8; fh[l] = (fh[l - 1] + 7) / 8; }
+	std::vector<uint8_t> cs, nowhere;
+	// one coded frame: level l (0: the main frame) with `role`, behind `into` (null: a file of its own, a regular last frame)
+	auto write = [&](int l, LfRole &role, std::vector<uint8_t> *into, const Options &o) {
+		SeqFrame q;
+		q.canvas_w = W; q.canvas_h = H; q.cs = into; q.first = into && into->empty(); q.is_last = l == 0;
+		q.have_crop = l == 0 && crop_w > 0;
+		g_seq = into ? &q : nullptr; g_lf = &role;
+		const int e = run_vardct(q.have_crop ? crop_w : fw[l], q.have_crop ? crop_h : fh[l], seed + (uint64_t) l, out, o);
+		g_seq = nullptr; g_lf = nullptr;
+		if (e) die("lflevels: a frame could not be written");
+	};
+	LfRole roles[3];
+	if (picture) {
+		// the samples each LF frame codes: the next finer frame's cell means, found by writing that frame to nowhere first
+		Options dry = main_opt; dry.kv.erase("dumpsrc");
+		roles[0].capture = true;
+		write(0, roles[0], &nowhere, dry);
+		for (int c = 0; c < 3; ++c) roles[1].pic[c] = roles[0].means[c];
+		if (roles[0].means_w != fw[1] || roles[0].means_h != fh[1]) die("lflevels: the cell means are not the LF frame's size");
+		if (levels == 2) {
+			nowhere.clear(); roles[1].capture = true;
+			write(1, roles[1], &nowhere, lf_opt_of(1));
+			for (int c = 0; c < 3; ++c) roles[2].pic[c] = roles[1].means[c];
+			roles[1].capture = false;
+		}
+		roles[0].capture = false;
+	}
+	const bool alone = twin || only >= 0;
+	int written = 0;
+	for (int l = levels; l >= 0; --l) {
+		LfRole &r = roles[l];
+		const int k = levels - l;   // its place in coded order
+		if (only >= 0 && k > only) break;
+		const bool last_of_call = only >= 0 ? k == only : l == 0;
+		if (l < levels && !picture) { r.replicate = true; for (int c = 0; c < 3; ++c) r.src[c] = roles[l + 1].out[c]; r.src_w = roles[l + 1].out_w; }
+		if (alone && last_of_call) {
+			if (l < levels && picture) die("only=: a frame with use_lf_frame decodes alone only where it is flat");
+			Options o = l == 0 ? main_opt : lf_opt_of(l);
+			if (l == 0) { o.kv["nosmooth"] = "1"; o.kv["extraprec"] = "0"; }
+			write(l, r, nullptr, o);
+			++written;
+			break;
+		}
+		r.level = l; r.use = l < levels;
+		nowhere.clear();
+		write(l, r, alone ? &nowhere : &cs, l == 0 ? main_opt : lf_opt_of(l));
+		++written;
+	}
+	if (!alone && !write_file(out, cs)) die("cannot write output");
+	if (opt_in.geti("stats", 0)) printf("{\"frames\": %d, \"lfidx_distinct\": %d}\n", alone ? 1 : written, roles[only >= 0 ? levels - only : 0].lfidx_distinct);
+	return 0;
+}
+
 int main(int argc, char **argv) {
 	if (argc < 6) { fprintf(stderr, "usage: %s vardct|modular W H SEED OUT [key=value ...]\n", argv[0]); return 1; }
 	Options opt;
@@ -2256,7 +2425,11 @@ int main(int argc, char **argv) {
 		if (g_orientation < 1 || g_orientation > 8) die("orientation=1..8");
 		opt.kv.erase("orientation");
 	}
-	static const char *const SEQ_KEYS[] = {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only"};
+	if (opt.kv.count("lflevels")) {
+		if (!vardct) die("lflevels= belongs to the vardct mode");
+		return run_lf_sequence(W, H, seed, argv[5], opt);
+	}
+	static const char *const SEQ_KEYS[] ={"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only"};
 	bool sequence = false;
 	for (const char *k : SEQ_KEYS) sequence = sequence || opt.kv.count(k);
 	if (!sequence) return vardct ? run_vardct(W, H, seed, argv[5], opt) : run_modular(W, H, seed, argv[5], opt);
