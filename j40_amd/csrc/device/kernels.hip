@@ -1395,6 +1395,18 @@ void k2_batch_grids(const int32_t *last_totals, size_t cells_total, int32_t nfra
 	}
 }
 
+} // namespace j40hip
+// for a test that wants a workgroup's run to cross a frame border: launch l's {first DctSelect, one past the last, varblocks per tile,
+// cells per varblock at least} and the most workgroups a launch gets; returns the number of launches (l out of range: nothing written)
+extern "C" __attribute__((visibility("default"))) int32_t j40hip_debug_k2_launch(int32_t l, int32_t *out5) {
+	if (l >= 0 && l < j40hip::K2_NUM_BATCH_LAUNCHES && out5) {
+		const j40hip::K2BatchLaunch &L = j40hip::K2_TABLE.l[l];
+		out5[0] = L.a; out5[1] = L.b; out5[2] = L.per_wg; out5[3] = L.min_cells; out5[4] = j40hip::K2_WG_SLOTS;
+	}
+	return j40hip::K2_NUM_BATCH_LAUNCHES;
+}
+namespace j40hip {
+
 // grids: workgroups per launch (k2_batch_grids); large_scratch: 6 * 65536 floats per workgroup of the last launch (K2_LARGE_WGS of
 // them); totals_dev: K2_NUM_BATCH_LAUNCHES ints, the tiles each launch found
 void launch_vardct_batch(const K2Frame *frames_dev, int32_t nframes, int32_t *tile_prefix_dev, int32_t *totals_dev, const int32_t *grids, float *large_scratch, hipStream_t stream, hipStream_t *side, int nside, hipEvent_t fork, hipEvent_t *side_done, int32_t shift) {

@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 from refdec import Ref, RefStage  # noqa: E402
 from streams import synth, VARDCT_CASES, MODULAR_CASES  # noqa: E402
+import tone_streams  # noqa: E402
 
 
 def sha(a):
@@ -48,6 +49,9 @@ def main():
     cases.append(("modular_palette_predictor_6_custom_wp", "modular", 300, 200, 104, dict(palette=3, dpred=6, wp="max")))
     cases.append(("modular_noise_15_bit", "modular", 96, 64, 105, dict(bpp=15, rct=-1, noise=32767, tree=1)))
     cases.append(("modular_sample_overflow", "modular", 96, 64, 106, dict(povf=3000, prefix=1)))
+    # an image header with ToneMapping and the custom-transform block written out (tests/test_tone_opsin.py): intensity_target 1000, the
+    # opsin matrix with two rows exchanged, three different biases, quant biases of its own; every transform size
+    cases.append(("vardct_custom_opsin_tone", "vardct", 776, 520, tone_streams.SEED, tone_streams.options_of("swapped_all_tone_1000", "all_transforms")))
     for name, mode, w, h, seed, opts in cases:
         data = synth(mode, w, h, seed, **opts)
         with open(os.path.join(HERE, name + ".jxl"), "wb") as fp:

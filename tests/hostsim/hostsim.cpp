@@ -238,6 +238,14 @@ extern "C" __attribute__((visibility("default"))) uint32_t hostsim_decode(const 
 	return e;
 }
 
+// the second attempt alone: dense coefficient planes from the start (what j40hip_frame_force_dense asks of the runtime), for streams
+// whose events never overflow
+extern "C" __attribute__((visibility("default"))) uint32_t hostsim_decode_dense(const uint8_t *buf, size_t size, uint8_t *rgba, float *coeffs_out, int only_entropy) {
+	g_first_attempt = 0;
+	mod_block_reset();
+	return hostsim_decode_once(buf, size, rgba, coeffs_out, only_entropy & ~16, true);
+}
+
 // the Modular blocks of the last hostsim_decode (mod_block.hpp): guard bytes that no longer read 0x5a; the bytes of the regions called `name`
 extern "C" __attribute__((visibility("default"))) int64_t hostsim_guard_damage(void) { return (int64_t) g_guard_damage; }
 extern "C" __attribute__((visibility("default"))) int64_t hostsim_region_bytes(const char *name) { return mod_block_region_bytes(name); }

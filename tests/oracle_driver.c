@@ -53,6 +53,27 @@ __attribute__((visibility("default"))) uint32_t oracle_run(const void *buf, size
 	return err;
 }
 
+/* the header's constants as the plan view of a parsed handle carries them: out[0..8] opsin_inv_mat, [9..11] opsin_bias, [12]
+ * intensity_target, [13..15] quant_bias, [16] quant_bias_num. through_seam: as the view of a second handle built from that view
+ * (j40hip_frame_from_vardct_view) carries them */
+__attribute__((visibility("default"))) uint32_t oracle_view_consts(j40hip_frame *f, float *out, int through_seam) {
+	j40hip_vardct_view v;
+	j40hip_frame *g = NULL;
+	int i;
+	uint32_t err = j40hip_frame_vardct_view(f, &v);
+	if (!err && through_seam) {
+		g = j40hip_frame_from_vardct_view(&v, &err);
+		if (g) err = j40hip_frame_vardct_view(g, &v);
+	}
+	if (!err) {
+		for (i = 0; i < 9; ++i) out[i] = v.opsin_inv_mat[i];
+		for (i = 0; i < 3; ++i) { out[9 + i] = v.opsin_bias[i]; out[13 + i] = v.quant_bias[i]; }
+		out[12] = v.intensity_target; out[16] = v.quant_bias_num;
+	}
+	if (g) j40hip_frame_free(g);
+	return err;
+}
+
 /* the seam in the other direction: parse -> view -> j40hip_frame_from_vardct_view (a second handle that never saw the
  * bitstream's headers) -> its view -> the oracle. mode 1: decode that second handle on the GPU instead (rgba = host buffer
  * of width * 4 bytes per row). Modes 2 / 3: the same, with the view flattened into the LF-bundle blob and rebuilt from it. */

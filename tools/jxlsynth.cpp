@@ -73,12 +73,20 @@ static LfRole *g_lf = nullptr;
 
 // orientation=N (1..8, every mode): ImageMetadata.extra_fields carries orientation - 1; 0: the option was not given
 static int g_orientation = 0;
+// tone=IT,MIN[,LINEAR_BELOW[,RELATIVE]] (vardct): extra fields (orientation 1 and nothing else unless other options say otherwise) and
+// ToneMapping written out: intensity_target, min_nits, linear_below as f16 bits, relative_to_max_display. Empty: the option was not given
+static std::vector<uint32_t> g_tone;
+// opsin=M00,..,M22,B0,B1,B2,Q0,Q1,Q2,QNUM (vardct): default_m = 0 and the custom-transform block: opsin_inv_mat row-major, opsin_bias,
+// quant_bias, quant_bias_num as f16, then cw_mask = 0 (cwmask=1..7: a stream decoders refuse). A value is a decimal number that an
+// f16 holds exactly, or `h` and four hex digits: the f16's bits as they are (h7c00: an infinity, which decoders refuse as well)
+static std::vector<uint32_t> g_opsin;
+static int g_cw_mask = 0;
 // ImageMetadata.extra_fields (j40.h:3147-3163): 0, or for an animation: orientation 1, no intrinsic size, no preview, the animation
 // header (tps 10 / 1, loops 0, no timecodes); with orientation=N: extra fields with that orientation (and, outside an animation,
 // nothing else)
 static void write_extra_fields(BitWriter &cs) {
 	const bool anim = g_seq && g_seq->anim;
-	if (!anim && !g_orientation) { cs.put(0, 1); return; }
+	if (!anim && !g_orientation && g_tone.empty()) { cs.put(0, 1); return; }
 	cs.put(1, 1);
 	cs.put((uint64_t) (g_orientation ? g_orientation - 1 : 0), 3); cs.put(0, 1); cs.put(0, 1);   // orientation - 1, have_intrinsic_size, have_preview
 	if (!anim) { cs.put(0, 1); return; }            // have_animation
@@ -88,8 +96,6 @@ static void write_extra_fields(BitWriter &cs) {
 	cs.put(0, 2);                                   // num_loops U32(0, u(3), u(16), u(32)) = 0
 	cs.put(0, 1);                                   // have_timecodes
 }
-// ... and what they add behind ColourEncoding: ToneMapping.all_default (j40.h:3234)
-static void write_tone_mapping(BitWriter &cs) { if ((g_seq && g_seq->anim) || g_orientation) cs.put(1, 1); }
 
 // the frame header from have_crop to save_before_color_transform (j40.h:5285-5336). Outside a sequence: no crop, Replace, is_last.
 static void write_frame_placement(BitWriter &cs, int num_ec, int frame_w, int frame_h) {
@@ -239,6 +245,25 @@ static uint32_t f16_bits(float v) {
 	const uint32_t sign = u >> 31, mant = u & 0x7fffff; const int e = (int) ((u >> 23) & 0xff) - 127 + 15;
 	if (e <= 0 || e >= 31 || (mant & 0x1fff)) die("f16: value not exactly representable");
 	return sign << 15 | (uint32_t) e << 10 | mant >> 13;
+}
+
+// ... and what they add behind ColourEncoding: ToneMapping (j40.h:3270-3286), all_default unless tone= is given
+static void write_tone_mapping(BitWriter &cs) {
+	if (!(g_seq && g_seq->anim) && !g_orientation && g_tone.empty()) return;
+	if (g_tone.empty()) { cs.put(1, 1); return; }
+	cs.put(0, 1);
+	cs.put(g_tone[0], 16); cs.put(g_tone[1], 16);   // intensity_target, min_nits
+	cs.put(g_tone[3] ? 1 : 0, 1);                   // relative_to_max_display
+	cs.put(g_tone[2], 16);                          // linear_below
+}
+// the end of the image header (j40.h:3270-3307). Behind a written-out ImageMetadata (`metadata`): ToneMapping, no extensions; then in
+// either case default_m, and with opsin=: the 16 values (in an XYB image only, as the format says) and cw_mask
+static void write_header_tail(BitWriter &cs, bool metadata, bool xyb) {
+	if (metadata) { write_tone_mapping(cs); cs.put(0, 2); }   // extensions
+	if (g_opsin.empty()) { cs.put(1, 1); return; }            // default_m
+	cs.put(0, 1);
+	if (xyb) for (size_t i = 0; i < 16; ++i) cs.put(g_opsin[i], 16);
+	cs.put((uint64_t) g_cw_mask, 3);
 }
 
 // dq=1: the dequantisation matrices of HfGlobal in their coded forms (j40.h:4696-4760) instead of "all default": band
@@ -1334,10 +1359,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		}
 		cs.put(noxyb ? 0 : 1, 1);           // xyb_encoded
 		cs.put(1, 1);                       // ColourEncoding.all_default
-		write_tone_mapping(cs);
-		cs.put(0, 2);                       // extensions
-		cs.put(1, 1);                       // default_m
-	} else if (img_bpp != 8 || (seq_anim && !with_alpha) || (noxyb && !with_alpha) || (g_orientation && !with_alpha && !icc_bytes)) {   // (orientation=N: the metadata written out where it would be all_default)
+		write_header_tail(cs, true, !noxyb);
+	} else if (img_bpp != 8 || (seq_anim && !with_alpha) || (noxyb && !with_alpha) || ((g_orientation || !g_tone.empty()) && !with_alpha && !icc_bytes)) {   // (orientation=N, tone=: the metadata written out where it would be all_default)
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		write_bit_depth(cs, img_bpp);
@@ -1355,12 +1378,10 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			cs.put(1, 2);                   // rendering intent 1
 		} else
 		cs.put(1, 1);                       // ColourEncoding.all_default
-		write_tone_mapping(cs);
-		cs.put(0, 2);                       // extensions
-		cs.put(1, 1);                       // default_m
+		write_header_tail(cs, true, !noxyb);
 	} else if (!icc_bytes && !with_alpha) {
 		cs.put(1, 1);   // ImageMetadata.all_default: 8-bit, XYB, no extra channels
-		cs.put(1, 1);   // default_m
+		write_header_tail(cs, false, true);
 	} else if (!icc_bytes) {
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
@@ -1369,9 +1390,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(1, 2); cs.put(1, 1);         // one extra channel, d_alpha
 		cs.put(noxyb ? 0 : 1, 1);           // xyb_encoded (noxyb=1: the reference runs the XYB inverse on VarDCT frames regardless, j40.h:7206)
 		cs.put(1, 1);                       // ColourEncoding.all_default
-		write_tone_mapping(cs);
-		cs.put(0, 2);                       // extensions
-		cs.put(1, 1);                       // default_m
+		write_header_tail(cs, true, !noxyb);
 	} else {
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
@@ -1382,9 +1401,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(0, 1);                       // ColourEncoding: not all_default
 		cs.put(1, 1);                       // want_icc
 		cs.put(0, 2);                       // colour_space = RGB (enum selector 0)
-		write_tone_mapping(cs);
-		cs.put(0, 2);                       // extensions
-		cs.put(1, 1);                       // default_m
+		write_header_tail(cs, true, true);
 		write_icc_stream(cs, rng, icc_bytes);
 	}
 	}
@@ -2137,9 +2154,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	const int icc_bytes = opt.geti("icc", 0);
 	if (!icc_bytes) cs.put(1, 1);       // ColourEncoding.all_default (sRGB)
 	else { cs.put(0, 1); cs.put(1, 1); cs.put(0, 2); }   // want_icc, colour_space = RGB
-	write_tone_mapping(cs);
-	cs.put(0, 2);                       // extensions
-	cs.put(1, 1);                       // default_m
+	write_header_tail(cs, true, opt.geti("xyb", 0) != 0);   // (tone= / opsin= are refused in this mode: the all-default tail)
 	if (icc_bytes) write_icc_stream(cs, rng, icc_bytes);
 	}
 	const int flag_xyb = opt.geti("xyb", 0), flag_ycbcr = opt.geti("ycbcr", 0);
@@ -2424,6 +2439,30 @@ int main(int argc, char **argv) {
 		g_orientation = opt.geti("orientation", 0);
 		if (g_orientation < 1 || g_orientation > 8) die("orientation=1..8");
 		opt.kv.erase("orientation");
+	}
+	if (opt.kv.count("tone") || opt.kv.count("opsin") || opt.kv.count("cwmask")) {
+		if (!vardct) die("tone=, opsin= and cwmask= belong to the vardct mode");
+		auto halves = [&](const char *k) {   // f16 bits of every value of the list
+			std::vector<uint32_t> v; const std::string s = opt.gets(k, "");
+			for (size_t at = 0; at < s.size(); ) {
+				size_t e = s.find(',', at); if (e == std::string::npos) e = s.size();
+				const std::string t = s.substr(at, e - at);
+				if (t.size() == 5 && t[0] == 'h') v.push_back((uint32_t) strtoul(t.c_str() + 1, nullptr, 16) & 0xffff);
+				else v.push_back(f16_bits(strtof(t.c_str(), nullptr)));
+				at = e + 1;
+			}
+			return v;
+		};
+		if (opt.kv.count("tone")) {
+			g_tone = halves("tone");
+			if (g_tone.size() < 2 || g_tone.size() > 4) die("tone=IT,MIN[,LINEAR_BELOW[,RELATIVE]]");
+			g_tone.resize(4, 0);
+		}
+		if (opt.kv.count("opsin")) { g_opsin = halves("opsin"); if (g_opsin.size() != 16) die("opsin= wants 16 values"); }
+		if (opt.kv.count("cwmask") && g_opsin.empty()) die("cwmask= wants opsin=");
+		g_cw_mask = opt.geti("cwmask", 0);
+		if (g_cw_mask < 0 || g_cw_mask > 7) die("cwmask=0..7");
+		for (const char *k : {"tone", "opsin", "cwmask"}) opt.kv.erase(k);
 	}
 	if (opt.kv.count("lflevels")) {
 		if (!vardct) die("lflevels= belongs to the vardct mode");
