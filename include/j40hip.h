@@ -82,6 +82,9 @@ J40HIP_API uint32_t j40hip_frame_lf_plane(const j40hip_frame *f, int c, float *o
 /* the constants of the preview's colour tail as parsed: out15 = opsin_inv_mat[9] (row-major), opsin_bias[3], intensity_target, and the
  * LF chroma-from-luma factors kx_lf, kb_lf (j40.h:7115-7116) */
 J40HIP_API void j40hip_frame_colour_consts(const j40hip_frame *f, float *out15);
+/* LfGlobal's LF dequantisation as parsed: out3 = m_lf_scaled of X, Y, B (defaults 1/4096, 1/512, 1/256) -- the factors of a VarDCT frame's
+ * LF samples and of a Modular frame's samples under j40hip_frame_set_modular_xyb */
+J40HIP_API void j40hip_frame_lf_dequant(const j40hip_frame *f, float *out3);
 
 /* out[0..20] = width, height, is_modular, num_lf_groups, num_groups, num_passes, nb_block_ctx,
  * block_ctx_size, num_hf_presets, global_scale, quant_lf, x_qm_scale, b_qm_scale, nb_qf_thr,
@@ -320,6 +323,42 @@ J40HIP_API void j40hip_frame_ycbcr(const j40hip_frame *f, int32_t out[8]);
  *      j40hip_frame_wide: out[0] the image has 32-bit buffers; out[1] its bit depth; out[2] the last decode ran the int32 kernels;
  *      out[3] bytes per sample of the frame's planes on the device (2 or 4; 0 before an upload). ---- */
 J40HIP_API void j40hip_frame_wide(const j40hip_frame *f, int32_t out[4]);
+/* ---- Modular frames of XYB images ("Modular frames of XYB images"; DESIGN.md section 4 has the rule). An image with
+ *      xyb_encoded = 1 may carry its colour in a Modular frame (lossy Modular, every LF frame a real encoder writes): three planes of
+ *      quantised integers Y, X, B - Y. The reference applies no colour transform to a Modular frame (j40.h:7910-7962) and renders those
+ *      integers as R, G, B; so does this library unless asked. PARITY UNPINNED: no decoder at hand pins the rule.
+ *      set: mode -1 follows the environment (J40HIP_MODULAR_XYB=1 serves; the default), 0 renders R, G, B, 1 renders through the XYB
+ *      colour tail: Y = (float) c0 * m[1], X = (float) c1 * m[0], B = (float) (c2 + c0) * m[2] with m = LfGlobal's LF dequantisation
+ *      (integer sum, one conversion, one multiply), then what a VarDCT frame's colour tail makes of X, Y, B; A from the alpha plane as
+ *      before. Mode 1 is refused with "Umx?" (the frame is left as it was) for a frame the rule does not apply to: VarDCT frames, images
+ *      with xyb_encoded = 0, grey images, do_ycbcr, float samples, bpp < 8, handles built from a view. The environment variable alone
+ *      leaves such frames as they were. It holds from the next decode on.
+ *      Served with the switch on: both output formats, a region, a group range, scale 1 and 2 (through the full-size staging image and
+ *      k_downscale), the orientation, wide frames, sequences (Replace and the blend modes). "TODO" or as before: batches and pipelines
+ *      (no Modular frames there), restoration filters (a Modular frame applies none), type-2 frames, patches, splines, noise, upsampling.
+ *      j40hip_frame_modular_xyb: out[0] the rule applies to the frame; out[1] it is in force; out[2] bytes per sample of the frame's
+ *      planes (2 or 4; 0 for a VarDCT frame); out[3] the last decode went through k_modular_xyb_pack / k_modular_to_xyb.
+ *      With the switch in force j40hip_frame_read_xyb(f, 0, out) answers for such a frame after a decode: the three planes X, Y, B
+ *      ([3][height][width] floats) by k_modular_to_xyb over the decoded integer planes -- "rnge" where that decode covered part of the
+ *      frame only (a region's groups, a partial group range): the planes outside it are not this decode's. ---- */
+J40HIP_API uint32_t j40hip_frame_set_modular_xyb(j40hip_frame *f, int mode);
+J40HIP_API void j40hip_frame_modular_xyb(const j40hip_frame *f, int32_t out[4]);
+/* known-answer / measuring hook: the Modular XYB kernels on caller-supplied planes in device memory. planes_dev: c0, c1, c2 (width x
+ * height samples of sample_bytes 2 or 4 each, tightly packed); alpha_dev: the alpha plane of the same kind, or null; m: the three
+ * dequantisation factors; colour_consts: the 15 floats of j40hip_frame_colour_consts (the last two are not used); bpp 8..16.
+ * fused_dev: k_modular_xyb_pack's pixels. two_kernel_dev: k_modular_to_xyb into xyb_dev (3 * width * height floats: X, Y, B), then the
+ * VarDCT colour tail's kernel over those planes, A from the alpha plane by the pack kernels' rule. Both images in `format`
+ * (J40HIP_U8X4 or J40HIP_U16X4), stride_bytes a row, rows pixel-aligned. The call waits for `stream`. 0, "rnge", "Ufm?". */
+J40HIP_API uint32_t j40hip_kat_device_modular_xyb(const void *const planes_dev[3], const void *alpha_dev, int32_t sample_bytes, int32_t width, int32_t height, const float m[3], const float colour_consts[15],
+		int32_t bpp, int32_t format, void *fused_dev, void *two_kernel_dev, size_t stride_bytes, float *xyb_dev, void *stream);
+/* measuring hook (tools/modxyb_probe.py): ONE kernel over caller-supplied device memory, enqueued on `stream` and not waited for.
+ * kernel 0: k_modular_xyb_pack (in_dev: the planes c0, c1, c2 as above); 1: k_pack_planes on the same planes; 2: k_xyb_to_rgba (in_dev: three
+ * float planes X, Y, B of width x height, sample_bytes ignored; frame_dev: what j40hip_kat_device_colour_frame filled). No alpha plane.
+ * j40hip_kat_device_colour_frame: the colour tail's frame constants for k_xyb_to_rgba into frame_dev, device memory of at least
+ * `bytes` bytes; returns the bytes it needs, writing nothing when `bytes` is less, or 0 when the copy failed (synchronous). */
+J40HIP_API uint32_t j40hip_kat_device_modular_xyb_launch(int32_t kernel, const void *const in_dev[3], int32_t sample_bytes, int32_t width, int32_t height, const float m[3], const float colour_consts[15],
+		int32_t bpp, int32_t format, void *out_dev, size_t stride_bytes, const void *frame_dev, void *stream);
+J40HIP_API size_t j40hip_kat_device_colour_frame(const float colour_consts[15], int32_t bpp, void *frame_dev, size_t bytes);
 /* staged hook: plane c (0 Cb, 1 Y, 2 Cr) of the last decode that went through the YCbCr path, as k_ycbcr_tail read it -- the pixel
  * kernels' samples, or the restoration filters' result where those ran -- tightly packed: width x height floats for a 4:4:4 frame;
  * for a subsampled one the block grid padded to whole MCUs, ((ceil(width / (8 << mh)) << mh) * 8 >> hshift[c]) x (likewise with
@@ -565,8 +604,10 @@ J40HIP_API uint32_t j40hip_batch_reset(j40hip_batch *b, j40hip_frame *const *fra
  *      no adaptive smoothing (k_lf_from_frame); its LF indices count the thresholds t with sample > (float) t * mult_lf of that
  *      channel at extra_precision 0 (k_lf_frame_bctx then looks the block contexts up again) -- PARITY UNPINNED, like what an LF
  *      frame stores: the reference refuses such streams. "lfno": the slot was never filled (found at j40hip_sequence_open, it ends the
- *      index); "lfsz": the stored picture is not ceil(w / 8) x ceil(h / 8). Still "TODO" with the switch: a Modular LF frame, an image
- *      that is not XYB encoded or has extra channels, use_lf_frame on a YCbCr frame. The main frame of such a still (a regular frame
+ *      index); "lfsz": the stored picture is not ceil(w / 8) x ceil(h / 8). A Modular LF frame (the only kind libjxl writes) is served when
+ *      J40HIP_SEQ_MODULAR_XYB is given as well: its integer planes are decoded and k_modular_to_xyb makes the slot's three planes of
+ *      them (j40hip_frame_set_modular_xyb's rule, PARITY UNPINNED); with the LF switch alone it stays "TODO". Still "TODO" with the
+ *      switches: an image that is not XYB encoded or has extra channels, use_lf_frame on a YCbCr or Modular frame. The main frame of such a still (a regular frame
  *      with use_lf_frame that covers the canvas) is the one handle of a sequence that takes j40hip_frame_set_scale and
  *      j40hip_frame_set_orientation, for decodes of its own once the playback has filled its LF slot; the playback refuses it
  *      ("Usc?" / "Uor?") while either is set. j40hip_sequence_rewind unbinds the handles from the slots ("lfno" until played again). Outside a sequence (j40hip_frame_parse*, batches, the pipeline) such
@@ -574,6 +615,10 @@ J40HIP_API uint32_t j40hip_batch_reset(j40hip_batch *b, j40hip_frame *const *fra
  *      that picture. ---- */
 #define J40HIP_SEQ_BLEND 2u   /* j40hip_sequence_open: serve the blend modes Add (1), Blend (2), MulAdd (3) and Mul (4) too */
 #define J40HIP_SEQ_LFFRAME 16u   /* j40hip_sequence_open: serve LF frames (type 1) and the frames that take their LF image from one (use_lf_frame) */
+/* j40hip_sequence_open: the Modular frames of an XYB image go through the XYB colour tail (j40hip_frame_set_modular_xyb's mode 1 on every
+ * handle the rule applies to; J40HIP_MODULAR_XYB=1 in the environment does the same). Together with J40HIP_SEQ_LFFRAME a Modular LF frame
+ * is served: k_modular_to_xyb fills its LF slot. With either alone such a frame stays "TODO". */
+#define J40HIP_SEQ_MODULAR_XYB 32u
 typedef struct j40hip_sequence j40hip_sequence;
 J40HIP_API j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads, uint32_t flags, uint32_t *err);
 J40HIP_API void j40hip_sequence_free(j40hip_sequence *s);

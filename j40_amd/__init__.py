@@ -134,6 +134,10 @@ def lib():
         "j40hip_frame_set_ycbcr": (u32, [vp, C.c_int]), "j40hip_frame_ycbcr": (None, [vp, vp]), "j40hip_frame_read_ycbcr": (u32, [vp, C.c_int, vp]),
         "j40hip_frame_wide": (None, [vp, vp]), "j40hip_frame_read_plane_i32": (u32, [vp, C.c_int, vp]),
         "j40hip_kat_device_ycbcr_tail": (u32, [vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+        "j40hip_frame_set_modular_xyb": (u32, [vp, C.c_int]), "j40hip_frame_modular_xyb": (None, [vp, vp]),
+        "j40hip_kat_device_modular_xyb": (u32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, sz, vp, vp]),
+        "j40hip_kat_device_modular_xyb_launch": (u32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, vp, sz, vp, vp]),
+        "j40hip_kat_device_colour_frame": (sz, [vp, i32, vp, sz]),
         "j40hip_frame_set_region": (u32, [vp, i32, i32, i32, i32]), "j40hip_frame_region": (None, [vp, vp]),
         "j40hip_frame_set_scale": (u32, [vp, i32]), "j40hip_frame_scale": (None, [vp, vp]), "j40hip_pipeline_set_scale": (u32, [vp, i32]),
         "j40hip_kat_device_downscale": (u32, [vp, sz, vp, sz, i32, i32, i32, i32, vp]),
@@ -143,7 +147,7 @@ def lib():
         "j40hip_frame_read_xyb": (u32, [vp, C.c_int, vp]), "j40hip_frame_restoration_ms": (C.c_float, [vp]),
         "j40hip_kat_device_restoration": (u32, [vp, i32, i32, vp, vp, vp, C.c_int, C.c_int, vp]),
         "j40hip_frame_lf_end": (i64, [vp]), "j40hip_frame_lf_size": (None, [vp, C.POINTER(i32), C.POINTER(i32)]),
-        "j40hip_frame_lf_plane": (u32, [vp, C.c_int, vp]), "j40hip_frame_colour_consts": (None, [vp, vp]),
+        "j40hip_frame_lf_plane": (u32, [vp, C.c_int, vp]), "j40hip_frame_colour_consts": (None, [vp, vp]), "j40hip_frame_lf_dequant": (None, [vp, vp]),
         "j40hip_frame_decode_lf": (u32, [vp, vp, sz, vp]), "j40hip_frame_decode_lf_to_host": (u32, [vp, vp, sz]),
         "j40hip_frames_decode_lf": (u32, [vp, i64, vp, vp, vp]), "j40hip_frame_read_lf": (u32, [vp, C.c_int, vp]),
         "j40hip_pipeline_result": (u32, [vp, i64]), "j40hip_pipeline_stats": (None, [vp, vp]), "j40hip_pipeline_stats_ex": (None, [vp, vp]), "j40hip_pipeline_lf_stats": (None, [vp, vp]), "j40hip_pipeline_reset_stats": (None, [vp]),
@@ -234,7 +238,7 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
     scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
     (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
@@ -252,12 +256,15 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     ("TODO" with the other switches): the playback fills the LF slots at full size, then the main frame's own handle -- which keeps
     its LF source -- is decoded once more at the scale and / or in the orientation, as any frame is (Frame.set_scale,
     Frame.set_orientation; a refusal where the shown frame is not a full-canvas frame with use_lf_frame). A stream that is no
-    sequence is decoded as without it."""
+    sequence is decoded as without it.
+    modular_xyb=True: a Modular frame of an XYB image goes through the XYB colour tail for this call whatever J40HIP_MODULAR_XYB says
+    (Frame.set_modular_xyb(1); "Umx?" for a frame the rule does not apply to), through the thin C-ABI on device 0. With lf_frames=True
+    the sequence is opened with both switches, which serves a Modular LF frame."""
     if lf_frames:
         if alpha or ycbcr or wide:
             return "TODO", None
         try:
-            seq = Sequence(data, lf_frames=True)
+            seq = Sequence(data, lf_frames=True, modular_xyb=bool(modular_xyb))
         except J40Error as e:
             if e.code != "Usq?":
                 return e.code, None
@@ -281,13 +288,15 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
                 return e.code, None
             finally:
                 seq.close()
-    if alpha or scale or ycbcr or orient or wide:
+    if alpha or scale or ycbcr or orient or wide or modular_xyb:
         try:
             fr = Frame(data, ycbcr=bool(ycbcr), wide=bool(wide))
         except J40Error as e:
             return e.code, None
         try:
             code = fr.set_alpha(1) if alpha else ""
+            if not code and modular_xyb:
+                code = fr.set_modular_xyb(1)
             if not code and ycbcr:
                 code = fr.set_ycbcr(1)
             if not code and scale:
@@ -419,6 +428,39 @@ def kat_device_orient(src, orientation, fmt=None, pad=0, device=0):
     host = d_out.cpu().numpy().reshape(oh, stride)
     guard = bool((host[:, ow * pb:] == 0xA5).all())
     return "", np.ascontiguousarray(host[:, :ow * pb]).view(src.dtype).reshape(oh, ow, 4), guard
+
+
+def kat_device_modular_xyb(planes, alpha, m, colour_consts, bpp, fmt=J40_U8X4, pad=0, device=0):
+    """the Modular XYB kernels alone (j40hip_kat_device_modular_xyb): planes [3, h, w] int16 or int32 (c0, c1, c2), alpha [h, w] of the
+    same dtype or None, m [3], colour_consts [15] -> (err4, fused [h, w, 4], two_kernel [h, w, 4], xyb [3, h, w] float32, guard):
+    k_modular_xyb_pack's pixels; those of k_modular_to_xyb followed by the VarDCT colour tail's kernel; the planes in between. Rows
+    carry `pad` guard bytes filled with 0xA5 beforehand; guard: they all came back untouched."""
+    import torch
+    planes = np.ascontiguousarray(planes)
+    assert planes.dtype in (np.int16, np.int32) and planes.ndim == 3 and planes.shape[0] == 3
+    _, h, w = planes.shape
+    pb = 8 if fmt == J40_U16X4 else 4
+    stride = w * pb + pad
+    dev = "cuda:%d" % device
+    d_planes = [torch.from_numpy(planes[c].copy()).to(dev) for c in range(3)]
+    d_alpha = None if alpha is None else torch.from_numpy(np.ascontiguousarray(alpha, planes.dtype)).to(dev)
+    d_fused = torch.full((h * stride,), 0xA5, dtype=torch.uint8, device=dev)
+    d_two = torch.full((h * stride,), 0xA5, dtype=torch.uint8, device=dev)
+    d_xyb = torch.zeros((3, h, w), dtype=torch.float32, device=dev)
+    ptrs = (C.c_void_p * 3)(*[p.data_ptr() for p in d_planes])
+    mm = np.ascontiguousarray(m, np.float32); cc = np.ascontiguousarray(colour_consts, np.float32)
+    assert mm.size == 3 and cc.size == 15
+    stream = torch.cuda.current_stream(device)
+    code = err4(lib().j40hip_kat_device_modular_xyb(ptrs, d_alpha.data_ptr() if d_alpha is not None else None, planes.dtype.itemsize, w, h, mm.ctypes.data, cc.ctypes.data,
+                                                    int(bpp), int(fmt), d_fused.data_ptr(), d_two.data_ptr(), stride, d_xyb.data_ptr(), stream.cuda_stream))
+    stream.synchronize()
+    if code:
+        return code, None, None, None, True
+    dt = np.uint16 if pb == 8 else np.uint8
+    hosts = [t.cpu().numpy().reshape(h, stride) for t in (d_fused, d_two)]
+    guard = all(bool((x[:, w * pb:] == 0xA5).all()) for x in hosts)
+    fused, two = [np.ascontiguousarray(x[:, :w * pb]).view(dt).reshape(h, w, 4) for x in hosts]
+    return "", fused, two, d_xyb.cpu().numpy(), guard
 
 
 def kat_device_srgb_u16(values, bpp):
@@ -734,12 +776,31 @@ class Frame:
         lib().j40hip_frame_ycbcr(self.h, a.ctypes.data)
         return {"ycbcr": int(a[0]), "shifts": tuple((int(a[1 + 2 * c]), int(a[2 + 2 * c])) for c in range(3)), "used": int(a[7])}
 
+    def set_modular_xyb(self, mode):
+        """a Modular frame of an XYB image: -1 as J40HIP_MODULAR_XYB says, 0 rendered as R, G, B (the reference's pixels), 1 through the
+        XYB colour tail (PARITY UNPINNED); returns "" or "Umx?" (mode 1 on a frame the rule does not apply to: VarDCT, not XYB encoded,
+        grey, YCbCr, float samples, fewer than 8 bits)"""
+        return err4(lib().j40hip_frame_set_modular_xyb(self.h, int(mode)))
+
+    def modular_xyb(self):
+        """{"applies": the rule applies to the frame, "on": it is in force, "sample_bytes": 2 or 4 (0: a VarDCT frame), "used": the last
+        decode went through k_modular_xyb_pack / k_modular_to_xyb}"""
+        a = np.zeros(4, np.int32)
+        lib().j40hip_frame_modular_xyb(self.h, a.ctypes.data)
+        return {"applies": int(a[0]), "on": int(a[1]), "sample_bytes": int(a[2]), "used": int(a[3])}
+
     def wide(self):
         """{"wide": the image has 32-bit Modular buffers, "bpp": its bit depth, "used": the last decode ran the int32 kernels,
         "sample_bytes": bytes per sample of the uploaded frame's planes (0 before an upload)}"""
         a = np.zeros(4, np.int32)
         lib().j40hip_frame_wide(self.h, a.ctypes.data)
         return {"wide": int(a[0]), "bpp": int(a[1]), "used": int(a[2]), "sample_bytes": int(a[3])}
+
+    def read_plane_i16(self, c, shape):
+        """after a decode of a narrow Modular frame: channel c of the frame's planes (after the inverse transforms), int16 [shape]"""
+        a = np.zeros(shape, np.int16)
+        self._chk(lib().j40hip_frame_read_plane_i16(self.h, int(c), a.ctypes.data), "in j40hip_frame_read_plane_i16")
+        return a
 
     def read_plane_i32(self, c, shape):
         """after a decode of a wide frame: channel c of the frame's planes (after the inverse transforms), int32 [shape]"""
@@ -771,7 +832,8 @@ class Frame:
         return a
 
     def read_xyb(self, stage):
-        """after a decode that ran the filters: stage 0 / 1 -> [3, height, width] float32 (before / after them), 2 -> the reciprocal sigmas [h8, w8]"""
+        """after a decode that ran the filters: stage 0 / 1 -> [3, height, width] float32 (before / after them), 2 -> the reciprocal sigmas [h8, w8].
+        A Modular frame of an XYB image decoded with set_modular_xyb(1) in force: stage 0 -> the planes X, Y, B by k_modular_to_xyb"""
         a = np.zeros((3, self.height, self.width), np.float32) if stage < 2 else np.zeros(((self.height + 7) // 8, (self.width + 7) // 8), np.float32)
         self._chk(lib().j40hip_frame_read_xyb(self.h, stage, a.ctypes.data), "in j40hip_frame_read_xyb")
         return a
@@ -865,6 +927,12 @@ class Frame:
         lib().j40hip_frame_colour_consts(self.h, a.ctypes.data)
         return a[:9].reshape(3, 3).copy(), a[9:12].copy(), np.float32(a[12]), np.float32(a[13]), np.float32(a[14])
 
+    def lf_dequant(self):
+        """LfGlobal's LF dequantisation m_lf_scaled (X, Y, B) as parsed, float32 [3]"""
+        a = np.zeros(3, np.float32)
+        lib().j40hip_frame_lf_dequant(self.h, a.ctypes.data)
+        return a
+
     def decode_lf(self, rgba_ptr, stride_bytes, stream=0):
         """the preview into device memory, asynchronously on `stream`"""
         self._chk(lib().j40hip_frame_decode_lf(self.h, rgba_ptr, stride_bytes, stream), "in j40hip_frame_decode_lf")
@@ -929,6 +997,7 @@ def decode_lf_many(datas, fmt=J40_U8X4, device=0):
 
 SEQ_BLEND = 2   # j40hip_sequence_open's flag J40HIP_SEQ_BLEND: the blend modes Add, Blend, MulAdd and Mul are served
 SEQ_LFFRAME = 16   # ... J40HIP_SEQ_LFFRAME: LF frames (type 1) and the frames with use_lf_frame are served
+SEQ_MODULAR_XYB = 32   # ... J40HIP_SEQ_MODULAR_XYB: Modular frames of an XYB image go through the XYB colour tail; with SEQ_LFFRAME a Modular LF frame is served
 SEQUENCE_BLEND_FIELDS = ("mode", "alpha_mode", "alpha_chan", "clamp", "alpha_alpha_chan", "alpha_clamp", "src", "blended")
 SEQUENCE_FRAME_FIELDS = ("x0", "y0", "w", "h", "duration", "is_last", "shown", "type", "blend", "src", "save_as_reference", "saved",
                          "offset", "end", "first_section", "code", "tps_num", "tps_den", "loops", "canvas_w", "canvas_h")
@@ -939,13 +1008,15 @@ class Sequence:
     an index over headers and TOCs on the host, every coded frame an ordinary Frame, the displayed canvases composed on the device.
     blend=True (or J40HIP_BLEND=1): frames with the blend modes Add, Blend, MulAdd and Mul are served too, else "TODO" for such a frame.
     lf_frames=True (or J40HIP_LFFRAME=1): LF frames (type 1) and the frames that take their LF image from one (use_lf_frame) are
-    served too, else "TODO"; an LF frame is a row that is neither shown nor saved (frame_lf)"""
+    served too, else "TODO"; an LF frame is a row that is neither shown nor saved (frame_lf).
+    modular_xyb=True (or J40HIP_MODULAR_XYB=1): the Modular frames of an XYB image go through the XYB colour tail (Frame.set_modular_xyb);
+    together with lf_frames=True a Modular LF frame is served, with either alone it is "TODO"."""
 
-    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False):
+    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False, modular_xyb: bool = False):
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0)
+        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0) | (SEQ_MODULAR_XYB if modular_xyb else 0)
         self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags, C.byref(err))
         if not self.h:
             raise J40Error(err4(err.value), "in j40hip_sequence_open")
@@ -1055,14 +1126,15 @@ class Sequence:
         return err4(code), int(k.value)
 
 
-def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False):
+def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False, modular_xyb=False):
     """every displayed frame of an animation or a layered still: ([(rgba ndarray [height, width, 4], duration in ticks), ...],
     (tps_num, tps_den, loops)). alpha=True: VarDCT frames keep their alpha channel (Frame.set_alpha(1); J40Error where that refuses).
     blend=True: frames with a blend mode other than Replace are composed too (Sequence's blend=), else such a frame raises "TODO".
     wide=True: an image with 32-bit Modular buffers is served (Sequence's wide=; its Modular frames only).
     lf_frames=True: LF frames and the frames that take their LF image from one are served (Sequence's lf_frames=), else "TODO".
+    modular_xyb=True: Modular frames of an XYB image go through the XYB colour tail (Sequence's modular_xyb=).
     A frame that fails raises J40Error with its code. A stream whose first frame is its last is not a sequence ("Usq?"): decode()."""
-    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames)
+    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames, modular_xyb=modular_xyb)
     try:
         seq.set_output_format(fmt)
         if alpha:

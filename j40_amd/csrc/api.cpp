@@ -206,6 +206,8 @@ uint32_t read_whole_file(j40__inner *inner) {
 bool frames_policy() { return j40hip::env_on("J40HIP_FRAMES", false); }
 // J40HIP_LFFRAME=1: a stream that holds an LF frame (type 1; libjxl's progressive_dc) goes through a sequence too, whatever
 // J40HIP_FRAMES says -- j40hip_sequence_open reads the same variable and serves such frames. Without it such a stream is "TODO".
+// (J40HIP_MODULAR_XYB=1 needs nothing here: a frame handle and j40hip_sequence_open read it themselves -- Modular frames of an XYB image then
+// go through the XYB colour tail, and together with J40HIP_LFFRAME=1 a Modular LF frame is served.)
 bool lf_frames_policy() { return j40hip::env_on("J40HIP_LFFRAME", false); }
 // J40HIP_SCALE=1|2: every image decodes at 1:2 / 1:4 (j40hip_frame_set_scale): j40_frame_pixels_* then report the small image's width,
 // height and stride. Looked at when an image is first advanced, like J40HIP_FRAMES; unset, 0 or anything else: full size.

@@ -21,6 +21,11 @@ struct j40hip_frame {
 	int alpha = -1;                  // the alpha channel of a VarDCT frame (j40hip_frame_set_alpha): -1 as J40HIP_ALPHA says, 0 dropped (A = 255, the reference's pixels), 1 kept
 	bool alpha_written = false;      // the last decode merged the alpha channel into its pixels
 	int ycbcr = -1;                  // YCbCr VarDCT frames (j40hip_frame_set_ycbcr): -1 as J40HIP_YCBCR says, 0 refused ("TODO", the reference's answer), 1 served
+	// Modular frames of XYB images (j40hip_frame_set_modular_xyb): -1 as J40HIP_MODULAR_XYB says, 0 rendered as R, G, B (the reference's pixels), 1 through
+	// the XYB colour tail; and whether the last decode went through k_modular_xyb_pack / k_modular_to_xyb
+	int modular_xyb = -1;
+	bool modular_xyb_used = false;
+	bool modular_xyb_whole = false;   // ... and decoded every group: the planes hold the whole frame (j40hip_frame_read_xyb)
 	bool wide_used = false;          // the last decode ran the int32 instantiations of the Modular kernels (a wide frame, j40hip_frame_wide)
 	bool ycbcr_used = false;         // the last decode went through the YCbCr planes and k_ycbcr_tail
 	int32_t output_format = J40HIP_U8X4;   // what the decode entry points write (j40hip_frame_set_output_format): u8x4 or u16x4
@@ -89,6 +94,7 @@ struct j40hip_sequence {
 	int threads = 1; uint32_t flags = 0;
 	bool blend = false;              // the blend modes other than Replace are served (J40HIP_SEQ_BLEND or J40HIP_BLEND=1)
 	bool lf_frames = false;          // LF frames and use_lf_frame are served (J40HIP_SEQ_LFFRAME or J40HIP_LFFRAME=1)
+	bool modular_xyb = false;        // Modular frames of an XYB image go through the XYB colour tail (J40HIP_SEQ_MODULAR_XYB or J40HIP_MODULAR_XYB=1)
 	int32_t alpha_ec = -1;           // the extra channel that is rendered as A (rendered_alpha_channel); -1: none
 	int32_t output_format = J40HIP_U8X4;
 	j40hip_sequence_device *dev = nullptr;
@@ -108,6 +114,18 @@ inline bool j40hip_alpha_kept(const j40hip_frame *h) {
 inline bool j40hip_ycbcr_on(const j40hip_frame *h) {
 	const bool asked = h->ycbcr >= 0 ? h->ycbcr == 1 : j40hip::ycbcr_env();
 	return asked && !h->from_view && !h->from_sequence;
+}
+
+// Modular frames of XYB images: the frames the rule applies to -- a Modular frame of a colour image with
+// xyb_encoded = 1, integer samples of 8 bits or more, no YCbCr -- and whether it is in force: asked for (or J40HIP_MODULAR_XYB=1) on such
+// a frame; with the environment variable alone every other frame decodes as before
+inline bool j40hip_modular_xyb_applies(const j40hip_frame *h) {
+	const j40hip::Frame &f = h->frame;
+	return f.fh.is_modular && f.im.xyb_encoded && !f.im.grey && !f.fh.do_ycbcr && !f.im.exp_bits && f.im.bpp >= 8 && !f.lf_only && !h->from_view;
+}
+inline bool j40hip_modular_xyb_on(const j40hip_frame *h) {
+	const bool asked = h->modular_xyb >= 0 ? h->modular_xyb == 1 : j40hip::modular_xyb_env();
+	return asked && j40hip_modular_xyb_applies(h);
 }
 
 // A handle a sequence hands out for the main frame of a still whose LF image is a frame of its own: a regular frame with use_lf_frame

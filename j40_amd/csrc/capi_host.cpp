@@ -160,6 +160,7 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 		s->threads = threads < 1 ? 1 : threads > 16 ? 16 : threads; s->flags = flags;
 		s->blend = (flags & J40HIP_SEQ_BLEND) != 0 || env_on("J40HIP_BLEND", false);   // (looked at with every sequence that is opened)
 		s->lf_frames = (flags & J40HIP_SEQ_LFFRAME) != 0 || env_on("J40HIP_LFFRAME", false);
+		s->modular_xyb = (flags & J40HIP_SEQ_MODULAR_XYB) != 0 || env_on("J40HIP_MODULAR_XYB", false);
 		size_t at = 0;
 		parse_image_header(s->cs, s->cs_size, &s->im, &at, (flags & J40HIP_PARSE_WIDE) != 0 || wide_env());
 		s->alpha_ec = rendered_alpha_channel(s->im);
@@ -169,7 +170,7 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 			Toc toc;
 			row.offset = at;
 			try {
-				parse_sequence_frame_header(s->cs, s->cs_size, at, s->im, s->blend, s->lf_frames, &row.fh, &toc);
+				parse_sequence_frame_header(s->cs, s->cs_size, at, s->im, s->blend, s->lf_frames, &row.fh, &toc, s->lf_frames && s->modular_xyb);
 				row.first_section = at + toc.first_offset; row.end = at + toc.end_offset;
 				// (a frame whose sections the stream does not hold to their end: whatever follows it cannot be found)
 				if (row.end > s->cs_size) row.code = E4("shrt");
@@ -275,11 +276,12 @@ j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err
 		h->cs = h->cs_storage.data();
 		h->bare_codestream = true;
 		h->frame.defer_lf_tail = (s->flags & 1u) != 0;
-		h->frame.seq_im = &s->im; h->frame.seq_blend = s->blend; h->frame.allow_lf_frame = s->lf_frames; h->frame.allow_wide = (s->flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
+		h->frame.seq_im = &s->im; h->frame.seq_blend = s->blend; h->frame.allow_lf_frame = s->lf_frames; h->frame.allow_modular_lf = s->lf_frames && s->modular_xyb; h->frame.allow_wide = (s->flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
 		parse_frame(h->cs, h->cs_size, &h->frame, s->threads);
 		h->threads = s->threads;
 		h->output_format = s->output_format;
 		h->from_sequence = true;
+		h->modular_xyb = s->modular_xyb ? 1 : 0;   // (in force where the rule applies: j40hip_modular_xyb_on)
 	} catch (const DecodeError &e) { code = e.code; }
 	catch (const std::exception &) { code = E4("!mem"); }
 	h->frame.seq_im = nullptr;   // (copied into the frame)
@@ -338,6 +340,21 @@ void j40hip_frame_ycbcr(const j40hip_frame *h, int32_t out[8]) {
 	out[0] = !fh.is_modular && fh.do_ycbcr ? 1 : 0;
 	for (int c = 0; c < 3; ++c) { out[1 + 2 * c] = fh.hshift[c]; out[2 + 2 * c] = fh.vshift[c]; }
 	out[7] = h->ycbcr_used ? 1 : 0;
+}
+
+// ---- Modular frames of XYB images (include/j40hip.h) ----
+uint32_t j40hip_frame_set_modular_xyb(j40hip_frame *h, int mode) {
+	if (!h) return j40hip::ERR_RNGE;
+	if (mode > 0 && !j40hip_modular_xyb_applies(h)) return E4("Umx?");
+	h->modular_xyb = mode < 0 ? -1 : mode > 0 ? 1 : 0;
+	return 0;
+}
+void j40hip_frame_modular_xyb(const j40hip_frame *h, int32_t out[4]) {
+	if (!out) return;
+	memset(out, 0, sizeof(int32_t) * 4);
+	if (!h) return;
+	out[0] = j40hip_modular_xyb_applies(h) ? 1 : 0; out[1] = j40hip_modular_xyb_on(h) ? 1 : 0;
+	out[2] = h->frame.fh.is_modular ? (h->frame.wide() ? 4 : 2) : 0; out[3] = h->modular_xyb_used ? 1 : 0;
 }
 
 // ---- region decode (include/j40hip.h) ----
@@ -472,6 +489,8 @@ void j40hip_frame_colour_consts(const j40hip_frame *h, float *out) {
 	out[13] = f.base_corr_x + (float) f.x_factor_lf * f.inv_colour_factor;   // j40.h:7115-7116
 	out[14] = f.base_corr_b + (float) f.b_factor_lf * f.inv_colour_factor;
 }
+
+void j40hip_frame_lf_dequant(const j40hip_frame *h, float *out) { for (int i = 0; i < 3; ++i) out[i] = h->frame.m_lf_scaled[i]; }
 
 void j40hip_frame_lf_group_info(const j40hip_frame *h, int64_t gg, int32_t *out) {
 	const LfGroup &g = h->frame.lf_groups[(size_t) gg];

@@ -223,6 +223,7 @@ bool j40hip_rt::ensure_constant_tables(int device) {
 	upload_constant_tables(half_secants(), afv_basis(), srgb_u8_thresholds(), nullptr);
 	upload_lf_tail_tables(half_secants(), lf2llf_scales(), nullptr);
 	upload_lf_preview_tables(srgb_u8_thresholds(), nullptr);
+	upload_modular_xyb_tables(srgb_u8_thresholds(), nullptr);
 	if (hipStreamSynchronize(nullptr) != hipSuccess) return false;
 	return g_const_done[device] = true;
 }

@@ -102,6 +102,17 @@ void launch_ycbcr_tail(const YcbcrTail &t, uint8_t *rgba, size_t stride, hipStre
 // shift: the scale shift; 1, 2: ceil(width / s) x ceil(height / s) pixels, each the mean of its cell's rendered samples (scale_dev.h)
 void launch_pack_planes(PlanePtr r, PlanePtr g, PlanePtr b, PlanePtr a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false, int32_t shift = 0);
 
+// a Modular frame of an XYB image through the XYB colour tail (device/modular_xyb_kernels.hip, modular_xyb_dev.h): c0, c1, c2 the colour
+// planes (quantised Y, X, B - Y), a as above; k: the frame's m_lf_scaled and colour constants. The rect form as launch_pack_planes_rect.
+// launch_modular_to_xyb: the rectangle's three float planes alone, its sample (0, 0) first, `pitch` floats a row
+struct ModXybConsts;
+void upload_modular_xyb_tables(const float *srgb_thr, hipStream_t stream);
+void launch_modular_xyb_pack(PlanePtr c0, PlanePtr c1, PlanePtr c2, PlanePtr a, int32_t width, int32_t height, const ModXybConsts &k, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
+void launch_modular_xyb_pack_rect(PlanePtr c0, PlanePtr c1, PlanePtr c2, PlanePtr a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, const ModXybConsts &k, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
+// (the known-answer hook's two-kernel route: the A of every pixel of a width x height image from the alpha plane, pack_rgba8 / pack_rgba16's sample)
+void launch_kat_alpha_from_plane(PlanePtr a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16);
+void launch_modular_to_xyb(PlanePtr c0, PlanePtr c1, PlanePtr c2, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, const ModXybConsts &k, float *x, float *y, float *b, size_t pitch, hipStream_t stream);
+
 // reduced-size decode (device/scale_kernels.hip, scale_dev.h): the full W x H image at src made 1:2 (shift 1) or 1:4 (shift 2) at dst,
 // pixel_bytes 4 or 8, every row pixel-aligned
 void launch_downscale(const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, int32_t W, int32_t H, int32_t shift, int32_t pixel_bytes, hipStream_t stream);

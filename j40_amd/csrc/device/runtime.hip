@@ -21,12 +21,18 @@ bool j40hip_rt::modular_groups_independent(const j40hip_frame *h) {
 // cover's rows, and the rectangle packed with the destination moved back by its origin; every section where the groups depend on
 // each other
 // shift: the scale shift of a whole-frame decode (decode_scaled): the pack kernel writes the small image
-static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, const int32_t *region = nullptr, int32_t shift = 0) {
+// A Modular frame of an XYB image with the switch in force (j40hip_frame_set_modular_xyb): k_modular_xyb_pack stands in for k_pack_planes at
+// all three places (never at a shift: decode_scaled stages such a frame). xyb_out (decode_frame_xyb, a Modular LF frame; the whole frame
+// only): no pixels -- k_modular_to_xyb leaves the three float planes there, width * height floats each.
+static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, const int32_t *region = nullptr, int32_t shift = 0, float *xyb_out = nullptr) {
 	j40hip_device_state *st = h->dev;
 	const DevModPlan &plan = st->mod;
 	const Frame &fr = h->frame;
 	const bool wide = st->mod_wide;   // int32 planes (the plane pointers carry the sample size themselves)
 	h->wide_used = wide;
+	const bool xyb = modular_xyb_on(h) && st->final_planes.size() >= 3;
+	h->modular_xyb_used = xyb;
+	if ((xyb_out && !xyb) || (xyb && shift > 0)) return ERR_TODO;
 	RegionCover cover = {0, 0, 0, 0, 0, 0};
 	bool covered = false;   // only the cover's groups are decoded
 	if (region) {
@@ -46,6 +52,7 @@ static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_by
 	// (sharded decodes, j40hip_frame_set_group_range: LfGlobal's section and this process' groups of every pass)
 	const bool ranged = per_pass > 0 && !(st->first_group == 0 && st->num_groups == (int64_t) per_pass);
 	const int32_t g0 = ranged ? (int32_t) st->first_group : 0, gn = ranged ? (int32_t) st->num_groups : per_pass;
+	h->modular_xyb_whole = xyb && !covered && !ranged;
 	if (covered) {
 		launch_modular_sections(plan, 0, lead, st->mod_info, s);
 		for (int32_t p = 0; p < st->mod_passes; ++p) for (int32_t r = 0; r < cover.rows; ++r) launch_modular_sections(plan, lead + p * per_pass + (cover.gy0 + r) * cover.gcolumns + cover.gx0, cover.cols, st->mod_info, s);
@@ -73,14 +80,23 @@ static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_by
 		else launch_paste_plane(op.src, op.p0, op.p1, op.a, op.p2, s);
 	}
 	const PlanePtr alpha = st->alpha_channel >= 0 ? st->final_planes[(size_t) st->alpha_channel] : PlanePtr{nullptr, st->final_planes[0].sample_bytes};
-	if (region) {   // the rectangle alone; pixel (x0, y0) of the frame is the first one at rgba_dev
+	const ModXybConsts xk = xyb ? modular_xyb_consts(fr) : ModXybConsts();
+	if (xyb_out) {
+		const size_t plane = (size_t) fr.fh.width * (size_t) fr.fh.height;
+		launch_modular_to_xyb(st->final_planes[0], st->final_planes[1], st->final_planes[2], fr.fh.width, 0, 0, fr.fh.width, fr.fh.height, xk, xyb_out, xyb_out + plane, xyb_out + 2 * plane, (size_t) fr.fh.width, s);
+	} else if (region) {   // the rectangle alone; pixel (x0, y0) of the frame is the first one at rgba_dev
 		uint8_t *moved = (uint8_t *) rgba_dev - ((size_t) region[1] * stride_bytes + (size_t) region[0] * pixel_bytes(h));
-		launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, region[0], region[1], region[2], region[3], fr.im.bpp, moved, stride_bytes, s, out16(h));
+		if (xyb) launch_modular_xyb_pack_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, region[0], region[1], region[2], region[3], xk, moved, stride_bytes, s, out16(h));
+		else launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, region[0], region[1], region[2], region[3], fr.im.bpp, moved, stride_bytes, s, out16(h));
 	} else if (ranged) {   // only this process' pixels are written
 		int32_t rects[3][4];
 		const int nr = group_range_rects(g0, gn, fr.fh.width, fr.fh.height, fr.fh.group_size_shift, rects);
-		for (int k = 0; k < nr; ++k) launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
-	} else launch_pack_planes(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h), shift);
+		for (int k = 0; k < nr; ++k) {
+			if (xyb) launch_modular_xyb_pack_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], xk, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
+			else launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
+		}
+	} else if (xyb) launch_modular_xyb_pack(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, xk, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
+	else launch_pack_planes(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h), shift);
 	marks.mark(3);
 	if (uint32_t e = marks.finish(ms3)) return e;
 	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
@@ -363,7 +379,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 }
 
 // what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it
-static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->wide_used = false; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
+static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->wide_used = false; h->modular_xyb_used = false; h->modular_xyb_whole = false; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
 
 // One VarDCT decode as decode_impl (whole frames, group ranges) and decode_region (covers) describe it to run_vardct
 struct VardctRun {
@@ -470,6 +486,12 @@ uint32_t j40hip_rt::decode_frame_xyb(j40hip_frame *h, float *planes, hipStream_t
 	if (!h || !h->dev || !planes) return ERR_GPU;
 	j40hip_device_state *st = h->dev;
 	// (what keeps it from being three full-size XYB planes: Modular and YCbCr samples, extra channels behind the coefficients, part of a frame)
+	// a Modular LF frame (the sequence serves Modular XYB frames too): its integer planes, then k_modular_to_xyb
+	if (st->is_modular) {
+		if (!modular_xyb_on(h) || h->region_set || h->scale > 0 || h->partial_range) return ERR_TODO;
+		if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
+		return decode_modular(h, nullptr, 0, s, nullptr, nullptr, 0, planes);
+	}
 	if (h->frame.lf_only || st->is_modular || st->ycbcr || st->has_trailers || h->region_set || h->scale > 0 || h->partial_range) return ERR_TODO;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
 	VardctRun run = {0, (int32_t) h->frame.fh.num_groups, nullptr, st->d_vb_sorted, st->class_start, nullptr, 0, true, nullptr, nullptr, 0, 0, 0};
@@ -600,7 +622,8 @@ static uint32_t decode_scaled(j40hip_frame *h, void *rgba_dev, size_t stride_byt
 	if (scaled_stride_too_small(h, stride_bytes)) return ERR_RNGE;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
 	const int rmode = restoration_mode(h);
-	const bool staged = !st->is_modular && ((rmode && (fr.fh.restoration.gab || fr.fh.restoration.epf_iters > 0)) || (st->has_trailers && j40hip_alpha_kept(h)));
+	// (a Modular frame through the XYB colour tail: the mean is of rendered bytes, and k_modular_xyb_pack writes full-size pixels only)
+	const bool staged = st->is_modular ? modular_xyb_on(h) : ((rmode && (fr.fh.restoration.gab || fr.fh.restoration.epf_iters > 0)) || (st->has_trailers && j40hip_alpha_kept(h)));
 	if (staged) {
 		const size_t img_stride = ((size_t) W * pb + 15) & ~(size_t) 15, bytes = img_stride * (size_t) H;
 		if (!st->scale_staging.ensure(st->device, bytes, false)) return ERR_MEM;

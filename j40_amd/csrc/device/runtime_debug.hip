@@ -65,7 +65,24 @@ extern "C" uint32_t j40hip_frame_read_ycbcr(j40hip_frame *h, int c, float *out) 
 
 // after a decode that ran the filters (synchronised): stage 0 the samples as the inverse transforms left them, 1 the filtered ones --
 // three planes of width * height floats (X, Y, B); stage 2: the reciprocal-sigma plane (w8 * h8 floats)
+// (a Modular frame of an XYB image with the switch in force, stage 0: k_modular_to_xyb over the integer planes the last decode left --
+// "rnge" where that decode covered part of the frame, a region's groups or a group range: the planes outside it are stale)
+static uint32_t read_modular_xyb(j40hip_frame *h, float *out) {
+	j40hip_device_state *st = h->dev;
+	if (!h->modular_xyb_whole) return ERR_RNGE;
+	const FrameHeader &fh = h->frame.fh;
+	const size_t plane = (size_t) fh.width * (size_t) fh.height;
+	if (!out || st->final_planes.size() < 3) return ERR_RNGE;
+	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
+	ScopedBlock block;
+	if (!block.ensure(st->device, sizeof(float) * 3 * plane, true)) return ERR_MEM;
+	float *d = (float *) block.ptr;
+	launch_modular_to_xyb(st->final_planes[0], st->final_planes[1], st->final_planes[2], fh.width, 0, 0, fh.width, fh.height, modular_xyb_consts(h->frame), d, d + plane, d + 2 * plane, (size_t) fh.width, nullptr);
+	if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) return ERR_GPU;
+	return hipMemcpy(out, d, sizeof(float) * 3 * plane, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+}
 extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out) {
+	if (h && h->dev && h->dev->is_modular && stage == 0 && h->modular_xyb_used && modular_xyb_on(h)) return guarded([&] { return read_modular_xyb(h, out); });
 	if (!h || !h->dev || !h->dev->restore_ran || !h->dev->d_xyb) return ERR_RNGE;
 	j40hip_device_state *st = h->dev;
 	const FrameHeader &fh = h->frame.fh;
@@ -85,6 +102,80 @@ extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out
 		src = spare;
 	}
 	return hipMemcpy(out, src, 3 * plane * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+}
+// m[3] and the 15 colour constants of j40hip_frame_colour_consts as the kernels take them: by value (ModXybConsts) and as a DevFrame's fields
+static void kat_colour_consts(const float *m, const float *cc15, int32_t bpp, ModXybConsts *k, DevFrame *df) {
+	memset(df, 0, sizeof *df);
+	for (int c = 0; c < 3; ++c) { k->m[c] = m ? m[c] : 0.0f; k->cc.opsin_bias[c] = df->opsin_bias[c] = cc15[9 + c]; k->cc.cbrt_opsin_bias[c] = df->cbrt_opsin_bias[c] = cbrtf(cc15[9 + c]); }
+	for (int i = 0; i < 9; ++i) k->cc.m[i] = df->opsin_inv_mat[i] = cc15[i];
+	k->cc.itscale = df->itscale = 255.0f / cc15[12]; k->cc.bpp = df->bpp = bpp;
+}
+// known-answer / measuring hook: the Modular XYB kernels on caller-supplied planes (include/j40hip.h)
+extern "C" uint32_t j40hip_kat_device_modular_xyb(const void *const planes_dev[3], const void *alpha_dev, int32_t sample_bytes, int32_t width, int32_t height, const float m[3], const float colour_consts[15],
+		int32_t bpp, int32_t format, void *fused_dev, void *two_kernel_dev, size_t stride_bytes, float *xyb_dev, void *stream) {
+	return guarded([&]() -> uint32_t {
+		if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
+		const size_t pb = format == J40HIP_U16X4 ? 8 : 4;
+		if (!planes_dev || !planes_dev[0] || !planes_dev[1] || !planes_dev[2] || !m || !colour_consts || !fused_dev || !two_kernel_dev || !xyb_dev) return ERR_RNGE;
+		if ((sample_bytes != 2 && sample_bytes != 4) || width <= 0 || height <= 0 || width > (1 << 28) || height > (1 << 28) || bpp < 8 || bpp > 16 || (bpp == 16 && sample_bytes == 2)) return ERR_RNGE;
+		if (stride_bytes < pb * (size_t) width || stride_bytes % pb || (uintptr_t) fused_dev % pb || (uintptr_t) two_kernel_dev % pb) return ERR_RNGE;
+		for (int c = 0; c < 3; ++c) if ((uintptr_t) planes_dev[c] % (size_t) sample_bytes) return ERR_RNGE;
+		if ((uintptr_t) alpha_dev % (size_t) sample_bytes || (uintptr_t) xyb_dev % 4) return ERR_RNGE;
+		int device = 0;
+		if (hipGetDevice(&device) != hipSuccess || !ensure_constant_tables(device)) return ERR_GPU;
+		hipStream_t s = (hipStream_t) stream;
+		ModXybConsts k;
+		DevFrame df;
+		kat_colour_consts(m, colour_consts, bpp, &k, &df);
+		df.width = width; df.height = height;
+		auto pp = [&](const void *p) { return PlanePtr{(uint8_t *) const_cast<void *>(p), sample_bytes}; };
+		launch_modular_xyb_pack(pp(planes_dev[0]), pp(planes_dev[1]), pp(planes_dev[2]), pp(alpha_dev), width, height, k, (uint8_t *) fused_dev, stride_bytes, s, pb == 8);
+		// the two-kernel route: the planes, the VarDCT colour tail's kernel over them (A opaque), A from the alpha plane as the pack kernels render it
+		const size_t plane = (size_t) width * (size_t) height;
+		launch_modular_to_xyb(pp(planes_dev[0]), pp(planes_dev[1]), pp(planes_dev[2]), width, 0, 0, width, height, k, xyb_dev, xyb_dev + plane, xyb_dev + 2 * plane, (size_t) width, s);
+		j40hip_device_state tmp; tmp.device = device;
+		bool ok = true;
+		DevFrame *d_frame = tmp.upload(&df, 1, s, ok);
+		if (ok) {
+			launch_xyb_to_rgba(xyb_dev, (size_t) width, d_frame, width, height, (uint8_t *) two_kernel_dev, stride_bytes, s, pb == 8);
+			if (alpha_dev) launch_kat_alpha_from_plane(pp(alpha_dev), width, height, bpp, (uint8_t *) two_kernel_dev, stride_bytes, s, pb == 8);
+			ok = hipGetLastError() == hipSuccess;
+		}
+		if (hipStreamSynchronize(s) != hipSuccess) ok = false;   // (df and the uploaded copy live until here)
+		for (auto &b : tmp.buffers) b.release();
+		tmp.buffers.clear();
+		return ok ? 0 : ERR_GPU;
+	});
+}
+// measuring hooks (tools/modxyb_probe.py; include/j40hip.h)
+extern "C" size_t j40hip_kat_device_colour_frame(const float colour_consts[15], int32_t bpp, void *frame_dev, size_t bytes) {
+	if (!colour_consts || !frame_dev || bytes < sizeof(DevFrame)) return sizeof(DevFrame);
+	ModXybConsts k; DevFrame df;
+	kat_colour_consts(nullptr, colour_consts, bpp, &k, &df);
+	return hipMemcpy(frame_dev, &df, sizeof df, hipMemcpyHostToDevice) == hipSuccess ? sizeof(DevFrame) : 0;   // (0: the copy failed)
+}
+extern "C" uint32_t j40hip_kat_device_modular_xyb_launch(int32_t kernel, const void *const in_dev[3], int32_t sample_bytes, int32_t width, int32_t height, const float m[3], const float colour_consts[15],
+		int32_t bpp, int32_t format, void *out_dev, size_t stride_bytes, const void *frame_dev, void *stream) {
+	return guarded([&]() -> uint32_t {
+	if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
+	const size_t pb = format == J40HIP_U16X4 ? 8 : 4;
+	if (kernel < 0 || kernel > 2 || !in_dev || !in_dev[0] || !in_dev[1] || !in_dev[2] || !m || !colour_consts || !out_dev || width <= 0 || height <= 0 || bpp < 8 || bpp > 16) return ERR_RNGE;
+	if ((kernel != 2 && sample_bytes != 2 && sample_bytes != 4) || (kernel == 2 && !frame_dev) || stride_bytes < pb * (size_t) width || stride_bytes % pb || (uintptr_t) out_dev % pb) return ERR_RNGE;
+	for (int c = 0; c < 3; ++c) if ((uintptr_t) in_dev[c] % (size_t) (kernel == 2 ? 4 : sample_bytes)) return ERR_RNGE;
+	int device = 0;
+	if (hipGetDevice(&device) != hipSuccess || !ensure_constant_tables(device)) return ERR_GPU;
+	ModXybConsts k; DevFrame df;
+	kat_colour_consts(m, colour_consts, bpp, &k, &df);
+	auto pp = [&](const void *p) { return PlanePtr{(uint8_t *) const_cast<void *>(p), sample_bytes}; };
+	const PlanePtr none = {nullptr, sample_bytes};
+	if (kernel == 0) launch_modular_xyb_pack(pp(in_dev[0]), pp(in_dev[1]), pp(in_dev[2]), none, width, height, k, (uint8_t *) out_dev, stride_bytes, (hipStream_t) stream, pb == 8);
+	else if (kernel == 1) launch_pack_planes(pp(in_dev[0]), pp(in_dev[1]), pp(in_dev[2]), none, width, height, bpp, (uint8_t *) out_dev, stride_bytes, (hipStream_t) stream, pb == 8);
+	else {
+		if ((const float *) in_dev[1] != (const float *) in_dev[0] + (size_t) width * (size_t) height || (const float *) in_dev[2] != (const float *) in_dev[1] + (size_t) width * (size_t) height) return ERR_RNGE;   // (one behind the other)
+		launch_xyb_to_rgba((const float *) in_dev[0], (size_t) width, (const DevFrame *) frame_dev, width, height, (uint8_t *) out_dev, stride_bytes, (hipStream_t) stream, pb == 8);
+	}
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+	});
 }
 extern "C" float j40hip_frame_restoration_ms(const j40hip_frame *h) { return h && h->dev ? h->dev->restore_ms : 0.0f; }
 // known-answer hook: the filter kernels on caller-supplied planes ([3][h][w] floats, in place), a w8*h8 sharpness map and the HfMul

@@ -16,6 +16,7 @@
 #include "../plan_build.hpp"
 #include "../mod_layout.hpp"
 #include "kernels.h"
+#include "modular_xyb_dev.h"
 #include "runtime_shared.hpp"
 
 using namespace j40hip;      // (an internal header: every unit that includes it is written in these two namespaces)
@@ -264,6 +265,17 @@ inline int32_t scaled_width(const j40hip_frame *h) { return (h->frame.fh.width +
 inline int32_t scaled_height(const j40hip_frame *h) { return (h->frame.fh.height + (1 << h->scale) - 1) >> h->scale; }
 // at a shift above 0 the rows must hold the small image's pixels, in both formats
 inline bool scaled_stride_too_small(const j40hip_frame *h, size_t stride_bytes) { return h->scale > 0 ? stride_bytes < pixel_bytes(h) * (size_t) scaled_width(h) : stride_too_small(h, stride_bytes); }
+
+// a Modular frame of an XYB image through the XYB colour tail (j40hip_frame_set_modular_xyb): in force for this frame, and what its kernels
+// take -- LfGlobal's LF dequantisation and the colour constants as fill_frame_constants (plan_build.cpp) states them for DevFrame
+inline bool modular_xyb_on(const j40hip_frame *h) { return j40hip_modular_xyb_on(h); }
+inline ModXybConsts modular_xyb_consts(const Frame &fr) {
+	ModXybConsts k;
+	for (int c = 0; c < 3; ++c) { k.m[c] = fr.m_lf_scaled[c]; k.cc.opsin_bias[c] = fr.im.opsin_bias[c]; k.cc.cbrt_opsin_bias[c] = cbrtf(fr.im.opsin_bias[c]); }
+	for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) k.cc.m[i * 3 + j] = fr.im.opsin_inv_mat[i][j];
+	k.cc.itscale = 255.0f / fr.im.intensity_target; k.cc.bpp = fr.im.bpp;
+	return k;
+}
 
 // what crosses units
 bool host_vb_sorted(j40hip_device_state *st);                                  // runtime_upload.hip

@@ -167,6 +167,9 @@ static uint32_t upload_impl(j40hip_frame *h, int device, hipStream_t s) {
 	h->partial_range = false;   // (an upload decodes every group again)
 	if (j40hip_device_count() <= device || hipSetDevice(device) != hipSuccess) return ERR_GPU;
 	if (h->frame.lf_only) return upload_lf_only(h, device, s);
+	// (a frame the Modular XYB switch may be put in force for: its colour tail reads the sRGB thresholds, which a Modular upload never needed --
+	// taken here, once per device, so that the decode entry points stay asynchronous)
+	if (h->frame.fh.is_modular && j40hip_modular_xyb_applies(h) && !ensure_constant_tables(device)) return ERR_GPU;
 	if (h->frame.fh.is_modular) return upload_modular(h, device);
 	HostPlan &hp = t_host_plan;   // (this thread's, storage kept from frame to frame)
 	hp.reset();

@@ -880,9 +880,9 @@ int32_t rendered_alpha_channel(const ImageMeta &im) {
 	for (size_t i = 0; i < im.ec.size(); ++i) if (im.ec[i].type == EC_ALPHA) return (int32_t) i;
 	return -1;
 }
-uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, bool lf_frames, bool xyb) {
+uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, bool lf_frames, bool xyb, bool modular_lf) {
 	bool ok = (fh.type == 0 || fh.type == 3) && !fh.use_lf_frame;
-	if (lf_frames && (fh.type == 1 || fh.use_lf_frame)) ok = (fh.type == 0 || fh.type == 3 || (fh.type == 1 && !fh.is_modular)) && xyb && !(fh.use_lf_frame && (fh.do_ycbcr || fh.is_modular))
+	if (lf_frames && (fh.type == 1 || fh.use_lf_frame)) ok = (fh.type == 0 || fh.type == 3 || (fh.type == 1 && (!fh.is_modular || (modular_lf && !fh.do_ycbcr)))) && xyb && !(fh.use_lf_frame && (fh.do_ycbcr || fh.is_modular))
 		&& !(fh.type == 1 && !fh.ec_blend.empty());   // (an LF frame with extra channels behind its coefficients: nothing here keeps or checks them)
 	if (!blend) {
 		ok = ok && fh.blend.mode == 0;
@@ -894,11 +894,11 @@ uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, b
 	}
 	return ok ? 0 : (uint32_t) E4("TODO");
 }
-void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, bool lf_frames, FrameHeader *fh, Toc *toc) {
+void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, bool lf_frames, FrameHeader *fh, Toc *toc, bool modular_lf) {
 	J40HIP_SHOULD(offset < cs_size, "shrt");
 	BitReader br(cs + offset, cs_size - offset);
 	read_frame_header(br, im, fh, true, lf_frames);
-	if (uint32_t e = sequence_refusal(*fh, blend, rendered_alpha_channel(im), lf_frames, im.xyb_encoded)) raise(e);
+	if (uint32_t e = sequence_refusal(*fh, blend, rendered_alpha_channel(im), lf_frames, im.xyb_encoded, modular_lf)) raise(e);
 	read_toc(br, *fh, toc);
 }
 
@@ -908,7 +908,7 @@ static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size
 	if (f->seq_im) {   // a sequence's member: its bytes start at the frame header
 		f->im = *f->seq_im;
 		read_frame_header(br, f->im, &f->fh, true, f->allow_lf_frame);
-		if (uint32_t e = sequence_refusal(f->fh, f->seq_blend, rendered_alpha_channel(f->im), f->allow_lf_frame, f->im.xyb_encoded)) raise(e);
+		if (uint32_t e = sequence_refusal(f->fh, f->seq_blend, rendered_alpha_channel(f->im), f->allow_lf_frame, f->im.xyb_encoded, f->allow_modular_lf)) raise(e);
 	} else {
 		read_image_header(br, &f->im, f->allow_wide);
 		read_frame_header(br, f->im, &f->fh);

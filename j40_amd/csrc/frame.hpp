@@ -22,6 +22,7 @@ inline bool alpha_env() { static const bool v = [] { const char *e = env_str("J4
 inline bool orient_env() { static const bool v = [] { const char *e = env_str("J40HIP_ORIENT"); return e && atoi(e) > 0; }(); return v; }
 // J40HIP_YCBCR=1: YCbCr VarDCT frames (recompressed JPEGs) are served where j40hip_frame_set_ycbcr(f, 1) would be taken (include/j40hip.h); read once
 inline bool wide_env() { static const bool v = [] { const char *e = env_str("J40HIP_WIDE"); return e && atoi(e) > 0; }(); return v; }
+inline bool modular_xyb_env() { static const bool v = [] { const char *e = env_str("J40HIP_MODULAR_XYB"); return e && atoi(e) > 0; }(); return v; }
 inline bool ycbcr_env() { static const bool v = [] { const char *e = env_str("J40HIP_YCBCR"); return e && atoi(e) > 0; }(); return v; }
 
 struct ExtraChannel { int32_t type = 0, bpp = 8, exp_bits = 0, dim_shift = 0; bool alpha_associated = false; };
@@ -213,6 +214,9 @@ struct Frame {
 	// a frame with use_lf_frame is parsed -- its LfGroup sections start at nb_varblocks, its LF integers and LF indices stay zero (the
 	// device fills both in from the LF frame's picture, device/lf_tail_kernels.hip) -- instead of refused with "TODO". Set before parse_frame.
 	bool allow_lf_frame = false;
+	// ... and Modular LF frames among them (the sequence also renders Modular frames of XYB images through the XYB colour tail,
+	// J40HIP_SEQ_MODULAR_XYB or J40HIP_MODULAR_XYB=1: k_modular_to_xyb fills the LF slot). Set before parse_frame.
+	bool allow_modular_lf = false;
 	bool wide() const { return !im.modular_16bit_buffers; }
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
@@ -220,7 +224,7 @@ struct Frame {
 		Frame g;
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
-		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr; g.allow_wide = allow_wide; g.allow_lf_frame = allow_lf_frame;
+		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr; g.allow_wide = allow_wide; g.allow_lf_frame = allow_lf_frame; g.allow_modular_lf = allow_modular_lf;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section
@@ -239,16 +243,16 @@ void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t
 // header and TOC of the frame that starts at byte `offset` of the codestream, for a sequence's index: nothing behind the TOC is
 // read. The TOC's offsets count from `offset`. Raises what the header or the TOC raise, "TODO" for what sequence_refusal refuses.
 // blend: the sequence serves the blend modes other than Replace, lf_frames: and LF frames (sequence_refusal).
-void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, bool lf_frames, FrameHeader *fh, Toc *toc);
+void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, bool lf_frames, FrameHeader *fh, Toc *toc, bool modular_lf = false);
 // the extra channel whose samples become the pixels' A (plan_build.cpp: alpha_channel): the first one of type alpha; -1: none
 int32_t rendered_alpha_channel(const ImageMeta &im);
 // 0, or "TODO": the frame is of a kind a sequence does not serve -- types 1 and 2, use_lf_frame, and a blend mode other than Replace
 // in any channel. With `blend` the other four modes are served for the colour channels and for extra channel `alpha_ec` (the rendered
 // alpha, -1: none; the other extra channels' entries are not looked at), unless a Blend or MulAdd of either names another alpha
-// channel than `alpha_ec`. With `lf_frames` type 1 and use_lf_frame pass, unless the LF frame is a Modular one (nothing renders Modular
-// samples to XYB floats) or of an image with extra channels, the image is not XYB encoded (`xyb`), or the frame with use_lf_frame is a
+// channel than `alpha_ec`. With `lf_frames` type 1 and use_lf_frame pass, unless the LF frame is a Modular one and `modular_lf` is not
+// set (without the Modular XYB switch nothing renders Modular samples to XYB floats) or of an image with extra channels, the image is not XYB encoded (`xyb`), or the frame with use_lf_frame is a
 // YCbCr or Modular one
-uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, bool lf_frames = false, bool xyb = true);
+uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, bool lf_frames = false, bool xyb = true, bool modular_lf = false);
 
 // parses headers, TOC, LfGlobal, HfGlobal and every LfGroup section. `threads` > 1 decodes LfGroup
 // sections concurrently (they are independent given LfGlobal)

@@ -70,13 +70,42 @@ struct LfRole {
 	int lfidx_distinct = 0;     // out: how many values its cells' LF index takes
 };
 static LfRole *g_lf = nullptr;
+// lfmodular=1 (lflevels=; run_lf_sequence): the Modular writer codes these three planes (c0, c1, c2: quantised Y, X, B - Y on a grid of
+// cells `src_w` wide, each cell over 8 x 8 samples) as an LF frame of `level` (type 1, lf_level, no placement fields) of an XYB image
+struct ModularLfRole { int level = 0; std::vector<int32_t> src[3]; int src_w = 0; };
+static ModularLfRole *g_mod_lf = nullptr;
+
+// forward opsin (numerical inverse of the decoder's default inverse matrix, j40.h:3109): sRGB samples in [0, 1] to X, Y, B. The VarDCT
+// writer's to_xyb, and what xybpic=1 quantises in Modular mode.
+struct ForwardOpsin {
+	double fwd[3][3], bias, cbias;
+	ForwardOpsin() {
+		const double inv[3][3] = {
+			{11.031566901960783, -9.866943921568629, -0.16462299647058826},
+			{-3.254147380392157, 4.418770392156863, -0.16462299647058826},
+			{-3.6588512862745097, 2.7129230470588235, 1.9459282392156863}};
+		double a = inv[0][0], b = inv[0][1], c = inv[0][2], d = inv[1][0], e = inv[1][1], f = inv[1][2], g = inv[2][0], h = inv[2][1], i = inv[2][2];
+		double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
+		fwd[0][0] = (e * i - f * h) / det; fwd[0][1] = (c * h - b * i) / det; fwd[0][2] = (b * f - c * e) / det;
+		fwd[1][0] = (f * g - d * i) / det; fwd[1][1] = (a * i - c * g) / det; fwd[1][2] = (c * d - a * f) / det;
+		fwd[2][0] = (d * h - e * g) / det; fwd[2][1] = (b * g - a * h) / det; fwd[2][2] = (a * e - b * d) / det;
+		bias = -0.0037930732552754493; cbias = cbrt(bias);
+	}
+	void operator()(const float rgb[3], double xyb[3]) const {
+		double lin[3];
+		for (int c = 0; c < 3; ++c) { double v = rgb[c]; lin[c] = v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4); }
+		double mix[3];
+		for (int c = 0; c < 3; ++c) mix[c] = cbrt(fwd[c][0] * lin[0] + fwd[c][1] * lin[1] + fwd[c][2] * lin[2] - bias) + cbias;
+		xyb[0] = (mix[0] - mix[1]) * 0.5; xyb[1] = (mix[0] + mix[1]) * 0.5; xyb[2] = mix[2];
+	}
+};
 
 // orientation=N (1..8, every mode): ImageMetadata.extra_fields carries orientation - 1; 0: the option was not given
 static int g_orientation = 0;
-// tone=IT,MIN[,LINEAR_BELOW[,RELATIVE]] (vardct): extra fields (orientation 1 and nothing else unless other options say otherwise) and
+// tone=IT,MIN[,LINEAR_BELOW[,RELATIVE]] (vardct, and modular with xyb=1): extra fields (orientation 1 and nothing else unless other options say otherwise) and
 // ToneMapping written out: intensity_target, min_nits, linear_below as f16 bits, relative_to_max_display. Empty: the option was not given
 static std::vector<uint32_t> g_tone;
-// opsin=M00,..,M22,B0,B1,B2,Q0,Q1,Q2,QNUM (vardct): default_m = 0 and the custom-transform block: opsin_inv_mat row-major, opsin_bias,
+// opsin=M00,..,M22,B0,B1,B2,Q0,Q1,Q2,QNUM (vardct, and modular with xyb=1): default_m = 0 and the custom-transform block: opsin_inv_mat row-major, opsin_bias,
 // quant_bias, quant_bias_num as f16, then cw_mask = 0 (cwmask=1..7: a stream decoders refuse). A value is a decimal number that an
 // f16 holds exactly, or `h` and four hex digits: the f16's bits as they are (h7c00: an infinity, which decoders refuse as well)
 static std::vector<uint32_t> g_opsin;
@@ -501,27 +530,11 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 
 	Picture pic(W, H, seed);
 
-	// ---- forward opsin (numerical inverse of the decoder's default inverse matrix, j40.h:3109) ----
-	const double inv[3][3] = {
-		{11.031566901960783, -9.866943921568629, -0.16462299647058826},
-		{-3.254147380392157, 4.418770392156863, -0.16462299647058826},
-		{-3.6588512862745097, 2.7129230470588235, 1.9459282392156863}};
-	double fwd[3][3];
-	{
-		double a = inv[0][0], b = inv[0][1], c = inv[0][2], d = inv[1][0], e = inv[1][1], f = inv[1][2], g = inv[2][0], h = inv[2][1], i = inv[2][2];
-		double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
-		fwd[0][0] = (e * i - f * h) / det; fwd[0][1] = (c * h - b * i) / det; fwd[0][2] = (b * f - c * e) / det;
-		fwd[1][0] = (f * g - d * i) / det; fwd[1][1] = (a * i - c * g) / det; fwd[1][2] = (c * d - a * f) / det;
-		fwd[2][0] = (d * h - e * g) / det; fwd[2][1] = (b * g - a * h) / det; fwd[2][2] = (a * e - b * d) / det;
-	}
-	const double bias = -0.0037930732552754493, cbias = cbrt(bias);
-	auto to_xyb = [&](const float rgb[3], double xyb[3]) {
-		double lin[3];
-		for (int c = 0; c < 3; ++c) { double v = rgb[c]; lin[c] = v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4); }
-		double mix[3];
-		for (int c = 0; c < 3; ++c) mix[c] = cbrt(fwd[c][0] * lin[0] + fwd[c][1] * lin[1] + fwd[c][2] * lin[2] - bias) + cbias;
-		xyb[0] = (mix[0] - mix[1]) * 0.5; xyb[1] = (mix[0] + mix[1]) * 0.5; xyb[2] = mix[2];
-	};
+	// ---- forward opsin (ForwardOpsin, above) ----
+	const ForwardOpsin opsin_fwd;
+	const double (&fwd)[3][3] = opsin_fwd.fwd;
+	const double bias = opsin_fwd.bias, cbias = opsin_fwd.cbias;
+	auto to_xyb = [&](const float rgb[3], double xyb[3]) { opsin_fwd(rgb, xyb); };
 	// LF dequant steps (j40.h:6562): m_lf_scaled / (global_scale * quant_lf) * 65536
 	const double m_lf[3] = {1.0 / 4096, 1.0 / 512, 1.0 / 256};
 	double lfstep[3]; for (int c = 0; c < 3; ++c) lfstep[c] = m_lf[c] / ((double) global_scale * quant_lf) * (double) (65536 >> extra_prec);
@@ -1656,6 +1669,45 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		if (deep_alpha) { int32_t &a = ch[(size_t) (3 + extra)].at(x, y); const int amax = (1 << bpp) - 1; a = a == 255 ? amax : a == 0 ? 0 : std::min(amax, a * amax / 255 + ((x * 7 + y * 13) & ((1 << (bpp - 8)) - 1))); }
 	}
 
+	// xyb=1: the image says xyb_encoded, and the three colour channels are read as quantised XYB -- c0 = Y / m[1], c1 = X / m[0],
+	// c2 = B / m[2] - c0 with m = LfGlobal's LF dequantisation (the reference renders them as R, G, B all the same). By default the picture
+	// above stands as it is, whatever colours that makes. xybpic=1: the procedural picture itself, through the VarDCT writer's forward
+	// opsin (ForwardOpsin) and rounded to those integers: a lossy-Modular encode in miniature. dumprgb=PATH then writes the source picture,
+	// float32 [height][width][3], sRGB samples in [0, 1]. lfdequant=a,b,c: m, other than the default 1/4096, 1/512, 1/256 (each times 128
+	// must be a value an f16 holds).
+	const int flag_xyb_image = opt.geti("xyb", 0), xybpic = opt.geti("xybpic", 0);
+	double m_lf[3] = {1.0 / 4096, 1.0 / 512, 1.0 / 256};
+	const bool custom_m_lf = opt.kv.count("lfdequant") != 0;
+	if (custom_m_lf && (sscanf(opt.gets("lfdequant", "").c_str(), "%lf,%lf,%lf", &m_lf[0], &m_lf[1], &m_lf[2]) != 3 || !(m_lf[0] > 0 && m_lf[1] > 0 && m_lf[2] > 0))) die("modular: lfdequant=a,b,c, all positive");
+	if ((xybpic || custom_m_lf) && !flag_xyb_image) die("modular: xybpic=1 and lfdequant= describe an XYB image: they want xyb=1");
+	if (xybpic && (palette || squeeze || repeat > 1 || tile_px || noise || opt.kv.count("range") || opt.geti("fourvalues", 0) || bias)) die("modular: xybpic=1 codes the procedural picture itself: no palette, squeeze, repeat, tile, noise, range, fourvalues or bias");
+	if (opt.kv.count("dumprgb") && !xybpic) die("modular: dumprgb= writes the picture xybpic=1 codes");
+	if (xybpic) {
+		const ForwardOpsin to_xyb;
+		std::vector<float> source;
+		for (int y = 0; y < pic_h; ++y) for (int x = 0; x < pic_w; ++x) {
+			float rgb[3]; double xyb[3];
+			pic.rgb((float) x, (float) y, rgb);
+			for (int c = 0; c < 3; ++c) { rgb[c] = std::min(1.0f, std::max(0.0f, rgb[c])); source.push_back(rgb[c]); }
+			to_xyb(rgb, xyb);
+			const int32_t c0 = (int32_t) lrint(xyb[1] / m_lf[1]);
+			ch[(size_t) colour0].at(x, y) = c0;
+			ch[(size_t) colour0 + 1].at(x, y) = (int32_t) lrint(xyb[0] / m_lf[0]);
+			ch[(size_t) colour0 + 2].at(x, y) = (int32_t) lrint(xyb[2] / m_lf[2]) - c0;
+			if (!wide) for (int c = 0; c < 3; ++c) if (ch[(size_t) colour0 + (size_t) c].at(x, y) < -32768 || ch[(size_t) colour0 + (size_t) c].at(x, y) > 32767) die("modular: xybpic=1: a quantised sample leaves int16 (a coarser lfdequant=, or wide=1)");
+		}
+		if (opt.kv.count("dumprgb")) {
+			FILE *fp = fopen(opt.gets("dumprgb", "").c_str(), "wb");
+			if (!fp || fwrite(source.data(), 4, source.size(), fp) != source.size()) die("cannot write dumprgb");
+			fclose(fp);
+		}
+	}
+	// (lfmodular=1 of lflevels=: the planes run_lf_sequence hands over, each cell over 8 x 8 samples)
+	if (g_mod_lf) {
+		if (!flag_xyb_image || palette || squeeze || repeat > 1 || alpha || extra || wide || !g_seq) die("modular: an LF frame is written by lflevels= lfmodular=1 only");
+		for (int c = 0; c < 3; ++c) for (int y = 0; y < pic_h; ++y) for (int x = 0; x < pic_w; ++x) ch[(size_t) colour0 + (size_t) c].at(x, y) = g_mod_lf->src[c][(size_t) (y / 8) * (size_t) g_mod_lf->src_w + (size_t) (x / 8)];
+	}
+
 	if (squeeze && repeat > 1) {   // lay the tile out over the whole frame
 		for (Channel &c : ch) {
 			Channel full(W, H);
@@ -2061,7 +2113,8 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	std::vector<std::vector<uint8_t>> sections;
 	{
 		BitWriter bw;
-		bw.put(1, 1);                 // LF channel dequantisation: default
+		if (!custom_m_lf) bw.put(1, 1);   // LF channel dequantisation: default
+		else { bw.put(0, 1); for (int c = 0; c < 3; ++c) bw.f16((float) (m_lf[c] * 128.0)); }   // (read back divided by 128, j40.h:6268)
 		bw.put(1, 1);                 // global tree present
 		write_code_spec(bw, treespec); tree_enc.flush(bw);
 		write_code_spec(bw, gspec);
@@ -2152,15 +2205,26 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	// frames (j40.h:8209-8210, 7910) and renders the three channels as they are
 	cs.put(opt.geti("xyb", 0) ? 1 : 0, 1);   // xyb_encoded
 	const int icc_bytes = opt.geti("icc", 0);
+	if (opt.geti("grey", 0)) {
+		// grey=1 (with xyb=1, no icc): the colour encoding says grey, D65, sRGB transfer, relative intent. An XYB image codes three
+		// channels whatever its colour space (j40.h:3619), so the stream is a valid one -- of a grey image
+		if (!opt.geti("xyb", 0) || icc_bytes) die("modular: grey=1 wants xyb=1 (three coded channels all the same) and no icc");
+		cs.put(0, 1); cs.put(0, 1);     // ColourEncoding: not all_default, no ICC profile
+		cs.put(1, 2);                   // colour_space = grey (enum value 1)
+		cs.put(1, 2);                   // white_point = D65
+		cs.put(0, 1);                   // no gamma
+		cs.put(2, 2); cs.put(11, 4);    // transfer function 13 (sRGB): enum selector 2, 2 + 11
+		cs.put(1, 2);                   // rendering intent 1
+	} else
 	if (!icc_bytes) cs.put(1, 1);       // ColourEncoding.all_default (sRGB)
 	else { cs.put(0, 1); cs.put(1, 1); cs.put(0, 2); }   // want_icc, colour_space = RGB
-	write_header_tail(cs, true, opt.geti("xyb", 0) != 0);   // (tone= / opsin= are refused in this mode: the all-default tail)
+	write_header_tail(cs, true, opt.geti("xyb", 0) != 0);   // (tone= / opsin=: with xyb=1 only, main() sees to it)
 	if (icc_bytes) write_icc_stream(cs, rng, icc_bytes);
 	}
 	const int flag_xyb = opt.geti("xyb", 0), flag_ycbcr = opt.geti("ycbcr", 0);
 	cs.pad();
 	cs.put(0, 1);                       // FrameHeader: not all_default
-	cs.put(0, 2);                       // regular frame
+	cs.put(g_mod_lf ? 1 : 0, 2);        // regular frame (an LF frame: type 1)
 	cs.put(1, 1);                       // modular
 	cs.u64(0);                          // flags
 	if (!flag_xyb) cs.put(flag_ycbcr ? 1 : 0, 1);   // do_ycbcr
@@ -2173,6 +2237,8 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 1);                  // num_ds = 0
 		for (int i = 0; i < num_passes - 1; ++i) cs.put(0, 2);  // shift[i]
 	}
+	if (g_mod_lf) cs.put((uint64_t) (g_mod_lf->level - 1), 2);   // lf_level - 1; no crop, no blend info, never last, saved nowhere (j40.h:5285-5336)
+	else
 	write_frame_placement(cs, extra + (alpha ? 1 : 0), Wfull, Hfull);   // have_crop, blend modes (colour, extra channels), is_last
 	cs.u32(0, 0, 0, 0, 4, 16, 5, 48, 10);
 	cs.put(0, 1); cs.put(0, 1); cs.put(0, 2); cs.u64(0);   // restoration: explicit, gab off, epf 0, no extensions
@@ -2261,9 +2327,16 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 		srcs = split_list(opt_in.gets("srcs", ""), ','), saves = split_list(opt_in.gets("saves", ""), ','), blends = split_list(opt_in.gets("blends", ""), ','),
 		ecblends = split_list(opt_in.gets("ecblends", ""), ','), ecsrcs = split_list(opt_in.gets("ecsrcs", ""), ',');
 	if (!durs.empty() && !anim) die("durations= wants anim=1 (frames of a still have no duration)");
+	// modes=v,m,...: per-frame writers, v the VarDCT one and m the Modular one (an empty entry: the command's mode). Every frame gets every
+	// option; the first frame writes the image header, so the options must describe one image to both writers (a Modular frame under a
+	// VarDCT frame's header: xyb=1, and alpha=1 for both or neither)
+	const std::vector<std::string> modes = split_list(opt_in.gets("modes", ""), ',');
+	bool any_vardct = vardct;
+	for (const std::string &m : modes) { if (!m.empty() && m != "v" && m != "m") die("modes=v|m,..."); any_vardct = any_vardct || m == "v"; }
+	if (!modes.empty() && any_vardct && !opt_in.geti("xyb", 0)) die("modes=: a Modular frame beside VarDCT frames is a frame of an XYB image: xyb=1");
 	Options opt = opt_in;
-	for (const char *k : {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "container", "stats"}) opt.kv.erase(k);
-	if (vardct && !opt.kv.count("fullheader")) opt.kv["fullheader"] = "1";
+	for (const char *k : {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "container", "stats", "modes"}) opt.kv.erase(k);
+	if (any_vardct && !opt.kv.count("fullheader")) opt.kv["fullheader"] = "1";
 	auto at = [](const std::vector<std::string> &v, int k, int def) { return k < (int) v.size() && !v[(size_t) k].empty() ? atoi(v[(size_t) k].c_str()) : def; };
 	std::vector<uint8_t> cs;
 	std::string rows;
@@ -2285,7 +2358,8 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 		if (only >= 0 && k != only) continue;
 		q.first = cs.empty();
 		g_seq = &q;
-		const int e = vardct ? run_vardct(fw, fh, seed + (uint64_t) k, out, opt) : run_modular(fw, fh, seed + (uint64_t) k, out, opt);
+		const bool frame_vardct = k < (int) modes.size() && !modes[(size_t) k].empty() ? modes[(size_t) k] == "v" : vardct;
+		const int e = frame_vardct ? run_vardct(fw, fh, seed + (uint64_t) k, out, opt) : run_modular(fw, fh, seed + (uint64_t) k, out, opt);
 		g_seq = nullptr;
 		if (e) return e;
 		// (the first frame's bytes start with the signature and the image header: its frame header is found by a reader, not here)
@@ -2338,6 +2412,11 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 //                    with use_lf_frame unless it is flat (then its LF integers are written out, as in a twin)
 //   bctx=1           the custom block-context map with LF thresholds combines with all of it but lfkind=picture (above)
 //   lfcrop=w,h       the main frame is a crop of w x h at (0, 0): a stream a decoder has to refuse, its LF frame is not of its cells' size
+//   lfmodular=1      (flat) the coarsest LF frame is written as a Modular frame of the XYB image -- the only kind of LF frame libjxl writes --
+//                    whose planes c0 = qY, c1 = qX, c2 = qB - qY are the flat VarDCT LF frame's integers, each over an 8 x 8 square. A decoder
+//                    that renders such a frame to XYB floats as (float) c0 * m[1], (float) c1 * m[0], (float) (c2 + c0) * m[2] arrives at the
+//                    flat VarDCT LF frame's samples float for float where that frame's LF step is m itself: global_scale * quant_lf = 65536;
+//                    and nocfl=1, so that no B sample carries a Y term. Refused elsewhere. (lftwin=1: the twin is the same stream either way.)
 // stats=1 prints the number of coded frames and how many values the main frame's LF index takes.
 static int run_lf_sequence(int W, int H, uint64_t seed, const char *out, const Options &opt_in) {
 	const int levels = opt_in.geti("lflevels", 1), twin = opt_in.geti("lftwin", 0), only = opt_in.geti("only", -1);
@@ -2350,8 +2429,15 @@ static int run_lf_sequence(int W, int H, uint64_t seed, const char *out, const O
 	if (opt_in.geti("extraprec", 0) || opt_in.geti("container", 0)) die("lflevels: extraprec=0 and no container");
 	if (only >= levels) die("only= names an LF frame here (0: the coarsest); the main frame is nothing without its LF frame");
 	if (only >= 0 && twin) die("only= and lftwin=1 exclude each other");
+	const int lfmodular = opt_in.geti("lfmodular", 0);
+	if (lfmodular) {
+		if (picture || only >= 0) die("lfmodular=1 writes the flat LF frame's integers as a Modular frame: lfkind=flat, no only=");
+		if ((long long) opt_in.geti("global_scale", 0) * opt_in.geti("quant_lf", 0) != 65536) die("lfmodular=1: the Modular LF frame's samples are integers times LfGlobal's LF dequantisation; they equal the flat VarDCT LF frame's only where its LF step is that factor: global_scale * quant_lf = 65536 (for instance global_scale=4096 quant_lf=16)");
+		if (!opt_in.geti("nocfl", 0)) die("lfmodular=1 wants nocfl=1: with chroma-from-luma the B samples carry a Y term that B - Y integers do not state");
+		if (opt_in.geti("alpha", 0)) die("lfmodular=1: no extra channels (an LF frame of such an image is refused)");
+	}
 	Options main_opt = opt_in;
-	for (const char *k : {"lflevels", "lfkind", "lftwin", "only", "stats", "lfgab", "lfepf", "lfcrop", "lfhfmul"}) main_opt.kv.erase(k);
+	for (const char *k : {"lflevels", "lfkind", "lftwin", "only", "stats", "lfgab", "lfepf", "lfcrop", "lfhfmul", "lfmodular"}) main_opt.kv.erase(k);
 	int crop_w = 0, crop_h = 0;
 	if (opt_in.kv.count("lfcrop") && (sscanf(opt_in.gets("lfcrop", "").c_str(), "%d,%d", &crop_w, &crop_h) != 2 || crop_w < 1 || crop_h < 1 || crop_w > W || crop_h > H || picture || twin || only >= 0)) die("lfcrop=w,h within the image, with lfkind=flat and neither lftwin nor only");
 	main_opt.kv["fullheader"] = "1";
@@ -2419,6 +2505,25 @@ static int run_lf_sequence(int W, int H, uint64_t seed, const char *out, const O
 		}
 		r.level = l; r.use = l < levels;
 		nowhere.clear();
+		if (lfmodular && l == levels) {
+			// the flat VarDCT LF frame to nowhere, for its integers (streamed order Y, X, B); then the Modular frame that states them
+			write(l, r, &nowhere, lf_opt_of(l));
+			ModularLfRole mr;
+			mr.level = l; mr.src_w = r.out_w;
+			mr.src[0] = r.out[0]; mr.src[1] = r.out[1]; mr.src[2] = r.out[2];
+			for (size_t i = 0; i < mr.src[2].size(); ++i) mr.src[2][i] -= mr.src[0][i];
+			Options mo;
+			mo.kv["xyb"] = "1"; mo.kv["rct"] = "-1";
+			SeqFrame q;
+			q.canvas_w = W; q.canvas_h = H; q.cs = alone ? &nowhere : &cs; q.first = q.cs->empty() || alone; q.is_last = false;
+			if (alone) nowhere.clear();
+			g_seq = &q; g_mod_lf = &mr;
+			const int e = run_modular(fw[l], fh[l], seed + (uint64_t) l, out, mo);
+			g_seq = nullptr; g_mod_lf = nullptr;
+			if (e) die("lflevels: the Modular LF frame could not be written");
+			++written;
+			continue;
+		}
 		write(l, r, alone ? &nowhere : &cs, l == 0 ? main_opt : lf_opt_of(l));
 		++written;
 	}
@@ -2441,7 +2546,7 @@ int main(int argc, char **argv) {
 		opt.kv.erase("orientation");
 	}
 	if (opt.kv.count("tone") || opt.kv.count("opsin") || opt.kv.count("cwmask")) {
-		if (!vardct) die("tone=, opsin= and cwmask= belong to the vardct mode");
+		if (!vardct && !opt.geti("xyb", 0)) die("tone=, opsin= and cwmask= belong to the vardct mode and to Modular frames of an XYB image (xyb=1)");
 		auto halves = [&](const char *k) {   // f16 bits of every value of the list
 			std::vector<uint32_t> v; const std::string s = opt.gets(k, "");
 			for (size_t at = 0; at < s.size(); ) {
@@ -2468,7 +2573,7 @@ int main(int argc, char **argv) {
 		if (!vardct) die("lflevels= belongs to the vardct mode");
 		return run_lf_sequence(W, H, seed, argv[5], opt);
 	}
-	static const char *const SEQ_KEYS[] ={"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only"};
+	static const char *const SEQ_KEYS[] ={"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "modes"};
 	bool sequence = false;
 	for (const char *k : SEQ_KEYS) sequence = sequence || opt.kv.count(k);
 	if (!sequence) return vardct ? run_vardct(W, H, seed, argv[5], opt) : run_modular(W, H, seed, argv[5], opt);
