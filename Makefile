@@ -15,8 +15,11 @@ SRC = j40_amd/csrc
 HOST_OBJS = build/obj/plan_build.o build/obj/plan_front.o build/obj/entropy.o build/obj/modular.o build/obj/tables.o build/obj/frame.o build/obj/capi_host.o build/obj/api.o
 DEV_OBJS = build/obj/kernels.o build/obj/modular_kernels.o build/obj/runtime.o build/obj/runtime_upload.o build/obj/runtime_lf.o build/obj/runtime_batch.o build/obj/runtime_lfp.o build/obj/runtime_debug.o build/obj/device_memory.o build/obj/pipeline.o build/obj/lf_tail_kernels.o build/obj/modular_coop.o build/obj/modular_quad.o build/obj/modular_split.o build/obj/lf_decode.o build/obj/plan_kernels.o build/obj/async.o build/obj/hostcopy.o build/obj/lf_preview.o build/obj/alpha_kernels.o build/obj/region_kernels.o build/obj/compose_kernels.o build/obj/runtime_seq.o build/obj/scale_kernels.o build/obj/ycbcr_kernels.o build/obj/orient_kernels.o build/obj/modular_xyb_kernels.o
 
-.PHONY: all lib tools oracle hostsim clean
+.PHONY: all lib tools oracle hostsim clean print-objs
 all: lib tools hostsim oracle
+# the library's objects, for tools/build_variant.sh
+print-objs:
+	@echo $(HOST_OBJS) $(DEV_OBJS)
 lib: build/libj40hip.so
 tools: build/jxlsynth
 oracle:

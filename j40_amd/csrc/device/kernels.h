@@ -19,26 +19,24 @@ void launch_store_group_rects(const uint32_t *order, int32_t k, int32_t gcolumns
 uint32_t hf_lanes_lds_bytes(const HfLaunchInfo &info);
 void launch_hf_entropy_lanes(const DevPlan *plans, const HfLaneWork *work, int32_t num_work, bool tables_in_lds, uint32_t lds_bytes, hipStream_t stream);
 void launch_hf_lanes(const DevPlan *plans, const HfLaneWork *work, int32_t num_work, int32_t waves_per_wg, uint32_t lds_bytes, hipStream_t stream, hipEvent_t started = nullptr, hipEvent_t stopped = nullptr, uint32_t *queue = nullptr);
-// rgba16: the 16-bit output (J40_U16X4, 8 bytes a pixel; idct_dev.h xyb_to_rgba16) instead of u8x4; shift: the scale shift (1, 2: the
-// kernels write the 1:2 / 1:4 image, scale_dev.h; `rgba` and `stride` are then the small image's)
-void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false, int32_t shift = 0);
-
-
 // every frame of a batch: one persistent launch per class of transforms, spread over `nside` side streams that fork from and join
 // `stream` (nside = 0: all on `stream`). tile_prefix_dev: K2_NUM_BATCH_LAUNCHES * (nframes + 1) ints of scratch; totals_dev:
 // K2_NUM_BATCH_LAUNCHES ints (out: tiles per launch); grids: workgroups per launch, from k2_batch_grids
 enum { K2_NUM_BATCH_LAUNCHES = 16, K2_LARGE_WGS = 256, K2_WG_SLOTS = 32768 };   // K2_WG_SLOTS: the most workgroups a launch gets (k2_batch_grids' wg_slots)
 void k2_batch_grids(const int32_t *last_totals, size_t cells_total, int32_t nframes, int32_t wg_slots, int32_t *grids);
 void launch_vardct_batch(const K2Frame *frames_dev, int32_t nframes, int32_t *tile_prefix_dev, int32_t *totals_dev, const int32_t *grids, float *large_scratch, hipStream_t stream, hipStream_t *side, int nside, hipEvent_t fork, hipEvent_t *side_done, int32_t shift = 0);
-void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false, int32_t shift = 0);
+// The pixel stage of one frame. Where its samples go (K2Target): `out` says as what -- RGBA8: u8x4 pixels; RGBA16: the 16-bit output
+// (J40_U16X4, 8 bytes a pixel; idct_dev.h xyb_to_rgba16); XYB: left in XYB for the restoration filters and LF frames
+// (device/restore_kernels.h, restore_dev.h), three float planes of `stride` bytes per row, one behind the other; YCC: a subsampled
+// YCbCr frame (DevFrame::ycc_shifts; it holds DCT8 blocks alone), three float planes one behind the other, each of the padded grid's
+// size at its channel's resolution (ycbcr_dev.h: ycc_plane_dims), `stride` unused -- and `shift` is the scale shift (1, 2: the kernels
+// write the 1:2 / 1:4 image, scale_dev.h; `base` and `stride` are then the small image's; the pixel forms only).
+enum class OutMode { RGBA8, XYB, RGBA16, YCC };
+struct K2Target { void *base; size_t stride; OutMode out; int32_t shift; };
+void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, const K2Target &to, hipStream_t stream);
 
-// the restoration filters (device/restore_kernels.h, restore_dev.h): the pixel kernels with the samples left in XYB (three float planes of
-// `stride` bytes per row, one behind the other), the reciprocal-sigma plane, Gaborish + the edge-preserving filter's steps between
-// `xyb` and `tmp` (returns where the result lies), the colour tail on planes
-void launch_vardct_frame_xyb(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, float *xyb, size_t stride, hipStream_t stream);
-// a subsampled YCbCr frame (DevFrame::ycc_shifts): its DCT8 blocks into three float planes one behind the other, each of the padded
-// grid's size at its channel's resolution (ycbcr_dev.h: ycc_plane_dims)
-void launch_vardct_frame_ycc(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *planes, hipStream_t stream);
+// the restoration filters (device/restore_kernels.h, restore_dev.h): the reciprocal-sigma plane, Gaborish + the edge-preserving
+// filter's steps between `xyb` and `tmp` (returns where the result lies), the colour tail on planes
 void launch_epf_sigma(const DevPlan &plan, int32_t num_lf_groups, const int16_t *sharpness, const RestoreParams &p, float *sigma, uint32_t *sharp_or, hipStream_t stream);
 void launch_epf_sigma_cells(const int16_t *sharpness, const float *hfmul_inv, const RestoreParams &p, float *sigma, uint32_t *sharp_or, hipStream_t stream);
 float *launch_restoration(float *xyb, float *tmp, size_t pitch, const RestoreParams &p, bool gab, int32_t epf_iters, const float *sigma, hipStream_t stream);

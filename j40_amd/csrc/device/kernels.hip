@@ -15,6 +15,7 @@
 #include <type_traits>
 #include <cstring>
 #include <cstdlib>
+#include <cassert>
 #include "hf_dev.h"
 #include "hf_lanes_dev.h"
 #include "idct_dev.h"
@@ -516,7 +517,7 @@ __device__ __forceinline__ void stage_event_prefix(uint32_t mine, uint32_t *pref
 // two above, by hand. M0 is not used by anything else in these kernels.
 #ifndef J40_K2_AHEAD
 // (global_load_lds_dword is a gfx9 instruction: the library is written for gfx950; built for anything else -- the Makefile's ARCH can be
-// overridden -- the prologue falls back to K2_PREFETCH_BLK)
+// overridden -- the prologue falls back to K2Ahead::prefetch_blk)
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__) && !defined(__gfx940__) && !defined(__gfx90a__)
 #define J40_K2_AHEAD 0
 #else
@@ -533,6 +534,7 @@ template <int NB> struct K2Ahead {
 	static_assert(NB <= 64, "K2Ahead: a tile's blocks must fit wavefront 0");
 	enum { REC_DW = 10, REC_SLOT = NB * REC_DW, BE_SLOT = NB * 4 };
 	uint32_t *rec, *be;   // LDS: [3][REC_SLOT], [2][BE_SLOT]
+	int32_t next_blk; bool next_blk_valid;   // J40_K2_AHEAD=0, lane b: the ordinal of block b of the run's NEXT tile, fetched while this one is worked on (prefetch_blk)
 	__device__ __forceinline__ static uint32_t lds_address(const uint32_t *p) { return (uint32_t) __builtin_amdgcn_readfirstlane((int32_t) (uint32_t) (uintptr_t) p); }   // (the low half of a flat LDS address is the LDS offset)
 	__device__ __forceinline__ const uint32_t *records(int32_t k) const { return rec + (k % 3) * REC_SLOT; }
 	__device__ __forceinline__ const uint32_t *entries(int32_t k) const { return be + (k & 1) * BE_SLOT; }
@@ -554,28 +556,30 @@ template <int NB> struct K2Ahead {
 			if (l < nb * 4) { const uint32_t blk = r[(l >> 2) * REC_DW + 8]; k2_copy_dword_to_lds(block_events + 4 * (size_t) blk + (uint32_t) (l & 3), base + (uint32_t) j * 256u); }
 		}
 	}
-};
-// the tile's prologue for both kernel families: `k` = the tile's number in its frame's list; true: records and entries are in LDS
-#define K2_AHEAD_PROLOGUE(NB_) \
-	const int32_t ahead_k = first / (NB_); \
-	if (BATCH && J40_K2_AHEAD) { \
-		const bool next_ok = it.tile < it.tile_end && it.tile < it.frame_end, next2_ok = it.tile + 1 < it.tile_end && it.tile + 1 < it.frame_end; \
-		if (tid < 64) { \
-			if (entered) { \
-				ahead.ask_records(list, count, ahead_k, tid); \
-				if (next_ok) ahead.ask_records(list, count, ahead_k + 1, tid); \
-				k2_copies_wait(); \
-				if (sparse) { ahead.ask_entries(plan.block_events, nb, ahead_k, tid); k2_copies_wait(); } \
-			} \
-			if (next2_ok) ahead.ask_records(list, count, ahead_k + 2, tid); \
-			if (next_ok && sparse) ahead.ask_entries(plan.block_events, min((NB_), count - first - (NB_)), ahead_k + 1, tid); \
-		} \
+	// the tile's prologue for both kernel families (batch-wide launches with J40_K2_AHEAD; nothing otherwise): the tile is number
+	// first / NB of its frame's list, `it` has been stepped past it; behind it the tile's records and entries are in LDS
+	template <bool BATCH> __device__ __forceinline__ void ask_ahead(const K2Iter &it, bool entered, const DevVarblock *list, int32_t count, int32_t first, int32_t nb, bool sparse, const uint32_t *block_events, int32_t tid) const {
+		if (!(BATCH && J40_K2_AHEAD)) return;
+		const int32_t k = first / NB;
+		const bool next_ok = it.tile < it.tile_end && it.tile < it.frame_end, next2_ok = it.tile + 1 < it.tile_end && it.tile + 1 < it.frame_end;
+		if (tid < 64) {
+			if (entered) {
+				ask_records(list, count, k, tid);
+				if (next_ok) ask_records(list, count, k + 1, tid);
+				k2_copies_wait();
+				if (sparse) { ask_entries(block_events, nb, k, tid); k2_copies_wait(); }
+			}
+			if (next2_ok) ask_records(list, count, k + 2, tid);
+			if (next_ok && sparse) ask_entries(block_events, min(NB, count - first - NB), k + 1, tid);
+		}
 	}
-
-#define K2_PREFETCH_BLK(NB_) do { \
-		next_blk_valid = BATCH && it.tile < it.tile_end && it.tile < it.frame_end; \
-		if (next_blk_valid && first + (NB_) + tid < count && tid < (NB_)) next_blk = list[first + (NB_) + tid].blk; \
-	} while (0)
+	// J40_K2_AHEAD=0: lanes 0 .. NB - 1 fetch the ordinals of the next tile's blocks (the comment above)
+	template <bool BATCH> __device__ __forceinline__ void prefetch_blk(const K2Iter &it, const DevVarblock *list, int32_t count, int32_t first, int32_t tid) {
+		if (BATCH && J40_K2_AHEAD) return;
+		next_blk_valid = BATCH && it.tile < it.tile_end && it.tile < it.frame_end;
+		if (next_blk_valid && first + NB + tid < count && tid < NB) next_blk = list[first + NB + tid].blk;
+	}
+};
 
 // J40_K2_WAVES_PER_EU: the kernels of the small shapes (up to 16 x 8) are asked to fit the registers that eight wavefronts per SIMD
 // leave -- 53-58 instead of 72-77, no spills --, which pays once the prologue's two loads travel together: pixel stage of 256 8K frames
@@ -583,53 +587,79 @@ template <int NB> struct K2Ahead {
 #ifndef J40_K2_WAVES_PER_EU
 #define J40_K2_WAVES_PER_EU 8
 #endif
-// OutMode::XYB (single-frame launches only; the restoration filters' input, restore_kernels.hip): the samples leave as they come out of
-// the inverse transforms -- three float planes of the frame, X, Y, B, `stride_bytes` per row (4 bytes a sample, like RGBA), one
-// behind the other from `rgba` -- instead of going through the colour conversion. The fused default is not touched by it.
-// The pixel kernels' output mode (a template parameter: each mode is an instantiation of its own, none pays for the others' code):
-// RGBA8 -- the colour tail to one u8x4 word per pixel, the default and the batches' form; XYB -- store_xyb above; RGBA16 -- the
-// colour tail to four u16 (xyb_to_rgba16, J40_U16X4), 8 bytes per pixel as one store (single-frame launches only)
-// YCC -- a subsampled YCbCr frame (DevFrame::ycc_shifts; the 8x8 DCT kernel only, single-frame launches): store_ycc below
-enum class OutMode { RGBA8, XYB, RGBA16, YCC };
+// The pixel kernels' output mode (OutMode, kernels.h; a template parameter: each mode is an instantiation of its own, none pays for
+// the others' code): RGBA8 -- the colour tail to one u8x4 word per pixel, the default and the batches' form; RGBA16 -- the colour tail
+// to four u16 (xyb_to_rgba16, J40_U16X4), 8 bytes per pixel as one store (single-frame launches only); XYB (single-frame launches
+// only; the restoration filters' input, restore_kernels.hip) -- the samples leave as they come out of the inverse transforms: three
+// float planes of the frame, X, Y, B, `stride_bytes` per row (4 bytes a sample, like RGBA), one behind the other from `rgba`, instead
+// of going through the colour conversion; YCC -- a subsampled YCbCr frame (DevFrame::ycc_shifts; the 8x8 DCT kernel only,
+// single-frame launches): store_ycc below
 template <OutMode OUT> constexpr int out_bytes() { return OUT == OutMode::RGBA16 ? 8 : 4; }   // bytes a pixel (a sample, XYB) takes in the output
+template <OutMode OUT> __device__ __forceinline__ typename ScaleAcc<out_bytes<OUT>()>::pixel colour_tail(float sx, float sy, float sb, const ColourConsts &cc, const J40_LDS float *thr) {
+	if constexpr (OUT == OutMode::RGBA16) return xyb_to_rgba16(sx, sy, sb, cc, thr);
+	else return xyb_to_rgba8(sx, sy, sb, cc, thr);
+}
+// How the kernel families hand their samples to the colour tail: a view whose at(c, dy, dx) is channel c's sample dy rows and dx
+// columns from the view's origin. TileView: an LDS tile, the three channels `plane` floats apart, `pitch` floats a row (k_vardct_dct's
+// tiles, and the specials' through SP8()); LargeView: where large_block left each channel, a pitch of its own each.
+struct TileView {
+	const float *t; int32_t plane, pitch;
+	__device__ __forceinline__ float at(int c, int32_t dy, int32_t dx) const { return t[c * plane + dy * pitch + dx]; }
+};
+struct LargeView {
+	const LargeSamples &S; int32_t y, x;
+	__device__ __forceinline__ float at(int c, int32_t dy, int32_t dx) const { return S.p[c][(y + dy) * S.pitch[c] + x + dx]; }
+};
+// A pixel leaves by a plain store or by a non-temporal one (written once, never read here: kept out of the L2's way, -2 % for
+// k_vardct_dct). Every site passes the kind it always had: k_vardct_dct streams everything, the specials and k_vardct_large store the
+// full-size u8x4 pixel plainly (full_size_store) and stream the rest; nobody has measured the two against each other there.
+enum class Store { PLAIN, STREAM };
+template <OutMode OUT> constexpr Store full_size_store() { return OUT == OutMode::RGBA8 ? Store::PLAIN : Store::STREAM; }
+template <Store KIND, class Pixel> __device__ __forceinline__ void store_pixel(Pixel px, uint8_t *at) {
+	if constexpr (KIND == Store::STREAM) __builtin_nontemporal_store(px, (Pixel *) at);
+	else *(Pixel *) at = px;
+}
+__device__ __forceinline__ void store_xyb(uint8_t *base, size_t off, size_t plane_bytes, float sx, float sy, float sb) {
+	*(float *) (base + off) = sx; *(float *) (base + plane_bytes + off) = sy; *(float *) (base + 2 * plane_bytes + off) = sb;
+}
+// the full-size tail of every family: the sample at the view's origin to `off` bytes into the output (plane_bytes: XYB alone)
+template <OutMode OUT, Store KIND, class View> __device__ __forceinline__ void emit_pixel(const View &v, uint8_t *base, size_t off, size_t plane_bytes, const ColourConsts &cc, const J40_LDS float *thr) {
+	static_assert(OUT != OutMode::YCC, "store_ycc places its own samples");
+	if constexpr (OUT == OutMode::XYB) store_xyb(base, off, plane_bytes, v.at(0, 0, 0), v.at(1, 0, 0), v.at(2, 0, 0));
+	else store_pixel<KIND>(colour_tail<OUT>(v.at(0, 0, 0), v.at(1, 0, 0), v.at(2, 0, 0), cc, thr), base + off);
+}
 // Reduced-size output (j40hip_frame_set_scale; scale_dev.h), the kernels' second output parameter K = the scale shift: in the colour + pack
 // phase a lane owns an OUTPUT pixel of a block. It reads its s x s samples of the three planes from the tiles, runs the colour tail of the
 // full decode on each, adds the packed pixels up (ScaleAcc) and stores their rounded mean at (py >> K, px >> K) + its place in the block:
 // the bytes k_downscale makes of the full image, without the full image. A varblock starts at a multiple of 8 pixels, so no cell
 // straddles two of them; effw / effh clip the cells of the frame's right and bottom edges. K = 0 is the code it always was.
-template <OutMode OUT> __device__ __forceinline__ typename ScaleAcc<out_bytes<OUT>()>::pixel colour_tail(float sx, float sy, float sb, const ColourConsts &cc, const J40_LDS float *thr) {
-	if constexpr (OUT == OutMode::RGBA16) return xyb_to_rgba16(sx, sy, sb, cc, thr);
-	else return xyb_to_rgba8(sx, sy, sb, cc, thr);
-}
-// the mean of the cw x ch samples at t (three planes `plane` floats apart, `pitch` floats a row), K > 0
-template <OutMode OUT, int K> __device__ __forceinline__ typename ScaleAcc<out_bytes<OUT>()>::pixel scaled_pixel(const float *t, int32_t plane, int32_t pitch, int32_t cw, int32_t ch, const ColourConsts &cc, const J40_LDS float *thr) {
+// scaled_pixel: the mean of the cw x ch samples from the view's origin, K > 0
+template <OutMode OUT, int K, class View> __device__ __forceinline__ typename ScaleAcc<out_bytes<OUT>()>::pixel scaled_pixel(const View &cell, int32_t cw, int32_t ch, const ColourConsts &cc, const J40_LDS float *thr) {
+	static_assert(K > 0 && (OUT == OutMode::RGBA8 || OUT == OutMode::RGBA16), "the float planes stay full size");
 	ScaleAcc<out_bytes<OUT>()> acc;
 	acc.clear();
 #pragma unroll 1
 	for (int32_t dy = 0; dy < ch; ++dy) {
 #pragma unroll 1
-		for (int32_t dx = 0; dx < cw; ++dx) { const float *q = t + dy * pitch + dx; acc.add(colour_tail<OUT>(q[0], q[plane], q[2 * plane], cc, thr)); }
+		for (int32_t dx = 0; dx < cw; ++dx) acc.add(colour_tail<OUT>(cell.at(0, dy, dx), cell.at(1, dy, dx), cell.at(2, dy, dx), cc, thr));
 	}
 	return acc.mean(cw * ch, K);
 }
 // K = 2, the lane split: a lane per (output pixel, cell row) -- four neighbouring lanes own one output pixel, each runs the colour tail on
-// its row of the cell (row r = lane & 3; a row below the frame's edge adds nothing), and the four partial sums meet by two exchanges
-// between neighbours. Every lane of the four gets the pixel; lane 0 of them stores it. With a lane per output pixel the 8 x 8 classes
-// had 64 output pixels a tile for 256 lanes and 16 tails a lane: the pixel stage ran 18 % slower than at full size. All four lanes of a
-// pixel must make the call (the caller's work count is a multiple of four and its early-outs depend on the pixel alone).
-template <OutMode OUT> __device__ __forceinline__ typename ScaleAcc<out_bytes<OUT>()>::pixel scaled_pixel_by_rows(const float *row, int32_t plane, int32_t cw, bool has_row, int32_t n, const ColourConsts &cc, const J40_LDS float *thr) {
+// its row of the cell (row r = lane & 3, the view's origin; a row below the frame's edge adds nothing), and the four partial sums meet
+// by two exchanges between neighbours. Every lane of the four gets the pixel; lane 0 of them stores it. With a lane per output pixel
+// the 8 x 8 classes had 64 output pixels a tile for 256 lanes and 16 tails a lane: the pixel stage ran 18 % slower than at full size.
+// All four lanes of a pixel must make the call (the caller's work count is a multiple of four and its early-outs depend on the pixel alone).
+template <OutMode OUT, class View> __device__ __forceinline__ typename ScaleAcc<out_bytes<OUT>()>::pixel scaled_pixel_by_rows(const View &row, int32_t cw, bool has_row, int32_t n, const ColourConsts &cc, const J40_LDS float *thr) {
 	ScaleAcc<out_bytes<OUT>()> acc;
 	acc.clear();
 	if (has_row) {
 #pragma unroll 1
-		for (int32_t dx = 0; dx < cw; ++dx) acc.add(colour_tail<OUT>(row[dx], row[plane + dx], row[2 * plane + dx], cc, thr));
+		for (int32_t dx = 0; dx < cw; ++dx) acc.add(colour_tail<OUT>(row.at(0, 0, dx), row.at(1, 0, dx), row.at(2, 0, dx), cc, thr));
 	}
 	acc.lo += __shfl_xor(acc.lo, 1); acc.hi += __shfl_xor(acc.hi, 1);
 	acc.lo += __shfl_xor(acc.lo, 2); acc.hi += __shfl_xor(acc.hi, 2);
 	return acc.mean(n, 2);
-}
-__device__ __forceinline__ void store_xyb(uint8_t *base, size_t off, size_t plane_bytes, float sx, float sy, float sb) {
-	*(float *) (base + off) = sx; *(float *) (base + plane_bytes + off) = sy; *(float *) (base + 2 * plane_bytes + off) = sb;
 }
 
 // OutMode::YCC: sample (x, y) of the 8x8 block at pixel (px, py) into the planes of a subsampled YCbCr frame -- three float planes one
@@ -655,6 +685,63 @@ __device__ __forceinline__ void store_ycc(uint8_t *base, const YccPlanes &p, int
 	}
 }
 
+// What a frame's tiles share, fetched when the workgroup's run of tiles enters the frame (wave-uniform: scalar registers).
+// order_idx: which of the frame's coefficient orders the kernel's transforms read (pass 0; the three channels' orders are consecutive)
+// (the plan stays a variable of its own, and the quantisation biases scalars: tiles_scatter_events indexes both by channel, and one such
+// index into a member would keep the whole struct in scratch memory, 448 bytes a lane)
+struct K2FrameEntry {
+	ColourConsts cc; const uint16_t *order;
+	float qbias0, qbias1, qbias2, qbias_num, kx_lf, kb_lf, x_qm_mul, b_qm_mul; bool sparse;
+};
+template <bool BATCH> __device__ __forceinline__ void k2_enter_frame(DevPlan &plan, K2FrameEntry &e, const K2Frame *batch, int32_t frame, int32_t order_idx) {
+	if (BATCH) { plan = batch[frame].plan; uniform_plan(plan); }
+	const DevFrame &f = *plan.frame;
+	e.cc = load_colour_consts(f); uniform_colour(e.cc);
+	e.order = uni(plan.pool_u16 + f.order_off[order_idx * 3]);
+	e.qbias0 = uni(f.quant_bias[0]); e.qbias1 = uni(f.quant_bias[1]); e.qbias2 = uni(f.quant_bias[2]); e.qbias_num = uni(f.quant_bias_num); e.kx_lf = uni(f.kx_lf); e.kb_lf = uni(f.kb_lf);
+	e.x_qm_mul = uni(f.x_qm_mul); e.b_qm_mul = uni(f.b_qm_mul); e.sparse = uni((int32_t) f.sparse_coeffs) != 0;
+}
+// A tile's staging, the same in k_vardct_dct and the specials. k2_tile_begin: what wavefront 0 asks for ahead (K2Ahead) and, in a
+// single-pass frame, the cleared tiles (`tile_floats` a block). k2_tile_records: lane b < nb takes block b's record and its entry of
+// block_events -- from the LDS ring or from list[] --, writes geom[b] and g_be[b] and returns the record (zeroes in the other lanes);
+// the blocks' event counts go to ev_prefix (stage_event_prefix: visible behind the next barrier).
+// (asking for the tile's records first and zeroing the tiles while they are on their way was measured: nineteen registers more and
+// 67.2 against 64.4 ms for the stage)
+template <int NB, bool BATCH>
+__device__ __forceinline__ void k2_tile_begin(const K2Ahead<NB> &ahead, const K2Iter &it, bool entered, bool sparse, const uint32_t *block_events, const DevVarblock *list, int32_t count, int32_t first, int32_t nb,
+		float *tiles, int32_t tile_floats, int32_t tid, int32_t nthreads) {
+	ahead.template ask_ahead<BATCH>(it, entered, list, count, first, nb, sparse, block_events, tid);
+	if (sparse) zero_tiles(tiles, nb * tile_floats, tid, nthreads);
+}
+template <int NB, bool BATCH>
+__device__ __forceinline__ DevVarblock k2_tile_records(K2Ahead<NB> &ahead, const K2Iter &it, const K2FrameEntry &e, const uint32_t *block_events, const DevVarblock *list, int32_t count, int32_t first, int32_t nb,
+		VbGeom *geom, uint32_t (*g_be)[4], uint32_t *ev_prefix, int32_t tid) {
+	DevVarblock vb = {};
+	uint32_t nevents = 0;
+	if (tid < nb) {
+		uint32_t be0 = 0, be1 = 0, be2 = 0, be3 = 0;
+		if (BATCH && J40_K2_AHEAD) {   // record and entry are in LDS (K2Ahead)
+			vb = *(const DevVarblock *) (ahead.records(first / NB) + tid * 10);
+			if (e.sparse) { const uint32_t *be = ahead.entries(first / NB) + tid * 4; be0 = be[0]; be1 = be[1]; be2 = be[2]; be3 = be[3]; }
+		} else {
+			vb = list[first + tid];
+			// (the block's entry of block_events is asked for together with its record when the tile before this one fetched its
+			// ordinal ahead -- prefetch_blk below --: one round trip to memory in front of the tile instead of two in a row)
+			const int32_t blk = ahead.next_blk_valid ? ahead.next_blk : vb.blk;
+			if (e.sparse) { const uint32_t *be = block_events + 4 * (size_t) blk; be0 = be[0]; be1 = be[1]; be2 = be[2]; be3 = be[3]; }
+		}
+		VbGeom g;
+		g.coeff_base = vb.coeff_base; g.llf_base = vb.llf_base;
+		g.mult[1] = vb.mult1; g.mult[0] = vb.mult1 * e.x_qm_mul; g.mult[2] = vb.mult1 * e.b_qm_mul;   // (varblock_geometry with the frame's factors at hand; j40.h:7078-7080)
+		g.kx_hf = vb.kx_hf; g.kb_hf = vb.kb_hf; g.px = vb.px; g.py = vb.py; g.effw = vb.effw; g.effh = vb.effh;
+		geom[tid] = g;
+		if (e.sparse) { g_be[tid][0] = be0; g_be[tid][1] = be1; g_be[tid][2] = be2; g_be[tid][3] = be3; nevents = be1 + be2 + be3; }
+	}
+	ahead.template prefetch_blk<BATCH>(it, list, count, first, tid);
+	stage_event_prefix<NB>(nevents, ev_prefix, tid);
+	return vb;
+}
+
 template <int LOGR, int LOGC, int NB, bool BATCH, OutMode OUT = OutMode::RGBA8, int K = 0>
 __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU : 1)) k_vardct_dct(DevPlan plan_arg, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, uint8_t *rgba, size_t stride_bytes,
 		const K2Frame *batch, const int32_t *tile_prefix, int32_t nframes, int32_t class_a, int32_t class_b) {
@@ -672,57 +759,26 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 	constexpr int PAR = N >= 256 ? 1 : 256 / N;   // blocks a pass of the 256 lanes covers
 	constexpr int PER = N >= 256 ? N / 256 : 1;   // pixel positions per lane
 	K2_PHASES_BEGIN;
-	// what a frame's tiles share, fetched when the workgroup's run of tiles enters the frame (wave-uniform: scalar registers)
 	DevPlan plan = plan_arg;
-	ColourConsts cc;
-	const float *dq = nullptr, *dq_scan = nullptr; const uint16_t *order = nullptr;
-	float qbias0 = 0, qbias1 = 0, qbias2 = 0, qbias_num = 0, kx_lf = 0, kb_lf = 0, x_qm_mul = 0, b_qm_mul = 0;
-	bool sparse = false;
-	int32_t next_blk = 0; bool next_blk_valid = false;   // lane b: the ordinal of block b of the run's NEXT tile, fetched while this one is worked on (J40_K2_AHEAD=0)
+	K2FrameEntry e = {};
+	const ColourConsts &cc = e.cc;
+	const float *dq = nullptr, *dq_scan = nullptr;   // (of the frame, like e)
 	__shared__ uint32_t ahead_rec[3 * K2Ahead<NB>::REC_SLOT], ahead_be[2 * K2Ahead<NB>::BE_SLOT];
-	const K2Ahead<NB> ahead = {ahead_rec, ahead_be};
+	K2Ahead<NB> ahead = {ahead_rec, ahead_be, 0, false};
 	for (K2Iter it = k2_begin<BATCH>(tile_prefix, nframes); ; ) {
 		int32_t frame, first; bool entered;
 		if (!k2_bind<BATCH>(it, batch, tile_prefix, class_a, class_b, NB, list, count, rgba, stride_bytes, frame, first, entered)) break;
 		if (entered) {
-			if (BATCH) { plan = batch[frame].plan; uniform_plan(plan); }
-			const DevFrame &f = *plan.frame;
-			cc = load_colour_consts(f); uniform_colour(cc);
-			dq = uni(plan.pool_f32 + f.dq_off[param_idx]);
-			order = uni(plan.pool_u16 + f.order_off[order_idx * 3]);   // pass 0; the three channels' orders are consecutive
-			dq_scan = uni(plan.pool_f32 + f.dq_scan_off[param_idx]);
-			qbias0 = uni(f.quant_bias[0]); qbias1 = uni(f.quant_bias[1]); qbias2 = uni(f.quant_bias[2]); qbias_num = uni(f.quant_bias_num); kx_lf = uni(f.kx_lf); kb_lf = uni(f.kb_lf);
-			x_qm_mul = uni(f.x_qm_mul); b_qm_mul = uni(f.b_qm_mul); sparse = uni((int32_t) f.sparse_coeffs) != 0;
+			k2_enter_frame<BATCH>(plan, e, batch, frame, order_idx);
+			dq = uni(plan.pool_f32 + plan.frame->dq_off[param_idx]);
+			dq_scan = uni(plan.pool_f32 + plan.frame->dq_scan_off[param_idx]);
 		}
+		const bool sparse = e.sparse;
 		const int32_t nb = min(NB, count - first);
 		const int32_t dq_size = R * C;
-		// (asking for the tile's records first and zeroing the tiles while they are on their way was measured: nineteen registers more
-		// and 67.2 against 64.4 ms for the stage)
-		K2_AHEAD_PROLOGUE(NB)
-		if (sparse) zero_tiles(lds, nb * 3 * TILE, tid, nthreads);
-		uint32_t nevents = 0;
-		if (tid < nb) {
-			DevVarblock vb;
-			uint32_t be0 = 0, be1 = 0, be2 = 0, be3 = 0;
-			if (BATCH && J40_K2_AHEAD) {   // record and entry are in LDS (K2Ahead)
-				vb = *(const DevVarblock *) (ahead.records(ahead_k) + tid * 10);
-				if (sparse) { const uint32_t *be = ahead.entries(ahead_k) + tid * 4; be0 = be[0]; be1 = be[1]; be2 = be[2]; be3 = be[3]; }
-			} else {
-				vb = list[first + tid];
-				// (the block's entry of block_events is asked for together with its record when the tile before this one fetched its
-				// ordinal ahead -- K2_PREFETCH_BLK below --: one round trip to memory in front of the tile instead of two in a row)
-				const int32_t blk = next_blk_valid ? next_blk : vb.blk;
-				if (sparse) { const uint32_t *be = plan.block_events + 4 * (size_t) blk; be0 = be[0]; be1 = be[1]; be2 = be[2]; be3 = be[3]; }
-			}
-			VbGeom g;
-			g.coeff_base = vb.coeff_base; g.llf_base = vb.llf_base;
-			g.mult[1] = vb.mult1; g.mult[0] = vb.mult1 * x_qm_mul; g.mult[2] = vb.mult1 * b_qm_mul;   // (varblock_geometry with the frame's factors at hand; j40.h:7078-7080)
-			g.kx_hf = vb.kx_hf; g.kb_hf = vb.kb_hf; g.px = vb.px; g.py = vb.py; g.effw = vb.effw; g.effh = vb.effh;
-			geom[tid] = g; g_out[tid] = (size_t) (g.py >> K) * stride_bytes + (size_t) (g.px >> K) * out_bytes<OUT>();
-			if (sparse) { g_be[tid][0] = be0; g_be[tid][1] = be1; g_be[tid][2] = be2; g_be[tid][3] = be3; nevents = be1 + be2 + be3; }
-		}
-		if (!(BATCH && J40_K2_AHEAD)) K2_PREFETCH_BLK(NB);
-		stage_event_prefix<NB>(nevents, ev_prefix, tid);
+		k2_tile_begin<NB, BATCH>(ahead, it, entered, sparse, plan.block_events, list, count, first, nb, lds, 3 * TILE, tid, nthreads);
+		const DevVarblock vb = k2_tile_records<NB, BATCH>(ahead, it, e, plan.block_events, list, count, first, nb, geom, g_be, ev_prefix, tid);
+		if (tid < nb) g_out[tid] = (size_t) (vb.py >> K) * stride_bytes + (size_t) (vb.px >> K) * out_bytes<OUT>();
 		K2_PHASE(0);
 		// ---- load: dequantise + chroma-from-luma + LLF into the LDS tiles ----
 		if (sparse) {
@@ -732,9 +788,9 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 			__syncthreads();
 			K2_PHASE(1);
 			const TileMap map = {R, C, P, 0};
-			const float qbias[3] = {qbias0, qbias1, qbias2};
-			tiles_scatter_events<NB>(plan, geom, g_be, ev_prefix, order, dq_scan, nullptr, N, map, lds, 3 * TILE, TILE, qbias, qbias_num, tid, nthreads);
-			tiles_fill_llf(plan, geom, nb, LONG, VH8, VW8, map, lds, 3 * TILE, TILE, kx_lf, kb_lf, tid, nthreads);
+			const float qbias[3] = {e.qbias0, e.qbias1, e.qbias2};
+			tiles_scatter_events<NB>(plan, geom, g_be, ev_prefix, e.order, dq_scan, nullptr, N, map, lds, 3 * TILE, TILE, qbias, e.qbias_num, tid, nthreads);
+			tiles_fill_llf(plan, geom, nb, LONG, VH8, VW8, map, lds, 3 * TILE, TILE, e.kx_lf, e.kb_lf, tid, nthreads);
 		} else {
 			// multi-pass frames: dense planes in canonical order, coalesced over the canonical index
 			__syncthreads();
@@ -777,26 +833,24 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 		K2_PHASE(4);
 		// ---- colour + pack: a lane owns pixel position (y, x) for every block of the workgroup ----
 		if constexpr (K == 2) {   // ... 1:4: four lanes an output pixel, a cell row each (scaled_pixel_by_rows)
-			static_assert(OUT != OutMode::XYB, "the XYB planes stay full size");
 			constexpr int OC = C >> 2, ON = N >> 4;
 			for (int32_t w = tid; w < nb * ON * 4; w += nthreads) {   // (nthreads and the count are multiples of four: a pixel's lanes stay together)
 				const int32_t r = w & 3, q = w >> 2, b = q / ON, o = q % ON, oy = o / OC, ox = o % OC;
 				const VbGeom &g = geom[b];
 				const int32_t cw = scale_span(ox, g.effw, 2), ch = scale_span(oy, g.effh, 2);
 				if (cw <= 0 || ch <= 0) continue;
-				const auto px = scaled_pixel_by_rows<OUT>(lds + (size_t) b * 3 * TILE + ((oy << 2) + r) * P + (ox << 2), TILE, cw, r < ch, cw * ch, cc, srgb_thr);
-				if (r == 0) __builtin_nontemporal_store(px, (decltype(px) *) (rgba + g_out[b] + (size_t) oy * stride_bytes + (size_t) ox * out_bytes<OUT>()));
+				const auto px = scaled_pixel_by_rows<OUT>(TileView{lds + (size_t) b * 3 * TILE + ((oy << 2) + r) * P + (ox << 2), TILE, P}, cw, r < ch, cw * ch, cc, srgb_thr);
+				if (r == 0) store_pixel<Store::STREAM>(px, rgba + g_out[b] + (size_t) oy * stride_bytes + (size_t) ox * out_bytes<OUT>());
 			}
 		} else if constexpr (K > 0) {   // ... 1:2: output pixel w of the tile's blocks (scaled_pixel)
-			static_assert(OUT != OutMode::XYB, "the XYB planes stay full size");
 			constexpr int OC = C >> K, ON = N >> (2 * K);
 			for (int32_t w = tid; w < nb * ON; w += nthreads) {
 				const int32_t b = w / ON, o = w % ON, oy = o / OC, ox = o % OC;
 				const VbGeom &g = geom[b];
 				const int32_t cw = scale_span(ox, g.effw, K), ch = scale_span(oy, g.effh, K);
 				if (cw <= 0 || ch <= 0) continue;
-				const auto px = scaled_pixel<OUT, K>(lds + (size_t) b * 3 * TILE + (oy << K) * P + (ox << K), TILE, P, cw, ch, cc, srgb_thr);
-				__builtin_nontemporal_store(px, (decltype(px) *) (rgba + g_out[b] + (size_t) oy * stride_bytes + (size_t) ox * out_bytes<OUT>()));
+				const auto px = scaled_pixel<OUT, K>(TileView{lds + (size_t) b * 3 * TILE + (oy << K) * P + (ox << K), TILE, P}, cw, ch, cc, srgb_thr);
+				store_pixel<Store::STREAM>(px, rgba + g_out[b] + (size_t) oy * stride_bytes + (size_t) ox * out_bytes<OUT>());
 			}
 		} else {
 		YccPlanes ycc = {};
@@ -808,18 +862,14 @@ __global__ void __launch_bounds__(256, (LOGR + LOGC <= 7 ? J40_K2_WAVES_PER_EU :
 			const uint32_t in_block = (uint32_t) y * (uint32_t) stride_bytes + (uint32_t) x * (uint32_t) out_bytes<OUT>();   // a block spans < 4 GB of output
 			for (int32_t b = N >= 256 ? 0 : tid / N; b < nb; b += PAR) {
 				const VbGeom &g = geom[b];
+				const TileView t = {lds + (size_t) b * 3 * TILE + y * P + x, TILE, P};
 				if constexpr (OUT == OutMode::YCC) {   // (the whole block: the planes reach the padded grid)
-					const float *t = lds + (size_t) b * 3 * TILE + y * P + x;
-					const float s3[3] = {t[0], t[TILE], t[2 * TILE]};
+					const float s3[3] = {t.at(0, 0, 0), t.at(1, 0, 0), t.at(2, 0, 0)};
 					store_ycc(rgba, ycc, g.px, g.py, y, x, s3);
-					continue;
+				} else {
+					if (y >= g.effh || x >= g.effw) continue;
+					emit_pixel<OUT, Store::STREAM>(t, rgba, g_out[b] + in_block, OUT == OutMode::XYB ? stride_bytes * (size_t) plan.frame->height : 0, cc, srgb_thr);
 				}
-				if (y >= g.effh || x >= g.effw) continue;
-				const float *t = lds + (size_t) b * 3 * TILE + y * P + x;
-				if constexpr (OUT == OutMode::XYB) { store_xyb(rgba, g_out[b] + in_block, stride_bytes * (size_t) plan.frame->height, t[0], t[TILE], t[2 * TILE]); continue; }
-				if constexpr (OUT == OutMode::RGBA16) { __builtin_nontemporal_store(xyb_to_rgba16(t[0], t[TILE], t[2 * TILE], cc, srgb_thr), (uint64_t *) (rgba + g_out[b] + in_block)); continue; }
-				const uint32_t px = xyb_to_rgba8(t[0], t[TILE], t[2 * TILE], cc, srgb_thr);
-				__builtin_nontemporal_store(px, (uint32_t *) (rgba + g_out[b] + in_block));   // written once, never read here: keep it out of the L2's way (-2 %)
 			}
 		}
 		}   // (K == 0: the full-size tail)
@@ -877,65 +927,40 @@ __device__ __forceinline__ void vardct_special_body(DevPlan plan_arg, const DevV
 	J40_STAGE_SRGB_THRESHOLDS(f);
 	__shared__ int32_t g_param[NB], g_sel[NB];
 	__shared__ uint32_t g_be[NB][4], g_dq[NB], ev_prefix[NB + 1];
-	// what a frame's tiles share, fetched when the workgroup's run of tiles enters the frame (k_vardct_dct)
 	DevPlan plan = plan_arg;
-	ColourConsts cc;
-	const uint16_t *order = nullptr;
-	float qbias[3] = {0, 0, 0}, qbias_num = 0, kx_lf = 0, kb_lf = 0, x_qm_mul = 0, b_qm_mul = 0;
-	uint32_t dq_scan_off[5] = {0, 0, 0, 0, 0};   // of the parameter sets 1, 2, 3, 9, 10
-	bool sparse = false;
-	int32_t next_blk = 0; bool next_blk_valid = false;   // (k_vardct_dct: the next tile's block ordinals, fetched ahead)
+	K2FrameEntry e = {};
+	const ColourConsts &cc = e.cc;
+	uint32_t dq_scan_off[5] = {0, 0, 0, 0, 0};   // of the parameter sets 1, 2, 3, 9, 10 (of the frame, like e)
 	__shared__ uint32_t ahead_rec[3 * K2Ahead<NB>::REC_SLOT], ahead_be[2 * K2Ahead<NB>::BE_SLOT];
-	const K2Ahead<NB> ahead = {ahead_rec, ahead_be};
+	K2Ahead<NB> ahead = {ahead_rec, ahead_be, 0, false};
 	K2_PHASES_BEGIN;
 	for (K2Iter it = k2_begin<BATCH>(tile_prefix, nframes); ; ) {
 		int32_t frame, first; bool entered;
 		if (!k2_bind<BATCH>(it, batch, tile_prefix, class_a, class_b, NB, list, count, rgba, stride_bytes, frame, first, entered)) break;
 		if (entered) {
-			if (BATCH) { plan = batch[frame].plan; uniform_plan(plan); }
+			k2_enter_frame<BATCH>(plan, e, batch, frame, 1);   // all 8x8 specials share order 1
 			const DevFrame &fe = *plan.frame;
-			cc = load_colour_consts(fe); uniform_colour(cc);
-			order = uni(plan.pool_u16 + fe.order_off[1 * 3]);   // all 8x8 specials share order 1
-			qbias[0] = uni(fe.quant_bias[0]); qbias[1] = uni(fe.quant_bias[1]); qbias[2] = uni(fe.quant_bias[2]); qbias_num = uni(fe.quant_bias_num); kx_lf = uni(fe.kx_lf); kb_lf = uni(fe.kb_lf);
-			x_qm_mul = uni(fe.x_qm_mul); b_qm_mul = uni(fe.b_qm_mul); sparse = uni((int32_t) fe.sparse_coeffs) != 0;
 			dq_scan_off[0] = uni((uint32_t) fe.dq_scan_off[1]); dq_scan_off[1] = uni((uint32_t) fe.dq_scan_off[2]); dq_scan_off[2] = uni((uint32_t) fe.dq_scan_off[3]);
 			dq_scan_off[3] = uni((uint32_t) fe.dq_scan_off[9]); dq_scan_off[4] = uni((uint32_t) fe.dq_scan_off[10]);
 		}
 		const DevFrame &f = *plan.frame;
+		const bool sparse = e.sparse;
 		const int32_t nb = min(NB, count - first);
 		K2_PHASE(0);
-		K2_AHEAD_PROLOGUE(NB)
-		if (sparse) zero_tiles(tiles, nb * 3 * P, tid, nthreads);
+		k2_tile_begin<NB, BATCH>(ahead, it, entered, sparse, plan.block_events, list, count, first, nb, tiles, 3 * P, tid, nthreads);
 		K2_PHASE(1);
-		uint32_t nevents = 0;
+		const DevVarblock vb = k2_tile_records<NB, BATCH>(ahead, it, e, plan.block_events, list, count, first, nb, geom, g_be, ev_prefix, tid);
 		if (tid < nb) {
-			DevVarblock vb;
-			uint32_t be0 = 0, be1 = 0, be2 = 0, be3 = 0;
-			if (BATCH && J40_K2_AHEAD) {   // (k_vardct_dct)
-				vb = *(const DevVarblock *) (ahead.records(ahead_k) + tid * 10);
-				if (sparse) { const uint32_t *be = ahead.entries(ahead_k) + tid * 4; be0 = be[0]; be1 = be[1]; be2 = be[2]; be3 = be[3]; }
-			} else {
-				vb = list[first + tid];
-				const int32_t blk = next_blk_valid ? next_blk : vb.blk;
-				if (sparse) { const uint32_t *be = plan.block_events + 4 * (size_t) blk; be0 = be[0]; be1 = be[1]; be2 = be[2]; be3 = be[3]; }
-			}
-			VbGeom g;
-			g.coeff_base = vb.coeff_base; g.llf_base = vb.llf_base;
-			g.mult[1] = vb.mult1; g.mult[0] = vb.mult1 * x_qm_mul; g.mult[2] = vb.mult1 * b_qm_mul;   // (varblock_geometry; j40.h:7078-7080)
-			g.kx_hf = vb.kx_hf; g.kb_hf = vb.kb_hf; g.px = vb.px; g.py = vb.py; g.effw = vb.effw; g.effh = vb.effh;
-			geom[tid] = g;
-			if (sparse) { g_be[tid][0] = be0; g_be[tid][1] = be1; g_be[tid][2] = be2; g_be[tid][3] = be3; nevents = be1 + be2 + be3; }
 			g_sel[tid] = vb.dctsel;
 			g_param[tid] = vb.dctsel == 1 ? 1 : vb.dctsel == 2 ? 2 : vb.dctsel == 3 ? 3 : vb.dctsel <= 13 ? 9 : 10;
 			g_dq[tid] = vb.dctsel == 1 ? dq_scan_off[0] : vb.dctsel == 2 ? dq_scan_off[1] : vb.dctsel == 3 ? dq_scan_off[2] : vb.dctsel <= 13 ? dq_scan_off[3] : dq_scan_off[4];
 		}
-		if (!(BATCH && J40_K2_AHEAD)) K2_PREFETCH_BLK(NB);
-		stage_event_prefix<NB>(nevents, ev_prefix, tid);
 		if (sparse) {
 			__syncthreads();
 			const TileMap map = {8, 8, SP8_PITCH, 1};
-			tiles_scatter_events<NB>(plan, geom, g_be, ev_prefix, order, plan.pool_f32, g_dq, 64, map, tiles, 3 * P, P, qbias, qbias_num, tid, nthreads);
-			tiles_fill_llf(plan, geom, nb, 8, 1, 1, map, tiles, 3 * P, P, kx_lf, kb_lf, tid, nthreads);
+			const float qbias[3] = {e.qbias0, e.qbias1, e.qbias2};
+			tiles_scatter_events<NB>(plan, geom, g_be, ev_prefix, e.order, plan.pool_f32, g_dq, 64, map, tiles, 3 * P, P, qbias, e.qbias_num, tid, nthreads);
+			tiles_fill_llf(plan, geom, nb, 8, 1, 1, map, tiles, 3 * P, P, e.kx_lf, e.kb_lf, tid, nthreads);
 		} else {
 			__syncthreads();
 			for (int32_t w = tid; w < nb * 64; w += nthreads) {
@@ -967,8 +992,8 @@ __device__ __forceinline__ void vardct_special_body(DevPlan plan_arg, const DevV
 				const VbGeom &g = geom[b];
 				const int32_t cw = scale_span(ox, g.effw, 2), ch = scale_span(oy, g.effh, 2);
 				if (cw <= 0 || ch <= 0) continue;
-				const auto px = scaled_pixel_by_rows<OUT>(tiles + (size_t) b * 3 * P + SP8((((oy << 2) + r) << 3) + (ox << 2)), P, cw, r < ch, cw * ch, cc, srgb_thr);
-				if (r == 0) __builtin_nontemporal_store(px, (decltype(px) *) (rgba + (size_t) ((g.py >> 2) + oy) * stride_bytes + (size_t) ((g.px >> 2) + ox) * out_bytes<OUT>()));
+				const auto px = scaled_pixel_by_rows<OUT>(TileView{tiles + (size_t) b * 3 * P + SP8((((oy << 2) + r) << 3) + (ox << 2)), P, SP8_PITCH}, cw, r < ch, cw * ch, cc, srgb_thr);
+				if (r == 0) store_pixel<Store::STREAM>(px, rgba + (size_t) ((g.py >> 2) + oy) * stride_bytes + (size_t) ((g.px >> 2) + ox) * out_bytes<OUT>());
 			}
 		} else if constexpr (K > 0) {   // 1:2: a lane an output pixel (k_vardct_dct); the cell's samples are SP8_PITCH apart down a column
 			constexpr int OC = 8 >> K, ON = 64 >> (2 * K);
@@ -977,19 +1002,16 @@ __device__ __forceinline__ void vardct_special_body(DevPlan plan_arg, const DevV
 				const VbGeom &g = geom[b];
 				const int32_t cw = scale_span(ox, g.effw, K), ch = scale_span(oy, g.effh, K);
 				if (cw <= 0 || ch <= 0) continue;
-				const auto px = scaled_pixel<OUT, K>(tiles + (size_t) b * 3 * P + SP8(((oy << K) << 3) + (ox << K)), P, SP8_PITCH, cw, ch, cc, srgb_thr);
-				__builtin_nontemporal_store(px, (decltype(px) *) (rgba + (size_t) ((g.py >> K) + oy) * stride_bytes + (size_t) ((g.px >> K) + ox) * out_bytes<OUT>()));
+				const auto px = scaled_pixel<OUT, K>(TileView{tiles + (size_t) b * 3 * P + SP8(((oy << K) << 3) + (ox << K)), P, SP8_PITCH}, cw, ch, cc, srgb_thr);
+				store_pixel<Store::STREAM>(px, rgba + (size_t) ((g.py >> K) + oy) * stride_bytes + (size_t) ((g.px >> K) + ox) * out_bytes<OUT>());
 			}
 		} else {
 		for (int32_t w = tid; w < nb * 64; w += nthreads) {
 			const int32_t b = w >> 6, i = w & 63, y = i >> 3, x = i & 7;
 			const VbGeom &g = geom[b];
 			if (y >= g.effh || x >= g.effw) continue;
-			const float *t = tiles + (size_t) b * 3 * P + SP8(i);
-			if constexpr (OUT == OutMode::XYB) { store_xyb(rgba, (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4, stride_bytes * (size_t) f.height, t[0], t[P], t[2 * P]); continue; }
-			if constexpr (OUT == OutMode::RGBA16) { __builtin_nontemporal_store(xyb_to_rgba16(t[0], t[P], t[2 * P], cc, srgb_thr), (uint64_t *) (rgba + (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 8)); continue; }
-			const uint32_t px = xyb_to_rgba8(t[0], t[P], t[2 * P], cc, srgb_thr);
-			*(uint32_t *) (rgba + (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4) = px;
+			emit_pixel<OUT, full_size_store<OUT>()>(TileView{tiles + (size_t) b * 3 * P + SP8(i), P, SP8_PITCH}, rgba, (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * out_bytes<OUT>(),
+				OUT == OutMode::XYB ? stride_bytes * (size_t) f.height : 0, cc, srgb_thr);
 		}
 		}   // (K == 0: the full-size tail)
 		K2_PHASE(5);
@@ -1058,24 +1080,17 @@ __global__ void __launch_bounds__(J40_LARGE_THREADS) k_vardct_large(DevPlan plan
 		const LargeSamples S = large_block(ex, plan, vb, g, panels, A, B, c_half_secants);
 		if constexpr (K > 0) {   // reduced size: a lane an output pixel (k_vardct_dct), the samples where large_block left them
 			for (int32_t o = tid; o < size >> (2 * K); o += nthreads) {
-				const int32_t oy = o >> (log_columns - K), ox = o & ((C >> K) - 1), y = oy << K, x = ox << K;
+				const int32_t oy = o >> (log_columns - K), ox = o & ((C >> K) - 1);
 				const int32_t cw = scale_span(ox, g.effw, K), ch = scale_span(oy, g.effh, K);
 				if (cw <= 0 || ch <= 0) continue;
-				ScaleAcc<out_bytes<OUT>()> acc;
-				acc.clear();
-				for (int32_t dy = 0; dy < ch; ++dy) for (int32_t dx = 0; dx < cw; ++dx)
-					acc.add(colour_tail<OUT>(S.p[0][(y + dy) * S.pitch[0] + x + dx], S.p[1][(y + dy) * S.pitch[1] + x + dx], S.p[2][(y + dy) * S.pitch[2] + x + dx], cc, srgb_thr));
-				const auto px = acc.mean(cw * ch, K);
-				__builtin_nontemporal_store(px, (decltype(px) *) (rgba + (size_t) ((g.py >> K) + oy) * stride_bytes + (size_t) ((g.px >> K) + ox) * out_bytes<OUT>()));
+				const auto px = scaled_pixel<OUT, K>(LargeView{S, oy << K, ox << K}, cw, ch, cc, srgb_thr);
+				store_pixel<Store::STREAM>(px, rgba + (size_t) ((g.py >> K) + oy) * stride_bytes + (size_t) ((g.px >> K) + ox) * out_bytes<OUT>());
 			}
 		} else {
 		for (int32_t i = tid; i < size; i += nthreads) {
 			const int32_t y = i >> log_columns, x = i & (C - 1);
 			if (y >= g.effh || x >= g.effw) continue;
-			if constexpr (OUT == OutMode::XYB) { store_xyb(rgba, (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4, stride_bytes * (size_t) f.height, S.p[0][y * S.pitch[0] + x], S.p[1][y * S.pitch[1] + x], S.p[2][y * S.pitch[2] + x]); continue; }
-			if constexpr (OUT == OutMode::RGBA16) { __builtin_nontemporal_store(xyb_to_rgba16(S.p[0][y * S.pitch[0] + x], S.p[1][y * S.pitch[1] + x], S.p[2][y * S.pitch[2] + x], cc, srgb_thr), (uint64_t *) (rgba + (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 8)); continue; }
-			const uint32_t px = xyb_to_rgba8(S.p[0][y * S.pitch[0] + x], S.p[1][y * S.pitch[1] + x], S.p[2][y * S.pitch[2] + x], cc, srgb_thr);
-			*(uint32_t *) (rgba + (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * 4) = px;
+			emit_pixel<OUT, full_size_store<OUT>()>(LargeView{S, y, x}, rgba, (size_t) (g.py + y) * stride_bytes + (size_t) (g.px + x) * out_bytes<OUT>(), OUT == OutMode::XYB ? stride_bytes * (size_t) f.height : 0, cc, srgb_thr);
 		}
 		}   // (K == 0: the full-size tail)
 		if (!BATCH) break;
@@ -1165,137 +1180,103 @@ void launch_hf_entropy(const DevPlan &plan, const HfLaunchInfo &info, int32_t fi
 	}
 }
 
-// `batch` = nullptr: one frame, everything in the kernel arguments. Otherwise a persistent launch over the tiles of one class of
-// `nframes` frames (k2_bind): `grid` workgroups, tile_prefix = this launch's row of the table k_k2_tiles built; plan / list /
-// count / rgba / stride are then ignored, `large_scratch` holds 6 * 65536 floats per workgroup of the launch.
-struct K2Launch { const K2Frame *batch; const int32_t *tile_prefix; int32_t nframes, class_a, class_b, grid; OutMode out; int32_t shift; };   // out: XYB / RGBA16 for single-frame launches only; shift: the scale shift (RGBA8 / RGBA16)
+// `batch` = nullptr: one frame, everything in the kernel arguments (tile_prefix null, nframes 1, the classes and grid 0). Otherwise a
+// persistent launch over the tiles of one class of `nframes` frames (k2_bind): `grid` workgroups, tile_prefix = this launch's row of
+// the table k_k2_tiles built; plan / list / count and the target's base and stride are then ignored, `large_scratch` holds
+// 6 * 65536 floats per workgroup of the launch.
+struct K2Launch { const K2Frame *batch; const int32_t *tile_prefix; int32_t nframes, class_a, class_b, grid; K2Target to; };
 
-// the reduced-size instantiations (K = 1, 2): single-frame launches in both formats, batch-wide launches in u8x4 (what the pipeline writes)
-template <int LOGR, int LOGC, int NB, bool BATCH, OutMode OUT, int K>
-static void launch_dct_scaled_as(const DevPlan &plan, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
-	constexpr size_t lds_bytes = (size_t) NB * 3 * (1 << LOGR) * ((1 << LOGC) + 1) * sizeof(float);
-	static bool configured = false;
-	if (!configured) { (void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, BATCH, OUT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes); configured = true; }
-	if (BATCH) hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, BATCH, OUT, K>), dim3((unsigned) bl.grid), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
-	else hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, BATCH, OUT, K>), dim3((unsigned) ((count + NB - 1) / NB)), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, nullptr, 1, 0, 0);
-}
-template <int LOGR, int LOGC, int NB>
-static void launch_dct_scaled(const DevPlan &plan, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
-#define J40_DCT_SCALED(BATCH_, OUT_) do { \
-		if (bl.shift == 1) launch_dct_scaled_as<LOGR, LOGC, NB, BATCH_, OUT_, 1>(plan, list, count, param_idx, order_idx, rgba, stride, bl, stream); \
-		else launch_dct_scaled_as<LOGR, LOGC, NB, BATCH_, OUT_, 2>(plan, list, count, param_idx, order_idx, rgba, stride, bl, stream); \
-	} while (0)
-	if (bl.batch) J40_DCT_SCALED(true, OutMode::RGBA8);
-	else if (bl.out == OutMode::RGBA16) J40_DCT_SCALED(false, OutMode::RGBA16);
-	else J40_DCT_SCALED(false, OutMode::RGBA8);
-#undef J40_DCT_SCALED
-}
-template <bool BATCH, OutMode OUT, int K>
-static void launch_large_scaled_as(const DevPlan &plan, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
-	constexpr size_t lds_bytes = 2 * (size_t) LARGE_PANEL_FLOATS * sizeof(float);
-	static bool configured = false;
-	if (!configured) { (void) hipFuncSetAttribute((const void *) k_vardct_large<BATCH, OUT, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes); configured = true; }
-	if (BATCH) hipLaunchKernelGGL((k_vardct_large<BATCH, OUT, K>), dim3((unsigned) bl.grid), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
-	else hipLaunchKernelGGL((k_vardct_large<BATCH, OUT, K>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
-}
-
-
-template <int LOGR, int LOGC, int NB>
-static void launch_dct(const DevPlan &plan, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
-	if (bl.shift > 0) { launch_dct_scaled<LOGR, LOGC, NB>(plan, list, count, param_idx, order_idx, rgba, stride, bl, stream); return; }
-	constexpr size_t lds_bytes = (size_t) NB * 3 * (1 << LOGR) * ((1 << LOGC) + 1) * sizeof(float);
-	static bool configured = false;
-	if (!configured) {
-		(void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-		(void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-		(void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, false, OutMode::XYB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-		(void) hipFuncSetAttribute((const void *) k_vardct_dct<LOGR, LOGC, NB, false, OutMode::RGBA16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-		configured = true;
+// The variants of a pixel kernel, written once: what a launch asks for at run time (batch-wide or one frame, the target's OutMode and
+// scale shift) to the kernel's template arguments (BATCH, OUT, K), handed to `launch` as a K2Variant. The legal ones -- each an
+// instantiation of every kernel shape, ten a shape -- are
+//   batch-wide    RGBA8    K = 0, 1, 2     (what the pipeline writes)
+//   one frame     RGBA8    K = 0, 1, 2
+//   one frame     RGBA16   K = 0, 1, 2
+//   one frame     XYB      K = 0           (the float planes stay full size)
+//   one frame     YCC      K = 0           WITH_YCC: k_vardct_dct<3, 3, 16> alone (a subsampled YCbCr frame holds nothing but DCT8)
+// and anything else is a mistake of the host code that asks: it stops at the assert, and launches nothing where asserts are off.
+template <bool BATCH_, OutMode OUT_, int K_> struct K2Variant { static constexpr bool BATCH = BATCH_; static constexpr OutMode OUT = OUT_; static constexpr int K = K_; };
+template <bool BATCH, OutMode OUT, class Launch> static bool k2_dispatch_shift(int32_t shift, Launch &launch) {
+	switch (shift) {
+	case 0: launch(K2Variant<BATCH, OUT, 0>()); return true;
+	case 1: launch(K2Variant<BATCH, OUT, 1>()); return true;
+	case 2: launch(K2Variant<BATCH, OUT, 2>()); return true;
+	default: return false;
 	}
-	const int32_t blocks = (count + NB - 1) / NB;
-	if (!bl.batch && bl.out == OutMode::XYB) hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, false, OutMode::XYB>), dim3((unsigned) blocks), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, nullptr, 1, 0, 0);
-	else if (!bl.batch && bl.out == OutMode::RGBA16) hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, false, OutMode::RGBA16>), dim3((unsigned) blocks), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, nullptr, 1, 0, 0);
-	else if (bl.batch) hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, true>), dim3((unsigned) bl.grid), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
-	else hipLaunchKernelGGL((k_vardct_dct<LOGR, LOGC, NB, false>), dim3((unsigned) blocks), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, rgba, stride, bl.batch, nullptr, 1, 0, 0);
 }
+template <bool WITH_YCC, class Launch> static void k2_dispatch(const K2Launch &bl, Launch launch) {
+	bool legal = false;
+	if (bl.batch) legal = bl.to.out == OutMode::RGBA8 && k2_dispatch_shift<true, OutMode::RGBA8>(bl.to.shift, launch);
+	else switch (bl.to.out) {
+	case OutMode::RGBA8: legal = k2_dispatch_shift<false, OutMode::RGBA8>(bl.to.shift, launch); break;
+	case OutMode::RGBA16: legal = k2_dispatch_shift<false, OutMode::RGBA16>(bl.to.shift, launch); break;
+	case OutMode::XYB: if (bl.to.shift == 0) { launch(K2Variant<false, OutMode::XYB, 0>()); legal = true; } break;
+	case OutMode::YCC: if constexpr (WITH_YCC) if (bl.to.shift == 0) { launch(K2Variant<false, OutMode::YCC, 0>()); legal = true; } break;
+	}
+	assert(legal && "pixel kernels: no such variant (K2Launch)");
+	(void) legal;
+}
+
+// The launch helpers, one a kernel family: each picks its instantiation through k2_dispatch. Dynamic LDS is allowed for here, once
+// per instantiation (the static's initialisation), for every instantiation that has any; K2_TAIL_ARGS: the arguments all end with.
+template <auto KERNEL> static void k2_allow_lds(size_t bytes) {
+	static const hipError_t allowed = hipFuncSetAttribute((const void *) KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
+	(void) allowed;
+}
+static dim3 k2_grid(const K2Launch &bl, int32_t count, int32_t per_wg) { return dim3((unsigned) (bl.batch ? bl.grid : (count + per_wg - 1) / per_wg)); }
+#define K2_TAIL_ARGS (uint8_t *) bl.to.base, bl.to.stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b
+template <int LOGR, int LOGC, int NB>
+static void launch_dct(const DevPlan &plan, const DevVarblock *list, int32_t count, int32_t param_idx, int32_t order_idx, const K2Launch &bl, hipStream_t stream) {
+	constexpr size_t lds_bytes = (size_t) NB * 3 * (1 << LOGR) * ((1 << LOGC) + 1) * sizeof(float);
+	k2_dispatch<LOGR == 3 && LOGC == 3>(bl, [&](auto v) {
+		using V = decltype(v);
+		constexpr auto kernel = k_vardct_dct<LOGR, LOGC, NB, V::BATCH, V::OUT, V::K>;
+		k2_allow_lds<kernel>(lds_bytes);
+		hipLaunchKernelGGL(kernel, k2_grid(bl, count, NB), dim3(256), lds_bytes, stream, plan, list, count, param_idx, order_idx, K2_TAIL_ARGS);
+	});
+}
+// SET: vardct_special_body's (1: k_vardct_special_123, 2: _halves, 3: _afv); static LDS alone
+template <int SET>
+static void launch_special(const DevPlan &plan, const DevVarblock *list, int32_t count, const K2Launch &bl, hipStream_t stream) {
+	constexpr int NB = J40_K2_SPECIAL_NB;
+	k2_dispatch<false>(bl, [&](auto v) {
+		using V = decltype(v);
+		constexpr auto kernel = SET == 1 ? k_vardct_special_123<NB, V::BATCH, V::OUT, V::K> : SET == 2 ? k_vardct_special_halves<NB, V::BATCH, V::OUT, V::K> : k_vardct_special_afv<NB, V::BATCH, V::OUT, V::K>;
+		hipLaunchKernelGGL(kernel, k2_grid(bl, count, NB), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, K2_TAIL_ARGS);
+	});
+}
+static void launch_large(const DevPlan &plan, const DevVarblock *list, int32_t count, float *large_scratch, const K2Launch &bl, hipStream_t stream) {
+	constexpr size_t lds_bytes = 2 * (size_t) LARGE_PANEL_FLOATS * sizeof(float);
+	k2_dispatch<false>(bl, [&](auto v) {
+		using V = decltype(v);
+		constexpr auto kernel = k_vardct_large<V::BATCH, V::OUT, V::K>;
+		k2_allow_lds<kernel>(lds_bytes);
+		hipLaunchKernelGGL(kernel, k2_grid(bl, count, 1), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, K2_TAIL_ARGS);
+	});
+}
+#undef K2_TAIL_ARGS
 
 // list = varblocks of one DctSelect value (of a run of values for the 8x8 specials and for the 128/256-sized transforms)
-static void launch_vardct_class_impl(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, const K2Launch &bl, hipStream_t stream) {
+static void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, const K2Launch &bl, hipStream_t stream) {
 	if (count <= 0 && !bl.batch) return;
 	switch (dctsel) {
-	case 0: launch_dct<3, 3, 16>(plan, list, count, 0, 0, rgba, stride, bl, stream); break;
-	case 4: launch_dct<4, 4, 8>(plan, list, count, 4, 2, rgba, stride, bl, stream); break;
-	case 5: launch_dct<5, 5, 2>(plan, list, count, 5, 3, rgba, stride, bl, stream); break;
-	case 6: launch_dct<4, 3, 8>(plan, list, count, 6, 4, rgba, stride, bl, stream); break;
-	case 7: launch_dct<3, 4, 8>(plan, list, count, 6, 4, rgba, stride, bl, stream); break;
-	case 8: launch_dct<5, 3, 4>(plan, list, count, 7, 5, rgba, stride, bl, stream); break;
-	case 9: launch_dct<3, 5, 4>(plan, list, count, 7, 5, rgba, stride, bl, stream); break;
-	case 10: launch_dct<5, 4, 4>(plan, list, count, 8, 6, rgba, stride, bl, stream); break;
-	case 11: launch_dct<4, 5, 4>(plan, list, count, 8, 6, rgba, stride, bl, stream); break;
-	case 18: launch_dct<6, 6, 1>(plan, list, count, 11, 7, rgba, stride, bl, stream); break;
-	case 19: launch_dct<6, 5, 1>(plan, list, count, 12, 8, rgba, stride, bl, stream); break;
-	case 20: launch_dct<5, 6, 1>(plan, list, count, 12, 8, rgba, stride, bl, stream); break;
-#define J40_SPECIAL_SCALED(KERNEL_, BATCH_, OUT_, K_) do { \
-		if (BATCH_) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, BATCH_, OUT_, K_>), dim3((unsigned) bl.grid), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b); \
-		else hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, BATCH_, OUT_, K_>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
-	} while (0)
-#define J40_LAUNCH_SPECIAL(KERNEL_) do { \
-		if (bl.shift > 0) { \
-			if (bl.batch) { if (bl.shift == 1) J40_SPECIAL_SCALED(KERNEL_, true, OutMode::RGBA8, 1); else J40_SPECIAL_SCALED(KERNEL_, true, OutMode::RGBA8, 2); } \
-			else if (bl.out == OutMode::RGBA16) { if (bl.shift == 1) J40_SPECIAL_SCALED(KERNEL_, false, OutMode::RGBA16, 1); else J40_SPECIAL_SCALED(KERNEL_, false, OutMode::RGBA16, 2); } \
-			else { if (bl.shift == 1) J40_SPECIAL_SCALED(KERNEL_, false, OutMode::RGBA8, 1); else J40_SPECIAL_SCALED(KERNEL_, false, OutMode::RGBA8, 2); } \
-			break; \
-		} \
-		if (!bl.batch && bl.out == OutMode::XYB) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, false, OutMode::XYB>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
-		else if (!bl.batch && bl.out == OutMode::RGBA16) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, false, OutMode::RGBA16>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
-		else if (bl.batch) hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, true>), dim3((unsigned) bl.grid), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b); \
-		else hipLaunchKernelGGL((KERNEL_<J40_K2_SPECIAL_NB, false>), dim3((unsigned) ((count + J40_K2_SPECIAL_NB - 1) / J40_K2_SPECIAL_NB)), dim3(J40_K2_SPECIAL_THREADS), 0, stream, plan, list, count, rgba, stride, bl.batch, nullptr, 1, 0, 0); \
-	} while (0)
-	case 1: case 2: case 3: J40_LAUNCH_SPECIAL(k_vardct_special_123); break;
-	case 12: case 13: J40_LAUNCH_SPECIAL(k_vardct_special_halves); break;
-	case 14: case 15: case 16: case 17: J40_LAUNCH_SPECIAL(k_vardct_special_afv); break;
-#undef J40_LAUNCH_SPECIAL
-#undef J40_SPECIAL_SCALED
-	default:
-		if (bl.shift > 0) {
-			if (bl.batch) { if (bl.shift == 1) launch_large_scaled_as<true, OutMode::RGBA8, 1>(plan, list, count, large_scratch, rgba, stride, bl, stream); else launch_large_scaled_as<true, OutMode::RGBA8, 2>(plan, list, count, large_scratch, rgba, stride, bl, stream); }
-			else if (bl.out == OutMode::RGBA16) { if (bl.shift == 1) launch_large_scaled_as<false, OutMode::RGBA16, 1>(plan, list, count, large_scratch, rgba, stride, bl, stream); else launch_large_scaled_as<false, OutMode::RGBA16, 2>(plan, list, count, large_scratch, rgba, stride, bl, stream); }
-			else { if (bl.shift == 1) launch_large_scaled_as<false, OutMode::RGBA8, 1>(plan, list, count, large_scratch, rgba, stride, bl, stream); else launch_large_scaled_as<false, OutMode::RGBA8, 2>(plan, list, count, large_scratch, rgba, stride, bl, stream); }
-			break;
-		}
-		{
-			constexpr size_t lds_bytes = 2 * (size_t) LARGE_PANEL_FLOATS * sizeof(float);
-			static bool configured = false;
-			if (!configured) {
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, OutMode::XYB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-				(void) hipFuncSetAttribute((const void *) k_vardct_large<false, OutMode::RGBA16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes);
-				configured = true;
-			}
-			if (bl.batch) {
-				hipLaunchKernelGGL((k_vardct_large<true>), dim3((unsigned) bl.grid), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, bl.tile_prefix, bl.nframes, bl.class_a, bl.class_b);
-			} else if (bl.out == OutMode::XYB) {
-				hipLaunchKernelGGL((k_vardct_large<false, OutMode::XYB>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
-			} else if (bl.out == OutMode::RGBA16) {
-				hipLaunchKernelGGL((k_vardct_large<false, OutMode::RGBA16>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
-			} else {
-				hipLaunchKernelGGL((k_vardct_large<false>), dim3((unsigned) count), dim3(J40_LARGE_THREADS), lds_bytes, stream, plan, list, count, large_scratch, rgba, stride, bl.batch, nullptr, 1, 0, 0);
-			}
-		}
-		break;
+	case 0: launch_dct<3, 3, 16>(plan, list, count, 0, 0, bl, stream); break;
+	case 4: launch_dct<4, 4, 8>(plan, list, count, 4, 2, bl, stream); break;
+	case 5: launch_dct<5, 5, 2>(plan, list, count, 5, 3, bl, stream); break;
+	case 6: launch_dct<4, 3, 8>(plan, list, count, 6, 4, bl, stream); break;
+	case 7: launch_dct<3, 4, 8>(plan, list, count, 6, 4, bl, stream); break;
+	case 8: launch_dct<5, 3, 4>(plan, list, count, 7, 5, bl, stream); break;
+	case 9: launch_dct<3, 5, 4>(plan, list, count, 7, 5, bl, stream); break;
+	case 10: launch_dct<5, 4, 4>(plan, list, count, 8, 6, bl, stream); break;
+	case 11: launch_dct<4, 5, 4>(plan, list, count, 8, 6, bl, stream); break;
+	case 18: launch_dct<6, 6, 1>(plan, list, count, 11, 7, bl, stream); break;
+	case 19: launch_dct<6, 5, 1>(plan, list, count, 12, 8, bl, stream); break;
+	case 20: launch_dct<5, 6, 1>(plan, list, count, 12, 8, bl, stream); break;
+	case 1: case 2: case 3: launch_special<1>(plan, list, count, bl, stream); break;
+	case 12: case 13: launch_special<2>(plan, list, count, bl, stream); break;
+	case 14: case 15: case 16: case 17: launch_special<3>(plan, list, count, bl, stream); break;
+	default: launch_large(plan, list, count, large_scratch, bl, stream); break;
 	}
-}
-// the DCT8 blocks of a subsampled YCbCr frame (nothing else occurs in one: frame.cpp, ycbcr_scope) into its planes (store_ycc)
-void launch_vardct_frame_ycc(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *planes, hipStream_t stream) {
-	const int32_t count = class_start[1] - class_start[0];
-	if (count <= 0) return;
-	constexpr int NB = 16;
-	constexpr size_t lds_bytes = (size_t) NB * 3 * 8 * 9 * sizeof(float);
-	hipLaunchKernelGGL((k_vardct_dct<3, 3, NB, false, OutMode::YCC>), dim3((unsigned) ((count + NB - 1) / NB)), dim3(256), lds_bytes, stream, plan, sorted + class_start[0], count, 0, 0, (uint8_t *) planes, (size_t) 0, nullptr, nullptr, 1, 0, 0);
-}
-void launch_vardct_class(const DevPlan &plan, int32_t dctsel, const DevVarblock *list, int32_t count, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16, int32_t shift) {
-	launch_vardct_class_impl(plan, dctsel, list, count, large_scratch, rgba, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, rgba16 ? OutMode::RGBA16 : OutMode::RGBA8, shift}, stream);
 }
 
 // known-answer hook: the renderer's per-sample tail (sRGB transfer + conversion, j40.h:7213-7240 / 7925-7935)
@@ -1338,14 +1319,9 @@ static bool class_range(int d, int *a, int *b) {
 	*a = d; *b = d == 1 ? 4 : d == 12 ? 14 : d == 14 ? 18 : d + 1;
 	return true;
 }
-void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16, int32_t shift) {
+void launch_vardct_frame(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, const K2Target &to, hipStream_t stream) {
 	for (int d = 0, a, b; d < 27; ++d) if (class_range(d, &a, &b))
-		launch_vardct_class(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, rgba, stride, stream, rgba16, shift);
-}
-// the same with the samples left in XYB: three float planes of the frame from `xyb`, `stride` bytes per row (store_xyb)
-void launch_vardct_frame_xyb(const DevPlan &plan, const int32_t *class_start, const DevVarblock *sorted, float *large_scratch, float *xyb, size_t stride, hipStream_t stream) {
-	for (int d = 0, a, b; d < 27; ++d) if (class_range(d, &a, &b))
-		launch_vardct_class_impl(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, (uint8_t *) xyb, stride, K2Launch{nullptr, nullptr, 1, 0, 0, 0, OutMode::XYB, 0}, stream);
+		launch_vardct_class(plan, d, sorted + class_start[a], class_start[b] - class_start[a], large_scratch, K2Launch{nullptr, nullptr, 1, 0, 0, 0, to}, stream);
 }
 
 // ---- the same for every frame of a batch at once: one persistent launch per class ----
@@ -1415,7 +1391,7 @@ void launch_vardct_batch(const K2Frame *frames_dev, int32_t nframes, int32_t *ti
 	if (nside > 0) { (void) hipEventRecord(fork, stream); for (int k = 0; k < nside; ++k) (void) hipStreamWaitEvent(side[k], fork, 0); }
 	for (int l = 0; l < K2_NUM_BATCH_LAUNCHES; ++l) {
 		const auto &L = K2_TABLE.l[l];
-		launch_vardct_class_impl(none, L.a, nullptr, 0, large_scratch, nullptr, 0, K2Launch{frames_dev, tile_prefix_dev + (size_t) l * (size_t) (nframes + 1), nframes, L.a, L.b, grids[l], OutMode::RGBA8, shift}, nside > 0 ? side[K2_LAUNCH_STREAM[l] % nside] : stream);
+		launch_vardct_class(none, L.a, nullptr, 0, large_scratch, K2Launch{frames_dev, tile_prefix_dev + (size_t) l * (size_t) (nframes + 1), nframes, L.a, L.b, grids[l], K2Target{nullptr, 0, OutMode::RGBA8, shift}}, nside > 0 ? side[K2_LAUNCH_STREAM[l] % nside] : stream);
 	}
 	if (nside > 0) for (int k = 0; k < nside; ++k) { (void) hipEventRecord(side_done[k], side[k]); (void) hipStreamWaitEvent(stream, side_done[k], 0); }
 }

@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(256) k_xyb_to_rgba(XybPlanes in, const DevFram
 	__builtin_nontemporal_store(px, (uint32_t *) (rgba + (size_t) y * stride_bytes + (size_t) x * 4));
 }
 
-// `xyb`: three planes of width x height floats, `pitch` floats per row, one behind the other (what launch_vardct_frame_xyb wrote);
+// `xyb`: three planes of width x height floats, `pitch` floats per row, one behind the other (what launch_vardct_frame wrote for an OutMode::XYB target);
 // `tmp`: as much again. Runs Gaborish (when p.gab_w[0][0] != 0 ... `gab`), then `epf_iters` steps; returns where the result lies (xyb or tmp).
 float *launch_restoration(float *xyb, float *tmp, size_t pitch, const RestoreParams &p, bool gab, int32_t epf_iters, const float *sigma, hipStream_t stream) {
 	const size_t plane = pitch * (size_t) p.height;

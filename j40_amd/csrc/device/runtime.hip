@@ -273,7 +273,7 @@ uint32_t j40hip_rt::restore_params(const FrameHeader &fh, int mode, RestoreParam
 	return 0;
 }
 // ---- YCbCr frames (j40hip_frame_set_ycbcr; device/ycbcr_dev.h, ycbcr_kernels.hip) ----
-// k_ycbcr_tail over three full-size planes one behind the other, `pitch` floats a row (a 4:4:4 frame: what launch_vardct_frame_xyb or
+// k_ycbcr_tail over three full-size planes one behind the other, `pitch` floats a row (a 4:4:4 frame: what launch_vardct_frame, OutMode::XYB, or
 // the restoration filters left)
 static void ycbcr_tail_444(j40hip_frame *h, const float *planes, size_t pitch, uint8_t *img, size_t stride, hipStream_t s) {
 	j40hip_device_state *st = h->dev;
@@ -298,7 +298,7 @@ static uint32_t ycbcr_pixels(j40hip_frame *h, const int32_t *class_start, const 
 		const size_t pitch = ((size_t) W + 3) & ~(size_t) 3;
 		if (!st->d_ycc) st->d_ycc = st->scratch<float>(3 * pitch * (size_t) H, ok);
 		if (!ok) { st->d_ycc = nullptr; return ERR_MEM; }
-		launch_vardct_frame_xyb(st->plan, class_start, list, st->d_large_scratch, st->d_ycc, pitch * 4, s);
+		launch_vardct_frame(st->plan, class_start, list, st->d_large_scratch, K2Target{st->d_ycc, pitch * 4, OutMode::XYB, 0}, s);
 		ycbcr_tail_444(h, st->d_ycc, pitch, img, stride, s);
 		return 0;
 	}
@@ -310,7 +310,7 @@ static uint32_t ycbcr_pixels(j40hip_frame *h, const int32_t *class_start, const 
 	for (int c = 0; c < 3; ++c) total += (size_t) t.pw[c] * (size_t) t.ph[c];
 	if (!st->d_ycc) st->d_ycc = st->scratch<float>(total, ok);
 	if (!ok) { st->d_ycc = nullptr; return ERR_MEM; }
-	launch_vardct_frame_ycc(st->plan, class_start, list, st->d_ycc, s);
+	launch_vardct_frame(st->plan, class_start, list, st->d_large_scratch, K2Target{st->d_ycc, 0, OutMode::YCC, 0}, s);
 	size_t off = 0;
 	for (int c = 0; c < 3; ++c) {
 		t.plane[c] = st->d_ycc + off; t.pitch[c] = t.pw[c]; t.hshift[c] = fr.fh.hshift[c]; t.vshift[c] = fr.fh.vshift[c];
@@ -350,7 +350,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 		st->restore_err = perr;
 		if (!rgba_dev) return 0;   // (planes are wanted, not pixels -- run_vardct's xyb_out: the caller makes the unfiltered ones)
 		if (st->ycbcr) return ycbcr_pixels(h, st->class_start, st->d_vb_sorted, rgba_dev, stride_bytes, s);
-		launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, rgba_dev, stride_bytes, s, out16(h));
+		launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{rgba_dev, stride_bytes, out_mode(h), 0}, s);
 		return 0;
 	}
 	bool ok = true;
@@ -360,7 +360,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	// J40HIP_RESTORATION_TIMING: the filters' time between two events of this call's own, destroyed on every way out
 	struct Pair { hipEvent_t ev[2] = {nullptr, nullptr}; ~Pair() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); } } pair;
 	static const bool timed = env_str("J40HIP_RESTORATION_TIMING") != nullptr;
-	launch_vardct_frame_xyb(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, st->d_xyb, (size_t) W * 4, s);
+	launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{st->d_xyb, (size_t) W * 4, OutMode::XYB, 0}, s);
 	const StageMarks marks{timed && hipEventCreate(&pair.ev[0]) == hipSuccess && hipEventCreate(&pair.ev[1]) == hipSuccess ? pair.ev : nullptr, s};
 	marks.mark(0);
 	uint32_t *sharp_or = (uint32_t *) (st->d_sigma + cells);   // (the device's own OR of the sharpness values: unused, the host checked)
@@ -441,7 +441,7 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 			filtered = st->restore_ran != 0;   // (else the filters could not run, restore_err says why: the unfiltered planes)
 			if (filtered && hipMemcpyAsync(run.xyb_out, st->d_restored, sizeof(float) * 3 * plane, hipMemcpyDeviceToDevice, s) != hipSuccess) return ERR_GPU;
 		}
-		if (!filtered) launch_vardct_frame_xyb(plan, run.class_start, run.list, st->d_large_scratch, run.xyb_out, W * 4, s);
+		if (!filtered) launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, K2Target{run.xyb_out, W * 4, OutMode::XYB, 0}, s);
 	} else
 	if (rmode && (r.gab || r.epf_iters > 0)) {
 		// the restoration filters asked for and signalled: the pixel kernels leave the samples in XYB planes, Gaborish and the
@@ -449,7 +449,7 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 		if (uint32_t e = decode_restored(h, run.img, run.img_stride, rmode, s)) return e;
 	} else if (st->ycbcr) {
 		if (uint32_t e = ycbcr_pixels(h, run.class_start, run.list, run.img, run.img_stride, s)) return e;
-	} else launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, run.img, run.img_stride, s, out16(h), run.shift);
+	} else launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, K2Target{run.img, run.img_stride, out_mode(h), run.shift}, s);
 	if (run.crop_to) launch_region_crop(run.crop_from, run.img_stride, run.crop_to, run.crop_stride, run.crop_w, run.crop_h, (int32_t) pixel_bytes(h), s);
 	marks.mark(3);
 	if (uint32_t e = marks.finish(ms3)) return e;
@@ -832,10 +832,10 @@ static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host
 	plan_long.block_events = st->d_two_shadow;
 	launch_hf_entropy_fast_ordered(plan_long, st->hf, st->d_two_order, 0, k, s1);          // the long sections, on their own
 	launch_hf_entropy_fast_ordered(plan, st->hf, st->d_two_order, k, ng - k, s0);           // all the others
-	launch_vardct_frame(plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, d, stride_bytes, s0, out16(h));
+	launch_vardct_frame(plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{d, stride_bytes, out_mode(h), 0}, s0);
 	if (hipEventRecord(tp.ev[1], s0) != hipSuccess || hipStreamWaitEvent(s1, tp.ev[1], 0) != hipSuccess) return ERR_GPU;
 	launch_merge_block_events(plan, st->d_two_order, k, st->d_two_shadow, s1);
-	launch_vardct_frame(plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, d, stride_bytes, s1, out16(h));
+	launch_vardct_frame(plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{d, stride_bytes, out_mode(h), 0}, s1);
 	if (hipEventRecord(tp.ev[2], s1) != hipSuccess) return ERR_GPU;
 	if (hipGetLastError() != hipSuccess) return ERR_GPU;
 	// the image of the first pass over the link while the long sections are still being decoded: the copy the one-phase decode issues,

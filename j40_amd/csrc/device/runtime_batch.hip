@@ -172,14 +172,14 @@ static uint32_t batch_enqueue(j40hip_batch *b, void *const *rgba_dev, const size
 	if (b->side_in_use == 0) {
 		for (size_t i = 0; i < b->frames.size(); ++i) {
 			j40hip_device_state *st = b->frames[i]->dev;
-			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev[i], stride_bytes[i], s, out16(b->frames[i]), b->frames[i]->scale);
+			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{rgba_dev[i], stride_bytes[i], out_mode(b->frames[i]), b->frames[i]->scale}, s);
 		}
 	} else {
 		if (hipEventRecord(b->fork, s) != hipSuccess) return ERR_GPU;
 		for (int k = 0; k < b->side_in_use; ++k) if (hipStreamWaitEvent(b->side[(size_t) k], b->fork, 0) != hipSuccess) return ERR_GPU;
 		for (size_t i = 0; i < b->frames.size(); ++i) {
 			j40hip_device_state *st = b->frames[i]->dev;
-			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, (uint8_t *) rgba_dev[i], stride_bytes[i], b->side[i % (size_t) b->side_in_use], out16(b->frames[i]), b->frames[i]->scale);
+			launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{rgba_dev[i], stride_bytes[i], out_mode(b->frames[i]), b->frames[i]->scale}, b->side[i % (size_t) b->side_in_use]);
 		}
 		for (size_t k = 0; k < (size_t) b->side_in_use; ++k) {
 			if (hipEventRecord(b->side_done[k], b->side[k]) != hipSuccess || hipStreamWaitEvent(s, b->side_done[k], 0) != hipSuccess) return ERR_GPU;

@@ -97,7 +97,7 @@ extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out
 	const int steps = (r.gab ? 1 : 0) + (r.epf_iters >= 3 ? 3 : r.epf_iters);
 	if (steps >= 2) {   // d_xyb has been written over by the second step: once more, into whichever buffer the result does not occupy
 		float *spare = st->d_restored == st->d_xyb ? st->d_xyb_tmp : st->d_xyb;
-		launch_vardct_frame_xyb(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, spare, (size_t) fh.width * 4, nullptr);
+		launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{spare, (size_t) fh.width * 4, OutMode::XYB, 0}, nullptr);
 		if (hipStreamSynchronize(nullptr) != hipSuccess) return ERR_GPU;
 		src = spare;
 	}

@@ -257,6 +257,7 @@ namespace j40hip_rt {
 
 // the frame's output format (j40hip_frame_set_output_format): 16-bit RGBA, 8 bytes a pixel, or the default u8x4
 inline bool out16(const j40hip_frame *h) { return h->output_format == J40HIP_U16X4; }
+inline OutMode out_mode(const j40hip_frame *h) { return out16(h) ? OutMode::RGBA16 : OutMode::RGBA8; }   // (the pixel kernels' form of it: K2Target)
 inline size_t pixel_bytes(const j40hip_frame *h) { return out16(h) ? 8 : 4; }
 // a 16-bit frame's rows must hold 8 * width bytes: "rnge" before anything is launched (the u8 entry points keep their old contract)
 inline bool stride_too_small(const j40hip_frame *h, size_t stride_bytes) { return out16(h) && stride_bytes < 8 * (size_t) h->frame.fh.width; }
