@@ -34,7 +34,7 @@ struct j40hip_frame {
 	bool region_set = false;
 	int32_t region[4] = {0, 0, 0, 0};                              // x0, y0, w, h
 	int32_t region_widened = 0, region_sections = 0, region_varblocks = 0;
-	bool partial_range = false;      // j40hip_frame_set_group_range narrowed the uploaded frame to some of its groups (excludes a region)
+	bool partial_range = false;      // j40hip_frame_set_group_range narrowed the uploaded frame to some of its groups (what the setters know of the upload)
 	// reduced-size decode (j40hip_frame_set_scale): the scale shift the decode entry points write at (0: full size, 1: 1:2, 2: 1:4), and of
 	// the last decode at a shift above 0 whether it went through a full-size staging image and how large that was (j40hip_frame_scale)
 	int32_t scale = 0, scale_staged = -1;
@@ -101,19 +101,20 @@ struct j40hip_sequence {
 };
 extern "C" void j40hip_sequence_release_device(j40hip_sequence *s);   // device/runtime_seq.hip
 
+// a tri-state mode of a handle (-1: as its environment switch says, read only then; else the mode itself)
+template <typename Env> inline int mode_on(int mode, Env env) { return mode >= 0 ? mode : (int) env(); }
+
 // the alpha mode in force: kept only where asked for (or J40HIP_ALPHA=1) AND the frame is one keep mode serves (plan_build.cpp:
 // alpha_keep_scope) -- with the environment variable alone every other frame decodes opaque as before
 inline bool j40hip_alpha_kept(const j40hip_frame *h) {
 	int32_t index;
-	const bool asked = h->alpha >= 0 ? h->alpha == 1 : j40hip::alpha_env();
-	return asked && !h->from_view && j40hip::alpha_keep_scope(h->frame, &index) == 0;
+	return mode_on(h->alpha, j40hip::alpha_env) && !h->from_view && j40hip::alpha_keep_scope(h->frame, &index) == 0;
 }
 
 // YCbCr frames are served: asked for (or J40HIP_YCBCR=1) on a handle of the single-frame decode -- not one a sequence hands out, not
 // one built from a view (whose LF bundle knows nothing of channel sizes)
 inline bool j40hip_ycbcr_on(const j40hip_frame *h) {
-	const bool asked = h->ycbcr >= 0 ? h->ycbcr == 1 : j40hip::ycbcr_env();
-	return asked && !h->from_view && !h->from_sequence;
+	return mode_on(h->ycbcr, j40hip::ycbcr_env) && !h->from_view && !h->from_sequence;
 }
 
 // Modular frames of XYB images: the frames the rule applies to -- a Modular frame of a colour image with
@@ -124,8 +125,7 @@ inline bool j40hip_modular_xyb_applies(const j40hip_frame *h) {
 	return f.fh.is_modular && f.im.xyb_encoded && !f.im.grey && !f.fh.do_ycbcr && !f.im.exp_bits && f.im.bpp >= 8 && !f.lf_only && !h->from_view;
 }
 inline bool j40hip_modular_xyb_on(const j40hip_frame *h) {
-	const bool asked = h->modular_xyb >= 0 ? h->modular_xyb == 1 : j40hip::modular_xyb_env();
-	return asked && j40hip_modular_xyb_applies(h);
+	return mode_on(h->modular_xyb, j40hip::modular_xyb_env) && j40hip_modular_xyb_applies(h);
 }
 
 // A handle a sequence hands out for the main frame of a still whose LF image is a frame of its own: a regular frame with use_lf_frame
@@ -141,17 +141,7 @@ inline bool j40hip_lf_still_handle(const j40hip_frame *h) {
 // only where the mode was set on the handle itself (the environment never orients a sequence's handles)
 inline int32_t j40hip_orientation_in_force(const j40hip_frame *h) {
 	if (h->from_sequence) return h->orient == 1 && j40hip_lf_still_handle(h) ? h->frame.im.orientation : 1;
-	const bool asked = h->orient >= 0 ? h->orient == 1 : j40hip::orient_env();
-	return asked ? h->frame.im.orientation : 1;
-}
-
-// The size of the stored-order image the next decode makes, which the orientation is applied to: the region's rectangle, else the frame
-// at its scale shift (ceil(width / s) x ceil(height / s); shift 0: the frame). The one statement of it: j40hip_frame_orientation reports
-// from it and decode_oriented sizes its staging image from it.
-inline void j40hip_stored_out_size(const j40hip_frame *h, int32_t *W, int32_t *H) {
-	const int32_t s = 1 << h->scale;
-	*W = h->region_set ? h->region[2] : (h->frame.fh.width + s - 1) >> h->scale;
-	*H = h->region_set ? h->region[3] : (h->frame.fh.height + s - 1) >> h->scale;
+	return mode_on(h->orient, j40hip::orient_env) ? h->frame.im.orientation : 1;
 }
 
 // internal (a sequence's playback, device/runtime_seq.hip): the LF frame's picture the next decodes of a frame with use_lf_frame read --

@@ -5,10 +5,9 @@
 #include <algorithm>
 #include <thread>
 #include <type_traits>
-#include "capi.hpp"
+#include "decode_route.hpp"
 #include "tables.hpp"
 #include "device/region_dev.h"
-#include "device/orient_dev.h"
 
 using namespace j40hip;
 
@@ -360,13 +359,12 @@ void j40hip_frame_modular_xyb(const j40hip_frame *h, int32_t out[4]) {
 // ---- region decode (include/j40hip.h) ----
 uint32_t j40hip_frame_set_region(j40hip_frame *h, int32_t x0, int32_t y0, int32_t w, int32_t hh) {
 	if (!h) return j40hip::ERR_RNGE;
-	if (h->frame.lf_only) return E4("Ulf?");
+	if (h->frame.lf_only) return ERR_ULF;
 	const int32_t W = h->frame.fh.width, H = h->frame.fh.height;
 	const bool clear = x0 == 0 && y0 == 0 && ((w == 0 && hh == 0) || (w == W && hh == H));
 	if (!clear) {
 		if (x0 < 0 || y0 < 0 || w <= 0 || hh <= 0 || (int64_t) x0 + w > W || (int64_t) y0 + hh > H) return j40hip::ERR_RNGE;
-		if (h->partial_range) return E4("Urg?");
-		if (h->scale > 0) return E4("Usc?");   // a region and a scale exclude each other
+		if (uint32_t e = mode_refusal(h, Mode::Region)) return e;
 	}
 	h->region_set = !clear;
 	h->region[0] = clear ? 0 : x0; h->region[1] = clear ? 0 : y0; h->region[2] = clear ? 0 : w; h->region[3] = clear ? 0 : hh;
@@ -390,8 +388,8 @@ void j40hip_frame_region(const j40hip_frame *h, int32_t out[12]) {
 uint32_t j40hip_frame_set_scale(j40hip_frame *h, int32_t shift) {
 	if (!h || shift < 0 || shift > 2) return j40hip::ERR_RNGE;
 	if (shift > 0) {
-		if (h->frame.lf_only) return E4("Ulf?");
-		if (h->region_set || h->partial_range || (h->from_sequence && !j40hip_lf_still_handle(h))) return E4("Usc?");   // (the main frame of an LF-frame still: capi.hpp)
+		if (h->frame.lf_only) return ERR_ULF;
+		if (uint32_t e = mode_refusal(h, Mode::Scale)) return e;
 	}
 	if (shift != h->scale) { h->scale_staged = -1; h->scale_staging_bytes = 0; }
 	h->scale = shift;
@@ -402,16 +400,14 @@ void j40hip_frame_scale(const j40hip_frame *h, int32_t out[5]) {
 	memset(out, 0, sizeof(int32_t) * 5);
 	out[3] = -1;
 	if (!h) return;
-	const int32_t s = 1 << h->scale;
-	out[0] = h->scale; out[1] = (h->frame.fh.width + s - 1) >> h->scale; out[2] = (h->frame.fh.height + s - 1) >> h->scale;
+	out[0] = h->scale; out[1] = scaled_size(h->frame.fh.width, h->scale); out[2] = scaled_size(h->frame.fh.height, h->scale);
 	out[3] = h->scale_staged; out[4] = (int32_t) std::min<int64_t>(h->scale_staging_bytes, INT32_MAX);
 }
 
 // ---- oriented output (include/j40hip.h; device/orient_dev.h has the arithmetic) ----
 uint32_t j40hip_frame_set_orientation(j40hip_frame *h, int mode) {
 	if (!h) return j40hip::ERR_RNGE;
-	if (mode > 0 && h->from_sequence && !j40hip_lf_still_handle(h)) return E4("Uor?");   // the playback writes stored order (the main frame of an LF-frame still: capi.hpp)
-	if (mode > 0 && h->partial_range && h->frame.im.orientation != 1) return E4("Uor?");   // a partial group range writes its own rectangles of the stored image: nothing whole to turn
+	if (mode > 0) if (uint32_t e = mode_refusal(h, Mode::Orientation)) return e;
 	h->orient = mode < 0 ? -1 : mode > 0 ? 1 : 0;
 	return 0;
 }
@@ -420,11 +416,8 @@ void j40hip_frame_orientation(const j40hip_frame *h, int32_t out[6]) {
 	memset(out, 0, sizeof(int32_t) * 6);
 	out[0] = 1;
 	if (!h) return;
-	const int32_t o = j40hip_orientation_in_force(h);
-	int32_t W, H;
-	j40hip_stored_out_size(h, &W, &H);
-	out[0] = h->frame.im.orientation; out[1] = o != 1 ? 1 : 0;
-	j40hip::orient_out_size(W, H, o, &out[2], &out[3]);
+	const DecodeRoute r = resolve_route(h, nullptr);   // (sizes alone: nothing of an upload decides them)
+	out[0] = h->frame.im.orientation; out[1] = r.orientation != 1 ? 1 : 0; out[2] = r.out_w; out[3] = r.out_h;
 	out[4] = h->orient_applied; out[5] = (int32_t) std::min<int64_t>(h->orient_staging_bytes, INT32_MAX);
 }
 uint32_t j40hip_frame_orient_rect(const j40hip_frame *h, int to_stored, const int32_t in[4], int32_t out[4]) {

@@ -15,7 +15,7 @@
 #include <memory>
 #include <mutex>
 #include <vector>
-#include "../capi.hpp"
+#include "../decode_route.hpp"
 #include "../plan_front.hpp"
 #include "kernels.h"
 #include "runtime_shared.hpp"
@@ -249,7 +249,7 @@ static j40hip_aframe *aframe_prepare_body(const void *buf, size_t size, int devi
 	h.bare_codestream = h.cs == (const uint8_t *) buf && h.cs_size == size;
 	if (!parse_frame_front(h.cs, h.cs_size, &fr, &tasks, &extra_prec, &plain)) return nullptr;
 	{   // the restoration filters asked for (J40HIP_RESTORATION) and signalled by the frame: the single-frame path runs them (runtime.hip: decode_restored)
-		if (j40hip_rt::restoration_env() && (fr.fh.restoration.gab || fr.fh.restoration.epf_iters > 0)) return nullptr;
+		if (restoration_env() && signals_filters(fr.fh)) return nullptr;
 	}
 	const double tp1 = prof_now();
 	af->st = static_tables_for(fr, device);

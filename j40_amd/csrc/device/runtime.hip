@@ -16,21 +16,25 @@ bool j40hip_rt::modular_groups_independent(const j40hip_frame *h) {
 	return true;
 }
 
+// what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it
+static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->wide_used = false; h->modular_xyb_used = false; h->modular_xyb_whole = false; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
+
 // region (j40hip_frame_set_region): null, or the rectangle {x0, y0, w, h} that becomes the w x h pixels at rgba_dev -- the sections of
 // its cover only (LfGlobal's too), one launch per row of the cover's groups and pass, the frame-wide per-pixel transforms over the
 // cover's rows, and the rectangle packed with the destination moved back by its origin; every section where the groups depend on
 // each other
 // shift: the scale shift of a whole-frame decode (decode_scaled): the pack kernel writes the small image
-// A Modular frame of an XYB image with the switch in force (j40hip_frame_set_modular_xyb): k_modular_xyb_pack stands in for k_pack_planes at
-// all three places (never at a shift: decode_scaled stages such a frame). xyb_out (decode_frame_xyb, a Modular LF frame; the whole frame
-// only): no pixels -- k_modular_to_xyb leaves the three float planes there, width * height floats each.
-static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, const int32_t *region = nullptr, int32_t shift = 0, float *xyb_out = nullptr) {
+// A Modular frame of an XYB image with the switch in force (j40hip_frame_set_modular_xyb): k_modular_xyb_pack stands in for k_pack_planes
+// for whole frames and rectangles alike (never at a shift: decode_scaled stages such a frame). xyb_out (decode_frame_xyb, a Modular LF
+// frame; the whole frame only): no pixels -- k_modular_to_xyb leaves the three float planes there, width * height floats each.
+static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, const int32_t *region = nullptr, int32_t shift = 0, float *xyb_out = nullptr) {
 	j40hip_device_state *st = h->dev;
 	const DevModPlan &plan = st->mod;
 	const Frame &fr = h->frame;
 	const bool wide = st->mod_wide;   // int32 planes (the plane pointers carry the sample size themselves)
+	reset_decode_flags(h);
 	h->wide_used = wide;
-	const bool xyb = modular_xyb_on(h) && st->final_planes.size() >= 3;
+	const bool xyb = route.modular_xyb && st->final_planes.size() >= 3;
 	h->modular_xyb_used = xyb;
 	if ((xyb_out && !xyb) || (xyb && shift > 0)) return ERR_TODO;
 	RegionCover cover = {0, 0, 0, 0, 0, 0};
@@ -49,8 +53,8 @@ static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_by
 	// LfGlobal's section and the first pass together, then every further pass on its own: a pass rewrites what the one before
 	// it wrote (j40.h:7025-7033), so they must not overlap; the sections' own RCTs only matter for the last pass
 	const int32_t per_pass = st->mod_sections_per_pass, lead = st->mod_sections - per_pass * st->mod_passes;
-	// (sharded decodes, j40hip_frame_set_group_range: LfGlobal's section and this process' groups of every pass)
-	const bool ranged = per_pass > 0 && !(st->first_group == 0 && st->num_groups == (int64_t) per_pass);
+	// (sharded decodes, j40hip_frame_set_group_range: LfGlobal's section and this process' groups of every pass; only frames with a section per group take one)
+	const bool ranged = !route.every_group;
 	const int32_t g0 = ranged ? (int32_t) st->first_group : 0, gn = ranged ? (int32_t) st->num_groups : per_pass;
 	h->modular_xyb_whole = xyb && !covered && !ranged;
 	if (covered) {
@@ -81,20 +85,20 @@ static uint32_t decode_modular(j40hip_frame *h, void *rgba_dev, size_t stride_by
 	}
 	const PlanePtr alpha = st->alpha_channel >= 0 ? st->final_planes[(size_t) st->alpha_channel] : PlanePtr{nullptr, st->final_planes[0].sample_bytes};
 	const ModXybConsts xk = xyb ? modular_xyb_consts(fr) : ModXybConsts();
+	// rectangle (x0, y0, w, hh) of the frame into the image whose pixel (0, 0) is at `img`
+	auto pack_rect = [&](int32_t x0, int32_t y0, int32_t w, int32_t hh, uint8_t *img) {
+		if (xyb) launch_modular_xyb_pack_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, x0, y0, w, hh, xk, img, stride_bytes, s, out16(h));
+		else launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, x0, y0, w, hh, fr.im.bpp, img, stride_bytes, s, out16(h));
+	};
 	if (xyb_out) {
 		const size_t plane = (size_t) fr.fh.width * (size_t) fr.fh.height;
 		launch_modular_to_xyb(st->final_planes[0], st->final_planes[1], st->final_planes[2], fr.fh.width, 0, 0, fr.fh.width, fr.fh.height, xk, xyb_out, xyb_out + plane, xyb_out + 2 * plane, (size_t) fr.fh.width, s);
 	} else if (region) {   // the rectangle alone; pixel (x0, y0) of the frame is the first one at rgba_dev
-		uint8_t *moved = (uint8_t *) rgba_dev - ((size_t) region[1] * stride_bytes + (size_t) region[0] * pixel_bytes(h));
-		if (xyb) launch_modular_xyb_pack_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, region[0], region[1], region[2], region[3], xk, moved, stride_bytes, s, out16(h));
-		else launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, region[0], region[1], region[2], region[3], fr.im.bpp, moved, stride_bytes, s, out16(h));
+		pack_rect(region[0], region[1], region[2], region[3], (uint8_t *) rgba_dev - ((size_t) region[1] * stride_bytes + (size_t) region[0] * pixel_bytes(h)));
 	} else if (ranged) {   // only this process' pixels are written
 		int32_t rects[3][4];
 		const int nr = group_range_rects(g0, gn, fr.fh.width, fr.fh.height, fr.fh.group_size_shift, rects);
-		for (int k = 0; k < nr; ++k) {
-			if (xyb) launch_modular_xyb_pack_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], xk, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
-			else launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
-		}
+		for (int k = 0; k < nr; ++k) pack_rect(rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], (uint8_t *) rgba_dev);
 	} else if (xyb) launch_modular_xyb_pack(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, xk, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	else launch_pack_planes(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h), shift);
 	marks.mark(3);
@@ -167,8 +171,6 @@ static uint32_t validate_trailers(j40hip_frame *h, hipStream_t s) {
 	return ok ? 0 : ERR_GPU;
 }
 
-// The alpha mode in force (j40hip_frame_set_alpha; -1: J40HIP_ALPHA) for a frame keep mode can serve -- elsewhere the environment
-// variable leaves the decode as it was (capi.hpp: j40hip_alpha_kept).
 // keep_alpha: validate_trailers for such a frame. The same Modular decode of every section's sub-image, but into frame-wide planes
 // (build_trailer_plan's keep mode), then k_alpha_merge of the alpha channel's plane into the pixels at `rgba_dev`, which the pixel
 // kernels have written opaque on the same stream. A ranged decode takes only its groups' sections and rectangles. The plan, the
@@ -182,7 +184,7 @@ static uint32_t keep_alpha(j40hip_frame *h, void *rgba_dev, size_t stride_bytes,
 	const Frame &fr = h->frame;
 	int32_t alpha_index = -1;
 	if (uint32_t e = alpha_keep_scope(fr, &alpha_index)) return e;
-	const bool whole = st->first_group == 0 && st->num_groups == fr.fh.num_groups;
+	const bool whole = !h->partial_range;
 	std::vector<uint32_t> status;
 	if (!ak.ready || ak.first_group != st->first_group || ak.num_groups != st->num_groups) {
 		ak.ready = false;
@@ -230,8 +232,8 @@ static uint32_t keep_alpha(j40hip_frame *h, void *rgba_dev, size_t stride_bytes,
 }
 
 // the extra channels' sub-images behind a decode's coefficients: kept (the alpha channel merged into `rgba_dev`) or only validated
-static uint32_t finish_trailers(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, bool whole) {
-	if (j40hip_alpha_kept(h) && rgba_dev) {
+static uint32_t finish_trailers(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, bool whole, bool alpha_merged) {
+	if (alpha_merged && rgba_dev) {
 		bool fallback = false;
 		const uint32_t e = keep_alpha(h, rgba_dev, stride_bytes, s, &fallback);
 		if (!fallback) return e;
@@ -243,10 +245,6 @@ static uint32_t finish_trailers(j40hip_frame *h, void *rgba_dev, size_t stride_b
 // Off unless asked for: j40 parses the frame header's RestorationFilter bundle and ignores it (j40.h:5339-5366; its j40__gaborish /
 // j40__epf are never called), and the default decode matches j40. J40HIP_RESTORATION=1 (or j40hip_frame_set_restoration(f, 1)) runs the
 // filters a VarDCT frame signals; =j40 (2) runs them exactly as j40's routines stand, aliased line buffers and all (restore_dev.h).
-static int restoration_mode(const j40hip_frame *h) {
-	if (h->restoration >= 0) return h->restoration;
-	return j40hip_rt::restoration_env();
-}
 static bool surely_nonzero(float x) { return std::isfinite(x) && std::fabs(x) >= 1e-8f; }   // j40.h:625
 // the kernels' parameters from the frame header's; 0 or the reference routines' own complaints: "gab0" (j40.h:7289), "epf0" (j40.h:7384)
 uint32_t j40hip_rt::restore_params(const FrameHeader &fh, int mode, RestoreParams *p) {
@@ -378,17 +376,18 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	return 0;
 }
 
-// what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it
-static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->wide_used = false; h->modular_xyb_used = false; h->modular_xyb_whole = false; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
-
-// One VarDCT decode as decode_impl (whole frames, group ranges) and decode_region (covers) describe it to run_vardct
+// One VarDCT decode as decode_impl (whole frames, group ranges), decode_region (covers), decode_scaled and decode_frame_xyb describe it to
+// run_vardct; as it stands, the whole frame from the frame's own lists, with nothing to write to yet
 struct VardctRun {
-	int32_t first_group, num_groups;     // the groups of the entropy launch ...
-	const RegionCover *cover;            // ... or (not null) a region's cover: through the fast kernel's order list (region.d_order), else a launch per row of its groups
+	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged) {}
+	int32_t first_group = 0, num_groups; // the groups of the entropy launch ...
+	const RegionCover *cover = nullptr;  // ... or (not null) a region's cover: through the fast kernel's order list (region.d_order), else a launch per row of its groups
 	const DevVarblock *list; const int32_t *class_start;   // what the pixel kernels take
-	uint8_t *img; size_t img_stride;     // where they write
-	bool whole;                          // every group is decoded: the restoration filters may run, the extra channels' sub-images can be validated
-	const uint8_t *crop_from; uint8_t *crop_to; size_t crop_stride; int32_t crop_w, crop_h;   // crop_to not null: these pixels of img are then moved there
+	uint8_t *img = nullptr; size_t img_stride = 0;   // where they write
+	bool whole = true;                   // every group is decoded: the extra channels' sub-images can be validated
+	int restoration;                     // the route's: the mode the restoration filters run in (0: they do not; never where `whole` is false)
+	bool alpha_merged;                   // the route's
+	const uint8_t *crop_from = nullptr; uint8_t *crop_to = nullptr; size_t crop_stride = 0; int32_t crop_w = 0, crop_h = 0;   // crop_to not null: these pixels of img are then moved there
 	int32_t shift = 0;                   // the scale shift the pixel kernels write at (decode_scaled's fused route: img is the small image)
 	float *xyb_out = nullptr;            // not null (an LF frame of a sequence, decode_frame_xyb): no pixels, img is null -- the three XYB planes, width * height
 	                                     // floats each, as the inverse transforms or (where they run) the restoration filters leave them, go here
@@ -419,7 +418,6 @@ static uint32_t lf_frame_tail(j40hip_frame *h, hipStream_t s) {
 static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s, float *ms3) {
 	j40hip_device_state *st = h->dev;
 	const DevPlan &plan = st->plan;
-	const FrameHeader::Restoration &r = h->frame.fh.restoration;
 	const StageMarks marks{ms3 ? st->ev : nullptr, s};
 	reset_decode_flags(h);
 	marks.mark(0);
@@ -432,18 +430,18 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 	else if (hf_entropy_fast_path(plan, st->hf)) launch_hf_entropy_fast_ordered(plan, st->hf, st->region.d_order, 0, region_cover_groups(*run.cover), s);
 	else for (int32_t row = 0; row < run.cover->rows; ++row) launch_hf_entropy(plan, st->hf, (run.cover->gy0 + row) * run.cover->gcolumns + run.cover->gx0, run.cover->cols, s);
 	marks.mark(2);
-	const int rmode = run.whole ? restoration_mode(h) : 0;
+	const int rmode = run.restoration;
 	if (run.xyb_out) {
 		const size_t W = (size_t) h->frame.fh.width, plane = W * (size_t) h->frame.fh.height;
 		bool filtered = false;
-		if (rmode && (r.gab || r.epf_iters > 0)) {
+		if (rmode) {
 			if (uint32_t e = decode_restored(h, nullptr, 0, rmode, s)) return e;
 			filtered = st->restore_ran != 0;   // (else the filters could not run, restore_err says why: the unfiltered planes)
 			if (filtered && hipMemcpyAsync(run.xyb_out, st->d_restored, sizeof(float) * 3 * plane, hipMemcpyDeviceToDevice, s) != hipSuccess) return ERR_GPU;
 		}
 		if (!filtered) launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, K2Target{run.xyb_out, W * 4, OutMode::XYB, 0}, s);
 	} else
-	if (rmode && (r.gab || r.epf_iters > 0)) {
+	if (rmode) {
 		// the restoration filters asked for and signalled: the pixel kernels leave the samples in XYB planes, Gaborish and the
 		// edge-preserving filter run over the whole picture, the colour tail follows on the filtered planes (restore_kernels.h)
 		if (uint32_t e = decode_restored(h, run.img, run.img_stride, rmode, s)) return e;
@@ -454,66 +452,56 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 	marks.mark(3);
 	if (uint32_t e = marks.finish(ms3)) return e;
 	if (hipGetLastError() != hipSuccess) return ERR_GPU;
-	if (st->has_trailers) return finish_trailers(h, run.img, run.img_stride, s, run.whole);   // (synchronises `s`)
+	if (st->has_trailers) return finish_trailers(h, run.img, run.img_stride, s, run.whole, run.alpha_merged);   // (synchronises `s`)
 	return 0;
 }
 
-static uint32_t decode_region(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3);
-static uint32_t decode_scaled(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3);
+static uint32_t decode_region(j40hip_frame *h, const DecodeRoute &route, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3);
+static uint32_t decode_scaled(j40hip_frame *h, const DecodeRoute &route, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3);
 
-static uint32_t decode_impl(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, bool whole_frame = false) {
-	if (h && h->frame.lf_only) return ERR_ULF;
-	if (!h || !h->dev) return ERR_GPU;
-	// a YCbCr frame: uploaded with the switch on, decoded only while it stays on, and whole -- a region, a scale and a group range
-	// keep refusing such frames
-	if (h->dev->ycbcr && (!j40hip_ycbcr_on(h) || h->region_set || h->scale > 0 || whole_frame || h->dev->first_group != 0 || h->dev->num_groups != h->frame.fh.num_groups)) return ERR_TODO;
-	if (h->region_set && !whole_frame) return decode_region(h, rgba_dev, stride_bytes, s, ms3);   // (whole_frame: decode_region's own call, for a widened region)
-	if (h->scale > 0 && !whole_frame) return decode_scaled(h, rgba_dev, stride_bytes, s, ms3);    // (... and decode_scaled's, for a staged combination)
-	if (stride_too_small(h, stride_bytes)) return ERR_RNGE;
+// The stored-order decode of a route that refuses nothing (decode_oriented has looked). full_size: decode_region's and decode_scaled's
+// own call for a route with full_size_first -- the whole frame at full size, whatever shape the route has
+static uint32_t decode_impl(j40hip_frame *h, const DecodeRoute &route, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3, bool full_size = false) {
+	if (route.shape == DecodeRoute::Region && !full_size) return decode_region(h, route, rgba_dev, stride_bytes, s, ms3);
+	if (route.shape == DecodeRoute::Scaled && !full_size) return decode_scaled(h, route, rgba_dev, stride_bytes, s, ms3);
 	j40hip_device_state *st = h->dev;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
-	if (st->is_modular) return decode_modular(h, rgba_dev, stride_bytes, s, ms3);
-	// (a sharded decode: only the varblocks of this process' groups)
-	const bool whole = st->first_group == 0 && st->num_groups == h->frame.fh.num_groups;
-	const VardctRun run = {(int32_t) st->first_group, (int32_t) st->num_groups, nullptr, whole ? st->d_vb_sorted : st->d_vb_range, whole ? st->class_start : st->range_class_start,
-		(uint8_t *) rgba_dev, stride_bytes, whole, nullptr, nullptr, 0, 0, 0};
+	if (st->is_modular) return decode_modular(h, route, rgba_dev, stride_bytes, s, ms3);
+	VardctRun run(h, route);
+	run.img = (uint8_t *) rgba_dev; run.img_stride = stride_bytes;
+	if (!route.every_group) {   // a sharded decode: only this process' groups and their varblocks
+		run.first_group = (int32_t) st->first_group; run.num_groups = (int32_t) st->num_groups; run.whole = false;
+		run.list = st->d_vb_range; run.class_start = st->range_class_start;
+	}
 	return run_vardct(h, run, s, ms3);
 }
 
-// An LF frame of a sequence (runtime_seq.hip: play_frame): the whole VarDCT frame decoded to its three XYB planes at `planes` (width *
-// height floats each, one behind the other), no colour conversion, no pixels. Enqueued on `s` like j40hip_frame_decode.
+// An LF frame of a sequence (runtime_seq.hip: play_frame): the whole frame decoded to its three XYB planes at `planes` (width * height
+// floats each, one behind the other), no colour conversion, no pixels -- a VarDCT frame's as the inverse transforms or the restoration
+// filters leave them, a Modular XYB frame's integer planes through k_modular_to_xyb. Enqueued on `s` like j40hip_frame_decode.
 uint32_t j40hip_rt::decode_frame_xyb(j40hip_frame *h, float *planes, hipStream_t s) {
 	if (!h || !h->dev || !planes) return ERR_GPU;
 	j40hip_device_state *st = h->dev;
-	// (what keeps it from being three full-size XYB planes: Modular and YCbCr samples, extra channels behind the coefficients, part of a frame)
-	// a Modular LF frame (the sequence serves Modular XYB frames too): its integer planes, then k_modular_to_xyb
-	if (st->is_modular) {
-		if (!modular_xyb_on(h) || h->region_set || h->scale > 0 || h->partial_range) return ERR_TODO;
-		if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
-		return decode_modular(h, nullptr, 0, s, nullptr, nullptr, 0, planes);
-	}
-	if (h->frame.lf_only || st->is_modular || st->ycbcr || st->has_trailers || h->region_set || h->scale > 0 || h->partial_range) return ERR_TODO;
+	const DecodeRoute route = route_of(h);
+	if (route.xyb_refusal) return route.xyb_refusal;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
-	VardctRun run = {0, (int32_t) h->frame.fh.num_groups, nullptr, st->d_vb_sorted, st->class_start, nullptr, 0, true, nullptr, nullptr, 0, 0, 0};
+	if (st->is_modular) return decode_modular(h, route, nullptr, 0, s, nullptr, nullptr, 0, planes);
+	VardctRun run(h, route);
 	run.xyb_out = planes;
 	return run_vardct(h, run, s, nullptr);
 }
 
 // ---- region decode (j40hip_frame_set_region, include/j40hip.h; device/region_dev.h, region_kernels.hip) ----
-// The staging image of `bytes` bytes, kept with the frame and grown on demand (nothing is allocated on the path of a later decode, so
-// the asynchronous entry point stays asynchronous).
-static uint8_t *region_staging(j40hip_device_state *st, size_t bytes) {
-	return st->region.staging.ensure(st->device, bytes, false) ? (uint8_t *) st->region.staging.ptr : nullptr;
-}
-// An image of img_w x img_h pixels in the staging block whose pixel (off_x, *) sits within 16 bytes like the destination's rows do, so
-// that k_region_crop moves every row in 16-byte pieces; *stride: its row stride. Null: no memory.
+// An image of img_w x img_h pixels in the staging block -- kept with the frame and grown on demand, so that nothing is allocated on the path of
+// a later decode and the asynchronous entry point stays asynchronous -- whose pixel (off_x, *) sits within 16 bytes like the destination's rows
+// do, so that k_region_crop moves every row in 16-byte pieces; *stride: its row stride. Null: no memory.
 static uint8_t *region_image(j40hip_frame *h, const void *dst, size_t dst_stride, int32_t img_w, int32_t img_h, int32_t off_x, size_t *stride) {
 	const size_t pb = pixel_bytes(h), row = ((size_t) img_w * pb + 15) & ~(size_t) 15;
 	const bool alike = (uintptr_t) dst % pb == 0 && dst_stride % pb == 0;   // (else the rows stay pixel by pixel)
 	*stride = row + (alike ? dst_stride & 15 : 0);
 	const size_t lead = alike ? ((uintptr_t) dst - (size_t) off_x * pb) & 15 : 0;
-	uint8_t *base = region_staging(h->dev, lead + *stride * (size_t) img_h + 16);
-	return base ? base + lead : nullptr;
+	CacheBlock &block = h->dev->region.staging;
+	return block.ensure(h->dev->device, lead + *stride * (size_t) img_h + 16, false) ? (uint8_t *) block.ptr + lead : nullptr;
 }
 
 // the group-major index of the varblock list, once per upload: three kernels and one copy back of the segments' starts
@@ -566,26 +554,23 @@ static uint32_t region_gather(j40hip_frame *h, const RegionCover &cover, hipStre
 	return 0;
 }
 
-static uint32_t decode_region(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
+static uint32_t decode_region(j40hip_frame *h, const DecodeRoute &route, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
 	j40hip_device_state *st = h->dev;
 	const Frame &fr = h->frame;
 	const int32_t x0 = h->region[0], y0 = h->region[1], w = h->region[2], hh = h->region[3];
-	const size_t pb = pixel_bytes(h);
-	if (stride_bytes < pb * (size_t) w) return ERR_RNGE;
+	const size_t pb = route.pixel_bytes;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
-	if (st->is_modular) return decode_modular(h, rgba_dev, stride_bytes, s, ms3, h->region);
+	if (st->is_modular) return decode_modular(h, route, rgba_dev, stride_bytes, s, ms3, h->region);
 	const int32_t W = fr.fh.width, H = fr.fh.height, shift = fr.fh.group_size_shift;
 	const RegionCover cover = region_cover(x0, y0, w, hh, shift, fr.fh.gcolumns);
 	const int32_t ncover = region_cover_groups(cover);
-	const int rmode = restoration_mode(h);
-	const bool widen = (rmode && (fr.fh.restoration.gab || fr.fh.restoration.epf_iters > 0)) || (st->has_trailers && j40hip_alpha_kept(h));
-	if (widen) {
+	if (route.full_size_first) {
 		// the filters read across groups, the kept alpha is merged into full-size pixels: the whole frame as ever, into a staging image
 		size_t img_stride = 0;
 		uint8_t *img = region_image(h, rgba_dev, stride_bytes, W, H, x0, &img_stride);
 		if (!img) return ERR_MEM;
 		h->region_widened = 1; h->region_sections = st->total_sections; h->region_varblocks = (int32_t) st->vb_count;
-		if (uint32_t e = decode_impl(h, img, img_stride, s, ms3, true)) return e;
+		if (uint32_t e = decode_impl(h, route, img, img_stride, s, ms3, true)) return e;
 		launch_region_crop(img + (size_t) y0 * img_stride + (size_t) x0 * pb, img_stride, (uint8_t *) rgba_dev, stride_bytes, w, hh, (int32_t) pb, s);
 		return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 	}
@@ -601,42 +586,37 @@ static uint32_t decode_region(j40hip_frame *h, void *rgba_dev, size_t stride_byt
 	uint8_t *img = direct ? (uint8_t *) rgba_dev : region_image(h, rgba_dev, stride_bytes, cw, ch, x0 - cx0, &img_stride);
 	if (!img) return ERR_MEM;
 	h->region_widened = 0; h->region_sections = all ? st->total_sections : fr.fh.num_passes * ncover; h->region_varblocks = class_start[REGION_KEYS - 1];
-	// (drop mode, or the frame would have been widened; a partial cover does not validate the sub-images, like a group range)
-	const VardctRun run = {0, (int32_t) fr.fh.num_groups, all ? nullptr : &cover, list, class_start, img, img_stride, all,
-		direct ? nullptr : img + (size_t) (y0 - cy0) * img_stride + (size_t) (x0 - cx0) * pb, direct ? nullptr : (uint8_t *) rgba_dev, stride_bytes, w, hh};
+	// (drop mode, no filters, or the frame would have been widened; a partial cover does not validate the sub-images, like a group range)
+	VardctRun run(h, route);
+	run.cover = all ? nullptr : &cover; run.list = list; run.class_start = class_start; run.img = img; run.img_stride = img_stride; run.whole = all;
+	if (!direct) { run.crop_from = img + (size_t) (y0 - cy0) * img_stride + (size_t) (x0 - cx0) * pb; run.crop_to = (uint8_t *) rgba_dev; run.crop_stride = stride_bytes; run.crop_w = w; run.crop_h = hh; }
 	return run_vardct(h, run, s, ms3);
 }
 
 // ---- reduced-size decode (j40hip_frame_set_scale, include/j40hip.h; device/scale_dev.h, scale_kernels.hip) ----
-// The whole frame at scale shift k: ceil(width / s) x ceil(height / s) pixels at rgba_dev. Fused wherever the pixels come out of the
-// pixel kernels (VarDCT) or the pack kernel (Modular): those write the small image and nothing else. Staged where other kernels write
-// full-size pixels -- restoration filters in force on a frame that signals them (k_xyb_to_rgba), keep-alpha mode (k_alpha_merge): the
-// frame decodes as ever into a full-size image kept with the frame, and k_downscale makes the small one of it. Every section is
-// entropy-decoded either way: status and codes are the full decode's. (A region or a partial group range never gets here: the setters
-// exclude them.)
-static uint32_t decode_scaled(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
+// The whole frame at scale shift k: ceil(width / s) x ceil(height / s) pixels at rgba_dev. Fused: the pixel kernels (VarDCT) or the pack
+// kernel (Modular) write the small image and nothing else. Staged (the route's full_size_first): the frame decodes as ever into a full-size
+// image kept with the frame, and k_downscale makes the small one of it. Every section is entropy-decoded either way: status and codes
+// are the full decode's.
+static uint32_t decode_scaled(j40hip_frame *h, const DecodeRoute &route, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
 	j40hip_device_state *st = h->dev;
 	const Frame &fr = h->frame;
 	const int32_t W = fr.fh.width, H = fr.fh.height, k = h->scale;
-	const size_t pb = pixel_bytes(h);
-	if (scaled_stride_too_small(h, stride_bytes)) return ERR_RNGE;
+	const size_t pb = route.pixel_bytes;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
-	const int rmode = restoration_mode(h);
-	// (a Modular frame through the XYB colour tail: the mean is of rendered bytes, and k_modular_xyb_pack writes full-size pixels only)
-	const bool staged = st->is_modular ? modular_xyb_on(h) : ((rmode && (fr.fh.restoration.gab || fr.fh.restoration.epf_iters > 0)) || (st->has_trailers && j40hip_alpha_kept(h)));
-	if (staged) {
+	if (route.full_size_first) {
 		const size_t img_stride = ((size_t) W * pb + 15) & ~(size_t) 15, bytes = img_stride * (size_t) H;
 		if (!st->scale_staging.ensure(st->device, bytes, false)) return ERR_MEM;
 		uint8_t *img = (uint8_t *) st->scale_staging.ptr;
 		h->scale_staged = 1; h->scale_staging_bytes = (int64_t) bytes;
-		if (uint32_t e = decode_impl(h, img, img_stride, s, ms3, true)) return e;
+		if (uint32_t e = decode_impl(h, route, img, img_stride, s, ms3, true)) return e;
 		launch_downscale(img, img_stride, (uint8_t *) rgba_dev, stride_bytes, W, H, k, (int32_t) pb, s);
 		return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 	}
 	h->scale_staged = 0; h->scale_staging_bytes = 0;
-	if (st->is_modular) return decode_modular(h, rgba_dev, stride_bytes, s, ms3, nullptr, k);
-	VardctRun run = {0, (int32_t) fr.fh.num_groups, nullptr, st->d_vb_sorted, st->class_start, (uint8_t *) rgba_dev, stride_bytes, true, nullptr, nullptr, 0, 0, 0};
-	run.shift = k;
+	if (st->is_modular) return decode_modular(h, route, rgba_dev, stride_bytes, s, ms3, nullptr, k);
+	VardctRun run(h, route);
+	run.img = (uint8_t *) rgba_dev; run.img_stride = stride_bytes; run.shift = k;
 	return run_vardct(h, run, s, ms3);
 }
 
@@ -652,40 +632,29 @@ extern "C" uint32_t j40hip_kat_device_downscale(void *out_dev, size_t out_stride
 }
 
 // ---- oriented output (j40hip_frame_set_orientation, include/j40hip.h; device/orient_dev.h, orient_kernels.hip) ----
-// The head of the single-frame decode entries. With the image's orientation in force and other than 1 the decode -- whatever it is: VarDCT,
-// Modular, YCbCr, filters, kept alpha, a region, a scale, either format -- is pointed at a stored-order staging image of exactly its W x H
-// pixels, one block of the device memory cache kept with the frame, and k_orient then writes the caller's buffer on the same stream: the
-// orientation is applied last, to the pixels the handle writes with the mode off. Else nothing is staged and the path is decode_impl's.
-// the staging image of W x H pixels; null: no memory
-static uint8_t *orient_image(j40hip_frame *h, int32_t W, int32_t H, size_t *stride) {
+// The head of the single-frame decode entries: the route's refusal, then the decode. With an orientation other than 1 in force the decode
+// -- whatever it is -- is pointed at a stored-order staging image of exactly its W x H pixels, one block of the device memory cache kept
+// with the frame, and k_orient then writes the caller's buffer on the same stream: the orientation is applied last.
+static uint32_t decode_oriented(j40hip_frame *h, const DecodeRoute &route, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
+	if (h->dev && !h->frame.lf_only) { h->orient_applied = 0; h->orient_staging_bytes = 0; }
+	if (route.refusal) return route.refusal;   // before anything is launched or allocated
+	if (route.orientation == 1) return decode_impl(h, route, rgba_dev, stride_bytes, s, ms3);
 	j40hip_device_state *st = h->dev;
-	*stride = pixel_bytes(h) * (size_t) W;
-	const size_t bytes = *stride * (size_t) H;
-	if (!st->orient_staging.ensure(st->device, bytes, false)) return nullptr;
+	const int32_t W = route.stored_w, H = route.stored_h;
+	const size_t img_stride = route.pixel_bytes * (size_t) W, bytes = img_stride * (size_t) H;
+	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
+	if (!st->orient_staging.ensure(st->device, bytes, false)) return ERR_MEM;
 	h->orient_staging_bytes = (int64_t) bytes;
-	return (uint8_t *) st->orient_staging.ptr;
-}
-static uint32_t decode_oriented(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
-	if (!h || !h->dev || h->frame.lf_only) return decode_impl(h, rgba_dev, stride_bytes, s, ms3);   // (its refusals)
-	h->orient_applied = 0; h->orient_staging_bytes = 0;
-	const int32_t o = j40hip_orientation_in_force(h);
-	if (o == 1) return decode_impl(h, rgba_dev, stride_bytes, s, ms3);
-	// a partial group range writes its own rectangles and leaves the caller's other pixels alone: there is no whole stored-order image
-	// to turn, and the staging block's other pixels are whatever the block held. Refused before anything is launched.
-	if (h->partial_range) return ERR_UOR;
-	int32_t W, H, ow, oh;
-	j40hip_stored_out_size(h, &W, &H);
-	orient_out_size(W, H, o, &ow, &oh);
-	const size_t pb = pixel_bytes(h);
-	if (!rgba_dev || stride_bytes < pb * (size_t) ow) return ERR_RNGE;   // before anything is launched (any alignment of pointer and stride serves, as in stored order)
-	if (hipSetDevice(h->dev->device) != hipSuccess) return ERR_GPU;
-	size_t img_stride = 0;
-	uint8_t *img = orient_image(h, W, H, &img_stride);
-	if (!img) return ERR_MEM;
-	if (uint32_t e = decode_impl(h, img, img_stride, s, ms3)) return e;
-	launch_orient(img, img_stride, (uint8_t *) rgba_dev, stride_bytes, W, H, o, (int32_t) pb, s);
+	uint8_t *img = (uint8_t *) st->orient_staging.ptr;
+	if (uint32_t e = decode_impl(h, route, img, img_stride, s, ms3)) return e;
+	launch_orient(img, img_stride, (uint8_t *) rgba_dev, stride_bytes, W, H, route.orientation, (int32_t) route.pixel_bytes, s);   // (any alignment of pointer and stride serves, as in stored order)
 	h->orient_applied = 1;
 	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+}
+// the decode entry points' head: the route of this call, then the decode
+static uint32_t decode_entry(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
+	if (!h) return ERR_GPU;
+	return decode_oriented(h, route_of(h, rgba_dev != nullptr, stride_bytes), rgba_dev, stride_bytes, s, ms3);
 }
 
 // known-answer / measuring hook: k_orient alone
@@ -705,11 +674,11 @@ extern "C" uint32_t j40hip_kat_device_orient(void *out_dev, size_t out_stride, c
 }
 
 extern "C" uint32_t j40hip_frame_decode(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, void *stream) {
-	return guarded([&] { return decode_oriented(h, rgba_dev, stride_bytes, (hipStream_t) stream, nullptr); });
+	return guarded([&] { return decode_entry(h, rgba_dev, stride_bytes, (hipStream_t) stream, nullptr); });
 }
 
 extern "C" uint32_t j40hip_frame_decode_timed(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, void *stream, float *ms3) {
-	return guarded([&] { return decode_oriented(h, rgba_dev, stride_bytes, (hipStream_t) stream, ms3); });
+	return guarded([&] { return decode_entry(h, rgba_dev, stride_bytes, (hipStream_t) stream, ms3); });
 }
 
 // Status words reduced to a frame's verdict: the code of the first failing section in the order the reference reads them, which is the
@@ -739,7 +708,7 @@ static uint32_t j40hip_frame_status_body(j40hip_frame *h) {
 		// sub-images behind the coefficients are checked now, so that both modes report damage in them like the reference
 		st->trailers_pending = false;
 		if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
-		if (uint32_t e = finish_trailers(h, st->pending_rgba, st->pending_stride, nullptr, true)) return e;
+		if (uint32_t e = finish_trailers(h, st->pending_rgba, st->pending_stride, nullptr, true, route_of(h).alpha_merged)) return e;
 	}
 	st->status_host.assign((size_t) st->total_sections, 0);
 	if (hipMemcpy(st->status_host.data(), st->plan.status, sizeof(uint32_t) * st->status_host.size(), hipMemcpyDeviceToHost) != hipSuccess) return ERR_GPU;
@@ -780,14 +749,14 @@ void j40hip_rt::two_phase_shutdown() {
 }
 
 // decides once per upload whether the frame is decoded in two phases and with which groups on the second stream (st->two_k of st->two_order)
-static void two_phase_plan(j40hip_frame *h, size_t image_bytes) {
+static void two_phase_plan(j40hip_frame *h, size_t image_bytes, bool every_group) {
 	j40hip_device_state *st = h->dev;
 	st->two_k = 0;
 	const bool allowed = env_on("J40HIP_TWO_PHASE", true);   // (looked at per upload: tests switch it between frames)
 	const Frame &fr = h->frame;
 	const int64_t ng = fr.fh.num_groups;
 	if (!allowed || st->is_modular || st->ycbcr || !st->plan.events || !st->plan.block_events || st->has_trailers || fr.toc.single || fr.fh.num_passes != 1 || ng < 64 || image_bytes < ((size_t) 16 << 20)) return;
-	if (st->first_group != 0 || st->num_groups != ng || fr.toc.pass_groups.size() != (size_t) ng) return;
+	if (!every_group || fr.toc.pass_groups.size() != (size_t) ng) return;
 	if (!hf_entropy_fast_path(st->plan, st->hf)) return;
 	std::vector<uint32_t> order((size_t) ng);
 	for (int64_t g = 0; g < ng; ++g) order[(size_t) g] = (uint32_t) g;
@@ -808,13 +777,13 @@ static void two_phase_plan(j40hip_frame *h, size_t image_bytes) {
 
 // pixels of a whole VarDCT frame into rgba_host; d: the device image (stride_bytes per row). Returns the frame's code like decode_impl +
 // j40hip_frame_status would; *done = false: nothing was enqueued, the caller decodes the usual way.
-static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host, size_t stride_bytes, bool *done) {
+static uint32_t decode_two_phase(j40hip_frame *h, const DecodeRoute &route, uint8_t *d, uint8_t *rgba_host, size_t stride_bytes, bool *done) {
 	*done = false;
 	j40hip_device_state *st = h->dev;
 	const Frame &fr = h->frame;
 	const size_t bytes = stride_bytes * (size_t) fr.fh.height;
-	if (st->two_k < 0) two_phase_plan(h, bytes);
-	if (st->two_k <= 0 || restoration_mode(h) != 0 || st->first_group != 0 || st->num_groups != fr.fh.num_groups) return 0;   // (a group range set since: the usual way)
+	if (st->two_k < 0) two_phase_plan(h, bytes, route.every_group);
+	if (st->two_k <= 0 || route.restoration_asked || !route.every_group) return 0;   // (a restoration mode, or a group range set since the plan: the usual way)
 	TwoPhaseStream tp;
 	if (!two_phase_borrow(st->device, &tp)) return 0;
 	struct GiveBack { const TwoPhaseStream &t; ~GiveBack() { (void) hipStreamSynchronize(t.s); g_two_phase_idle.give(t); } } give_back{tp};   // (whatever way the decode ends: nothing of it is left on the stream)
@@ -854,7 +823,7 @@ static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host
 		else (void) hipGetLastError();
 	}
 	const int32_t shift = fr.fh.group_size_shift, gdim = 1 << shift;
-	const size_t pb = pixel_bytes(h);
+	const size_t pb = route.pixel_bytes;
 	if (mapped) launch_store_group_rects(st->d_two_order, k, fr.fh.gcolumns, shift, fr.fh.width, fr.fh.height, d, mapped, stride_bytes, s1, (int32_t) pb);
 	else {
 		if (hipEventSynchronize(tp.ev[2]) != hipSuccess) return ERR_GPU;
@@ -875,37 +844,30 @@ static uint32_t decode_two_phase(j40hip_frame *h, uint8_t *d, uint8_t *rgba_host
 }
 
 static uint32_t decode_to_host(j40hip_frame *h, void *rgba_host, size_t stride_bytes) {
-	if (h && h->frame.lf_only) return ERR_ULF;
-	if (!h || !h->dev) return ERR_GPU;
-	h->orient_applied = 0; h->orient_staging_bytes = 0;
-	const int32_t orientation = j40hip_orientation_in_force(h);   // (other than 1: the oriented image's rows, made by decode_oriented the one-phase way)
-	const bool region = h->region_set || h->scale > 0 || orientation != 1 || h->frame.fh.use_lf_frame;   // (a frame with use_lf_frame: its tail runs in run_vardct) (only the rectangle's rows, or the small image's, exist on either side, and they go the one-phase way)
-	int32_t sw, sh, ow, oh;
-	j40hip_stored_out_size(h, &sw, &sh);
-	orient_out_size(sw, sh, orientation, &ow, &oh);
-	if (orientation != 1 && h->partial_range) return ERR_UOR;   // (decode_oriented's refusal, before the block is taken)
-	if (orientation != 1 ? stride_bytes < pixel_bytes(h) * (size_t) ow : h->region_set ? stride_bytes < pixel_bytes(h) * (size_t) h->region[2] : scaled_stride_too_small(h, stride_bytes)) return ERR_RNGE;
-	const Frame &fr = h->frame;
+	if (!h) return ERR_GPU;
+	DecodeRoute route = route_of(h, true, stride_bytes);
+	if (h->dev && !h->frame.lf_only) { h->orient_applied = 0; h->orient_staging_bytes = 0; }
+	if (route.refusal) return route.refusal;   // before the block is taken
 	const int device = h->dev->device;
 	if (hipSetDevice(device) != hipSuccess) return ERR_GPU;
 	// the device image uses the caller's row stride, so one contiguous copy brings it back
-	const size_t bytes = stride_bytes * (size_t) (orientation != 1 ? oh : h->region_set ? h->region[3] : h->scale > 0 ? scaled_height(h) : fr.fh.height);
+	const size_t bytes = stride_bytes * (size_t) route.out_h;
 	ScopedBlock block;   // (whatever way the call ends, the image goes back behind a device-wide wait)
 	if (!block.ensure(device, bytes, true)) return ERR_GPU;
 	void *d = block.ptr;
+	// (two phases: whole frames in stored order only -- just the rectangle's rows, the small image's or the oriented one's exist on either side)
 	bool two_phase = false;
-	uint32_t err = region ? 0 : decode_two_phase(h, (uint8_t *) d, (uint8_t *) rgba_host, stride_bytes, &two_phase);
+	uint32_t err = route.two_phase ? decode_two_phase(h, route, (uint8_t *) d, (uint8_t *) rgba_host, stride_bytes, &two_phase) : 0;
 	if (two_phase && err != ERR_EVOF) return err;   // (the pixels are in rgba_host, or the frame has failed; "evof": the dense form below)
 	if (two_phase) (void) hipDeviceSynchronize();
-	err = decode_oriented(h, d, stride_bytes, nullptr, nullptr);
-	if (!err && hipStreamSynchronize(nullptr) != hipSuccess) err = ERR_GPU;
-	if (!err) err = j40hip_frame_status(h);
-	if (err == ERR_EVOF) {   // a section with more non-zero coefficients than its event region holds: decode with dense planes
-		h->force_dense = true;
-		err = j40hip_frame_upload(h, device);
-		if (!err) err = decode_oriented(h, d, stride_bytes, nullptr, nullptr);
+	// the device-side path, waited for; once more with dense planes after a section with more non-zero coefficients than its event region holds
+	err = 0;
+	for (int dense = 0; dense < 2; ++dense) {
+		if (dense) { h->force_dense = true; err = j40hip_frame_upload(h, device); route = route_of(h, true, stride_bytes); }
+		if (!err) err = decode_oriented(h, route, d, stride_bytes, nullptr, nullptr);
 		if (!err && hipStreamSynchronize(nullptr) != hipSuccess) err = ERR_GPU;
 		if (!err) err = j40hip_frame_status(h);
+		if (err != ERR_EVOF) break;
 	}
 	// (the decode has been waited for: the copy may go to the SDMA engine a pipeline of this process measured, hostcopy.hpp)
 	if (!err && !hostcopy_d2h_sync(device, rgba_host, d, bytes) && hipMemcpy(rgba_host, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) err = ERR_GPU;

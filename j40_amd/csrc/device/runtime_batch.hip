@@ -49,8 +49,7 @@ static uint32_t batch_assign(j40hip_batch *b, j40hip_frame *const *frames, int64
 		j40hip_frame *h = frames[i];
 		if (h && h->frame.lf_only) return ERR_ULF;
 		if (!h || !h->dev) return ERR_GPU;
-		if (h->region_set) return ERR_URG;         // a batch writes whole frames
-		if (j40hip_orientation_in_force(h) != 1) return ERR_UOR;   // ... in stored order
+		if (uint32_t e = mode_refusal(h, Mode::Batch)) return e;   // a batch writes whole frames in stored order
 		if (h->dev->is_modular) return ERR_TODO;   // Modular frames: decode them one by one
 		if (h->dev->ycbcr) return ERR_TODO;        // YCbCr frames (j40hip_frame_set_ycbcr): the single-frame decode alone serves them
 		if (h->frame.fh.use_lf_frame) return ERR_TODO;   // a frame that takes its LF image from an LF frame: a sequence's playback alone serves it
@@ -130,11 +129,12 @@ static uint32_t batch_enqueue(j40hip_batch *b, void *const *rgba_dev, const size
 	if (!b) return ERR_GPU;
 	// every member in one output format (mixed batches: "Uof?"), each 16-bit member's rows wide enough: checked before anything is launched
 	for (size_t i = 0; i < b->frames.size(); ++i) {
+		const DecodeRoute route = route_of(b->frames[i]);
 		if (b->frames[i]->output_format != b->frames[0]->output_format) return ERR4('U', 'o', 'f', '?');
 		// ... and at one scale shift ("Usc?"); a keep-alpha member's alpha is merged into full-size pixels when its status is read: not at a scale
 		if (b->frames[i]->scale != b->frames[0]->scale) return ERR_USC;
-		if (b->frames[i]->scale > 0 && b->frames[i]->dev && b->frames[i]->dev->has_trailers && j40hip_alpha_kept(b->frames[i])) return ERR_USC;
-		if (scaled_stride_too_small(b->frames[i], stride_bytes[i])) return ERR_RNGE;
+		if (route.shape == DecodeRoute::Scaled && route.alpha_merged) return ERR_USC;
+		if (stride_bytes[i] < route.min_stride) return ERR_RNGE;
 	}
 	if (hipSetDevice(b->device) != hipSuccess) return ERR_GPU;
 	// a member that was uploaded again since the batch was made (j40hip_frame_force_dense + j40hip_frame_upload after "evof")

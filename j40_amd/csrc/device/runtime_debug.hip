@@ -82,7 +82,7 @@ static uint32_t read_modular_xyb(j40hip_frame *h, float *out) {
 	return hipMemcpy(out, d, sizeof(float) * 3 * plane, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
 }
 extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out) {
-	if (h && h->dev && h->dev->is_modular && stage == 0 && h->modular_xyb_used && modular_xyb_on(h)) return guarded([&] { return read_modular_xyb(h, out); });
+	if (h && h->dev && h->dev->is_modular && stage == 0 && h->modular_xyb_used && j40hip_modular_xyb_on(h)) return guarded([&] { return read_modular_xyb(h, out); });
 	if (!h || !h->dev || !h->dev->restore_ran || !h->dev->d_xyb) return ERR_RNGE;
 	j40hip_device_state *st = h->dev;
 	const FrameHeader &fh = h->frame.fh;

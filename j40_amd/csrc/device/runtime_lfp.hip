@@ -136,7 +136,7 @@ static uint32_t lfp_launch(j40hip_frame *const *frames, int64_t n, void *const *
 
 extern "C" uint32_t j40hip_frames_decode_lf(j40hip_frame *const *frames, int64_t n, void *const *rgba_dev, const size_t *stride_bytes, void *stream) {
 	// many previews in one launch are written in stored order: a member whose orientation is in force is refused before anything is launched
-	for (int64_t i = 0; frames && i < n; ++i) if (frames[i] && j40hip_orientation_in_force(frames[i]) != 1) return ERR_UOR;
+	for (int64_t i = 0; frames && i < n; ++i) if (frames[i]) if (uint32_t e = mode_refusal(frames[i], Mode::LfPreviewBatch)) return e;
 	return guarded([&] { return lfp_launch(frames, n, rgba_dev, stride_bytes, (hipStream_t) stream, false, 0); });
 }
 

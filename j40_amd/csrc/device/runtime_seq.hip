@@ -116,8 +116,7 @@ uint32_t play_frame(j40hip_sequence *s, int64_t k, uint8_t *out, size_t out_stri
 	const FrameHeader &fh = row.fh;
 	if (fh.type == 1) return play_lf_frame(s, k, h, stream, sync);
 	// (the main frame of an LF-frame still takes a scale and the orientation for decodes of its own, capi.hpp: the canvas is full size, stored order)
-	if (h->scale > 0) return ERR_USC;
-	if (j40hip_orientation_in_force(h) != 1) return ERR_UOR;
+	if (uint32_t e = mode_refusal(h, Mode::Playback)) return e;
 	const int32_t W = s->im.width, H = s->im.height;
 	const size_t pb = seq_pixel_bytes(s);
 	// where the canvas of this frame is made

@@ -13,8 +13,6 @@ extern "C" void j40hip_cache_counters(uint64_t *out);   // device_memory.hip: wh
 namespace j40hip_rt {
 
 // switches that more than one unit reads, each with one meaning
-// J40HIP_RESTORATION: 0 off (the default), 1 the filters a frame signals, 2 (`j40`) as j40's routines stand; read once
-inline int restoration_env() { static const int v = [] { const char *e = j40hip::env_str("J40HIP_RESTORATION"); return !e ? 0 : !strcmp(e, "j40") ? 2 : atoi(e) > 0 ? 1 : 0; }(); return v; }
 inline bool async_timing() { return j40hip::env_str("J40HIP_ASYNC_TIMING") != nullptr; }   // (looked at per call)
 inline bool generic_lanes() { return j40hip::env_on("J40HIP_GENERIC_LANES", false); }        // =1: the batches' entropy launch through the general kernel (per call)
 inline int waves_per_wg(int dflt, int hi) { return j40hip::env_int("J40HIP_WAVES_PER_WG", dflt, 1, hi); }

@@ -11,7 +11,7 @@
 #include <atomic>
 #include <cmath>
 #include <unistd.h>
-#include "../capi.hpp"
+#include "../decode_route.hpp"
 #include "../tables.hpp"
 #include "../plan_build.hpp"
 #include "../mod_layout.hpp"
@@ -26,10 +26,6 @@ namespace j40hip_rt {
 
 constexpr uint32_t ERR4(char a, char b, char c, char d) { return ((uint32_t) (uint8_t) a << 24) | ((uint32_t) (uint8_t) b << 16) | ((uint32_t) (uint8_t) c << 8) | (uint32_t) (uint8_t) d; }
 constexpr uint32_t ERR_GPU = ERR4('!', 'g', 'p', 'u'), ERR_MEM = ERR4('!', 'm', 'e', 'm');
-constexpr uint32_t ERR_URG = ERR4('U', 'r', 'g', '?');   // a region (j40hip_frame_set_region) where only whole frames or group ranges are served, or the other way round
-constexpr uint32_t ERR_USC = ERR4('U', 's', 'c', '?');   // a scale (j40hip_frame_set_scale) where only full-size frames are served, or the other way round
-constexpr uint32_t ERR_UOR = ERR4('U', 'o', 'r', '?');   // an orientation in force (j40hip_frame_set_orientation) where only stored order is served
-constexpr uint32_t ERR_ULF = ERR4('U', 'l', 'f', '?');   // an LF-only frame (J40HIP_PARSE_LF_ONLY) has nothing but its LF image: the full decode's entry points refuse it
 
 // no exception crosses the C ABI: a parse error keeps its code, anything else (std::bad_alloc from a vector, ...) is "!mem"
 template <typename F> uint32_t guarded(F f) {
@@ -259,17 +255,15 @@ namespace j40hip_rt {
 inline bool out16(const j40hip_frame *h) { return h->output_format == J40HIP_U16X4; }
 inline OutMode out_mode(const j40hip_frame *h) { return out16(h) ? OutMode::RGBA16 : OutMode::RGBA8; }   // (the pixel kernels' form of it: K2Target)
 inline size_t pixel_bytes(const j40hip_frame *h) { return out16(h) ? 8 : 4; }
-// a 16-bit frame's rows must hold 8 * width bytes: "rnge" before anything is launched (the u8 entry points keep their old contract)
-inline bool stride_too_small(const j40hip_frame *h, size_t stride_bytes) { return out16(h) && stride_bytes < 8 * (size_t) h->frame.fh.width; }
-// the size the frame's scale shift gives (j40hip_frame_set_scale): ceil(width / s) x ceil(height / s)
-inline int32_t scaled_width(const j40hip_frame *h) { return (h->frame.fh.width + (1 << h->scale) - 1) >> h->scale; }
-inline int32_t scaled_height(const j40hip_frame *h) { return (h->frame.fh.height + (1 << h->scale) - 1) >> h->scale; }
-// at a shift above 0 the rows must hold the small image's pixels, in both formats
-inline bool scaled_stride_too_small(const j40hip_frame *h, size_t stride_bytes) { return h->scale > 0 ? stride_bytes < pixel_bytes(h) * (size_t) scaled_width(h) : stride_too_small(h, stride_bytes); }
+// what the handle's next decode does (decode_route.hpp), with the upload's facts; `have_out`, `stride_bytes`: the caller's image
+inline DecodeRoute route_of(const j40hip_frame *h, bool have_out = true, size_t stride_bytes = SIZE_MAX) {
+	const j40hip_device_state *st = h->dev;
+	const UploadFacts up = {st && st->is_modular, st && st->ycbcr, st && st->has_trailers, st ? st->first_group : 0, st ? st->num_groups : 0};
+	return resolve_route(h, st ? &up : nullptr, have_out, stride_bytes);
+}
 
-// a Modular frame of an XYB image through the XYB colour tail (j40hip_frame_set_modular_xyb): in force for this frame, and what its kernels
-// take -- LfGlobal's LF dequantisation and the colour constants as fill_frame_constants (plan_build.cpp) states them for DevFrame
-inline bool modular_xyb_on(const j40hip_frame *h) { return j40hip_modular_xyb_on(h); }
+// a Modular frame of an XYB image through the XYB colour tail (j40hip_frame_set_modular_xyb): what its kernels take -- LfGlobal's LF
+// dequantisation and the colour constants as fill_frame_constants (plan_build.cpp) states them for DevFrame
 inline ModXybConsts modular_xyb_consts(const Frame &fr) {
 	ModXybConsts k;
 	for (int c = 0; c < 3; ++c) { k.m[c] = fr.m_lf_scaled[c]; k.cc.opsin_bias[c] = fr.im.opsin_bias[c]; k.cc.cbrt_opsin_bias[c] = cbrtf(fr.im.opsin_bias[c]); }

@@ -286,22 +286,17 @@ extern "C" void j40hip_frame_force_dense(j40hip_frame *h, int dense) { if (h) h-
 static uint32_t j40hip_frame_set_group_range_body(j40hip_frame *h, int64_t first_group, int64_t num_groups) {
 	if (!h || !h->dev) return ERR_GPU;
 	if (first_group < 0 || num_groups < 0 || first_group + num_groups > h->frame.fh.num_groups) return ERR_RNGE;
-	if (h->region_set && !(first_group == 0 && num_groups == h->frame.fh.num_groups)) return ERR_URG;   // a region and a partial range exclude each other
-	if (h->scale > 0 && !(first_group == 0 && num_groups == h->frame.fh.num_groups)) return ERR_USC;     // ... and so do a scale and a partial range
-	if (j40hip_orientation_in_force(h) != 1 && !(first_group == 0 && num_groups == h->frame.fh.num_groups)) return ERR_UOR;   // ... and an orientation in force and one
+	const bool whole = first_group == 0 && num_groups == h->frame.fh.num_groups;
+	if (!whole) if (uint32_t e = mode_refusal(h, Mode::GroupRange)) return e;   // (a region, a scale, an orientation in force: decode_route.hpp)
 	j40hip_device_state *st = h->dev;
 	if (st->is_modular) {
 		// Modular frames: the groups' sections are independent of each other (no predictor looks across a group's edge), and so are
 		// the per-pixel inverse transforms (RCT, plain palette); a palette with predicted deltas or a Squeeze step reads across
 		// groups, and frames coded with Squeeze have no one-section-per-group layout at all: those are decoded whole
-		const bool whole = first_group == 0 && num_groups == h->frame.fh.num_groups;
 		if (!whole && !modular_groups_independent(h)) return ERR_TODO;
-		st->first_group = first_group; st->num_groups = num_groups; h->partial_range = !whole;
-		return 0;
 	}
-	st->first_group = first_group; st->num_groups = num_groups;
-	h->partial_range = !(first_group == 0 && num_groups == h->frame.fh.num_groups);
-	if (!h->partial_range) return 0;
+	st->first_group = first_group; st->num_groups = num_groups; h->partial_range = !whole;
+	if (whole || st->is_modular) return 0;
 	// varblocks never straddle a group (the largest transform is one group wide), so the pixel kernels' work lists are
 	// the full lists filtered by the group of each block's top-left pixel
 	const FrameHeader &fh = h->frame.fh;

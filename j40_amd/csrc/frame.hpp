@@ -23,6 +23,8 @@ inline bool orient_env() { static const bool v = [] { const char *e = env_str("J
 // J40HIP_YCBCR=1: YCbCr VarDCT frames (recompressed JPEGs) are served where j40hip_frame_set_ycbcr(f, 1) would be taken (include/j40hip.h); read once
 inline bool wide_env() { static const bool v = [] { const char *e = env_str("J40HIP_WIDE"); return e && atoi(e) > 0; }(); return v; }
 inline bool modular_xyb_env() { static const bool v = [] { const char *e = env_str("J40HIP_MODULAR_XYB"); return e && atoi(e) > 0; }(); return v; }
+// J40HIP_RESTORATION: 0 off (the default), 1 the filters a frame signals, 2 (`j40`) as j40's routines stand; read once
+inline int restoration_env() { static const int v = [] { const char *e = env_str("J40HIP_RESTORATION"); return !e ? 0 : !strcmp(e, "j40") ? 2 : atoi(e) > 0 ? 1 : 0; }(); return v; }
 inline bool ycbcr_env() { static const bool v = [] { const char *e = env_str("J40HIP_YCBCR"); return e && atoi(e) > 0; }(); return v; }
 
 struct ExtraChannel { int32_t type = 0, bpp = 8, exp_bits = 0, dim_shift = 0; bool alpha_associated = false; };
