@@ -343,6 +343,53 @@ J40HIP_API void j40hip_frame_wide(const j40hip_frame *f, int32_t out[4]);
  *      frame only (a region's groups, a partial group range): the planes outside it are not this decode's. ---- */
 J40HIP_API uint32_t j40hip_frame_set_modular_xyb(j40hip_frame *f, int mode);
 J40HIP_API void j40hip_frame_modular_xyb(const j40hip_frame *f, int32_t out[4]);
+/* ---- The colour mode ("Colour space"). The image header's ColourEncoding names white point, primaries
+ *      and a transfer function or gamma. The reference reads it and renders every XYB image as sRGB primaries, D65, sRGB curve; so does
+ *      this library unless asked. PARITY UNPINNED: the formulas are the standards' (BT.709, BT.2100, SMPTE 428 / 431, sRGB, ST 2084); no
+ *      decoder at hand pins libjxl's conventions, above all the HLG inverse OOTF and blending in the signalled space.
+ *      set: mode -1 follows the environment (J40HIP_COLOUR=1 serves; the default), 0 renders sRGB, 1 renders an XYB image in the signalled
+ *      space: the gamut matrix (Bradford-adapted where the white points differ) folded into the inverse opsin matrix, then the signalled
+ *      curve -- linear, sRGB, BT.709, DCI (x^(1/2.6)), gamma, PQ (1.0 = intensity_target nits), HLG (BT.2100's inverse OOTF first) -- and
+ *      level = floor(maxpixel * f + 0.5) at the frame's bit depth, reduced to u8 / u16 as ever (k_colour_tail). An image whose encoding is
+ *      the sRGB default goes the usual way, byte for byte. Mode 1 is refused with "Ucs?" (the frame is left as it was) for: an image that
+ *      wants its ICC profile interpreted, transfer function 2 (unknown), a grey image, custom chromaticities that span nothing, a YCbCr
+ *      frame, a Modular frame that does not go through the XYB colour tail (j40hip_frame_set_modular_xyb), an LF-only handle, a handle
+ *      built from a view. An image with xyb_encoded = 0 holds samples in its signalled space already: accepted, and nothing changes. The
+ *      environment variable alone leaves every such frame as it was. It holds from the next decode on.
+ *      Served with the mode in force: both output formats, a region and scale 1 and 2 (through the full-size staging image), the
+ *      orientation, kept alpha, the restoration filters (the tail runs on the filtered planes), Modular XYB frames, sequences
+ *      (J40HIP_SEQ_COLOUR: the canvas holds pixels in the signalled space). "Ucs?" with the mode in force: a partial group range, a
+ *      batch member (j40hip_batch_create), the LF preview -- j40hip_frame_decode_lf, j40hip_frame_decode_lf_to_host and
+ *      j40hip_frames_decode_lf alike, whose tail renders sRGB (j40hip_frame_read_lf's float planes are served). A pipeline is not
+ *      refused: it renders sRGB whatever the mode or the environment says. j40hip_frame_decode_xyb's planes are not affected.
+ *      j40hip_frame_colour: out[0] the rule applies to the frame; out[1] it is in force; out[2] white point, out[3] primaries, out[4]
+ *      transfer function (-1 with a gamma), out[5] colour space -- the enums as parsed; out[6] the last decode went through
+ *      k_colour_tail (2: and it was an 8-bit frame whose curve has no threshold table -- the linear curve, which is cheaper evaluated,
+ *      or a gamma so small that its levels span more buckets than a table holds -- so the curve was evaluated per sample, at the cost
+ *      of the deeper frames' path); out[7] what mode 1 would be refused with (0: nothing).
+ *      j40hip_frame_colour_encoding: out[0] colour space, [1] white point, [2..3] its xy, [4] primaries, [5..10] their xy (R, G, B),
+ *      [11] have_gamma, [12] gamma, [13] transfer function, [14] rendering intent, [15] want_icc. xy and gamma are the stream's
+ *      integers (1e-6 and 1e-7 units); an enum's xy are the values it stands for.
+ *      After a decode that took the tail without the restoration filters, j40hip_frame_read_xyb (stages 0 and 1) answers with the
+ *      planes the tail read. ---- */
+J40HIP_API uint32_t j40hip_frame_set_colour(j40hip_frame *f, int mode);
+J40HIP_API void j40hip_frame_colour(const j40hip_frame *f, int32_t out[8]);
+J40HIP_API void j40hip_frame_colour_encoding(const j40hip_frame *f, int32_t out[16]);
+/* host known answers (no device): the gamut matrix of an encoding given as j40hip_frame_colour_encoding states it (`enc`), row-major
+ * into p[9], the luminance row into lum[3]; 0 or "Ucs?" */
+J40HIP_API uint32_t j40hip_colour_gamut_matrix(const int32_t enc[16], double p[9], double lum[3]);
+/* host known answer (no device): the threshold table an 8-bit frame's tail uses for the encoding's curve at intensity_target -- 1794
+ * floats into `out` (out_floats: its room): 258 thresholds, then the bucket bytes; range[0..1]: the first and last bucket (a float's top
+ * 16 bits). 0, "rnge" (no room), "Ucs?": the curve has no table (its levels span more buckets than the table holds), the tail evaluates it. */
+J40HIP_API uint32_t j40hip_colour_table(const int32_t enc[16], float intensity_target, float *out, size_t out_floats, int32_t range[2]);
+/* known-answer / measuring hook: k_colour_tail on caller-supplied planes in device memory, enqueued on `stream` and not waited for.
+ * xyb_dev: three planes X, Y, B of width x height floats, one behind the other; colour_consts: the 15 floats of
+ * j40hip_frame_colour_consts ([0..8] the matrix the tail uses as it stands -- the caller folds the gamut matrix in --, [9..11] the opsin
+ * bias, [12] intensity_target); enc: the encoding as above (its curve is taken), lum: the luminance row HLG's OOTF uses; bpp 8..16.
+ * table_dev: null, or for bpp 8 what j40hip_colour_table made, in device memory (all 1794 floats), with its range: the tail then takes
+ * the table instead of the curve. The image in `format`, stride_bytes a row, rows pixel-aligned. 0, "rnge", "Ufm?", "Ucs?". */
+J40HIP_API uint32_t j40hip_kat_device_colour_tail(const float *xyb_dev, int32_t width, int32_t height, const float colour_consts[15], const int32_t enc[16], const float lum[3],
+		int32_t bpp, const float *table_dev, const int32_t table_range[2], int32_t format, void *out_dev, size_t stride_bytes, void *stream);
 /* known-answer / measuring hook: the Modular XYB kernels on caller-supplied planes in device memory. planes_dev: c0, c1, c2 (width x
  * height samples of sample_bytes 2 or 4 each, tightly packed); alpha_dev: the alpha plane of the same kind, or null; m: the three
  * dequantisation factors; colour_consts: the 15 floats of j40hip_frame_colour_consts (the last two are not used); bpp 8..16.
@@ -619,6 +666,14 @@ J40HIP_API uint32_t j40hip_batch_reset(j40hip_batch *b, j40hip_frame *const *fra
  * handle the rule applies to; J40HIP_MODULAR_XYB=1 in the environment does the same). Together with J40HIP_SEQ_LFFRAME a Modular LF frame
  * is served: k_modular_to_xyb fills its LF slot. With either alone such a frame stays "TODO". */
 #define J40HIP_SEQ_MODULAR_XYB 32u
+/* j40hip_sequence_open: every handle of the sequence renders in the colour space the image header signals (j40hip_frame_set_colour's mode 1
+ * wherever the rule applies and the encoding is not the sRGB default; J40HIP_COLOUR=1 in the environment does the same): the canvas and the
+ * reference slots then hold pixels in that space, and the blend modes work on them as they are (PARITY UNPINNED). One canvas holds
+ * one colour space: with the flag, an image the mode refuses as a whole (want_icc, transfer function 2, grey) fails j40hip_sequence_open
+ * with "Ucs?" (under the environment variable alone such a sequence plays as sRGB, every frame of it); and where the image's frames do
+ * render in the signalled space, j40hip_sequence_frame answers "Ucs?" for a frame that cannot -- a Modular frame while
+ * J40HIP_SEQ_MODULAR_XYB is off -- instead of composing it as sRGB among them. */
+#define J40HIP_SEQ_COLOUR 64u
 typedef struct j40hip_sequence j40hip_sequence;
 J40HIP_API j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads, uint32_t flags, uint32_t *err);
 J40HIP_API void j40hip_sequence_free(j40hip_sequence *s);

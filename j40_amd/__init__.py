@@ -138,6 +138,10 @@ def lib():
         "j40hip_kat_device_modular_xyb": (u32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, sz, vp, vp]),
         "j40hip_kat_device_modular_xyb_launch": (u32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, vp, sz, vp, vp]),
         "j40hip_kat_device_colour_frame": (sz, [vp, i32, vp, sz]),
+        "j40hip_frame_set_colour": (u32, [vp, C.c_int]), "j40hip_frame_colour": (None, [vp, vp]), "j40hip_frame_colour_encoding": (None, [vp, vp]),
+        "j40hip_colour_gamut_matrix": (u32, [vp, vp, vp]),
+        "j40hip_colour_table": (u32, [vp, C.c_float, vp, sz, vp]),
+        "j40hip_kat_device_colour_tail": (u32, [vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, sz, vp]),
         "j40hip_frame_set_region": (u32, [vp, i32, i32, i32, i32]), "j40hip_frame_region": (None, [vp, vp]),
         "j40hip_frame_set_scale": (u32, [vp, i32]), "j40hip_frame_scale": (None, [vp, vp]), "j40hip_pipeline_set_scale": (u32, [vp, i32]),
         "j40hip_kat_device_downscale": (u32, [vp, sz, vp, sz, i32, i32, i32, i32, vp]),
@@ -238,7 +242,7 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False, colour=False):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
     scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
     (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
@@ -259,12 +263,15 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     sequence is decoded as without it.
     modular_xyb=True: a Modular frame of an XYB image goes through the XYB colour tail for this call whatever J40HIP_MODULAR_XYB says
     (Frame.set_modular_xyb(1); "Umx?" for a frame the rule does not apply to), through the thin C-ABI on device 0. With lf_frames=True
-    the sequence is opened with both switches, which serves a Modular LF frame."""
+    the sequence is opened with both switches, which serves a Modular LF frame.
+    colour=True: an XYB image is rendered in the colour space its header signals for this call whatever J40HIP_COLOUR says
+    (Frame.set_colour(1); "Ucs?" for what that refuses), through the thin C-ABI on device 0; with lf_frames=True the sequence is opened
+    with the switch."""
     if lf_frames:
         if alpha or ycbcr or wide:
             return "TODO", None
         try:
-            seq = Sequence(data, lf_frames=True, modular_xyb=bool(modular_xyb))
+            seq = Sequence(data, lf_frames=True, modular_xyb=bool(modular_xyb), colour=bool(colour))
         except J40Error as e:
             if e.code != "Usq?":
                 return e.code, None
@@ -288,7 +295,7 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
                 return e.code, None
             finally:
                 seq.close()
-    if alpha or scale or ycbcr or orient or wide or modular_xyb:
+    if alpha or scale or ycbcr or orient or wide or modular_xyb or colour:
         try:
             fr = Frame(data, ycbcr=bool(ycbcr), wide=bool(wide))
         except J40Error as e:
@@ -299,6 +306,8 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
                 code = fr.set_modular_xyb(1)
             if not code and ycbcr:
                 code = fr.set_ycbcr(1)
+            if not code and colour:
+                code = fr.set_colour(1)
             if not code and scale:
                 code = fr.set_scale(scale)
             if not code and orient:
@@ -325,18 +334,22 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     return err, out
 
 
-def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False, wide=False):
+def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False, wide=False, colour=False):
     """rectangle (x, y, w, h) of the image through the thin C-ABI: returns (err4, ndarray [h, w, 4] or None), uint8 or uint16 with
     fmt=J40_U16X4 -- the crop of what decode() returns, decoded from the pass groups that cover it (Frame.set_region). The verdict is
     the one over the sections that were decoded, then the public API's look behind the frame.
     orient=True: (x, y, w, h) is a rectangle of the DISPLAYED picture -- the frame in the orientation its stream carries; it is mapped
     to stored coordinates (Frame.orient_rect) and the result is the crop of the oriented whole picture, [h, w, 4].
-    wide=True: as decode()'s."""
+    wide=True, colour=True: as decode()'s."""
     try:
         fr = Frame(data, wide=bool(wide))
     except J40Error as e:
         return e.code, None
     try:
+        if colour:
+            code = fr.set_colour(1)
+            if code:
+                return code, None
         if orient:
             code, stored = fr.orient_rect((x, y, w, h), to_stored=True)
             if not code:
@@ -428,6 +441,62 @@ def kat_device_orient(src, orientation, fmt=None, pad=0, device=0):
     host = d_out.cpu().numpy().reshape(oh, stride)
     guard = bool((host[:, ow * pb:] == 0xA5).all())
     return "", np.ascontiguousarray(host[:, :ow * pb]).view(src.dtype).reshape(oh, ow, 4), guard
+
+
+def colour_gamut_matrix(enc_words):
+    """j40hip_colour_gamut_matrix (host only): (err4, P [3, 3] float64: linear sRGB / D65 -> the encoding's primaries and white point,
+    lum [3]: the luminance of the three target-space values) for an encoding given as Frame.colour_encoding(words=True) states it"""
+    import numpy as np
+    enc = np.ascontiguousarray(enc_words, np.int32)
+    p = np.zeros(9, np.float64); lum = np.zeros(3, np.float64)
+    code = err4(lib().j40hip_colour_gamut_matrix(enc.ctypes.data, p.ctypes.data, lum.ctypes.data))
+    return code, p.reshape(3, 3), lum
+
+
+COLOUR_TABLE_FLOATS = 258 + 48 * 128 // 4
+
+
+def colour_table(enc_words, intensity_target):
+    """j40hip_colour_table (host only): (err4, table float32 [COLOUR_TABLE_FLOATS], (first bucket, last bucket)) -- the threshold table an
+    8-bit frame's colour tail uses for the encoding's curve; "Ucs?": the curve has none"""
+    import numpy as np
+    enc = np.ascontiguousarray(enc_words, np.int32)
+    table = np.zeros(COLOUR_TABLE_FLOATS, np.float32); rng = np.zeros(2, np.int32)
+    code = err4(lib().j40hip_colour_table(enc.ctypes.data, float(intensity_target), table.ctypes.data, table.size, rng.ctypes.data))
+    return code, table, (int(rng[0]), int(rng[1]))
+
+
+def kat_device_colour_tail(xyb, colour_consts, enc_words, lum, bpp, fmt=J40_U8X4, use_table=True, pad=0, device=0):
+    """k_colour_tail alone (j40hip_kat_device_colour_tail): xyb [3, h, w] float32 (X, Y, B), colour_consts the 15 floats of
+    Frame.colour_consts() with the matrix the tail is to use in [0:9], the encoding's 16 words, lum [3]. An 8-bit frame takes the curve's
+    threshold table (colour_table) where it has one, unless use_table=False. Returns (err4, pixels [h, w, 4] uint8 or uint16). Rows
+    `pad` pixels longer than the image; the padding must come back untouched (asserted here)"""
+    import numpy as np
+    import torch
+    xyb = np.ascontiguousarray(xyb, np.float32)
+    _, h, w = xyb.shape
+    pb = 8 if fmt == J40_U16X4 else 4
+    dev = torch.device("cuda", device)
+    cc = np.ascontiguousarray(colour_consts, np.float32); enc = np.ascontiguousarray(enc_words, np.int32); lm = np.ascontiguousarray(lum, np.float32)
+    table, rng = None, np.zeros(2, np.int32)
+    if bpp == 8 and use_table:
+        code, t, r = colour_table(enc, cc[12])
+        if not code:
+            table, rng = t, np.array(r, np.int32)
+    with torch.cuda.device(dev):
+        d_in = torch.from_numpy(xyb).to(dev)
+        d_table = torch.from_numpy(table).to(dev) if table is not None else None
+        out = torch.full((h, (w + pad) * pb), 0xA5, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        code = err4(lib().j40hip_kat_device_colour_tail(d_in.data_ptr(), w, h, cc.ctypes.data, enc.ctypes.data, lm.ctypes.data, int(bpp),
+                                                         d_table.data_ptr() if d_table is not None else None, rng.ctypes.data, fmt, out.data_ptr(), (w + pad) * pb, None))
+        torch.cuda.synchronize(dev)
+        host = out.cpu().numpy()
+    if code:
+        return code, None
+    assert (host[:, w * pb:] == 0xA5).all(), "k_colour_tail wrote behind a row's pixels"
+    px = np.ascontiguousarray(host[:, :w * pb])
+    return "", (px.view(np.uint16) if pb == 8 else px).reshape(h, w, 4)
 
 
 def kat_device_modular_xyb(planes, alpha, m, colour_consts, bpp, fmt=J40_U8X4, pad=0, device=0):
@@ -782,6 +851,37 @@ class Frame:
         grey, YCbCr, float samples, fewer than 8 bits)"""
         return err4(lib().j40hip_frame_set_modular_xyb(self.h, int(mode)))
 
+    # ---- the colour mode (include/j40hip.h) ----
+    def set_colour(self, mode):
+        """1: an XYB image is rendered in the colour space its header signals (white point, primaries, transfer function or gamma) by
+        k_colour_tail; 0: as sRGB (the reference's pixels); -1 (the default): as J40HIP_COLOUR says (j40hip_frame_set_colour). An image
+        whose encoding is the sRGB default decodes the usual way either way. Returns "" or "Ucs?" (want_icc, transfer function 2, grey,
+        a YCbCr frame, a Modular frame without set_modular_xyb(1), a partial group range; the frame is left as it was)"""
+        return err4(lib().j40hip_frame_set_colour(self.h, int(mode)))
+
+    def colour(self):
+        """{applies, in_force, white_point, primaries, transfer (-1 with a gamma), colour_space, used: the last decode went through
+        k_colour_tail, curve_evaluated_at_8_bits: ... and it was an 8-bit frame whose curve has no threshold table (linear, or a gamma
+        next to nothing), refusal: what set_colour(1) would answer}"""
+        import numpy as np
+        a = np.zeros(8, np.int32)
+        lib().j40hip_frame_colour(self.h, a.ctypes.data)
+        return {"applies": bool(a[0]), "in_force": bool(a[1]), "white_point": int(a[2]), "primaries": int(a[3]), "transfer": int(a[4]), "colour_space": int(a[5]),
+                "used": bool(a[6]), "curve_evaluated_at_8_bits": int(a[6]) == 2, "refusal": err4(int(a[7]) & 0xffffffff)}
+
+    def colour_encoding(self, words=False):
+        """the image header's ColourEncoding as parsed: {colour_space, white_point, white_xy, primaries, primaries_xy (R, G, B),
+        have_gamma, gamma, transfer, intent, want_icc}; xy in units of 1e-6 and gamma of 1e-7, the stream's integers (an enum's xy: the
+        values it stands for). words=True: the 16 int32 words as j40hip_frame_colour_encoding writes them"""
+        import numpy as np
+        a = np.zeros(16, np.int32)
+        lib().j40hip_frame_colour_encoding(self.h, a.ctypes.data)
+        if words:
+            return a
+        return {"colour_space": int(a[0]), "white_point": int(a[1]), "white_xy": (int(a[2]), int(a[3])), "primaries": int(a[4]),
+                "primaries_xy": tuple((int(a[5 + 2 * c]), int(a[6 + 2 * c])) for c in range(3)), "have_gamma": bool(a[11]), "gamma": int(a[12]),
+                "transfer": int(a[13]), "intent": int(a[14]), "want_icc": bool(a[15])}
+
     def modular_xyb(self):
         """{"applies": the rule applies to the frame, "on": it is in force, "sample_bytes": 2 or 4 (0: a VarDCT frame), "used": the last
         decode went through k_modular_xyb_pack / k_modular_to_xyb}"""
@@ -997,6 +1097,7 @@ def decode_lf_many(datas, fmt=J40_U8X4, device=0):
 
 SEQ_BLEND = 2   # j40hip_sequence_open's flag J40HIP_SEQ_BLEND: the blend modes Add, Blend, MulAdd and Mul are served
 SEQ_LFFRAME = 16   # ... J40HIP_SEQ_LFFRAME: LF frames (type 1) and the frames with use_lf_frame are served
+SEQ_COLOUR = 64   # ... J40HIP_SEQ_COLOUR: every handle renders in the colour space the image header signals (Frame.set_colour)
 SEQ_MODULAR_XYB = 32   # ... J40HIP_SEQ_MODULAR_XYB: Modular frames of an XYB image go through the XYB colour tail; with SEQ_LFFRAME a Modular LF frame is served
 SEQUENCE_BLEND_FIELDS = ("mode", "alpha_mode", "alpha_chan", "clamp", "alpha_alpha_chan", "alpha_clamp", "src", "blended")
 SEQUENCE_FRAME_FIELDS = ("x0", "y0", "w", "h", "duration", "is_last", "shown", "type", "blend", "src", "save_as_reference", "saved",
@@ -1009,14 +1110,16 @@ class Sequence:
     blend=True (or J40HIP_BLEND=1): frames with the blend modes Add, Blend, MulAdd and Mul are served too, else "TODO" for such a frame.
     lf_frames=True (or J40HIP_LFFRAME=1): LF frames (type 1) and the frames that take their LF image from one (use_lf_frame) are
     served too, else "TODO"; an LF frame is a row that is neither shown nor saved (frame_lf).
+    colour=True (or J40HIP_COLOUR=1): every handle renders in the colour space the image header signals (Frame.set_colour): the canvas
+    holds pixels in that space, the blend modes work on them as they are.
     modular_xyb=True (or J40HIP_MODULAR_XYB=1): the Modular frames of an XYB image go through the XYB colour tail (Frame.set_modular_xyb);
     together with lf_frames=True a Modular LF frame is served, with either alone it is "TODO"."""
 
-    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False, modular_xyb: bool = False):
+    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False, modular_xyb: bool = False, colour: bool = False):
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0) | (SEQ_MODULAR_XYB if modular_xyb else 0)
+        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0) | (SEQ_MODULAR_XYB if modular_xyb else 0) | (SEQ_COLOUR if colour else 0)
         self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags, C.byref(err))
         if not self.h:
             raise J40Error(err4(err.value), "in j40hip_sequence_open")
@@ -1126,15 +1229,16 @@ class Sequence:
         return err4(code), int(k.value)
 
 
-def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False, modular_xyb=False):
+def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False, modular_xyb=False, colour=False):
     """every displayed frame of an animation or a layered still: ([(rgba ndarray [height, width, 4], duration in ticks), ...],
     (tps_num, tps_den, loops)). alpha=True: VarDCT frames keep their alpha channel (Frame.set_alpha(1); J40Error where that refuses).
     blend=True: frames with a blend mode other than Replace are composed too (Sequence's blend=), else such a frame raises "TODO".
     wide=True: an image with 32-bit Modular buffers is served (Sequence's wide=; its Modular frames only).
     lf_frames=True: LF frames and the frames that take their LF image from one are served (Sequence's lf_frames=), else "TODO".
     modular_xyb=True: Modular frames of an XYB image go through the XYB colour tail (Sequence's modular_xyb=).
+    colour=True: every frame is rendered in the colour space the image header signals (Sequence's colour=).
     A frame that fails raises J40Error with its code. A stream whose first frame is its last is not a sequence ("Usq?"): decode()."""
-    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames, modular_xyb=modular_xyb)
+    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames, modular_xyb=modular_xyb, colour=colour)
     try:
         seq.set_output_format(fmt)
         if alpha:

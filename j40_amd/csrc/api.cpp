@@ -216,6 +216,9 @@ int scale_policy() { const int e = j40hip::env_int("J40HIP_SCALE", 0, INT_MIN, I
 // j40_frame_pixels_* then report the oriented picture's width, height and stride. Such images take the single-frame route -- the
 // serving pipeline writes stored order -- and sequences are not served.
 bool orient_policy() { return j40hip::orient_env(); }
+// J40HIP_COLOUR=1: XYB images come out in the colour space their header signals (j40hip_frame_set_colour's default mode follows the same
+// variable, j40hip_sequence_open reads it too). Such images take the single-frame route: the serving pipeline renders sRGB.
+bool colour_policy() { return j40hip::colour_env(); }
 int parse_thread_count() {
 	static const int v = [] { const int e = j40hip::env_int("J40HIP_PARSE_THREADS", 0, 0, INT_MAX); return e > 0 ? e : std::max(1, std::min(12, j40hip_cpu_quota())); }();
 	return v;
@@ -270,7 +273,7 @@ j40_err advance(j40__inner *inner, int origin) {
 	const int64_t now = (int64_t) now_ms();
 	if (inside.n > 1) g_last_overlap_ms.store(now);
 	const bool u16 = inner->format == J40_U16X4;   // (16-bit images take the single-frame path: the pipeline writes u8x4 only)
-	const bool serve = !u16 && !orient_policy() && (policy == 1 || (policy == 2 && (inside.n > 1 || now - g_last_overlap_ms.load() < 200)));
+	const bool serve = !u16 && !orient_policy() && !colour_policy() && (policy == 1 || (policy == 2 && (inside.n > 1 || now - g_last_overlap_ms.load() < 200)));
 	const bool timing = j40hip::api_timing();
 	uint32_t err = 0;
 	std::unique_ptr<FileSource> src;

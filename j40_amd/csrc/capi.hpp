@@ -3,6 +3,7 @@
 #include "../../include/j40hip.h"
 #include "frame.hpp"
 #include "plan_build.hpp"
+#include "colour_space.hpp"
 
 struct j40hip_device_state;  // defined in device/runtime_state.hpp
 
@@ -26,6 +27,11 @@ struct j40hip_frame {
 	int modular_xyb = -1;
 	bool modular_xyb_used = false;
 	bool modular_xyb_whole = false;   // ... and decoded every group: the planes hold the whole frame (j40hip_frame_read_xyb)
+	// the colour mode (j40hip_frame_set_colour): -1 as J40HIP_COLOUR says, 0 every XYB image rendered as sRGB (the reference's pixels), 1 in the
+	// colour space the image header signals; and whether the last decode went through k_colour_tail
+	int colour = -1;
+	bool colour_used = false;
+	bool colour_curve_8bit = false;   // ... of an 8-bit frame without a threshold table: the curve was evaluated per sample (the linear curve, or one whose levels no table holds)
 	bool wide_used = false;          // the last decode ran the int32 instantiations of the Modular kernels (a wide frame, j40hip_frame_wide)
 	bool ycbcr_used = false;         // the last decode went through the YCbCr planes and k_ycbcr_tail
 	int32_t output_format = J40HIP_U8X4;   // what the decode entry points write (j40hip_frame_set_output_format): u8x4 or u16x4
@@ -94,6 +100,8 @@ struct j40hip_sequence {
 	int threads = 1; uint32_t flags = 0;
 	bool blend = false;              // the blend modes other than Replace are served (J40HIP_SEQ_BLEND or J40HIP_BLEND=1)
 	bool lf_frames = false;          // LF frames and use_lf_frame are served (J40HIP_SEQ_LFFRAME or J40HIP_LFFRAME=1)
+	bool colour = false;             // every handle renders in the signalled colour space (J40HIP_SEQ_COLOUR or J40HIP_COLOUR=1)
+	bool colour_asked = false;       // ... by the flag itself: an image the mode refuses as a whole then fails j40hip_sequence_open
 	bool modular_xyb = false;        // Modular frames of an XYB image go through the XYB colour tail (J40HIP_SEQ_MODULAR_XYB or J40HIP_MODULAR_XYB=1)
 	int32_t alpha_ec = -1;           // the extra channel that is rendered as A (rendered_alpha_channel); -1: none
 	int32_t output_format = J40HIP_U8X4;
@@ -126,6 +134,24 @@ inline bool j40hip_modular_xyb_applies(const j40hip_frame *h) {
 }
 inline bool j40hip_modular_xyb_on(const j40hip_frame *h) {
 	return mode_on(h->modular_xyb, j40hip::modular_xyb_env) && j40hip_modular_xyb_applies(h);
+}
+
+// The colour mode: what the setter refuses ("Ucs?"), the frames the rule applies to -- XYB images it does not refuse --
+// and whether it is in force: asked for (or J40HIP_COLOUR=1) on such a frame whose encoding is not the sRGB default; with the environment
+// variable alone every other frame decodes as before. An image with xyb_encoded = 0 holds samples in its signalled space already:
+// accepted, never in force. A YCbCr frame, a Modular frame that does not go through the XYB colour tail, the LF preview and a handle
+// built from a view have no XYB tail to redirect.
+inline uint32_t j40hip_colour_refusal(const j40hip_frame *h) {
+	const j40hip::Frame &f = h->frame;
+	if (f.fh.do_ycbcr) return j40hip::colour::ERR_UCS;
+	if (!f.im.xyb_encoded) return 0;
+	if (uint32_t e = j40hip::colour::image_refusal(f.im)) return e;
+	if (f.lf_only || h->from_view) return j40hip::colour::ERR_UCS;
+	return f.fh.is_modular && !j40hip_modular_xyb_on(h) ? j40hip::colour::ERR_UCS : 0;
+}
+inline bool j40hip_colour_applies(const j40hip_frame *h) { return h->frame.im.xyb_encoded && !j40hip_colour_refusal(h); }
+inline bool j40hip_colour_on(const j40hip_frame *h) {
+	return mode_on(h->colour, j40hip::colour_env) && !h->frame.im.cenc.srgb_default() && j40hip_colour_applies(h);
 }
 
 // A handle a sequence hands out for the main frame of a still whose LF image is a frame of its own: a regular frame with use_lf_frame

@@ -160,9 +160,13 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 		s->blend = (flags & J40HIP_SEQ_BLEND) != 0 || env_on("J40HIP_BLEND", false);   // (looked at with every sequence that is opened)
 		s->lf_frames = (flags & J40HIP_SEQ_LFFRAME) != 0 || env_on("J40HIP_LFFRAME", false);
 		s->modular_xyb = (flags & J40HIP_SEQ_MODULAR_XYB) != 0 || env_on("J40HIP_MODULAR_XYB", false);
+		s->colour = (flags & J40HIP_SEQ_COLOUR) != 0 || env_on("J40HIP_COLOUR", false);
+		s->colour_asked = (flags & J40HIP_SEQ_COLOUR) != 0;
 		size_t at = 0;
 		parse_image_header(s->cs, s->cs_size, &s->im, &at, (flags & J40HIP_PARSE_WIDE) != 0 || wide_env());
 		s->alpha_ec = rendered_alpha_channel(s->im);
+		// the flag on an image the colour mode refuses as a whole (the environment variable alone leaves such a sequence as it was)
+		if (s->colour_asked) if (uint32_t e = j40hip::colour::image_refusal(s->im)) raise(e);
 		int32_t lf_row[4] = {-1, -1, -1, -1};   // the row whose picture LF slot k holds when the playback gets here
 		for (;;) {
 			j40hip_sequence::Row row;
@@ -281,6 +285,11 @@ j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err
 		h->output_format = s->output_format;
 		h->from_sequence = true;
 		h->modular_xyb = s->modular_xyb ? 1 : 0;   // (in force where the rule applies: j40hip_modular_xyb_on)
+		h->colour = s->colour ? 1 : 0;             // (likewise: j40hip_colour_on)
+		// one canvas, one colour space: where the image's frames render in the signalled space, a frame that cannot -- a Modular frame
+		// without the Modular XYB switch -- is refused rather than composed as sRGB among them
+		const bool image_in_force = s->colour && s->im.xyb_encoded && !s->im.cenc.srgb_default() && !j40hip::colour::image_refusal(s->im);
+		if (image_in_force && j40hip_colour_refusal(h)) raise(ERR_UCS);
 	} catch (const DecodeError &e) { code = e.code; }
 	catch (const std::exception &) { code = E4("!mem"); }
 	h->frame.seq_im = nullptr;   // (copied into the frame)
@@ -354,6 +363,57 @@ void j40hip_frame_modular_xyb(const j40hip_frame *h, int32_t out[4]) {
 	if (!h) return;
 	out[0] = j40hip_modular_xyb_applies(h) ? 1 : 0; out[1] = j40hip_modular_xyb_on(h) ? 1 : 0;
 	out[2] = h->frame.fh.is_modular ? (h->frame.wide() ? 4 : 2) : 0; out[3] = h->modular_xyb_used ? 1 : 0;
+}
+
+// ---- the colour mode (include/j40hip.h; colour_space.hpp has the maths) ----
+uint32_t j40hip_frame_set_colour(j40hip_frame *h, int mode) {
+	if (!h) return j40hip::ERR_RNGE;
+	if (mode > 0) {
+		if (uint32_t e = j40hip_colour_refusal(h)) return e;
+		// (in force from here on: what a partial group range refuses the other way round, mode_refusal)
+		if (h->partial_range && h->frame.im.xyb_encoded && !h->frame.im.cenc.srgb_default()) return ERR_UCS;
+	}
+	h->colour = mode < 0 ? -1 : mode > 0 ? 1 : 0;
+	return 0;
+}
+static void colour_encoding_words(const j40hip::ImageMeta &im, int32_t out[16]) {
+	const j40hip::ColourEncoding &ce = im.cenc;
+	out[0] = ce.colour_space; out[1] = ce.white_point; out[2] = ce.white_xy[0]; out[3] = ce.white_xy[1]; out[4] = ce.primaries;
+	for (int c = 0; c < 3; ++c) { out[5 + 2 * c] = ce.prim_xy[c][0]; out[6 + 2 * c] = ce.prim_xy[c][1]; }
+	out[11] = ce.have_gamma ? 1 : 0; out[12] = ce.gamma; out[13] = ce.transfer; out[14] = ce.intent; out[15] = im.want_icc ? 1 : 0;
+}
+void j40hip_frame_colour(const j40hip_frame *h, int32_t out[8]) {
+	if (!out) return;
+	memset(out, 0, sizeof(int32_t) * 8);
+	if (!h) return;
+	const j40hip::ColourEncoding &ce = h->frame.im.cenc;
+	out[0] = j40hip_colour_applies(h) ? 1 : 0; out[1] = j40hip_colour_on(h) ? 1 : 0;
+	out[2] = ce.white_point; out[3] = ce.primaries; out[4] = ce.have_gamma ? -1 : ce.transfer; out[5] = ce.colour_space;
+	out[6] = h->colour_used ? (h->colour_curve_8bit ? 2 : 1) : 0; out[7] = (int32_t) j40hip_colour_refusal(h);
+}
+void j40hip_frame_colour_encoding(const j40hip_frame *h, int32_t out[16]) {
+	if (!out) return;
+	memset(out, 0, sizeof(int32_t) * 16);
+	if (h) colour_encoding_words(h->frame.im, out);
+}
+uint32_t j40hip_colour_gamut_matrix(const int32_t enc[16], double p[9], double lum[3]) {
+	if (!enc || !p || !lum) return j40hip::ERR_RNGE;
+	const j40hip::ColourEncoding ce = j40hip::colour::encoding_from_words(enc);
+	double m[3][3];
+	if (!j40hip::colour::gamut_matrix(ce, m, lum)) return ERR_UCS;
+	for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) p[i * 3 + j] = m[i][j];
+	return 0;
+}
+uint32_t j40hip_colour_table(const int32_t enc[16], float intensity_target, float *out, size_t out_floats, int32_t range[2]) {
+	if (!enc || !out || !range || out_floats < (size_t) j40hip::COLOUR_TABLE_FLOATS || !(intensity_target > 0.0f)) return j40hip::ERR_RNGE;
+	try {
+		const j40hip::ColourEncoding ce = j40hip::colour::encoding_from_words(enc);
+		const double lum[3] = {0.0, 0.0, 0.0};   // (the table is of the curve alone: HLG's OOTF runs in front of it)
+		std::vector<float> table;
+		if (!j40hip::colour::build_table(j40hip::colour::curve_of(ce, intensity_target, lum), &table, &range[0], &range[1])) return ERR_UCS;
+		memcpy(out, table.data(), sizeof(float) * (size_t) j40hip::COLOUR_TABLE_FLOATS);
+	} catch (const std::exception &) { return E4("!mem"); }
+	return 0;
 }
 
 // ---- region decode (include/j40hip.h) ----

@@ -10,6 +10,7 @@ namespace j40hip {
 constexpr uint32_t ERR_URG = E4("Urg?");   // a region (j40hip_frame_set_region) where only whole frames or group ranges are served, or the other way round
 constexpr uint32_t ERR_USC = E4("Usc?");   // a scale (j40hip_frame_set_scale) where only full-size frames are served, or the other way round
 constexpr uint32_t ERR_UOR = E4("Uor?");   // an orientation in force (j40hip_frame_set_orientation) where only stored order is served
+constexpr uint32_t ERR_UCS = colour::ERR_UCS;   // the colour mode (j40hip_frame_set_colour) on an image it does not serve, or in force where only sRGB pixels are served
 constexpr uint32_t ERR_ULF = E4("Ulf?");   // an LF-only frame (J40HIP_PARSE_LF_ONLY) has nothing but its LF image: the full decode's entry points refuse it
 
 // ---- which modes exclude which ----
@@ -25,10 +26,11 @@ inline uint32_t mode_refusal(const j40hip_frame *h, Mode what) {
 	case Mode::Scale:          return h->region_set || h->partial_range || owned ? ERR_USC : 0;
 	// (a partial group range writes its own rectangles of the stored image: nothing whole to turn)
 	case Mode::Orientation:    return owned || (h->partial_range && h->frame.im.orientation != 1) ? ERR_UOR : 0;
-	case Mode::GroupRange:     return h->region_set ? ERR_URG : h->scale > 0 ? ERR_USC : oriented() ? ERR_UOR : 0;
-	case Mode::Batch:          return h->region_set ? ERR_URG : oriented() ? ERR_UOR : 0;   // a batch writes whole frames in stored order, at any one scale
+	// (the colour tail runs over whole pictures: a partial range has none; batches and pipelines render sRGB only)
+	case Mode::GroupRange:     return h->region_set ? ERR_URG : h->scale > 0 ? ERR_USC : oriented() ? ERR_UOR : j40hip_colour_on(h) ? ERR_UCS : 0;
+	case Mode::Batch:          return h->region_set ? ERR_URG : oriented() ? ERR_UOR : j40hip_colour_on(h) ? ERR_UCS : 0;   // a batch writes whole frames in stored order, at any one scale
 	case Mode::Playback:       return h->scale > 0 ? ERR_USC : oriented() ? ERR_UOR : 0;    // the canvas is full size, stored order
-	case Mode::LfPreviewBatch: return oriented() ? ERR_UOR : 0;
+	case Mode::LfPreviewBatch: return oriented() ? ERR_UOR : j40hip_colour_on(h) ? ERR_UCS : 0;
 	}
 	return 0;
 }
@@ -47,11 +49,12 @@ struct DecodeRoute {
 	int32_t stored_w = 0, stored_h = 0, out_w = 0, out_h = 0;   // the stored-order image the decode makes (the region's rectangle, else the frame at its scale shift) and, in the orientation in force, the image written
 	size_t pixel_bytes = 4, min_stride = 0;   // of the image written (a whole u8 frame in stored order: 0, the entry points' old contract)
 	enum Shape { Whole, Region, Scaled } shape = Whole;
-	bool full_size_first = false;      // a region or a scale served from full-size pixels in a staging image: filters in force, merged alpha; at a scale a Modular XYB frame (k_modular_xyb_pack writes full-size pixels only, the mean is of rendered bytes)
+	bool full_size_first = false;      // a region or a scale served from full-size pixels in a staging image: filters in force, merged alpha, the colour mode in force; at a scale a Modular XYB frame (k_modular_xyb_pack writes full-size pixels only, the mean is of rendered bytes)
 	int restoration_asked = 0;         // the restoration mode of a VarDCT plan decoding every group (the filters run over whole frames), whatever the frame signals
 	int restoration = 0;               // ... and in force: where the frame signals filters
 	bool alpha_merged = false;         // the extra channels' sub-images carry an alpha channel that is kept: k_alpha_merge writes it into full-size pixels
 	bool modular_xyb = false;          // a Modular plan through the XYB colour tail
+	bool colour = false;               // the colour mode in force: the XYB planes (filtered where the filters are in force; a Modular XYB plan's by k_modular_to_xyb) go through k_colour_tail
 	bool every_group = true;           // no partial group range
 	bool two_phase = false;            // decode_to_host may try its two phases: a whole frame in stored order that takes no LF frame's picture
 	uint32_t xyb_refusal = 0;          // decode_frame_xyb's answer: "TODO" for what keeps the decode from being three full-size XYB planes
@@ -76,13 +79,15 @@ inline DecodeRoute resolve_route(const j40hip_frame *h, const UploadFacts *up, b
 	r.restoration = signals_filters(fr.fh) ? r.restoration_asked : 0;
 	r.alpha_merged = up->has_trailers && j40hip_alpha_kept(h);
 	r.modular_xyb = up->is_modular && j40hip_modular_xyb_on(h);
-	const bool full_size_only = up->is_modular ? r.modular_xyb && r.shape == DecodeRoute::Scaled : r.restoration || r.alpha_merged;
+	r.colour = j40hip_colour_on(h);
+	const bool full_size_only = r.colour || (up->is_modular ? r.modular_xyb && r.shape == DecodeRoute::Scaled : r.restoration || r.alpha_merged);
 	r.full_size_first = r.shape != DecodeRoute::Whole && full_size_only;
-	r.two_phase = r.shape == DecodeRoute::Whole && r.orientation == 1 && !fr.fh.use_lf_frame;
+	r.two_phase = r.shape == DecodeRoute::Whole && r.orientation == 1 && !fr.fh.use_lf_frame && !r.colour;
 	r.xyb_refusal = r.shape != DecodeRoute::Whole || !r.every_group || (up->is_modular ? !r.modular_xyb : up->ycbcr || up->has_trailers) ? (uint32_t) ERR_TODO : 0;
 	// in the entry points' order: an orientation over a partial range (no whole stored image to turn), the oriented image's rows, a YCbCr plan
 	// (served only while its switch stays on, and whole), the stored image's rows
 	if (r.orientation != 1 && !r.every_group) r.refusal = ERR_UOR;
+	else if (r.colour && !r.every_group) r.refusal = ERR_UCS;   // (a group range set before the mode: mode_refusal's rule)
 	else if (r.orientation != 1 && (!have_out || stride_bytes < r.min_stride)) r.refusal = ERR_RNGE;
 	else if (up->ycbcr && (!j40hip_ycbcr_on(h) || r.shape != DecodeRoute::Whole || !r.every_group)) r.refusal = ERR_TODO;
 	else if (stride_bytes < r.min_stride) r.refusal = ERR_RNGE;

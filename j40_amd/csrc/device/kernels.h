@@ -4,6 +4,7 @@
 #include "plan.h"
 #include "restore_dev.h"
 #include "region_dev.h"
+#include "colour_dev.h"
 
 namespace j40hip {
 
@@ -41,6 +42,10 @@ void launch_epf_sigma(const DevPlan &plan, int32_t num_lf_groups, const int16_t 
 void launch_epf_sigma_cells(const int16_t *sharpness, const float *hfmul_inv, const RestoreParams &p, float *sigma, uint32_t *sharp_or, hipStream_t stream);
 float *launch_restoration(float *xyb, float *tmp, size_t pitch, const RestoreParams &p, bool gab, int32_t epf_iters, const float *sigma, hipStream_t stream);
 void launch_xyb_to_rgba(const float *xyb, size_t pitch, const DevFrame *frame_dev, int32_t width, int32_t height, uint8_t *rgba, size_t stride_bytes, hipStream_t stream, bool rgba16 = false);
+
+// the colour mode's tail (device/colour_kernels.hip, colour_dev.h): k_colour_tail over three planes laid out as launch_xyb_to_rgba's,
+// in the colour space `p` describes; p.table: device memory
+void launch_colour_tail(const float *xyb, size_t pitch, const ColourTailParams &p, int32_t width, int32_t height, uint8_t *out, size_t stride_bytes, hipStream_t stream, bool rgba16 = false);
 
 // LfGroup tail on the device (device/lf_tail_kernels.hip)
 void upload_lf_tail_tables(const float *half_secants, const float *lf2llf, hipStream_t stream);
@@ -107,8 +112,9 @@ struct ModXybConsts;
 void upload_modular_xyb_tables(const float *srgb_thr, hipStream_t stream);
 void launch_modular_xyb_pack(PlanePtr c0, PlanePtr c1, PlanePtr c2, PlanePtr a, int32_t width, int32_t height, const ModXybConsts &k, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
 void launch_modular_xyb_pack_rect(PlanePtr c0, PlanePtr c1, PlanePtr c2, PlanePtr a, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, const ModXybConsts &k, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16 = false);
-// (the known-answer hook's two-kernel route: the A of every pixel of a width x height image from the alpha plane, pack_rgba8 / pack_rgba16's sample)
-void launch_kat_alpha_from_plane(PlanePtr a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16);
+// the A of every pixel of a width x height image from the alpha plane, pack_rgba8 / pack_rgba16's sample, into pixels written opaque:
+// behind k_colour_tail on a Modular XYB frame under the colour mode, and the known-answer hook's two-kernel route
+void launch_alpha_from_plane(PlanePtr a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16);
 void launch_modular_to_xyb(PlanePtr c0, PlanePtr c1, PlanePtr c2, int32_t plane_width, int32_t x0, int32_t y0, int32_t rw, int32_t rh, const ModXybConsts &k, float *x, float *y, float *b, size_t pitch, hipStream_t stream);
 
 // reduced-size decode (device/scale_kernels.hip, scale_dev.h): the full W x H image at src made 1:2 (shift 1) or 1:4 (shift 2) at dst,

@@ -39,7 +39,8 @@ __global__ void __launch_bounds__(256) k_modular_to_xyb(const S *c0, const S *c1
 	modular_to_xyb_lane<S>(c0, c1, c2, r, lx, ly, k.m, out.p, pitch);
 }
 
-// the known-answer hook's two-kernel route: A alone, by the pack kernels' own functions (modular_dev.h)
+// A alone, by the pack kernels' own functions (modular_dev.h), into pixels another kernel has written opaque: behind k_colour_tail on a
+// Modular XYB frame under the colour mode (runtime.hip), and the known-answer hook's two-kernel route
 template <typename S, bool RGBA16>
 __global__ void __launch_bounds__(256) k_kat_alpha_from_plane(const S *a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride_bytes) {
 	const int32_t x = (int32_t) (blockIdx.x * 64 + (threadIdx.x & 63)), y = (int32_t) (blockIdx.y * 4 + (threadIdx.x >> 6));
@@ -48,7 +49,7 @@ __global__ void __launch_bounds__(256) k_kat_alpha_from_plane(const S *a, int32_
 	if constexpr (RGBA16) ((uint16_t *) (rgba + (size_t) y * stride_bytes))[(size_t) x * 4 + 3] = (uint16_t) (pack_rgba16(0, 0, 0, v, bpp) >> 48);
 	else (rgba + (size_t) y * stride_bytes)[(size_t) x * 4 + 3] = (uint8_t) (pack_rgba8(0, 0, 0, v, bpp) >> 24);
 }
-void launch_kat_alpha_from_plane(PlanePtr a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
+void launch_alpha_from_plane(PlanePtr a, int32_t width, int32_t height, int32_t bpp, uint8_t *rgba, size_t stride, hipStream_t stream, bool rgba16) {
 	const dim3 grid((unsigned) ((width + 63) / 64), (unsigned) ((height + 3) / 4));
 	if (a.wide()) {
 		if (rgba16) hipLaunchKernelGGL((k_kat_alpha_from_plane<int32_t, true>), grid, dim3(256), 0, stream, (const int32_t *) a.p, width, height, bpp, rgba, stride);

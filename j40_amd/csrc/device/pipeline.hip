@@ -198,6 +198,7 @@ uint32_t decode_single(j40hip_pipeline *p, Job *j, hipStream_t s) {
 	j40hip_frame *fr = j40hip_frame_parse_ex(j->buf, j->size, 1, 1u, &err);
 	if (!fr) return err ? err : E_MEM;
 	(void) j40hip_frame_set_orientation(fr, 0);   // a pipeline writes stored order, whatever J40HIP_ORIENT says
+	(void) j40hip_frame_set_colour(fr, 0);        // ... and sRGB, whatever J40HIP_COLOUR says
 	int64_t info[21];
 	j40hip_frame_info(fr, info);
 	const int32_t shift = p->scale.load();

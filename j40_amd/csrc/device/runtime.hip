@@ -6,6 +6,7 @@
 #include "hostcopy.hpp"
 #include "ycbcr_dev.h"
 #include "orient_dev.h"
+#include <map>
 
 // a Modular frame's groups can be decoded apart from each other when every group has a section of its own and no frame-wide inverse
 // transform reads across groups (j40hip_frame_set_group_range's rule; a region is otherwise widened to every group)
@@ -17,7 +18,65 @@ bool j40hip_rt::modular_groups_independent(const j40hip_frame *h) {
 }
 
 // what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it
-static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->wide_used = false; h->modular_xyb_used = false; h->modular_xyb_whole = false; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
+static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->wide_used = false; h->modular_xyb_used = false; h->modular_xyb_whole = false; h->colour_used = false; h->colour_curve_8bit = false; h->dev->colour_planes = nullptr; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
+
+// ---- the colour mode (j40hip_frame_set_colour; colour_space.hpp, device/colour_dev.h, colour_kernels.hip) ----
+// The threshold tables of 8-bit frames, one per distinct (curve, exponent, intensity_target): built once per process by bisection over
+// the floats (a few milliseconds), never dropped -- the copies to the devices read them
+struct ColourTableKey { int32_t tf; double g; float it; bool operator<(const ColourTableKey &o) const { return tf != o.tf ? tf < o.tf : g != o.g ? g < o.g : it < o.it; } };
+struct ColourTableEntry { bool usable = false; std::vector<float> table; int32_t blo = 0, bhi = 0; };
+static const ColourTableEntry &colour_table_of(const ColourCurve &k, float intensity_target) {
+	static std::mutex m;
+	static std::map<ColourTableKey, ColourTableEntry> cache;
+	const bool keyed_it = k.tf == CTF_PQ;   // (the only curve whose levels depend on intensity_target; HLG's OOTF runs in front of its table)
+	const ColourTableKey key = {k.tf, k.tf == CTF_GAMMA ? k.g : 0.0, keyed_it ? intensity_target : 0.0f};
+	std::lock_guard<std::mutex> lock(m);
+	auto it = cache.find(key);
+	if (it != cache.end()) return it->second;
+	ColourTableEntry e;
+	e.usable = colour::build_table(k, &e.table, &e.blo, &e.bhi);
+	return cache.emplace(key, std::move(e)).first->second;
+}
+// the tail's parameters of this frame, made at the first decode that takes it
+static uint32_t colour_params(j40hip_frame *h, hipStream_t s, const ColourTailParams **out) {
+	j40hip_device_state *st = h->dev;
+	if (!st->colour.ready) {
+		ColourTailParams p;
+		memset(&p, 0, sizeof p);
+		if (!colour::tail_consts(h->frame.im, &p.cc, &p.curve)) return ERR_UCS;   // (cannot happen: the route is in force only where the setter would pass)
+		// (the linear curve needs no power: evaluating it is faster than staging its table)
+		if (h->frame.im.bpp == 8 && p.curve.tf != CTF_LINEAR) {
+			const ColourTableEntry &e = colour_table_of(p.curve, h->frame.im.intensity_target);
+			if (e.usable) {
+				bool ok = true;
+				p.table = st->upload(e.table.data(), e.table.size(), s, ok);
+				if (!ok) return ERR_MEM;
+				p.blo = e.blo; p.bhi = e.bhi; p.table_floats = COLOUR_THRESHOLDS + (e.bhi - e.blo + 1 + 3) / 4;
+			}
+		}
+		st->colour.p = p; st->colour.ready = true;
+	}
+	*out = &st->colour.p;
+	return 0;
+}
+static bool fh_bpp8_without_table(const j40hip_frame *h, const ColourTailParams &p) { return h->frame.im.bpp == 8 && !p.table; }
+// k_colour_tail over `planes` (width x height floats each, one behind the other) into the caller's image
+static uint32_t colour_pixels(j40hip_frame *h, const float *planes, uint8_t *img, size_t stride_bytes, hipStream_t s) {
+	const ColourTailParams *p = nullptr;
+	if (uint32_t e = colour_params(h, s, &p)) return e;
+	const FrameHeader &fh = h->frame.fh;
+	launch_colour_tail(planes, (size_t) fh.width, *p, fh.width, fh.height, img, stride_bytes, s, out16(h));
+	h->colour_used = true; h->dev->colour_planes = planes;
+	h->colour_curve_8bit = fh_bpp8_without_table(h, *p);   // (an 8-bit frame whose curve has no table: j40hip_frame_colour says so)
+	return 0;
+}
+// where the tail's input goes when the restoration filters' buffers do not exist: three planes of the frame's size, kept with the frame
+static float *colour_plane_buffer(j40hip_device_state *st, const FrameHeader &fh) {
+	if (st->d_xyb) return st->d_xyb;
+	bool ok = true;
+	if (!st->d_colour_xyb) st->d_colour_xyb = st->scratch<float>(3 * (size_t) fh.width * (size_t) fh.height, ok);
+	return ok ? st->d_colour_xyb : (st->d_colour_xyb = nullptr);
+}
 
 // region (j40hip_frame_set_region): null, or the rectangle {x0, y0, w, h} that becomes the w x h pixels at rgba_dev -- the sections of
 // its cover only (LfGlobal's too), one launch per row of the cover's groups and pass, the frame-wide per-pixel transforms over the
@@ -37,6 +96,8 @@ static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *
 	const bool xyb = route.modular_xyb && st->final_planes.size() >= 3;
 	h->modular_xyb_used = xyb;
 	if ((xyb_out && !xyb) || (xyb && shift > 0)) return ERR_TODO;
+	const bool colour = route.colour && xyb && !xyb_out;   // (whole frames: the route stages a region or a scale)
+	if (colour && (region || shift > 0 || !route.every_group)) return ERR_TODO;
 	RegionCover cover = {0, 0, 0, 0, 0, 0};
 	bool covered = false;   // only the cover's groups are decoded
 	if (region) {
@@ -99,6 +160,14 @@ static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *
 		int32_t rects[3][4];
 		const int nr = group_range_rects(g0, gn, fr.fh.width, fr.fh.height, fr.fh.group_size_shift, rects);
 		for (int k = 0; k < nr; ++k) pack_rect(rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], (uint8_t *) rgba_dev);
+	} else if (colour) {
+		// the colour mode: the float planes, k_colour_tail over them (A opaque), A from its plane as the pack kernels render it
+		float *d = colour_plane_buffer(st, fr.fh);
+		if (!d) return ERR_MEM;
+		const size_t plane = (size_t) fr.fh.width * (size_t) fr.fh.height;
+		launch_modular_to_xyb(st->final_planes[0], st->final_planes[1], st->final_planes[2], fr.fh.width, 0, 0, fr.fh.width, fr.fh.height, xk, d, d + plane, d + 2 * plane, (size_t) fr.fh.width, s);
+		if (uint32_t e = colour_pixels(h, d, (uint8_t *) rgba_dev, stride_bytes, s)) return e;
+		if (alpha.p) launch_alpha_from_plane(alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	} else if (xyb) launch_modular_xyb_pack(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, xk, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	else launch_pack_planes(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h), shift);
 	marks.mark(3);
@@ -323,7 +392,17 @@ static uint32_t ycbcr_pixels(j40hip_frame *h, const int32_t *class_start, const 
 	return 0;
 }
 
-static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t stride_bytes, int mode, hipStream_t s) {
+// the colour mode without the filters: the pixel kernels leave the samples in XYB planes, k_colour_tail follows -- one pass more over three
+// float planes than the fused tail, the route the restoration filters already take
+static uint32_t colour_unfiltered(j40hip_frame *h, const int32_t *class_start, const DevVarblock *list, uint8_t *img, size_t stride_bytes, hipStream_t s) {
+	j40hip_device_state *st = h->dev;
+	float *d = colour_plane_buffer(st, h->frame.fh);
+	if (!d) return ERR_MEM;
+	launch_vardct_frame(st->plan, class_start, list, st->d_large_scratch, K2Target{d, (size_t) h->frame.fh.width * 4, OutMode::XYB, 0}, s);
+	return colour_pixels(h, d, img, stride_bytes, s);
+}
+
+static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t stride_bytes, int mode, hipStream_t s, bool colour = false) {
 	j40hip_device_state *st = h->dev;
 	const Frame &fr = h->frame;
 	const FrameHeader::Restoration &r = fr.fh.restoration;
@@ -348,6 +427,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 		st->restore_err = perr;
 		if (!rgba_dev) return 0;   // (planes are wanted, not pixels -- run_vardct's xyb_out: the caller makes the unfiltered ones)
 		if (st->ycbcr) return ycbcr_pixels(h, st->class_start, st->d_vb_sorted, rgba_dev, stride_bytes, s);
+		if (colour) return colour_unfiltered(h, st->class_start, st->d_vb_sorted, rgba_dev, stride_bytes, s);
 		launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{rgba_dev, stride_bytes, out_mode(h), 0}, s);
 		return 0;
 	}
@@ -370,6 +450,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	marks.mark(1);
 	if (!rgba_dev) {}   // (planes are wanted, not pixels: d_restored is the result)
 	else if (st->ycbcr) ycbcr_tail_444(h, st->d_restored, (size_t) W, rgba_dev, stride_bytes, s);   // (the filtered planes are Cb, Y, Cr)
+	else if (colour) { if (uint32_t e = colour_pixels(h, st->d_restored, rgba_dev, stride_bytes, s)) return e; }
 	else launch_xyb_to_rgba(st->d_restored, (size_t) W, st->plan.frame, W, H, rgba_dev, stride_bytes, s, out16(h));
 	st->restore_ran = mode;
 	if (marks.ev && hipEventSynchronize(pair.ev[1]) == hipSuccess) (void) hipEventElapsedTime(&st->restore_ms, pair.ev[0], pair.ev[1]);
@@ -379,7 +460,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 // One VarDCT decode as decode_impl (whole frames, group ranges), decode_region (covers), decode_scaled and decode_frame_xyb describe it to
 // run_vardct; as it stands, the whole frame from the frame's own lists, with nothing to write to yet
 struct VardctRun {
-	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged) {}
+	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged), colour(r.colour) {}
 	int32_t first_group = 0, num_groups; // the groups of the entropy launch ...
 	const RegionCover *cover = nullptr;  // ... or (not null) a region's cover: through the fast kernel's order list (region.d_order), else a launch per row of its groups
 	const DevVarblock *list; const int32_t *class_start;   // what the pixel kernels take
@@ -387,6 +468,7 @@ struct VardctRun {
 	bool whole = true;                   // every group is decoded: the extra channels' sub-images can be validated
 	int restoration;                     // the route's: the mode the restoration filters run in (0: they do not; never where `whole` is false)
 	bool alpha_merged;                   // the route's
+	bool colour;                         // the route's: the pixels come from k_colour_tail (whole frames at full size: the route stages everything else)
 	const uint8_t *crop_from = nullptr; uint8_t *crop_to = nullptr; size_t crop_stride = 0; int32_t crop_w = 0, crop_h = 0;   // crop_to not null: these pixels of img are then moved there
 	int32_t shift = 0;                   // the scale shift the pixel kernels write at (decode_scaled's fused route: img is the small image)
 	float *xyb_out = nullptr;            // not null (an LF frame of a sequence, decode_frame_xyb): no pixels, img is null -- the three XYB planes, width * height
@@ -444,7 +526,10 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 	if (rmode) {
 		// the restoration filters asked for and signalled: the pixel kernels leave the samples in XYB planes, Gaborish and the
 		// edge-preserving filter run over the whole picture, the colour tail follows on the filtered planes (restore_kernels.h)
-		if (uint32_t e = decode_restored(h, run.img, run.img_stride, rmode, s)) return e;
+		if (uint32_t e = decode_restored(h, run.img, run.img_stride, rmode, s, run.colour)) return e;
+	} else if (run.colour) {
+		if (!run.whole || run.shift || run.cover) return ERR_TODO;   // (cannot happen: full_size_first)
+		if (uint32_t e = colour_unfiltered(h, run.class_start, run.list, run.img, run.img_stride, s)) return e;
 	} else if (st->ycbcr) {
 		if (uint32_t e = ycbcr_pixels(h, run.class_start, run.list, run.img, run.img_stride, s)) return e;
 	} else launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, K2Target{run.img, run.img_stride, out_mode(h), run.shift}, s);
@@ -560,7 +645,7 @@ static uint32_t decode_region(j40hip_frame *h, const DecodeRoute &route, void *r
 	const int32_t x0 = h->region[0], y0 = h->region[1], w = h->region[2], hh = h->region[3];
 	const size_t pb = route.pixel_bytes;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
-	if (st->is_modular) return decode_modular(h, route, rgba_dev, stride_bytes, s, ms3, h->region);
+	if (st->is_modular && !route.full_size_first) return decode_modular(h, route, rgba_dev, stride_bytes, s, ms3, h->region);   // (staged: a Modular XYB frame under the colour mode)
 	const int32_t W = fr.fh.width, H = fr.fh.height, shift = fr.fh.group_size_shift;
 	const RegionCover cover = region_cover(x0, y0, w, hh, shift, fr.fh.gcolumns);
 	const int32_t ncover = region_cover_groups(cover);

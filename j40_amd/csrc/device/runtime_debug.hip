@@ -83,6 +83,11 @@ static uint32_t read_modular_xyb(j40hip_frame *h, float *out) {
 }
 extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out) {
 	if (h && h->dev && h->dev->is_modular && stage == 0 && h->modular_xyb_used && j40hip_modular_xyb_on(h)) return guarded([&] { return read_modular_xyb(h, out); });
+	// (the colour mode without the filters: the planes the last decode's k_colour_tail read, stages 0 and 1 alike)
+	if (h && h->dev && !h->dev->restore_ran && h->colour_used && h->dev->colour_planes && (stage == 0 || stage == 1) && out) {
+		if (hipSetDevice(h->dev->device) != hipSuccess) return ERR_GPU;
+		return hipMemcpy(out, h->dev->colour_planes, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+	}
 	if (!h || !h->dev || !h->dev->restore_ran || !h->dev->d_xyb) return ERR_RNGE;
 	j40hip_device_state *st = h->dev;
 	const FrameHeader &fh = h->frame.fh;
@@ -138,13 +143,37 @@ extern "C" uint32_t j40hip_kat_device_modular_xyb(const void *const planes_dev[3
 		DevFrame *d_frame = tmp.upload(&df, 1, s, ok);
 		if (ok) {
 			launch_xyb_to_rgba(xyb_dev, (size_t) width, d_frame, width, height, (uint8_t *) two_kernel_dev, stride_bytes, s, pb == 8);
-			if (alpha_dev) launch_kat_alpha_from_plane(pp(alpha_dev), width, height, bpp, (uint8_t *) two_kernel_dev, stride_bytes, s, pb == 8);
+			if (alpha_dev) launch_alpha_from_plane(pp(alpha_dev), width, height, bpp, (uint8_t *) two_kernel_dev, stride_bytes, s, pb == 8);
 			ok = hipGetLastError() == hipSuccess;
 		}
 		if (hipStreamSynchronize(s) != hipSuccess) ok = false;   // (df and the uploaded copy live until here)
 		for (auto &b : tmp.buffers) b.release();
 		tmp.buffers.clear();
 		return ok ? 0 : ERR_GPU;
+	});
+}
+// known-answer / measuring hook: k_colour_tail on caller-supplied planes, enqueued and not waited for (include/j40hip.h)
+extern "C" uint32_t j40hip_kat_device_colour_tail(const float *xyb_dev, int32_t width, int32_t height, const float colour_consts[15], const int32_t enc[16], const float lum[3],
+		int32_t bpp, const float *table_dev, const int32_t table_range[2], int32_t format, void *out_dev, size_t stride_bytes, void *stream) {
+	return guarded([&]() -> uint32_t {
+		if (format != J40HIP_U8X4 && format != J40HIP_U16X4) return ERR4('U', 'f', 'm', '?');
+		const size_t pb = format == J40HIP_U16X4 ? 8 : 4;
+		if (!xyb_dev || !colour_consts || !enc || !lum || !out_dev || width <= 0 || height <= 0 || width > (1 << 18) || height > (1 << 18) || bpp < 8 || bpp > 16) return ERR_RNGE;
+		if (stride_bytes < pb * (size_t) width || stride_bytes % pb || (uintptr_t) out_dev % pb || (uintptr_t) xyb_dev % 4 || !(colour_consts[12] > 0.0f)) return ERR_RNGE;
+		if (table_dev && (bpp != 8 || !table_range || table_range[0] < 0 || table_range[1] < table_range[0] || table_range[1] - table_range[0] + 1 > COLOUR_BUCKETS_MAX || (uintptr_t) table_dev % 4)) return ERR_RNGE;
+		const ColourEncoding ce = colour::encoding_from_words(enc);
+		if (!ce.have_gamma && ce.transfer != 1 && ce.transfer != 8 && ce.transfer != 13 && ce.transfer != 16 && ce.transfer != 17 && ce.transfer != 18) return ERR_UCS;
+		if (ce.have_gamma && (ce.gamma <= 0 || ce.gamma > 10000000)) return ERR_UCS;
+		ModXybConsts k; DevFrame df;
+		kat_colour_consts(nullptr, colour_consts, bpp, &k, &df);
+		ColourTailParams p;
+		memset(&p, 0, sizeof p);
+		p.cc = k.cc;
+		const double lumd[3] = {lum[0], lum[1], lum[2]};
+		p.curve = colour::curve_of(ce, colour_consts[12], lumd);
+		if (table_dev) { p.table = table_dev; p.blo = table_range[0]; p.bhi = table_range[1]; p.table_floats = COLOUR_THRESHOLDS + (p.bhi - p.blo + 1 + 3) / 4; }
+		launch_colour_tail(xyb_dev, (size_t) width, p, width, height, (uint8_t *) out_dev, stride_bytes, (hipStream_t) stream, pb == 8);
+		return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 	});
 }
 // measuring hooks (tools/modxyb_probe.py; include/j40hip.h)

@@ -135,7 +135,7 @@ static uint32_t lfp_launch(j40hip_frame *const *frames, int64_t n, void *const *
 }
 
 extern "C" uint32_t j40hip_frames_decode_lf(j40hip_frame *const *frames, int64_t n, void *const *rgba_dev, const size_t *stride_bytes, void *stream) {
-	// many previews in one launch are written in stored order: a member whose orientation is in force is refused before anything is launched
+	// many previews in one launch are written in stored order and as sRGB: a member whose orientation or colour mode is in force is refused before anything is launched
 	for (int64_t i = 0; frames && i < n; ++i) if (frames[i]) if (uint32_t e = mode_refusal(frames[i], Mode::LfPreviewBatch)) return e;
 	return guarded([&] { return lfp_launch(frames, n, rgba_dev, stride_bytes, (hipStream_t) stream, false, 0); });
 }
@@ -145,6 +145,7 @@ extern "C" uint32_t j40hip_frames_decode_lf(j40hip_frame *const *frames, int64_t
 static uint32_t lfp_one(j40hip_frame *h, void *rgba_dev, size_t stride_bytes, hipStream_t s) {
 	if (!h || !h->dev) return ERR_GPU;
 	if (h->frame.fh.use_lf_frame) return ERR_TODO;   // (it holds no LF integers: the LF frame's own handle decodes that picture)
+	if (j40hip_colour_on(h)) return ERR_UCS;   // the preview's tail renders sRGB: refused while the colour mode is in force (the float planes, j40hip_frame_read_lf, are not its business)
 	h->orient_applied = 0; h->orient_staging_bytes = 0;
 	const int32_t o = j40hip_orientation_in_force(h);
 	if (o == 1) return lfp_launch(&h, 1, &rgba_dev, &stride_bytes, s, false, 0);

@@ -17,6 +17,7 @@
 #include "../mod_layout.hpp"
 #include "kernels.h"
 #include "modular_xyb_dev.h"
+#include "colour_dev.h"
 #include "runtime_shared.hpp"
 
 using namespace j40hip;      // (an internal header: every unit that includes it is written in these two namespaces)
@@ -187,6 +188,13 @@ struct j40hip_device_state {
 	uint32_t restore_err = 0;            // the last decode's "gab0" / "epf0" / "shrp" (reported behind the sections' codes)
 	int restore_ran = 0;                 // the mode the last decode ran the filters in (0: it did not)
 	float restore_ms = 0;
+	// the colour mode (j40hip_frame_set_colour; runtime.hip: colour_pixels). colour: the tail's parameters and, for an 8-bit frame, its
+	// threshold table in device memory, made at the first decode that takes the tail, kept with the frame. d_colour_xyb: the planes the
+	// pixel kernels (or k_modular_to_xyb) leave for it where the restoration filters' buffers do not exist. colour_planes: what the last
+	// decode's tail read (j40hip_frame_read_xyb)
+	struct ColourTail { bool ready = false; ColourTailParams p; } colour;
+	float *d_colour_xyb = nullptr;
+	const float *colour_planes = nullptr;
 	// a YCbCr frame (j40hip_frame_set_ycbcr; runtime.hip: ycbcr_pixels). ycbcr: the plan was built for one (the switch was on at upload).
 	// d_ycc: the planes the pixel kernels leave for k_ycbcr_tail, made at the first decode, kept with the frame. ycc_read: what the last
 	// decode's tail read (j40hip_frame_read_ycbcr) -- those planes, or the restoration filters' result

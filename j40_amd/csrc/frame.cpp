@@ -141,9 +141,25 @@ static void read_extensions(BitReader &br) {  // j40.h:3088
 	br.skip_bits_like_reference(nbits);
 }
 
-static void read_customxy(BitReader &br) {
-	(void) br.u32(0, 19, 0x80000, 19, 0x100000, 20, 0x200000, 21);
-	(void) br.u32(0, 19, 0x80000, 19, 0x100000, 20, 0x200000, 21);
+// a CustomXY: two values of 1e-6 each, stored sign-folded (the sign in bit 0)
+static void read_customxy(BitReader &br, int32_t xy[2]) {
+	for (int i = 0; i < 2; ++i) {
+		const uint32_t u = (uint32_t) br.u32(0, 19, 0x80000, 19, 0x100000, 20, 0x200000, 21);
+		xy[i] = (int32_t) (u >> 1) ^ -(int32_t) (u & 1);
+	}
+}
+// the chromaticities the white point and primaries enums stand for (BT.709 / sRGB, BT.2100, SMPTE 431 / 428; 1e-6 each)
+static void enum_white_xy(int32_t wp, int32_t xy[2]) {
+	static const int32_t D65[2] = {312700, 329000}, E[2] = {333333, 333333}, DCI[2] = {314000, 351000};
+	const int32_t *s = wp == 10 ? E : wp == 11 ? DCI : D65;
+	xy[0] = s[0]; xy[1] = s[1];
+}
+static void enum_primaries_xy(int32_t pr, int32_t xy[3][2]) {
+	static const int32_t SRGB[3][2] = {{640000, 330000}, {300000, 600000}, {150000, 60000}};
+	static const int32_t BT2100[3][2] = {{708000, 292000}, {170000, 797000}, {131000, 46000}};
+	static const int32_t P3[3][2] = {{680000, 320000}, {265000, 690000}, {150000, 60000}};
+	const int32_t (*s)[2] = pr == 9 ? BT2100 : pr == 11 ? P3 : SRGB;
+	for (int i = 0; i < 3; ++i) { xy[i][0] = s[i][0]; xy[i][1] = s[i][1]; }
 }
 
 static void read_image_metadata(BitReader &br, ImageMeta *im, bool allow_wide) {  // j40.h:3104
@@ -208,27 +224,34 @@ static void read_image_metadata(BitReader &br, ImageMeta *im, bool allow_wide) {
 			int32_t cspace = br.enum_();
 			J40HIP_SHOULD(cspace <= 3, "csp?");
 			im->grey = cspace == 1;
+			ColourEncoding &ce = im->cenc;
+			ce.colour_space = cspace;
 			if (!im->want_icc) {
 				if (cspace != 2) {
 					int32_t wp = br.enum_();
 					J40HIP_SHOULD(wp == 1 || wp == 2 || wp == 10 || wp == 11, "wpt?");
-					if (wp == 2) read_customxy(br);
+					ce.white_point = wp;
+					if (wp == 2) read_customxy(br, ce.white_xy); else enum_white_xy(wp, ce.white_xy);
 					if (cspace != 1) {
 						int32_t pr = br.enum_();
 						J40HIP_SHOULD(pr == 1 || pr == 2 || pr == 9 || pr == 11, "prm?");
-						if (pr == 2) { read_customxy(br); read_customxy(br); read_customxy(br); }
+						ce.primaries = pr;
+						if (pr == 2) { for (int i = 0; i < 3; ++i) read_customxy(br, ce.prim_xy[i]); } else enum_primaries_xy(pr, ce.prim_xy);
 					}
 				}
 				if (br.u(1)) {
 					int32_t gamma = (int32_t) br.u(24);
 					J40HIP_SHOULD(gamma > 0 && gamma <= 10000000, "gama");
 					if (cspace == 2) J40HIP_SHOULD(gamma == 3333333, "gama");
+					ce.have_gamma = true; ce.gamma = gamma;
 				} else {
 					int32_t tf = br.enum_();
 					J40HIP_SHOULD(tf == 1 || tf == 2 || tf == 8 || tf == 13 || tf == 16 || tf == 17 || tf == 18, "tfn?");
+					ce.transfer = tf;
 				}
 				int32_t intent = br.enum_();
 				J40HIP_SHOULD(intent <= 3, "itt?");
+				ce.intent = intent;
 			}
 		}
 		if (extra_fields) {

@@ -30,7 +30,29 @@ inline bool ycbcr_env() { static const bool v = [] { const char *e = env_str("J4
 struct ExtraChannel { int32_t type = 0, bpp = 8, exp_bits = 0, dim_shift = 0; bool alpha_associated = false; };
 enum { EC_ALPHA = 0, EC_SPOT = 2, EC_BLACK = 4, EC_CFA = 5 };
 
+// J40HIP_COLOUR=1: XYB images are rendered in the colour space their header signals where j40hip_frame_set_colour(f, 1) would be taken (include/j40hip.h); read once
+inline bool colour_env() { static const bool v = [] { const char *e = env_str("J40HIP_COLOUR"); return e && atoi(e) > 0; }(); return v; }
+
+// ColourEncoding as the stream states it (the defaults: what all_default means -- RGB, D65, sRGB primaries, sRGB transfer, relative intent).
+// The reference reads it and drops it; the colour mode (j40hip_frame_set_colour, colour_space.hpp) renders XYB images by it. Custom xy:
+// the stream's integers, 1e6 to the unit; filled in for the enums too
+struct ColourEncoding {
+	int32_t colour_space = 0;                  // 0 RGB, 1 grey, 2 XYB, 3 unknown
+	int32_t white_point = 1;                   // 1 D65, 2 custom, 10 E, 11 DCI
+	int32_t white_xy[2] = {312700, 329000};
+	int32_t primaries = 1;                     // 1 sRGB, 2 custom, 9 BT.2100, 11 P3
+	int32_t prim_xy[3][2] = {{640000, 330000}, {300000, 600000}, {150000, 60000}};
+	bool have_gamma = false;
+	int32_t gamma = 0;                         // with have_gamma: the exponent times 1e7
+	int32_t transfer = 13;                     // else: 1 BT.709, 2 unknown, 8 linear, 13 sRGB, 16 PQ, 17 DCI, 18 HLG
+	int32_t intent = 1;
+	bool srgb_default() const {   // what today's tail renders: nothing for the colour mode to do
+		return colour_space == 0 && white_point == 1 && primaries == 1 && !have_gamma && transfer == 13;
+	}
+};
+
 struct ImageMeta {
+	ColourEncoding cenc;
 	int32_t width = 0, height = 0;
 	int32_t bpp = 8, exp_bits = 0;
 	int32_t orientation = 1;   // 1..8, the EXIF numbering (the stream holds orientation - 1 in its extra fields; 1 where it has none)

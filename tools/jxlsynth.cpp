@@ -110,6 +110,38 @@ static std::vector<uint32_t> g_tone;
 // f16 holds exactly, or `h` and four hex digits: the f16's bits as they are (h7c00: an infinity, which decoders refuse as well)
 static std::vector<uint32_t> g_opsin;
 static int g_cw_mask = 0;
+// cenc=1 and its family (every mode): ColourEncoding written out instead of all_default -- RGB, no ICC profile, then white=N (1 D65, 2 custom
+// with whitexy=X,Y, 10 E, 11 DCI), primaries=N (1 sRGB, 2 custom with primxy=RX,RY,GX,GY,BX,BY, 9 BT.2100, 11 P3), gamma=G (have_gamma, G in
+// units of 1e-7) or tf=N (1 BT.709, 2 unknown, 8 linear, 13 sRGB, 16 PQ, 17 DCI, 18 HLG), intent=N. The xy values are integers of 1e-6. Any
+// of the family implies cenc=1. Nothing else of the stream changes: the coefficients are those of the stream without it.
+static struct { bool set = false; int white = 1, primaries = 1, tf = 13, gamma = 0, intent = 1; int whitexy[2] = {312700, 329000}; int primxy[6] = {640000, 330000, 300000, 600000, 150000, 60000}; } g_cenc;
+static void put_enum(BitWriter &cs, int v) {   // Enum: U32(0, 1, 2 + u(4), 18 + u(6))
+	if (v < 2) cs.put((uint64_t) v, 2);
+	else if (v < 18) { cs.put(2, 2); cs.put((uint64_t) (v - 2), 4); }
+	else { cs.put(3, 2); cs.put((uint64_t) (v - 18), 6); }
+}
+static void put_customxy_value(BitWriter &cs, int v) {   // U32(u(19), 0x80000 + u(19), 0x100000 + u(20), 0x200000 + u(21)) of the sign-folded value
+	const uint32_t u = v >= 0 ? (uint32_t) v << 1 : ((uint32_t) (-(int64_t) v) << 1) - 1;
+	if (u < 0x80000u) { cs.put(0, 2); cs.put(u, 19); }
+	else if (u < 0x100000u) { cs.put(1, 2); cs.put(u - 0x80000u, 19); }
+	else if (u < 0x200000u) { cs.put(2, 2); cs.put(u - 0x100000u, 20); }
+	else { if (u - 0x200000u >= (1u << 21)) die("cenc: xy value out of range"); cs.put(3, 2); cs.put(u - 0x200000u, 21); }
+}
+// ColourEncoding as cenc= states it; false (and nothing written): the option was not given, the caller writes its own
+static bool write_colour_encoding(BitWriter &cs) {
+	if (!g_cenc.set) return false;
+	cs.put(0, 1); cs.put(0, 1);         // not all_default, no ICC profile
+	put_enum(cs, 0);                    // colour_space = RGB
+	put_enum(cs, g_cenc.white);
+	if (g_cenc.white == 2) for (int v : g_cenc.whitexy) put_customxy_value(cs, v);
+	put_enum(cs, g_cenc.primaries);
+	if (g_cenc.primaries == 2) for (int v : g_cenc.primxy) put_customxy_value(cs, v);
+	if (g_cenc.gamma) { cs.put(1, 1); cs.put((uint64_t) g_cenc.gamma, 24); }
+	else { cs.put(0, 1); put_enum(cs, g_cenc.tf); }
+	put_enum(cs, g_cenc.intent);
+	return true;
+}
+
 // ImageMetadata.extra_fields (j40.h:3147-3163): 0, or for an animation: orientation 1, no intrinsic size, no preview, the animation
 // header (tps 10 / 1, loops 0, no timecodes); with orientation=N: extra fields with that orientation (and, outside an animation,
 // nothing else)
@@ -1371,9 +1403,9 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			cs.put((uint64_t) (alpha_assoc ? 1 : 0), 1);   // alpha_associated (j40.h:3188)
 		}
 		cs.put(noxyb ? 0 : 1, 1);           // xyb_encoded
-		cs.put(1, 1);                       // ColourEncoding.all_default
+		if (!write_colour_encoding(cs)) cs.put(1, 1);   // ColourEncoding.all_default (cenc=: written out)
 		write_header_tail(cs, true, !noxyb);
-	} else if (img_bpp != 8 || (seq_anim && !with_alpha) || (noxyb && !with_alpha) || ((g_orientation || !g_tone.empty()) && !with_alpha && !icc_bytes)) {   // (orientation=N, tone=: the metadata written out where it would be all_default)
+	} else if ((g_cenc.set && !with_alpha && !icc_bytes) || img_bpp != 8 || (seq_anim && !with_alpha) || (noxyb && !with_alpha) || ((g_orientation || !g_tone.empty()) && !with_alpha && !icc_bytes)) {   // (orientation=N, tone=: the metadata written out where it would be all_default)
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
 		write_bit_depth(cs, img_bpp);
@@ -1390,7 +1422,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 			cs.put(2, 2); cs.put(11, 4);    // transfer function 13 (sRGB): enum selector 2, 2 + 11
 			cs.put(1, 2);                   // rendering intent 1
 		} else
-		cs.put(1, 1);                       // ColourEncoding.all_default
+		if (!write_colour_encoding(cs)) cs.put(1, 1);   // ColourEncoding.all_default (cenc=: written out)
 		write_header_tail(cs, true, !noxyb);
 	} else if (!icc_bytes && !with_alpha) {
 		cs.put(1, 1);   // ImageMetadata.all_default: 8-bit, XYB, no extra channels
@@ -1402,7 +1434,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(vd_wide ? 0 : 1, 1);         // modular_16bit_buffers (wide=1: 0)
 		cs.put(1, 2); cs.put(1, 1);         // one extra channel, d_alpha
 		cs.put(noxyb ? 0 : 1, 1);           // xyb_encoded (noxyb=1: the reference runs the XYB inverse on VarDCT frames regardless, j40.h:7206)
-		cs.put(1, 1);                       // ColourEncoding.all_default
+		if (!write_colour_encoding(cs)) cs.put(1, 1);   // ColourEncoding.all_default (cenc=: written out)
 		write_header_tail(cs, true, !noxyb);
 	} else {
 		cs.put(0, 1);                       // ImageMetadata: not all_default
@@ -2216,7 +2248,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 		cs.put(2, 2); cs.put(11, 4);    // transfer function 13 (sRGB): enum selector 2, 2 + 11
 		cs.put(1, 2);                   // rendering intent 1
 	} else
-	if (!icc_bytes) cs.put(1, 1);       // ColourEncoding.all_default (sRGB)
+	if (!icc_bytes) { if (!write_colour_encoding(cs)) cs.put(1, 1); }   // ColourEncoding.all_default (sRGB; cenc=: written out)
 	else { cs.put(0, 1); cs.put(1, 1); cs.put(0, 2); }   // want_icc, colour_space = RGB
 	write_header_tail(cs, true, opt.geti("xyb", 0) != 0);   // (tone= / opsin=: with xyb=1 only, main() sees to it)
 	if (icc_bytes) write_icc_stream(cs, rng, icc_bytes);
@@ -2544,6 +2576,25 @@ int main(int argc, char **argv) {
 		g_orientation = opt.geti("orientation", 0);
 		if (g_orientation < 1 || g_orientation > 8) die("orientation=1..8");
 		opt.kv.erase("orientation");
+	}
+	{   // the cenc= family
+		static const char *const CENC_KEYS[] = {"cenc", "white", "primaries", "tf", "gamma", "intent", "whitexy", "primxy"};
+		for (const char *k : CENC_KEYS) g_cenc.set = g_cenc.set || opt.kv.count(k);
+		if (opt.kv.count("cenc") && !opt.geti("cenc", 0)) g_cenc.set = false;
+		auto ints = [&](const char *k, int *out, size_t n) {
+			const std::string v = opt.gets(k, "");
+			size_t at = 0, got = 0;
+			while (at < v.size() && got < n) { size_t e = v.find(',', at); if (e == std::string::npos) e = v.size(); out[got++] = atoi(v.substr(at, e - at).c_str()); at = e + 1; }
+			if (got != n) die("cenc: whitexy= wants 2 values, primxy= 6");
+		};
+		g_cenc.white = opt.geti("white", 1); g_cenc.primaries = opt.geti("primaries", 1); g_cenc.tf = opt.geti("tf", 13);
+		g_cenc.gamma = opt.geti("gamma", 0); g_cenc.intent = opt.geti("intent", 1);
+		if (opt.kv.count("whitexy")) ints("whitexy", g_cenc.whitexy, 2);
+		if (opt.kv.count("primxy")) ints("primxy", g_cenc.primxy, 6);
+		if (g_cenc.set && (g_cenc.white < 0 || g_cenc.white > 81 || g_cenc.primaries < 0 || g_cenc.primaries > 81 || g_cenc.tf < 0 || g_cenc.tf > 81 || g_cenc.intent < 0 || g_cenc.intent > 81 || g_cenc.gamma < 0 || g_cenc.gamma >= (1 << 24)))
+			die("cenc: a value out of its field's range");
+		if (g_cenc.set && (opt.geti("grey", 0) || opt.geti("icc", 0))) die("cenc= does not combine with grey=1 or icc=");
+		for (const char *k : CENC_KEYS) opt.kv.erase(k);
 	}
 	if (opt.kv.count("tone") || opt.kv.count("opsin") || opt.kv.count("cwmask")) {
 		if (!vardct && !opt.geti("xyb", 0)) die("tone=, opsin= and cwmask= belong to the vardct mode and to Modular frames of an XYB image (xyb=1)");
