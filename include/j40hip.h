@@ -452,7 +452,7 @@ J40HIP_API void j40hip_frame_region(const j40hip_frame *f, int32_t out[12]);
  *      pixels the reference pins. An opaque frame stays A = 255 (65535).
  *      set: any parsed frame, uploaded or not; it holds from the next decode on, across uploads. A shift outside 0..2: "rnge". A shift
  *      above 0 is refused with "Usc?" for a frame with a region or a partial group range and for a handle j40hip_sequence_frame handed
- *      out (other than the main frame of an LF-frame still, see J40HIP_SEQ_LFFRAME), with "Ulf?" for an LF-only frame; j40hip_frame_set_region and j40hip_frame_set_group_range on a frame with a shift above 0
+ *      out (other than the main frame of an LF-frame still, see J40HIP_SEQ_LFFRAME, and a full-canvas frame with patches, see J40HIP_SEQ_PATCHES), with "Ulf?" for an LF-only frame; j40hip_frame_set_region and j40hip_frame_set_group_range on a frame with a shift above 0
  *      return "Usc?": whichever setter comes second is refused. A refused call leaves the frame as it was. Shift 0 always succeeds.
  *      At a shift above 0 j40hip_frame_decode / _timed / _decode_to_host write ow x oh pixels; stride_bytes below 4 * ow (u8) or 8 * ow
  *      (u16) is "rnge" before anything is launched; nothing outside the ow pixels of each of the oh rows is written;
@@ -576,7 +576,8 @@ J40HIP_API void j40hip_frame_restoration(const j40hip_frame *f, j40hip_restorati
 J40HIP_API void j40hip_frame_set_restoration(j40hip_frame *f, int mode);                    /* -1: as the environment says (default), 0 off, 1 on, 2 as j40's routines stand */
 J40HIP_API int j40hip_frame_sharpness(const j40hip_frame *f, int64_t gg, int16_t *out);     /* LfGroup gg's sharpness map as decoded (i16 w8*h8; j40__lf_group_st::sharpness) */
 /* after a decode that ran the filters, stream synchronised: stage 0 the XYB samples as the inverse transforms left them, 1 the filtered
- * ones ([3][height][width] floats); 2 the reciprocal-sigma plane of the edge-preserving filter (w8*h8 floats, < 0: the cell is skipped) */
+ * ones ([3][height][width] floats); 2 the reciprocal-sigma plane of the edge-preserving filter (w8*h8 floats, < 0: the cell is skipped).
+ * Stage 3, after any decode of a frame with patches (J40HIP_SEQ_PATCHES): the planes after k_patch_blend, as the tail read them */
 J40HIP_API uint32_t j40hip_frame_read_xyb(j40hip_frame *f, int stage, float *out);
 J40HIP_API float j40hip_frame_restoration_ms(const j40hip_frame *f);   /* device time of the filter kernels in the last decode (J40HIP_RESTORATION_TIMING=1) */
 /* known-answer hook: the filter kernels on caller-supplied planes (xyb: [3][h][w] floats, host, in place), a w8*h8 sharpness map and the
@@ -696,6 +697,41 @@ J40HIP_API void j40hip_sequence_frame_lf(const j40hip_sequence *s, int64_t k, in
 /* debug read-back (synchronises the device): plane c (0 X, 1 Y, 2 B) of LF slot `level` - 1 as the playback last filled it, tightly
  * packed floats of the LF frame's size. "rnge": no such slot, or nothing stored in it since the last rewind. */
 J40HIP_API uint32_t j40hip_sequence_read_lf_slot(j40hip_sequence *s, int32_t level, int32_t c, float *out);
+/* ---- patches: reference-only frames and the patch dictionary. PARITY UNPINNED: the reference holds no code for either (j40.h:6262 is a
+ *      TODO); off by default. With J40HIP_SEQ_PATCHES (or J40HIP_PATCHES=1 in the environment) a sequence takes
+ *      - a reference-only frame (type 2) with save_before_colour_transform = 1 of an image with xyb_encoded = 1: a frame of its own width
+ *        and height, without an origin, never shown. Its three float32 planes X, Y, B -- what the inverse transforms (and, where they are
+ *        in force, the restoration filters) leave of it -- are stored in reference slot save_as_reference; a Modular one needs
+ *        J40HIP_SEQ_MODULAR_XYB as well. A slot holds such planes or saved pixels, whichever the playback put there last. Type 2 with
+ *        save_before_colour_transform = 0, with patches of its own, or in an image with xyb_encoded = 0 stays "TODO";
+ *      - a frame with has_patches: the patch dictionary at the head of its LfGlobal names rectangles of those slots and where they go
+ *        onto the frame's own XYB samples, in dictionary order, in blend mode None (0), Replace (1), Add (2) or Mul (3; with clamp the
+ *        source is clamped to [0, 1]) -- one float32 operation per sample and channel (k_patch_blend), after the restoration filters and
+ *        before the colour tail. A dictionary with a mode that uses alpha (4..7), or with an extra channel's entry other than None, is "TODO".
+ *      "ptch": a dictionary that is damaged -- a mode above 7, a slot above 3, a rectangle that leaves its reference frame, a placement
+ *      that is negative or leaves the frame, more reference patches than 1024 + pixels / 4 (or four times as many placements). "ptno": a
+ *      slot that no reference-only frame has filled when the frame is reached. Both are found when the index is built (the row's code).
+ *      A frame with patches decodes whole frames at full size: a region or a scale is cut from the full-size picture, a group range, a
+ *      batch, a pipeline and the LF preview of such a frame are "TODO". Without the flag every stream is taken or refused as before. ---- */
+#define J40HIP_SEQ_PATCHES 128u
+/* out8: [0] has_patches, [1] the dictionary's reference patches, [2] its placements, [3] the slots they read (bit k: slot k), [4] whether
+ * the row is a reference-only frame stored as XYB planes, [5] the slot it is stored in (-1: none), [6] the tiles of the frame that a
+ * placement other than None touches (k_patch_blend's workgroups; 0: it is not launched), [7] how often the decodes of the row's handle
+ * have launched k_patch_blend. k out of range: zeros. */
+J40HIP_API void j40hip_sequence_frame_patches(const j40hip_sequence *s, int64_t k, int32_t *out8);
+/* placement i (dictionary order) of coded frame k as parsed. out10: [0..1] x, y on the frame, [2..3] width, height, [4..5] x0, y0 in the
+ * reference frame, [6] the slot, [7] the colour channels' mode, [8] clamp, [9] which reference patch it places. "rnge": no such placement. */
+J40HIP_API uint32_t j40hip_sequence_frame_patch(const j40hip_sequence *s, int64_t k, int64_t i, int32_t *out10);
+/* debug read-back: the size of the planes in reference slot `slot` as the playback last filled it, and (synchronises the device) plane c
+ * (0 X, 1 Y, 2 B) of it, tightly packed floats. "rnge": no such slot, or it holds no reference-only frame since the last rewind. */
+J40HIP_API uint32_t j40hip_sequence_ref_slot_size(j40hip_sequence *s, int32_t slot, int32_t *width, int32_t *height);
+J40HIP_API uint32_t j40hip_sequence_read_ref_slot(j40hip_sequence *s, int32_t slot, int32_t c, float *out);
+/* known-answer / measuring hook: k_patch_blend alone. planes_dev: three planes (X, Y, B) of width x height floats, one behind the other,
+ * changed in place; slot_dev[k]: the three planes of slot k, slot_w[k] x slot_h[k] floats each (null: empty); placements: count times
+ * nine integers x, y, w, h, x0, y0, slot, mode, clamp, in dictionary order. The list is checked ("ptch", "ptno") and binned on the host;
+ * tiles_out (optional): the workgroups launched. Enqueued on `stream` and waited for. */
+J40HIP_API uint32_t j40hip_kat_device_patches(float *planes_dev, int32_t width, int32_t height, const float *const slot_dev[4], const int32_t slot_w[4], const int32_t slot_h[4],
+		const int32_t *placements, int32_t count, int32_t *tiles_out, void *stream);
 /* Coded frame k, fully parsed at the first call: an ordinary frame handle of the frame's own (crop) size over a copy of the frame's
  * own bytes, owned by the sequence (do not free it). Every single-frame and batch entry point takes it -- upload, decode, region,
  * LF preview, alpha mode, status. NULL and the code for a frame that is refused or does not parse. */

@@ -128,6 +128,9 @@ def lib():
         "j40hip_kat_device_compose": (u32, [vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, u32, u32, i32, vp]),
         "j40hip_sequence_frame_blend": (None, [vp, i64, vp]),
         "j40hip_sequence_frame_lf": (None, [vp, i64, vp]), "j40hip_sequence_read_lf_slot": (u32, [vp, i32, i32, vp]),
+        "j40hip_sequence_frame_patches": (None, [vp, i64, vp]), "j40hip_sequence_frame_patch": (u32, [vp, i64, i64, vp]),
+        "j40hip_sequence_ref_slot_size": (u32, [vp, i32, vp, vp]), "j40hip_sequence_read_ref_slot": (u32, [vp, i32, i32, vp]),
+        "j40hip_kat_device_patches": (u32, [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]),
         "j40hip_kat_device_blend": (u32, [vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, u32, u32, i32, i32, i32, vp]),
         "j40hip_frame_restoration": (None, [vp, vp]), "j40hip_frame_set_restoration": (None, [vp, C.c_int]), "j40hip_frame_sharpness": (C.c_int, [vp, i64, vp]),
         "j40hip_frame_set_alpha": (u32, [vp, C.c_int]), "j40hip_frame_alpha": (None, [vp, vp]),
@@ -242,7 +245,7 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False, colour=False):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False, blend=False):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
     scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
     (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
@@ -266,12 +269,17 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     the sequence is opened with both switches, which serves a Modular LF frame.
     colour=True: an XYB image is rendered in the colour space its header signals for this call whatever J40HIP_COLOUR says
     (Frame.set_colour(1); "Ucs?" for what that refuses), through the thin C-ABI on device 0; with lf_frames=True the sequence is opened
-    with the switch."""
-    if lf_frames:
-        if alpha or ycbcr or wide:
+    with the switch.
+    patches=True: a stream with reference-only frames and patch dictionaries is served for this call whatever J40HIP_PATCHES says:
+    through a Sequence on device 0 opened with the switch (Sequence's patches=), the first displayed canvas. It combines with
+    modular_xyb=, colour=, lf_frames= and blend= (Sequence's blend=, which only this route takes), which open the sequence with theirs,
+    and with fmt and scale (the shown frame's own handle decoded once more at the scale, as with lf_frames=True: a full-canvas frame with
+    patches takes one); "TODO" with orient= unless lf_frames= is given too."""
+    if lf_frames or patches:
+        if alpha or ycbcr or wide or (patches and not lf_frames and orient):
             return "TODO", None
         try:
-            seq = Sequence(data, lf_frames=True, modular_xyb=bool(modular_xyb), colour=bool(colour))
+            seq = Sequence(data, lf_frames=bool(lf_frames), modular_xyb=bool(modular_xyb), colour=bool(colour), patches=bool(patches), blend=bool(blend))
         except J40Error as e:
             if e.code != "Usq?":
                 return e.code, None
@@ -530,6 +538,61 @@ def kat_device_modular_xyb(planes, alpha, m, colour_consts, bpp, fmt=J40_U8X4, p
     guard = all(bool((x[:, w * pb:] == 0xA5).all()) for x in hosts)
     fused, two = [np.ascontiguousarray(x[:, :w * pb]).view(dt).reshape(h, w, 4) for x in hosts]
     return "", fused, two, d_xyb.cpu().numpy(), guard
+
+
+def kat_device_xyb_to_rgba(xyb, colour_consts, bpp, fmt=J40_U8X4, device=0):
+    """the VarDCT colour tail's kernel alone (k_xyb_to_rgba through j40hip_kat_device_modular_xyb_launch, kernel 2): xyb [3, h, w] float32
+    (X, Y, B), colour_consts the 15 floats of Frame.colour_consts() -> (err4, pixels [h, w, 4] uint8 or uint16), A opaque"""
+    import torch
+    xyb = np.ascontiguousarray(xyb, np.float32)
+    _, h, w = xyb.shape
+    pb = 8 if fmt == J40_U16X4 else 4
+    dev = "cuda:%d" % device
+    cc = np.ascontiguousarray(colour_consts, np.float32); mm = np.zeros(3, np.float32)
+    assert cc.size == 15
+    size = int(lib().j40hip_kat_device_colour_frame(cc.ctypes.data, int(bpp), None, 0))
+    d_frame = torch.zeros(size, dtype=torch.uint8, device=dev)
+    d_in = torch.from_numpy(xyb).to(dev)
+    d_out = torch.zeros((h, w * pb), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    if lib().j40hip_kat_device_colour_frame(cc.ctypes.data, int(bpp), d_frame.data_ptr(), size) != size:
+        return "!gpu", None
+    ptrs = (C.c_void_p * 3)(*[d_in[c].data_ptr() for c in range(3)])
+    with torch.cuda.device(dev):
+        code = err4(lib().j40hip_kat_device_modular_xyb_launch(2, ptrs, 4, w, h, mm.ctypes.data, cc.ctypes.data, int(bpp), int(fmt), d_out.data_ptr(), w * pb, d_frame.data_ptr(), None))
+        torch.cuda.synchronize(dev)
+    if code:
+        return code, None
+    px = d_out.cpu().numpy()
+    return "", (px.view(np.uint16) if pb == 8 else px).reshape(h, w, 4)
+
+
+def kat_device_patches(planes, slots, placements, device=0):
+    """k_patch_blend alone (j40hip_kat_device_patches): planes [3, h, w] float32 (X, Y, B); slots: four entries, each None or [3, sh, sw]
+    float32; placements: rows of nine integers x, y, w, h, x0, y0, slot, mode, clamp in dictionary order -> (err4, the planes after the
+    patches or None, the workgroups launched). The planes sit between guard floats, which must come back untouched (asserted here)"""
+    import torch
+    planes = np.ascontiguousarray(planes, np.float32)
+    _, h, w = planes.shape
+    dev = "cuda:%d" % device
+    guard = 64
+    buf = np.full(guard + planes.size + guard, 12345.0, np.float32)
+    buf[guard:guard + planes.size] = planes.ravel()
+    d_buf = torch.from_numpy(buf).to(dev)
+    d_slots = [None if s is None else torch.from_numpy(np.ascontiguousarray(s, np.float32)).to(dev) for s in slots]
+    ptrs = (C.c_void_p * 4)(*[None if t is None else t.data_ptr() for t in d_slots])
+    sw = np.array([0 if s is None else s.shape[2] for s in slots], np.int32); sh = np.array([0 if s is None else s.shape[1] for s in slots], np.int32)
+    pl = np.ascontiguousarray(placements, np.int32).reshape(-1, 9)
+    tiles = C.c_int32(0)
+    torch.cuda.synchronize(dev)
+    with torch.cuda.device(dev):
+        code = err4(lib().j40hip_kat_device_patches(d_buf.data_ptr() + 4 * guard, w, h, ptrs, sw.ctypes.data, sh.ctypes.data, pl.ctypes.data, len(pl), C.byref(tiles), None))
+        torch.cuda.synchronize(dev)
+    host = d_buf.cpu().numpy()
+    assert (host[:guard] == 12345.0).all() and (host[-guard:] == 12345.0).all(), "k_patch_blend wrote outside the planes"
+    if code:
+        return code, None, 0
+    return "", host[guard:guard + planes.size].reshape(3, h, w).copy(), int(tiles.value)
 
 
 def kat_device_srgb_u16(values, bpp):
@@ -933,8 +996,9 @@ class Frame:
 
     def read_xyb(self, stage):
         """after a decode that ran the filters: stage 0 / 1 -> [3, height, width] float32 (before / after them), 2 -> the reciprocal sigmas [h8, w8].
-        A Modular frame of an XYB image decoded with set_modular_xyb(1) in force: stage 0 -> the planes X, Y, B by k_modular_to_xyb"""
-        a = np.zeros((3, self.height, self.width), np.float32) if stage < 2 else np.zeros(((self.height + 7) // 8, (self.width + 7) // 8), np.float32)
+        A Modular frame of an XYB image decoded with set_modular_xyb(1) in force: stage 0 -> the planes X, Y, B by k_modular_to_xyb.
+        A frame with patches (Sequence's patches=): stage 3 -> [3, height, width], the planes after k_patch_blend, as the tail read them"""
+        a = np.zeros((3, self.height, self.width), np.float32) if stage != 2 else np.zeros(((self.height + 7) // 8, (self.width + 7) // 8), np.float32)
         self._chk(lib().j40hip_frame_read_xyb(self.h, stage, a.ctypes.data), "in j40hip_frame_read_xyb")
         return a
 
@@ -1098,6 +1162,9 @@ def decode_lf_many(datas, fmt=J40_U8X4, device=0):
 SEQ_BLEND = 2   # j40hip_sequence_open's flag J40HIP_SEQ_BLEND: the blend modes Add, Blend, MulAdd and Mul are served
 SEQ_LFFRAME = 16   # ... J40HIP_SEQ_LFFRAME: LF frames (type 1) and the frames with use_lf_frame are served
 SEQ_COLOUR = 64   # ... J40HIP_SEQ_COLOUR: every handle renders in the colour space the image header signals (Frame.set_colour)
+SEQ_PATCHES = 128   # ... J40HIP_SEQ_PATCHES: reference-only frames (type 2) and the frames with a patch dictionary are served
+SEQUENCE_PATCHES_FIELDS = ("has_patches", "num_ref", "placements", "slots", "stored_xyb", "xyb_slot", "tiles", "launches")
+SEQUENCE_PATCH_FIELDS = ("x", "y", "w", "h", "x0", "y0", "ref", "mode", "clamp", "source")
 SEQ_MODULAR_XYB = 32   # ... J40HIP_SEQ_MODULAR_XYB: Modular frames of an XYB image go through the XYB colour tail; with SEQ_LFFRAME a Modular LF frame is served
 SEQUENCE_BLEND_FIELDS = ("mode", "alpha_mode", "alpha_chan", "clamp", "alpha_alpha_chan", "alpha_clamp", "src", "blended")
 SEQUENCE_FRAME_FIELDS = ("x0", "y0", "w", "h", "duration", "is_last", "shown", "type", "blend", "src", "save_as_reference", "saved",
@@ -1113,13 +1180,16 @@ class Sequence:
     colour=True (or J40HIP_COLOUR=1): every handle renders in the colour space the image header signals (Frame.set_colour): the canvas
     holds pixels in that space, the blend modes work on them as they are.
     modular_xyb=True (or J40HIP_MODULAR_XYB=1): the Modular frames of an XYB image go through the XYB colour tail (Frame.set_modular_xyb);
-    together with lf_frames=True a Modular LF frame is served, with either alone it is "TODO"."""
+    together with lf_frames=True a Modular LF frame is served, with either alone it is "TODO".
+    patches=True (or J40HIP_PATCHES=1): reference-only frames (type 2, stored as XYB planes in their reference slot, never shown) and
+    the frames whose patch dictionary blends rectangles of them onto their own XYB samples are served too, else "TODO" (frame_patches,
+    frame_patch, read_ref_slot); a Modular reference-only frame needs modular_xyb=True as well. PARITY UNPINNED."""
 
-    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False, modular_xyb: bool = False, colour: bool = False):
+    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False, modular_xyb: bool = False, colour: bool = False, patches: bool = False):
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0) | (SEQ_MODULAR_XYB if modular_xyb else 0) | (SEQ_COLOUR if colour else 0)
+        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0) | (SEQ_MODULAR_XYB if modular_xyb else 0) | (SEQ_COLOUR if colour else 0) | (SEQ_PATCHES if patches else 0)
         self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags, C.byref(err))
         if not self.h:
             raise J40Error(err4(err.value), "in j40hip_sequence_open")
@@ -1181,6 +1251,35 @@ class Sequence:
                 raise J40Error(err4(code), "in j40hip_sequence_read_lf_slot")
         return out
 
+    def frame_patches(self, k):
+        """patches: coded frame k's row as a dict (SEQUENCE_PATCHES_FIELDS) -- whether it has a dictionary, its reference patches and
+        placements, the slots they read (a bit mask), whether the row is a reference-only frame stored as XYB planes and in which slot,
+        the tiles k_patch_blend gets, and how often the row's handle has launched it"""
+        out = np.zeros(8, np.int32)
+        lib().j40hip_sequence_frame_patches(self.h, k, out.ctypes.data)
+        return dict(zip(SEQUENCE_PATCHES_FIELDS, out.tolist()))
+
+    def frame_patch(self, k, i):
+        """placement i (dictionary order) of coded frame k as parsed, as a dict (SEQUENCE_PATCH_FIELDS)"""
+        out = np.zeros(10, np.int32)
+        code = lib().j40hip_sequence_frame_patch(self.h, k, i, out.ctypes.data)
+        if code:
+            raise J40Error(err4(code), "in j40hip_sequence_frame_patch")
+        return dict(zip(SEQUENCE_PATCH_FIELDS, out.tolist()))
+
+    def read_ref_slot(self, slot):
+        """debug read-back: the planes reference slot `slot` holds since a reference-only frame was played into it, [3, h, w] float32 (X, Y, B)"""
+        w, h = C.c_int32(), C.c_int32()
+        code = lib().j40hip_sequence_ref_slot_size(self.h, slot, C.byref(w), C.byref(h))
+        if code:
+            raise J40Error(err4(code), "in j40hip_sequence_ref_slot_size")
+        out = np.zeros((3, h.value, w.value), np.float32)
+        for c in range(3):
+            code = lib().j40hip_sequence_read_ref_slot(self.h, slot, c, out[c].ctypes.data)
+            if code:
+                raise J40Error(err4(code), "in j40hip_sequence_read_ref_slot")
+        return out
+
     def frame(self, k):
         """coded frame k as a Frame the sequence owns: crop-sized, for every single-frame and batch entry point. It lives as long as the
         sequence: close() of the sequence closes it too"""
@@ -1229,7 +1328,7 @@ class Sequence:
         return err4(code), int(k.value)
 
 
-def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False, modular_xyb=False, colour=False):
+def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False):
     """every displayed frame of an animation or a layered still: ([(rgba ndarray [height, width, 4], duration in ticks), ...],
     (tps_num, tps_den, loops)). alpha=True: VarDCT frames keep their alpha channel (Frame.set_alpha(1); J40Error where that refuses).
     blend=True: frames with a blend mode other than Replace are composed too (Sequence's blend=), else such a frame raises "TODO".
@@ -1237,8 +1336,9 @@ def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False,
     lf_frames=True: LF frames and the frames that take their LF image from one are served (Sequence's lf_frames=), else "TODO".
     modular_xyb=True: Modular frames of an XYB image go through the XYB colour tail (Sequence's modular_xyb=).
     colour=True: every frame is rendered in the colour space the image header signals (Sequence's colour=).
+    patches=True: reference-only frames and the frames with a patch dictionary are served (Sequence's patches=), else "TODO".
     A frame that fails raises J40Error with its code. A stream whose first frame is its last is not a sequence ("Usq?"): decode()."""
-    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames, modular_xyb=modular_xyb, colour=colour)
+    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames, modular_xyb=modular_xyb, colour=colour, patches=patches)
     try:
         seq.set_output_format(fmt)
         if alpha:

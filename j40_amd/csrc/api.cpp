@@ -209,6 +209,9 @@ bool frames_policy() { return j40hip::env_on("J40HIP_FRAMES", false); }
 // (J40HIP_MODULAR_XYB=1 needs nothing here: a frame handle and j40hip_sequence_open read it themselves -- Modular frames of an XYB image then
 // go through the XYB colour tail, and together with J40HIP_LFFRAME=1 a Modular LF frame is served.)
 bool lf_frames_policy() { return j40hip::env_on("J40HIP_LFFRAME", false); }
+// J40HIP_PATCHES=1: likewise a stream that holds a reference-only frame (type 2) or a frame with patches -- j40hip_sequence_open reads the
+// same variable and serves them. Without it such a stream is "TODO".
+bool patches_policy() { return j40hip::env_on("J40HIP_PATCHES", false); }
 // J40HIP_SCALE=1|2: every image decodes at 1:2 / 1:4 (j40hip_frame_set_scale): j40_frame_pixels_* then report the small image's width,
 // height and stride. Looked at when an image is first advanced, like J40HIP_FRAMES; unset, 0 or anything else: full size.
 int scale_policy() { const int e = j40hip::env_int("J40HIP_SCALE", 0, INT_MIN, INT_MAX); return e == 1 || e == 2 ? e : 0; }
@@ -250,7 +253,7 @@ j40_err advance(j40__inner *inner, int origin) {
 	const int shift = scale_policy();
 	if (shift && frames_policy()) { inner->origin = origin; return inner->err = code4("Usc?"); }   // sequences are not served at a scale
 	if (orient_policy() && frames_policy()) { inner->origin = origin; return inner->err = code4("Uor?"); }   // ... nor in an orientation
-	if (!inner->seq_checked && (frames_policy() || lf_frames_policy())) {
+	if (!inner->seq_checked && (frames_policy() || lf_frames_policy() || patches_policy())) {
 		// a file is read whole first; a stream that is not a sequence ("Usq?": its first frame is its last), or whose headers fail,
 		// takes the single-frame route below, which decodes it or reports what is wrong with it
 		inner->seq_checked = 1;
@@ -258,15 +261,21 @@ j40_err advance(j40__inner *inner, int origin) {
 		uint32_t serr = 0;
 		inner->seq = j40hip_sequence_open(inner->buf, inner->size, parse_thread_count(), 1u, &serr);
 		if (inner->seq && !frames_policy()) {
-			// J40HIP_LFFRAME=1 alone: only a stream with an LF frame goes this way, every other one stays what it was without the variable
-			bool lf = false;
-			for (int64_t k = 0, n = j40hip_sequence_num_frames(inner->seq); k < n; ++k) { int32_t v[4]; j40hip_sequence_frame_lf(inner->seq, k, v); lf = lf || v[0] > 0; }
-			if (!lf || shift || orient_policy()) { j40hip_sequence_free(inner->seq); inner->seq = nullptr; }
-			if (lf && (shift || orient_policy())) { inner->origin = origin; return inner->err = code4(shift ? "Usc?" : "Uor?"); }   // (as above: sequences are served at full size, in stored order)
+			// J40HIP_LFFRAME=1 or J40HIP_PATCHES=1 alone: only a stream with an LF frame, a reference-only frame or patches goes this way, every
+			// other one stays what it was without the variable
+			bool routed = false;
+			for (int64_t k = 0, n = j40hip_sequence_num_frames(inner->seq); k < n; ++k) {
+				int32_t v[4], p[8];
+				j40hip_sequence_frame_lf(inner->seq, k, v); j40hip_sequence_frame_patches(inner->seq, k, p);
+				routed = routed || (lf_frames_policy() && v[0] > 0) || (patches_policy() && (p[0] || p[4]));
+			}
+			if (!routed || shift || orient_policy()) { j40hip_sequence_free(inner->seq); inner->seq = nullptr; }
+			if (routed && (shift || orient_policy())) { inner->origin = origin; return inner->err = code4(shift ? "Usc?" : "Uor?"); }   // (as above: sequences are served at full size, in stored order)
 		}
 		if (inner->seq) return 0;
 		// (an LF-frame stream whose index fails on its first row: the LF frame is missing or of the wrong size. The single-frame route would say "TODO")
 		if (lf_frames_policy() && (serr == code4("lfno") || serr == code4("lfsz"))) { inner->origin = origin; return inner->err = serr; }
+		if (patches_policy() && (serr == code4("ptno") || serr == code4("ptch"))) { inner->origin = origin; return inner->err = serr; }
 	}
 	struct Inside { int n; Inside() : n(++g_inside) {} ~Inside() { --g_inside; } } inside;
 	const int policy = serve_policy();

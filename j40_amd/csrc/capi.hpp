@@ -4,6 +4,8 @@
 #include "frame.hpp"
 #include "plan_build.hpp"
 #include "colour_space.hpp"
+#include "device/patch_dev.h"
+#include <memory>
 
 struct j40hip_device_state;  // defined in device/runtime_state.hpp
 
@@ -56,6 +58,12 @@ struct j40hip_frame {
 	// null: nothing bound, such a frame's decode is "lfno"
 	const float *lf_src[3] = {nullptr, nullptr, nullptr};
 	int32_t lf_src_w = 0, lf_src_h = 0;
+	// a frame with patches (a sequence with J40HIP_SEQ_PATCHES): the reference slots its next decodes read -- per slot the three device
+	// planes (X, Y, B) of a reference-only frame, w x h floats each, one behind the other, bound by the playback (j40hip_frame_bind_patch_source);
+	// null: nothing bound, a decode that reads the slot is "ptno". patch_launches: how often a decode of this handle has launched k_patch_blend
+	struct PatchSource { const float *base = nullptr; int32_t w = 0, h = 0; } patch_src[4];
+	int64_t patch_launches = 0;
+	std::shared_ptr<const j40hip::PatchPlan> patch_plan;   // the placements as records and their tiles, as the sequence's index made them (null: no dictionary)
 	int threads = 1;                 // what the frame was parsed with: the plan build at upload may use as many (plan_build.cpp)
 	// backing storage of the plan views (include/j40hip.h)
 	struct Views {
@@ -94,6 +102,13 @@ struct j40hip_sequence {
 		int8_t alpha_mode = 0, src = 0;
 		bool blended = false;
 		int32_t lf_src = -1;         // LF frames (J40HIP_SEQ_LFFRAME): the row whose picture this frame's LF samples are (use_lf_frame), -1: none
+		// patches (J40HIP_SEQ_PATCHES): the row is a reference-only frame, stored as three XYB planes in reference slot `xyb_slot` and never
+		// shown; or a frame with patches -- its dictionary and, made of it once here, the records and their binning into tiles, which the
+		// frame's handle shares (j40hip_frame::patch_plan) and its upload copies to the device
+		bool stored_xyb = false;
+		int32_t xyb_slot = -1;
+		j40hip::PatchDictionary patches;
+		std::shared_ptr<const j40hip::PatchPlan> patch_plan;
 	};
 	std::vector<Row> rows;
 	std::vector<j40hip_frame *> frames;   // [rows.size()], parsed when first asked for
@@ -103,6 +118,7 @@ struct j40hip_sequence {
 	bool colour = false;             // every handle renders in the signalled colour space (J40HIP_SEQ_COLOUR or J40HIP_COLOUR=1)
 	bool colour_asked = false;       // ... by the flag itself: an image the mode refuses as a whole then fails j40hip_sequence_open
 	bool modular_xyb = false;        // Modular frames of an XYB image go through the XYB colour tail (J40HIP_SEQ_MODULAR_XYB or J40HIP_MODULAR_XYB=1)
+	bool patches = false;            // reference-only frames and patch dictionaries are served (J40HIP_SEQ_PATCHES or J40HIP_PATCHES=1)
 	int32_t alpha_ec = -1;           // the extra channel that is rendered as A (rendered_alpha_channel); -1: none
 	int32_t output_format = J40HIP_U8X4;
 	j40hip_sequence_device *dev = nullptr;
@@ -162,6 +178,13 @@ inline bool j40hip_lf_still_handle(const j40hip_frame *h) {
 	return h->from_sequence && fh.use_lf_frame && fh.type != 1 && fh.x0 == 0 && fh.y0 == 0 && fh.width == h->frame.im.width && fh.height == h->frame.im.height;
 }
 
+// Likewise the handle of a frame with patches that covers the canvas: once the playback has bound its reference slots it decodes alone
+// like any frame, so it takes a scale (a region it takes anyway); the playback refuses it while one is set. Never an orientation.
+inline bool j40hip_patch_still_handle(const j40hip_frame *h) {
+	const j40hip::FrameHeader &fh = h->frame.fh;
+	return h->from_sequence && fh.has_patches && (fh.type == 0 || fh.type == 3) && fh.x0 == 0 && fh.y0 == 0 && fh.width == h->frame.im.width && fh.height == h->frame.im.height;
+}
+
 // the orientation the next decode writes in: the stream's where the mode (or J40HIP_ORIENT=1) applies it, else 1 (stored order). A handle
 // a sequence hands out is never oriented: the playback writes stored order -- but for the main frame of an LF-frame still, and that one
 // only where the mode was set on the handle itself (the environment never orients a sequence's handles)
@@ -175,6 +198,12 @@ inline int32_t j40hip_orientation_in_force(const j40hip_frame *h) {
 inline void j40hip_frame_bind_lf_source(j40hip_frame *h, const float *const planes[3], int32_t w, int32_t hh) {
 	for (int c = 0; c < 3; ++c) h->lf_src[c] = planes[c];
 	h->lf_src_w = w; h->lf_src_h = hh;
+}
+
+// internal (a sequence's playback): the reference-only frame's planes in slot `slot` that the next decodes of a frame with patches read,
+// which must stay where they are until those decodes have run; base null: the slot is empty
+inline void j40hip_frame_bind_patch_source(j40hip_frame *h, int32_t slot, const float *base, int32_t w, int32_t hh) {
+	h->patch_src[slot].base = base; h->patch_src[slot].w = w; h->patch_src[slot].h = hh;
 }
 
 extern "C" j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads, uint32_t flags, j40hip::LfDeviceDecoder lf_decoder, void *lf_ctx, uint32_t *err);

@@ -8,6 +8,7 @@
 #include "decode_route.hpp"
 #include "tables.hpp"
 #include "device/region_dev.h"
+#include "device/patch_dev.h"
 
 using namespace j40hip;
 
@@ -162,18 +163,20 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 		s->modular_xyb = (flags & J40HIP_SEQ_MODULAR_XYB) != 0 || env_on("J40HIP_MODULAR_XYB", false);
 		s->colour = (flags & J40HIP_SEQ_COLOUR) != 0 || env_on("J40HIP_COLOUR", false);
 		s->colour_asked = (flags & J40HIP_SEQ_COLOUR) != 0;
+		s->patches = (flags & J40HIP_SEQ_PATCHES) != 0 || env_on("J40HIP_PATCHES", false);
 		size_t at = 0;
 		parse_image_header(s->cs, s->cs_size, &s->im, &at, (flags & J40HIP_PARSE_WIDE) != 0 || wide_env());
 		s->alpha_ec = rendered_alpha_channel(s->im);
 		// the flag on an image the colour mode refuses as a whole (the environment variable alone leaves such a sequence as it was)
 		if (s->colour_asked) if (uint32_t e = j40hip::colour::image_refusal(s->im)) raise(e);
 		int32_t lf_row[4] = {-1, -1, -1, -1};   // the row whose picture LF slot k holds when the playback gets here
+		int32_t ref_row[4] = {-1, -1, -1, -1};  // the reference-only frame whose XYB planes reference slot k holds then (-1: none, or pixels)
 		for (;;) {
 			j40hip_sequence::Row row;
 			Toc toc;
 			row.offset = at;
 			try {
-				parse_sequence_frame_header(s->cs, s->cs_size, at, s->im, s->blend, s->lf_frames, &row.fh, &toc, s->lf_frames && s->modular_xyb);
+				parse_sequence_frame_header(s->cs, s->cs_size, at, s->im, s->blend, s->lf_frames, &row.fh, &toc, s->lf_frames && s->modular_xyb, s->patches, s->patches && s->modular_xyb);
 				row.first_section = at + toc.first_offset; row.end = at + toc.end_offset;
 				// (a frame whose sections the stream does not hold to their end: whatever follows it cannot be found)
 				if (row.end > s->cs_size) row.code = E4("shrt");
@@ -199,13 +202,36 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 					}
 				}
 				if (row.fh.type == 1 && !row.code) lf_row[row.fh.lf_level - 1] = (int32_t) s->rows.size();
+				if (s->patches && row.fh.has_patches && !row.code) {
+					// its dictionary, from the head of LfGlobal: every slot it names holds a reference-only frame by now ("ptno": it does not), and every
+					// source rectangle lies inside that frame ("ptch") -- only here are both frames known
+					parse_sequence_patches(s->cs, s->cs_size, at, s->im, row.fh, toc, &row.patches);
+					if (row.patches.unserved || !s->im.xyb_encoded) row.code = E4("TODO");
+					auto plan = std::make_shared<PatchPlan>();
+					std::vector<PatchRec> &recs = plan->recs;
+					for (const PatchPlacement &p : row.patches.placements) {
+						if (row.code) break;
+						const int32_t src = ref_row[p.ref];
+						if (src < 0) { row.code = E4("ptno"); break; }
+						const FrameHeader &ref = s->rows[(size_t) src].fh;
+						if ((int64_t) p.sx + p.w > ref.width || (int64_t) p.sy + p.h > ref.height) { row.code = E4("ptch"); break; }
+						recs.push_back(PatchRec{p.x, p.y, p.w, p.h, p.sx, p.sy, p.ref, p.mode | p.clamp << 8});
+					}
+					// (the tiles the placements touch, bounded before anything is made of them: patch_dev.h)
+					if (!row.code && !patch_bin(recs.data(), recs.size(), row.fh.width, row.fh.height, &plan->bins)) row.code = E4("ptch");
+					if (!row.code) row.patch_plan = plan;
+				}
+				if (row.fh.type == 2 && !row.code) { row.stored_xyb = true; row.xyb_slot = row.fh.save_as_ref; }
 			} catch (const DecodeError &e) { row.code = e.code; }
 			if (s->rows.empty()) {
 				if (row.code) raise(row.code);
 				J40HIP_SHOULD(!row.fh.is_last, "Usq?");   // not a sequence: j40hip_frame_parse's
 			}
 			row.shown = !row.code && (row.fh.duration > 0 || row.fh.is_last);
-			row.saved = !row.code && !row.fh.is_last && (row.fh.duration == 0 || row.fh.save_as_ref != 0) && row.fh.type != 1;   // (an LF frame goes to its LF slot only)
+			row.saved = !row.code && !row.fh.is_last && (row.fh.duration == 0 || row.fh.save_as_ref != 0) && row.fh.type != 1 && row.fh.type != 2;   // (an LF frame goes to its LF slot only, a reference-only frame to its slot's XYB planes)
+			// (a slot holds one thing: pixels saved into it take the place of a reference-only frame's planes)
+			if (row.stored_xyb) ref_row[row.xyb_slot] = (int32_t) s->rows.size();
+			else if (row.saved) ref_row[row.fh.save_as_ref] = -1;
 			s->rows.push_back(row);
 			if (row.code || row.fh.is_last) break;
 			at = row.end;
@@ -252,6 +278,26 @@ void j40hip_sequence_frame_blend(const j40hip_sequence *s, int64_t k, int32_t *o
 	out[4] = a.alpha_chan; out[5] = a.clamp; out[6] = r.src; out[7] = r.blended && !r.code;
 }
 
+void j40hip_sequence_frame_patches(const j40hip_sequence *s, int64_t k, int32_t *out8) {
+	if (!out8) return;
+	memset(out8, 0, sizeof(int32_t) * 8);
+	if (!s || k < 0 || k >= (int64_t) s->rows.size()) return;
+	const j40hip_sequence::Row &r = s->rows[(size_t) k];
+	const j40hip_frame *h = s->frames[(size_t) k];
+	out8[0] = r.fh.has_patches; out8[1] = r.patches.num_ref; out8[2] = (int32_t) r.patches.placements.size(); out8[3] = (int32_t) r.patches.slots;
+	out8[4] = r.stored_xyb; out8[5] = r.xyb_slot; out8[6] = r.patch_plan ? (int32_t) r.patch_plan->bins.tile_ids.size() : 0; out8[7] = h ? (int32_t) h->patch_launches : 0;
+}
+
+uint32_t j40hip_sequence_frame_patch(const j40hip_sequence *s, int64_t k, int64_t i, int32_t *out10) {
+	if (!s || !out10 || k < 0 || k >= (int64_t) s->rows.size()) return E4("rnge");
+	const std::vector<PatchPlacement> &pl = s->rows[(size_t) k].patches.placements;
+	if (i < 0 || i >= (int64_t) pl.size()) return E4("rnge");
+	const PatchPlacement &p = pl[(size_t) i];
+	const int32_t v[10] = {p.x, p.y, p.w, p.h, p.sx, p.sy, p.ref, p.mode, p.clamp, p.source};
+	memcpy(out10, v, sizeof v);
+	return 0;
+}
+
 void j40hip_sequence_frame_lf(const j40hip_sequence *s, int64_t k, int32_t *out) {
 	if (!out) return;
 	memset(out, 0, sizeof(int32_t) * 4);
@@ -280,10 +326,12 @@ j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err
 		h->bare_codestream = true;
 		h->frame.defer_lf_tail = (s->flags & 1u) != 0;
 		h->frame.seq_im = &s->im; h->frame.seq_blend = s->blend; h->frame.allow_lf_frame = s->lf_frames; h->frame.allow_modular_lf = s->lf_frames && s->modular_xyb; h->frame.allow_wide = (s->flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
+		h->frame.allow_patches = s->patches; h->frame.allow_modular_ref = s->patches && s->modular_xyb;
 		parse_frame(h->cs, h->cs_size, &h->frame, s->threads);
 		h->threads = s->threads;
 		h->output_format = s->output_format;
 		h->from_sequence = true;
+		h->patch_plan = r.patch_plan;
 		h->modular_xyb = s->modular_xyb ? 1 : 0;   // (in force where the rule applies: j40hip_modular_xyb_on)
 		h->colour = s->colour ? 1 : 0;             // (likewise: j40hip_colour_on)
 		// one canvas, one colour space: where the image's frames render in the signalled space, a frame that cannot -- a Modular frame

@@ -5,6 +5,7 @@
 #include "restore_dev.h"
 #include "region_dev.h"
 #include "colour_dev.h"
+#include "patch_dev.h"
 
 namespace j40hip {
 
@@ -46,6 +47,10 @@ void launch_xyb_to_rgba(const float *xyb, size_t pitch, const DevFrame *frame_de
 // the colour mode's tail (device/colour_kernels.hip, colour_dev.h): k_colour_tail over three planes laid out as launch_xyb_to_rgba's,
 // in the colour space `p` describes; p.table: device memory
 void launch_colour_tail(const float *xyb, size_t pitch, const ColourTailParams &p, int32_t width, int32_t height, uint8_t *out, size_t stride_bytes, hipStream_t stream, bool rgba16 = false);
+
+// patches (device/patch_kernels.hip, patch_dev.h): k_patch_blend over the three planes at `planes` (width * height floats each, one behind
+// the other), one workgroup per non-empty tile of `p` (device memory); nothing is launched for a list without tiles
+void launch_patch_blend(float *planes, int32_t width, int32_t height, const DevPatches &p, const PatchSlots &slots, hipStream_t stream);
 
 // LfGroup tail on the device (device/lf_tail_kernels.hip)
 void upload_lf_tail_tables(const float *half_secants, const float *lf2llf, hipStream_t stream);

@@ -18,7 +18,7 @@ bool j40hip_rt::modular_groups_independent(const j40hip_frame *h) {
 }
 
 // what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it
-static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->wide_used = false; h->modular_xyb_used = false; h->modular_xyb_whole = false; h->colour_used = false; h->colour_curve_8bit = false; h->dev->colour_planes = nullptr; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
+static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->wide_used = false; h->modular_xyb_used = false; h->modular_xyb_whole = false; h->colour_used = false; h->colour_curve_8bit = false; h->dev->colour_planes = nullptr; h->dev->patch_planes = nullptr; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
 
 // ---- the colour mode (j40hip_frame_set_colour; colour_space.hpp, device/colour_dev.h, colour_kernels.hip) ----
 // The threshold tables of 8-bit frames, one per distinct (curve, exponent, intensity_target): built once per process by bisection over
@@ -78,6 +78,25 @@ static float *colour_plane_buffer(j40hip_device_state *st, const FrameHeader &fh
 	return ok ? st->d_colour_xyb : (st->d_colour_xyb = nullptr);
 }
 
+// ---- patches (a sequence opened with J40HIP_SEQ_PATCHES; device/patch_dev.h, patch_kernels.hip) ----
+// The frame's patch dictionary onto `planes` (width x height floats each, X, Y, B one behind the other), on `s`: called by every route
+// that hands planes to a tail, after the restoration filters and before the tail. Nothing for a frame without patches; nothing is
+// launched for a dictionary whose placements are all of mode None. The slots are those the playback has bound ("ptno": it has not),
+// checked against every record once more on the host -- the kernel checks nothing.
+uint32_t j40hip_rt::apply_patches(j40hip_frame *h, float *planes, hipStream_t s) {
+	if (!h->frame.fh.has_patches) return 0;
+	j40hip_device_state *st = h->dev;
+	PatchSlots slots;
+	for (int k = 0; k < 4; ++k) { slots.base[k] = h->patch_src[k].base; slots.w[k] = h->patch_src[k].w; slots.h[k] = h->patch_src[k].h; }
+	if (!h->patch_plan) return ERR_TODO;   // (cannot happen: only a sequence's handle parses a dictionary, and its index made the plan)
+	for (const PatchRec &r : h->patch_plan->recs) if (uint32_t e = patch_check(r, slots, h->frame.fh.width, h->frame.fh.height)) return e;
+	st->patch_planes = planes;
+	if (st->patch.dev.num_tiles <= 0) return 0;
+	launch_patch_blend(planes, h->frame.fh.width, h->frame.fh.height, st->patch.dev, slots, s);
+	++h->patch_launches;
+	return 0;
+}
+
 // region (j40hip_frame_set_region): null, or the rectangle {x0, y0, w, h} that becomes the w x h pixels at rgba_dev -- the sections of
 // its cover only (LfGlobal's too), one launch per row of the cover's groups and pass, the frame-wide per-pixel transforms over the
 // cover's rows, and the rectangle packed with the destination moved back by its origin; every section where the groups depend on
@@ -97,7 +116,9 @@ static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *
 	h->modular_xyb_used = xyb;
 	if ((xyb_out && !xyb) || (xyb && shift > 0)) return ERR_TODO;
 	const bool colour = route.colour && xyb && !xyb_out;   // (whole frames: the route stages a region or a scale)
-	if (colour && (region || shift > 0 || !route.every_group)) return ERR_TODO;
+	const bool patches = route.patches && !xyb_out;        // (likewise)
+	if (patches && (!xyb || !st->patch.d_frame)) return ERR_TODO;
+	if ((colour || patches) && (region || shift > 0 || !route.every_group)) return ERR_TODO;
 	RegionCover cover = {0, 0, 0, 0, 0, 0};
 	bool covered = false;   // only the cover's groups are decoded
 	if (region) {
@@ -160,13 +181,16 @@ static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *
 		int32_t rects[3][4];
 		const int nr = group_range_rects(g0, gn, fr.fh.width, fr.fh.height, fr.fh.group_size_shift, rects);
 		for (int k = 0; k < nr; ++k) pack_rect(rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], (uint8_t *) rgba_dev);
-	} else if (colour) {
-		// the colour mode: the float planes, k_colour_tail over them (A opaque), A from its plane as the pack kernels render it
+	} else if (colour || patches) {
+		// the colour mode, a frame with patches: the float planes, the patches onto them, k_colour_tail (or the sRGB tail) over them (A opaque),
+		// A from its plane as the pack kernels render it
 		float *d = colour_plane_buffer(st, fr.fh);
 		if (!d) return ERR_MEM;
 		const size_t plane = (size_t) fr.fh.width * (size_t) fr.fh.height;
 		launch_modular_to_xyb(st->final_planes[0], st->final_planes[1], st->final_planes[2], fr.fh.width, 0, 0, fr.fh.width, fr.fh.height, xk, d, d + plane, d + 2 * plane, (size_t) fr.fh.width, s);
-		if (uint32_t e = colour_pixels(h, d, (uint8_t *) rgba_dev, stride_bytes, s)) return e;
+		if (uint32_t e = apply_patches(h, d, s)) return e;
+		if (!colour) launch_xyb_to_rgba(d, (size_t) fr.fh.width, st->patch.d_frame, fr.fh.width, fr.fh.height, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
+		else if (uint32_t e = colour_pixels(h, d, (uint8_t *) rgba_dev, stride_bytes, s)) return e;
 		if (alpha.p) launch_alpha_from_plane(alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	} else if (xyb) launch_modular_xyb_pack(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, xk, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	else launch_pack_planes(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h), shift);
@@ -392,14 +416,19 @@ static uint32_t ycbcr_pixels(j40hip_frame *h, const int32_t *class_start, const 
 	return 0;
 }
 
-// the colour mode without the filters: the pixel kernels leave the samples in XYB planes, k_colour_tail follows -- one pass more over three
-// float planes than the fused tail, the route the restoration filters already take
-static uint32_t colour_unfiltered(j40hip_frame *h, const int32_t *class_start, const DevVarblock *list, uint8_t *img, size_t stride_bytes, hipStream_t s) {
+// the colour mode, or a frame with patches, without the filters: the pixel kernels leave the samples in XYB planes, the patches go onto
+// them, k_colour_tail (`colour`) or the sRGB tail follows -- one pass more over three float planes than the fused tail, the route the
+// restoration filters already take
+static uint32_t planes_unfiltered(j40hip_frame *h, const int32_t *class_start, const DevVarblock *list, uint8_t *img, size_t stride_bytes, hipStream_t s, bool colour) {
 	j40hip_device_state *st = h->dev;
-	float *d = colour_plane_buffer(st, h->frame.fh);
+	const FrameHeader &fh = h->frame.fh;
+	float *d = colour_plane_buffer(st, fh);
 	if (!d) return ERR_MEM;
-	launch_vardct_frame(st->plan, class_start, list, st->d_large_scratch, K2Target{d, (size_t) h->frame.fh.width * 4, OutMode::XYB, 0}, s);
-	return colour_pixels(h, d, img, stride_bytes, s);
+	launch_vardct_frame(st->plan, class_start, list, st->d_large_scratch, K2Target{d, (size_t) fh.width * 4, OutMode::XYB, 0}, s);
+	if (uint32_t e = apply_patches(h, d, s)) return e;
+	if (colour) return colour_pixels(h, d, img, stride_bytes, s);
+	launch_xyb_to_rgba(d, (size_t) fh.width, st->plan.frame, fh.width, fh.height, img, stride_bytes, s, out16(h));
+	return 0;
 }
 
 static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t stride_bytes, int mode, hipStream_t s, bool colour = false) {
@@ -427,7 +456,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 		st->restore_err = perr;
 		if (!rgba_dev) return 0;   // (planes are wanted, not pixels -- run_vardct's xyb_out: the caller makes the unfiltered ones)
 		if (st->ycbcr) return ycbcr_pixels(h, st->class_start, st->d_vb_sorted, rgba_dev, stride_bytes, s);
-		if (colour) return colour_unfiltered(h, st->class_start, st->d_vb_sorted, rgba_dev, stride_bytes, s);
+		if (colour || fr.fh.has_patches) return planes_unfiltered(h, st->class_start, st->d_vb_sorted, rgba_dev, stride_bytes, s, colour);
 		launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{rgba_dev, stride_bytes, out_mode(h), 0}, s);
 		return 0;
 	}
@@ -448,6 +477,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	}
 	st->d_restored = launch_restoration(st->d_xyb, st->d_xyb_tmp, (size_t) W, p, r.gab, r.epf_iters, st->d_sigma, s);
 	marks.mark(1);
+	if (rgba_dev) if (uint32_t e = apply_patches(h, const_cast<float *>(st->d_restored), s)) return e;   // (the filters' own buffer: nothing else reads it before the next decode)
 	if (!rgba_dev) {}   // (planes are wanted, not pixels: d_restored is the result)
 	else if (st->ycbcr) ycbcr_tail_444(h, st->d_restored, (size_t) W, rgba_dev, stride_bytes, s);   // (the filtered planes are Cb, Y, Cr)
 	else if (colour) { if (uint32_t e = colour_pixels(h, st->d_restored, rgba_dev, stride_bytes, s)) return e; }
@@ -460,7 +490,7 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 // One VarDCT decode as decode_impl (whole frames, group ranges), decode_region (covers), decode_scaled and decode_frame_xyb describe it to
 // run_vardct; as it stands, the whole frame from the frame's own lists, with nothing to write to yet
 struct VardctRun {
-	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged), colour(r.colour) {}
+	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged), colour(r.colour), patches(r.patches) {}
 	int32_t first_group = 0, num_groups; // the groups of the entropy launch ...
 	const RegionCover *cover = nullptr;  // ... or (not null) a region's cover: through the fast kernel's order list (region.d_order), else a launch per row of its groups
 	const DevVarblock *list; const int32_t *class_start;   // what the pixel kernels take
@@ -469,6 +499,7 @@ struct VardctRun {
 	int restoration;                     // the route's: the mode the restoration filters run in (0: they do not; never where `whole` is false)
 	bool alpha_merged;                   // the route's
 	bool colour;                         // the route's: the pixels come from k_colour_tail (whole frames at full size: the route stages everything else)
+	bool patches;                        // the route's: the frame's patches go onto its XYB planes ahead of the tail (whole frames at full size, likewise)
 	const uint8_t *crop_from = nullptr; uint8_t *crop_to = nullptr; size_t crop_stride = 0; int32_t crop_w = 0, crop_h = 0;   // crop_to not null: these pixels of img are then moved there
 	int32_t shift = 0;                   // the scale shift the pixel kernels write at (decode_scaled's fused route: img is the small image)
 	float *xyb_out = nullptr;            // not null (an LF frame of a sequence, decode_frame_xyb): no pixels, img is null -- the three XYB planes, width * height
@@ -527,9 +558,9 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 		// the restoration filters asked for and signalled: the pixel kernels leave the samples in XYB planes, Gaborish and the
 		// edge-preserving filter run over the whole picture, the colour tail follows on the filtered planes (restore_kernels.h)
 		if (uint32_t e = decode_restored(h, run.img, run.img_stride, rmode, s, run.colour)) return e;
-	} else if (run.colour) {
+	} else if (run.colour || run.patches) {
 		if (!run.whole || run.shift || run.cover) return ERR_TODO;   // (cannot happen: full_size_first)
-		if (uint32_t e = colour_unfiltered(h, run.class_start, run.list, run.img, run.img_stride, s)) return e;
+		if (uint32_t e = planes_unfiltered(h, run.class_start, run.list, run.img, run.img_stride, s, run.colour)) return e;
 	} else if (st->ycbcr) {
 		if (uint32_t e = ycbcr_pixels(h, run.class_start, run.list, run.img, run.img_stride, s)) return e;
 	} else launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, K2Target{run.img, run.img_stride, out_mode(h), run.shift}, s);

@@ -82,6 +82,13 @@ static uint32_t read_modular_xyb(j40hip_frame *h, float *out) {
 	return hipMemcpy(out, d, sizeof(float) * 3 * plane, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
 }
 extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out) {
+	// (stage 3, a frame with patches: the planes the last decode left after k_patch_blend, ahead of its tail)
+	// (patch_planes lives in the upload's own state, which every upload makes anew: it names a buffer of this upload or nothing)
+	if (stage == 3) return guarded([&]() -> uint32_t {
+		if (!h || !h->dev || !h->dev->patch_planes || !h->frame.fh.has_patches || !out) return ERR_RNGE;
+		if (hipSetDevice(h->dev->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ERR_GPU;
+		return hipMemcpy(out, h->dev->patch_planes, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+	});
 	if (h && h->dev && h->dev->is_modular && stage == 0 && h->modular_xyb_used && j40hip_modular_xyb_on(h)) return guarded([&] { return read_modular_xyb(h, out); });
 	// (the colour mode without the filters: the planes the last decode's k_colour_tail read, stages 0 and 1 alike)
 	if (h && h->dev && !h->dev->restore_ran && h->colour_used && h->dev->colour_planes && (stage == 0 || stage == 1) && out) {

@@ -20,6 +20,12 @@ struct j40hip_sequence_device {
 	CacheBlock lf_slot[4];
 	int32_t lf_w[4] = {0, 0, 0, 0}, lf_h[4] = {0, 0, 0, 0};
 	bool lf_filled[4] = {false, false, false, false};
+	// patches (J40HIP_SEQ_PATCHES): reference slot k as a reference-only frame fills it -- three planes of float32 (X, Y, B), ref_w x ref_h
+	// each, one behind the other; taken at the upload for the largest such frame the index stores there. A slot holds these planes or
+	// pixels (`slot`), whichever the playback put there last
+	CacheBlock ref_xyb[4];
+	int32_t ref_w[4] = {0, 0, 0, 0}, ref_h[4] = {0, 0, 0, 0};
+	bool ref_filled[4] = {false, false, false, false};
 	int64_t cursor = 0;          // the next coded frame
 	int64_t decoded = 0;         // coded frames [0, decoded) have been enqueued since the last rewind
 };
@@ -43,14 +49,16 @@ size_t staging_bound(const j40hip_sequence *s, int32_t w, int32_t h) { return 32
 bool reserve_blocks(j40hip_sequence *s) {
 	j40hip_sequence_device *d = s->dev;
 	d->slot_stride = ((size_t) s->im.width * seq_pixel_bytes(s) + 15) & ~(size_t) 15;
-	size_t staging = 0, lf_bytes[4] = {0, 0, 0, 0};
+	size_t staging = 0, lf_bytes[4] = {0, 0, 0, 0}, ref_bytes[4] = {0, 0, 0, 0};
 	for (const j40hip_sequence::Row &row : s->rows) {
 		if (row.code) break;
+		if (row.stored_xyb) { size_t &b = ref_bytes[row.xyb_slot]; b = std::max(b, sizeof(float) * 3 * (size_t) row.fh.width * (size_t) row.fh.height); continue; }
 		if (row.fh.type == 1) { size_t &b = lf_bytes[row.fh.lf_level - 1]; b = std::max(b, sizeof(float) * 3 * (size_t) row.fh.width * (size_t) row.fh.height); continue; }
 		if (row.saved && !d->slot[row.fh.save_as_ref].ensure(d->device, slot_bytes(s), false)) return false;
 		if (row.blended || !(row.fh.x0 == 0 && row.fh.y0 == 0 && row.fh.width == s->im.width && row.fh.height == s->im.height)) staging = std::max(staging, staging_bound(s, row.fh.width, row.fh.height));
 	}
 	for (int k = 0; k < 4; ++k) if (lf_bytes[k] && !d->lf_slot[k].ensure(d->device, lf_bytes[k], false)) return false;
+	for (int k = 0; k < 4; ++k) if (ref_bytes[k] && !d->ref_xyb[k].ensure(d->device, ref_bytes[k], false)) return false;
 	return !staging || d->staging.ensure(d->device, staging, false);
 }
 
@@ -91,6 +99,45 @@ uint32_t play_lf_frame(j40hip_sequence *s, int64_t k, j40hip_frame *h, hipStream
 	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 }
 
+// A reference-only frame (type 2): its XYB planes into its reference slot, nothing composed, nothing shown
+uint32_t play_ref_frame(j40hip_sequence *s, int64_t k, j40hip_frame *h, hipStream_t stream, bool sync) {
+	j40hip_sequence_device *d = s->dev;
+	const j40hip_sequence::Row &row = s->rows[(size_t) k];
+	const FrameHeader &fh = row.fh;
+	const int slot = row.xyb_slot;
+	const size_t bytes = sizeof(float) * 3 * (size_t) fh.width * (size_t) fh.height;
+	if (slot < 0 || slot > 3 || !d->ref_xyb[slot].ptr || d->ref_xyb[slot].bytes < bytes) return ERR_GPU;   // (reserve_blocks sized it)
+	float *planes = (float *) d->ref_xyb[slot].ptr;
+	uint32_t e = decode_frame_xyb(h, planes, stream);
+	if (e) return e;
+	d->decoded = std::max(d->decoded, k + 1);
+	if (sync) {
+		if (hipStreamSynchronize(stream) != hipSuccess) return ERR_GPU;
+		e = j40hip_frame_status(h);
+		if (e == ERR_EVOF) {   // (as play_frame: dense planes)
+			h->force_dense = true;
+			if ((e = j40hip_frame_upload(h, d->device)) != 0 || (e = decode_frame_xyb(h, planes, stream)) != 0) return e;
+			if (hipStreamSynchronize(stream) != hipSuccess) return ERR_GPU;
+			e = j40hip_frame_status(h);
+		}
+		if (e) return e;
+	}
+	d->ref_w[slot] = fh.width; d->ref_h[slot] = fh.height; d->ref_filled[slot] = true;
+	d->slot_saved[slot] = false;   // (the slot holds planes now: no pixels for a later frame to draw over)
+	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
+}
+
+// the reference slots a frame with patches reads, as the playback last filled them ("ptno": it never did)
+uint32_t bind_patch_sources(j40hip_sequence *s, const j40hip_sequence::Row &row, j40hip_frame *h) {
+	j40hip_sequence_device *d = s->dev;
+	for (int k = 0; k < 4; ++k) {
+		const bool read = (row.patches.slots >> k & 1) != 0;
+		if (read && (!d->ref_filled[k] || !d->ref_xyb[k].ptr)) return ERR4('p', 't', 'n', 'o');
+		j40hip_frame_bind_patch_source(h, k, read ? (const float *) d->ref_xyb[k].ptr : nullptr, read ? d->ref_w[k] : 0, read ? d->ref_h[k] : 0);
+	}
+	return 0;
+}
+
 uint8_t *slot_image(j40hip_sequence *s, int k) {
 	const CacheBlock &b = s->dev->slot[k];
 	return b.ptr && b.bytes >= slot_bytes(s) ? (uint8_t *) b.ptr : nullptr;
@@ -115,6 +162,7 @@ uint32_t play_frame(j40hip_sequence *s, int64_t k, uint8_t *out, size_t out_stri
 	if (!h || !h->dev || h->dev->device != d->device) return ERR_GPU;
 	const FrameHeader &fh = row.fh;
 	if (fh.type == 1) return play_lf_frame(s, k, h, stream, sync);
+	if (row.stored_xyb) return play_ref_frame(s, k, h, stream, sync);
 	// (the main frame of an LF-frame still takes a scale and the orientation for decodes of its own, capi.hpp: the canvas is full size, stored order)
 	if (uint32_t e = mode_refusal(h, Mode::Playback)) return e;
 	const int32_t W = s->im.width, H = s->im.height;
@@ -128,6 +176,7 @@ uint32_t play_frame(j40hip_sequence *s, int64_t k, uint8_t *out, size_t out_stri
 	uint8_t *img = dst; size_t img_stride = dst_stride;
 	if (!exact) { img = staging_image(s, dst, dst_stride, fh.width, fh.height, r.fx, r.cx0, &img_stride); if (!img) return ERR_GPU; }
 	if (fh.use_lf_frame) { if (uint32_t e = bind_lf_source(s, h, fh.lf_level)) return e; }   // (its LfGroup tail reads the LF frame's picture)
+	if (fh.has_patches) { if (uint32_t e = bind_patch_sources(s, row, h)) return e; }        // (its patches read the reference-only frames' planes)
 	uint32_t e = j40hip_frame_decode(h, img, img_stride, stream);
 	if (e) return e;
 	d->decoded = std::max(d->decoded, k + 1);   // (enqueued: j40hip_sequence_status looks at it, whatever becomes of it)
@@ -151,7 +200,7 @@ uint32_t play_frame(j40hip_sequence *s, int64_t k, uint8_t *out, size_t out_stri
 		if (hipGetLastError() != hipSuccess) return ERR_GPU;
 	}
 	if (row.saved) {
-		d->slot_saved[fh.save_as_ref] = true;
+		d->slot_saved[fh.save_as_ref] = true; d->ref_filled[fh.save_as_ref] = false;   // (pixels take the place of a reference-only frame's planes)
 		if (out && hipMemcpy2DAsync(out, out_stride, dst, dst_stride, (size_t) W * pb, (size_t) H, hipMemcpyDeviceToDevice, stream) != hipSuccess) return ERR_GPU;
 	}
 	return 0;
@@ -184,6 +233,7 @@ extern "C" void j40hip_sequence_release_device(j40hip_sequence *s) {
 	auto give = [&](CacheBlock &b) { if (b.ptr) { b.release(waited); waited = true; } };   // (one device-wide wait covers them all)
 	for (CacheBlock &b : s->dev->slot) give(b);
 	for (CacheBlock &b : s->dev->lf_slot) give(b);
+	for (CacheBlock &b : s->dev->ref_xyb) give(b);
 	give(s->dev->staging);
 	delete s->dev;
 	s->dev = nullptr;
@@ -250,6 +300,8 @@ extern "C" void j40hip_sequence_rewind(j40hip_sequence *s) {
 	s->dev->cursor = s->dev->decoded = 0;
 	for (bool &b : s->dev->slot_saved) b = false;
 	for (bool &b : s->dev->lf_filled) b = false;
+	for (bool &b : s->dev->ref_filled) b = false;
+	for (j40hip_frame *h : s->frames) if (h) for (int k = 0; k < 4; ++k) j40hip_frame_bind_patch_source(h, k, nullptr, 0, 0);
 	// (no handle keeps reading a slot that the next playback fills again: a decode of its own is "lfno" until the playback has passed it)
 	static const float *const none[3] = {nullptr, nullptr, nullptr};
 	for (j40hip_frame *h : s->frames) if (h) j40hip_frame_bind_lf_source(h, none, 0, 0);
@@ -262,6 +314,58 @@ extern "C" uint32_t j40hip_sequence_read_lf_slot(j40hip_sequence *s, int32_t lev
 		const size_t plane = (size_t) d->lf_w[level - 1] * (size_t) d->lf_h[level - 1];
 		if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ERR_GPU;
 		return hipMemcpy(out, (const float *) d->lf_slot[level - 1].ptr + (size_t) c * plane, sizeof(float) * plane, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+	});
+}
+
+extern "C" uint32_t j40hip_sequence_ref_slot_size(j40hip_sequence *s, int32_t slot, int32_t *width, int32_t *height) {
+	if (!s || !s->dev || slot < 0 || slot > 3 || !width || !height || !s->dev->ref_filled[slot]) return ERR_RNGE;
+	*width = s->dev->ref_w[slot]; *height = s->dev->ref_h[slot];
+	return 0;
+}
+
+extern "C" uint32_t j40hip_sequence_read_ref_slot(j40hip_sequence *s, int32_t slot, int32_t c, float *out) {
+	return guarded([&]() -> uint32_t {
+		if (!s || !s->dev || slot < 0 || slot > 3 || c < 0 || c > 2 || !out || !s->dev->ref_filled[slot]) return ERR_RNGE;
+		const j40hip_sequence_device *d = s->dev;
+		const size_t plane = (size_t) d->ref_w[slot] * (size_t) d->ref_h[slot];
+		if (hipSetDevice(d->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ERR_GPU;
+		return hipMemcpy(out, (const float *) d->ref_xyb[slot].ptr + (size_t) c * plane, sizeof(float) * plane, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+	});
+}
+
+// known-answer / measuring hook: k_patch_blend on caller-supplied planes, slot planes and placement list (include/j40hip.h). The list is
+// checked and binned on the host and copied; the launch is enqueued on `stream` and waited for (the copies live until then)
+extern "C" uint32_t j40hip_kat_device_patches(float *planes_dev, int32_t width, int32_t height, const float *const slot_dev[4], const int32_t slot_w[4], const int32_t slot_h[4],
+		const int32_t *placements, int32_t count, int32_t *tiles_out, void *stream) {
+	return guarded([&]() -> uint32_t {
+		if (!planes_dev || width <= 0 || height <= 0 || (int64_t) width * height > (1 << 28) || !slot_dev || !slot_w || !slot_h || count < 0 || (count && !placements)) return ERR_RNGE;
+		PatchSlots slots;
+		for (int k = 0; k < 4; ++k) { slots.base[k] = slot_dev[k]; slots.w[k] = slot_w[k]; slots.h[k] = slot_h[k]; if (slot_dev[k] && (slot_w[k] <= 0 || slot_h[k] <= 0)) return ERR_RNGE; }
+		std::vector<PatchRec> recs((size_t) count);
+		for (int32_t i = 0; i < count; ++i) {
+			const int32_t *v = placements + (size_t) i * 9;   // x, y, w, h, sx, sy, slot, mode, clamp
+			if (v[8] != 0 && v[8] != 1) return ERR4('p', 't', 'c', 'h');
+			recs[(size_t) i] = PatchRec{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7] | v[8] << 8};
+			if (uint32_t e = patch_check(recs[(size_t) i], slots, width, height)) return e;
+		}
+		PatchBins bins;
+		if (!patch_bin(recs.data(), recs.size(), width, height, &bins)) return ERR4('p', 't', 'c', 'h');   // (more tile entries than patch_bin_limit)
+		if (tiles_out) *tiles_out = (int32_t) bins.tile_ids.size();
+		if (bins.tile_ids.empty()) return 0;
+		int device = 0;
+		if (hipGetDevice(&device) != hipSuccess) return ERR_GPU;
+		hipStream_t st = (hipStream_t) stream;
+		j40hip_device_state tmp; tmp.device = device;
+		bool ok = true;
+		DevPatches p;
+		p.recs = tmp.upload(recs.data(), recs.size(), st, ok); p.tile_ids = tmp.upload(bins.tile_ids.data(), bins.tile_ids.size(), st, ok);
+		p.offsets = tmp.upload(bins.offsets.data(), bins.offsets.size(), st, ok); p.index = tmp.upload(bins.index.data(), bins.index.size(), st, ok);
+		p.num_tiles = (int32_t) bins.tile_ids.size(); p.tiles_x = bins.tiles_x;
+		if (ok) { launch_patch_blend(planes_dev, width, height, p, slots, st); ok = hipGetLastError() == hipSuccess; }
+		if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+		for (auto &b : tmp.buffers) b.release();
+		tmp.buffers.clear();
+		return ok ? 0 : ERR_GPU;
 	});
 }
 

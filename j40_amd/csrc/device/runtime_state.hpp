@@ -195,6 +195,12 @@ struct j40hip_device_state {
 	struct ColourTail { bool ready = false; ColourTailParams p; } colour;
 	float *d_colour_xyb = nullptr;
 	const float *colour_planes = nullptr;
+	// a frame with patches (runtime.hip: apply_patches): the handle's records and tiles (j40hip_frame::patch_plan, made when the sequence's
+	// index was built) copied into the frame's scratch at the upload; d_frame: a Modular frame's colour
+	// constants as the sRGB tail takes them (a VarDCT frame's are its plan's). patch_planes: the planes the last decode left after its
+	// patches (j40hip_frame_read_xyb, stage 3)
+	struct Patches { DevPatches dev = {nullptr, nullptr, nullptr, nullptr, 0, 0}; std::vector<DevFrame> host_frame; const DevFrame *d_frame = nullptr; } patch;
+	const float *patch_planes = nullptr;
 	// a YCbCr frame (j40hip_frame_set_ycbcr; runtime.hip: ycbcr_pixels). ycbcr: the plan was built for one (the switch was on at upload).
 	// d_ycc: the planes the pixel kernels leave for k_ycbcr_tail, made at the first decode, kept with the frame. ycc_read: what the last
 	// decode's tail read (j40hip_frame_read_ycbcr) -- those planes, or the restoration filters' result
@@ -286,6 +292,7 @@ uint32_t upload_lf_only(j40hip_frame *h, int device, hipStream_t s);           /
 bool modular_groups_independent(const j40hip_frame *h);                        // runtime.hip
 uint32_t clear_before_decode(j40hip_device_state *st, hipStream_t s);          // runtime.hip
 uint32_t decode_frame_xyb(j40hip_frame *h, float *planes, hipStream_t s);      // runtime.hip
+uint32_t apply_patches(j40hip_frame *h, float *planes, hipStream_t s);         // runtime.hip
 uint32_t restore_params(const FrameHeader &fh, int mode, RestoreParams *p);    // runtime.hip
 void lf_services_shutdown();   // runtime_lf.hip, runtime.hip, runtime_lfp.hip: j40hip_shutdown's steps
 void two_phase_shutdown();

@@ -159,6 +159,28 @@ bool j40hip_rt::host_vb_sorted(j40hip_device_state *st) {
 	return true;
 }
 
+// A frame with patches: its records and their tiles, as the sequence's index made them (j40hip_frame::patch_plan, which outlives the
+// copies), into the frame's scratch; a Modular frame's colour constants for the sRGB tail beside them. Waits for the copies.
+static uint32_t upload_patches(j40hip_frame *h, hipStream_t s) {
+	if (!h->frame.fh.has_patches) return 0;
+	j40hip_device_state *st = h->dev;
+	j40hip_device_state::Patches &pt = st->patch;
+	if (!h->patch_plan) { j40hip_release_device(h); return ERR_TODO; }   // (cannot happen: only a sequence's handle parses a dictionary)
+	const PatchPlan &plan = *h->patch_plan;
+	bool ok = true;
+	if (!plan.bins.tile_ids.empty()) {
+		pt.dev.recs = st->upload(plan.recs.data(), plan.recs.size(), s, ok);
+		pt.dev.tile_ids = st->upload(plan.bins.tile_ids.data(), plan.bins.tile_ids.size(), s, ok);
+		pt.dev.offsets = st->upload(plan.bins.offsets.data(), plan.bins.offsets.size(), s, ok);
+		pt.dev.index = st->upload(plan.bins.index.data(), plan.bins.index.size(), s, ok);
+		pt.dev.num_tiles = (int32_t) plan.bins.tile_ids.size(); pt.dev.tiles_x = plan.bins.tiles_x;
+	}
+	if (st->is_modular) { pt.host_frame.assign(1, DevFrame()); fill_frame_constants(h->frame, pt.host_frame.data()); pt.d_frame = st->upload(pt.host_frame.data(), 1, s, ok); }
+	if (hipStreamSynchronize(s) != hipSuccess) ok = false;
+	if (!ok) { j40hip_release_device(h); return ERR_GPU; }
+	return 0;
+}
+
 // `s`: the stream the copies and fills are enqueued on; the call returns once they have completed (the plan is staged in the
 // calling thread's pinned buffer, which the next upload of this thread reuses)
 static uint32_t upload_impl(j40hip_frame *h, int device, hipStream_t s) {
@@ -170,7 +192,7 @@ static uint32_t upload_impl(j40hip_frame *h, int device, hipStream_t s) {
 	// (a frame the Modular XYB switch may be put in force for: its colour tail reads the sRGB thresholds, which a Modular upload never needed --
 	// taken here, once per device, so that the decode entry points stay asynchronous)
 	if (h->frame.fh.is_modular && j40hip_modular_xyb_applies(h) && !ensure_constant_tables(device)) return ERR_GPU;
-	if (h->frame.fh.is_modular) return upload_modular(h, device);
+	if (h->frame.fh.is_modular) { const uint32_t e = upload_modular(h, device); return e ? e : upload_patches(h, s); }
 	HostPlan &hp = t_host_plan;   // (this thread's, storage kept from frame to frame)
 	hp.reset();
 	hp.force_dense = h->force_dense;
@@ -278,7 +300,7 @@ static uint32_t upload_impl(j40hip_frame *h, int device, hipStream_t s) {
 	if (t_lf_done ? (hipEventRecord(t_lf_done, s) != hipSuccess || hipEventSynchronize(t_lf_done) != hipSuccess) : hipStreamSynchronize(s) != hipSuccess) ok = false;
 	if (timing) fprintf(stderr, "[j40hip upload] plan build %.2f ms (%d threads), staging %.2f ms (%.1f MB), copy + LfGroup tail + wait %.2f ms\n", tu1 - tu0, h->threads, tu2 - tu1, (double) copy_bytes / 1e6, now() - tu2);
 	if (!ok) { j40hip_release_device(h); return ERR_GPU; }
-	return 0;
+	return upload_patches(h, s);
 }
 
 extern "C" void j40hip_frame_force_dense(j40hip_frame *h, int dense) { if (h) h->force_dense = dense != 0; }

@@ -283,15 +283,15 @@ static void read_image_metadata(BitReader &br, ImageMeta *im, bool allow_wide) {
 // frame header (j40.h:5163)
 
 // `sequence`: the frame belongs to a frame sequence, which refuses the types it does not serve as soon as it has read them
-// `lf_frames`: ... and the sequence serves LF frames (type 1)
-static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f, bool sequence = false, bool lf_frames = false) {
+// `lf_frames`: ... and the sequence serves LF frames (type 1), `patches`: and reference-only frames (type 2)
+static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f, bool sequence = false, bool lf_frames = false, bool patches = false) {
 	f->width = im.width; f->height = im.height;
 	f->ec_blend.assign(im.ec.size(), FrameHeader::Blend());
 	br.zero_pad_to_byte();
 	if (!br.u(1)) {
 		bool full_frame = true;
 		f->type = (int32_t) br.u(2);
-		if (sequence) J40HIP_SHOULD(f->type == 0 || f->type == 3 || (lf_frames && f->type == 1), "TODO");
+		if (sequence) J40HIP_SHOULD(f->type == 0 || f->type == 3 || (lf_frames && f->type == 1) || (patches && f->type == 2), "TODO");
 		f->is_modular = br.u(1);
 		uint64_t flags = br.u64();
 		f->has_noise = flags & 1; f->has_patches = flags >> 1 & 1; f->has_splines = flags >> 4 & 1;
@@ -452,7 +452,12 @@ static void init_global_modular(Frame *f) {  // j40.h:3619
 
 static void read_lf_global(BitReader &br, Frame *f) {
 	const FrameHeader &fh = f->fh;
-	J40HIP_SHOULD(!fh.has_patches && !fh.has_splines && !fh.has_noise, "TODO");
+	J40HIP_SHOULD((!fh.has_patches || f->allow_patches) && !fh.has_splines && !fh.has_noise, "TODO");
+	if (fh.has_patches) {   // the dictionary, ahead of everything else (splines and noise would follow it)
+		J40HIP_SHOULD(f->im.xyb_encoded && fh.type != 2 && fh.type != 1, "TODO");
+		read_patch_dictionary(br, f->im, fh, &f->patches);
+		J40HIP_SHOULD(!f->patches.unserved, "TODO");
+	}
 	if (!br.u(1)) for (int i = 0; i < 3; ++i) f->m_lf_scaled[i] = br.f16() / 128.0f;
 	if (!fh.is_modular) {
 		f->global_scale = br.u32(1, 11, 2049, 11, 4097, 12, 8193, 16);
@@ -903,8 +908,10 @@ int32_t rendered_alpha_channel(const ImageMeta &im) {
 	for (size_t i = 0; i < im.ec.size(); ++i) if (im.ec[i].type == EC_ALPHA) return (int32_t) i;
 	return -1;
 }
-uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, bool lf_frames, bool xyb, bool modular_lf) {
+uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, bool lf_frames, bool xyb, bool modular_lf, bool patches, bool modular_ref) {
 	bool ok = (fh.type == 0 || fh.type == 3) && !fh.use_lf_frame;
+	// (a reference-only frame: the XYB planes of a frame that decode_frame_xyb serves, saved before the colour transform)
+	if (patches && fh.type == 2) ok = fh.save_before_ct && xyb && !fh.has_patches && !fh.use_lf_frame && !fh.do_ycbcr && (!fh.is_modular || modular_ref);
 	if (lf_frames && (fh.type == 1 || fh.use_lf_frame)) ok = (fh.type == 0 || fh.type == 3 || (fh.type == 1 && (!fh.is_modular || (modular_lf && !fh.do_ycbcr)))) && xyb && !(fh.use_lf_frame && (fh.do_ycbcr || fh.is_modular))
 		&& !(fh.type == 1 && !fh.ec_blend.empty());   // (an LF frame with extra channels behind its coefficients: nothing here keeps or checks them)
 	if (!blend) {
@@ -917,12 +924,77 @@ uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, b
 	}
 	return ok ? 0 : (uint32_t) E4("TODO");
 }
-void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, bool lf_frames, FrameHeader *fh, Toc *toc, bool modular_lf) {
+void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, bool lf_frames, FrameHeader *fh, Toc *toc, bool modular_lf, bool patches, bool modular_ref) {
 	J40HIP_SHOULD(offset < cs_size, "shrt");
 	BitReader br(cs + offset, cs_size - offset);
-	read_frame_header(br, im, fh, true, lf_frames);
-	if (uint32_t e = sequence_refusal(*fh, blend, rendered_alpha_channel(im), lf_frames, im.xyb_encoded, modular_lf)) raise(e);
+	read_frame_header(br, im, fh, true, lf_frames, patches);
+	if (uint32_t e = sequence_refusal(*fh, blend, rendered_alpha_channel(im), lf_frames, im.xyb_encoded, modular_lf, patches, modular_ref)) raise(e);
 	read_toc(br, *fh, toc);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the patch dictionary. PARITY UNPINNED: the reference stops at has_patches (j40.h:6262); this is the standard's layout as far as it
+// can be recalled without the text. One entropy-coded stream over 10 contexts of hybrid integers: the number of
+// reference patches (context 0); per reference patch its slot (1), x0 and y0 in the reference frame (3), width - 1 and height - 1 (2),
+// count - 1 (7); per placement x and y -- the first one's as they are (4), a later one's as the sign-folded difference to the placement
+// before (6) -- and once for each of num_extra_channels + 1 blend entries, the colour channels' first, the mode (5), an alpha channel
+// (8; with mode >= 4 and more than one extra channel) and clamp (9; with mode >= 3).
+void read_patch_dictionary(BitReader &br, const ImageMeta &im, const FrameHeader &fh, PatchDictionary *out) {
+	*out = PatchDictionary();
+	CodeSpec spec;
+	read_code_spec(br, 10, &spec);
+	CodeState code(&spec);
+	auto get = [&](int32_t ctx) { return decode_symbol(br, code, ctx, 0); };
+	// what a damaged stream can make the host allocate: as many reference patches as a frame of this size could hold, four placements each
+	const int64_t max_ref = 1024 + (int64_t) fh.width * fh.height / 4, max_placements = 4 * max_ref;
+	const int32_t num_ref = get(0);
+	J40HIP_SHOULD(num_ref >= 0 && num_ref <= max_ref, "ptch");
+	out->num_ref = num_ref;
+	const size_t entries = im.ec.size() + 1;
+	for (int32_t i = 0; i < num_ref; ++i) {
+		PatchPlacement p;
+		memset(&p, 0, sizeof p);
+		p.source = i;
+		p.ref = get(1);
+		J40HIP_SHOULD(p.ref >= 0 && p.ref <= 3, "ptch");
+		p.sx = get(3); p.sy = get(3);
+		const int32_t w1 = get(2), h1 = get(2);
+		J40HIP_SHOULD(p.sx >= 0 && p.sy >= 0 && w1 >= 0 && h1 >= 0 && w1 < (1 << 18) && h1 < (1 << 18) && p.sx < (1 << 18) && p.sy < (1 << 18), "ptch");   // (no reference frame is larger)
+		p.w = w1 + 1; p.h = h1 + 1;
+		const int32_t count1 = get(7);
+		J40HIP_SHOULD(count1 >= 0 && (int64_t) out->placements.size() + count1 + 1 <= max_placements, "ptch");
+		for (int32_t j = 0; j <= count1; ++j) {
+			if (j == 0) { p.x = get(4); p.y = get(4); J40HIP_SHOULD(p.x >= 0 && p.y >= 0, "ptch"); }
+			else {
+				const int64_t x = (int64_t) p.x + unpack_signed(get(6)), y = (int64_t) p.y + unpack_signed(get(6));
+				J40HIP_SHOULD(x >= 0 && y >= 0 && x <= INT32_MAX && y <= INT32_MAX, "ptch");   // a negative coordinate
+				p.x = (int32_t) x; p.y = (int32_t) y;
+			}
+			J40HIP_SHOULD((int64_t) p.x + p.w <= fh.width && (int64_t) p.y + p.h <= fh.height, "ptch");   // the placement leaves the frame
+			p.mode = 0; p.clamp = 0;
+			for (size_t e = 0; e < entries; ++e) {
+				const int32_t mode = get(5);
+				J40HIP_SHOULD(mode >= 0 && mode <= 7, "ptch");
+				int32_t clamp = 0;
+				if (mode >= 4 && im.ec.size() > 1) { const int32_t a = get(8); J40HIP_SHOULD(a >= 0 && (size_t) a < im.ec.size(), "ptch"); }
+				if (mode >= 3) { clamp = get(9); J40HIP_SHOULD(clamp == 0 || clamp == 1, "ptch"); }
+				if (e == 0) { p.mode = mode; p.clamp = clamp; if (mode >= 4) out->unserved = true; }
+				else if (mode != 0) out->unserved = true;
+			}
+			out->placements.push_back(p);
+			out->slots |= 1u << p.ref;
+		}
+	}
+	finish_code(br, code);
+}
+
+void parse_sequence_patches(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, const FrameHeader &fh, const Toc &toc, PatchDictionary *out) {
+	// LfGlobal: the frame's one section (read to the end of the codestream, as parse_frame reads it), or the section the TOC names
+	const Section sec = toc.single ? toc.single_section : toc.lf_global;
+	const size_t at = std::min(cs_size, offset + sec.offset);
+	const size_t size = toc.single ? cs_size - at : std::min(sec.size, cs_size - at);
+	BitReader br(cs + at, size);
+	read_patch_dictionary(br, im, fh, out);
 }
 
 static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size, Frame *f) {
@@ -930,8 +1002,8 @@ static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size
 	BitReader br(cs, limit);
 	if (f->seq_im) {   // a sequence's member: its bytes start at the frame header
 		f->im = *f->seq_im;
-		read_frame_header(br, f->im, &f->fh, true, f->allow_lf_frame);
-		if (uint32_t e = sequence_refusal(f->fh, f->seq_blend, rendered_alpha_channel(f->im), f->allow_lf_frame, f->im.xyb_encoded, f->allow_modular_lf)) raise(e);
+		read_frame_header(br, f->im, &f->fh, true, f->allow_lf_frame, f->allow_patches);
+		if (uint32_t e = sequence_refusal(f->fh, f->seq_blend, rendered_alpha_channel(f->im), f->allow_lf_frame, f->im.xyb_encoded, f->allow_modular_lf, f->allow_patches, f->allow_modular_ref)) raise(e);
 	} else {
 		read_image_header(br, &f->im, f->allow_wide);
 		read_frame_header(br, f->im, &f->fh);

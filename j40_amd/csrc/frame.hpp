@@ -114,6 +114,17 @@ struct FrameHeader {
 
 struct Section { size_t offset = 0, size = 0; };  // byte range inside the codestream
 
+// The patch dictionary at the head of LfGlobal (a frame with has_patches; read with Frame::allow_patches only). PARITY UNPINNED: the
+// reference holds no code for it (j40.h:6262). A placement puts the w x h samples at (sx, sy) of the reference-only frame in slot `ref`
+// onto the frame's XYB samples at (x, y), in the colour channels' blend mode (0 None, 1 Replace, 2 Add, 3 Mul; 4..7 use alpha)
+struct PatchPlacement { int32_t x, y, w, h, sx, sy, ref, mode, clamp, source; };   // source: which reference patch of the dictionary it places
+struct PatchDictionary {
+	int32_t num_ref = 0;                        // reference patches
+	std::vector<PatchPlacement> placements;     // flat, in dictionary order
+	uint32_t slots = 0;                         // bit k: a placement reads slot k
+	bool unserved = false;                      // a mode 4..7, or an extra channel's entry other than None: parsed, "TODO"
+};
+
 struct Toc {
 	bool single = false;
 	Section single_section;               // when the frame has exactly one section: readable to the end of the codestream like in the
@@ -241,6 +252,11 @@ struct Frame {
 	// ... and Modular LF frames among them (the sequence also renders Modular frames of XYB images through the XYB colour tail,
 	// J40HIP_SEQ_MODULAR_XYB or J40HIP_MODULAR_XYB=1: k_modular_to_xyb fills the LF slot). Set before parse_frame.
 	bool allow_modular_lf = false;
+	// Patches are asked for (a sequence opened with J40HIP_SEQ_PATCHES or J40HIP_PATCHES=1): a sequence's member of type 2 is taken, and a
+	// frame with has_patches is parsed -- its dictionary into `patches` -- instead of refused with "TODO". Set before parse_frame.
+	bool allow_patches = false;
+	bool allow_modular_ref = false;   // ... and Modular reference-only frames among them (the sequence has the Modular XYB switch too)
+	PatchDictionary patches;
 	bool wide() const { return !im.modular_16bit_buffers; }
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
@@ -249,6 +265,7 @@ struct Frame {
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
 		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr; g.allow_wide = allow_wide; g.allow_lf_frame = allow_lf_frame; g.allow_modular_lf = allow_modular_lf;
+		g.allow_patches = allow_patches; g.allow_modular_ref = allow_modular_ref;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section
@@ -267,7 +284,13 @@ void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t
 // header and TOC of the frame that starts at byte `offset` of the codestream, for a sequence's index: nothing behind the TOC is
 // read. The TOC's offsets count from `offset`. Raises what the header or the TOC raise, "TODO" for what sequence_refusal refuses.
 // blend: the sequence serves the blend modes other than Replace, lf_frames: and LF frames (sequence_refusal).
-void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, bool lf_frames, FrameHeader *fh, Toc *toc, bool modular_lf = false);
+// patches: and reference-only frames (type 2), modular_ref: Modular ones among them.
+void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, bool blend, bool lf_frames, FrameHeader *fh, Toc *toc, bool modular_lf = false, bool patches = false, bool modular_ref = false);
+// the patch dictionary of a frame with has_patches (`im`: its image's metadata, the size is the frame's own). Raises "shrt", the entropy
+// code's errors and "ptch"; a dictionary that parses but is not served comes back with `unserved` set
+void read_patch_dictionary(BitReader &br, const ImageMeta &im, const FrameHeader &fh, PatchDictionary *out);
+// ... of the frame whose header starts at byte `offset` of the codestream and whose TOC (offsets from `offset`) is `toc`, for a sequence's index
+void parse_sequence_patches(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, const FrameHeader &fh, const Toc &toc, PatchDictionary *out);
 // the extra channel whose samples become the pixels' A (plan_build.cpp: alpha_channel): the first one of type alpha; -1: none
 int32_t rendered_alpha_channel(const ImageMeta &im);
 // 0, or "TODO": the frame is of a kind a sequence does not serve -- types 1 and 2, use_lf_frame, and a blend mode other than Replace
@@ -276,7 +299,9 @@ int32_t rendered_alpha_channel(const ImageMeta &im);
 // channel than `alpha_ec`. With `lf_frames` type 1 and use_lf_frame pass, unless the LF frame is a Modular one and `modular_lf` is not
 // set (without the Modular XYB switch nothing renders Modular samples to XYB floats) or of an image with extra channels, the image is not XYB encoded (`xyb`), or the frame with use_lf_frame is a
 // YCbCr or Modular one
-uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, bool lf_frames = false, bool xyb = true, bool modular_lf = false);
+// With `patches` a reference-only frame (type 2) passes where it is saved before the colour transform, of an XYB image, has no patches of
+// its own and is a VarDCT frame or `modular_ref` is set.
+uint32_t sequence_refusal(const FrameHeader &fh, bool blend, int32_t alpha_ec, bool lf_frames = false, bool xyb = true, bool modular_lf = false, bool patches = false, bool modular_ref = false);
 
 // parses headers, TOC, LfGlobal, HfGlobal and every LfGroup section. `threads` > 1 decodes LfGroup
 // sections concurrently (they are independent given LfGlobal)

@@ -51,10 +51,65 @@ struct SeqFrame {
 	int ec_blend = 0, ec_src = 0;     // the extra channels' blend mode and source slot (the colour channels' unless ecblends= / ecsrcs= say otherwise)
 	long long duration = 0;
 	bool is_last = true;
+	int type = 0;                     // types=: 0 a regular frame, 2 a reference-only frame (its own size, no origin, no blend info, never last)
+	int save_before_ct = 1;           // ... whose save_before_color_transform bit is this (sbct=0: a stream a decoder has to refuse)
 	std::vector<uint8_t> *cs = nullptr;   // the codestream so far
 	size_t first_section = 0;         // out: where this frame's first section starts in `cs`
 };
 static SeqFrame *g_seq = nullptr;
+
+// patches=: the patch dictionary of the frame being written. A reference patch is the w x h rectangle at (x0, y0) of the reference-only
+// frame in slot `ref`; every placement puts it at (x, y) of the frame in blend mode `mode` (0 None, 1 Replace, 2 Add, 3 Mul, 4..7 the
+// alpha-using ones) with `clamp`. Nothing is checked: a dictionary a decoder has to refuse -- a mode above 7, a slot above 3, a rectangle
+// or a placement outside its frame, a later placement left of or above the frame -- is written as it stands.
+//   twin (patchtwin=1): the frame without the flag and without the dictionary, every other byte alike
+//   ec_mode (patchec=M): the mode of every extra channel's blend entry (default 0, None)
+//   cut (patchcut=1): LfGlobal ends in the middle of the dictionary (frames with several sections)
+struct PatchPlace { long long x, y; int mode, clamp; };
+struct PatchRef { int ref, x0, y0, w, h; std::vector<PatchPlace> at; };
+struct PatchRole { std::vector<PatchRef> refs; bool twin = false; int ec_mode = 0; bool cut = false; };
+static PatchRole *g_patch = nullptr;
+static bool patch_flag() { return g_patch && !g_patch->twin; }
+// One entropy-coded stream over 10 contexts (three clusters, ANS): num_ref (context 0); per reference patch ref (1), x0, y0 (3), w - 1,
+// h - 1 (2), count - 1 (7); per placement x, y (4; from the second on the sign-folded differences to the one before, 6) and for each of
+// num_ec + 1 blend entries the mode (5), the alpha channel (8; mode >= 4 and more than one extra channel) and clamp (9; mode >= 3)
+static void write_patch_dictionary(BitWriter &bw, int num_ec) {
+	if (!patch_flag()) return;
+	CodeSpecW spec;
+	std::vector<uint8_t> map(10);
+	for (int i = 0; i < 10; ++i) map[(size_t) i] = (uint8_t) (i % 3);
+	spec.init(10, map, 3);
+	spec.log_alpha = 8;
+	for (auto &c : spec.cfg) c = HybridCfg{4, 2, 0};
+	StreamEncoder enc(spec);
+	auto fold = [](long long v) { return (uint32_t) (v >= 0 ? 2 * v : -2 * v - 1); };
+	enc.add(0, (uint32_t) g_patch->refs.size());
+	for (const PatchRef &r : g_patch->refs) {
+		enc.add(1, (uint32_t) r.ref); enc.add(3, (uint32_t) r.x0); enc.add(3, (uint32_t) r.y0); enc.add(2, (uint32_t) (r.w - 1)); enc.add(2, (uint32_t) (r.h - 1));
+		enc.add(7, (uint32_t) (r.at.size() - 1));
+		for (size_t j = 0; j < r.at.size(); ++j) {
+			const PatchPlace &q = r.at[j];
+			if (j == 0) { enc.add(4, (uint32_t) q.x); enc.add(4, (uint32_t) q.y); }
+			else { enc.add(6, fold(q.x - r.at[j - 1].x)); enc.add(6, fold(q.y - r.at[j - 1].y)); }
+			for (int e = 0; e <= num_ec; ++e) {
+				const int mode = e == 0 ? q.mode : g_patch->ec_mode;
+				enc.add(5, (uint32_t) mode);
+				if (mode >= 4 && num_ec > 1) enc.add(8, 0);
+				if (mode >= 3) enc.add(9, (uint32_t) (e == 0 ? q.clamp : 0));
+			}
+		}
+	}
+	count_stream(spec, enc);
+	write_code_spec(bw, spec);
+	enc.flush(bw);
+}
+// patchcut=1: true when LfGlobal is to end here, in the middle of the dictionary that has just been written into the empty `bw`
+static bool cut_patch_dictionary(BitWriter &bw) {
+	if (!patch_flag() || !g_patch->cut) return false;
+	bw.pad();
+	bw.bytes.resize(bw.bytes.size() / 2);
+	return true;
+}
 
 // LF frames (lflevels=1|2; run_lf_sequence): what the VarDCT writer is told about the frame it writes, and what it hands back for the
 // next one. The planes of integers are frame-wide, ceil(W / 8) cells a row, in streamed order Y, X, B.
@@ -170,6 +225,13 @@ static void write_frame_placement(BitWriter &cs, int num_ec, int frame_w, int fr
 	}
 	const SeqFrame &q = *g_seq;
 	bool full_frame = true;
+	if (q.type == 2) {   // a reference-only frame: its size alone, no blend info, no duration, never last (j40.h:5285-5336)
+		cs.put(q.have_crop ? 1 : 0, 1);
+		if (q.have_crop) { crop_u32(frame_w); crop_u32(frame_h); }
+		cs.put((uint64_t) q.save, 2);
+		cs.put((uint64_t) q.save_before_ct, 1);
+		return;
+	}
 	cs.put(q.have_crop ? 1 : 0, 1);
 	if (q.have_crop) {
 		crop_u32(pack_signed(q.x0)); crop_u32(pack_signed(q.y0)); crop_u32(frame_w); crop_u32(frame_h);
@@ -1278,7 +1340,10 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 
 	// ---- assemble sections ----
 	std::vector<std::vector<uint8_t>> sections;
-	auto write_lf_global = [&](BitWriter &bw) {   // LfGlobal (j40.h:6257)
+	auto write_lf_global = [&](BitWriter &section) {   // LfGlobal (j40.h:6257)
+		write_patch_dictionary(section, num_ec);                 // (patches=: the dictionary comes first)
+		BitWriter dropped;                                       // (patchcut=1: the rest is written all the same, the code specs' tables are made here)
+		BitWriter &bw = cut_patch_dictionary(section) ? dropped : section;
 		bw.put(1, 1);                                            // LF channel dequantisation: default
 		bw.u32(global_scale, 1, 11, 2049, 11, 4097, 12, 8193, 16);
 		bw.u32(quant_lf, 16, 0, 1, 5, 1, 8, 1, 16);
@@ -1456,9 +1521,10 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		cs.put(0, 1);
 		const bool lf_frame = g_lf && g_lf->level > 0, use_lf_frame = g_lf && g_lf->use;
 		if ((lf_frame || use_lf_frame) && !g_seq) die("vardct: an LF frame, and a frame with use_lf_frame, is written by lflevels= only");
-		cs.put(lf_frame ? 1 : 0, 2);        // regular frame (an LF frame: type 1)
+		const int seq_type = g_seq ? g_seq->type : 0;
+		cs.put(lf_frame ? 1 : (uint64_t) seq_type, 2);   // regular frame (an LF frame: type 1; types=: a reference-only frame, type 2)
 		cs.put(0, 1);                       // VarDCT
-		cs.u64((skip_smooth ? 128 : 0) | (use_lf_frame ? 32 : 0));      // flags
+		cs.u64((skip_smooth ? 128 : 0) | (use_lf_frame ? 32 : 0) | (patch_flag() ? 2 : 0));      // flags
 		if (noxyb) cs.put(ycbcr ? 1 : 0, 1);   // do_ycbcr (read only without xyb_encoded)
 		// (jpegup=N: the header says N whatever the stream holds -- a layout the decoder has to refuse before it reads anything of it)
 		if (ycbcr) cs.put((uint64_t) opt.geti("jpegup", jpeg_upsampling), 6);   // jpeg_upsampling (read with do_ycbcr)
@@ -1467,7 +1533,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		for (int i = 0; i < num_ec; ++i) cs.put(0, 2);   // ec_log_upsampling
 		}
 		if (!noxyb) { cs.put((uint64_t) x_qm, 3); cs.put((uint64_t) b_qm, 3); }
-		cs.u32(num_passes, 1, 0, 2, 0, 3, 0, 4, 3);
+		if (seq_type == 2 && num_passes != 1) die("vardct: a reference-only frame codes no passes: passes=1");
+		if (seq_type != 2) cs.u32(num_passes, 1, 0, 2, 0, 3, 0, 4, 3);   // (not coded for a reference-only frame, j40.h:5276)
 		if (num_passes > 1) {
 			cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 1);                  // num_ds = 0
 			for (int i = 0; i < num_passes - 1; ++i) cs.put(0, 2);  // shift[i]
@@ -2145,6 +2212,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	std::vector<std::vector<uint8_t>> sections;
 	{
 		BitWriter bw;
+		write_patch_dictionary(bw, extra + (alpha ? 1 : 0));   // (patches=: the dictionary comes first)
 		if (!custom_m_lf) bw.put(1, 1);   // LF channel dequantisation: default
 		else { bw.put(0, 1); for (int c = 0; c < 3; ++c) bw.f16((float) (m_lf[c] * 128.0)); }   // (read back divided by 128, j40.h:6268)
 		bw.put(1, 1);                 // global tree present
@@ -2256,15 +2324,17 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	const int flag_xyb = opt.geti("xyb", 0), flag_ycbcr = opt.geti("ycbcr", 0);
 	cs.pad();
 	cs.put(0, 1);                       // FrameHeader: not all_default
-	cs.put(g_mod_lf ? 1 : 0, 2);        // regular frame (an LF frame: type 1)
+	const int seq_type = g_seq ? g_seq->type : 0;
+	cs.put(g_mod_lf ? 1 : (uint64_t) seq_type, 2);   // regular frame (an LF frame: type 1; types=: a reference-only frame, type 2)
 	cs.put(1, 1);                       // modular
-	cs.u64(0);                          // flags
+	cs.u64(patch_flag() ? 2 : 0);       // flags
 	if (!flag_xyb) cs.put(flag_ycbcr ? 1 : 0, 1);   // do_ycbcr
 	if (!flag_xyb && flag_ycbcr) cs.put(0, 6);      // jpeg_upsampling: none
 	cs.put(0, 2);                       // log_upsampling
 	for (int k = 0; k < extra + (alpha ? 1 : 0); ++k) cs.put(0, 2);   // extra channel upsampling
 	cs.put((uint64_t) (group_shift - 7), 2);
-	cs.u32(num_passes, 1, 0, 2, 0, 3, 0, 4, 3);
+	if (seq_type == 2 && num_passes != 1) die("modular: a reference-only frame codes no passes: passes=1");
+	if (seq_type != 2) cs.u32(num_passes, 1, 0, 2, 0, 3, 0, 4, 3);   // (not coded for a reference-only frame, j40.h:5276)
 	if (num_passes > 1) {
 		cs.u32(0, 0, 0, 1, 0, 2, 0, 3, 1);                  // num_ds = 0
 		for (int i = 0; i < num_passes - 1; ++i) cs.put(0, 2);  // shift[i]
@@ -2342,6 +2412,14 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 //   blends=            per-frame blend mode, all channels alike (default 0, Replace; 1 Add, 2 Blend, 3 MulAdd, 4 Mul)
 //   ecblends= ecsrcs=  per-frame blend mode and source slot of the extra channels alone (default: the colour channels')
 //   only=k             coded frame k alone, as a last frame, under the same image header, with the same crop and the same section bytes
+//                      (a reference-only frame: as a regular frame)
+//   types=             per-frame type: 0 a regular frame (default), 2 a reference-only frame with save_before_color_transform = 1 (sbct=0: 0),
+//                      of the size its crops= entry gives, without an origin; saved into its saves= slot, never shown
+//   patches=           per frame (entries separated by ';') the patch dictionary: reference patches separated by '/', each
+//                      ref,x0,y0,w,h:x,y,mode,clamp[:x,y,mode,clamp...] -- the rectangle of the reference frame in slot ref and where it goes in
+//                      which blend mode. Sets the frame's has_patches flag; nothing is checked (PatchRole). patchec=M: the extra channels'
+//                      entries have mode M; patchcut=1: LfGlobal ends inside the dictionary; patchtwin=1: the flag and the dictionary left
+//                      out, every other byte alike. stats=1 lists the placements written
 // The last frame is is_last. stats=1 prints frames, shown, saved_slots and every frame's offsets instead of the mode's own statistics.
 static std::vector<std::string> split_list(const std::string &v, char sep) {
 	std::vector<std::string> out;
@@ -2357,7 +2435,8 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 	const bool anim = opt_in.geti("anim", 0) != 0;
 	const std::vector<std::string> durs = split_list(opt_in.gets("durations", ""), ','), crops = split_list(opt_in.gets("crops", ""), ';'),
 		srcs = split_list(opt_in.gets("srcs", ""), ','), saves = split_list(opt_in.gets("saves", ""), ','), blends = split_list(opt_in.gets("blends", ""), ','),
-		ecblends = split_list(opt_in.gets("ecblends", ""), ','), ecsrcs = split_list(opt_in.gets("ecsrcs", ""), ',');
+		ecblends = split_list(opt_in.gets("ecblends", ""), ','), ecsrcs = split_list(opt_in.gets("ecsrcs", ""), ','),
+		types = split_list(opt_in.gets("types", ""), ','), patches = split_list(opt_in.gets("patches", ""), ';');
 	if (!durs.empty() && !anim) die("durations= wants anim=1 (frames of a still have no duration)");
 	// modes=v,m,...: per-frame writers, v the VarDCT one and m the Modular one (an empty entry: the command's mode). Every frame gets every
 	// option; the first frame writes the image header, so the options must describe one image to both writers (a Modular frame under a
@@ -2367,13 +2446,32 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 	for (const std::string &m : modes) { if (!m.empty() && m != "v" && m != "m") die("modes=v|m,..."); any_vardct = any_vardct || m == "v"; }
 	if (!modes.empty() && any_vardct && !opt_in.geti("xyb", 0)) die("modes=: a Modular frame beside VarDCT frames is a frame of an XYB image: xyb=1");
 	Options opt = opt_in;
-	for (const char *k : {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "container", "stats", "modes"}) opt.kv.erase(k);
+	for (const char *k : {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "container", "stats", "modes", "types", "patches", "patchtwin", "patchec", "patchcut", "sbct"}) opt.kv.erase(k);
 	if (any_vardct && !opt.kv.count("fullheader")) opt.kv["fullheader"] = "1";
 	auto at = [](const std::vector<std::string> &v, int k, int def) { return k < (int) v.size() && !v[(size_t) k].empty() ? atoi(v[(size_t) k].c_str()) : def; };
 	std::vector<uint8_t> cs;
-	std::string rows;
+	std::string rows, patch_rows;
 	int shown = 0; unsigned saved_slots = 0;
 	for (int k = 0; k < N; ++k) {
+		PatchRole role;
+		role.twin = opt_in.geti("patchtwin", 0) != 0; role.ec_mode = opt_in.geti("patchec", 0); role.cut = opt_in.geti("patchcut", 0) != 0;
+		if (k < (int) patches.size() && !patches[(size_t) k].empty()) {
+			std::string placed;
+			for (const std::string &one : split_list(patches[(size_t) k], '/')) {
+				const std::vector<std::string> parts = split_list(one, ':');
+				PatchRef r;
+				if (parts.size() < 2 || sscanf(parts[0].c_str(), "%d,%d,%d,%d,%d", &r.ref, &r.x0, &r.y0, &r.w, &r.h) != 5 || r.ref < 0 || r.x0 < 0 || r.y0 < 0 || r.w < 1 || r.h < 1) die("patches=ref,x0,y0,w,h:x,y,mode,clamp[:x,y,mode,clamp...][/...];...");
+				for (size_t j = 1; j < parts.size(); ++j) {
+					PatchPlace q;
+					if (sscanf(parts[j].c_str(), "%lld,%lld,%d,%d", &q.x, &q.y, &q.mode, &q.clamp) != 4 || q.mode < 0 || q.clamp < 0 || q.clamp > 1 || (j == 1 && (q.x < 0 || q.y < 0))) die("patches=: a placement is x,y,mode,clamp (the first one of a reference patch not negative)");
+					r.at.push_back(q);
+					char tmp[200]; snprintf(tmp, sizeof tmp, "%s[%lld, %lld, %d, %d, %d, %d, %d, %d, %d, %zu]", placed.empty() ? "" : ", ", q.x, q.y, r.w, r.h, r.x0, r.y0, r.ref, q.mode, q.clamp, role.refs.size());
+					placed += tmp;
+				}
+				role.refs.push_back(r);
+			}
+			if (only < 0 || k == only) { char tmp[64]; snprintf(tmp, sizeof tmp, "%s{\"frame\": %d, \"placements\": [", patch_rows.empty() ? "" : ", ", k); patch_rows += tmp + placed + "]}"; }
+		}
 		SeqFrame q;
 		q.canvas_w = W; q.canvas_h = H; q.anim = anim; q.cs = &cs;
 		int fw = W, fh = H;
@@ -2385,14 +2483,19 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 		q.ec_blend = at(ecblends, k, q.blend); q.ec_src = at(ecsrcs, k, q.src);
 		if (q.blend < 0 || q.blend > 4 || q.src < 0 || q.src > 3 || q.ec_blend < 0 || q.ec_blend > 4 || q.ec_src < 0 || q.ec_src > 3 || q.save < 0 || q.save > 3 || q.duration < 0) die("blends 0..4, srcs and saves 0..3, durations >= 0");
 		q.is_last = only >= 0 || k == N - 1;
-		if (q.duration > 0 || q.is_last) ++shown;
-		if (!q.is_last && (q.duration == 0 || q.save != 0)) saved_slots |= 1u << q.save;
+		q.type = only >= 0 ? 0 : at(types, k, 0); q.save_before_ct = opt_in.geti("sbct", 1) ? 1 : 0;
+		if (q.type != 0 && q.type != 2) die("types=0|2,...");
+		if (q.type == 2 && q.is_last) die("types=: a reference-only frame is never the last one");
+		if (q.type == 2) { q.x0 = q.y0 = 0; q.blend = q.ec_blend = 0; }
+		if (only >= 0 && at(types, k, 0) == 2) { q.have_crop = false; q.canvas_w = fw; q.canvas_h = fh; }   // (alone: a regular frame of an image of its own size)
+		if (q.type != 2 && (q.duration > 0 || q.is_last)) ++shown;
+		if (q.type != 2 && !q.is_last && (q.duration == 0 || q.save != 0)) saved_slots |= 1u << q.save;
 		if (only >= 0 && k != only) continue;
 		q.first = cs.empty();
-		g_seq = &q;
+		g_seq = &q; g_patch = role.refs.empty() ? nullptr : &role;
 		const bool frame_vardct = k < (int) modes.size() && !modes[(size_t) k].empty() ? modes[(size_t) k] == "v" : vardct;
 		const int e = frame_vardct ? run_vardct(fw, fh, seed + (uint64_t) k, out, opt) : run_modular(fw, fh, seed + (uint64_t) k, out, opt);
-		g_seq = nullptr;
+		g_seq = nullptr; g_patch = nullptr;
 		if (e) return e;
 		// (the first frame's bytes start with the signature and the image header: its frame header is found by a reader, not here)
 		char tmp[160]; snprintf(tmp, sizeof tmp, "%s{\"frame\": %d, \"first_section\": %zu, \"end\": %zu}", rows.empty() ? "" : ", ", k, q.first_section, cs.size());
@@ -2420,7 +2523,7 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 		}
 	}
 	if (!write_file(out, file)) die("cannot write output");
-	if (opt_in.geti("stats", 0)) printf("{\"frames\": %d, \"shown\": %d, \"saved_slots\": %d, \"written\": [%s]}\n", only >= 0 ? 1 : N, only >= 0 ? 1 : shown, only >= 0 ? 0 : __builtin_popcount(saved_slots), rows.c_str());
+	if (opt_in.geti("stats", 0)) printf("{\"frames\": %d, \"shown\": %d, \"saved_slots\": %d, \"written\": [%s], \"patches\": [%s]}\n", only >= 0 ? 1 : N, only >= 0 ? 1 : shown, only >= 0 ? 0 : __builtin_popcount(saved_slots), rows.c_str(), patch_rows.c_str());
 	fprintf(stderr, "%s %dx%d: %zu bytes, %d coded frame(s)%s\n", vardct ? "vardct" : "modular", W, H, file.size(), only >= 0 ? 1 : N, anim ? ", animation" : "");
 	return 0;
 }
@@ -2624,7 +2727,7 @@ int main(int argc, char **argv) {
 		if (!vardct) die("lflevels= belongs to the vardct mode");
 		return run_lf_sequence(W, H, seed, argv[5], opt);
 	}
-	static const char *const SEQ_KEYS[] ={"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "modes"};
+	static const char *const SEQ_KEYS[] ={"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "modes", "types", "patches"};
 	bool sequence = false;
 	for (const char *k : SEQ_KEYS) sequence = sequence || opt.kv.count(k);
 	if (!sequence) return vardct ? run_vardct(W, H, seed, argv[5], opt) : run_modular(W, H, seed, argv[5], opt);
