@@ -9,6 +9,25 @@
 
 struct j40hip_device_state;  // defined in device/runtime_state.hpp
 
+// What the last decode of a handle did, for j40hip_frame_status, the getters and the read-back hooks. A decode begins with a fresh one, so
+// a field added here is reset with the rest. (What the getters report "of the last decode with a region / scale / orientation" outlives
+// the decodes without one and stays on the handle.)
+struct LastDecode {
+	bool alpha_written = false;       // merged the alpha channel into its pixels
+	bool ycbcr_used = false;          // went through the YCbCr planes and k_ycbcr_tail
+	bool wide_used = false;           // ran the int32 instantiations of the Modular kernels (a wide frame, j40hip_frame_wide)
+	bool modular_xyb_used = false;    // went through k_modular_xyb_pack / k_modular_to_xyb
+	bool modular_xyb_whole = false;   // ... and decoded every group: the planes hold the whole frame (j40hip_frame_read_xyb)
+	bool colour_used = false;         // went through k_colour_tail
+	bool colour_curve_8bit = false;   // ... of an 8-bit frame without a threshold table: the curve was evaluated per sample (the linear curve, or one whose levels no table holds)
+	int restore_ran = 0;              // the mode the restoration filters ran in (0: they did not)
+	uint32_t restore_err = 0;         // their "gab0" / "epf0" / "shrp" (reported behind the sections' codes)
+	bool trailers_pending = false;    // decoded by a batch: j40hip_frame_status validates the extra channels' sub-images before it reports
+	const float *tail_planes = nullptr;   // the three XYB planes the tail read, after the filters and the patches (j40hip_frame_read_xyb); device memory of the upload
+	// the upload's device state is released: nothing of it is named or reported any longer
+	void device_released() { restore_ran = 0; restore_err = 0; trailers_pending = false; tail_planes = nullptr; }
+};
+
 struct j40hip_frame {
 	const uint8_t *cs = nullptr;     // codestream bytes (inside the caller's buffer, or cs_storage)
 	size_t cs_size = 0;
@@ -22,20 +41,14 @@ struct j40hip_frame {
 	bool force_dense = false;        // upload with dense coefficient planes (set after a decode ran out of event space, ERR_EVOF)
 	int restoration = -1;            // the restoration filters (j40hip_frame_set_restoration): -1 as J40HIP_RESTORATION says, 0 off, 1 on, 2 as j40's routines stand
 	int alpha = -1;                  // the alpha channel of a VarDCT frame (j40hip_frame_set_alpha): -1 as J40HIP_ALPHA says, 0 dropped (A = 255, the reference's pixels), 1 kept
-	bool alpha_written = false;      // the last decode merged the alpha channel into its pixels
 	int ycbcr = -1;                  // YCbCr VarDCT frames (j40hip_frame_set_ycbcr): -1 as J40HIP_YCBCR says, 0 refused ("TODO", the reference's answer), 1 served
 	// Modular frames of XYB images (j40hip_frame_set_modular_xyb): -1 as J40HIP_MODULAR_XYB says, 0 rendered as R, G, B (the reference's pixels), 1 through
-	// the XYB colour tail; and whether the last decode went through k_modular_xyb_pack / k_modular_to_xyb
+	// the XYB colour tail
 	int modular_xyb = -1;
-	bool modular_xyb_used = false;
-	bool modular_xyb_whole = false;   // ... and decoded every group: the planes hold the whole frame (j40hip_frame_read_xyb)
 	// the colour mode (j40hip_frame_set_colour): -1 as J40HIP_COLOUR says, 0 every XYB image rendered as sRGB (the reference's pixels), 1 in the
-	// colour space the image header signals; and whether the last decode went through k_colour_tail
+	// colour space the image header signals
 	int colour = -1;
-	bool colour_used = false;
-	bool colour_curve_8bit = false;   // ... of an 8-bit frame without a threshold table: the curve was evaluated per sample (the linear curve, or one whose levels no table holds)
-	bool wide_used = false;          // the last decode ran the int32 instantiations of the Modular kernels (a wide frame, j40hip_frame_wide)
-	bool ycbcr_used = false;         // the last decode went through the YCbCr planes and k_ycbcr_tail
+	LastDecode last;                 // what the last decode did: every decode begins with last = LastDecode()
 	int32_t output_format = J40HIP_U8X4;   // what the decode entry points write (j40hip_frame_set_output_format): u8x4 or u16x4
 	// region decode (j40hip_frame_set_region): the rectangle the decode entry points write instead of the whole frame, and what the last
 	// decode with it cost (j40hip_frame_region's fields 9-11)

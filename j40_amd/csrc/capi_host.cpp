@@ -379,7 +379,7 @@ void j40hip_frame_alpha(const j40hip_frame *h, int32_t out[4]) {
 	if (!h) return;
 	for (size_t i = 0; i < h->frame.im.ec.size(); ++i) if (h->frame.im.ec[i].type == j40hip::EC_ALPHA) { out[0] = (int32_t) i; out[1] = h->frame.im.ec[i].bpp; break; }
 	out[2] = j40hip_alpha_kept(h) ? 1 : 0;
-	out[3] = h->alpha_written ? 1 : 0;
+	out[3] = h->last.alpha_written ? 1 : 0;
 }
 
 // ---- YCbCr VarDCT frames (include/j40hip.h) ----
@@ -395,7 +395,7 @@ void j40hip_frame_ycbcr(const j40hip_frame *h, int32_t out[8]) {
 	const j40hip::FrameHeader &fh = h->frame.fh;
 	out[0] = !fh.is_modular && fh.do_ycbcr ? 1 : 0;
 	for (int c = 0; c < 3; ++c) { out[1 + 2 * c] = fh.hshift[c]; out[2 + 2 * c] = fh.vshift[c]; }
-	out[7] = h->ycbcr_used ? 1 : 0;
+	out[7] = h->last.ycbcr_used ? 1 : 0;
 }
 
 // ---- Modular frames of XYB images (include/j40hip.h) ----
@@ -410,7 +410,7 @@ void j40hip_frame_modular_xyb(const j40hip_frame *h, int32_t out[4]) {
 	memset(out, 0, sizeof(int32_t) * 4);
 	if (!h) return;
 	out[0] = j40hip_modular_xyb_applies(h) ? 1 : 0; out[1] = j40hip_modular_xyb_on(h) ? 1 : 0;
-	out[2] = h->frame.fh.is_modular ? (h->frame.wide() ? 4 : 2) : 0; out[3] = h->modular_xyb_used ? 1 : 0;
+	out[2] = h->frame.fh.is_modular ? (h->frame.wide() ? 4 : 2) : 0; out[3] = h->last.modular_xyb_used ? 1 : 0;
 }
 
 // ---- the colour mode (include/j40hip.h; colour_space.hpp has the maths) ----
@@ -437,7 +437,7 @@ void j40hip_frame_colour(const j40hip_frame *h, int32_t out[8]) {
 	const j40hip::ColourEncoding &ce = h->frame.im.cenc;
 	out[0] = j40hip_colour_applies(h) ? 1 : 0; out[1] = j40hip_colour_on(h) ? 1 : 0;
 	out[2] = ce.white_point; out[3] = ce.primaries; out[4] = ce.have_gamma ? -1 : ce.transfer; out[5] = ce.colour_space;
-	out[6] = h->colour_used ? (h->colour_curve_8bit ? 2 : 1) : 0; out[7] = (int32_t) j40hip_colour_refusal(h);
+	out[6] = h->last.colour_used ? (h->last.colour_curve_8bit ? 2 : 1) : 0; out[7] = (int32_t) j40hip_colour_refusal(h);
 }
 void j40hip_frame_colour_encoding(const j40hip_frame *h, int32_t out[16]) {
 	if (!out) return;

@@ -1,6 +1,7 @@
 // j40_amd/csrc/decode_route.hpp -- the one place that interprets a frame handle's modes (output format, region, scale, orientation, restoration,
 // kept alpha, YCbCr, Modular XYB, the group range): resolve_route states what the next decode does, mode_refusal which modes exclude which; the
 // setters, the getters and every decode entry read their answers. A further mode is added here. Host code only: no HIP, nothing allocated.
+// (A further operation on a frame's XYB planes -- behind the filters, ahead of the tail -- is added in device/runtime.hip: render_planes.)
 #pragma once
 #include "capi.hpp"
 #include "device/orient_dev.h"

@@ -248,7 +248,7 @@ static j40hip_aframe *aframe_prepare_body(const void *buf, size_t size, int devi
 	extract_codestream((const uint8_t *) buf, size, &h.cs, &h.cs_size, &h.cs_storage, &h.container_stray_tail);
 	h.bare_codestream = h.cs == (const uint8_t *) buf && h.cs_size == size;
 	if (!parse_frame_front(h.cs, h.cs_size, &fr, &tasks, &extra_prec, &plain)) return nullptr;
-	{   // the restoration filters asked for (J40HIP_RESTORATION) and signalled by the frame: the single-frame path runs them (runtime.hip: decode_restored)
+	{   // the restoration filters asked for (J40HIP_RESTORATION) and signalled by the frame: the single-frame path runs them (runtime.hip: run_filters)
 		if (restoration_env() && signals_filters(fr.fh)) return nullptr;
 	}
 	const double tp1 = prof_now();

@@ -17,9 +17,6 @@ bool j40hip_rt::modular_groups_independent(const j40hip_frame *h) {
 	return true;
 }
 
-// what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it
-static void reset_decode_flags(j40hip_frame *h) { h->dev->trailers_pending = false; h->alpha_written = false; h->ycbcr_used = false; h->wide_used = false; h->modular_xyb_used = false; h->modular_xyb_whole = false; h->colour_used = false; h->colour_curve_8bit = false; h->dev->colour_planes = nullptr; h->dev->patch_planes = nullptr; h->dev->restore_ran = 0; h->dev->restore_err = 0; }
-
 // ---- the colour mode (j40hip_frame_set_colour; colour_space.hpp, device/colour_dev.h, colour_kernels.hip) ----
 // The threshold tables of 8-bit frames, one per distinct (curve, exponent, intensity_target): built once per process by bisection over
 // the floats (a few milliseconds), never dropped -- the copies to the devices read them
@@ -60,23 +57,6 @@ static uint32_t colour_params(j40hip_frame *h, hipStream_t s, const ColourTailPa
 	return 0;
 }
 static bool fh_bpp8_without_table(const j40hip_frame *h, const ColourTailParams &p) { return h->frame.im.bpp == 8 && !p.table; }
-// k_colour_tail over `planes` (width x height floats each, one behind the other) into the caller's image
-static uint32_t colour_pixels(j40hip_frame *h, const float *planes, uint8_t *img, size_t stride_bytes, hipStream_t s) {
-	const ColourTailParams *p = nullptr;
-	if (uint32_t e = colour_params(h, s, &p)) return e;
-	const FrameHeader &fh = h->frame.fh;
-	launch_colour_tail(planes, (size_t) fh.width, *p, fh.width, fh.height, img, stride_bytes, s, out16(h));
-	h->colour_used = true; h->dev->colour_planes = planes;
-	h->colour_curve_8bit = fh_bpp8_without_table(h, *p);   // (an 8-bit frame whose curve has no table: j40hip_frame_colour says so)
-	return 0;
-}
-// where the tail's input goes when the restoration filters' buffers do not exist: three planes of the frame's size, kept with the frame
-static float *colour_plane_buffer(j40hip_device_state *st, const FrameHeader &fh) {
-	if (st->d_xyb) return st->d_xyb;
-	bool ok = true;
-	if (!st->d_colour_xyb) st->d_colour_xyb = st->scratch<float>(3 * (size_t) fh.width * (size_t) fh.height, ok);
-	return ok ? st->d_colour_xyb : (st->d_colour_xyb = nullptr);
-}
 
 // ---- patches (a sequence opened with J40HIP_SEQ_PATCHES; device/patch_dev.h, patch_kernels.hip) ----
 // The frame's patch dictionary onto `planes` (width x height floats each, X, Y, B one behind the other), on `s`: called by every route
@@ -90,10 +70,59 @@ uint32_t j40hip_rt::apply_patches(j40hip_frame *h, float *planes, hipStream_t s)
 	for (int k = 0; k < 4; ++k) { slots.base[k] = h->patch_src[k].base; slots.w[k] = h->patch_src[k].w; slots.h[k] = h->patch_src[k].h; }
 	if (!h->patch_plan) return ERR_TODO;   // (cannot happen: only a sequence's handle parses a dictionary, and its index made the plan)
 	for (const PatchRec &r : h->patch_plan->recs) if (uint32_t e = patch_check(r, slots, h->frame.fh.width, h->frame.fh.height)) return e;
-	st->patch_planes = planes;
 	if (st->patch.dev.num_tiles <= 0) return 0;
 	launch_patch_blend(planes, h->frame.fh.width, h->frame.fh.height, st->patch.dev, slots, s);
 	++h->patch_launches;
+	return 0;
+}
+
+// ---- the plane stage: from the frame's three full-size float planes (X, Y, B; a YCbCr frame's Cb, Y, Cr) to the caller's pixels ----
+// Who enters it is decided once per decode, before anything is launched (run_vardct, decode_modular): a decode whose restoration filters
+// run, the colour mode, a frame with patches, a 4:4:4 YCbCr plan, a caller that wants the planes themselves. Two steps: the planes are
+// made (vardct_planes: the pixel kernels with OutMode::XYB, then the filters; decode_modular: k_modular_to_xyb), then rendered
+// (render_planes). A further operation on XYB planes is one call in render_planes.
+
+// the frame's own planes, width floats a row: the filters' first buffer and everybody else's only one, made at the first decode that needs them
+static uint32_t plane_buffer(j40hip_device_state *st, const FrameHeader &fh, float **out) {
+	if (!st->keep(st->d_xyb, 3 * (size_t) fh.width * (size_t) fh.height)) return ERR_MEM;
+	*out = st->d_xyb;
+	return 0;
+}
+
+// k_ycbcr_tail over the planes `t` names (plane, pitch, size and shifts of every channel) into the caller's image; j40hip_frame_read_ycbcr reads them
+static uint32_t ycbcr_tail(j40hip_frame *h, YcbcrTail &t, uint8_t *img, size_t stride, hipStream_t s) {
+	t.width = h->frame.fh.width; t.height = h->frame.fh.height;
+	ycbcr_tail_scale(&t, h->frame.im.bpp, out16(h));
+	if (!ycbcr_tail_valid(t)) return ERR_RNGE;   // (cannot happen: full-size planes, or planes that reach the padded grid)
+	launch_ycbcr_tail(t, img, stride, s, out16(h));
+	j40hip_device_state::YccRead &r = h->dev->ycc_read;
+	for (int c = 0; c < 3; ++c) { r.plane[c] = t.plane[c]; r.pitch[c] = t.pitch[c]; r.pw[c] = t.pw[c]; r.ph[c] = t.ph[c]; }
+	h->last.ycbcr_used = true;
+	return 0;
+}
+
+// Render the planes (`pitch` floats a row, one plane behind the other) into the caller's image: the frame's patches onto them, then exactly
+// one tail -- k_ycbcr_tail for a YCbCr plan, k_colour_tail for the colour mode (`colour`), else the sRGB tail -- and a Modular plan's A from
+// its plane, as the pack kernels render it (the tails write A opaque). What the tail read stays for j40hip_frame_read_xyb.
+static uint32_t render_planes(j40hip_frame *h, float *planes, size_t pitch, bool colour, uint8_t *img, size_t stride_bytes, hipStream_t s) {
+	j40hip_device_state *st = h->dev;
+	const Frame &fr = h->frame;
+	const int32_t W = fr.fh.width, H = fr.fh.height;
+	if (uint32_t e = apply_patches(h, planes, s)) return e;
+	h->last.tail_planes = planes;
+	if (st->ycbcr) {
+		YcbcrTail t;
+		for (int c = 0; c < 3; ++c) { t.plane[c] = planes + (size_t) c * pitch * (size_t) H; t.pitch[c] = (int32_t) pitch; t.pw[c] = W; t.ph[c] = H; t.hshift[c] = t.vshift[c] = 0; }
+		return ycbcr_tail(h, t, img, stride_bytes, s);
+	}
+	if (colour) {
+		const ColourTailParams *p = nullptr;
+		if (uint32_t e = colour_params(h, s, &p)) return e;
+		launch_colour_tail(planes, pitch, *p, W, H, img, stride_bytes, s, out16(h));
+		h->last.colour_used = true;
+		h->last.colour_curve_8bit = fh_bpp8_without_table(h, *p);   // (an 8-bit frame whose curve has no table: j40hip_frame_colour says so)
+	} else launch_xyb_to_rgba(planes, pitch, st->is_modular ? st->patch.d_frame : st->plan.frame, W, H, img, stride_bytes, s, out16(h));
+	if (st->is_modular && st->alpha_channel >= 0) launch_alpha_from_plane(st->final_planes[(size_t) st->alpha_channel], W, H, fr.im.bpp, img, stride_bytes, s, out16(h));
 	return 0;
 }
 
@@ -110,15 +139,16 @@ static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *
 	const DevModPlan &plan = st->mod;
 	const Frame &fr = h->frame;
 	const bool wide = st->mod_wide;   // int32 planes (the plane pointers carry the sample size themselves)
-	reset_decode_flags(h);
-	h->wide_used = wide;
+	h->last = LastDecode();   // (what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it)
+	h->last.wide_used = wide;
 	const bool xyb = route.modular_xyb && st->final_planes.size() >= 3;
-	h->modular_xyb_used = xyb;
+	h->last.modular_xyb_used = xyb;
 	if ((xyb_out && !xyb) || (xyb && shift > 0)) return ERR_TODO;
 	const bool colour = route.colour && xyb && !xyb_out;   // (whole frames: the route stages a region or a scale)
 	const bool patches = route.patches && !xyb_out;        // (likewise)
 	if (patches && (!xyb || !st->patch.d_frame)) return ERR_TODO;
 	if ((colour || patches) && (region || shift > 0 || !route.every_group)) return ERR_TODO;
+	const bool planes = colour || patches || xyb_out;   // the decode goes through the plane stage
 	RegionCover cover = {0, 0, 0, 0, 0, 0};
 	bool covered = false;   // only the cover's groups are decoded
 	if (region) {
@@ -138,7 +168,7 @@ static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *
 	// (sharded decodes, j40hip_frame_set_group_range: LfGlobal's section and this process' groups of every pass; only frames with a section per group take one)
 	const bool ranged = !route.every_group;
 	const int32_t g0 = ranged ? (int32_t) st->first_group : 0, gn = ranged ? (int32_t) st->num_groups : per_pass;
-	h->modular_xyb_whole = xyb && !covered && !ranged;
+	h->last.modular_xyb_whole = xyb && !covered && !ranged;
 	if (covered) {
 		launch_modular_sections(plan, 0, lead, st->mod_info, s);
 		for (int32_t p = 0; p < st->mod_passes; ++p) for (int32_t r = 0; r < cover.rows; ++r) launch_modular_sections(plan, lead + p * per_pass + (cover.gy0 + r) * cover.gcolumns + cover.gx0, cover.cols, st->mod_info, s);
@@ -172,26 +202,19 @@ static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *
 		if (xyb) launch_modular_xyb_pack_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, x0, y0, w, hh, xk, img, stride_bytes, s, out16(h));
 		else launch_pack_planes_rect(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, x0, y0, w, hh, fr.im.bpp, img, stride_bytes, s, out16(h));
 	};
-	if (xyb_out) {
+	if (planes) {
+		// the plane stage: the float planes by k_modular_to_xyb -- into the caller's slot, which is all it wants, or the frame's own, which are rendered
 		const size_t plane = (size_t) fr.fh.width * (size_t) fr.fh.height;
-		launch_modular_to_xyb(st->final_planes[0], st->final_planes[1], st->final_planes[2], fr.fh.width, 0, 0, fr.fh.width, fr.fh.height, xk, xyb_out, xyb_out + plane, xyb_out + 2 * plane, (size_t) fr.fh.width, s);
+		float *d = xyb_out;
+		if (!d) if (uint32_t e = plane_buffer(st, fr.fh, &d)) return e;
+		launch_modular_to_xyb(st->final_planes[0], st->final_planes[1], st->final_planes[2], fr.fh.width, 0, 0, fr.fh.width, fr.fh.height, xk, d, d + plane, d + 2 * plane, (size_t) fr.fh.width, s);
+		if (!xyb_out) if (uint32_t e = render_planes(h, d, (size_t) fr.fh.width, colour, (uint8_t *) rgba_dev, stride_bytes, s)) return e;
 	} else if (region) {   // the rectangle alone; pixel (x0, y0) of the frame is the first one at rgba_dev
 		pack_rect(region[0], region[1], region[2], region[3], (uint8_t *) rgba_dev - ((size_t) region[1] * stride_bytes + (size_t) region[0] * pixel_bytes(h)));
 	} else if (ranged) {   // only this process' pixels are written
 		int32_t rects[3][4];
 		const int nr = group_range_rects(g0, gn, fr.fh.width, fr.fh.height, fr.fh.group_size_shift, rects);
 		for (int k = 0; k < nr; ++k) pack_rect(rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], (uint8_t *) rgba_dev);
-	} else if (colour || patches) {
-		// the colour mode, a frame with patches: the float planes, the patches onto them, k_colour_tail (or the sRGB tail) over them (A opaque),
-		// A from its plane as the pack kernels render it
-		float *d = colour_plane_buffer(st, fr.fh);
-		if (!d) return ERR_MEM;
-		const size_t plane = (size_t) fr.fh.width * (size_t) fr.fh.height;
-		launch_modular_to_xyb(st->final_planes[0], st->final_planes[1], st->final_planes[2], fr.fh.width, 0, 0, fr.fh.width, fr.fh.height, xk, d, d + plane, d + 2 * plane, (size_t) fr.fh.width, s);
-		if (uint32_t e = apply_patches(h, d, s)) return e;
-		if (!colour) launch_xyb_to_rgba(d, (size_t) fr.fh.width, st->patch.d_frame, fr.fh.width, fr.fh.height, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
-		else if (uint32_t e = colour_pixels(h, d, (uint8_t *) rgba_dev, stride_bytes, s)) return e;
-		if (alpha.p) launch_alpha_from_plane(alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	} else if (xyb) launch_modular_xyb_pack(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, xk, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	else launch_pack_planes(st->final_planes[0], st->final_planes[1], st->final_planes[2], alpha, fr.fh.width, fr.fh.height, fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h), shift);
 	marks.mark(3);
@@ -315,7 +338,7 @@ static uint32_t keep_alpha(j40hip_frame *h, void *rgba_dev, size_t stride_bytes,
 		const int nr = group_range_rects((int32_t) st->first_group, (int32_t) st->num_groups, fr.fh.width, fr.fh.height, fr.fh.group_size_shift, rects);
 		for (int k = 0; k < nr; ++k) launch_alpha_merge(ak.alpha_plane, fr.fh.width, rects[k][0], rects[k][1], rects[k][2] - rects[k][0], rects[k][3] - rects[k][1], fr.im.bpp, (uint8_t *) rgba_dev, stride_bytes, s, out16(h));
 	}
-	h->alpha_written = true;
+	h->last.alpha_written = true;
 	bool ok = hipGetLastError() == hipSuccess;
 	if (ok && ak.num_sections) ok = hipMemcpyAsync(found.data(), ak.plan.status, sizeof(uint32_t) * found.size(), hipMemcpyDeviceToHost, s) == hipSuccess;
 	if (ok) ok = hipStreamSynchronize(s) == hipSuccess;
@@ -363,111 +386,49 @@ uint32_t j40hip_rt::restore_params(const FrameHeader &fh, int mode, RestoreParam
 	}
 	return 0;
 }
-// ---- YCbCr frames (j40hip_frame_set_ycbcr; device/ycbcr_dev.h, ycbcr_kernels.hip) ----
-// k_ycbcr_tail over three full-size planes one behind the other, `pitch` floats a row (a 4:4:4 frame: what launch_vardct_frame, OutMode::XYB, or
-// the restoration filters left)
-static void ycbcr_tail_444(j40hip_frame *h, const float *planes, size_t pitch, uint8_t *img, size_t stride, hipStream_t s) {
-	j40hip_device_state *st = h->dev;
-	const int32_t W = h->frame.fh.width, H = h->frame.fh.height;
-	YcbcrTail t;
-	for (int c = 0; c < 3; ++c) { t.plane[c] = planes + (size_t) c * pitch * (size_t) H; t.pitch[c] = (int32_t) pitch; t.pw[c] = W; t.ph[c] = H; t.hshift[c] = t.vshift[c] = 0; }
-	t.width = W; t.height = H;
-	ycbcr_tail_scale(&t, h->frame.im.bpp, out16(h));
-	launch_ycbcr_tail(t, img, stride, s, out16(h));
-	for (int c = 0; c < 3; ++c) { st->ycc_read.plane[c] = t.plane[c]; st->ycc_read.pitch[c] = t.pitch[c]; st->ycc_read.pw[c] = W; st->ycc_read.ph[c] = H; }
-	h->ycbcr_used = true;
-}
-// The pixel stage of a YCbCr frame: the pixel kernels leave float planes -- a 4:4:4 frame the three full-size planes of OutMode::XYB,
-// rows padded to 16 bytes; a subsampled one a plane per channel at the channel's resolution over the padded grid (OutMode::YCC) --
-// and k_ycbcr_tail makes the pixels of them. The planes are made at the first decode and kept with the frame.
-static uint32_t ycbcr_pixels(j40hip_frame *h, const int32_t *class_start, const DevVarblock *list, uint8_t *img, size_t stride, hipStream_t s) {
-	j40hip_device_state *st = h->dev;
+// The filters' preparation, once per upload: the kernels' parameters, the frame-wide sharpness map and what keeps the filters from running
+// -- in the order the reference's routines complain: "gab0" / "epf0", a picture one sample wide, "shrp". Known from the header and the map
+// alone, so a decode looks here before it decides its route.
+static const j40hip_device_state::Restore &restore_prepared(j40hip_frame *h) {
+	j40hip_device_state::Restore &rs = h->dev->restore;
+	if (rs.ready) return rs;
 	const Frame &fr = h->frame;
-	const int32_t W = fr.fh.width, H = fr.fh.height;
-	bool ok = true;
-	if (!fr.fh.subsampled()) {
-		const size_t pitch = ((size_t) W + 3) & ~(size_t) 3;
-		if (!st->d_ycc) st->d_ycc = st->scratch<float>(3 * pitch * (size_t) H, ok);
-		if (!ok) { st->d_ycc = nullptr; return ERR_MEM; }
-		launch_vardct_frame(st->plan, class_start, list, st->d_large_scratch, K2Target{st->d_ycc, pitch * 4, OutMode::XYB, 0}, s);
-		ycbcr_tail_444(h, st->d_ycc, pitch, img, stride, s);
-		return 0;
+	const FrameHeader::Restoration &r = fr.fh.restoration;
+	rs.err = restore_params(fr.fh, 1, &rs.p);   // (mode 2 differs in `quirk` alone: run_filters sets it)
+	if (!rs.err && r.gab && fr.fh.width < 2) rs.err = ERR_TODO;   // (j40__gaborish reads sample 1 of every row, j40.h:7304)
+	// the sharpness map: frame-wide, in the cell order of `blocks` (LfGroup after LfGroup); "shrp" as j40__epf_recip_sigmas finds it (j40.h:7399)
+	if (!rs.err && r.epf_iters > 0) {
+		uint16_t ub = 0;
+		for (const LfGroup &gg : fr.lf_groups) {
+			if (gg.sharpness.size() != (size_t) gg.width8 * (size_t) gg.height8) { rs.err = ERR_TODO; break; }   // (a frame handle built without it: from a view or an LF bundle)
+			for (int16_t v : gg.sharpness) ub |= (uint16_t) v;
+			rs.sharp.insert(rs.sharp.end(), gg.sharpness.begin(), gg.sharpness.end());
+		}
+		if (!rs.err && !(ub < 8)) rs.err = ERR4('s', 'h', 'r', 'p');
 	}
-	uint32_t shifts = 0;
-	for (int c = 0; c < 3; ++c) shifts |= (uint32_t) (fr.fh.hshift[c] | fr.fh.vshift[c] << 1) << (2 * c);
-	YcbcrTail t;
-	ycc_plane_dims(W, H, shifts, t.pw, t.ph);
-	size_t total = 0;
-	for (int c = 0; c < 3; ++c) total += (size_t) t.pw[c] * (size_t) t.ph[c];
-	if (!st->d_ycc) st->d_ycc = st->scratch<float>(total, ok);
-	if (!ok) { st->d_ycc = nullptr; return ERR_MEM; }
-	launch_vardct_frame(st->plan, class_start, list, st->d_large_scratch, K2Target{st->d_ycc, 0, OutMode::YCC, 0}, s);
-	size_t off = 0;
-	for (int c = 0; c < 3; ++c) {
-		t.plane[c] = st->d_ycc + off; t.pitch[c] = t.pw[c]; t.hshift[c] = fr.fh.hshift[c]; t.vshift[c] = fr.fh.vshift[c];
-		off += (size_t) t.pw[c] * (size_t) t.ph[c];
-	}
-	t.width = W; t.height = H;
-	ycbcr_tail_scale(&t, fr.im.bpp, out16(h));
-	if (!ycbcr_tail_valid(t)) return ERR_RNGE;   // (cannot happen: the planes reach the padded grid)
-	launch_ycbcr_tail(t, img, stride, s, out16(h));
-	for (int c = 0; c < 3; ++c) { st->ycc_read.plane[c] = t.plane[c]; st->ycc_read.pitch[c] = t.pitch[c]; st->ycc_read.pw[c] = t.pw[c]; st->ycc_read.ph[c] = t.ph[c]; }
-	h->ycbcr_used = true;
-	return 0;
+	rs.ready = true;
+	return rs;
 }
 
-// the colour mode, or a frame with patches, without the filters: the pixel kernels leave the samples in XYB planes, the patches go onto
-// them, k_colour_tail (`colour`) or the sRGB tail follows -- one pass more over three float planes than the fused tail, the route the
-// restoration filters already take
-static uint32_t planes_unfiltered(j40hip_frame *h, const int32_t *class_start, const DevVarblock *list, uint8_t *img, size_t stride_bytes, hipStream_t s, bool colour) {
-	j40hip_device_state *st = h->dev;
-	const FrameHeader &fh = h->frame.fh;
-	float *d = colour_plane_buffer(st, fh);
-	if (!d) return ERR_MEM;
-	launch_vardct_frame(st->plan, class_start, list, st->d_large_scratch, K2Target{d, (size_t) fh.width * 4, OutMode::XYB, 0}, s);
-	if (uint32_t e = apply_patches(h, d, s)) return e;
-	if (colour) return colour_pixels(h, d, img, stride_bytes, s);
-	launch_xyb_to_rgba(d, (size_t) fh.width, st->plan.frame, fh.width, fh.height, img, stride_bytes, s, out16(h));
-	return 0;
-}
-
-static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t stride_bytes, int mode, hipStream_t s, bool colour = false) {
+// Gaborish and the edge-preserving filter over the frame's planes (d_xyb, where the pixel kernels have left the samples on `s`) in `mode`;
+// d_restored says where the result lies. Their second set of planes, the sigmas and the map's copy are made at the first run.
+static uint32_t run_filters(j40hip_frame *h, int mode, hipStream_t s) {
 	j40hip_device_state *st = h->dev;
 	const Frame &fr = h->frame;
 	const FrameHeader::Restoration &r = fr.fh.restoration;
 	const int32_t W = fr.fh.width, H = fr.fh.height;
-	const size_t cells = (size_t) ((W + 7) / 8) * (size_t) ((H + 7) / 8), plane = (size_t) W * (size_t) H;
-	RestoreParams p;
-	uint32_t perr = restore_params(fr.fh, mode, &p);
-	if (!perr && r.gab && W < 2) perr = ERR_TODO;   // (j40__gaborish reads sample 1 of every row, j40.h:7304)
-	// the sharpness map: frame-wide, in the cell order of `blocks` (LfGroup after LfGroup); "shrp" as j40__epf_recip_sigmas finds it (j40.h:7399)
-	std::vector<int16_t> sharp;
-	if (!perr && r.epf_iters > 0) {
-		sharp.reserve(cells);
-		uint16_t ub = 0;
-		for (const LfGroup &gg : fr.lf_groups) {
-			if (gg.sharpness.size() != (size_t) gg.width8 * (size_t) gg.height8) { perr = ERR_TODO; break; }   // (a frame handle built without it: from a view or an LF bundle)
-			for (int16_t v : gg.sharpness) ub |= (uint16_t) v;
-			sharp.insert(sharp.end(), gg.sharpness.begin(), gg.sharpness.end());
-		}
-		if (!perr && !(ub < 8)) perr = ERR4('s', 'h', 'r', 'p');
+	const size_t cells = (size_t) ((W + 7) / 8) * (size_t) ((H + 7) / 8);
+	if (!st->keep(st->d_xyb_tmp, 3 * (size_t) W * (size_t) H) || !st->keep(st->d_sigma, cells + 64)) return ERR_MEM;
+	if (r.epf_iters > 0 && !st->d_sharp) {
+		bool ok = true;
+		st->d_sharp = st->upload(st->restore.sharp.data(), st->restore.sharp.size(), s, ok);
+		if (!ok) { st->d_sharp = nullptr; return ERR_MEM; }
 	}
-	if (perr) {   // the filters cannot run: the picture without them, and the complaint behind the sections' own (j40hip_frame_status)
-		st->restore_err = perr;
-		if (!rgba_dev) return 0;   // (planes are wanted, not pixels -- run_vardct's xyb_out: the caller makes the unfiltered ones)
-		if (st->ycbcr) return ycbcr_pixels(h, st->class_start, st->d_vb_sorted, rgba_dev, stride_bytes, s);
-		if (colour || fr.fh.has_patches) return planes_unfiltered(h, st->class_start, st->d_vb_sorted, rgba_dev, stride_bytes, s, colour);
-		launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{rgba_dev, stride_bytes, out_mode(h), 0}, s);
-		return 0;
-	}
-	bool ok = true;
-	if (!st->d_xyb) { st->d_xyb = st->scratch<float>(3 * plane, ok); st->d_xyb_tmp = st->scratch<float>(3 * plane, ok); st->d_sigma = st->scratch<float>(cells + 64, ok); }
-	if (r.epf_iters > 0 && !st->d_sharp) st->d_sharp = st->upload(sharp.data(), sharp.size(), s, ok);
-	if (!ok) return ERR_MEM;
+	RestoreParams p = st->restore.p;
+	p.quirk = mode == 2 ? 1 : 0;
 	// J40HIP_RESTORATION_TIMING: the filters' time between two events of this call's own, destroyed on every way out
 	struct Pair { hipEvent_t ev[2] = {nullptr, nullptr}; ~Pair() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); } } pair;
 	static const bool timed = env_str("J40HIP_RESTORATION_TIMING") != nullptr;
-	launch_vardct_frame(st->plan, st->class_start, st->d_vb_sorted, st->d_large_scratch, K2Target{st->d_xyb, (size_t) W * 4, OutMode::XYB, 0}, s);
 	const StageMarks marks{timed && hipEventCreate(&pair.ev[0]) == hipSuccess && hipEventCreate(&pair.ev[1]) == hipSuccess ? pair.ev : nullptr, s};
 	marks.mark(0);
 	uint32_t *sharp_or = (uint32_t *) (st->d_sigma + cells);   // (the device's own OR of the sharpness values: unused, the host checked)
@@ -477,14 +438,32 @@ static uint32_t decode_restored(j40hip_frame *h, uint8_t *rgba_dev, size_t strid
 	}
 	st->d_restored = launch_restoration(st->d_xyb, st->d_xyb_tmp, (size_t) W, p, r.gab, r.epf_iters, st->d_sigma, s);
 	marks.mark(1);
-	if (rgba_dev) if (uint32_t e = apply_patches(h, const_cast<float *>(st->d_restored), s)) return e;   // (the filters' own buffer: nothing else reads it before the next decode)
-	if (!rgba_dev) {}   // (planes are wanted, not pixels: d_restored is the result)
-	else if (st->ycbcr) ycbcr_tail_444(h, st->d_restored, (size_t) W, rgba_dev, stride_bytes, s);   // (the filtered planes are Cb, Y, Cr)
-	else if (colour) { if (uint32_t e = colour_pixels(h, st->d_restored, rgba_dev, stride_bytes, s)) return e; }
-	else launch_xyb_to_rgba(st->d_restored, (size_t) W, st->plan.frame, W, H, rgba_dev, stride_bytes, s, out16(h));
-	st->restore_ran = mode;
+	h->last.restore_ran = mode;
 	if (marks.ev && hipEventSynchronize(pair.ev[1]) == hipSuccess) (void) hipEventElapsedTime(&st->restore_ms, pair.ev[0], pair.ev[1]);
 	return 0;
+}
+
+// ---- YCbCr frames (j40hip_frame_set_ycbcr; device/ycbcr_dev.h, ycbcr_kernels.hip) ----
+// The pixel stage of a subsampled YCbCr frame, which has no full-size planes and so a route of its own: the pixel kernels leave a plane
+// per channel at the channel's resolution over the padded grid (OutMode::YCC), and k_ycbcr_tail makes the pixels of them. (A 4:4:4
+// frame goes through the plane stage.) The planes are made at the first decode and kept with the frame.
+static uint32_t ycbcr_pixels(j40hip_frame *h, const int32_t *class_start, const DevVarblock *list, uint8_t *img, size_t stride, hipStream_t s) {
+	j40hip_device_state *st = h->dev;
+	const Frame &fr = h->frame;
+	uint32_t shifts = 0;
+	for (int c = 0; c < 3; ++c) shifts |= (uint32_t) (fr.fh.hshift[c] | fr.fh.vshift[c] << 1) << (2 * c);
+	YcbcrTail t;
+	ycc_plane_dims(fr.fh.width, fr.fh.height, shifts, t.pw, t.ph);
+	size_t total = 0;
+	for (int c = 0; c < 3; ++c) total += (size_t) t.pw[c] * (size_t) t.ph[c];
+	if (!st->keep(st->d_ycc, total)) return ERR_MEM;
+	launch_vardct_frame(st->plan, class_start, list, st->d_large_scratch, K2Target{st->d_ycc, 0, OutMode::YCC, 0}, s);
+	size_t off = 0;
+	for (int c = 0; c < 3; ++c) {
+		t.plane[c] = st->d_ycc + off; t.pitch[c] = t.pw[c]; t.hshift[c] = fr.fh.hshift[c]; t.vshift[c] = fr.fh.vshift[c];
+		off += (size_t) t.pw[c] * (size_t) t.ph[c];
+	}
+	return ycbcr_tail(h, t, img, stride, s);
 }
 
 // One VarDCT decode as decode_impl (whole frames, group ranges), decode_region (covers), decode_scaled and decode_frame_xyb describe it to
@@ -528,11 +507,45 @@ static uint32_t lf_frame_tail(j40hip_frame *h, hipStream_t s) {
 	return 0;
 }
 
+// Make the planes of a VarDCT plan: the pixel kernels with OutMode::XYB, then the restoration filters (`filters`: their mode, 0: they do
+// not run). Where: the caller's slot (run.xyb_out) when nothing runs over the planes afterwards; the padded planes of a 4:4:4 YCbCr frame
+// the filters do not run on; else the frame's own, from where what the filters leave is copied into the slot. *out: where they lie.
+static uint32_t vardct_planes(j40hip_frame *h, const VardctRun &run, int filters, hipStream_t s, float **out, size_t *out_pitch) {
+	j40hip_device_state *st = h->dev;
+	const FrameHeader &fh = h->frame.fh;
+	float *d = run.xyb_out;
+	size_t pitch = (size_t) fh.width;
+	if (st->ycbcr && !filters) {   // (rows padded to 16 bytes)
+		pitch = ((size_t) fh.width + 3) & ~(size_t) 3;
+		if (!st->keep(st->d_ycc, 3 * pitch * (size_t) fh.height)) return ERR_MEM;
+		d = st->d_ycc;
+	} else if (filters || !d) if (uint32_t e = plane_buffer(st, fh, &d)) return e;
+	launch_vardct_frame(st->plan, run.class_start, run.list, st->d_large_scratch, K2Target{d, pitch * 4, OutMode::XYB, 0}, s);
+	if (filters) {
+		if (uint32_t e = run_filters(h, filters, s)) return e;
+		d = const_cast<float *>(st->d_restored);   // (the filters' own buffer: nothing else reads it before the next decode)
+		if (run.xyb_out && hipMemcpyAsync(run.xyb_out, d, sizeof(float) * 3 * pitch * (size_t) fh.height, hipMemcpyDeviceToDevice, s) != hipSuccess) return ERR_GPU;
+	}
+	*out = d; *out_pitch = pitch;
+	return 0;
+}
+
 static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s, float *ms3) {
 	j40hip_device_state *st = h->dev;
 	const DevPlan &plan = st->plan;
 	const StageMarks marks{ms3 ? st->ev : nullptr, s};
-	reset_decode_flags(h);
+	h->last = LastDecode();   // (what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it)
+	// What follows the entropy kernels, decided before anything is launched. The restoration filters asked for and signalled run where
+	// their parameters are valid; else the picture comes without them and their complaint behind the sections' own (j40hip_frame_status).
+	// The decode goes through the plane stage for them, for the colour mode, for patches, for a 4:4:4 YCbCr plan (a subsampled one whose
+	// filters run is treated as one) and for a caller that wants the planes; anything else takes the fused pixel kernels.
+	int filters = 0;
+	if (run.restoration) {
+		const uint32_t complaint = restore_prepared(h).err;
+		if (complaint) h->last.restore_err = complaint; else filters = run.restoration;
+	}
+	const bool planes = filters || run.colour || run.patches || (st->ycbcr && !h->frame.fh.subsampled()) || run.xyb_out;
+	if (planes && (!run.whole || run.shift || run.cover)) return ERR_TODO;   // (cannot happen: the route decodes such a frame whole and at full size)
 	marks.mark(0);
 	if (uint32_t e = clear_before_decode(st, s)) return e;
 	if (hipMemsetAsync(plan.status, 0, sizeof(uint32_t) * (size_t) st->total_sections, s) != hipSuccess) return ERR_GPU;
@@ -543,24 +556,10 @@ static uint32_t run_vardct(j40hip_frame *h, const VardctRun &run, hipStream_t s,
 	else if (hf_entropy_fast_path(plan, st->hf)) launch_hf_entropy_fast_ordered(plan, st->hf, st->region.d_order, 0, region_cover_groups(*run.cover), s);
 	else for (int32_t row = 0; row < run.cover->rows; ++row) launch_hf_entropy(plan, st->hf, (run.cover->gy0 + row) * run.cover->gcolumns + run.cover->gx0, run.cover->cols, s);
 	marks.mark(2);
-	const int rmode = run.restoration;
-	if (run.xyb_out) {
-		const size_t W = (size_t) h->frame.fh.width, plane = W * (size_t) h->frame.fh.height;
-		bool filtered = false;
-		if (rmode) {
-			if (uint32_t e = decode_restored(h, nullptr, 0, rmode, s)) return e;
-			filtered = st->restore_ran != 0;   // (else the filters could not run, restore_err says why: the unfiltered planes)
-			if (filtered && hipMemcpyAsync(run.xyb_out, st->d_restored, sizeof(float) * 3 * plane, hipMemcpyDeviceToDevice, s) != hipSuccess) return ERR_GPU;
-		}
-		if (!filtered) launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, K2Target{run.xyb_out, W * 4, OutMode::XYB, 0}, s);
-	} else
-	if (rmode) {
-		// the restoration filters asked for and signalled: the pixel kernels leave the samples in XYB planes, Gaborish and the
-		// edge-preserving filter run over the whole picture, the colour tail follows on the filtered planes (restore_kernels.h)
-		if (uint32_t e = decode_restored(h, run.img, run.img_stride, rmode, s, run.colour)) return e;
-	} else if (run.colour || run.patches) {
-		if (!run.whole || run.shift || run.cover) return ERR_TODO;   // (cannot happen: full_size_first)
-		if (uint32_t e = planes_unfiltered(h, run.class_start, run.list, run.img, run.img_stride, s, run.colour)) return e;
+	if (planes) {
+		float *d = nullptr; size_t pitch = 0;
+		if (uint32_t e = vardct_planes(h, run, filters, s, &d, &pitch)) return e;
+		if (!run.xyb_out) if (uint32_t e = render_planes(h, d, pitch, run.colour, run.img, run.img_stride, s)) return e;
 	} else if (st->ycbcr) {
 		if (uint32_t e = ycbcr_pixels(h, run.class_start, run.list, run.img, run.img_stride, s)) return e;
 	} else launch_vardct_frame(plan, run.class_start, run.list, st->d_large_scratch, K2Target{run.img, run.img_stride, out_mode(h), run.shift}, s);
@@ -819,17 +818,17 @@ static uint32_t j40hip_frame_status_body(j40hip_frame *h) {
 		const uint32_t code = first_failure(st->status_host, (size_t) st->total_sections, [&](size_t i) { return (size_t) st->mod_section_offsets[i]; });
 		return code ? code : st->status_host[(size_t) st->total_sections];
 	}
-	if (st->trailers_pending) {
+	if (h->last.trailers_pending) {
 		// the frame was last decoded by a batch (asynchronous: it cannot stop for the host in the middle): the extra channels'
 		// sub-images behind the coefficients are checked now, so that both modes report damage in them like the reference
-		st->trailers_pending = false;
+		h->last.trailers_pending = false;
 		if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
 		if (uint32_t e = finish_trailers(h, st->pending_rgba, st->pending_stride, nullptr, true, route_of(h).alpha_merged)) return e;
 	}
 	st->status_host.assign((size_t) st->total_sections, 0);
 	if (hipMemcpy(st->status_host.data(), st->plan.status, sizeof(uint32_t) * st->status_host.size(), hipMemcpyDeviceToHost) != hipSuccess) return ERR_GPU;
 	const uint32_t code = vardct_verdict(h, st->status_host);
-	return code ? code : st->restore_err;   // (the filters run behind the last section: their complaint comes after every section's)
+	return code ? code : h->last.restore_err;   // (the filters run behind the last section: their complaint comes after every section's)
 }
 
 // ---- the single-image path in two phases ----
@@ -910,7 +909,7 @@ static uint32_t decode_two_phase(j40hip_frame *h, const DecodeRoute &route, uint
 	const DevPlan &plan = st->plan;
 	const int32_t ng = (int32_t) fr.fh.num_groups, k = st->two_k;
 	hipStream_t s0 = nullptr, s1 = tp.s;
-	reset_decode_flags(h);
+	h->last = LastDecode();   // (what the last decode left behind for j40hip_frame_status and the getters: every decode starts from none of it)
 	if (hipMemsetAsync(plan.status, 0, sizeof(uint32_t) * (size_t) st->total_sections, s0) != hipSuccess) return ERR_GPU;
 	if (hipEventRecord(tp.ev[0], s0) != hipSuccess || hipStreamWaitEvent(s1, tp.ev[0], 0) != hipSuccess) return ERR_GPU;
 	DevPlan plan_long = plan;
@@ -976,15 +975,9 @@ static uint32_t decode_to_host(j40hip_frame *h, void *rgba_host, size_t stride_b
 	uint32_t err = route.two_phase ? decode_two_phase(h, route, (uint8_t *) d, (uint8_t *) rgba_host, stride_bytes, &two_phase) : 0;
 	if (two_phase && err != ERR_EVOF) return err;   // (the pixels are in rgba_host, or the frame has failed; "evof": the dense form below)
 	if (two_phase) (void) hipDeviceSynchronize();
-	// the device-side path, waited for; once more with dense planes after a section with more non-zero coefficients than its event region holds
-	err = 0;
-	for (int dense = 0; dense < 2; ++dense) {
-		if (dense) { h->force_dense = true; err = j40hip_frame_upload(h, device); route = route_of(h, true, stride_bytes); }
-		if (!err) err = decode_oriented(h, route, d, stride_bytes, nullptr, nullptr);
-		if (!err && hipStreamSynchronize(nullptr) != hipSuccess) err = ERR_GPU;
-		if (!err) err = j40hip_frame_status(h);
-		if (err != ERR_EVOF) break;
-	}
+	// the device-side path, waited for (wait_with_dense_retry: the route is resolved anew for the frame uploaded again)
+	err = decode_oriented(h, route, d, stride_bytes, nullptr, nullptr);
+	if (!err) err = wait_with_dense_retry(h, device, nullptr, [&] { route = route_of(h, true, stride_bytes); return decode_oriented(h, route, d, stride_bytes, nullptr, nullptr); });
 	// (the decode has been waited for: the copy may go to the SDMA engine a pipeline of this process measured, hostcopy.hpp)
 	if (!err && !hostcopy_d2h_sync(device, rgba_host, d, bytes) && hipMemcpy(rgba_host, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) err = ERR_GPU;
 	return err;

@@ -159,8 +159,8 @@ static uint32_t batch_enqueue(j40hip_batch *b, void *const *rgba_dev, const size
 	for (size_t i = 0; i < b->frames.size(); ++i) {
 		j40hip_frame *h = b->frames[i];
 		j40hip_device_state *st = h->dev;
-		st->trailers_pending = st->has_trailers;
-		st->pending_rgba = h->scale > 0 ? nullptr : rgba_dev[i]; st->pending_stride = stride_bytes[i]; h->alpha_written = false;   // (a kept alpha is merged when the status is read -- never into a small image: the sub-images are validated all the same)
+		h->last.trailers_pending = st->has_trailers;
+		st->pending_rgba = h->scale > 0 ? nullptr : rgba_dev[i]; st->pending_stride = stride_bytes[i]; h->last.alpha_written = false;   // (a kept alpha is merged when the status is read -- never into a small image: the sub-images are validated all the same)
 		if (uint32_t e = clear_before_decode(st, s)) return e;
 		// (no need to clear the status words: a batch decodes every section of every frame and the entropy kernels store
 		// each section's status unconditionally -- 256 tiny fills were 4 % of a step)

@@ -57,7 +57,7 @@ extern "C" uint32_t j40hip_kat_device_ycbcr_tail(const float *const planes_dev[3
 }
 // staged hook: plane c of the last decode through the YCbCr path as the tail read it, tightly packed (include/j40hip.h)
 extern "C" uint32_t j40hip_frame_read_ycbcr(j40hip_frame *h, int c, float *out) {
-	if (!h || !h->dev || !h->ycbcr_used || c < 0 || c > 2 || !out || !h->dev->ycc_read.plane[c]) return ERR_RNGE;
+	if (!h || !h->dev || !h->last.ycbcr_used || c < 0 || c > 2 || !out || !h->dev->ycc_read.plane[c]) return ERR_RNGE;
 	const j40hip_device_state::YccRead &r = h->dev->ycc_read;
 	if (hipSetDevice(h->dev->device) != hipSuccess) return ERR_GPU;
 	return hipMemcpy2D(out, (size_t) r.pw[c] * 4, r.plane[c], (size_t) r.pitch[c] * 4, (size_t) r.pw[c] * 4, (size_t) r.ph[c], hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
@@ -69,7 +69,7 @@ extern "C" uint32_t j40hip_frame_read_ycbcr(j40hip_frame *h, int c, float *out) 
 // "rnge" where that decode covered part of the frame, a region's groups or a group range: the planes outside it are stale)
 static uint32_t read_modular_xyb(j40hip_frame *h, float *out) {
 	j40hip_device_state *st = h->dev;
-	if (!h->modular_xyb_whole) return ERR_RNGE;
+	if (!h->last.modular_xyb_whole) return ERR_RNGE;
 	const FrameHeader &fh = h->frame.fh;
 	const size_t plane = (size_t) fh.width * (size_t) fh.height;
 	if (!out || st->final_planes.size() < 3) return ERR_RNGE;
@@ -82,20 +82,20 @@ static uint32_t read_modular_xyb(j40hip_frame *h, float *out) {
 	return hipMemcpy(out, d, sizeof(float) * 3 * plane, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
 }
 extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out) {
-	// (stage 3, a frame with patches: the planes the last decode left after k_patch_blend, ahead of its tail)
-	// (patch_planes lives in the upload's own state, which every upload makes anew: it names a buffer of this upload or nothing)
+	// (stage 3, a frame with patches: the planes the last decode's tail read, after k_patch_blend)
+	// (tail_planes names a buffer of this upload or nothing: a release of the device state forgets it)
 	if (stage == 3) return guarded([&]() -> uint32_t {
-		if (!h || !h->dev || !h->dev->patch_planes || !h->frame.fh.has_patches || !out) return ERR_RNGE;
+		if (!h || !h->dev || !h->last.tail_planes || !h->frame.fh.has_patches || !out) return ERR_RNGE;
 		if (hipSetDevice(h->dev->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ERR_GPU;
-		return hipMemcpy(out, h->dev->patch_planes, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+		return hipMemcpy(out, h->last.tail_planes, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
 	});
-	if (h && h->dev && h->dev->is_modular && stage == 0 && h->modular_xyb_used && j40hip_modular_xyb_on(h)) return guarded([&] { return read_modular_xyb(h, out); });
+	if (h && h->dev && h->dev->is_modular && stage == 0 && h->last.modular_xyb_used && j40hip_modular_xyb_on(h)) return guarded([&] { return read_modular_xyb(h, out); });
 	// (the colour mode without the filters: the planes the last decode's k_colour_tail read, stages 0 and 1 alike)
-	if (h && h->dev && !h->dev->restore_ran && h->colour_used && h->dev->colour_planes && (stage == 0 || stage == 1) && out) {
+	if (h && h->dev && !h->last.restore_ran && h->last.colour_used && h->last.tail_planes && (stage == 0 || stage == 1) && out) {
 		if (hipSetDevice(h->dev->device) != hipSuccess) return ERR_GPU;
-		return hipMemcpy(out, h->dev->colour_planes, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+		return hipMemcpy(out, h->last.tail_planes, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
 	}
-	if (!h || !h->dev || !h->dev->restore_ran || !h->dev->d_xyb) return ERR_RNGE;
+	if (!h || !h->dev || !h->last.restore_ran || !h->dev->d_xyb) return ERR_RNGE;
 	j40hip_device_state *st = h->dev;
 	const FrameHeader &fh = h->frame.fh;
 	const size_t plane = (size_t) fh.width * (size_t) fh.height, cells = (size_t) ((fh.width + 7) / 8) * (size_t) ((fh.height + 7) / 8);
@@ -306,7 +306,7 @@ extern "C" void j40hip_frame_wide(const j40hip_frame *h, int32_t out[4]) {
 	if (!out) return;
 	memset(out, 0, sizeof(int32_t) * 4);
 	if (!h) return;
-	out[0] = h->frame.wide() ? 1 : 0; out[1] = h->frame.im.bpp; out[2] = h->wide_used ? 1 : 0;
+	out[0] = h->frame.wide() ? 1 : 0; out[1] = h->frame.im.bpp; out[2] = h->last.wide_used ? 1 : 0;
 	out[3] = h->dev && h->dev->is_modular ? (h->dev->mod_wide ? 4 : 2) : 0;
 }
 

@@ -35,7 +35,7 @@ namespace {
 size_t seq_pixel_bytes(const j40hip_sequence *s) { return s->output_format == J40HIP_U16X4 ? 8 : 4; }
 
 // whether the decode of `h` that has just been enqueued writes an alpha channel of its own (else A is full scale)
-bool renders_alpha(const j40hip_frame *h) { return h->dev->is_modular ? h->dev->alpha_channel >= 0 : h->alpha_written; }
+bool renders_alpha(const j40hip_frame *h) { return h->dev->is_modular ? h->dev->alpha_channel >= 0 : h->last.alpha_written; }
 
 size_t slot_bytes(const j40hip_sequence *s) { return s->dev->slot_stride * (size_t) s->im.height; }
 
@@ -72,58 +72,17 @@ uint32_t bind_lf_source(j40hip_sequence *s, j40hip_frame *h, int32_t slot) {
 	return 0;
 }
 
-// An LF frame (type 1): its XYB planes into its LF slot, nothing composed. It may take its own LF image from the next coarser level.
-uint32_t play_lf_frame(j40hip_sequence *s, int64_t k, j40hip_frame *h, hipStream_t stream, bool sync) {
+// A frame the playback keeps as planes -- an LF frame (type 1) in its LF slot, a reference-only frame (type 2) in its reference slot: the
+// whole frame's XYB planes into `block`, nothing composed, nothing shown; *w, *h, *filled: the slot's bookkeeping
+uint32_t play_plane_frame(j40hip_sequence *s, int64_t k, j40hip_frame *h, hipStream_t stream, bool sync, const CacheBlock &block, int32_t *w, int32_t *hh, bool *filled) {
 	j40hip_sequence_device *d = s->dev;
 	const FrameHeader &fh = s->rows[(size_t) k].fh;
-	const int slot = fh.lf_level - 1;
-	const size_t bytes = sizeof(float) * 3 * (size_t) fh.width * (size_t) fh.height;
-	if (slot < 0 || slot > 3 || !d->lf_slot[slot].ptr || d->lf_slot[slot].bytes < bytes) return ERR_GPU;   // (reserve_blocks sized it)
-	if (fh.use_lf_frame) { if (uint32_t e = bind_lf_source(s, h, fh.lf_level)) return e; }
-	float *planes = (float *) d->lf_slot[slot].ptr;
-	uint32_t e = decode_frame_xyb(h, planes, stream);
-	if (e) return e;
+	if (!block.ptr || block.bytes < sizeof(float) * 3 * (size_t) fh.width * (size_t) fh.height) return ERR_GPU;   // (reserve_blocks sized it)
+	float *planes = (float *) block.ptr;
+	if (uint32_t e = decode_frame_xyb(h, planes, stream)) return e;
 	d->decoded = std::max(d->decoded, k + 1);
-	if (sync) {
-		if (hipStreamSynchronize(stream) != hipSuccess) return ERR_GPU;
-		e = j40hip_frame_status(h);
-		if (e == ERR_EVOF) {   // (as play_frame: dense planes)
-			h->force_dense = true;
-			if ((e = j40hip_frame_upload(h, d->device)) != 0 || (e = decode_frame_xyb(h, planes, stream)) != 0) return e;
-			if (hipStreamSynchronize(stream) != hipSuccess) return ERR_GPU;
-			e = j40hip_frame_status(h);
-		}
-		if (e) return e;
-	}
-	d->lf_w[slot] = fh.width; d->lf_h[slot] = fh.height; d->lf_filled[slot] = true;
-	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
-}
-
-// A reference-only frame (type 2): its XYB planes into its reference slot, nothing composed, nothing shown
-uint32_t play_ref_frame(j40hip_sequence *s, int64_t k, j40hip_frame *h, hipStream_t stream, bool sync) {
-	j40hip_sequence_device *d = s->dev;
-	const j40hip_sequence::Row &row = s->rows[(size_t) k];
-	const FrameHeader &fh = row.fh;
-	const int slot = row.xyb_slot;
-	const size_t bytes = sizeof(float) * 3 * (size_t) fh.width * (size_t) fh.height;
-	if (slot < 0 || slot > 3 || !d->ref_xyb[slot].ptr || d->ref_xyb[slot].bytes < bytes) return ERR_GPU;   // (reserve_blocks sized it)
-	float *planes = (float *) d->ref_xyb[slot].ptr;
-	uint32_t e = decode_frame_xyb(h, planes, stream);
-	if (e) return e;
-	d->decoded = std::max(d->decoded, k + 1);
-	if (sync) {
-		if (hipStreamSynchronize(stream) != hipSuccess) return ERR_GPU;
-		e = j40hip_frame_status(h);
-		if (e == ERR_EVOF) {   // (as play_frame: dense planes)
-			h->force_dense = true;
-			if ((e = j40hip_frame_upload(h, d->device)) != 0 || (e = decode_frame_xyb(h, planes, stream)) != 0) return e;
-			if (hipStreamSynchronize(stream) != hipSuccess) return ERR_GPU;
-			e = j40hip_frame_status(h);
-		}
-		if (e) return e;
-	}
-	d->ref_w[slot] = fh.width; d->ref_h[slot] = fh.height; d->ref_filled[slot] = true;
-	d->slot_saved[slot] = false;   // (the slot holds planes now: no pixels for a later frame to draw over)
+	if (sync) if (uint32_t e = wait_with_dense_retry(h, d->device, stream, [&] { return decode_frame_xyb(h, planes, stream); })) return e;
+	*w = fh.width; *hh = fh.height; *filled = true;
 	return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 }
 
@@ -161,8 +120,19 @@ uint32_t play_frame(j40hip_sequence *s, int64_t k, uint8_t *out, size_t out_stri
 	j40hip_frame *h = s->frames[(size_t) k];
 	if (!h || !h->dev || h->dev->device != d->device) return ERR_GPU;
 	const FrameHeader &fh = row.fh;
-	if (fh.type == 1) return play_lf_frame(s, k, h, stream, sync);
-	if (row.stored_xyb) return play_ref_frame(s, k, h, stream, sync);
+	if (fh.type == 1) {   // an LF frame: it may take its own LF image from the next coarser level
+		const int slot = fh.lf_level - 1;
+		if (slot < 0 || slot > 3) return ERR_GPU;
+		if (fh.use_lf_frame) { if (uint32_t e = bind_lf_source(s, h, fh.lf_level)) return e; }
+		return play_plane_frame(s, k, h, stream, sync, d->lf_slot[slot], &d->lf_w[slot], &d->lf_h[slot], &d->lf_filled[slot]);
+	}
+	if (row.stored_xyb) {   // a reference-only frame
+		const int slot = row.xyb_slot;
+		if (slot < 0 || slot > 3) return ERR_GPU;
+		const uint32_t e = play_plane_frame(s, k, h, stream, sync, d->ref_xyb[slot], &d->ref_w[slot], &d->ref_h[slot], &d->ref_filled[slot]);
+		if (!e) d->slot_saved[slot] = false;   // (the slot holds planes now: no pixels for a later frame to draw over)
+		return e;
+	}
 	// (the main frame of an LF-frame still takes a scale and the orientation for decodes of its own, capi.hpp: the canvas is full size, stored order)
 	if (uint32_t e = mode_refusal(h, Mode::Playback)) return e;
 	const int32_t W = s->im.width, H = s->im.height;
@@ -180,17 +150,7 @@ uint32_t play_frame(j40hip_sequence *s, int64_t k, uint8_t *out, size_t out_stri
 	uint32_t e = j40hip_frame_decode(h, img, img_stride, stream);
 	if (e) return e;
 	d->decoded = std::max(d->decoded, k + 1);   // (enqueued: j40hip_sequence_status looks at it, whatever becomes of it)
-	if (sync) {
-		if (hipStreamSynchronize(stream) != hipSuccess) return ERR_GPU;
-		e = j40hip_frame_status(h);
-		if (e == ERR_EVOF) {   // a section with more non-zero coefficients than its event region holds: dense planes
-			h->force_dense = true;
-			if ((e = j40hip_frame_upload(h, d->device)) != 0 || (e = j40hip_frame_decode(h, img, img_stride, stream)) != 0) return e;
-			if (hipStreamSynchronize(stream) != hipSuccess) return ERR_GPU;
-			e = j40hip_frame_status(h);
-		}
-		if (e) return e;
-	}
+	if (sync) if ((e = wait_with_dense_retry(h, d->device, stream, [&] { return j40hip_frame_decode(h, img, img_stride, stream); })) != 0) return e;
 	if (!exact) {
 		const uint8_t *src = d->slot_saved[row.src] ? (const uint8_t *) d->slot[row.src].ptr : nullptr;
 		const bool a0 = renders_alpha(h);

@@ -160,7 +160,6 @@ struct j40hip_device_state {
 	bool mod_local_rcts = false;
 	bool has_trailers = false;           // VarDCT frame whose sections go on with the extra channels' Modular sub-image
 	bool idle = false;                   // j40hip_frame_mark_idle: nothing is pending on this frame's memory, freeing it needs no device-wide wait
-	bool trailers_pending = false;       // ... decoded by a batch since: j40hip_frame_status validates the sub-images before it reports
 	ModLaunchInfo mod_info = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	std::vector<uint32_t> mod_section_offsets;
 	// group: the group whose section's sub-image the op belongs to (mod_sub_ops; a ranged decode skips the ops of groups it did not decode), -1: the frame's
@@ -182,28 +181,26 @@ struct j40hip_device_state {
 	CacheBlock two_block;
 	std::vector<uint32_t> two_order;
 	hipStream_t two_stream = nullptr; hipEvent_t two_ev[3] = {nullptr, nullptr, nullptr};
-	// the restoration filters (decode_impl, restore_*): made at the first decode that runs them, kept with the frame
-	float *d_xyb = nullptr, *d_xyb_tmp = nullptr, *d_sigma = nullptr; int16_t *d_sharp = nullptr;
-	const float *d_restored = nullptr;   // where the last decode's filtered planes lie (d_xyb or d_xyb_tmp)
-	uint32_t restore_err = 0;            // the last decode's "gab0" / "epf0" / "shrp" (reported behind the sections' codes)
-	int restore_ran = 0;                 // the mode the last decode ran the filters in (0: it did not)
+	// the plane stage (runtime.hip). d_xyb: the frame's three full-size float planes (X, Y, B; width floats a row), made at the first
+	// decode that goes through planes (plane_buffer), kept with the frame
+	float *d_xyb = nullptr;
+	// the restoration filters (runtime.hip: restore_prepared, run_filters). restore: their parameters, the frame-wide sharpness map and
+	// what keeps them from running, made at the first decode that asks for them, kept with the upload. The second set of planes, the
+	// reciprocal sigmas and the map's copy are made at the first decode that runs them
+	struct Restore { bool ready = false; RestoreParams p; uint32_t err = 0; std::vector<int16_t> sharp; } restore;
+	float *d_xyb_tmp = nullptr, *d_sigma = nullptr; int16_t *d_sharp = nullptr;
+	const float *d_restored = nullptr;   // where the last filtered planes lie (d_xyb or d_xyb_tmp)
 	float restore_ms = 0;
-	// the colour mode (j40hip_frame_set_colour; runtime.hip: colour_pixels). colour: the tail's parameters and, for an 8-bit frame, its
-	// threshold table in device memory, made at the first decode that takes the tail, kept with the frame. d_colour_xyb: the planes the
-	// pixel kernels (or k_modular_to_xyb) leave for it where the restoration filters' buffers do not exist. colour_planes: what the last
-	// decode's tail read (j40hip_frame_read_xyb)
+	// the colour mode (j40hip_frame_set_colour; runtime.hip: colour_params). colour: the tail's parameters and, for an 8-bit frame, its
+	// threshold table in device memory, made at the first decode that takes the tail, kept with the frame
 	struct ColourTail { bool ready = false; ColourTailParams p; } colour;
-	float *d_colour_xyb = nullptr;
-	const float *colour_planes = nullptr;
 	// a frame with patches (runtime.hip: apply_patches): the handle's records and tiles (j40hip_frame::patch_plan, made when the sequence's
 	// index was built) copied into the frame's scratch at the upload; d_frame: a Modular frame's colour
-	// constants as the sRGB tail takes them (a VarDCT frame's are its plan's). patch_planes: the planes the last decode left after its
-	// patches (j40hip_frame_read_xyb, stage 3)
+	// constants as the sRGB tail takes them (a VarDCT frame's are its plan's)
 	struct Patches { DevPatches dev = {nullptr, nullptr, nullptr, nullptr, 0, 0}; std::vector<DevFrame> host_frame; const DevFrame *d_frame = nullptr; } patch;
-	const float *patch_planes = nullptr;
 	// a YCbCr frame (j40hip_frame_set_ycbcr; runtime.hip: ycbcr_pixels). ycbcr: the plan was built for one (the switch was on at upload).
-	// d_ycc: the planes the pixel kernels leave for k_ycbcr_tail, made at the first decode, kept with the frame. ycc_read: what the last
-	// decode's tail read (j40hip_frame_read_ycbcr) -- those planes, or the restoration filters' result
+	// d_ycc: the planes the pixel kernels leave for k_ycbcr_tail where the filters do not run, made at the first such decode, kept with
+	// the frame. ycc_read: what the last decode's tail read (j40hip_frame_read_ycbcr) -- those planes, or the restoration filters' result
 	bool ycbcr = false;
 	float *d_ycc = nullptr;
 	struct YccRead { const float *plane[3] = {nullptr, nullptr, nullptr}; int32_t pitch[3] = {0, 0, 0}, pw[3] = {0, 0, 0}, ph[3] = {0, 0, 0}; } ycc_read;
@@ -261,6 +258,8 @@ struct j40hip_device_state {
 		buffers.push_back(b);
 		return (T *) b.ptr;
 	}
+	// a buffer kept with the frame, made when first needed; false ("!mem"): there is none, and the pointer stays null
+	template <typename T> bool keep(T *&p, size_t n) { bool ok = true; if (!p) p = scratch<T>(n, ok); return p != nullptr; }
 };
 
 namespace j40hip_rt {
@@ -294,6 +293,18 @@ uint32_t clear_before_decode(j40hip_device_state *st, hipStream_t s);          /
 uint32_t decode_frame_xyb(j40hip_frame *h, float *planes, hipStream_t s);      // runtime.hip
 uint32_t apply_patches(j40hip_frame *h, float *planes, hipStream_t s);         // runtime.hip
 uint32_t restore_params(const FrameHeader &fh, int mode, RestoreParams *p);    // runtime.hip
+// A synchronous entry's wait behind a decode it has enqueued on `s`: the stream, then the frame's status. A section with more non-zero
+// coefficients than its event region holds ("evof") has the frame uploaded again with dense planes, `decode` enqueues it once more, and
+// that one's status is the answer.
+template <typename F> uint32_t wait_with_dense_retry(j40hip_frame *h, int device, hipStream_t s, F decode) {
+	for (int dense = 0;; ++dense) {
+		if (hipStreamSynchronize(s) != hipSuccess) return ERR_GPU;
+		uint32_t e = j40hip_frame_status(h);
+		if (e != ERR_EVOF || dense) return e;
+		h->force_dense = true;
+		if ((e = j40hip_frame_upload(h, device)) != 0 || (e = decode()) != 0) return e;
+	}
+}
 void lf_services_shutdown();   // runtime_lf.hip, runtime.hip, runtime_lfp.hip: j40hip_shutdown's steps
 void two_phase_shutdown();
 void lfp_args_shutdown();

@@ -11,6 +11,7 @@ extern "C" void j40hip_release_device(j40hip_frame *f) {
 	for (auto &e : f->dev->ev) if (e) (void) hipEventDestroy(e);
 	delete f->dev;
 	f->dev = nullptr;
+	f->last.device_released();
 }
 
 extern "C" int j40hip_device_count(void) {

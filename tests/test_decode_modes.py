@@ -41,6 +41,11 @@ def load_fixture(path):
         return json.load(fp)
 
 
+def write_fixture(path, table):
+    with open(path, "wb") as raw, gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0, compresslevel=9) as fp:   # (no name, no time: the same bytes for the same table)
+        fp.write((json.dumps(table, separators=(",", ":"), sort_keys=True) + "\n").encode())
+
+
 def no_switches():
     for name in SWITCHES:
         assert os.environ.get(name, "") in ("", "0"), "this file sets every mode itself: unset %s" % name
@@ -395,6 +400,5 @@ if __name__ == "__main__":
         j40_amd.shutdown()
     else:
         raise SystemExit("record-setters OUT COMMIT | record-routes OUT COMMIT")
-    with open(out, "wb") as raw, gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0, compresslevel=9) as fp:   # (no name, no time: the same bytes for the same table)
-        fp.write((json.dumps(table, separators=(",", ":"), sort_keys=True) + "\n").encode())
+    write_fixture(out, table)
     print({k: v for k, v in table.items() if k in ("cases", "header")})
