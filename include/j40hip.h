@@ -70,6 +70,19 @@ J40HIP_API void j40hip_frame_free(j40hip_frame *f);
  * with 32-bit sample planes; a VarDCT frame of one is "TODO" at parse. J40HIP_WIDE=1 in the environment does the same for every parse,
  * and j40hip_sequence_open takes the flag too. */
 #define J40HIP_PARSE_WIDE 8u
+/* flags & J40HIP_PARSE_NOISE: photon noise is asked for. PARITY UNPINNED: the reference stops at has_noise (j40.h:6264, "TODO"), and so
+ * does every parse without this flag. With it a frame whose header has has_noise is parsed -- its eight NoiseParameters follow the patch
+ * dictionary in LfGlobal (splines, which would stand between them, stay "TODO") -- and every decode of the frame adds the noise to the
+ * frame's XYB samples behind the restoration filters and the patches, ahead of the colour tail (k_noise_fill, k_noise_add;
+ * j40_amd/csrc/device/noise_dev.h states the rule). "TODO" at parse even with the flag: an image with xyb_encoded = 0; an LF frame or a
+ * reference-only frame (type 1 or 2) with has_noise. A frame with noise decodes whole frames at full size: a region or a scale is cut
+ * or averaged from the full-size picture, the orientation, kept alpha, the restoration filters, the colour mode and patches combine
+ * with it; a Modular frame needs the Modular XYB switch (j40hip_frame_set_modular_xyb), a YCbCr plan, a group range, a batch, a
+ * pipeline, the LF preview and an LF-only parse of such a frame are "TODO". A LUT of eight zeros launches nothing.
+ * J40HIP_NOISE=1 in the environment does the same for every parse, and j40hip_sequence_open takes the flag too: the frames of a
+ * sequence get the seed counters of their place in it (visible: the shown frames before it, nonvisible: the frames since the last
+ * shown one); a stand-alone handle has both 0. */
+#define J40HIP_PARSE_NOISE 256u
 /* the shortest prefix of the codestream holding headers, TOC, LfGlobal and every LfGroup section (the largest end among those
  * sections, so a permuted TOC is covered); a bare codestream's file prefix. Single-section frames: the whole codestream. */
 J40HIP_API int64_t j40hip_frame_lf_end(const j40hip_frame *f);
@@ -579,6 +592,9 @@ J40HIP_API int j40hip_frame_sharpness(const j40hip_frame *f, int64_t gg, int16_t
  * ones ([3][height][width] floats); 2 the reciprocal-sigma plane of the edge-preserving filter (w8*h8 floats, < 0: the cell is skipped).
  * Stage 3, after any decode of a frame with patches (J40HIP_SEQ_PATCHES): the planes after k_patch_blend, as the tail read them */
 J40HIP_API uint32_t j40hip_frame_read_xyb(j40hip_frame *f, int stage, float *out);
+/* Stage 4, after any decode of a frame with noise (J40HIP_PARSE_NOISE): the planes after k_noise_add, as the tail read them. For a
+ * frame with both patches and noise stage 3 answers "rnge": the patched planes are noised in place, what stood between the two is gone.
+ * A frame whose LUT is all zeros answers stage 4 with the planes the tail read. */
 J40HIP_API float j40hip_frame_restoration_ms(const j40hip_frame *f);   /* device time of the filter kernels in the last decode (J40HIP_RESTORATION_TIMING=1) */
 /* known-answer hook: the filter kernels on caller-supplied planes (xyb: [3][h][w] floats, host, in place), a w8*h8 sharpness map and the
  * HfMul reciprocal of the varblock covering each cell; mode 1 or 2; sigma_out optional. 0 or "gab0" / "epf0" / "shrp" / "!gpu". */
@@ -697,6 +713,21 @@ J40HIP_API void j40hip_sequence_frame_lf(const j40hip_sequence *s, int64_t k, in
 /* debug read-back (synchronises the device): plane c (0 X, 1 Y, 2 B) of LF slot `level` - 1 as the playback last filled it, tightly
  * packed floats of the LF frame's size. "rnge": no such slot, or nothing stored in it since the last rewind. */
 J40HIP_API uint32_t j40hip_sequence_read_lf_slot(j40hip_sequence *s, int32_t level, int32_t c, float *out);
+/* ---- photon noise (J40HIP_PARSE_NOISE above) ----
+ * j40hip_frame_noise: has_noise of the frame's header; lut8 (optional): the eight NoiseParameters / 1024, seeds2 (optional): the seed
+ * counters visible, nonvisible the next decode uses. launches: how often decodes of the handle have launched the two kernels.
+ * j40hip_frame_noise_ms: with J40HIP_NOISE_TIMING=1 in the environment the device time of k_noise_fill (ms2[0]) and k_noise_add (ms2[1])
+ * in the last decode, which then waits for them; else zeros. */
+J40HIP_API int j40hip_frame_noise(const j40hip_frame *f, float *lut8, uint32_t *seeds2);
+J40HIP_API int64_t j40hip_frame_noise_launches(const j40hip_frame *f);
+J40HIP_API void j40hip_frame_noise_ms(const j40hip_frame *f, float *ms2);
+/* known-answer / measuring hook: the two kernels alone. planes_dev: three planes (X, Y, B) of width x height floats, one behind the
+ * other, changed in place; group_dim: the side of a group (a multiple of 16, 16..1024); lut8, ytox (base_corr_x), ytob (base_corr_b),
+ * visible, nonvisible: as the rule takes them. raw_out_dev (optional): the three raw planes the fill made, width x height floats each,
+ * tightly packed. A LUT of zeros launches nothing and leaves raw_out_dev alone. ms2 (optional): the two kernels' device time.
+ * Enqueued on `stream` and waited for. "rnge": a size the kernels do not take. */
+J40HIP_API uint32_t j40hip_kat_device_noise(float *planes_dev, int32_t width, int32_t height, int32_t group_dim, const float *lut8, float ytox, float ytob,
+		uint32_t visible, uint32_t nonvisible, float *raw_out_dev, void *stream, float *ms2);
 /* ---- patches: reference-only frames and the patch dictionary. PARITY UNPINNED: the reference holds no code for either (j40.h:6262 is a
  *      TODO); off by default. With J40HIP_SEQ_PATCHES (or J40HIP_PATCHES=1 in the environment) a sequence takes
  *      - a reference-only frame (type 2) with save_before_colour_transform = 1 of an image with xyb_encoded = 1: a frame of its own width

@@ -24,6 +24,7 @@ J40_U8X4 = 0x0F33
 J40_U16X4 = 0x0F35
 PARSE_LF_ONLY = 2   # J40HIP_PARSE_LF_ONLY (include/j40hip.h): the LF preview's parse
 PARSE_YCBCR = 4     # J40HIP_PARSE_YCBCR: YCbCr frames are asked for (a subsampled one is parsed instead of refused)
+PARSE_NOISE = 256   # J40HIP_PARSE_NOISE: photon noise is asked for (a frame with has_noise is parsed and its noise added instead of "TODO"); j40hip_sequence_open takes it too
 PARSE_WIDE = 8      # J40HIP_PARSE_WIDE: wide Modular frames are asked for (an image with 32-bit Modular buffers is parsed instead of "fm32")
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,6 +129,8 @@ def lib():
         "j40hip_kat_device_compose": (u32, [vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, u32, u32, i32, vp]),
         "j40hip_sequence_frame_blend": (None, [vp, i64, vp]),
         "j40hip_sequence_frame_lf": (None, [vp, i64, vp]), "j40hip_sequence_read_lf_slot": (u32, [vp, i32, i32, vp]),
+        "j40hip_frame_noise": (C.c_int, [vp, vp, vp]), "j40hip_frame_noise_launches": (i64, [vp]), "j40hip_frame_noise_ms": (None, [vp, vp]),
+        "j40hip_kat_device_noise": (u32, [vp, i32, i32, i32, vp, C.c_float, C.c_float, u32, u32, vp, vp, vp]),
         "j40hip_sequence_frame_patches": (None, [vp, i64, vp]), "j40hip_sequence_frame_patch": (u32, [vp, i64, i64, vp]),
         "j40hip_sequence_ref_slot_size": (u32, [vp, i32, vp, vp]), "j40hip_sequence_read_ref_slot": (u32, [vp, i32, i32, vp]),
         "j40hip_kat_device_patches": (u32, [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]),
@@ -245,7 +248,7 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False, blend=False):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False, blend=False, noise=False):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
     scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
     (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
@@ -274,12 +277,14 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     through a Sequence on device 0 opened with the switch (Sequence's patches=), the first displayed canvas. It combines with
     modular_xyb=, colour=, lf_frames= and blend= (Sequence's blend=, which only this route takes), which open the sequence with theirs,
     and with fmt and scale (the shown frame's own handle decoded once more at the scale, as with lf_frames=True: a full-canvas frame with
-    patches takes one); "TODO" with orient= unless lf_frames= is given too."""
+    patches takes one); "TODO" with orient= unless lf_frames= is given too.
+    noise=True: a frame with photon noise (has_noise) is served for this call whatever J40HIP_NOISE says (PARSE_NOISE; PARITY UNPINNED),
+    through the thin C-ABI on device 0; it combines with every switch above (a sequence is opened with it)."""
     if lf_frames or patches:
         if alpha or ycbcr or wide or (patches and not lf_frames and orient):
             return "TODO", None
         try:
-            seq = Sequence(data, lf_frames=bool(lf_frames), modular_xyb=bool(modular_xyb), colour=bool(colour), patches=bool(patches), blend=bool(blend))
+            seq = Sequence(data, lf_frames=bool(lf_frames), modular_xyb=bool(modular_xyb), colour=bool(colour), patches=bool(patches), blend=bool(blend), noise=bool(noise))
         except J40Error as e:
             if e.code != "Usq?":
                 return e.code, None
@@ -303,9 +308,9 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
                 return e.code, None
             finally:
                 seq.close()
-    if alpha or scale or ycbcr or orient or wide or modular_xyb or colour:
+    if alpha or scale or ycbcr or orient or wide or modular_xyb or colour or noise:
         try:
-            fr = Frame(data, ycbcr=bool(ycbcr), wide=bool(wide))
+            fr = Frame(data, ycbcr=bool(ycbcr), wide=bool(wide), noise=bool(noise))
         except J40Error as e:
             return e.code, None
         try:
@@ -342,15 +347,15 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     return err, out
 
 
-def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False, wide=False, colour=False):
+def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False, wide=False, colour=False, noise=False):
     """rectangle (x, y, w, h) of the image through the thin C-ABI: returns (err4, ndarray [h, w, 4] or None), uint8 or uint16 with
     fmt=J40_U16X4 -- the crop of what decode() returns, decoded from the pass groups that cover it (Frame.set_region). The verdict is
     the one over the sections that were decoded, then the public API's look behind the frame.
     orient=True: (x, y, w, h) is a rectangle of the DISPLAYED picture -- the frame in the orientation its stream carries; it is mapped
     to stored coordinates (Frame.orient_rect) and the result is the crop of the oriented whole picture, [h, w, 4].
-    wide=True, colour=True: as decode()'s."""
+    wide=True, colour=True, noise=True: as decode()'s (a frame with noise: the crop of the full-size picture)."""
     try:
-        fr = Frame(data, wide=bool(wide))
+        fr = Frame(data, wide=bool(wide), noise=bool(noise))
     except J40Error as e:
         return e.code, None
     try:
@@ -595,6 +600,36 @@ def kat_device_patches(planes, slots, placements, device=0):
     return "", host[guard:guard + planes.size].reshape(3, h, w).copy(), int(tiles.value)
 
 
+def kat_device_noise(planes, group_dim, lut, ytox, ytob, visible=0, nonvisible=0, device=0, want_ms=False):
+    """k_noise_fill and k_noise_add alone (j40hip_kat_device_noise): planes [3, h, w] float32 (X, Y, B) -> (err4, the planes after the noise
+    or None, the raw planes [3, h, w] the fill made -- zeros for a LUT of zeros, which launches nothing); with want_ms a fourth entry, the
+    two kernels' device time in ms. The planes sit between guard floats, which must come back untouched (asserted here)"""
+    import torch
+    planes = np.ascontiguousarray(planes, np.float32)
+    _, h, w = planes.shape
+    dev = "cuda:%d" % device
+    guard = 64
+    buf = np.full(guard + planes.size + guard, 12345.0, np.float32)
+    buf[guard:guard + planes.size] = planes.ravel()
+    d_buf = torch.from_numpy(buf).to(dev)
+    d_raw = torch.zeros(guard + planes.size + guard, dtype=torch.float32, device=dev)
+    lut = np.ascontiguousarray(lut, np.float32)
+    assert lut.size == 8
+    ms = np.zeros(2, np.float32)
+    torch.cuda.synchronize(dev)
+    with torch.cuda.device(dev):
+        code = err4(lib().j40hip_kat_device_noise(d_buf.data_ptr() + 4 * guard, w, h, int(group_dim), lut.ctypes.data, float(ytox), float(ytob), int(visible), int(nonvisible),
+                                                  d_raw.data_ptr() + 4 * guard, None, ms.ctypes.data if want_ms else None))
+        torch.cuda.synchronize(dev)
+    host = d_buf.cpu().numpy(); raw = d_raw.cpu().numpy()
+    assert (host[:guard] == 12345.0).all() and (host[-guard:] == 12345.0).all(), "k_noise_add wrote outside the planes"
+    assert (raw[:guard] == 0.0).all() and (raw[-guard:] == 0.0).all(), "the raw planes' copy wrote outside them"
+    if code:
+        return (code, None, None) + ((None,) if want_ms else ())
+    out = ("", host[guard:guard + planes.size].reshape(3, h, w).copy(), raw[guard:guard + planes.size].reshape(3, h, w).copy())
+    return out + (((float(ms[0]), float(ms[1])),) if want_ms else ())
+
+
 def kat_device_srgb_u16(values, bpp):
     """j40hip_kat_device_srgb_u16: linear values -> the 16-bit output sample at bit depth bpp, on the device; returns (err4, uint16 array)"""
     v = np.ascontiguousarray(values, np.float32)
@@ -617,18 +652,20 @@ def kat_device_restoration(planes, sharpness, hfmul_inv, r, mode=1, device=0):
 class Frame:
     """thin C-ABI (include/j40hip.h): host parse, plan upload, hot path on a HIP stream"""
 
-    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False, ycbcr=False, wide=False):
+    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False, ycbcr=False, wide=False, noise=False):
         """lf_device: a HIP device index -- the LfGroup streams are decoded there instead of on the host (j40hip_frame_parse_on).
         lf_only: parse what the LF preview needs and nothing more (J40HIP_PARSE_LF_ONLY): `data` may end at lf_end(); such a frame
         can only be previewed (decode_lf_to_host, decode_lf).
         ycbcr: YCbCr frames are asked for (J40HIP_PARSE_YCBCR): a frame with subsampled channels is parsed instead of refused; serving
         it still takes set_ycbcr(1) (or J40HIP_YCBCR=1)
         wide: wide Modular frames are asked for (J40HIP_PARSE_WIDE): an image with 32-bit Modular buffers is parsed instead of refused
-        with "fm32", and its Modular frame is decoded with int32 sample planes (wide())"""
+        with "fm32", and its Modular frame is decoded with int32 sample planes (wide())
+        noise: photon noise is asked for (J40HIP_PARSE_NOISE; PARITY UNPINNED): a frame with has_noise is parsed instead of refused
+        with "TODO" and every decode adds its noise (noise_params(), noise_launches(), read_xyb(4))"""
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        flags = (PARSE_LF_ONLY if lf_only else 0) | (PARSE_YCBCR if ycbcr else 0) | (PARSE_WIDE if wide else 0)
+        flags = (PARSE_LF_ONLY if lf_only else 0) | (PARSE_YCBCR if ycbcr else 0) | (PARSE_WIDE if wide else 0) | (PARSE_NOISE if noise else 0)
         if lf_device is None:
             self.h = L.j40hip_frame_parse_ex(self._buf, len(data), threads, flags, C.byref(err))
         else:
@@ -997,10 +1034,29 @@ class Frame:
     def read_xyb(self, stage):
         """after a decode that ran the filters: stage 0 / 1 -> [3, height, width] float32 (before / after them), 2 -> the reciprocal sigmas [h8, w8].
         A Modular frame of an XYB image decoded with set_modular_xyb(1) in force: stage 0 -> the planes X, Y, B by k_modular_to_xyb.
-        A frame with patches (Sequence's patches=): stage 3 -> [3, height, width], the planes after k_patch_blend, as the tail read them"""
+        A frame with patches (Sequence's patches=): stage 3 -> [3, height, width], the planes after k_patch_blend, as the tail read them.
+        A frame with noise (noise=True): stage 4 -> the planes after k_noise_add, as the tail read them (with both, stage 3 is "rnge")"""
         a = np.zeros((3, self.height, self.width), np.float32) if stage != 2 else np.zeros(((self.height + 7) // 8, (self.width + 7) // 8), np.float32)
         self._chk(lib().j40hip_frame_read_xyb(self.h, stage, a.ctypes.data), "in j40hip_frame_read_xyb")
         return a
+
+    def noise_params(self):
+        """photon noise (j40hip_frame_noise): None for a frame without has_noise, else a dict -- "lut": the eight NoiseParameters / 1024
+        (float32), "seeds": the seed counters (visible, nonvisible) the next decode uses (a sequence's index counts them)"""
+        lut = np.zeros(8, np.float32); seeds = np.zeros(2, np.uint32)
+        if not lib().j40hip_frame_noise(self.h, lut.ctypes.data, seeds.ctypes.data):
+            return None
+        return {"lut": lut, "seeds": (int(seeds[0]), int(seeds[1]))}
+
+    def noise_launches(self):
+        """how often decodes of this handle have launched k_noise_fill and k_noise_add (never for a LUT of eight zeros)"""
+        return int(lib().j40hip_frame_noise_launches(self.h))
+
+    def noise_ms(self):
+        """with J40HIP_NOISE_TIMING=1: the device time of (k_noise_fill, k_noise_add) in the last decode"""
+        ms = np.zeros(2, np.float32)
+        lib().j40hip_frame_noise_ms(self.h, ms.ctypes.data)
+        return float(ms[0]), float(ms[1])
 
     def restoration_ms(self):
         return float(lib().j40hip_frame_restoration_ms(self.h))
@@ -1183,13 +1239,15 @@ class Sequence:
     together with lf_frames=True a Modular LF frame is served, with either alone it is "TODO".
     patches=True (or J40HIP_PATCHES=1): reference-only frames (type 2, stored as XYB planes in their reference slot, never shown) and
     the frames whose patch dictionary blends rectangles of them onto their own XYB samples are served too, else "TODO" (frame_patches,
-    frame_patch, read_ref_slot); a Modular reference-only frame needs modular_xyb=True as well. PARITY UNPINNED."""
+    frame_patch, read_ref_slot); a Modular reference-only frame needs modular_xyb=True as well. PARITY UNPINNED.
+    noise=True (or J40HIP_NOISE=1): frames with photon noise are served (Frame's noise=); each gets the seed counters of its place in
+    the sequence (Frame.noise_params()), so two shown frames get different fields. PARITY UNPINNED."""
 
-    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False, modular_xyb: bool = False, colour: bool = False, patches: bool = False):
+    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False, modular_xyb: bool = False, colour: bool = False, patches: bool = False, noise: bool = False):
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0) | (SEQ_MODULAR_XYB if modular_xyb else 0) | (SEQ_COLOUR if colour else 0) | (SEQ_PATCHES if patches else 0)
+        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0) | (SEQ_MODULAR_XYB if modular_xyb else 0) | (SEQ_COLOUR if colour else 0) | (SEQ_PATCHES if patches else 0) | (PARSE_NOISE if noise else 0)
         self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags, C.byref(err))
         if not self.h:
             raise J40Error(err4(err.value), "in j40hip_sequence_open")
@@ -1328,7 +1386,7 @@ class Sequence:
         return err4(code), int(k.value)
 
 
-def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False):
+def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False, noise=False):
     """every displayed frame of an animation or a layered still: ([(rgba ndarray [height, width, 4], duration in ticks), ...],
     (tps_num, tps_den, loops)). alpha=True: VarDCT frames keep their alpha channel (Frame.set_alpha(1); J40Error where that refuses).
     blend=True: frames with a blend mode other than Replace are composed too (Sequence's blend=), else such a frame raises "TODO".
@@ -1337,8 +1395,9 @@ def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False,
     modular_xyb=True: Modular frames of an XYB image go through the XYB colour tail (Sequence's modular_xyb=).
     colour=True: every frame is rendered in the colour space the image header signals (Sequence's colour=).
     patches=True: reference-only frames and the frames with a patch dictionary are served (Sequence's patches=), else "TODO".
+    noise=True: frames with photon noise are served (Sequence's noise=), else "TODO".
     A frame that fails raises J40Error with its code. A stream whose first frame is its last is not a sequence ("Usq?"): decode()."""
-    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames, modular_xyb=modular_xyb, colour=colour, patches=patches)
+    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames, modular_xyb=modular_xyb, colour=colour, patches=patches, noise=noise)
     try:
         seq.set_output_format(fmt)
         if alpha:

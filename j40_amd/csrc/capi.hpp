@@ -76,6 +76,10 @@ struct j40hip_frame {
 	// null: nothing bound, a decode that reads the slot is "ptno". patch_launches: how often a decode of this handle has launched k_patch_blend
 	struct PatchSource { const float *base = nullptr; int32_t w = 0, h = 0; } patch_src[4];
 	int64_t patch_launches = 0;
+	// a frame with noise (J40HIP_PARSE_NOISE): the seed counters its decodes use -- a sequence's index counts them (Row::noise_seeds), a
+	// stand-alone handle has zeros; noise_launches: how often a decode of this handle has launched k_noise_fill and k_noise_add
+	uint32_t noise_seeds[2] = {0, 0};
+	int64_t noise_launches = 0;
 	std::shared_ptr<const j40hip::PatchPlan> patch_plan;   // the placements as records and their tiles, as the sequence's index made them (null: no dictionary)
 	int threads = 1;                 // what the frame was parsed with: the plan build at upload may use as many (plan_build.cpp)
 	// backing storage of the plan views (include/j40hip.h)
@@ -122,6 +126,9 @@ struct j40hip_sequence {
 		int32_t xyb_slot = -1;
 		j40hip::PatchDictionary patches;
 		std::shared_ptr<const j40hip::PatchPlan> patch_plan;
+		// photon noise (J40HIP_PARSE_NOISE): the counters visible, nonvisible when the playback reaches the row -- the shown frames before
+		// it, the frames since the last shown one (device/noise_dev.h)
+		uint32_t noise_seeds[2] = {0, 0};
 	};
 	std::vector<Row> rows;
 	std::vector<j40hip_frame *> frames;   // [rows.size()], parsed when first asked for
@@ -131,6 +138,7 @@ struct j40hip_sequence {
 	bool colour = false;             // every handle renders in the signalled colour space (J40HIP_SEQ_COLOUR or J40HIP_COLOUR=1)
 	bool colour_asked = false;       // ... by the flag itself: an image the mode refuses as a whole then fails j40hip_sequence_open
 	bool modular_xyb = false;        // Modular frames of an XYB image go through the XYB colour tail (J40HIP_SEQ_MODULAR_XYB or J40HIP_MODULAR_XYB=1)
+	bool noise = false;              // frames with has_noise are served (J40HIP_PARSE_NOISE or J40HIP_NOISE=1)
 	bool patches = false;            // reference-only frames and patch dictionaries are served (J40HIP_SEQ_PATCHES or J40HIP_PATCHES=1)
 	int32_t alpha_ec = -1;           // the extra channel that is rendered as A (rendered_alpha_channel); -1: none
 	int32_t output_format = J40HIP_U8X4;

@@ -27,6 +27,7 @@ j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads,
 		h->frame.lf_decoder = lf_decoder; h->frame.lf_decoder_ctx = lf_ctx;
 		h->frame.allow_ycbcr = (flags & J40HIP_PARSE_YCBCR) != 0 || ycbcr_env();
 		h->frame.allow_wide = (flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
+		h->frame.allow_noise = (flags & J40HIP_PARSE_NOISE) != 0 || noise_env();
 		extract_codestream((const uint8_t *) buf, size, &h->cs, &h->cs_size, &h->cs_storage, &h->container_stray_tail);
 		h->bare_codestream = h->cs == (const uint8_t *) buf && h->cs_size == size;
 		parse_frame(h->cs, h->cs_size, &h->frame, threads);
@@ -57,6 +58,7 @@ j40hip_frame *j40hip_frame_parse_streamed(const void *buf, size_t size, int thre
 		h->frame.need_bytes = need; h->frame.have_bytes = have; h->frame.need_ctx = ctx;
 		h->frame.allow_ycbcr = (flags & J40HIP_PARSE_YCBCR) != 0 || ycbcr_env();
 		h->frame.allow_wide = (flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
+		h->frame.allow_noise = (flags & J40HIP_PARSE_NOISE) != 0 || noise_env();
 		h->cs = p; h->cs_size = size; h->bare_codestream = true;
 		parse_frame(h->cs, h->cs_size, &h->frame, threads);
 		h->threads = threads < 1 ? 1 : threads > 16 ? 16 : threads;
@@ -164,6 +166,8 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 		s->colour = (flags & J40HIP_SEQ_COLOUR) != 0 || env_on("J40HIP_COLOUR", false);
 		s->colour_asked = (flags & J40HIP_SEQ_COLOUR) != 0;
 		s->patches = (flags & J40HIP_SEQ_PATCHES) != 0 || env_on("J40HIP_PATCHES", false);
+		s->noise = (flags & J40HIP_PARSE_NOISE) != 0 || noise_env();
+		uint32_t noise_seeds[2] = {0, 0};   // visible, nonvisible as the playback reaches the next row
 		size_t at = 0;
 		parse_image_header(s->cs, s->cs_size, &s->im, &at, (flags & J40HIP_PARSE_WIDE) != 0 || wide_env());
 		s->alpha_ec = rendered_alpha_channel(s->im);
@@ -228,6 +232,8 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 				J40HIP_SHOULD(!row.fh.is_last, "Usq?");   // not a sequence: j40hip_frame_parse's
 			}
 			row.shown = !row.code && (row.fh.duration > 0 || row.fh.is_last);
+			row.noise_seeds[0] = noise_seeds[0]; row.noise_seeds[1] = noise_seeds[1];
+			if (row.shown) { ++noise_seeds[0]; noise_seeds[1] = 0; } else ++noise_seeds[1];
 			row.saved = !row.code && !row.fh.is_last && (row.fh.duration == 0 || row.fh.save_as_ref != 0) && row.fh.type != 1 && row.fh.type != 2;   // (an LF frame goes to its LF slot only, a reference-only frame to its slot's XYB planes)
 			// (a slot holds one thing: pixels saved into it take the place of a reference-only frame's planes)
 			if (row.stored_xyb) ref_row[row.xyb_slot] = (int32_t) s->rows.size();
@@ -278,6 +284,14 @@ void j40hip_sequence_frame_blend(const j40hip_sequence *s, int64_t k, int32_t *o
 	out[4] = a.alpha_chan; out[5] = a.clamp; out[6] = r.src; out[7] = r.blended && !r.code;
 }
 
+int j40hip_frame_noise(const j40hip_frame *h, float *lut8, uint32_t *seeds2) {
+	if (!h) return 0;
+	if (lut8) memcpy(lut8, h->frame.noise_lut, sizeof(float) * 8);
+	if (seeds2) { seeds2[0] = h->noise_seeds[0]; seeds2[1] = h->noise_seeds[1]; }
+	return h->frame.fh.has_noise ? 1 : 0;
+}
+int64_t j40hip_frame_noise_launches(const j40hip_frame *h) { return h ? h->noise_launches : 0; }
+
 void j40hip_sequence_frame_patches(const j40hip_sequence *s, int64_t k, int32_t *out8) {
 	if (!out8) return;
 	memset(out8, 0, sizeof(int32_t) * 8);
@@ -326,12 +340,13 @@ j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err
 		h->bare_codestream = true;
 		h->frame.defer_lf_tail = (s->flags & 1u) != 0;
 		h->frame.seq_im = &s->im; h->frame.seq_blend = s->blend; h->frame.allow_lf_frame = s->lf_frames; h->frame.allow_modular_lf = s->lf_frames && s->modular_xyb; h->frame.allow_wide = (s->flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
-		h->frame.allow_patches = s->patches; h->frame.allow_modular_ref = s->patches && s->modular_xyb;
+		h->frame.allow_patches = s->patches; h->frame.allow_modular_ref = s->patches && s->modular_xyb; h->frame.allow_noise = s->noise;
 		parse_frame(h->cs, h->cs_size, &h->frame, s->threads);
 		h->threads = s->threads;
 		h->output_format = s->output_format;
 		h->from_sequence = true;
 		h->patch_plan = r.patch_plan;
+		h->noise_seeds[0] = r.noise_seeds[0]; h->noise_seeds[1] = r.noise_seeds[1];
 		h->modular_xyb = s->modular_xyb ? 1 : 0;   // (in force where the rule applies: j40hip_modular_xyb_on)
 		h->colour = s->colour ? 1 : 0;             // (likewise: j40hip_colour_on)
 		// one canvas, one colour space: where the image's frames render in the signalled space, a frame that cannot -- a Modular frame

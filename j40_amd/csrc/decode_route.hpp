@@ -2,6 +2,10 @@
 // kept alpha, YCbCr, Modular XYB, the group range): resolve_route states what the next decode does, mode_refusal which modes exclude which; the
 // setters, the getters and every decode entry read their answers. A further mode is added here. Host code only: no HIP, nothing allocated.
 // (A further operation on a frame's XYB planes -- behind the filters, ahead of the tail -- is added in device/runtime.hip: render_planes.)
+// Photon noise (a frame parsed with J40HIP_PARSE_NOISE whose header has has_noise) is such an operation, and like patches a property of the
+// frame, not a mode of the handle: DecodeRoute::noise sends the decode through the plane stage -- whole frames at full size, from which a
+// region is cut and a scale averaged (full_size_first), in one phase --, and refuses what has no full-size XYB planes to add it to: a
+// Modular frame without the Modular XYB switch, a YCbCr plan, a partial group range, a batch, many LF previews in one launch (an LF-only parse of such a frame is refused by the parse).
 #pragma once
 #include "capi.hpp"
 #include "device/orient_dev.h"
@@ -24,7 +28,8 @@ inline uint32_t mode_refusal(const j40hip_frame *h, Mode what) {
 	const bool owned = h->from_sequence && !j40hip_lf_still_handle(h);   // the playback owns its size and order (capi.hpp: but for the main frame of an LF-frame still)
 	const bool owned_size = owned && !j40hip_patch_still_handle(h);     // ... its size also but for a full-canvas frame with patches
 	// (patches go onto whole pictures' planes through one handle's own tail: no batch, no preview of the LF image alone, no partial range)
-	const bool patches = h->frame.fh.has_patches;
+	// (noise likewise: it is added to whole pictures' planes)
+	const bool patches = h->frame.fh.has_patches || h->frame.fh.has_noise;
 	if (patches && (what == Mode::GroupRange || what == Mode::Batch || what == Mode::LfPreviewBatch)) return ERR_TODO;
 	switch (what) {
 	case Mode::Region:         return h->partial_range ? ERR_URG : h->scale > 0 ? ERR_USC : 0;
@@ -60,6 +65,7 @@ struct DecodeRoute {
 	bool alpha_merged = false;         // the extra channels' sub-images carry an alpha channel that is kept: k_alpha_merge writes it into full-size pixels
 	bool modular_xyb = false;          // a Modular plan through the XYB colour tail
 	bool patches = false;              // the frame has a patch dictionary: its pixels come from XYB planes (the filtered ones where the filters are in force), k_patch_blend over them, then the tail
+	bool noise = false;                // the frame has noise: likewise, k_noise_fill and k_noise_add behind the patches, ahead of the tail
 	bool colour = false;               // the colour mode in force: the XYB planes (filtered where the filters are in force; a Modular XYB plan's by k_modular_to_xyb) go through k_colour_tail
 	bool every_group = true;           // no partial group range
 	bool two_phase = false;            // decode_to_host may try its two phases: a whole frame in stored order that takes no LF frame's picture
@@ -87,16 +93,17 @@ inline DecodeRoute resolve_route(const j40hip_frame *h, const UploadFacts *up, b
 	r.modular_xyb = up->is_modular && j40hip_modular_xyb_on(h);
 	r.colour = j40hip_colour_on(h);
 	r.patches = fr.fh.has_patches;
-	const bool full_size_only = r.colour || r.patches || (up->is_modular ? r.modular_xyb && r.shape == DecodeRoute::Scaled : r.restoration || r.alpha_merged);
+	r.noise = fr.fh.has_noise;
+	const bool full_size_only = r.colour || r.patches || r.noise || (up->is_modular ? r.modular_xyb && r.shape == DecodeRoute::Scaled : r.restoration || r.alpha_merged);
 	r.full_size_first = r.shape != DecodeRoute::Whole && full_size_only;
-	r.two_phase = r.shape == DecodeRoute::Whole && r.orientation == 1 && !fr.fh.use_lf_frame && !r.colour && !r.patches;
-	r.xyb_refusal = r.patches || r.shape != DecodeRoute::Whole || !r.every_group || (up->is_modular ? !r.modular_xyb : up->ycbcr || up->has_trailers) ? (uint32_t) ERR_TODO : 0;
+	r.two_phase = r.shape == DecodeRoute::Whole && r.orientation == 1 && !fr.fh.use_lf_frame && !r.colour && !r.patches && !r.noise;
+	r.xyb_refusal = r.patches || r.noise || r.shape != DecodeRoute::Whole || !r.every_group || (up->is_modular ? !r.modular_xyb : up->ycbcr || up->has_trailers) ? (uint32_t) ERR_TODO : 0;
 	// in the entry points' order: an orientation over a partial range (no whole stored image to turn), the oriented image's rows, a YCbCr plan
 	// (served only while its switch stays on, and whole), the stored image's rows
 	if (r.orientation != 1 && !r.every_group) r.refusal = ERR_UOR;
 	else if (r.colour && !r.every_group) r.refusal = ERR_UCS;   // (a group range set before the mode: mode_refusal's rule)
 	// (a Modular frame's planes reach XYB through the Modular XYB switch alone)
-	else if (r.patches && (!r.every_group || (up->is_modular && !r.modular_xyb) || up->ycbcr)) r.refusal = ERR_TODO;
+	else if ((r.patches || r.noise) && (!r.every_group || (up->is_modular && !r.modular_xyb) || up->ycbcr)) r.refusal = ERR_TODO;
 	else if (r.orientation != 1 && (!have_out || stride_bytes < r.min_stride)) r.refusal = ERR_RNGE;
 	else if (up->ycbcr && (!j40hip_ycbcr_on(h) || r.shape != DecodeRoute::Whole || !r.every_group)) r.refusal = ERR_TODO;
 	else if (stride_bytes < r.min_stride) r.refusal = ERR_RNGE;

@@ -6,6 +6,7 @@
 #include "region_dev.h"
 #include "colour_dev.h"
 #include "patch_dev.h"
+#include "noise_dev.h"
 
 namespace j40hip {
 
@@ -51,6 +52,12 @@ void launch_colour_tail(const float *xyb, size_t pitch, const ColourTailParams &
 // patches (device/patch_kernels.hip, patch_dev.h): k_patch_blend over the three planes at `planes` (width * height floats each, one behind
 // the other), one workgroup per non-empty tile of `p` (device memory); nothing is launched for a list without tiles
 void launch_patch_blend(float *planes, int32_t width, int32_t height, const DevPatches &p, const PatchSlots &slots, hipStream_t stream);
+
+// photon noise (device/noise_kernels.hip, noise_dev.h): k_noise_fill makes the three raw planes at `raw` (noise_pitch(W) floats a row, one
+// plane behind the other) from the frame's four jump sets in device memory; k_noise_add convolves them and adds the result onto the
+// three planes at `planes` (`ppitch` floats a row, one behind the other), in place
+void launch_noise_fill(float *raw, const NoiseFillArgs &a, const uint64_t *sets_dev, hipStream_t stream);
+void launch_noise_add(float *planes, size_t ppitch, const float *raw, int32_t W, int32_t H, const NoiseParams &p, hipStream_t stream);
 
 // LfGroup tail on the device (device/lf_tail_kernels.hip)
 void upload_lf_tail_tables(const float *half_secants, const float *lf2llf, hipStream_t stream);

@@ -76,6 +76,89 @@ uint32_t j40hip_rt::apply_patches(j40hip_frame *h, float *planes, hipStream_t s)
 	return 0;
 }
 
+// ---- photon noise (a frame parsed with J40HIP_PARSE_NOISE; device/noise_dev.h, noise_kernels.hip) ----
+// The two kernels on `s`: the raw planes into `raw` (3 * noise_pitch(W) * H floats) from the jump sets at `sets` (device memory), their
+// convolution added onto `planes` (W floats a row). ms2 not null (J40HIP_NOISE_TIMING, the known-answer hook): the call waits for them
+// and reports each kernel's device time, between events of its own, destroyed on every way out.
+static uint32_t run_noise_kernels(float *planes, float *raw, const uint64_t *sets, const NoiseFillArgs &a, const NoiseParams &p, hipStream_t s, float *ms2) {
+	struct Trio { hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; ~Trio() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); } } trio;
+	bool timed = ms2 != nullptr;
+	for (int i = 0; timed && i < 3; ++i) timed = hipEventCreate(&trio.ev[i]) == hipSuccess;
+	if (timed) (void) hipEventRecord(trio.ev[0], s);
+	launch_noise_fill(raw, a, sets, s);
+	if (timed) (void) hipEventRecord(trio.ev[1], s);
+	launch_noise_add(planes, (size_t) a.W, raw, a.W, a.H, p, s);
+	if (timed) (void) hipEventRecord(trio.ev[2], s);
+	if (hipGetLastError() != hipSuccess) return ERR_GPU;
+	if (ms2) { ms2[0] = ms2[1] = 0.0f; }
+	if (timed) {
+		if (hipEventSynchronize(trio.ev[2]) != hipSuccess) return ERR_GPU;
+		(void) hipEventElapsedTime(&ms2[0], trio.ev[0], trio.ev[1]); (void) hipEventElapsedTime(&ms2[1], trio.ev[1], trio.ev[2]);
+	}
+	return 0;
+}
+
+// The frame's noise onto `planes` (width x height floats each, X, Y, B one behind the other), on `s`: called by render_planes behind the
+// patches and ahead of the tail. Nothing for a frame without noise; nothing is launched or allocated for a LUT of eight zeros. The raw
+// planes and the frame's four jump sets (built on the host by repeated squaring, once per upload) are kept with the frame like d_xyb.
+uint32_t j40hip_rt::apply_noise(j40hip_frame *h, float *planes, hipStream_t s) {
+	const Frame &fr = h->frame;
+	if (!fr.fh.has_noise || noise_lut_is_zero(fr.noise_lut)) return 0;
+	j40hip_device_state *st = h->dev;
+	const int32_t W = fr.fh.width, H = fr.fh.height, gdim = 1 << fr.fh.group_size_shift;
+	const NoiseFillArgs a = {W, H, gdim, (W + gdim - 1) / gdim, (H + gdim - 1) / gdim, h->noise_seeds[0], h->noise_seeds[1]};
+	NoiseParams p;
+	memcpy(p.lut, fr.noise_lut, sizeof p.lut);
+	p.ytox = fr.base_corr_x; p.ytob = fr.base_corr_b;   // (a Modular frame's LfGlobal has neither: the defaults 0 and 1)
+	if (!st->keep(st->noise.d_raw, 3 * noise_pitch(W) * (size_t) H)) return ERR_MEM;
+	if (!st->noise.d_sets) {
+		st->noise.host_sets.assign((size_t) 4 * NOISE_SET_WORDS, 0);   // (kept: the copy is asynchronous)
+		noise_frame_jumps(a, st->noise.host_sets.data());
+		bool ok = true;
+		st->noise.d_sets = st->upload(st->noise.host_sets.data(), st->noise.host_sets.size(), s, ok);
+		if (!ok) { st->noise.d_sets = nullptr; return ERR_MEM; }
+	}
+	static const bool timed = env_str("J40HIP_NOISE_TIMING") != nullptr;
+	if (uint32_t e = run_noise_kernels(planes, st->noise.d_raw, st->noise.d_sets, a, p, s, timed ? st->noise.ms : nullptr)) return e;
+	++h->noise_launches;
+	return 0;
+}
+
+extern "C" void j40hip_frame_noise_ms(const j40hip_frame *h, float *ms2) {
+	if (!ms2) return;
+	ms2[0] = h && h->dev ? h->dev->noise.ms[0] : 0.0f; ms2[1] = h && h->dev ? h->dev->noise.ms[1] : 0.0f;
+}
+
+extern "C" uint32_t j40hip_kat_device_noise(float *planes_dev, int32_t width, int32_t height, int32_t group_dim, const float *lut8, float ytox, float ytob,
+		uint32_t visible, uint32_t nonvisible, float *raw_out_dev, void *stream, float *ms2) {
+	return guarded([&]() -> uint32_t {
+		if (ms2) ms2[0] = ms2[1] = 0.0f;
+		if (!planes_dev || !lut8 || width <= 0 || height <= 0 || (int64_t) width * height > (1 << 28) || group_dim < 16 || group_dim > 1024 || group_dim % 16) return ERR_RNGE;
+		if (noise_lut_is_zero(lut8)) return 0;
+		const NoiseFillArgs a = {width, height, group_dim, (width + group_dim - 1) / group_dim, (height + group_dim - 1) / group_dim, visible, nonvisible};
+		NoiseParams p;
+		memcpy(p.lut, lut8, sizeof p.lut);
+		p.ytox = ytox; p.ytob = ytob;
+		int device = 0;
+		if (hipGetDevice(&device) != hipSuccess) return ERR_GPU;
+		hipStream_t s = (hipStream_t) stream;
+		j40hip_device_state tmp; tmp.device = device;
+		bool ok = true;
+		std::vector<uint64_t> sets((size_t) 4 * NOISE_SET_WORDS);
+		noise_frame_jumps(a, sets.data());
+		const size_t pitch = noise_pitch(width);
+		float *raw = tmp.scratch<float>(3 * pitch * (size_t) height, ok);
+		const uint64_t *d_sets = tmp.upload(sets.data(), sets.size(), s, ok);
+		uint32_t e = ok ? run_noise_kernels(planes_dev, raw, d_sets, a, p, s, ms2) : ERR_MEM;
+		// (the raw planes without their rows' padding)
+		if (!e && raw_out_dev && hipMemcpy2DAsync(raw_out_dev, sizeof(float) * (size_t) width, raw, sizeof(float) * pitch, sizeof(float) * (size_t) width, 3 * (size_t) height, hipMemcpyDeviceToDevice, s) != hipSuccess) e = ERR_GPU;
+		if (hipStreamSynchronize(s) != hipSuccess && !e) e = ERR_GPU;
+		for (auto &b : tmp.buffers) b.release();
+		tmp.buffers.clear();
+		return e;
+	});
+}
+
 // ---- the plane stage: from the frame's three full-size float planes (X, Y, B; a YCbCr frame's Cb, Y, Cr) to the caller's pixels ----
 // Who enters it is decided once per decode, before anything is launched (run_vardct, decode_modular): a decode whose restoration filters
 // run, the colour mode, a frame with patches, a 4:4:4 YCbCr plan, a caller that wants the planes themselves. Two steps: the planes are
@@ -101,7 +184,7 @@ static uint32_t ycbcr_tail(j40hip_frame *h, YcbcrTail &t, uint8_t *img, size_t s
 	return 0;
 }
 
-// Render the planes (`pitch` floats a row, one plane behind the other) into the caller's image: the frame's patches onto them, then exactly
+// Render the planes (`pitch` floats a row, one plane behind the other) into the caller's image: the frame's patches onto them, its noise, then exactly
 // one tail -- k_ycbcr_tail for a YCbCr plan, k_colour_tail for the colour mode (`colour`), else the sRGB tail -- and a Modular plan's A from
 // its plane, as the pack kernels render it (the tails write A opaque). What the tail read stays for j40hip_frame_read_xyb.
 static uint32_t render_planes(j40hip_frame *h, float *planes, size_t pitch, bool colour, uint8_t *img, size_t stride_bytes, hipStream_t s) {
@@ -109,6 +192,8 @@ static uint32_t render_planes(j40hip_frame *h, float *planes, size_t pitch, bool
 	const Frame &fr = h->frame;
 	const int32_t W = fr.fh.width, H = fr.fh.height;
 	if (uint32_t e = apply_patches(h, planes, s)) return e;
+	if (fr.fh.has_noise && pitch != (size_t) W) return ERR_TODO;   // (cannot happen: only a YCbCr plan pads its rows, and the route refuses it)
+	if (uint32_t e = apply_noise(h, planes, s)) return e;
 	h->last.tail_planes = planes;
 	if (st->ycbcr) {
 		YcbcrTail t;
@@ -145,7 +230,7 @@ static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *
 	h->last.modular_xyb_used = xyb;
 	if ((xyb_out && !xyb) || (xyb && shift > 0)) return ERR_TODO;
 	const bool colour = route.colour && xyb && !xyb_out;   // (whole frames: the route stages a region or a scale)
-	const bool patches = route.patches && !xyb_out;        // (likewise)
+	const bool patches = (route.patches || route.noise) && !xyb_out;        // (likewise; noise goes the patches' way)
 	if (patches && (!xyb || !st->patch.d_frame)) return ERR_TODO;
 	if ((colour || patches) && (region || shift > 0 || !route.every_group)) return ERR_TODO;
 	const bool planes = colour || patches || xyb_out;   // the decode goes through the plane stage
@@ -469,7 +554,7 @@ static uint32_t ycbcr_pixels(j40hip_frame *h, const int32_t *class_start, const 
 // One VarDCT decode as decode_impl (whole frames, group ranges), decode_region (covers), decode_scaled and decode_frame_xyb describe it to
 // run_vardct; as it stands, the whole frame from the frame's own lists, with nothing to write to yet
 struct VardctRun {
-	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged), colour(r.colour), patches(r.patches) {}
+	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged), colour(r.colour), patches(r.patches || r.noise) {}
 	int32_t first_group = 0, num_groups; // the groups of the entropy launch ...
 	const RegionCover *cover = nullptr;  // ... or (not null) a region's cover: through the fast kernel's order list (region.d_order), else a launch per row of its groups
 	const DevVarblock *list; const int32_t *class_start;   // what the pixel kernels take
@@ -478,7 +563,7 @@ struct VardctRun {
 	int restoration;                     // the route's: the mode the restoration filters run in (0: they do not; never where `whole` is false)
 	bool alpha_merged;                   // the route's
 	bool colour;                         // the route's: the pixels come from k_colour_tail (whole frames at full size: the route stages everything else)
-	bool patches;                        // the route's: the frame's patches go onto its XYB planes ahead of the tail (whole frames at full size, likewise)
+	bool patches;                        // the route's patches or noise: the frame's patches, its noise, go onto its XYB planes ahead of the tail (whole frames at full size, likewise)
 	const uint8_t *crop_from = nullptr; uint8_t *crop_to = nullptr; size_t crop_stride = 0; int32_t crop_w = 0, crop_h = 0;   // crop_to not null: these pixels of img are then moved there
 	int32_t shift = 0;                   // the scale shift the pixel kernels write at (decode_scaled's fused route: img is the small image)
 	float *xyb_out = nullptr;            // not null (an LF frame of a sequence, decode_frame_xyb): no pixels, img is null -- the three XYB planes, width * height

@@ -84,8 +84,10 @@ static uint32_t read_modular_xyb(j40hip_frame *h, float *out) {
 extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out) {
 	// (stage 3, a frame with patches: the planes the last decode's tail read, after k_patch_blend)
 	// (tail_planes names a buffer of this upload or nothing: a release of the device state forgets it)
-	if (stage == 3) return guarded([&]() -> uint32_t {
-		if (!h || !h->dev || !h->last.tail_planes || !h->frame.fh.has_patches || !out) return ERR_RNGE;
+	// (stage 4, a frame with noise: likewise, after k_noise_add. With both, what stood between the two kernels is gone: stage 3 is "rnge")
+	if (stage == 3 || stage == 4) return guarded([&]() -> uint32_t {
+		if (!h || !h->dev || !h->last.tail_planes || !out) return ERR_RNGE;
+		if (stage == 3 ? !h->frame.fh.has_patches || h->frame.fh.has_noise : !h->frame.fh.has_noise) return ERR_RNGE;
 		if (hipSetDevice(h->dev->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ERR_GPU;
 		return hipMemcpy(out, h->last.tail_planes, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
 	});

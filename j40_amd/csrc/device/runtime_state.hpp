@@ -198,6 +198,9 @@ struct j40hip_device_state {
 	// index was built) copied into the frame's scratch at the upload; d_frame: a Modular frame's colour
 	// constants as the sRGB tail takes them (a VarDCT frame's are its plan's)
 	struct Patches { DevPatches dev = {nullptr, nullptr, nullptr, nullptr, 0, 0}; std::vector<DevFrame> host_frame; const DevFrame *d_frame = nullptr; } patch;
+	// a frame with noise (runtime.hip: apply_noise): the three raw random planes (noise_pitch(width) floats a row) and the frame's four
+	// jump sets, made at the first decode that adds noise, kept with the frame; ms: the two kernels' device time (J40HIP_NOISE_TIMING)
+	struct Noise { float *d_raw = nullptr; const uint64_t *d_sets = nullptr; std::vector<uint64_t> host_sets; float ms[2] = {0, 0}; } noise;
 	// a YCbCr frame (j40hip_frame_set_ycbcr; runtime.hip: ycbcr_pixels). ycbcr: the plan was built for one (the switch was on at upload).
 	// d_ycc: the planes the pixel kernels leave for k_ycbcr_tail where the filters do not run, made at the first such decode, kept with
 	// the frame. ycc_read: what the last decode's tail read (j40hip_frame_read_ycbcr) -- those planes, or the restoration filters' result
@@ -292,6 +295,7 @@ bool modular_groups_independent(const j40hip_frame *h);                        /
 uint32_t clear_before_decode(j40hip_device_state *st, hipStream_t s);          // runtime.hip
 uint32_t decode_frame_xyb(j40hip_frame *h, float *planes, hipStream_t s);      // runtime.hip
 uint32_t apply_patches(j40hip_frame *h, float *planes, hipStream_t s);         // runtime.hip
+uint32_t apply_noise(j40hip_frame *h, float *planes, hipStream_t s);           // runtime.hip
 uint32_t restore_params(const FrameHeader &fh, int mode, RestoreParams *p);    // runtime.hip
 // A synchronous entry's wait behind a decode it has enqueued on `s`: the stream, then the frame's status. A section with more non-zero
 // coefficients than its event region holds ("evof") has the frame uploaded again with dense planes, `decode` enqueues it once more, and

@@ -452,12 +452,16 @@ static void init_global_modular(Frame *f) {  // j40.h:3619
 
 static void read_lf_global(BitReader &br, Frame *f) {
 	const FrameHeader &fh = f->fh;
-	J40HIP_SHOULD((!fh.has_patches || f->allow_patches) && !fh.has_splines && !fh.has_noise, "TODO");
-	if (fh.has_patches) {   // the dictionary, ahead of everything else (splines and noise would follow it)
+	J40HIP_SHOULD((!fh.has_patches || f->allow_patches) && !fh.has_splines && (!fh.has_noise || f->allow_noise), "TODO");
+	// (noise goes onto the XYB samples of a frame that is shown as it is: not an LF frame's, not a reference-only frame's)
+	// (... and not an LF-only parse: the LF image of such a frame is not its preview)
+	if (fh.has_noise) J40HIP_SHOULD(f->im.xyb_encoded && fh.type != 1 && fh.type != 2 && !f->lf_only, "TODO");
+	if (fh.has_patches) {   // the dictionary, ahead of everything else (splines would follow it, the noise parameters do)
 		J40HIP_SHOULD(f->im.xyb_encoded && fh.type != 2 && fh.type != 1, "TODO");
 		read_patch_dictionary(br, f->im, fh, &f->patches);
 		J40HIP_SHOULD(!f->patches.unserved, "TODO");
 	}
+	if (fh.has_noise) for (int i = 0; i < 8; ++i) f->noise_lut[i] = (float) br.u(10) / 1024.0f;   // NoiseParameters
 	if (!br.u(1)) for (int i = 0; i < 3; ++i) f->m_lf_scaled[i] = br.f16() / 128.0f;
 	if (!fh.is_modular) {
 		f->global_scale = br.u32(1, 11, 2049, 11, 4097, 12, 8193, 16);

@@ -21,6 +21,7 @@ inline bool alpha_env() { static const bool v = [] { const char *e = env_str("J4
 // J40HIP_ORIENT=1: single-frame decodes apply the image's orientation where j40hip_frame_set_orientation(f, 1) would be taken (include/j40hip.h); read once
 inline bool orient_env() { static const bool v = [] { const char *e = env_str("J40HIP_ORIENT"); return e && atoi(e) > 0; }(); return v; }
 // J40HIP_YCBCR=1: YCbCr VarDCT frames (recompressed JPEGs) are served where j40hip_frame_set_ycbcr(f, 1) would be taken (include/j40hip.h); read once
+inline bool noise_env() { return env_on("J40HIP_NOISE", false); }   // (read at every parse)
 inline bool wide_env() { static const bool v = [] { const char *e = env_str("J40HIP_WIDE"); return e && atoi(e) > 0; }(); return v; }
 inline bool modular_xyb_env() { static const bool v = [] { const char *e = env_str("J40HIP_MODULAR_XYB"); return e && atoi(e) > 0; }(); return v; }
 // J40HIP_RESTORATION: 0 off (the default), 1 the filters a frame signals, 2 (`j40`) as j40's routines stand; read once
@@ -257,6 +258,11 @@ struct Frame {
 	bool allow_patches = false;
 	bool allow_modular_ref = false;   // ... and Modular reference-only frames among them (the sequence has the Modular XYB switch too)
 	PatchDictionary patches;
+	// Photon noise is asked for (J40HIP_PARSE_NOISE, or J40HIP_NOISE=1): a frame with has_noise is parsed -- its eight NoiseParameters
+	// into noise_lut, each u(10) / 1024 -- instead of refused with "TODO"; the frame must be a regular or skip-progressive one (type 0
+	// or 3) of an image with xyb_encoded = 1. Set before parse_frame. (device/noise_dev.h has the rule.)
+	bool allow_noise = false;
+	float noise_lut[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	bool wide() const { return !im.modular_16bit_buffers; }
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
@@ -265,7 +271,7 @@ struct Frame {
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
 		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr; g.allow_wide = allow_wide; g.allow_lf_frame = allow_lf_frame; g.allow_modular_lf = allow_modular_lf;
-		g.allow_patches = allow_patches; g.allow_modular_ref = allow_modular_ref;
+		g.allow_patches = allow_patches; g.allow_modular_ref = allow_modular_ref; g.allow_noise = allow_noise;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section

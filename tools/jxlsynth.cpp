@@ -111,6 +111,24 @@ static bool cut_patch_dictionary(BitWriter &bw) {
 	return true;
 }
 
+// noise=v0,...,v7: the frame being written has the noise flag (FrameHeader.flags bit 0) and its eight NoiseParameters, u(10) each, in
+// LfGlobal behind the patch dictionary (splines, which would stand between them, are never written). Both LfGlobal writers.
+//   twin (noisetwin=1): the frame without the flag and without the parameters, every other byte alike
+struct NoiseRole { int v[8] = {0, 0, 0, 0, 0, 0, 0, 0}; bool twin = false; };
+static NoiseRole *g_noise = nullptr;
+static bool noise_flag() { return g_noise && !g_noise->twin; }
+static void write_noise_parameters(BitWriter &bw) {
+	if (!noise_flag()) return;
+	for (int i = 0; i < 8; ++i) bw.put((uint64_t) g_noise->v[i], 10);
+}
+// (the Modular writer has a noise=N of its own, the amplitude of its samples' noise: one integer. Eight of them are these parameters.)
+static bool photon_noise_given(const Options &opt) { return opt.kv.count("noise") && opt.gets("noise", "").find(',') != std::string::npos; }
+static void parse_noise_role(const std::string &s, NoiseRole *r) {
+	int *v = r->v;
+	if (sscanf(s.c_str(), "%d,%d,%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7) != 8) die("noise=v0,...,v7 (eight integers 0..1023)");
+	for (int i = 0; i < 8; ++i) if (v[i] < 0 || v[i] > 1023) die("noise=: a value outside 0..1023");
+}
+
 // LF frames (lflevels=1|2; run_lf_sequence): what the VarDCT writer is told about the frame it writes, and what it hands back for the
 // next one. The planes of integers are frame-wide, ceil(W / 8) cells a row, in streamed order Y, X, B.
 struct LfRole {
@@ -585,7 +603,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	const int jpeg_upsampling = subsampling == "420" ? 4 : subsampling == "422" ? 8 : subsampling == "440" ? 12 : 0;
 	const int dct8only = jpeg ? 1 : opt.geti("dct8only", subsampled ? 1 : 0), fixed_hfmul = jpeg ? 1 : opt.geti("hfmul", 0), nocfl = jpeg ? 1 : opt.geti("nocfl", 0), flatchroma = opt.geti("flatchroma", 0);
 	if (fixed_hfmul < 0 || fixed_hfmul > 256) die("vardct: hfmul=1..256");
-	const int nonzero_header = opt.geti("fullheader", (num_passes > 1 || ycbcr) ? 1 : 0);
+	const int nonzero_header = opt.geti("fullheader", (num_passes > 1 || ycbcr || g_noise) ? 1 : 0);
 	const int x_qm = opt.geti("xqm", 3), b_qm = opt.geti("bqm", 2);
 	const int skip_smooth = jpeg ? 1 : opt.geti("nosmooth", subsampled ? 1 : 0);
 	const int small_clusters = opt.geti("simpleclusters", 0); // <= 8 clusters: simple cluster-map form
@@ -1344,6 +1362,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		write_patch_dictionary(section, num_ec);                 // (patches=: the dictionary comes first)
 		BitWriter dropped;                                       // (patchcut=1: the rest is written all the same, the code specs' tables are made here)
 		BitWriter &bw = cut_patch_dictionary(section) ? dropped : section;
+		write_noise_parameters(bw);                              // (noise=: behind the dictionary)
 		bw.put(1, 1);                                            // LF channel dequantisation: default
 		bw.u32(global_scale, 1, 11, 2049, 11, 4097, 12, 8193, 16);
 		bw.u32(quant_lf, 16, 0, 1, 5, 1, 8, 1, 16);
@@ -1524,7 +1543,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		const int seq_type = g_seq ? g_seq->type : 0;
 		cs.put(lf_frame ? 1 : (uint64_t) seq_type, 2);   // regular frame (an LF frame: type 1; types=: a reference-only frame, type 2)
 		cs.put(0, 1);                       // VarDCT
-		cs.u64((skip_smooth ? 128 : 0) | (use_lf_frame ? 32 : 0) | (patch_flag() ? 2 : 0));      // flags
+		cs.u64((skip_smooth ? 128 : 0) | (use_lf_frame ? 32 : 0) | (patch_flag() ? 2 : 0) | (noise_flag() ? 1 : 0));      // flags
 		if (noxyb) cs.put(ycbcr ? 1 : 0, 1);   // do_ycbcr (read only without xyb_encoded)
 		// (jpegup=N: the header says N whatever the stream holds -- a layout the decoder has to refuse before it reads anything of it)
 		if (ycbcr) cs.put((uint64_t) opt.geti("jpegup", jpeg_upsampling), 6);   // jpeg_upsampling (read with do_ycbcr)
@@ -2213,6 +2232,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	{
 		BitWriter bw;
 		write_patch_dictionary(bw, extra + (alpha ? 1 : 0));   // (patches=: the dictionary comes first)
+		write_noise_parameters(bw);                            // (noise=: behind it)
 		if (!custom_m_lf) bw.put(1, 1);   // LF channel dequantisation: default
 		else { bw.put(0, 1); for (int c = 0; c < 3; ++c) bw.f16((float) (m_lf[c] * 128.0)); }   // (read back divided by 128, j40.h:6268)
 		bw.put(1, 1);                 // global tree present
@@ -2327,7 +2347,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	const int seq_type = g_seq ? g_seq->type : 0;
 	cs.put(g_mod_lf ? 1 : (uint64_t) seq_type, 2);   // regular frame (an LF frame: type 1; types=: a reference-only frame, type 2)
 	cs.put(1, 1);                       // modular
-	cs.u64(patch_flag() ? 2 : 0);       // flags
+	cs.u64((patch_flag() ? 2 : 0) | (noise_flag() ? 1 : 0));       // flags
 	if (!flag_xyb) cs.put(flag_ycbcr ? 1 : 0, 1);   // do_ycbcr
 	if (!flag_xyb && flag_ycbcr) cs.put(0, 6);      // jpeg_upsampling: none
 	cs.put(0, 2);                       // log_upsampling
@@ -2420,6 +2440,8 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 //                      which blend mode. Sets the frame's has_patches flag; nothing is checked (PatchRole). patchec=M: the extra channels'
 //                      entries have mode M; patchcut=1: LfGlobal ends inside the dictionary; patchtwin=1: the flag and the dictionary left
 //                      out, every other byte alike. stats=1 lists the placements written
+//   noise=             per frame (entries separated by ';') the eight NoiseParameters v0,...,v7 (0..1023): sets the frame's noise flag; an
+//                      empty entry: a frame without noise. noisetwin=1: the flag and the parameters left out, every other byte alike
 // The last frame is is_last. stats=1 prints frames, shown, saved_slots and every frame's offsets instead of the mode's own statistics.
 static std::vector<std::string> split_list(const std::string &v, char sep) {
 	std::vector<std::string> out;
@@ -2436,7 +2458,8 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 	const std::vector<std::string> durs = split_list(opt_in.gets("durations", ""), ','), crops = split_list(opt_in.gets("crops", ""), ';'),
 		srcs = split_list(opt_in.gets("srcs", ""), ','), saves = split_list(opt_in.gets("saves", ""), ','), blends = split_list(opt_in.gets("blends", ""), ','),
 		ecblends = split_list(opt_in.gets("ecblends", ""), ','), ecsrcs = split_list(opt_in.gets("ecsrcs", ""), ','),
-		types = split_list(opt_in.gets("types", ""), ','), patches = split_list(opt_in.gets("patches", ""), ';');
+		types = split_list(opt_in.gets("types", ""), ','), patches = split_list(opt_in.gets("patches", ""), ';'),
+		noises = split_list(photon_noise_given(opt_in) ? opt_in.gets("noise", "") : std::string(), ';');
 	if (!durs.empty() && !anim) die("durations= wants anim=1 (frames of a still have no duration)");
 	// modes=v,m,...: per-frame writers, v the VarDCT one and m the Modular one (an empty entry: the command's mode). Every frame gets every
 	// option; the first frame writes the image header, so the options must describe one image to both writers (a Modular frame under a
@@ -2446,7 +2469,8 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 	for (const std::string &m : modes) { if (!m.empty() && m != "v" && m != "m") die("modes=v|m,..."); any_vardct = any_vardct || m == "v"; }
 	if (!modes.empty() && any_vardct && !opt_in.geti("xyb", 0)) die("modes=: a Modular frame beside VarDCT frames is a frame of an XYB image: xyb=1");
 	Options opt = opt_in;
-	for (const char *k : {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "container", "stats", "modes", "types", "patches", "patchtwin", "patchec", "patchcut", "sbct"}) opt.kv.erase(k);
+	for (const char *k : {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "container", "stats", "modes", "types", "patches", "patchtwin", "patchec", "patchcut", "sbct", "noisetwin"}) opt.kv.erase(k);
+	if (photon_noise_given(opt_in)) opt.kv.erase("noise");
 	if (any_vardct && !opt.kv.count("fullheader")) opt.kv["fullheader"] = "1";
 	auto at = [](const std::vector<std::string> &v, int k, int def) { return k < (int) v.size() && !v[(size_t) k].empty() ? atoi(v[(size_t) k].c_str()) : def; };
 	std::vector<uint8_t> cs;
@@ -2472,6 +2496,10 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 			}
 			if (only < 0 || k == only) { char tmp[64]; snprintf(tmp, sizeof tmp, "%s{\"frame\": %d, \"placements\": [", patch_rows.empty() ? "" : ", ", k); patch_rows += tmp + placed + "]}"; }
 		}
+		NoiseRole noise;
+		noise.twin = opt_in.geti("noisetwin", 0) != 0;
+		const bool noisy = k < (int) noises.size() && !noises[(size_t) k].empty();
+		if (noisy) parse_noise_role(noises[(size_t) k], &noise);
 		SeqFrame q;
 		q.canvas_w = W; q.canvas_h = H; q.anim = anim; q.cs = &cs;
 		int fw = W, fh = H;
@@ -2492,10 +2520,10 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 		if (q.type != 2 && !q.is_last && (q.duration == 0 || q.save != 0)) saved_slots |= 1u << q.save;
 		if (only >= 0 && k != only) continue;
 		q.first = cs.empty();
-		g_seq = &q; g_patch = role.refs.empty() ? nullptr : &role;
+		g_seq = &q; g_patch = role.refs.empty() ? nullptr : &role; g_noise = noisy ? &noise : nullptr;
 		const bool frame_vardct = k < (int) modes.size() && !modes[(size_t) k].empty() ? modes[(size_t) k] == "v" : vardct;
 		const int e = frame_vardct ? run_vardct(fw, fh, seed + (uint64_t) k, out, opt) : run_modular(fw, fh, seed + (uint64_t) k, out, opt);
-		g_seq = nullptr; g_patch = nullptr;
+		g_seq = nullptr; g_patch = nullptr; g_noise = nullptr;
 		if (e) return e;
 		// (the first frame's bytes start with the signature and the image header: its frame header is found by a reader, not here)
 		char tmp[160]; snprintf(tmp, sizeof tmp, "%s{\"frame\": %d, \"first_section\": %zu, \"end\": %zu}", rows.empty() ? "" : ", ", k, q.first_section, cs.size());
@@ -2552,6 +2580,7 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 //                    that renders such a frame to XYB floats as (float) c0 * m[1], (float) c1 * m[0], (float) (c2 + c0) * m[2] arrives at the
 //                    flat VarDCT LF frame's samples float for float where that frame's LF step is m itself: global_scale * quant_lf = 65536;
 //                    and nocfl=1, so that no B sample carries a Y term. Refused elsewhere. (lftwin=1: the twin is the same stream either way.)
+// noise=v0,...,v7: the main frame's noise parameters (noisetwin=1: left out again); noiself=1: the LF frames carry them too.
 // stats=1 prints the number of coded frames and how many values the main frame's LF index takes.
 static int run_lf_sequence(int W, int H, uint64_t seed, const char *out, const Options &opt_in) {
 	const int levels = opt_in.geti("lflevels", 1), twin = opt_in.geti("lftwin", 0), only = opt_in.geti("only", -1);
@@ -2572,7 +2601,13 @@ static int run_lf_sequence(int W, int H, uint64_t seed, const char *out, const O
 		if (opt_in.geti("alpha", 0)) die("lfmodular=1: no extra channels (an LF frame of such an image is refused)");
 	}
 	Options main_opt = opt_in;
-	for (const char *k : {"lflevels", "lfkind", "lftwin", "only", "stats", "lfgab", "lfepf", "lfcrop", "lfhfmul", "lfmodular"}) main_opt.kv.erase(k);
+	for (const char *k : {"lflevels", "lfkind", "lftwin", "only", "stats", "lfgab", "lfepf", "lfcrop", "lfhfmul", "lfmodular", "noisetwin", "noiself"}) main_opt.kv.erase(k);
+	if (photon_noise_given(opt_in)) main_opt.kv.erase("noise");
+	// noise= (one entry): the main frame's; noiself=1: the LF frames get the flag and the parameters too (a stream a decoder has to refuse)
+	NoiseRole noise;
+	noise.twin = opt_in.geti("noisetwin", 0) != 0;
+	const bool noisy = photon_noise_given(opt_in), noise_lf = opt_in.geti("noiself", 0) != 0;
+	if (noisy) parse_noise_role(opt_in.gets("noise", ""), &noise);
 	int crop_w = 0, crop_h = 0;
 	if (opt_in.kv.count("lfcrop") && (sscanf(opt_in.gets("lfcrop", "").c_str(), "%d,%d", &crop_w, &crop_h) != 2 || crop_w < 1 || crop_h < 1 || crop_w > W || crop_h > H || picture || twin || only >= 0)) die("lfcrop=w,h within the image, with lfkind=flat and neither lftwin nor only");
 	main_opt.kv["fullheader"] = "1";
@@ -2601,9 +2636,9 @@ static int run_lf_sequence(int W, int H, uint64_t seed, const char *out, const O
 		SeqFrame q;
 		q.canvas_w = W; q.canvas_h = H; q.cs = into; q.first = into && into->empty(); q.is_last = l == 0;
 		q.have_crop = l == 0 && crop_w > 0;
-		g_seq = into ? &q : nullptr; g_lf = &role;
+		g_seq = into ? &q : nullptr; g_lf = &role; g_noise = noisy && (l == 0 || noise_lf) ? &noise : nullptr;
 		const int e = run_vardct(q.have_crop ? crop_w : fw[l], q.have_crop ? crop_h : fh[l], seed + (uint64_t) l, out, o);
-		g_seq = nullptr; g_lf = nullptr;
+		g_seq = nullptr; g_lf = nullptr; g_noise = nullptr;
 		if (e) die("lflevels: a frame could not be written");
 	};
 	LfRole roles[3];
@@ -2730,6 +2765,12 @@ int main(int argc, char **argv) {
 	static const char *const SEQ_KEYS[] ={"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "modes", "types", "patches"};
 	bool sequence = false;
 	for (const char *k : SEQ_KEYS) sequence = sequence || opt.kv.count(k);
-	if (!sequence) return vardct ? run_vardct(W, H, seed, argv[5], opt) : run_modular(W, H, seed, argv[5], opt);
+	if (!sequence) {   // (noise= on a single frame: the one entry)
+		NoiseRole noise;
+		noise.twin = opt.geti("noisetwin", 0) != 0;
+		if (photon_noise_given(opt)) { parse_noise_role(opt.gets("noise", ""), &noise); g_noise = &noise; opt.kv.erase("noise"); }
+		opt.kv.erase("noisetwin");
+		return vardct ? run_vardct(W, H, seed, argv[5], opt) : run_modular(W, H, seed, argv[5], opt);
+	}
 	return run_sequence(vardct, W, H, seed, argv[5], opt);
 }
