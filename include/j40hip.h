@@ -83,6 +83,26 @@ J40HIP_API void j40hip_frame_free(j40hip_frame *f);
  * sequence get the seed counters of their place in it (visible: the shown frames before it, nonvisible: the frames since the last
  * shown one); a stand-alone handle has both 0. */
 #define J40HIP_PARSE_NOISE 256u
+/* flags & J40HIP_PARSE_UPSAMPLING: upsampling is asked for. PARITY UNPINNED: the reference refuses a frame header with upsampling or an
+ * ec_upsampling other than 1 (j40.h:3297-3306, 5244-5249) and custom upsampling weights in the image header (j40.h:3638) with "TODO", and so
+ * does every parse without this flag. With it the custom weights are read and kept, and a frame coded at 1:2, 1:4 or 1:8
+ * (cjxl --resampling=2|4|8) is parsed: its header's width and height are the SHOWN size, everything up to and including the restoration
+ * filters works on the CODED size ceil(shown / K), and every decode stretches the filtered XYB planes K times (k_upsample: a 5 x 5 stencil,
+ * K x K outputs a coded sample, each clamped to its neighbourhood's range; j40_amd/csrc/device/upsample_dev.h states the rule) ahead of the
+ * colour tail and writes the shown size. j40hip_frame_info, the region, the scale and the orientation speak of the shown size;
+ * j40hip_frame_coded_size of the coded one. The weights: the stream's custom table for the frame's K, else the defaults the application
+ * supplied (j40hip_set_upsampling_defaults -- nothing here holds the standard's default tables); neither: "updf" at parse. "usmp": an
+ * extra channel coded finer than the frame ((ec_upsampling << dim_shift) < upsampling). Served: VarDCT frames of XYB images and, through
+ * the Modular XYB switch, Modular ones (an image with xyb_encoded = 0 that is no YCbCr frame: "TODO" at parse); both output formats, the orientation, the restoration filters, the colour mode; a region is cut
+ * from and a scale averaged over the shown-size picture. An extra channel of a VarDCT frame coarser than the frame (ec_upsampling up to four
+ * times upsampling) is decoded at its own size, ceil(shown / ec_upsampling), and dropped. "TODO" even with the flag: an extra channel
+ * from eight times coarser than the frame on, or coarser at all in a Modular frame; frames of types 1 and 2, an LF-only parse, every frame of a sequence (at parse); a partial group range, a batch, a
+ * pipeline, the many-frames LF preview, kept alpha (j40hip_frame_set_alpha), a Modular frame with an alpha channel or without the Modular
+ * XYB switch, a YCbCr plan, a frame that also has patches or noise (at the setter or the decode, before anything is launched).
+ * J40HIP_UPSAMPLING=1 in the environment does the same for every parse, the ten-function API's too. j40hip_sequence_open takes
+ * J40HIP_SEQ_UPSAMPLING (the same bit): the image header's custom weights are read; its frames with upsampling > 1 stay "TODO". */
+#define J40HIP_PARSE_UPSAMPLING 512u
+#define J40HIP_SEQ_UPSAMPLING 512u
 /* the shortest prefix of the codestream holding headers, TOC, LfGlobal and every LfGroup section (the largest end among those
  * sections, so a permuted TOC is covered); a bare codestream's file prefix. Single-section frames: the whole codestream. */
 J40HIP_API int64_t j40hip_frame_lf_end(const j40hip_frame *f);
@@ -595,6 +615,8 @@ J40HIP_API uint32_t j40hip_frame_read_xyb(j40hip_frame *f, int stage, float *out
 /* Stage 4, after any decode of a frame with noise (J40HIP_PARSE_NOISE): the planes after k_noise_add, as the tail read them. For a
  * frame with both patches and noise stage 3 answers "rnge": the patched planes are noised in place, what stood between the two is gone.
  * A frame whose LUT is all zeros answers stage 4 with the planes the tail read. */
+/* Stage 5, after any decode of an upsampled frame (J40HIP_PARSE_UPSAMPLING): the planes k_upsample wrote, [3][shown height][shown width],
+ * as the tail read them. Stages 0 and 1 keep the coded size. */
 J40HIP_API float j40hip_frame_restoration_ms(const j40hip_frame *f);   /* device time of the filter kernels in the last decode (J40HIP_RESTORATION_TIMING=1) */
 /* known-answer hook: the filter kernels on caller-supplied planes (xyb: [3][h][w] floats, host, in place), a w8*h8 sharpness map and the
  * HfMul reciprocal of the varblock covering each cell; mode 1 or 2; sigma_out optional. 0 or "gab0" / "epf0" / "shrp" / "!gpu". */
@@ -728,6 +750,27 @@ J40HIP_API void j40hip_frame_noise_ms(const j40hip_frame *f, float *ms2);
  * Enqueued on `stream` and waited for. "rnge": a size the kernels do not take. */
 J40HIP_API uint32_t j40hip_kat_device_noise(float *planes_dev, int32_t width, int32_t height, int32_t group_dim, const float *lut8, float ytox, float ytob,
 		uint32_t visible, uint32_t nonvisible, float *raw_out_dev, void *stream, float *ms2);
+/* ---- upsampling (J40HIP_PARSE_UPSAMPLING above) ----
+ * j40hip_set_upsampling_defaults: the standard's default weights for k = 2, 4 or 8 (n = 15, 55, 210: the upper triangle of the symmetric
+ * 5k/2 x 5k/2 matrix, row by row), supplied by the application once; process-wide, behind a mutex; frames parsed afterwards without a
+ * custom table for their K copy them; n = 0 takes the table back. "rnge": another k or n.
+ * j40hip_frame_upsampling: *k = the frame's upsampling (1, 2, 4, 8); weights (optional, room for 210 floats): the table the frame copied at
+ * parse, *n (optional) of them (0 for k = 1). j40hip_frame_coded_size: the size the frame is coded at (j40hip_frame_info has the shown one).
+ * j40hip_frame_upsample_ms: with J40HIP_UPSAMPLE_TIMING=1 in the environment the device time of k_upsample in the last decode, which then
+ * waits for it; else 0. */
+J40HIP_API uint32_t j40hip_set_upsampling_defaults(int k, const float *w, int n);
+J40HIP_API uint32_t j40hip_frame_upsampling(const j40hip_frame *f, int32_t *k, float *weights, int32_t *n);
+J40HIP_API void j40hip_frame_coded_size(const j40hip_frame *f, int32_t *width, int32_t *height);
+J40HIP_API float j40hip_frame_upsample_ms(const j40hip_frame *f);
+/* known-answer / measuring hooks. j40hip_kat_upsampling_kernel: the expanded table [k][k][25] of the 15 / 55 / 210 weights --
+ * out[(oy * k + ox) * 25 + 5 * sy + sx]: what output phase (ox, oy) gives the coded sample at (sx - 2, sy - 2).
+ * j40hip_kat_device_upsample: k_upsample alone. planes_dev: three planes of width x height floats, one behind the other; out_dev: three of
+ * out_w x out_h (out_w <= k * width, out_h <= k * height: the cut). ms (optional): the kernel's device time. Enqueued on `stream` and waited
+ * for. j40hip_kat_host_upsample: the same functions compiled for the CPU over host memory; tiled = 0 the rule sample by sample, 1 the
+ * kernel's tile functions thread by thread. "rnge": a factor or a size they do not take. */
+J40HIP_API uint32_t j40hip_kat_upsampling_kernel(int32_t k, const float *weights, float *out);
+J40HIP_API uint32_t j40hip_kat_device_upsample(const float *planes_dev, int32_t width, int32_t height, int32_t k, const float *weights, int32_t out_w, int32_t out_h, float *out_dev, void *stream, float *ms);
+J40HIP_API uint32_t j40hip_kat_host_upsample(const float *planes, int32_t width, int32_t height, int32_t k, const float *weights, int32_t out_w, int32_t out_h, float *out, int tiled);
 /* ---- patches: reference-only frames and the patch dictionary. PARITY UNPINNED: the reference holds no code for either (j40.h:6262 is a
  *      TODO); off by default. With J40HIP_SEQ_PATCHES (or J40HIP_PATCHES=1 in the environment) a sequence takes
  *      - a reference-only frame (type 2) with save_before_colour_transform = 1 of an image with xyb_encoded = 1: a frame of its own width

@@ -25,6 +25,7 @@ J40_U16X4 = 0x0F35
 PARSE_LF_ONLY = 2   # J40HIP_PARSE_LF_ONLY (include/j40hip.h): the LF preview's parse
 PARSE_YCBCR = 4     # J40HIP_PARSE_YCBCR: YCbCr frames are asked for (a subsampled one is parsed instead of refused)
 PARSE_NOISE = 256   # J40HIP_PARSE_NOISE: photon noise is asked for (a frame with has_noise is parsed and its noise added instead of "TODO"); j40hip_sequence_open takes it too
+PARSE_UPSAMPLING = 512   # J40HIP_PARSE_UPSAMPLING: upsampling is asked for (custom weights and a frame coded at 1:2, 1:4 or 1:8 are parsed and served instead of "TODO"); J40HIP_SEQ_UPSAMPLING is the same bit
 PARSE_WIDE = 8      # J40HIP_PARSE_WIDE: wide Modular frames are asked for (an image with 32-bit Modular buffers is parsed instead of "fm32")
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -129,6 +130,11 @@ def lib():
         "j40hip_kat_device_compose": (u32, [vp, sz, vp, sz, vp, sz, i32, i32, i32, i32, i32, i32, u32, u32, i32, vp]),
         "j40hip_sequence_frame_blend": (None, [vp, i64, vp]),
         "j40hip_sequence_frame_lf": (None, [vp, i64, vp]), "j40hip_sequence_read_lf_slot": (u32, [vp, i32, i32, vp]),
+        "j40hip_set_upsampling_defaults": (u32, [C.c_int, vp, C.c_int]), "j40hip_frame_upsampling": (u32, [vp, vp, vp, vp]),
+        "j40hip_frame_coded_size": (None, [vp, vp, vp]), "j40hip_frame_upsample_ms": (C.c_float, [vp]),
+        "j40hip_kat_upsampling_kernel": (u32, [i32, vp, vp]),
+        "j40hip_kat_device_upsample": (u32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
+        "j40hip_kat_host_upsample": (u32, [vp, i32, i32, i32, vp, i32, i32, vp, C.c_int]),
         "j40hip_frame_noise": (C.c_int, [vp, vp, vp]), "j40hip_frame_noise_launches": (i64, [vp]), "j40hip_frame_noise_ms": (None, [vp, vp]),
         "j40hip_kat_device_noise": (u32, [vp, i32, i32, i32, vp, C.c_float, C.c_float, u32, u32, vp, vp, vp]),
         "j40hip_sequence_frame_patches": (None, [vp, i64, vp]), "j40hip_sequence_frame_patch": (u32, [vp, i64, i64, vp]),
@@ -248,7 +254,7 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False, blend=False, noise=False):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False, blend=False, noise=False, upsampling=False):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
     scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
     (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
@@ -279,7 +285,10 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     and with fmt and scale (the shown frame's own handle decoded once more at the scale, as with lf_frames=True: a full-canvas frame with
     patches takes one); "TODO" with orient= unless lf_frames= is given too.
     noise=True: a frame with photon noise (has_noise) is served for this call whatever J40HIP_NOISE says (PARSE_NOISE; PARITY UNPINNED),
-    through the thin C-ABI on device 0; it combines with every switch above (a sequence is opened with it)."""
+    through the thin C-ABI on device 0; it combines with every switch above (a sequence is opened with it).
+    upsampling=True: a frame coded at 1:2, 1:4 or 1:8 (and custom upsampling weights) is served for this call whatever J40HIP_UPSAMPLING
+    says (PARSE_UPSAMPLING; PARITY UNPINNED), through the thin C-ABI on device 0: the picture has the shown size. It combines with fmt,
+    scale, orient, modular_xyb (which a Modular frame needs) and colour; "TODO" with alpha=True and for every frame of a sequence."""
     if lf_frames or patches:
         if alpha or ycbcr or wide or (patches and not lf_frames and orient):
             return "TODO", None
@@ -308,9 +317,9 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
                 return e.code, None
             finally:
                 seq.close()
-    if alpha or scale or ycbcr or orient or wide or modular_xyb or colour or noise:
+    if alpha or scale or ycbcr or orient or wide or modular_xyb or colour or noise or upsampling:
         try:
-            fr = Frame(data, ycbcr=bool(ycbcr), wide=bool(wide), noise=bool(noise))
+            fr = Frame(data, ycbcr=bool(ycbcr), wide=bool(wide), noise=bool(noise), upsampling=bool(upsampling))
         except J40Error as e:
             return e.code, None
         try:
@@ -347,15 +356,16 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     return err, out
 
 
-def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False, wide=False, colour=False, noise=False):
+def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False, wide=False, colour=False, noise=False, upsampling=False):
     """rectangle (x, y, w, h) of the image through the thin C-ABI: returns (err4, ndarray [h, w, 4] or None), uint8 or uint16 with
     fmt=J40_U16X4 -- the crop of what decode() returns, decoded from the pass groups that cover it (Frame.set_region). The verdict is
     the one over the sections that were decoded, then the public API's look behind the frame.
     orient=True: (x, y, w, h) is a rectangle of the DISPLAYED picture -- the frame in the orientation its stream carries; it is mapped
     to stored coordinates (Frame.orient_rect) and the result is the crop of the oriented whole picture, [h, w, 4].
-    wide=True, colour=True, noise=True: as decode()'s (a frame with noise: the crop of the full-size picture)."""
+    wide=True, colour=True, noise=True: as decode()'s (a frame with noise: the crop of the full-size picture).
+    upsampling=True: as decode()'s; the rectangle lies in the shown-size picture and is cut from it."""
     try:
-        fr = Frame(data, wide=bool(wide), noise=bool(noise))
+        fr = Frame(data, wide=bool(wide), noise=bool(noise), upsampling=bool(upsampling))
     except J40Error as e:
         return e.code, None
     try:
@@ -600,6 +610,70 @@ def kat_device_patches(planes, slots, placements, device=0):
     return "", host[guard:guard + planes.size].reshape(3, h, w).copy(), int(tiles.value)
 
 
+def set_upsampling_defaults(k, weights):
+    """the standard's default upsampling weights for k = 2, 4 or 8 (15, 55 or 210 numbers: the upper triangle of the symmetric matrix,
+    row by row), supplied once by the application -- nothing in this package holds them; process-wide. Frames parsed afterwards that
+    carry no custom table for their K copy them; until then, and after weights=None, such frames answer "updf". Returns the err4 ("rnge": another k or count)"""
+    if weights is None:      # (takes the table back: frames parsed afterwards answer "updf" again)
+        return err4(lib().j40hip_set_upsampling_defaults(int(k), None, 0))
+    w = np.ascontiguousarray(weights, np.float32).ravel()
+    if w.size == 0:
+        return "rnge"
+    return err4(lib().j40hip_set_upsampling_defaults(int(k), w.ctypes.data, int(w.size)))
+
+
+def kat_upsampling_kernel(k, weights):
+    """j40hip_kat_upsampling_kernel: the expanded table [k, k, 5, 5] of the packed weights -- [oy, ox, sy, sx]: what output phase (ox, oy)
+    gives the coded sample at (sx - 2, sy - 2); (err4, ndarray or None)"""
+    w = np.ascontiguousarray(weights, np.float32).ravel()
+    if k not in (2, 4, 8) or w.size != {2: 15, 4: 55, 8: 210}[k]:
+        return "rnge", None
+    out = np.zeros((k, k, 5, 5), np.float32)
+    code = err4(lib().j40hip_kat_upsampling_kernel(int(k), w.ctypes.data, out.ctypes.data))
+    return code, (None if code else out)
+
+
+def kat_host_upsample(planes, k, weights, out_w=None, out_h=None, tiled=False):
+    """k_upsample's host twin (j40hip_kat_host_upsample): planes [3, h, w] float32 -> (err4, [3, out_h, out_w] or None); tiled: the
+    kernel's tile functions thread by thread instead of the rule sample by sample"""
+    planes = np.ascontiguousarray(planes, np.float32)
+    _, h, w = planes.shape
+    out_w = k * w if out_w is None else out_w; out_h = k * h if out_h is None else out_h
+    wt = np.ascontiguousarray(weights, np.float32).ravel()
+    if k not in (2, 4, 8) or wt.size != {2: 15, 4: 55, 8: 210}[k] or out_w <= 0 or out_h <= 0:
+        return "rnge", None
+    out = np.zeros((3, out_h, out_w), np.float32)
+    code = err4(lib().j40hip_kat_host_upsample(planes.ctypes.data, w, h, int(k), wt.ctypes.data, int(out_w), int(out_h), out.ctypes.data, 1 if tiled else 0))
+    return code, (None if code else out)
+
+
+def kat_device_upsample(planes, k, weights, out_w=None, out_h=None, device=0, want_ms=False):
+    """k_upsample alone (j40hip_kat_device_upsample): planes [3, h, w] float32 -> (err4, [3, out_h, out_w] or None); with want_ms a third
+    entry, the kernel's device time in ms. The output sits between guard floats, which must come back untouched (asserted here)"""
+    import torch
+    planes = np.ascontiguousarray(planes, np.float32)
+    _, h, w = planes.shape
+    out_w = k * w if out_w is None else out_w; out_h = k * h if out_h is None else out_h
+    wt = np.ascontiguousarray(weights, np.float32).ravel()
+    if k not in (2, 4, 8) or wt.size != {2: 15, 4: 55, 8: 210}[k] or out_w <= 0 or out_h <= 0:
+        return ("rnge", None) + ((None,) if want_ms else ())
+    dev = "cuda:%d" % device
+    guard = 64
+    n = 3 * out_h * out_w
+    d_in = torch.from_numpy(planes).to(dev)
+    d_out = torch.full((guard + n + guard,), 12345.0, dtype=torch.float32, device=dev)
+    ms = C.c_float(0.0)
+    torch.cuda.synchronize(dev)
+    with torch.cuda.device(dev):
+        code = err4(lib().j40hip_kat_device_upsample(d_in.data_ptr(), w, h, int(k), wt.ctypes.data, int(out_w), int(out_h), d_out.data_ptr() + 4 * guard, None, C.byref(ms) if want_ms else None))
+        torch.cuda.synchronize(dev)
+    host = d_out.cpu().numpy()
+    assert (host[:guard] == 12345.0).all() and (host[-guard:] == 12345.0).all(), "k_upsample wrote outside the planes"
+    if code:
+        return (code, None) + ((None,) if want_ms else ())
+    return ("", host[guard:guard + n].reshape(3, out_h, out_w).copy()) + ((float(ms.value),) if want_ms else ())
+
+
 def kat_device_noise(planes, group_dim, lut, ytox, ytob, visible=0, nonvisible=0, device=0, want_ms=False):
     """k_noise_fill and k_noise_add alone (j40hip_kat_device_noise): planes [3, h, w] float32 (X, Y, B) -> (err4, the planes after the noise
     or None, the raw planes [3, h, w] the fill made -- zeros for a LUT of zeros, which launches nothing); with want_ms a fourth entry, the
@@ -652,7 +726,7 @@ def kat_device_restoration(planes, sharpness, hfmul_inv, r, mode=1, device=0):
 class Frame:
     """thin C-ABI (include/j40hip.h): host parse, plan upload, hot path on a HIP stream"""
 
-    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False, ycbcr=False, wide=False, noise=False):
+    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False, ycbcr=False, wide=False, noise=False, upsampling=False):
         """lf_device: a HIP device index -- the LfGroup streams are decoded there instead of on the host (j40hip_frame_parse_on).
         lf_only: parse what the LF preview needs and nothing more (J40HIP_PARSE_LF_ONLY): `data` may end at lf_end(); such a frame
         can only be previewed (decode_lf_to_host, decode_lf).
@@ -661,11 +735,14 @@ class Frame:
         wide: wide Modular frames are asked for (J40HIP_PARSE_WIDE): an image with 32-bit Modular buffers is parsed instead of refused
         with "fm32", and its Modular frame is decoded with int32 sample planes (wide())
         noise: photon noise is asked for (J40HIP_PARSE_NOISE; PARITY UNPINNED): a frame with has_noise is parsed instead of refused
-        with "TODO" and every decode adds its noise (noise_params(), noise_launches(), read_xyb(4))"""
+        with "TODO" and every decode adds its noise (noise_params(), noise_launches(), read_xyb(4))
+        upsampling: upsampling is asked for (J40HIP_PARSE_UPSAMPLING; PARITY UNPINNED): custom upsampling weights and a frame coded at
+        1:2, 1:4 or 1:8 are parsed instead of refused with "TODO"; width and height are the SHOWN size, which every decode writes
+        (upsampling(), coded_size(), read_xyb(5))"""
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        flags = (PARSE_LF_ONLY if lf_only else 0) | (PARSE_YCBCR if ycbcr else 0) | (PARSE_WIDE if wide else 0) | (PARSE_NOISE if noise else 0)
+        flags = (PARSE_LF_ONLY if lf_only else 0) | (PARSE_YCBCR if ycbcr else 0) | (PARSE_WIDE if wide else 0) | (PARSE_NOISE if noise else 0) | (PARSE_UPSAMPLING if upsampling else 0)
         if lf_device is None:
             self.h = L.j40hip_frame_parse_ex(self._buf, len(data), threads, flags, C.byref(err))
         else:
@@ -1035,10 +1112,30 @@ class Frame:
         """after a decode that ran the filters: stage 0 / 1 -> [3, height, width] float32 (before / after them), 2 -> the reciprocal sigmas [h8, w8].
         A Modular frame of an XYB image decoded with set_modular_xyb(1) in force: stage 0 -> the planes X, Y, B by k_modular_to_xyb.
         A frame with patches (Sequence's patches=): stage 3 -> [3, height, width], the planes after k_patch_blend, as the tail read them.
-        A frame with noise (noise=True): stage 4 -> the planes after k_noise_add, as the tail read them (with both, stage 3 is "rnge")"""
-        a = np.zeros((3, self.height, self.width), np.float32) if stage != 2 else np.zeros(((self.height + 7) // 8, (self.width + 7) // 8), np.float32)
+        A frame with noise (noise=True): stage 4 -> the planes after k_noise_add, as the tail read them (with both, stage 3 is "rnge").
+        An upsampled frame (upsampling=True): stage 5 -> [3, height, width] of the shown size, the planes k_upsample wrote and the tail
+        read; every other stage has the coded size (coded_size())"""
+        cw, ch = (self.width, self.height) if stage == 5 else self.coded_size()
+        a = np.zeros((3, ch, cw), np.float32) if stage != 2 else np.zeros(((ch + 7) // 8, (cw + 7) // 8), np.float32)
         self._chk(lib().j40hip_frame_read_xyb(self.h, stage, a.ctypes.data), "in j40hip_frame_read_xyb")
         return a
+
+    def upsampling(self):
+        """(K, weights): the frame's upsampling (1, 2, 4 or 8) and the table it copied at parse -- the stream's custom one for its K, else
+        the defaults set_upsampling_defaults supplied --, float32 [15 / 55 / 210]; empty for K = 1"""
+        k = C.c_int32(); n = C.c_int32(); w = np.zeros(210, np.float32)
+        self._chk(lib().j40hip_frame_upsampling(self.h, C.byref(k), w.ctypes.data, C.byref(n)), "in j40hip_frame_upsampling")
+        return int(k.value), w[:int(n.value)].copy()
+
+    def coded_size(self):
+        """(width, height) the frame is coded at: ceil(shown / K) for an upsampled frame, else width and height themselves"""
+        w = C.c_int32(); h = C.c_int32()
+        lib().j40hip_frame_coded_size(self.h, C.byref(w), C.byref(h))
+        return int(w.value), int(h.value)
+
+    def upsample_ms(self):
+        """with J40HIP_UPSAMPLE_TIMING=1: the device time of k_upsample in the last decode"""
+        return float(lib().j40hip_frame_upsample_ms(self.h))
 
     def noise_params(self):
         """photon noise (j40hip_frame_noise): None for a frame without has_noise, else a dict -- "lut": the eight NoiseParameters / 1024

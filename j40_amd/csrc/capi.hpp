@@ -24,8 +24,9 @@ struct LastDecode {
 	uint32_t restore_err = 0;         // their "gab0" / "epf0" / "shrp" (reported behind the sections' codes)
 	bool trailers_pending = false;    // decoded by a batch: j40hip_frame_status validates the extra channels' sub-images before it reports
 	const float *tail_planes = nullptr;   // the three XYB planes the tail read, after the filters and the patches (j40hip_frame_read_xyb); device memory of the upload
+	const float *coded_planes = nullptr;  // an upsampled frame: the coded planes k_upsample read (tail_planes are the shown-size ones it wrote); else null
 	// the upload's device state is released: nothing of it is named or reported any longer
-	void device_released() { restore_ran = 0; restore_err = 0; trailers_pending = false; tail_planes = nullptr; }
+	void device_released() { restore_ran = 0; restore_err = 0; trailers_pending = false; tail_planes = nullptr; coded_planes = nullptr; }
 };
 
 struct j40hip_frame {

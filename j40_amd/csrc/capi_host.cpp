@@ -9,6 +9,7 @@
 #include "tables.hpp"
 #include "device/region_dev.h"
 #include "device/patch_dev.h"
+#include "device/upsample_dev.h"
 
 using namespace j40hip;
 
@@ -28,6 +29,7 @@ j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads,
 		h->frame.allow_ycbcr = (flags & J40HIP_PARSE_YCBCR) != 0 || ycbcr_env();
 		h->frame.allow_wide = (flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
 		h->frame.allow_noise = (flags & J40HIP_PARSE_NOISE) != 0 || noise_env();
+		h->frame.allow_upsampling = (flags & J40HIP_PARSE_UPSAMPLING) != 0 || upsampling_env();
 		extract_codestream((const uint8_t *) buf, size, &h->cs, &h->cs_size, &h->cs_storage, &h->container_stray_tail);
 		h->bare_codestream = h->cs == (const uint8_t *) buf && h->cs_size == size;
 		parse_frame(h->cs, h->cs_size, &h->frame, threads);
@@ -59,6 +61,7 @@ j40hip_frame *j40hip_frame_parse_streamed(const void *buf, size_t size, int thre
 		h->frame.allow_ycbcr = (flags & J40HIP_PARSE_YCBCR) != 0 || ycbcr_env();
 		h->frame.allow_wide = (flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
 		h->frame.allow_noise = (flags & J40HIP_PARSE_NOISE) != 0 || noise_env();
+		h->frame.allow_upsampling = (flags & J40HIP_PARSE_UPSAMPLING) != 0 || upsampling_env();
 		h->cs = p; h->cs_size = size; h->bare_codestream = true;
 		parse_frame(h->cs, h->cs_size, &h->frame, threads);
 		h->threads = threads < 1 ? 1 : threads > 16 ? 16 : threads;
@@ -169,7 +172,8 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 		s->noise = (flags & J40HIP_PARSE_NOISE) != 0 || noise_env();
 		uint32_t noise_seeds[2] = {0, 0};   // visible, nonvisible as the playback reaches the next row
 		size_t at = 0;
-		parse_image_header(s->cs, s->cs_size, &s->im, &at, (flags & J40HIP_PARSE_WIDE) != 0 || wide_env());
+		// (J40HIP_SEQ_UPSAMPLING: the image header's custom weights are read; a frame of a sequence with upsampling > 1 stays "TODO")
+		parse_image_header(s->cs, s->cs_size, &s->im, &at, (flags & J40HIP_PARSE_WIDE) != 0 || wide_env(), (flags & J40HIP_SEQ_UPSAMPLING) != 0 || upsampling_env());
 		s->alpha_ec = rendered_alpha_channel(s->im);
 		// the flag on an image the colour mode refuses as a whole (the environment variable alone leaves such a sequence as it was)
 		if (s->colour_asked) if (uint32_t e = j40hip::colour::image_refusal(s->im)) raise(e);
@@ -292,6 +296,51 @@ int j40hip_frame_noise(const j40hip_frame *h, float *lut8, uint32_t *seeds2) {
 }
 int64_t j40hip_frame_noise_launches(const j40hip_frame *h) { return h ? h->noise_launches : 0; }
 
+// ---- upsampling (include/j40hip.h; device/upsample_dev.h has the rule) ----
+uint32_t j40hip_set_upsampling_defaults(int k, const float *w, int n) { return j40hip::set_upsampling_defaults(k, w, n) ? 0 : j40hip::ERR_RNGE; }
+uint32_t j40hip_frame_upsampling(const j40hip_frame *h, int32_t *k, float *weights, int32_t *n) {
+	if (!h) return j40hip::ERR_RNGE;
+	if (k) *k = h->frame.fh.upsampling;
+	if (n) *n = (int32_t) h->frame.up_table.size();
+	if (weights && !h->frame.up_table.empty()) memcpy(weights, h->frame.up_table.data(), sizeof(float) * h->frame.up_table.size());
+	return 0;
+}
+void j40hip_frame_coded_size(const j40hip_frame *h, int32_t *w, int32_t *hh) {
+	if (w) *w = h ? h->frame.fh.width : 0;
+	if (hh) *hh = h ? h->frame.fh.height : 0;
+}
+uint32_t j40hip_kat_upsampling_kernel(int32_t k, const float *weights, float *out) {
+	if (!j40hip::upsample_factor_valid(k) || !weights || !out) return j40hip::ERR_RNGE;
+	j40hip::upsample_expand(k, weights, out);
+	return 0;
+}
+// k_upsample's host twin: the same functions compiled for the CPU. tiled = 0: upsample_sample per output sample; 1: the tile functions
+// as the kernel's workgroups run them, every thread of every tile one after the other
+extern "C++" { template <int K> static void host_upsample(const float *src, int32_t w, int32_t h, const float *e, int32_t out_w, int32_t out_h, float *out, int tiled) {
+	using namespace j40hip;
+	for (int c = 0; c < 3; ++c) {
+		const float *sp = src + (size_t) c * (size_t) w * (size_t) h;
+		float *op = out + (size_t) c * (size_t) out_w * (size_t) out_h;
+		if (!tiled) { for (int32_t Y = 0; Y < out_h; ++Y) for (int32_t X = 0; X < out_w; ++X) op[(size_t) Y * (size_t) out_w + (size_t) X] = upsample_sample<K>(sp, w, h, e, X, Y); continue; }
+		float tile[UP_LDS_FLOATS];
+		for (int32_t ty = 0; ty < (h + UP_TILE_H - 1) / UP_TILE_H; ++ty) for (int32_t tx = 0; tx < (w + UP_TILE_W - 1) / UP_TILE_W; ++tx) {
+			for (int32_t t = 0; t < UP_THREADS; ++t) upsample_tile_stage(tile, sp, w, h, tx, ty, t);
+			for (int32_t t = 0; t < UP_THREADS; ++t) upsample_tile_lane<K>(op, (size_t) out_w, out_w, out_h, w, h, tile, e, tx, ty, t);
+		}
+	}
+} }
+uint32_t j40hip_kat_host_upsample(const float *planes, int32_t width, int32_t height, int32_t k, const float *weights, int32_t out_w, int32_t out_h, float *out, int tiled) {
+	if (!planes || !weights || !out || !j40hip::upsample_factor_valid(k) || width <= 0 || height <= 0 || out_w <= 0 || out_h <= 0 || (int64_t) out_w > (int64_t) k * width || (int64_t) out_h > (int64_t) k * height) return j40hip::ERR_RNGE;
+	try {
+		std::vector<float> e((size_t) k * k * 25);
+		j40hip::upsample_expand(k, weights, e.data());
+		if (k == 2) host_upsample<2>(planes, width, height, e.data(), out_w, out_h, out, tiled);
+		else if (k == 4) host_upsample<4>(planes, width, height, e.data(), out_w, out_h, out, tiled);
+		else host_upsample<8>(planes, width, height, e.data(), out_w, out_h, out, tiled);
+	} catch (const std::exception &) { return E4("!mem"); }
+	return 0;
+}
+
 void j40hip_sequence_frame_patches(const j40hip_sequence *s, int64_t k, int32_t *out8) {
 	if (!out8) return;
 	memset(out8, 0, sizeof(int32_t) * 8);
@@ -383,6 +432,7 @@ uint32_t j40hip_frame_set_alpha(j40hip_frame *h, int mode) {
 	int32_t index;
 	uint32_t e = j40hip::alpha_keep_scope(h->frame, &index);
 	if (!e && h->from_view) e = j40hip::ERR_TODO;   // (no global tree to decode the sub-images with)
+	if (!e && h->frame.fh.upsampling > 1) e = j40hip::ERR_TODO;   // (an upsampled frame's alpha would have to be stretched too: dropped only)
 	if (e && e != (uint32_t) j40hip::ERR_TODO) return e;   // "Ual?": nothing to keep or drop
 	if (mode > 0 && e) return e;
 	h->alpha = mode < 0 ? -1 : mode > 0 ? 1 : 0;
@@ -483,7 +533,7 @@ uint32_t j40hip_colour_table(const int32_t enc[16], float intensity_target, floa
 uint32_t j40hip_frame_set_region(j40hip_frame *h, int32_t x0, int32_t y0, int32_t w, int32_t hh) {
 	if (!h) return j40hip::ERR_RNGE;
 	if (h->frame.lf_only) return ERR_ULF;
-	const int32_t W = h->frame.fh.width, H = h->frame.fh.height;
+	const int32_t W = h->frame.fh.shown_width(), H = h->frame.fh.shown_height();   // (the shown size: an upsampled frame's picture)
 	const bool clear = x0 == 0 && y0 == 0 && ((w == 0 && hh == 0) || (w == W && hh == H));
 	if (!clear) {
 		if (x0 < 0 || y0 < 0 || w <= 0 || hh <= 0 || (int64_t) x0 + w > W || (int64_t) y0 + hh > H) return j40hip::ERR_RNGE;
@@ -499,9 +549,11 @@ void j40hip_frame_region(const j40hip_frame *h, int32_t out[12]) {
 	memset(out, 0, sizeof(int32_t) * 12);
 	if (!h) return;
 	const j40hip::FrameHeader &fh = h->frame.fh;
-	out[2] = fh.width; out[3] = fh.height;
+	out[2] = fh.shown_width(); out[3] = fh.shown_height();
 	if (h->region_set) for (int i = 0; i < 4; ++i) out[i] = h->region[i];
-	const j40hip::RegionCover c = j40hip::region_cover(out[0], out[1], out[2], out[3], fh.group_size_shift, fh.gcolumns);
+	// (an upsampled frame: the rectangle lies in the shown-size picture, which is cut from a decode of every group -- the cover is the coded frame's)
+	const bool up = fh.upsampling > 1;
+	const j40hip::RegionCover c = up ? j40hip::region_cover(0, 0, fh.width, fh.height, fh.group_size_shift, fh.gcolumns) : j40hip::region_cover(out[0], out[1], out[2], out[3], fh.group_size_shift, fh.gcolumns);
 	out[4] = c.gx0; out[5] = c.gy0; out[6] = c.cols; out[7] = c.rows;
 	out[8] = h->region_set ? 1 : 0;
 	out[9] = h->region_widened; out[10] = h->region_sections; out[11] = h->region_varblocks;
@@ -523,7 +575,7 @@ void j40hip_frame_scale(const j40hip_frame *h, int32_t out[5]) {
 	memset(out, 0, sizeof(int32_t) * 5);
 	out[3] = -1;
 	if (!h) return;
-	out[0] = h->scale; out[1] = scaled_size(h->frame.fh.width, h->scale); out[2] = scaled_size(h->frame.fh.height, h->scale);
+	out[0] = h->scale; out[1] = scaled_size(h->frame.fh.shown_width(), h->scale); out[2] = scaled_size(h->frame.fh.shown_height(), h->scale);
 	out[3] = h->scale_staged; out[4] = (int32_t) std::min<int64_t>(h->scale_staging_bytes, INT32_MAX);
 }
 
@@ -545,7 +597,7 @@ void j40hip_frame_orientation(const j40hip_frame *h, int32_t out[6]) {
 }
 uint32_t j40hip_frame_orient_rect(const j40hip_frame *h, int to_stored, const int32_t in[4], int32_t out[4]) {
 	if (!h || !in || !out) return j40hip::ERR_RNGE;
-	const int32_t W = h->frame.fh.width, H = h->frame.fh.height, o = h->frame.im.orientation;
+	const int32_t W = h->frame.fh.shown_width(), H = h->frame.fh.shown_height(), o = h->frame.im.orientation;
 	int32_t lw, lh;   // the image the rectangle lies in
 	if (to_stored) j40hip::orient_out_size(W, H, o, &lw, &lh); else { lw = W; lh = H; }
 	if (in[0] < 0 || in[1] < 0 || in[2] <= 0 || in[3] <= 0 || (int64_t) in[0] + in[2] > lw || (int64_t) in[1] + in[3] > lh) return j40hip::ERR_RNGE;
@@ -564,7 +616,7 @@ void j40hip_frame_free(j40hip_frame *f) {
 void j40hip_frame_info(const j40hip_frame *h, int64_t *out) {
 	const Frame &f = h->frame;
 	int i = 0;
-	out[i++] = f.fh.width; out[i++] = f.fh.height; out[i++] = f.fh.is_modular;
+	out[i++] = f.fh.shown_width(); out[i++] = f.fh.shown_height(); out[i++] = f.fh.is_modular;
 	out[i++] = f.fh.num_lf_groups; out[i++] = f.fh.num_groups; out[i++] = f.fh.num_passes;
 	out[i++] = f.nb_block_ctx; out[i++] = (int64_t) f.block_ctx_map.size(); out[i++] = f.num_hf_presets;
 	out[i++] = f.global_scale; out[i++] = f.quant_lf; out[i++] = f.fh.x_qm_scale; out[i++] = f.fh.b_qm_scale;

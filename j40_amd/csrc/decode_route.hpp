@@ -6,6 +6,11 @@
 // frame, not a mode of the handle: DecodeRoute::noise sends the decode through the plane stage -- whole frames at full size, from which a
 // region is cut and a scale averaged (full_size_first), in one phase --, and refuses what has no full-size XYB planes to add it to: a
 // Modular frame without the Modular XYB switch, a YCbCr plan, a partial group range, a batch, many LF previews in one launch (an LF-only parse of such a frame is refused by the parse).
+// Upsampling (a frame parsed with J40HIP_PARSE_UPSAMPLING whose header has upsampling > 1) is such an operation too, the one that changes the
+// planes' size: DecodeRoute::upsampling sends the decode through the plane stage, where k_upsample stretches the coded planes to the shown
+// size ahead of the tail; stored_w and stored_h come from the shown size, a region is cut from and a scale averaged over the shown-size
+// picture, in one phase. Refused ("TODO"): what noise refuses, and kept alpha, a frame that also has patches or noise (shown-size
+// operations: a follow-up), a Modular frame with an alpha channel, every frame of a sequence (the parse).
 #pragma once
 #include "capi.hpp"
 #include "device/orient_dev.h"
@@ -29,7 +34,8 @@ inline uint32_t mode_refusal(const j40hip_frame *h, Mode what) {
 	const bool owned_size = owned && !j40hip_patch_still_handle(h);     // ... its size also but for a full-canvas frame with patches
 	// (patches go onto whole pictures' planes through one handle's own tail: no batch, no preview of the LF image alone, no partial range)
 	// (noise likewise: it is added to whole pictures' planes)
-	const bool patches = h->frame.fh.has_patches || h->frame.fh.has_noise;
+	// (an upsampled frame likewise: its coded planes are stretched whole)
+	const bool patches = h->frame.fh.has_patches || h->frame.fh.has_noise || h->frame.fh.upsampling > 1;
 	if (patches && (what == Mode::GroupRange || what == Mode::Batch || what == Mode::LfPreviewBatch)) return ERR_TODO;
 	switch (what) {
 	case Mode::Region:         return h->partial_range ? ERR_URG : h->scale > 0 ? ERR_USC : 0;
@@ -51,7 +57,7 @@ inline bool signals_filters(const FrameHeader &fh) { return fh.restoration.gab |
 
 // what the decision needs of the upload (j40hip_device_state's): a Modular plan, a VarDCT plan built for a YCbCr frame, sections that go on
 // with the extra channels' sub-images, the group range
-struct UploadFacts { bool is_modular, ycbcr, has_trailers; int64_t first_group, num_groups; };
+struct UploadFacts { bool is_modular, ycbcr, has_trailers; int64_t first_group, num_groups; bool modular_alpha = false; };   // modular_alpha: a Modular plan renders A from a plane of its own
 
 struct DecodeRoute {
 	uint32_t refusal = 0;              // what every single-frame decode entry answers before anything is launched or allocated (not its concern: xyb_refusal)
@@ -66,6 +72,7 @@ struct DecodeRoute {
 	bool modular_xyb = false;          // a Modular plan through the XYB colour tail
 	bool patches = false;              // the frame has a patch dictionary: its pixels come from XYB planes (the filtered ones where the filters are in force), k_patch_blend over them, then the tail
 	bool noise = false;                // the frame has noise: likewise, k_noise_fill and k_noise_add behind the patches, ahead of the tail
+	bool upsampling = false;           // the frame is coded at 1:2, 1:4 or 1:8: k_upsample behind the filters makes the shown-size planes the tail reads
 	bool colour = false;               // the colour mode in force: the XYB planes (filtered where the filters are in force; a Modular XYB plan's by k_modular_to_xyb) go through k_colour_tail
 	bool every_group = true;           // no partial group range
 	bool two_phase = false;            // decode_to_host may try its two phases: a whole frame in stored order that takes no LF frame's picture
@@ -78,8 +85,8 @@ inline DecodeRoute resolve_route(const j40hip_frame *h, const UploadFacts *up, b
 	const Frame &fr = h->frame;
 	r.orientation = j40hip_orientation_in_force(h);
 	r.shape = h->region_set ? DecodeRoute::Region : h->scale > 0 ? DecodeRoute::Scaled : DecodeRoute::Whole;
-	r.stored_w = h->region_set ? h->region[2] : scaled_size(fr.fh.width, h->scale);
-	r.stored_h = h->region_set ? h->region[3] : scaled_size(fr.fh.height, h->scale);
+	r.stored_w = h->region_set ? h->region[2] : scaled_size(fr.fh.shown_width(), h->scale);
+	r.stored_h = h->region_set ? h->region[3] : scaled_size(fr.fh.shown_height(), h->scale);
 	orient_out_size(r.stored_w, r.stored_h, r.orientation, &r.out_w, &r.out_h);
 	r.pixel_bytes = h->output_format == J40HIP_U16X4 ? 8 : 4;
 	const bool old_contract = r.shape == DecodeRoute::Whole && r.orientation == 1 && r.pixel_bytes == 4;
@@ -94,16 +101,20 @@ inline DecodeRoute resolve_route(const j40hip_frame *h, const UploadFacts *up, b
 	r.colour = j40hip_colour_on(h);
 	r.patches = fr.fh.has_patches;
 	r.noise = fr.fh.has_noise;
-	const bool full_size_only = r.colour || r.patches || r.noise || (up->is_modular ? r.modular_xyb && r.shape == DecodeRoute::Scaled : r.restoration || r.alpha_merged);
+	r.upsampling = fr.fh.upsampling > 1;
+	const bool full_size_only = r.colour || r.patches || r.noise || r.upsampling || (up->is_modular ? r.modular_xyb && r.shape == DecodeRoute::Scaled : r.restoration || r.alpha_merged);
 	r.full_size_first = r.shape != DecodeRoute::Whole && full_size_only;
-	r.two_phase = r.shape == DecodeRoute::Whole && r.orientation == 1 && !fr.fh.use_lf_frame && !r.colour && !r.patches && !r.noise;
-	r.xyb_refusal = r.patches || r.noise || r.shape != DecodeRoute::Whole || !r.every_group || (up->is_modular ? !r.modular_xyb : up->ycbcr || up->has_trailers) ? (uint32_t) ERR_TODO : 0;
+	r.two_phase = r.shape == DecodeRoute::Whole && r.orientation == 1 && !fr.fh.use_lf_frame && !r.colour && !r.patches && !r.noise && !r.upsampling;
+	r.xyb_refusal = r.patches || r.noise || r.upsampling || r.shape != DecodeRoute::Whole || !r.every_group || (up->is_modular ? !r.modular_xyb : up->ycbcr || up->has_trailers) ? (uint32_t) ERR_TODO : 0;
 	// in the entry points' order: an orientation over a partial range (no whole stored image to turn), the oriented image's rows, a YCbCr plan
 	// (served only while its switch stays on, and whole), the stored image's rows
 	if (r.orientation != 1 && !r.every_group) r.refusal = ERR_UOR;
 	else if (r.colour && !r.every_group) r.refusal = ERR_UCS;   // (a group range set before the mode: mode_refusal's rule)
 	// (a Modular frame's planes reach XYB through the Modular XYB switch alone)
-	else if ((r.patches || r.noise) && (!r.every_group || (up->is_modular && !r.modular_xyb) || up->ycbcr)) r.refusal = ERR_TODO;
+	else if ((r.patches || r.noise || r.upsampling) && (!r.every_group || (up->is_modular && !r.modular_xyb) || up->ycbcr)) r.refusal = ERR_TODO;
+	// (noise is a shown-size operation, the kept alpha and a Modular frame's alpha plane would have to be stretched as well)
+	// (a frame with patches exists in sequences alone, whose frames the parse refuses: nothing to ask here)
+	else if (r.upsampling && (r.noise || r.alpha_merged || (up->is_modular && up->modular_alpha))) r.refusal = ERR_TODO;
 	else if (r.orientation != 1 && (!have_out || stride_bytes < r.min_stride)) r.refusal = ERR_RNGE;
 	else if (up->ycbcr && (!j40hip_ycbcr_on(h) || r.shape != DecodeRoute::Whole || !r.every_group)) r.refusal = ERR_TODO;
 	else if (stride_bytes < r.min_stride) r.refusal = ERR_RNGE;

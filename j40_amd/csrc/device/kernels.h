@@ -7,6 +7,7 @@
 #include "colour_dev.h"
 #include "patch_dev.h"
 #include "noise_dev.h"
+#include "upsample_dev.h"
 
 namespace j40hip {
 
@@ -58,6 +59,11 @@ void launch_patch_blend(float *planes, int32_t width, int32_t height, const DevP
 // three planes at `planes` (`ppitch` floats a row, one behind the other), in place
 void launch_noise_fill(float *raw, const NoiseFillArgs &a, const uint64_t *sets_dev, hipStream_t stream);
 void launch_noise_add(float *planes, size_t ppitch, const float *raw, int32_t W, int32_t H, const NoiseParams &p, hipStream_t stream);
+
+// upsampling (device/upsample_kernels.hip, upsample_dev.h): k_upsample<k> stretches the three coded planes at `src` (w x h floats each, one
+// behind the other) into the three at `out` (up_w x up_h each, up_w <= k * w, up_h <= k * h) by the expanded table at `table_dev`
+// (k * k * 25 floats, device memory). false: a factor or a size it does not take, nothing launched
+bool launch_upsample(const float *src, int32_t w, int32_t h, int32_t k, const float *table_dev, float *out, int32_t up_w, int32_t up_h, hipStream_t stream);
 
 // LfGroup tail on the device (device/lf_tail_kernels.hip)
 void upload_lf_tail_tables(const float *half_secants, const float *lf2llf, hipStream_t stream);

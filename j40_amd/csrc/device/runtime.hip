@@ -159,6 +159,73 @@ extern "C" uint32_t j40hip_kat_device_noise(float *planes_dev, int32_t width, in
 	});
 }
 
+// ---- upsampling (a frame parsed with J40HIP_PARSE_UPSAMPLING whose header has upsampling > 1; device/upsample_dev.h, upsample_kernels.hip) ----
+// k_upsample on `s` between two events of its own when ms is not null (J40HIP_UPSAMPLE_TIMING, the known-answer hook): the call then
+// waits for the kernel and reports its device time. The events are destroyed on every way out.
+static uint32_t run_upsample_kernel(const float *src, int32_t w, int32_t h, int32_t k, const float *table_dev, float *out, int32_t up_w, int32_t up_h, hipStream_t s, float *ms) {
+	struct Pair { hipEvent_t ev[2] = {nullptr, nullptr}; ~Pair() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); } } pair;
+	bool timed = ms != nullptr;
+	for (int i = 0; timed && i < 2; ++i) timed = hipEventCreate(&pair.ev[i]) == hipSuccess;
+	if (ms) *ms = 0.0f;
+	if (timed) (void) hipEventRecord(pair.ev[0], s);
+	if (!launch_upsample(src, w, h, k, table_dev, out, up_w, up_h, s)) return ERR_RNGE;
+	if (timed) (void) hipEventRecord(pair.ev[1], s);
+	if (hipGetLastError() != hipSuccess) return ERR_GPU;
+	if (timed) {
+		if (hipEventSynchronize(pair.ev[1]) != hipSuccess) return ERR_GPU;
+		(void) hipEventElapsedTime(ms, pair.ev[0], pair.ev[1]);
+	}
+	return 0;
+}
+
+// The frame's coded planes at `planes` (width x height floats each, X, Y, B one behind the other) stretched into its shown-size planes, on
+// `s`: called by render_planes ahead of everything else it does. *out: where the planes the tail reads lie -- `planes` themselves for a
+// frame with upsampling = 1, for which nothing is launched or allocated. The shown-size planes and the expanded table (built on the host
+// once per upload) are kept with the frame like d_xyb.
+uint32_t j40hip_rt::apply_upsampling(j40hip_frame *h, const float *planes, float **out, hipStream_t s) {
+	const Frame &fr = h->frame;
+	const int32_t k = fr.fh.upsampling;
+	if (k <= 1) { *out = const_cast<float *>(planes); return 0; }
+	j40hip_device_state *st = h->dev;
+	const int32_t up_w = fr.fh.shown_width(), up_h = fr.fh.shown_height();
+	if (!upsample_factor_valid(k) || (int32_t) fr.up_table.size() != upsample_weight_count(k)) return ERR_TODO;   // (cannot happen: the parse made both)
+	if (!st->keep(st->up.d_up, 3 * (size_t) up_w * (size_t) up_h)) return ERR_MEM;
+	if (!st->up.d_table) {
+		st->up.host_table.assign((size_t) k * k * 25, 0.0f);
+		upsample_expand(k, fr.up_table.data(), st->up.host_table.data());
+		bool ok = true;
+		st->up.d_table = st->upload(st->up.host_table.data(), st->up.host_table.size(), s, ok);
+		if (!ok) { st->up.d_table = nullptr; return ERR_MEM; }
+	}
+	static const bool timed = env_str("J40HIP_UPSAMPLE_TIMING") != nullptr;
+	if (uint32_t e = run_upsample_kernel(planes, fr.fh.width, fr.fh.height, k, st->up.d_table, st->up.d_up, up_w, up_h, s, timed ? &st->up.ms : nullptr)) return e;
+	*out = st->up.d_up;
+	return 0;
+}
+
+extern "C" float j40hip_frame_upsample_ms(const j40hip_frame *h) { return h && h->dev ? h->dev->up.ms : 0.0f; }
+
+extern "C" uint32_t j40hip_kat_device_upsample(const float *planes_dev, int32_t width, int32_t height, int32_t k, const float *weights, int32_t out_w, int32_t out_h, float *out_dev, void *stream, float *ms) {
+	return guarded([&]() -> uint32_t {
+		if (ms) *ms = 0.0f;
+		if (!planes_dev || !weights || !out_dev || !upsample_factor_valid(k) || width <= 0 || height <= 0 || out_w <= 0 || out_h <= 0 || (int64_t) out_w > (int64_t) k * width || (int64_t) out_h > (int64_t) k * height
+			|| (int64_t) out_w * out_h > (1 << 28)) return ERR_RNGE;
+		int device = 0;
+		if (hipGetDevice(&device) != hipSuccess) return ERR_GPU;
+		hipStream_t s = (hipStream_t) stream;
+		j40hip_device_state tmp; tmp.device = device;
+		bool ok = true;
+		std::vector<float> table((size_t) k * k * 25);
+		upsample_expand(k, weights, table.data());
+		const float *d_table = tmp.upload(table.data(), table.size(), s, ok);
+		uint32_t e = ok ? run_upsample_kernel(planes_dev, width, height, k, d_table, out_dev, out_w, out_h, s, ms) : ERR_MEM;
+		if (hipStreamSynchronize(s) != hipSuccess && !e) e = ERR_GPU;
+		for (auto &b : tmp.buffers) b.release();
+		tmp.buffers.clear();
+		return e;
+	});
+}
+
 // ---- the plane stage: from the frame's three full-size float planes (X, Y, B; a YCbCr frame's Cb, Y, Cr) to the caller's pixels ----
 // Who enters it is decided once per decode, before anything is launched (run_vardct, decode_modular): a decode whose restoration filters
 // run, the colour mode, a frame with patches, a 4:4:4 YCbCr plan, a caller that wants the planes themselves. Two steps: the planes are
@@ -190,7 +257,15 @@ static uint32_t ycbcr_tail(j40hip_frame *h, YcbcrTail &t, uint8_t *img, size_t s
 static uint32_t render_planes(j40hip_frame *h, float *planes, size_t pitch, bool colour, uint8_t *img, size_t stride_bytes, hipStream_t s) {
 	j40hip_device_state *st = h->dev;
 	const Frame &fr = h->frame;
-	const int32_t W = fr.fh.width, H = fr.fh.height;
+	// the coded planes first: an upsampled frame's are stretched into a buffer of their own, and everything below runs over that one, with
+	// the shown size and its pitch (the route refuses such a frame with patches, with noise or as a YCbCr plan)
+	if (fr.fh.upsampling > 1) {
+		if (pitch != (size_t) fr.fh.width) return ERR_TODO;   // (cannot happen: only a YCbCr plan pads its rows)
+		h->last.coded_planes = planes;
+		if (uint32_t e = apply_upsampling(h, planes, &planes, s)) return e;
+		pitch = (size_t) fr.fh.shown_width();
+	}
+	const int32_t W = fr.fh.shown_width(), H = fr.fh.shown_height();
 	if (uint32_t e = apply_patches(h, planes, s)) return e;
 	if (fr.fh.has_noise && pitch != (size_t) W) return ERR_TODO;   // (cannot happen: only a YCbCr plan pads its rows, and the route refuses it)
 	if (uint32_t e = apply_noise(h, planes, s)) return e;
@@ -230,7 +305,7 @@ static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *
 	h->last.modular_xyb_used = xyb;
 	if ((xyb_out && !xyb) || (xyb && shift > 0)) return ERR_TODO;
 	const bool colour = route.colour && xyb && !xyb_out;   // (whole frames: the route stages a region or a scale)
-	const bool patches = (route.patches || route.noise) && !xyb_out;        // (likewise; noise goes the patches' way)
+	const bool patches = (route.patches || route.noise || route.upsampling) && !xyb_out;        // (likewise; noise and upsampling go the patches' way)
 	if (patches && (!xyb || !st->patch.d_frame)) return ERR_TODO;
 	if ((colour || patches) && (region || shift > 0 || !route.every_group)) return ERR_TODO;
 	const bool planes = colour || patches || xyb_out;   // the decode goes through the plane stage
@@ -554,7 +629,7 @@ static uint32_t ycbcr_pixels(j40hip_frame *h, const int32_t *class_start, const 
 // One VarDCT decode as decode_impl (whole frames, group ranges), decode_region (covers), decode_scaled and decode_frame_xyb describe it to
 // run_vardct; as it stands, the whole frame from the frame's own lists, with nothing to write to yet
 struct VardctRun {
-	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged), colour(r.colour), patches(r.patches || r.noise) {}
+	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged), colour(r.colour), patches(r.patches || r.noise || r.upsampling) {}
 	int32_t first_group = 0, num_groups; // the groups of the entropy launch ...
 	const RegionCover *cover = nullptr;  // ... or (not null) a region's cover: through the fast kernel's order list (region.d_order), else a launch per row of its groups
 	const DevVarblock *list; const int32_t *class_start;   // what the pixel kernels take
@@ -563,7 +638,7 @@ struct VardctRun {
 	int restoration;                     // the route's: the mode the restoration filters run in (0: they do not; never where `whole` is false)
 	bool alpha_merged;                   // the route's
 	bool colour;                         // the route's: the pixels come from k_colour_tail (whole frames at full size: the route stages everything else)
-	bool patches;                        // the route's patches or noise: the frame's patches, its noise, go onto its XYB planes ahead of the tail (whole frames at full size, likewise)
+	bool patches;                        // the route's patches, noise or upsampling: the frame's patches, its noise, go onto its XYB planes ahead of the tail, an upsampled frame's planes are stretched there (whole frames at full size, likewise)
 	const uint8_t *crop_from = nullptr; uint8_t *crop_to = nullptr; size_t crop_stride = 0; int32_t crop_w = 0, crop_h = 0;   // crop_to not null: these pixels of img are then moved there
 	int32_t shift = 0;                   // the scale shift the pixel kernels write at (decode_scaled's fused route: img is the small image)
 	float *xyb_out = nullptr;            // not null (an LF frame of a sequence, decode_frame_xyb): no pixels, img is null -- the three XYB planes, width * height
@@ -762,18 +837,20 @@ static uint32_t decode_region(j40hip_frame *h, const DecodeRoute &route, void *r
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
 	if (st->is_modular && !route.full_size_first) return decode_modular(h, route, rgba_dev, stride_bytes, s, ms3, h->region);   // (staged: a Modular XYB frame under the colour mode)
 	const int32_t W = fr.fh.width, H = fr.fh.height, shift = fr.fh.group_size_shift;
-	const RegionCover cover = region_cover(x0, y0, w, hh, shift, fr.fh.gcolumns);
-	const int32_t ncover = region_cover_groups(cover);
 	if (route.full_size_first) {
 		// the filters read across groups, the kept alpha is merged into full-size pixels: the whole frame as ever, into a staging image
+		// (of the shown size: an upsampled frame's picture is what the rectangle lies in)
+		const int32_t SW = fr.fh.shown_width(), SH = fr.fh.shown_height();
 		size_t img_stride = 0;
-		uint8_t *img = region_image(h, rgba_dev, stride_bytes, W, H, x0, &img_stride);
+		uint8_t *img = region_image(h, rgba_dev, stride_bytes, SW, SH, x0, &img_stride);
 		if (!img) return ERR_MEM;
 		h->region_widened = 1; h->region_sections = st->total_sections; h->region_varblocks = (int32_t) st->vb_count;
 		if (uint32_t e = decode_impl(h, route, img, img_stride, s, ms3, true)) return e;
 		launch_region_crop(img + (size_t) y0 * img_stride + (size_t) x0 * pb, img_stride, (uint8_t *) rgba_dev, stride_bytes, w, hh, (int32_t) pb, s);
 		return hipGetLastError() == hipSuccess ? 0 : ERR_GPU;
 	}
+	const RegionCover cover = region_cover(x0, y0, w, hh, shift, fr.fh.gcolumns);
+	const int32_t ncover = region_cover_groups(cover);
 	const bool all = ncover == (int32_t) fr.fh.num_groups;   // (the whole frame's lists and launches serve; also every single-section frame)
 	if (!all) if (uint32_t e = region_gather(h, cover, s)) return e;
 	const DevVarblock *list = all ? st->d_vb_sorted : st->region.d_list;
@@ -801,7 +878,7 @@ static uint32_t decode_region(j40hip_frame *h, const DecodeRoute &route, void *r
 static uint32_t decode_scaled(j40hip_frame *h, const DecodeRoute &route, void *rgba_dev, size_t stride_bytes, hipStream_t s, float *ms3) {
 	j40hip_device_state *st = h->dev;
 	const Frame &fr = h->frame;
-	const int32_t W = fr.fh.width, H = fr.fh.height, k = h->scale;
+	const int32_t W = fr.fh.shown_width(), H = fr.fh.shown_height(), k = h->scale;   // (the shown size: only a staged decode sees an upsampled frame)
 	const size_t pb = route.pixel_bytes;
 	if (hipSetDevice(st->device) != hipSuccess) return ERR_GPU;
 	if (route.full_size_first) {

@@ -85,6 +85,12 @@ extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out
 	// (stage 3, a frame with patches: the planes the last decode's tail read, after k_patch_blend)
 	// (tail_planes names a buffer of this upload or nothing: a release of the device state forgets it)
 	// (stage 4, a frame with noise: likewise, after k_noise_add. With both, what stood between the two kernels is gone: stage 3 is "rnge")
+	// (stage 5, an upsampled frame: the shown-size planes k_upsample wrote and the tail read; stages 0 and 1 stay the coded planes)
+	if (stage == 5) return guarded([&]() -> uint32_t {
+		if (!h || !h->dev || !h->last.tail_planes || !h->last.coded_planes || h->frame.fh.upsampling <= 1 || !out) return ERR_RNGE;
+		if (hipSetDevice(h->dev->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ERR_GPU;
+		return hipMemcpy(out, h->last.tail_planes, sizeof(float) * 3 * (size_t) h->frame.fh.shown_width() * (size_t) h->frame.fh.shown_height(), hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+	});
 	if (stage == 3 || stage == 4) return guarded([&]() -> uint32_t {
 		if (!h || !h->dev || !h->last.tail_planes || !out) return ERR_RNGE;
 		if (stage == 3 ? !h->frame.fh.has_patches || h->frame.fh.has_noise : !h->frame.fh.has_noise) return ERR_RNGE;
@@ -95,7 +101,8 @@ extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out
 	// (the colour mode without the filters: the planes the last decode's k_colour_tail read, stages 0 and 1 alike)
 	if (h && h->dev && !h->last.restore_ran && h->last.colour_used && h->last.tail_planes && (stage == 0 || stage == 1) && out) {
 		if (hipSetDevice(h->dev->device) != hipSuccess) return ERR_GPU;
-		return hipMemcpy(out, h->last.tail_planes, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+		const float *coded = h->frame.fh.upsampling > 1 ? h->last.coded_planes : h->last.tail_planes;   // (an upsampled frame's tail read the stretched planes)
+		return coded && hipMemcpy(out, coded, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
 	}
 	if (!h || !h->dev || !h->last.restore_ran || !h->dev->d_xyb) return ERR_RNGE;
 	j40hip_device_state *st = h->dev;

@@ -201,6 +201,10 @@ struct j40hip_device_state {
 	// a frame with noise (runtime.hip: apply_noise): the three raw random planes (noise_pitch(width) floats a row) and the frame's four
 	// jump sets, made at the first decode that adds noise, kept with the frame; ms: the two kernels' device time (J40HIP_NOISE_TIMING)
 	struct Noise { float *d_raw = nullptr; const uint64_t *d_sets = nullptr; std::vector<uint64_t> host_sets; float ms[2] = {0, 0}; } noise;
+	// an upsampled frame (runtime.hip: apply_upsampling): the three shown-size planes k_upsample writes and the tail reads
+	// (3 * up_width * up_height floats) and the frame's expanded weight table (host_table: built once per upload, kept: the copy is
+	// asynchronous), made at the first decode, kept with the frame; nothing for upsampling = 1. ms: the kernel's device time (J40HIP_UPSAMPLE_TIMING)
+	struct Upsample { float *d_up = nullptr; const float *d_table = nullptr; std::vector<float> host_table; float ms = 0; } up;
 	// a YCbCr frame (j40hip_frame_set_ycbcr; runtime.hip: ycbcr_pixels). ycbcr: the plan was built for one (the switch was on at upload).
 	// d_ycc: the planes the pixel kernels leave for k_ycbcr_tail where the filters do not run, made at the first such decode, kept with
 	// the frame. ycc_read: what the last decode's tail read (j40hip_frame_read_ycbcr) -- those planes, or the restoration filters' result
@@ -274,7 +278,7 @@ inline size_t pixel_bytes(const j40hip_frame *h) { return out16(h) ? 8 : 4; }
 // what the handle's next decode does (decode_route.hpp), with the upload's facts; `have_out`, `stride_bytes`: the caller's image
 inline DecodeRoute route_of(const j40hip_frame *h, bool have_out = true, size_t stride_bytes = SIZE_MAX) {
 	const j40hip_device_state *st = h->dev;
-	const UploadFacts up = {st && st->is_modular, st && st->ycbcr, st && st->has_trailers, st ? st->first_group : 0, st ? st->num_groups : 0};
+	const UploadFacts up = {st && st->is_modular, st && st->ycbcr, st && st->has_trailers, st ? st->first_group : 0, st ? st->num_groups : 0, st && st->is_modular && st->alpha_channel >= 0};
 	return resolve_route(h, st ? &up : nullptr, have_out, stride_bytes);
 }
 
@@ -296,6 +300,7 @@ uint32_t clear_before_decode(j40hip_device_state *st, hipStream_t s);          /
 uint32_t decode_frame_xyb(j40hip_frame *h, float *planes, hipStream_t s);      // runtime.hip
 uint32_t apply_patches(j40hip_frame *h, float *planes, hipStream_t s);         // runtime.hip
 uint32_t apply_noise(j40hip_frame *h, float *planes, hipStream_t s);           // runtime.hip
+uint32_t apply_upsampling(j40hip_frame *h, const float *planes, float **out, hipStream_t s);   // runtime.hip
 uint32_t restore_params(const FrameHeader &fh, int mode, RestoreParams *p);    // runtime.hip
 // A synchronous entry's wait behind a decode it has enqueued on `s`: the stream, then the frame's status. A section with more non-zero
 // coefficients than its event region holds ("evof") has the frame uploaded again with dense planes, `decode` enqueues it once more, and

@@ -162,7 +162,7 @@ static void enum_primaries_xy(int32_t pr, int32_t xy[3][2]) {
 	for (int i = 0; i < 3; ++i) { xy[i][0] = s[i][0]; xy[i][1] = s[i][1]; }
 }
 
-static void read_image_metadata(BitReader &br, ImageMeta *im, bool allow_wide) {  // j40.h:3104
+static void read_image_metadata(BitReader &br, ImageMeta *im, bool allow_wide, bool allow_upsampling) {  // j40.h:3104
 	static const float OPSIN_INV[3][3] = {
 		{11.031566901960783f, -9.866943921568629f, -0.16462299647058826f},
 		{-3.254147380392157f, 4.418770392156863f, -0.16462299647058826f},
@@ -275,8 +275,37 @@ static void read_image_metadata(BitReader &br, ImageMeta *im, bool allow_wide) {
 			for (int i = 0; i < 3; ++i) im->quant_bias[i] = br.f16();
 			im->quant_bias_num = br.f16();
 		}
-		J40HIP_SHOULD(br.u(3) == 0, "TODO");  // custom upsampling weights
+		// custom upsampling weights: up2_weight, up4_weight, up8_weight, each behind its bit of the mask (read with the switch alone)
+		im->cw_mask = (int32_t) br.u(3);
+		J40HIP_SHOULD(im->cw_mask == 0 || allow_upsampling, "TODO");
+		static const int32_t COUNT[3] = {15, 55, 210};
+		for (int t = 0; t < 3; ++t) if (im->cw_mask >> t & 1) {
+			im->up_weights[t].resize((size_t) COUNT[t]);
+			for (float &w : im->up_weights[t]) w = br.f16();
+		}
 	}
+}
+
+// ---- the default upsampling weights (frame.hpp) ----
+static std::mutex g_up_defaults_mutex;
+static std::vector<float> g_up_defaults[3];
+static int up_table_index(int32_t k) { return k == 2 ? 0 : k == 4 ? 1 : k == 8 ? 2 : -1; }
+bool set_upsampling_defaults(int32_t k, const float *w, int32_t n) {
+	static const int32_t COUNT[3] = {15, 55, 210};
+	const int t = up_table_index(k);
+	if (t < 0 || (n != 0 && (!w || n != COUNT[t]))) return false;
+	std::lock_guard<std::mutex> lock(g_up_defaults_mutex);
+	if (n == 0) { g_up_defaults[t].clear(); return true; }   // (n = 0 takes the table back: frames parsed afterwards answer "updf" again)
+	g_up_defaults[t].assign(w, w + n);
+	return true;
+}
+bool get_upsampling_defaults(int32_t k, std::vector<float> *out) {
+	const int t = up_table_index(k);
+	if (t < 0) return false;
+	std::lock_guard<std::mutex> lock(g_up_defaults_mutex);
+	if (g_up_defaults[t].empty()) return false;
+	*out = g_up_defaults[t];
+	return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -284,7 +313,8 @@ static void read_image_metadata(BitReader &br, ImageMeta *im, bool allow_wide) {
 
 // `sequence`: the frame belongs to a frame sequence, which refuses the types it does not serve as soon as it has read them
 // `lf_frames`: ... and the sequence serves LF frames (type 1), `patches`: and reference-only frames (type 2)
-static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f, bool sequence = false, bool lf_frames = false, bool patches = false) {
+// `upsampling`: upsampling is asked for (Frame::allow_upsampling; never for a sequence's frame, which stays "TODO")
+static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f, bool sequence = false, bool lf_frames = false, bool patches = false, bool upsampling = false) {
 	f->width = im.width; f->height = im.height;
 	f->ec_blend.assign(im.ec.size(), FrameHeader::Blend());
 	br.zero_pad_to_byte();
@@ -306,8 +336,15 @@ static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f
 				for (int c = 0; c < 3; ++c) { const int8_t *m = FACTOR[(f->jpeg_upsampling >> (2 * c)) & 3]; maxh = std::max<int>(maxh, m[0]); maxv = std::max<int>(maxv, m[1]); }
 				for (int c = 0; c < 3; ++c) { const int8_t *m = FACTOR[(f->jpeg_upsampling >> (2 * c)) & 3]; f->hshift[c] = (int8_t) (maxh / m[0] - 1); f->vshift[c] = (int8_t) (maxv / m[1] - 1); }
 			}
-			J40HIP_SHOULD(br.u(2) == 0, "TODO");  // upsampling
-			for (size_t i = 0; i < im.ec.size(); ++i) J40HIP_SHOULD(br.u(2) == 0, "TODO");
+			// upsampling and every extra channel's ec_upsampling (with the switch alone: the reference refuses both, j40.h:5244-5249)
+			f->upsampling = 1 << (int32_t) br.u(2);
+			J40HIP_SHOULD(f->upsampling == 1 || upsampling, "TODO");
+			f->ec_upsampling.assign(im.ec.size(), 1);
+			for (size_t i = 0; i < im.ec.size(); ++i) {
+				f->ec_upsampling[i] = 1 << (int32_t) br.u(2);
+				J40HIP_SHOULD(f->ec_upsampling[i] == 1 || upsampling, "TODO");
+				J40HIP_SHOULD((f->ec_upsampling[i] << im.ec[i].dim_shift) >= f->upsampling, "usmp");   // (j40.h:3637)
+			}
 		}
 		if (f->is_modular) f->group_size_shift = 7 + (int32_t) br.u(2);
 		else if (im.xyb_encoded) { f->x_qm_scale = (int32_t) br.u(3); f->b_qm_scale = (int32_t) br.u(3); }
@@ -383,6 +420,16 @@ static void read_frame_header(BitReader &br, const ImageMeta &im, FrameHeader *f
 		}
 		read_extensions(br);
 	}
+	// the header's size is the shown one; an upsampled frame is coded at ceil(shown / K), and from here on width and height mean that
+	f->up_width = f->width; f->up_height = f->height;
+	if (f->upsampling > 1) {
+		J40HIP_SHOULD(!sequence, "TODO");   // (no frame of a sequence; a stand-alone frame of type 1 or 2 is refused by its caller whatever its upsampling)
+		f->width = ceil_div(f->up_width, f->upsampling); f->height = ceil_div(f->up_height, f->upsampling);
+	}
+	// An extra channel coarser than the frame (ec_upsampling above upsampling; "usmp" has seen to the other way): a VarDCT frame's, which
+	// is decoded at its own size and dropped (init_global_modular), up to four times coarser -- from eight times on its samples would
+	// belong to the LfGroup sections. A Modular frame renders its alpha plane, which nothing stretches on its own: "TODO"
+	for (int32_t e : f->ec_upsampling) J40HIP_SHOULD(e == f->upsampling || (!f->is_modular && e <= 4 * f->upsampling), "TODO");
 	f->grows = ceil_div(f->height, 1 << f->group_size_shift);
 	f->gcolumns = ceil_div(f->width, 1 << f->group_size_shift);
 	f->num_groups = (int64_t) f->grows * f->gcolumns;
@@ -447,6 +494,15 @@ static void init_global_modular(Frame *f) {  // j40.h:3619
 	f->gmodular.channel.assign((size_t) n, Plane());
 	for (size_t i = 0; i < im.ec.size(); ++i) J40HIP_SHOULD(im.ec[i].dim_shift == 0, "TODO");
 	for (Plane &p : f->gmodular.channel) { p.width = fh.width; p.height = fh.height; }
+	// (PARITY UNPINNED, device/upsample_dev.h) extra channel i is coded at ceil(shown / ec_upsampling[i]); where that is coarser than the
+	// frame its groups hold the frame's group rectangles shifted down by log2(ec_upsampling[i] / upsampling), like a squeezed channel's
+	for (size_t i = 0; i < im.ec.size() && i < fh.ec_upsampling.size(); ++i) if (fh.ec_upsampling[i] > fh.upsampling) {
+		Plane &p = f->gmodular.channel[f->gmodular.channel.size() - im.ec.size() + i];
+		int32_t s = 0;
+		while ((fh.upsampling << s) < fh.ec_upsampling[i]) ++s;
+		p.width = ceil_div(fh.shown_width(), fh.ec_upsampling[i]); p.height = ceil_div(fh.shown_height(), fh.ec_upsampling[i]);
+		p.hshift = p.vshift = (int8_t) s;
+	}
 	f->gmodular.bpp = im.bpp;
 }
 
@@ -897,14 +953,14 @@ static void skip_icc(BitReader &br) {
 
 // signature, image and frame headers, TOC (sections clipped to the bytes that exist), the LfGroups' geometry
 // `limit`: how much of the codestream's cs_size bytes may be read (streaming input: what has arrived; else cs_size)
-static void read_image_header(BitReader &br, ImageMeta *im, bool allow_wide) {
+static void read_image_header(BitReader &br, ImageMeta *im, bool allow_wide, bool allow_upsampling = false) {
 	J40HIP_SHOULD(br.u(16) == 0x0aff, "!jxl");
-	read_image_metadata(br, im, allow_wide);
+	read_image_metadata(br, im, allow_wide, allow_upsampling);
 	if (im->want_icc) skip_icc(br);
 }
-void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame, bool allow_wide) {
+void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame, bool allow_wide, bool allow_upsampling) {
 	BitReader br(cs, cs_size);
-	read_image_header(br, im, allow_wide);
+	read_image_header(br, im, allow_wide, allow_upsampling);
 	br.zero_pad_to_byte();
 	*first_frame = br.byte_position();
 }
@@ -1009,10 +1065,19 @@ static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size
 		read_frame_header(br, f->im, &f->fh, true, f->allow_lf_frame, f->allow_patches);
 		if (uint32_t e = sequence_refusal(f->fh, f->seq_blend, rendered_alpha_channel(f->im), f->allow_lf_frame, f->im.xyb_encoded, f->allow_modular_lf, f->allow_patches, f->allow_modular_ref)) raise(e);
 	} else {
-		read_image_header(br, &f->im, f->allow_wide);
-		read_frame_header(br, f->im, &f->fh);
+		read_image_header(br, &f->im, f->allow_wide, f->allow_upsampling);
+		read_frame_header(br, f->im, &f->fh, false, false, false, f->allow_upsampling);
 		J40HIP_SHOULD(f->fh.is_last, "TODO");
 		J40HIP_SHOULD(f->fh.type == 0, "TODO");
+	}
+	if (f->fh.upsampling > 1) {   // the frame's table: the stream's own for its K first, else what the application supplied
+		const int t = up_table_index(f->fh.upsampling);
+		if (f->im.cw_mask >> t & 1) f->up_table = f->im.up_weights[t];
+		else J40HIP_SHOULD(get_upsampling_defaults(f->fh.upsampling, &f->up_table), "updf");
+		// (an LF-only parse: the LF image of such a frame is not its 1:8 preview)
+		J40HIP_SHOULD(!f->lf_only, "TODO");
+		// (the stretch is of XYB planes, like noise; a YCbCr frame parses and its plan is refused by the route)
+		J40HIP_SHOULD(f->im.xyb_encoded || f->fh.do_ycbcr, "TODO");
 	}
 	// an image with 32-bit Modular buffers: its Modular frames only, and only where they were asked for (its VarDCT frames would need wide LF,
 	// HF-metadata and extra-channel streams; the reference's word for the combination is TODO as well, j40.h:7868)

@@ -22,6 +22,7 @@ inline bool alpha_env() { static const bool v = [] { const char *e = env_str("J4
 inline bool orient_env() { static const bool v = [] { const char *e = env_str("J40HIP_ORIENT"); return e && atoi(e) > 0; }(); return v; }
 // J40HIP_YCBCR=1: YCbCr VarDCT frames (recompressed JPEGs) are served where j40hip_frame_set_ycbcr(f, 1) would be taken (include/j40hip.h); read once
 inline bool noise_env() { return env_on("J40HIP_NOISE", false); }   // (read at every parse)
+inline bool upsampling_env() { return env_on("J40HIP_UPSAMPLING", false); }   // J40HIP_UPSAMPLING=1: every parse asks for upsampling (J40HIP_PARSE_UPSAMPLING); read at every parse
 inline bool wide_env() { static const bool v = [] { const char *e = env_str("J40HIP_WIDE"); return e && atoi(e) > 0; }(); return v; }
 inline bool modular_xyb_env() { static const bool v = [] { const char *e = env_str("J40HIP_MODULAR_XYB"); return e && atoi(e) > 0; }(); return v; }
 // J40HIP_RESTORATION: 0 off (the default), 1 the filters a frame signals, 2 (`j40`) as j40's routines stand; read once
@@ -67,6 +68,10 @@ struct ImageMeta {
 	float opsin_bias[3];
 	float quant_bias[3];
 	float quant_bias_num = 0.145f;
+	// custom upsampling weights (read with the upsampling switch only, else a non-zero mask is "TODO"): bit 0 of cw_mask: up_weights[0] holds
+	// the 15 up2_weight, bit 1: [1] the 55 up4_weight, bit 2: [2] the 210 up8_weight, each as its F16 reads (device/upsample_dev.h)
+	int32_t cw_mask = 0;
+	std::vector<float> up_weights[3];
 };
 
 struct FrameHeader {
@@ -91,6 +96,19 @@ struct FrameHeader {
 	int32_t x_qm_scale = 3, b_qm_scale = 2;
 	int32_t num_passes = 1;
 	int32_t x0 = 0, y0 = 0, width = 0, height = 0;
+	// Upsampling (read with the upsampling switch only, else anything but 1 is "TODO"; device/upsample_dev.h has the rule): upsampling = K,
+	// 1, 2, 4 or 8. width and height above are the CODED size, ceil(shown / K) -- what groups, LF groups, the TOC, varblocks, Modular
+	// channels and the filters work on --; up_width and up_height the SHOWN size, what the header states and a decode writes. K = 1: the
+	// two agree (a header that was not parsed, a plan view's, has up_width = 0: shown_width() answers for both).
+	// WHICH SIZE A READER WANTS: whatever works on coded samples -- groups, sections, varblocks, LF cells, Modular channels, the filters,
+	// the planes ahead of k_upsample -- reads width and height (coded_width() says so out loud); whatever speaks of the picture -- the
+	// output, its staging images, the region, the scale, the orientation, the tails -- reads shown_width() and shown_height().
+	int32_t upsampling = 1, up_width = 0, up_height = 0;
+	std::vector<int32_t> ec_upsampling;   // every extra channel's
+	int32_t shown_width() const { return up_width > 0 ? up_width : width; }
+	int32_t shown_height() const { return up_height > 0 ? up_height : height; }
+	int32_t coded_width() const { return width; }
+	int32_t coded_height() const { return height; }
 	// how the frame goes onto the canvas (j40.h:5297-5336). The reference reads these and drops them; frame sequences (capi.hpp: j40hip_sequence) keep them
 	struct Blend { int8_t mode = 0, alpha_chan = 0, clamp = 0, src_ref = 0; };
 	Blend blend;                          // the colour channels'
@@ -263,6 +281,11 @@ struct Frame {
 	// or 3) of an image with xyb_encoded = 1. Set before parse_frame. (device/noise_dev.h has the rule.)
 	bool allow_noise = false;
 	float noise_lut[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	// Upsampling is asked for (J40HIP_PARSE_UPSAMPLING, or J40HIP_UPSAMPLING=1): custom weights in the image header and a frame header with
+	// upsampling > 1 are parsed instead of refused with "TODO". up_table: the 15 / 55 / 210 weights of the frame's K, copied at parse from
+	// the stream's custom table for that K, else from the process-wide defaults (set_upsampling_defaults); neither: "updf". Empty for K = 1.
+	bool allow_upsampling = false;
+	std::vector<float> up_table;
 	bool wide() const { return !im.modular_16bit_buffers; }
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
@@ -271,7 +294,7 @@ struct Frame {
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
 		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr; g.allow_wide = allow_wide; g.allow_lf_frame = allow_lf_frame; g.allow_modular_lf = allow_modular_lf;
-		g.allow_patches = allow_patches; g.allow_modular_ref = allow_modular_ref; g.allow_noise = allow_noise;
+		g.allow_patches = allow_patches; g.allow_modular_ref = allow_modular_ref; g.allow_noise = allow_noise; g.allow_upsampling = allow_upsampling;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section
@@ -286,7 +309,11 @@ void extract_codestream(const uint8_t *data, size_t size, const uint8_t **cs, si
 
 // signature, image metadata and ICC profile of a codestream: everything in front of the first frame header. *first_frame: the byte
 // the first frame header starts at
-void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame, bool allow_wide = false);
+void parse_image_header(const uint8_t *cs, size_t cs_size, ImageMeta *im, size_t *first_frame, bool allow_wide = false, bool allow_upsampling = false);
+// The standard's default upsampling weights, which nothing here holds: the application supplies them once (j40hip_set_upsampling_defaults).
+// Process-wide, behind a mutex. set: false for a k other than 2, 4, 8 or an n other than 15, 55, 210; get: false while none were supplied
+bool set_upsampling_defaults(int32_t k, const float *w, int32_t n);
+bool get_upsampling_defaults(int32_t k, std::vector<float> *out);
 // header and TOC of the frame that starts at byte `offset` of the codestream, for a sequence's index: nothing behind the TOC is
 // read. The TOC's offsets count from `offset`. Raises what the header or the TOC raise, "TODO" for what sequence_refusal refuses.
 // blend: the sequence serves the blend modes other than Replace, lf_frames: and LF frames (sequence_refusal).

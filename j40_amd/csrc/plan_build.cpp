@@ -828,6 +828,7 @@ uint32_t alpha_keep_scope(const Frame &fr, int32_t *index) {
 	// the extra channels in the pass-group sections of a single pass, no transform over the frame-wide image
 	if (fr.lf_only || fr.toc.single || fr.fh.num_passes != 1 || fr.num_gm_channels != 0 || fr.gmodular.nb_meta_channels != 0) return ERR_TODO;
 	if (!fr.gmodular.transforms.empty() || fr.gmodular.channel.size() != fr.im.ec.size() || fr.gmodular.channel.size() > (size_t) MOD_MAX_CHANNELS) return ERR_TODO;
+	for (const Plane &p : fr.gmodular.channel) if (p.hshift || p.vshift) return ERR_TODO;   // (an extra channel coarser than the frame, ec_upsampling: decoded at its own size, dropped only)
 	return 0;
 }
 
@@ -869,7 +870,19 @@ uint32_t build_trailer_plan(const Frame &fr, const uint8_t *cs, size_t cs_size, 
 		const Section &ps = fr.toc.single ? fr.toc.single_section : fr.toc.pass_groups[(size_t) idx];
 		const GroupInfo gi = group_info(fr.fh, g);
 		Modular m; m.bpp = fr.im.bpp;
-		for (int32_t c = fr.num_gm_channels; c < nch; ++c) { Plane p; p.width = gi.gw; p.height = gi.gh; m.channel.push_back(p); }
+		for (int32_t c = fr.num_gm_channels; c < nch; ++c) {
+			// (a channel coarser than the frame, ec_upsampling above upsampling: the group's rectangle shifted down, as build_modular_plan cuts a squeezed channel)
+			const Plane &fp = gm.channel[(size_t) c];
+			Plane p; p.width = gi.gw; p.height = gi.gh;
+			if (fp.hshift > 0 || fp.vshift > 0) {
+				if (keep) return ERR_TODO;   // (alpha_keep_scope refuses such a frame)
+				const int32_t dim = 1 << fr.fh.group_size_shift, left = (g % fr.fh.gcolumns) * dim, top = (g / fr.fh.gcolumns) * dim;
+				p.width = std::min(dim >> fp.hshift, fp.width - (left >> fp.hshift)); p.height = std::min(dim >> fp.vshift, fp.height - (top >> fp.vshift));
+				p.hshift = fp.hshift; p.vshift = fp.vshift;
+				if (p.width <= 0 || p.height <= 0) return ERR_TODO;   // (cannot happen: ceil(shown / E) reaches every group of ceil(shown / K))
+			}
+			m.channel.push_back(p);
+		}
 		const size_t start = (size_t) end_bits[idx];
 		if (start < 8 * ps.offset || start > 8 * (ps.offset + ps.size)) { trailer_errors->push_back({idx, E4("shrt")}); continue; }
 		BitReader br(cs + ps.offset, ps.size);

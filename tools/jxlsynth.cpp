@@ -183,6 +183,23 @@ static std::vector<uint32_t> g_tone;
 // f16 holds exactly, or `h` and four hex digits: the f16's bits as they are (h7c00: an infinity, which decoders refuse as well)
 static std::vector<uint32_t> g_opsin;
 static int g_cw_mask = 0;
+// upsampling=2|4|8 (vardct, and modular with xyb=1; a single frame): the frame header says upsampling = K and every extra channel's
+// ec_upsampling = K. The positional size stays the CODED one; the image header states the SHOWN size, upshown=W,H (default K * coded),
+// which must satisfy coded = ceil(shown / K).
+//   upweights=nearest|default|V,V,...: the K's custom weight table in the image header (default_m = 0, the mask bit of that K, 15 / 55 /
+//     210 F16). nearest: M[i][j] = 1 where i % 5 == 2 && j % 5 == 2, else 0 -- every output is its coded sample; a list: the packed upper
+//     triangle, each value rounded to F16; default: no table (a decoder takes the standard's). A stream with a table writes the transform
+//     block out: opsin='s values, else the format's defaults rounded to F16.
+//   uptwin=1: the same coded frame with upsampling = 1, the coded size in the image header and no table (its transform block as above,
+//     so that both streams render alike).
+//     uptwin=2: the twin keeps the table (custom weights in an image whose frame has upsampling = 1).
+//   ecup=1|2|4|8: the extra channels' ec_upsampling says this instead of K (streams a decoder refuses: "usmp" below K, "TODO" above)
+struct UpRole { int k = 1, shown_w = 0, shown_h = 0, twin = 0, ecup = 0; bool block = false; std::vector<uint32_t> table; };
+static UpRole g_up;
+static bool up_flag() { return g_up.k > 1 && !g_up.twin; }
+static int up_log_of(int k) { return k == 2 ? 1 : k == 4 ? 2 : k == 8 ? 3 : 0; }
+static int up_log() { return up_flag() ? up_log_of(g_up.k) : 0; }
+static int up_ec_log() { return g_up.ecup ? up_log_of(g_up.ecup) : up_log(); }   // (ecup= holds for a twin too: ec_upsampling beside upsampling = 1)
 // cenc=1 and its family (every mode): ColourEncoding written out instead of all_default -- RGB, no ICC profile, then white=N (1 D65, 2 custom
 // with whitexy=X,Y, 10 E, 11 DCI), primaries=N (1 sRGB, 2 custom with primxy=RX,RY,GX,GY,BX,BY, 9 BT.2100, 11 P3), gamma=G (have_gamma, G in
 // units of 1e-7) or tf=N (1 BT.709, 2 unknown, 8 linear, 13 sRGB, 16 PQ, 17 DCI, 18 HLG), intent=N. The xy values are integers of 1e-6. Any
@@ -387,6 +404,22 @@ static uint32_t f16_bits(float v) {
 	if (e <= 0 || e >= 31 || (mant & 0x1fff)) die("f16: value not exactly representable");
 	return sign << 15 | (uint32_t) e << 10 | mant >> 13;
 }
+// the nearest f16 (ties to even) of a value within the normal range, or of zero (upweights=, and the default transform beside it)
+static uint32_t f16_round_bits(float v) {
+	if (v == 0.0f) return 0;
+	uint32_t u; memcpy(&u, &v, 4);
+	const uint32_t sign = u >> 31;
+	uint32_t mag = u & 0x7fffffffu;
+	if (mag < 0x38800000u) {   // below 2^-14: the subnormals' step, 2^-24
+		const float a = v < 0 ? -v : v;
+		const uint32_t q = (uint32_t) lrintf(a * 16777216.0f);   // (ties to even in the default rounding mode)
+		return sign << 15 | q;   // (q = 1024 is the smallest normal: the bit pattern carries over)
+	}
+	mag += 0xfffu + (mag >> 13 & 1);   // round the 13 dropped bits, ties to even
+	const int e = (int) (mag >> 23) - 127 + 15;
+	if (e >= 31) die("f16: value out of range");
+	return sign << 15 | (uint32_t) e << 10 | (mag >> 13 & 0x3ff);
+}
 
 // ... and what they add behind ColourEncoding: ToneMapping (j40.h:3270-3286), all_default unless tone= is given
 static void write_tone_mapping(BitWriter &cs) {
@@ -401,10 +434,18 @@ static void write_tone_mapping(BitWriter &cs) {
 // either case default_m, and with opsin=: the 16 values (in an XYB image only, as the format says) and cw_mask
 static void write_header_tail(BitWriter &cs, bool metadata, bool xyb) {
 	if (metadata) { write_tone_mapping(cs); cs.put(0, 2); }   // extensions
-	if (g_opsin.empty()) { cs.put(1, 1); return; }            // default_m
+	if (g_opsin.empty() && !g_up.block) { cs.put(1, 1); return; }            // default_m
 	cs.put(0, 1);
-	if (xyb) for (size_t i = 0; i < 16; ++i) cs.put(g_opsin[i], 16);
-	cs.put((uint64_t) g_cw_mask, 3);
+	if (xyb && !g_opsin.empty()) for (size_t i = 0; i < 16; ++i) cs.put(g_opsin[i], 16);
+	else if (xyb) {   // (upweights=: the format's default transform, as F16 holds it)
+		static const float DEFAULTS[16] = {11.031566901960783f, -9.866943921568629f, -0.16462299647058826f, -3.254147380392157f, 4.418770392156863f, -0.16462299647058826f,
+			-3.6588512862745097f, 2.7129230470588235f, 1.9459282392156863f, -0.0037930732552754493f, -0.0037930732552754493f, -0.0037930732552754493f,
+			1.0f - 0.05465007330715401f, 1.0f - 0.07005449891748593f, 1.0f - 0.049935103337343655f, 0.145f};
+		for (float v : DEFAULTS) cs.put(f16_round_bits(v), 16);
+	}
+	const int up_bit = (up_flag() || g_up.twin == 2) && !g_up.table.empty() ? g_up.k >> 1 : 0;   // (K = 2: bit 0, 4: bit 1, 8: bit 2)
+	cs.put((uint64_t) (g_cw_mask | up_bit), 3);
+	if (up_bit) for (uint32_t v : g_up.table) cs.put(v, 16);
 }
 
 // dq=1: the dequantisation matrices of HfGlobal in their coded forms (j40.h:4696-4760) instead of "all default": band
@@ -603,7 +644,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	const int jpeg_upsampling = subsampling == "420" ? 4 : subsampling == "422" ? 8 : subsampling == "440" ? 12 : 0;
 	const int dct8only = jpeg ? 1 : opt.geti("dct8only", subsampled ? 1 : 0), fixed_hfmul = jpeg ? 1 : opt.geti("hfmul", 0), nocfl = jpeg ? 1 : opt.geti("nocfl", 0), flatchroma = opt.geti("flatchroma", 0);
 	if (fixed_hfmul < 0 || fixed_hfmul > 256) die("vardct: hfmul=1..256");
-	const int nonzero_header = opt.geti("fullheader", (num_passes > 1 || ycbcr || g_noise) ? 1 : 0);
+	const int nonzero_header = opt.geti("fullheader", (num_passes > 1 || ycbcr || g_noise || g_up.k > 1) ? 1 : 0);   // (upsampling=: the twin's header too)
 	const int x_qm = opt.geti("xqm", 3), b_qm = opt.geti("bqm", 2);
 	const int skip_smooth = jpeg ? 1 : opt.geti("nosmooth", subsampled ? 1 : 0);
 	const int small_clusters = opt.geti("simpleclusters", 0); // <= 8 clusters: simple cluster-map form
@@ -1065,11 +1106,21 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		}
 		for (int g = 0; g < num_groups; ++g) {
 			const int gx = (g % gcols) * 256, gy = (g / gcols) * 256, gw = std::min(256, W - gx), gh = std::min(256, H - gy);
-			std::vector<Channel> sub((size_t) num_ec, Channel(gw, gh));
-			for (int y = 0; y < gh; ++y) for (int x = 0; x < gw; ++x) {
-				for (int k = 0; k < ec_extra; ++k) sub[(size_t) k].at(x, y) = (((((gx + x) >> 3) * (k + 2) + ((gy + y) >> 2)) & 31) * emax) / 31;
-				sub[(size_t) ec_extra].at(x, y) = alpha.at(gx + x, gy + y);
+			// (ecup= above the frame's upsampling: the extra channels are coded 1 << es times coarser than the frame, ceil(shown / ecup)
+			// samples an axis, and a group holds the rectangle of its own shifted down by es)
+			const int eff_k = up_flag() ? g_up.k : 1, eff_w = up_flag() ? g_up.shown_w : W, eff_h = up_flag() ? g_up.shown_h : H;
+			// (eight times coarser: such samples would belong to the LfGroup sections; the header says so and the channels stay as they are -- a stream decoders refuse at the header)
+			const int es = g_up.ecup > eff_k && g_up.ecup < 8 * eff_k ? up_log_of(g_up.ecup) - up_log_of(eff_k) : 0;
+			const int ecw = es ? (eff_w + g_up.ecup - 1) / g_up.ecup : W, ech = es ? (eff_h + g_up.ecup - 1) / g_up.ecup : H;
+			if (es && ecw <= 256 && ech <= 256) die("vardct: ecup=: the coarser extra channels would fit one group and belong to LfGlobal, which this writer leaves empty; take a larger frame");
+			const int sx0 = gx >> es, sy0 = gy >> es, sw = std::min(256 >> es, ecw - sx0), sh = std::min(256 >> es, ech - sy0);
+			std::vector<Channel> sub((size_t) num_ec, Channel(sw, sh));
+			for (int y = 0; y < sh; ++y) for (int x = 0; x < sw; ++x) {
+				const int fx = std::min(W - 1, (sx0 + x) << es), fy = std::min(H - 1, (sy0 + y) << es);
+				for (int k = 0; k < ec_extra; ++k) sub[(size_t) k].at(x, y) = ((((fx >> 3) * (k + 2) + (fy >> 2)) & 31) * emax) / 31;
+				sub[(size_t) ec_extra].at(x, y) = alpha.at(fx, fy);
 			}
+			(void) gw; (void) gh;
 			alpha_enc.emplace_back(gspec);
 			if (!gspec.lz77) for (int c = 0; c < num_ec; ++c) encode_channel(tree, sub, c, 1 + 3 * num_lf_groups + 17 + g, wp_in(200 + g), alpha_enc.back());
 			else {
@@ -1463,7 +1514,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	if (vd_wide && img_bpp == 8 && !with_alpha) die("vardct: wide=1 wants metadata that is written out: bpp=9..15 or alpha=1");
 	if (!g_seq || g_seq->first) {
 	cs.put(0xff, 8); cs.put(0x0a, 8);
-	write_size_header(cs, g_seq ? g_seq->canvas_w : W, g_seq ? g_seq->canvas_h : H);
+	write_size_header(cs, g_seq ? g_seq->canvas_w : up_flag() ? g_up.shown_w : W, g_seq ? g_seq->canvas_h : up_flag() ? g_up.shown_h : H);   // (upsampling=: the shown size)
 	if (with_alpha && (img_bpp != 8 || ec_extra || alpha_bpp != 8 || alpha_assoc)) {
 		cs.put(0, 1);                       // ImageMetadata: not all_default
 		write_extra_fields(cs);             // no extra fields (an animation: its header)
@@ -1548,8 +1599,8 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		// (jpegup=N: the header says N whatever the stream holds -- a layout the decoder has to refuse before it reads anything of it)
 		if (ycbcr) cs.put((uint64_t) opt.geti("jpegup", jpeg_upsampling), 6);   // jpeg_upsampling (read with do_ycbcr)
 		if (!use_lf_frame) {                // (not coded with use_lf_frame, j40.h:5262)
-		cs.put(0, 2);                       // log_upsampling
-		for (int i = 0; i < num_ec; ++i) cs.put(0, 2);   // ec_log_upsampling
+		cs.put((uint64_t) up_log(), 2);     // log_upsampling (upsampling=)
+		for (int i = 0; i < num_ec; ++i) cs.put((uint64_t) up_ec_log(), 2);   // ec_log_upsampling
 		}
 		if (!noxyb) { cs.put((uint64_t) x_qm, 3); cs.put((uint64_t) b_qm, 3); }
 		if (seq_type == 2 && num_passes != 1) die("vardct: a reference-only frame codes no passes: passes=1");
@@ -2296,7 +2347,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	if (g_seq && (opt.geti("icc", 0) || repeat > 1)) die("modular: frames= does not combine with icc or repeat");
 	if (!g_seq || g_seq->first) {
 	cs.put(0xff, 8); cs.put(0x0a, 8);
-	write_size_header(cs, g_seq ? g_seq->canvas_w : Wfull, g_seq ? g_seq->canvas_h : Hfull);
+	write_size_header(cs, g_seq ? g_seq->canvas_w : up_flag() ? g_up.shown_w : Wfull, g_seq ? g_seq->canvas_h : up_flag() ? g_up.shown_h : Hfull);   // (upsampling=: the shown size)
 	cs.put(0, 1);                       // ImageMetadata: not all_default
 	write_extra_fields(cs);             // no extra fields (an animation: its header)
 	write_bit_depth(cs, bpp);
@@ -2350,8 +2401,8 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	cs.u64((patch_flag() ? 2 : 0) | (noise_flag() ? 1 : 0));       // flags
 	if (!flag_xyb) cs.put(flag_ycbcr ? 1 : 0, 1);   // do_ycbcr
 	if (!flag_xyb && flag_ycbcr) cs.put(0, 6);      // jpeg_upsampling: none
-	cs.put(0, 2);                       // log_upsampling
-	for (int k = 0; k < extra + (alpha ? 1 : 0); ++k) cs.put(0, 2);   // extra channel upsampling
+	cs.put((uint64_t) up_log(), 2);     // log_upsampling (upsampling=)
+	for (int k = 0; k < extra + (alpha ? 1 : 0); ++k) cs.put((uint64_t) up_ec_log(), 2);   // extra channel upsampling
 	cs.put((uint64_t) (group_shift - 7), 2);
 	if (seq_type == 2 && num_passes != 1) die("modular: a reference-only frame codes no passes: passes=1");
 	if (seq_type != 2) cs.u32(num_passes, 1, 0, 2, 0, 3, 0, 4, 3);   // (not coded for a reference-only frame, j40.h:5276)
@@ -2758,6 +2809,32 @@ int main(int argc, char **argv) {
 		if (g_cw_mask < 0 || g_cw_mask > 7) die("cwmask=0..7");
 		for (const char *k : {"tone", "opsin", "cwmask"}) opt.kv.erase(k);
 	}
+	if (opt.kv.count("upsampling")) {
+		g_up.k = opt.geti("upsampling", 1);
+		if (g_up.k != 2 && g_up.k != 4 && g_up.k != 8) die("upsampling=2|4|8");
+		if (!vardct && !opt.geti("xyb", 0)) die("upsampling= belongs to the vardct mode and to Modular frames of an XYB image (xyb=1)");
+		for (const char *k : {"lflevels", "frames", "anim", "modes", "types", "patches"}) if (opt.kv.count(k)) die("upsampling= belongs to a single frame");
+		g_up.twin = opt.geti("uptwin", 0);
+		g_up.ecup = opt.geti("ecup", 0);
+		if (g_up.twin < 0 || g_up.twin > 2 || (g_up.ecup != 0 && g_up.ecup != 1 && g_up.ecup != 2 && g_up.ecup != 4 && g_up.ecup != 8)) die("uptwin=0|1|2, ecup=1|2|4|8");
+		g_up.shown_w = g_up.k * W; g_up.shown_h = g_up.k * H;
+		if (opt.kv.count("upshown") && sscanf(opt.gets("upshown", "").c_str(), "%d,%d", &g_up.shown_w, &g_up.shown_h) != 2) die("upshown=W,H");
+		if ((g_up.shown_w + g_up.k - 1) / g_up.k != W || (g_up.shown_h + g_up.k - 1) / g_up.k != H) die("upshown=: the positional size must be ceil(shown / K)");
+		const std::string uw = opt.gets("upweights", "default");
+		const int n5 = 5 * g_up.k / 2, count = n5 * (n5 + 1) / 2;
+		if (uw == "nearest") {
+			for (int y = 0; y < n5; ++y) for (int x = y; x < n5; ++x) g_up.table.push_back(f16_bits(y % 5 == 2 && x % 5 == 2 ? 1.0f : 0.0f));
+		} else if (uw != "default") {
+			for (size_t at = 0; at < uw.size(); ) {
+				size_t e = uw.find(',', at); if (e == std::string::npos) e = uw.size();
+				g_up.table.push_back(f16_round_bits(strtof(uw.substr(at, e - at).c_str(), nullptr)));
+				at = e + 1;
+			}
+			if ((int) g_up.table.size() != count) die("upweights=: 15 values for upsampling=2, 55 for 4, 210 for 8");
+		}
+		g_up.block = !g_up.table.empty();
+		for (const char *k : {"upsampling", "uptwin", "upshown", "upweights", "ecup"}) opt.kv.erase(k);
+	} else if (opt.kv.count("uptwin") || opt.kv.count("upshown") || opt.kv.count("upweights")) die("uptwin=, upshown= and upweights= want upsampling=");
 	if (opt.kv.count("lflevels")) {
 		if (!vardct) die("lflevels= belongs to the vardct mode");
 		return run_lf_sequence(W, H, seed, argv[5], opt);
