@@ -13,7 +13,7 @@ CXXFLAGS += -DJ40_LANE_EV_FLUSH=$(EVENT_RING)
 HIPFLAGS = --offload-arch=$(ARCH) -std=c++17 -O3 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fvisibility=hidden -Wall -DJ40_LANE_EV_FLUSH=$(EVENT_RING) $(EXTRA_HIPFLAGS)
 SRC = j40_amd/csrc
 HOST_OBJS = build/obj/plan_build.o build/obj/plan_front.o build/obj/entropy.o build/obj/modular.o build/obj/tables.o build/obj/frame.o build/obj/capi_host.o build/obj/api.o
-DEV_OBJS = build/obj/kernels.o build/obj/modular_kernels.o build/obj/runtime.o build/obj/runtime_upload.o build/obj/runtime_lf.o build/obj/runtime_batch.o build/obj/runtime_lfp.o build/obj/runtime_debug.o build/obj/device_memory.o build/obj/pipeline.o build/obj/lf_tail_kernels.o build/obj/modular_coop.o build/obj/modular_quad.o build/obj/modular_split.o build/obj/lf_decode.o build/obj/plan_kernels.o build/obj/async.o build/obj/hostcopy.o build/obj/lf_preview.o build/obj/alpha_kernels.o build/obj/region_kernels.o build/obj/compose_kernels.o build/obj/runtime_seq.o build/obj/scale_kernels.o build/obj/ycbcr_kernels.o build/obj/orient_kernels.o build/obj/modular_xyb_kernels.o build/obj/colour_kernels.o build/obj/patch_kernels.o build/obj/noise_kernels.o build/obj/upsample_kernels.o
+DEV_OBJS = build/obj/kernels.o build/obj/modular_kernels.o build/obj/runtime.o build/obj/runtime_upload.o build/obj/runtime_lf.o build/obj/runtime_batch.o build/obj/runtime_lfp.o build/obj/runtime_debug.o build/obj/device_memory.o build/obj/pipeline.o build/obj/lf_tail_kernels.o build/obj/modular_coop.o build/obj/modular_quad.o build/obj/modular_split.o build/obj/lf_decode.o build/obj/plan_kernels.o build/obj/async.o build/obj/hostcopy.o build/obj/lf_preview.o build/obj/alpha_kernels.o build/obj/region_kernels.o build/obj/compose_kernels.o build/obj/runtime_seq.o build/obj/scale_kernels.o build/obj/ycbcr_kernels.o build/obj/orient_kernels.o build/obj/modular_xyb_kernels.o build/obj/colour_kernels.o build/obj/patch_kernels.o build/obj/noise_kernels.o build/obj/upsample_kernels.o build/obj/spline_kernels.o
 
 .PHONY: all lib tools oracle hostsim clean print-objs
 all: lib tools hostsim oracle
@@ -57,8 +57,10 @@ PATCHSIM = $(if $(wildcard tests/hostsim/patch_sim.cpp),build/libhostsim_patches
 PATCHMAIN = $(if $(wildcard tests/hostsim/patch_main.cpp),build/patch_main build/patch_main_san)
 NOISESIM = $(if $(wildcard tests/hostsim/noise_sim.cpp),build/libhostsim_noise.so)
 NOISEMAIN = $(if $(wildcard tests/hostsim/noise_main.cpp),build/noise_main build/noise_main_san)
+SPLINESIM = $(if $(wildcard tests/hostsim/spline_sim.cpp),build/libhostsim_splines.so)
+SPLINEMAIN = $(if $(wildcard tests/hostsim/spline_main.cpp),build/spline_main build/spline_main_san)
 UPSAMPLEMAIN = $(if $(wildcard tests/hostsim/upsample_main.cpp),build/upsample_main build/upsample_main_san)
-hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/libhostsim_compose.so build/libhostsim_blend.so build/libhostsim_scale.so build/libhostsim_ycbcr.so build/libhostsim_orient.so build/libhostsim_lfframe.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN) $(SCALEMAIN) $(YCBCRMAIN) $(ORIENTMAIN) $(WIDESIM) $(WIDEMAIN) $(MODXYBSIM) $(MODXYBMAIN) $(COLOURSIM) $(COLOURMAIN) $(PATCHSIM) $(PATCHMAIN) $(NOISESIM) $(NOISEMAIN) $(UPSAMPLEMAIN)
+hostsim: build/libhostsim.so build/libhostsim_ring8.so build/libhostsim_alpha.so build/libhostsim_region.so build/libhostsim_compose.so build/libhostsim_blend.so build/libhostsim_scale.so build/libhostsim_ycbcr.so build/libhostsim_orient.so build/libhostsim_lfframe.so build/liboracle_driver.so build/api_threads $(LAYOUTMAIN) $(SCALEMAIN) $(YCBCRMAIN) $(ORIENTMAIN) $(WIDESIM) $(WIDEMAIN) $(MODXYBSIM) $(MODXYBMAIN) $(COLOURSIM) $(COLOURMAIN) $(PATCHSIM) $(PATCHMAIN) $(NOISESIM) $(NOISEMAIN) $(UPSAMPLEMAIN) $(SPLINESIM) $(SPLINEMAIN)
 # test-only glue: parses a stream with the product's host parser, takes the plan view and hands it to
 # the CPU oracle (oracle/libj40oracle.so)
 build/liboracle_driver.so: tests/oracle_driver.c build/libj40hip.so oracle/hotpath_oracle.c include/j40hip.h
@@ -227,6 +229,19 @@ build/noise_main: $(NOISEMAIN_SRC) $(SRC)/device/noise_dev.h
 build/noise_main_san: $(NOISEMAIN_SRC) $(SRC)/device/noise_dev.h
 	@mkdir -p build
 	$(CXX) $(filter-out -fPIC -shared,$(HOSTSIM_FLAGS)) -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(NOISEMAIN_SRC)
+
+# splines on the CPU (tests/test_splines.py): device/spline_dev.h's dequantisation, binning and lane function over planes in host memory ...
+build/libhostsim_splines.so: tests/hostsim/spline_sim.cpp $(SRC)/device/spline_dev.h
+	@mkdir -p build
+	$(CXX) $(HOSTSIM_FLAGS) -o $@ tests/hostsim/spline_sim.cpp
+# ... and as a program of its own, plain and with the host sanitizers (an executable: never loaded into Python)
+SPLINEMAIN_SRC = tests/hostsim/spline_main.cpp tests/hostsim/spline_sim.cpp
+build/spline_main: $(SPLINEMAIN_SRC) $(SRC)/device/spline_dev.h
+	@mkdir -p build
+	$(CXX) $(filter-out -fPIC -shared,$(HOSTSIM_FLAGS)) -o $@ $(SPLINEMAIN_SRC)
+build/spline_main_san: $(SPLINEMAIN_SRC) $(SRC)/device/spline_dev.h
+	@mkdir -p build
+	$(CXX) $(filter-out -fPIC -shared,$(HOSTSIM_FLAGS)) -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(SPLINEMAIN_SRC)
 
 # upsampling on the CPU (tests/test_upsampling.py): device/upsample_dev.h's rule and tile functions as a program of its own, plain and with
 # the host sanitizers (an executable: never loaded into Python; the library's j40hip_kat_host_upsample is the same code for the tests' numpy)

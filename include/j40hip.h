@@ -72,7 +72,7 @@ J40HIP_API void j40hip_frame_free(j40hip_frame *f);
 #define J40HIP_PARSE_WIDE 8u
 /* flags & J40HIP_PARSE_NOISE: photon noise is asked for. PARITY UNPINNED: the reference stops at has_noise (j40.h:6264, "TODO"), and so
  * does every parse without this flag. With it a frame whose header has has_noise is parsed -- its eight NoiseParameters follow the patch
- * dictionary in LfGlobal (splines, which would stand between them, stay "TODO") -- and every decode of the frame adds the noise to the
+ * dictionary in LfGlobal (behind the splines, where the frame has them: J40HIP_PARSE_SPLINES) -- and every decode of the frame adds the noise to the
  * frame's XYB samples behind the restoration filters and the patches, ahead of the colour tail (k_noise_fill, k_noise_add;
  * j40_amd/csrc/device/noise_dev.h states the rule). "TODO" at parse even with the flag: an image with xyb_encoded = 0; an LF frame or a
  * reference-only frame (type 1 or 2) with has_noise. A frame with noise decodes whole frames at full size: a region or a scale is cut
@@ -83,6 +83,22 @@ J40HIP_API void j40hip_frame_free(j40hip_frame *f);
  * sequence get the seed counters of their place in it (visible: the shown frames before it, nonvisible: the frames since the last
  * shown one); a stand-alone handle has both 0. */
 #define J40HIP_PARSE_NOISE 256u
+/* flags & J40HIP_PARSE_SPLINES: splines are asked for. PARITY UNPINNED: the reference stops at has_splines (j40.h:6263, "TODO"), and so
+ * does every parse without this flag. With it a frame whose header has has_splines is parsed -- the splines follow the patch dictionary
+ * in LfGlobal, ahead of the noise parameters: one entropy-coded stream over six contexts -- and every decode of the frame draws them
+ * onto the frame's XYB samples behind the restoration filters and the patches, ahead of the noise and the colour tail (k_spline_draw;
+ * j40_amd/csrc/device/spline_dev.h states the rule). A damaged spline stream is "spln": more splines than min(1 << 24, W * H / 4), more
+ * control points than min(1 << 20, W * H / 2), a starting or control-point coordinate of magnitude above 1 << 23, two successive
+ * control points that are equal, more than 1 << 22 segments (counted along the curves, before any is dropped), more than 1 << 24
+ * (tile, segment) pairs; at parse for a handle, at j40hip_sequence_open for a frame of a sequence. "TODO" at parse even with the flag:
+ * an image with xyb_encoded = 0; an LF frame or a reference-only frame (type 1 or 2) with has_splines; an LF-only parse. A frame with
+ * splines decodes as one with noise does: whole frames at full size, from which a region is cut and a scale averaged; the orientation,
+ * kept alpha, the restoration filters, the colour mode, patches and noise combine with it; a Modular frame needs the Modular XYB
+ * switch; a YCbCr plan, a group range, a batch, a pipeline, the LF preview and a frame that is upsampled as well are "TODO". A frame
+ * whose segments all drop launches nothing. J40HIP_SPLINES=1 in the environment does the same for every parse, and
+ * j40hip_sequence_open takes the flag too (J40HIP_SEQ_SPLINES). */
+#define J40HIP_PARSE_SPLINES 1024u
+#define J40HIP_SEQ_SPLINES 1024u
 /* flags & J40HIP_PARSE_UPSAMPLING: upsampling is asked for. PARITY UNPINNED: the reference refuses a frame header with upsampling or an
  * ec_upsampling other than 1 (j40.h:3297-3306, 5244-5249) and custom upsampling weights in the image header (j40.h:3638) with "TODO", and so
  * does every parse without this flag. With it the custom weights are read and kept, and a frame coded at 1:2, 1:4 or 1:8
@@ -612,6 +628,9 @@ J40HIP_API int j40hip_frame_sharpness(const j40hip_frame *f, int64_t gg, int16_t
  * ones ([3][height][width] floats); 2 the reciprocal-sigma plane of the edge-preserving filter (w8*h8 floats, < 0: the cell is skipped).
  * Stage 3, after any decode of a frame with patches (J40HIP_SEQ_PATCHES): the planes after k_patch_blend, as the tail read them */
 J40HIP_API uint32_t j40hip_frame_read_xyb(j40hip_frame *f, int stage, float *out);
+/* Stage 6, after any decode of a frame with splines (J40HIP_PARSE_SPLINES) and without noise: the planes after k_spline_draw, as the tail
+ * read them. With noise as well stage 6 answers "rnge" and stage 4 has the planes after both. With patches as well stage 3 answers with the
+ * planes between k_patch_blend and k_spline_draw, which such a decode copies before the splines are drawn (with or without noise). */
 /* Stage 4, after any decode of a frame with noise (J40HIP_PARSE_NOISE): the planes after k_noise_add, as the tail read them. For a
  * frame with both patches and noise stage 3 answers "rnge": the patched planes are noised in place, what stood between the two is gone.
  * A frame whose LUT is all zeros answers stage 4 with the planes the tail read. */
@@ -735,6 +754,26 @@ J40HIP_API void j40hip_sequence_frame_lf(const j40hip_sequence *s, int64_t k, in
 /* debug read-back (synchronises the device): plane c (0 X, 1 Y, 2 B) of LF slot `level` - 1 as the playback last filled it, tightly
  * packed floats of the LF frame's size. "rnge": no such slot, or nothing stored in it since the last rewind. */
 J40HIP_API uint32_t j40hip_sequence_read_lf_slot(j40hip_sequence *s, int32_t level, int32_t c, float *out);
+/* ---- splines (J40HIP_PARSE_SPLINES above) ----
+ * j40hip_frame_splines: has_splines of the frame's header; num_splines, quant_adjust (optional): as parsed.
+ * j40hip_frame_spline: spline i as the stream holds it -- start2: its starting point, num_points: its further control points, deltas:
+ * up to `cap` of their 2 * num_points double deltas (x and y in turn), coef128: the coefficients [4][32] of X, Y, B and sigma. "rnge": no
+ * such spline. j40hip_frame_spline_segments: the number of segments the next decode draws, up to `cap` of them copied to `out` -- 12
+ * 4-byte words each: x0, x1, y0, y1 (int32, the box, inclusive), cx, cy, 1 / sigma, sigma * multiplier / 4, colour X, Y, B (float), a pad.
+ * j40hip_frame_spline_bins: out2[0] the 64 x 32 tiles the segments touch, out2[1] the (tile, segment) pairs.
+ * launches: how often decodes of the handle have launched k_spline_draw. j40hip_frame_spline_ms: with J40HIP_SPLINE_TIMING=1 in the
+ * environment the kernel's device time in the last decode, which then waits for it; else 0. */
+J40HIP_API int j40hip_frame_splines(const j40hip_frame *f, int32_t *num_splines, int32_t *quant_adjust);
+J40HIP_API uint32_t j40hip_frame_spline(const j40hip_frame *f, int64_t i, int64_t *start2, int32_t *num_points, int64_t *deltas, int64_t cap, int32_t *coef128);
+J40HIP_API int64_t j40hip_frame_spline_segments(const j40hip_frame *f, void *out, int64_t cap);
+J40HIP_API void j40hip_frame_spline_bins(const j40hip_frame *f, int64_t *out2);
+J40HIP_API int64_t j40hip_frame_spline_launches(const j40hip_frame *f);
+J40HIP_API float j40hip_frame_spline_ms(const j40hip_frame *f);
+/* known-answer / measuring hook: k_spline_draw alone. planes_dev: three planes (X, Y, B) of width x height floats, one behind the other,
+ * changed in place; segments: n records of 12 words in host memory, in drawing order, every box inside the frame ("rnge": one is not),
+ * binned here as the parse bins a frame's. tiles_out (optional): the tiles launched. No segments launch nothing. ms (optional): the
+ * kernel's device time. Enqueued on `stream` and waited for. */
+J40HIP_API uint32_t j40hip_kat_device_splines(float *planes_dev, int32_t width, int32_t height, const void *segments, int64_t n, int64_t *tiles_out, void *stream, float *ms);
 /* ---- photon noise (J40HIP_PARSE_NOISE above) ----
  * j40hip_frame_noise: has_noise of the frame's header; lut8 (optional): the eight NoiseParameters / 1024, seeds2 (optional): the seed
  * counters visible, nonvisible the next decode uses. launches: how often decodes of the handle have launched the two kernels.

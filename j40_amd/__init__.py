@@ -24,6 +24,7 @@ J40_U8X4 = 0x0F33
 J40_U16X4 = 0x0F35
 PARSE_LF_ONLY = 2   # J40HIP_PARSE_LF_ONLY (include/j40hip.h): the LF preview's parse
 PARSE_YCBCR = 4     # J40HIP_PARSE_YCBCR: YCbCr frames are asked for (a subsampled one is parsed instead of refused)
+PARSE_SPLINES = 1024   # J40HIP_PARSE_SPLINES / J40HIP_SEQ_SPLINES: splines are asked for (a frame with has_splines is parsed and its splines drawn instead of "TODO"); j40hip_sequence_open takes it too
 PARSE_NOISE = 256   # J40HIP_PARSE_NOISE: photon noise is asked for (a frame with has_noise is parsed and its noise added instead of "TODO"); j40hip_sequence_open takes it too
 PARSE_UPSAMPLING = 512   # J40HIP_PARSE_UPSAMPLING: upsampling is asked for (custom weights and a frame coded at 1:2, 1:4 or 1:8 are parsed and served instead of "TODO"); J40HIP_SEQ_UPSAMPLING is the same bit
 PARSE_WIDE = 8      # J40HIP_PARSE_WIDE: wide Modular frames are asked for (an image with 32-bit Modular buffers is parsed instead of "fm32")
@@ -136,6 +137,10 @@ def lib():
         "j40hip_kat_device_upsample": (u32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
         "j40hip_kat_host_upsample": (u32, [vp, i32, i32, i32, vp, i32, i32, vp, C.c_int]),
         "j40hip_frame_noise": (C.c_int, [vp, vp, vp]), "j40hip_frame_noise_launches": (i64, [vp]), "j40hip_frame_noise_ms": (None, [vp, vp]),
+        "j40hip_frame_splines": (C.c_int, [vp, vp, vp]), "j40hip_frame_spline": (u32, [vp, i64, vp, vp, vp, i64, vp]),
+        "j40hip_frame_spline_segments": (i64, [vp, vp, i64]), "j40hip_frame_spline_bins": (None, [vp, vp]),
+        "j40hip_frame_spline_launches": (i64, [vp]), "j40hip_frame_spline_ms": (C.c_float, [vp]),
+        "j40hip_kat_device_splines": (u32, [vp, i32, i32, vp, i64, vp, vp, vp]),
         "j40hip_kat_device_noise": (u32, [vp, i32, i32, i32, vp, C.c_float, C.c_float, u32, u32, vp, vp, vp]),
         "j40hip_sequence_frame_patches": (None, [vp, i64, vp]), "j40hip_sequence_frame_patch": (u32, [vp, i64, i64, vp]),
         "j40hip_sequence_ref_slot_size": (u32, [vp, i32, vp, vp]), "j40hip_sequence_read_ref_slot": (u32, [vp, i32, i32, vp]),
@@ -254,7 +259,7 @@ def from_file(path: str) -> Image:
     return img
 
 
-def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False, blend=False, noise=False, upsampling=False):
+def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False, blend=False, noise=False, upsampling=False, splines=False):
     """whole path through the public API; returns (err4, rgba ndarray or None): uint8 [h, w, 4], or uint16 with fmt=J40_U16X4.
     scale=1 / 2: the 1:2 / 1:4 image, ceil(h / s) x ceil(w / s), every sample the rounded mean of its cell of the full decode
     (Frame.set_scale); like alpha=True it goes through the thin C-ABI on device 0.
@@ -288,12 +293,14 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     through the thin C-ABI on device 0; it combines with every switch above (a sequence is opened with it).
     upsampling=True: a frame coded at 1:2, 1:4 or 1:8 (and custom upsampling weights) is served for this call whatever J40HIP_UPSAMPLING
     says (PARSE_UPSAMPLING; PARITY UNPINNED), through the thin C-ABI on device 0: the picture has the shown size. It combines with fmt,
-    scale, orient, modular_xyb (which a Modular frame needs) and colour; "TODO" with alpha=True and for every frame of a sequence."""
+    scale, orient, modular_xyb (which a Modular frame needs) and colour; "TODO" with alpha=True and for every frame of a sequence.
+    splines=True: a frame with splines (has_splines) is served for this call whatever J40HIP_SPLINES says (PARSE_SPLINES; PARITY UNPINNED),
+    through the thin C-ABI on device 0; it combines with every switch above but upsampling= (a sequence is opened with it)."""
     if lf_frames or patches:
         if alpha or ycbcr or wide or (patches and not lf_frames and orient):
             return "TODO", None
         try:
-            seq = Sequence(data, lf_frames=bool(lf_frames), modular_xyb=bool(modular_xyb), colour=bool(colour), patches=bool(patches), blend=bool(blend), noise=bool(noise))
+            seq = Sequence(data, lf_frames=bool(lf_frames), modular_xyb=bool(modular_xyb), colour=bool(colour), patches=bool(patches), blend=bool(blend), noise=bool(noise), splines=bool(splines))
         except J40Error as e:
             if e.code != "Usq?":
                 return e.code, None
@@ -317,9 +324,9 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
                 return e.code, None
             finally:
                 seq.close()
-    if alpha or scale or ycbcr or orient or wide or modular_xyb or colour or noise or upsampling:
+    if alpha or scale or ycbcr or orient or wide or modular_xyb or colour or noise or upsampling or splines:
         try:
-            fr = Frame(data, ycbcr=bool(ycbcr), wide=bool(wide), noise=bool(noise), upsampling=bool(upsampling))
+            fr = Frame(data, ycbcr=bool(ycbcr), wide=bool(wide), noise=bool(noise), upsampling=bool(upsampling), splines=bool(splines))
         except J40Error as e:
             return e.code, None
         try:
@@ -356,16 +363,17 @@ def decode(data: bytes, fmt=J40_U8X4, alpha=False, scale=0, ycbcr=False, orient=
     return err, out
 
 
-def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False, wide=False, colour=False, noise=False, upsampling=False):
+def decode_region(data: bytes, x, y, w, h, fmt=J40_U8X4, device=0, orient=False, wide=False, colour=False, noise=False, upsampling=False, splines=False):
     """rectangle (x, y, w, h) of the image through the thin C-ABI: returns (err4, ndarray [h, w, 4] or None), uint8 or uint16 with
     fmt=J40_U16X4 -- the crop of what decode() returns, decoded from the pass groups that cover it (Frame.set_region). The verdict is
     the one over the sections that were decoded, then the public API's look behind the frame.
     orient=True: (x, y, w, h) is a rectangle of the DISPLAYED picture -- the frame in the orientation its stream carries; it is mapped
     to stored coordinates (Frame.orient_rect) and the result is the crop of the oriented whole picture, [h, w, 4].
     wide=True, colour=True, noise=True: as decode()'s (a frame with noise: the crop of the full-size picture).
-    upsampling=True: as decode()'s; the rectangle lies in the shown-size picture and is cut from it."""
+    upsampling=True: as decode()'s; the rectangle lies in the shown-size picture and is cut from it.
+    splines=True: as decode()'s (the crop of the full-size picture)."""
     try:
-        fr = Frame(data, wide=bool(wide), noise=bool(noise), upsampling=bool(upsampling))
+        fr = Frame(data, wide=bool(wide), noise=bool(noise), upsampling=bool(upsampling), splines=bool(splines))
     except J40Error as e:
         return e.code, None
     try:
@@ -674,6 +682,33 @@ def kat_device_upsample(planes, k, weights, out_w=None, out_h=None, device=0, wa
     return ("", host[guard:guard + n].reshape(3, out_h, out_w).copy()) + ((float(ms.value),) if want_ms else ())
 
 
+def kat_device_splines(planes, segments, device=0, want_ms=False):
+    """k_spline_draw alone (j40hip_kat_device_splines): planes [3, h, w] float32 (X, Y, B), segments [n, 12] uint32 words as
+    Frame.spline_segments() gives them -> (err4, the planes after the splines or None, the tiles launched); with want_ms a fourth
+    entry, the kernel's device time in ms. The planes sit between guard floats, which must come back untouched (asserted here)"""
+    import torch
+    planes = np.ascontiguousarray(planes, np.float32)
+    _, h, w = planes.shape
+    segments = np.ascontiguousarray(segments, np.uint32).reshape(-1, 12)
+    dev = "cuda:%d" % device
+    guard = 64
+    buf = np.full(guard + planes.size + guard, 12345.0, np.float32)
+    buf[guard:guard + planes.size] = planes.ravel()
+    d_buf = torch.from_numpy(buf).to(dev)
+    tiles = C.c_int64(0)
+    ms = C.c_float(0.0)
+    torch.cuda.synchronize(dev)
+    with torch.cuda.device(dev):
+        code = err4(lib().j40hip_kat_device_splines(d_buf.data_ptr() + 4 * guard, w, h, segments.ctypes.data, segments.shape[0], C.byref(tiles), None, C.byref(ms) if want_ms else None))
+        torch.cuda.synchronize(dev)
+    host = d_buf.cpu().numpy()
+    assert (host[:guard] == 12345.0).all() and (host[-guard:] == 12345.0).all(), "k_spline_draw wrote outside the planes"
+    if code:
+        return (code, None, 0) + ((None,) if want_ms else ())
+    out = ("", host[guard:guard + planes.size].reshape(3, h, w).copy(), int(tiles.value))
+    return out + ((float(ms.value),) if want_ms else ())
+
+
 def kat_device_noise(planes, group_dim, lut, ytox, ytob, visible=0, nonvisible=0, device=0, want_ms=False):
     """k_noise_fill and k_noise_add alone (j40hip_kat_device_noise): planes [3, h, w] float32 (X, Y, B) -> (err4, the planes after the noise
     or None, the raw planes [3, h, w] the fill made -- zeros for a LUT of zeros, which launches nothing); with want_ms a fourth entry, the
@@ -726,7 +761,7 @@ def kat_device_restoration(planes, sharpness, hfmul_inv, r, mode=1, device=0):
 class Frame:
     """thin C-ABI (include/j40hip.h): host parse, plan upload, hot path on a HIP stream"""
 
-    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False, ycbcr=False, wide=False, noise=False, upsampling=False):
+    def __init__(self, data: bytes, threads: int = 4, lf_device=None, lf_only=False, ycbcr=False, wide=False, noise=False, upsampling=False, splines=False):
         """lf_device: a HIP device index -- the LfGroup streams are decoded there instead of on the host (j40hip_frame_parse_on).
         lf_only: parse what the LF preview needs and nothing more (J40HIP_PARSE_LF_ONLY): `data` may end at lf_end(); such a frame
         can only be previewed (decode_lf_to_host, decode_lf).
@@ -736,13 +771,15 @@ class Frame:
         with "fm32", and its Modular frame is decoded with int32 sample planes (wide())
         noise: photon noise is asked for (J40HIP_PARSE_NOISE; PARITY UNPINNED): a frame with has_noise is parsed instead of refused
         with "TODO" and every decode adds its noise (noise_params(), noise_launches(), read_xyb(4))
+        splines: splines are asked for (J40HIP_PARSE_SPLINES; PARITY UNPINNED): a frame with has_splines is parsed instead of refused
+        with "TODO" and every decode draws them (splines(), spline_segments(), spline_launches(), read_xyb(6)); "spln": a damaged one
         upsampling: upsampling is asked for (J40HIP_PARSE_UPSAMPLING; PARITY UNPINNED): custom upsampling weights and a frame coded at
         1:2, 1:4 or 1:8 are parsed instead of refused with "TODO"; width and height are the SHOWN size, which every decode writes
         (upsampling(), coded_size(), read_xyb(5))"""
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        flags = (PARSE_LF_ONLY if lf_only else 0) | (PARSE_YCBCR if ycbcr else 0) | (PARSE_WIDE if wide else 0) | (PARSE_NOISE if noise else 0) | (PARSE_UPSAMPLING if upsampling else 0)
+        flags = (PARSE_LF_ONLY if lf_only else 0) | (PARSE_YCBCR if ycbcr else 0) | (PARSE_WIDE if wide else 0) | (PARSE_NOISE if noise else 0) | (PARSE_UPSAMPLING if upsampling else 0) | (PARSE_SPLINES if splines else 0)
         if lf_device is None:
             self.h = L.j40hip_frame_parse_ex(self._buf, len(data), threads, flags, C.byref(err))
         else:
@@ -1113,6 +1150,8 @@ class Frame:
         A Modular frame of an XYB image decoded with set_modular_xyb(1) in force: stage 0 -> the planes X, Y, B by k_modular_to_xyb.
         A frame with patches (Sequence's patches=): stage 3 -> [3, height, width], the planes after k_patch_blend, as the tail read them.
         A frame with noise (noise=True): stage 4 -> the planes after k_noise_add, as the tail read them (with both, stage 3 is "rnge").
+        A frame with splines (splines=True): stage 6 -> the planes after k_spline_draw, as the tail read them ("rnge" where noise
+        follows: stage 4 then has the planes after both); with patches as well, stage 3 -> the planes between k_patch_blend and k_spline_draw.
         An upsampled frame (upsampling=True): stage 5 -> [3, height, width] of the shown size, the planes k_upsample wrote and the tail
         read; every other stage has the coded size (coded_size())"""
         cw, ch = (self.width, self.height) if stage == 5 else self.coded_size()
@@ -1136,6 +1175,45 @@ class Frame:
     def upsample_ms(self):
         """with J40HIP_UPSAMPLE_TIMING=1: the device time of k_upsample in the last decode"""
         return float(lib().j40hip_frame_upsample_ms(self.h))
+
+    def splines(self):
+        """the splines as parsed (j40hip_frame_splines, j40hip_frame_spline): None for a frame without has_splines, else a dict --
+        "quant_adjust", and "splines": a list of dicts with "start" (x, y), "deltas" (the double deltas of the further control points,
+        [n, 2] int64) and "coef" ([4, 32] int32: X, Y, B, sigma)"""
+        n = C.c_int32(); qa = C.c_int32()
+        if not lib().j40hip_frame_splines(self.h, C.byref(n), C.byref(qa)):
+            return None
+        out = []
+        for i in range(n.value):
+            start = np.zeros(2, np.int64); npts = C.c_int32(); coef = np.zeros((4, 32), np.int32)
+            self._chk(lib().j40hip_frame_spline(self.h, i, start.ctypes.data, C.byref(npts), None, 0, coef.ctypes.data), "in j40hip_frame_spline")
+            dd = np.zeros((npts.value, 2), np.int64)
+            self._chk(lib().j40hip_frame_spline(self.h, i, None, None, dd.ctypes.data, dd.size, None), "in j40hip_frame_spline")
+            out.append({"start": (int(start[0]), int(start[1])), "deltas": dd, "coef": coef})
+        return {"quant_adjust": int(qa.value), "splines": out}
+
+    def spline_segments(self):
+        """the segments the next decode draws (j40hip_frame_spline_segments): [n, 12] uint32 words -- x0, x1, y0, y1 (int32), cx, cy,
+        1 / sigma, sigma * multiplier / 4, colour X, Y, B (float32 bits), a pad -- in drawing order"""
+        n = int(lib().j40hip_frame_spline_segments(self.h, None, 0))
+        a = np.zeros((n, 12), np.uint32)
+        if n:
+            lib().j40hip_frame_spline_segments(self.h, a.ctypes.data, n)
+        return a
+
+    def spline_bins(self):
+        """(the 64 x 32 tiles the segments touch, the (tile, segment) pairs)"""
+        a = np.zeros(2, np.int64)
+        lib().j40hip_frame_spline_bins(self.h, a.ctypes.data)
+        return int(a[0]), int(a[1])
+
+    def spline_launches(self):
+        """how often decodes of this handle have launched k_spline_draw (never for a frame whose segments all dropped)"""
+        return int(lib().j40hip_frame_spline_launches(self.h))
+
+    def spline_ms(self):
+        """with J40HIP_SPLINE_TIMING=1: the device time of k_spline_draw in the last decode"""
+        return float(lib().j40hip_frame_spline_ms(self.h))
 
     def noise_params(self):
         """photon noise (j40hip_frame_noise): None for a frame without has_noise, else a dict -- "lut": the eight NoiseParameters / 1024
@@ -1338,13 +1416,15 @@ class Sequence:
     the frames whose patch dictionary blends rectangles of them onto their own XYB samples are served too, else "TODO" (frame_patches,
     frame_patch, read_ref_slot); a Modular reference-only frame needs modular_xyb=True as well. PARITY UNPINNED.
     noise=True (or J40HIP_NOISE=1): frames with photon noise are served (Frame's noise=); each gets the seed counters of its place in
-    the sequence (Frame.noise_params()), so two shown frames get different fields. PARITY UNPINNED."""
+    the sequence (Frame.noise_params()), so two shown frames get different fields. PARITY UNPINNED.
+    splines=True (or J40HIP_SPLINES=1): frames with splines are served (Frame's splines=); a damaged spline stream ("spln") ends the
+    index at its frame. PARITY UNPINNED."""
 
-    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False, modular_xyb: bool = False, colour: bool = False, patches: bool = False, noise: bool = False):
+    def __init__(self, data: bytes, threads: int = 4, flags: int = 0, blend: bool = False, wide: bool = False, lf_frames: bool = False, modular_xyb: bool = False, colour: bool = False, patches: bool = False, noise: bool = False, splines: bool = False):
         L = lib()
         self._buf = C.create_string_buffer(data, len(data))
         err = C.c_uint32()
-        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0) | (SEQ_MODULAR_XYB if modular_xyb else 0) | (SEQ_COLOUR if colour else 0) | (SEQ_PATCHES if patches else 0) | (PARSE_NOISE if noise else 0)
+        flags |= (SEQ_BLEND if blend else 0) | (PARSE_WIDE if wide else 0) | (SEQ_LFFRAME if lf_frames else 0) | (SEQ_MODULAR_XYB if modular_xyb else 0) | (SEQ_COLOUR if colour else 0) | (SEQ_PATCHES if patches else 0) | (PARSE_NOISE if noise else 0) | (PARSE_SPLINES if splines else 0)
         self.h = L.j40hip_sequence_open(self._buf, len(data), threads, flags, C.byref(err))
         if not self.h:
             raise J40Error(err4(err.value), "in j40hip_sequence_open")
@@ -1483,7 +1563,7 @@ class Sequence:
         return err4(code), int(k.value)
 
 
-def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False, noise=False):
+def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False, wide=False, lf_frames=False, modular_xyb=False, colour=False, patches=False, noise=False, splines=False):
     """every displayed frame of an animation or a layered still: ([(rgba ndarray [height, width, 4], duration in ticks), ...],
     (tps_num, tps_den, loops)). alpha=True: VarDCT frames keep their alpha channel (Frame.set_alpha(1); J40Error where that refuses).
     blend=True: frames with a blend mode other than Replace are composed too (Sequence's blend=), else such a frame raises "TODO".
@@ -1493,8 +1573,9 @@ def decode_frames(data: bytes, fmt=J40_U8X4, alpha=False, device=0, blend=False,
     colour=True: every frame is rendered in the colour space the image header signals (Sequence's colour=).
     patches=True: reference-only frames and the frames with a patch dictionary are served (Sequence's patches=), else "TODO".
     noise=True: frames with photon noise are served (Sequence's noise=), else "TODO".
+    splines=True: frames with splines are served (Sequence's splines=), else "TODO".
     A frame that fails raises J40Error with its code. A stream whose first frame is its last is not a sequence ("Usq?"): decode()."""
-    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames, modular_xyb=modular_xyb, colour=colour, patches=patches, noise=noise)
+    seq = Sequence(data, blend=blend, wide=wide, lf_frames=lf_frames, modular_xyb=modular_xyb, colour=colour, patches=patches, noise=noise, splines=splines)
     try:
         seq.set_output_format(fmt)
         if alpha:

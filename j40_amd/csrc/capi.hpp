@@ -26,7 +26,8 @@ struct LastDecode {
 	const float *tail_planes = nullptr;   // the three XYB planes the tail read, after the filters and the patches (j40hip_frame_read_xyb); device memory of the upload
 	const float *coded_planes = nullptr;  // an upsampled frame: the coded planes k_upsample read (tail_planes are the shown-size ones it wrote); else null
 	// the upload's device state is released: nothing of it is named or reported any longer
-	void device_released() { restore_ran = 0; restore_err = 0; trailers_pending = false; tail_planes = nullptr; coded_planes = nullptr; }
+	const float *patched_planes = nullptr;   // a frame with patches and splines: a copy of the planes between k_patch_blend and k_spline_draw (stage 3); else null
+	void device_released() { restore_ran = 0; restore_err = 0; trailers_pending = false; tail_planes = nullptr; coded_planes = nullptr; patched_planes = nullptr; }
 };
 
 struct j40hip_frame {
@@ -81,6 +82,8 @@ struct j40hip_frame {
 	// stand-alone handle has zeros; noise_launches: how often a decode of this handle has launched k_noise_fill and k_noise_add
 	uint32_t noise_seeds[2] = {0, 0};
 	int64_t noise_launches = 0;
+	// a frame with splines (J40HIP_PARSE_SPLINES): how often a decode of this handle has launched k_spline_draw
+	int64_t spline_launches = 0;
 	std::shared_ptr<const j40hip::PatchPlan> patch_plan;   // the placements as records and their tiles, as the sequence's index made them (null: no dictionary)
 	int threads = 1;                 // what the frame was parsed with: the plan build at upload may use as many (plan_build.cpp)
 	// backing storage of the plan views (include/j40hip.h)
@@ -140,6 +143,7 @@ struct j40hip_sequence {
 	bool colour_asked = false;       // ... by the flag itself: an image the mode refuses as a whole then fails j40hip_sequence_open
 	bool modular_xyb = false;        // Modular frames of an XYB image go through the XYB colour tail (J40HIP_SEQ_MODULAR_XYB or J40HIP_MODULAR_XYB=1)
 	bool noise = false;              // frames with has_noise are served (J40HIP_PARSE_NOISE or J40HIP_NOISE=1)
+	bool splines = false;            // frames with has_splines are served (J40HIP_SEQ_SPLINES or J40HIP_SPLINES=1)
 	bool patches = false;            // reference-only frames and patch dictionaries are served (J40HIP_SEQ_PATCHES or J40HIP_PATCHES=1)
 	int32_t alpha_ec = -1;           // the extra channel that is rendered as A (rendered_alpha_channel); -1: none
 	int32_t output_format = J40HIP_U8X4;

@@ -29,6 +29,7 @@ j40hip_frame *j40hip_frame_parse_with(const void *buf, size_t size, int threads,
 		h->frame.allow_ycbcr = (flags & J40HIP_PARSE_YCBCR) != 0 || ycbcr_env();
 		h->frame.allow_wide = (flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
 		h->frame.allow_noise = (flags & J40HIP_PARSE_NOISE) != 0 || noise_env();
+		h->frame.allow_splines = (flags & J40HIP_PARSE_SPLINES) != 0 || splines_env();
 		h->frame.allow_upsampling = (flags & J40HIP_PARSE_UPSAMPLING) != 0 || upsampling_env();
 		extract_codestream((const uint8_t *) buf, size, &h->cs, &h->cs_size, &h->cs_storage, &h->container_stray_tail);
 		h->bare_codestream = h->cs == (const uint8_t *) buf && h->cs_size == size;
@@ -61,6 +62,7 @@ j40hip_frame *j40hip_frame_parse_streamed(const void *buf, size_t size, int thre
 		h->frame.allow_ycbcr = (flags & J40HIP_PARSE_YCBCR) != 0 || ycbcr_env();
 		h->frame.allow_wide = (flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
 		h->frame.allow_noise = (flags & J40HIP_PARSE_NOISE) != 0 || noise_env();
+		h->frame.allow_splines = (flags & J40HIP_PARSE_SPLINES) != 0 || splines_env();
 		h->frame.allow_upsampling = (flags & J40HIP_PARSE_UPSAMPLING) != 0 || upsampling_env();
 		h->cs = p; h->cs_size = size; h->bare_codestream = true;
 		parse_frame(h->cs, h->cs_size, &h->frame, threads);
@@ -170,6 +172,7 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 		s->colour_asked = (flags & J40HIP_SEQ_COLOUR) != 0;
 		s->patches = (flags & J40HIP_SEQ_PATCHES) != 0 || env_on("J40HIP_PATCHES", false);
 		s->noise = (flags & J40HIP_PARSE_NOISE) != 0 || noise_env();
+		s->splines = (flags & J40HIP_SEQ_SPLINES) != 0 || splines_env();
 		uint32_t noise_seeds[2] = {0, 0};   // visible, nonvisible as the playback reaches the next row
 		size_t at = 0;
 		// (J40HIP_SEQ_UPSAMPLING: the image header's custom weights are read; a frame of a sequence with upsampling > 1 stays "TODO")
@@ -228,6 +231,12 @@ j40hip_sequence *j40hip_sequence_open(const void *buf, size_t size, int threads,
 					// (the tiles the placements touch, bounded before anything is made of them: patch_dev.h)
 					if (!row.code && !patch_bin(recs.data(), recs.size(), row.fh.width, row.fh.height, &plan->bins)) row.code = E4("ptch");
 					if (!row.code) row.patch_plan = plan;
+				}
+				if (s->splines && row.fh.has_splines && !row.code) {
+					// a damaged spline stream ("spln") shows only once LfGlobal has been read as far as the base correlations: that much of
+					// it is read here; whatever else is wrong with the frame is found when its handle is parsed, as ever
+					try { parse_sequence_splines(s->cs, s->cs_size, at, s->im, row.fh, toc, s->patches, s->noise); }
+					catch (const DecodeError &e) { if (e.code == (uint32_t) E4("spln")) row.code = e.code; }
 				}
 				if (row.fh.type == 2 && !row.code) { row.stored_xyb = true; row.xyb_slot = row.fh.save_as_ref; }
 			} catch (const DecodeError &e) { row.code = e.code; }
@@ -295,6 +304,33 @@ int j40hip_frame_noise(const j40hip_frame *h, float *lut8, uint32_t *seeds2) {
 	return h->frame.fh.has_noise ? 1 : 0;
 }
 int64_t j40hip_frame_noise_launches(const j40hip_frame *h) { return h ? h->noise_launches : 0; }
+
+// ---- splines (include/j40hip.h; device/spline_dev.h has the rule) ----
+int j40hip_frame_splines(const j40hip_frame *h, int32_t *num_splines, int32_t *quant_adjust) {
+	if (num_splines) *num_splines = h ? (int32_t) h->frame.splines.splines.size() : 0;
+	if (quant_adjust) *quant_adjust = h ? h->frame.splines.quant_adjust : 0;
+	return h && h->frame.fh.has_splines ? 1 : 0;
+}
+uint32_t j40hip_frame_spline(const j40hip_frame *h, int64_t i, int64_t *start2, int32_t *num_points, int64_t *deltas, int64_t cap, int32_t *coef128) {
+	if (!h || i < 0 || i >= (int64_t) h->frame.splines.splines.size()) return j40hip::ERR_RNGE;
+	const QuantSpline &q = h->frame.splines.splines[(size_t) i];
+	if (start2) { start2[0] = q.x; start2[1] = q.y; }
+	if (num_points) *num_points = (int32_t) (q.dd.size() / 2);
+	if (deltas) for (int64_t k = 0; k < cap && k < (int64_t) q.dd.size(); ++k) deltas[k] = q.dd[(size_t) k];
+	if (coef128) memcpy(coef128, q.coef, sizeof q.coef);
+	return 0;
+}
+int64_t j40hip_frame_spline_segments(const j40hip_frame *h, void *out, int64_t cap) {
+	if (!h) return 0;
+	const std::vector<SplineSeg> &segs = h->frame.spline_plan.segs;
+	if (out && cap > 0 && !segs.empty()) memcpy(out, segs.data(), sizeof(SplineSeg) * (size_t) std::min<int64_t>(cap, (int64_t) segs.size()));
+	return (int64_t) segs.size();
+}
+void j40hip_frame_spline_bins(const j40hip_frame *h, int64_t *out2) {
+	if (!out2) return;
+	out2[0] = h ? (int64_t) h->frame.spline_plan.tile_ids.size() : 0; out2[1] = h ? (int64_t) h->frame.spline_plan.seg_idx.size() : 0;
+}
+int64_t j40hip_frame_spline_launches(const j40hip_frame *h) { return h ? h->spline_launches : 0; }
 
 // ---- upsampling (include/j40hip.h; device/upsample_dev.h has the rule) ----
 uint32_t j40hip_set_upsampling_defaults(int k, const float *w, int n) { return j40hip::set_upsampling_defaults(k, w, n) ? 0 : j40hip::ERR_RNGE; }
@@ -389,7 +425,7 @@ j40hip_frame *j40hip_sequence_frame(j40hip_sequence *s, int64_t k, uint32_t *err
 		h->bare_codestream = true;
 		h->frame.defer_lf_tail = (s->flags & 1u) != 0;
 		h->frame.seq_im = &s->im; h->frame.seq_blend = s->blend; h->frame.allow_lf_frame = s->lf_frames; h->frame.allow_modular_lf = s->lf_frames && s->modular_xyb; h->frame.allow_wide = (s->flags & J40HIP_PARSE_WIDE) != 0 || wide_env();
-		h->frame.allow_patches = s->patches; h->frame.allow_modular_ref = s->patches && s->modular_xyb; h->frame.allow_noise = s->noise;
+		h->frame.allow_patches = s->patches; h->frame.allow_modular_ref = s->patches && s->modular_xyb; h->frame.allow_noise = s->noise; h->frame.allow_splines = s->splines;
 		parse_frame(h->cs, h->cs_size, &h->frame, s->threads);
 		h->threads = s->threads;
 		h->output_format = s->output_format;

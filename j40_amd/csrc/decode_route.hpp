@@ -6,6 +6,8 @@
 // frame, not a mode of the handle: DecodeRoute::noise sends the decode through the plane stage -- whole frames at full size, from which a
 // region is cut and a scale averaged (full_size_first), in one phase --, and refuses what has no full-size XYB planes to add it to: a
 // Modular frame without the Modular XYB switch, a YCbCr plan, a partial group range, a batch, many LF previews in one launch (an LF-only parse of such a frame is refused by the parse).
+// Splines (a frame parsed with J40HIP_PARSE_SPLINES whose header has has_splines) are such an operation as well, between the patches and the
+// noise: DecodeRoute::splines goes wherever patches and noise go.
 // Upsampling (a frame parsed with J40HIP_PARSE_UPSAMPLING whose header has upsampling > 1) is such an operation too, the one that changes the
 // planes' size: DecodeRoute::upsampling sends the decode through the plane stage, where k_upsample stretches the coded planes to the shown
 // size ahead of the tail; stored_w and stored_h come from the shown size, a region is cut from and a scale averaged over the shown-size
@@ -35,7 +37,8 @@ inline uint32_t mode_refusal(const j40hip_frame *h, Mode what) {
 	// (patches go onto whole pictures' planes through one handle's own tail: no batch, no preview of the LF image alone, no partial range)
 	// (noise likewise: it is added to whole pictures' planes)
 	// (an upsampled frame likewise: its coded planes are stretched whole)
-	const bool patches = h->frame.fh.has_patches || h->frame.fh.has_noise || h->frame.fh.upsampling > 1;
+	// (splines likewise: they are drawn onto whole pictures' planes)
+	const bool patches = h->frame.fh.has_patches || h->frame.fh.has_splines || h->frame.fh.has_noise || h->frame.fh.upsampling > 1;
 	if (patches && (what == Mode::GroupRange || what == Mode::Batch || what == Mode::LfPreviewBatch)) return ERR_TODO;
 	switch (what) {
 	case Mode::Region:         return h->partial_range ? ERR_URG : h->scale > 0 ? ERR_USC : 0;
@@ -71,6 +74,7 @@ struct DecodeRoute {
 	bool alpha_merged = false;         // the extra channels' sub-images carry an alpha channel that is kept: k_alpha_merge writes it into full-size pixels
 	bool modular_xyb = false;          // a Modular plan through the XYB colour tail
 	bool patches = false;              // the frame has a patch dictionary: its pixels come from XYB planes (the filtered ones where the filters are in force), k_patch_blend over them, then the tail
+	bool splines = false;              // the frame has splines: likewise, k_spline_draw behind the patches, ahead of the noise
 	bool noise = false;                // the frame has noise: likewise, k_noise_fill and k_noise_add behind the patches, ahead of the tail
 	bool upsampling = false;           // the frame is coded at 1:2, 1:4 or 1:8: k_upsample behind the filters makes the shown-size planes the tail reads
 	bool colour = false;               // the colour mode in force: the XYB planes (filtered where the filters are in force; a Modular XYB plan's by k_modular_to_xyb) go through k_colour_tail
@@ -100,21 +104,23 @@ inline DecodeRoute resolve_route(const j40hip_frame *h, const UploadFacts *up, b
 	r.modular_xyb = up->is_modular && j40hip_modular_xyb_on(h);
 	r.colour = j40hip_colour_on(h);
 	r.patches = fr.fh.has_patches;
+	r.splines = fr.fh.has_splines;
 	r.noise = fr.fh.has_noise;
 	r.upsampling = fr.fh.upsampling > 1;
-	const bool full_size_only = r.colour || r.patches || r.noise || r.upsampling || (up->is_modular ? r.modular_xyb && r.shape == DecodeRoute::Scaled : r.restoration || r.alpha_merged);
+	const bool full_size_only = r.colour || r.patches || r.splines || r.noise || r.upsampling || (up->is_modular ? r.modular_xyb && r.shape == DecodeRoute::Scaled : r.restoration || r.alpha_merged);
 	r.full_size_first = r.shape != DecodeRoute::Whole && full_size_only;
-	r.two_phase = r.shape == DecodeRoute::Whole && r.orientation == 1 && !fr.fh.use_lf_frame && !r.colour && !r.patches && !r.noise && !r.upsampling;
-	r.xyb_refusal = r.patches || r.noise || r.upsampling || r.shape != DecodeRoute::Whole || !r.every_group || (up->is_modular ? !r.modular_xyb : up->ycbcr || up->has_trailers) ? (uint32_t) ERR_TODO : 0;
+	r.two_phase = r.shape == DecodeRoute::Whole && r.orientation == 1 && !fr.fh.use_lf_frame && !r.colour && !r.patches && !r.splines && !r.noise && !r.upsampling;
+	r.xyb_refusal = r.patches || r.splines || r.noise || r.upsampling || r.shape != DecodeRoute::Whole || !r.every_group || (up->is_modular ? !r.modular_xyb : up->ycbcr || up->has_trailers) ? (uint32_t) ERR_TODO : 0;
 	// in the entry points' order: an orientation over a partial range (no whole stored image to turn), the oriented image's rows, a YCbCr plan
 	// (served only while its switch stays on, and whole), the stored image's rows
 	if (r.orientation != 1 && !r.every_group) r.refusal = ERR_UOR;
 	else if (r.colour && !r.every_group) r.refusal = ERR_UCS;   // (a group range set before the mode: mode_refusal's rule)
 	// (a Modular frame's planes reach XYB through the Modular XYB switch alone)
-	else if ((r.patches || r.noise || r.upsampling) && (!r.every_group || (up->is_modular && !r.modular_xyb) || up->ycbcr)) r.refusal = ERR_TODO;
+	else if ((r.patches || r.splines || r.noise || r.upsampling) && (!r.every_group || (up->is_modular && !r.modular_xyb) || up->ycbcr)) r.refusal = ERR_TODO;
+	// (splines belong on the coded planes ahead of the stretch: a follow-up)
 	// (noise is a shown-size operation, the kept alpha and a Modular frame's alpha plane would have to be stretched as well)
 	// (a frame with patches exists in sequences alone, whose frames the parse refuses: nothing to ask here)
-	else if (r.upsampling && (r.noise || r.alpha_merged || (up->is_modular && up->modular_alpha))) r.refusal = ERR_TODO;
+	else if (r.upsampling && (r.splines || r.noise || r.alpha_merged || (up->is_modular && up->modular_alpha))) r.refusal = ERR_TODO;
 	else if (r.orientation != 1 && (!have_out || stride_bytes < r.min_stride)) r.refusal = ERR_RNGE;
 	else if (up->ycbcr && (!j40hip_ycbcr_on(h) || r.shape != DecodeRoute::Whole || !r.every_group)) r.refusal = ERR_TODO;
 	else if (stride_bytes < r.min_stride) r.refusal = ERR_RNGE;

@@ -7,6 +7,7 @@
 #include "colour_dev.h"
 #include "patch_dev.h"
 #include "noise_dev.h"
+#include "spline_dev.h"
 #include "upsample_dev.h"
 
 namespace j40hip {
@@ -64,6 +65,10 @@ void launch_noise_add(float *planes, size_t ppitch, const float *raw, int32_t W,
 // behind the other) into the three at `out` (up_w x up_h each, up_w <= k * w, up_h <= k * h) by the expanded table at `table_dev`
 // (k * k * 25 floats, device memory). false: a factor or a size it does not take, nothing launched
 bool launch_upsample(const float *src, int32_t w, int32_t h, int32_t k, const float *table_dev, float *out, int32_t up_w, int32_t up_h, hipStream_t stream);
+
+// splines (device/spline_kernels.hip, spline_dev.h): k_spline_draw adds the segments of `d` (device memory) onto the three planes at
+// `planes` (`pitch` floats a row, one behind the other), in place, one workgroup per touched tile; nothing is launched without tiles
+void launch_spline_draw(float *planes, size_t pitch, int32_t W, int32_t H, const DevSplines &d, hipStream_t stream);
 
 // LfGroup tail on the device (device/lf_tail_kernels.hip)
 void upload_lf_tail_tables(const float *half_secants, const float *lf2llf, hipStream_t stream);

@@ -159,6 +159,82 @@ extern "C" uint32_t j40hip_kat_device_noise(float *planes_dev, int32_t width, in
 	});
 }
 
+// ---- splines (a frame parsed with J40HIP_PARSE_SPLINES; device/spline_dev.h, spline_kernels.hip) ----
+// k_spline_draw on `s` between two events of its own when ms is not null (J40HIP_SPLINE_TIMING, the known-answer hook): the call then
+// waits for the kernel and reports its device time. The events are destroyed on every way out.
+static uint32_t run_spline_kernel(float *planes, int32_t W, int32_t H, const DevSplines &d, hipStream_t s, float *ms) {
+	struct Pair { hipEvent_t ev[2] = {nullptr, nullptr}; ~Pair() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); } } pair;
+	bool timed = ms != nullptr;
+	for (int i = 0; timed && i < 2; ++i) timed = hipEventCreate(&pair.ev[i]) == hipSuccess;
+	if (ms) *ms = 0.0f;
+	if (timed) (void) hipEventRecord(pair.ev[0], s);
+	launch_spline_draw(planes, (size_t) W, W, H, d, s);
+	if (timed) (void) hipEventRecord(pair.ev[1], s);
+	if (hipGetLastError() != hipSuccess) return ERR_GPU;
+	if (timed) {
+		if (hipEventSynchronize(pair.ev[1]) != hipSuccess) return ERR_GPU;
+		(void) hipEventElapsedTime(ms, pair.ev[0], pair.ev[1]);
+	}
+	return 0;
+}
+
+// the segments and the tiles' lists of `plan` into `st`'s memory (the host vectors must outlive the copies)
+static bool upload_spline_plan(j40hip_device_state *st, const SplinePlan &plan, hipStream_t s, DevSplines *d) {
+	bool ok = true;
+	d->segs = st->upload(plan.segs.data(), plan.segs.size(), s, ok);
+	d->tile_ids = st->upload(plan.tile_ids.data(), plan.tile_ids.size(), s, ok);
+	d->tile_start = st->upload(plan.tile_start.data(), plan.tile_start.size(), s, ok);
+	d->seg_idx = st->upload(plan.seg_idx.data(), plan.seg_idx.size(), s, ok);
+	d->num_tiles = (int32_t) plan.tile_ids.size(); d->tiles_x = plan.tiles_x;
+	return ok;
+}
+
+// The frame's splines onto `planes` (width x height floats each, X, Y, B one behind the other), on `s`: called by render_planes behind the
+// patches and ahead of the noise. Nothing for a frame without splines; nothing is launched or allocated for a frame whose segments all
+// dropped. The segments and their tiles (made by the parse) are uploaded once per upload and kept with the frame.
+uint32_t j40hip_rt::apply_splines(j40hip_frame *h, float *planes, hipStream_t s) {
+	const Frame &fr = h->frame;
+	if (!fr.fh.has_splines || fr.spline_plan.tile_ids.empty()) return 0;
+	j40hip_device_state *st = h->dev;
+	if (!st->spline.dev.segs) {
+		DevSplines d;
+		if (!upload_spline_plan(st, fr.spline_plan, s, &d)) return ERR_MEM;
+		st->spline.dev = d;
+	}
+	static const bool timed = env_str("J40HIP_SPLINE_TIMING") != nullptr;
+	if (uint32_t e = run_spline_kernel(planes, fr.fh.width, fr.fh.height, st->spline.dev, s, timed ? &st->spline.ms : nullptr)) return e;
+	++h->spline_launches;
+	return 0;
+}
+
+extern "C" float j40hip_frame_spline_ms(const j40hip_frame *h) { return h && h->dev ? h->dev->spline.ms : 0.0f; }
+
+extern "C" uint32_t j40hip_kat_device_splines(float *planes_dev, int32_t width, int32_t height, const void *segments, int64_t n, int64_t *tiles_out, void *stream, float *ms) {
+	return guarded([&]() -> uint32_t {
+		if (ms) *ms = 0.0f;
+		if (tiles_out) *tiles_out = 0;
+		if (!planes_dev || width <= 0 || height <= 0 || (int64_t) width * height > (1 << 28) || n < 0 || n > SPLINE_MAX_SEGMENTS || (n > 0 && !segments)) return ERR_RNGE;
+		SplinePlan plan;
+		plan.segs.resize((size_t) n);
+		if (n) memcpy(plan.segs.data(), segments, sizeof(SplineSeg) * (size_t) n);
+		// (the kernel checks nothing: every box lies inside the frame)
+		for (const SplineSeg &g : plan.segs) if (g.x0 < 0 || g.x0 > g.x1 || g.x1 >= width || g.y0 < 0 || g.y0 > g.y1 || g.y1 >= height) return ERR_RNGE;
+		if (!spline_bin(width, &plan)) return ERR_RNGE;
+		if (tiles_out) *tiles_out = (int64_t) plan.tile_ids.size();
+		if (plan.tile_ids.empty()) return 0;
+		int device = 0;
+		if (hipGetDevice(&device) != hipSuccess) return ERR_GPU;
+		hipStream_t s = (hipStream_t) stream;
+		j40hip_device_state tmp; tmp.device = device;
+		DevSplines d;
+		uint32_t e = upload_spline_plan(&tmp, plan, s, &d) ? run_spline_kernel(planes_dev, width, height, d, s, ms) : ERR_MEM;
+		if (hipStreamSynchronize(s) != hipSuccess && !e) e = ERR_GPU;
+		for (auto &b : tmp.buffers) b.release();
+		tmp.buffers.clear();
+		return e;
+	});
+}
+
 // ---- upsampling (a frame parsed with J40HIP_PARSE_UPSAMPLING whose header has upsampling > 1; device/upsample_dev.h, upsample_kernels.hip) ----
 // k_upsample on `s` between two events of its own when ms is not null (J40HIP_UPSAMPLE_TIMING, the known-answer hook): the call then
 // waits for the kernel and reports its device time. The events are destroyed on every way out.
@@ -251,7 +327,7 @@ static uint32_t ycbcr_tail(j40hip_frame *h, YcbcrTail &t, uint8_t *img, size_t s
 	return 0;
 }
 
-// Render the planes (`pitch` floats a row, one plane behind the other) into the caller's image: the frame's patches onto them, its noise, then exactly
+// Render the planes (`pitch` floats a row, one plane behind the other) into the caller's image: the frame's patches onto them, its splines, its noise, then exactly
 // one tail -- k_ycbcr_tail for a YCbCr plan, k_colour_tail for the colour mode (`colour`), else the sRGB tail -- and a Modular plan's A from
 // its plane, as the pack kernels render it (the tails write A opaque). What the tail read stays for j40hip_frame_read_xyb.
 static uint32_t render_planes(j40hip_frame *h, float *planes, size_t pitch, bool colour, uint8_t *img, size_t stride_bytes, hipStream_t s) {
@@ -267,7 +343,15 @@ static uint32_t render_planes(j40hip_frame *h, float *planes, size_t pitch, bool
 	}
 	const int32_t W = fr.fh.shown_width(), H = fr.fh.shown_height();
 	if (uint32_t e = apply_patches(h, planes, s)) return e;
-	if (fr.fh.has_noise && pitch != (size_t) W) return ERR_TODO;   // (cannot happen: only a YCbCr plan pads its rows, and the route refuses it)
+	if ((fr.fh.has_noise || fr.fh.has_splines) && pitch != (size_t) W) return ERR_TODO;   // (cannot happen: only a YCbCr plan pads its rows, and the route refuses it)
+	// (a frame with patches and splines: what k_patch_blend left stays readable as stage 3, in a copy -- the splines are drawn in place)
+	if (fr.fh.has_patches && fr.fh.has_splines) {
+		const size_t n = 3 * (size_t) W * (size_t) H;
+		if (!st->keep(st->spline.d_patched, n)) return ERR_MEM;
+		if (hipMemcpyAsync(st->spline.d_patched, planes, sizeof(float) * n, hipMemcpyDeviceToDevice, s) != hipSuccess) return ERR_GPU;
+		h->last.patched_planes = st->spline.d_patched;
+	}
+	if (uint32_t e = apply_splines(h, planes, s)) return e;
 	if (uint32_t e = apply_noise(h, planes, s)) return e;
 	h->last.tail_planes = planes;
 	if (st->ycbcr) {
@@ -305,7 +389,7 @@ static uint32_t decode_modular(j40hip_frame *h, const DecodeRoute &route, void *
 	h->last.modular_xyb_used = xyb;
 	if ((xyb_out && !xyb) || (xyb && shift > 0)) return ERR_TODO;
 	const bool colour = route.colour && xyb && !xyb_out;   // (whole frames: the route stages a region or a scale)
-	const bool patches = (route.patches || route.noise || route.upsampling) && !xyb_out;        // (likewise; noise and upsampling go the patches' way)
+	const bool patches = (route.patches || route.splines || route.noise || route.upsampling) && !xyb_out;        // (likewise; splines, noise and upsampling go the patches' way)
 	if (patches && (!xyb || !st->patch.d_frame)) return ERR_TODO;
 	if ((colour || patches) && (region || shift > 0 || !route.every_group)) return ERR_TODO;
 	const bool planes = colour || patches || xyb_out;   // the decode goes through the plane stage
@@ -629,7 +713,7 @@ static uint32_t ycbcr_pixels(j40hip_frame *h, const int32_t *class_start, const 
 // One VarDCT decode as decode_impl (whole frames, group ranges), decode_region (covers), decode_scaled and decode_frame_xyb describe it to
 // run_vardct; as it stands, the whole frame from the frame's own lists, with nothing to write to yet
 struct VardctRun {
-	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged), colour(r.colour), patches(r.patches || r.noise || r.upsampling) {}
+	VardctRun(const j40hip_frame *h, const DecodeRoute &r) : num_groups((int32_t) h->frame.fh.num_groups), list(h->dev->d_vb_sorted), class_start(h->dev->class_start), restoration(r.restoration), alpha_merged(r.alpha_merged), colour(r.colour), patches(r.patches || r.splines || r.noise || r.upsampling) {}
 	int32_t first_group = 0, num_groups; // the groups of the entropy launch ...
 	const RegionCover *cover = nullptr;  // ... or (not null) a region's cover: through the fast kernel's order list (region.d_order), else a launch per row of its groups
 	const DevVarblock *list; const int32_t *class_start;   // what the pixel kernels take

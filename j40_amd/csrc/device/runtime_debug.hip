@@ -91,11 +91,17 @@ extern "C" uint32_t j40hip_frame_read_xyb(j40hip_frame *h, int stage, float *out
 		if (hipSetDevice(h->dev->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ERR_GPU;
 		return hipMemcpy(out, h->last.tail_planes, sizeof(float) * 3 * (size_t) h->frame.fh.shown_width() * (size_t) h->frame.fh.shown_height(), hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
 	});
-	if (stage == 3 || stage == 4) return guarded([&]() -> uint32_t {
+	// (stage 6, a frame with splines: likewise, after k_spline_draw -- "rnge" where noise follows, stage 4 then has the planes after both.
+	// Stage 3 of a frame with patches and splines: the copy render_planes kept of the planes between k_patch_blend and k_spline_draw,
+	// with or without noise behind them)
+	if (stage == 3 || stage == 4 || stage == 6) return guarded([&]() -> uint32_t {
 		if (!h || !h->dev || !h->last.tail_planes || !out) return ERR_RNGE;
-		if (stage == 3 ? !h->frame.fh.has_patches || h->frame.fh.has_noise : !h->frame.fh.has_noise) return ERR_RNGE;
+		const FrameHeader &fh = h->frame.fh;
+		const bool kept = stage == 3 && fh.has_patches && fh.has_splines;
+		if (kept && !h->last.patched_planes) return ERR_RNGE;
+		if (kept ? false : stage == 3 ? !fh.has_patches || fh.has_noise : stage == 6 ? !fh.has_splines || fh.has_noise : !fh.has_noise) return ERR_RNGE;
 		if (hipSetDevice(h->dev->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ERR_GPU;
-		return hipMemcpy(out, h->last.tail_planes, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
+		return hipMemcpy(out, kept ? h->last.patched_planes : h->last.tail_planes, sizeof(float) * 3 * (size_t) h->frame.fh.width * (size_t) h->frame.fh.height, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ERR_GPU;
 	});
 	if (h && h->dev && h->dev->is_modular && stage == 0 && h->last.modular_xyb_used && j40hip_modular_xyb_on(h)) return guarded([&] { return read_modular_xyb(h, out); });
 	// (the colour mode without the filters: the planes the last decode's k_colour_tail read, stages 0 and 1 alike)

@@ -204,6 +204,11 @@ struct j40hip_device_state {
 	// an upsampled frame (runtime.hip: apply_upsampling): the three shown-size planes k_upsample writes and the tail reads
 	// (3 * up_width * up_height floats) and the frame's expanded weight table (host_table: built once per upload, kept: the copy is
 	// asynchronous), made at the first decode, kept with the frame; nothing for upsampling = 1. ms: the kernel's device time (J40HIP_UPSAMPLE_TIMING)
+	// a frame with splines (runtime.hip: apply_splines): its segments and the CSR lists of the tiles they touch (Frame::spline_plan, which
+	// outlives the copies), uploaded at the first decode that draws them, kept with the frame; ms: k_spline_draw's device time (J40HIP_SPLINE_TIMING)
+	// d_patched: a frame with patches as well -- the planes as k_patch_blend left them, copied before the splines are drawn in place, for
+	// j40hip_frame_read_xyb's stage 3 (made at the first such decode, kept with the frame)
+	struct Splines { DevSplines dev = {nullptr, nullptr, nullptr, nullptr, 0, 0}; float *d_patched = nullptr; float ms = 0; } spline;
 	struct Upsample { float *d_up = nullptr; const float *d_table = nullptr; std::vector<float> host_table; float ms = 0; } up;
 	// a YCbCr frame (j40hip_frame_set_ycbcr; runtime.hip: ycbcr_pixels). ycbcr: the plan was built for one (the switch was on at upload).
 	// d_ycc: the planes the pixel kernels leave for k_ycbcr_tail where the filters do not run, made at the first such decode, kept with
@@ -299,6 +304,7 @@ bool modular_groups_independent(const j40hip_frame *h);                        /
 uint32_t clear_before_decode(j40hip_device_state *st, hipStream_t s);          // runtime.hip
 uint32_t decode_frame_xyb(j40hip_frame *h, float *planes, hipStream_t s);      // runtime.hip
 uint32_t apply_patches(j40hip_frame *h, float *planes, hipStream_t s);         // runtime.hip
+uint32_t apply_splines(j40hip_frame *h, float *planes, hipStream_t s);         // runtime.hip
 uint32_t apply_noise(j40hip_frame *h, float *planes, hipStream_t s);           // runtime.hip
 uint32_t apply_upsampling(j40hip_frame *h, const float *planes, float **out, hipStream_t s);   // runtime.hip
 uint32_t restore_params(const FrameHeader &fh, int mode, RestoreParams *p);    // runtime.hip

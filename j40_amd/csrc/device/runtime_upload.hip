@@ -164,7 +164,7 @@ bool j40hip_rt::host_vb_sorted(j40hip_device_state *st) {
 // copies), into the frame's scratch; a Modular frame's colour constants for the sRGB tail beside them (a Modular frame with noise takes
 // that tail too, and an upsampled one). Waits for the copies.
 static uint32_t upload_patches(j40hip_frame *h, hipStream_t s) {
-	if (!h->frame.fh.has_patches && !((h->frame.fh.has_noise || h->frame.fh.upsampling > 1) && h->dev->is_modular)) return 0;
+	if (!h->frame.fh.has_patches && !((h->frame.fh.has_splines || h->frame.fh.has_noise || h->frame.fh.upsampling > 1) && h->dev->is_modular)) return 0;
 	j40hip_device_state *st = h->dev;
 	j40hip_device_state::Patches &pt = st->patch;
 	if (h->frame.fh.has_patches && !h->patch_plan) { j40hip_release_device(h); return ERR_TODO; }   // (cannot happen: only a sequence's handle parses a dictionary)

@@ -506,17 +506,23 @@ static void init_global_modular(Frame *f) {  // j40.h:3619
 	f->gmodular.bpp = im.bpp;
 }
 
-static void read_lf_global(BitReader &br, Frame *f) {
+// LfGlobal's front: the patch dictionary, the splines, the noise parameters, the LF dequantisation and, for a VarDCT frame, the quantiser,
+// the block contexts and the LF channel correlation -- as far as the spline segments need it. A sequence's index reads this much of a
+// frame with splines (parse_sequence_splines); read_lf_global goes on with the global Modular image.
+static void read_lf_global_front(BitReader &br, Frame *f) {
 	const FrameHeader &fh = f->fh;
-	J40HIP_SHOULD((!fh.has_patches || f->allow_patches) && !fh.has_splines && (!fh.has_noise || f->allow_noise), "TODO");
+	J40HIP_SHOULD((!fh.has_patches || f->allow_patches) && (!fh.has_splines || f->allow_splines) && (!fh.has_noise || f->allow_noise), "TODO");
+	// (splines likewise go onto the XYB samples of a frame that is shown as it is, and an LF image holds none of them)
+	if (fh.has_splines) J40HIP_SHOULD(f->im.xyb_encoded && fh.type != 1 && fh.type != 2 && !f->lf_only, "TODO");
 	// (noise goes onto the XYB samples of a frame that is shown as it is: not an LF frame's, not a reference-only frame's)
 	// (... and not an LF-only parse: the LF image of such a frame is not its preview)
 	if (fh.has_noise) J40HIP_SHOULD(f->im.xyb_encoded && fh.type != 1 && fh.type != 2 && !f->lf_only, "TODO");
-	if (fh.has_patches) {   // the dictionary, ahead of everything else (splines would follow it, the noise parameters do)
+	if (fh.has_patches) {   // the dictionary, ahead of everything else (the splines follow it, then the noise parameters)
 		J40HIP_SHOULD(f->im.xyb_encoded && fh.type != 2 && fh.type != 1, "TODO");
 		read_patch_dictionary(br, f->im, fh, &f->patches);
 		J40HIP_SHOULD(!f->patches.unserved, "TODO");
 	}
+	if (fh.has_splines) read_splines(br, fh, &f->splines);
 	if (fh.has_noise) for (int i = 0; i < 8; ++i) f->noise_lut[i] = (float) br.u(10) / 1024.0f;   // NoiseParameters
 	if (!br.u(1)) for (int i = 0; i < 3; ++i) f->m_lf_scaled[i] = br.f16() / 128.0f;
 	if (!fh.is_modular) {
@@ -547,6 +553,15 @@ static void read_lf_global(BitReader &br, Frame *f) {
 			f->b_factor_lf = (int32_t) br.u(8) - 127;
 		}
 	}
+	if (fh.has_splines) {   // the segments every decode draws and their tiles, now that the base correlations are known (device/spline_dev.h)
+		J40HIP_SHOULD(spline_segments(f->splines, f->base_corr_x, f->base_corr_b, fh.width, fh.height, &f->spline_plan.segs), "spln");
+		J40HIP_SHOULD(spline_bin(fh.width, &f->spline_plan), "spln");
+	}
+}
+
+static void read_lf_global(BitReader &br, Frame *f) {
+	const FrameHeader &fh = f->fh;
+	read_lf_global_front(br, f);
 	init_global_modular(f);
 	if (br.u(1)) {  // global tree
 		// tree size limit with the reference's saturating 32-bit products (j40.h:6321-6322)
@@ -1048,6 +1063,49 @@ void read_patch_dictionary(BitReader &br, const ImageMeta &im, const FrameHeader
 	finish_code(br, code);
 }
 
+// ------------------------------------------------------------------------------------------------
+// the splines. PARITY UNPINNED: the reference stops at has_splines (j40.h:6263); this is the standard's layout as far as it can be
+// recalled without the text. One entropy-coded stream over 6 contexts of hybrid integers: the quantisation
+// adjustment (context 0), starting positions (1), the number of splines - 1 (2), a spline's number of further control points (3), their
+// double deltas (4), the DCT coefficients (5). Order: the count; every spline's starting point, the first as it is, a later one's as the
+// sign-folded difference to the spline before; the adjustment, sign-folded; then per spline its number of control points, that many
+// sign-folded pairs, and 3 x 32 colour coefficients (X, Y, B) and 32 sigma coefficients, sign-folded. "spln": more splines than
+// min(1 << 24, W * H / 4), more control points than min(1 << 20, W * H / 2) in all, a starting coordinate of magnitude above 1 << 23 (the
+// accumulated control points and the segments are bounded where they are made: spline_dev.h).
+void read_splines(BitReader &br, const FrameHeader &fh, SplineData *out) {
+	*out = SplineData();
+	CodeSpec spec;
+	read_code_spec(br, 6, &spec);
+	CodeState code(&spec);
+	auto get = [&](int32_t ctx) { return decode_symbol(br, code, ctx, 0); };
+	const int64_t area = (int64_t) fh.width * fh.height, max_splines = std::min<int64_t>((int64_t) 1 << 24, area / 4), max_points = std::min<int64_t>((int64_t) 1 << 20, area / 2);
+	const int64_t lim = (int64_t) 1 << 23;
+	const int64_t num = (int64_t) (uint32_t) get(2) + 1;
+	J40HIP_SHOULD(num <= max_splines, "spln");
+	out->splines.resize((size_t) num);
+	for (int64_t i = 0; i < num; ++i) {
+		QuantSpline &q = out->splines[(size_t) i];
+		const int32_t vx = get(1), vy = get(1);
+		J40HIP_SHOULD(vx >= 0 && vy >= 0, "spln");
+		if (i == 0) { q.x = vx; q.y = vy; }
+		else { q.x = out->splines[(size_t) i - 1].x + unpack_signed(vx); q.y = out->splines[(size_t) i - 1].y + unpack_signed(vy); }
+		J40HIP_SHOULD(q.x <= lim && q.x >= -lim && q.y <= lim && q.y >= -lim, "spln");
+	}
+	const int32_t qa = get(0);
+	J40HIP_SHOULD(qa >= 0, "spln");
+	out->quant_adjust = unpack_signed(qa);
+	int64_t points = 0;
+	for (int64_t i = 0; i < num; ++i) {
+		QuantSpline &q = out->splines[(size_t) i];
+		const int32_t n = get(3);
+		J40HIP_SHOULD(n >= 0 && (points += n) <= max_points, "spln");
+		q.dd.resize((size_t) n * 2);
+		for (int64_t &d : q.dd) { const int32_t v = get(4); J40HIP_SHOULD(v >= 0, "spln"); d = unpack_signed(v); }
+		for (int c = 0; c < 4; ++c) for (int k = 0; k < 32; ++k) { const int32_t v = get(5); J40HIP_SHOULD(v >= 0, "spln"); q.coef[c][k] = unpack_signed(v); }
+	}
+	finish_code(br, code);
+}
+
 void parse_sequence_patches(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, const FrameHeader &fh, const Toc &toc, PatchDictionary *out) {
 	// LfGlobal: the frame's one section (read to the end of the codestream, as parse_frame reads it), or the section the TOC names
 	const Section sec = toc.single ? toc.single_section : toc.lf_global;
@@ -1055,6 +1113,19 @@ void parse_sequence_patches(const uint8_t *cs, size_t cs_size, size_t offset, co
 	const size_t size = toc.single ? cs_size - at : std::min(sec.size, cs_size - at);
 	BitReader br(cs + at, size);
 	read_patch_dictionary(br, im, fh, out);
+}
+
+// A frame with splines of a sequence, when the index is built: LfGlobal's front alone, which raises what parse_frame would raise for it
+// ("spln" for a damaged spline stream: only here, behind the base correlations, are the segments and their tiles known)
+void parse_sequence_splines(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, const FrameHeader &fh, const Toc &toc, bool allow_patches, bool allow_noise) {
+	const Section sec = toc.single ? toc.single_section : toc.lf_global;
+	const size_t at = std::min(cs_size, offset + sec.offset);
+	const size_t size = toc.single ? cs_size - at : std::min(sec.size, cs_size - at);
+	BitReader br(cs + at, size);
+	Frame f;
+	f.im = im; f.fh = fh;
+	f.allow_patches = allow_patches; f.allow_noise = allow_noise; f.allow_splines = true;
+	read_lf_global_front(br, &f);
 }
 
 static void parse_headers_within(const uint8_t *cs, size_t limit, size_t cs_size, Frame *f) {

@@ -7,6 +7,7 @@
 // j40__lf_group (6722), j40__hf_global (6819), j40__load_dq_matrix (4828), j40__natural_order (4980).
 #pragma once
 #include "modular.hpp"
+#include "device/spline_dev.h"
 #include <algorithm>
 #include <array>
 
@@ -22,6 +23,7 @@ inline bool alpha_env() { static const bool v = [] { const char *e = env_str("J4
 inline bool orient_env() { static const bool v = [] { const char *e = env_str("J40HIP_ORIENT"); return e && atoi(e) > 0; }(); return v; }
 // J40HIP_YCBCR=1: YCbCr VarDCT frames (recompressed JPEGs) are served where j40hip_frame_set_ycbcr(f, 1) would be taken (include/j40hip.h); read once
 inline bool noise_env() { return env_on("J40HIP_NOISE", false); }   // (read at every parse)
+inline bool splines_env() { return env_on("J40HIP_SPLINES", false); }   // J40HIP_SPLINES=1: every parse asks for splines (J40HIP_PARSE_SPLINES); read at every parse
 inline bool upsampling_env() { return env_on("J40HIP_UPSAMPLING", false); }   // J40HIP_UPSAMPLING=1: every parse asks for upsampling (J40HIP_PARSE_UPSAMPLING); read at every parse
 inline bool wide_env() { static const bool v = [] { const char *e = env_str("J40HIP_WIDE"); return e && atoi(e) > 0; }(); return v; }
 inline bool modular_xyb_env() { static const bool v = [] { const char *e = env_str("J40HIP_MODULAR_XYB"); return e && atoi(e) > 0; }(); return v; }
@@ -286,6 +288,14 @@ struct Frame {
 	// the stream's custom table for that K, else from the process-wide defaults (set_upsampling_defaults); neither: "updf". Empty for K = 1.
 	bool allow_upsampling = false;
 	std::vector<float> up_table;
+	// Splines are asked for (J40HIP_PARSE_SPLINES, or J40HIP_SPLINES=1): a frame with has_splines is parsed -- its quantised splines into
+	// `splines`, behind the patch dictionary and ahead of the noise parameters; the segments every decode draws and their tiles into
+	// `spline_plan` once LfGlobal's base correlations are known -- instead of refused with "TODO"; the frame must be a regular or
+	// skip-progressive one (type 0 or 3) of an image with xyb_encoded = 1. A damaged stream is "spln". Set before
+	// parse_frame. (device/spline_dev.h has the rule.)
+	bool allow_splines = false;
+	SplineData splines;
+	SplinePlan spline_plan;
 	bool wide() const { return !im.modular_16bit_buffers; }
 	// A fresh Frame with the fields a caller sets BEFORE parse_frame -- the ones declared above, from defer_lf_tail on -- and nothing
 	// else (the streaming header parse starts over with one when the prefix it had ran out). A field added to that set goes in here.
@@ -294,7 +304,7 @@ struct Frame {
 		g.defer_lf_tail = defer_lf_tail; g.lf_decoder = lf_decoder; g.lf_decoder_ctx = lf_decoder_ctx;
 		g.need_bytes = need_bytes; g.need_ctx = need_ctx; g.have_bytes = have_bytes;
 		g.lf_only = lf_only; g.seq_im = seq_im; g.seq_blend = seq_blend; g.allow_ycbcr = allow_ycbcr; g.allow_wide = allow_wide; g.allow_lf_frame = allow_lf_frame; g.allow_modular_lf = allow_modular_lf;
-		g.allow_patches = allow_patches; g.allow_modular_ref = allow_modular_ref; g.allow_noise = allow_noise; g.allow_upsampling = allow_upsampling;
+		g.allow_patches = allow_patches; g.allow_modular_ref = allow_modular_ref; g.allow_noise = allow_noise; g.allow_splines = allow_splines; g.allow_upsampling = allow_upsampling;
 		return g;
 	}
 	// Modular frames: LfGlobal's channel data is left to the device; it starts at this bit of the section
@@ -322,6 +332,8 @@ void parse_sequence_frame_header(const uint8_t *cs, size_t cs_size, size_t offse
 // the patch dictionary of a frame with has_patches (`im`: its image's metadata, the size is the frame's own). Raises "shrt", the entropy
 // code's errors and "ptch"; a dictionary that parses but is not served comes back with `unserved` set
 void read_patch_dictionary(BitReader &br, const ImageMeta &im, const FrameHeader &fh, PatchDictionary *out);
+void read_splines(BitReader &br, const FrameHeader &fh, SplineData *out);
+void parse_sequence_splines(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, const FrameHeader &fh, const Toc &toc, bool allow_patches, bool allow_noise);
 // ... of the frame whose header starts at byte `offset` of the codestream and whose TOC (offsets from `offset`) is `toc`, for a sequence's index
 void parse_sequence_patches(const uint8_t *cs, size_t cs_size, size_t offset, const ImageMeta &im, const FrameHeader &fh, const Toc &toc, PatchDictionary *out);
 // the extra channel whose samples become the pixels' A (plan_build.cpp: alpha_channel): the first one of type alpha; -1: none

@@ -112,7 +112,7 @@ static bool cut_patch_dictionary(BitWriter &bw) {
 }
 
 // noise=v0,...,v7: the frame being written has the noise flag (FrameHeader.flags bit 0) and its eight NoiseParameters, u(10) each, in
-// LfGlobal behind the patch dictionary (splines, which would stand between them, are never written). Both LfGlobal writers.
+// LfGlobal behind the patch dictionary and the splines (splines=, below). Both LfGlobal writers.
 //   twin (noisetwin=1): the frame without the flag and without the parameters, every other byte alike
 struct NoiseRole { int v[8] = {0, 0, 0, 0, 0, 0, 0, 0}; bool twin = false; };
 static NoiseRole *g_noise = nullptr;
@@ -128,6 +128,94 @@ static void parse_noise_role(const std::string &s, NoiseRole *r) {
 	if (sscanf(s.c_str(), "%d,%d,%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7) != 8) die("noise=v0,...,v7 (eight integers 0..1023)");
 	for (int i = 0; i < 8; ++i) if (v[i] < 0 || v[i] > 1023) die("noise=: a value outside 0..1023");
 }
+
+// splines=: the splines of the frame being written: the frame has the splines flag (FrameHeader.flags bit 4) and the spline data in
+// LfGlobal between the patch dictionary and the noise parameters. Both LfGlobal writers. A description is a list of splines separated
+// by '/'; a spline is  x,y[:dx,dy...][|c:i=v,...]  -- its starting point, the double deltas of its further control points as the stream
+// holds them (delta += d, point += delta), and a sparse list of quantised coefficients, c = 0 X, 1 Y, 2 B, 3 sigma, i = 0..31. qadj=: the
+// quantisation adjustment. Nothing is checked: what a decoder has to refuse is written as it stands. splinecount=N: the stream says N
+// splines whatever follows; splinen=N: the first spline says N further control points whatever follows.
+//   twin (splinetwin=1): the frame without the flag and without the data, every other byte alike
+//   cut (splinecut=1): LfGlobal ends in the middle of the spline data (frames with several sections)
+// One entropy-coded stream over 6 contexts (three clusters, ANS): count - 1 (context 2); per spline x, y (1; from the second spline on the
+// sign-folded differences to the one before); the adjustment, sign-folded (0); per spline its number of control points (3), their double
+// deltas, sign-folded (4), and 4 x 32 coefficients, sign-folded (5)
+struct SplineW { long long x = 0, y = 0; std::vector<long long> dd; int coef[4][32]; SplineW() { memset(coef, 0, sizeof coef); } };
+struct SplineRole { std::vector<SplineW> splines; int qadj = 0; long long count = -1, first_n = -1; bool twin = false, cut = false; };
+static SplineRole *g_spline = nullptr;
+static bool spline_flag() { return g_spline && !g_spline->twin; }
+static void write_splines(BitWriter &bw) {
+	if (!spline_flag()) return;
+	CodeSpecW spec;
+	std::vector<uint8_t> map(6);
+	for (int i = 0; i < 6; ++i) map[(size_t) i] = (uint8_t) (i % 3);
+	spec.init(6, map, 3);
+	spec.log_alpha = 8;
+	for (auto &c : spec.cfg) c = HybridCfg{4, 2, 0};
+	StreamEncoder enc(spec);
+	auto fold = [](long long v) { return (uint32_t) (v >= 0 ? 2 * v : -2 * v - 1); };
+	const std::vector<SplineW> &sp = g_spline->splines;
+	enc.add(2, (uint32_t) ((g_spline->count >= 0 ? g_spline->count : (long long) sp.size()) - 1));
+	for (size_t i = 0; i < sp.size(); ++i) {
+		if (i == 0) { enc.add(1, (uint32_t) sp[i].x); enc.add(1, (uint32_t) sp[i].y); }
+		else { enc.add(1, fold(sp[i].x - sp[i - 1].x)); enc.add(1, fold(sp[i].y - sp[i - 1].y)); }
+	}
+	enc.add(0, fold(g_spline->qadj));
+	for (size_t i = 0; i < sp.size(); ++i) {
+		enc.add(3, (uint32_t) (i == 0 && g_spline->first_n >= 0 ? g_spline->first_n : (long long) sp[i].dd.size() / 2));
+		for (long long d : sp[i].dd) enc.add(4, fold(d));
+		for (int c = 0; c < 4; ++c) for (int k = 0; k < 32; ++k) enc.add(5, fold(sp[i].coef[c][k]));
+	}
+	count_stream(spec, enc);
+	write_code_spec(bw, spec);
+	enc.flush(bw);
+}
+// splinecut=1: true when LfGlobal is to end here, in the middle of the spline data that has just been written behind `before` bytes of `bw`
+static bool cut_splines(BitWriter &bw, size_t before) {
+	if (!spline_flag() || !g_spline->cut) return false;
+	bw.pad();
+	bw.bytes.resize(before + (bw.bytes.size() - before) / 2);
+	return true;
+}
+static void parse_spline_role(const std::string &text, SplineRole *r) {
+	size_t at = 0;
+	while (at <= text.size()) {
+		size_t end = text.find('/', at);
+		if (end == std::string::npos) end = text.size();
+		const std::string one = text.substr(at, end - at);
+		at = end + 1;
+		if (one.empty()) continue;
+		SplineW w;
+		const size_t bar = one.find('|');
+		const std::string pts = one.substr(0, bar), coefs = bar == std::string::npos ? std::string() : one.substr(bar + 1);
+		size_t p = 0; bool first = true;
+		while (p <= pts.size()) {
+			size_t q = pts.find(':', p);
+			if (q == std::string::npos) q = pts.size();
+			long long a = 0, b = 0;
+			if (sscanf(pts.substr(p, q - p).c_str(), "%lld,%lld", &a, &b) != 2) die("splines=: a point is x,y");
+			if (first) { w.x = a; w.y = b; first = false; } else { w.dd.push_back(a); w.dd.push_back(b); }
+			p = q + 1;
+		}
+		p = 0;
+		while (p < coefs.size()) {
+			size_t q = coefs.find(',', p);
+			if (q == std::string::npos) q = coefs.size();
+			int c = 0, i = 0, v = 0;
+			if (sscanf(coefs.substr(p, q - p).c_str(), "%d:%d=%d", &c, &i, &v) != 3 || c < 0 || c > 3 || i < 0 || i > 31) die("splines=: a coefficient is c:i=v, c = 0..3, i = 0..31");
+			w.coef[c][i] = v;
+			p = q + 1;
+		}
+		r->splines.push_back(w);
+	}
+	if (r->splines.empty()) die("splines=: no spline");
+}
+static void spline_role_options(const Options &opt, SplineRole *r) {
+	r->qadj = opt.geti("qadj", 0); r->twin = opt.geti("splinetwin", 0) != 0; r->cut = opt.geti("splinecut", 0) != 0;
+	r->count = opt.kv.count("splinecount") ? atoll(opt.gets("splinecount", "").c_str()) : -1;
+	r->first_n = opt.kv.count("splinen") ? atoll(opt.gets("splinen", "").c_str()) : -1;
+}
+static const char *const SPLINE_KEYS[] = {"splines", "qadj", "splinetwin", "splinecut", "splinecount", "splinen"};
 
 // LF frames (lflevels=1|2; run_lf_sequence): what the VarDCT writer is told about the frame it writes, and what it hands back for the
 // next one. The planes of integers are frame-wide, ceil(W / 8) cells a row, in streamed order Y, X, B.
@@ -644,7 +732,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	const int jpeg_upsampling = subsampling == "420" ? 4 : subsampling == "422" ? 8 : subsampling == "440" ? 12 : 0;
 	const int dct8only = jpeg ? 1 : opt.geti("dct8only", subsampled ? 1 : 0), fixed_hfmul = jpeg ? 1 : opt.geti("hfmul", 0), nocfl = jpeg ? 1 : opt.geti("nocfl", 0), flatchroma = opt.geti("flatchroma", 0);
 	if (fixed_hfmul < 0 || fixed_hfmul > 256) die("vardct: hfmul=1..256");
-	const int nonzero_header = opt.geti("fullheader", (num_passes > 1 || ycbcr || g_noise || g_up.k > 1) ? 1 : 0);   // (upsampling=: the twin's header too)
+	const int nonzero_header = opt.geti("fullheader", (num_passes > 1 || ycbcr || g_noise || g_spline || g_up.k > 1) ? 1 : 0);   // (upsampling=: the twin's header too)
 	const int x_qm = opt.geti("xqm", 3), b_qm = opt.geti("bqm", 2);
 	const int skip_smooth = jpeg ? 1 : opt.geti("nosmooth", subsampled ? 1 : 0);
 	const int small_clusters = opt.geti("simpleclusters", 0); // <= 8 clusters: simple cluster-map form
@@ -1412,8 +1500,11 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 	auto write_lf_global = [&](BitWriter &section) {   // LfGlobal (j40.h:6257)
 		write_patch_dictionary(section, num_ec);                 // (patches=: the dictionary comes first)
 		BitWriter dropped;                                       // (patchcut=1: the rest is written all the same, the code specs' tables are made here)
-		BitWriter &bw = cut_patch_dictionary(section) ? dropped : section;
-		write_noise_parameters(bw);                              // (noise=: behind the dictionary)
+		BitWriter &bw0 = cut_patch_dictionary(section) ? dropped : section;
+		const size_t before_splines = bw0.bytes.size();
+		write_splines(bw0);                                      // (splines=: behind the dictionary)
+		BitWriter &bw = &bw0 == &section && cut_splines(section, before_splines) ? dropped : bw0;   // (splinecut=1: as patchcut=1)
+		write_noise_parameters(bw);                              // (noise=: behind the splines)
 		bw.put(1, 1);                                            // LF channel dequantisation: default
 		bw.u32(global_scale, 1, 11, 2049, 11, 4097, 12, 8193, 16);
 		bw.u32(quant_lf, 16, 0, 1, 5, 1, 8, 1, 16);
@@ -1594,7 +1685,7 @@ static int run_vardct(int W, int H, uint64_t seed, const char *out, const Option
 		const int seq_type = g_seq ? g_seq->type : 0;
 		cs.put(lf_frame ? 1 : (uint64_t) seq_type, 2);   // regular frame (an LF frame: type 1; types=: a reference-only frame, type 2)
 		cs.put(0, 1);                       // VarDCT
-		cs.u64((skip_smooth ? 128 : 0) | (use_lf_frame ? 32 : 0) | (patch_flag() ? 2 : 0) | (noise_flag() ? 1 : 0));      // flags
+		cs.u64((skip_smooth ? 128 : 0) | (use_lf_frame ? 32 : 0) | (patch_flag() ? 2 : 0) | (noise_flag() ? 1 : 0) | (spline_flag() ? 16 : 0));      // flags
 		if (noxyb) cs.put(ycbcr ? 1 : 0, 1);   // do_ycbcr (read only without xyb_encoded)
 		// (jpegup=N: the header says N whatever the stream holds -- a layout the decoder has to refuse before it reads anything of it)
 		if (ycbcr) cs.put((uint64_t) opt.geti("jpegup", jpeg_upsampling), 6);   // jpeg_upsampling (read with do_ycbcr)
@@ -2283,7 +2374,8 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	{
 		BitWriter bw;
 		write_patch_dictionary(bw, extra + (alpha ? 1 : 0));   // (patches=: the dictionary comes first)
-		write_noise_parameters(bw);                            // (noise=: behind it)
+		write_splines(bw);                                     // (splines=: behind it)
+		write_noise_parameters(bw);                            // (noise=: behind them)
 		if (!custom_m_lf) bw.put(1, 1);   // LF channel dequantisation: default
 		else { bw.put(0, 1); for (int c = 0; c < 3; ++c) bw.f16((float) (m_lf[c] * 128.0)); }   // (read back divided by 128, j40.h:6268)
 		bw.put(1, 1);                 // global tree present
@@ -2398,7 +2490,7 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 	const int seq_type = g_seq ? g_seq->type : 0;
 	cs.put(g_mod_lf ? 1 : (uint64_t) seq_type, 2);   // regular frame (an LF frame: type 1; types=: a reference-only frame, type 2)
 	cs.put(1, 1);                       // modular
-	cs.u64((patch_flag() ? 2 : 0) | (noise_flag() ? 1 : 0));       // flags
+	cs.u64((patch_flag() ? 2 : 0) | (noise_flag() ? 1 : 0) | (spline_flag() ? 16 : 0));       // flags
 	if (!flag_xyb) cs.put(flag_ycbcr ? 1 : 0, 1);   // do_ycbcr
 	if (!flag_xyb && flag_ycbcr) cs.put(0, 6);      // jpeg_upsampling: none
 	cs.put((uint64_t) up_log(), 2);     // log_upsampling (upsampling=)
@@ -2493,6 +2585,9 @@ int run_modular(int W, int H, uint64_t seed, const char *out, const Options &opt
 //                      out, every other byte alike. stats=1 lists the placements written
 //   noise=             per frame (entries separated by ';') the eight NoiseParameters v0,...,v7 (0..1023): sets the frame's noise flag; an
 //                      empty entry: a frame without noise. noisetwin=1: the flag and the parameters left out, every other byte alike
+//   splines=           per frame (entries separated by ';') the frame's splines (SplineRole above: x,y[:dx,dy...][|c:i=v,...], '/' between
+//                      splines): sets the frame's splines flag; an empty entry: a frame without splines. qadj=, splinecount=, splinen=,
+//                      splinecut=1 and splinetwin=1 apply to every frame that has an entry
 // The last frame is is_last. stats=1 prints frames, shown, saved_slots and every frame's offsets instead of the mode's own statistics.
 static std::vector<std::string> split_list(const std::string &v, char sep) {
 	std::vector<std::string> out;
@@ -2510,7 +2605,8 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 		srcs = split_list(opt_in.gets("srcs", ""), ','), saves = split_list(opt_in.gets("saves", ""), ','), blends = split_list(opt_in.gets("blends", ""), ','),
 		ecblends = split_list(opt_in.gets("ecblends", ""), ','), ecsrcs = split_list(opt_in.gets("ecsrcs", ""), ','),
 		types = split_list(opt_in.gets("types", ""), ','), patches = split_list(opt_in.gets("patches", ""), ';'),
-		noises = split_list(photon_noise_given(opt_in) ? opt_in.gets("noise", "") : std::string(), ';');
+		noises = split_list(photon_noise_given(opt_in) ? opt_in.gets("noise", "") : std::string(), ';'),
+		splines = split_list(opt_in.gets("splines", ""), ';');
 	if (!durs.empty() && !anim) die("durations= wants anim=1 (frames of a still have no duration)");
 	// modes=v,m,...: per-frame writers, v the VarDCT one and m the Modular one (an empty entry: the command's mode). Every frame gets every
 	// option; the first frame writes the image header, so the options must describe one image to both writers (a Modular frame under a
@@ -2521,6 +2617,7 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 	if (!modes.empty() && any_vardct && !opt_in.geti("xyb", 0)) die("modes=: a Modular frame beside VarDCT frames is a frame of an XYB image: xyb=1");
 	Options opt = opt_in;
 	for (const char *k : {"frames", "anim", "durations", "crops", "srcs", "saves", "blends", "ecblends", "ecsrcs", "only", "container", "stats", "modes", "types", "patches", "patchtwin", "patchec", "patchcut", "sbct", "noisetwin"}) opt.kv.erase(k);
+	for (const char *k : SPLINE_KEYS) opt.kv.erase(k);
 	if (photon_noise_given(opt_in)) opt.kv.erase("noise");
 	if (any_vardct && !opt.kv.count("fullheader")) opt.kv["fullheader"] = "1";
 	auto at = [](const std::vector<std::string> &v, int k, int def) { return k < (int) v.size() && !v[(size_t) k].empty() ? atoi(v[(size_t) k].c_str()) : def; };
@@ -2551,6 +2648,10 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 		noise.twin = opt_in.geti("noisetwin", 0) != 0;
 		const bool noisy = k < (int) noises.size() && !noises[(size_t) k].empty();
 		if (noisy) parse_noise_role(noises[(size_t) k], &noise);
+		SplineRole spl;   // (splines=: per frame, entries separated by ';', an empty entry: a frame without splines)
+		spline_role_options(opt_in, &spl);
+		const bool splined = k < (int) splines.size() && !splines[(size_t) k].empty();
+		if (splined) parse_spline_role(splines[(size_t) k], &spl);
 		SeqFrame q;
 		q.canvas_w = W; q.canvas_h = H; q.anim = anim; q.cs = &cs;
 		int fw = W, fh = H;
@@ -2571,10 +2672,10 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 		if (q.type != 2 && !q.is_last && (q.duration == 0 || q.save != 0)) saved_slots |= 1u << q.save;
 		if (only >= 0 && k != only) continue;
 		q.first = cs.empty();
-		g_seq = &q; g_patch = role.refs.empty() ? nullptr : &role; g_noise = noisy ? &noise : nullptr;
+		g_seq = &q; g_patch = role.refs.empty() ? nullptr : &role; g_noise = noisy ? &noise : nullptr; g_spline = splined ? &spl : nullptr;
 		const bool frame_vardct = k < (int) modes.size() && !modes[(size_t) k].empty() ? modes[(size_t) k] == "v" : vardct;
 		const int e = frame_vardct ? run_vardct(fw, fh, seed + (uint64_t) k, out, opt) : run_modular(fw, fh, seed + (uint64_t) k, out, opt);
-		g_seq = nullptr; g_patch = nullptr; g_noise = nullptr;
+		g_seq = nullptr; g_patch = nullptr; g_noise = nullptr; g_spline = nullptr;
 		if (e) return e;
 		// (the first frame's bytes start with the signature and the image header: its frame header is found by a reader, not here)
 		char tmp[160]; snprintf(tmp, sizeof tmp, "%s{\"frame\": %d, \"first_section\": %zu, \"end\": %zu}", rows.empty() ? "" : ", ", k, q.first_section, cs.size());
@@ -2632,6 +2733,7 @@ static int run_sequence(bool vardct, int W, int H, uint64_t seed, const char *ou
 //                    flat VarDCT LF frame's samples float for float where that frame's LF step is m itself: global_scale * quant_lf = 65536;
 //                    and nocfl=1, so that no B sample carries a Y term. Refused elsewhere. (lftwin=1: the twin is the same stream either way.)
 // noise=v0,...,v7: the main frame's noise parameters (noisetwin=1: left out again); noiself=1: the LF frames carry them too.
+// splines=: the main frame's splines (splinetwin=1: left out again); splinelf=1: the LF frames carry them too.
 // stats=1 prints the number of coded frames and how many values the main frame's LF index takes.
 static int run_lf_sequence(int W, int H, uint64_t seed, const char *out, const Options &opt_in) {
 	const int levels = opt_in.geti("lflevels", 1), twin = opt_in.geti("lftwin", 0), only = opt_in.geti("only", -1);
@@ -2652,7 +2754,13 @@ static int run_lf_sequence(int W, int H, uint64_t seed, const char *out, const O
 		if (opt_in.geti("alpha", 0)) die("lfmodular=1: no extra channels (an LF frame of such an image is refused)");
 	}
 	Options main_opt = opt_in;
-	for (const char *k : {"lflevels", "lfkind", "lftwin", "only", "stats", "lfgab", "lfepf", "lfcrop", "lfhfmul", "lfmodular", "noisetwin", "noiself"}) main_opt.kv.erase(k);
+	for (const char *k : {"lflevels", "lfkind", "lftwin", "only", "stats", "lfgab", "lfepf", "lfcrop", "lfhfmul", "lfmodular", "noisetwin", "noiself", "splinelf"}) main_opt.kv.erase(k);
+	for (const char *k : SPLINE_KEYS) main_opt.kv.erase(k);
+	// splines= (one entry): the main frame's; splinelf=1: the LF frames get the flag and the data too (a stream a decoder has to refuse)
+	SplineRole spl;
+	spline_role_options(opt_in, &spl);
+	const bool splined = opt_in.kv.count("splines") != 0, spline_lf = opt_in.geti("splinelf", 0) != 0;
+	if (splined) parse_spline_role(opt_in.gets("splines", ""), &spl);
 	if (photon_noise_given(opt_in)) main_opt.kv.erase("noise");
 	// noise= (one entry): the main frame's; noiself=1: the LF frames get the flag and the parameters too (a stream a decoder has to refuse)
 	NoiseRole noise;
@@ -2687,9 +2795,9 @@ static int run_lf_sequence(int W, int H, uint64_t seed, const char *out, const O
 		SeqFrame q;
 		q.canvas_w = W; q.canvas_h = H; q.cs = into; q.first = into && into->empty(); q.is_last = l == 0;
 		q.have_crop = l == 0 && crop_w > 0;
-		g_seq = into ? &q : nullptr; g_lf = &role; g_noise = noisy && (l == 0 || noise_lf) ? &noise : nullptr;
+		g_seq = into ? &q : nullptr; g_lf = &role; g_noise = noisy && (l == 0 || noise_lf) ? &noise : nullptr; g_spline = splined && (l == 0 || spline_lf) ? &spl : nullptr;
 		const int e = run_vardct(q.have_crop ? crop_w : fw[l], q.have_crop ? crop_h : fh[l], seed + (uint64_t) l, out, o);
-		g_seq = nullptr; g_lf = nullptr; g_noise = nullptr;
+		g_seq = nullptr; g_lf = nullptr; g_noise = nullptr; g_spline = nullptr;
 		if (e) die("lflevels: a frame could not be written");
 	};
 	LfRole roles[3];
@@ -2847,6 +2955,10 @@ int main(int argc, char **argv) {
 		noise.twin = opt.geti("noisetwin", 0) != 0;
 		if (photon_noise_given(opt)) { parse_noise_role(opt.gets("noise", ""), &noise); g_noise = &noise; opt.kv.erase("noise"); }
 		opt.kv.erase("noisetwin");
+		SplineRole spl;   // (splines= on a single frame: the one entry)
+		spline_role_options(opt, &spl);
+		if (opt.kv.count("splines")) { parse_spline_role(opt.gets("splines", ""), &spl); g_spline = &spl; }
+		for (const char *k : SPLINE_KEYS) opt.kv.erase(k);
 		return vardct ? run_vardct(W, H, seed, argv[5], opt) : run_modular(W, H, seed, argv[5], opt);
 	}
 	return run_sequence(vardct, W, H, seed, argv[5], opt);
